@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's configs on MI355X.
 
-  python bench.py [--config 2|3|4|5] [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+  python bench.py [--config 2|3|4|5] [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default: config 2, the headline -- a "step" is one pass of the hot path (`sw_striped_16`, score + end
@@ -13,6 +13,8 @@ Weak scaling (default): every rank holds its own batch of that size.  `--scaling
 split across the ranks by the shard planner (uniform for equal lengths, cumulative cells for mixed lengths).
 No data-path collective; for N > 1 the records of each step are gathered to rank 0 over RCCL, overlapped
 with the next step's kernel.  Rank 0 prints ONE JSON line.
+`--dump-outputs DIR`: rank 0 writes what the last timed step of the measured config returned to its caller as DIR/<name>.npy
+(float64), so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import ctypes as C
@@ -191,6 +193,11 @@ class Workload:
     def records(self, k):
         return self.d_out[k % 2]
 
+    def outputs(self, k):
+        """What step k handed its caller: ({name: per-pair array of length n}, {name: any other array})."""
+        rec = self.records(k).cpu().numpy()
+        return {f: rec[:, i] for i, f in enumerate(self.pkg.RECORD_DTYPE.names)}, {}
+
 
 class Cfg2(Workload):
     config = 2
@@ -340,6 +347,12 @@ class Cfg3(Workload):
                                             self.max_rlen, self.d_out[k % 2].data_ptr(), self.d_st[k % 2].data_ptr(),
                                             stream.cuda_stream)
 
+    def outputs(self, k):
+        per_pair, other = Workload.outputs(self, k)
+        st = self.d_st[k % 2].cpu().numpy()
+        per_pair.update({f: st[:, i] for i, f in enumerate(self.pkg.STATS_DTYPE.names)})
+        return per_pair, other
+
     def pcie_inclusive(self):
         """the same batch through pmx_align_profile_batch: references from host memory, records + statistics back to host memory"""
         return _profile_host_entry(self, stats=True)
@@ -413,6 +426,20 @@ class Cfg4(Workload):
         self.pkg.align_batch_cigar_device(self.cfg, self.n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
                                           wl.CFG4["len"], wl.CFG4["len"], self.d_out[k % 2].data_ptr(),
                                           self.d_text[k % 2].data_ptr(), self.cap, self.d_toff[k % 2].data_ptr(), stream.cuda_stream)
+
+    def outputs(self, k):
+        """records and the length of every pair's CIGAR text; the text itself for a fixed seeded sample of pairs (the whole text is
+        ~100 MB): cigar_sample_pair (pair indices), cigar_sample_offsets, cigar_sample_text (byte values)"""
+        per_pair, other = Workload.outputs(self, k)
+        toff = self.d_toff[k % 2].cpu().numpy()
+        per_pair["cigar_length"] = toff[1:] - toff[:-1]
+        text = self.d_text[k % 2][: int(toff[-1])].cpu().numpy()
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(self.n, size=min(self.n, 4096), replace=False))
+        parts = [text[toff[i]:toff[i + 1]] for i in pick]
+        soff = np.zeros(len(pick) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in parts], out=soff[1:])
+        other.update(cigar_sample_pair=pick, cigar_sample_offsets=soff, cigar_sample_text=np.concatenate(parts))
+        return per_pair, other
 
     def exchange(self, k, sharding, backend, cache=None):
         """N > 1: this step's CIGAR text follows the records to rank 0 (sizes first, then offsets and text padded to the longest
@@ -601,16 +628,39 @@ class Cfg5(Workload):
 
 WORKLOADS = {2: Cfg2, 3: Cfg3, 4: Cfg4, 5: Cfg5}
 
+DUMP_LIMIT = 64 << 20          # bytes of .npy payload `--dump-outputs` may write
+DUMP_SEED = 20260100
+
+
+def dump_outputs(w, k, out_dir):
+    """Step k's outputs as out_dir/<name>.npy in float64 (exact for every int32 field and every offset below 2**53).  Past
+    DUMP_LIMIT the per-pair arrays are cut to a fixed seeded sample of pairs, whose indices go to sample_index.npy.
+    Returns the names written."""
+    per_pair, other = w.outputs(k)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in other.items()}
+    budget = DUMP_LIMIT - sum(a.nbytes for a in arrays.values())
+    row = 8 * len(per_pair)
+    if w.n * row > budget:
+        m = max(0, budget // (row + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(w.n, size=m, replace=False))
+        per_pair = {name: a[idx] for name, a in per_pair.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    arrays.update({name: np.asarray(a, dtype=np.float64) for name, a in per_pair.items()})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
 
 class _Env:
     """What every config's run shares: the package, the device, the process group."""
     pass
 
 
-def run_config(env, config, steps, warmup, scaling, pairs, cpu_legs=True, deferred=None):
+def run_config(env, config, steps, warmup, scaling, pairs, cpu_legs=True, deferred=None, dump_dir=None):
     """One BASELINE config: W untimed + K timed steps bracketed by barrier + synchronize, max over ranks.
-    Returns the JSON line as a dict on rank 0, None elsewhere.  deferred (a list): the host-side legs (`pcie_inclusive`,
-    `cpu_baseline`) are appended to it as closures instead of being run here -- the default run measures every config on the GPU
+    Returns the JSON line as a dict on rank 0, None elsewhere.  dump_dir: rank 0 writes the last timed step's outputs there
+    (dump_outputs).  deferred (a list): the host-side legs (`pcie_inclusive`, `cpu_baseline`) are appended to it as closures instead of being run here -- the default run measures every config on the GPU
     first and the CPU legs afterwards: a CPU leg of one config (16 OpenMP threads, pinned staging buffers) ahead of the next
     config's GPU steps cost those 4-5 % (their pipelines are many launches and stream waits per step)."""
     torch, pkg, dev, dist = env.torch, env.pkg, env.dev, env.dist
@@ -688,6 +738,7 @@ def run_config(env, config, steps, warmup, scaling, pairs, cpu_legs=True, deferr
     kernel = pkg.lib.pmx_last_kernel().decode()        # name + shape + arithmetic variant of what this thread just launched
     if hasattr(w, "finish"):
         w.finish()
+    dumped = dump_outputs(w, w.last_k, dump_dir) if dump_dir and rank == 0 else None
 
     line = None
     if rank == 0:
@@ -713,6 +764,8 @@ def run_config(env, config, steps, warmup, scaling, pairs, cpu_legs=True, deferr
                          "algorithmic_bytes": int(w.algo_bytes),
                          "note": w.algo_note + "; the path is VALU-bound, see roofline_valu"},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": dump_dir, "step": w.last_k, "arrays": dumped}
         if pmc and "lds_bank_conflict" in pmc:
             line["lds_bank_conflict"] = dict(pmc["lds_bank_conflict"], source=pmc["source"])
         if pmc and pmc.get("stale"):
@@ -783,6 +836,8 @@ def main():
     ap.add_argument("--pairs", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu-baseline", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--headline-only", action="store_true", help="default run without configs 3-5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs of the measured config (config 2 by default) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -827,7 +882,8 @@ def main():
     alongside = (args.config is None and not args.headline_only and world == 1 and not multi and args.pairs is None
                  and args.scaling == "weak")
     deferred = [] if alongside else None      # (one config alone: its host legs follow its GPU steps at once)
-    line = run_config(env, head, args.steps, args.warmup, args.scaling, args.pairs, cpu_legs=not args.no_cpu_baseline, deferred=deferred)
+    line = run_config(env, head, args.steps, args.warmup, args.scaling, args.pairs, cpu_legs=not args.no_cpu_baseline, deferred=deferred,
+                      dump_dir=args.dump_outputs)
     if alongside:
         # the other BASELINE configs under the same clock (each: value, ms_per_step, roofline, roofline_valu, cpu_baseline, pcie_inclusive);
         # every config's GPU steps first, the host-side legs of all of them afterwards

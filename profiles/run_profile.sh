@@ -1,15 +1,16 @@
 #!/bin/bash
 # Collects the rocprofv3 evidence for one command on the GPU box (run through gpurun):
 #   profiles/run_profile.sh <tag> <label> <kernel substring> <launch divisor> -- <program and arguments>
-# e.g. profiles/run_profile.sh r03 cfg4 pmx_nwsg16v_kernel 6 -- python3 /root/repo/bench.py --config 4 --steps 5 --warmup 1 --no-cpu-baseline
+# e.g. profiles/run_profile.sh r03 cfg4 pmx_nwsg16v_kernel 6 -- python3 $PWD/bench.py --config 4 --steps 5 --warmup 1 --no-cpu-baseline
 # kernel-trace + stats in one run; every PMC group in its own run (never combined with a trace); the program itself follows
 # `--` (no launcher in between); the time limit wraps rocprofv3 from outside.  Environment switches (e.g. the serialised
 # pipelines PMX_CIGAR_NO_OVERLAP / PMX_STATS_NO_OVERLAP) are exported by the caller and inherited.
-# Output: gpurun_out/prof_<tag>_<label>/{<label>_kernel_stats.csv, <label>_pmc_summary.json, ...}
+# Output: profiles/_out/prof_<tag>_<label>/{<label>_kernel_stats.csv, <label>_pmc_summary.json, ...}
 set -u
 TAG=$1; LABEL=$2; NEEDLE=$3; DIV=$4; shift 4
 [ "$1" = "--" ] && shift
-OUT=/root/repo/gpurun_out/prof_${TAG}_${LABEL}
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$R/profiles/_out/prof_${TAG}_${LABEL}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- "$@" > $OUT/trace.log 2>&1
@@ -24,5 +25,5 @@ timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fet
 echo "pmc_fetch rc=$?"
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- "$@" > $OUT/pmc_write.log 2>&1
 echo "pmc_write rc=$?"
-python3 /root/repo/profiles/summarize_pmc.py $OUT "$NEEDLE" $OUT/${LABEL}_pmc_summary.json $DIV
+python3 $R/profiles/summarize_pmc.py $OUT "$NEEDLE" $OUT/${LABEL}_pmc_summary.json $DIV
 ls $OUT

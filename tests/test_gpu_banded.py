@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import workloads as wl
-from util import random_seqs, mutate, DNA, AA
+from util import random_seqs, mutate, DNA, AA, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -73,7 +73,7 @@ def test_banded_batch_every_mode_with_band_centres(pkg, orc, mode, k, form, monk
 def test_banded_batch_sg_variants_and_protein(pkg, orc):
     rng = np.random.default_rng(8300)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     qs = random_seqs(rng, 200, 5, 150, AA)
     rs = [mutate(rng, q, 0.3, 0.05, AA) + random_seqs(rng, 1, 0, 30, AA)[0] for q in qs]
     qb, qo = orc.pack(qs); rb, ro = orc.pack(rs)
@@ -158,7 +158,7 @@ def test_ssw_begin_positions_and_packed_cigar(pkg, orc):
         core = mutate(rng, q[rng.integers(0, len(q) // 2):], 0.12, 0.06)
         r = random_seqs(rng, 1, 0, 40)[0] + core + random_seqs(rng, 1, 0, 40)[0] if t % 4 else random_seqs(rng, 1, 5, 200)[0]
         cases.append((q, r, pm, om, 5, 2))
-    pb, ob = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pb, ob = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     for t in range(120):
         q = random_seqs(rng, 1, 10, 150, AA)[0]
         r = random_seqs(rng, 1, 0, 30, AA)[0] + mutate(rng, q, 0.3, 0.05, AA) + random_seqs(rng, 1, 0, 30, AA)[0]
@@ -197,7 +197,7 @@ def test_fuzz_banded_batches(pkg, orc, seed):
     rng = np.random.default_rng(seed)
     mats = [(pkg.Matrix.create(b"ACGT", 2, -3), orc.Matrix.create("ACGT", 2, -3), DNA),
             (pkg.Matrix.create(b"ACGT", 5, -4), orc.Matrix.create("ACGT", 5, -4), DNA),
-            (pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt"), AA)]
+            (pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt")), AA)]
     for it in range(10):
         pm, om, alpha = mats[int(rng.integers(0, len(mats)))]
         mode = int(rng.integers(0, 3))

@@ -402,7 +402,7 @@ def test_profile_host_entry_uploads_behind_the_kernels(pkg, orc):
     n = 15000
     q, rbuf, roff = wl.make_cfg3(n, rank=3)
     assert int(roff[-1]) > (64 << 20)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(os.path.join(ROOT, "tests", "golden", "blosum62.txt"))
     al = pkg.Aligner.new().profile(pkg.Profile.new(q, True, pm)).matrix(pm).gap_open(11).gap_extend(1).solution_width(16).build()
     rec, st = al.align_batch_packed(None, None, rbuf, roff)
     assert "packed trace" in pkg.lib.pmx_last_kernel().decode()
@@ -425,16 +425,18 @@ def test_profile_host_entry_uploads_behind_the_kernels(pkg, orc):
     assert (got["score"][idx] == want0[:, 0]).all() and (got["end_ref"][idx] == want0[:, 2]).all()
 
 
-def test_bench_default_line_carries_every_config():
+def test_bench_default_line_carries_every_config(tmp_path):
     """The driver's command (`python bench.py --gpus 1 --steps K --warmup W`) in a fresh child process: ONE JSON line with the
     contract's keys, config 2 as `value`, `roofline` (algorithmic bytes over the kernel's time, measured traffic from the committed
     PMC summary or null), `roofline_valu`, `cpu_baseline` whose sampled results equal the GPU's -- and BASELINE configs 3, 4 and 5
-    under `configs`, each with the same objects.  The host-side legs run after every GPU measurement."""
+    under `configs`, each with the same objects.  The host-side legs run after every GPU measurement.  `--dump-outputs`: the last timed
+    step's records of config 2, one float64 array per field, within 64 MB."""
     import json
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PMX_BENCH_FORCE_DIST"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+    dump = str(tmp_path / "outputs")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", dump],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -462,3 +464,9 @@ def test_bench_default_line_carries_every_config():
         assert rec["value"] > 500 and rec["ms_per_step"] > 0 and ("cfg%s" % k) in rec["config"]["workload"], k
         check(rec, "cfg" + k)
     assert line["configs"]["5"]["banded_sw"]["ms"] > 0
+    d = line["dumped_outputs"]
+    assert d["dir"] == dump and d["step"] == 2 and d["arrays"] == ["end_query", "end_ref", "flags", "score"]
+    out = {name: np.load(os.path.join(dump, name + ".npy")) for name in d["arrays"]}
+    assert all(a.dtype == np.float64 and a.shape == (line["config"]["pairs_per_gpu"],) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert (out["flags"] == 0).all() and (out["score"] >= 0).all() and (out["end_query"] < wl.CFG2["len"]).all()

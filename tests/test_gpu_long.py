@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from util import random_seqs, mutate, DNA, AA
+from util import random_seqs, mutate, DNA, AA, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -85,7 +85,7 @@ def test_end_positions_under_ties(pkg, orc, mode, form):
 
 def test_protein_and_profile_arm(pkg, orc):
     rng = np.random.default_rng(9960)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     q = random_seqs(rng, 1, 1500, 1500, AA)[0]
     rs = [mutate(rng, q, 0.3, 0.05, AA), random_seqs(rng, 1, 2500, 2500, AA)[0], (random_seqs(rng, 1, 900, 900, AA)[0] + mutate(rng, q[300:900], 0.2, 0.04, AA))]
     rb, ro = orc.pack(rs)

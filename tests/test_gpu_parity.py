@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from util import random_seqs, mutate, score_from_cigar, cigar_ops, DNA, AA
+from util import random_seqs, mutate, score_from_cigar, cigar_ops, DNA, AA, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -126,7 +126,7 @@ def test_cfg1_protein_pair_fixture(pkg):
     """BASELINE config 1: one protein pair, BLOSUM62, gaps 11/1, through Aligner::align() semantics (one-off, profile
     arm, stats, traceback) and through the batch entries; expected values from tests/golden/cfg1_protein_pair.json"""
     import json
-    fx = json.load(open("tests/golden/cfg1_protein_pair.json"))
+    fx = json.load(open(golden("cfg1_protein_pair.json")))
     q, r = fx["query"].encode(), fx["ref"].encode()
     pm = pkg.Matrix.from_name("blosum62")
     for name, sel in (("sw", "local"), ("nw", "global_"), ("sg", "semi_global")):
@@ -249,7 +249,7 @@ def test_sw16_blosum62_all_instantiations(pkg, orc, maxlen):
     """one batch per (G,R) instantiation of the fast kernel"""
     rng = np.random.default_rng(1300 + maxlen)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     n = 120 if maxlen <= 512 else 40
     qs = random_seqs(rng, n, max(1, maxlen // 3), maxlen, AA)
     qs[0] = random_seqs(rng, 1, maxlen, maxlen, AA)[0]
@@ -291,7 +291,7 @@ def test_sw16_every_arithmetic_variant(pkg, orc, monkeypatch, env):
     qs = random_seqs(rng, 60, 100, 700)
     rs = [mutate(rng, q, 0.05, 0.05) for q in qs]                    # long, high-scoring
     _fast_case(pkg, orc, qs, rs, 5, 2, pm, om)
-    bm, bo = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    bm, bo = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     qs = random_seqs(rng, 100, 30, 256, AA)
     rs = [mutate(rng, q, 0.3, 0.05, AA) for q in qs]
     _fast_case(pkg, orc, qs, rs, 11, 1, bm, bo)
@@ -376,7 +376,7 @@ def test_sw16q_shared_query_protein_database_search(pkg, orc, qlen):
     """the profile arm of local alignment (one protein query, BLOSUM62 11/1, many references): the workgroup-shared
     profile kernel in each of its shapes, ragged reference lengths (length-sorted order), planted homologs"""
     rng = np.random.default_rng(1600 + qlen)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     q = random_seqs(rng, 1, qlen, qlen, AA)[0]
     n = 400 if qlen <= 500 else 120
     rs = random_seqs(rng, n, 30, 900, AA)
@@ -403,7 +403,7 @@ def test_sw16_long_references_fetch_variant(pkg, orc, alpha):
     if alpha == "dna":
         pm, om, al, go, ge = pkg.Matrix.create(b"ACGT", 2, -3), orc.Matrix.create("ACGT", 2, -3), DNA, 5, 2
     else:
-        pm, om, al, go, ge = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt"), AA, 11, 1
+        pm, om, al, go, ge = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt")), AA, 11, 1
     for qlo, qhi, n in ((30, 160, 60), (200, 320, 40), (600, 1000, 20)):      # (more than 16 pairs: fewer would take pmx_long32_kernel)
         qs = random_seqs(rng, n, qlo, qhi, al)
         rs = [random_seqs(rng, 1, 1000, 4000, al)[0] + mutate(rng, q, 0.15, 0.04, al) + random_seqs(rng, 1, 100, 2500, al)[0] for q in qs]
@@ -416,7 +416,7 @@ def test_sw16_long_references_fetch_variant(pkg, orc, alpha):
 def test_sw16m_matrix_lookup_per_pair_protein(pkg, orc, qhi, rhi):
     """per-pair protein batches (> 2048 pairs): no LDS profile, scores are read from the transposed matrix in LDS"""
     rng = np.random.default_rng(1800 + qhi)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     n = 2100
     qs = random_seqs(rng, n, max(1, qhi // 3), qhi, AA)
     qs[0] = random_seqs(rng, 1, qhi, qhi, AA)[0]
@@ -521,7 +521,7 @@ def test_nwsg16_sg_variants(pkg, orc):
 def test_nwsg16_blosum62_all_instantiations(pkg, orc, maxlen):
     rng = np.random.default_rng(3200 + maxlen)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     n = 100 if maxlen <= 511 else 30
     qs = random_seqs(rng, n, max(1, maxlen // 3), maxlen, AA)
     qs[0] = random_seqs(rng, 1, maxlen, maxlen, AA)[0]
@@ -571,7 +571,7 @@ def test_nwsg16_long_references_and_skew_growth(pkg, orc):
 def test_nwsg16q_shared_query_profile_arm(pkg, orc, qlen):
     """global / semi-global with one reused protein profile: the workgroup-shared-profile kernel in each shape"""
     rng = np.random.default_rng(3400 + qlen)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     q = random_seqs(rng, 1, qlen, qlen, AA)[0]
     n = 300 if qlen <= 511 else 60
     rs = [mutate(rng, q, 0.3, 0.05, AA) if rng.random() < 0.5 else random_seqs(rng, 1, 20, qlen + 300, AA)[0] for _ in range(n)]
@@ -594,7 +594,7 @@ def test_nwsg16q_shared_query_profile_arm(pkg, orc, qlen):
 def test_nwsg16_query_fills_every_row(pkg, orc, qlen):
     """second generation, scores only: queries of exactly G * R rows (no virtual row on top), per-pair and shared"""
     rng = np.random.default_rng(3500 + qlen)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     n = 2100 if qlen == 160 else 40
     qs = random_seqs(rng, n, qlen, qlen, AA)
     rs = [mutate(rng, q, 0.3, 0.05, AA) if i % 2 else random_seqs(rng, 1, 20, qlen + 100, AA)[0] for i, q in enumerate(qs)]
@@ -613,7 +613,7 @@ def test_nwsg16_query_fills_every_row(pkg, orc, qlen):
 def test_nwsg16m_matrix_lookup_per_pair_protein(pkg, orc, qhi, rhi):
     """global / semi-global, per-pair protein batches (> 2048 pairs): scores read from the transposed matrix in LDS"""
     rng = np.random.default_rng(3600 + qhi)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     n = 2100
     qs = random_seqs(rng, n, max(1, qhi // 3), qhi, AA)
     qs[0] = random_seqs(rng, 1, qhi, qhi, AA)[0]
@@ -690,7 +690,7 @@ def test_general_multi_band_protein(pkg, orc):
     """queries longer than one 64-row band, BLOSUM62 11/1 (BASELINE config 1 style)"""
     rng = np.random.default_rng(2100)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     for ql in (64, 65, 128, 129, 200):
         q = random_seqs(rng, 1, ql, ql, AA)[0]
         r = mutate(rng, q, 0.3, 0.05, AA)
@@ -760,7 +760,7 @@ def test_nwsg_width8_range_tracking_in_the_packed_kernel(pkg, orc, gaps, n):
 
 def test_nwsg_width8_protein_profile_arm_and_long_references(pkg, orc):
     rng = np.random.default_rng(2360)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     q = random_seqs(rng, 1, 12, 12, AA)[0]
     rs = random_seqs(rng, 3000, 1, 160, AA) + [mutate(rng, q, 0.2, 0.05, AA) for _ in range(200)]
     rb, ro = orc.pack(rs)
@@ -808,7 +808,7 @@ def test_profile_batch_nw_stats_blosum62(pkg, orc):
     """BASELINE config 3 shape, reduced: one reused protein query, global + stats"""
     rng = np.random.default_rng(2500)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     q = random_seqs(rng, 1, 300, 300, AA)[0]
     rs = [mutate(rng, q, 0.4, 0.05, AA) + random_seqs(rng, 1, 0, 200, AA)[0] for _ in range(60)]
     prof = pkg.Profile.new(q, True, pm)
@@ -977,7 +977,7 @@ def test_stats16_local(pkg, orc, gaps, monkeypatch, by_trace):
           else random_seqs(rng, 1, 1, 300)[0] for i, q in enumerate(qs)]
     qs += [b"A", b"ACGT"]; rs += [b"C", b"TTTT"]
     _stats_case(pkg, orc, 2, None, qs, rs, gaps[0], gaps[1], pm, om)
-    b62, ob62 = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    b62, ob62 = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     q = random_seqs(rng, 1, 300, 300, AA)[0]
     rs2 = [random_seqs(rng, 1, 0, 100, AA)[0] + mutate(rng, q, 0.4, 0.05, AA)[50:250] + random_seqs(rng, 1, 0, 300, AA)[0] for _ in range(40)]
     _stats_case(pkg, orc, 2, None, None, rs2, 11, 1, b62, ob62, shared_query=q)
@@ -1025,7 +1025,7 @@ def test_stats_by_traceback_protein_short_references(pkg, orc):
     """large alphabets, per-pair queries, short references, a full batch: the matrix-lookup statistics kernel without
     free ends, statistics counted along the packed traceback otherwise"""
     rng = np.random.default_rng(5400)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     qs = random_seqs(rng, 2100, 40, 200, AA)
     rs = [mutate(rng, q, 0.3, 0.06, AA) if i % 3 else random_seqs(rng, 1, 10, 260, AA)[0] for i, q in enumerate(qs)]
     for mode, sg, route in ((2, None, "trace"), (0, None, "lookup"), (1, None, "trace"), (1, orc.S1_BEG | orc.S2_END, "trace"),
@@ -1039,7 +1039,7 @@ def test_stats_by_traceback_protein_short_references(pkg, orc):
 def test_stats16p_matrix_lookup_long_references(pkg, orc):
     """config 3's one-off form: per-pair protein queries against long references, global + statistics"""
     rng = np.random.default_rng(5500)
-    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     for qlo, qhi, n in ((40, 160, 24), (250, 320, 16), (500, 640, 8)):
         qs = random_seqs(rng, n, qlo, qhi, AA)
         rs = [random_seqs(rng, 1, 300, 1500, AA)[0] + mutate(rng, q, 0.3, 0.05, AA) + random_seqs(rng, 1, 300, 1500, AA)[0] for q in qs]
@@ -1052,7 +1052,7 @@ def test_stats16_shared_query_blosum62(pkg, orc):
     """config 3 shape through the 4-wave shared-profile variant"""
     rng = np.random.default_rng(5200)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     q = random_seqs(rng, 1, 300, 300, AA)[0]
     rs = [mutate(rng, q, 0.4, 0.05, AA) + random_seqs(rng, 1, 0, 300, AA)[0] for _ in range(41)]
     rs += random_seqs(rng, 9, 800, 1500, AA)
@@ -1156,7 +1156,7 @@ def test_batch_cigar_chunking(pkg, orc, monkeypatch):
 def test_trace16_cigar_blosum62(pkg, orc):
     rng = np.random.default_rng(4200)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     qs = random_seqs(rng, 60, 30, 250, AA)
     rs = [mutate(rng, q, 0.3, 0.06, AA) for q in qs]
     for mode in (0, 1):
@@ -1165,7 +1165,7 @@ def test_trace16_cigar_blosum62(pkg, orc):
 
 def test_pssm_single_pair(pkg, orc):
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     q, r = b"MKVLAAGIVGL", b"MKVIAGGLVGL"
     ps = pm.to_pssm(q)
     got = pkg.Aligner.new().matrix(ps).gap_open(11).gap_extend(1).build().align(q, r)
@@ -1254,7 +1254,7 @@ def test_fuzz_every_dispatch_path(pkg, orc):
     mats = [("dna23", pkg.Matrix.create(b"ACGT", 2, -3), orc.Matrix.create("ACGT", 2, -3), DNA),
             ("dna11", pkg.Matrix.default(), orc.Matrix.default(), DNA),
             ("dna54", pkg.Matrix.create(b"ACGTN", 5, -4), orc.Matrix.create("ACGTN", 5, -4), DNA),
-            ("b62", pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt"), AA)]
+            ("b62", pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt")), AA)]
     for it in range(60):
         name, pm, om, alpha = mats[int(rng.integers(0, len(mats)))]
         mode = int(rng.integers(0, 3))
@@ -1549,7 +1549,7 @@ def test_nwsg16_row_offset_very_negative_scores_and_every_free_end(pkg, orc, gap
     open_, ext = gaps
     rng = np.random.default_rng(3900 + open_ * 7 + ext)
     dpm, dom = pkg.Matrix.create(b"ACGT", 2, -3), orc.Matrix.create("ACGT", 2, -3)
-    ppm, pom = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    ppm, pom = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     # DNA: equal-length long queries vs short references (perm-table blocks), and ragged both ways (LDS-profile form)
     qs = random_seqs(rng, 64, 900, 900) + random_seqs(rng, 40, 5, 40) + random_seqs(rng, 40, 400, 1000)
     rs = random_seqs(rng, 64, 3, 60) + random_seqs(rng, 40, 800, 2500) + random_seqs(rng, 40, 1, 30)
@@ -1622,7 +1622,7 @@ def test_fuzz_traceback_and_statistics_global_and_semi_global(pkg, orc, seed, mo
     rng = np.random.default_rng(seed)
     monkeypatch.setenv("PMX_STATS_BY_TRACE", "1")
     dpm, dom = pkg.Matrix.create(b"ACGT", 2, -3), orc.Matrix.create("ACGT", 2, -3)
-    ppm, pom = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    ppm, pom = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     for it in range(6):
         protein = rng.random() < 0.35
         pm, om, alpha = (ppm, pom, AA) if protein else (dpm, dom, DNA)

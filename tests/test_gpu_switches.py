@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from util import random_seqs, mutate, DNA, AA
+from util import random_seqs, mutate, DNA, AA, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +29,7 @@ def _suite(pkg, orc):
     """[(label, callable returning a tuple of numpy arrays / bytes)], plus oracle expectations for the score batches."""
     rng = np.random.default_rng(9700)
     dna_p, dna_o = pkg.Matrix.create(b"ACGT", 2, -3), orc.Matrix.create("ACGT", 2, -3)
-    b62_p, b62_o = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+    b62_p, b62_o = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
     n = 2600                                                        # above the 2048-pair thresholds of the batch kernels
     dq = random_seqs(rng, n, 20, 150); dr = [mutate(rng, q, 0.1, 0.03) if k % 3 else random_seqs(rng, 1, 20, 160)[0] for k, q in enumerate(dq)]
     pq = random_seqs(rng, n, 20, 120, AA); pr = [mutate(rng, q, 0.3, 0.05, AA) if k % 2 else random_seqs(rng, 1, 20, 140, AA)[0] for k, q in enumerate(pq)]

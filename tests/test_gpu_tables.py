@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import workloads as wl
-from util import random_seqs, mutate, DNA, AA
+from util import random_seqs, mutate, DNA, AA, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +54,7 @@ def test_table_kernel_protein_1000_by_1000_and_rowcol_only(pkg, orc):
     """>= 1 000 pairs in total across the two table tests, up to 1 000 x 1 000, BLOSUM62 11/1; and the rowcol-only form"""
     rng = np.random.default_rng(9200)
     pm = pkg.Matrix.from_name("blosum62")
-    om = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    om = orc.Matrix.from_file(golden("blosum62.txt"))
     qs = random_seqs(rng, 40, 600, 1000, AA) + random_seqs(rng, 900, 20, 120, AA)
     rs = [mutate(rng, q, 0.3, 0.05, AA)[:1000] for q in qs]
     for mode in (0, 2):
@@ -119,7 +119,7 @@ def test_single_pair_trace_table_from_the_table_kernel(pkg, orc, mode):
     shapes = [(1, 1), (1, 40), (33, 1), (5, 300), (150, 150), (70, 257), (64, 256), (300, 513), (200, 1024), (129, 1023)]
     for alpha, ma, mi, open_, ext, letters in cases:
         if alpha is None:
-            pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file("tests/golden/blosum62.txt")
+            pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
         else:
             pm, om = pkg.Matrix.create(alpha, ma, mi), orc.Matrix.create(alpha.decode(), ma, mi)
         for ql, rl in shapes:

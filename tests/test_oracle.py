@@ -4,7 +4,7 @@ the striped CPU port against the scalar DP."""
 import numpy as np
 import pytest
 
-from util import random_seqs, mutate, score_from_cigar, DNA, AA
+from util import random_seqs, mutate, score_from_cigar, DNA, AA, golden
 
 MODES = {"nw": 0, "sg": 1, "sw": 2}
 
@@ -51,7 +51,7 @@ def test_banded_and_ssw_kats_are_plain_dp_consistent(orc, kats):
 
 
 def test_blosum62_fixture(orc):
-    m = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    m = orc.Matrix.from_file(golden("blosum62.txt"))
     assert m.size == 24 and (m.scores == m.scores.T).all()
     assert m.scores[m.mapper[ord("W")], m.mapper[ord("W")]] == 11
     assert m.scores[m.mapper[ord("a")], m.mapper[ord("R")]] == -1
@@ -153,7 +153,7 @@ def test_striped_cpu_port_matches_scalar(orc, gaps):
 
 def test_striped_cpu_port_blosum62(orc):
     rng = np.random.default_rng(301)
-    m = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    m = orc.Matrix.from_file(golden("blosum62.txt"))
     qs = random_seqs(rng, 100, 10, 300, AA)
     rs = [mutate(rng, q, 0.3, 0.05, AA) for q in qs]
     qb, qo = orc.pack(qs); rb, ro = orc.pack(rs)
@@ -173,8 +173,8 @@ def test_cfg1_fixture_is_reproduced(orc):
     """BASELINE config 1 (one protein pair, BLOSUM62 11/1): the committed oracle outputs (tests/golden/make_cfg1.py)
     pin the scalar oracle against regressions; the GPU suite replays the same pair through the mirror."""
     import json
-    fx = json.load(open("tests/golden/cfg1_protein_pair.json"))
-    m = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    fx = json.load(open(golden("cfg1_protein_pair.json")))
+    m = orc.Matrix.from_file(golden("blosum62.txt"))
     q, r = fx["query"].encode(), fx["ref"].encode()
     for name, mode in (("sw", orc.SW), ("nw", orc.NW), ("sg", orc.SG)):
         w = orc.align(mode, q, r, fx["open"], fx["extend"], m, stats=True, trace=True)
@@ -191,7 +191,7 @@ def test_vectorised_cpu_ports_of_the_stats_and_trace_modes(orc):
     models and wildcards."""
     from util import AA
     rng = np.random.default_rng(4242)
-    b62 = orc.Matrix.from_file("tests/golden/blosum62.txt")
+    b62 = orc.Matrix.from_file(golden("blosum62.txt"))
     for qlen, n, lo, hi, o, e in ((300, 45, 380, 520, 11, 1), (37, 33, 1, 90, 3, 3), (120, 17, 100, 140, 5, 0)):
         q = random_seqs(rng, 1, qlen, qlen, AA)[0]
         rs = [mutate(rng, q, 0.3, 0.05, AA) + random_seqs(rng, 1, 0, 60, AA)[0] if k % 2 else random_seqs(rng, 1, lo, hi, AA)[0] for k in range(n)]

@@ -1,10 +1,17 @@
 """Shared helpers for the parity tests (seeded synthetic inputs, score-from-CIGAR recomputation)."""
+import os
 import re
 
 import numpy as np
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DNA = np.frombuffer(b"ACGT", dtype=np.uint8)
 AA = np.frombuffer(b"ARNDCQEGHILKMFPSTWYV", dtype=np.uint8)
+
+
+def golden(name):
+    """Path of a stored fixture under tests/golden/, whatever the working directory."""
+    return os.path.join(GOLDEN, name)
 
 
 def random_seqs(rng, n, lo, hi, alphabet=DNA):
