@@ -15,6 +15,7 @@
 // 32-bit lanes (no saturation inside a band), score + end positions with the oracle's rules for every mode.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <algorithm>
 
 #define B_NEG (INT32_MIN / 2)
@@ -25,19 +26,6 @@ __device__ __forceinline__ bool b_better_sw(const BCand &a, const BCand &b)     
     if (a.H != b.H) return a.H > b.H;
     if (a.j != b.j) return a.j < b.j;
     return a.i < b.i;
-}
-
-template <int LP>
-__device__ __forceinline__ int b_from_below(int x)      // value of lane - 1 (garbage at the group's first lane: the caller overrides)
-{
-    if (LP == 16) return __builtin_amdgcn_update_dpp(x, x, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
-    return __builtin_amdgcn_update_dpp(x, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-}
-template <int LP>
-__device__ __forceinline__ int b_from_above(int x)      // value of lane + 1
-{
-    if (LP == 16) return __builtin_amdgcn_update_dpp(x, x, 0x101 /*row_shl:1*/, 0xF, 0xF, false);
-    return __builtin_amdgcn_update_dpp(x, x, 0x130 /*wave_shl:1*/, 0xF, 0xF, false);
 }
 
 template <int LP>
@@ -120,8 +108,8 @@ void pmx_banded_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
         sc_next = score_of(ni, nj);                             // independent of this step's arithmetic: its latency is hidden
         const int p = u & 1;
         const bool active = have && s <= s_last && u <= 2 * band && i >= 0 && i < ql && j >= 0 && j < rl;
-        const int belowH = b_from_below<LP>(Hm1), belowE = b_from_below<LP>(Em1);
-        const int aboveH = b_from_above<LP>(Hm1), aboveF = b_from_above<LP>(Fm1);
+        const int belowH = lane_prev<LP>(Hm1), belowE = lane_prev<LP>(Em1);
+        const int aboveH = lane_next<LP>(Hm1), aboveF = lane_next<LP>(Fm1);
         int upH = p ? aboveH : Hm1, upF = p ? aboveF : Fm1;
         int leftH = p ? Hm1 : belowH, leftE = p ? Em1 : belowE;
         int dg = Hm2;
@@ -277,8 +265,8 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
         const bool inside = i >= 0 && i < ql && j >= 0 && j < rl;
         const int sc = inside ? (int)mat[qm[i] + rm[j]] : 0;
         const bool active = have && s <= s_last && u <= 2 * band && inside;
-        const int belowH = b_from_below<LP>(Hm1), belowE = b_from_below<LP>(Em1);
-        const int aboveH = b_from_above<LP>(Hm1), aboveF = b_from_above<LP>(Fm1);
+        const int belowH = lane_prev<LP>(Hm1), belowE = lane_prev<LP>(Em1);
+        const int aboveH = lane_next<LP>(Hm1), aboveF = lane_next<LP>(Fm1);
         int upH = p ? aboveH : Hm1, upF = p ? aboveF : Fm1;
         int leftH = p ? Hm1 : belowH, leftE = p ? Em1 : belowE;
         int dg = Hm2;
@@ -417,26 +405,11 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
 // against everything) floors to 0 like the boundary it stands for, feeds nothing real (dependencies run down and right) and can
 // never strictly exceed a real cell (its value reaches it through a gap) -- so both sequences are staged with pad margins on
 // both sides and EVERY step runs the lean form.  Values are biased (true 0 = B, B = 1024 + open + extend: every live value is
-// 0 or in [1024, 31743], where v_pk_maximum3_f16 is an exact integer max3 and v_pk_sub_u16 with clamp keeps "minus infinity" = 0
-// sticky); the strips carry H - open and the scores carry + open, so the diagonal sum is one add; the zero floor is folded into
-// E.  A lane keeps its best and the step where it was first strictly exceeded (per half); cell (i, j) follows from the step.
-// 15.5 instructions per TWO cells.  The host proves the range (score bound + B < 31744, min score + open >= 0).
-typedef short b_v2s __attribute__((ext_vector_type(2)));
-typedef unsigned short b_v2us __attribute__((ext_vector_type(2)));
-typedef _Float16 b_v2h __attribute__((ext_vector_type(2)));
-#define BPK(x) __builtin_bit_cast(b_v2s, (int)(x))
-#define BI32(x) __builtin_bit_cast(int, (x))
-__device__ __forceinline__ int bp_max3(int a, int b, int c)
-{
-    const b_v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(b_v2h, a), __builtin_bit_cast(b_v2h, b)),
-                                                  __builtin_bit_cast(b_v2h, c));
-    return __builtin_bit_cast(int, r);
-}
-__device__ __forceinline__ int bp_subus(int a, int b)         // v_pk_sub_u16 clamp: saturates at 0
-{
-    return __builtin_bit_cast(int, __builtin_elementwise_sub_sat(__builtin_bit_cast(b_v2us, a), __builtin_bit_cast(b_v2us, b)));
-}
-
+// 0 or in the exact window [1024, 31743] of pmx_pk16.h); the strips carry H - open and the scores carry + open, so the diagonal
+// sum is one add; the zero floor is folded into E.  A lane keeps its best and the step where it was first strictly exceeded
+// (per half); cell (i, j) follows from the step.  15.5 instructions per TWO cells.  The host proves the range (score bound + B
+// < 31744, min score + open >= 0).
+//
 // FORM 0: a byte lookup in the padded matrix per cell (any alphabet up to PMX_MAX_FAST_MSIZE - 1 letters).
 // FORM 1 (<= 7 letters + the pad symbol): a matrix row is 8 bytes -- one ds_read_b64 per query symbol and a v_perm_b32 by the
 //   reference symbol replace the byte lookup (fewer address adds; measured 40.0 -> 38.3 ms on cfg 5's second pass).
@@ -577,7 +550,7 @@ void pmx_banded_packed_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
     nsteps = (nsteps + 7) & ~7;
     __syncthreads();
 
-    const int B = 1024 + open + ext;                          // true 0
+    const int B = PK16_LO + open + ext;                       // true 0
     const int B2 = B * 0x00010001, vOpen = open * 0x00010001, vExt = ext * 0x00010001;
     int bH = B2, bT = 0;                                      // best (only a score above 0 is tracked) and the step where it was first exceeded
     const int keep_odd = x >= band ? 0 : -1;                  // the lane's odd diagonal lies outside the band: forced to "minus infinity"
@@ -593,7 +566,6 @@ void pmx_banded_packed_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
         if (LP == 32) r &= last_ok;
         return r;
     };
-    const b_v2s sh15 = {15, 15};
     int signs = (int)0x80008000;
     asm volatile("" : "+v"(signs));
     // best and its step, per half, once per PAIR of steps (a lane's even cell and the odd cell after it): 0xFFFF where either exceeds
@@ -601,12 +573,12 @@ void pmx_banded_packed_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
     // "the odd cell is the larger" (sign of He - Ho: on a tie the even cell, the earlier one, stands).  6 instructions per two
     // steps; one track per step was 8.
     auto track2 = [&](int He, int Ho, int tau2) {
-        const int P = bp_max3(bH, He, Ho);
-        const int m = BI32((BPK(bH) - BPK(P)) >> sh15);
-        const int d = BI32(BPK(He) - BPK(Ho));
+        const int P = pk_max3(bH, He, Ho);
+        const int m = pk_lt(bH, P);
+        const int d = I32(PK(He) - PK(Ho));
         int tw;
         asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(tw) : "v"(d), "v"(signs), "s"(tau2 * 0x00010001));      // (one SGPR per instruction)
-        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bT) : "v"(m), "v"(tw), "v"(bT));
+        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bT) : "v"(m), "v"(tw), "v"(bT));   // (written out: bfi() here schedules differently)
         bH = P;
     };
     // LDS read positions (element indices), clamped into the trailing pad once a pair has run past its sequences
@@ -682,21 +654,21 @@ void pmx_banded_packed_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
             int He;
             {   // even step: left from lane x - 1, up = own previous cell
                 const int lHo = below(Ho1), lEe = below(Ee1);
-                const int E = bp_max3(lEe, lHo, floorv), F = bp_max3(Fe1, Ho1, Ho1);
-                const int H = bp_max3(Ho2 + sc[2 * k], E, F);
+                const int E = pk_max3(lEe, lHo, floorv), F = pk_max3(Fe1, Ho1, Ho1);
+                const int H = pk_max3(Ho2 + sc[2 * k], E, F);
                 He = H;
-                Ho2 = Ho1; Ho1 = bp_subus(H, vOpen); Ee1 = bp_subus(E, vExt); Fe1 = bp_subus(F, vExt);
+                Ho2 = Ho1; Ho1 = pk_subus(H, vOpen); Ee1 = pk_subus(E, vExt); Fe1 = pk_subus(F, vExt);
             }
             {   // odd step: up from lane x + 1, left = own previous cell
                 const int uHo = above(Ho1), uFe = above(Fe1);
-                int E = bp_max3(Ee1, Ho1, floorv);
-                const int F = bp_max3(uFe, uHo, uHo);
-                int H = bp_max3(Ho2 + sc[2 * k + 1], E, F);
+                int E = pk_max3(Ee1, Ho1, floorv);
+                const int F = pk_max3(uFe, uHo, uHo);
+                int H = pk_max3(Ho2 + sc[2 * k + 1], E, F);
                 // the band's last lane: its odd diagonal is outside.  H and E forced to "minus infinity" keep every lane beyond it at
                 // 0 for good (they read pad symbols, and nothing else feeds them), so the F that comes back from there is 0 unforced
                 H &= keep_odd; E &= keep_odd;
                 track2(He, H, (t0 >> 1) + k);
-                Ho2 = Ho1; Ho1 = bp_subus(H, vOpen); Ee1 = bp_subus(E, vExt); Fe1 = bp_subus(F, vExt);
+                Ho2 = Ho1; Ho1 = pk_subus(H, vOpen); Ee1 = pk_subus(E, vExt); Fe1 = pk_subus(F, vExt);
             }
         }
     }

@@ -20,10 +20,9 @@
 // no triangles at the ends of a strip, no masks in the loop.
 //
 // Arithmetic (the model, cell for cell: tests/bstrip_model.py, checked against the banded oracle on the CPU tier):
-//   * values are STORED as true + sigma(tau, d) + bias in the window [1024, 31743] where v_pk_maximum3_f16 is an exact integer max3
-//     (profiles/microbench/max3_f16_int.hip); sigma = ext * (tau + d) for global / semi-global (E along the row needs no subtraction),
-//     ext * (2 tau + d) in the double-skew variant (F needs none either: 6 instructions per two cells), ext * tau for local alignment
-//     (the zero floor is ONE value per row and rides on the E chain);
+//   * values are STORED as true + sigma(tau, d) + bias in the exact window [1024, 31743] of pmx_pk16.h; sigma = ext * (tau + d) for
+//     global / semi-global (E along the row needs no subtraction), ext * (2 tau + d) in the double-skew variant (F needs none either:
+//     6 instructions per two cells), ext * tau for local alignment (the zero floor is ONE value per row and rides on the E chain);
 //   * scores come from v_perm_b32: the table is the 4 score bytes of the row's query letter (one dword per pair from LDS), the
 //     selector is the cell's reference letter; the selectors slide one cell per row (a shift of the register names every 4 rows);
 //   * columns left of the matrix are VIRTUAL: selector 0x0C (score byte 0) keeps them low, and for a free query begin the column
@@ -36,23 +35,14 @@
 //     launcher runs those pairs in pmx_banded_kernel.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
 
-typedef short s_v2s __attribute__((ext_vector_type(2)));
-typedef _Float16 s_v2h __attribute__((ext_vector_type(2)));
-#define SPK(x) __builtin_bit_cast(s_v2s, (int)(x))
-#define SI32(x) __builtin_bit_cast(int, (x))
 #define S_NEG (INT32_MIN / 2)
 
-__device__ __forceinline__ int s_max3(int a, int b, int c)      // exact integer max3 on patterns in [1024, 31743]
-{
-    const s_v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(s_v2h, a), __builtin_bit_cast(s_v2h, b)),
-                                                  __builtin_bit_cast(s_v2h, c));
-    return __builtin_bit_cast(int, r);
-}
-__device__ __forceinline__ int s_max2(int a, int b) { return SI32(__builtin_elementwise_max(SPK(a), SPK(b))); }
+__device__ __forceinline__ int s_max2(int a, int b) { return I32(__builtin_elementwise_max(PK(a), PK(b))); }
 
 // value of group member g - 1 (lanes of a group sit 16 / G apart inside a DPP row of 16); member 0 keeps `old`
 template <int G>
@@ -376,9 +366,9 @@ void pmx_bstrip_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
                 const int T = Hx[c] + s;
                 const int Fe = FSUB ? Fin - ext2 : Fin;
                 const int Ee = ESUB ? E - ext2 : E;
-                const int H = s_max3(T, Ee, Fe);
+                const int H = pk_max3(T, Ee, Fe);
                 const int X = H - Cg2;
-                E = SW ? s_max3(Ee, X, Zpe) : s_max2(Ee, X);
+                E = SW ? pk_max3(Ee, X, Zpe) : s_max2(Ee, X);
                 Fn[c] = s_max2(Fe, X);
                 Hx[c] = X;
             };
@@ -418,11 +408,11 @@ void pmx_bstrip_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
                     //      win by an earlier column (j = tau + c: an earlier cell index by more than the rows in between): rare, exact ----
                     int rm = Hx[0];
 #pragma unroll
-                    for (int c = 1; c + 1 < C; c += 2) rm = s_max3(rm, Hx[c], Hx[c + 1]);
+                    for (int c = 1; c + 1 < C; c += 2) rm = pk_max3(rm, Hx[c], Hx[c + 1]);
                     if ((C & 1) == 0) rm = s_max2(rm, Hx[C - 1]);
-                    const s_v2s fifteen = {15, 15};
-                    const int d2 = SI32(SPK(best) - SPK(rm));
-                    const int mgt = SI32(SPK(d2) >> fifteen);                        // 0xFFFF per half where the row exceeds the best
+                    const v2s fifteen = {15, 15};
+                    const int d2 = I32(PK(best) - PK(rm));
+                    const int mgt = I32(PK(d2) >> fifteen);                          // 0xFFFF per half where the row exceeds the best
                     // a half with d2 == 0 whose best is one this lane has SEEN (a bound taken over from the group cannot be tied: it lies
                     // below the group's best)
                     // ... and only while the saved cell is young: a later row wins a tie by an earlier COLUMN (tau + c), i.e. within C - 2 rows
@@ -455,7 +445,7 @@ void pmx_bstrip_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
                             }
                         }
                     }
-                    if (__builtin_amdgcn_ballot_w64(mgt != 0) != 0) {
+                    if (__builtin_amdgcn_ballot_w64(mgt != 0) != 0) {      // (v_bfi written out: bfi() here schedules differently)
                         asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bestrow) : "v"(mgt), "v"((tau & 0xFFFF) * 0x00010001), "v"(bestrow));
 #pragma unroll
                         for (int c = 0; c < C; ++c) {
@@ -517,8 +507,8 @@ void pmx_bstrip_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
             for (int off = G / 2; off >= 1; off >>= 1) v = s_max2(v, __shfl_xor(v, SUBG * off, 64));
             const int fresh = v - 0x00010001 + form;
             const int nb = s_max2(best, fresh);
-            const s_v2s fifteen = {15, 15};
-            fake |= SI32((SPK(best) - SPK(nb)) >> fifteen);                          // halves that were raised
+            const v2s fifteen = {15, 15};
+            fake |= I32((PK(best) - PK(nb)) >> fifteen);                             // halves that were raised (pk_lt() schedules differently)
             best = nb;
         }
     }
@@ -610,7 +600,7 @@ static bool bstrip_window(int mode, int m, int n, int open, int ext, int smin, i
     if (open < ext || ext < 0 || Cg > 120) return false;
     const long long OB = Cg + (long long)a * ext;
     if (smin + OB < 0 || smax + OB > 254) return false;
-    const long long LOW = 1024 + 2LL * std::max(open, ext) + 8;
+    const long long LOW = PK16_LO + 2LL * std::max(open, ext) + 8;
     const long long L = std::min(m, n);
     long long lo_true, hi_true = (long long)std::max(0, smax) * L;
     if (mode == PMX_MODE_SW) lo_true = 0;
@@ -620,7 +610,7 @@ static bool bstrip_window(int mode, int m, int n, int open, int ext, int smin, i
     const long long need_lo = LOW + 2LL * open + 300 + (long long)rows * ext;
     const long long B = need_lo - (lo_true + sig_lo);
     const long long top = hi_true + sig_hi + B + 256;
-    if (top > 31743 - 8) return false;
+    if (top > PK16_HI - 8) return false;
     *bias = (int)B; *low = (int)LOW;
     return true;
 }

@@ -20,6 +20,7 @@
 // oracle/pmx_oracle.c (the checker); they are restated here, not shared.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 
 #define NEG_INF (INT32_MIN / 2)
 #ifndef PMX_MW_MAX_PAIRS
@@ -36,9 +37,6 @@
 #define T_DEL_F 64
 
 struct Cand { int H, i, j, M, S, L; };
-
-// value of lane-1 (DPP wave_shr:1; lane 0 keeps its own value, which the caller overrides)
-__device__ __forceinline__ int lane_up(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xF, 0xF, false); }
 
 // true if a should replace b under "larger H, then smaller j, then smaller i"
 __device__ __forceinline__ bool better_sw(const Cand &a, const Cand &b)
@@ -181,7 +179,7 @@ void pmx_general_kernel(const PmxGeneralArgs a)
                 const int s = s_n;
                 s_n = mrow[sym_n];
                 sym_n = rs[j + 2];
-                int upH = lane_up(oH), upF = lane_up(oF);
+                int upH = lane_prev<64>(oH), upF = lane_prev<64>(oF);
                 if (lane == 0) {
                     if (bandi == 0) { upH = row_pen ? -(open + j * ext) : 0; upF = NEG_INF; }
                     else { upH = pb[0]; upF = pb[1]; pb[0] = bound[8LL * (j + 1) + 0]; pb[1] = bound[8LL * (j + 1) + 1]; }
@@ -203,11 +201,11 @@ void pmx_general_kernel(const PmxGeneralArgs a)
             s_n = mrow[sym_n];
             sym_n = rs[max(0, min(rl, j + 2))];
             // --- values of the row above for column j (produced one step ago by lane-1) ---
-            int upH = lane_up(oH), upF = lane_up(oF);
+            int upH = lane_prev<64>(oH), upF = lane_prev<64>(oF);
             int upHM = 0, upHS = 0, upHL = 0, upFM = 0, upFS = 0, upFL = 0;
             if (STATS) {
-                upHM = lane_up(oHM); upHS = lane_up(oHS); upHL = lane_up(oHL);
-                upFM = lane_up(oFM); upFS = lane_up(oFS); upFL = lane_up(oFL);
+                upHM = lane_prev<64>(oHM); upHS = lane_prev<64>(oHS); upHL = lane_prev<64>(oHL);
+                upFM = lane_prev<64>(oFM); upFS = lane_prev<64>(oFS); upFL = lane_prev<64>(oFL);
             }
             const bool active = row_ok && j >= jlo && j <= jhi;
             if (lane == 0 && j <= jhi) {
@@ -524,7 +522,7 @@ void pmx_general_mw_kernel(const PmxGeneralArgs a)
                 const int s = s_n;
                 s_n = mrow[sym_n];
                 sym_n = rs[j + 2];
-                int upH = lane_up(oH), upF = lane_up(oF);
+                int upH = lane_prev<64>(oH), upF = lane_prev<64>(oF);
                 if (lane == 0) {
                     if (bandi == 0) { upH = row_pen ? -(open + j * ext) : 0; upF = NEG_INF; }
                     else { upH = pb0; upF = pb1; pb0 = bound[8LL * (j + 1) + 0]; pb1 = bound[8LL * (j + 1) + 1]; }
@@ -545,11 +543,11 @@ void pmx_general_mw_kernel(const PmxGeneralArgs a)
                 s_n = mrow[sym_n];
                 sym_n = rs[max(0, min(rl, j + 2))];
                 // --- values of the row above for column j (produced one step ago by lane-1) ---
-                int upH = lane_up(oH), upF = lane_up(oF);
+                int upH = lane_prev<64>(oH), upF = lane_prev<64>(oF);
                 int upHM = 0, upHS = 0, upHL = 0, upFM = 0, upFS = 0, upFL = 0;
                 if (STATS) {
-                    upHM = lane_up(oHM); upHS = lane_up(oHS); upHL = lane_up(oHL);
-                    upFM = lane_up(oFM); upFS = lane_up(oFS); upFL = lane_up(oFL);
+                    upHM = lane_prev<64>(oHM); upHS = lane_prev<64>(oHS); upHL = lane_prev<64>(oHL);
+                    upFM = lane_prev<64>(oFM); upFS = lane_prev<64>(oFS); upFL = lane_prev<64>(oFL);
                 }
                 const bool active = row_ok && j >= jlo && j <= jhi;
                 if (lane == 0 && j <= jhi) {

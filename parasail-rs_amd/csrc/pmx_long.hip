@@ -32,6 +32,7 @@
 // (score, column, row) in a finalize kernel.  nw -- the corner.  sg -- first maximum of the last row by ascending column,
 // then the last column (smallest row) only if strictly greater; free begins are boundary values.
 #include "pmx_common.h"
+#include "pmx_pk16.h"
 #include <type_traits>
 
 #define LONG_NEG (-(1 << 30))
@@ -51,10 +52,8 @@ struct PmxLongArgs {
     int spin_limit;                                    // polls of one wait before a band gives up
 };
 
-__device__ __forceinline__ int dpp_wave_shr(int old, int x) { return __builtin_amdgcn_update_dpp(old, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false); }
-// (lane 63 has no source and gets 0: what enters there reaches lane 0 only after 64 shifts, and every rotating register is reloaded by then;
-//  without an `old` operand the result is not tied to the source's register -- one v_mov_b32 less per shift)
-__device__ __forceinline__ int dpp_wave_shl(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x130 /*wave_shl:1*/, 0xF, 0xF, true); }
+// The rotating registers move with lane_next_untied: lane 63 has no source and gets 0, and what enters there reaches lane 0 only
+// after 64 shifts, when every rotating register has been reloaded.
 
 template <int R, int MODE, int CH /* columns per boundary chunk: 64, or 16 (lanes 0 .. 15 load; a band runs ~50 steps closer behind the one above) */>
 __global__ __launch_bounds__(64)
@@ -158,8 +157,8 @@ void pmx_long32_kernel(PmxLongArgs a)
     // the symbol chain moves one lane per step whatever the DP does (lanes that have not started yet hand garbage on that
     // the front of real symbols overwrites before it is used); the profile row of the symbol is read one step ahead
     auto advance = [&](int (&w)[R / 2]) {
-        const int sy = dpp_wave_shr(symch, symcur);
-        symch = dpp_wave_shl(symch);
+        const int sy = lane_prev<64>(symch, symcur);
+        symch = lane_next_untied(symch);
         symcur = sy;
         if (R == 2) w[0] = *reinterpret_cast<const int *>(prof_lane + sy);
         else if (R == 4) { const int2 v = *reinterpret_cast<const int2 *>(prof_lane + sy); w[0] = v.x; w[1] = v.y; }
@@ -180,8 +179,8 @@ void pmx_long32_kernel(PmxLongArgs a)
         if (decltype(last_of_chunk)::value && ((t + 1) & 63) == 0) reload_sym(t + 1);
         advance(wn);                                       // the next step's scores, in flight while this step computes
         __builtin_amdgcn_sched_barrier(0);
-        const int Hin = dpp_wave_shr(Hb, Hout), Fin = dpp_wave_shr(Fb, Fout);
-        Hb = dpp_wave_shl(Hb); Fb = dpp_wave_shl(Fb);
+        const int Hin = lane_prev<64>(Hb, Hout), Fin = lane_prev<64>(Fb, Fout);
+        Hb = lane_next_untied(Hb); Fb = lane_next_untied(Fb);
         if (!EDGE || t >= lane) {
             int F = Fin, d = diag;
 #pragma unroll
@@ -402,8 +401,8 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
         if (base + CH < T) prefetch_bound(base + CH);
     };
     auto advance = [&](int (&wa)[R / 2], int (&wb)[R / 2]) {
-        const int sy = dpp_wave_shr(symch, symcur);
-        symch = dpp_wave_shl(symch);
+        const int sy = lane_prev<64>(symch, symcur);
+        symch = lane_next_untied(symch);
         symcur = sy;
         const unsigned char *pa = prof_lane + (sy & 0xFFFF), *pb = prof_lane + ((unsigned)sy >> 16);
         if (R == 2) { wa[0] = *reinterpret_cast<const int *>(pa); wb[0] = *reinterpret_cast<const int *>(pb); }
@@ -415,9 +414,9 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
         if (decltype(last_of_chunk)::value && ((t + 1) & 63) == 0) reload_sym(t + 1);
         advance(na, nb);
         __builtin_amdgcn_sched_barrier(0);
-        const int Hin0 = dpp_wave_shr(Hb0, Hout0), Fin0 = dpp_wave_shr(Fb0, Fout0);
-        const int Hin1 = dpp_wave_shr(Hb1, Hout1), Fin1 = dpp_wave_shr(Fb1, Fout1);
-        Hb0 = dpp_wave_shl(Hb0); Fb0 = dpp_wave_shl(Fb0); Hb1 = dpp_wave_shl(Hb1); Fb1 = dpp_wave_shl(Fb1);
+        const int Hin0 = lane_prev<64>(Hb0, Hout0), Fin0 = lane_prev<64>(Fb0, Fout0);
+        const int Hin1 = lane_prev<64>(Hb1, Hout1), Fin1 = lane_prev<64>(Fb1, Fout1);
+        Hb0 = lane_next_untied(Hb0); Fb0 = lane_next_untied(Fb0); Hb1 = lane_next_untied(Hb1); Fb1 = lane_next_untied(Fb1);
         if (!EDGE || t >= lane) {
             int N0[R], N1[R];
             int F0 = Fin0, F1 = Fin1, d0 = diag, d1 = Hin0;

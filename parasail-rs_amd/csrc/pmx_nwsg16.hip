@@ -9,9 +9,9 @@
 // one-step skew between neighbouring lanes (DPP), per-pair query profile in LDS.  Differences:
 //
 //   * Values are biased by 16384 so that negative scores are representable: the exact window is
-//     true value in [-15360, 15359] (bit patterns [1024, 31743], where v_pk_maximum3_f16 is an exact
-//     integer max3).  The host proves from lengths, gap penalties and matrix extremes that no cell can
-//     leave the window; otherwise the general 32-bit kernel is used.
+//     true value in [-15360, 15359] (bit patterns [1024, 31743], see pmx_pk16.h).  The host proves from
+//     lengths, gap penalties and matrix extremes that no cell can leave the window; otherwise the general
+//     32-bit kernel is used.
 //   * The query is aligned to the BOTTOM of the G*R-row strip set, so its last row is always the last
 //     register of the last lane.  The P = G*R - qlen rows above it are *virtual rows*, the G-1 pad
 //     symbols in front of the reference are *virtual columns*.  Their profile scores are chosen so
@@ -26,13 +26,8 @@
 //     wins only if strictly greater -- oracle/pmx_oracle.c states the rule).
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-typedef unsigned short v2us __attribute__((ext_vector_type(2)));
-
-#define PK(x)  __builtin_bit_cast(v2s, (int)(x))
-#define I32(x) __builtin_bit_cast(int, (x))
 
 #ifndef PMX_QSTAGE
 #define PMX_QSTAGE 8                   // steps of trace records the shared-profile sweep gathers in LDS per flush (4 or 8)
@@ -45,43 +40,13 @@ __device__ __forceinline__ v2s n_addw(v2s a, v2s b)       // wrapping add (v_pk_
 {
     return __builtin_bit_cast(v2s, __builtin_bit_cast(v2us, a) + __builtin_bit_cast(v2us, b));
 }
-__device__ __forceinline__ v2s n_subus(v2s a, v2s b)      // v_pk_sub_u16 clamp
+__device__ __forceinline__ v2s n_min3f(v2s a, v2s b, v2s c)     // v_pk_minimum3_f16: exact integer min3 in the window of pmx_pk16.h
 {
-    return __builtin_bit_cast(v2s, __builtin_elementwise_sub_sat(__builtin_bit_cast(v2us, a), __builtin_bit_cast(v2us, b)));
-}
-__device__ __forceinline__ v2s n_max3(v2s a, v2s b, v2s c)
-{
-    int r;
-    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(I32(a)), "v"(I32(b)), "v"(I32(c)));
-    return PK(r);
-}
-typedef _Float16 n_v2h __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2s n_max3f(v2s a, v2s b, v2s c)     // same instruction, as a builtin (no inline-asm wait states)
-{
-    const n_v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(n_v2h, a), __builtin_bit_cast(n_v2h, b)),
-                                                  __builtin_bit_cast(n_v2h, c));
+    const v2h r = __builtin_elementwise_minimum(__builtin_elementwise_minimum(__builtin_bit_cast(v2h, a), __builtin_bit_cast(v2h, b)),
+                                                __builtin_bit_cast(v2h, c));
     return __builtin_bit_cast(v2s, r);
-}
-__device__ __forceinline__ v2s n_min3f(v2s a, v2s b, v2s c)     // v_pk_minimum3_f16: exact integer min3 on the same patterns
-{
-    const n_v2h r = __builtin_elementwise_minimum(__builtin_elementwise_minimum(__builtin_bit_cast(n_v2h, a), __builtin_bit_cast(n_v2h, b)),
-                                                  __builtin_bit_cast(n_v2h, c));
-    return __builtin_bit_cast(v2s, r);
-}
-__device__ __forceinline__ int n_bfi(int m, int a, int b)
-{
-    int r;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ int s_bfi(int m /* scalar constant */, int a, int b)
-{
-    int r;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(m), "v"(a), "v"(b));
-    return r;
 }
 // per-half masks (0xFFFF / 0) on values below 32768
-__device__ __forceinline__ int m_lt(v2s a, v2s b) { const v2s sh = {15, 15}; return I32((a - b) >> sh); }      // a < b
 __device__ __forceinline__ int m_eq(v2s a, v2s b)
 {
     const v2us one = {1, 1};
@@ -93,23 +58,6 @@ __device__ __forceinline__ int m_ult(v2s a, v2s b)        // unsigned a < b (a m
     const v2us one = {1, 1}, zero = {0, 0};
     const v2us d = __builtin_elementwise_sub_sat(__builtin_bit_cast(v2us, b), __builtin_bit_cast(v2us, a));
     return I32(__builtin_bit_cast(v2s, zero - __builtin_elementwise_min(d, one)));
-}
-
-// IL (G == 8): two groups interleaved in a DPP row of 16 lanes (lane = 2 g + (slot & 1) + 16 (slot >> 1)): row_shr:2
-// moves every group up by one lane and the row's first two lanes keep `neutral` -- no select (see pmx_sw16.hip).
-template <int G, bool IL = false>
-__device__ __forceinline__ int n_shift_up(int x, int neutral, int g)
-{
-    if (IL) return __builtin_amdgcn_update_dpp(neutral, x, 0x112 /*row_shr:2*/, 0xF, 0xF, false);
-    if (G <= 16) {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
-        if (G < 16) r = (g == 0) ? neutral : r;
-        return r;
-    } else {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-        if (G < 64) r = (g == 0) ? neutral : r;
-        return r;
-    }
 }
 
 template <int G, int R>
@@ -270,17 +218,17 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
         for (int k = 0; k < R / 2; ++k) { wa[k] = sa[k]; wb[k] = sb[k]; }
     };
     auto step = [&](const v2s (&Hold)[R], v2s (&Hnew)[R], const int (&wa)[R / 2], const int (&wb)[R / 2]) {
-        const int Hin = n_shift_up<G>(Hout, NB2, g);     // row above lane 0: H = 0
-        v2s F = PK(n_shift_up<G>(Fout, 0, g));           //                   F = -inf
+        const int Hin = group_shift_up<G>(Hout, NB2, g); // row above lane 0: H = 0
+        v2s F = PK(group_shift_up<G>(Fout, 0, g));       //                   F = -inf
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const v2s s = PK(__builtin_amdgcn_perm(wb[k / 2], wa[k / 2], (k & 1) ? 0x07060302 : 0x05040100));
             const v2s d = (k == 0) ? diag0 : Hold[k - 1];
             const v2s Tt = n_addw(d, s);
-            const v2s H = n_max3(Tt, E[k], F);
-            const v2s Ho = n_subus(H, vOpen);
-            E[k] = n_max3(n_subus(E[k], vExt), Ho, Ho);
-            F = n_max3(n_subus(F, vExt), Ho, Ho);
+            const v2s H = pk_max3_asm(Tt, E[k], F);
+            const v2s Ho = pk_subus(H, vOpen);
+            E[k] = pk_max3_asm(pk_subus(E[k], vExt), Ho, Ho);
+            F = pk_max3_asm(pk_subus(F, vExt), Ho, Ho);
             Hnew[k] = H;
         }
         diag0 = PK(Hin);
@@ -290,11 +238,11 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
         // ---- captures ----
         const v2s jv = PK(jj);
         const int mLast = m_eq(jv, rl1);                  // this lane is at column rlen-1
-        res = n_bfi(mLast, Hout, res);
+        res = bfi(mLast, Hout, res);
         if (s2_end) {
-            const int imp = m_lt(bestrow, PK(Hout)) & m_ult(jv, rlv);
-            bestrow = PK(n_bfi(imp, Hout, I32(bestrow)));
-            bestrowj = n_bfi(imp, jj, bestrowj);
+            const int imp = pk_lt(bestrow, PK(Hout)) & m_ult(jv, rlv);
+            bestrow = PK(bfi(imp, Hout, I32(bestrow)));
+            bestrowj = bfi(imp, jj, bestrowj);
         }
         if (s1_end && __builtin_amdgcn_ballot_w64(mLast != 0) != 0) {
             // last column of this strip: maximum over the REAL rows, smallest row first
@@ -304,18 +252,18 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const int er = g * R + k;
-                const int mreal = ~m_lt(PK(pack2(er, er)), Pv);
+                const int mreal = ~pk_lt(PK(pack2(er, er)), Pv);
                 vals[k] = PK(I32(Hnew[k]) & mreal);
-                cm = n_max3(cm, vals[k], vals[k]);
+                cm = pk_max3_asm(cm, vals[k], vals[k]);
             }
 #pragma unroll
             for (int k = R - 1; k >= 0; --k) {
                 const int er = g * R + k;
-                krow = n_bfi(m_eq(vals[k], cm), pack2(er, er), krow);
+                krow = bfi(m_eq(vals[k], cm), pack2(er, er), krow);
             }
-            const int imp = m_lt(bestcol, cm) & mLast;
-            bestcol = PK(n_bfi(imp, I32(cm), I32(bestcol)));
-            bestcoli = n_bfi(imp, krow, bestcoli);
+            const int imp = pk_lt(bestcol, cm) & mLast;
+            bestcol = PK(bfi(imp, I32(cm), I32(bestcol)));
+            bestcoli = bfi(imp, krow, bestcoli);
         }
         jj = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, jj) + one2));
     };
@@ -670,8 +618,8 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         pl = PK(r);
     };
     auto step = [&](const int (&Hold)[R], int (&Hnew)[R], const int (&wa)[RS / 4], const int (&wb)[RS / 4], int t) {
-        const int Hin = n_shift_up<G, IL>(Hout, topX, g);
-        int F = n_shift_up<G, IL>(Fout, topX, g);            // F^ into row 0 = X of the row above (see the header)
+        const int Hin = group_shift_up<G, IL>(Hout, topX, g);
+        int F = group_shift_up<G, IL>(Fout, topX, g);        // F^ into row 0 = X of the row above (see the header)
         int Tpre[R];
         v2s plane[TR ? R / 4 : 1];
         int tacc = 0, tprev = 0;
@@ -689,7 +637,7 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int Fe = ROWX ? F : F - vExt;
-            const int H = I32(n_max3f(PK(Tpre[k]), PK(E[k]), PK(Fe)));
+            const int H = I32(pk_max3(PK(Tpre[k]), PK(E[k]), PK(Fe)));
             const int X = H - vC;
             if (TR && !TRB) {
                 push(plane[k / 4], Tpre[k], H);      // ND
@@ -703,20 +651,20 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
                 const int dEO = I32(PK(E[k]) - PK(X)), dFO = I32(PK(Fe) - PK(X));
                 if ((k & 1) == 0) {
                     tacc = dND;                                                   // bit 15 (the rest is replaced below)
-                    tacc = s_bfi(0x40004000, dNDL, tacc);
-                    tacc = s_bfi(0x20002000, dEO, tacc);
-                    tacc = s_bfi(0x10001000, dFO, tacc);
+                    tacc = bfi_sgpr(0x40004000, dNDL, tacc);
+                    tacc = bfi_sgpr(0x20002000, dEO, tacc);
+                    tacc = bfi_sgpr(0x10001000, dFO, tacc);
                 } else {
-                    tacc = s_bfi(0x08000800, dND, tacc);
-                    tacc = s_bfi(0x04000400, dNDL, tacc);
-                    tacc = s_bfi(0x02000200, dEO, tacc);
-                    tacc = s_bfi(0x01000100, dFO, tacc);
+                    tacc = bfi_sgpr(0x08000800, dND, tacc);
+                    tacc = bfi_sgpr(0x04000400, dNDL, tacc);
+                    tacc = bfi_sgpr(0x02000200, dEO, tacc);
+                    tacc = bfi_sgpr(0x01000100, dFO, tacc);
                     if ((k & 3) == 1) tprev = tacc;                              // rows 4x, 4x+1
                     else plane[k / 4] = PK(__builtin_amdgcn_perm(tprev, tacc, 0x07030501));   // + rows 4x+2, 4x+3: top bytes of the halves
                 }
             }
-            E[k] = I32(n_max3f(PK(E[k]), PK(X), PK(X)));
-            F = I32(n_max3f(PK(Fe), PK(X), PK(X)));
+            E[k] = I32(pk_max3(PK(E[k]), PK(X), PK(X)));
+            F = I32(pk_max3(PK(Fe), PK(X), PK(X)));
             Hnew[k] = X;
         }
         if (TR) {
@@ -743,12 +691,12 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 #pragma unroll
             for (int k = 1; k < R; k += 2) {
                 const int k2 = k + 1 < R ? k + 1 : k;
-                cmx = n_max3f(cmx, PK(Hnew[k]), PK(Hnew[k2]));
+                cmx = pk_max3(cmx, PK(Hnew[k]), PK(Hnew[k2]));
                 cmn = n_min3f(cmn, PK(Hnew[k]), PK(Hnew[k2]));
             }
             const int inside = m_ult(jv, rlv);            // this lane's column lies in [0, rlen)
-            runmax = PK(n_bfi(inside, I32(n_max3f(runmax, cmx, cmx)), I32(runmax)));
-            runmin = PK(n_bfi(inside, I32(n_min3f(runmin, cmn, cmn)), I32(runmin)));
+            runmax = PK(bfi(inside, I32(pk_max3(runmax, cmx, cmx)), I32(runmax)));
+            runmin = PK(bfi(inside, I32(n_min3f(runmin, cmn, cmn)), I32(runmin)));
             runmax = PK(I32(runmax) + vExt); runmin = PK(I32(runmin) + vExt);      // into the next column's skew
         }
         const int mLast = m_eq(jv, rl1);                  // this lane is at column rlen-1
@@ -762,9 +710,9 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
                 int hl = Hnew[0];
 #pragma unroll
                 for (int k = 1; k < R; ++k) hl = (ks == k) ? Hnew[k] : hl;
-                res = n_bfi(mLast, hl, res);
+                res = bfi(mLast, hl, res);
             }
-        } else res = n_bfi(mLast, Hlast, res);
+        } else res = bfi(mLast, Hlast, res);
         if (s2_end) {
             if (PT && R > 16) {                           // the last row in every step from a long strip: a select chain (one per row; the
                 Hlast = Hnew[0];                          //  perm-table form's occupancy is worth several times that)
@@ -772,9 +720,9 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
                 for (int k = 1; k < R; ++k) Hlast = (ks == k) ? Hnew[k] : Hlast;
             }
             const v2s cand = PK(I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, Hlast) - __builtin_bit_cast(v2us, skewX))));   // nb + true H
-            const int imp = m_lt(bestrow, cand) & m_ult(jv, rlv);
-            bestrow = PK(n_bfi(imp, I32(cand), I32(bestrow)));
-            bestrowj = n_bfi(imp, jj, bestrowj);
+            const int imp = pk_lt(bestrow, cand) & m_ult(jv, rlv);
+            bestrow = PK(bfi(imp, I32(cand), I32(bestrow)));
+            bestrowj = bfi(imp, jj, bestrowj);
         }
         if (s1_end && __builtin_amdgcn_ballot_w64(mLast != 0) != 0) {
             const v2s Pv = PK(pack2(PvA, PvB));
@@ -783,18 +731,18 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const int er = g * R + k;
-                const int mreal = PT ? (er < qlu ? -1 : 0) : ~m_lt(PK(pack2(er, er)), Pv);
+                const int mreal = PT ? (er < qlu ? -1 : 0) : ~pk_lt(PK(pack2(er, er)), Pv);
                 vals[k] = PK((Hnew[k] + pack2((QP - er) * rx, (QP - er) * rx)) & mreal);       // rows compare in the form of the LAST row's offset (+ (QP - er) rx: inside the proven window, which holds the rows' offsets)
-                cm = n_max3f(cm, vals[k], vals[k]);
+                cm = pk_max3(cm, vals[k], vals[k]);
             }
 #pragma unroll
             for (int k = R - 1; k >= 0; --k) {
                 const int er = g * R + k;
-                krow = n_bfi(m_eq(vals[k], cm), pack2(er, er), krow);
+                krow = bfi(m_eq(vals[k], cm), pack2(er, er), krow);
             }
-            const int imp = m_lt(bestcol, cm) & mLast;
-            bestcol = PK(n_bfi(imp, I32(cm), I32(bestcol)));
-            bestcoli = n_bfi(imp, krow, bestcoli);
+            const int imp = pk_lt(bestcol, cm) & mLast;
+            bestcol = PK(bfi(imp, I32(cm), I32(bestcol)));
+            bestcoli = bfi(imp, krow, bestcoli);
         }
         jj = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, jj) + one2));
         skewX = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, skewX) + __builtin_bit_cast(v2us, vExt)));   // halves may be negative: per-half add
@@ -1036,8 +984,8 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
     };
     uint32_t *tw = TR ? tbuf + (((size_t)blockIdx.x * WAVES + wave) * 64 + lane) * (size_t)Tmax * TD : nullptr;
     auto step = [&](int bsel, int t) {
-        const int Hin = n_shift_up<G>(Hout, topX, g);
-        int F = n_shift_up<G>(Fout, topX, g);
+        const int Hin = group_shift_up<G>(Hout, topX, g);
+        int F = group_shift_up<G>(Fout, topX, g);
         // rows in blocks of HBLK: the diagonal sums of a block are formed before its rows overwrite the strip (one block: halving it
         // for R = 20 did not lower the allocator's register count)
         constexpr int HBLK = R;
@@ -1057,26 +1005,26 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
 #pragma unroll
         for (int k = k0; k < k0 + HBLK; ++k) {
             const int Fe = F;                                // (row offset: no subtraction)
-            const int H = I32(n_max3f(PK(Tpre[k - k0]), PK(E[k]), PK(Fe)));
+            const int H = I32(pk_max3(PK(Tpre[k - k0]), PK(E[k]), PK(Fe)));
             const int Xn = H - vC;
             if (TR) {     // ND, NDL, EO, FO: the sign of each difference, inserted at its bit of the row pair's byte (see pmx_nwsg16v_kernel)
                 const int dND = I32(PK(Tpre[k - k0]) - PK(H)), dNDL = I32(PK(Fe) - PK(H));
                 const int dEO = I32(PK(E[k]) - PK(Xn)), dFO = I32(PK(Fe) - PK(Xn));
                 if ((k & 1) == 0) {
                     tacc = dND;
-                    tacc = s_bfi(0x40004000, dNDL, tacc);
-                    tacc = s_bfi(0x20002000, dEO, tacc);
-                    tacc = s_bfi(0x10001000, dFO, tacc);
+                    tacc = bfi_sgpr(0x40004000, dNDL, tacc);
+                    tacc = bfi_sgpr(0x20002000, dEO, tacc);
+                    tacc = bfi_sgpr(0x10001000, dFO, tacc);
                 } else {
-                    tacc = s_bfi(0x08000800, dND, tacc);
-                    tacc = s_bfi(0x04000400, dNDL, tacc);
-                    tacc = s_bfi(0x02000200, dEO, tacc);
-                    tacc = s_bfi(0x01000100, dFO, tacc);
+                    tacc = bfi_sgpr(0x08000800, dND, tacc);
+                    tacc = bfi_sgpr(0x04000400, dNDL, tacc);
+                    tacc = bfi_sgpr(0x02000200, dEO, tacc);
+                    tacc = bfi_sgpr(0x01000100, dFO, tacc);
                     ty[k / 2] = tacc;                      // byte 1: pair A's rows k-1, k; byte 3: pair B's
                 }
             }
-            E[k] = I32(n_max3f(PK(E[k]), PK(Xn), PK(Xn)));
-            F = I32(n_max3f(PK(Fe), PK(Xn), PK(Xn)));
+            E[k] = I32(pk_max3(PK(E[k]), PK(Xn), PK(Xn)));
+            F = I32(pk_max3(PK(Fe), PK(Xn), PK(Xn)));
             X[k] = Xn;
         }
         }
@@ -1112,12 +1060,12 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
         // ---- captures (as in pmx_nwsg16v_kernel) ----
         const v2s jv = PK(jj);
         const int mLast = m_eq(jv, rl1);
-        res = n_bfi(mLast, Hout, res);
+        res = bfi(mLast, Hout, res);
         if (s2_end) {
             const v2s cand = PK(I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, Hout) - __builtin_bit_cast(v2us, skewX))));
-            const int imp = m_lt(bestrow, cand) & m_ult(jv, rlv);
-            bestrow = PK(n_bfi(imp, I32(cand), I32(bestrow)));
-            bestrowj = n_bfi(imp, jj, bestrowj);
+            const int imp = pk_lt(bestrow, cand) & m_ult(jv, rlv);
+            bestrow = PK(bfi(imp, I32(cand), I32(bestrow)));
+            bestrowj = bfi(imp, jj, bestrowj);
         }
         if (s1_end && __builtin_amdgcn_ballot_w64(mLast != 0) != 0) {
             v2s cm = PK(0); int krow = 0;
@@ -1126,16 +1074,16 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
             for (int k = 0; k < R; ++k) {
                 const int er = g * R + k;
                 vals[k] = PK(er >= P ? X[k] + pack2((QP - er) * rx, (QP - er) * rx) : 0);          // rows compare in the form of the last row's offset
-                cm = n_max3f(cm, vals[k], vals[k]);
+                cm = pk_max3(cm, vals[k], vals[k]);
             }
 #pragma unroll
             for (int k = R - 1; k >= 0; --k) {
                 const int er = g * R + k;
-                krow = n_bfi(m_eq(vals[k], cm), pack2(er, er), krow);
+                krow = bfi(m_eq(vals[k], cm), pack2(er, er), krow);
             }
-            const int imp = m_lt(bestcol, cm) & mLast;
-            bestcol = PK(n_bfi(imp, I32(cm), I32(bestcol)));
-            bestcoli = n_bfi(imp, krow, bestcoli);
+            const int imp = pk_lt(bestcol, cm) & mLast;
+            bestcol = PK(bfi(imp, I32(cm), I32(bestcol)));
+            bestcoli = bfi(imp, krow, bestcoli);
         }
         jj = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, jj) + one2));
         skewX = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, skewX) + __builtin_bit_cast(v2us, vExt)));
@@ -1344,8 +1292,8 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         pl = r;
     };
     auto step = [&](int bsel, int t) {
-        const int Hin = n_shift_up<G>(Hout, topX, g);
-        int F = n_shift_up<G>(Fout, topX, g);
+        const int Hin = group_shift_up<G>(Hout, topX, g);
+        int F = group_shift_up<G>(Fout, topX, g);
         int Tpre[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -1360,7 +1308,7 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int Fe = F;                                // (row offset: no subtraction)
-            const int H = I32(n_max3f(PK(Tpre[k]), PK(E[k]), PK(Fe)));
+            const int H = I32(pk_max3(PK(Tpre[k]), PK(E[k]), PK(Fe)));
             const int Xn = H - vC;
             if (TR) {
                 push(plane[k / 4], Tpre[k], H);      // ND
@@ -1368,8 +1316,8 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
                 push(plane[k / 4], E[k], Xn);        // EO
                 push(plane[k / 4], Fe, Xn);          // FO
             }
-            E[k] = I32(n_max3f(PK(E[k]), PK(Xn), PK(Xn)));
-            F = I32(n_max3f(PK(Fe), PK(Xn), PK(Xn)));
+            E[k] = I32(pk_max3(PK(E[k]), PK(Xn), PK(Xn)));
+            F = I32(pk_max3(PK(Fe), PK(Xn), PK(Xn)));
             X[k] = Xn;
         }
         if (TR) {
@@ -1386,12 +1334,12 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         // ---- captures (as in pmx_nwsg16v_kernel) ----
         const v2s jv = PK(jj);
         const int mLast = m_eq(jv, rl1);
-        res = n_bfi(mLast, Hout, res);
+        res = bfi(mLast, Hout, res);
         if (s2_end) {
             const v2s cand = PK(I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, Hout) - __builtin_bit_cast(v2us, skewX))));
-            const int imp = m_lt(bestrow, cand) & m_ult(jv, rlv);
-            bestrow = PK(n_bfi(imp, I32(cand), I32(bestrow)));
-            bestrowj = n_bfi(imp, jj, bestrowj);
+            const int imp = pk_lt(bestrow, cand) & m_ult(jv, rlv);
+            bestrow = PK(bfi(imp, I32(cand), I32(bestrow)));
+            bestrowj = bfi(imp, jj, bestrowj);
         }
         if (s1_end && __builtin_amdgcn_ballot_w64(mLast != 0) != 0) {
             v2s cm = PK(0); int krow = 0;
@@ -1399,18 +1347,18 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const int er = g * R + k;
-                const int mreal = ~m_lt(PK(pack2(er, er)), PK(pack2(PvA, PvB)));
+                const int mreal = ~pk_lt(PK(pack2(er, er)), PK(pack2(PvA, PvB)));
                 vals[k] = PK((X[k] + pack2((QP - er) * rx, (QP - er) * rx)) & mreal);
-                cm = n_max3f(cm, vals[k], vals[k]);
+                cm = pk_max3(cm, vals[k], vals[k]);
             }
 #pragma unroll
             for (int k = R - 1; k >= 0; --k) {
                 const int er = g * R + k;
-                krow = n_bfi(m_eq(vals[k], cm), pack2(er, er), krow);
+                krow = bfi(m_eq(vals[k], cm), pack2(er, er), krow);
             }
-            const int imp = m_lt(bestcol, cm) & mLast;
-            bestcol = PK(n_bfi(imp, I32(cm), I32(bestcol)));
-            bestcoli = n_bfi(imp, krow, bestcoli);
+            const int imp = pk_lt(bestcol, cm) & mLast;
+            bestcol = PK(bfi(imp, I32(cm), I32(bestcol)));
+            bestcoli = bfi(imp, krow, bestcoli);
         }
         jj = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, jj) + one2));
         skewX = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, skewX) + __builtin_bit_cast(v2us, vExt)));
@@ -1760,7 +1708,7 @@ int pmx_nwsgv_bias(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, 
         growth = (long long)(b.max_rlen + 2 * 64 + 4) * ext;           // (column skew: + ext per column)
     }
     const long long span = (hi - lo) + growth + 2LL * open + (m.max > 0 ? m.max : 0) + 2048;
-    if (m.min + open < 0 || m.max + open > 255 || span >= 31743) return 0;
+    if (m.min + open < 0 || m.max + open > 255 || span >= PK16_HI) return 0;
     return (int)(1536 - lo + open);
 }
 

@@ -1,0 +1,124 @@
+// pmx_pk16.h -- the packed-int16 and DPP lane primitives the fast kernels are built from.  gfx950 only.
+//
+// The exact window.  Packed kernels keep two int16 values per 32-bit register and take max3 / min3 of them with
+// v_pk_maximum3_f16 / v_pk_minimum3_f16, which compare the halves as f16.  Bit patterns in [1024, 31743] are the
+// positive normal f16 values, and for those the f16 order is the integer order of the patterns (sign 0, exponent above
+// mantissa); 1 .. 1023 are denormals, 31744 = 0x7C00 is +inf and above it lie the NaNs.  So on values that are 0 or
+// inside the window both instructions are an exact integer max3 / min3 (exhaustively checked on the chip:
+// profiles/microbench/max3_f16_int.hip), and the clamped v_pk_sub_u16 keeps them there: a result that would fall below
+// 0 stays 0, the "minus infinity" that loses every max3.  A pattern with the sign bit set (a pad score of -32768) is a
+// negative f16 and loses every max3 as well.  Each kernel biases its values into the window, and the host proves before
+// the launch that no live value can leave it (or flags the pairs whose best reaches PK16_RERUN_LIMIT for a 32-bit re-run).
+#pragma once
+#include <hip/hip_runtime.h>
+
+constexpr int PK16_LO = 1024;              // lowest pattern of the exact window
+constexpr int PK16_HI = 31743;             // highest pattern of the exact window (31744 = +inf)
+constexpr int PK16_SW_BIAS = 2048;         // stored form of a true 0 in the local kernels (pmx_sw16*.hip)
+constexpr int PK16_SW_BIAS2 = (PK16_SW_BIAS << 16) | PK16_SW_BIAS;
+// a local kernel's best (stored form) at or above this may have left the window (maxs: the matrix's largest score): the
+// pair is re-run in 32 bits
+#define PK16_RERUN_LIMIT(maxs) (PK16_HI + 1 - ((maxs) > 0 ? (maxs) : 0))
+
+typedef short v2s __attribute__((ext_vector_type(2)));
+typedef unsigned short v2us __attribute__((ext_vector_type(2)));
+typedef _Float16 v2h __attribute__((ext_vector_type(2)));
+
+#define PK(x)  __builtin_bit_cast(v2s, (int)(x))
+#define I32(x) __builtin_bit_cast(int, (x))
+
+// ---- packed int16 arithmetic ----
+
+// integer max3 on patterns in {0} U [PK16_LO, PK16_HI]: fmaximum(fmaximum(a, b), c) on v2f16 selects v_pk_maximum3_f16.
+// A builtin rather than inline asm: the hazard recognizer pads every inline-asm result with an s_nop.
+__device__ __forceinline__ v2s pk_max3(v2s a, v2s b, v2s c)
+{
+    const v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(v2h, a), __builtin_bit_cast(v2h, b)),
+                                                __builtin_bit_cast(v2h, c));
+    return __builtin_bit_cast(v2s, r);
+}
+__device__ __forceinline__ int pk_max3(int a, int b, int c)
+{
+    const v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(v2h, a), __builtin_bit_cast(v2h, b)),
+                                                __builtin_bit_cast(v2h, c));
+    return __builtin_bit_cast(int, r);
+}
+// the same instruction as inline asm, s_nop included (pmx_nwsg16_kernel, the first-generation nw / sg kernel)
+__device__ __forceinline__ v2s pk_max3_asm(v2s a, v2s b, v2s c)
+{
+    int r;
+    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(I32(a)), "v"(I32(b)), "v"(I32(c)));
+    return PK(r);
+}
+
+// v_pk_sub_u16 with clamp: saturates at 0
+__device__ __forceinline__ v2s pk_subus(v2s a, v2s b)
+{
+    return __builtin_bit_cast(v2s, __builtin_elementwise_sub_sat(__builtin_bit_cast(v2us, a), __builtin_bit_cast(v2us, b)));
+}
+__device__ __forceinline__ int pk_subus(int a, int b)
+{
+    return __builtin_bit_cast(int, __builtin_elementwise_sub_sat(__builtin_bit_cast(v2us, a), __builtin_bit_cast(v2us, b)));
+}
+
+// per half: 0xFFFF where a < b, else 0 (values below 32768)
+__device__ __forceinline__ int pk_lt(v2s a, v2s b) { const v2s sh = {15, 15}; return I32((a - b) >> sh); }
+__device__ __forceinline__ int pk_lt(int a, int b) { return pk_lt(PK(a), PK(b)); }
+
+// (m & a) | (~m & b) with the mask in a VGPR
+__device__ __forceinline__ int bfi(int m, int a, int b)
+{
+    int r;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
+    return r;
+}
+// the same with a wave-uniform mask in an SGPR
+__device__ __forceinline__ int bfi_sgpr(int m, int a, int b)
+{
+    int r;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(m), "v"(a), "v"(b));
+    return r;
+}
+
+// ---- unpacked u16 lanes: full-rate VOP2 on the low 16 bits ----
+
+__device__ __forceinline__ unsigned add_u16(unsigned a, unsigned b) { unsigned r; asm("v_add_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ unsigned sub_u16(unsigned a, unsigned b) { unsigned r; asm("v_sub_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ unsigned max_u16(unsigned a, unsigned b) { unsigned r; asm("v_max_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
+// ---- DPP lane moves inside groups of G lanes (G = 16: DPP row, G = 32 / 64: whole wave) ----
+
+// value of lane - 1 (row_shr:1 / wave_shr:1); a lane without a source (the first of its row or of the wave) gets `old`
+// (operands in the order of __builtin_amdgcn_update_dpp).  Group boundaries inside a row or a wave are the caller's.
+template <int G>
+__device__ __forceinline__ int lane_prev(int old, int x)
+{
+    if (G <= 16) return __builtin_amdgcn_update_dpp(old, x, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
+    return __builtin_amdgcn_update_dpp(old, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
+}
+template <int G>
+__device__ __forceinline__ int lane_prev(int x) { return lane_prev<G>(x, x); }
+
+// value of lane - 1 inside a G-lane group; member g == 0 of the group gets `neutral`.
+// IL (G == 8 only): two groups share a DPP row of 16 lanes, interleaved (lane = 2 g + (slot & 1) + 16 (slot >> 1)).
+// row_shr:2 then moves every group up by one lane, and the row's first two lanes -- lane 0 of both groups --
+// have no source and keep `neutral`: no select is needed.
+template <int G, bool IL = false>
+__device__ __forceinline__ int group_shift_up(int x, int neutral, int g)
+{
+    if (G == 1) return neutral;
+    if (IL) return __builtin_amdgcn_update_dpp(neutral, x, 0x112 /*row_shr:2*/, 0xF, 0xF, false);
+    const int r = lane_prev<G>(neutral, x);
+    return (G == 16 || G == 64) ? r : (g == 0 ? neutral : r);
+}
+
+// value of lane + 1 (row_shl:1 / wave_shl:1); a lane without a source keeps its own value
+template <int G>
+__device__ __forceinline__ int lane_next(int x)
+{
+    if (G <= 16) return __builtin_amdgcn_update_dpp(x, x, 0x101 /*row_shl:1*/, 0xF, 0xF, false);
+    return __builtin_amdgcn_update_dpp(x, x, 0x130 /*wave_shl:1*/, 0xF, 0xF, false);
+}
+// value of lane + 1 over the wave; lane 63 gets 0 (bound_ctrl).  Without an `old` operand the result is not tied to
+// the source's register: one v_mov_b32 less per move than lane_next<64>.
+__device__ __forceinline__ int lane_next_untied(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x130 /*wave_shl:1*/, 0xF, 0xF, true); }

@@ -18,28 +18,18 @@
 //     switched off on virtual columns).  Needs open >= extend >= 1.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
 
 #define SB 32768
 #define SNEG (-16384)
 
-__device__ __forceinline__ unsigned sa16(unsigned a, unsigned b) { unsigned r; asm("v_add_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned ss16(unsigned a, unsigned b) { unsigned r; asm("v_sub_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned sm16(unsigned a, unsigned b) { unsigned r; asm("v_max_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // (x0, x1) = (a < b) ? (t0, t1) : (f0, f1)      -- 16-bit unsigned compare, 32-bit selects
 __device__ __forceinline__ void sel2_lt(unsigned &x0, unsigned &x1, unsigned a, unsigned b,
                                         unsigned t0, unsigned t1, unsigned f0, unsigned f1)
 {
     asm("v_cmp_lt_u16_e32 vcc, %2, %3\n\tv_cndmask_b32_e32 %0, %6, %4, vcc\n\tv_cndmask_b32_e32 %1, %7, %5, vcc"
         : "=&v"(x0), "=&v"(x1) : "v"(a), "v"(b), "v"(t0), "v"(t1), "v"(f0), "v"(f1) : "vcc");
-}
-
-__device__ __forceinline__ unsigned s_up(unsigned x) { return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x138, 0xF, 0xF, false); }
-template <int G>
-__device__ __forceinline__ unsigned s_shift_up(unsigned x)
-{
-    if (G <= 16) return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x111, 0xF, 0xF, false);
-    return s_up(x);
 }
 
 struct SCand { int H, i, j; unsigned MS, L; };
@@ -167,8 +157,8 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
                     const unsigned (&w)[R], const unsigned (&wi)[R], int t) {
         const int jcol = t - g;
         const unsigned linc = (jcol >= 0 && jcol < rl) ? 1u : 0u;
-        unsigned Hin = s_shift_up<G>(Hout), HMSin = s_shift_up<G>(HMSout), HLin = s_shift_up<G>(HLout);
-        unsigned F = s_shift_up<G>(Fout), FMS = s_shift_up<G>(FMSout), FL = s_shift_up<G>(FLout);
+        unsigned Hin = lane_prev<G>(Hout), HMSin = lane_prev<G>(HMSout), HLin = lane_prev<G>(HLout);
+        unsigned F = lane_prev<G>(Fout), FMS = lane_prev<G>(FMSout), FL = lane_prev<G>(FLout);
         if (g == 0) {                            // top boundary of column t
             const unsigned topH = (unsigned)(SB + (row_pen ? -(open + t * ext) : 0));
             const unsigned topL = row_pen ? (unsigned)(t + 1) : 0u;
@@ -180,9 +170,9 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
             const unsigned d = (k == 0) ? diag0 : Hold[k - 1];
             const unsigned dMS = (k == 0) ? diagMS0 : MSold[k - 1];
             const unsigned dL = (k == 0) ? diagL0 : Lold[k - 1];
-            const unsigned Tt = sa16(d, w[k]);
+            const unsigned Tt = add_u16(d, w[k]);
             const unsigned TMS = dMS + wi[k], TL = dL + linc;
-            unsigned H = sm16(sm16(Tt, E[k]), F);
+            unsigned H = max_u16(max_u16(Tt, E[k]), F);
             unsigned xMS, xL, hMS, hL;
             sel2_lt(xMS, xL, F, H, EMS[k], EL[k], FMS, FL);        // not from F -> E's stats, else F's
             sel2_lt(hMS, hL, Tt, H, xMS, xL, TMS, TL);             // not diagonal -> gap stats, else diagonal's
@@ -190,16 +180,16 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
                 unsigned zMS, zL;
                 sel2_lt(zMS, zL, (unsigned)SB, H, hMS, hL, 0u, 0u);
                 hMS = zMS; hL = zL;
-                H = sm16(H, (unsigned)SB);
+                H = max_u16(H, (unsigned)SB);
             }
-            const unsigned Ho = ss16(H, vOpen), Ee = ss16(E[k], vExt), Fe = ss16(F, vExt);
+            const unsigned Ho = sub_u16(H, vOpen), Ee = sub_u16(E[k], vExt), Fe = sub_u16(F, vExt);
             unsigned eMS, eL, fMS, fL;
             sel2_lt(eMS, eL, Ee, Ho, hMS, hL, EMS[k], EL[k]);      // E opened from H
             sel2_lt(fMS, fL, Fe, Ho, hMS, hL, FMS, FL);            // F opened from H
             EMS[k] = eMS; EL[k] = eL + 1u;
             FMS = fMS; FL = fL + 1u;
-            E[k] = sm16(Ee, Ho);
-            F = sm16(Fe, Ho);
+            E[k] = max_u16(Ee, Ho);
+            F = max_u16(Fe, Ho);
             Hnew[k] = H; MSnew[k] = hMS; Lnew[k] = hL;
         }
         diag0 = Hin; diagMS0 = HMSin; diagL0 = HLin;
@@ -210,7 +200,7 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         if (SW) {
             unsigned cm = Hnew[0] & 0xFFFFu;
 #pragma unroll
-            for (int k = 1; k < R; ++k) cm = sm16(cm, Hnew[k]) & 0xFFFFu;
+            for (int k = 1; k < R; ++k) cm = max_u16(cm, Hnew[k]) & 0xFFFFu;
             const bool imp = cm > swbest;
             swbest = imp ? cm : swbest;
             swcol = imp ? (unsigned)jcol : swcol;

@@ -19,37 +19,8 @@
 //     (profile arm) the planes are built once per 4-wave workgroup.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
-
-typedef short p_v2s __attribute__((ext_vector_type(2)));
-typedef unsigned short p_v2u __attribute__((ext_vector_type(2)));
-typedef _Float16 p_v2h __attribute__((ext_vector_type(2)));
-#define P_PK(x)  __builtin_bit_cast(p_v2s, (int)(x))
-#define P_I32(x) __builtin_bit_cast(int, (x))
-
-__device__ __forceinline__ int p_max3(int a, int b, int c)       // v_pk_maximum3_f16: exact integer max3 on [1024, 31743] patterns
-{
-    const p_v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(p_v2h, a), __builtin_bit_cast(p_v2h, b)),
-                                                  __builtin_bit_cast(p_v2h, c));
-    return __builtin_bit_cast(int, r);
-}
-__device__ __forceinline__ int p_lt(int a, int b)                // per half: 0xFFFF where a < b (values below 32768)
-{
-    const p_v2s sh = {15, 15};
-    return P_I32((P_PK(a) - P_PK(b)) >> sh);
-}
-__device__ __forceinline__ int p_bfi(int m, int a, int b)        // (m & a) | (~m & b)
-{
-    int r;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
-    return r;
-}
-template <int G>
-__device__ __forceinline__ int p_shift_up(int x)                 // value of lane - 1 (group boundaries are fixed up by the caller)
-{
-    if (G <= 16) return __builtin_amdgcn_update_dpp(x, x, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
-    return __builtin_amdgcn_update_dpp(x, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-}
 
 struct PCand { int H; int i; int jL; int MS; };                  // true score, row, column | length << 16, matches | similar << 16
 
@@ -231,8 +202,8 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
         // tie with the F chain when open == ext, and then has to carry the same length (row index + 1)
         const int linc = jcol < 0 ? (col_pen ? one2 : 0)
                                   : ((jcol < rlA ? 1 : 0) | (jcol < rlB ? 0x10000 : 0));
-        int Hin = p_shift_up<G>(Hout), HMin = p_shift_up<G>(HMout), HSin = p_shift_up<G>(HSout), HLin = p_shift_up<G>(HLout);
-        int F = p_shift_up<G>(Fout), fM = p_shift_up<G>(FMout), fS = p_shift_up<G>(FSout), fL = p_shift_up<G>(FLout);
+        int Hin = lane_prev<G>(Hout), HMin = lane_prev<G>(HMout), HSin = lane_prev<G>(HSout), HLin = lane_prev<G>(HLout);
+        int F = lane_prev<G>(Fout), fM = lane_prev<G>(FMout), fS = lane_prev<G>(FSout), fL = lane_prev<G>(FLout);
         if (g == 0) {                                 // top boundary of column t (F^ into row 0 = X of the row above)
             Hin = topX; HMin = 0; HSin = 0; HLin = topL;
             F = topX; fM = 0; fS = 0; fL = topL + one2;
@@ -243,10 +214,10 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
             const unsigned selw = 0x0C000C00u | (unsigned)(k & 3) | ((4u + (unsigned)(k & 3)) << 16);
             int s, im, is;
             if (ML) {
-                const p_v2u fifteen = {15, 15}, one_ = {1, 1};
+                const v2us fifteen = {15, 15}, one_ = {1, 1};
                 s = wml[bsel][k];
-                is = P_I32(__builtin_bit_cast(p_v2s, __builtin_bit_cast(p_v2u, P_PK(vOpenP) - P_PK(s)) >> fifteen));            // score + open > open
-                im = P_I32(__builtin_bit_cast(p_v2s, (__builtin_bit_cast(p_v2u, qc[k] ^ rc2[bsel]) - one_) >> fifteen));         // equal letter codes
+                is = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, PK(vOpenP) - PK(s)) >> fifteen));                     // score + open > open
+                im = I32(__builtin_bit_cast(v2s, (__builtin_bit_cast(v2us, qc[k] ^ rc2[bsel]) - one_) >> fifteen));              // equal letter codes
             } else {
                 s = __builtin_amdgcn_perm(wsc[bsel][1][k / 4], wsc[bsel][0][k / 4], selw);
                 im = __builtin_amdgcn_perm(wim[bsel][1][k / 4], wim[bsel][0][k / 4], selw);
@@ -261,18 +232,18 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int Fe = F - vExt;
-            const int H = p_max3(T[k], E[k], Fe);
+            const int H = pk_max3(T[k], E[k], Fe);
             const int Xn = H - vC;
-            const int mNDL = p_lt(Fe, H);                              // not from F -> E's statistics, else F's
-            const int xM = p_bfi(mNDL, eM[k], fM), xS = p_bfi(mNDL, eS[k], fS), xL = p_bfi(mNDL, eL[k], fL);
-            const int mND = p_lt(T[k], H);                             // not diagonal -> gap statistics, else the diagonal's
-            const int nM = p_bfi(mND, xM, TM[k]), nS = p_bfi(mND, xS, TS[k]), nL = p_bfi(mND, xL, TL[k]);
-            const int mEO = p_lt(E[k], Xn);                            // E of the next column opened from H
-            eM[k] = p_bfi(mEO, nM, eM[k]); eS[k] = p_bfi(mEO, nS, eS[k]); eL[k] = p_bfi(mEO, nL, eL[k]) + one2;
-            const int mFO = p_lt(Fe, Xn);                              // F of the next row opened from H
-            fM = p_bfi(mFO, nM, fM); fS = p_bfi(mFO, nS, fS); fL = p_bfi(mFO, nL, fL) + one2;
-            E[k] = p_max3(E[k], Xn, Xn);
-            F = p_max3(Fe, Xn, Xn);
+            const int mNDL = pk_lt(Fe, H);                             // not from F -> E's statistics, else F's
+            const int xM = bfi(mNDL, eM[k], fM), xS = bfi(mNDL, eS[k], fS), xL = bfi(mNDL, eL[k], fL);
+            const int mND = pk_lt(T[k], H);                            // not diagonal -> gap statistics, else the diagonal's
+            const int nM = bfi(mND, xM, TM[k]), nS = bfi(mND, xS, TS[k]), nL = bfi(mND, xL, TL[k]);
+            const int mEO = pk_lt(E[k], Xn);                           // E of the next column opened from H
+            eM[k] = bfi(mEO, nM, eM[k]); eS[k] = bfi(mEO, nS, eS[k]); eL[k] = bfi(mEO, nL, eL[k]) + one2;
+            const int mFO = pk_lt(Fe, Xn);                             // F of the next row opened from H
+            fM = bfi(mFO, nM, fM); fS = bfi(mFO, nS, fS); fL = bfi(mFO, nL, fL) + one2;
+            E[k] = pk_max3(E[k], Xn, Xn);
+            F = pk_max3(Fe, Xn, Xn);
             X[k] = Xn; hM[k] = nM; hS[k] = nS; hL[k] = nL;
         }
         diag0 = Hin; dM0 = HMin; dS0 = HSin; dL0 = HLin;

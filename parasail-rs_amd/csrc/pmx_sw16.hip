@@ -38,56 +38,13 @@
 // can strictly exceed the true maximum nor precede its first occurrence in column-major order.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-#define PK(x)  __builtin_bit_cast(v2s, (int)(x))
-#define I32(x) __builtin_bit_cast(int, (x))
 
 __device__ __forceinline__ v2s pk_adds(v2s a, v2s b) { return __builtin_elementwise_add_sat(a, b); }
 __device__ __forceinline__ v2s pk_subs(v2s a, v2s b) { return __builtin_elementwise_sub_sat(a, b); }
 __device__ __forceinline__ v2s pk_max(v2s a, v2s b) { return __builtin_elementwise_max(a, b); }
 
-// value of lane-1 inside a G-lane group; lane 0 of the group receives `neutral`.
-// IL (G == 8 only): two groups share a DPP row of 16 lanes, interleaved (lane = 2 g + (slot & 1) + 16 (slot >> 1)).
-// row_shr:2 then moves every group up by one lane, and the row's first two lanes -- lane 0 of both groups --
-// have no source and keep `neutral`: no select is needed.
-template <int G, bool IL = false>
-__device__ __forceinline__ int group_shift_up(int x, int neutral, int g)
-{
-    if (G == 1) return neutral;
-    if (IL) return __builtin_amdgcn_update_dpp(neutral, x, 0x112 /*row_shr:2*/, 0xF, 0xF, false);
-    if (G <= 16) {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
-        if (G < 16) r = (g == 0) ? neutral : r;
-        return r;
-    } else {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-        if (G < 64) r = (g == 0) ? neutral : r;
-        return r;
-    }
-}
-
-#define NEG16 ((short)-32768)
-#define M3_BIAS 2048
-#define M3_BIAS2 ((M3_BIAS << 16) | M3_BIAS)
-#define M3_LIMIT(maxs) (31744 - ((maxs) > 0 ? (maxs) : 0))     // a best at or above this may have left the exact range
-
-typedef unsigned short v2us __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2s pk_subus(v2s a, v2s b)      // v_pk_sub_u16 clamp: saturates at 0
-{
-    return __builtin_bit_cast(v2s, __builtin_elementwise_sub_sat(__builtin_bit_cast(v2us, a), __builtin_bit_cast(v2us, b)));
-}
-typedef _Float16 v2h __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2s pk_max3f(v2s a, v2s b, v2s c)   // integer max3 on {0} U [1024, 31743] patterns
-{
-    // fmaximum(fmaximum(a, b), c) on v2f16 selects v_pk_maximum3_f16 on gfx950.  A builtin rather
-    // than inline asm: the hazard recognizer pads every inline-asm result with an s_nop.
-    const v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(v2h, a), __builtin_bit_cast(v2h, b)),
-                                                __builtin_bit_cast(v2h, c));
-    return __builtin_bit_cast(v2s, r);
-}
 #ifndef PMX_SHARE_PERIOD
 #define PMX_SHARE_PERIOD 16     // steps between two exchanges of the group's score bound (a power of two; see share_bound)
 #endif
@@ -131,7 +88,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
     const int lane = threadIdx.x;
-    constexpr bool IL = G == 8 && VAR != 7;     // interleaved 8-lane groups (see group_shift_up); the trace layout keeps plain groups
+    constexpr bool IL = G == 8 && VAR != 7;     // interleaved 8-lane groups (see group_shift_up in pmx_pk16.h); the trace layout keeps plain groups
     const int g = IL ? (lane % 16) / 2 : lane % G;
     const int slot = IL ? (lane / 16) * 2 + (lane & 1) : lane / G;
     const int PROF_STRIDE = PT ? 0 : msize * QP * EB;   // bytes per pair
@@ -295,9 +252,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 
     const v2s vOpen = PK((open & 0xFFFF) | (open << 16));
     const v2s vExt = PK((ext & 0xFFFF) | (ext << 16));
-    typedef unsigned short v2u __attribute__((ext_vector_type(2)));
     // "zero" of the value domain: -32768 for the saturating-int16 variant, BIAS for the max3 variant
-    constexpr int ZERO2 = M3 ? M3_BIAS2 : FLOOR2;
+    constexpr int ZERO2 = M3 ? PK16_SW_BIAS2 : FLOOR2;
     const v2s vZero = PK(ZERO2);
 
     // Two copies of the H strip: a step reads one and writes the other, so the loop-carried
@@ -336,8 +292,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     const size_t t_ss = 4;
     uint32_t *tw = TR ? tbuf + ((size_t)blockIdx.x * Tmax) * 256 + (size_t)lane * Tmax * 4 : nullptr;
     auto push = [&](v2s &pl, v2s a, v2s b) {        // pl = 2 * pl + (a < b), per half
-        const v2u fifteen = {15, 15};
-        const int bit = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2u, a - b) >> fifteen));
+        const v2us fifteen = {15, 15};
+        const int bit = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, a - b) >> fifteen));
         int r;
         asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(I32(pl)), "v"(0x00020002), "v"(bit));
         pl = PK(r);
@@ -375,7 +331,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             v2s H;
             if (SK) {
                 const v2s Fe = PK(I32(F) - I32(vExt));            // F~ of this row (F^ - ext), also F^'s extension
-                H = pk_max3f(Tpre[k], E[k], Fe);
+                H = pk_max3(Tpre[k], E[k], Fe);
                 const v2s X = PK(I32(H) - I32(vC));
                 if (TR) {
                     push(plane[k / 4], Tpre[k], H);      // ND
@@ -383,38 +339,36 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
                     push(plane[k / 4], E[k], X);         // EO
                     push(plane[k / 4], Fe, X);           // FO
                 }
-                E[k] = pk_max3f(E[k], X, X);
-                F = pk_max3f(Fe, X, PK(Zv));
+                E[k] = pk_max3(E[k], X, X);
+                F = pk_max3(Fe, X, PK(Zv));
                 Hnew[k] = X;
                 // the column maximum, the running best and the saved strip all live in the X form (H~ - (open - ext)):
                 // the strip itself is what gets saved, no second copy of the column is kept in registers
-                if (k & 1) colmax = pk_max3f(colmax, Hnew[k - 1], X);
-                else if (k == R - 1) colmax = pk_max3f(colmax, X, best);      // odd R: the spare operand folds the running best in
+                if (k & 1) colmax = pk_max3(colmax, Hnew[k - 1], X);
+                else if (k == R - 1) colmax = pk_max3(colmax, X, best);       // odd R: the spare operand folds the running best in
             } else if (V2) {
                 // Same domain as the max3 variant, but the strips carry H - open and the profile
                 // carries score + open (>= 0), so add and subtract never carry or borrow across
                 // the 16-bit halves and run as full-rate 32-bit VOP2 (v_add_u32 / v_sub_u32).
-                H = pk_max3f(Tpre[k], E[k], F);
+                H = pk_max3(Tpre[k], E[k], F);
                 const v2s Ho = PK(I32(H) - I32(vOpen));
-                E[k] = pk_max3f(Epre[k], Ho, Ho);
-                F = pk_max3f(PK(I32(F) - I32(vExt)), Ho, vZero);
+                E[k] = pk_max3(Epre[k], Ho, Ho);
+                F = pk_max3(PK(I32(F) - I32(vExt)), Ho, vZero);
                 Hnew[k] = Ho;
                 Hcur[k] = H;
-                if (k & 1) colmax = pk_max3f(colmax, Hcur[k - 1], H);
-                else if (k == R - 1) colmax = pk_max3f(colmax, H, H);
+                if (k & 1) colmax = pk_max3(colmax, Hcur[k - 1], H);
+                else if (k == R - 1) colmax = pk_max3(colmax, H, H);
             } else if (M3) {
-                // Biased unsigned lanes: every live value is 0 or in [1024, 31743], where the bit
-                // patterns of non-negative f16 order like integers, so v_pk_maximum3_f16 is an exact
-                // integer max3 (profiles/microbench/max3_f16_int.hip).  A pad score of -32768 sets the
-                // sign bit: a negative f16 that loses against everything.
-                const v2s Tt = PK(I32(__builtin_bit_cast(v2u, d) + __builtin_bit_cast(v2u, s)));
-                H = pk_max3f(Tt, E[k], F);
+                // Biased unsigned lanes: every live value is 0 or in the exact window of pmx_pk16.h.
+                // A pad score of -32768 sets the sign bit: a negative f16 that loses against everything.
+                const v2s Tt = PK(I32(__builtin_bit_cast(v2us, d) + __builtin_bit_cast(v2us, s)));
+                H = pk_max3(Tt, E[k], F);
                 const v2s Ho = pk_subus(H, vOpen);
-                E[k] = pk_max3f(pk_subus(E[k], vExt), Ho, Ho);
-                F = pk_max3f(pk_subus(F, vExt), Ho, vZero);
+                E[k] = pk_max3(pk_subus(E[k], vExt), Ho, Ho);
+                F = pk_max3(pk_subus(F, vExt), Ho, vZero);
                 Hnew[k] = H;
-                if (k & 1) colmax = pk_max3f(colmax, Hnew[k - 1], H);
-                else if (k == R - 1) colmax = pk_max3f(colmax, H, H);
+                if (k & 1) colmax = pk_max3(colmax, Hnew[k - 1], H);
+                else if (k == R - 1) colmax = pk_max3(colmax, H, H);
             } else {
                 H = pk_adds(d, s);
                 H = pk_max(H, E[k]);
@@ -439,7 +393,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         Fout = I32(F);
         // end-position bookkeeping: strictly greater than the lane's best so far?
         constexpr bool FOLDED = SK && (R & 1);          // colmax already holds max(best, column maximum)
-        const v2s nb = FOLDED ? colmax : M3 ? pk_max3f(best, colmax, colmax) : pk_max(best, colmax);
+        const v2s nb = FOLDED ? colmax : M3 ? pk_max3(best, colmax, colmax) : pk_max(best, colmax);
         int m;   // 0xFFFF in every half whose column maximum strictly exceeds the best so far
         {
             const v2s dd = FOLDED ? (best - nb) : M3 ? (best - colmax) : pk_subs(best, colmax);   // negative exactly where colmax > best
@@ -453,11 +407,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bestcol) : "v"(m), "s"((t & 0xFFFF) * 0x00010001), "v"(bestcol));   // the step index is uniform: SGPR operand
             fake &= ~m;
 #pragma unroll
-            for (int k = 0; k < R; ++k) {
-                int hs;
-                asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(hs) : "v"(m), "v"(I32((V2 && !SK) ? Hcur[k] : Hnew[k])), "v"(I32(Hsave[k])));
-                Hsave[k] = PK(hs);
-            }
+            for (int k = 0; k < R; ++k) Hsave[k] = PK(bfi(m, I32((V2 && !SK) ? Hcur[k] : Hnew[k]), I32(Hsave[k])));
         }
         best = SK ? PK(I32(nb) + I32(vExt)) : nb;                           // SK: carried into the next column's skew
         if (SK) Zv += I32(vExt);
@@ -502,13 +452,12 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 #pragma unroll
         for (int off = G / 2; off >= 1; off >>= 1) {
             const int o = __shfl_xor(v, (IL ? 2 : 1) * off, 64);
-            v = I32(pk_max3f(PK(v), PK(o), PK(o)));
+            v = pk_max3(v, o, o);
         }
         const int fresh = v - 0x00010001 + skew0;
         const int old = vprev ? vprev + ((SHP * ext) & 0xFFFF) * 0x00010001 + skew0 : 0;        // (0: below every live value)
-        const v2s nbest = pk_max3f(best, PK(fresh), PK(old));
-        const v2s sh = {15, 15};
-        fake |= I32((best - nbest) >> sh);                  // halves that were raised
+        const v2s nbest = pk_max3(best, PK(fresh), PK(old));
+        fake |= pk_lt(best, nbest);                         // halves that were raised
         best = nbest;
         vprev = v;
     };
@@ -544,7 +493,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             if ((short)(I32(Hsave[k]) >> 16) == tB) kB = k;
         }
         const int unskew = SK ? (G - g + T) * ext - (open - ext) : 0;
-        const unsigned sA = (unsigned)(bA - unskew - (M3 ? M3_BIAS : -32768)), sB = (unsigned)(bB - unskew - (M3 ? M3_BIAS : -32768));
+        const unsigned sA = (unsigned)(bA - unskew - (M3 ? PK16_SW_BIAS : -32768)), sB = (unsigned)(bB - unskew - (M3 ? PK16_SW_BIAS : -32768));
         const unsigned rA = g * R + kA, rB = g * R + kB;
         keyA = ((unsigned long long)sA << 32) | ((0xFFFFu - cA) << 16) | (0xFFFFu - rA);
         keyB = ((unsigned long long)sB << 32) | ((0xFFFFu - cB) << 16) | (0xFFFFu - rB);
@@ -569,7 +518,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
                 rec.score = (int)(key >> 32);
                 rec.end_ref = 0xFFFF - (int)((key >> 16) & 0xFFFF);
                 rec.end_query = 0xFFFF - (int)(key & 0xFFFF);
-                if (M3) rec.flags = (rec.score + M3_BIAS >= limit) ? PMX_FLAG_RERUN : 0;   // left the exact range: redo in 32 bits
+                if (M3) rec.flags = (rec.score + PK16_SW_BIAS >= limit) ? PMX_FLAG_RERUN : 0; // left the exact range: redo in 32 bits
                 else rec.flags = rec.score > 32767 ? PMX_FLAG_SATURATED : 0;
                 if (rec.score > sat_above) rec.flags |= PMX_FLAG_SATURATED;
                 if (PT && ((wild >> h) & 1)) {                                              // wildcard in the query: redo with the LDS profile
@@ -605,7 +554,7 @@ static int launch_one(const PmxBatch &b, const PmxDevMatrix &m, int open, int ex
     }
     hipLaunchKernelGGL((pmx_sw16_kernel<G, R, VAR>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                       m.msize, open, ext, RP, b.q_shared, M3_LIMIT(m.max) - (VAR >= 4 ? (b.max_rlen + 2 * G + 4) * ext : 0), b.perm,
+                       m.msize, open, ext, RP, b.q_shared, PK16_RERUN_LIMIT(m.max) - (VAR >= 4 ? (b.max_rlen + 2 * G + 4) * ext : 0), b.perm,
                        n_dev, b.retry_list, b.retry_count, b.sat_above > 0 ? b.sat_above : 2147483647, tbuf, Tmax, d_out);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return -(int)e;
@@ -627,7 +576,7 @@ static bool sw16_trace_ok(const PmxBatch &b, const PmxDevMatrix &m, int open, in
     if (m.msize > PMX_MAX_FAST_MSIZE || open < ext || ext < 0 || open > 1024 || b.max_rlen > 30000 || b.q_shared || b.perm) return false;
     if (m.min < -1024 || m.max > 2048 || m.min + open < 0 || open + ext > 1024 || m.max + open > 255) return false;
     const long long feasible = (long long)(b.max_qlen < b.max_rlen ? b.max_qlen : b.max_rlen) * (m.max > 0 ? m.max : 0);
-    return feasible + M3_BIAS < (long long)M3_LIMIT(m.max) - (long long)(b.max_rlen + 2 * 64 + 4) * ext;
+    return feasible + PK16_SW_BIAS < (long long)PK16_RERUN_LIMIT(m.max) - (long long)(b.max_rlen + 2 * 64 + 4) * ext;
 }
 int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int *variant, int *Tmax, size_t *trace_bytes)
 {
@@ -687,7 +636,7 @@ int pmx_launch_sw16(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
     // score can reach the correspondingly lower re-run limit
     const long long feasible = (long long)(b.max_qlen < b.max_rlen ? b.max_qlen : b.max_rlen) * (m.max > 0 ? m.max : 0);
     const bool sk = var == 2 && open >= ext && !pmx_env("PMX_SW16_NO_SKEW") &&
-                    feasible + M3_BIAS < (long long)M3_LIMIT(m.max) - (long long)(b.max_rlen + 2 * 64 + 4) * ext;
+                    feasible + PK16_SW_BIAS < (long long)PK16_RERUN_LIMIT(m.max) - (long long)(b.max_rlen + 2 * 64 + 4) * ext;
     // alphabets of <= 4 letters (+ wildcard): no LDS profile, the v_perm looks the score up (see PT in the kernel)
     const bool pt = sk && u8ok && m.msize <= 5 && b.retry_list && b.retry_count && !b.q_has_wildcard && !pmx_env("PMX_SW16_NO_PERMTABLE");
     // one shared query (profile arm) with a real LDS profile: the workgroup-shared-profile kernel (pmx_sw16q.hip)

@@ -11,36 +11,8 @@
 // pmx_sw16.hip's skewed variants.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
-
-typedef short m_v2s __attribute__((ext_vector_type(2)));
-typedef _Float16 m_v2h __attribute__((ext_vector_type(2)));
-#define M_PK(x)  __builtin_bit_cast(m_v2s, (int)(x))
-#define M_I32(x) __builtin_bit_cast(int, (x))
-#define M_BIASx 2048
-#define M_BIAS2x ((M_BIASx << 16) | M_BIASx)
-#define M_LIMITx(maxs) (31744 - ((maxs) > 0 ? (maxs) : 0))
-
-__device__ __forceinline__ int m_max3(int a, int b, int c)
-{
-    const m_v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(m_v2h, a), __builtin_bit_cast(m_v2h, b)),
-                                                  __builtin_bit_cast(m_v2h, c));
-    return __builtin_bit_cast(int, r);
-}
-// value of lane-1 inside a G-lane group; lane 0 of the group receives `neutral`.
-template <int G>
-__device__ __forceinline__ int m_shift_up(int x, int neutral, int g)
-{
-    if (G <= 16) {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
-        if (G < 16) r = (g == 0) ? neutral : r;
-        return r;
-    } else {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-        if (G < 64) r = (g == 0) ? neutral : r;
-        return r;
-    }
-}
 
 // TR: also writes the 4-bit traceback cells (bits and layout of pmx_nwsg16v_kernel<..,true>; rows top-aligned).
 template <int G, int R, bool TR>
@@ -113,14 +85,14 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     auto pack2 = [](int a, int b) -> int { return (a & 0xFFFF) | (b << 16); };
     const int vOpen = pack2(open, open), vExt = pack2(ext, ext), vC = vOpen - vExt;
     const int skew0 = (((G - g) * ext) & 0xFFFF) * 0x00010001;       // this lane's first column is j = -g
-    const int vInitH = M_BIAS2x - vOpen + skew0;
+    const int vInitH = PK16_SW_BIAS2 - vOpen + skew0;
 
     int X[R], E[R], Hsave[R];
 #pragma unroll
-    for (int k = 0; k < R; ++k) { X[k] = vInitH; E[k] = vInitH; Hsave[k] = M_BIAS2x; }
-    int best = M_BIAS2x + skew0 - vC;            // X form
+    for (int k = 0; k < R; ++k) { X[k] = vInitH; E[k] = vInitH; Hsave[k] = PK16_SW_BIAS2; }
+    int best = PK16_SW_BIAS2 + skew0 - vC;       // X form
     int bestcol = g * 0x00010001;               // step of the first strict improvement (column = step - g)
-    int Zv = M_BIAS2x + skew0 + vExt;            // "F^ = 0" of the current column; += ext per step
+    int Zv = PK16_SW_BIAS2 + skew0 + vExt;       // "F^ = 0" of the current column; += ext per step
     int Hout = Zv - vExt - vOpen, Fout = Zv - vExt;
     int diag0 = vInitH;
 
@@ -137,16 +109,15 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     const size_t t_ss = 4;
     uint32_t *tw = TR ? tbuf + ((size_t)blockIdx.x * Tmax) * 256 + (size_t)lane * Tmax * 4 : nullptr;
     auto push = [&](int &pl, int a, int b) {          // pl = 2 * pl + (a < b), per half
-        typedef unsigned short u2 __attribute__((ext_vector_type(2)));
-        const u2 fifteen = {15, 15};
-        const int bit = M_I32(__builtin_bit_cast(m_v2s, __builtin_bit_cast(u2, M_PK(a) - M_PK(b)) >> fifteen));
+        const v2us fifteen = {15, 15};
+        const int bit = I32(__builtin_bit_cast(v2s, __builtin_bit_cast(v2us, PK(a) - PK(b)) >> fifteen));
         int r;
         asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(pl), "v"(0x00020002), "v"(bit));
         pl = r;
     };
     auto step = [&](int bsel, int t) {
-        const int Hin = m_shift_up<G>(Hout, Zv - vOpen, g);
-        int F = m_shift_up<G>(Fout, Zv, g);
+        const int Hin = group_shift_up<G>(Hout, Zv - vOpen, g);
+        int F = group_shift_up<G>(Fout, Zv, g);
         int T[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -162,7 +133,7 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int Fe = F - vExt;
-            const int H = m_max3(T[k], E[k], Fe);
+            const int H = pk_max3(T[k], E[k], Fe);
             const int Xn = H - vC;
             if (TR) {
                 push(plane[k / 4], T[k], H);         // ND
@@ -170,11 +141,11 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
                 push(plane[k / 4], E[k], Xn);        // EO
                 push(plane[k / 4], Fe, Xn);          // FO
             }
-            E[k] = m_max3(E[k], Xn, Xn);
-            F = m_max3(Fe, Xn, Zv);
+            E[k] = pk_max3(E[k], Xn, Xn);
+            F = pk_max3(Fe, Xn, Zv);
             X[k] = Xn;
-            if (k & 1) colmax = (k == 1) ? m_max3(X[0], Xn, Xn) : m_max3(colmax, X[k - 1], Xn);
-            else if (k == R - 1) colmax = m_max3(colmax, Xn, Xn);
+            if (k & 1) colmax = (k == 1) ? pk_max3(X[0], Xn, Xn) : pk_max3(colmax, X[k - 1], Xn);
+            else if (k == R - 1) colmax = pk_max3(colmax, Xn, Xn);
         }
         if (TR) {
             uint4 w4;
@@ -187,17 +158,12 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
         diag0 = Hin;
         Hout = X[R - 1];
         Fout = F;
-        const int nb = m_max3(best, colmax, colmax);
-        const m_v2s sh = {15, 15};
-        const int m = M_I32((M_PK(best) - M_PK(colmax)) >> sh);     // 0xFFFF where the column maximum strictly exceeds the best so far
+        const int nb = pk_max3(best, colmax, colmax);
+        const int m = pk_lt(best, colmax);                     // 0xFFFF where the column maximum strictly exceeds the best so far
         if (__builtin_amdgcn_ballot_w64(m != 0) != 0) {            // (wave-uniform: most steps of a long sweep improve no lane's best)
             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bestcol) : "v"(m), "s"((t & 0xFFFF) * 0x00010001), "v"(bestcol));
 #pragma unroll
-            for (int k = 0; k < R; ++k) {
-                int hs;
-                asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(hs) : "v"(m), "v"(X[k]), "v"(Hsave[k]));
-                Hsave[k] = hs;
-            }
+            for (int k = 0; k < R; ++k) Hsave[k] = bfi(m, X[k], Hsave[k]);
         }
         best = nb + vExt;
         Zv += vExt;
@@ -240,7 +206,7 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
             if ((short)(Hsave[k] >> 16) == tB) kB = k;
         }
         const int unskew = (G - g + T_) * ext - (open - ext);
-        const unsigned sA = (unsigned)(bA - unskew - M_BIASx), sB = (unsigned)(bB - unskew - M_BIASx);
+        const unsigned sA = (unsigned)(bA - unskew - PK16_SW_BIAS), sB = (unsigned)(bB - unskew - PK16_SW_BIAS);
         const unsigned rA = g * R + kA, rB = g * R + kB;
         keyA = ((unsigned long long)sA << 32) | ((0xFFFFu - cA) << 16) | (0xFFFFu - rA);
         keyB = ((unsigned long long)sB << 32) | ((0xFFFFu - cB) << 16) | (0xFFFFu - rB);
@@ -261,7 +227,7 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
                 rec.score = (int)(key >> 32);
                 rec.end_ref = 0xFFFF - (int)((key >> 16) & 0xFFFF);
                 rec.end_query = 0xFFFF - (int)(key & 0xFFFF);
-                rec.flags = (rec.score + M_BIASx >= limit) ? PMX_FLAG_RERUN : 0;
+                rec.flags = (rec.score + PK16_SW_BIAS >= limit) ? PMX_FLAG_RERUN : 0;
                 if (rec.score > sat_above) rec.flags |= PMX_FLAG_SATURATED;
                 out[pi] = rec;
             }
@@ -279,7 +245,7 @@ static int launch_m(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_sw16m_kernel<G, R, TR>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
-                       M_LIMITx(m.max) - (b.max_rlen + 2 * G + 4) * ext, b.sat_above > 0 ? b.sat_above : 2147483647, b.perm, d_out, tbuf, Tmax);
+                       PK16_RERUN_LIMIT(m.max) - (b.max_rlen + 2 * G + 4) * ext, b.sat_above > 0 ? b.sat_above : 2147483647, b.perm, d_out, tbuf, Tmax);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
 }

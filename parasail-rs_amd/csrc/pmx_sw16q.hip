@@ -12,36 +12,8 @@
 // LDS drops from 57 KB per wave to 11 KB per workgroup, the occupancy from 0.5 to 4 waves per SIMD.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
-
-typedef short q_v2s __attribute__((ext_vector_type(2)));
-typedef _Float16 q_v2h __attribute__((ext_vector_type(2)));
-#define Q_PK(x)  __builtin_bit_cast(q_v2s, (int)(x))
-#define Q_I32(x) __builtin_bit_cast(int, (x))
-#define Q_BIAS 2048
-#define Q_BIAS2 ((Q_BIAS << 16) | Q_BIAS)
-#define Q_LIMIT(maxs) (31744 - ((maxs) > 0 ? (maxs) : 0))
-
-__device__ __forceinline__ int q_max3(int a, int b, int c)
-{
-    const q_v2h r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(q_v2h, a), __builtin_bit_cast(q_v2h, b)),
-                                                  __builtin_bit_cast(q_v2h, c));
-    return __builtin_bit_cast(int, r);
-}
-// value of lane-1 inside a G-lane group; lane 0 of the group receives `neutral`.
-template <int G>
-__device__ __forceinline__ int q_shift_up(int x, int neutral, int g)
-{
-    if (G <= 16) {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x111 /*row_shr:1*/, 0xF, 0xF, false);
-        if (G < 16) r = (g == 0) ? neutral : r;
-        return r;
-    } else {
-        int r = __builtin_amdgcn_update_dpp(neutral, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-        if (G < 64) r = (g == 0) ? neutral : r;
-        return r;
-    }
-}
 
 template <int G, int R, int WAVES>
 __global__ __launch_bounds__(64 * WAVES)
@@ -105,14 +77,14 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
     auto pack2 = [](int a, int b) -> int { return (a & 0xFFFF) | (b << 16); };
     const int vOpen = pack2(open, open), vExt = pack2(ext, ext), vC = vOpen - vExt;
     const int skew0 = (((G - g) * ext) & 0xFFFF) * 0x00010001;       // this lane's first column is j = -g
-    const int vInitH = Q_BIAS2 - vOpen + skew0;
+    const int vInitH = PK16_SW_BIAS2 - vOpen + skew0;
 
     int X[R], E[R], Hsave[R];
 #pragma unroll
-    for (int k = 0; k < R; ++k) { X[k] = vInitH; E[k] = vInitH; Hsave[k] = Q_BIAS2; }
-    int best = Q_BIAS2 + skew0 - vC;            // X form
+    for (int k = 0; k < R; ++k) { X[k] = vInitH; E[k] = vInitH; Hsave[k] = PK16_SW_BIAS2; }
+    int best = PK16_SW_BIAS2 + skew0 - vC;      // X form
     int bestcol = g * 0x00010001;               // step of the first strict improvement (column = step - g)
-    int Zv = Q_BIAS2 + skew0 + vExt;            // "F^ = 0" of the current column; += ext per step
+    int Zv = PK16_SW_BIAS2 + skew0 + vExt;      // "F^ = 0" of the current column; += ext per step
     int Hout = Zv - vExt - vOpen, Fout = Zv - vExt;
     int diag0 = vInitH;
 
@@ -123,8 +95,8 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
         for (int x = 0; x < W4; ++x) { w[bsel][0][x] = a[x]; w[bsel][1][x] = b[x]; }
     };
     auto step = [&](int bsel, int t) {
-        const int Hin = q_shift_up<G>(Hout, Zv - vOpen, g);
-        int F = q_shift_up<G>(Fout, Zv, g);
+        const int Hin = group_shift_up<G>(Hout, Zv - vOpen, g);
+        int F = group_shift_up<G>(Fout, Zv, g);
         int T[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -136,28 +108,23 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int Fe = F - vExt;
-            const int H = q_max3(T[k], E[k], Fe);
+            const int H = pk_max3(T[k], E[k], Fe);
             const int Xn = H - vC;
-            E[k] = q_max3(E[k], Xn, Xn);
-            F = q_max3(Fe, Xn, Zv);
+            E[k] = pk_max3(E[k], Xn, Xn);
+            F = pk_max3(Fe, Xn, Zv);
             X[k] = Xn;
-            if (k & 1) colmax = (k == 1) ? q_max3(X[0], Xn, Xn) : q_max3(colmax, X[k - 1], Xn);
-            else if (k == R - 1) colmax = q_max3(colmax, Xn, Xn);
+            if (k & 1) colmax = (k == 1) ? pk_max3(X[0], Xn, Xn) : pk_max3(colmax, X[k - 1], Xn);
+            else if (k == R - 1) colmax = pk_max3(colmax, Xn, Xn);
         }
         diag0 = Hin;
         Hout = X[R - 1];
         Fout = F;
-        const int nb = q_max3(best, colmax, colmax);
-        const q_v2s sh = {15, 15};
-        const int m = Q_I32((Q_PK(best) - Q_PK(colmax)) >> sh);     // 0xFFFF where the column maximum strictly exceeds the best so far
+        const int nb = pk_max3(best, colmax, colmax);
+        const int m = pk_lt(best, colmax);                     // 0xFFFF where the column maximum strictly exceeds the best so far
         if (__builtin_amdgcn_ballot_w64(m != 0) != 0) {            // (wave-uniform: most steps of a long sweep improve no lane's best)
             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bestcol) : "v"(m), "s"((t & 0xFFFF) * 0x00010001), "v"(bestcol));
 #pragma unroll
-            for (int k = 0; k < R; ++k) {
-                int hs;
-                asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(hs) : "v"(m), "v"(X[k]), "v"(Hsave[k]));
-                Hsave[k] = hs;
-            }
+            for (int k = 0; k < R; ++k) Hsave[k] = bfi(m, X[k], Hsave[k]);
         }
         best = nb + vExt;
         Zv += vExt;
@@ -200,7 +167,7 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
             if ((short)(Hsave[k] >> 16) == tB) kB = k;
         }
         const int unskew = (G - g + T_) * ext - (open - ext);
-        const unsigned sA = (unsigned)(bA - unskew - Q_BIAS), sB = (unsigned)(bB - unskew - Q_BIAS);
+        const unsigned sA = (unsigned)(bA - unskew - PK16_SW_BIAS), sB = (unsigned)(bB - unskew - PK16_SW_BIAS);
         const unsigned rA = g * R + kA, rB = g * R + kB;
         keyA = ((unsigned long long)sA << 32) | ((0xFFFFu - cA) << 16) | (0xFFFFu - rA);
         keyB = ((unsigned long long)sB << 32) | ((0xFFFFu - cB) << 16) | (0xFFFFu - rB);
@@ -221,7 +188,7 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
                 rec.score = (int)(key >> 32);
                 rec.end_ref = 0xFFFF - (int)((key >> 16) & 0xFFFF);
                 rec.end_query = 0xFFFF - (int)(key & 0xFFFF);
-                rec.flags = (rec.score + Q_BIAS >= limit) ? PMX_FLAG_RERUN : 0;
+                rec.flags = (rec.score + PK16_SW_BIAS >= limit) ? PMX_FLAG_RERUN : 0;
                 if (rec.score > sat_above) rec.flags |= PMX_FLAG_SATURATED;
                 out[pi] = rec;
             }
@@ -240,7 +207,7 @@ static int launch_q(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_sw16q_kernel<G, R, WAVES>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                        b.qbuf, b.q_shared, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
-                       Q_LIMIT(m.max) - (b.max_rlen + 2 * G + 4) * ext, b.sat_above > 0 ? b.sat_above : 2147483647, b.perm, d_out);
+                       PK16_RERUN_LIMIT(m.max) - (b.max_rlen + 2 * G + 4) * ext, b.sat_above > 0 ? b.sat_above : 2147483647, b.perm, d_out);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
 }

@@ -17,14 +17,11 @@
 //   * 32-bit lanes: no saturation, every mode (nw / sg with any free ends / sw), end positions with the oracle's rules.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
 
 #define TNEG (INT32_MIN / 2)
 
-__device__ __forceinline__ int t_lane_below(int x, int fill)          // value of lane - 1, `fill` in lane 0
-{
-    return __builtin_amdgcn_update_dpp(fill, x, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-}
 // inclusive prefix maximum over the 64 lanes
 __device__ __forceinline__ int t_prefix_max(int v)
 {
@@ -95,7 +92,7 @@ void pmx_table_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
         const int qo = (int)qs[i] * 2;                                 // uniform: column of the transposed matrix
         const int hleft = colB(i);                                     // H(i, -1)
         const int dleft = i == 0 ? 0 : colB(i - 1);                    // H(i-1, -1)
-        int diag = t_lane_below(Hp[C - 1], dleft);                     // H(i-1, j0-1)
+        int diag = lane_prev<64>(dleft, Hp[C - 1]);                    // H(i-1, j0-1)
         int Ht[C];
         int Tt[TRACE ? C : 1], tb[TRACE ? C : 1];                      // TRACE: T per column, trace byte under construction
         int agg = TNEG;                                                // E leaving this lane's columns if nothing came in, + (C-1) ext
@@ -117,7 +114,7 @@ void pmx_table_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
         // E entering lane l = max over lanes l' < l of out(l') - (l-1-l') * C * ext, and the left boundary for lane 0
         int und = agg + lane * decay;                                  // un-decayed
         und = t_prefix_max(und);
-        int ein = t_lane_below(und, TNEG) - (lane - 1) * decay;        // from the lanes below
+        int ein = lane_prev<64>(TNEG, und) - (lane - 1) * decay;       // from the lanes below
         const int eb = hleft - open - lane * decay;                    // the boundary's gap, decayed over lane * C columns
         ein = max(lane == 0 ? TNEG : ein, eb);
         if (ein < TNEG) ein = TNEG;
@@ -142,7 +139,7 @@ void pmx_table_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
         }
         if (TRACE) {
             // E bit of the lane's first column: the left neighbour is lane - 1's last column (or the boundary column: it always opens)
-            const int hl = t_lane_below(Hp[C - 1], hleft), el = t_lane_below(e_last, TNEG);
+            const int hl = lane_prev<64>(hleft, Hp[C - 1]), el = lane_prev<64>(TNEG, e_last);
             tb[0] |= (hl - open > el - ext) ? PARASAIL_DIAG_E : PARASAIL_INS_E;
             int8_t *dst = trace_out + (long long)i * rl + j0;
 #pragma unroll

@@ -22,6 +22,7 @@
 //     emits run-length BAM ops.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_pk16.h"
 #include <cstdlib>
 
 #define TB 32768                 // bias of the u16 lanes
@@ -33,27 +34,10 @@
 #define OP_FOR_INS_STATE PMX_BAM_OP_FOR_INS_STATE    // include/pmx_conventions.h
 #define OP_FOR_DEL_STATE PMX_BAM_OP_FOR_DEL_STATE    // include/pmx_conventions.h
 
-__device__ __forceinline__ unsigned a16(unsigned a, unsigned b) { unsigned r; asm("v_add_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned s16(unsigned a, unsigned b) { unsigned r; asm("v_sub_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ unsigned m16(unsigned a, unsigned b) { unsigned r; asm("v_max_u16_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // plane = plane * 2 + (a < b)   (unsigned 16-bit compare)
 __device__ __forceinline__ void push_lt(unsigned &plane, unsigned a, unsigned b)
 {
     asm("v_cmp_lt_u16_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(plane) : "v"(a), "v"(b) : "vcc");
-}
-
-template <int G>
-__device__ __forceinline__ unsigned t_shift_up(unsigned x, unsigned neutral, int g)
-{
-    if (G <= 16) {
-        int r = __builtin_amdgcn_update_dpp((int)neutral, (int)x, 0x111, 0xF, 0xF, false);
-        if (G < 16) r = (g == 0) ? (int)neutral : r;
-        return (unsigned)r;
-    } else {
-        int r = __builtin_amdgcn_update_dpp((int)neutral, (int)x, 0x138, 0xF, 0xF, false);
-        if (G < 64) r = (g == 0) ? (int)neutral : r;
-        return (unsigned)r;
-    }
 }
 
 template <int G, int R, bool SW>
@@ -183,25 +167,25 @@ void pmx_trace16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         for (int k = 0; k < R; ++k) w[k] = sp[k];
     };
     auto step = [&](const unsigned (&Hold)[R], unsigned (&Hnew)[R], const unsigned (&w)[R], int t) {
-        const unsigned Hin = t_shift_up<G>(Hout, (unsigned)TB, g);
-        unsigned F = t_shift_up<G>(Fout, (unsigned)(TB + TNEG), g);
+        const unsigned Hin = group_shift_up<G>(Hout, TB, g);
+        unsigned F = group_shift_up<G>(Fout, TB + TNEG, g);
         unsigned plane[TW];
 #pragma unroll
         for (int x = 0; x < TW; ++x) plane[x] = 0;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const unsigned d = (k == 0) ? diag0 : Hold[k - 1];
-            const unsigned Tt = a16(d, w[k]);
-            unsigned H = m16(m16(Tt, E[k]), F);
-            if (SW) H = m16(H, (unsigned)TB);          // local: floor at zero (the walk stops where the score is used up)
+            const unsigned Tt = add_u16(d, w[k]);
+            unsigned H = max_u16(max_u16(Tt, E[k]), F);
+            if (SW) H = max_u16(H, (unsigned)TB);      // local: floor at zero (the walk stops where the score is used up)
             push_lt(plane[k / 8], Tt, H);          // ND
             push_lt(plane[k / 8], F, H);           // NDL
-            const unsigned Ho = s16(H, vOpen);
-            const unsigned Ee = s16(E[k], vExt), Fe = s16(F, vExt);
+            const unsigned Ho = sub_u16(H, vOpen);
+            const unsigned Ee = sub_u16(E[k], vExt), Fe = sub_u16(F, vExt);
             push_lt(plane[k / 8], Ee, Ho);         // EO (next column)
             push_lt(plane[k / 8], Fe, Ho);         // FO (next row)
-            E[k] = m16(Ee, Ho);
-            F = m16(Fe, Ho);
+            E[k] = max_u16(Ee, Ho);
+            F = max_u16(Fe, Ho);
             Hnew[k] = H;
         }
         diag0 = Hin;
@@ -215,7 +199,7 @@ void pmx_trace16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         if (SW) {
             unsigned cm = Hnew[0] & 0xFFFFu;
 #pragma unroll
-            for (int k = 1; k < R; ++k) cm = m16(cm, Hnew[k]) & 0xFFFFu;
+            for (int k = 1; k < R; ++k) cm = max_u16(cm, Hnew[k]) & 0xFFFFu;
             const bool imp = cm > swbest;          // strictly greater: the first column reaching a value keeps it
             swbest = imp ? cm : swbest;
             swcol = imp ? (unsigned)jcol : swcol;
