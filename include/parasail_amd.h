@@ -389,6 +389,11 @@ int pmx_documented_matrix_names(char *buf, int cap);
 int pmx_bstrip_window(int mode, int max_qlen, int max_rlen, int open, int extend, int score_min, int score_max, int capacity, int rows,
                       int double_skew, int *bias, int *low);
 int pmx_bstrip_shape(int band, int *lanes_per_pair, int *offsets_per_lane);
+/* Launch geometry of the band-strip kernel for a batch with queries <= max_qlen and references <= max_rlen (band, lane shape, one
+ * shared query or not): the most row steps a pair runs, the bytes per lane group of the query and selector streams, the dynamic
+ * LDS.  1, or 0 on an argument out of range. */
+int pmx_bstrip_geometry(int max_qlen, int max_rlen, int band, int lanes_per_pair, int offsets_per_lane, int q_shared,
+                        int *rows, int *query_stream, int *selector_stream, long long *lds);
 /* Test hook of the packed global / semi-global kernels (pmx_nwsg16.hip; model: tests/nwsgv_model.c): the host's range proof --
  * the bias nb of the stored form when the int16 window holds every pair of up to max_qlen x max_rlen under this scoring in a shape of
  * shape_rows rows (0: the dispatcher's estimate before a shape is picked), else 0.  rowx: the row-offset form (every width but 8). */

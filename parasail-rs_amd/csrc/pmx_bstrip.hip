@@ -624,6 +624,36 @@ extern "C" int pmx_bstrip_window(int mode, int m, int n, int open, int ext, int 
     return ok ? 1 : 0;
 }
 
+// Launch geometry of a batch with queries <= max_qlen rows, references <= max_rlen columns (exported below as a test hook; the CPU
+// tier checks it against every pair such a batch admits: tests/test_bstrip_model.py):
+//   rows  the most row steps a pair runs: i_e - i_s + 1 of the kernel's geometry, at most min(ql, rl + 2 band), reached by
+//         d0 = -band (j0 = -2 band, i_s = 0) -- a query longer than its reference by more than the band runs past the last column;
+//   QC    query-stream bytes per lane group (one shared query: once), RC selector-stream bytes per lane group, lds their sum
+struct BsGeometry { int rows, QC, RC; size_t lds; };
+static BsGeometry bstrip_geometry(int max_qlen, int max_rlen, int band, int G, int C, bool q_shared)
+{
+    const int U = 4;                                 // the kernel's rows between two selector shifts
+    BsGeometry s;
+    s.rows = (int)std::min<long long>(max_qlen, (long long)max_rlen + 2LL * band);
+    // (one shared query: a pair whose band enters the matrix at row i_s reads letters up to i_s + the wave's step count)
+    s.QC = ((q_shared ? 2 * max_qlen : s.rows) + 2 * G + U + 8 + 3) & ~3;
+    s.RC = (s.rows + G + U + G * C + 8 + 3) & ~3;
+    const int NG = 64 / G;
+    s.lds = (size_t)NG * s.RC + (q_shared ? (size_t)s.QC : (size_t)NG * s.QC);
+    return s;
+}
+extern "C" int pmx_bstrip_geometry(int max_qlen, int max_rlen, int band, int G, int C, int q_shared,
+                                   int *rows, int *QC, int *RC, long long *lds)
+{
+    if (max_qlen <= 0 || max_rlen <= 0 || band < 0 || G <= 0 || 64 % G || C <= 0) return 0;
+    const BsGeometry s = bstrip_geometry(max_qlen, max_rlen, band, G, C, q_shared != 0);
+    if (rows) *rows = s.rows;
+    if (QC) *QC = s.QC;
+    if (RC) *RC = s.RC;
+    if (lds) *lds = (long long)s.lds;
+    return 1;
+}
+
 // lanes per pair and offsets per lane for a band: the smallest capacity G * C >= 2 band + 1
 struct BsShape { int G, C; };
 // (capacity 32 on four lanes: <2,16> keeps 32 lane groups' streams in LDS -- two waves per SIMD -- and measured 2.17 ms against
@@ -677,7 +707,10 @@ int pmx_launch_bstrip(int mode, int sg_flags, int open, int ext, const PmxDevMat
     if (!pmx_bstrip_shape(band, &G, &C)) return 1;
     const bool sw = mode == PMX_MODE_SW;
     const bool ds = !sw && !pmx_env("PMX_BSTRIP_ONE_SKEW");
-    const int cap = G * C, rows = std::min(max_qlen, max_rlen + band + 1);
+    const int cap = G * C;
+    const BsGeometry geo = bstrip_geometry(max_qlen, max_rlen, band, G, C, q_shared != 0);
+    const int rows = geo.rows, QC = geo.QC, RC = geo.RC;
+    const size_t lds = geo.lds;
     SConst k;
     k.mode = mode; k.sg_flags = sg_flags; k.open = open; k.ext = ext; k.band = band;
     int modev = sw ? 2 : (ds ? 1 : 0);
@@ -685,11 +718,6 @@ int pmx_launch_bstrip(int mode, int sg_flags, int open, int ext, const PmxDevMat
         if (modev != 1 || !bstrip_window(mode, max_qlen, max_rlen, open, ext, m.min, m.max, cap, rows, false, &k.bias, &k.low)) return 1;
         modev = 0;
     }
-    const int U = 4;
-    // (one shared query: a pair whose band enters the matrix at row i_s reads letters up to i_s + the wave's step count)
-    const int QC = ((q_shared ? 2 * max_qlen : rows) + 2 * G + U + 8 + 3) & ~3, RC = (rows + G + U + cap + 8 + 3) & ~3;
-    const int NG = 64 / G;
-    const size_t lds = (size_t)NG * RC + (q_shared ? (size_t)QC : (size_t)NG * QC);
     if (lds > 148 * 1024) return 1;
     const int eL = cap - (2 * band + 1);
     // offsets in front of the band in the first live lane: one (the common case: capacity = band width + 1) has a guard of its own; <8,13>

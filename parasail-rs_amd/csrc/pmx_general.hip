@@ -160,7 +160,9 @@ void pmx_general_kernel(const PmxGeneralArgs a)
                     if (STATS) { diagM = bound[8LL * (jlo - 1) + 2]; diagS = bound[8LL * (jlo - 1) + 3]; diagL = bound[8LL * (jlo - 1) + 4]; }
                 }
             }
-            if (lane == 0 && bandi > 0 && jlo > 0) {          // the read-ahead of the previous band's row starts at jlo
+            // the read-ahead of the previous band's row starts at jlo -- at jlo == 0 as well: a band that enters the matrix below the
+            // previous 64 rows left nothing of this pair in `bound` (pjhi < 0)
+            if (lane == 0 && bandi > 0) {
                 const bool in = jlo <= pjhi;
                 pb[0] = in ? bound[8LL * jlo + 0] : NEG_INF; pb[1] = in ? bound[8LL * jlo + 1] : NEG_INF;
                 if (STATS) { for (int x = 2; x < 8; ++x) pb[x] = in ? bound[8LL * jlo + x] : 0; }
@@ -504,7 +506,9 @@ void pmx_general_mw_kernel(const PmxGeneralArgs a)
                         if (STATS) { diagM = bound[8LL * (jlo - 1) + 2]; diagS = bound[8LL * (jlo - 1) + 3]; diagL = bound[8LL * (jlo - 1) + 4]; }
                     }
                 }
-                if (lane == 0 && bandi > 0 && jlo > 0) {          // the read-ahead of the previous band's row starts at jlo
+                // the read-ahead of the previous band's row starts at jlo -- at jlo == 0 as well: a band that enters the matrix below the
+                // previous 64 rows left nothing of this pair in `bound` (pjhi < 0)
+                if (lane == 0 && bandi > 0) {
                     const bool in = jlo <= pjhi;
                     pb0 = in ? bound[8LL * jlo + 0] : NEG_INF; pb1 = in ? bound[8LL * jlo + 1] : NEG_INF;
                     if (STATS) { pb2 = in ? bound[8LL * jlo + 2] : 0; pb3 = in ? bound[8LL * jlo + 3] : 0; pb4 = in ? bound[8LL * jlo + 4] : 0;
