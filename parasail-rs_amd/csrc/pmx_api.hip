@@ -1367,18 +1367,31 @@ static thread_local const char *g_last_kernel = "";
 extern "C" const char *pmx_last_kernel(void) { return g_last_kernel; }
 
 
-// General kernel (one wave per pair) over a batch.  Its scratch -- the boundary row between 64-row bands, 8 ints per reference
-// column, and for references beyond the LDS a mapped copy in HBM -- only has to cover the pairs of one launch: chunks of ~2 GB.
-// band >= 0: cells with |(j - i) - diag[pair]| > band are excluded (diag == nullptr: the main diagonal).
-static int general_batch(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
-                         const uint8_t *d_qbuf, const int64_t *d_qoff, int q_shared,
-                         const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen,
-                         int band, const int32_t *d_diag, bool want_stats,
-                         pmx_record_t *d_out, pmx_stats_t *d_stats_out, hipStream_t st, int32_t max_qlen = 0)
+// What every general-kernel batch shares: the n pairs, the square matrix, the gap model, the configured width, no band.
+static PmxGeneralArgs general_args(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
+                                   const uint8_t *d_qbuf, const int64_t *d_qoff, int q_shared,
+                                   const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen)
 {
-    const size_t stride = (size_t)8 * max_rlen;
-    const bool fits = pmx_general_lds_fits(dm.d.msize, dm.d.msize, max_rlen);
-    const size_t rs_stride = fits ? 0 : (((size_t)max_rlen + 8 + 15) & ~(size_t)15);
+    PmxGeneralArgs a; memset(&a, 0, sizeof a);
+    a.qbuf = d_qbuf; a.qoff = q_shared ? nullptr : d_qoff; a.shared_qlen = q_shared;
+    a.rbuf = d_rbuf; a.roff = d_roff; a.n = n; a.max_rlen = max_rlen;
+    a.scores = dm.d.scores; a.mapper = dm.d.mapper; a.msize = dm.d.msize; a.mat_rows = dm.d.msize;
+    a.mode = cfg->mode; a.sg_flags = cfg->sg_flags; a.open = cfg->open; a.ext = cfg->extend;
+    a.band = -1; a.bits = cfg->width;
+    return a;
+}
+
+// General kernel (one wave per pair) over the batch `t` describes.  Its scratch -- the boundary row between 64-row bands, 8 ints
+// per reference column, and for references beyond the LDS a mapped copy in HBM -- only has to cover the pairs of one launch:
+// chunks of ~2 GB (PMX_GENERAL_CHUNK_BYTES).  With t.index set (a re-run of listed pairs) a chunk is a stretch of the list and the
+// outputs stay indexed by pair; otherwise a chunk is a stretch of the batch and every per-pair pointer moves with it.
+// band >= 0: cells with |(j - i) - diag[pair]| > band are excluded (diag == nullptr: the main diagonal).
+static int general_batch(const PmxGeneralArgs &t, bool want_stats, hipStream_t st, const char *what = "general kernel launch failed")
+{
+    const int64_t n = t.n;
+    const size_t stride = (size_t)8 * t.max_rlen;
+    const bool fits = pmx_general_lds_fits(t.mat_rows, t.msize, t.max_rlen);
+    const size_t rs_stride = fits ? 0 : (((size_t)t.max_rlen + 8 + 15) & ~(size_t)15);
     const size_t per_pair = stride * sizeof(int32_t) + rs_stride;
     const char *cb = pmx_env("PMX_GENERAL_CHUNK_BYTES");
     int64_t chunk = (int64_t)((cb && atof(cb) > 0 ? atof(cb) : 2e9) / (double)per_pair);
@@ -1387,19 +1400,17 @@ static int general_batch(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
     void *bound = nullptr;
     if (scratch_reserve((size_t)chunk * per_pair, &bound)) return -1;
     for (int64_t c0 = 0; c0 < n; c0 += chunk) {
-        const int64_t m = (n - c0 < chunk) ? n - c0 : chunk;
-        PmxGeneralArgs a; memset(&a, 0, sizeof a);
-        a.qbuf = d_qbuf; a.qoff = q_shared ? nullptr : d_qoff + c0; a.shared_qlen = q_shared;
-        a.rbuf = d_rbuf; a.roff = d_roff + c0; a.n = m; a.max_rlen = max_rlen;
-        a.scores = dm.d.scores; a.mapper = dm.d.mapper; a.msize = dm.d.msize; a.mat_rows = dm.d.msize; a.pssm = 0;
-        a.mode = cfg->mode; a.sg_flags = cfg->sg_flags; a.open = cfg->open; a.ext = cfg->extend;
-        a.band = band; a.diag = d_diag ? d_diag + c0 : nullptr;
-        a.bits = cfg->width; a.max_qlen = max_qlen;
+        PmxGeneralArgs a = t;
+        a.n = (n - c0 < chunk) ? n - c0 : chunk;
+        if (a.index) a.index += c0;
+        else {
+            a.roff += c0; if (a.qoff) a.qoff += c0; if (a.diag) a.diag += c0;
+            if (a.rec) a.rec += c0; if (a.stats) a.stats += c0; if (a.tab_off) a.tab_off += c0;
+        }
         a.bound = (int32_t *)bound; a.bound_stride = (long long)stride;
         if (!fits) { a.rs_scratch = (uint8_t *)bound + (size_t)chunk * stride * sizeof(int32_t); a.rs_stride = (long long)rs_stride; }
-        a.rec = d_out + c0; a.stats = d_stats_out ? d_stats_out + c0 : nullptr;
         const int rc = pmx_launch_general(a, want_stats, st);
-        if (rc) { set_err("general kernel launch failed (%d)", rc); return rc < 0 ? rc : -1; }
+        if (rc) { set_err("%s (%d)", what, rc); return rc < 0 ? rc : -1; }
     }
     return 0;
 }
@@ -1432,6 +1443,39 @@ static int trace_ws_init()
         HIP_OR_RET(hipEventCreateWithFlags(&g_tws.walk_done[k], hipEventDisableTiming));
     }
     g_tws.dev = dev;
+    return 0;
+}
+
+// Per-pair packed traceback over a batch in chunks of `chunk` pairs (variant / Tmax planned for one chunk).  two: two trace buffers
+// of cbytes each and two sets of block flags, sweeps of consecutive chunks alternating between the caller's stream and an internal
+// one (the tail of one launch is backfilled by the next), the walk of chunk c on the high-priority walk stream beside the sweep of
+// chunk c + 1; otherwise one buffer and sweep and walk back to back on `st`.  Per pair the walk leaves either the path's statistics
+// (stats) or run-length ops in implicit slots (ops / ops_base) with their count, begins and CIGAR text length.
+struct TraceOutputs { pmx_stats_t *stats; uint32_t *ops; long long ops_base; int32_t *nops, *beg, *textlen; };
+static size_t trace_flag_stride(int64_t chunk) { return (size_t)chunk / 2 + 16; }    // ints of one set of per-block flags
+static int trace_chunks(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch &b, int variant, int Tmax, int64_t chunk, bool two,
+                        uint32_t *tbuf, size_t cbytes, int *bflags, pmx_record_t *d_out, const TraceOutputs &o, hipStream_t st,
+                        const char *what)
+{
+    const size_t fstride = trace_flag_stride(chunk);
+    if (two) { HIP_OR_RET(hipEventRecord(g_tws.start, st)); HIP_OR_RET(hipStreamWaitEvent(g_tws.aux, g_tws.start, 0)); }
+    int idx = 0;
+    for (int64_t c0 = 0; c0 < b.n; c0 += chunk, ++idx) {
+        PmxBatch bk = b;
+        bk.n = (b.n - c0 < chunk) ? b.n - c0 : chunk;
+        bk.qoff = b.qoff + c0; bk.roff = b.roff + c0;
+        bk.blockflag = bflags + (size_t)(idx & 1) * fstride;
+        const hipStream_t sws = (two && (idx & 1)) ? g_tws.aux : st;
+        if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(sws, g_tws.walk_done[idx & 1], 0));     // this trace buffer's last walk is done
+        PmxWalkSplit sp = {two ? g_tws.walk : st, g_tws.sweep_done[idx & 1], two ? g_tws.walk_done[idx & 1] : nullptr,
+                           o.ops_base - c0, o.textlen ? o.textlen + c0 : nullptr};
+        const int rc = pmx_launch_trace16(variant, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out + c0,
+                                          (uint32_t *)((unsigned char *)tbuf + (two ? (size_t)(idx & 1) * cbytes : 0)), Tmax,
+                                          o.ops, nullptr, o.nops ? o.nops + c0 : nullptr, o.beg ? o.beg + 2 * c0 : nullptr, sws,
+                                          o.stats ? o.stats + c0 : nullptr, &sp);
+        if (rc) { set_err("%s (%d)", what, rc); return rc < 0 ? rc : -1; }
+    }
+    if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));      // the walk stream is in order: the last walk covers all
     return 0;
 }
 
@@ -1566,6 +1610,45 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
     return 0;
 }
 
+// Statistics of per-pair batches = counts along the packed traceback path (the same decisions and tie-breaks as the coupled
+// statistics tables).  The packed traceback sweep runs at more than twice the speed of the statistics kernel and the walk is cheap;
+// the trace scratch is bounded by working in chunks (no host synchronisation).  (A few pairs: the one-pass statistics kernel has the
+// lower latency.)  0 done (asynchronously on st), 1 not eligible, <0 error.
+static int stats_by_trace_pairs(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch &b,
+                                pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t st)
+{
+    if (b.q_shared || !(b.n >= 2048 || pmx_env("PMX_STATS_BY_TRACE")) || pmx_env("PMX_NO_STATS_BY_TRACE")) return 1;
+    const int64_t n = b.n;
+    PmxBatch bt = b; bt.perm = nullptr;
+    int variant = 0, Tmax = 0; size_t tbytes = 0;
+    if (pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) != 0 || variant < 10) return 1;
+    double budget = 8e9;
+    { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess && 0.15 * (double)fb < budget) budget = 0.15 * (double)fb; }
+    const double per_pair = (double)tbytes / (double)n + 1.0;
+    int64_t nchunks = (int64_t)((double)tbytes / budget) + 1;
+    if (nchunks < 2 && n >= 16384) nchunks = 2;            // two chunks at least: the walk of one runs beside the sweep of the next
+    int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
+    if ((double)chunk * per_pair > budget) chunk = (int64_t)(budget / per_pair) / 64 * 64;
+    if (chunk < 64) chunk = 64;
+    if (chunk > n) chunk = n;
+    bt.n = chunk;
+    (void)pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes);
+    bt.n = n;
+    const size_t cbytes = (tbytes + 255) & ~(size_t)255;
+    const bool two = chunk < n;
+    if (two && trace_ws_init()) return -1;
+    uint32_t *tbuf = nullptr;
+    if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE)) return -1;
+    int *bflags = nullptr;
+    if (scratch_reserve(2 * trace_flag_stride(chunk) * sizeof(int), (void **)&bflags, SCR_RETRY)) return -1;
+    const TraceOutputs o = {d_stats, nullptr, 0, nullptr, nullptr, nullptr};
+    const int rc = trace_chunks(cfg, dm, bt, variant, Tmax, chunk, two, tbuf, cbytes, bflags, d_out, o, st,
+                                "stats-by-traceback launch failed");
+    if (rc) return rc;
+    g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel/stats" : "pmx_nwsg16v_kernel/packed trace + pmx_walkp_kernel/stats";
+    return 0;
+}
+
 // pmx_long32_kernel over a batch, in chunks of bounded scratch: 0 done, 1 not eligible, < 0 error.  Score and end positions, 32-bit
 // lanes, any gap model (open < extend included), alphabets up to 64 letters, no limit on either length.  Widths: local -- any
 // (saturation = a score beyond the width); global / semi-global -- sat, 32, 64, or a fixed width whose range the boundary row /
@@ -1654,6 +1737,33 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
     return 0;
 }
 
+// Overflow promotion after the fast local kernel (`sat`, 32, 64): pairs whose int16 lanes overflowed are re-run in the 32-bit
+// general kernel.  Skipped without any synchronisation when no score can reach 32768.  0 done, < 0 error.
+static int promote_overflowed(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch &b, pmx_record_t *d_out, hipStream_t st)
+{
+    const long long bound_score = (long long)(b.max_qlen < b.max_rlen ? b.max_qlen : b.max_rlen) *
+                                  (cfg->matrix->max > 0 ? cfg->matrix->max : 0);
+    // (the max3 variant of the fast kernel is exact up to 29 696 - max score; beyond that it sets
+    //  PMX_FLAG_RERUN and the pair is redone here whatever the requested width)
+    if (bound_score <= 27000) return 0;
+    const int mask = PMX_FLAG_RERUN | ((cfg->width == 16 || cfg->width == 8) ? 0 : PMX_FLAG_SATURATED);
+    DevBuf<int64_t> list; DevBuf<int> cnt;
+    if (list.try_alloc((size_t)b.n) || cnt.try_alloc(1)) { set_err("out of device memory (promotion list)"); return -2; }
+    int rc = pmx_launch_collect_saturated(d_out, b.n, list.p, cnt.p, mask, st);
+    if (rc) { set_err("collect kernel failed (%d)", rc); return rc; }
+    int count = 0;
+    HIP_OR_RET(hipMemcpyAsync(&count, cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    if (count == 0) return 0;
+    PmxGeneralArgs a = general_args(cfg, dm, count, b.qbuf, b.qoff, b.q_shared, b.rbuf, b.roff, b.max_rlen);
+    a.index = list.p; a.rec = d_out;
+    a.bits = cfg->width == 16 ? 16 : cfg->width == 8 ? 8 : 32;
+    rc = general_batch(a, false, st, "promotion launch failed");
+    if (rc) return rc;
+    HIP_OR_RET(hipStreamSynchronize(st));      // the list is released on return
+    return 0;
+}
+
 // Device-resident batch.  q_shared > 0: every pair uses the one query d_qbuf[0..q_shared) (profile arm).
 static int run_batch_device(const pmx_config_t *cfg, int64_t n,
                             const uint8_t *d_qbuf, const int64_t *d_qoff, int q_shared,
@@ -1698,123 +1808,35 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
         }
         const int rc = pmx_launch_sw16(b, dm.d, cfg->open, cfg->extend, d_out, st, &g_last_kernel);
         if (rc < 0) { set_err("sw16 launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
-        if (rc == 0) {
-            // Overflow promotion (`sat`, 32, 64): pairs whose int16 lanes overflowed are re-run in the
-            // 32-bit kernel.  Skipped without any synchronisation when no score can reach 32768.
-            const long long bound_score = (long long)(max_qlen < max_rlen ? max_qlen : max_rlen) *
-                                          (cfg->matrix->max > 0 ? cfg->matrix->max : 0);
-            // (the max3 variant of the fast kernel is exact up to 29 696 - max score; beyond that it sets
-            //  PMX_FLAG_RERUN and the pair is redone here whatever the requested width)
-            if (bound_score <= 27000) return 0;
-            const int mask = PMX_FLAG_RERUN | ((cfg->width == 16 || cfg->width == 8) ? 0 : PMX_FLAG_SATURATED);
-            DevBuf<int64_t> list; DevBuf<int> cnt;
-            if (list.try_alloc((size_t)n) || cnt.try_alloc(1)) { set_err("out of device memory (promotion list)"); return -2; }
-            int rc2 = pmx_launch_collect_saturated(d_out, n, list.p, cnt.p, mask, st);
-            if (rc2) { set_err("collect kernel failed (%d)", rc2); return rc2; }
-            int count = 0;
-            HIP_OR_RET(hipMemcpyAsync(&count, cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-            HIP_OR_RET(hipStreamSynchronize(st));
-            if (count == 0) return 0;
-            DevBuf<int32_t> bnd; DevBuf<uint8_t> rsb;
-            const size_t stride2 = (size_t)8 * max_rlen;
-            const bool fits2 = pmx_general_lds_fits(dm.d.msize, dm.d.msize, max_rlen);
-            const size_t rs2 = fits2 ? 0 : (((size_t)max_rlen + 8 + 15) & ~(size_t)15);
-            if (bnd.try_alloc((size_t)count * stride2) || (!fits2 && rsb.try_alloc((size_t)count * rs2))) {
-                set_err("out of device memory (promotion pass of %d pairs)", count); return -2;
-            }
-            PmxGeneralArgs a; memset(&a, 0, sizeof a);
-            a.qbuf = d_qbuf; a.qoff = q_shared ? nullptr : d_qoff; a.shared_qlen = q_shared;
-            a.rbuf = d_rbuf; a.roff = d_roff; a.n = count; a.index = list.p; a.max_rlen = max_rlen;
-            a.scores = dm.d.scores; a.mapper = dm.d.mapper; a.msize = dm.d.msize; a.mat_rows = dm.d.msize;
-            a.mode = cfg->mode; a.sg_flags = cfg->sg_flags; a.open = cfg->open; a.ext = cfg->extend; a.band = -1;
-            a.bits = cfg->width == 16 ? 16 : cfg->width == 8 ? 8 : 32; a.bound = bnd.p; a.bound_stride = (long long)stride2; a.rec = d_out;
-            if (!fits2) { a.rs_scratch = rsb.p; a.rs_stride = (long long)rs2; }
-            rc2 = pmx_launch_general(a, false, st);
-            if (rc2) { set_err("promotion launch failed (%d)", rc2); return rc2 < 0 ? rc2 : -1; }
-            HIP_OR_RET(hipStreamSynchronize(st));      // scratch is released on return
-            return 0;
-        }
+        if (rc == 0) return promote_overflowed(cfg, dm, b, d_out, st);
         // rc == 1: shape not covered by the fast kernel -> general kernel below
     }
-    // statistics: (0) small alphabets in full batches: counts along the packed traceback; (1) the packed statistics kernel
-    // (shared profile, or per-pair over a large alphabet, no free end); (2) large alphabets with short references: traceback
-    // again; (3) the unpacked statistics kernel
     if (q_shared && want == PMX_WANT_STATS && cfg->width != 8 && cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE &&
         (cfg->mode == PMX_MODE_NW || cfg->mode == PMX_MODE_SG) && (n >= 512 || pmx_env("PMX_STATS_BY_TRACE"))) {
         // profile arm with statistics (BASELINE config 3): traceback sweep + counting walk
         const int rc = stats_by_trace_shared(cfg, dm, b, d_out, d_stats_out, st);
-        if (rc < 0) return rc;
-        if (rc == 0) return 0;
+        if (rc <= 0) return rc;
     }
     if (upload_wait(INT64_MAX, st, 0)) return -1;             // (host entry with a sliced upload: every other path reads the whole batch)
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1) {
-            if (want == PMX_WANT_STATS && cfg->width != 8 && cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE) {
-                // second generation (two pairs per lane slot); global / semi-global inside its exact window
-                const int rc = pmx_launch_stats16p(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out, d_stats_out, st, &g_last_kernel);
-                if (rc < 0) { set_err("stats16p launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
-                if (rc == 0) return 0;
-            }
-            if (!(dm.d.msize > 8 && (max_rlen <= 1024 || pmx_env("PMX_STATS_BY_TRACE_ANY")))) break;
-        }
-        if (want == PMX_WANT_STATS && cfg->width != 8 && cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE &&
-            (dm.d.msize <= 8 || pass == 1) && !q_shared && (n >= 2048 || pmx_env("PMX_STATS_BY_TRACE")) && !pmx_env("PMX_NO_STATS_BY_TRACE")) {
-            // (a few pairs: the one-pass statistics kernel has the lower latency)
-            // Small alphabets: statistics = counts along the traceback path (the same decisions and tie-breaks as the
-            // coupled statistics tables).  The packed traceback sweep runs at more than twice the speed of the
-            // statistics kernel and the walk is cheap; the trace scratch is bounded by working in chunks (same stream,
-            // no host synchronisation).  Large alphabets take this route for short references only (measured: per-pair
-            // protein 285 x 285, sw 0.37 -> 1.03 TCUPS, nw 0.40 -> 0.89 with the matrix-lookup traceback kernels; against 5-kaa references the staged references
-            // and per-pair profiles starve the 16-rows-per-lane traceback shapes and the statistics kernel wins).
-            PmxBatch bt = b; bt.perm = nullptr;
-            int variant = 0, Tmax = 0; size_t tbytes = 0;
-            if (pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) == 0 && variant >= 10) {
-                double budget = 8e9;
-                { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess && 0.15 * (double)fb < budget) budget = 0.15 * (double)fb; }
-                const double per_pair = (double)tbytes / (double)n + 1.0;
-                int64_t nchunks = (int64_t)((double)tbytes / budget) + 1;
-                if (nchunks < 2 && n >= 16384) nchunks = 2;            // two chunks at least: the walk of one runs beside the sweep of the next
-                int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
-                if ((double)chunk * per_pair > budget) chunk = (int64_t)(budget / per_pair) / 64 * 64;
-                if (chunk < 64) chunk = 64;
-                if (chunk > n) chunk = n;
-                bt.n = chunk;
-                (void)pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes);
-                const size_t cbytes = (tbytes + 255) & ~(size_t)255;
-                const bool two = chunk < n;
-                if (two && trace_ws_init()) return -1;
-                uint32_t *tbuf = nullptr;
-                if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE)) return -1;
-                const size_t fstride = (size_t)chunk / 2 + 16;           // per-block flags of a chunk's sweep, two sets (as in cigar_device_run)
-                int *bflags = nullptr;
-                if (scratch_reserve(2 * fstride * sizeof(int), (void **)&bflags, SCR_RETRY)) return -1;
-                // as in the batch CIGAR entry: two trace buffers, the counting walk of chunk c on the walk stream beside the sweep of
-                // chunk c + 1, sweeps alternating between the caller's stream and an internal one
-                if (two) { HIP_OR_RET(hipEventRecord(g_tws.start, st)); HIP_OR_RET(hipStreamWaitEvent(g_tws.aux, g_tws.start, 0)); }
-                int idx = 0;
-                for (int64_t c0 = 0; c0 < n; c0 += chunk, ++idx) {
-                    PmxBatch bc = bt;
-                    bc.n = (n - c0 < chunk) ? n - c0 : chunk;
-                    bc.qoff = d_qoff + c0; bc.roff = d_roff + c0;
-                    bc.blockflag = bflags + (size_t)(idx & 1) * fstride;
-                    const hipStream_t sws = (two && (idx & 1)) ? g_tws.aux : st;
-                    if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(sws, g_tws.walk_done[idx & 1], 0));
-                    PmxWalkSplit sp = {two ? g_tws.walk : st, g_tws.sweep_done[idx & 1], two ? g_tws.walk_done[idx & 1] : nullptr, 0, nullptr};
-                    const int rc = pmx_launch_trace16(variant, bc, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out + c0,
-                                                      (uint32_t *)((unsigned char *)tbuf + (two ? (size_t)(idx & 1) * cbytes : 0)), Tmax,
-                                                      nullptr, nullptr, nullptr, nullptr, sws, d_stats_out + c0, two ? &sp : nullptr);
-                    if (rc) { set_err("stats-by-traceback launch failed (%d)", rc); return rc < 0 ? rc : -1; }
-                }
-                if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));
-                g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel/stats" : "pmx_nwsg16v_kernel/packed trace + pmx_walkp_kernel/stats";
-                return 0;
-            }
-        }
-    }
     if (want == PMX_WANT_STATS && cfg->width != 8 && cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE) {
-        const int rc = pmx_launch_stats16(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out, d_stats_out, st, &g_last_kernel);
-        if (rc < 0) { set_err("stats16 launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
-        if (rc == 0) return 0;
+        // Statistics, each step 0 done / 1 not eligible (the next one is tried) / < 0 error: (a) small alphabets: counts along the
+        // packed traceback; (b) the packed statistics kernel (two pairs per lane slot; shared profile, or per-pair over a large
+        // alphabet; global / semi-global inside its exact window); (c) large alphabets with short references: traceback again
+        // (measured: per-pair protein 285 x 285, sw 0.37 -> 1.03 TCUPS, nw 0.40 -> 0.89 with the matrix-lookup traceback kernels;
+        // against 5-kaa references the staged references and per-pair profiles starve the 16-rows-per-lane traceback shapes and the
+        // statistics kernel wins); (d) the unpacked statistics kernel.
+        auto launched = [](int rc, const char *what) {
+            if (rc < 0) set_err("%s launch failed: %s", what, hipGetErrorString((hipError_t)(-rc)));
+            return rc;
+        };
+        int rc = dm.d.msize <= 8 ? stats_by_trace_pairs(cfg, dm, b, d_out, d_stats_out, st) : 1;
+        if (rc == 1)
+            rc = launched(pmx_launch_stats16p(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out, d_stats_out, st, &g_last_kernel), "stats16p");
+        if (rc == 1 && dm.d.msize > 8 && (max_rlen <= 1024 || pmx_env("PMX_STATS_BY_TRACE_ANY")))
+            rc = stats_by_trace_pairs(cfg, dm, b, d_out, d_stats_out, st);
+        if (rc == 1)
+            rc = launched(pmx_launch_stats16(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out, d_stats_out, st, &g_last_kernel), "stats16");
+        if (rc <= 0) return rc;
     }
     if ((cfg->mode == PMX_MODE_NW || cfg->mode == PMX_MODE_SG) && want == 0 && (cfg->width != 8 || !pmx_env("PMX_NWSG8_GENERAL")) &&
         cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE) {
@@ -1837,8 +1859,9 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
         const int rc = long_batch(cfg, dm, b, n, max_qlen, max_rlen, d_out, st);
         if (rc <= 0) return rc;
     }
-    const int rcg = general_batch(cfg, dm, n, d_qbuf, d_qoff, q_shared, d_rbuf, d_roff, max_rlen, -1, nullptr,
-                                  (want & PMX_WANT_STATS) != 0, d_out, d_stats_out, st, max_qlen);
+    PmxGeneralArgs a = general_args(cfg, dm, n, d_qbuf, d_qoff, q_shared, d_rbuf, d_roff, max_rlen);
+    a.max_qlen = max_qlen; a.rec = d_out; a.stats = d_stats_out;
+    const int rcg = general_batch(a, (want & PMX_WANT_STATS) != 0, st);
     if (rcg) return rcg;
     g_last_kernel = "pmx_general_kernel";
     return 0;
@@ -1924,6 +1947,32 @@ static pmx_config_t with_sort_hint(const pmx_config_t *cfg, int32_t min_rlen, in
     return c;
 }
 
+// Streams and events of one host entry (one thread_local instance per entry): a copy stream, a compute stream, with `back` a third
+// stream for the way back, and one upload / one finish event per slice.  Created on the thread's device, again after a move.
+namespace {
+struct HostStreams {
+    hipStream_t copy = nullptr, comp = nullptr, back = nullptr; hipEvent_t up[8] = {}, done[8] = {}; int dev = -1;
+    int init(bool with_back)
+    {
+        int d = 0; HIP_OR_RET(hipGetDevice(&d));
+        if (dev == d) return 0;
+        if (copy) {                                        // the thread moved to another device: release the old device's objects
+            (void)hipStreamDestroy(copy); (void)hipStreamDestroy(comp); if (back) (void)hipStreamDestroy(back);
+            for (int k = 0; k < 8; ++k) { (void)hipEventDestroy(up[k]); (void)hipEventDestroy(done[k]); }
+            *this = HostStreams();
+        }
+        HIP_OR_RET(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+        HIP_OR_RET(hipStreamCreateWithFlags(&comp, hipStreamNonBlocking));
+        if (with_back) HIP_OR_RET(hipStreamCreateWithFlags(&back, hipStreamNonBlocking));
+        for (int k = 0; k < 8; ++k) {
+            HIP_OR_RET(hipEventCreateWithFlags(&up[k], hipEventDisableTiming));
+            HIP_OR_RET(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+        }
+        dev = d; return 0;
+    }
+};
+}  // namespace
+
 // Host buffers in, host records out.  packed2: the sequence buffers hold 2 bits per base (base b in byte b / 4 at bits 2 (b % 4),
 // code c = letter c of the matrix alphabet) and the offsets count bases: a quarter of the bytes cross PCIe and a small kernel
 // spells them out into the staging buffers before the slice is aligned.
@@ -1960,23 +2009,9 @@ static int host_batch(const pmx_config_t *cfg, int64_t n,
         scratch_reserve(sizeof(pmx_record_t) * n, (void **)&drec.p, SCR_HREC) ||
         (stats && scratch_reserve(sizeof(pmx_stats_t) * n, (void **)&dst.p, SCR_HST)) ||
         (packed2 && (scratch_reserve(qbytes / 4 + 16, (void **)&dq2.p, SCR_HQ2) || scratch_reserve(rbytes / 4 + 16, (void **)&dr2.p, SCR_HR2)))) return -1;
-    static thread_local hipStream_t s_copy = nullptr, s_comp = nullptr, s_back = nullptr;
-    static thread_local hipEvent_t s_ev[8], s_done[8];
-    static thread_local int s_dev = -1;
-    int dev = 0; HIP_OR_RET(hipGetDevice(&dev));
-    if (s_dev != dev) {
-        if (s_copy) {                                      // the thread moved to another device: release the old device's objects
-            (void)hipStreamDestroy(s_copy); (void)hipStreamDestroy(s_comp); (void)hipStreamDestroy(s_back);
-            for (auto &e : s_ev) (void)hipEventDestroy(e);
-            for (auto &e : s_done) (void)hipEventDestroy(e);
-        }
-        HIP_OR_RET(hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking));
-        HIP_OR_RET(hipStreamCreateWithFlags(&s_comp, hipStreamNonBlocking));
-        HIP_OR_RET(hipStreamCreateWithFlags(&s_back, hipStreamNonBlocking));
-        for (auto &e : s_ev) HIP_OR_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : s_done) HIP_OR_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        s_dev = dev;
-    }
+    static thread_local HostStreams hs;
+    if (hs.init(true)) return -1;
+    const hipStream_t s_copy = hs.copy, s_comp = hs.comp, s_back = hs.back; hipEvent_t *const s_ev = hs.up, *const s_done = hs.done;
     HIP_OR_RET(hipMemcpyAsync(dqo.p, qoff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_copy));
     HIP_OR_RET(hipMemcpyAsync(dro.p, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_copy));
     if (scan.valid()) scan.get();
@@ -2067,20 +2102,10 @@ extern "C" int pmx_align_profile_batch(const pmx_config_t *cfg, const parasail_p
     if (scratch_reserve(rbytes + 16, (void **)&dr.p, SCR_HR) || scratch_reserve(sizeof(int64_t) * (n + 1), (void **)&dro.p, SCR_HRO) ||
         scratch_reserve(sizeof(pmx_record_t) * n, (void **)&drec.p, SCR_HREC) ||
         (stats && scratch_reserve(sizeof(pmx_stats_t) * n, (void **)&dst.p, SCR_HST))) return -1;
-    static thread_local hipStream_t s_copy = nullptr, s_comp = nullptr;
-    static thread_local hipEvent_t s_up[8], s_done[8];
-    static thread_local int s_dev = -1;
-    int dev = 0; HIP_OR_RET(hipGetDevice(&dev));
-    if (s_dev != dev) {
-        if (s_copy) { (void)hipStreamDestroy(s_copy); (void)hipStreamDestroy(s_comp); for (int k = 0; k < 8; ++k) { (void)hipEventDestroy(s_up[k]); (void)hipEventDestroy(s_done[k]); } }
-        HIP_OR_RET(hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking));
-        HIP_OR_RET(hipStreamCreateWithFlags(&s_comp, hipStreamNonBlocking));
-        for (int k = 0; k < 8; ++k) {
-            HIP_OR_RET(hipEventCreateWithFlags(&s_up[k], hipEventDisableTiming));
-            HIP_OR_RET(hipEventCreateWithFlags(&s_done[k], hipEventDisableTiming));
-        }
-        s_dev = dev;
-    }
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t s_copy = hs.copy, s_comp = hs.comp; hipEvent_t *const s_up = hs.up, *const s_done = hs.done;
+    const int dev = hs.dev;
     // (a slice must still fill the chip: at least 32 k references each)
     const int K = rbytes >= ((size_t)64 << 20) ? (int)std::max<int64_t>(1, std::min<int64_t>(8, n / 32768)) : 1;
     // slices of about equal bytes (the references may be ragged)
@@ -2194,8 +2219,9 @@ static int banded_device(const pmx_config_t *cfg, int64_t n, const uint8_t *d_qb
                                       retry_scr ? (unsigned *)retry_scr + 1 : nullptr, (int *)retry_scr);
     if (rcb < 0) { set_err("banded kernel launch failed: %s", hipGetErrorString((hipError_t)(-rcb))); return rcb; }
     if (rcb == 0) { g_last_kernel = kname; return 0; }
-    const int rc = general_batch(&c, dm, n, d_qbuf, d_qoff, q_shared, d_rbuf, d_roff, max_rlen, band, d_diag, false, d_out, nullptr,
-                                 (hipStream_t)stream, max_qlen);
+    PmxGeneralArgs a = general_args(&c, dm, n, d_qbuf, d_qoff, q_shared, d_rbuf, d_roff, max_rlen);
+    a.max_qlen = max_qlen; a.band = band; a.diag = d_diag; a.rec = d_out;
+    const int rc = general_batch(a, false, (hipStream_t)stream);
     if (rc == 0) g_last_kernel = "pmx_general_kernel/banded";
     return rc;
 }
@@ -2280,32 +2306,13 @@ extern "C" int pmx_align_batch_table_device(const pmx_config_t *cfg, int64_t n,
     if (rc < 0) { set_err("table kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
     if (rc == 0) { g_last_kernel = "pmx_table_kernel"; return 0; }
     // outside the row-by-row kernel's window (references beyond 1 024 symbols, open < extend, ...): the general kernel, in chunks
-    const size_t stride = (size_t)8 * max_rlen;
-    const bool fits = pmx_general_lds_fits(dm.d.msize, dm.d.msize, max_rlen);
-    const size_t rs_stride = fits ? 0 : (((size_t)max_rlen + 8 + 15) & ~(size_t)15);
-    const size_t per_pair = stride * sizeof(int32_t) + rs_stride;
-    const char *cb = pmx_env("PMX_GENERAL_CHUNK_BYTES");
-    int64_t chunk = (int64_t)((cb && atof(cb) > 0 ? atof(cb) : 2e9) / (double)per_pair);
-    if (chunk < 1) chunk = 1;
-    if (chunk > n) chunk = n;
-    void *bound = nullptr;
-    if (scratch_reserve((size_t)chunk * per_pair, &bound)) return -1;
     DevBuf<pmx_record_t> tmp_rec;
     if (!d_out && tmp_rec.try_alloc((size_t)n)) { set_err("out of device memory"); return -2; }
-    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
-        const int64_t m = (n - c0 < chunk) ? n - c0 : chunk;
-        PmxGeneralArgs a; memset(&a, 0, sizeof a);
-        a.qbuf = d_qbuf; a.qoff = d_qoff + c0; a.rbuf = d_rbuf; a.roff = d_roff + c0; a.n = m; a.max_rlen = max_rlen;
-        a.scores = dm.d.scores; a.mapper = dm.d.mapper; a.msize = dm.d.msize; a.mat_rows = dm.d.msize;
-        a.mode = cfg->mode; a.sg_flags = cfg->sg_flags; a.open = cfg->open; a.ext = cfg->extend; a.band = -1; a.bits = 32;
-        a.bound = (int32_t *)bound; a.bound_stride = (long long)stride;
-        if (!fits) { a.rs_scratch = (uint8_t *)bound + (size_t)chunk * stride * sizeof(int32_t); a.rs_stride = (long long)rs_stride; }
-        a.rec = (d_out ? d_out : tmp_rec.p) + c0;
-        a.tab_off = d_tab_off ? d_tab_off + c0 : nullptr; a.score_table = d_score_table;
-        a.score_row = d_score_row; a.score_col = d_score_col;
-        rc = pmx_launch_general(a, false, st);
-        if (rc) { set_err("general kernel launch failed (%d)", rc); return rc < 0 ? rc : -1; }
-    }
+    PmxGeneralArgs a = general_args(cfg, dm, n, d_qbuf, d_qoff, 0, d_rbuf, d_roff, max_rlen);
+    a.bits = 32; a.rec = d_out ? d_out : tmp_rec.p;
+    a.tab_off = d_tab_off; a.score_table = d_score_table; a.score_row = d_score_row; a.score_col = d_score_col;
+    rc = general_batch(a, false, st);
+    if (rc) return rc;
     if (!d_out) HIP_OR_RET(hipStreamSynchronize(st));
     g_last_kernel = "pmx_general_kernel/tables";
     return 0;
@@ -2343,34 +2350,17 @@ static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n
     const bool two = chunk < n && !pmx_env("PMX_CIGAR_NO_OVERLAP");     // (diagnostics: sweep and walk back to back on one stream)
     uint32_t *tbuf = nullptr, *dops = nullptr; unsigned char *misc = nullptr;
     const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
-    const size_t fstride = (size_t)chunk / 2 + 16;           // per-block flags of a chunk's sweep (perm-table form / LDS-profile form), two sets
-    const size_t misc_bytes = (size_t)(4 * n + 2) * sizeof(int32_t) + 256 + scan_bytes + 256 + 2 * fstride * sizeof(int);
+    const size_t misc_bytes = (size_t)(4 * n + 2) * sizeof(int32_t) + 256 + scan_bytes + 256 + 2 * trace_flag_stride(chunk) * sizeof(int);
     if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE) ||
         scratch_reserve((size_t)n * ((size_t)mq + mr + 1) * sizeof(uint32_t), (void **)&dops, SCR_OPS) ||
         scratch_reserve(misc_bytes, (void **)&misc, SCR_CIG)) return -1;
     int32_t *nops = (int32_t *)misc, *beg = nops + n, *textlen = beg + 2 * n;
     void *scan_tmp = (void *)(((uintptr_t)(textlen + n + 2) + 255) & ~(uintptr_t)255);
     int *bflags = (int *)(((uintptr_t)scan_tmp + scan_bytes + 255) & ~(uintptr_t)255);
-    // sweeps of consecutive chunks alternate between the caller's stream and an internal one (the tail of one launch is
-    // backfilled by the next); every walk runs on the high-priority walk stream after its sweep
-    if (two) { HIP_OR_RET(hipEventRecord(g_tws.start, st)); HIP_OR_RET(hipStreamWaitEvent(g_tws.aux, g_tws.start, 0)); }
-    int idx = 0;
-    for (int64_t c0 = 0; c0 < n; c0 += chunk, ++idx) {
-        PmxBatch bk = b;
-        bk.n = (n - c0 < chunk) ? n - c0 : chunk;
-        bk.qoff = d_qoff + c0; bk.roff = d_roff + c0;
-        bk.blockflag = bflags + (size_t)(idx & 1) * fstride;
-        const hipStream_t sws = (two && (idx & 1)) ? g_tws.aux : st;
-        if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(sws, g_tws.walk_done[idx & 1], 0));     // this trace buffer's last walk is done
-        PmxWalkSplit sp = {two ? g_tws.walk : st, g_tws.sweep_done[idx & 1], two ? g_tws.walk_done[idx & 1] : nullptr,
-                           ops_base - c0, textlen + c0};
-        const int rc = pmx_launch_trace16(variant, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out + c0,
-                                          (uint32_t *)((unsigned char *)tbuf + (two ? (size_t)(idx & 1) * cbytes : 0)), Tmax,
-                                          dops, nullptr, nops + c0, beg + 2 * c0, sws, nullptr, &sp);
-        if (rc) { set_err("traceback launch failed (%d)", rc); return rc < 0 ? rc : -1; }
-    }
-    if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));      // the walk stream is in order: the last walk covers all
-    int rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan_tmp, scan_bytes, st);
+    const TraceOutputs o = {nullptr, dops, ops_base, nops, beg, textlen};
+    int rc = trace_chunks(cfg, dm, b, variant, Tmax, chunk, two, tbuf, cbytes, bflags, d_out, o, st, "traceback launch failed");
+    if (rc) return rc;
+    rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan_tmp, scan_bytes, st);
     if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
     rc = pmx_launch_cigar_render_slots(dops, d_qoff, d_roff, ops_base, nops, d_text_off, d_text, capacity, n, st);
     if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
@@ -2507,22 +2497,12 @@ static int cigar_chunk(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
         DevBuf<int64_t> dto;
         if (dto.try_alloc(n + 1)) { set_err("out of device memory"); return -2; }
         HIP_OR_RET(hipMemcpy(dto.p, tab_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-        int8_t *dtrace = nullptr; void *bound = nullptr;
+        int8_t *dtrace = nullptr;
         if (scratch_reserve((size_t)tab_off[n], (void **)&dtrace, SCR_TRACE)) return -1;
-        const size_t stride = (size_t)8 * mr;
-        const bool fits = pmx_general_lds_fits(dm.d.msize, dm.d.msize, mr);
-        const size_t rs_stride = fits ? 0 : (((size_t)mr + 8 + 15) & ~(size_t)15);
-        if (scratch_reserve((size_t)n * (stride * sizeof(int32_t) + rs_stride), &bound)) return -1;
-        PmxGeneralArgs a; memset(&a, 0, sizeof a);
-        if (!fits) { a.rs_scratch = (uint8_t *)bound + (size_t)n * stride * sizeof(int32_t); a.rs_stride = (long long)rs_stride; }
-        a.qbuf = dq.p; a.qoff = dqo.p; a.rbuf = dr.p; a.roff = dro.p; a.n = n; a.max_rlen = mr;
-        a.scores = dm.d.scores; a.mapper = dm.d.mapper; a.msize = dm.d.msize; a.mat_rows = dm.d.msize;
-        a.mode = cfg->mode; a.sg_flags = cfg->sg_flags; a.open = cfg->open; a.ext = cfg->extend; a.band = -1;
-        a.bits = cfg->width;
-        a.bound = (int32_t *)bound; a.bound_stride = (long long)stride;
+        PmxGeneralArgs a = general_args(cfg, dm, n, dq.p, dqo.p, 0, dr.p, dro.p, mr);
         a.rec = drec.p; a.tab_off = dto.p; a.trace_table = dtrace;
-        rc = pmx_launch_general(a, false, nullptr);
-        if (rc) { set_err("general kernel launch failed (%d)", rc); return rc < 0 ? rc : -1; }
+        rc = general_batch(a, false, nullptr);
+        if (rc) return rc;
         PmxWalkArgs w; memset(&w, 0, sizeof w);
         w.qbuf = dq.p; w.qoff = dqo.p; w.rbuf = dr.p; w.roff = dro.p; w.n = n;
         w.mapper = dm.d.mapper; w.mode = cfg->mode; w.trace_table = dtrace; w.tab_off = dto.p; w.rec = drec.p;
@@ -2576,20 +2556,9 @@ static int cigar_host_pipelined(const pmx_config_t *cfg, const DevMat &dm, int64
         int variant = 0, Tmax = 0; size_t tbytes = 0;
         if (cfg->width == 8 || pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) != 0 || variant < 10) return 1;
     }
-    static thread_local hipStream_t s_copy = nullptr, s_comp = nullptr;
-    static thread_local hipEvent_t s_up[8], s_done[8];
-    static thread_local int s_dev = -1;
-    int dev = 0; HIP_OR_RET(hipGetDevice(&dev));
-    if (s_dev != dev) {
-        if (s_copy) { (void)hipStreamDestroy(s_copy); (void)hipStreamDestroy(s_comp); for (int k = 0; k < 8; ++k) { (void)hipEventDestroy(s_up[k]); (void)hipEventDestroy(s_done[k]); } }
-        HIP_OR_RET(hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking));
-        HIP_OR_RET(hipStreamCreateWithFlags(&s_comp, hipStreamNonBlocking));
-        for (int k = 0; k < 8; ++k) {
-            HIP_OR_RET(hipEventCreateWithFlags(&s_up[k], hipEventDisableTiming));
-            HIP_OR_RET(hipEventCreateWithFlags(&s_done[k], hipEventDisableTiming));
-        }
-        s_dev = dev;
-    }
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t s_copy = hs.copy, s_comp = hs.comp; hipEvent_t *const s_up = hs.up, *const s_done = hs.done;
     const int K = n >= 262144 ? 8 : n >= 32768 ? 2 : 1;
     const size_t qbytes = (size_t)qoff[n], rbytes = (size_t)roff[n];
     // text capacity per slice: half a byte per sequence symbol + 16 per pair covers related reads many times over; a slice

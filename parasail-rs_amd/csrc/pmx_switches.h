@@ -61,7 +61,7 @@ struct PmxSwitchDoc { const char *name, *kind, *what; };
     X("PMX_BANDED_NO_SHARED_ROWS",    "force", "packed banded kernel, one shared query over <= 7 letters: each pair on its own query rows (forms 1 / 0) instead of both pairs of a lane group on the same rows") \
     X("PMX_BANDED_NO_STAGING",        "force", "banded: per-cell kernel (symbols from HBM) instead of the LDS-staged kernel with the lean interior loop") \
     X("PMX_GENERAL_ONE_WAVE",         "force", "general kernel: one wave per pair also for few long pairs (no pipelined sharing of a pair among the waves of a workgroup)") \
-    X("PMX_GENERAL_CHUNK_BYTES",      "value", "batches through the general kernel (score fallback, score tables): bytes of boundary scratch per chunk (tests force one-pair chunks)") \
+    X("PMX_GENERAL_CHUNK_BYTES",      "value", "batches through the general kernel (score and banded fallbacks, promotion pass, score tables, CIGAR fallback): bytes of boundary scratch per chunk (tests force one-pair chunks)") \
     X("PMX_NO_LONG_KERNEL",           "force", "few long pairs: the per-pair kernels instead of the kernel that spreads one pair's query bands over the chip") \
     X("PMX_LONG_ROWS_PER_LANE",       "value", "long-pair kernel: rows per lane (2, 4 or 16: bands of 128, 256 or 1 024 query rows)") \
     X("PMX_LONG_TWO_COLUMNS",         "force", "long-pair kernel: two columns per step also where the dispatcher's time model prefers one (batches, square pairs)") \
