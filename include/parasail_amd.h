@@ -309,6 +309,26 @@ int pmx_align_batch_banded_device(const pmx_config_t *cfg, int64_t n,
 int pmx_align_profile_batch_banded_device(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
                                           const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen,
                                           int32_t band, const int32_t *d_diag, pmx_record_t *d_out, void *stream);
+/* Banded batches with traceback (extension).  Same band rule as pmx_align_batch_banded: cell (i, j) of pair k belongs to the band
+ * iff |(j - i) - diag[k]| <= band.  cfg->want must contain PMX_WANT_CIGAR and/or PMX_WANT_STATS; PMX_WANT_SORTED is allowed.
+ * Records are the 32-bit banded records (cfg->width is ignored), identical to pmx_align_batch_banded's.  A pair whose band misses
+ * its end cell has score INT32_MIN / 2, an empty CIGAR and zero statistics.  profile != NULL: the profile arm (qbuf / qoff and
+ * max_qlen are ignored).  The CIGAR text follows pmx_align_batch_cigar (a block freed with pmx_free, cigar_off n + 1 entries); the
+ * device entry follows pmx_align_batch_cigar_device (n + 1 offsets; a pair whose text would cross cigar_capacity is not written;
+ * offsets start at 0).  NW, SG with any free ends, SW; square matrices of size <= 32 (31 letters + the wildcard: "ACGTA", nuc44 and
+ * BLOSUM62 included); any open / extend; bands 0 .. 63; any lengths.  Refused
+ * with -1 and a pmx_last_error() text before any GPU work: bands above 63, larger alphabets, PSSM matrices, a want without
+ * PMX_WANT_CIGAR and PMX_WANT_STATS. */
+int pmx_align_batch_banded_cigar(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                                 const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff,
+                                 int32_t band, const int32_t *diag,
+                                 pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */,
+                                 char **cigar_buf, int64_t *cigar_off /* NULL unless WANT_CIGAR */);
+int pmx_align_batch_banded_cigar_device(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                                        const uint8_t *d_qbuf, const int64_t *d_qoff, const uint8_t *d_rbuf, const int64_t *d_roff,
+                                        int32_t max_qlen, int32_t max_rlen, int32_t band, const int32_t *d_diag,
+                                        pmx_record_t *d_out, pmx_stats_t *d_stats_out,
+                                        char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream);
 
 /* CIGAR text for a batch (semi-global / global / local with traceback done on the device).
  * cigar_off has n+1 entries; *cigar_buf is malloc'd by the callee and freed with pmx_free. */
@@ -394,6 +414,10 @@ int pmx_bstrip_shape(int band, int *lanes_per_pair, int *offsets_per_lane);
  * LDS.  1, or 0 on an argument out of range. */
 int pmx_bstrip_geometry(int max_qlen, int max_rlen, int band, int lanes_per_pair, int offsets_per_lane, int q_shared,
                         int *rows, int *query_stream, int *selector_stream, long long *lds);
+/* Test hook of the banded traceback (parasail-rs_amd/csrc/pmx_banded.hip): the one bound of its trace scratch for a batch with
+ * queries <= max_qlen and references <= max_rlen (one shared query or not) -- lanes per pair, step pairs per pair, bytes per pair
+ * region (rows * lanes).  1, or 0 on an argument out of range. */
+int pmx_bandtr_geometry(int max_qlen, int max_rlen, int band, int q_shared, int *lanes_per_pair, int *rows, long long *stride);
 /* Test hook of the packed global / semi-global kernels (pmx_nwsg16.hip; model: tests/nwsgv_model.c): the host's range proof --
  * the bias nb of the stored form when the int16 window holds every pair of up to max_qlen x max_rlen under this scoring in a shape of
  * shape_rows rows (0: the dispatcher's estimate before a shape is picked), else 0.  rowx: the row-offset form (every width but 8). */

@@ -85,6 +85,19 @@ extern "C" {
         qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
         band: i32, diag: *const i32, out: *mut PmxRecord,
     ) -> c_int;
+    fn pmx_align_batch_banded_cigar(
+        cfg: *const PmxConfig, profile: *const parasail_profile_t, n: i64,
+        qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
+        band: i32, diag: *const i32, out: *mut PmxRecord, stats_out: *mut PmxStats,
+        cigar_buf: *mut *mut c_char, cigar_off: *mut i64,
+    ) -> c_int;
+    pub fn pmx_align_batch_banded_cigar_device(
+        cfg: *const PmxConfig, profile: *const parasail_profile_t, n: i64,
+        d_qbuf: *const u8, d_qoff: *const i64, d_rbuf: *const u8, d_roff: *const i64,
+        max_qlen: i32, max_rlen: i32, band: i32, d_diag: *const i32,
+        d_out: *mut PmxRecord, d_stats_out: *mut PmxStats,
+        d_cigar_text: *mut c_char, cigar_capacity: i64, d_cigar_off: *mut i64, stream: *mut c_void,
+    ) -> c_int;
     fn pmx_align_batch_multi(
         cfg: *const PmxConfig, n: i64,
         qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
@@ -278,6 +291,31 @@ impl Aligner {
             return Err(last_error());
         }
         Ok(records)
+    }
+
+    /// Banded batch with traceback (extension): the records of `banded_batch`, the CIGAR text of each pair's path inside the band
+    /// (empty where the band misses the end cell) and, with `want_stats`, matches / similar / length along that path.
+    pub fn banded_cigar_batch(&self, queries: Option<&Packed>, references: &Packed, diag: Option<&[i32]>, want_stats: bool)
+                              -> Result<(Vec<PmxRecord>, BatchCigars, Option<Vec<PmxStats>>)> {
+        let band = self.bandwidth.ok_or(Error::NoBandwidth)?;
+        let n = references.len();
+        let mut records = vec![PmxRecord::default(); n];
+        let mut stats = if want_stats { Some(vec![PmxStats::default(); n]) } else { None };
+        let stats_ptr = stats.as_mut().map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let mut off = vec![0i64; n + 1];
+        let mut text: *mut c_char = std::ptr::null_mut();
+        let cfg = self.pmx_config(PMX_WANT_CIGAR | if want_stats { PMX_WANT_STATS } else { 0 });
+        let (qb, qo) = queries.map_or((std::ptr::null(), std::ptr::null()), |q| (q.buf.as_ptr(), q.off.as_ptr()));
+        let prof = if self.profile.is_null() { std::ptr::null() } else { **self.profile as *const parasail_profile_t };
+        let rc = unsafe {
+            pmx_align_batch_banded_cigar(&cfg, prof, n as i64, qb, qo, references.buf.as_ptr(), references.off.as_ptr(),
+                                         band, diag.map_or(std::ptr::null(), |d| d.as_ptr()), records.as_mut_ptr(), stats_ptr,
+                                         &mut text, off.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok((records, BatchCigars { text, off }, stats))
     }
 
     /// One process driving several GPUs of the node: contiguous blocks of about equal cell counts, one per listed device;

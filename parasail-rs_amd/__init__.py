@@ -133,6 +133,11 @@ _sig("pmx_align_batch_banded_device", C.c_int, C.POINTER(pmx_config_t), C.c_int6
      C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_align_profile_batch_banded_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_align_batch_banded_cigar", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p)
+_sig("pmx_align_batch_banded_cigar_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_void_p)
 _sig("pmx_align_batch_multi", C.c_int, C.POINTER(pmx_config_t), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 _sig("pmx_align_profile_batch_multi", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -815,6 +820,39 @@ class Aligner:
         if rc:
             raise BatchError(lib.pmx_last_error().decode())
         return out
+
+    def align_batch_banded_cigar(self, queries, references, band, diag=None, stats=False):
+        """Banded batch with traceback (extension): the records of align_batch_banded, the CIGAR string of each pair's path inside
+        the band ("" where the band misses the end cell) and, with stats=True, matches / similar / length along it.
+        Returns (records, cigars) or (records, cigars, stats)."""
+        rbuf, roff = pack(references)
+        n = len(roff) - 1
+        cfg = self._config()
+        cfg.want = WANT_CIGAR | (WANT_STATS if stats else 0)
+        out = np.zeros(n, dtype=RECORD_DTYPE)
+        st = np.zeros(n, dtype=STATS_DTYPE) if stats else None
+        coff = np.zeros(n + 1, dtype=np.int64)
+        d = None if diag is None else np.ascontiguousarray(diag, dtype=np.int32)
+        if self._profile.is_null():
+            qbuf, qoff = pack(queries)
+            if len(qoff) - 1 != n:
+                raise BatchError("queries and references differ in count")
+            prof, qp, qop = None, qbuf.ctypes.data, qoff.ctypes.data
+        else:
+            prof, qp, qop = self._profile.inner, None, None
+        cbuf = C.c_void_p()
+        rc = lib.pmx_align_batch_banded_cigar(C.byref(cfg), prof, n, qp, qop, rbuf.ctypes.data, roff.ctypes.data, int(band),
+                                              d.ctypes.data if d is not None else None, out.ctypes.data,
+                                              st.ctypes.data if st is not None else None, C.byref(cbuf), coff.ctypes.data)
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        try:
+            raw = C.string_at(cbuf.value, int(coff[n])) if cbuf.value and coff[n] else b""
+        finally:
+            if cbuf.value:
+                lib.pmx_free(cbuf)
+        cigars = [raw[coff[k]:coff[k + 1]].decode() for k in range(n)]
+        return (out, cigars, st) if stats else (out, cigars)
 
     def align_batch_cigar(self, queries, references):
         qbuf, qoff = pack(queries)

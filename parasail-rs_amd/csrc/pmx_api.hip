@@ -2687,6 +2687,183 @@ extern "C" int pmx_align_batch_cigar(const pmx_config_t *cfg, int64_t n,
 }
 
 
+// ---- banded batches with traceback (extension) ---------------------------------------------------------------------------
+// The trace form of the 32-bit banded kernels (pmx_banded.hip) writes the band's decision bits to HBM scratch in the anti-diagonal
+// layout of pmx_common.h, and pmx_walkb_kernel (pmx_walkb.hip) walks them: run-length ops into the per-pair slots of the device CIGAR
+// entry, and / or the path's statistics.  Same band rule, records and oracle as banded_device.
+static int banded_trace_check(const pmx_config_t *cfg, int32_t band)
+{
+    if (check_cfg(cfg)) return -1;
+    if (band < 0 || band > 63) { set_err("banded traceback supports bands 0 .. 63 (got %d)", band); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
+    if (cfg->matrix->size > PMX_MAX_FAST_MSIZE) { set_err("banded traceback supports alphabets of up to %d letters (matrix size %d)", PMX_MAX_FAST_MSIZE, cfg->matrix->size); return -1; }
+    if (!(cfg->want & (PMX_WANT_CIGAR | PMX_WANT_STATS))) { set_err("banded traceback needs PMX_WANT_CIGAR and / or PMX_WANT_STATS in cfg->want"); return -1; }
+    if (cfg->want & ~(PMX_WANT_CIGAR | PMX_WANT_STATS | PMX_WANT_SORTED)) { set_err("unknown want bits 0x%x", cfg->want); return -1; }
+    return 0;
+}
+
+// Validated by the caller.  d_qoff is NULL with one shared query of q_shared bytes; offsets start at 0.  Asynchronous on `st`.
+static int banded_trace_device(const pmx_config_t *cfg, int64_t n, const uint8_t *d_qbuf, const int64_t *d_qoff, int q_shared,
+                               const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_qlen, int32_t max_rlen,
+                               int32_t band, const int32_t *d_diag, pmx_record_t *d_out, pmx_stats_t *d_stats,
+                               char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st)
+{
+    const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
+    DevMat dm;
+    if (get_devmat(cfg->matrix, &dm)) return -1;
+    if (trace_ws_init()) return -1;
+    const PmxBandTrGeometry g = pmx_bandtr_geometry_of(max_qlen, max_rlen, band);
+    // chunks as in cigar_device_run: at most ~12 GB of trace each (two buffers), at most 15 % of the free HBM, two once it pays
+    double chunk_bytes = 12e9;
+    { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess && 0.15 * (double)fb < chunk_bytes) chunk_bytes = 0.15 * (double)fb; }
+    if (const char *e = pmx_env("PMX_CIGAR_CHUNK_BYTES")) chunk_bytes = atof(e);      // tests force small chunks
+    // The walk (one lane per pair) costs about what the sweep does and only the last chunk's walk is exposed: eight chunks once the
+    // batch is worth it (measured on 1.25 M pairs of 250 x 250, band 15: two chunks 24.3 ms, nine 20.5 ms)
+    int64_t nchunks = (int64_t)((double)n * (double)g.stride / chunk_bytes) + 1;
+    if (nchunks < 8 && n >= 8 * 16384) nchunks = 8;
+    else if (nchunks < 2 && n >= 16384) nchunks = 2;
+    int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
+    if (chunk > n) chunk = n;
+    const bool two = chunk < n;
+    const size_t cbytes = ((size_t)chunk * (size_t)g.stride + 255) & ~(size_t)255;
+    uint8_t *tbuf = nullptr; uint32_t *dops = nullptr; unsigned char *misc = nullptr;
+    const size_t scan_bytes = want_cigar ? pmx_text_scan_scratch_bytes(n) : 0;
+    const size_t misc_bytes = (size_t)(2 * n + 2) * sizeof(int32_t) + 256 + (size_t)(n + 1) * sizeof(int64_t) + 256 + scan_bytes;
+    if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE) ||
+        (want_cigar && scratch_reserve((size_t)n * ((size_t)max_qlen + max_rlen + 1) * sizeof(uint32_t), (void **)&dops, SCR_OPS)) ||
+        scratch_reserve(misc_bytes, (void **)&misc, SCR_CIG)) return -1;
+    int32_t *nops = (int32_t *)misc, *textlen = nops + n;
+    int64_t *slot_qoff = (int64_t *)(((uintptr_t)(textlen + n + 2) + 255) & ~(uintptr_t)255);
+    void *scan_tmp = (void *)(((uintptr_t)(slot_qoff + n + 1) + 255) & ~(uintptr_t)255);
+    if (want_cigar && q_shared) {                 // the slot render finds a slot from query offsets: k * qlen for the shared query
+        const int rc = pmx_launch_shared_offsets(slot_qoff, n, q_shared, st);
+        if (rc) { set_err("offset kernel launch failed (%d)", rc); return rc; }
+    }
+    const int64_t *sq = q_shared ? slot_qoff : d_qoff;
+    const char *kname = "pmx_banded_kernel/trace";
+    if (two) { HIP_OR_RET(hipEventRecord(g_tws.start, st)); HIP_OR_RET(hipStreamWaitEvent(g_tws.aux, g_tws.start, 0)); }
+    int idx = 0;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk, ++idx) {
+        const int64_t m = (n - c0 < chunk) ? n - c0 : chunk;
+        const hipStream_t sws = (two && (idx & 1)) ? g_tws.aux : st;
+        if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(sws, g_tws.walk_done[idx & 1], 0));     // this trace buffer's last walk is done
+        const PmxBandTrace tr = {tbuf + (two ? (size_t)(idx & 1) * cbytes : 0), g.stride};
+        const int64_t *qo = d_qoff ? d_qoff + c0 : nullptr;
+        const int32_t *dg = d_diag ? d_diag + c0 : nullptr;
+        int rc = pmx_launch_banded_trace(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0,
+                                         max_qlen, max_rlen, band, dg, d_out + c0, tr, sws, &kname);
+        if (rc) { set_err("banded trace launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
+        hipStream_t ws = sws;
+        if (two) {
+            HIP_OR_RET(hipEventRecord(g_tws.sweep_done[idx & 1], sws));
+            HIP_OR_RET(hipStreamWaitEvent(g_tws.walk, g_tws.sweep_done[idx & 1], 0));
+            ws = g_tws.walk;
+        }
+        if (want_stats)
+            rc = pmx_launch_walkb(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0, band, dg,
+                                  d_out + c0, tr, nullptr, 0, nullptr, nullptr, nullptr, d_stats + c0, ws);
+        if (!rc && want_cigar)
+            rc = pmx_launch_walkb(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0, band, dg,
+                                  d_out + c0, tr, sq + c0, -c0, dops, nops + c0, textlen + c0, nullptr, ws);
+        if (rc) { set_err("banded walk launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
+        if (two) HIP_OR_RET(hipEventRecord(g_tws.walk_done[idx & 1], ws));
+    }
+    if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));      // the walk stream is in order: the last walk covers all
+    if (want_cigar) {
+        int rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan_tmp, scan_bytes, st);
+        if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
+        rc = pmx_launch_cigar_render_slots(dops, sq, d_roff, 0, nops, d_text_off, d_text, capacity, n, st);
+        if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
+    }
+    g_last_kernel = strcmp(kname, "pmx_banded_staged_kernel/trace") == 0 ? "pmx_banded_staged_kernel/trace + pmx_walkb_kernel"
+                                                                          : "pmx_banded_kernel/trace + pmx_walkb_kernel";
+    return 0;
+}
+
+extern "C" int pmx_align_batch_banded_cigar_device(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                                                   const uint8_t *d_qbuf, const int64_t *d_qoff, const uint8_t *d_rbuf, const int64_t *d_roff,
+                                                   int32_t max_qlen, int32_t max_rlen, int32_t band, const int32_t *d_diag,
+                                                   pmx_record_t *d_out, pmx_stats_t *d_stats_out,
+                                                   char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream)
+{
+    if (banded_trace_check(cfg, band)) return -1;
+    if (n <= 0) return 0;
+    if (profile && profile->matrix != cfg->matrix) { set_err("profile was built with a different matrix"); return -1; }
+    if (!d_rbuf || !d_roff || !d_out || (!profile && (!d_qbuf || !d_qoff))) { set_err("null buffer"); return -1; }
+    if ((cfg->want & PMX_WANT_STATS) && !d_stats_out) { set_err("stats requested without a stats buffer"); return -1; }
+    if ((cfg->want & PMX_WANT_CIGAR) && (!d_cigar_text || !d_cigar_off)) { set_err("null cigar output"); return -1; }
+    if ((!profile && max_qlen <= 0) || max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    const uint8_t *dq = d_qbuf;
+    if (profile && profile_device_query(profile, &dq)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return banded_trace_device(cfg, n, dq, profile ? nullptr : d_qoff, profile ? profile->s1Len : 0, d_rbuf, d_roff,
+                               profile ? profile->s1Len : max_qlen, max_rlen, band, d_diag, d_out, d_stats_out,
+                               d_cigar_text, cigar_capacity, d_cigar_off, (hipStream_t)stream);
+}
+
+// Host buffers in, host records / statistics / CIGAR text out (the text as pmx_align_batch_cigar's: a block freed with pmx_free).
+extern "C" int pmx_align_batch_banded_cigar(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                                            const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff,
+                                            int32_t band, const int32_t *diag,
+                                            pmx_record_t *out, pmx_stats_t *stats_out, char **cigar_buf, int64_t *cigar_off)
+{
+    if (banded_trace_check(cfg, band)) return -1;
+    const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
+    if (want_cigar && (!cigar_buf || !cigar_off)) { set_err("null cigar output"); return -1; }
+    if (want_stats && !stats_out) { set_err("stats requested without a stats buffer"); return -1; }
+    if (want_cigar) *cigar_buf = nullptr;
+    if (n <= 0) return 0;
+    if (!rbuf || !roff || !out || (!profile && (!qbuf || !qoff))) { set_err("null buffer"); return -1; }
+    if (profile && profile->matrix != cfg->matrix) { set_err("profile was built with a different matrix"); return -1; }
+    int32_t mq = 0, mr = 0; bool bad = false;
+    host_maxlens(n, roff, &mr, &bad);
+    if (!profile) host_maxlens(n, qoff, &mq, &bad); else mq = profile->s1Len;
+    if (bad || roff[0] != 0 || (!profile && qoff[0] != 0)) { set_err("bad offsets (every sequence needs length >= 1, offsets start at 0)"); return -1; }
+    const int64_t qbytes = profile ? (int64_t)n * profile->s1Len : qoff[n];
+    // text capacity: half a byte per symbol + 16 per pair covers related pairs many times over; a batch that needs more runs again
+    int64_t capacity = want_cigar ? ((qbytes + roff[n]) / 2 + 16 * n + 256) : 0;
+    DevBuf<uint8_t> dq, dr; DevBuf<int64_t> dqo, dro, dtoff; DevBuf<int32_t> dd; DevBuf<pmx_record_t> drec; DevBuf<pmx_stats_t> dst;
+    DevBuf<char> dtext;
+    if (dr.try_alloc((size_t)roff[n]) || dro.try_alloc(n + 1) || drec.try_alloc(n) || (diag && dd.try_alloc(n)) ||
+        (want_stats && dst.try_alloc(n)) || (want_cigar && (dtoff.try_alloc(n + 1) || dtext.try_alloc((size_t)capacity + 1))) ||
+        (!profile && (dq.try_alloc((size_t)qoff[n]) || dqo.try_alloc(n + 1)))) { set_err("out of device memory"); return -2; }
+    HIP_OR_RET(hipMemcpy(dr.p, rbuf, (size_t)roff[n], hipMemcpyHostToDevice));
+    HIP_OR_RET(hipMemcpy(dro.p, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+    if (diag) HIP_OR_RET(hipMemcpy(dd.p, diag, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    if (!profile) {
+        HIP_OR_RET(hipMemcpy(dq.p, qbuf, (size_t)qoff[n], hipMemcpyHostToDevice));
+        HIP_OR_RET(hipMemcpy(dqo.p, qoff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+    }
+    for (int pass = 0; pass < 2; ++pass) {
+        const int rc = pmx_align_batch_banded_cigar_device(cfg, profile, n, dq.p, dqo.p, dr.p, dro.p, mq, mr, band, diag ? dd.p : nullptr,
+                                                           drec.p, dst.p, dtext.p, capacity, dtoff.p, nullptr);
+        if (rc) return rc;
+        HIP_OR_RET(hipDeviceSynchronize());
+        if (!want_cigar) break;
+        HIP_OR_RET(hipMemcpy(cigar_off, dtoff.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
+        if (cigar_off[n] <= capacity) break;
+        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
+        (void)hipFree(dtext.p); dtext.p = nullptr;
+        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    }
+    HIP_OR_RET(hipMemcpy(out, drec.p, sizeof(pmx_record_t) * n, hipMemcpyDeviceToHost));
+    if (want_stats) HIP_OR_RET(hipMemcpy(stats_out, dst.p, sizeof(pmx_stats_t) * n, hipMemcpyDeviceToHost));
+    if (want_cigar) {
+        TextBuf text;
+        char *dst_text = text.grow((size_t)cigar_off[n]);
+        if (!dst_text) { set_err("out of memory"); return -1; }
+        if (cigar_off[n]) {
+            const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
+        }
+        text.len = (size_t)cigar_off[n];
+        text.p[text.len] = 0;
+        *cigar_buf = text.p; g_text_pool.handed_out(text.p, text.cap);
+    }
+    return 0;
+}
+
 // ============================================================================= multi-GPU ===
 // Pairs are independent (the reference's only parallel story is user threads sharing a read-only profile,
 // tests/test_parasail.rs:689-723), so a batch shards across the GPUs of a node with no data-path collective: a contiguous block

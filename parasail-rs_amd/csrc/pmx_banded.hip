@@ -28,15 +28,39 @@ __device__ __forceinline__ bool b_better_sw(const BCand &a, const BCand &b)     
     return a.i < b.i;
 }
 
+// Trace form (both kernels): the instantiation with one PmxBandTrace argument (pmx_common.h) also writes, per band cell, the decision
+// bits ND (H not from the diagonal), NDL (H not from F), EO (E of the next column opened), FO (F of the next row opened) with the
+// oracle's comparisons, into the anti-diagonal layout of pmx_common.h.  The score-only form keeps the parameter list it had.
+__device__ __forceinline__ PmxBandTrace band_trace_arg() { return {nullptr, 0}; }
+__device__ __forceinline__ PmxBandTrace band_trace_arg(PmxBandTrace t) { return t; }
+// the lane's view of its pair's region: the even origin s0, the step pairs it writes (never past the region, whatever lengths the
+// caller declared) and its byte of step pair 0.  (pmx_banded_kernel derives it inside its trace-only blocks: state declared outside
+// them changed the score-only form's register allocation.)
+struct BandTraceLane { int s0, rows; uint8_t *p; };
 template <int LP>
+__device__ __forceinline__ BandTraceLane band_trace_lane(const PmxBandTrace &tc, int s_first, int s_last, int band, int d0, long long pair, int x)
+{
+    BandTraceLane t;
+    t.s0 = s_first - ((s_first + band - d0) & 1);
+    t.rows = min(s_last >= t.s0 ? ((s_last - t.s0) >> 1) + 1 : 0, (int)(tc.stride / LP));
+    t.p = tc.buf + pair * tc.stride + x;
+    return t;
+}
+__device__ __forceinline__ int band_nibble(int hd, int H, int E, int F, int open, int ext)
+{
+    return ((hd < E || hd < F) ? 8 : 0) | (F < E ? 4 : 0) | (H - open > E - ext ? 2 : 0) | (H - open > F - ext ? 1 : 0);
+}
+
+template <int LP, typename... Trace>
 __global__ __launch_bounds__(64)
 void pmx_banded_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, int q_shared,
                        const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff, long long n,
                        const int16_t *__restrict__ gmat, const uint8_t *__restrict__ gmap, int msize,
                        int mode, int sg_flags, int open, int ext, int band, const int32_t *__restrict__ diag,
                        const unsigned *__restrict__ list /* optional: the pairs to work on ... */, const int *__restrict__ n_dev /* ... and their count (device) */,
-                       pmx_record_t *__restrict__ out)
+                       pmx_record_t *__restrict__ out, Trace... trace)
 {
+    constexpr bool TR = sizeof...(Trace) > 0;
     __shared__ int16_t mat[PMX_MAX_FAST_MSIZE * PMX_MAX_FAST_MSIZE];
     __shared__ unsigned char map[256];
     for (int x = threadIdx.x; x < msize * msize; x += 64) mat[x] = gmat[x];
@@ -98,7 +122,7 @@ void pmx_banded_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
     int ni, nj, nu;
     cell_of(s_first, ni, nj, nu);
     int sc_next = score_of(ni, nj);
-
+    int trlo = 0;                                               // trace form: the even step's nibble, until its byte is written
     for (int t = 0; t < nsteps; ++t) {
         const int s = s_first + t;
         int i, j, u;
@@ -121,6 +145,12 @@ void pmx_banded_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
         int F = max(upF - ext, upH - open); if (F < B_NEG) F = B_NEG;
         int H = max(dg + sc, max(E, F));
         if (sw && H < 0) H = 0;
+        if constexpr (TR) {
+            const BandTraceLane tl = band_trace_lane<LP>(band_trace_arg(trace...), s_first, s_last, band, d0, pair, x);
+            const int tau = s - tl.s0, nib = band_nibble(dg + sc, H, E, F, open, ext);
+            if (!(tau & 1)) trlo = nib;
+            else if (have && (tau >> 1) < tl.rows) tl.p[(size_t)(tau >> 1) * LP] = (uint8_t)(trlo | (nib << 4));
+        }
         if (!active) { H = B_NEG; E = B_NEG; F = B_NEG; }
         else {
             const BCand c = {H, i, j};
@@ -132,6 +162,11 @@ void pmx_banded_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
             }
         }
         Hm2 = Hm1; Hm1 = H; Em1 = E; Fm1 = F;
+    }
+    if constexpr (TR) {                                         // the last step was even: its byte is still open
+        const BandTraceLane tl = band_trace_lane<LP>(band_trace_arg(trace...), s_first, s_last, band, d0, pair, x);
+        const int tau = s_first + nsteps - 1 - tl.s0;
+        if (nsteps > 0 && !(tau & 1) && have && (tau >> 1) < tl.rows) tl.p[(size_t)(tau >> 1) * LP] = (uint8_t)trlo;
     }
 
     // ---- reduction over the group ----
@@ -193,14 +228,15 @@ void pmx_banded_retry(int mode, int sg_flags, int open, int ext, const PmxDevMat
 //   * cells outside the band are never masked in the lean loop: lanes beyond the band compute on "minus infinity" inputs that
 //     stay far below every real value, only the band's last lane is forced on odd steps (its odd diagonal is outside).
 // Same results as the kernel above, cell for cell (tests/test_gpu_banded.py runs both against the banded oracle).
-template <int LP, bool SW>
+template <int LP, bool SW, typename... Trace>
 __global__ __launch_bounds__(64)
 void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, int q_shared,
                               const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff, long long n,
                               const int16_t *__restrict__ gmat, const uint8_t *__restrict__ gmap, int msize,
                               int mode, int sg_flags, int open, int ext, int band, const int32_t *__restrict__ diag,
-                              int QC, int RC /* staging capacity per pair: symbols */, pmx_record_t *__restrict__ out)
+                              int QC, int RC /* staging capacity per pair: symbols */, pmx_record_t *__restrict__ out, Trace... trace)
 {
+    constexpr bool TR = sizeof...(Trace) > 0;
     __shared__ int16_t mat[PMX_MAX_FAST_MSIZE * PMX_MAX_FAST_MSIZE];
     __shared__ unsigned char map[256];
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
@@ -258,6 +294,14 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
     int Hm1 = B_NEG, Em1 = B_NEG, Fm1 = B_NEG, Hm2 = B_NEG;
     BCand best = {B_NEG, 0, 0}, brow = {B_NEG, 0, 0}, bcol = {B_NEG, 0, 0};
     int corner = B_NEG;
+    // trace form: step pair m = tau / 2 of this lane is the byte trp[m * LP] (s0 is the layout's even origin already)
+    int tr_rows = s_last >= s0 ? ((s_last - s0) >> 1) + 1 : 0;
+    uint8_t *trp = nullptr;
+    int trlo = 0;
+    if constexpr (TR) {                                               // (never past the region, whatever lengths the caller declared)
+        const PmxBandTrace tc = band_trace_arg(trace...);
+        trp = tc.buf + pair * tc.stride + x; tr_rows = min(tr_rows, (int)(tc.stride / LP));
+    }
 
     auto checked_step = [&](int tau) {
         const int p = tau & 1, m = tau >> 1;
@@ -278,6 +322,11 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
         int F = max(upF - ext, upH - open); if (F < B_NEG) F = B_NEG;
         int H = max(dg + sc, max(E, F));
         if (SW && H < 0) H = 0;
+        if constexpr (TR) {
+            const int nib = band_nibble(dg + sc, H, E, F, open, ext);
+            if (!p) trlo = nib;
+            else if (have && m < tr_rows) trp[(size_t)m * LP] = (uint8_t)(trlo | (nib << 4));
+        }
         if (!active) { H = B_NEG; E = B_NEG; F = B_NEG; }
         else {
             const BCand c = {H, i, j};
@@ -341,11 +390,13 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
             qp += 4; rp += 4;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
+                int nibE = 0;
                 {   // even step: left from lane x - 1, up = own previous cell
                     const int lHo = below(Ho1), lEe = below(Ee1);
                     const int E = max(lEe, lHo), F = max(Fe1, Ho1);
                     int H = max(Hr2 + sc[2 * k], max(E, F));
                     if (SW) { H = max(H, floorv); if (H > bH) { bH = H; bT = 8 * B + 2 * k; } }
+                    if constexpr (TR) nibE = band_nibble(Hr2 + sc[2 * k], H, E, F, open, ext);
                     Hr2 = Hr1; Hr1 = H; Ho1 = H - open; Ee1 = E - ext; Fe1 = F - ext;
                 }
                 {   // odd step: up from lane x + 1, left = own previous cell
@@ -355,6 +406,11 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
                     if (SW) H = max(H, floorv);
                     H &= keep_odd; E &= keep_odd; F &= keep_odd;      // (nothing real may leak to the lanes beyond the band)
                     if (SW) { if (H > bH) { bH = H; bT = 8 * B + 2 * k + 1; } }
+                    // (interior cells: every compared value inside the band is finite, or both sides are "minus infinity" where the
+                    //  walk never looks -- the biased, unclamped values give the oracle's bits)
+                    if constexpr (TR) {
+                        if (have && 4 * B + k < tr_rows) trp[(size_t)(4 * B + k) * LP] = (uint8_t)(nibE | (band_nibble(Hr2 + sc[2 * k + 1], H, E, F, open, ext) << 4));
+                    }
                     Hr2 = Hr1; Hr1 = H; Ho1 = H - open; Ee1 = E - ext; Fe1 = F - ext;
                 }
             }
@@ -368,6 +424,9 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
         tau = 8 * (Bhi + 1);
     }
     for (; tau < nsteps; ++tau) checked_step(tau);
+    if constexpr (TR) {                                               // the last step was even: its byte is still open
+        if ((nsteps & 1) && have && (nsteps >> 1) < tr_rows) trp[(size_t)(nsteps >> 1) * LP] = (uint8_t)trlo;
+    }
 
     // ---- reduction over the group (as in the kernel above) -------------------------------------------------------------------
 #pragma unroll
@@ -772,6 +831,65 @@ int pmx_launch_banded(int mode, int sg_flags, int open, int ext, const PmxDevMat
 #undef LB
 #undef LS
     if (kernel_name) *kernel_name = staged ? "pmx_banded_staged_kernel" : "pmx_banded_kernel";
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+// ---- trace form: geometry and launch -----------------------------------------------------------------------------------
+// A pair's band crosses at most min(qlen + rlen - 1, 2 min(qlen, rlen) + 2 band - 1) steps: one diagonal crosses at most 2 min - 1
+// steps, and the first steps of two diagonals of the band lie at most 2 band apart.  The bound is reached (a centre of +-band with
+// the longer sequence at least 2 band longer, or a band that holds both corners), also with the query length fixed (one shared
+// query).  The even origin s0 may add one step in front: rows = (steps + 2) / 2 step pairs.
+PmxBandTrGeometry pmx_bandtr_geometry_of(int max_qlen, int max_rlen, int band)
+{
+    PmxBandTrGeometry g;
+    g.LP = band <= 15 ? 16 : band <= 31 ? 32 : 64;
+    const long long mn = std::min(max_qlen, max_rlen);
+    const long long steps = std::min((long long)max_qlen + max_rlen - 1, 2 * mn + 2LL * band - 1);
+    g.rows = (int)((steps + 2) / 2);
+    g.stride = (long long)g.rows * g.LP;
+    return g;
+}
+extern "C" int pmx_bandtr_geometry(int max_qlen, int max_rlen, int band, int q_shared, int *lanes_per_pair, int *rows, long long *stride)
+{
+    (void)q_shared;                                      // (the bound is reached with the query length fixed as well)
+    if (max_qlen <= 0 || max_rlen <= 0 || band < 0 || band > 63) return 0;
+    const PmxBandTrGeometry g = pmx_bandtr_geometry_of(max_qlen, max_rlen, band);
+    if (lanes_per_pair) *lanes_per_pair = g.LP;
+    if (rows) *rows = g.rows;
+    if (stride) *stride = g.stride;
+    return 1;
+}
+
+int pmx_launch_banded_trace(int mode, int sg_flags, int open, int ext, const PmxDevMatrix &m, long long n,
+                            const uint8_t *qbuf, const int64_t *qoff, int q_shared, const uint8_t *rbuf, const int64_t *roff,
+                            int max_qlen, int max_rlen, int band, const int32_t *diag, pmx_record_t *out, const PmxBandTrace &tr,
+                            hipStream_t stream, const char **kernel_name)
+{
+    if (n <= 0) return 0;
+    // (the staging rule of pmx_launch_banded)
+    const int LPs = band <= 15 ? 16 : band <= 31 ? 32 : 64, NPW = 64 / LPs;
+    const int QC = (max_qlen + 3) & ~3, RC = (max_rlen + 3) & ~3;
+    const size_t lds = (size_t)NPW * ((size_t)QC * 2 + RC);
+    const bool staged = lds <= 60 * 1024 && open <= 512 && ext <= 512 && (long long)max_qlen + max_rlen < (1 << 20);
+    const bool sw = mode == PMX_MODE_SW;
+    const unsigned grid = (unsigned)((n + NPW - 1) / NPW);
+#define LBT(LP) hipLaunchKernelGGL((pmx_banded_kernel<LP, PmxBandTrace>), dim3(grid), dim3(64), 0, stream, \
+                                   qbuf, qoff, q_shared, rbuf, roff, n, m.scores, m.mapper, m.msize, mode, sg_flags, open, ext, band, diag, nullptr, nullptr, out, tr)
+#define LST(LP, SWF) hipLaunchKernelGGL((pmx_banded_staged_kernel<LP, SWF, PmxBandTrace>), dim3(grid), dim3(64), lds, stream, \
+                                        qbuf, qoff, q_shared, rbuf, roff, n, m.scores, m.mapper, m.msize, mode, sg_flags, open, ext, band, diag, QC, RC, out, tr)
+    if (staged) {
+        if (band <= 15) { if (sw) LST(16, true); else LST(16, false); }
+        else if (band <= 31) { if (sw) LST(32, true); else LST(32, false); }
+        else { if (sw) LST(64, true); else LST(64, false); }
+    } else {
+        if (band <= 15) LBT(16);
+        else if (band <= 31) LBT(32);
+        else LBT(64);
+    }
+#undef LBT
+#undef LST
+    if (kernel_name) *kernel_name = staged ? "pmx_banded_staged_kernel/trace" : "pmx_banded_kernel/trace";
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
 }

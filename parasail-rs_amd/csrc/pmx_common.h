@@ -167,6 +167,45 @@ int pmx_launch_banded(int mode, int sg_flags, int open, int ext, const PmxDevMat
                       int max_qlen, int max_rlen, int band, const int32_t *diag, pmx_record_t *out, hipStream_t stream, const char **kernel_name = nullptr,
                       void *sort_scratch = nullptr /* pmx_sort_scratch_bytes(n) bytes: lets the packed forms pair up bands of equal length */,
                       unsigned *retry_list = nullptr, int *retry_count = nullptr /* [count][n entries] twice (retry_count first): lets the band-strip kernel hand pairs back */);
+// Trace form of the 32-bit banded kernels (pmx_banded.hip) and its walk (pmx_walkb.hip).  Layout: a pair's steps s = i + j are
+// counted from the even origin s0 (s0 + band - d0 even, s0 = s_first or s_first - 1); on step s lane x of the pair's lane group holds
+// band diagonal u = 2x + ((s - s0) & 1), and step pair m = (s - s0) / 2 of lane x is the byte buf[pair * stride + m * LP + x]: the
+// nibble ND NDL EO FO (as in pmx_walkp.hip) of the even step low, of the odd step high.  Every cell of step pair m lies in row
+// m + (s0 + band - d0) / 2 - x.
+struct PmxBandTrace { uint8_t *buf; long long stride; };
+// Step range of one pair's band: the band's cells inside the matrix lie on steps s_first .. s_last (s_last = -1: none); rows = the
+// pair's step pairs from s0.
+struct PmxBandSteps { int s_first, s_last, s0, rows; };
+__host__ __device__ inline PmxBandSteps pmx_band_steps(int ql, int rl, int band, int d0)
+{
+    PmxBandSteps r;
+    const int dlo = d0 - band, dhi = d0 + band;
+    r.s_first = dlo > 0 ? dlo : dhi < 0 ? -dhi : 0;
+    int i1 = ql - 1, j1 = rl - 1;
+    if (j1 - i1 > dhi) j1 = i1 + dhi; else if (j1 - i1 < dlo) i1 = j1 - dlo;
+    r.s_last = (i1 >= 0 && j1 >= 0 && !(dlo > rl - 1 || dhi < -(ql - 1))) ? i1 + j1 : -1;
+    r.s0 = r.s_first - ((r.s_first + band - d0) & 1);
+    r.rows = r.s_last >= r.s0 ? ((r.s_last - r.s0) >> 1) + 1 : 0;
+    return r;
+}
+// The one bound of a launch (exported as the test hook pmx_bandtr_geometry): LP lanes per pair, at most `rows` step pairs per pair
+// of up to max_qlen x max_rlen (any centre), stride = rows * LP bytes per pair region.  Scratch sizing and walk addressing use it.
+struct PmxBandTrGeometry { int LP, rows; long long stride; };
+PmxBandTrGeometry pmx_bandtr_geometry_of(int max_qlen, int max_rlen, int band);
+// The traced sweep: staged form where both sequences fit the LDS, else the checked form.  0 launched, <0 HIP error.
+int pmx_launch_banded_trace(int mode, int sg_flags, int open, int ext, const PmxDevMatrix &m, long long n,
+                            const uint8_t *qbuf, const int64_t *qoff, int q_shared, const uint8_t *rbuf, const int64_t *roff,
+                            int max_qlen, int max_rlen, int band, const int32_t *diag, pmx_record_t *out, const PmxBandTrace &tr,
+                            hipStream_t stream, const char **kernel_name);
+// Walk over the traced band (pmx_walkb.hip): ops (pmx_walkp's slot format; slot of pair k ends at slot_qoff[k + 1] + roff[k + 1] + k + 1
+// - ops_base) with nops / textlen, or the path's statistics (stats_out != nullptr).  0 launched, <0 HIP error.
+int pmx_launch_walkb(int mode, int sg_flags, int open, int ext, const PmxDevMatrix &m, long long n,
+                     const uint8_t *qbuf, const int64_t *qoff, int q_shared, const uint8_t *rbuf, const int64_t *roff,
+                     int band, const int32_t *diag, const pmx_record_t *recs, const PmxBandTrace &tr,
+                     const int64_t *slot_qoff, long long ops_base, uint32_t *ops, int32_t *nops, int32_t *textlen,
+                     pmx_stats_t *stats_out, hipStream_t stream);
+// off[k] = k * qlen, k = 0 .. n: the query offsets a shared query stands for (slot placement of the profile arm).
+int pmx_launch_shared_offsets(int64_t *off, long long n, int qlen, hipStream_t stream);
 // Band-strip kernel (pmx_bstrip.hip): band coordinates, packed int16, alphabets of <= 4 letters (+ wildcard).  Same contract.
 int pmx_launch_bstrip(int mode, int sg_flags, int open, int ext, const PmxDevMatrix &m, long long n,
                       const uint8_t *qbuf, const int64_t *qoff, int q_shared, const uint8_t *rbuf, const int64_t *roff,
