@@ -122,3 +122,31 @@ __device__ __forceinline__ int lane_next(int x)
 // value of lane + 1 over the wave; lane 63 gets 0 (bound_ctrl).  Without an `old` operand the result is not tied to
 // the source's register: one v_mov_b32 less per move than lane_next<64>.
 __device__ __forceinline__ int lane_next_untied(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x130 /*wave_shl:1*/, 0xF, 0xF, true); }
+
+// x of another lane of the same DPP row, every lane having a source (row rotations, quad permutes, mirrors): no `old`
+// operand, so the result is not tied to a register
+template <int CTRL>
+__device__ __forceinline__ int row_dpp(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
+
+// packed max3 over the G lanes of a group, result in every member (groups as in group_shift_up).  Inside a DPP row of
+// 16 the rounds are DPP moves that keep every lane inside its group: row_ror for 16 adjacent lanes or for the
+// interleaved 8-lane groups (a rotation by an even count keeps the parity), quad_perm / row_half_mirror for 2, 4 or 8
+// adjacent lanes.  Groups wider than a row add one ds_bpermute round per doubling.
+template <int G, bool IL = false>
+__device__ __forceinline__ int group_max3(int v)
+{
+    if constexpr (IL || G >= 16) {
+        if (!IL) { const int o = row_dpp<0x121 /*row_ror:1*/>(v); v = pk_max3(v, o, o); }
+        { const int o = row_dpp<0x122 /*row_ror:2*/>(v); v = pk_max3(v, o, o); }
+        { const int o = row_dpp<0x124 /*row_ror:4*/>(v); v = pk_max3(v, o, o); }
+        { const int o = row_dpp<0x128 /*row_ror:8*/>(v); v = pk_max3(v, o, o); }
+    } else {
+        static_assert(G == 1 || G == 2 || G == 4 || G == 8, "adjacent groups inside a row");
+        if (G >= 2) { const int o = row_dpp<0xB1 /*quad_perm:[1,0,3,2]*/>(v); v = pk_max3(v, o, o); }
+        if (G >= 4) { const int o = row_dpp<0x4E /*quad_perm:[2,3,0,1]*/>(v); v = pk_max3(v, o, o); }
+        if (G >= 8) { const int o = row_dpp<0x141 /*row_half_mirror*/>(v); v = pk_max3(v, o, o); }
+    }
+    if (G >= 32) { const int o = __builtin_amdgcn_ds_bpermute(((int)__lane_id() ^ 16) * 4, v); v = pk_max3(v, o, o); }
+    if (G >= 64) { const int o = __builtin_amdgcn_ds_bpermute(((int)__lane_id() ^ 32) * 4, v); v = pk_max3(v, o, o); }
+    return v;
+}

@@ -96,15 +96,21 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     // LDS carve: [prof NP][shared pad row QP*2][rsym NP*RP][mat msize*msize*2][map 256][pair table NP*4 ints]
     // The pad row sits right behind the last pair's profile; pair p reaches it with the symbol
     // value (NP - p) * msize, so no per-pair copy is needed.
+    // PT: [score tables 32][rsym NP*RP][mat ...]...: the tables sit at a fixed LDS offset, so a staged symbol byte is the
+    // table read's address as it is (immediate offset, no address arithmetic in the sweep).
+    constexpr int PT_TABS = 32;
     int16_t *prof = reinterpret_cast<int16_t *>(lds);
-    unsigned char *rsym = lds + (PT ? 0 : NP * PROF_STRIDE + QP * EB);
+    unsigned char *rsym = lds + (PT ? PT_TABS : NP * PROF_STRIDE + QP * EB);
     int16_t *mat = reinterpret_cast<int16_t *>(rsym + (FETCH ? 0 : NP * RP));
     unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
     long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((msize * msize * 2) & 7)) & 7));   // per pair: q offset, qlen, r offset, rlen, pair index
 
-    int *tabs = reinterpret_cast<int *>(ptab + 5 * NP);      // PT: per reference symbol the 4 query-letter scores (+open), entry msize = pad = 0
+    // PT: per reference symbol the 4 query-letter scores (+open), entry msize = pad = 0.  Addressed as LDS address 0: the kernel
+    // has no static LDS, so `lds` starts there; a plain integer address folds into the read (the symbol of `lds` does not)
+    typedef __attribute__((address_space(3))) int *lds_int;
+    auto tab_at = [](int byte) -> int { return *(lds_int)(uintptr_t)byte; };
     constexpr int QS = (G * R + 3) / 4 * 4;
-    unsigned char *qsym = reinterpret_cast<unsigned char *>(tabs + 8);   // PT: mapped query letters, QS bytes per pair (0xFF below the query)
+    unsigned char *qsym = reinterpret_cast<unsigned char *>(ptab + 5 * NP);   // PT: mapped query letters, QS bytes per pair (0xFF below the query)
 
     const long long pair0 = (long long)blockIdx.x * NP;
 
@@ -147,7 +153,10 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 #pragma unroll
                 for (int u = 0; u < UB; ++u) {
                     const int p = p0 + u;
-                    rsym[p * RP + j] = ok[u] ? map[raw[u]] : (unsigned char)(PT ? msize : (NP - p) * msize);
+                    if (PT)     // the slot's pairs A, B side by side, as byte offsets of their table entries
+                        rsym[(p >> 1) * 2 * RP + 2 * j + (p & 1)] = (unsigned char)(4 * (ok[u] ? map[raw[u]] : msize));
+                    else
+                        rsym[p * RP + j] = ok[u] ? map[raw[u]] : (unsigned char)((NP - p) * msize);
                 }
             }
         }
@@ -226,7 +235,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             int v = 0;
             if (lane < msize)
                 for (int k = 0; k < 4 && k < msize; ++k) v |= ((mat[k * msize + lane] + open) & 0xFF) << (8 * k);
-            tabs[lane] = v;
+            ((lds_int)(uintptr_t)0)[lane] = v;
         }
     }
     __syncthreads();
@@ -246,8 +255,10 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     const int pA = 2 * slot, pB = 2 * slot + 1;
     const unsigned char *profA = lds + pA * PROF_STRIDE + g * (RS * EB);
     const unsigned char *profB = lds + pB * PROF_STRIDE + g * (RS * EB);
-    const unsigned char *rsA = rsym + pA * RP + (G - 1) - g;
-    const unsigned char *rsB = rsym + pB * RP + (G - 1) - g;
+    // PT: A and B of a step are adjacent bytes (SS = 2 bytes per step), already table offsets
+    constexpr int SS = PT ? 2 : 1;
+    const unsigned char *rsA = PT ? rsym + slot * 2 * RP + 2 * ((G - 1) - g) : rsym + pA * RP + (G - 1) - g;
+    const unsigned char *rsB = PT ? rsA + 1 : rsym + pB * RP + (G - 1) - g;
     const int SYMSTRIDE = QP * EB;
 
     const v2s vOpen = PK((open & 0xFFFF) | (open << 16));
@@ -281,7 +292,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     v2s diag0 = PK(SK ? I32(vInitH) : HNEUTRAL);   // H(i0-1, j-1)   (V2: minus open)
 
     auto load_scores = [&](int symA, int symB, int (&wa)[RS / WR], int (&wb)[RS / WR]) {
-        if (PT) { wa[0] = tabs[symA]; wb[0] = tabs[symB]; return; }
+        if (PT) { wa[0] = tab_at(symA); wb[0] = tab_at(symB); return; }
         const int *sa = reinterpret_cast<const int *>(profA + symA * SYMSTRIDE);
         const int *sb = reinterpret_cast<const int *>(profB + symB * SYMSTRIDE);
 #pragma unroll
@@ -394,15 +405,19 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         // end-position bookkeeping: strictly greater than the lane's best so far?
         constexpr bool FOLDED = SK && (R & 1);          // colmax already holds max(best, column maximum)
         const v2s nb = FOLDED ? colmax : M3 ? pk_max3(best, colmax, colmax) : pk_max(best, colmax);
-        int m;   // 0xFFFF in every half whose column maximum strictly exceeds the best so far
-        {
+        // 0xFFFF in every half whose column maximum strictly exceeds the best so far
+        auto improved = [&]() -> int {
             const v2s dd = FOLDED ? (best - nb) : M3 ? (best - colmax) : pk_subs(best, colmax);   // negative exactly where colmax > best
             const v2s sh = {15, 15};
-            m = I32(dd >> sh);                              // v_pk_ashrrev_i16
-        }
+            return I32(dd >> sh);                           // v_pk_ashrrev_i16
+        };
+        // FOLDED: nb = max(best, column maximum) per half, so "some half improved" is nb != best as a 32-bit word -- one
+        // v_cmp for the ballot; the per-half mask is built only in the (rarer) steps that save.
+        int m = FOLDED ? 0 : improved();
         // The strip is saved only in steps where some lane of the wave improves (a wave-uniform branch around R + 1 v_bfi_b32):
         // improvements get rare as a sweep goes on -- a lane's best is a running maximum -- so long sweeps skip most saves.
-        if (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
+        if (__builtin_amdgcn_ballot_w64(FOLDED ? I32(nb) != I32(best) : m != 0) != 0) {
+            if (FOLDED) m = improved();
             // v_bfi_b32 d = (m & a) | (~m & b)
             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bestcol) : "v"(m), "s"((t & 0xFFFF) * 0x00010001), "v"(bestcol));   // the step index is uniform: SGPR operand
             fake &= ~m;
@@ -414,7 +429,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     };
 
     // software pipeline: scores of step t+1 are fetched from LDS while step t computes
-    const int T = max_rlen + G - 1;                      // steps: the last lane's last real column
+    const int T = __builtin_amdgcn_readfirstlane(max_rlen) + G - 1;   // steps: the last lane's last real column (uniform: SALU loop test)
     int w0a[RS / WR], w0b[RS / WR], w1a[RS / WR], w1b[RS / WR];
     // FETCH: raw byte of step x (column x - g), -1 outside the reference; the pad symbol is the pair's own
     const int rlA_ = (int)ptab[5 * pA + 3], rlB_ = (int)ptab[5 * pB + 3];
@@ -434,7 +449,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         nsA = symA_of(r1a); nsB = symB_of(r1b);
     } else {
         load_scores(rsA[0], rsB[0], w0a, w0b);
-        nsA = rsA[1]; nsB = rsB[1];
+        nsA = rsA[SS]; nsB = rsB[SS];
     }
     // Every 16 steps the lanes of a group agree on a lower bound of their pair's final score -- the largest best any of them holds
     // (compared with the lane-dependent part of the skew taken off) -- and each raises its own `best` to one BELOW it: a lane
@@ -448,12 +463,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     // drops them (they could otherwise tie with the true end cell's score).
     constexpr int SHP = PMX_SHARE_PERIOD > G ? PMX_SHARE_PERIOD : G;
     auto share_bound = [&]() {
-        int v = I32(best) - skew0;
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) {
-            const int o = __shfl_xor(v, (IL ? 2 : 1) * off, 64);
-            v = pk_max3(v, o, o);
-        }
+        const int v = group_max3<G, IL>(I32(best) - skew0);
         const int fresh = v - 0x00010001 + skew0;
         const int old = vprev ? vprev + ((SHP * ext) & 0xFFFF) * 0x00010001 + skew0 : 0;        // (0: below every live value)
         const v2s nbest = pk_max3(best, PK(fresh), PK(old));
@@ -461,16 +471,19 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         best = nbest;
         vprev = v;
     };
+    const unsigned char *rcur = rsA;            // PT: rsA + SS * t, advanced once per iteration; the reads take immediate offsets
     for (int t = 0; t + 1 < T; t += 2) {
         if (SK && G > 1 && (t & (SHP - 1)) == 0 && t) share_bound();
         load_scores(nsA, nsB, w1a, w1b);
         if (FETCH) { nsA = symA_of(m2a); nsB = symB_of(m2b); fetch(t + 4, m2a, m2b); }
+        else if (PT) { nsA = rcur[2 * SS]; nsB = rcur[2 * SS + 1]; asm("" : "+v"(nsA), "+v"(nsB)); }
         else { nsA = rsA[t + 2]; nsB = rsB[t + 2]; }
         __builtin_amdgcn_sched_barrier(0);      // keep the LDS reads ahead of the step they overlap with
         step(HA, HB, w0a, w0b, t);
         __builtin_amdgcn_sched_barrier(0);
         load_scores(nsA, nsB, w0a, w0b);
         if (FETCH) { nsA = symA_of(m3a); nsB = symB_of(m3b); fetch(t + 5, m3a, m3b); }
+        else if (PT) { nsA = rcur[3 * SS]; nsB = rcur[3 * SS + 1]; asm("" : "+v"(nsA), "+v"(nsB)); rcur += 2 * SS; }
         else { nsA = rsA[t + 3]; nsB = rsB[t + 3]; }
         __builtin_amdgcn_sched_barrier(0);
         step(HB, HA, w1a, w1b, t + 1);
