@@ -254,13 +254,21 @@ typedef struct pmx_stats {
 } pmx_stats_t;
 
 /* Sequences are packed back to back: pair k's query is qbuf[qoff[k] .. qoff[k+1]).
- * Returns 0 on success, <0 on error (pmx_last_error() describes it). */
+ * Returns 0 on success, <0 on error (pmx_last_error() describes it).
+ *
+ * PSSM matrices (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) are taken by pmx_align_batch / _2bit / _device,
+ * pmx_align_profile_batch / _device, pmx_align_batch_cigar and the _multi entries, in every mode (nw, sg with any free ends, sw)
+ * and width, with or without PMX_WANT_STATS.  Every query (or the profile's query) must have the PSSM's length; cell (i, j) scores
+ * pssm[i][mapper[r[j]]], `matches` counts mapper[q[i]] == mapper[r[j]] along the path and `similar` counts pssm[i][.] > 0: each record,
+ * its statistics and its CIGAR equal those of the one-pair call with the same PSSM.  Refused with -1 and a pmx_last_error() text
+ * before any GPU work: a query length different from the PSSM's (device entries: max_qlen; the caller keeps every query at that
+ * length), and a PSSM whose length x size int16 rows do not fit 160 KB.  Banded and table batches do not take a PSSM. */
 
 /* Host buffers in, host records out (H2D + kernels + D2H inside). */
 int pmx_align_batch(const pmx_config_t *cfg, int64_t n,
                     const uint8_t *qbuf, const int64_t *qoff,
                     const uint8_t *rbuf, const int64_t *roff,
-                    pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */);
+                    pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */);   /* PSSM: every query has its length */
 
 /* The same with 2-bit packed sequences (additive input form for 4-letter alphabets): base b of a buffer sits in byte b / 4 at
  * bits 2 (b % 4) and holds the index of its letter in the matrix alphabet (0..3); the offsets count BASES.  A quarter of the
@@ -280,14 +288,15 @@ int pmx_align_batch_device(const pmx_config_t *cfg, int64_t n,
                            const uint8_t *d_qbuf, const int64_t *d_qoff,
                            const uint8_t *d_rbuf, const int64_t *d_roff,
                            int32_t max_qlen, int32_t max_rlen,
-                           pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream);
+                           pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream);   /* PSSM: max_qlen == its length, and every query */
 
-/* One reused query profile against many references (profile arm, src/aligner/mod.rs:431-450). */
+/* One reused query profile against many references (profile arm, src/aligner/mod.rs:431-450).  A PSSM: the profile's query
+ * length must equal the PSSM's length (the database search of one position-specific profile). */
 int pmx_align_profile_batch(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
                             const uint8_t *rbuf, const int64_t *roff,
                             pmx_record_t *out, pmx_stats_t *stats_out);
 
-/* The same with device-resident references (device pointers, asynchronous on `stream`). */
+/* The same with device-resident references (device pointers, asynchronous on `stream`); the same PSSM rule. */
 int pmx_align_profile_batch_device(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
                                    const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen,
                                    pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream);
@@ -331,7 +340,7 @@ int pmx_align_batch_banded_cigar_device(const pmx_config_t *cfg, const parasail_
                                         char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream);
 
 /* CIGAR text for a batch (semi-global / global / local with traceback done on the device).
- * cigar_off has n+1 entries; *cigar_buf is malloc'd by the callee and freed with pmx_free. */
+ * cigar_off has n+1 entries; *cigar_buf is malloc'd by the callee and freed with pmx_free.  A PSSM: every query has its length. */
 int pmx_align_batch_cigar(const pmx_config_t *cfg, int64_t n,
                           const uint8_t *qbuf, const int64_t *qoff,
                           const uint8_t *rbuf, const int64_t *roff,
@@ -376,6 +385,7 @@ int pmx_align_batch_multi(const pmx_config_t *cfg, int64_t n,
 int pmx_align_profile_batch_multi(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
                                   const uint8_t *rbuf, const int64_t *roff,
                                   const int *devices, int ndev, pmx_record_t *out, pmx_stats_t *stats_out);
+/* (a PSSM: the rules of pmx_align_batch / pmx_align_profile_batch) */
 /* bounds[0..parts]: block g = pairs [bounds[g], bounds[g+1]).  qoff == NULL: one shared query.  Pure host arithmetic. */
 int pmx_shard_bounds_by_cells(int64_t n, const int64_t *qoff, const int64_t *roff, int parts, int64_t *bounds);
 

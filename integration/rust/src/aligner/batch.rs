@@ -227,7 +227,9 @@ impl Aligner {
     }
 
     /// Align many independent pairs in one call.  With a profile (`AlignerBuilder::profile`) pass `None` for the queries, as
-    /// `align()` does (`src/aligner/mod.rs:394-396`): every reference is aligned against the profile's query.
+    /// `align()` does (`src/aligner/mod.rs:394-396`): every reference is aligned against the profile's query.  A PSSM matrix
+    /// (`Matrix::create_pssm` / `from_file` / `to_pssm`) is taken when the profile's query, or every query, has the PSSM's length;
+    /// each record and its statistics equal `align()`'s with the same PSSM.
     pub fn align_batch(&self, queries: Option<&Packed>, references: &Packed) -> Result<BatchResult> {
         let n = references.len();
         let mut records = vec![PmxRecord::default(); n];
@@ -255,7 +257,7 @@ impl Aligner {
         Ok(BatchResult { records, stats })
     }
 
-    /// Score, end positions and CIGAR text per pair (an aligner built with `use_trace()`).
+    /// Score, end positions and CIGAR text per pair (an aligner built with `use_trace()`).  A PSSM: every query has its length.
     pub fn align_batch_cigar(&self, queries: &Packed, references: &Packed) -> Result<(Vec<PmxRecord>, BatchCigars)> {
         let n = references.len();
         assert_eq!(queries.len(), n, "one query per reference");
@@ -319,7 +321,7 @@ impl Aligner {
     }
 
     /// One process driving several GPUs of the node: contiguous blocks of about equal cell counts, one per listed device;
-    /// records come back in input order.
+    /// records come back in input order.  A PSSM: the length rule of `align_batch`.
     pub fn align_batch_multi(&self, queries: Option<&Packed>, references: &Packed, devices: &[i32]) -> Result<BatchResult> {
         let n = references.len();
         let mut records = vec![PmxRecord::default(); n];

@@ -748,7 +748,8 @@ class Aligner:
     def align_batch(self, queries, references):
         """Many independent pairs in one call.  Returns a structured array with fields
         score, end_query, end_ref, flags (and, for a stats aligner, a second array with
-        matches, similar, length)."""
+        matches, similar, length).  A PSSM matrix is taken when every query (or the profile's
+        query) has the PSSM's length; each record equals align()'s with the same PSSM."""
         qbuf, qoff = pack(queries)
         rbuf, roff = pack(references)
         return self.align_batch_packed(qbuf, qoff, rbuf, roff)

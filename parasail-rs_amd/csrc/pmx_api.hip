@@ -502,6 +502,7 @@ static int get_devmat(const parasail_matrix_t *m, DevMat *out)
     HIP_OR_RET(hipMemcpy(dm.scores, s16.data(), cells * 2, hipMemcpyHostToDevice));
     HIP_OR_RET(hipMemcpy(dm.mapper, map8.data(), 256, hipMemcpyHostToDevice));
     dm.d.scores = dm.scores; dm.d.mapper = dm.mapper; dm.d.msize = m->size; dm.d.min = m->min; dm.d.max = m->max;
+    dm.d.pssm = m->type == PARASAIL_MATRIX_TYPE_PSSM ? 1 : 0; dm.d.rows = dm.d.pssm ? m->length : m->size;
     g_devmats[key] = dm;
     *out = dm;
     return 0;
@@ -1309,16 +1310,41 @@ static int check_cfg(const pmx_config_t *cfg)
     return 0;
 }
 
+// A PSSM in a batch: every query has the PSSM's length (min_qlen .. max_qlen: the lengths the entry can see), and its rows alone
+// fit the general kernel's LDS -- the general kernel is the fallback of every request the PSSM forms of the shared-profile kernels
+// do not serve.  0 fine (or not a PSSM), -1 refused with a message.
+static int pssm_batch_check(const parasail_matrix_t *m, int32_t min_qlen, int32_t max_qlen)
+{
+    if (m->type != PARASAIL_MATRIX_TYPE_PSSM) return 0;
+    if (min_qlen != m->length || max_qlen != m->length) {
+        set_err("PSSM length %d differs from the query length (%d..%d)", m->length, min_qlen, max_qlen); return -1;
+    }
+    if ((((size_t)m->length * m->size * 2 + 15) & ~(size_t)15) > 160 * 1024) {
+        set_err("PSSM of %d rows x %d symbols does not fit the general kernel's LDS", m->length, m->size); return -1;
+    }
+    return 0;
+}
+
 static bool fast_sw_eligible(const pmx_config_t *cfg)
 {
-    // (width 8 included: for local alignment the saturation rule only needs the score, see PmxBatch::sat_above)
+    // (width 8 included: for local alignment the saturation rule only needs the score, see PmxBatch::sat_above;
+    //  a PSSM: pmx_launch_sw16 routes it into the PSSM form of the shared-profile kernel only)
     return cfg->mode == PMX_MODE_SW && (cfg->want & ~PMX_WANT_SORTED) == 0 &&
-           cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE;
+           (cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE || cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM);
 }
 
 extern "C" const char *pmx_kernel_for(const pmx_config_t *cfg, int32_t max_qlen, int32_t max_rlen)
 {
     if (check_cfg(cfg)) return "invalid";
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {       // (score only: the PSSM forms of the shared-profile kernels, as batches run them)
+        if ((cfg->want & ~PMX_WANT_SORTED) == 0 && cfg->mode == PMX_MODE_SW && cfg->matrix->size <= PMX_MAX_FAST_MSIZE &&
+            max_qlen <= 2048 && max_rlen <= 60000)
+            return "pmx_sw16q_kernel";
+        if ((cfg->want & ~PMX_WANT_SORTED) == 0 && cfg->mode != PMX_MODE_SW && cfg->width != 8 && cfg->open >= cfg->extend &&
+            max_qlen <= 2048 && cfg->matrix->size < PMX_MAX_FAST_MSIZE)
+            return "pmx_nwsg16q_kernel";
+        return "pmx_general_kernel";
+    }
     if (fast_sw_eligible(cfg) && cfg->matrix->size <= PMX_MAX_FAST_MSIZE && max_qlen <= 2048 && max_rlen <= 60000)
         return "pmx_sw16_kernel";
     if ((cfg->mode == PMX_MODE_NW || cfg->mode == PMX_MODE_SG) && (cfg->want & ~PMX_WANT_SORTED) == 0 &&
@@ -1367,7 +1393,7 @@ static thread_local const char *g_last_kernel = "";
 extern "C" const char *pmx_last_kernel(void) { return g_last_kernel; }
 
 
-// What every general-kernel batch shares: the n pairs, the square matrix, the gap model, the configured width, no band.
+// What every general-kernel batch shares: the n pairs, the matrix (a PSSM by query row), the gap model, the configured width, no band.
 static PmxGeneralArgs general_args(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
                                    const uint8_t *d_qbuf, const int64_t *d_qoff, int q_shared,
                                    const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen)
@@ -1375,7 +1401,7 @@ static PmxGeneralArgs general_args(const pmx_config_t *cfg, const DevMat &dm, in
     PmxGeneralArgs a; memset(&a, 0, sizeof a);
     a.qbuf = d_qbuf; a.qoff = q_shared ? nullptr : d_qoff; a.shared_qlen = q_shared;
     a.rbuf = d_rbuf; a.roff = d_roff; a.n = n; a.max_rlen = max_rlen;
-    a.scores = dm.d.scores; a.mapper = dm.d.mapper; a.msize = dm.d.msize; a.mat_rows = dm.d.msize;
+    a.scores = dm.d.scores; a.mapper = dm.d.mapper; a.msize = dm.d.msize; a.mat_rows = dm.d.rows; a.pssm = dm.d.pssm;
     a.mode = cfg->mode; a.sg_flags = cfg->sg_flags; a.open = cfg->open; a.ext = cfg->extend;
     a.band = -1; a.bits = cfg->width;
     return a;
@@ -1605,7 +1631,8 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
     }
     if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));      // (the walk stream is in order: the last walk covers all, the remainder's too)
     static thread_local char name[96];
-    snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d>/shared profile/packed trace + pmx_walkp_kernel/stats", G, R);
+    if (dm.d.pssm) snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d,pssm>/shared PSSM profile/packed trace + pmx_walkp_kernel<pssm>/stats", G, R);
+    else snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d>/shared profile/packed trace + pmx_walkp_kernel/stats", G, R);
     g_last_kernel = name;
     return 0;
 }
@@ -1777,11 +1804,15 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
     if (max_qlen <= 0 || max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
     if ((cfg->want & PMX_WANT_STATS) && !d_stats_out) { set_err("stats requested without a stats buffer"); return -1; }
     if (cfg->want & PMX_WANT_CIGAR) { set_err("use pmx_align_batch_cigar for CIGAR output"); return -1; }
+    if (pssm_batch_check(cfg->matrix, max_qlen, max_qlen)) return -1;
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
     hipStream_t st = (hipStream_t)stream;
     PmxBatch b = {d_qbuf, d_qoff, d_rbuf, d_roff, n, max_qlen, max_rlen, q_shared, nullptr, nullptr, nullptr, 0, 0};
     const int want = cfg->want & ~PMX_WANT_SORTED;
+    // A PSSM's scores do not depend on the query letters: score-only per-pair batches run on the PSSM forms of the shared-profile
+    // kernels exactly as a profile batch does (b.q_shared = the PSSM's length; those forms read no query byte, no wildcard handling)
+    if (dm.d.pssm && want == 0) { b.q_shared = max_qlen; q_shared_wild = 0; }
     if ((cfg->want & PMX_WANT_SORTED) && n >= 64 && n < (1LL << 32)) {
         void *scr = nullptr;
         if (scratch_reserve(pmx_sort_scratch_bytes(n), &scr, SCR_SORT)) return -1;
@@ -1797,7 +1828,7 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
         if (rc <= 0) return rc;
     }
     if (fast_sw_eligible(cfg)) {
-        b.q_has_wildcard = q_shared ? q_shared_wild : 0;
+        b.q_has_wildcard = b.q_shared ? q_shared_wild : 0;
         b.sat_above = cfg->width == 8 ? 127 : 0;
         if (n >= 4096 && n < (1LL << 32) && !b.q_has_wildcard) {
             // scratch that lets the launcher pick a kernel which hands some pairs back for a second launch
@@ -1811,9 +1842,9 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
         if (rc == 0) return promote_overflowed(cfg, dm, b, d_out, st);
         // rc == 1: shape not covered by the fast kernel -> general kernel below
     }
-    if (q_shared && want == PMX_WANT_STATS && cfg->width != 8 && cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE &&
+    if (q_shared && want == PMX_WANT_STATS && cfg->width != 8 && (cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE || dm.d.pssm) &&
         (cfg->mode == PMX_MODE_NW || cfg->mode == PMX_MODE_SG) && (n >= 512 || pmx_env("PMX_STATS_BY_TRACE"))) {
-        // profile arm with statistics (BASELINE config 3): traceback sweep + counting walk
+        // profile arm with statistics (BASELINE config 3): traceback sweep + counting walk (a PSSM: the PSSM forms of both)
         const int rc = stats_by_trace_shared(cfg, dm, b, d_out, d_stats_out, st);
         if (rc <= 0) return rc;
     }
@@ -1839,7 +1870,7 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
         if (rc <= 0) return rc;
     }
     if ((cfg->mode == PMX_MODE_NW || cfg->mode == PMX_MODE_SG) && want == 0 && (cfg->width != 8 || !pmx_env("PMX_NWSG8_GENERAL")) &&
-        cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE) {
+        (cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE || dm.d.pssm)) {
         // (width 8: the same int16 kernels, which then also track the range of H for the saturation flag -- the reference's
         //  narrowest width is its fastest on a CPU; it must not be the slow road here)
         b.track8 = cfg->width == 8;
@@ -1852,7 +1883,6 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
         if (rc < 0) { set_err("nwsg16 launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
         if (rc == 0) return 0;     // the host-side range proof makes overflow impossible: no promotion pass
     }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
     if (want == 0) {
         // Outside every packed kernel's window (gap models with open < extend, alphabets of 32 and more letters, value ranges the
         // int16 lanes cannot prove): the 32-bit band kernel, one wave per 256 query rows -- several times the general kernel's rate
@@ -1863,7 +1893,7 @@ static int run_batch_device(const pmx_config_t *cfg, int64_t n,
     a.max_qlen = max_qlen; a.rec = d_out; a.stats = d_stats_out;
     const int rcg = general_batch(a, (want & PMX_WANT_STATS) != 0, st);
     if (rcg) return rcg;
-    g_last_kernel = "pmx_general_kernel";
+    g_last_kernel = dm.d.pssm ? "pmx_general_kernel/pssm" : "pmx_general_kernel";
     return 0;
 }
 
@@ -1895,6 +1925,7 @@ extern "C" int pmx_align_batch_device(const pmx_config_t *cfg, int64_t n,
                                       int32_t max_qlen, int32_t max_rlen,
                                       pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream)
 {
+    if (check_cfg(cfg) || (n > 0 && pssm_batch_check(cfg->matrix, max_qlen, max_qlen))) return -1;     // (before any GPU work)
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     return run_batch_device(cfg, n, d_qbuf, d_qoff, 0, d_rbuf, d_roff, max_qlen, max_rlen, d_out, d_stats_out, stream);
@@ -1983,6 +2014,11 @@ static int host_batch(const pmx_config_t *cfg, int64_t n,
     if (check_cfg(cfg)) return -1;
     if (n <= 0) return 0;
     if (!qbuf || !qoff || !rbuf || !roff || !out) { set_err("null buffer"); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {           // (every query has the PSSM's length: checked before any GPU work)
+        int32_t mq = 0, mnq = 0; bool bad = false;
+        host_maxlens(n, qoff, &mq, &bad, &mnq);
+        if (pssm_batch_check(cfg->matrix, mnq, mq)) return -1;
+    }
     // the length scan runs beside the first transfers (it needs the host only; the offsets go up meanwhile)
     LenScan ls;
     std::future<void> scan;
@@ -2084,7 +2120,7 @@ extern "C" int pmx_align_profile_batch(const pmx_config_t *cfg, const parasail_p
     if (n <= 0) return 0;
     if (!rbuf || !roff || !out) { set_err("null buffer"); return -1; }
     if (profile->matrix != cfg->matrix) { set_err("profile was built with a different matrix"); return -1; }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
+    if (pssm_batch_check(cfg->matrix, profile->s1Len, profile->s1Len)) return -1;
     int32_t mr = 0, mnr = 0; bool bad = false;
     host_maxlens(n, roff, &mr, &bad, &mnr);
     if (bad || roff[0] != 0) { set_err("bad reference offsets"); return -1; }
@@ -2180,7 +2216,7 @@ extern "C" int pmx_align_profile_batch_device(const pmx_config_t *cfg, const par
     if (check_cfg(cfg)) return -1;
     if (!profile) { set_err("null profile"); return -1; }
     if (profile->matrix != cfg->matrix) { set_err("profile was built with a different matrix"); return -1; }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
+    if (pssm_batch_check(cfg->matrix, profile->s1Len, profile->s1Len)) return -1;
     const uint8_t *dq = nullptr;
     if (profile_device_query(profile, &dq)) return -1;
     StreamGuard guard(stream);
@@ -2204,7 +2240,7 @@ static int banded_device(const pmx_config_t *cfg, int64_t n, const uint8_t *d_qb
     if (band < 0) { set_err("band must be >= 0"); return -1; }
     if (max_qlen <= 0 || max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
     if (cfg->want & ~PMX_WANT_SORTED) { set_err("banded batches return score and end positions only"); return -1; }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by banded batches"); return -1; }
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
     StreamGuard guard(stream);
@@ -2256,6 +2292,7 @@ extern "C" int pmx_align_batch_banded(const pmx_config_t *cfg, const parasail_pr
     if (check_cfg(cfg)) return -1;
     if (n <= 0) return 0;
     if (!rbuf || !roff || !out || (!profile && (!qbuf || !qoff))) { set_err("null buffer"); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by banded batches"); return -1; }
     int32_t mq = 0, mr = 0; bool bad = false;
     host_maxlens(n, roff, &mr, &bad);
     if (!profile) host_maxlens(n, qoff, &mq, &bad); else mq = profile->s1Len;
@@ -2295,7 +2332,7 @@ extern "C" int pmx_align_batch_table_device(const pmx_config_t *cfg, int64_t n,
     if (d_score_table && !d_tab_off) { set_err("a score table needs d_tab_off"); return -1; }
     if (max_qlen <= 0 || max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
     if (cfg->want & ~PMX_WANT_SORTED) { set_err("table batches return score tables, rows / columns and records"); return -1; }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by table batches"); return -1; }
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
     StreamGuard guard(stream);
@@ -2634,7 +2671,11 @@ extern "C" int pmx_align_batch_cigar(const pmx_config_t *cfg, int64_t n,
     if (!cigar_buf || !cigar_off) { set_err("null cigar output"); return -1; }
     *cigar_buf = nullptr;
     if (n <= 0) return 0;
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {           // (the general trace table + pmx_walk_kernel: it reads no score)
+        int32_t mq = 0, mnq = 0; bool bad = false;
+        host_maxlens(n, qoff, &mq, &bad, &mnq);
+        if (pssm_batch_check(cfg->matrix, mnq, mq)) return -1;
+    }
     if (qoff[0] != 0 || roff[0] != 0) { set_err("offset arrays must start at 0"); return -1; }
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
@@ -2695,7 +2736,7 @@ static int banded_trace_check(const pmx_config_t *cfg, int32_t band)
 {
     if (check_cfg(cfg)) return -1;
     if (band < 0 || band > 63) { set_err("banded traceback supports bands 0 .. 63 (got %d)", band); return -1; }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are single-pair only"); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by banded batches"); return -1; }
     if (cfg->matrix->size > PMX_MAX_FAST_MSIZE) { set_err("banded traceback supports alphabets of up to %d letters (matrix size %d)", PMX_MAX_FAST_MSIZE, cfg->matrix->size); return -1; }
     if (!(cfg->want & (PMX_WANT_CIGAR | PMX_WANT_STATS))) { set_err("banded traceback needs PMX_WANT_CIGAR and / or PMX_WANT_STATS in cfg->want"); return -1; }
     if (cfg->want & ~(PMX_WANT_CIGAR | PMX_WANT_STATS | PMX_WANT_SORTED)) { set_err("unknown want bits 0x%x", cfg->want); return -1; }

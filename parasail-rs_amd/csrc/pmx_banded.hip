@@ -763,6 +763,7 @@ int pmx_launch_banded(int mode, int sg_flags, int open, int ext, const PmxDevMat
                       int max_qlen, int max_rlen, int band, const int32_t *diag, pmx_record_t *out, hipStream_t stream,
                       const char **kernel_name, void *sort_scratch, unsigned *retry_list, int *retry_count)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (n <= 0) return 0;
     if (pmx_env("PMX_NO_FAST_BANDED")) return 1;
     // the band-strip kernel (band coordinates, packed int16, C offsets per lane) where its window holds
@@ -866,6 +867,7 @@ int pmx_launch_banded_trace(int mode, int sg_flags, int open, int ext, const Pmx
                             int max_qlen, int max_rlen, int band, const int32_t *diag, pmx_record_t *out, const PmxBandTrace &tr,
                             hipStream_t stream, const char **kernel_name)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (n <= 0) return 0;
     // (the staging rule of pmx_launch_banded)
     const int LPs = band <= 15 ? 16 : band <= 31 ? 32 : 64, NPW = 64 / LPs;

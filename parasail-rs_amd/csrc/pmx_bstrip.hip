@@ -701,6 +701,7 @@ int pmx_launch_bstrip(int mode, int sg_flags, int open, int ext, const PmxDevMat
                       int max_qlen, int max_rlen, int band, const int32_t *diag, pmx_record_t *out, hipStream_t stream,
                       const char **kernel_name, void *sort_scratch, unsigned *retry_list, int *retry_count)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (pmx_env("PMX_BANDED_NO_STRIP") || !retry_list || !retry_count) return 1;
     if (m.msize > 5 || n <= 0 || n >= (1LL << 31)) return 1;
     int G = 0, C = 0;

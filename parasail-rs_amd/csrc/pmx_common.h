@@ -12,10 +12,12 @@ int pmx_ensure_lds_attr(const void *kernel, int bytes = 160 * 1024);
 
 // Device-side view of a substitution matrix (built once per parasail_matrix_t, cached).
 struct PmxDevMatrix {
-    const int16_t *scores;   // [msize*msize], scores[qsym*msize + rsym]   (device)
+    const int16_t *scores;   // [rows*msize]: scores[qsym*msize + rsym], or for a PSSM scores[i*msize + rsym] (query row i)  (device)
     const uint8_t *mapper;   // [256] byte -> symbol index                  (device)
     int msize;
     int min, max;
+    int pssm;                // 1: a PSSM of `rows` query positions; only the kernels that declare a PSSM form take one
+    int rows;                // rows of `scores`: msize, or the PSSM's length
 };
 
 // Batch of pairs, device-resident, packed layout of include/parasail_amd.h.

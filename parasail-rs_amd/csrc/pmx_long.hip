@@ -605,6 +605,7 @@ size_t pmx_long_scratch_bytes(long long n, int max_qlen, int max_rlen, int R, lo
 int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R,
                     void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, hipStream_t stream, int spin_limit, int chunk_cols, int two_cols)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (b.perm || m.msize > 64) return 1;
     if (m.max + open + ext > 32000 || m.min + open < -16000 || open < 0 || ext < 0) return 1;      // int16 profile entries (score + open [+ ext])
     if ((long long)(b.max_qlen + b.max_rlen) * (long long)(ext > open ? ext : open) > (1LL << 29)) return 1;   // boundary values stay above LONG_NEG

@@ -872,7 +872,9 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 // ENDS = false: the instance for GLOBAL alignment -- no free-end captures compiled in.  The rare capture branches sit on top of the
 // sweep's ~165 live registers: <16,20,TR> takes 178 VGPRs with them (two waves per SIMD; forced to 168 it spills and is 10 % slower)
 // and 149 without (three waves per SIMD) -- BASELINE config 3 is global.
-template <int G, int R, int WAVES, bool TR = false, bool ENDS = true>
+// PSSM = true: effective row er >= P reads PSSM row er - P (gmat[(er - P) * msize + sym]) instead of the matrix row of the query's
+// symbol; the msize^2 matrix is not staged and the query bytes are not read.  Virtual rows, the pad symbol and the sweep are unchanged.
+template <int G, int R, int WAVES, bool TR = false, bool ENDS = true, bool PSSM = false>
 __global__ __launch_bounds__(64 * WAVES)
 void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
                         const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff,
@@ -900,8 +902,9 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
 
     unsigned char *psc = lds;                   // [MS1][QPS]
     int16_t *mat = reinterpret_cast<int16_t *>(lds + ((MS1 * QPS + 7) & ~7));
-    unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((msize * msize * 2) & 7)) & 7));   // per pair: r offset, rlen, pair index
+    const int mcells = PSSM ? 0 : msize * msize;    // (PSSM: no staged matrix)
+    unsigned char *map = reinterpret_cast<unsigned char *>(mat + mcells);
+    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((mcells * 2) & 7)) & 7));   // per pair: r offset, rlen, pair index
     // TR: eight steps of every lane's trace records are gathered in LDS and leave as one contiguous piece of the lane's stream
     // (96 or 128 bytes: whole 32-byte sectors; single 12/16-byte stores of thousands of resident lanes overflow the L2's write combining)
     constexpr int TSTG = PMX_QSTAGE;               // steps gathered per flush
@@ -909,7 +912,7 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
     uint32_t *tstage = reinterpret_cast<uint32_t *>(ptab + 3 * NP) + (size_t)(wave * 64 + lane) * TSTR;
 
     const long long pair0 = (long long)blockIdx.x * NP;
-    for (int i = tid; i < msize * msize; i += NT) mat[i] = gmat[i];
+    for (int i = tid; i < mcells; i += NT) mat[i] = gmat[i];
     for (int i = tid; i < 256; i += NT) map[i] = gmap[i];
     if (tid < NP) {
         long long pos = pair0 + tid; if (pos >= n) pos = n - 1;
@@ -931,8 +934,13 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
     for (int er = tid; er < QP; er += NT) {
         unsigned char *sc = psc + (er / R) * RS + er % R;
         if (er >= P) {
-            const int q = map[qbuf[er - P]];
-            for (int sym = 0; sym < msize; ++sym) sc[sym * QPS] = (unsigned char)(mat[q * msize + sym] + open + rx);
+            if constexpr (PSSM) {
+                const int16_t *prow = gmat + (size_t)(er - P) * msize;
+                for (int sym = 0; sym < msize; ++sym) sc[sym * QPS] = (unsigned char)(prow[sym] + open + rx);
+            } else {
+                const int q = map[qbuf[er - P]];
+                for (int sym = 0; sym < msize; ++sym) sc[sym * QPS] = (unsigned char)(mat[q * msize + sym] + open + rx);
+            }
             sc[msize * QPS] = (unsigned char)vcol_b;
         } else {
             for (int sym = 0; sym < msize; ++sym) sc[sym * QPS] = (unsigned char)vrow_b;
@@ -1449,12 +1457,24 @@ static int launch_nwsgm(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     return e == hipSuccess ? 0 : -(int)e;
 }
 
+template <int G, int R, bool TR, bool PSSM>
+static int launch_nwsgq_form(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
+                             pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf, int Tmax);
+// (a PSSM, m.pssm: the instance with PSSM = true; its LDS holds no matrix)
 template <int G, int R, bool TR = false>
 static int launch_nwsgq(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
                         pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf = nullptr, int Tmax = 0)
 {
+    if (m.pssm) return launch_nwsgq_form<G, R, TR, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
+    return launch_nwsgq_form<G, R, TR, false>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
+}
+template <int G, int R, bool TR, bool PSSM>
+static int launch_nwsgq_form(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
+                             pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf, int Tmax)
+{
     constexpr int RS = (R + 3) / 4 * 4, WAVES = 4, NP = 2 * (64 / G) * WAVES;
-    const size_t lds = (size_t)(m.msize + 1) * G * RS + 8 + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 24 +
+    if (PSSM && m.rows != b.q_shared) return 1;
+    const size_t lds = (size_t)(m.msize + 1) * G * RS + 8 + (PSSM ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)NP * 24 +
                        (TR ? (size_t)WAVES * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4 : 0);
     if (lds > 160 * 1024) return 1;
     const bool sg = mode == PMX_MODE_SG;
@@ -1464,16 +1484,16 @@ static int launch_nwsgq(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     if (blocks <= 0) return 0;
     if constexpr (TR && R >= 19) {
         if (!s1_end && !s2_end && !pmx_env("PMX_NWSGQ_ENDS_ALWAYS")) {       // no free end: the instance without captures (three waves per SIMD)
-            { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16q_kernel<G, R, WAVES, TR, false>)); if (rc) return rc; }
-            hipLaunchKernelGGL((pmx_nwsg16q_kernel<G, R, WAVES, TR, false>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
+            { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16q_kernel<G, R, WAVES, TR, false, PSSM>)); if (rc) return rc; }
+            hipLaunchKernelGGL((pmx_nwsg16q_kernel<G, R, WAVES, TR, false, PSSM>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                                b.qbuf, b.q_shared, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
                                col_pen, row_pen, 0, 0, nb, b.perm, d_out, tbuf, Tmax);
             const hipError_t e = hipGetLastError();
             return e == hipSuccess ? 0 : -(int)e;
         }
     }
-    { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16q_kernel<G, R, WAVES, TR>)); if (rc) return rc; }
-    hipLaunchKernelGGL((pmx_nwsg16q_kernel<G, R, WAVES, TR>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
+    { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16q_kernel<G, R, WAVES, TR, true, PSSM>)); if (rc) return rc; }
+    hipLaunchKernelGGL((pmx_nwsg16q_kernel<G, R, WAVES, TR, true, PSSM>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                        b.qbuf, b.q_shared, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
                        col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb, b.perm, d_out, tbuf, Tmax);
     hipError_t e = hipGetLastError();
@@ -1492,13 +1512,14 @@ int pmx_nwsgq_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG) return 1;
     if (!b.q_shared || !pmx_nwsgv_bias(b, m, open, ext, 1)) return 1;
     if ((m.max > 0 ? m.max : 0) + 2 * open > 250) return 1;
+    if (m.pssm && m.rows != b.q_shared) return 1;
     for (int vo = 0; vo < 7; ++vo) {
         const int v = kQShapeOrder[vo];
         const int G = kQShapeG[v], R = kQShapeR[v];
         if (b.q_shared > G * R - 1) continue;
         if (R >= 19 && (short_waves || pmx_env("PMX_NWSGQ_NO_R20"))) continue;      // (short_waves: half the rows per lane = half the time per wave)
         if (R == 19 && pmx_env("PMX_NWSGQ_NO_R19")) continue;
-        const size_t lds = (size_t)(m.msize + 1) * G * ((R + 3) / 4 * 4) + 8 + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)(2 * (64 / G) * 4) * 24 +
+        const size_t lds = (size_t)(m.msize + 1) * G * ((R + 3) / 4 * 4) + 8 + (m.pssm ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)(2 * (64 / G) * 4) * 24 +
                            (size_t)4 * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4;
         if (lds > 160 * 1024) continue;
         const long long NP = 2 * (64 / G) * 4;
@@ -1528,7 +1549,7 @@ long long pmx_nwsgq_trace_round_pairs(int variant, const PmxDevMatrix &m, int mo
     const int v = variant - 30;
     if (v < 0 || v >= 7) return 0;
     const int G = kQShapeG[v], R = kQShapeR[v];
-    const size_t lds = (size_t)(m.msize + 1) * G * ((R + 3) / 4 * 4) + 8 + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)(2 * (64 / G) * 4) * 24 +
+    const size_t lds = (size_t)(m.msize + 1) * G * ((R + 3) / 4 * 4) + 8 + (m.pssm ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)(2 * (64 / G) * 4) * 24 +
                        (size_t)4 * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4;
     const bool ends = mode == PMX_MODE_SG && (sg_flags & (PMX_SG_QE | PMX_SG_DE));
     switch (v) {
@@ -1726,6 +1747,7 @@ extern "C" int pmx_window_nwsgv(int max_qlen, int max_rlen, int msize, int score
 int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
                          int *variant, int *Tmax, size_t *trace_bytes)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG) return 1;
     if (b.q_shared || b.perm || !pmx_nwsgv_bias(b, m, open, ext, 1)) return 1;
     if (m.msize > 8 && m.msize < 32 && !pmx_env("PMX_NWSG16_NO_MATRIX_LOOKUP")) {   // large alphabet: the matrix-lookup kernel (1 KB of LDS)
@@ -1753,6 +1775,7 @@ int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int
 int pmx_launch_nwsgv_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
                            pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     const int nb = pmx_nwsgv_bias(b, m, open, ext, 1);
     if (!nb) return 1;
     switch (variant) {
@@ -1774,6 +1797,7 @@ int pmx_launch_nwsg16(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg
 {
     if (pmx_env("PMX_NO_FAST_NWSG")) return 1;
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG) return 1;
+    if (m.pssm && (!b.q_shared || b.track8 || m.rows != b.q_shared)) return 1;     // a PSSM: the shared-profile form only
     if (m.msize > PMX_MAX_FAST_MSIZE - 1) return 1;
     if (open < ext || open < 0 || ext < 0) return 1;           // the virtual-row/column fixed points need open >= extend
     if (b.max_rlen > 30000) return 1;
@@ -1783,19 +1807,20 @@ int pmx_launch_nwsg16(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg
     //  query may fill all G * R rows; the first generation and the traceback walk need row -1 to exist)
     if (const int nb = pmx_nwsgv_bias(b, m, open, ext, b.track8 ? 0 : 1)) {      // (width 8's range tracking: the form without the row offset)
         if (b.q_shared && !b.track8 && !pmx_env("PMX_NWSG16_NO_SHARED")) {        // profile arm: one profile per workgroup, references from HBM
-#define TRYQ(GG, RR, NAME)                                                      \
+#define TRYQ(GG, RR, NAME, PNAME)                                               \
             if (q <= (GG) * (RR)) {                                         \
                 int rc = launch_nwsgq<GG, RR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream); \
-                if (rc <= 0) { if (kernel_name) *kernel_name = NAME; return rc; } \
+                if (rc <= 0) { if (kernel_name) *kernel_name = m.pssm ? PNAME : NAME; return rc; } \
             }
-            TRYQ(16, 10, "pmx_nwsg16q_kernel<16,10>/shared profile")
-            TRYQ(16, 16, "pmx_nwsg16q_kernel<16,16>/shared profile")
-            TRYQ(32, 10, "pmx_nwsg16q_kernel<32,10>/shared profile")
-            TRYQ(32, 16, "pmx_nwsg16q_kernel<32,16>/shared profile")
-            TRYQ(64, 16, "pmx_nwsg16q_kernel<64,16>/shared profile")
-            TRYQ(64, 32, "pmx_nwsg16q_kernel<64,32>/shared profile")
+            TRYQ(16, 10, "pmx_nwsg16q_kernel<16,10>/shared profile", "pmx_nwsg16q_kernel<16,10,pssm>/shared PSSM profile")
+            TRYQ(16, 16, "pmx_nwsg16q_kernel<16,16>/shared profile", "pmx_nwsg16q_kernel<16,16,pssm>/shared PSSM profile")
+            TRYQ(32, 10, "pmx_nwsg16q_kernel<32,10>/shared profile", "pmx_nwsg16q_kernel<32,10,pssm>/shared PSSM profile")
+            TRYQ(32, 16, "pmx_nwsg16q_kernel<32,16>/shared profile", "pmx_nwsg16q_kernel<32,16,pssm>/shared PSSM profile")
+            TRYQ(64, 16, "pmx_nwsg16q_kernel<64,16>/shared profile", "pmx_nwsg16q_kernel<64,16,pssm>/shared PSSM profile")
+            TRYQ(64, 32, "pmx_nwsg16q_kernel<64,32>/shared profile", "pmx_nwsg16q_kernel<64,32,pssm>/shared PSSM profile")
 #undef TRYQ
         }
+        if (m.pssm) return 1;
         if (!b.q_shared && !b.track8 && m.msize > 8 && m.msize < 32 && b.n > 2048 && !pmx_env("PMX_NWSG16_NO_MATRIX_LOOKUP")) {   // per-pair, large alphabet
 #define TRYM(GG, RR, NAME)                                                      \
             if (q <= (GG) * (RR)) {                                             \
@@ -1841,7 +1866,7 @@ int pmx_launch_nwsg16(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg
         TRYV(64, 32, "pmx_nwsg16v_kernel<64,32>")
 #undef TRYV
     }
-    if (b.track8) return 1;                                    // (the first-generation kernel does not track the range: general kernel)
+    if (b.track8 || m.pssm) return 1;                          // (the first-generation kernel does not track the range / read a PSSM: general kernel)
     // exact window of the biased lanes: every H, E, F, H-open, E-ext and H(diag)+score stays inside
     const long long lo = -(3LL * open + (long long)(b.max_qlen + b.max_rlen + 2) * ext + (m.min < 0 ? -m.min : 0));
     const long long hi = (long long)(b.max_qlen < b.max_rlen ? b.max_qlen : b.max_rlen) * (m.max > 0 ? m.max : 0) + (m.max > 0 ? m.max : 0);

@@ -344,6 +344,7 @@ static int launch_stats(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
 int pmx_launch_stats16(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
                        pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t stream, const char **kernel_name)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (pmx_env("PMX_NO_FAST_STATS")) return 1;
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG && mode != PMX_MODE_SW) return 1;
     if (m.msize > PMX_MAX_FAST_MSIZE - 1) return 1;

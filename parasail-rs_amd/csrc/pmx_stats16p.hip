@@ -373,6 +373,7 @@ static int launch_statsp(const PmxBatch &b, const PmxDevMatrix &m, int mode, int
 int pmx_launch_stats16p(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
                         pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t stream, const char **kernel_name)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (pmx_env("PMX_NO_FAST_STATS") || pmx_env("PMX_STATS16_GEN1")) return 1;
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG) return 1;
     // Where it pays (measured): one shared query profile per workgroup (the profile arm, config 3) and results that

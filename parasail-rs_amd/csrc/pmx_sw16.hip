@@ -593,6 +593,7 @@ static bool sw16_trace_ok(const PmxBatch &b, const PmxDevMatrix &m, int open, in
 }
 int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int *variant, int *Tmax, size_t *trace_bytes)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (!sw16_trace_ok(b, m, open, ext)) return 1;
     if (m.msize > 8 && m.msize < 32 && !pmx_env("PMX_SW16_NO_MATRIX_LOOKUP")) {     // large alphabet: the matrix-lookup kernel (no profile, 1 KB of LDS)
         int G = 0;
@@ -618,6 +619,7 @@ int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int 
 int pmx_launch_sw16_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                           pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (!sw16_trace_ok(b, m, open, ext)) return 1;
     if (variant >= 4) return pmx_launch_sw16m_trace(variant - 4, b, m, open, ext, d_out, tbuf, Tmax, stream);
     switch (variant) {
@@ -651,6 +653,8 @@ int pmx_launch_sw16(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
     const bool sk = var == 2 && open >= ext && !pmx_env("PMX_SW16_NO_SKEW") &&
                     feasible + PK16_SW_BIAS < (long long)PK16_RERUN_LIMIT(m.max) - (long long)(b.max_rlen + 2 * 64 + 4) * ext;
     // alphabets of <= 4 letters (+ wildcard): no LDS profile, the v_perm looks the score up (see PT in the kernel)
+    // a PSSM: only the workgroup-shared byte profile reads its rows (every other form here builds profiles from symbols)
+    if (m.pssm) return (b.q_shared && var == 2 && u8ok && sk) ? pmx_launch_sw16q(b, m, open, ext, d_out, stream, kernel_name) : 1;
     const bool pt = sk && u8ok && m.msize <= 5 && b.retry_list && b.retry_count && !b.q_has_wildcard && !pmx_env("PMX_SW16_NO_PERMTABLE");
     // one shared query (profile arm) with a real LDS profile: the workgroup-shared-profile kernel (pmx_sw16q.hip)
     if (b.q_shared && var == 2 && u8ok && sk && !pt) {

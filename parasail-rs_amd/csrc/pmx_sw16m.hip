@@ -254,6 +254,7 @@ static int launch_m(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
 int pmx_launch_sw16m_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                            pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     switch (variant) {
     case 1: return launch_m<16, 16, true>(b, m, open, ext, d_out, stream, tbuf, Tmax);
     case 2: return launch_m<32, 16, true>(b, m, open, ext, d_out, stream, tbuf, Tmax);
@@ -267,6 +268,7 @@ int pmx_launch_sw16m_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m
 int pmx_launch_sw16m(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                      pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (b.q_shared || m.msize > 31 || pmx_env("PMX_SW16_NO_MATRIX_LOOKUP")) return 1;
     const int q = b.max_qlen;
 #define TRYM(GG, RR, NAME)                                                      \

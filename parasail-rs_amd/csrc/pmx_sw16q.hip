@@ -10,12 +10,15 @@
 //   * reference symbols are not staged in LDS: each lane fetches its next symbols from HBM two steps ahead
 //     (neighbouring lanes read neighbouring bytes).  16 references of 5 kaa would otherwise take 80 KB.
 // LDS drops from 57 KB per wave to 11 KB per workgroup, the occupancy from 0.5 to 4 waves per SIMD.
+//
+// PSSM form (PSSM = true): the profile byte of query row er is PSSM row er (gmat[er * msize + sym]) instead of the matrix row of
+// the query's symbol; the msize^2 matrix is not staged and the query bytes are not read.  The sweep is the same instruction stream.
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
 #include <cstdlib>
 
-template <int G, int R, int WAVES>
+template <int G, int R, int WAVES, bool PSSM = false>
 __global__ __launch_bounds__(64 * WAVES)
 void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
                       const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff,
@@ -40,11 +43,12 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
 
     unsigned char *psc = lds;                   // [MS1][QPS]
     int16_t *mat = reinterpret_cast<int16_t *>(lds + ((MS1 * QPS + 7) & ~7));
-    unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((msize * msize * 2) & 7)) & 7));   // per pair: r offset, rlen, pair index
+    const int mcells = PSSM ? 0 : msize * msize;    // (PSSM: no staged matrix)
+    unsigned char *map = reinterpret_cast<unsigned char *>(mat + mcells);
+    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((mcells * 2) & 7)) & 7));   // per pair: r offset, rlen, pair index
 
     const long long pair0 = (long long)blockIdx.x * NP;
-    for (int i = tid; i < msize * msize; i += NT) mat[i] = gmat[i];
+    for (int i = tid; i < mcells; i += NT) mat[i] = gmat[i];
     for (int i = tid; i < 256; i += NT) map[i] = gmap[i];
     if (tid < NP) {
         long long pos = pair0 + tid; if (pos >= n) pos = n - 1;
@@ -57,9 +61,14 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
     __syncthreads();
     // the shared profile: query row i = l * R + k sits at byte l * RS + k; rows beyond the query score 0
     for (int er = tid; er < G * R; er += NT) {
-        const int q0 = (er < qlen) ? (int)map[qbuf[er]] : -1;
         unsigned char *sc = psc + (er / R) * RS + er % R;
-        for (int sym = 0; sym < msize; ++sym) sc[sym * QPS] = (unsigned char)(((q0 < 0) ? 0 : mat[q0 * msize + sym]) + open);
+        if constexpr (PSSM) {
+            const int16_t *prow = gmat + (size_t)er * msize;
+            for (int sym = 0; sym < msize; ++sym) sc[sym * QPS] = (unsigned char)(((er < qlen) ? prow[sym] : 0) + open);
+        } else {
+            const int q0 = (er < qlen) ? (int)map[qbuf[er]] : -1;
+            for (int sym = 0; sym < msize; ++sym) sc[sym * QPS] = (unsigned char)(((q0 < 0) ? 0 : mat[q0 * msize + sym]) + open);
+        }
         sc[msize * QPS] = 0;
     }
     __syncthreads();
@@ -196,16 +205,16 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
     }
 }
 
-template <int G, int R, int WAVES>
+template <int G, int R, int WAVES, bool PSSM = false>
 static int launch_q(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, pmx_record_t *d_out, hipStream_t stream)
 {
     constexpr int RS = (R + 3) / 4 * 4, NP = 2 * (64 / G) * WAVES;
-    const size_t lds = (size_t)(m.msize + 1) * G * RS + 8 + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 24;
+    const size_t lds = (size_t)(m.msize + 1) * G * RS + 8 + (PSSM ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)NP * 24;
     if (lds > 160 * 1024) return 1;
-    { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_sw16q_kernel<G, R, WAVES>)); if (rc) return rc; }
+    { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_sw16q_kernel<G, R, WAVES, PSSM>)); if (rc) return rc; }
     const long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
-    hipLaunchKernelGGL((pmx_sw16q_kernel<G, R, WAVES>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
+    hipLaunchKernelGGL((pmx_sw16q_kernel<G, R, WAVES, PSSM>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                        b.qbuf, b.q_shared, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
                        PK16_RERUN_LIMIT(m.max) - (b.max_rlen + 2 * G + 4) * ext, b.sat_above > 0 ? b.sat_above : 2147483647, b.perm, d_out);
     hipError_t e = hipGetLastError();
@@ -213,12 +222,29 @@ static int launch_q(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
 }
 
 // 0 launched, 1 not eligible (the caller goes on with pmx_sw16's own variants), <0 HIP error.
-// The caller has already established the conditions of the skewed byte-profile variant.
+// The caller has already established the conditions of the skewed byte-profile variant.  A PSSM (m.pssm) takes the PSSM form: the
+// shared query is the PSSM's rows (b.q_shared = its length).
 int pmx_launch_sw16q(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                      pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
 {
     if (!b.q_shared || pmx_env("PMX_SW16_NO_SHARED")) return 1;
     const int q = b.max_qlen;
+    if (m.pssm) {
+        if (m.rows != b.q_shared) return 1;
+#define TRYP(GG, RR, NAME)                                                      \
+        if (q <= (GG) * (RR)) {                                                 \
+            int rc = launch_q<GG, RR, 4, true>(b, m, open, ext, d_out, stream); \
+            if (rc <= 0) { if (kernel_name) *kernel_name = NAME; return rc; }   \
+        }
+        TRYP(16, 10, "pmx_sw16q_kernel<16,10,pssm>/shared PSSM profile")
+        TRYP(16, 16, "pmx_sw16q_kernel<16,16,pssm>/shared PSSM profile")
+        TRYP(32, 10, "pmx_sw16q_kernel<32,10,pssm>/shared PSSM profile")
+        TRYP(32, 16, "pmx_sw16q_kernel<32,16,pssm>/shared PSSM profile")
+        TRYP(64, 16, "pmx_sw16q_kernel<64,16,pssm>/shared PSSM profile")
+        TRYP(64, 32, "pmx_sw16q_kernel<64,32,pssm>/shared PSSM profile")
+#undef TRYP
+        return 1;
+    }
 #define TRYQ(GG, RR, NAME)                                                      \
     if (q <= (GG) * (RR)) {                                                     \
         int rc = launch_q<GG, RR, 4>(b, m, open, ext, d_out, stream);          \

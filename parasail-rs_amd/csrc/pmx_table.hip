@@ -234,6 +234,7 @@ int pmx_launch_table(int mode, int sg_flags, int open, int ext, const PmxDevMatr
                      int max_qlen, int max_rlen, const int64_t *tab_off, int32_t *table, int32_t *row_out, int32_t *col_out,
                      pmx_record_t *out, hipStream_t stream, int8_t *trace)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (n <= 0) return 0;
     if (pmx_env("PMX_NO_FAST_TABLE")) return 1;
     if (open < ext || ext < 0 || m.msize > PMX_MAX_FAST_MSIZE || max_rlen > 64 * 16 || max_qlen > 100000) return 1;

@@ -457,6 +457,7 @@ static int launch_trace(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
 int pmx_trace16_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
                      int *variant, int *Tmax, size_t *trace_bytes, bool packed_ok)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (pmx_env("PMX_NO_FAST_TRACE")) return 1;
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG && mode != PMX_MODE_SW) return 1;
     if (m.msize > PMX_MAX_FAST_MSIZE - 1) return 1;
@@ -491,6 +492,7 @@ int pmx_launch_trace16(int variant, const PmxBatch &b, const PmxDevMatrix &m, in
                        uint32_t *ops, const int64_t *ops_off, int32_t *nops, int32_t *beg, hipStream_t stream, pmx_stats_t *stats_out,
                        const PmxWalkSplit *split)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     const bool sw = mode == PMX_MODE_SW;
     const bool sg_ = mode == PMX_MODE_SG;
     const int col_pen_ = sw ? 0 : !(sg_ && (sg_flags & PMX_SG_QB)), row_pen_ = sw ? 0 : !(sg_ && (sg_flags & PMX_SG_DB));

@@ -121,6 +121,7 @@ int pmx_launch_walkb(int mode, int sg_flags, int open, int ext, const PmxDevMatr
                      const int64_t *slot_qoff, long long ops_base, uint32_t *ops, int32_t *nops, int32_t *textlen,
                      pmx_stats_t *stats_out, hipStream_t stream)
 {
+    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (n <= 0) return 0;
     const bool sg = mode == PMX_MODE_SG;
     const int col_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_QB));   // H(i, -1) penalised

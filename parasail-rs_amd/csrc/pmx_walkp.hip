@@ -30,7 +30,10 @@
 // ST (statistics instead of run-length ops) and SW (local alignment: the path ends where the score is used up) are template
 // parameters: the walk is VALU-bound beside the sweep it overlaps with, and each mode carries the other modes' bookkeeping otherwise
 // (score lookups and prefix sums only SW / ST need, run merging and text lengths only the op mode needs).
-template <int G, int R, bool ST, bool SW>
+// PS: `scores` is a PSSM (row = query position): the score of a diagonal cell is scores[i * msize + rsym], read through the cache
+// (the rows one walk reaches are few and every pair of the batch shares them); no matrix is staged.  m_eq still compares the mapped
+// symbols of the letters.
+template <int G, int R, bool ST, bool SW, bool PS = false>
 __global__ __launch_bounds__(256)
 void pmx_walkp_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, int q_shared,
                       const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff,
@@ -49,7 +52,7 @@ void pmx_walkp_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     __shared__ unsigned char s_map[256];
     __shared__ int16_t s_scores[PMX_MAX_FAST_MSIZE * PMX_MAX_FAST_MSIZE];
     for (int x = threadIdx.x; x < 256; x += blockDim.x) s_map[x] = mapper[x];
-    for (int x = threadIdx.x; x < msize * msize; x += blockDim.x) s_scores[x] = scores[x];
+    if constexpr (!PS) for (int x = threadIdx.x; x < msize * msize; x += blockDim.x) s_scores[x] = scores[x];
     __syncthreads();
 
     const int lane = threadIdx.x & 63, l = lane & (LG - 1), gbase = lane & ~(LG - 1);
@@ -114,7 +117,9 @@ void pmx_walkp_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
         }
         const int nib = cell ? (int)((w >> (8 * (bb & 3) + ((k & 1) ? 0 : 4))) & 0xFu) : 0;
         if (where == 0) { a = s_map[a]; bsym = s_map[bsym]; }
-        const int sc = ((ST || SW) && where == 0 && cell) ? (int)s_scores[a * msize + bsym] : 0;
+        int sc;
+        if constexpr (PS) sc = ((ST || SW) && where == 0 && cell) ? (int)scores[(size_t)pi_ * msize + bsym] : 0;
+        else sc = ((ST || SW) && where == 0 && cell) ? (int)s_scores[a * msize + bsym] : 0;
         // group masks
         const unsigned m_cell = group_bits(cell);
         const unsigned m_diag = group_bits(cell && !(nib & 8));
@@ -209,15 +214,18 @@ void pmx_walkp_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     beg[2 * pair] = i + 1; beg[2 * pair + 1] = j + 1;
 }
 
-// variant: the packed sweep's lane-group size index (0..3 -> G = 8, 16, 32, 64); rows per lane R = 16 or 10
+// variant: the packed sweep's lane-group size index (0..3 -> G = 8, 16, 32, 64); rows per lane R = 16 or 10.  A PSSM (m.pssm):
+// statistics of global / semi-global paths only (the PS form), 1 otherwise.
 int pmx_launch_walkp(int gsel, int R, const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, int Tmax, int top_aligned,
                      pmx_stats_t *stats_out, int row_pen, int col_pen, const uint32_t *tbuf, const pmx_record_t *recs,
                      uint32_t *ops, const int64_t *ops_off, long long ops_base, int32_t *nops, int32_t *beg, int32_t *textlen,
                      hipStream_t stream, const int *blockflag)
 {
     if (b.n <= 0) return 0;
+    if (m.pssm && (stats_out == nullptr || mode == PMX_MODE_SW || m.rows != b.q_shared)) return 1;
     const dim3 grid((unsigned)((b.n * LG + 255) / 256)), block(256);
-#define WALKP4(GG, RR, STV, SWV) hipLaunchKernelGGL((pmx_walkp_kernel<GG, RR, STV, SWV>), grid, block, 0, stream, \
+#define WALKP4(GG, RR, STV, SWV) do { if (m.pssm) WALKP5(GG, RR, true, false, true); else WALKP5(GG, RR, STV, SWV, false); } while (0)
+#define WALKP5(GG, RR, STV, SWV, PSV) hipLaunchKernelGGL((pmx_walkp_kernel<GG, RR, STV, SWV, PSV>), grid, block, 0, stream, \
         b.qbuf, b.qoff, b.q_shared, b.rbuf, b.roff, (long long)b.n, b.perm, m.mapper, m.scores, m.msize, open, ext, mode, Tmax, top_aligned, blockflag, \
         stats_out, row_pen, col_pen, tbuf, recs, ops, ops_off, ops_base, nops, beg, textlen)
 #define WALKP(GG, RR) do { const bool st_ = stats_out != nullptr, sw_ = mode == PMX_MODE_SW; \
@@ -245,6 +253,7 @@ int pmx_launch_walkp(int gsel, int R, const PmxBatch &b, const PmxDevMatrix &m, 
     } else return 1;
 #undef WALKP
 #undef WALKP4
+#undef WALKP5
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
 }
