@@ -339,6 +339,41 @@ int pmx_align_batch_banded_cigar_device(const pmx_config_t *cfg, const parasail_
                                         pmx_record_t *d_out, pmx_stats_t *d_stats_out,
                                         char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream);
 
+/* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
+ * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
+ * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from
+ * band to band and the (H, E) of every tile_cols-th column, and a walk re-derives, from the end cell backwards, just the tiles the
+ * optimal path enters.  No buffer on the device or the host is proportional to qlen x rlen; pmx_long_cigar_scratch_bytes() tells the
+ * checkpoint scratch of one chunk of pairs for given maxima (no GPU needed; -1 with a pmx_last_error() text for options not offered).
+ * Beside it the call keeps, for the whole batch, 4 bytes per op slot (qlen + rlen + 1 slots per pair; the device entry, which sees
+ * only the maxima, n x (max_qlen + max_rlen + 1)), 8 bytes per pair and the text.
+ * cfg->want must contain PMX_WANT_CIGAR and/or PMX_WANT_STATS; PMX_WANT_SORTED is allowed.  NW, SG with any free ends, SW; square
+ * matrices of up to 64 letters; any open >= 0, extend >= 0 the long-pair kernel takes; any lengths >= 1 (pairs shorter than a band or a
+ * tile are correct, not fast).  Records are the 32-bit records of pmx_align_batch for the same pair (cfg->width is ignored); CIGAR text,
+ * letters (PMX_CIGAR_SWAP_ID) and statistics are those of pmx_align_batch_cigar / the statistics kernels.  The text follows
+ * pmx_align_batch_cigar (a block freed with pmx_free, cigar_off n + 1 entries); the device entry follows
+ * pmx_align_batch_cigar_device (n + 1 offsets starting at 0; a pair whose text would cross cigar_capacity is not written; asynchronous
+ * on `stream`: a call whose scratch is already large enough returns without a host synchronisation; the first call of a thread, and
+ * one that needs more scratch than any before it, allocate, which synchronises).  opts == NULL or a zero field: the default.  tile_cols: 64, 128 or 256; band_rows: 128, 256 or
+ * 1024.  The choice never changes a result.
+ * The bands of a pair wait for one another with a bounded wait (pmx_align_batch on long pairs does the same); should a wait run out,
+ * the host entry returns -3 with a pmx_last_error() text and no alignment; the device entry leaves every record of that chunk of
+ * pairs and of the later ones with PMX_FLAG_RERUN, an empty text and zero statistics (earlier chunks are complete): a record with
+ * PMX_FLAG_RERUN means the call has to be redone.  Refused with -1 and a pmx_last_error() text before any GPU work: PSSM matrices,
+ * a want without PMX_WANT_CIGAR and PMX_WANT_STATS, options not offered, bad offsets. */
+typedef struct pmx_long_cigar_opts { int tile_cols; int band_rows; } pmx_long_cigar_opts_t;   /* 0 = default */
+int pmx_align_batch_cigar_long(const pmx_config_t *cfg, int64_t n,
+                               const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff,
+                               pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */,
+                               char **cigar_buf, int64_t *cigar_off /* NULL unless WANT_CIGAR */,
+                               const pmx_long_cigar_opts_t *opts);
+int pmx_align_batch_cigar_long_device(const pmx_config_t *cfg, int64_t n,
+                                      const uint8_t *d_qbuf, const int64_t *d_qoff, const uint8_t *d_rbuf, const int64_t *d_roff,
+                                      int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out,
+                                      char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream,
+                                      const pmx_long_cigar_opts_t *opts);
+long long pmx_long_cigar_scratch_bytes(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_long_cigar_opts_t *opts);
+
 /* CIGAR text for a batch (semi-global / global / local with traceback done on the device).
  * cigar_off has n+1 entries; *cigar_buf is malloc'd by the callee and freed with pmx_free.  A PSSM: every query has its length. */
 int pmx_align_batch_cigar(const pmx_config_t *cfg, int64_t n,

@@ -59,6 +59,14 @@ pub struct PmxStats {
     pub length: i32,
 }
 
+/// `pmx_long_cigar_opts_t`: tile width and band height of the tiled long-pair traceback (0 = default; never change a result).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct PmxLongCigarOpts {
+    pub tile_cols: c_int,
+    pub band_rows: c_int,
+}
+
 pub const PMX_WANT_STATS: c_int = 1;
 pub const PMX_WANT_CIGAR: c_int = 2;
 pub const PMX_WANT_SORTED: c_int = 4;
@@ -98,6 +106,20 @@ extern "C" {
         d_out: *mut PmxRecord, d_stats_out: *mut PmxStats,
         d_cigar_text: *mut c_char, cigar_capacity: i64, d_cigar_off: *mut i64, stream: *mut c_void,
     ) -> c_int;
+    fn pmx_align_batch_cigar_long(
+        cfg: *const PmxConfig, n: i64,
+        qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
+        out: *mut PmxRecord, stats_out: *mut PmxStats,
+        cigar_buf: *mut *mut c_char, cigar_off: *mut i64, opts: *const PmxLongCigarOpts,
+    ) -> c_int;
+    pub fn pmx_align_batch_cigar_long_device(
+        cfg: *const PmxConfig, n: i64,
+        d_qbuf: *const u8, d_qoff: *const i64, d_rbuf: *const u8, d_roff: *const i64,
+        max_qlen: i32, max_rlen: i32, d_out: *mut PmxRecord, d_stats_out: *mut PmxStats,
+        d_cigar_text: *mut c_char, cigar_capacity: i64, d_cigar_off: *mut i64, stream: *mut c_void,
+        opts: *const PmxLongCigarOpts,
+    ) -> c_int;
+    pub fn pmx_long_cigar_scratch_bytes(n: i64, max_qlen: i32, max_rlen: i32, opts: *const PmxLongCigarOpts) -> i64;
     fn pmx_align_batch_multi(
         cfg: *const PmxConfig, n: i64,
         qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
@@ -293,6 +315,29 @@ impl Aligner {
             return Err(last_error());
         }
         Ok(records)
+    }
+
+    /// Long pairs with traceback in linear memory (extension, `pmx_align_batch_cigar_long`): records, CIGAR text and, with
+    /// `want_stats`, matches / similar / length along each path.  No buffer is proportional to `qlen x rlen`.
+    pub fn cigar_long_batch(&self, queries: &Packed, references: &Packed, want_stats: bool, opts: Option<PmxLongCigarOpts>)
+                            -> Result<(Vec<PmxRecord>, BatchCigars, Option<Vec<PmxStats>>)> {
+        let n = references.len();
+        let mut records = vec![PmxRecord::default(); n];
+        let mut stats = if want_stats { Some(vec![PmxStats::default(); n]) } else { None };
+        let stats_ptr = stats.as_mut().map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let mut off = vec![0i64; n + 1];
+        let mut text: *mut c_char = std::ptr::null_mut();
+        let cfg = self.pmx_config(PMX_WANT_CIGAR | if want_stats { PMX_WANT_STATS } else { 0 });
+        let opts = opts.unwrap_or_default();
+        let rc = unsafe {
+            pmx_align_batch_cigar_long(&cfg, n as i64, queries.buf.as_ptr(), queries.off.as_ptr(),
+                                       references.buf.as_ptr(), references.off.as_ptr(),
+                                       records.as_mut_ptr(), stats_ptr, &mut text, off.as_mut_ptr(), &opts)
+        };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok((records, BatchCigars { text, off }, stats))
     }
 
     /// Banded batch with traceback (extension): the records of `banded_batch`, the CIGAR text of each pair's path inside the band

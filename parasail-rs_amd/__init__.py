@@ -54,6 +54,10 @@ class pmx_config_t(C.Structure):
                 ("width", C.c_int), ("want", C.c_int), ("matrix", C.POINTER(parasail_matrix_t))]
 
 
+class pmx_long_cigar_opts_t(C.Structure):
+    _fields_ = [("tile_cols", C.c_int), ("band_rows", C.c_int)]
+
+
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
 STATS_DTYPE = np.dtype([("matches", "<i4"), ("similar", "<i4"), ("length", "<i4")])
 
@@ -138,6 +142,12 @@ _sig("pmx_align_batch_banded_cigar", C.c_int, C.POINTER(pmx_config_t), C.c_void_
 _sig("pmx_align_batch_banded_cigar_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_void_p)
+_sig("pmx_align_batch_cigar_long", C.c_int, C.POINTER(pmx_config_t), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(pmx_long_cigar_opts_t))
+_sig("pmx_align_batch_cigar_long_device", C.c_int, C.POINTER(pmx_config_t), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_long_cigar_opts_t))
+_sig("pmx_long_cigar_scratch_bytes", C.c_longlong, C.c_int64, C.c_int32, C.c_int32, C.POINTER(pmx_long_cigar_opts_t))
 _sig("pmx_align_batch_multi", C.c_int, C.POINTER(pmx_config_t), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 _sig("pmx_align_profile_batch_multi", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -855,6 +865,37 @@ class Aligner:
         cigars = [raw[coff[k]:coff[k + 1]].decode() for k in range(n)]
         return (out, cigars, st) if stats else (out, cigars)
 
+    def align_batch_cigar_long(self, queries, references, stats=False, cigar=True, tile_cols=0, band_rows=0):
+        """Long pairs with traceback in linear memory (extension): the records of align_batch, each pair's CIGAR string and, with
+        stats=True, matches / similar / length along the path.  tile_cols / band_rows: 0 = default (never change a result).
+        Returns (records, cigars), (records, cigars, stats) or, with cigar=False, (records, stats)."""
+        qbuf, qoff = pack(queries)
+        rbuf, roff = pack(references)
+        n = len(roff) - 1
+        if len(qoff) - 1 != n:
+            raise BatchError("queries and references differ in count")
+        cfg = self._config()
+        cfg.want = (WANT_CIGAR if cigar else 0) | (WANT_STATS if stats else 0)
+        out = np.zeros(n, dtype=RECORD_DTYPE)
+        st = np.zeros(n, dtype=STATS_DTYPE) if stats else None
+        coff = np.zeros(n + 1, dtype=np.int64)
+        opts = pmx_long_cigar_opts_t(int(tile_cols), int(band_rows))
+        cbuf = C.c_void_p()
+        rc = lib.pmx_align_batch_cigar_long(C.byref(cfg), n, qbuf.ctypes.data, qoff.ctypes.data, rbuf.ctypes.data, roff.ctypes.data,
+                                            out.ctypes.data, st.ctypes.data if st is not None else None,
+                                            C.byref(cbuf) if cigar else None, coff.ctypes.data if cigar else None, C.byref(opts))
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        if not cigar:
+            return out, st
+        try:
+            raw = C.string_at(cbuf.value, int(coff[n])) if cbuf.value and coff[n] else b""
+        finally:
+            if cbuf.value:
+                lib.pmx_free(cbuf)
+        cigars = [raw[coff[k]:coff[k + 1]].decode() for k in range(n)]
+        return (out, cigars, st) if stats else (out, cigars)
+
     def align_batch_cigar(self, queries, references):
         qbuf, qoff = pack(queries)
         rbuf, roff = pack(references)
@@ -927,6 +968,25 @@ def align_batch_cigar_device(cfg, n, d_qbuf, d_qoff, d_rbuf, d_roff, max_qlen, m
                                           d_out, d_text, capacity, d_text_off, stream)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_batch_cigar_long_device(cfg, n, d_qbuf, d_qoff, d_rbuf, d_roff, max_qlen, max_rlen, d_out, d_stats, d_text, capacity, d_text_off,
+                                  stream=0, tile_cols=0, band_rows=0):
+    """Device-pointer entry of the tiled long-pair traceback: records, statistics, CIGAR text + n+1 text offsets in device memory."""
+    opts = pmx_long_cigar_opts_t(int(tile_cols), int(band_rows))
+    rc = lib.pmx_align_batch_cigar_long_device(C.byref(cfg), n, d_qbuf, d_qoff, d_rbuf, d_roff, max_qlen, max_rlen,
+                                               d_out, d_stats, d_text, capacity, d_text_off, stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def long_cigar_scratch_bytes(n, max_qlen, max_rlen, tile_cols=0, band_rows=0):
+    """Device scratch of one chunk of the tiled long-pair traceback (a planner: no GPU needed)."""
+    opts = pmx_long_cigar_opts_t(int(tile_cols), int(band_rows))
+    v = lib.pmx_long_cigar_scratch_bytes(n, max_qlen, max_rlen, C.byref(opts))
+    if v < 0:
+        raise BatchError(lib.pmx_last_error().decode())
+    return int(v)
 
 
 def align_profile_batch_device(cfg, profile, n, d_rbuf, d_roff, max_rlen, d_out, d_stats=None, stream=0):

@@ -488,6 +488,33 @@ public:
         return out;
     }
 
+    // additive: long pairs with traceback in linear memory (pmx_align_batch_cigar_long): records + CIGAR text and, with `stats`, the
+    // path's matches / similar / length.  tile_cols / band_rows: 0 = default; they never change a result.
+    std::vector<pmx_record_t> align_batch_cigar_long(const std::vector<Bytes> &queries, const std::vector<Bytes> &refs,
+                                                     std::vector<std::string> &cigars, std::vector<pmx_stats_t> *stats = nullptr,
+                                                     int tile_cols = 0, int band_rows = 0) const
+    {
+        if (queries.size() != refs.size()) throw Error(ErrorKind::Batch, "queries and references differ in count");
+        std::string qb, rb; std::vector<int64_t> qo(1, 0), ro(1, 0);
+        for (auto &q : queries) { qb += q; qo.push_back((int64_t)qb.size()); }
+        for (auto &r : refs) { rb += r; ro.push_back((int64_t)rb.size()); }
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        cfg.want = PMX_WANT_CIGAR | (stats ? PMX_WANT_STATS : 0);
+        std::vector<pmx_record_t> out(refs.size());
+        std::vector<int64_t> coff(refs.size() + 1);
+        if (stats) stats->resize(refs.size());
+        const pmx_long_cigar_opts_t opts = {tile_cols, band_rows};
+        char *text = nullptr;
+        const int rc = pmx_align_batch_cigar_long(&cfg, (int64_t)refs.size(), (const uint8_t *)qb.data(), qo.data(), (const uint8_t *)rb.data(),
+                                                  ro.data(), out.data(), stats ? stats->data() : nullptr, &text, coff.data(), &opts);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        cigars.resize(refs.size());
+        for (size_t k = 0; k < refs.size(); ++k) cigars[k].assign(text + coff[k], text + coff[k + 1]);
+        pmx_free(text);
+        return out;
+    }
+
     std::shared_ptr<Matrix> matrix;
     int gap_open = 0, gap_extend = 0;
     std::string vec_strategy;

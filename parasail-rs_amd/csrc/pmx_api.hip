@@ -2535,7 +2535,10 @@ static int cigar_chunk(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
         if (dto.try_alloc(n + 1)) { set_err("out of device memory"); return -2; }
         HIP_OR_RET(hipMemcpy(dto.p, tab_off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
         int8_t *dtrace = nullptr;
-        if (scratch_reserve((size_t)tab_off[n], (void **)&dtrace, SCR_TRACE)) return -1;
+        if (scratch_reserve((size_t)tab_off[n], (void **)&dtrace, SCR_TRACE)) {
+            set_err("a byte trace table of %lld bytes could not be reserved; pmx_align_batch_cigar_long traces long pairs in linear memory", (long long)tab_off[n]);
+            return -1;
+        }
         PmxGeneralArgs a = general_args(cfg, dm, n, dq.p, dqo.p, 0, dr.p, dro.p, mr);
         a.rec = drec.p; a.tab_off = dto.p; a.trace_table = dtrace;
         rc = general_batch(a, false, nullptr);
@@ -2881,6 +2884,201 @@ extern "C" int pmx_align_batch_banded_cigar(const pmx_config_t *cfg, const paras
                                                            drec.p, dst.p, dtext.p, capacity, dtoff.p, nullptr);
         if (rc) return rc;
         HIP_OR_RET(hipDeviceSynchronize());
+        if (!want_cigar) break;
+        HIP_OR_RET(hipMemcpy(cigar_off, dtoff.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
+        if (cigar_off[n] <= capacity) break;
+        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
+        (void)hipFree(dtext.p); dtext.p = nullptr;
+        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    }
+    HIP_OR_RET(hipMemcpy(out, drec.p, sizeof(pmx_record_t) * n, hipMemcpyDeviceToHost));
+    if (want_stats) HIP_OR_RET(hipMemcpy(stats_out, dst.p, sizeof(pmx_stats_t) * n, hipMemcpyDeviceToHost));
+    if (want_cigar) {
+        TextBuf text;
+        char *dst_text = text.grow((size_t)cigar_off[n]);
+        if (!dst_text) { set_err("out of memory"); return -1; }
+        if (cigar_off[n]) {
+            const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
+        }
+        text.len = (size_t)cigar_off[n];
+        text.p[text.len] = 0;
+        *cigar_buf = text.p; g_text_pool.handed_out(text.p, text.cap);
+    }
+    return 0;
+}
+
+// ==================================================================== long pairs: traceback in linear memory ===
+// pmx_align_batch_cigar_long: the checkpoint form of the long-pair sweep (pmx_long.hip, CK) keeps the row granules it hands from band
+// to band anyway plus the (H, E) of every tile_cols-th column; pmx_walkt_kernel (pmx_walkt.hip) re-derives, from the end cell
+// backwards, only the tiles the path enters.  Nothing is proportional to qlen x rlen: per pair 8 bytes per column and band, 8 bytes per
+// row and column tile, 4 bytes per op slot.  Chunks of pairs share one scratch; sweep and walk of a chunk run back to back on the
+// caller's stream, so a chunk's checkpoints live until its walk is done and the next chunk's sweep starts behind it.
+static const int LONGCIG_DEFAULT_TILE = 128;
+struct LongCigPlan { int R, tile_cols; size_t sweep_bytes /* of one chunk, rounded to 256 */, ck_bytes; int64_t chunk; };
+static size_t longcig_budget_default() { return ((size_t)4 << 30) + ((size_t)64 << 20); }      // (long_batch's ceiling)
+// 0 fine, -1 refused with a message.  `budget` = bytes one chunk may take (a single pair always gets what it needs).
+static int longcig_plan(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_long_cigar_opts_t *opts, size_t budget, LongCigPlan *pl)
+{
+    if (n <= 0 || max_qlen <= 0 || max_rlen <= 0) { set_err("n, max_qlen and max_rlen must be positive"); return -1; }
+    int tile = opts ? opts->tile_cols : 0, rows = opts ? opts->band_rows : 0;
+    if (tile == 0) tile = LONGCIG_DEFAULT_TILE;
+    if (tile != 64 && tile != 128 && tile != 256) { set_err("tile_cols %d is not offered (64, 128, 256; 0 = default)", tile); return -1; }
+    if (rows != 0 && rows != 128 && rows != 256 && rows != 1024) { set_err("band_rows %d is not offered (128, 256, 1024; 0 = the dispatcher's choice)", rows); return -1; }
+    long long bstride = 0; int nbmax = 0;
+    auto per_pair = [&](int R) { return pmx_long_scratch_bytes(1, max_qlen, max_rlen, R, &bstride, &nbmax) - 64 + pmx_long_ck_bytes(1, max_qlen, max_rlen, R, tile); };
+    int R = rows ? rows / 64 : 4;
+    if (!rows && per_pair(R) > ((size_t)4 << 30)) R = 16;          // (fewer bands: fewer row granules; as long_batch)
+    const size_t pp = per_pair(R);
+    int64_t chunk = (int64_t)(budget / pp);
+    if (chunk < 1) chunk = 1;
+    if (chunk > n) chunk = n;
+    if (chunk * (int64_t)nbmax > 0x7FFFFFFFLL) chunk = 0x7FFFFFFFLL / nbmax;
+    pl->R = R; pl->tile_cols = tile; pl->chunk = chunk;
+    pl->sweep_bytes = (pmx_long_scratch_bytes(chunk, max_qlen, max_rlen, R, &bstride, &nbmax) + 255) & ~(size_t)255;
+    pl->ck_bytes = pmx_long_ck_bytes(chunk, max_qlen, max_rlen, R, tile);
+    return 0;
+}
+
+extern "C" long long pmx_long_cigar_scratch_bytes(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_long_cigar_opts_t *opts)
+{
+    LongCigPlan pl;
+    size_t budget = longcig_budget_default();
+    if (const char *e = pmx_env("PMX_LONG_CHUNK_BYTES")) budget = (size_t)atof(e);
+    if (longcig_plan(n, max_qlen, max_rlen, opts, budget, &pl)) return -1;
+    return (long long)(pl.sweep_bytes + pl.ck_bytes);
+}
+
+static int long_cigar_check(const pmx_config_t *cfg, const pmx_long_cigar_opts_t *opts)
+{
+    if (check_cfg(cfg)) return -1;
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by the tiled long-pair traceback"); return -1; }
+    if (!(cfg->want & (PMX_WANT_CIGAR | PMX_WANT_STATS))) { set_err("pmx_align_batch_cigar_long needs PMX_WANT_CIGAR and / or PMX_WANT_STATS in cfg->want"); return -1; }
+    if (cfg->want & ~(PMX_WANT_CIGAR | PMX_WANT_STATS | PMX_WANT_SORTED)) { set_err("unknown want bits 0x%x", cfg->want); return -1; }
+    if (cfg->matrix->size > 64) { set_err("the long-pair kernels take alphabets of up to 64 letters (matrix size %d)", cfg->matrix->size); return -1; }
+    LongCigPlan pl;
+    return longcig_plan(1, 1, 1, opts, longcig_budget_default(), &pl);          // (the options alone)
+}
+
+// Validated by the caller; offsets start at 0.  Asynchronous on `st`; *d_abort = the launch's abort word (device).
+static int long_cigar_device(const pmx_config_t *cfg, int64_t n, const uint8_t *d_qbuf, const int64_t *d_qoff,
+                             const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_qlen, int32_t max_rlen,
+                             pmx_record_t *d_out, pmx_stats_t *d_stats, char *d_text, int64_t capacity, int64_t *d_text_off,
+                             const pmx_long_cigar_opts_t *opts, hipStream_t st, const int **d_abort,
+                             int64_t op_slots = 0 /* sum of qlen + rlen + 1 over the batch where the caller knows it; 0: n x the maxima */)
+{
+    const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
+    DevMat dm;
+    if (get_devmat(cfg->matrix, &dm)) return -1;
+    size_t fb = 0, tb = 0;
+    if (hipMemGetInfo(&fb, &tb) != hipSuccess) fb = 0;
+    size_t budget = std::min<size_t>((size_t)4 << 30, fb / 4) + ((size_t)64 << 20);
+    if (const char *e = pmx_env("PMX_LONG_CHUNK_BYTES")) budget = (size_t)atof(e);        // tests force several chunks
+    LongCigPlan pl;
+    if (longcig_plan(n, max_qlen, max_rlen, opts, budget, &pl)) return -1;
+    const int R = pl.R;
+    // two columns per step for a few pairs (latency), one for a batch that fills the chip (long_batch, measured); the switches of the
+    // long-pair sweep act on the shared code as they do there
+    int two_cols = (pl.chunk <= 16 && R != 16) ? 1 : 0;
+    if (pmx_env("PMX_LONG_TWO_COLUMNS")) two_cols = R != 16;
+    if (pmx_env("PMX_LONG_ONE_COLUMN")) two_cols = 0;
+    int spin_limit = 1 << 20;
+    if (const char *e = pmx_env("PMX_LONG_SPIN_LIMIT")) spin_limit = atoi(e);
+    int chunk_cols = 16;
+    if (const char *e = pmx_env("PMX_LONG_CHUNK_COLS")) chunk_cols = atoi(e) == 64 ? 64 : 16;
+    unsigned char *scr = nullptr; uint32_t *dops = nullptr; unsigned char *misc = nullptr;
+    const size_t scan_bytes = want_cigar ? pmx_text_scan_scratch_bytes(n) : 0;
+    const size_t misc_bytes = (size_t)(2 * n + 2) * sizeof(int32_t) + 256 + scan_bytes;
+    if (scratch_reserve(pl.sweep_bytes + pl.ck_bytes, (void **)&scr, SCR_LONG) ||
+        (want_cigar && scratch_reserve((op_slots > 0 ? (size_t)op_slots : (size_t)n * ((size_t)max_qlen + max_rlen + 1)) * sizeof(uint32_t), (void **)&dops, SCR_OPS)) ||
+        scratch_reserve(misc_bytes, (void **)&misc, SCR_CIG)) return -1;
+    int32_t *nops = (int32_t *)misc, *textlen = nops + n;
+    void *scan_tmp = (void *)(((uintptr_t)(textlen + n + 2) + 255) & ~(uintptr_t)255);
+    HIP_OR_RET(hipMemsetAsync(scr, 0, 64, st));
+    for (int64_t c0 = 0; c0 < n; c0 += pl.chunk) {
+        PmxBatch b; memset(&b, 0, sizeof b);
+        b.qbuf = d_qbuf; b.qoff = d_qoff + c0; b.rbuf = d_rbuf; b.roff = d_roff + c0;
+        b.n = (n - c0 < pl.chunk) ? n - c0 : pl.chunk; b.max_qlen = max_qlen; b.max_rlen = max_rlen;
+        long long bstride = 0; int nbmax = 0;
+        void *ck = scr + ((pmx_long_scratch_bytes(b.n, max_qlen, max_rlen, R, &bstride, &nbmax) + 255) & ~(size_t)255);
+        int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, scr, d_out + c0, 2147483647, 0, st,
+                                 spin_limit, chunk_cols, two_cols, ck, pl.tile_cols);
+        if (rc < 0) { set_err("checkpoint sweep launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
+        if (rc) { set_err("the long-pair sweep does not take this configuration (alphabet above 64 letters, scores or gap penalties beyond its 16-bit profile, lengths x penalties beyond 2^29)"); return -1; }
+        rc = pmx_launch_walkt(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, pl.tile_cols, scr, ck, d_out + c0,
+                              d_qoff + c0, -c0, dops, want_cigar ? nops + c0 : nullptr, want_cigar ? textlen + c0 : nullptr,
+                              want_stats ? d_stats + c0 : nullptr, st);
+        if (rc) { set_err("tile walk launch failed (%d)", rc); return rc < 0 ? rc : -1; }
+    }
+    if (want_cigar) {
+        int rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan_tmp, scan_bytes, st);
+        if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
+        rc = pmx_launch_cigar_render_slots(dops, d_qoff, d_roff, 0, nops, d_text_off, d_text, capacity, n, st);
+        if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
+    }
+    if (d_abort) *d_abort = reinterpret_cast<const int *>(scr);
+    g_last_kernel = R == 16 ? "pmx_long32_kernel<16,ck>/checkpoint sweep + pmx_walkt_kernel"
+                  : two_cols ? (R == 2 ? "pmx_long32_kernel_c2<2,ck>/checkpoint sweep + pmx_walkt_kernel" : "pmx_long32_kernel_c2<4,ck>/checkpoint sweep + pmx_walkt_kernel")
+                  : (R == 2 ? "pmx_long32_kernel<2,ck>/checkpoint sweep + pmx_walkt_kernel" : "pmx_long32_kernel<4,ck>/checkpoint sweep + pmx_walkt_kernel");
+    return 0;
+}
+
+extern "C" int pmx_align_batch_cigar_long_device(const pmx_config_t *cfg, int64_t n,
+                                                 const uint8_t *d_qbuf, const int64_t *d_qoff, const uint8_t *d_rbuf, const int64_t *d_roff,
+                                                 int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out,
+                                                 char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream,
+                                                 const pmx_long_cigar_opts_t *opts)
+{
+    if (long_cigar_check(cfg, opts)) return -1;
+    if (n <= 0) return 0;
+    if (!d_qbuf || !d_qoff || !d_rbuf || !d_roff || !d_out) { set_err("null buffer"); return -1; }
+    if ((cfg->want & PMX_WANT_STATS) && !d_stats_out) { set_err("stats requested without a stats buffer"); return -1; }
+    if ((cfg->want & PMX_WANT_CIGAR) && (!d_cigar_text || !d_cigar_off)) { set_err("null cigar output"); return -1; }
+    if (max_qlen <= 0 || max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return long_cigar_device(cfg, n, d_qbuf, d_qoff, d_rbuf, d_roff, max_qlen, max_rlen, d_out, d_stats_out,
+                             d_cigar_text, cigar_capacity, d_cigar_off, opts, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int pmx_align_batch_cigar_long(const pmx_config_t *cfg, int64_t n,
+                                          const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff,
+                                          pmx_record_t *out, pmx_stats_t *stats_out, char **cigar_buf, int64_t *cigar_off,
+                                          const pmx_long_cigar_opts_t *opts)
+{
+    if (long_cigar_check(cfg, opts)) return -1;
+    const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
+    if (want_cigar && (!cigar_buf || !cigar_off)) { set_err("null cigar output"); return -1; }
+    if (want_stats && !stats_out) { set_err("stats requested without a stats buffer"); return -1; }
+    if (want_cigar) *cigar_buf = nullptr;
+    if (n <= 0) return 0;
+    if (!qbuf || !qoff || !rbuf || !roff || !out) { set_err("null buffer"); return -1; }
+    int32_t mq = 0, mr = 0; bool bad = false;
+    host_maxlens(n, roff, &mr, &bad);
+    host_maxlens(n, qoff, &mq, &bad);
+    if (bad || roff[0] != 0 || qoff[0] != 0) { set_err("bad offsets (every sequence needs length >= 1, offsets start at 0)"); return -1; }
+    // text capacity: half a byte per symbol + 16 per pair covers related pairs many times over; a batch that needs more runs again
+    int64_t capacity = want_cigar ? ((qoff[n] + roff[n]) / 2 + 16 * n + 256) : 0;
+    DevBuf<uint8_t> dq, dr; DevBuf<int64_t> dqo, dro, dtoff; DevBuf<pmx_record_t> drec; DevBuf<pmx_stats_t> dst; DevBuf<char> dtext;
+    if (dr.try_alloc((size_t)roff[n]) || dro.try_alloc(n + 1) || dq.try_alloc((size_t)qoff[n]) || dqo.try_alloc(n + 1) || drec.try_alloc(n) ||
+        (want_stats && dst.try_alloc(n)) || (want_cigar && (dtoff.try_alloc(n + 1) || dtext.try_alloc((size_t)capacity + 1)))) { set_err("out of device memory"); return -2; }
+    HIP_OR_RET(hipMemcpy(dr.p, rbuf, (size_t)roff[n], hipMemcpyHostToDevice));
+    HIP_OR_RET(hipMemcpy(dro.p, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+    HIP_OR_RET(hipMemcpy(dq.p, qbuf, (size_t)qoff[n], hipMemcpyHostToDevice));
+    HIP_OR_RET(hipMemcpy(dqo.p, qoff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+    for (int pass = 0; pass < 2; ++pass) {
+        const int *d_abort = nullptr;
+        const int rc = long_cigar_device(cfg, n, dq.p, dqo.p, dr.p, dro.p, mq, mr, drec.p, dst.p, dtext.p, capacity, dtoff.p, opts, nullptr, &d_abort,
+                                         qoff[n] + roff[n] + n);
+        if (rc) return rc;
+        HIP_OR_RET(hipDeviceSynchronize());
+        int gave_up = 0;
+        HIP_OR_RET(hipMemcpy(&gave_up, d_abort, sizeof(int), hipMemcpyDeviceToHost));
+        if (gave_up) {
+            set_err("checkpoint sweep: a band's bounded wait for the band above ran out (dispatch order assumption broken, or PMX_LONG_SPIN_LIMIT); "
+                    "no alignment is returned");
+            return -3;
+        }
         if (!want_cigar) break;
         HIP_OR_RET(hipMemcpy(cigar_off, dtoff.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
         if (cigar_off[n] <= capacity) break;

@@ -249,7 +249,19 @@ size_t pmx_long_scratch_bytes(long long n, int max_qlen, int max_rlen, int R, lo
 int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R,
                     void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, hipStream_t stream, int spin_limit = 1 << 20,
                     int chunk_cols = 16 /* boundary columns a band takes over at a time: 16 or 64 (two-column form: steps, 32 or 64) */,
-                    int two_cols = 1 /* rows per lane 2 or 4: the form with two columns per step */);
+                    int two_cols = 1 /* rows per lane 2 or 4: the form with two columns per step */,
+                    void *ck = nullptr /* != NULL: the checkpoint forms -- pmx_long_ck_bytes() bytes for the (H, E) of every tile_cols-th column */,
+                    int tile_cols = 0 /* a power of two */);
+long long pmx_long_ck_slots(int max_rlen, int tile_cols);
+size_t pmx_long_ck_bytes(long long n, int max_qlen, int max_rlen, int R, int tile_cols);
+// Tiled traceback over what the checkpoint sweep left (pmx_walkt.hip): one wave per pair re-derives the tiles the path enters.  Run-length
+// ops / nops / textlen as pmx_launch_walkb (ops == NULL: none) and / or the path's statistics (stats_out != NULL), in one pass.
+// 0 launched, 1 not eligible (the tile's decision bits do not fit the LDS), <0 HIP error.
+size_t pmx_walkt_lds_bytes(int msize, int BR, int tile_cols);
+int pmx_launch_walkt(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R, int tile_cols,
+                     const void *scratch, const void *ck, const pmx_record_t *recs,
+                     const int64_t *slot_qoff, long long ops_base, uint32_t *ops, int32_t *nops, int32_t *textlen,
+                     pmx_stats_t *stats_out, hipStream_t stream);
 
 // Run-time CIGAR letter convention (switch PMX_CIGAR_SWAP_ID, read per call): 1 = exchange I and D in everything handed out.
 int pmx_cigar_swapped();

@@ -50,12 +50,16 @@ struct PmxLongArgs {
     pmx_record_t *out; int sat_above; int force_sat;
     int *abort_word;                                   // device word, zero before the launch: a band gave up waiting
     int spin_limit;                                    // polls of one wait before a band gives up
+    // column checkpoints (CK forms only; layout: pmx_walkt.hip): per (pair, band) `ckslots` slots of 64 R granules (H, E), slot s =
+    // the band's rows at column (s + 1) * tile_cols - 1, in the kernel's own value form
+    int2 *ck; long long ckslots; int ckshift;          // tile_cols = 1 << ckshift
 };
 
 // The rotating registers move with lane_next_untied: lane 63 has no source and gets 0, and what enters there reaches lane 0 only
 // after 64 shifts, when every rotating register has been reloaded.
 
-template <int R, int MODE, int CH /* columns per boundary chunk: 64, or 16 (lanes 0 .. 15 load; a band runs ~50 steps closer behind the one above) */>
+template <int R, int MODE, int CH /* columns per boundary chunk: 64, or 16 (lanes 0 .. 15 load; a band runs ~50 steps closer behind the one above) */,
+          bool CK = false /* also store the band's (H, E) of every tile_cols-th column (the tiled traceback's left boundaries) */>
 __global__ __launch_bounds__(64)
 void pmx_long32_kernel(PmxLongArgs a)
 {
@@ -113,6 +117,8 @@ void pmx_long32_kernel(PmxLongArgs a)
     const int RU = (rl + 63) & ~63, T = RU + 64;
     const unsigned long long *bin = band ? a.bound + ((size_t)pair * a.nbmax + band - 1) * a.bstride : nullptr;
     unsigned long long *bout = lastband ? nullptr : a.bound + ((size_t)pair * a.nbmax + band) * a.bstride;
+    int2 *const ckout = CK ? a.ck + ((size_t)pair * a.nbmax + band) * (size_t)a.ckslots * BR + lane * R : nullptr;
+    const int ckmask = CK ? (1 << a.ckshift) - 1 : 0, ckshift = CK ? a.ckshift : 0;
 
     // chunks of 64 columns: mapped reference symbols (as profile row offsets) and, below band 0, the boundary granules
     int symch = 0, Hb = 0, Fb = 0, symcur = msize * (BR * 2);
@@ -196,6 +202,11 @@ void pmx_long32_kernel(PmxLongArgs a)
                 Hnew[k] = Ho;
             }
             diag = Hin; Hout = Hnew[R - 1]; Fout = F;
+            if (CK && ((t - lane + 1) & ckmask) == 0 && t - lane < rl) {      // (a lane's R granules are contiguous: R x 8 bytes)
+                int2 *p = ckout + ((size_t)((t - lane + 1) >> ckshift) - 1) * BR;
+#pragma unroll
+                for (int k = 0; k < R; ++k) p[k] = make_int2(Hnew[k], E[k]);
+            }
             if (SW) {
                 int cm = Hnew[0];
 #pragma unroll
@@ -296,7 +307,7 @@ void pmx_long32_kernel(PmxLongArgs a)
 // producer's store, loop control) is shared by two columns.  The lanes' skew stays 64 STEPS -- a band starts 64 steps after the one
 // above, which is now 128 columns but the same time.  Same arithmetic, same granules (two per step and lane 63), same captures.
 // CH = steps per boundary chunk (2 CH columns; lanes 0 .. CH-1 load two granules each).
-template <int R, int MODE, int CH>
+template <int R, int MODE, int CH, bool CK = false>
 __global__ __launch_bounds__(64)
 void pmx_long32_kernel_c2(PmxLongArgs a)
 {
@@ -353,6 +364,8 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
     const int RU = (rl + 127) & ~127, CP = RU / 2, T = CP + 64;        // column pairs; steps
     const unsigned long long *bin = band ? a.bound + ((size_t)pair * a.nbmax + band - 1) * a.bstride : nullptr;
     unsigned long long *bout = lastband ? nullptr : a.bound + ((size_t)pair * a.nbmax + band) * a.bstride;
+    int2 *const ckout = CK ? a.ck + ((size_t)pair * a.nbmax + band) * (size_t)a.ckslots * BR + lane * R : nullptr;
+    const int ckmask = CK ? (1 << a.ckshift) - 1 : 0, ckshift = CK ? a.ckshift : 0;
 
     // chunks of 64 steps: mapped reference symbols (two profile row offsets per lane, 16 bits each); chunks of CH steps: granules
     const int padoff = msize * (BR * 2);
@@ -448,6 +461,11 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
 #pragma unroll
             for (int k = 0; k < R; ++k) H[k] = N1[k];
             diag = Hin1; Hout0 = N0[R - 1]; Hout1 = N1[R - 1]; Fout0 = F0; Fout1 = F1;
+            if (CK && ((2 * (t - lane) + 2) & ckmask) == 0 && 2 * (t - lane) + 1 < rl) {      // (tile_cols is even: always the block's second column)
+                int2 *p = ckout + ((size_t)((2 * (t - lane) + 2) >> ckshift) - 1) * BR;
+#pragma unroll
+                for (int k = 0; k < R; ++k) p[k] = make_int2(N1[k], E[k]);
+            }
             if (SW) {
                 int c0 = N0[0], c1 = N1[0];
 #pragma unroll
@@ -601,9 +619,19 @@ size_t pmx_long_scratch_bytes(long long n, int max_qlen, int max_rlen, int R, lo
     return (size_t)n * (size_t)*nbmax * ((size_t)*bstride * 8 + 32) + 64;      // + the abort word (the first 64 bytes of the scratch)
 }
 
+// Column checkpoints of the tiled traceback: slots per (pair, band), and the bytes behind a chunk's other scratch.
+long long pmx_long_ck_slots(int max_rlen, int tile_cols) { return max_rlen / tile_cols + 1; }
+size_t pmx_long_ck_bytes(long long n, int max_qlen, int max_rlen, int R, int tile_cols)
+{
+    const int BR = 64 * R, nbmax = (max_qlen + BR - 1) / BR;
+    return (size_t)n * nbmax * (size_t)pmx_long_ck_slots(max_rlen, tile_cols) * BR * 8;
+}
+
 // 0 launched, 1 not eligible, <0 HIP error.  `scratch` = pmx_long_scratch_bytes() bytes.
+// ck != NULL: the checkpoint forms; `ck` = pmx_long_ck_bytes() bytes.
 int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R,
-                    void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, hipStream_t stream, int spin_limit, int chunk_cols, int two_cols)
+                    void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, hipStream_t stream, int spin_limit, int chunk_cols, int two_cols,
+                    void *ck, int tile_cols)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (b.perm || m.msize > 64) return 1;
@@ -622,6 +650,12 @@ int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_f
     const size_t bound_bytes = (size_t)b.n * nbmax * (size_t)bstride * 8;
     a.cand = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(scratch) + 64 + bound_bytes);
     a.out = d_out; a.sat_above = sat_above; a.force_sat = force_sat;
+    a.ck = reinterpret_cast<int2 *>(ck); a.ckslots = 0; a.ckshift = 0;
+    if (ck) {
+        if (tile_cols < 2 || (tile_cols & (tile_cols - 1))) return 1;
+        while ((1 << a.ckshift) < tile_cols) ++a.ckshift;
+        a.ckslots = pmx_long_ck_slots(b.max_rlen, tile_cols);
+    }
     (void)bytes;
     hipError_t e = bound_bytes ? hipMemsetAsync(a.bound, 0x80, bound_bytes, stream) : hipSuccess;
     if (e != hipSuccess) return -(int)e;
@@ -630,26 +664,28 @@ int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_f
     if (lds > 160 * 1024) return 1;
     const long long blocks = b.n * nbmax;
     if (blocks <= 0 || blocks > 0x7FFFFFFFLL) return 1;
-#define LONG_LAUNCH(RR, MM, CC) do { \
-        const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_long32_kernel<RR, MM, CC>)); if (rc) return rc; \
-        hipLaunchKernelGGL((pmx_long32_kernel<RR, MM, CC>), dim3((unsigned)blocks), dim3(64), lds, stream, a); } while (0)
-#define LONG_MODES(RR, CC) do { \
-        if (mode == PMX_MODE_SW) LONG_LAUNCH(RR, PMX_MODE_SW, CC); else if (mode == PMX_MODE_SG) LONG_LAUNCH(RR, PMX_MODE_SG, CC); else LONG_LAUNCH(RR, PMX_MODE_NW, CC); } while (0)
-#define LONG_LAUNCH2(RR, MM, CC) do { \
-        const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_long32_kernel_c2<RR, MM, CC>)); if (rc) return rc; \
-        hipLaunchKernelGGL((pmx_long32_kernel_c2<RR, MM, CC>), dim3((unsigned)blocks), dim3(64), lds, stream, a); } while (0)
-#define LONG_MODES2(RR, CC) do { \
-        if (mode == PMX_MODE_SW) LONG_LAUNCH2(RR, PMX_MODE_SW, CC); else if (mode == PMX_MODE_SG) LONG_LAUNCH2(RR, PMX_MODE_SG, CC); else LONG_LAUNCH2(RR, PMX_MODE_NW, CC); } while (0)
-    const bool c16 = chunk_cols == 16;
-    if (two_cols && (R == 2 || R == 4)) {                  // (chunk_cols counts STEPS here: 32 or 64, two columns each)
-        const bool c32 = chunk_cols != 64;
-        if (R == 2) { if (c32) LONG_MODES2(2, 32); else LONG_MODES2(2, 64); }
-        else { if (c32) LONG_MODES2(4, 32); else LONG_MODES2(4, 64); }
-    }
-    else if (R == 2) { if (c16) LONG_MODES(2, 16); else LONG_MODES(2, 64); }
-    else if (R == 4) { if (c16) LONG_MODES(4, 16); else LONG_MODES(4, 64); }
-    else if (R == 16) LONG_MODES(16, 64);
-    else return 1;
+#define LONG_LAUNCH(RR, MM, CC, KK) do { \
+        const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_long32_kernel<RR, MM, CC, KK>)); if (rc) return rc; \
+        hipLaunchKernelGGL((pmx_long32_kernel<RR, MM, CC, KK>), dim3((unsigned)blocks), dim3(64), lds, stream, a); } while (0)
+#define LONG_MODES(RR, CC, KK) do { \
+        if (mode == PMX_MODE_SW) LONG_LAUNCH(RR, PMX_MODE_SW, CC, KK); else if (mode == PMX_MODE_SG) LONG_LAUNCH(RR, PMX_MODE_SG, CC, KK); else LONG_LAUNCH(RR, PMX_MODE_NW, CC, KK); } while (0)
+#define LONG_LAUNCH2(RR, MM, CC, KK) do { \
+        const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_long32_kernel_c2<RR, MM, CC, KK>)); if (rc) return rc; \
+        hipLaunchKernelGGL((pmx_long32_kernel_c2<RR, MM, CC, KK>), dim3((unsigned)blocks), dim3(64), lds, stream, a); } while (0)
+#define LONG_MODES2(RR, CC, KK) do { \
+        if (mode == PMX_MODE_SW) LONG_LAUNCH2(RR, PMX_MODE_SW, CC, KK); else if (mode == PMX_MODE_SG) LONG_LAUNCH2(RR, PMX_MODE_SG, CC, KK); else LONG_LAUNCH2(RR, PMX_MODE_NW, CC, KK); } while (0)
+    const bool c16 = chunk_cols == 16, c32 = chunk_cols != 64;
+#define LONG_FORMS(KK) do { \
+        if (two_cols && (R == 2 || R == 4)) {                  /* (chunk_cols counts STEPS here: 32 or 64, two columns each) */ \
+            if (R == 2) { if (c32) LONG_MODES2(2, 32, KK); else LONG_MODES2(2, 64, KK); } \
+            else { if (c32) LONG_MODES2(4, 32, KK); else LONG_MODES2(4, 64, KK); } \
+        } \
+        else if (R == 2) { if (c16) LONG_MODES(2, 16, KK); else LONG_MODES(2, 64, KK); } \
+        else if (R == 4) { if (c16) LONG_MODES(4, 16, KK); else LONG_MODES(4, 64, KK); } \
+        else if (R == 16) LONG_MODES(16, 64, KK); \
+        else return 1; } while (0)
+    if (ck) LONG_FORMS(true); else LONG_FORMS(false);
+#undef LONG_FORMS
 #undef LONG_MODES2
 #undef LONG_LAUNCH2
 #undef LONG_MODES
