@@ -857,12 +857,7 @@ class Aligner:
                                               st.ctypes.data if st is not None else None, C.byref(cbuf), coff.ctypes.data)
         if rc:
             raise BatchError(lib.pmx_last_error().decode())
-        try:
-            raw = C.string_at(cbuf.value, int(coff[n])) if cbuf.value and coff[n] else b""
-        finally:
-            if cbuf.value:
-                lib.pmx_free(cbuf)
-        cigars = [raw[coff[k]:coff[k + 1]].decode() for k in range(n)]
+        cigars = _take_cigars(cbuf, coff)
         return (out, cigars, st) if stats else (out, cigars)
 
     def align_batch_cigar_long(self, queries, references, stats=False, cigar=True, tile_cols=0, band_rows=0):
@@ -888,12 +883,7 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         if not cigar:
             return out, st
-        try:
-            raw = C.string_at(cbuf.value, int(coff[n])) if cbuf.value and coff[n] else b""
-        finally:
-            if cbuf.value:
-                lib.pmx_free(cbuf)
-        cigars = [raw[coff[k]:coff[k + 1]].decode() for k in range(n)]
+        cigars = _take_cigars(cbuf, coff)
         return (out, cigars, st) if stats else (out, cigars)
 
     def align_batch_cigar(self, queries, references):
@@ -927,6 +917,17 @@ class Aligner:
         raw._pmx_owner = _OwnedBuffer(cbuf)
         text = np.frombuffer(raw, dtype=np.uint8, count=nbytes)
         return out, text, coff
+
+
+def _take_cigars(cbuf, coff):
+    """The per-pair CIGAR strings out of a callee-allocated text block (offsets coff[n + 1]); the block is released."""
+    n = len(coff) - 1
+    try:
+        raw = C.string_at(cbuf.value, int(coff[n])) if cbuf.value and coff[n] else b""
+    finally:
+        if cbuf.value:
+            lib.pmx_free(cbuf)
+    return [raw[coff[k]:coff[k + 1]].decode() for k in range(n)]
 
 
 class _OwnedBuffer:

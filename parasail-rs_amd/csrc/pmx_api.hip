@@ -1472,37 +1472,137 @@ static int trace_ws_init()
     return 0;
 }
 
-// Per-pair packed traceback over a batch in chunks of `chunk` pairs (variant / Tmax planned for one chunk).  two: two trace buffers
-// of cbytes each and two sets of block flags, sweeps of consecutive chunks alternating between the caller's stream and an internal
-// one (the tail of one launch is backfilled by the next), the walk of chunk c on the high-priority walk stream beside the sweep of
-// chunk c + 1; otherwise one buffer and sweep and walk back to back on `st`.  Per pair the walk leaves either the path's statistics
-// (stats) or run-length ops in implicit slots (ops / ops_base) with their count, begins and CIGAR text length.
-struct TraceOutputs { pmx_stats_t *stats; uint32_t *ops; long long ops_base; int32_t *nops, *beg, *textlen; };
-static size_t trace_flag_stride(int64_t chunk) { return (size_t)chunk / 2 + 16; }    // ints of one set of per-block flags
-static int trace_chunks(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch &b, int variant, int Tmax, int64_t chunk, bool two,
-                        uint32_t *tbuf, size_t cbytes, int *bflags, pmx_record_t *d_out, const TraceOutputs &o, hipStream_t st,
-                        const char *what)
+// ---- chunks of a traceback batch: how large, and how their sweeps and walks overlap ----------------------------
+// Bytes of trace one chunk may take: `ceiling`, at most `share` of the free HBM; the value of a switch (tests force small chunks)
+// replaces both.  The callers hold the constants and the measurements behind them.
+static double chunk_budget(double ceiling, double share, const char *forced /* pmx_env() of the caller's switch, or nullptr */)
 {
-    const size_t fstride = trace_flag_stride(chunk);
+    if (forced) return atof(forced);
+    size_t fb = 0, tb = 0;
+    return hipMemGetInfo(&fb, &tb) == hipSuccess && share * (double)fb < ceiling ? share * (double)fb : ceiling;
+}
+// Pairs per chunk: as many equal chunks as `trace_bytes` needs under `budget`, at least `min_chunks` (what the caller's overlap
+// wants for a batch of this size), rounded up to whole groups of 64 pairs.
+static int64_t chunk_pairs(int64_t n, double trace_bytes, double budget, int64_t min_chunks)
+{
+    int64_t nchunks = (int64_t)(trace_bytes / budget) + 1;
+    if (nchunks < min_chunks) nchunks = min_chunks;
+    const int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
+    return chunk > n ? n : chunk;
+}
+
+// Typed arrays carved out of one block, each starting on a 256-byte boundary (the block's base is one: hipMalloc).  The same
+// sequence of take() calls runs twice -- over no block for the size, then over the reserved block -- so size and layout cannot
+// disagree.
+struct Carver {
+    unsigned char *base = nullptr; size_t used = 0;
+    template <typename T> T *take(size_t count)
+    {
+        T *p = base ? (T *)(base + used) : nullptr;
+        used = (used + count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+// layout(Carver &) takes what the caller needs; the block comes from the scratch slot.
+template <typename Layout> static int scratch_carve(int slot, Layout layout)
+{
+    Carver size, c; layout(size);
+    if (scratch_reserve(size.used, (void **)&c.base, slot)) return -1;
+    layout(c);
+    return 0;
+}
+
+// What the walks leave per pair for the CIGAR text -- run-length ops in the pair's slot, their count, the text's length -- and the
+// tail every device CIGAR road ends in on the caller's stream: one scan of the lengths into text offsets, one render of the slots.
+struct SlotText {
+    uint32_t *ops = nullptr; int32_t *nops = nullptr, *textlen = nullptr; void *scan = nullptr; size_t scan_bytes = 0;
+    int reserve_ops(size_t slots) { return scratch_reserve(slots * sizeof(uint32_t), (void **)&ops, SCR_OPS); }
+    void carve(Carver &c, int64_t n, bool text = true /* false: statistics only, no scan */)
+    {
+        nops = c.take<int32_t>((size_t)n); textlen = c.take<int32_t>((size_t)n + 2);
+        scan_bytes = text ? pmx_text_scan_scratch_bytes(n) : 0;
+        scan = c.take<unsigned char>(scan_bytes);
+    }
+    // slot of pair k: slot_qoff[k] + d_roff[k] + k - ops_base
+    int render(const int64_t *slot_qoff, const int64_t *d_roff, long long ops_base, int64_t n,
+               char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st) const
+    {
+        int rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan, scan_bytes, st);
+        if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
+        rc = pmx_launch_cigar_render_slots(ops, slot_qoff, d_roff, ops_base, nops, d_text_off, d_text, capacity, n, st);
+        if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
+        return 0;
+    }
+};
+
+// One chunk of overlap_chunks: pairs [c0, c0 + n), the idx-th chunk; its sweep goes to `sweep` into trace buffer `buf`, its walk to
+// `walk` behind sweep_done, and walk_done (null when everything runs back to back on one stream) frees the buffer for chunk idx + 2.
+struct ChunkTurn { int64_t c0, n; int idx, buf; hipStream_t sweep, walk; hipEvent_t sweep_done, walk_done; };
+// The walk stream waits for the sweep just launched / the walk just launched is what the buffer's next sweep waits for: for bodies
+// that launch sweep and walk themselves (pmx_launch_trace16 does both from the events in PmxWalkSplit).
+static int chunk_sweep_launched(const ChunkTurn &t)
+{
+    if (!t.walk_done) return 0;
+    HIP_OR_RET(hipEventRecord(t.sweep_done, t.sweep));
+    HIP_OR_RET(hipStreamWaitEvent(t.walk, t.sweep_done, 0));
+    return 0;
+}
+static int chunk_walk_launched(const ChunkTurn &t)
+{
+    if (t.walk_done) HIP_OR_RET(hipEventRecord(t.walk_done, t.walk));
+    return 0;
+}
+// [0, n) in chunks of `chunk` pairs, body(turn) once per chunk (non-zero ends the loop and is returned).  two: two trace buffers,
+// sweeps of consecutive chunks alternating between the caller's stream and an internal one (a chunk is a few thousand equally long
+// waves: the tail of one launch is backfilled by the next), the walk of chunk c on the high-priority walk stream beside the sweep of
+// chunk c + 1, and `st` continues behind the last walk; otherwise one buffer and sweep and walk back to back on `st`.
+// (trace_ws_init() first.)
+template <typename Body> static int overlap_chunks(int64_t n, int64_t chunk, bool two, hipStream_t st, Body body)
+{
     if (two) { HIP_OR_RET(hipEventRecord(g_tws.start, st)); HIP_OR_RET(hipStreamWaitEvent(g_tws.aux, g_tws.start, 0)); }
     int idx = 0;
-    for (int64_t c0 = 0; c0 < b.n; c0 += chunk, ++idx) {
-        PmxBatch bk = b;
-        bk.n = (b.n - c0 < chunk) ? b.n - c0 : chunk;
-        bk.qoff = b.qoff + c0; bk.roff = b.roff + c0;
-        bk.blockflag = bflags + (size_t)(idx & 1) * fstride;
-        const hipStream_t sws = (two && (idx & 1)) ? g_tws.aux : st;
-        if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(sws, g_tws.walk_done[idx & 1], 0));     // this trace buffer's last walk is done
-        PmxWalkSplit sp = {two ? g_tws.walk : st, g_tws.sweep_done[idx & 1], two ? g_tws.walk_done[idx & 1] : nullptr,
-                           o.ops_base - c0, o.textlen ? o.textlen + c0 : nullptr};
-        const int rc = pmx_launch_trace16(variant, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out + c0,
-                                          (uint32_t *)((unsigned char *)tbuf + (two ? (size_t)(idx & 1) * cbytes : 0)), Tmax,
-                                          o.ops, nullptr, o.nops ? o.nops + c0 : nullptr, o.beg ? o.beg + 2 * c0 : nullptr, sws,
-                                          o.stats ? o.stats + c0 : nullptr, &sp);
-        if (rc) { set_err("%s (%d)", what, rc); return rc < 0 ? rc : -1; }
+    for (int64_t c0 = 0; c0 < n; c0 += chunk, ++idx) {
+        const int slot = idx & 1;
+        const ChunkTurn t = {c0, (n - c0 < chunk) ? n - c0 : chunk, idx, two ? slot : 0, (two && slot) ? g_tws.aux : st, two ? g_tws.walk : st,
+                             g_tws.sweep_done[slot], two ? g_tws.walk_done[slot] : nullptr};
+        if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(t.sweep, g_tws.walk_done[slot], 0));     // this trace buffer's last walk is done
+        const int rc = body(t);
+        if (rc) return rc;
     }
     if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));      // the walk stream is in order: the last walk covers all
     return 0;
+}
+
+// Per-pair packed traceback over a batch the plan takes, in chunks of `chunk` pairs overlapped as overlap_chunks describes: the
+// sweep's shape (*variant) and trace bytes are planned for one chunk, with two trace buffers and two sets of block flags, or one.
+// Per pair the walk leaves either the path's statistics (stats) or run-length ops in implicit slots (ops / ops_base) with their
+// count, begins and CIGAR text length.
+struct TraceOutputs { pmx_stats_t *stats; uint32_t *ops; long long ops_base; int32_t *nops, *beg, *textlen; };
+static size_t trace_flag_stride(int64_t chunk) { return (size_t)chunk / 2 + 16; }    // ints of one set of per-block flags
+static int trace_chunks(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch &b, int64_t chunk, bool two, int *bflags,
+                        pmx_record_t *d_out, const TraceOutputs &o, hipStream_t st, const char *what, int *variant)
+{
+    PmxBatch bc = b; bc.n = chunk;
+    int Tmax = 0; size_t cbytes = 0;
+    (void)pmx_trace16_plan(bc, dm.d, cfg->mode, cfg->open, cfg->extend, variant, &Tmax, &cbytes);
+    cbytes = (cbytes + 255) & ~(size_t)255;
+    uint32_t *tbuf = nullptr;
+    if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE)) return -1;
+    const size_t fstride = trace_flag_stride(chunk);
+    return overlap_chunks(b.n, chunk, two, st, [&](const ChunkTurn &t) -> int {
+        const int64_t c0 = t.c0;
+        PmxBatch bk = b;
+        bk.n = t.n;
+        bk.qoff = b.qoff + c0; bk.roff = b.roff + c0;
+        bk.blockflag = bflags + (size_t)(t.idx & 1) * fstride;
+        PmxWalkSplit sp = {t.walk, t.sweep_done, t.walk_done, o.ops_base - c0, o.textlen ? o.textlen + c0 : nullptr};
+        const int rc = pmx_launch_trace16(*variant, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out + c0,
+                                          (uint32_t *)((unsigned char *)tbuf + (size_t)t.buf * cbytes), Tmax,
+                                          o.ops, nullptr, o.nops ? o.nops + c0 : nullptr, o.beg ? o.beg + 2 * c0 : nullptr, t.sweep,
+                                          o.stats ? o.stats + c0 : nullptr, &sp);
+        if (rc) { set_err("%s (%d)", what, rc); return rc < 0 ? rc : -1; }
+        return 0;
+    });
 }
 
 // 0 done (asynchronously on st), 1 not eligible, <0 error
@@ -1532,9 +1632,8 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
     if (pmx_nwsgq_trace_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes, &G, &R) != 0) return 1;
     if (trace_ws_init()) return -1;
     const long long NP = 2 * (64 / G) * 4;                     // pairs per workgroup of the sweep
-    double chunk_bytes = 40e9;                                 // (measured on cfg 3: 8 GB chunks 55.0 ms, 24 GB 53.1 ms, 40 GB 51.0 ms)
-    { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess && 0.2 * (double)fb < chunk_bytes) chunk_bytes = 0.2 * (double)fb; }
-    if (const char *e = pmx_env("PMX_STATS_CHUNK_BYTES")) chunk_bytes = atof(e);      // tests force small chunks
+    // (measured on cfg 3: 8 GB chunks 55.0 ms, 24 GB 53.1 ms, 40 GB 51.0 ms)
+    const double chunk_bytes = chunk_budget(40e9, 0.2, pmx_env("PMX_STATS_CHUNK_BYTES"));
     const double per_pair = (double)tbytes / (double)b.n;
     long long chunk = (long long)(chunk_bytes / per_pair) / NP * NP;
     if (chunk < NP) chunk = NP;
@@ -1580,18 +1679,16 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
     if (scratch_reserve(cbytes * (two ? 2 : 1) + rbytes, (void **)&tbuf, SCR_TRACE)) return -1;
     const bool sg = cfg->mode == PMX_MODE_SG;
     const int col_pen = !(sg && (cfg->sg_flags & PMX_SG_QB)), row_pen = !(sg && (cfg->sg_flags & PMX_SG_DB));
-    // Sweeps of consecutive chunks go to two streams in turn (the caller's and an internal one): a chunk is a few thousand equally
-    // long waves, so the tail of chunk c's launch is backfilled by chunk c + 1's workgroups instead of idling the chip.
-    if (two) { HIP_OR_RET(hipEventRecord(g_tws.start, st)); HIP_OR_RET(hipStreamWaitEvent(g_tws.aux, g_tws.start, 0)); }
-    if (rem_n) HIP_OR_RET(hipStreamWaitEvent(g_tws.aux2, g_tws.start, 0));
-    // one chunk: positions [c0, c0 + n_k) of the batch; sweep on `sws` into `tb`, walk on the walk stream behind it (slot = which events)
-    auto run_chunk = [&](long long c0, long long n_k, uint32_t *tb, size_t tb_bytes, hipStream_t sws, int slot, bool short_waves) -> int {
+    // one chunk: positions [t.c0, t.c0 + t.n) of the batch; sweep into the t.buf-th trace buffer (of tb_bytes), the walk behind it
+    auto run_chunk = [&](const ChunkTurn &t, size_t tb_bytes, bool short_waves) -> int {
+        const long long c0 = t.c0;
+        uint32_t *tb = (uint32_t *)((unsigned char *)tbuf + (size_t)t.buf * cbytes);
         PmxBatch bk = b;
-        bk.n = n_k;
+        bk.n = t.n;
         pmx_record_t *out_k = d_out; pmx_stats_t *st_k = d_stats;
         if (b.perm) bk.perm = b.perm + c0;                    // positions c0 .. of the processing order; records stay indexed by pair
         else { bk.roff = b.roff + c0; out_k = d_out + c0; st_k = d_stats + c0; }
-        if (!b.perm && upload_wait(c0 + bk.n, sws, sws == st ? 0 : 1)) return -1;                  // (host entry: this chunk's references are up)
+        if (!b.perm && upload_wait(c0 + bk.n, t.sweep, t.sweep == st ? 0 : 1)) return -1;                  // (host entry: this chunk's references are up)
         // The remainder after the whole rounds is less than one round: it runs on the shape with half the rows per lane (<32,10> for
         // <16,20> / <16,19>) -- twice the waves, each half as long
         int variant_k = variant, Tmax_k = Tmax, G_k = G, R_k = R;
@@ -1602,34 +1699,25 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
             }
         }
         const int gsel_k = G_k == 16 ? 1 : G_k == 32 ? 2 : 3;
-        int rc = pmx_launch_nwsgq_trace(variant_k, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, out_k, tb, Tmax_k, sws);
+        int rc = pmx_launch_nwsgq_trace(variant_k, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, out_k, tb, Tmax_k, t.sweep);
         if (rc) { set_err("shared-profile traceback sweep failed (%d)", rc); return rc < 0 ? rc : -1; }
-        hipStream_t ws = st;
-        if (two) {
-            HIP_OR_RET(hipEventRecord(g_tws.sweep_done[slot], sws));
-            HIP_OR_RET(hipStreamWaitEvent(g_tws.walk, g_tws.sweep_done[slot], 0));
-            ws = g_tws.walk;
-        }
+        if ((rc = chunk_sweep_launched(t)) != 0) return rc;
         rc = pmx_launch_walkp(gsel_k, R_k, bk, dm.d, cfg->mode, cfg->open, cfg->extend, Tmax_k, 0, st_k, row_pen, col_pen,
-                              tb, out_k, nullptr, nullptr, 0, nullptr, nullptr, nullptr, ws);
+                              tb, out_k, nullptr, nullptr, 0, nullptr, nullptr, nullptr, t.walk);
         if (rc) { set_err("statistics walk failed (%d)", rc); return rc < 0 ? rc : -1; }
-        if (two) HIP_OR_RET(hipEventRecord(g_tws.walk_done[slot], ws));
-        return 0;
+        return chunk_walk_launched(t);
     };
-    if (rem_n) {
-        const int rc = run_chunk(b.n - rem_n, rem_n, (uint32_t *)((unsigned char *)tbuf + 2 * cbytes), rbytes, g_tws.aux2, 2, true);
-        if (rc) return rc;
-    }
-    int idx = 0;
-    for (long long c0 = 0; c0 < b.n - rem_n; c0 += chunk, ++idx) {
-        const long long n_k = (b.n - rem_n - c0 < chunk) ? b.n - rem_n - c0 : chunk;
-        uint32_t *tb = (uint32_t *)((unsigned char *)tbuf + (two ? (size_t)(idx & 1) * cbytes : 0));
-        const hipStream_t sws = (two && (idx & 1)) ? g_tws.aux : st;
-        if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(sws, g_tws.walk_done[idx & 1], 0));    // this buffer's previous walk is done
-        const int rc = run_chunk(c0, n_k, tb, cbytes, sws, idx & 1, by_rounds && two && n_k < chunk);
-        if (rc) return rc;
-    }
-    if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));      // (the walk stream is in order: the last walk covers all, the remainder's too)
+    // (the final join covers the remainder too: its walk went to the walk stream first, and that stream is in order)
+    const int rc = overlap_chunks(b.n - rem_n, chunk, two, st, [&](const ChunkTurn &t) -> int {
+        if (rem_n && t.idx == 0) {                             // the remainder: a third stream, trace buffer and pair of events, ahead of the first chunk
+            HIP_OR_RET(hipStreamWaitEvent(g_tws.aux2, g_tws.start, 0));
+            const ChunkTurn rem = {b.n - rem_n, rem_n, 0, 2, g_tws.aux2, g_tws.walk, g_tws.sweep_done[2], g_tws.walk_done[2]};
+            const int rr = run_chunk(rem, rbytes, true);
+            if (rr) return rr;
+        }
+        return run_chunk(t, cbytes, by_rounds && two && t.n < chunk);
+    });
+    if (rc) return rc;
     static thread_local char name[96];
     if (dm.d.pssm) snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d,pssm>/shared PSSM profile/packed trace + pmx_walkp_kernel<pssm>/stats", G, R);
     else snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d>/shared profile/packed trace + pmx_walkp_kernel/stats", G, R);
@@ -1649,8 +1737,7 @@ static int stats_by_trace_pairs(const pmx_config_t *cfg, const DevMat &dm, const
     PmxBatch bt = b; bt.perm = nullptr;
     int variant = 0, Tmax = 0; size_t tbytes = 0;
     if (pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) != 0 || variant < 10) return 1;
-    double budget = 8e9;
-    { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess && 0.15 * (double)fb < budget) budget = 0.15 * (double)fb; }
+    const double budget = chunk_budget(8e9, 0.15, nullptr);
     const double per_pair = (double)tbytes / (double)n + 1.0;
     int64_t nchunks = (int64_t)((double)tbytes / budget) + 1;
     if (nchunks < 2 && n >= 16384) nchunks = 2;            // two chunks at least: the walk of one runs beside the sweep of the next
@@ -1658,22 +1745,46 @@ static int stats_by_trace_pairs(const pmx_config_t *cfg, const DevMat &dm, const
     if ((double)chunk * per_pair > budget) chunk = (int64_t)(budget / per_pair) / 64 * 64;
     if (chunk < 64) chunk = 64;
     if (chunk > n) chunk = n;
-    bt.n = chunk;
-    (void)pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes);
-    bt.n = n;
-    const size_t cbytes = (tbytes + 255) & ~(size_t)255;
     const bool two = chunk < n;
     if (two && trace_ws_init()) return -1;
-    uint32_t *tbuf = nullptr;
-    if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE)) return -1;
     int *bflags = nullptr;
     if (scratch_reserve(2 * trace_flag_stride(chunk) * sizeof(int), (void **)&bflags, SCR_RETRY)) return -1;
     const TraceOutputs o = {d_stats, nullptr, 0, nullptr, nullptr, nullptr};
-    const int rc = trace_chunks(cfg, dm, bt, variant, Tmax, chunk, two, tbuf, cbytes, bflags, d_out, o, st,
-                                "stats-by-traceback launch failed");
+    const int rc = trace_chunks(cfg, dm, bt, chunk, two, bflags, d_out, o, st, "stats-by-traceback launch failed", &variant);
     if (rc) return rc;
     g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel/stats" : "pmx_nwsg16v_kernel/packed trace + pmx_walkp_kernel/stats";
     return 0;
+}
+
+// The long-pair sweep's switches and scratch budget as both of its roads read them (long_batch, long_cigar_device); which form runs
+// without a switch is each road's own decision.
+struct LongKnobs {
+    bool two_columns, one_column;          // PMX_LONG_TWO_COLUMNS / PMX_LONG_ONE_COLUMN: force the form
+    // the bands of a pair wait for one another across workgroups; the wait is bounded (pmx_long.hip): ~2 us a poll
+    int spin_limit = 1 << 20, chunk_cols = 16;
+    size_t budget; bool budget_forced;     // bytes of scratch one chunk may take (PMX_LONG_CHUNK_BYTES: tests force several chunks)
+};
+static LongKnobs long_knobs()
+{
+    LongKnobs k;
+    k.two_columns = pmx_env("PMX_LONG_TWO_COLUMNS") != nullptr; k.one_column = pmx_env("PMX_LONG_ONE_COLUMN") != nullptr;
+    if (const char *e = pmx_env("PMX_LONG_SPIN_LIMIT")) k.spin_limit = atoi(e);             // tests force the give-up path
+    if (const char *e = pmx_env("PMX_LONG_CHUNK_COLS")) k.chunk_cols = atoi(e) == 64 ? 64 : 16;
+    size_t fb = 0, tb = 0;
+    if (hipMemGetInfo(&fb, &tb) != hipSuccess) fb = 0;
+    k.budget = std::min<size_t>((size_t)4 << 30, fb / 4) + ((size_t)64 << 20);
+    const char *e = pmx_env("PMX_LONG_CHUNK_BYTES");
+    if ((k.budget_forced = e != nullptr)) k.budget = (size_t)atof(e);
+    return k;
+}
+// "pmx_long32_kernel<4>/bands across the chip", "pmx_long32_kernel_c2<2,ck>/checkpoint sweep + pmx_walkt_kernel", ...
+static const char *long_kernel_name(int R, int two_cols, bool checkpoints)
+{
+    static thread_local char name[96];
+    snprintf(name, sizeof name, "pmx_long32_kernel%s<%d%s>/%s%s", two_cols ? "_c2" : "", R, checkpoints ? ",ck" : "",
+             checkpoints ? "checkpoint sweep + pmx_walkt_kernel" : "bands across the chip",
+             two_cols && !checkpoints ? ", two columns per step" : "");
+    return name;
 }
 
 // pmx_long32_kernel over a batch, in chunks of bounded scratch: 0 done, 1 not eligible, < 0 error.  Score and end positions, 32-bit
@@ -1712,27 +1823,19 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
         if (t22 < 0.95 * t1 && t22 <= t24) { two_cols = 1; R = 2; }          // (within 5 %: the first form)
         else if (t24 < 0.95 * t1) two_cols = 1;
     }
-    if (pmx_env("PMX_LONG_TWO_COLUMNS")) two_cols = 1;
-    if (pmx_env("PMX_LONG_ONE_COLUMN")) { two_cols = 0; R = 4; }
+    const LongKnobs knobs = long_knobs();
+    if (knobs.two_columns) two_cols = 1;
+    if (knobs.one_column) { two_cols = 0; R = 4; }
     if (const char *e = pmx_env("PMX_LONG_ROWS_PER_LANE")) R = atoi(e) == 2 ? 2 : atoi(e) == 16 ? 16 : 4;
     if (R == 16) two_cols = 0;
     size_t per_pair = pmx_long_scratch_bytes(1, max_qlen, max_rlen, R, &bstride, &nbmax);
     if (per_pair > ((size_t)4 << 30)) { R = 16; two_cols = 0; per_pair = pmx_long_scratch_bytes(1, max_qlen, max_rlen, R, &bstride, &nbmax); }
-    size_t fb = 0, tb = 0;
-    if (hipMemGetInfo(&fb, &tb) != hipSuccess) fb = 0;
-    size_t budget = std::min<size_t>((size_t)4 << 30, fb / 4) + ((size_t)64 << 20);
-    if (const char *e = pmx_env("PMX_LONG_CHUNK_BYTES")) budget = (size_t)atof(e);        // tests force several chunks
-    if (per_pair > budget && !pmx_env("PMX_LONG_CHUNK_BYTES")) return 1;
-    int64_t chunk = (int64_t)(budget / per_pair);
+    if (per_pair > knobs.budget && !knobs.budget_forced) return 1;
+    int64_t chunk = (int64_t)(knobs.budget / per_pair);
     if (chunk < 1) chunk = 1;
     if (chunk > n) chunk = n;
     void *scr = nullptr;
     if (scratch_reserve((size_t)chunk * per_pair, &scr, SCR_LONG)) return 1;
-    // the bands of a pair wait for one another across workgroups; the wait is bounded (pmx_long.hip): ~2 us a poll
-    int spin_limit = 1 << 20;
-    if (const char *e = pmx_env("PMX_LONG_SPIN_LIMIT")) spin_limit = atoi(e);             // tests force the give-up path
-    int chunk_cols = 16;
-    if (const char *e = pmx_env("PMX_LONG_CHUNK_COLS")) chunk_cols = atoi(e) == 64 ? 64 : 16;
     HIP_OR_RET(hipMemsetAsync(scr, 0, 64, st));
     for (int64_t c0 = 0; c0 < n; c0 += chunk) {
         PmxBatch b = b0;
@@ -1740,7 +1843,7 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
         b.n = (n - c0 < chunk) ? n - c0 : chunk;
         if (!b.q_shared) b.qoff = b0.qoff + c0;
         b.roff = b0.roff + c0;
-        const int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, scr, d_out + c0, sat_above, force_sat, st, spin_limit, chunk_cols, two_cols);
+        const int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, scr, d_out + c0, sat_above, force_sat, st, knobs.spin_limit, knobs.chunk_cols, two_cols);
         if (rc < 0) { set_err("long-pair kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
         if (rc) return c0 == 0 ? 1 : (set_err("long-pair kernel refused a later chunk"), -1);
     }
@@ -1758,9 +1861,7 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
                 "the call was redone on the per-pair kernels");
         return 1;
     }
-    g_last_kernel = R == 16 ? "pmx_long32_kernel<16>/bands across the chip"
-                  : two_cols ? (R == 2 ? "pmx_long32_kernel_c2<2>/bands across the chip, two columns per step" : "pmx_long32_kernel_c2<4>/bands across the chip, two columns per step")
-                  : (R == 2 ? "pmx_long32_kernel<2>/bands across the chip" : "pmx_long32_kernel<4>/bands across the chip");
+    g_last_kernel = long_kernel_name(R, two_cols, false);
     return 0;
 }
 
@@ -1943,6 +2044,34 @@ static void host_maxlens(int64_t n, const int64_t *off, int32_t *mx, bool *bad, 
     *mx = (int32_t)(m > INT32_MAX ? INT32_MAX : m);
     if (mn) *mn = (int32_t)(lo < 0 ? 0 : lo);
 }
+// A host batch staged on the device by plain synchronous copies: validated offsets and their maxima, references, queries (none with a
+// profile: one shared query), optional per-pair diagonals, and room for the records.  For the entries whose device work dwarfs the
+// transfer (banded, traced); host_batch, pmx_align_profile_batch and cigar_host_pipelined slice and pipeline theirs.
+struct StagedBatch {
+    DevBuf<uint8_t> dq, dr; DevBuf<int64_t> dqo, dro; DevBuf<int32_t> dd; DevBuf<pmx_record_t> drec;
+    int64_t n = 0; int32_t mq = 0, mr = 0;
+    int upload(const parasail_profile_t *profile, int64_t n_, const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff,
+               const int32_t *diag)
+    {
+        n = n_;
+        bool bad = false;
+        host_maxlens(n, roff, &mr, &bad);
+        if (!profile) host_maxlens(n, qoff, &mq, &bad); else mq = profile->s1Len;
+        if (bad || roff[0] != 0 || (!profile && qoff[0] != 0)) { set_err("bad offsets (every sequence needs length >= 1, offsets start at 0)"); return -1; }
+        if (dr.try_alloc((size_t)roff[n]) || dro.try_alloc(n + 1) || drec.try_alloc(n) || (diag && dd.try_alloc(n)) ||
+            (!profile && (dq.try_alloc((size_t)qoff[n]) || dqo.try_alloc(n + 1)))) { set_err("out of device memory"); return -2; }
+        HIP_OR_RET(hipMemcpy(dr.p, rbuf, (size_t)roff[n], hipMemcpyHostToDevice));
+        HIP_OR_RET(hipMemcpy(dro.p, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+        if (diag) HIP_OR_RET(hipMemcpy(dd.p, diag, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+        if (!profile) {
+            HIP_OR_RET(hipMemcpy(dq.p, qbuf, (size_t)qoff[n], hipMemcpyHostToDevice));
+            HIP_OR_RET(hipMemcpy(dqo.p, qoff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+        }
+        return 0;
+    }
+    int records(pmx_record_t *out) const { HIP_OR_RET(hipMemcpy(out, drec.p, sizeof(pmx_record_t) * n, hipMemcpyDeviceToHost)); return 0; }
+};
+
 // The same over both offset arrays of a large batch, split over a few host threads: the scan of 2 x 1M offsets is 1.2 ms on one
 // core, as long as a third of the device work it precedes.
 struct LenScan { int32_t mq = 0, mr = 0, mnr = INT32_MAX; bool bad = false; };
@@ -2293,26 +2422,12 @@ extern "C" int pmx_align_batch_banded(const pmx_config_t *cfg, const parasail_pr
     if (n <= 0) return 0;
     if (!rbuf || !roff || !out || (!profile && (!qbuf || !qoff))) { set_err("null buffer"); return -1; }
     if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by banded batches"); return -1; }
-    int32_t mq = 0, mr = 0; bool bad = false;
-    host_maxlens(n, roff, &mr, &bad);
-    if (!profile) host_maxlens(n, qoff, &mq, &bad); else mq = profile->s1Len;
-    if (bad || roff[0] != 0 || (!profile && qoff[0] != 0)) { set_err("bad offsets (every sequence needs length >= 1, offsets start at 0)"); return -1; }
-    DevBuf<uint8_t> dq, dr; DevBuf<int64_t> dqo, dro; DevBuf<int32_t> dd; DevBuf<pmx_record_t> drec;
-    if (dr.try_alloc((size_t)roff[n]) || dro.try_alloc(n + 1) || drec.try_alloc(n) || (diag && dd.try_alloc(n)) ||
-        (!profile && (dq.try_alloc((size_t)qoff[n]) || dqo.try_alloc(n + 1)))) { set_err("out of device memory"); return -2; }
-    HIP_OR_RET(hipMemcpy(dr.p, rbuf, (size_t)roff[n], hipMemcpyHostToDevice));
-    HIP_OR_RET(hipMemcpy(dro.p, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-    if (diag) HIP_OR_RET(hipMemcpy(dd.p, diag, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    int rc;
-    if (profile) rc = pmx_align_profile_batch_banded_device(cfg, profile, n, dr.p, dro.p, mr, band, diag ? dd.p : nullptr, drec.p, nullptr);
-    else {
-        HIP_OR_RET(hipMemcpy(dq.p, qbuf, (size_t)qoff[n], hipMemcpyHostToDevice));
-        HIP_OR_RET(hipMemcpy(dqo.p, qoff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-        rc = pmx_align_batch_banded_device(cfg, n, dq.p, dqo.p, dr.p, dro.p, mq, mr, band, diag ? dd.p : nullptr, drec.p, nullptr);
-    }
+    StagedBatch s;
+    int rc = s.upload(profile, n, qbuf, qoff, rbuf, roff, diag);
     if (rc) return rc;
-    HIP_OR_RET(hipMemcpy(out, drec.p, sizeof(pmx_record_t) * n, hipMemcpyDeviceToHost));
-    return 0;
+    rc = profile ? pmx_align_profile_batch_banded_device(cfg, profile, n, s.dr.p, s.dro.p, s.mr, band, s.dd.p, s.drec.p, nullptr)
+                 : pmx_align_batch_banded_device(cfg, n, s.dq.p, s.dqo.p, s.dr.p, s.dro.p, s.mq, s.mr, band, s.dd.p, s.drec.p, nullptr);
+    return rc ? rc : s.records(out);
 }
 
 // ---- score tables for a batch (extension; the reference returns one table per call, src/alignment/mod.rs:123-192) ----------
@@ -2373,34 +2488,20 @@ static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n
     if (trace_ws_init()) return -1;
     // chunks: at most ~12 GB of trace each (two buffers; measured on 1.25 M pairs of 250 x 250: 3 GB chunks 27.8 ms, 12 GB 26.2 ms --
     // fewer launch tails), at most 15 % of the free HBM each, at least two for the overlap once the batch is worth it
-    double chunk_bytes = 12e9;
-    { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess && 0.15 * (double)fb < chunk_bytes) chunk_bytes = 0.15 * (double)fb; }
-    if (const char *e = pmx_env("PMX_CIGAR_CHUNK_BYTES")) chunk_bytes = atof(e);      // tests force small chunks
-    int64_t nchunks = (int64_t)((double)tbytes / chunk_bytes) + 1;
-    if (nchunks < 2 && n >= 16384) nchunks = 2;
-    int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
-    if (chunk > n) chunk = n;
-    PmxBatch bc = b; bc.n = chunk;
-    size_t cbytes = 0;
-    (void)pmx_trace16_plan(bc, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &cbytes);
-    cbytes = (cbytes + 255) & ~(size_t)255;
+    const int64_t chunk = chunk_pairs(n, (double)tbytes, chunk_budget(12e9, 0.15, pmx_env("PMX_CIGAR_CHUNK_BYTES")), n >= 16384 ? 2 : 1);
     const bool two = chunk < n && !pmx_env("PMX_CIGAR_NO_OVERLAP");     // (diagnostics: sweep and walk back to back on one stream)
-    uint32_t *tbuf = nullptr, *dops = nullptr; unsigned char *misc = nullptr;
-    const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
-    const size_t misc_bytes = (size_t)(4 * n + 2) * sizeof(int32_t) + 256 + scan_bytes + 256 + 2 * trace_flag_stride(chunk) * sizeof(int);
-    if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE) ||
-        scratch_reserve((size_t)n * ((size_t)mq + mr + 1) * sizeof(uint32_t), (void **)&dops, SCR_OPS) ||
-        scratch_reserve(misc_bytes, (void **)&misc, SCR_CIG)) return -1;
-    int32_t *nops = (int32_t *)misc, *beg = nops + n, *textlen = beg + 2 * n;
-    void *scan_tmp = (void *)(((uintptr_t)(textlen + n + 2) + 255) & ~(uintptr_t)255);
-    int *bflags = (int *)(((uintptr_t)scan_tmp + scan_bytes + 255) & ~(uintptr_t)255);
-    const TraceOutputs o = {nullptr, dops, ops_base, nops, beg, textlen};
-    int rc = trace_chunks(cfg, dm, b, variant, Tmax, chunk, two, tbuf, cbytes, bflags, d_out, o, st, "traceback launch failed");
+    SlotText t; int32_t *beg = nullptr; int *bflags = nullptr;
+    if (t.reserve_ops((size_t)n * ((size_t)mq + mr + 1)) ||
+        scratch_carve(SCR_CIG, [&](Carver &c) {
+            t.carve(c, n);
+            beg = c.take<int32_t>(2 * (size_t)n);
+            bflags = c.take<int>(2 * trace_flag_stride(chunk));
+        })) return -1;
+    const TraceOutputs o = {nullptr, t.ops, ops_base, t.nops, beg, t.textlen};
+    int rc = trace_chunks(cfg, dm, b, chunk, two, bflags, d_out, o, st, "traceback launch failed", &variant);
     if (rc) return rc;
-    rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan_tmp, scan_bytes, st);
-    if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
-    rc = pmx_launch_cigar_render_slots(dops, d_qoff, d_roff, ops_base, nops, d_text_off, d_text, capacity, n, st);
-    if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
+    rc = t.render(d_qoff, d_roff, ops_base, n, d_text, capacity, d_text_off, st);
+    if (rc) return rc;
     g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : "pmx_nwsg16v_kernel/packed trace + pmx_walkp_kernel";
     return 0;
 }
@@ -2479,6 +2580,15 @@ struct TextBuf {
         return p + len;
     }
 };
+
+// Terminates the finished text, hands the block to the caller (who releases it with pmx_free) and tells the pool.
+static int publish_text(TextBuf &text, char **cigar_buf)
+{
+    if (!text.grow(0)) { set_err("out of memory"); return -1; }
+    text.p[text.len] = 0;
+    *cigar_buf = text.p; g_text_pool.handed_out(text.p, text.cap);
+    return 0;
+}
 
 // CIGAR for a batch.  Fast path: pmx_trace16 (4-bit trace in HBM, on-device walk); otherwise the general
 // kernel with byte trace tables and pmx_walk_kernel.  Only the run-length ops come back to the host, which
@@ -2687,23 +2797,13 @@ extern "C" int pmx_align_batch_cigar(const pmx_config_t *cfg, int64_t n,
     {
         const int rc = cigar_host_pipelined(cfg, dm, n, qbuf, qoff, rbuf, roff, out, text, cigar_off);
         if (rc < 0) { free(text.p); return rc; }
-        if (rc == 0) {
-            if (!text.grow(0)) { set_err("out of memory"); return -1; }
-            text.p[text.len] = 0;
-            *cigar_buf = text.p; g_text_pool.handed_out(text.p, text.cap);
-            return 0;
-        }
+        if (rc == 0) return publish_text(text, cigar_buf);
     }
     // Chunks bound the per-launch trace scratch: budgeted at one byte per cell of the padded tables (the
     // general kernel's layout; the fast kernels write 4 bits per cell).  Large chunks matter: the walk is one
     // lane per pair and hides its dependent-load latency only with many waves in flight.  Up to 96 GB,
     // at most 45 % of the free HBM.
-    double chunk_bytes = 96e9;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && 0.45 * (double)free_b < chunk_bytes) chunk_bytes = 0.45 * (double)free_b;
-    }
-    if (const char *e = pmx_env("PMX_CIGAR_CHUNK_BYTES")) chunk_bytes = atof(e);      // tests force small chunks
+    const double chunk_bytes = chunk_budget(96e9, 0.45, pmx_env("PMX_CIGAR_CHUNK_BYTES"));
     // equal shares: as many chunks as the budget needs, each with about the same number of table bytes
     double total_bytes = 0;
     for (int64_t k = 0; k < n; ++k) total_bytes += 1.0 * (double)(qoff[k + 1] - qoff[k] + 64) * (double)(roff[k + 1] - roff[k] + 64);
@@ -2724,12 +2824,67 @@ extern "C" int pmx_align_batch_cigar(const pmx_config_t *cfg, int64_t n,
         if (rc) { free(text.p); return rc; }
         c0 = c1;
     }
-    if (!text.grow(0)) { set_err("out of memory"); return -1; }
-    text.p[text.len] = 0;
-    *cigar_buf = text.p; g_text_pool.handed_out(text.p, text.cap);
+    return publish_text(text, cigar_buf);
+}
+
+// ---- what the traced entries (banded, long pairs) share around their device routines -------------------------------------------
+// cfg->want of a traced entry: CIGAR and / or statistics, nothing unknown.  `who` opens the message.
+static int traced_want_check(const pmx_config_t *cfg, const char *who)
+{
+    if (!(cfg->want & (PMX_WANT_CIGAR | PMX_WANT_STATS))) { set_err("%s needs PMX_WANT_CIGAR and / or PMX_WANT_STATS in cfg->want", who); return -1; }
+    if (cfg->want & ~(PMX_WANT_CIGAR | PMX_WANT_STATS | PMX_WANT_SORTED)) { set_err("unknown want bits 0x%x", cfg->want); return -1; }
+    return 0;
+}
+// An output for everything cfg->want asks for.  A call that lacks both is told about the statistics buffer by the device entries
+// and about the text by the host entries (text_first).
+static int traced_outputs_check(const pmx_config_t *cfg, const void *stats, const void *text, const void *text_off, bool text_first)
+{
+    const bool no_stats = (cfg->want & PMX_WANT_STATS) && !stats, no_text = (cfg->want & PMX_WANT_CIGAR) && (!text || !text_off);
+    if (no_text && (text_first || !no_stats)) { set_err("null cigar output"); return -1; }
+    if (no_stats) { set_err("stats requested without a stats buffer"); return -1; }
     return 0;
 }
 
+// Host entry of a traced batch: host buffers in, host records / statistics / CIGAR text out (the text as pmx_align_batch_cigar's: a
+// block freed with pmx_free).  run(staged batch, d_stats, d_text, capacity, d_text_off) is the device entry; it returns once the
+// device is done with the batch.
+template <typename Run>
+static int traced_host_batch(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                             const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, const int32_t *diag,
+                             pmx_record_t *out, pmx_stats_t *stats_out, char **cigar_buf, int64_t *cigar_off, Run run)
+{
+    const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
+    StagedBatch s;
+    int rc = s.upload(profile, n, qbuf, qoff, rbuf, roff, diag);
+    if (rc) return rc;
+    const int64_t qbytes = profile ? (int64_t)n * profile->s1Len : qoff[n];
+    // text capacity: half a byte per symbol + 16 per pair covers related pairs many times over; a batch that needs more runs again
+    int64_t capacity = want_cigar ? ((qbytes + roff[n]) / 2 + 16 * n + 256) : 0;
+    DevBuf<int64_t> dtoff; DevBuf<pmx_stats_t> dst; DevBuf<char> dtext;
+    if ((want_stats && dst.try_alloc(n)) || (want_cigar && (dtoff.try_alloc(n + 1) || dtext.try_alloc((size_t)capacity + 1)))) { set_err("out of device memory"); return -2; }
+    for (int pass = 0; pass < 2; ++pass) {
+        rc = run(s, dst.p, dtext.p, capacity, dtoff.p);
+        if (rc) return rc;
+        if (!want_cigar) break;
+        HIP_OR_RET(hipMemcpy(cigar_off, dtoff.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
+        if (cigar_off[n] <= capacity) break;
+        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
+        (void)hipFree(dtext.p); dtext.p = nullptr;
+        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    }
+    if ((rc = s.records(out)) != 0) return rc;
+    if (want_stats) HIP_OR_RET(hipMemcpy(stats_out, dst.p, sizeof(pmx_stats_t) * n, hipMemcpyDeviceToHost));
+    if (!want_cigar) return 0;
+    TextBuf text;
+    char *dst_text = text.grow((size_t)cigar_off[n]);
+    if (!dst_text) { set_err("out of memory"); return -1; }
+    if (cigar_off[n]) {
+        const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
+    }
+    text.len = (size_t)cigar_off[n];
+    return publish_text(text, cigar_buf);
+}
 
 // ---- banded batches with traceback (extension) ---------------------------------------------------------------------------
 // The trace form of the 32-bit banded kernels (pmx_banded.hip) writes the band's decision bits to HBM scratch in the anti-diagonal
@@ -2741,9 +2896,7 @@ static int banded_trace_check(const pmx_config_t *cfg, int32_t band)
     if (band < 0 || band > 63) { set_err("banded traceback supports bands 0 .. 63 (got %d)", band); return -1; }
     if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by banded batches"); return -1; }
     if (cfg->matrix->size > PMX_MAX_FAST_MSIZE) { set_err("banded traceback supports alphabets of up to %d letters (matrix size %d)", PMX_MAX_FAST_MSIZE, cfg->matrix->size); return -1; }
-    if (!(cfg->want & (PMX_WANT_CIGAR | PMX_WANT_STATS))) { set_err("banded traceback needs PMX_WANT_CIGAR and / or PMX_WANT_STATS in cfg->want"); return -1; }
-    if (cfg->want & ~(PMX_WANT_CIGAR | PMX_WANT_STATS | PMX_WANT_SORTED)) { set_err("unknown want bits 0x%x", cfg->want); return -1; }
-    return 0;
+    return traced_want_check(cfg, "banded traceback");
 }
 
 // Validated by the caller.  d_qoff is NULL with one shared query of q_shared bytes; offsets start at 0.  Asynchronous on `st`.
@@ -2758,67 +2911,42 @@ static int banded_trace_device(const pmx_config_t *cfg, int64_t n, const uint8_t
     if (trace_ws_init()) return -1;
     const PmxBandTrGeometry g = pmx_bandtr_geometry_of(max_qlen, max_rlen, band);
     // chunks as in cigar_device_run: at most ~12 GB of trace each (two buffers), at most 15 % of the free HBM, two once it pays
-    double chunk_bytes = 12e9;
-    { size_t fb = 0, tb = 0; if (hipMemGetInfo(&fb, &tb) == hipSuccess && 0.15 * (double)fb < chunk_bytes) chunk_bytes = 0.15 * (double)fb; }
-    if (const char *e = pmx_env("PMX_CIGAR_CHUNK_BYTES")) chunk_bytes = atof(e);      // tests force small chunks
+    const double chunk_bytes = chunk_budget(12e9, 0.15, pmx_env("PMX_CIGAR_CHUNK_BYTES"));
     // The walk (one lane per pair) costs about what the sweep does and only the last chunk's walk is exposed: eight chunks once the
     // batch is worth it (measured on 1.25 M pairs of 250 x 250, band 15: two chunks 24.3 ms, nine 20.5 ms)
-    int64_t nchunks = (int64_t)((double)n * (double)g.stride / chunk_bytes) + 1;
-    if (nchunks < 8 && n >= 8 * 16384) nchunks = 8;
-    else if (nchunks < 2 && n >= 16384) nchunks = 2;
-    int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
-    if (chunk > n) chunk = n;
+    const int64_t chunk = chunk_pairs(n, (double)n * (double)g.stride, chunk_bytes, n >= 8 * 16384 ? 8 : n >= 16384 ? 2 : 1);
     const bool two = chunk < n;
     const size_t cbytes = ((size_t)chunk * (size_t)g.stride + 255) & ~(size_t)255;
-    uint8_t *tbuf = nullptr; uint32_t *dops = nullptr; unsigned char *misc = nullptr;
-    const size_t scan_bytes = want_cigar ? pmx_text_scan_scratch_bytes(n) : 0;
-    const size_t misc_bytes = (size_t)(2 * n + 2) * sizeof(int32_t) + 256 + (size_t)(n + 1) * sizeof(int64_t) + 256 + scan_bytes;
+    uint8_t *tbuf = nullptr; SlotText t; int64_t *slot_qoff = nullptr;
     if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE) ||
-        (want_cigar && scratch_reserve((size_t)n * ((size_t)max_qlen + max_rlen + 1) * sizeof(uint32_t), (void **)&dops, SCR_OPS)) ||
-        scratch_reserve(misc_bytes, (void **)&misc, SCR_CIG)) return -1;
-    int32_t *nops = (int32_t *)misc, *textlen = nops + n;
-    int64_t *slot_qoff = (int64_t *)(((uintptr_t)(textlen + n + 2) + 255) & ~(uintptr_t)255);
-    void *scan_tmp = (void *)(((uintptr_t)(slot_qoff + n + 1) + 255) & ~(uintptr_t)255);
+        (want_cigar && t.reserve_ops((size_t)n * ((size_t)max_qlen + max_rlen + 1))) ||
+        scratch_carve(SCR_CIG, [&](Carver &c) { t.carve(c, n, want_cigar); slot_qoff = c.take<int64_t>((size_t)n + 1); })) return -1;
     if (want_cigar && q_shared) {                 // the slot render finds a slot from query offsets: k * qlen for the shared query
         const int rc = pmx_launch_shared_offsets(slot_qoff, n, q_shared, st);
         if (rc) { set_err("offset kernel launch failed (%d)", rc); return rc; }
     }
     const int64_t *sq = q_shared ? slot_qoff : d_qoff;
     const char *kname = "pmx_banded_kernel/trace";
-    if (two) { HIP_OR_RET(hipEventRecord(g_tws.start, st)); HIP_OR_RET(hipStreamWaitEvent(g_tws.aux, g_tws.start, 0)); }
-    int idx = 0;
-    for (int64_t c0 = 0; c0 < n; c0 += chunk, ++idx) {
-        const int64_t m = (n - c0 < chunk) ? n - c0 : chunk;
-        const hipStream_t sws = (two && (idx & 1)) ? g_tws.aux : st;
-        if (two && idx >= 2) HIP_OR_RET(hipStreamWaitEvent(sws, g_tws.walk_done[idx & 1], 0));     // this trace buffer's last walk is done
-        const PmxBandTrace tr = {tbuf + (two ? (size_t)(idx & 1) * cbytes : 0), g.stride};
+    int rc = overlap_chunks(n, chunk, two, st, [&](const ChunkTurn &k) -> int {
+        const int64_t c0 = k.c0, m = k.n;
+        const PmxBandTrace tr = {tbuf + (size_t)k.buf * cbytes, g.stride};
         const int64_t *qo = d_qoff ? d_qoff + c0 : nullptr;
         const int32_t *dg = d_diag ? d_diag + c0 : nullptr;
         int rc = pmx_launch_banded_trace(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0,
-                                         max_qlen, max_rlen, band, dg, d_out + c0, tr, sws, &kname);
+                                         max_qlen, max_rlen, band, dg, d_out + c0, tr, k.sweep, &kname);
         if (rc) { set_err("banded trace launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
-        hipStream_t ws = sws;
-        if (two) {
-            HIP_OR_RET(hipEventRecord(g_tws.sweep_done[idx & 1], sws));
-            HIP_OR_RET(hipStreamWaitEvent(g_tws.walk, g_tws.sweep_done[idx & 1], 0));
-            ws = g_tws.walk;
-        }
+        if ((rc = chunk_sweep_launched(k)) != 0) return rc;
         if (want_stats)
             rc = pmx_launch_walkb(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0, band, dg,
-                                  d_out + c0, tr, nullptr, 0, nullptr, nullptr, nullptr, d_stats + c0, ws);
+                                  d_out + c0, tr, nullptr, 0, nullptr, nullptr, nullptr, d_stats + c0, k.walk);
         if (!rc && want_cigar)
             rc = pmx_launch_walkb(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0, band, dg,
-                                  d_out + c0, tr, sq + c0, -c0, dops, nops + c0, textlen + c0, nullptr, ws);
+                                  d_out + c0, tr, sq + c0, -c0, t.ops, t.nops + c0, t.textlen + c0, nullptr, k.walk);
         if (rc) { set_err("banded walk launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
-        if (two) HIP_OR_RET(hipEventRecord(g_tws.walk_done[idx & 1], ws));
-    }
-    if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_tws.walk_done[(idx - 1) & 1], 0));      // the walk stream is in order: the last walk covers all
-    if (want_cigar) {
-        int rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan_tmp, scan_bytes, st);
-        if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
-        rc = pmx_launch_cigar_render_slots(dops, sq, d_roff, 0, nops, d_text_off, d_text, capacity, n, st);
-        if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
-    }
+        return chunk_walk_launched(k);
+    });
+    if (!rc && want_cigar) rc = t.render(sq, d_roff, 0, n, d_text, capacity, d_text_off, st);
+    if (rc) return rc;
     g_last_kernel = strcmp(kname, "pmx_banded_staged_kernel/trace") == 0 ? "pmx_banded_staged_kernel/trace + pmx_walkb_kernel"
                                                                           : "pmx_banded_kernel/trace + pmx_walkb_kernel";
     return 0;
@@ -2834,8 +2962,7 @@ extern "C" int pmx_align_batch_banded_cigar_device(const pmx_config_t *cfg, cons
     if (n <= 0) return 0;
     if (profile && profile->matrix != cfg->matrix) { set_err("profile was built with a different matrix"); return -1; }
     if (!d_rbuf || !d_roff || !d_out || (!profile && (!d_qbuf || !d_qoff))) { set_err("null buffer"); return -1; }
-    if ((cfg->want & PMX_WANT_STATS) && !d_stats_out) { set_err("stats requested without a stats buffer"); return -1; }
-    if ((cfg->want & PMX_WANT_CIGAR) && (!d_cigar_text || !d_cigar_off)) { set_err("null cigar output"); return -1; }
+    if (traced_outputs_check(cfg, d_stats_out, d_cigar_text, d_cigar_off, false)) return -1;
     if ((!profile && max_qlen <= 0) || max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
     const uint8_t *dq = d_qbuf;
     if (profile && profile_device_query(profile, &dq)) return -1;
@@ -2852,60 +2979,19 @@ extern "C" int pmx_align_batch_banded_cigar(const pmx_config_t *cfg, const paras
                                             int32_t band, const int32_t *diag,
                                             pmx_record_t *out, pmx_stats_t *stats_out, char **cigar_buf, int64_t *cigar_off)
 {
-    if (banded_trace_check(cfg, band)) return -1;
-    const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (want_cigar && (!cigar_buf || !cigar_off)) { set_err("null cigar output"); return -1; }
-    if (want_stats && !stats_out) { set_err("stats requested without a stats buffer"); return -1; }
-    if (want_cigar) *cigar_buf = nullptr;
+    if (banded_trace_check(cfg, band) || traced_outputs_check(cfg, stats_out, cigar_buf, cigar_off, true)) return -1;
+    if (cfg->want & PMX_WANT_CIGAR) *cigar_buf = nullptr;
     if (n <= 0) return 0;
     if (!rbuf || !roff || !out || (!profile && (!qbuf || !qoff))) { set_err("null buffer"); return -1; }
     if (profile && profile->matrix != cfg->matrix) { set_err("profile was built with a different matrix"); return -1; }
-    int32_t mq = 0, mr = 0; bool bad = false;
-    host_maxlens(n, roff, &mr, &bad);
-    if (!profile) host_maxlens(n, qoff, &mq, &bad); else mq = profile->s1Len;
-    if (bad || roff[0] != 0 || (!profile && qoff[0] != 0)) { set_err("bad offsets (every sequence needs length >= 1, offsets start at 0)"); return -1; }
-    const int64_t qbytes = profile ? (int64_t)n * profile->s1Len : qoff[n];
-    // text capacity: half a byte per symbol + 16 per pair covers related pairs many times over; a batch that needs more runs again
-    int64_t capacity = want_cigar ? ((qbytes + roff[n]) / 2 + 16 * n + 256) : 0;
-    DevBuf<uint8_t> dq, dr; DevBuf<int64_t> dqo, dro, dtoff; DevBuf<int32_t> dd; DevBuf<pmx_record_t> drec; DevBuf<pmx_stats_t> dst;
-    DevBuf<char> dtext;
-    if (dr.try_alloc((size_t)roff[n]) || dro.try_alloc(n + 1) || drec.try_alloc(n) || (diag && dd.try_alloc(n)) ||
-        (want_stats && dst.try_alloc(n)) || (want_cigar && (dtoff.try_alloc(n + 1) || dtext.try_alloc((size_t)capacity + 1))) ||
-        (!profile && (dq.try_alloc((size_t)qoff[n]) || dqo.try_alloc(n + 1)))) { set_err("out of device memory"); return -2; }
-    HIP_OR_RET(hipMemcpy(dr.p, rbuf, (size_t)roff[n], hipMemcpyHostToDevice));
-    HIP_OR_RET(hipMemcpy(dro.p, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-    if (diag) HIP_OR_RET(hipMemcpy(dd.p, diag, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    if (!profile) {
-        HIP_OR_RET(hipMemcpy(dq.p, qbuf, (size_t)qoff[n], hipMemcpyHostToDevice));
-        HIP_OR_RET(hipMemcpy(dqo.p, qoff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-    }
-    for (int pass = 0; pass < 2; ++pass) {
-        const int rc = pmx_align_batch_banded_cigar_device(cfg, profile, n, dq.p, dqo.p, dr.p, dro.p, mq, mr, band, diag ? dd.p : nullptr,
-                                                           drec.p, dst.p, dtext.p, capacity, dtoff.p, nullptr);
-        if (rc) return rc;
-        HIP_OR_RET(hipDeviceSynchronize());
-        if (!want_cigar) break;
-        HIP_OR_RET(hipMemcpy(cigar_off, dtoff.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
-        if (cigar_off[n] <= capacity) break;
-        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
-        (void)hipFree(dtext.p); dtext.p = nullptr;
-        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    }
-    HIP_OR_RET(hipMemcpy(out, drec.p, sizeof(pmx_record_t) * n, hipMemcpyDeviceToHost));
-    if (want_stats) HIP_OR_RET(hipMemcpy(stats_out, dst.p, sizeof(pmx_stats_t) * n, hipMemcpyDeviceToHost));
-    if (want_cigar) {
-        TextBuf text;
-        char *dst_text = text.grow((size_t)cigar_off[n]);
-        if (!dst_text) { set_err("out of memory"); return -1; }
-        if (cigar_off[n]) {
-            const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
-        }
-        text.len = (size_t)cigar_off[n];
-        text.p[text.len] = 0;
-        *cigar_buf = text.p; g_text_pool.handed_out(text.p, text.cap);
-    }
-    return 0;
+    return traced_host_batch(cfg, profile, n, qbuf, qoff, rbuf, roff, diag, out, stats_out, cigar_buf, cigar_off,
+        [&](const StagedBatch &s, pmx_stats_t *d_stats, char *d_text, int64_t capacity, int64_t *d_text_off) -> int {
+            const int rc = pmx_align_batch_banded_cigar_device(cfg, profile, n, s.dq.p, s.dqo.p, s.dr.p, s.dro.p, s.mq, s.mr, band, s.dd.p,
+                                                               s.drec.p, d_stats, d_text, capacity, d_text_off, nullptr);
+            if (rc) return rc;
+            HIP_OR_RET(hipDeviceSynchronize());
+            return 0;
+        });
 }
 
 // ==================================================================== long pairs: traceback in linear memory ===
@@ -2953,8 +3039,7 @@ static int long_cigar_check(const pmx_config_t *cfg, const pmx_long_cigar_opts_t
 {
     if (check_cfg(cfg)) return -1;
     if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by the tiled long-pair traceback"); return -1; }
-    if (!(cfg->want & (PMX_WANT_CIGAR | PMX_WANT_STATS))) { set_err("pmx_align_batch_cigar_long needs PMX_WANT_CIGAR and / or PMX_WANT_STATS in cfg->want"); return -1; }
-    if (cfg->want & ~(PMX_WANT_CIGAR | PMX_WANT_STATS | PMX_WANT_SORTED)) { set_err("unknown want bits 0x%x", cfg->want); return -1; }
+    if (traced_want_check(cfg, "pmx_align_batch_cigar_long")) return -1;
     if (cfg->matrix->size > 64) { set_err("the long-pair kernels take alphabets of up to 64 letters (matrix size %d)", cfg->matrix->size); return -1; }
     LongCigPlan pl;
     return longcig_plan(1, 1, 1, opts, longcig_budget_default(), &pl);          // (the options alone)
@@ -2970,30 +3055,19 @@ static int long_cigar_device(const pmx_config_t *cfg, int64_t n, const uint8_t *
     const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
-    size_t fb = 0, tb = 0;
-    if (hipMemGetInfo(&fb, &tb) != hipSuccess) fb = 0;
-    size_t budget = std::min<size_t>((size_t)4 << 30, fb / 4) + ((size_t)64 << 20);
-    if (const char *e = pmx_env("PMX_LONG_CHUNK_BYTES")) budget = (size_t)atof(e);        // tests force several chunks
+    const LongKnobs knobs = long_knobs();
     LongCigPlan pl;
-    if (longcig_plan(n, max_qlen, max_rlen, opts, budget, &pl)) return -1;
+    if (longcig_plan(n, max_qlen, max_rlen, opts, knobs.budget, &pl)) return -1;
     const int R = pl.R;
     // two columns per step for a few pairs (latency), one for a batch that fills the chip (long_batch, measured); the switches of the
     // long-pair sweep act on the shared code as they do there
     int two_cols = (pl.chunk <= 16 && R != 16) ? 1 : 0;
-    if (pmx_env("PMX_LONG_TWO_COLUMNS")) two_cols = R != 16;
-    if (pmx_env("PMX_LONG_ONE_COLUMN")) two_cols = 0;
-    int spin_limit = 1 << 20;
-    if (const char *e = pmx_env("PMX_LONG_SPIN_LIMIT")) spin_limit = atoi(e);
-    int chunk_cols = 16;
-    if (const char *e = pmx_env("PMX_LONG_CHUNK_COLS")) chunk_cols = atoi(e) == 64 ? 64 : 16;
-    unsigned char *scr = nullptr; uint32_t *dops = nullptr; unsigned char *misc = nullptr;
-    const size_t scan_bytes = want_cigar ? pmx_text_scan_scratch_bytes(n) : 0;
-    const size_t misc_bytes = (size_t)(2 * n + 2) * sizeof(int32_t) + 256 + scan_bytes;
+    if (knobs.two_columns) two_cols = R != 16;
+    if (knobs.one_column) two_cols = 0;
+    unsigned char *scr = nullptr; SlotText t;
     if (scratch_reserve(pl.sweep_bytes + pl.ck_bytes, (void **)&scr, SCR_LONG) ||
-        (want_cigar && scratch_reserve((op_slots > 0 ? (size_t)op_slots : (size_t)n * ((size_t)max_qlen + max_rlen + 1)) * sizeof(uint32_t), (void **)&dops, SCR_OPS)) ||
-        scratch_reserve(misc_bytes, (void **)&misc, SCR_CIG)) return -1;
-    int32_t *nops = (int32_t *)misc, *textlen = nops + n;
-    void *scan_tmp = (void *)(((uintptr_t)(textlen + n + 2) + 255) & ~(uintptr_t)255);
+        (want_cigar && t.reserve_ops(op_slots > 0 ? (size_t)op_slots : (size_t)n * ((size_t)max_qlen + max_rlen + 1))) ||
+        scratch_carve(SCR_CIG, [&](Carver &c) { t.carve(c, n, want_cigar); })) return -1;
     HIP_OR_RET(hipMemsetAsync(scr, 0, 64, st));
     for (int64_t c0 = 0; c0 < n; c0 += pl.chunk) {
         PmxBatch b; memset(&b, 0, sizeof b);
@@ -3002,24 +3076,20 @@ static int long_cigar_device(const pmx_config_t *cfg, int64_t n, const uint8_t *
         long long bstride = 0; int nbmax = 0;
         void *ck = scr + ((pmx_long_scratch_bytes(b.n, max_qlen, max_rlen, R, &bstride, &nbmax) + 255) & ~(size_t)255);
         int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, scr, d_out + c0, 2147483647, 0, st,
-                                 spin_limit, chunk_cols, two_cols, ck, pl.tile_cols);
+                                 knobs.spin_limit, knobs.chunk_cols, two_cols, ck, pl.tile_cols);
         if (rc < 0) { set_err("checkpoint sweep launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
         if (rc) { set_err("the long-pair sweep does not take this configuration (alphabet above 64 letters, scores or gap penalties beyond its 16-bit profile, lengths x penalties beyond 2^29)"); return -1; }
         rc = pmx_launch_walkt(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, pl.tile_cols, scr, ck, d_out + c0,
-                              d_qoff + c0, -c0, dops, want_cigar ? nops + c0 : nullptr, want_cigar ? textlen + c0 : nullptr,
+                              d_qoff + c0, -c0, t.ops, want_cigar ? t.nops + c0 : nullptr, want_cigar ? t.textlen + c0 : nullptr,
                               want_stats ? d_stats + c0 : nullptr, st);
         if (rc) { set_err("tile walk launch failed (%d)", rc); return rc < 0 ? rc : -1; }
     }
     if (want_cigar) {
-        int rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan_tmp, scan_bytes, st);
-        if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
-        rc = pmx_launch_cigar_render_slots(dops, d_qoff, d_roff, 0, nops, d_text_off, d_text, capacity, n, st);
-        if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
+        const int rc = t.render(d_qoff, d_roff, 0, n, d_text, capacity, d_text_off, st);
+        if (rc) return rc;
     }
     if (d_abort) *d_abort = reinterpret_cast<const int *>(scr);
-    g_last_kernel = R == 16 ? "pmx_long32_kernel<16,ck>/checkpoint sweep + pmx_walkt_kernel"
-                  : two_cols ? (R == 2 ? "pmx_long32_kernel_c2<2,ck>/checkpoint sweep + pmx_walkt_kernel" : "pmx_long32_kernel_c2<4,ck>/checkpoint sweep + pmx_walkt_kernel")
-                  : (R == 2 ? "pmx_long32_kernel<2,ck>/checkpoint sweep + pmx_walkt_kernel" : "pmx_long32_kernel<4,ck>/checkpoint sweep + pmx_walkt_kernel");
+    g_last_kernel = long_kernel_name(R, two_cols, true);
     return 0;
 }
 
@@ -3032,8 +3102,7 @@ extern "C" int pmx_align_batch_cigar_long_device(const pmx_config_t *cfg, int64_
     if (long_cigar_check(cfg, opts)) return -1;
     if (n <= 0) return 0;
     if (!d_qbuf || !d_qoff || !d_rbuf || !d_roff || !d_out) { set_err("null buffer"); return -1; }
-    if ((cfg->want & PMX_WANT_STATS) && !d_stats_out) { set_err("stats requested without a stats buffer"); return -1; }
-    if ((cfg->want & PMX_WANT_CIGAR) && (!d_cigar_text || !d_cigar_off)) { set_err("null cigar output"); return -1; }
+    if (traced_outputs_check(cfg, d_stats_out, d_cigar_text, d_cigar_off, false)) return -1;
     if (max_qlen <= 0 || max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
@@ -3046,61 +3115,26 @@ extern "C" int pmx_align_batch_cigar_long(const pmx_config_t *cfg, int64_t n,
                                           pmx_record_t *out, pmx_stats_t *stats_out, char **cigar_buf, int64_t *cigar_off,
                                           const pmx_long_cigar_opts_t *opts)
 {
-    if (long_cigar_check(cfg, opts)) return -1;
-    const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (want_cigar && (!cigar_buf || !cigar_off)) { set_err("null cigar output"); return -1; }
-    if (want_stats && !stats_out) { set_err("stats requested without a stats buffer"); return -1; }
-    if (want_cigar) *cigar_buf = nullptr;
+    if (long_cigar_check(cfg, opts) || traced_outputs_check(cfg, stats_out, cigar_buf, cigar_off, true)) return -1;
+    if (cfg->want & PMX_WANT_CIGAR) *cigar_buf = nullptr;
     if (n <= 0) return 0;
     if (!qbuf || !qoff || !rbuf || !roff || !out) { set_err("null buffer"); return -1; }
-    int32_t mq = 0, mr = 0; bool bad = false;
-    host_maxlens(n, roff, &mr, &bad);
-    host_maxlens(n, qoff, &mq, &bad);
-    if (bad || roff[0] != 0 || qoff[0] != 0) { set_err("bad offsets (every sequence needs length >= 1, offsets start at 0)"); return -1; }
-    // text capacity: half a byte per symbol + 16 per pair covers related pairs many times over; a batch that needs more runs again
-    int64_t capacity = want_cigar ? ((qoff[n] + roff[n]) / 2 + 16 * n + 256) : 0;
-    DevBuf<uint8_t> dq, dr; DevBuf<int64_t> dqo, dro, dtoff; DevBuf<pmx_record_t> drec; DevBuf<pmx_stats_t> dst; DevBuf<char> dtext;
-    if (dr.try_alloc((size_t)roff[n]) || dro.try_alloc(n + 1) || dq.try_alloc((size_t)qoff[n]) || dqo.try_alloc(n + 1) || drec.try_alloc(n) ||
-        (want_stats && dst.try_alloc(n)) || (want_cigar && (dtoff.try_alloc(n + 1) || dtext.try_alloc((size_t)capacity + 1)))) { set_err("out of device memory"); return -2; }
-    HIP_OR_RET(hipMemcpy(dr.p, rbuf, (size_t)roff[n], hipMemcpyHostToDevice));
-    HIP_OR_RET(hipMemcpy(dro.p, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-    HIP_OR_RET(hipMemcpy(dq.p, qbuf, (size_t)qoff[n], hipMemcpyHostToDevice));
-    HIP_OR_RET(hipMemcpy(dqo.p, qoff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-    for (int pass = 0; pass < 2; ++pass) {
-        const int *d_abort = nullptr;
-        const int rc = long_cigar_device(cfg, n, dq.p, dqo.p, dr.p, dro.p, mq, mr, drec.p, dst.p, dtext.p, capacity, dtoff.p, opts, nullptr, &d_abort,
-                                         qoff[n] + roff[n] + n);
-        if (rc) return rc;
-        HIP_OR_RET(hipDeviceSynchronize());
-        int gave_up = 0;
-        HIP_OR_RET(hipMemcpy(&gave_up, d_abort, sizeof(int), hipMemcpyDeviceToHost));
-        if (gave_up) {
-            set_err("checkpoint sweep: a band's bounded wait for the band above ran out (dispatch order assumption broken, or PMX_LONG_SPIN_LIMIT); "
-                    "no alignment is returned");
-            return -3;
-        }
-        if (!want_cigar) break;
-        HIP_OR_RET(hipMemcpy(cigar_off, dtoff.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
-        if (cigar_off[n] <= capacity) break;
-        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
-        (void)hipFree(dtext.p); dtext.p = nullptr;
-        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    }
-    HIP_OR_RET(hipMemcpy(out, drec.p, sizeof(pmx_record_t) * n, hipMemcpyDeviceToHost));
-    if (want_stats) HIP_OR_RET(hipMemcpy(stats_out, dst.p, sizeof(pmx_stats_t) * n, hipMemcpyDeviceToHost));
-    if (want_cigar) {
-        TextBuf text;
-        char *dst_text = text.grow((size_t)cigar_off[n]);
-        if (!dst_text) { set_err("out of memory"); return -1; }
-        if (cigar_off[n]) {
-            const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
-        }
-        text.len = (size_t)cigar_off[n];
-        text.p[text.len] = 0;
-        *cigar_buf = text.p; g_text_pool.handed_out(text.p, text.cap);
-    }
-    return 0;
+    return traced_host_batch(cfg, nullptr, n, qbuf, qoff, rbuf, roff, nullptr, out, stats_out, cigar_buf, cigar_off,
+        [&](const StagedBatch &s, pmx_stats_t *d_stats, char *d_text, int64_t capacity, int64_t *d_text_off) -> int {
+            const int *d_abort = nullptr;
+            const int rc = long_cigar_device(cfg, n, s.dq.p, s.dqo.p, s.dr.p, s.dro.p, s.mq, s.mr, s.drec.p, d_stats, d_text, capacity, d_text_off,
+                                             opts, nullptr, &d_abort, qoff[n] + roff[n] + n);
+            if (rc) return rc;
+            HIP_OR_RET(hipDeviceSynchronize());
+            int gave_up = 0;
+            HIP_OR_RET(hipMemcpy(&gave_up, d_abort, sizeof(int), hipMemcpyDeviceToHost));
+            if (gave_up) {
+                set_err("checkpoint sweep: a band's bounded wait for the band above ran out (dispatch order assumption broken, or PMX_LONG_SPIN_LIMIT); "
+                        "no alignment is returned");
+                return -3;
+            }
+            return 0;
+        });
 }
 
 // ============================================================================= multi-GPU ===

@@ -279,6 +279,47 @@ def test_banded_cigar_device_capacity(pkg, orc):
     assert (out.cpu().numpy().view(pkg.RECORD_DTYPE).reshape(-1) == want_rec).all()
 
 
+@pytest.mark.parametrize("mismatch", (-3, -1))
+def test_banded_cigar_text_beyond_the_estimate(pkg, orc, mismatch):
+    """the host entry's second pass: alternating match / mismatch pairs ("1=1X..." is two bytes of text per symbol) push the text past
+    the first capacity, (query bytes + reference bytes) / 2 + 16 n + 256, and the batch runs again with the exact size"""
+    import torch
+    rng = np.random.default_rng(9850 - mismatch)
+    pm, om = pkg.Matrix.create(b"ACGT", 2, mismatch), orc.Matrix.create("ACGT", 2, mismatch)
+    al = _aligner(pkg, 0, 0, pm, 5, 2)
+    qs = random_seqs(rng, 6, 100, 300)
+    rs = [mutate(rng, q, 0.08, 0.01) for q in qs]
+    for at, L in ((0, 600), (2, 2000), (5, 600), (9, 2000)):          # among ordinary related pairs: per-pair offsets and the total
+        qs.insert(at, (b"AC" * L)[:L]); rs.insert(at, (b"AG" * L)[:L])
+    n = len(rs)
+    rec, cig, st = _check(pkg, orc, al, 0, 0, qs, rs, 31, None, 5, 2, om)
+    estimate = (sum(len(x) for x in qs) + sum(len(x) for x in rs)) // 2 + 16 * n + 256
+    assert sum(len(c) for c in cig) > estimate                     # = cigar_off[n]: the first pass cannot have held it
+    for at, L in ((0, 600), (2, 2000), (5, 600), (9, 2000)):
+        assert cig[at] == "1=1X" * (L // 2) and rec["score"][at] == (2 + mismatch) * (L // 2)
+    # the device entry into an exact-size buffer
+    qb, qo = pkg.pack(qs); rb, ro = pkg.pack(rs)
+    dev = torch.device("cuda", 0)
+    d = [torch.from_numpy(x).to(dev) for x in (qb, qo, rb, ro)]
+    out = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    dst = torch.zeros((n, 3), dtype=torch.int32, device=dev)
+    toff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    need = sum(len(c) for c in cig)
+    text = torch.zeros(need, dtype=torch.uint8, device=dev)
+    cfg = al._config()
+    cfg.want = pkg.WANT_CIGAR | pkg.WANT_STATS
+    rc = pkg.lib.pmx_align_batch_banded_cigar_device(C.byref(cfg), None, n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(),
+                                                     d[3].data_ptr(), max(len(x) for x in qs), max(len(x) for x in rs), 31, None,
+                                                     out.data_ptr(), dst.data_ptr(), text.data_ptr(), need, toff.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream)
+    assert rc == 0, pkg.lib.pmx_last_error()
+    torch.cuda.synchronize()
+    raw, o = text.cpu().numpy().tobytes(), toff.cpu().numpy()
+    assert o[n] == need and [raw[o[k]:o[k + 1]].decode() for k in range(n)] == cig
+    assert (out.cpu().numpy().view(pkg.RECORD_DTYPE).reshape(-1) == rec).all()
+    assert (dst.cpu().numpy().view(pkg.STATS_DTYPE).reshape(-1) == st).all()
+
+
 def test_banded_cigar_300kbp_pair(pkg, orc):
     """one 300 kbp x 300 kbp global pair at band 32: re-scored and band-checked (the oracle is too slow here)"""
     rng = np.random.default_rng(9900)

@@ -285,6 +285,42 @@ def test_device_entry_and_capacity(pkg, orc):
     assert (st.cpu().numpy().view(pkg.STATS_DTYPE).reshape(-1) == want[2]).all()
 
 
+@pytest.mark.parametrize("mismatch", (-3, -1))
+def test_text_beyond_the_estimate(pkg, orc, mismatch):
+    """the host entry's second pass: alternating match / mismatch pairs ("1=1X..." is two bytes of text per symbol) push the text past
+    the first capacity, (query bytes + reference bytes) / 2 + 16 n + 256, and the batch runs again with the exact size"""
+    import torch
+    rng = np.random.default_rng(5025 - mismatch)
+    pm, om = pkg.Matrix.create(b"ACGT", 2, mismatch), orc.Matrix.create("ACGT", 2, mismatch)
+    qs, rs = _related(rng, 6, 300, 900, DNA)
+    for at, L in ((0, 600), (2, 2000), (5, 600), (9, 2000)):          # among ordinary related pairs: per-pair offsets and the total
+        qs.insert(at, (b"AC" * L)[:L]); rs.insert(at, (b"AG" * L)[:L])
+    n = len(rs)
+    got = _run(pkg, 0, 0, pm, 5, 2, qs, rs)
+    rec, cig, st, coff, raw = got
+    estimate = (sum(len(x) for x in qs) + sum(len(x) for x in rs)) // 2 + 16 * n + 256
+    assert coff[n] > estimate and coff[n] == len(raw)              # the first pass cannot have held it
+    for at, L in ((0, 600), (2, 2000), (5, 600), (9, 2000)):
+        assert cig[at] == "1=1X" * (L // 2) and rec["score"][at] == (2 + mismatch) * (L // 2)
+    _against_oracle(pkg, orc, 0, 0, om, 5, 2, qs, rs, got)
+    # the device entry into an exact-size buffer
+    qb, qo = pkg.pack(qs); rb, ro = pkg.pack(rs)
+    dev = torch.device("cuda", 0)
+    d = [torch.from_numpy(x).to(dev) for x in (qb, qo, rb, ro)]
+    out = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    dst = torch.zeros((n, 3), dtype=torch.int32, device=dev)
+    toff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    text = torch.zeros(int(coff[n]), dtype=torch.uint8, device=dev)
+    cfg = pkg.pmx_config_t(0, 0, 5, 2, 32, pkg.WANT_CIGAR | pkg.WANT_STATS, pm.inner)
+    pkg.align_batch_cigar_long_device(cfg, n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                                      max(len(x) for x in qs), max(len(x) for x in rs), out.data_ptr(), dst.data_ptr(),
+                                      text.data_ptr(), int(coff[n]), toff.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()
+    assert text.cpu().numpy().tobytes() == raw and (toff.cpu().numpy() == coff).all()
+    assert (out.cpu().numpy().view(pkg.RECORD_DTYPE).reshape(-1) == rec).all()
+    assert (dst.cpu().numpy().view(pkg.STATS_DTYPE).reshape(-1) == st).all()
+
+
 def test_device_entry_returns_before_the_work_is_done(pkg, orc):
     """the header's promise: a call whose scratch is already large enough does not synchronise with the host.  One 20 kbp pair is
     tens of milliseconds of device work; right after the (second, warmed-up) call returns the stream must still be busy."""
