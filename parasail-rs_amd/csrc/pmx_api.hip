@@ -1391,6 +1391,13 @@ static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 
 static thread_local const char *g_last_kernel = "";
 extern "C" const char *pmx_last_kernel(void) { return g_last_kernel; }
+// the per-pair global / semi-global traceback roads: the sweep as its launcher named it (kernel, decision form) + the walk
+static const char *nwsg_trace_kernel_name(const char *walk)
+{
+    static thread_local char name[160];
+    snprintf(name, sizeof name, "%s%s", pmx_nwsg_trace_name(), walk);
+    return name;
+}
 
 
 // What every general-kernel batch shares: the n pairs, the matrix (a PSSM by query row), the gap model, the configured width, no band.
@@ -1718,9 +1725,9 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
         return run_chunk(t, cbytes, by_rounds && two && t.n < chunk);
     });
     if (rc) return rc;
-    static thread_local char name[96];
-    if (dm.d.pssm) snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d,pssm>/shared PSSM profile/packed trace + pmx_walkp_kernel<pssm>/stats", G, R);
-    else snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d>/shared profile/packed trace + pmx_walkp_kernel/stats", G, R);
+    static thread_local char name[112];
+    if (dm.d.pssm) snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d,pssm>/shared PSSM profile/packed trace/bfi + pmx_walkp_kernel<pssm>/stats", G, R);
+    else snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d>/shared profile/packed trace/bfi + pmx_walkp_kernel/stats", G, R);
     g_last_kernel = name;
     return 0;
 }
@@ -1752,7 +1759,7 @@ static int stats_by_trace_pairs(const pmx_config_t *cfg, const DevMat &dm, const
     const TraceOutputs o = {d_stats, nullptr, 0, nullptr, nullptr, nullptr};
     const int rc = trace_chunks(cfg, dm, bt, chunk, two, bflags, d_out, o, st, "stats-by-traceback launch failed", &variant);
     if (rc) return rc;
-    g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel/stats" : "pmx_nwsg16v_kernel/packed trace + pmx_walkp_kernel/stats";
+    g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel/stats" : nwsg_trace_kernel_name(" + pmx_walkp_kernel/stats");
     return 0;
 }
 
@@ -2502,7 +2509,7 @@ static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n
     if (rc) return rc;
     rc = t.render(d_qoff, d_roff, ops_base, n, d_text, capacity, d_text_off, st);
     if (rc) return rc;
-    g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : "pmx_nwsg16v_kernel/packed trace + pmx_walkp_kernel";
+    g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : nwsg_trace_kernel_name(" + pmx_walkp_kernel");
     return 0;
 }
 
@@ -2635,7 +2642,7 @@ static int cigar_chunk(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
         if (scratch_reserve(tbytes, (void **)&tbuf, SCR_TRACE)) return -1;
         rc = pmx_launch_trace16(variant, b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, drec.p, tbuf, Tmax,
                                 dops, doo.p, dnops.p, dbeg.p, nullptr);
-        g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : variant >= 10 ? "pmx_nwsg16v_kernel/packed trace + pmx_walkp_kernel" : "pmx_trace16_kernel + pmx_walk16_kernel";
+        g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : variant >= 10 ? nwsg_trace_kernel_name(" + pmx_walkp_kernel") : "pmx_trace16_kernel + pmx_walk16_kernel";
         if (rc) { set_err("trace16 launch failed (%d)", rc); return rc < 0 ? rc : -1; }
     } else {
         std::vector<int64_t> tab_off(n + 1);

@@ -61,6 +61,8 @@ int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int
                          int *variant, int *Tmax, size_t *trace_bytes);
 int pmx_launch_nwsgv_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
                            pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream);
+// the sweep pmx_launch_nwsgv_trace launched last on this thread: kernel + "/packed trace" + the decision form ("/bfi", "/shift")
+const char *pmx_nwsg_trace_name();
 
 // Traceback with a shared query (pmx_nwsg16q_kernel<..., TR>): statistics of the profile arm are counted along the path.
 long long pmx_nwsgq_trace_round_pairs(int variant, const PmxDevMatrix &m, int mode, int sg_flags);

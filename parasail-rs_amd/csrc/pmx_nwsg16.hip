@@ -1439,6 +1439,8 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
     }
 }
 
+// which per-pair packed-traceback sweep this thread launched last (pmx_nwsg_trace_name below): 0 nwsg16v shift, 1 nwsg16v bfi, 2 nwsg16m
+static thread_local int g_nwsg_trace_form = 0;
 template <int G, int R, bool TR = false>
 static int launch_nwsgm(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
                         pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf = nullptr, int Tmax = 0)
@@ -1449,6 +1451,7 @@ static int launch_nwsgm(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     const int col_pen = !(sg && (sg_flags & PMX_SG_QB)), row_pen = !(sg && (sg_flags & PMX_SG_DB));
     const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
     const long long blocks = (b.n + NP - 1) / NP;
+    if (TR) g_nwsg_trace_form = 2;
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_nwsg16m_kernel<G, R, TR>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
@@ -1605,6 +1608,14 @@ static int launch_nwsg(const PmxBatch &b, const PmxDevMatrix &m, int mode, int s
 }
 
 static thread_local bool g_nwsgv_pt = false;          // the last launch_nwsgv of this thread ran the perm-table form first (kernel names)
+// the last per-pair packed-traceback sweep of this thread as it really launched (kernel names): /bfi = the one-instruction
+// bounded-difference decision merge (TRB), /shift = the three-instruction merge; /permtable = the perm-table form ran first
+const char *pmx_nwsg_trace_name()
+{
+    if (g_nwsg_trace_form == 2) return "pmx_nwsg16m_kernel/packed trace/shift";
+    if (g_nwsg_trace_form == 1) return g_nwsgv_pt ? "pmx_nwsg16v_kernel/packed trace/bfi/permtable (+ LDS profiles for marked blocks)" : "pmx_nwsg16v_kernel/packed trace/bfi";
+    return "pmx_nwsg16v_kernel/packed trace/shift";
+}
 // PTOK: the shape has a perm-table instantiation (the ones BASELINE-sized DNA batches take; every instantiation costs compile time)
 template <int G, int R, bool TR> struct NwsgPtShape {
     static constexpr bool value = (!TR && G == 8 && (R == 7 || R == 10 || R == 13 || R == 16 || R == 19 || R == 20)) || (G == 16 && R == 16) ||
@@ -1619,6 +1630,7 @@ static int launch_nwsgv(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     if (!b.track8 && !pmx_nwsgv_bias(b, m, open, ext, 1, G * R)) return 1;
     if (TR && !TRB && (m.max > 0 ? m.max : 0) + 2 * open <= 250 && !pmx_env("PMX_TRACE_NO_BFI"))     // bounded differences: the one-instruction merge
         return launch_nwsgv<G, R, TR, FETCH, TR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
+    if (TR) g_nwsg_trace_form = TRB ? 1 : 0;
     constexpr int RS = (R + 3) / 4 * 4, NP = 2 * (64 / G);
     const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
     const size_t lds = (size_t)NP * (m.msize + 1) * G * RS + (FETCH ? 0 : (size_t)NP * RP) +

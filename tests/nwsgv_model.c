@@ -19,11 +19,16 @@ typedef struct {
     int score, end_query, end_ref;
     int lo, hi;                 /* extreme patterns fed to max3 */
     int violations;             /* values outside [1024, 31743], profile bytes outside [0, 255], capture values outside [0, 32767] */
-    int first_violation_kind;   /* 1 max3 operand, 2 profile byte, 3 last-row capture, 4 last-column capture */
+    int first_violation_kind;   /* 1 max3 operand, 2 profile byte, 3 last-row capture, 4 last-column capture, 5 decision difference */
+    int dmin, dmax;             /* extreme decision differences (T - H, F - H, E - X, F - X): what the one-instruction merge inserts */
+    int diff_violations;        /* kind 5: lanes and steps with a difference outside [-256, 255].  Counted apart from `violations`: the window must hold for every
+                                 * admitted batch, this bound only where the host's gate (max score + 2 open <= 250) picks the one-instruction merge */
 } nwsgv_model_out;
 
 #define WLO 1024
 #define WHI 31743
+#define DLO (-256)
+#define DHI 255
 
 /* every operand of a max3 goes through here: the extremes are kept in locals of the caller (vlo, vhi) and compared with the window once
  * per lane and step */
@@ -34,8 +39,10 @@ typedef struct {
 /* q, r: mapped symbols (0 .. msize-1).  top_aligned: the perm-table form (query in rows 0 .. qlen-1, padding rows below score
  * -open); otherwise the query sits in the LAST qlen rows of the G*R and P = G*R - qlen virtual rows lie above it.
  * legacy_capture: the last-column capture form before the round-3 fix (values + cb - row offset): kept so that the test can show
- * the model flags it.  Returns 0, or -1 on bad arguments. */
-int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
+ * the model flags it.  pssm: `mat` is a position-specific matrix of qlen rows of msize values and query row i reads row i of it
+ * instead of the row of its letter (the PSSM = true instances of pmx_nwsg16q_kernel); q is not read.  Nothing else changes.
+ * Returns 0, or -1 on bad arguments. */
+int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture, int pssm,
                 const unsigned char *q, int qlen, const unsigned char *r, int rlen, int max_rlen,
                 const int *mat, int msize, int open, int ext, int col_pen, int row_pen, int s1_end, int s2_end, int nb,
                 nwsgv_model_out *out)
@@ -45,8 +52,10 @@ int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
     nwsgv_model_out *o = out;
     memset(o, 0, sizeof *o);
     o->lo = 1 << 30; o->hi = -(1 << 30);
+    o->dmin = 1 << 30; o->dmax = -(1 << 30);
     const int P = top_aligned ? 0 : QP - qlen;
     const int rx = rowx ? ext : 0;
+#define QROW(i) (pssm ? (i) : q[(i)])
     const int vrow_b = (row_pen ? 0 : open) + rx, vcol_b = (col_pen ? 0 : open) + rx;
 
     /* profile bytes [er][sym], sym == msize: the pad symbol (virtual / padding column) */
@@ -55,11 +64,11 @@ int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
         for (int sym = 0; sym <= msize; ++sym) {
             int v;
             if (top_aligned) {
-                if (er < qlen) v = sym < msize ? mat[q[er] * msize + sym] + open + rx : vcol_b;
+                if (er < qlen) v = sym < msize ? mat[QROW(er) * msize + sym] + open + rx : vcol_b;
                 else v = 0;                                     /* selector constant 0x0C: byte 0 */
-            } else if (er >= P) v = sym < msize ? mat[q[er - P] * msize + sym] + open + rx : vcol_b;
+            } else if (er >= P) v = sym < msize ? mat[QROW(er - P) * msize + sym] + open + rx : vcol_b;
             else v = sym < msize ? vrow_b : open + rx;
-            if (v < 0 || v > 255) { if (!o->violations) o->first_violation_kind = 2; o->violations++; }
+            if (v < 0 || v > 255) { if (!o->violations && !o->diff_violations) o->first_violation_kind = 2; o->violations++; }
             prof[(size_t)er * (msize + 1) + sym] = (unsigned char)v;
         }
     }
@@ -104,7 +113,7 @@ int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
             const int col = t - g;
             const int sym = (col >= 0 && col < rlen) ? r[col] : msize;
             int F = Fin[g];
-            int vlo = 1 << 30, vhi = -(1 << 30);
+            int vlo = 1 << 30, vhi = -(1 << 30), dlo = 1 << 30, dhi = -(1 << 30);
             const unsigned char *ps = profT + (size_t)sym * QP + g * R;
             int *Hg = H + g * R, *Eg = E + g * R;
             int dprev = diag0[g];
@@ -114,6 +123,9 @@ int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
                 const int Fe = F - fsub;
                 int Hh; MAX3C(Hh, Tpk, Eg[k], Fe);
                 const int X = Hh - (open - ext);
+                /* the four differences whose signs are the traceback decisions (ND, NDL, EO, FO) */
+                const int dd[4] = {Tpk - Hh, Fe - Hh, Eg[k] - X, Fe - X};
+                for (int d = 0; d < 4; ++d) { dlo = dlo < dd[d] ? dlo : dd[d]; dhi = dhi > dd[d] ? dhi : dd[d]; }
                 MAX3C(Eg[k], Eg[k], X, X);
                 MAX3C(F, Fe, X, X);
                 Hn[k] = X;
@@ -121,7 +133,10 @@ int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
             }
             if (vlo < o->lo) o->lo = vlo;
             if (vhi > o->hi) o->hi = vhi;
-            if (vlo < WLO || vhi > WHI) { if (!o->violations) o->first_violation_kind = 1; o->violations++; }
+            if (vlo < WLO || vhi > WHI) { if (!o->violations && !o->diff_violations) o->first_violation_kind = 1; o->violations++; }
+            if (dlo < o->dmin) o->dmin = dlo;
+            if (dhi > o->dmax) o->dmax = dhi;
+            if (dlo < DLO || dhi > DHI) { if (!o->violations && !o->diff_violations) o->first_violation_kind = 5; o->diff_violations++; }
             diag0[g] = Hin[g]; Hout[g] = Hn[R - 1]; Fout[g] = F;
             /* captures */
             const int j16 = jj[g] & 0xFFFF;
@@ -132,7 +147,7 @@ int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
                 const int inside = (unsigned)j16 < (unsigned)rlen;
                 const int cand = Hlast - skewX[g];                          /* nb + cb + true H */
                 if (inside && g == gs) {                                   /* (only the lane that holds the last row is read at the end) */
-                    if (cand < 0 || cand > 32767) { if (!o->violations) o->first_violation_kind = 3; o->violations++; }
+                    if (cand < 0 || cand > 32767) { if (!o->violations && !o->diff_violations) o->first_violation_kind = 3; o->violations++; }
                 }
                 const int c16 = (int)(short)(cand & 0xFFFF);
                 if (inside && bestrow[g] < c16) { bestrow[g] = c16; bestrowj[g] = j16; }
@@ -145,7 +160,7 @@ int nwsgv_model(int G, int R, int rowx, int top_aligned, int legacy_capture,
                     int v = 0;
                     if (real) {
                         v = legacy_capture ? Hn[k] + cb - er * rx : Hn[k] + (QP - er) * rx;
-                        if (v < WLO || v > WHI) { if (!o->violations) o->first_violation_kind = 4; o->violations++; }
+                        if (v < WLO || v > WHI) { if (!o->violations && !o->diff_violations) o->first_violation_kind = 4; o->violations++; }
                         v = (int)(short)(v & 0xFFFF);
                     }
                     Hn[k] = v;                                              /* (reused as vals[]) */

@@ -36,7 +36,7 @@ def test_cfg3_shared_profile_nw_stats_full_shape(pkg, orc):
     assert al.fn_name == wl.CFG3["name"]
     rec, st = al.align_batch_packed(None, None, rbuf, roff)
     kernel = pkg.lib.pmx_last_kernel().decode()
-    assert "nwsg16q" in kernel and "packed trace" in kernel and "stats" in kernel, kernel     # traceback sweep + counting walk
+    assert "nwsg16q" in kernel and "packed trace/bfi" in kernel and "stats" in kernel, kernel     # traceback sweep (one-instruction merge) + counting walk
     rlen = (roff[1:] - roff[:-1]).astype(np.int64)
     # every pair: global ends, no saturation at 16 bits, statistics consistent with each other and with the lengths
     assert (rec["flags"] == 0).all()
@@ -108,7 +108,7 @@ def test_cfg4_semi_global_cigar_full_shape(pkg, orc):
     assert al.fn_name == wl.CFG4["name"]
     rec, text, coff = al.align_batch_cigar_packed(qbuf, qoff, rbuf, roff)
     kernel = pkg.lib.pmx_last_kernel().decode()
-    assert "packed trace" in kernel, kernel
+    assert "pmx_nwsg16v_kernel/packed trace/bfi/permtable" in kernel, kernel      # (2 + 2 * 5 <= 250: the one-instruction merge)
     assert (rec["flags"] == 0).all()
     # every pair: the end lies on the last row or the last column, the CIGAR consumes both sequences completely
     # (the oracle's walk emits free end gaps), its =/X letters agree with the sequences, and re-scoring it with

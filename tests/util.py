@@ -54,3 +54,27 @@ def score_from_cigar(text, q, r, bq, br, scores, mapper, open_, ext):
             else:
                 j += n
     return s, i, j
+
+
+B62_LETTERS = b"ARNDCQEGHILKMFPSTWYVBZX*"
+
+
+def consensus_pssm(rng, L, top, bottom, lo=-6, hi=9, by_letter=None):
+    """A 24-letter PSSM (BLOSUM62's alphabet) whose every row holds `top` in its consensus column (one of the 20 amino acids) and
+    `bottom` under '*'; the rest is random in lo .. hi.  by_letter (a query of L letters): rows of equal query letters are equal --
+    the PSSM of a square matrix, which the square oracle scores at any length (the byte-encoded PSSM checker ends at 200 rows).
+    Returns (int32 [L, 24], the consensus sequence, the square matrix or None)."""
+    if by_letter is None:
+        vals = rng.integers(lo, hi + 1, size=(L, 24)).astype(np.int32)
+        cons = rng.integers(0, 20, size=L)
+        square = None
+    else:
+        square = rng.integers(lo, hi + 1, size=(24, 24)).astype(np.int32)
+        perm = rng.permutation(20)                                   # letter a's consensus column (need not be a)
+        idx = np.array([B62_LETTERS.index(bytes([c])) for c in by_letter])
+        square[np.arange(20), perm] = top
+        square[:, 23] = bottom
+        vals, cons = square[idx].copy(), perm[idx]
+    vals[np.arange(L), cons] = top
+    vals[:, 23] = bottom
+    return vals, bytes(B62_LETTERS[c] for c in cons), square
