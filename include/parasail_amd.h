@@ -339,6 +339,67 @@ int pmx_align_batch_banded_cigar_device(const pmx_config_t *cfg, const parasail_
                                         pmx_record_t *d_out, pmx_stats_t *d_stats_out,
                                         char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream);
 
+/* Profile database search (extension): one reused profile against n references, the references that score at least min_score --
+ * at most the best max_hits of them -- and, for each of those hits, a banded second pass with traceback around the first pass's
+ * diagonal.  Selection, compaction of the selected references and the second pass all run on the device; the references are
+ * uploaded once.
+ *
+ * Selection (pmx_select_hits_device, and the search entries through it).  The passing set is P = { k : score_k >= min_score }: only
+ * the score of a record is looked at.  With max_hits > 0 and |P| > max_hits the max_hits members of P that come first under (score
+ * descending, index ascending) are kept, the members inside the tie run at the last kept score included; max_hits == 0: no limit.
+ * PMX_HITS_BY_INDEX lists the selected in ascending index, PMX_HITS_BY_SCORE in (score descending, index ascending).  At most
+ * `capacity` indices are written, the first ones in that order; d_counts[0] is the full number selected and d_counts[1] is |P|.  The
+ * result is bit-identical from run to run.  Asynchronous on `stream`, no host synchronisation; scratch belongs to the calling thread
+ * like that of the other device entries (by score: 24 bytes per selectable hit for the sort). */
+#define PMX_HITS_BY_INDEX 0
+#define PMX_HITS_BY_SCORE 1
+int pmx_select_hits_device(const pmx_record_t *d_rec, int64_t n, int32_t min_score, int64_t max_hits /* 0 = no limit */, int order,
+                           int64_t *d_hit_index, int64_t capacity, int64_t *d_counts /* [0] selected, [1] passing the threshold */,
+                           void *stream);
+/* References d_index[0 .. h) of a packed device buffer, back to back in d_out: d_out_off receives h + 1 offsets starting at 0, a
+ * reference whose end would cross out_capacity is not written (the cigar_capacity rule).  No byte outside
+ * [d_rbuf, d_rbuf + d_roff[n]) is read.  Asynchronous on `stream`. */
+int pmx_gather_refs_device(const uint8_t *d_rbuf, const int64_t *d_roff, int64_t n, const int64_t *d_index, int64_t h,
+                           uint8_t *d_out, int64_t out_capacity, int64_t *d_out_off, void *stream);
+
+/* band < 0: no second pass -- hits with their first-pass records only, begins -1, any matrix the first pass takes (a PSSM too).
+ * band 0 .. 63: the second pass of pmx_align_batch_banded_cigar in its profile arm over the hits, diag = end_ref - end_query of the
+ * first pass; its limits hold (square matrices of size <= 32, no PSSM) and cfg->want must contain PMX_WANT_CIGAR and / or
+ * PMX_WANT_STATS.  The first pass is the score-only batch pmx_align_profile_batch_device runs for cfg (PMX_WANT_SORTED is passed on to
+ * both passes, the other want bits to the second). */
+typedef struct pmx_search_opts { int32_t min_score; int64_t max_hits; int32_t order; int32_t band; } pmx_search_opts_t;
+/* beg_query / beg_ref: the first cell of the second pass's path (what the one-pair parasail_cigar_t reports; 0 / 0 for global and
+ * semi-global paths), -1 without a second pass or where the band misses the end cell. */
+typedef struct pmx_hit { int64_t index; pmx_record_t first; int32_t diag, beg_query, beg_ref, reserved; } pmx_hit_t;
+/* One block, released with pmx_search_result_free: hits, recs (second-pass records; NULL with band < 0), stats (NULL unless
+ * PMX_WANT_STATS and band >= 0), cigar text (NULL unless PMX_WANT_CIGAR and band >= 0) and cigar_off (n_hits + 1 entries, always
+ * there; all 0 without text) point into it.  n_passing = |P|. */
+typedef struct pmx_search_result {
+    int64_t n_hits, n_passing;
+    pmx_hit_t *hits;
+    pmx_record_t *recs;
+    pmx_stats_t *stats;
+    char *cigar;
+    int64_t *cigar_off;
+} pmx_search_result_t;
+/* Host references in, one callee-allocated result out (*result is NULL on failure).  Zero hits is success with empty outputs and
+ * cigar_off[0] == 0.  Refused with -1 and a pmx_last_error() text before any GPU work: a NULL profile or opts, an order other than
+ * PMX_HITS_BY_*, a negative max_hits, a band above 63, a PSSM or a matrix beyond size 32 with band >= 0, a want without
+ * PMX_WANT_CIGAR and PMX_WANT_STATS with band >= 0. */
+int pmx_search_profile(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                       const uint8_t *rbuf, const int64_t *roff, const pmx_search_opts_t *opts, pmx_search_result_t **result);
+void pmx_search_result_free(pmx_search_result_t *result);
+/* Device references in, device outputs into caller buffers: d_first (n first-pass records; NULL: internal scratch), d_hits / d_recs /
+ * d_stats (`capacity` entries each; d_recs and d_stats as cfg->want and band ask), d_cigar_text / d_cigar_off (capacity + 1 offsets)
+ * following pmx_align_batch_banded_cigar_device: offsets of the hits written start at 0 and a hit whose text would cross
+ * cigar_capacity is not written.  min(d_counts[0], capacity) hits are written, the first ones in output order; entries beyond them
+ * are untouched.  A negative capacity is refused like the cases above.  The call synchronises `stream` ONCE, between the passes, to
+ * read the hit count; everything else is asynchronous on `stream`. */
+int pmx_search_profile_device(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                              const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen, const pmx_search_opts_t *opts,
+                              pmx_record_t *d_first, pmx_hit_t *d_hits, pmx_record_t *d_recs, pmx_stats_t *d_stats, int64_t capacity,
+                              char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, int64_t *d_counts, void *stream);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -67,6 +67,43 @@ pub struct PmxLongCigarOpts {
     pub band_rows: c_int,
 }
 
+/// `pmx_search_opts_t`: threshold, limit (0 = none), order and band of a profile search (`band < 0`: no second pass).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct PmxSearchOpts {
+    pub min_score: i32,
+    pub max_hits: i64,
+    pub order: i32,
+    pub band: i32,
+}
+
+/// `pmx_hit_t`: one hit of a profile search -- index of the reference, its first-pass record, the diagonal the second pass was
+/// centred on and the first cell of the second pass's path (-1 without one).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct PmxHit {
+    pub index: i64,
+    pub first: PmxRecord,
+    pub diag: i32,
+    pub beg_query: i32,
+    pub beg_ref: i32,
+    pub reserved: i32,
+}
+
+/// `pmx_search_result_t`: one callee-allocated block, released with `pmx_search_result_free`.
+#[repr(C)]
+pub struct PmxSearchResult {
+    pub n_hits: i64,
+    pub n_passing: i64,
+    pub hits: *mut PmxHit,
+    pub recs: *mut PmxRecord,
+    pub stats: *mut PmxStats,
+    pub cigar: *mut c_char,
+    pub cigar_off: *mut i64,
+}
+
+pub const PMX_HITS_BY_INDEX: i32 = 0;
+pub const PMX_HITS_BY_SCORE: i32 = 1;
 pub const PMX_WANT_STATS: c_int = 1;
 pub const PMX_WANT_CIGAR: c_int = 2;
 pub const PMX_WANT_SORTED: c_int = 4;
@@ -159,6 +196,25 @@ extern "C" {
         max_qlen: i32, max_rlen: i32, d_tab_off: *const i64, d_score_table: *mut i32,
         d_score_row: *mut i32, d_score_col: *mut i32, d_out: *mut PmxRecord, stream: *mut c_void,
     ) -> c_int;
+    fn pmx_search_profile(
+        cfg: *const PmxConfig, profile: *const parasail_profile_t, n: i64,
+        rbuf: *const u8, roff: *const i64, opts: *const PmxSearchOpts, result: *mut *mut PmxSearchResult,
+    ) -> c_int;
+    fn pmx_search_result_free(result: *mut PmxSearchResult);
+    pub fn pmx_search_profile_device(
+        cfg: *const PmxConfig, profile: *const parasail_profile_t, n: i64,
+        d_rbuf: *const u8, d_roff: *const i64, max_rlen: i32, opts: *const PmxSearchOpts,
+        d_first: *mut PmxRecord, d_hits: *mut PmxHit, d_recs: *mut PmxRecord, d_stats: *mut PmxStats, capacity: i64,
+        d_cigar_text: *mut c_char, cigar_capacity: i64, d_cigar_off: *mut i64, d_counts: *mut i64, stream: *mut c_void,
+    ) -> c_int;
+    pub fn pmx_select_hits_device(
+        d_rec: *const PmxRecord, n: i64, min_score: i32, max_hits: i64, order: c_int,
+        d_hit_index: *mut i64, capacity: i64, d_counts: *mut i64, stream: *mut c_void,
+    ) -> c_int;
+    pub fn pmx_gather_refs_device(
+        d_rbuf: *const u8, d_roff: *const i64, n: i64, d_index: *const i64, h: i64,
+        d_out: *mut u8, out_capacity: i64, d_out_off: *mut i64, stream: *mut c_void,
+    ) -> c_int;
     pub fn pmx_shard_bounds_by_cells(n: i64, qoff: *const i64, roff: *const i64, parts: c_int, bounds: *mut i64) -> c_int;
     pub fn pmx_host_register(p: *mut c_void, bytes: usize) -> c_int;
     pub fn pmx_host_unregister(p: *mut c_void) -> c_int;
@@ -231,6 +287,59 @@ impl Drop for BatchCigars {
 
 unsafe impl Send for BatchCigars {}
 
+/// Hits of a profile search: the callee's block, released with `pmx_search_result_free` on drop.
+pub struct SearchHits {
+    inner: *mut PmxSearchResult,
+}
+
+impl SearchHits {
+    fn r(&self) -> &PmxSearchResult {
+        unsafe { &*self.inner }
+    }
+    pub fn len(&self) -> usize {
+        self.r().n_hits as usize
+    }
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+    /// References that reached `min_score`, before `max_hits` cut them.
+    pub fn passing(&self) -> i64 {
+        self.r().n_passing
+    }
+    pub fn hits(&self) -> &[PmxHit] {
+        unsafe { std::slice::from_raw_parts(self.r().hits, self.len()) }
+    }
+    /// Records of the banded second pass (`None` with `band < 0`).
+    pub fn records(&self) -> Option<&[PmxRecord]> {
+        let p = self.r().recs;
+        if p.is_null() { None } else { Some(unsafe { std::slice::from_raw_parts(p, self.len()) }) }
+    }
+    pub fn stats(&self) -> Option<&[PmxStats]> {
+        let p = self.r().stats;
+        if p.is_null() { None } else { Some(unsafe { std::slice::from_raw_parts(p, self.len()) }) }
+    }
+    /// CIGAR text of hit `k` (`""` without a second pass).
+    pub fn cigar(&self, k: usize) -> &str {
+        let r = self.r();
+        if r.cigar.is_null() {
+            return "";
+        }
+        let off = unsafe { std::slice::from_raw_parts(r.cigar_off, self.len() + 1) };
+        let (a, e) = (off[k] as usize, off[k + 1] as usize);
+        unsafe { std::str::from_utf8_unchecked(std::slice::from_raw_parts(r.cigar.add(a) as *const u8, e - a)) }
+    }
+}
+
+impl Drop for SearchHits {
+    fn drop(&mut self) {
+        if !self.inner.is_null() {
+            unsafe { pmx_search_result_free(self.inner) }
+        }
+    }
+}
+
+unsafe impl Send for SearchHits {}
+
 fn last_error() -> Error {
     Error::Batch(unsafe { CStr::from_ptr(pmx_last_error()) }.to_string_lossy().into_owned())
 }
@@ -296,6 +405,27 @@ impl Aligner {
             return Err(last_error());
         }
         Ok((records, BatchCigars { text, off }))
+    }
+
+    /// Profile database search (extension, `pmx_search_profile`; an aligner built with `.profile()`): the references that score at
+    /// least `opts.min_score` -- the best `opts.max_hits` of them, 0 = all -- each with its first-pass record and, with
+    /// `opts.band >= 0`, the record, begin, CIGAR and (`want_stats`) statistics of a banded second pass around the first pass's
+    /// diagonal.  Selection, compaction of the selected references and the second pass run on the device.
+    pub fn search_profile(&self, references: &Packed, opts: PmxSearchOpts, want_stats: bool) -> Result<SearchHits> {
+        if self.profile.is_null() {
+            return Err(Error::Batch("aligner has no profile".to_string()));
+        }
+        let want = if opts.band >= 0 { PMX_WANT_CIGAR | if want_stats { PMX_WANT_STATS } else { 0 } } else { 0 };
+        let cfg = self.pmx_config(want);
+        let mut inner: *mut PmxSearchResult = std::ptr::null_mut();
+        let rc = unsafe {
+            pmx_search_profile(&cfg, **self.profile, references.len() as i64, references.buf.as_ptr(), references.off.as_ptr(),
+                               &opts, &mut inner)
+        };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok(SearchHits { inner })
     }
 
     /// Banded batch: the extension of `banded_nw` (`src/aligner/mod.rs:454-489`) to many pairs, any mode, and an optional

@@ -58,8 +58,29 @@ class pmx_long_cigar_opts_t(C.Structure):
     _fields_ = [("tile_cols", C.c_int), ("band_rows", C.c_int)]
 
 
+class pmx_record_t(C.Structure):
+    _fields_ = [("score", C.c_int32), ("end_query", C.c_int32), ("end_ref", C.c_int32), ("flags", C.c_int32)]
+
+
+class pmx_search_opts_t(C.Structure):
+    _fields_ = [("min_score", C.c_int32), ("max_hits", C.c_int64), ("order", C.c_int32), ("band", C.c_int32)]
+
+
+class pmx_hit_t(C.Structure):
+    _fields_ = [("index", C.c_int64), ("first", pmx_record_t), ("diag", C.c_int32), ("beg_query", C.c_int32),
+                ("beg_ref", C.c_int32), ("reserved", C.c_int32)]
+
+
+class pmx_search_result_t(C.Structure):
+    _fields_ = [("n_hits", C.c_int64), ("n_passing", C.c_int64), ("hits", C.c_void_p), ("recs", C.c_void_p),
+                ("stats", C.c_void_p), ("cigar", C.c_void_p), ("cigar_off", C.c_void_p)]
+
+
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
 STATS_DTYPE = np.dtype([("matches", "<i4"), ("similar", "<i4"), ("length", "<i4")])
+HIT_DTYPE = np.dtype([("index", "<i8"), ("first", RECORD_DTYPE), ("diag", "<i4"), ("beg_query", "<i4"), ("beg_ref", "<i4"),
+                      ("reserved", "<i4")])
+HITS_BY_INDEX, HITS_BY_SCORE = 0, 1
 
 MODE_NW, MODE_SG, MODE_SW = 0, 1, 2
 SG_QB, SG_QE, SG_DB, SG_DE, SG_ALL = 1, 2, 4, 8, 15
@@ -159,6 +180,16 @@ _sig("pmx_host_register", C.c_int, C.c_void_p, C.c_size_t)
 _sig("pmx_host_unregister", C.c_int, C.c_void_p)
 _sig("pmx_align_batch_2bit", C.c_int, C.POINTER(pmx_config_t), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_select_hits_device", C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+     C.c_void_p)
+_sig("pmx_gather_refs_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+     C.c_void_p)
+_sig("pmx_search_profile", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_search_opts_t), C.POINTER(C.POINTER(pmx_search_result_t)))
+_sig("pmx_search_result_free", None, C.POINTER(pmx_search_result_t))
+_sig("pmx_search_profile_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+     C.POINTER(pmx_search_opts_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+     C.c_void_p, C.c_void_p)
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -860,6 +891,32 @@ class Aligner:
         cigars = _take_cigars(cbuf, coff)
         return (out, cigars, st) if stats else (out, cigars)
 
+    def search_profile(self, references, min_score, max_hits=0, order=HITS_BY_INDEX, band=48, stats=False):
+        """Profile database search (extension; the aligner needs a profile): the references that score at least min_score -- at most
+        the best max_hits of them, 0 = no limit -- in ascending index or by (score descending, index ascending), each with its
+        first-pass record and, with band >= 0, a banded second pass around the first pass's diagonal: record, begin of the path,
+        CIGAR and (stats=True) matches / similar / length.  band < 0: no second pass (begins -1, no CIGAR).  Selection, the
+        compaction of the selected references and the second pass run on the device.  Returns a SearchHits."""
+        rbuf, roff = pack(references)
+        return self.search_profile_packed(rbuf, roff, min_score, max_hits, order, band, stats)
+
+    def search_profile_packed(self, rbuf, roff, min_score, max_hits=0, order=HITS_BY_INDEX, band=48, stats=False):
+        if self._profile.is_null():
+            raise NullProfile()
+        n = len(roff) - 1
+        cfg = self._config()
+        cfg.want = (WANT_CIGAR | (WANT_STATS if stats else 0)) if band >= 0 else 0
+        opts = pmx_search_opts_t(int(min_score), int(max_hits), int(order), int(band))
+        res = C.POINTER(pmx_search_result_t)()
+        rc = lib.pmx_search_profile(C.byref(cfg), self._profile.inner, n, rbuf.ctypes.data, roff.ctypes.data, C.byref(opts),
+                                    C.byref(res))
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        try:
+            return SearchHits(res.contents)
+        finally:
+            lib.pmx_search_result_free(res)
+
     def align_batch_cigar_long(self, queries, references, stats=False, cigar=True, tile_cols=0, band_rows=0):
         """Long pairs with traceback in linear memory (extension): the records of align_batch, each pair's CIGAR string and, with
         stats=True, matches / similar / length along the path.  tile_cols / band_rows: 0 = default (never change a result).
@@ -917,6 +974,36 @@ class Aligner:
         raw._pmx_owner = _OwnedBuffer(cbuf)
         text = np.frombuffer(raw, dtype=np.uint8, count=nbytes)
         return out, text, coff
+
+
+class SearchHits:
+    """Result of Aligner.search_profile: n_hits, n_passing, hits (HIT_DTYPE: index, first, diag, beg_query, beg_ref), recs
+    (RECORD_DTYPE of the second pass, None without one), stats (STATS_DTYPE or None), cigar_off (int64 [n_hits + 1]), cigar_text
+    (uint8) and cigars (list of str; empty strings without a second pass).  Shortcuts: index, score, end_query, end_ref (of the
+    second pass when there is one, else of the first), beg_query, beg_ref."""
+
+    def __init__(self, r):
+        h = int(r.n_hits)
+        self.n_hits, self.n_passing = h, int(r.n_passing)
+
+        def take(ptr, dtype, count):
+            if not ptr or not count:
+                return np.zeros(count, dtype=dtype)
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype).copy()
+        self.hits = take(r.hits, HIT_DTYPE, h)
+        self.recs = take(r.recs, RECORD_DTYPE, h) if r.recs else None
+        self.stats = take(r.stats, STATS_DTYPE, h) if r.stats else None
+        self.cigar_off = take(r.cigar_off, np.int64, h + 1)
+        self.cigar_text = take(r.cigar, np.uint8, int(self.cigar_off[h])) if r.cigar else np.zeros(0, dtype=np.uint8)
+        raw = self.cigar_text.tobytes()
+        self.cigars = [raw[self.cigar_off[k]:self.cigar_off[k + 1]].decode() for k in range(h)]
+        best = self.recs if self.recs is not None else self.hits["first"]
+        self.index = self.hits["index"]
+        self.score, self.end_query, self.end_ref = best["score"], best["end_query"], best["end_ref"]
+        self.beg_query, self.beg_ref = self.hits["beg_query"], self.hits["beg_ref"]
+
+    def __len__(self):
+        return self.n_hits
 
 
 def _take_cigars(cbuf, coff):
@@ -993,6 +1080,33 @@ def long_cigar_scratch_bytes(n, max_qlen, max_rlen, tile_cols=0, band_rows=0):
 def align_profile_batch_device(cfg, profile, n, d_rbuf, d_roff, max_rlen, d_out, d_stats=None, stream=0):
     """One reused query profile against device-resident references."""
     rc = lib.pmx_align_profile_batch_device(C.byref(cfg), profile.inner, n, d_rbuf, d_roff, max_rlen, d_out, d_stats, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def select_hits_device(d_rec, n, min_score, max_hits, order, d_hit_index, capacity, d_counts, stream=0):
+    """Device-pointer hit selection over n 16-byte records: indices of the records with score >= min_score (the best max_hits of
+    them, 0 = all) into d_hit_index (at most `capacity`), the numbers selected and passing into d_counts[0:2] (int64)."""
+    rc = lib.pmx_select_hits_device(d_rec, n, int(min_score), int(max_hits), int(order), d_hit_index, capacity, d_counts, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def gather_refs_device(d_rbuf, d_roff, n, d_index, h, d_out, out_capacity, d_out_off, stream=0):
+    """References d_index[0:h] of a packed device buffer back to back into d_out, their h + 1 offsets into d_out_off."""
+    rc = lib.pmx_gather_refs_device(d_rbuf, d_roff, n, d_index, h, d_out, out_capacity, d_out_off, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_profile_device(cfg, profile, n, d_rbuf, d_roff, max_rlen, min_score, max_hits, order, band, d_first, d_hits, d_recs,
+                          d_stats, capacity, d_text, cigar_capacity, d_text_off, d_counts, stream=0):
+    """Device-pointer profile search: hits (HIT_DTYPE), second-pass records / statistics / CIGAR text + offsets for at most
+    `capacity` hits into caller buffers, counts into d_counts[0:2].  Synchronises `stream` once, between the passes."""
+    opts = pmx_search_opts_t(int(min_score), int(max_hits), int(order), int(band))
+    rc = lib.pmx_search_profile_device(C.byref(cfg), profile.inner if profile is not None else None, n, d_rbuf, d_roff, max_rlen,
+                                       C.byref(opts), d_first, d_hits, d_recs, d_stats, capacity, d_text, cigar_capacity, d_text_off,
+                                       d_counts, stream)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

@@ -515,6 +515,41 @@ public:
         return out;
     }
 
+    // additive: profile database search (pmx_search_profile; the aligner was built with .profile()): the references scoring at least
+    // min_score -- the best max_hits of them, 0 = all -- by index or by score, each with its first-pass record and, with band >= 0, the
+    // banded second pass's record, begin, CIGAR and (with_stats) statistics.  band < 0: no second pass.
+    struct SearchHits {
+        int64_t n_passing = 0;
+        std::vector<pmx_hit_t> hits;
+        std::vector<pmx_record_t> recs;
+        std::vector<pmx_stats_t> stats;
+        std::vector<std::string> cigars;
+    };
+    SearchHits search_profile(const std::vector<Bytes> &refs, int32_t min_score, int64_t max_hits = 0, int order = PMX_HITS_BY_INDEX,
+                              int32_t band = 48, bool with_stats = false) const
+    {
+        if (!profile_) throw Error(ErrorKind::Batch, "aligner has no profile");
+        std::string rb; std::vector<int64_t> ro(1, 0);
+        for (auto &r : refs) { rb += r; ro.push_back((int64_t)rb.size()); }
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        cfg.want = band >= 0 ? (PMX_WANT_CIGAR | (with_stats ? PMX_WANT_STATS : 0)) : 0;
+        const pmx_search_opts_t opts = {min_score, max_hits, order, band};
+        pmx_search_result_t *res = nullptr;
+        const int rc = pmx_search_profile(&cfg, profile_->inner, (int64_t)refs.size(), (const uint8_t *)rb.data(), ro.data(), &opts, &res);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        SearchHits out;
+        const size_t h = (size_t)res->n_hits;
+        out.n_passing = res->n_passing;
+        out.hits.assign(res->hits, res->hits + h);
+        if (res->recs) out.recs.assign(res->recs, res->recs + h);
+        if (res->stats) out.stats.assign(res->stats, res->stats + h);
+        out.cigars.resize(h);
+        if (res->cigar) for (size_t k = 0; k < h; ++k) out.cigars[k].assign(res->cigar + res->cigar_off[k], res->cigar + res->cigar_off[k + 1]);
+        pmx_search_result_free(res);
+        return out;
+    }
+
     std::shared_ptr<Matrix> matrix;
     int gap_open = 0, gap_extend = 0;
     std::string vec_strategy;

@@ -1369,7 +1369,9 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_HTEXT = 12, SCR_HTOFF = 13,                                                   // staging of the host CIGAR entry
        SCR_HQ2 = 14, SCR_HR2 = 15,                                                       // 2-bit packed input as it arrived
        SCR_LONG = 16,                                                                    // boundary granules + band candidates of pmx_long.hip
-       SCR_SLOTS = 17 };
+       SCR_SEL = 17,                                                                     // hit selection: state, histogram, block counts, sort buffers (pmx_select.hip)
+       SCR_SRCH = 18, SCR_GREF = 19,                                                     // profile search: hit list / diagonals / lengths / offsets / begins; gathered references
+       SCR_SLOTS = 20 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -2910,7 +2912,8 @@ static int banded_trace_check(const pmx_config_t *cfg, int32_t band)
 static int banded_trace_device(const pmx_config_t *cfg, int64_t n, const uint8_t *d_qbuf, const int64_t *d_qoff, int q_shared,
                                const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_qlen, int32_t max_rlen,
                                int32_t band, const int32_t *d_diag, pmx_record_t *d_out, pmx_stats_t *d_stats,
-                               char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st)
+                               char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st,
+                               int32_t *d_beg = nullptr /* two ints per pair: the first cell of each path (the search entries) */)
 {
     const bool want_cigar = (cfg->want & PMX_WANT_CIGAR) != 0, want_stats = (cfg->want & PMX_WANT_STATS) != 0;
     DevMat dm;
@@ -2945,10 +2948,11 @@ static int banded_trace_device(const pmx_config_t *cfg, int64_t n, const uint8_t
         if ((rc = chunk_sweep_launched(k)) != 0) return rc;
         if (want_stats)
             rc = pmx_launch_walkb(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0, band, dg,
-                                  d_out + c0, tr, nullptr, 0, nullptr, nullptr, nullptr, d_stats + c0, k.walk);
+                                  d_out + c0, tr, nullptr, 0, nullptr, nullptr, nullptr, d_stats + c0, k.walk, d_beg ? d_beg + 2 * c0 : nullptr);
         if (!rc && want_cigar)
             rc = pmx_launch_walkb(cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, dm.d, m, d_qbuf, qo, q_shared, d_rbuf, d_roff + c0, band, dg,
-                                  d_out + c0, tr, sq + c0, -c0, t.ops, t.nops + c0, t.textlen + c0, nullptr, k.walk);
+                                  d_out + c0, tr, sq + c0, -c0, t.ops, t.nops + c0, t.textlen + c0, nullptr, k.walk,
+                                  d_beg && !want_stats ? d_beg + 2 * c0 : nullptr);
         if (rc) { set_err("banded walk launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
         return chunk_walk_launched(k);
     });
@@ -2999,6 +3003,271 @@ extern "C" int pmx_align_batch_banded_cigar(const pmx_config_t *cfg, const paras
             HIP_OR_RET(hipDeviceSynchronize());
             return 0;
         });
+}
+
+// ==================================================================== profile database search ===
+// pmx_search_profile[_device]: the score-only first pass of pmx_align_profile_batch_device, the selection and the gather of
+// pmx_select.hip, the banded trace road above in its profile arm over the gathered hits (diag = end_ref - end_query of the first
+// pass), and the begins pmx_walkb_kernel leaves.  One stream synchronisation, between the passes: the host has to know the number of
+// hits and of their reference bytes to size the second pass.
+extern "C" int pmx_select_hits_device(const pmx_record_t *d_rec, int64_t n, int32_t min_score, int64_t max_hits, int order,
+                                      int64_t *d_hit_index, int64_t capacity, int64_t *d_counts, void *stream)
+{
+    if (n < 0 || max_hits < 0 || capacity < 0) { set_err("negative n, max_hits or capacity"); return -1; }
+    if (order != PMX_HITS_BY_INDEX && order != PMX_HITS_BY_SCORE) { set_err("bad hit order %d", order); return -1; }
+    if (!d_counts || (n > 0 && !d_rec) || (n > 0 && capacity > 0 && !d_hit_index)) { set_err("null buffer"); return -1; }
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    void *scr = nullptr;
+    if (scratch_reserve(pmx_select_scratch_bytes(n, max_hits, order), &scr, SCR_SEL)) return -1;
+    const int rc = pmx_launch_select(d_rec, n, min_score, max_hits, order, d_hit_index, capacity, d_counts, scr, (hipStream_t)stream);
+    if (rc) { set_err("hit selection failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
+    return 0;
+}
+
+extern "C" int pmx_gather_refs_device(const uint8_t *d_rbuf, const int64_t *d_roff, int64_t n, const int64_t *d_index, int64_t h,
+                                      uint8_t *d_out, int64_t out_capacity, int64_t *d_out_off, void *stream)
+{
+    if (n < 0 || h < 0 || out_capacity < 0) { set_err("negative n, h or out_capacity"); return -1; }
+    if (!d_out_off || (h > 0 && (!d_rbuf || !d_roff || !d_index || !d_out))) { set_err("null buffer"); return -1; }
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    int32_t *hlen = nullptr; void *scan = nullptr; const size_t scan_bytes = pmx_text_scan_scratch_bytes(h);
+    if (scratch_carve(SCR_SRCH, [&](Carver &c) { hlen = c.take<int32_t>((size_t)h + 2); scan = c.take<unsigned char>(scan_bytes); })) return -1;
+    int rc = pmx_launch_hit_lengths(d_index, nullptr, h, nullptr, d_roff, nullptr, hlen, st);
+    if (!rc) rc = pmx_launch_text_offsets(hlen, h, d_out_off, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_gather_refs(d_rbuf, d_roff, n, d_index, h, d_out, d_out_off, out_capacity, st);
+    if (rc) { set_err("reference gather failed (%d)", rc); return rc; }
+    return 0;
+}
+
+// Everything a search refuses, before any GPU work.
+static int search_check(const pmx_config_t *cfg, const parasail_profile_t *profile, const pmx_search_opts_t *opts, int64_t n, int64_t capacity)
+{
+    if (check_cfg(cfg)) return -1;
+    if (!profile) { set_err("null profile"); return -1; }
+    if (!opts) { set_err("null search options"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (opts->order != PMX_HITS_BY_INDEX && opts->order != PMX_HITS_BY_SCORE) { set_err("bad hit order %d", opts->order); return -1; }
+    if (opts->max_hits < 0) { set_err("negative max_hits"); return -1; }
+    if (capacity < 0) { set_err("negative hit capacity"); return -1; }
+    if (opts->band > 63) { set_err("the second pass of a search supports bands 0 .. 63 (got %d); band < 0: none", opts->band); return -1; }
+    if (opts->band >= 0 && banded_trace_check(cfg, opts->band)) return -1;
+    if (cfg->want & ~(PMX_WANT_CIGAR | PMX_WANT_STATS | PMX_WANT_SORTED)) { set_err("unknown want bits 0x%x", cfg->want); return -1; }
+    if (profile->matrix != cfg->matrix) { set_err("profile was built with a different matrix"); return -1; }
+    return pssm_batch_check(cfg->matrix, profile->s1Len, profile->s1Len);
+}
+
+// The hit list of a search on the device, between selection and second pass.  cap: the most hits that can be listed.
+struct SearchHits {
+    int64_t cap = 0, *idx = nullptr, *roff = nullptr, *counts = nullptr; int32_t *diag = nullptr, *hlen = nullptr, *beg = nullptr;
+    void *scan = nullptr; size_t scan_bytes = 0;
+    int64_t selected = 0, passing = 0, h = 0, bytes = 0;      // read back: counts, hits listed, their reference bytes
+};
+static thread_local int64_t *g_search_pin = nullptr;          // three int64 of page-locked memory for that read-back
+
+// Selection over the first pass's records, hit diagonals / lengths / offsets, and the one synchronisation.  d_counts: the caller's
+// counts, or NULL.
+static int search_select(int64_t n, const pmx_record_t *d_first, const int64_t *d_roff, const pmx_search_opts_t *opts, int64_t capacity,
+                         int64_t *d_counts, hipStream_t st, SearchHits *sh)
+{
+    sh->cap = std::min<int64_t>(std::min<int64_t>(n, capacity), opts->max_hits > 0 ? opts->max_hits : n);
+    const int64_t cap = sh->cap;
+    sh->scan_bytes = pmx_text_scan_scratch_bytes(cap);
+    void *sel = nullptr;
+    if (scratch_reserve(pmx_select_scratch_bytes(n, opts->max_hits, opts->order), &sel, SCR_SEL) ||
+        scratch_carve(SCR_SRCH, [&](Carver &c) {
+            sh->idx = c.take<int64_t>((size_t)cap); sh->roff = c.take<int64_t>((size_t)cap + 1); sh->counts = c.take<int64_t>(2);
+            sh->diag = c.take<int32_t>((size_t)cap); sh->hlen = c.take<int32_t>((size_t)cap + 2); sh->beg = c.take<int32_t>(2 * (size_t)cap);
+            sh->scan = c.take<unsigned char>(sh->scan_bytes);
+        })) return -1;
+    if (!g_search_pin) HIP_OR_RET(hipHostMalloc((void **)&g_search_pin, 3 * sizeof(int64_t), hipHostMallocDefault));
+    int64_t *counts = d_counts ? d_counts : sh->counts;
+    int rc = pmx_launch_select(d_first, n, opts->min_score, opts->max_hits, opts->order, sh->idx, cap, counts, sel, st);
+    if (!rc) rc = pmx_launch_hit_lengths(sh->idx, counts, cap, d_first, d_roff, sh->diag, sh->hlen, st);
+    if (!rc) rc = pmx_launch_text_offsets(sh->hlen, cap, sh->roff, sh->scan, sh->scan_bytes, st);
+    if (rc) { set_err("hit selection failed (%d)", rc); return rc; }
+    HIP_OR_RET(hipMemcpyAsync(g_search_pin, counts, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipMemcpyAsync(g_search_pin + 2, sh->roff + cap, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    sh->selected = g_search_pin[0]; sh->passing = g_search_pin[1]; sh->bytes = g_search_pin[2];
+    sh->h = std::min<int64_t>(sh->selected, cap);
+    return 0;
+}
+
+// The hit records and, with band >= 0, the second pass over the gathered references.  Asynchronous on `st`; may be run again (a
+// larger text buffer).
+static int search_second(const pmx_config_t *cfg, const parasail_profile_t *profile, const uint8_t *dq, int64_t n,
+                         const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen, const pmx_search_opts_t *opts,
+                         const pmx_record_t *d_first, const SearchHits &sh, pmx_hit_t *d_hits, pmx_record_t *d_recs, pmx_stats_t *d_stats,
+                         char *d_text, int64_t text_capacity, int64_t *d_text_off, hipStream_t st)
+{
+    const int64_t h = sh.h;
+    int rc = pmx_launch_hit_records(sh.idx, d_first, sh.diag, h, d_hits, st);
+    if (rc) { set_err("hit record launch failed (%d)", rc); return rc; }
+    if (opts->band < 0 || h == 0) {
+        if (d_text_off) HIP_OR_RET(hipMemsetAsync(d_text_off, 0, sizeof(int64_t) * (size_t)(h + 1), st));
+        return 0;
+    }
+    uint8_t *gref = nullptr;
+    if (scratch_reserve((size_t)sh.bytes + 16, (void **)&gref, SCR_GREF)) return -1;      // (the padding of the host entries' staged references)
+    rc = pmx_launch_gather_refs(d_rbuf, d_roff, n, sh.idx, h, gref, sh.roff, sh.bytes, st);
+    if (rc) { set_err("reference gather failed (%d)", rc); return rc; }
+    const char *first_kernel = g_last_kernel;
+    rc = banded_trace_device(cfg, h, dq, nullptr, profile->s1Len, gref, sh.roff, profile->s1Len, max_rlen, opts->band, sh.diag,
+                             d_recs, d_stats, d_text, text_capacity, d_text_off, st, sh.beg);
+    if (rc) return rc;
+    static thread_local char name[256];
+    if (first_kernel != name) {
+        char both[256];
+        snprintf(both, sizeof both, "%s + pmx_select + pmx_gather_refs_kernel + %s", first_kernel, g_last_kernel);
+        memcpy(name, both, sizeof name);
+    }
+    g_last_kernel = name;
+    rc = pmx_launch_hit_begins(sh.beg, h, d_hits, st);
+    if (rc) { set_err("hit begin launch failed (%d)", rc); return rc; }
+    return 0;
+}
+
+extern "C" int pmx_search_profile_device(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                                         const uint8_t *d_rbuf, const int64_t *d_roff, int32_t max_rlen, const pmx_search_opts_t *opts,
+                                         pmx_record_t *d_first, pmx_hit_t *d_hits, pmx_record_t *d_recs, pmx_stats_t *d_stats, int64_t capacity,
+                                         char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, int64_t *d_counts, void *stream)
+{
+    if (search_check(cfg, profile, opts, n, capacity)) return -1;
+    if (!d_counts || (capacity > 0 && !d_hits)) { set_err("null buffer"); return -1; }
+    const bool second = opts->band >= 0;
+    if (second && capacity > 0 && (!d_recs || traced_outputs_check(cfg, d_stats, d_cigar_text, d_cigar_off, false))) {
+        if (!d_recs) set_err("null buffer");
+        return -1;
+    }
+    if (second && cigar_capacity < 0) { set_err("negative cigar_capacity"); return -1; }
+    if (n > 0 && (!d_rbuf || !d_roff)) { set_err("null buffer"); return -1; }
+    if (n > 0 && max_rlen <= 0) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    if (n == 0) {
+        HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), st));
+        if (d_cigar_off) HIP_OR_RET(hipMemsetAsync(d_cigar_off, 0, sizeof(int64_t), st));
+        return 0;
+    }
+    const uint8_t *dq = nullptr;
+    if (profile_device_query(profile, &dq)) return -1;
+    if (!d_first && scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&d_first, SCR_HREC)) return -1;
+    pmx_config_t cfg1 = *cfg;
+    cfg1.want &= PMX_WANT_SORTED;
+    int rc = run_batch_device(&cfg1, n, dq, nullptr, profile->s1Len, d_rbuf, d_roff, profile->s1Len, max_rlen, d_first, nullptr, stream,
+                              profile_has_wildcard(profile));
+    if (rc) return rc;
+    SearchHits sh;
+    if ((rc = search_select(n, d_first, d_roff, opts, capacity, d_counts, st, &sh)) != 0) return rc;
+    return search_second(cfg, profile, dq, n, d_rbuf, d_roff, max_rlen, opts, d_first, sh, d_hits, d_recs, d_stats,
+                         d_cigar_text, cigar_capacity, d_cigar_off, st);
+}
+
+extern "C" void pmx_search_result_free(pmx_search_result_t *result) { free(result); }
+
+extern "C" int pmx_search_profile(const pmx_config_t *cfg, const parasail_profile_t *profile, int64_t n,
+                                  const uint8_t *rbuf, const int64_t *roff, const pmx_search_opts_t *opts, pmx_search_result_t **result)
+{
+    if (!result) { set_err("null result pointer"); return -1; }
+    *result = nullptr;
+    if (search_check(cfg, profile, opts, n, 0)) return -1;
+    if (n > 0 && (!rbuf || !roff)) { set_err("null buffer"); return -1; }
+    const bool second = opts->band >= 0;
+    const bool want_cigar = second && (cfg->want & PMX_WANT_CIGAR), want_stats = second && (cfg->want & PMX_WANT_STATS);
+    // the result: one block -- header, hits, records, statistics, offsets, text
+    auto publish = [&](int64_t h, int64_t passing, int64_t text_bytes, pmx_search_result_t **out) -> int {
+        auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        const size_t o_hits = up(sizeof(pmx_search_result_t)), o_recs = o_hits + up(sizeof(pmx_hit_t) * (size_t)h);
+        const size_t o_stats = o_recs + (second ? up(sizeof(pmx_record_t) * (size_t)h) : 0);
+        const size_t o_off = o_stats + (want_stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0);
+        const size_t o_text = o_off + up(sizeof(int64_t) * (size_t)(h + 1)), total = o_text + (want_cigar ? (size_t)text_bytes + 1 : 0);
+        char *blk = (char *)calloc(1, total);
+        if (!blk) { set_err("out of memory"); return -1; }
+        pmx_search_result_t *r = (pmx_search_result_t *)blk;
+        r->n_hits = h; r->n_passing = passing;
+        r->hits = (pmx_hit_t *)(blk + o_hits);
+        r->recs = second ? (pmx_record_t *)(blk + o_recs) : nullptr;
+        r->stats = want_stats ? (pmx_stats_t *)(blk + o_stats) : nullptr;
+        r->cigar_off = (int64_t *)(blk + o_off);
+        r->cigar = want_cigar ? blk + o_text : nullptr;
+        *out = r;
+        return 0;
+    };
+    if (n == 0) return publish(0, 0, 0, result);
+    int32_t mr = 0, mnr = 0; bool bad = false;
+    host_maxlens(n, roff, &mr, &bad, &mnr);
+    if (bad || roff[0] != 0) { set_err("bad reference offsets"); return -1; }
+    pmx_config_t cfg1 = with_sort_hint(cfg, mnr, mr, n);
+    cfg1.want &= PMX_WANT_SORTED;
+    const uint8_t *dq = nullptr;
+    if (profile_device_query(profile, &dq)) return -1;
+    // the references go up once, in slices behind which the first pass runs (as in pmx_align_profile_batch), and stay for the gather
+    const size_t rbytes = (size_t)roff[n];
+    uint8_t *dr = nullptr; int64_t *dro = nullptr; pmx_record_t *dfirst = nullptr;
+    if (scratch_reserve(rbytes + 16, (void **)&dr, SCR_HR) || scratch_reserve(sizeof(int64_t) * (n + 1), (void **)&dro, SCR_HRO) ||
+        scratch_reserve(sizeof(pmx_record_t) * n, (void **)&dfirst, SCR_HREC)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t s_copy = hs.copy, s_comp = hs.comp;
+    StreamGuard guard(s_comp);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    const int K = rbytes >= ((size_t)64 << 20) ? (int)std::max<int64_t>(1, std::min<int64_t>(8, n / 32768)) : 1;
+    HIP_OR_RET(hipMemcpyAsync(dro, roff, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_copy));
+    const int wild = profile_has_wildcard(profile);
+    int64_t a = 0;
+    for (int sl = 0; sl < K; ++sl) {
+        int64_t e = n;
+        if (sl + 1 < K) {
+            e = std::lower_bound(roff, roff + n + 1, (int64_t)(rbytes / K) * (sl + 1)) - roff;
+            e = std::min<int64_t>(std::max<int64_t>(e, a), n);
+        }
+        if (e <= a) continue;
+        HIP_OR_RET(hipMemcpyAsync(dr + roff[a], rbuf + roff[a], (size_t)(roff[e] - roff[a]), hipMemcpyHostToDevice, s_copy));
+        HIP_OR_RET(hipEventRecord(hs.up[sl], s_copy));
+        HIP_OR_RET(hipStreamWaitEvent(s_comp, hs.up[sl], 0));
+        const int rc = run_batch_device(&cfg1, e - a, dq, nullptr, profile->s1Len, dr, dro + a, profile->s1Len, mr, dfirst + a, nullptr, s_comp, wild);
+        if (rc) { (void)hipStreamSynchronize(s_comp); (void)hipStreamSynchronize(s_copy); return rc; }
+        a = e;
+    }
+    SearchHits sh;
+    int rc = search_select(n, dfirst, dro, opts, n, nullptr, s_comp, &sh);
+    if (rc) { (void)hipStreamSynchronize(s_comp); return rc; }
+    const int64_t h = sh.h;
+    // text capacity as in traced_host_batch: half a byte per symbol + 16 per hit; a search that needs more runs its second pass again
+    int64_t capacity = want_cigar ? (((int64_t)h * profile->s1Len + sh.bytes) / 2 + 16 * h + 256) : 0;
+    DevBuf<pmx_hit_t> dhits; DevBuf<pmx_record_t> drecs; DevBuf<pmx_stats_t> dst; DevBuf<char> dtext; DevBuf<int64_t> dtoff;
+    if (dhits.try_alloc(h) || dtoff.try_alloc(h + 1) || (second && drecs.try_alloc(h)) || (want_stats && dst.try_alloc(h)) ||
+        (want_cigar && dtext.try_alloc((size_t)capacity + 1))) { set_err("out of device memory"); return -2; }
+    std::vector<int64_t> toff((size_t)h + 1, 0);
+    for (int pass = 0; pass < 2; ++pass) {
+        rc = search_second(cfg, profile, dq, n, dr, dro, mr, opts, dfirst, sh, dhits.p, drecs.p, dst.p, dtext.p, capacity,
+                           want_cigar ? dtoff.p : nullptr, s_comp);
+        if (rc) { (void)hipStreamSynchronize(s_comp); return rc; }
+        HIP_OR_RET(hipStreamSynchronize(s_comp));
+        if (!want_cigar) break;
+        HIP_OR_RET(hipMemcpy(toff.data(), dtoff.p, sizeof(int64_t) * (size_t)(h + 1), hipMemcpyDeviceToHost));
+        if (toff[h] <= capacity) break;
+        capacity = toff[h];
+        (void)hipFree(dtext.p); dtext.p = nullptr;
+        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    }
+    pmx_search_result_t *r = nullptr;
+    if (publish(h, sh.passing, toff[h], &r)) return -1;
+    hipError_t e = hipSuccess;
+    if (h) {
+        e = hipMemcpy(r->hits, dhits.p, sizeof(pmx_hit_t) * (size_t)h, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && second) e = hipMemcpy(r->recs, drecs.p, sizeof(pmx_record_t) * (size_t)h, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && want_stats) e = hipMemcpy(r->stats, dst.p, sizeof(pmx_stats_t) * (size_t)h, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && want_cigar && toff[h]) e = hipMemcpy(r->cigar, dtext.p, (size_t)toff[h], hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) { free(r); set_err("%s", hipGetErrorString(e)); return -(int)e; }
+    memcpy(r->cigar_off, toff.data(), sizeof(int64_t) * (size_t)(h + 1));
+    *result = r;
+    return 0;
 }
 
 // ==================================================================== long pairs: traceback in linear memory ===

@@ -207,7 +207,7 @@ int pmx_launch_walkb(int mode, int sg_flags, int open, int ext, const PmxDevMatr
                      const uint8_t *qbuf, const int64_t *qoff, int q_shared, const uint8_t *rbuf, const int64_t *roff,
                      int band, const int32_t *diag, const pmx_record_t *recs, const PmxBandTrace &tr,
                      const int64_t *slot_qoff, long long ops_base, uint32_t *ops, int32_t *nops, int32_t *textlen,
-                     pmx_stats_t *stats_out, hipStream_t stream);
+                     pmx_stats_t *stats_out, hipStream_t stream, int32_t *beg = nullptr /* two ints per pair: the path's first cell */);
 // off[k] = k * qlen, k = 0 .. n: the query offsets a shared query stands for (slot placement of the profile arm).
 int pmx_launch_shared_offsets(int64_t *off, long long n, int qlen, hipStream_t stream);
 // Band-strip kernel (pmx_bstrip.hip): band coordinates, packed int16, alphabets of <= 4 letters (+ wildcard).  Same contract.
@@ -242,6 +242,19 @@ size_t pmx_text_scan_scratch_bytes(long long n);
 int pmx_launch_text_offsets(const int32_t *textlen, long long n, int64_t *text_off, void *scratch, size_t scratch_bytes, hipStream_t stream);
 int pmx_launch_cigar_render_slots(const uint32_t *ops, const int64_t *qoff, const int64_t *roff, long long ops_base, const int32_t *nops,
                                   const int64_t *text_off, char *text, long long capacity, long long n, hipStream_t stream);
+
+// Hit selection and reference gather of the profile search (pmx_select.hip; semantics: include/parasail_amd.h).  `scratch` holds
+// pmx_select_scratch_bytes() bytes.  All asynchronous on `stream`; 0 launched, <0 HIP error.
+size_t pmx_select_scratch_bytes(long long n, long long max_hits, int order);
+int pmx_launch_select(const pmx_record_t *recs, long long n, int min_score, long long max_hits, int order,
+                      int64_t *hit_index, long long capacity, int64_t *counts, void *scratch, hipStream_t stream);
+// diag[p] = end_ref - end_query and hlen[p] = reference length of hit idx[p], p < min(counts[0], cap); 0 up to hlen[cap + 1]
+int pmx_launch_hit_lengths(const int64_t *idx, const int64_t *counts, long long cap, const pmx_record_t *recs, const int64_t *roff,
+                           int32_t *diag, int32_t *hlen, hipStream_t stream);
+int pmx_launch_hit_records(const int64_t *idx, const pmx_record_t *recs, const int32_t *diag, long long h, pmx_hit_t *hits, hipStream_t stream);
+int pmx_launch_hit_begins(const int32_t *beg, long long h, pmx_hit_t *hits, hipStream_t stream);
+int pmx_launch_gather_refs(const uint8_t *rbuf, const int64_t *roff, long long n, const int64_t *idx, long long h,
+                           uint8_t *out, const int64_t *ooff, long long out_cap, hipStream_t stream);
 
 // One long pair (or a few) across the chip: bands of the query on different CUs, pipelined through HBM granules (pmx_long.hip).
 // R = rows per lane (4 or 16).  0 launched, 1 not eligible, <0 HIP error; `scratch` holds pmx_long_scratch_bytes() bytes.

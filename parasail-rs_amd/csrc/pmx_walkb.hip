@@ -19,7 +19,9 @@
 #define OP_FOR_DEL_STATE PMX_BAM_OP_FOR_DEL_STATE    // include/pmx_conventions.h
 #define B_NEG (INT32_MIN / 2)
 
-template <bool ST, bool SW>
+// BG: also the cell where the walk stops -- the path's first cell (beg_query, beg_ref of oracle/pmx_oracle.c:orc_walk; 0 / 0 once a global
+// or semi-global path has used up a sequence; -1 / -1 without a path) -- two ints per pair.  Without BG `beg` is not looked at.
+template <bool ST, bool SW, bool BG>
 __global__ __launch_bounds__(256)
 void pmx_walkb_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, int q_shared,
                       const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff, long long n,
@@ -27,7 +29,8 @@ void pmx_walkb_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
                       int mode, int row_pen, int col_pen, int band, const int32_t *__restrict__ diag,
                       const pmx_record_t *__restrict__ recs, PmxBandTrace tr, int LP,
                       const int64_t *__restrict__ slot_qoff, long long ops_base, uint32_t *__restrict__ ops,
-                      int32_t *__restrict__ nops, int32_t *__restrict__ textlen, pmx_stats_t *__restrict__ stats_out)
+                      int32_t *__restrict__ nops, int32_t *__restrict__ textlen, pmx_stats_t *__restrict__ stats_out,
+                      int32_t *__restrict__ beg)
 {
     __shared__ unsigned char s_map[256];
     __shared__ int16_t s_scores[PMX_MAX_FAST_MSIZE * PMX_MAX_FAST_MSIZE];
@@ -58,6 +61,7 @@ void pmx_walkb_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     uint32_t *o_end = ST ? nullptr : ops + (slot_qoff[k + 1] + roff[k + 1] + k + 1 - ops_base);
     int cnt = 0, tlen = 0, nM = 0, nS = 0, nL = 0;
     uint32_t cur_op = 0, cur_len = 0;
+    int bi = -1, bj = -1;
     auto digits = [](uint32_t v) -> int { int d = 1; while (v >= 10) { v /= 10; ++d; } return d; };
     auto flush = [&]() { if (cur_len) { ++cnt; o_end[-cnt] = (cur_len << 4) | cur_op; tlen += digits(cur_len) + 1; } };
     auto add_run = [&](uint32_t op, int len) {
@@ -108,7 +112,12 @@ void pmx_walkb_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
                 --i;
             }
         }
+        if (BG) {
+            if (!SW && (i < 0 || j < 0)) i = j = -1;      // (the boundary gap run went to the matrix's corner)
+            bi = i + 1; bj = j + 1;
+        }
     }
+    if (BG) { beg[2 * k] = bi; beg[2 * k + 1] = bj; }
     if (ST) { pmx_stats_t s3; s3.matches = nM; s3.similar = nS; s3.length = nL; stats_out[k] = s3; return; }
     flush();
     nops[k] = cnt;
@@ -119,7 +128,7 @@ int pmx_launch_walkb(int mode, int sg_flags, int open, int ext, const PmxDevMatr
                      const uint8_t *qbuf, const int64_t *qoff, int q_shared, const uint8_t *rbuf, const int64_t *roff,
                      int band, const int32_t *diag, const pmx_record_t *recs, const PmxBandTrace &tr,
                      const int64_t *slot_qoff, long long ops_base, uint32_t *ops, int32_t *nops, int32_t *textlen,
-                     pmx_stats_t *stats_out, hipStream_t stream)
+                     pmx_stats_t *stats_out, hipStream_t stream, int32_t *beg)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (n <= 0) return 0;
@@ -128,12 +137,14 @@ int pmx_launch_walkb(int mode, int sg_flags, int open, int ext, const PmxDevMatr
     const int row_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_DB));   // H(-1, j) penalised
     const int LP = pmx_bandtr_geometry_of(1, 1, band).LP;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define WB(STV, SWV) hipLaunchKernelGGL((pmx_walkb_kernel<STV, SWV>), grid, block, 0, stream, qbuf, qoff, q_shared, rbuf, roff, n, \
-        m.mapper, m.scores, m.msize, open, ext, mode, row_pen, col_pen, band, diag, recs, tr, LP, slot_qoff, ops_base, ops, nops, textlen, stats_out)
+#define WB2(STV, SWV, BGV) hipLaunchKernelGGL((pmx_walkb_kernel<STV, SWV, BGV>), grid, block, 0, stream, qbuf, qoff, q_shared, rbuf, roff, n, \
+        m.mapper, m.scores, m.msize, open, ext, mode, row_pen, col_pen, band, diag, recs, tr, LP, slot_qoff, ops_base, ops, nops, textlen, stats_out, beg)
+#define WB(STV, SWV) do { if (beg) WB2(STV, SWV, true); else WB2(STV, SWV, false); } while (0)
     const bool sw = mode == PMX_MODE_SW;
     if (stats_out) { if (sw) WB(true, true); else WB(true, false); }
     else { if (sw) WB(false, true); else WB(false, false); }
 #undef WB
+#undef WB2
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
 }
