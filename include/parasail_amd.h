@@ -400,6 +400,77 @@ int pmx_search_profile_device(const pmx_config_t *cfg, const parasail_profile_t 
                               pmx_record_t *d_first, pmx_hit_t *d_hits, pmx_record_t *d_recs, pmx_stats_t *d_stats, int64_t capacity,
                               char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, int64_t *d_counts, void *stream);
 
+/* Sequence-set batches (extension): sequence sets that live on the device, batches whose pairs are index + window descriptors into
+ * those sets, and an all-vs-all entry that enumerates its pairs on the device.  A read aligned against several windows of a resident
+ * reference, or a set compared with itself, moves 32 bytes per pair over the link instead of both sequences once per pair.
+ *
+ * Sets.  pmx_seqset_create uploads a packed buffer (sequence k is buf[off[k] .. off[k + 1]), off non-decreasing from off[0] >= 0)
+ * and keeps a host copy of the offsets (8 bytes per sequence) for validation.  pmx_seqset_wrap_device copies nothing: d_buf (`bytes`
+ * bytes) and d_off (count + 1 entries) are the caller's device buffers and must outlive the set.  A set belongs to the device current
+ * at its creation.  NULL on failure (pmx_last_error() tells why).
+ *
+ * Results.  Record k is the record pmx_align_batch_device gives for the pair (query window, reference window) of descriptor k: the
+ * same score, the same end positions RELATIVE TO THE WINDOWS, the same flags, and the same statistics with PMX_WANT_STATS.  Every
+ * mode, width and matrix pmx_align_batch_device takes is taken, a PSSM under its rule (every query window has the PSSM's length;
+ * device entries: max_qlen == that length).  PMX_WANT_SORTED is passed on; PMX_WANT_CIGAR is refused.  Q and R may be the same set.
+ * Records are in pair order whatever the chunking: inside, the batch is cut into chunks of opts->chunk_pairs pairs (0 / NULL: a
+ * default derived from the maxima) whose windows a gather kernel packs into chunk buffers beside the previous chunk's alignment.
+ * chunk_pairs never changes a result.
+ *
+ * Bad descriptors: an index outside its set, beg < 0, a len below -1, a window reaching past the sequence's end, a resolved length
+ * of 0, a resolved length above max_qlen / max_rlen (device entries).  The device entries give a bad pair the record
+ * {0, -1, -1, PMX_FLAG_BAD_PAIR} and zero statistics; every other pair is unaffected and no byte outside a set's buffer is read (a
+ * wrapped set's offsets are checked against `bytes` too).  The host entries refuse the call with -1 and a pmx_last_error() text that
+ * names the first bad pair: before any GPU work when both sets carry host offsets, otherwise after the device pass has flagged it
+ * (`out` is then unspecified).
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: NULL sets or pairs; negative n, first or count; first + count
+ * beyond pmx_all_pairs_count(); a set of more than 2^31 - 1 sequences in the all-pairs entries; chunk_pairs < 0; max_qlen / max_rlen /
+ * max_len < 1; a set of another device than the current one; what pmx_align_batch_device refuses.  n == 0 / count == 0 succeeds and
+ * touches nothing.
+ *
+ * The device entries are asynchronous on `stream` (all pointers but the sets, cfg and opts are device pointers): a call whose scratch is
+ * already large enough returns without a host synchronisation; the first call of a thread, and one that needs more scratch than any
+ * before it, allocate, which synchronises.  Scratch belongs to the calling thread like that of the other device entries: two sets of
+ * chunk buffers of at most 256 MiB each (one chunk of one pair when a single pair needs more) and 41 bytes per pair of a chunk.
+ * pmx_last_kernel() names the alignment kernel the last chunk ran. */
+typedef struct pmx_seqset pmx_seqset_t;
+pmx_seqset_t *pmx_seqset_create(const uint8_t *buf, const int64_t *off, int64_t count);
+pmx_seqset_t *pmx_seqset_wrap_device(const uint8_t *d_buf, const int64_t *d_off, int64_t count, int64_t bytes);
+void    pmx_seqset_free(pmx_seqset_t *set);
+int64_t pmx_seqset_count(const pmx_seqset_t *set);          /* -1 for NULL */
+
+typedef struct pmx_pair {            /* 32 bytes */
+    int64_t q, r;                    /* sequence index in the query set / the reference set */
+    int32_t q_beg, q_len;            /* window inside that sequence; len -1 = from beg to its end */
+    int32_t r_beg, r_len;
+} pmx_pair_t;
+typedef struct pmx_pairs_opts { int64_t chunk_pairs; } pmx_pairs_opts_t;   /* 0 / NULL = default */
+
+#define PMX_FLAG_BAD_PAIR 8  /* result record flag of the set-batch device entries: the descriptor was bad, nothing was aligned */
+
+int pmx_align_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                    int64_t n, const pmx_pair_t *pairs,
+                    pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */, const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                           int64_t n, const pmx_pair_t *d_pairs, int32_t max_qlen, int32_t max_rlen,
+                           pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream,
+                           const pmx_pairs_opts_t *opts);
+
+/* All-vs-all: pairs [first, first + count) of the strict upper triangle of S x S in row-major order,
+ * p = i (2 N - i - 1) / 2 + (j - i - 1) with i < j; query = sequence i, reference = sequence j, whole sequences.  The descriptors are
+ * generated on the device chunk by chunk: nothing but the records crosses the link.  pmx_all_pairs_count: N (N - 1) / 2, or -1 for
+ * N < 0 or N > 2^31 - 1.  pmx_all_pairs_index: the exact (i, j) of pair p on the host; -1 for p outside [0, count). */
+int64_t pmx_all_pairs_count(int64_t nseq);
+int pmx_all_pairs_index(int64_t nseq, int64_t p, int64_t *i, int64_t *j);
+int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
+                        pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts);
+int pmx_align_all_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
+                               int32_t max_len, pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream,
+                               const pmx_pairs_opts_t *opts);
+/* Test hook: the descriptors the all-pairs entries generate, `count` of them into d_pairs; asynchronous on `stream`. */
+int pmx_all_pairs_enumerate_device(int64_t nseq, int64_t first, int64_t count, pmx_pair_t *d_pairs, void *stream);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -108,8 +108,66 @@ pub const PMX_WANT_STATS: c_int = 1;
 pub const PMX_WANT_CIGAR: c_int = 2;
 pub const PMX_WANT_SORTED: c_int = 4;
 
+/// One pair of a sequence-set batch (`pmx_pair_t`, 32 bytes): sequence indices and windows; a length of -1 runs to the sequence's end.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct PmxPair {
+    pub q: i64,
+    pub r: i64,
+    pub q_beg: i32,
+    pub q_len: i32,
+    pub r_beg: i32,
+    pub r_len: i32,
+}
+
+impl PmxPair {
+    /// Whole sequences `q` and `r`.
+    pub fn whole(q: i64, r: i64) -> PmxPair {
+        PmxPair { q, r, q_beg: 0, q_len: -1, r_beg: 0, r_len: -1 }
+    }
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct PmxPairsOpts {
+    pub chunk_pairs: i64, // 0 = default; never changes a result
+}
+
+/// Record flag of the set-batch device entries: the descriptor was bad, nothing was aligned.
+pub const PMX_FLAG_BAD_PAIR: i32 = 8;
+
+/// Opaque `pmx_seqset_t`.
+#[repr(C)]
+pub struct PmxSeqSet {
+    _private: [u8; 0],
+}
+
 #[link(name = "parasail_amd")]
 extern "C" {
+    fn pmx_seqset_create(buf: *const u8, off: *const i64, count: i64) -> *mut PmxSeqSet;
+    fn pmx_seqset_wrap_device(d_buf: *const u8, d_off: *const i64, count: i64, bytes: i64) -> *mut PmxSeqSet;
+    fn pmx_seqset_free(set: *mut PmxSeqSet);
+    fn pmx_seqset_count(set: *const PmxSeqSet) -> i64;
+    fn pmx_align_pairs(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, n: i64, pairs: *const PmxPair,
+        out: *mut PmxRecord, stats_out: *mut PmxStats, opts: *const PmxPairsOpts,
+    ) -> c_int;
+    pub fn pmx_align_pairs_device(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, n: i64, d_pairs: *const PmxPair,
+        max_qlen: i32, max_rlen: i32, d_out: *mut PmxRecord, d_stats_out: *mut PmxStats, stream: *mut c_void,
+        opts: *const PmxPairsOpts,
+    ) -> c_int;
+    fn pmx_all_pairs_count(nseq: i64) -> i64;
+    fn pmx_all_pairs_index(nseq: i64, p: i64, i: *mut i64, j: *mut i64) -> c_int;
+    fn pmx_align_all_pairs(
+        cfg: *const PmxConfig, s: *const PmxSeqSet, first: i64, count: i64,
+        out: *mut PmxRecord, stats_out: *mut PmxStats, opts: *const PmxPairsOpts,
+    ) -> c_int;
+    pub fn pmx_align_all_pairs_device(
+        cfg: *const PmxConfig, s: *const PmxSeqSet, first: i64, count: i64, max_len: i32,
+        d_out: *mut PmxRecord, d_stats_out: *mut PmxStats, stream: *mut c_void, opts: *const PmxPairsOpts,
+    ) -> c_int;
+    pub fn pmx_all_pairs_enumerate_device(nseq: i64, first: i64, count: i64, d_pairs: *mut PmxPair, stream: *mut c_void) -> c_int;
     fn pmx_align_batch(
         cfg: *const PmxConfig, n: i64,
         qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
@@ -344,6 +402,69 @@ fn last_error() -> Error {
     Error::Batch(unsafe { CStr::from_ptr(pmx_last_error()) }.to_string_lossy().into_owned())
 }
 
+/// A set of sequences resident on the device current at its creation (`pmx_seqset_t`), released on drop.
+pub struct SeqSet {
+    inner: *mut PmxSeqSet,
+}
+
+impl SeqSet {
+    /// Uploads the packed sequences once.
+    pub fn new(seqs: &Packed) -> Result<SeqSet> {
+        let inner = unsafe { pmx_seqset_create(seqs.buf.as_ptr(), seqs.off.as_ptr(), seqs.len() as i64) };
+        if inner.is_null() {
+            return Err(last_error());
+        }
+        Ok(SeqSet { inner })
+    }
+    /// No copy: the caller's device buffers (`d_off`: `count + 1` entries).
+    ///
+    /// # Safety
+    /// Both buffers are device memory of the current device and outlive the set.
+    pub unsafe fn wrap_device(d_buf: *const u8, d_off: *const i64, count: i64, bytes: i64) -> Result<SeqSet> {
+        let inner = pmx_seqset_wrap_device(d_buf, d_off, count, bytes);
+        if inner.is_null() {
+            return Err(last_error());
+        }
+        Ok(SeqSet { inner })
+    }
+    pub fn len(&self) -> usize {
+        unsafe { pmx_seqset_count(self.inner) as usize }
+    }
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+    /// For the `_device` entries.
+    pub fn as_ptr(&self) -> *const PmxSeqSet {
+        self.inner
+    }
+}
+
+impl Drop for SeqSet {
+    fn drop(&mut self) {
+        unsafe { pmx_seqset_free(self.inner) }
+    }
+}
+
+unsafe impl Send for SeqSet {}
+
+/// Pairs of the strict upper triangle of `nseq x nseq`.
+pub fn all_pairs_count(nseq: i64) -> Result<i64> {
+    let v = unsafe { pmx_all_pairs_count(nseq) };
+    if v < 0 {
+        return Err(last_error());
+    }
+    Ok(v)
+}
+
+/// `(i, j)`, `i < j`, of pair `p` in the row-major order of `Aligner::align_all_pairs`.
+pub fn all_pairs_index(nseq: i64, p: i64) -> Result<(i64, i64)> {
+    let (mut i, mut j) = (0i64, 0i64);
+    if unsafe { pmx_all_pairs_index(nseq, p, &mut i, &mut j) } != 0 {
+        return Err(last_error());
+    }
+    Ok((i, j))
+}
+
 impl Aligner {
     fn pmx_config(&self, want: c_int) -> PmxConfig {
         PmxConfig {
@@ -517,6 +638,44 @@ impl Aligner {
                                       devices.as_ptr(), devices.len() as c_int, records.as_mut_ptr(), stats_ptr)
             }
         };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok(BatchResult { records, stats })
+    }
+
+    /// Pairs by index and window into device-resident sets (`q` may be `r`): record k belongs to the pair (query window, reference
+    /// window) k, end positions relative to the windows.  A bad descriptor is an error that names the first.
+    pub fn align_pairs(&self, q: &SeqSet, r: &SeqSet, pairs: &[PmxPair], chunk_pairs: i64) -> Result<BatchResult> {
+        assert!(self.profile.is_null(), "align_pairs takes no profile");
+        let n = pairs.len();
+        let mut records = vec![PmxRecord::default(); n];
+        let mut stats = if self.want_stats { Some(vec![PmxStats::default(); n]) } else { None };
+        let stats_ptr = stats.as_mut().map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let cfg = self.pmx_config(if self.want_stats { PMX_WANT_STATS } else { 0 });
+        let opts = PmxPairsOpts { chunk_pairs };
+        let rc = unsafe { pmx_align_pairs(&cfg, q.inner, r.inner, n as i64, pairs.as_ptr(), records.as_mut_ptr(), stats_ptr, &opts) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok(BatchResult { records, stats })
+    }
+
+    /// Pairs `[first, first + count)` of the strict upper triangle of `s x s` (row-major, `all_pairs_index`), whole sequences,
+    /// enumerated on the device.  `count` `None`: to the last pair.
+    pub fn align_all_pairs(&self, s: &SeqSet, first: i64, count: Option<i64>, chunk_pairs: i64) -> Result<BatchResult> {
+        assert!(self.profile.is_null(), "align_all_pairs takes no profile");
+        let count = match count {
+            Some(c) => c,
+            None => all_pairs_count(s.len() as i64)? - first,
+        };
+        let n = count.max(0) as usize;
+        let mut records = vec![PmxRecord::default(); n];
+        let mut stats = if self.want_stats { Some(vec![PmxStats::default(); n]) } else { None };
+        let stats_ptr = stats.as_mut().map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let cfg = self.pmx_config(if self.want_stats { PMX_WANT_STATS } else { 0 });
+        let opts = PmxPairsOpts { chunk_pairs };
+        let rc = unsafe { pmx_align_all_pairs(&cfg, s.inner, first, count, records.as_mut_ptr(), stats_ptr, &opts) };
         if rc != 0 {
             return Err(last_error());
         }

@@ -76,16 +76,27 @@ class pmx_search_result_t(C.Structure):
                 ("stats", C.c_void_p), ("cigar", C.c_void_p), ("cigar_off", C.c_void_p)]
 
 
+class pmx_pair_t(C.Structure):
+    _fields_ = [("q", C.c_int64), ("r", C.c_int64), ("q_beg", C.c_int32), ("q_len", C.c_int32),
+                ("r_beg", C.c_int32), ("r_len", C.c_int32)]
+
+
+class pmx_pairs_opts_t(C.Structure):
+    _fields_ = [("chunk_pairs", C.c_int64)]
+
+
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
 STATS_DTYPE = np.dtype([("matches", "<i4"), ("similar", "<i4"), ("length", "<i4")])
 HIT_DTYPE = np.dtype([("index", "<i8"), ("first", RECORD_DTYPE), ("diag", "<i4"), ("beg_query", "<i4"), ("beg_ref", "<i4"),
                       ("reserved", "<i4")])
 HITS_BY_INDEX, HITS_BY_SCORE = 0, 1
+PAIR_DTYPE = np.dtype([("q", "<i8"), ("r", "<i8"), ("q_beg", "<i4"), ("q_len", "<i4"), ("r_beg", "<i4"), ("r_len", "<i4")])
 
 MODE_NW, MODE_SG, MODE_SW = 0, 1, 2
 SG_QB, SG_QE, SG_DB, SG_DE, SG_ALL = 1, 2, 4, 8, 15
 WANT_STATS, WANT_CIGAR, WANT_SORTED = 1, 2, 4
 FLAG_SATURATED = 1
+FLAG_BAD_PAIR = 8
 
 _MP = C.POINTER(parasail_matrix_t)
 _FN = C.CFUNCTYPE(C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, _MP)
@@ -190,6 +201,21 @@ _sig("pmx_search_result_free", None, C.POINTER(pmx_search_result_t))
 _sig("pmx_search_profile_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
      C.POINTER(pmx_search_opts_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
      C.c_void_p, C.c_void_p)
+_sig("pmx_seqset_create", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
+_sig("pmx_seqset_wrap_device", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64)
+_sig("pmx_seqset_free", None, C.c_void_p)
+_sig("pmx_seqset_count", C.c_int64, C.c_void_p)
+_sig("pmx_align_pairs", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_all_pairs_count", C.c_int64, C.c_int64)
+_sig("pmx_all_pairs_index", C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+_sig("pmx_align_all_pairs", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_all_pairs_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_all_pairs_enumerate_device", C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -814,6 +840,42 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return (out, stats) if stats is not None else out
 
+    def align_pairs(self, Q, R, pairs, chunk_pairs=0):
+        """Pairs by index and window into device-resident sequence sets (SeqSet; Q may be R).  `pairs`: a PAIR_DTYPE array, or
+        an iterable of (q, r) / (q, r, q_beg, q_len, r_beg, r_len) tuples (len -1: to the sequence's end).  Record k is the record
+        of the pair (query window, reference window) k, end positions relative to the windows.  A bad descriptor raises BatchError
+        naming the first."""
+        if not self._profile.is_null():
+            raise BatchError("align_pairs takes no profile")
+        pairs = as_pairs(pairs)
+        n = len(pairs)
+        cfg = self._config()
+        out = np.zeros(n, dtype=RECORD_DTYPE)
+        stats = np.zeros(n, dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
+        opts = pmx_pairs_opts_t(int(chunk_pairs))
+        rc = lib.pmx_align_pairs(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, out.ctypes.data,
+                                 stats.ctypes.data if stats is not None else None, C.byref(opts))
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        return (out, stats) if stats is not None else out
+
+    def align_all_pairs(self, S, first=0, count=None, chunk_pairs=0):
+        """Pairs [first, first + count) of the strict upper triangle of S x S (row-major; all_pairs_index gives (i, j) of a
+        pair), whole sequences, enumerated on the device.  count None: to the last pair."""
+        if not self._profile.is_null():
+            raise BatchError("align_all_pairs takes no profile")
+        if count is None:
+            count = all_pairs_count(len(S)) - int(first)
+        cfg = self._config()
+        out = np.zeros(max(int(count), 0), dtype=RECORD_DTYPE)
+        stats = np.zeros(len(out), dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
+        opts = pmx_pairs_opts_t(int(chunk_pairs))
+        rc = lib.pmx_align_all_pairs(C.byref(cfg), S._handle(), int(first), int(count), out.ctypes.data,
+                                     stats.ctypes.data if stats is not None else None, C.byref(opts))
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        return (out, stats) if stats is not None else out
+
     def align_batch_2bit(self, q2, qoff, r2, roff, out=None):
         """2-bit packed input (see pack_2bit): offsets count bases.  `out` as in align_batch_packed."""
         n = len(roff) - 1
@@ -1040,6 +1102,116 @@ def pack(seqs):
     if len(buf) == 0:
         buf = np.zeros(1, dtype=np.uint8)
     return buf, off
+
+
+class SeqSet:
+    """A set of sequences resident on the device current at its creation (pmx_seqset_t).  Released by close() or on deletion."""
+
+    def __init__(self, inner, keep=None):
+        self.inner = inner
+        self._keep = keep                     # wrapped sets: whatever owns the device buffers
+
+    @classmethod
+    def new(cls, seqs):
+        buf, off = pack(seqs)
+        return cls.packed(buf, off)
+
+    @classmethod
+    def packed(cls, buf, off):
+        """Sequence k is buf[off[k]:off[k + 1]] (uint8 buffer, int64 offsets): uploaded once."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if len(off) < 1:
+            raise BatchError("offsets need count + 1 entries")
+        inner = lib.pmx_seqset_create(buf.ctypes.data, off.ctypes.data, len(off) - 1)
+        if not inner:
+            raise BatchError(lib.pmx_last_error().decode())
+        return cls(inner)
+
+    @classmethod
+    def wrap_device(cls, d_buf, d_off, count, nbytes, keep=None):
+        """No copy: raw device addresses of the caller's buffer (`nbytes` bytes) and offsets (count + 1 int64), which must
+        outlive the set; `keep` is held for that purpose (e.g. the torch tensors)."""
+        inner = lib.pmx_seqset_wrap_device(d_buf, d_off, int(count), int(nbytes))
+        if not inner:
+            raise BatchError(lib.pmx_last_error().decode())
+        return cls(inner, keep)
+
+    def _handle(self):
+        if not self.inner:
+            raise BatchError("the sequence set is closed")
+        return self.inner
+
+    def __len__(self):
+        return int(lib.pmx_seqset_count(self._handle()))
+
+    def close(self):
+        if self.inner:
+            lib.pmx_seqset_free(self.inner)
+            self.inner = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def as_pairs(pairs):
+    """PAIR_DTYPE array from an array of that dtype or from (q, r) / (q, r, q_beg, q_len, r_beg, r_len) tuples."""
+    if isinstance(pairs, np.ndarray) and pairs.dtype == PAIR_DTYPE:
+        return np.ascontiguousarray(pairs)
+    rows = list(pairs)
+    a = np.zeros(len(rows), dtype=PAIR_DTYPE)
+    a["q_len"] = -1
+    a["r_len"] = -1
+    for k, t in enumerate(rows):
+        if len(t) == 2:
+            a[k]["q"], a[k]["r"] = t
+        else:
+            a[k] = tuple(t)
+    return a
+
+
+def all_pairs_count(nseq):
+    """Pairs of the strict upper triangle of nseq x nseq."""
+    v = lib.pmx_all_pairs_count(int(nseq))
+    if v < 0:
+        raise BatchError(lib.pmx_last_error().decode())
+    return int(v)
+
+
+def all_pairs_index(nseq, p):
+    """(i, j), i < j, of pair p in the row-major order of the all-pairs entries."""
+    i, j = C.c_int64(), C.c_int64()
+    if lib.pmx_all_pairs_index(int(nseq), int(p), C.byref(i), C.byref(j)):
+        raise BatchError(lib.pmx_last_error().decode())
+    return int(i.value), int(j.value)
+
+
+def align_pairs_device(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats=None, stream=0, chunk_pairs=0):
+    """Device-pointer entry of the set batches: n PAIR_DTYPE descriptors in, n records (and statistics) out, all in device memory.
+    A bad descriptor gets the record (0, -1, -1, FLAG_BAD_PAIR)."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_align_pairs_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, max_qlen, max_rlen, d_out, d_stats, stream,
+                                    C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_all_pairs_device(cfg, S, first, count, max_len, d_out, d_stats=None, stream=0, chunk_pairs=0):
+    """Device-pointer all-vs-all entry: pairs [first, first + count) of the upper triangle of S x S."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_align_all_pairs_device(C.byref(cfg), S._handle(), first, count, max_len, d_out, d_stats, stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def all_pairs_enumerate_device(nseq, first, count, d_pairs, stream=0):
+    """The descriptors the all-pairs entries generate, into `count` PAIR_DTYPE slots of device memory (test hook)."""
+    if lib.pmx_all_pairs_enumerate_device(int(nseq), int(first), int(count), d_pairs, stream):
+        raise BatchError(lib.pmx_last_error().decode())
 
 
 def align_batch_device(cfg, n, d_qbuf, d_qoff, d_rbuf, d_roff, max_qlen, max_rlen, d_out, d_stats=None, stream=0):

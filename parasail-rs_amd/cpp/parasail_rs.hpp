@@ -335,6 +335,51 @@ public:
 };
 
 // ----------------------------------------------------------------------------- Aligner --
+// additive: a set of sequences resident on the device current at its creation (pmx_seqset_t), for Aligner::align_pairs / align_all_pairs
+class SeqSet {
+public:
+    explicit SeqSet(const std::vector<Bytes> &seqs)
+    {
+        std::string buf; std::vector<int64_t> off(1, 0);
+        for (auto &s : seqs) { buf += s; off.push_back((int64_t)buf.size()); }
+        inner = pmx_seqset_create((const uint8_t *)buf.data(), off.data(), (int64_t)seqs.size());
+        if (!inner) throw Error(ErrorKind::Batch, pmx_last_error());
+    }
+    // sequence k is buf[off[k] .. off[k + 1]): uploaded once
+    SeqSet(const uint8_t *buf, const int64_t *off, int64_t count) : inner(pmx_seqset_create(buf, off, count))
+    {
+        if (!inner) throw Error(ErrorKind::Batch, pmx_last_error());
+    }
+    // no copy: the caller's device buffers (d_off: count + 1 entries), which must outlive the set
+    static SeqSet wrap_device(const uint8_t *d_buf, const int64_t *d_off, int64_t count, int64_t bytes)
+    {
+        pmx_seqset_t *p = pmx_seqset_wrap_device(d_buf, d_off, count, bytes);
+        if (!p) throw Error(ErrorKind::Batch, pmx_last_error());
+        return SeqSet(p);
+    }
+    SeqSet(SeqSet &&o) noexcept : inner(o.inner) { o.inner = nullptr; }
+    SeqSet &operator=(SeqSet &&o) noexcept { if (this != &o) { pmx_seqset_free(inner); inner = o.inner; o.inner = nullptr; } return *this; }
+    SeqSet(const SeqSet &) = delete;
+    SeqSet &operator=(const SeqSet &) = delete;
+    ~SeqSet() { pmx_seqset_free(inner); }
+    int64_t len() const { return pmx_seqset_count(inner); }
+    pmx_seqset_t *inner = nullptr;
+private:
+    explicit SeqSet(pmx_seqset_t *p) : inner(p) {}
+};
+inline int64_t all_pairs_count(int64_t nseq)
+{
+    const int64_t v = pmx_all_pairs_count(nseq);
+    if (v < 0) throw Error(ErrorKind::Batch, pmx_last_error());
+    return v;
+}
+inline std::pair<int64_t, int64_t> all_pairs_index(int64_t nseq, int64_t p)
+{
+    int64_t i = 0, j = 0;
+    if (pmx_all_pairs_index(nseq, p, &i, &j)) throw Error(ErrorKind::Batch, pmx_last_error());
+    return {i, j};
+}
+
 class Aligner;
 class AlignerBuilder {                                                        // src/aligner/mod.rs:67-370
 public:
@@ -547,6 +592,40 @@ public:
         out.cigars.resize(h);
         if (res->cigar) for (size_t k = 0; k < h; ++k) out.cigars[k].assign(res->cigar + res->cigar_off[k], res->cigar + res->cigar_off[k + 1]);
         pmx_search_result_free(res);
+        return out;
+    }
+
+    // additive: pairs by index and window into device-resident sets (pmx_align_pairs; Q may be R): record k belongs to the pair
+    // (query window, reference window) k, end positions relative to the windows.  A bad descriptor throws, naming the first.
+    std::vector<pmx_record_t> align_pairs(const SeqSet &Q, const SeqSet &R, const std::vector<pmx_pair_t> &pairs,
+                                          std::vector<pmx_stats_t> *stats = nullptr, int64_t chunk_pairs = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "align_pairs takes no profile");
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        std::vector<pmx_record_t> out(pairs.size());
+        if (cfg.want & PMX_WANT_STATS) { if (!stats) throw Error(ErrorKind::Batch, "stats aligner needs a stats vector"); stats->resize(pairs.size()); }
+        const pmx_pairs_opts_t opts = {chunk_pairs};
+        const int rc = pmx_align_pairs(&cfg, Q.inner, R.inner, (int64_t)pairs.size(), pairs.data(), out.data(),
+                                       (cfg.want & PMX_WANT_STATS) ? stats->data() : nullptr, &opts);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        return out;
+    }
+    // additive: pairs [first, first + count) of the strict upper triangle of S x S, row-major (all_pairs_index), whole sequences,
+    // enumerated on the device (pmx_align_all_pairs).  count < 0: to the last pair.
+    std::vector<pmx_record_t> align_all_pairs(const SeqSet &S, int64_t first = 0, int64_t count = -1,
+                                              std::vector<pmx_stats_t> *stats = nullptr, int64_t chunk_pairs = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "align_all_pairs takes no profile");
+        if (count < 0) count = all_pairs_count(S.len()) - first;
+        if (count < 0) throw Error(ErrorKind::Batch, "first is beyond the last pair");
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        std::vector<pmx_record_t> out((size_t)count);
+        if (cfg.want & PMX_WANT_STATS) { if (!stats) throw Error(ErrorKind::Batch, "stats aligner needs a stats vector"); stats->resize((size_t)count); }
+        const pmx_pairs_opts_t opts = {chunk_pairs};
+        const int rc = pmx_align_all_pairs(&cfg, S.inner, first, count, out.data(), (cfg.want & PMX_WANT_STATS) ? stats->data() : nullptr, &opts);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
         return out;
     }
 

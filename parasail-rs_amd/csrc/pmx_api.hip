@@ -1371,7 +1371,9 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_LONG = 16,                                                                    // boundary granules + band candidates of pmx_long.hip
        SCR_SEL = 17,                                                                     // hit selection: state, histogram, block counts, sort buffers (pmx_select.hip)
        SCR_SRCH = 18, SCR_GREF = 19,                                                     // profile search: hit list / diagonals / lengths / offsets / begins; gathered references
-       SCR_SLOTS = 20 };
+       SCR_PAIRS = 20, SCR_PGEN = 21,                                                    // set batches: two sets of chunk buffers (pmx_pairs.hip); enumerated descriptors
+       SCR_PUP = 22, SCR_PREC = 23, SCR_PST = 24,                                        // set batches, host entries: uploaded descriptors, records, statistics
+       SCR_SLOTS = 25 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -3560,4 +3562,421 @@ extern "C" int pmx_host_unregister(void *p)
     if (!p) return 0;
     HIP_OR_RET(hipHostUnregister(p));
     return 0;
+}
+
+// ---- sequence-set batches (semantics: include/parasail_amd.h; kernels: pmx_pairs.hip) ----------------------------------
+// A set: packed sequences on one device and, for an uploaded set, the host's copy of the offsets (validation, exact maxima).
+struct pmx_seqset {
+    const uint8_t *d_buf = nullptr; const int64_t *d_off = nullptr;
+    int64_t count = 0, bytes = 0;
+    int dev = -1;                    // -1: wrapped while no device was usable; every entry refuses such a set
+    bool owned = false;
+    std::vector<int64_t> h_off;      // count + 1 entries; empty: a wrapped set
+};
+
+extern "C" pmx_seqset_t *pmx_seqset_create(const uint8_t *buf, const int64_t *off, int64_t count)
+{
+    if (!off || count < 0 || (count > 0 && !buf)) { set_err("null buffer or negative count"); return nullptr; }
+    if (off[0] < 0) { set_err("offsets must not be negative"); return nullptr; }
+    for (int64_t k = 0; k < count; ++k)
+        if (off[k + 1] < off[k]) { set_err("offsets decrease at sequence %lld", (long long)k); return nullptr; }
+    if (off[count] > ((int64_t)1 << 40)) { set_err("bad offset array"); return nullptr; }
+    pmx_seqset *s = new (std::nothrow) pmx_seqset();
+    if (!s) { set_err("out of memory"); return nullptr; }
+    try { s->h_off.assign(off, off + count + 1); } catch (const std::bad_alloc &) { delete s; set_err("out of memory"); return nullptr; }
+    s->count = count; s->bytes = off[count]; s->owned = true;
+    void *db = nullptr, *dof = nullptr;
+    hipError_t e = hipGetDevice(&s->dev);
+    if (e == hipSuccess) e = hipMalloc(&db, (size_t)s->bytes + 16);
+    if (e == hipSuccess) e = hipMalloc(&dof, sizeof(int64_t) * (size_t)(count + 1));
+    if (e == hipSuccess && s->bytes > 0) e = hipMemcpy(db, buf, (size_t)s->bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dof, off, sizeof(int64_t) * (size_t)(count + 1), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_err("sequence set upload failed: %s", hipGetErrorString(e));
+        if (db) (void)hipFree(db);
+        if (dof) (void)hipFree(dof);
+        delete s; return nullptr;
+    }
+    s->d_buf = (const uint8_t *)db; s->d_off = (const int64_t *)dof;
+    return s;
+}
+
+extern "C" pmx_seqset_t *pmx_seqset_wrap_device(const uint8_t *d_buf, const int64_t *d_off, int64_t count, int64_t bytes)
+{
+    if (!d_off || count < 0 || bytes < 0 || (bytes > 0 && !d_buf)) { set_err("null buffer, negative count or negative bytes"); return nullptr; }
+    pmx_seqset *s = new (std::nothrow) pmx_seqset();
+    if (!s) { set_err("out of memory"); return nullptr; }
+    s->d_buf = d_buf; s->d_off = d_off; s->count = count; s->bytes = bytes;
+    if (hipGetDevice(&s->dev) != hipSuccess) s->dev = -1;
+    return s;
+}
+
+extern "C" void pmx_seqset_free(pmx_seqset_t *s)
+{
+    if (!s) return;
+    if (s->owned) {
+        int dev = -1;
+        const bool move = hipGetDevice(&dev) == hipSuccess && dev != s->dev;
+        if (move) (void)hipSetDevice(s->dev);
+        (void)hipFree((void *)s->d_buf); (void)hipFree((void *)s->d_off);
+        if (move) (void)hipSetDevice(dev);
+    }
+    delete s;
+}
+
+extern "C" int64_t pmx_seqset_count(const pmx_seqset_t *s) { return s ? s->count : -1; }
+
+extern "C" int64_t pmx_all_pairs_count(int64_t nseq)
+{
+    if (nseq < 0 || nseq > INT32_MAX) { set_err("nseq %lld is outside 0 .. 2^31 - 1", (long long)nseq); return -1; }
+    return nseq * (nseq - 1) / 2;
+}
+
+extern "C" int pmx_all_pairs_index(int64_t nseq, int64_t p, int64_t *i, int64_t *j)
+{
+    const int64_t total = pmx_all_pairs_count(nseq);
+    if (total < 0) return -1;
+    if (!i || !j) { set_err("null output"); return -1; }
+    if (p < 0 || p >= total) { set_err("pair %lld is outside 0 .. %lld", (long long)p, (long long)total - 1); return -1; }
+    unsigned long long ui = 0, uj = 0;
+    pmx_all_pairs_index_host((unsigned long long)nseq, (unsigned long long)p, &ui, &uj);
+    *i = (int64_t)ui; *j = (int64_t)uj;
+    return 0;
+}
+
+// The prep stream and the events of the chunk pipeline, per thread and device (the pattern of TraceWs).
+struct PairsWs { hipStream_t prep = nullptr; hipEvent_t start = nullptr, packed[2] = {nullptr, nullptr}, aligned[2] = {nullptr, nullptr}; int dev = -1; };
+static thread_local PairsWs g_pws;
+static int pairs_ws_init()
+{
+    int dev = 0; HIP_OR_RET(hipGetDevice(&dev));
+    if (g_pws.dev == dev) return 0;
+    if (g_pws.prep) {                                   // the thread moved to another device: release the old device's objects
+        (void)hipStreamDestroy(g_pws.prep); (void)hipEventDestroy(g_pws.start);
+        for (int k = 0; k < 2; ++k) { (void)hipEventDestroy(g_pws.packed[k]); (void)hipEventDestroy(g_pws.aligned[k]); }
+        g_pws = PairsWs();
+    }
+    HIP_OR_RET(hipStreamCreateWithFlags(&g_pws.prep, hipStreamNonBlocking));
+    HIP_OR_RET(hipEventCreateWithFlags(&g_pws.start, hipEventDisableTiming));
+    for (int k = 0; k < 2; ++k) {
+        HIP_OR_RET(hipEventCreateWithFlags(&g_pws.packed[k], hipEventDisableTiming));
+        HIP_OR_RET(hipEventCreateWithFlags(&g_pws.aligned[k], hipEventDisableTiming));
+    }
+    g_pws.dev = dev;
+    return 0;
+}
+
+// Pairs per chunk.  One chunk's packed windows take at most chunk * (max_qlen + max_rlen + 16) bytes; the default keeps that under
+// PMX_PAIRS_CHUNK_BYTES per set of buffers (two sets) and cuts the batch into equal chunks, whole groups of 64 pairs.  256 MiB: a
+// million 150 x 150 pairs (316 MB by this bound) are two chunks.  Measured there: one, two and four chunks take
+// 3.09, 3.09 and 3.13 ms -- the six launches a chunk adds cost more than the overlap returns, so chunks are as large as the scratch
+// allows, and 2 x 256 MiB is small beside the HBM of the cards this runs on.
+static const double PMX_PAIRS_CHUNK_BYTES = 256.0 * 1024 * 1024;
+static int64_t pairs_chunk(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_pairs_opts_t *opts)
+{
+    if (opts && opts->chunk_pairs > 0) return opts->chunk_pairs < n ? opts->chunk_pairs : n;
+    int64_t chunk = (int64_t)(PMX_PAIRS_CHUNK_BYTES / ((double)max_qlen + (double)max_rlen + 16.0));
+    if (chunk < 1) chunk = 1;
+    if (chunk >= n) return n;
+    const int64_t nchunks = (n + chunk - 1) / chunk;
+    chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
+    return chunk > n ? n : chunk;
+}
+
+// Everything a set batch refuses before any GPU work, shared by the four entries (R == Q for the all-pairs entries).
+static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, const pmx_pairs_opts_t *opts,
+                       int32_t max_qlen, int32_t max_rlen, bool stats_buffer)
+{
+    if (check_cfg(cfg)) return -1;
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (cfg->want & PMX_WANT_CIGAR) { set_err("set batches have no CIGAR output"); return -1; }
+    if ((cfg->want & PMX_WANT_STATS) && !stats_buffer) { set_err("stats requested without a stats buffer"); return -1; }
+    if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    if (pssm_batch_check(cfg->matrix, max_qlen, max_qlen)) return -1;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (Q->dev != dev || R->dev != dev) {
+        set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev != dev ? Q->dev : R->dev, dev); return -1;
+    }
+    return 0;
+}
+
+// The pair materialiser and the chunk loop.  Chunk c: (enumerate,) resolve, two offset scans and the gather on `prep` into buffer set
+// c & 1, then -- behind packed[c & 1] -- the alignment and the fix-up of bad pairs on the caller's stream, in chunk order:
+// run_batch_device keeps per-thread scratch and never runs twice at once.  aligned[c & 1] lets chunk c + 2's gather overwrite the set.
+// Everything `prep` does is waited for by `st`, so `st` ends behind the last fix-up and behind `prep`.  One chunk: all on `st`.
+// d_pairs == nullptr: pairs [first, first + n) of the upper triangle of Q x Q, generated per chunk.
+struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok; };
+static int pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first,
+                     int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out, hipStream_t st, int64_t chunk)
+{
+    const bool two = chunk < n, stats = (cfg->want & PMX_WANT_STATS) != 0;
+    PairsChunkBufs B[2]; void *scan = nullptr; pmx_pair_t *gen = nullptr;
+    const size_t scan_bytes = pmx_text_scan_scratch_bytes(chunk);
+    if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
+            for (int s = 0; s < (two ? 2 : 1); ++s) {
+                B[s].q = c.take<uint8_t>((size_t)chunk * (size_t)max_qlen + 16);      // (the slack of the host entries' staged copies)
+                B[s].r = c.take<uint8_t>((size_t)chunk * (size_t)max_rlen + 16);
+                B[s].qlen = c.take<int32_t>((size_t)chunk + 2); B[s].rlen = c.take<int32_t>((size_t)chunk + 2);
+                B[s].qoff = c.take<int64_t>((size_t)chunk + 1); B[s].roff = c.take<int64_t>((size_t)chunk + 1);
+                B[s].qsrc = c.take<int64_t>((size_t)chunk); B[s].rsrc = c.take<int64_t>((size_t)chunk);
+                B[s].ok = c.take<uint8_t>((size_t)chunk);
+            }
+            scan = c.take<unsigned char>(scan_bytes);           // (one: the scans of all chunks run in order on one stream)
+        })) return -1;
+    if (!d_pairs && scratch_reserve(sizeof(pmx_pair_t) * (size_t)chunk * (two ? 2 : 1), (void **)&gen, SCR_PGEN)) return -1;
+    hipStream_t prep = st;
+    if (two) {
+        if (pairs_ws_init()) return -1;
+        prep = g_pws.prep;
+        HIP_OR_RET(hipEventRecord(g_pws.start, st));
+        HIP_OR_RET(hipStreamWaitEvent(prep, g_pws.start, 0));
+    }
+    auto pack = [&](int64_t c0, int64_t cn, int slot) -> int {
+        const PairsChunkBufs &b = B[slot];
+        const pmx_pair_t *pc = d_pairs ? d_pairs + c0 : gen + (size_t)slot * (size_t)chunk;
+        int rc = d_pairs ? 0 : pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gen + (size_t)slot * (size_t)chunk, prep);
+        if (!rc) rc = pmx_launch_pairs_resolve(pc, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                               b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
+        if (!rc) rc = pmx_launch_text_offsets(b.qlen, cn, b.qoff, scan, scan_bytes, prep);
+        if (!rc) rc = pmx_launch_text_offsets(b.rlen, cn, b.roff, scan, scan_bytes, prep);
+        if (!rc) rc = pmx_launch_pairs_gather(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
+                                              b.qoff, b.roff, b.q, b.r, prep);
+        if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
+        if (two) HIP_OR_RET(hipEventRecord(g_pws.packed[slot], prep));
+        return 0;
+    };
+    int rc = pack(0, chunk, 0);
+    if (rc) return rc;
+    int idx = 0;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk, ++idx) {
+        const int slot = idx & 1;
+        const int64_t cn = n - c0 < chunk ? n - c0 : chunk, n0 = c0 + chunk;
+        if (n0 < n) {                                                                   // the next chunk's windows, beside this alignment
+            if (idx >= 1) HIP_OR_RET(hipStreamWaitEvent(prep, g_pws.aligned[slot ^ 1], 0));      // that set's last alignment is done
+            rc = pack(n0, n - n0 < chunk ? n - n0 : chunk, slot ^ 1);
+            if (rc) return rc;
+        }
+        if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_pws.packed[slot], 0));
+        const PairsChunkBufs &b = B[two ? slot : 0];
+        rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
+        if (rc) return rc;
+        rc = pmx_launch_pairs_fixup(b.ok, cn, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
+        if (rc) { set_err("bad-pair fix-up launch failed (%d)", rc); return rc; }
+        if (two) HIP_OR_RET(hipEventRecord(g_pws.aligned[slot], st));
+    }
+    return 0;
+}
+
+extern "C" int pmx_align_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                      int64_t n, const pmx_pair_t *d_pairs, int32_t max_qlen, int32_t max_rlen,
+                                      pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream, const pmx_pairs_opts_t *opts)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg)) return -1;
+    if (n == 0) return 0;
+    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run(cfg, Q, R, n, d_pairs, 0, max_qlen, max_rlen, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts));
+}
+
+// The all-pairs window [first, first + count) of a set: 0, or -1 with the cause.
+static int all_pairs_window(int64_t nseq, int64_t first, int64_t count)
+{
+    if (first < 0 || count < 0) { set_err("negative first or count"); return -1; }
+    const int64_t total = pmx_all_pairs_count(nseq);
+    if (total < 0) return -1;
+    if (first > total || count > total - first) {
+        set_err("pairs %lld .. %lld are beyond the %lld pairs of %lld sequences", (long long)first, (long long)first + (long long)count - 1, (long long)total, (long long)nseq);
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int pmx_align_all_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
+                                          int32_t max_len, pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream,
+                                          const pmx_pairs_opts_t *opts)
+{
+    if (!S) { set_err("null sequence set"); return -1; }
+    if (all_pairs_window(S->count, first, count)) return -1;
+    if (count > 0 && !d_out) { set_err("null records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg)) return -1;
+    if (count == 0) return 0;
+    if (pairs_check(cfg, S, S, opts, max_len, max_len, d_stats_out != nullptr)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run(cfg, S, S, count, nullptr, first, max_len, max_len, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(count, max_len, max_len, opts));
+}
+
+extern "C" int pmx_all_pairs_enumerate_device(int64_t nseq, int64_t first, int64_t count, pmx_pair_t *d_pairs, void *stream)
+{
+    if (all_pairs_window(nseq, first, count)) return -1;
+    if (count == 0) return 0;
+    if (!d_pairs) { set_err("null pairs"); return -1; }
+    const int rc = pmx_launch_all_pairs_enumerate(nseq, first, count, d_pairs, (hipStream_t)stream);
+    if (rc) { set_err("pair enumeration launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
+    return 0;
+}
+
+// One side of a descriptor against host offsets: nullptr, or what is wrong with it; *len = the resolved length.
+static const char *host_resolve_side(const std::vector<int64_t> &off, int64_t count, int64_t idx, int32_t beg, int32_t len, int64_t *out)
+{
+    if (idx < 0 || idx >= count) return "index outside the set";
+    if (beg < 0) return "negative window start";
+    if (len < -1) return "negative window length";
+    const int64_t slen = off[idx + 1] - off[idx], l = len < 0 ? slen - beg : (int64_t)len;
+    if (l < 1) return "empty window";
+    if ((int64_t)beg + l > slen) return "window reaches past the end of the sequence";
+    if (l > INT32_MAX) return "window longer than 2^31 - 1";
+    *out = l;
+    return nullptr;
+}
+
+// Pairs [a, e) against the host offsets: the first bad one (what is wrong with which side), or the extreme window lengths.
+struct PairScan { int64_t bad = -1; const char *what = nullptr, *side = nullptr; int64_t mq = 1, mr = 1, mnr = INT32_MAX; };
+static PairScan scan_pairs(const pmx_seqset *Q, const pmx_seqset *R, const pmx_pair_t *pairs, int64_t a, int64_t e)
+{
+    PairScan s;
+    for (int64_t k = a; k < e; ++k) {
+        int64_t ql = 0, rl = 0;
+        const char *what = host_resolve_side(Q->h_off, Q->count, pairs[k].q, pairs[k].q_beg, pairs[k].q_len, &ql);
+        const char *side = "query";
+        if (!what) { what = host_resolve_side(R->h_off, R->count, pairs[k].r, pairs[k].r_beg, pairs[k].r_len, &rl); side = "reference"; }
+        if (what) { s.bad = k; s.what = what; s.side = side; return s; }
+        s.mq = ql > s.mq ? ql : s.mq; s.mr = rl > s.mr ? rl : s.mr; s.mnr = rl < s.mnr ? rl : s.mnr;
+    }
+    return s;
+}
+
+// The longest good windows of a batch over a set without host offsets (one small kernel and one synchronisation).
+static int device_maxlens(const pmx_seqset *Q, const pmx_seqset *R, const pmx_pair_t *d_pairs, int64_t n, int32_t *mq, int32_t *mr, hipStream_t st)
+{
+    int32_t *d = nullptr, h[2] = {0, 0};
+    if (scratch_reserve(256, (void **)&d, SCR_PGEN)) return -1;
+    HIP_OR_RET(hipMemsetAsync(d, 0, 2 * sizeof(int32_t), st));
+    const int rc = pmx_launch_pairs_maxlen(d_pairs, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, d, st);
+    if (rc) { set_err("length scan launch failed (%d)", rc); return rc; }
+    HIP_OR_RET(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    *mq = h[0] > 0 ? h[0] : 1; *mr = h[1] > 0 ? h[1] : 1;        // (no good window at all: every record will be flagged)
+    return 0;
+}
+
+// Device records (and statistics) back to the host; a flagged record -- a set without host offsets was validated on the device -- is
+// the call's failure.
+static int pairs_copy_back(int64_t n, const pmx_record_t *drec, const pmx_stats_t *dst, pmx_record_t *out, pmx_stats_t *stats_out, bool scan_flags, hipStream_t st)
+{
+    HIP_OR_RET(hipMemcpyAsync(out, drec, sizeof(pmx_record_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (dst) HIP_OR_RET(hipMemcpyAsync(stats_out, dst, sizeof(pmx_stats_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    if (scan_flags)
+        for (int64_t k = 0; k < n; ++k)
+            if (out[k].flags & PMX_FLAG_BAD_PAIR) { set_err("pair %lld: bad descriptor (index, window or length)", (long long)k); return -1; }
+    return 0;
+}
+
+extern "C" int pmx_align_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                               int64_t n, const pmx_pair_t *pairs, pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg)) return -1;
+    if (n == 0) return 0;
+    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
+    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
+    if (host_offsets) {
+        // large batches: the scan is a few nanoseconds per pair of random reads into the offsets -- measured at 2.1 ms per million
+        // pairs on one core, of a 6.9 ms call -- so it is cut into slices on helper threads, merged in pair order
+        const int T = n >= 262144 ? 4 : 1;
+        PairScan part[4];
+        std::future<void> helper[4];
+        for (int t = 1; t < T; ++t) {
+            const int64_t a = n * t / T, e = n * (t + 1) / T;
+            try { helper[t] = std::async(std::launch::async, [&, t, a, e]() { part[t] = scan_pairs(Q, R, pairs, a, e); }); }
+            catch (const std::system_error &) { part[t] = scan_pairs(Q, R, pairs, a, e); }          // no helper thread to be had: scan inline
+        }
+        part[0] = scan_pairs(Q, R, pairs, 0, n / T);
+        for (int t = 1; t < T; ++t) if (helper[t].valid()) helper[t].get();
+        for (int t = 0; t < T; ++t) {
+            const PairScan &s = part[t];
+            if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
+            mq = s.mq > mq ? s.mq : mq; mr = s.mr > mr ? s.mr : mr; mnr = s.mnr < mnr ? s.mnr : mnr;
+        }
+    }
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    if (pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
+    if (scratch_reserve(sizeof(pmx_pair_t) * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
+        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
+    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
+    pmx_config_t cfg_s = *cfg;
+    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
+    else {
+        if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
+        if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
+    }
+    const int rc = pairs_run(&cfg_s, Q, R, n, dp, 0, q32, r32, drec, dst, st, pairs_chunk(n, q32, r32, opts));
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    return pairs_copy_back(n, drec, dst, out, stats_out, !host_offsets, st);
+}
+
+extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
+                                   pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts)
+{
+    if (!S) { set_err("null sequence set"); return -1; }
+    if (all_pairs_window(S->count, first, count)) return -1;
+    if (count > 0 && !out) { set_err("null records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg)) return -1;
+    if (count == 0) return 0;
+    const bool host_offsets = !S->h_off.empty();
+    int64_t mx = 1, mn = INT32_MAX;
+    if (host_offsets) {
+        int64_t empty = -1;                       // the first sequence that cannot be a whole-sequence window
+        for (int64_t k = 0; k < S->count; ++k) {
+            const int64_t l = S->h_off[k + 1] - S->h_off[k];
+            if ((l < 1 || l > INT32_MAX) && empty < 0) empty = k;
+            mx = l > mx ? l : mx; mn = l < mn ? l : mn;
+        }
+        if (empty >= 0) {                         // (rare: walk the window for the first pair that touches such a sequence)
+            if (mx > INT32_MAX) mx = INT32_MAX;
+            for (int64_t p = first; p < first + count; ++p) {
+                int64_t i = 0, j = 0, l = 0;
+                (void)pmx_all_pairs_index(S->count, p, &i, &j);
+                const char *what = host_resolve_side(S->h_off, S->count, i, 0, -1, &l);
+                const char *side = "query";
+                if (!what) { what = host_resolve_side(S->h_off, S->count, j, 0, -1, &l); side = "reference"; }
+                if (what) { set_err("pair %lld (%lld, %lld): %s: %s", (long long)(p - first), (long long)i, (long long)j, side, what); return -1; }
+            }
+        }
+    }
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    if (pairs_check(cfg, S, S, opts, (int32_t)mx, (int32_t)mx, stats_out != nullptr)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
+    if (scratch_reserve(sizeof(pmx_record_t) * (size_t)count, (void **)&drec, SCR_PREC) ||
+        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)count, (void **)&dst, SCR_PST))) return -1;
+    int32_t m32 = (int32_t)mx, unused = 0;
+    pmx_config_t cfg_s = *cfg;
+    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)(mn < 1 ? 1 : mn), m32, count);
+    else {
+        if (device_maxlens(S, S, nullptr, S->count, &m32, &unused, st)) return -1;
+        if (pssm_batch_check(cfg->matrix, m32, m32)) return -1;
+    }
+    const int rc = pairs_run(&cfg_s, S, S, count, nullptr, first, m32, m32, drec, dst, st, pairs_chunk(count, m32, m32, opts));
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    return pairs_copy_back(count, drec, dst, out, stats_out, !host_offsets, st);
 }

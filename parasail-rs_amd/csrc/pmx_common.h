@@ -256,6 +256,22 @@ int pmx_launch_hit_begins(const int32_t *beg, long long h, pmx_hit_t *hits, hipS
 int pmx_launch_gather_refs(const uint8_t *rbuf, const int64_t *roff, long long n, const int64_t *idx, long long h,
                            uint8_t *out, const int64_t *ooff, long long out_cap, hipStream_t stream);
 
+// Sequence-set batches (pmx_pairs.hip; semantics: include/parasail_amd.h).  All asynchronous on `stream`; 0 launched, <0 HIP error.
+// resolve: qlen / rlen hold n + 2 entries (the scan's input), qsrc / rsrc / ok n; a bad pair is 1 x 1 with ok = 0.
+int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
+                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                             int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, hipStream_t stream);
+int pmx_launch_pairs_gather(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
+                            const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
+                            const int64_t *qoff, const int64_t *roff, uint8_t *qout, uint8_t *rout, hipStream_t stream);
+int pmx_launch_pairs_fixup(const uint8_t *ok, long long n, pmx_record_t *rec, pmx_stats_t *stats /* may be NULL */, hipStream_t stream);
+int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long count, pmx_pair_t *pairs, hipStream_t stream);
+// out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
+int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
+                            const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);
+// p -> (i, j) of the strict upper triangle of nseq x nseq (2 <= nseq <= 2^31 - 1, p in range): the arithmetic the kernel runs
+void pmx_all_pairs_index_host(unsigned long long nseq, unsigned long long p, unsigned long long *i, unsigned long long *j);
+
 // One long pair (or a few) across the chip: bands of the query on different CUs, pipelined through HBM granules (pmx_long.hip).
 // R = rows per lane (4 or 16).  0 launched, 1 not eligible, <0 HIP error; `scratch` holds pmx_long_scratch_bytes() bytes.
 size_t pmx_long_scratch_bytes(long long n, int max_qlen, int max_rlen, int R, long long *bstride, int *nbmax);

@@ -1,0 +1,197 @@
+// pmx_pairs.hip -- sequence-set batches: pair descriptors (index + window into device-resident sequence sets) -> the packed chunk
+// buffers every alignment kernel reads (semantics: include/parasail_amd.h; pipeline: pmx_api.hip).
+//
+//   pmx_pairs_resolve_kernel        descriptor -> two lengths, two source byte offsets, a validity byte (a bad pair: 1 x 1)
+//   (pmx_launch_text_offsets        the chunk's packed qoff / roff from the lengths: pmx_sort.hip)
+//   pmx_pairs_gather_kernel         the windows into the chunk's packed buffers, a 16-lane group per sequence
+//   pmx_pairs_fixup_kernel          the records (and statistics) of bad pairs, after the chunk's alignment
+//   pmx_all_pairs_enumerate_kernel  p -> (i, j) of the strict upper triangle, whole-sequence descriptors
+//   pmx_pairs_maxlen_kernel         the longest resolved window per side (host entries over wrapped sets)
+//
+// All of them are bandwidth kernels in plain C++: vector loads and stores only.
+#include "pmx_common.h"
+
+// One side of a descriptor against its set.  0 = bad; otherwise the window's length, *src = its first byte in the set's buffer.
+// A set wrapped around caller buffers has unchecked offsets: a window is good only when it lies inside [0, bytes).
+static __device__ __forceinline__ int32_t pmx_resolve_side(const int64_t *__restrict__ off, long long count, long long bytes,
+                                                           long long idx, int32_t beg, int32_t len, int32_t max_len, long long *src)
+{
+    if (idx < 0 || idx >= count || beg < 0 || len < -1) return 0;
+    const long long o0 = off[idx], o1 = off[idx + 1];
+    if (o0 < 0 || o1 < o0 || o1 > bytes) return 0;
+    const long long slen = o1 - o0;
+    const long long l = len < 0 ? slen - (long long)beg : (long long)len;
+    if (l < 1 || (long long)beg + l > slen || l > (long long)max_len) return 0;
+    *src = o0 + beg;
+    return (int32_t)l;
+}
+
+__global__ __launch_bounds__(256)
+void pmx_pairs_resolve_kernel(const pmx_pair_t *__restrict__ pairs, long long n,
+                              const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
+                              const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
+                              int32_t max_qlen, int32_t max_rlen,
+                              int32_t *__restrict__ qlen, int32_t *__restrict__ rlen,
+                              int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n + 2) return;
+    if (k >= n) { qlen[k] = 0; rlen[k] = 0; return; }          // (the scan reads n + 1 lengths)
+    const pmx_pair_t p = pairs[k];
+    long long qs = 0, rs = 0;
+    int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, max_qlen, &qs);
+    int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
+    const bool good = ql > 0 && rl > 0;
+    if (!good) { ql = 1; rl = 1; qs = 0; rs = 0; }
+    qlen[k] = ql; rlen[k] = rl; qsrc[k] = qs; rsrc[k] = rs; ok[k] = good ? 1 : 0;
+}
+
+// Group g = 2 * pair + side copies one window: four sequences per wave, both sides of a pair in neighbouring groups.  Up to three head
+// bytes bring the destination to a dword boundary; each destination dword is then assembled from the two aligned source dwords that
+// hold its four bytes (one when the source is aligned too); the tail goes byte by byte.  A dword whose aligned source dwords would
+// reach outside [buf, buf + bytes) -- the first or last few bytes of a set, which has no promised slack -- is assembled from its own
+// four bytes.  Destinations lie inside the chunk buffer by construction: every length is at most the maximum the buffer was sized by.
+__global__ __launch_bounds__(256)
+void pmx_pairs_gather_kernel(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes, const uint8_t *__restrict__ r_buf, long long r_bytes,
+                             const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen,
+                             const int64_t *__restrict__ qsrc, const int64_t *__restrict__ rsrc, const uint8_t *__restrict__ ok,
+                             const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
+                             uint8_t *__restrict__ qout, uint8_t *__restrict__ rout)
+{
+    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
+    const int lane = threadIdx.x & 15;
+    if (g >= 2 * n) return;
+    const long long k = g >> 1;
+    const bool side = (g & 1) != 0;
+    uint8_t *dst = side ? rout + roff[k] : qout + qoff[k];
+    if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
+    const uint8_t *buf = side ? r_buf : q_buf;
+    const long long len = side ? rlen[k] : qlen[k];
+    const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
+    const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
+    long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
+    if (head > len) head = len;
+    if (lane < head) dst[lane] = src[lane];
+    const long long nd = (len - head) >> 2;
+    const uint8_t *s0 = src + head;
+    uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
+    for (long long x = lane; x < nd; x += 16) {
+        const uint8_t *s = s0 + 4 * x;
+        const uintptr_t sa = (uintptr_t)s & ~(uintptr_t)3;
+        const unsigned sh = (unsigned)((uintptr_t)s & 3);
+        uint32_t v;
+        if (sa >= lo_bound && sa + (sh ? 8 : 4) <= hi_bound) {
+            const uint32_t lo = *reinterpret_cast<const uint32_t *>(sa);
+            const uint32_t hi = sh ? *reinterpret_cast<const uint32_t *>(sa + 4) : 0u;
+            v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+        } else
+            v = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
+        d0[x] = v;
+    }
+    const long long done = head + 4 * nd;
+    if (lane < len - done) dst[done + lane] = src[done + lane];
+}
+
+__global__ __launch_bounds__(256)
+void pmx_pairs_fixup_kernel(const uint8_t *__restrict__ ok, long long n, pmx_record_t *__restrict__ rec, pmx_stats_t *__restrict__ stats)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n || ok[k]) return;
+    pmx_record_t r; r.score = 0; r.end_query = -1; r.end_ref = -1; r.flags = PMX_FLAG_BAD_PAIR;
+    rec[k] = r;
+    if (stats) { pmx_stats_t s; s.matches = 0; s.similar = 0; s.length = 0; stats[k] = s; }
+}
+
+// Row i of the strict upper triangle of N x N starts at pair s(i) = i (2 N - i - 1) / 2; i is the largest row with s(i) <= p.  The root
+// of (2 N - 1)^2 - 8 p in floating point gives i to within a step or two; the loops settle it in unsigned 64-bit arithmetic, exactly.
+// (2 N - 1)^2 < 2^64 and i (2 N - i - 1) < 2^63 for N <= 2^31 - 1.
+static __host__ __device__ inline unsigned long long pmx_row_start(unsigned long long N, unsigned long long i) { return i * (2 * N - i - 1) / 2; }
+static __host__ __device__ inline void pmx_pair_of(unsigned long long N, unsigned long long p, unsigned long long *pi, unsigned long long *pj)
+{
+    const unsigned long long b = 2 * N - 1, d = b * b - 8 * p;
+    const double root = sqrt((double)d);
+    double est = ((double)b - root) * 0.5;
+    unsigned long long i = est <= 0.0 ? 0 : (unsigned long long)est;
+    if (i > N - 2) i = N - 2;
+    while (i > 0 && pmx_row_start(N, i) > p) --i;
+    while (i < N - 2 && pmx_row_start(N, i + 1) <= p) ++i;
+    *pi = i; *pj = i + 1 + (p - pmx_row_start(N, i));
+}
+
+__global__ __launch_bounds__(256)
+void pmx_all_pairs_enumerate_kernel(long long nseq, long long first, long long count, pmx_pair_t *__restrict__ pairs)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    unsigned long long i, j;
+    pmx_pair_of((unsigned long long)nseq, (unsigned long long)(first + t), &i, &j);
+    pmx_pair_t d; d.q = (int64_t)i; d.r = (int64_t)j; d.q_beg = 0; d.q_len = -1; d.r_beg = 0; d.r_len = -1;
+    pairs[t] = d;
+}
+
+// out[0] / out[1] = the longest good query / reference window (0: none), the caller zeroes them.  pairs == nullptr: the n whole
+// sequences of the query-side set.  One atomic per wave and side.
+__global__ __launch_bounds__(256)
+void pmx_pairs_maxlen_kernel(const pmx_pair_t *__restrict__ pairs, long long n,
+                             const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
+                             const int64_t *__restrict__ r_off, long long r_count, long long r_bytes, int32_t *__restrict__ out)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    int32_t ql = 0, rl = 0;
+    if (k < n) {
+        long long s = 0;
+        if (pairs) {
+            const pmx_pair_t p = pairs[k];
+            ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, INT32_MAX, &s);
+            rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, INT32_MAX, &s);
+        } else
+            ql = rl = pmx_resolve_side(q_off, q_count, q_bytes, k, 0, -1, INT32_MAX, &s);
+    }
+    for (int d = 32; d >= 1; d >>= 1) { ql = max(ql, __shfl_xor(ql, d)); rl = max(rl, __shfl_xor(rl, d)); }
+    if ((threadIdx.x & 63) == 0) { if (ql > 0) atomicMax(&out[0], ql); if (rl > 0) atomicMax(&out[1], rl); }
+}
+
+static int pmx_pairs_launched() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
+
+int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
+                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                             int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_resolve_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, n, q_off, q_count, q_bytes,
+                       r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_gather(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
+                            const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
+                            const int64_t *qoff, const int64_t *roff, uint8_t *qout, uint8_t *rout, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_gather_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                       qlen, rlen, qsrc, rsrc, ok, qoff, roff, qout, rout);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_fixup(const uint8_t *ok, long long n, pmx_record_t *rec, pmx_stats_t *stats, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_fixup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, rec, stats);
+    return pmx_pairs_launched();
+}
+int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long count, pmx_pair_t *pairs, hipStream_t st)
+{
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL(pmx_all_pairs_enumerate_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, nseq, first, count, pairs);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
+                            const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_maxlen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pairs, n, q_off, q_count, q_bytes,
+                       r_off, r_count, r_bytes, out);
+    return pmx_pairs_launched();
+}
+void pmx_all_pairs_index_host(unsigned long long nseq, unsigned long long p, unsigned long long *i, unsigned long long *j)
+{
+    pmx_pair_of(nseq, p, i, j);
+}
