@@ -471,6 +471,58 @@ int pmx_align_all_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *S, i
 /* Test hook: the descriptors the all-pairs entries generate, `count` of them into d_pairs; asynchronous on `stream`. */
 int pmx_all_pairs_enumerate_device(int64_t nseq, int64_t first, int64_t count, pmx_pair_t *d_pairs, void *stream);
 
+/* Strands and CIGAR output for set batches: the extension stage of a read mapper (a read against candidate windows of a resident
+ * reference, half of them on the reverse strand, alignments and not only scores).
+ *
+ * Strand: one byte per pair (NULL: all 0).  0 = the query window as stored; 1 = the query window reverse-complemented: window bytes
+ * w[0 .. L) become w'[x] = comp[w[L - 1 - x]].  The reference window is never reversed.  comp is one fixed table of 256 bytes
+ * (pmx_complement_table): "ACGTUMRWSYKVHDBN" -> "TGCAAKYWSRMBDHVN", the lower-case letters the same way to lower case, every other
+ * byte to itself.  It is applied to the raw bytes before the matrix mapper, whatever the matrix (a caller aligning proteins passes no
+ * strands).  ALL POSITIONS OF A STRAND-1 PAIR -- end_query and beg_query alike -- ARE RELATIVE TO THE REVERSE-COMPLEMENTED WINDOW:
+ * position p of it is stored byte q_beg + L - 1 - p of the sequence.  A strand byte other than 0 or 1 is a bad descriptor: the device
+ * entry writes PMX_FLAG_BAD_PAIR, the host entry refuses and names the first such pair.
+ *
+ * Without PMX_WANT_CIGAR the _ex entries are pmx_align_pairs[_device] with the strand applied (record k and its statistics are what
+ * pmx_align_batch_device gives for the two resolved windows; with no strands the results are byte-identical to
+ * pmx_align_pairs_device); beg / d_beg and the text buffers must then be NULL.
+ *
+ * With PMX_WANT_CIGAR records, text and offsets are byte-identical to what pmx_align_batch_cigar_device writes for the same windows
+ * packed back to back: d_cigar_off holds n + 1 offsets from 0, d_cigar_off[n] is the number of bytes the batch needs, a pair whose
+ * text would cross cigar_capacity is not written.  d_beg (optional, 2 n) receives the walk's begin cell as pmx_hit_t documents it: the
+ * path's first cell, 0 / 0 for global and semi-global paths.  A bad pair gets {0, -1, -1, PMX_FLAG_BAD_PAIR}, an empty text
+ * (off[k + 1] == off[k]) and begins -1 / -1; every other pair is unaffected.  chunk_pairs never changes a byte of any output: every
+ * chunk's text starts at the running total, which stays on the device.  The window is that of pmx_align_batch_cigar_device -- no
+ * width 8, no PSSM, open >= extend, score + open within a byte, queries up to 1023 symbols; outside it both entries refuse with -1
+ * before any alignment runs (the check reads the maxima only) and point to pmx_align_batch_cigar.  PMX_WANT_CIGAR together with
+ * PMX_WANT_STATS is refused.  All-vs-all with CIGARs: pmx_all_pairs_enumerate_device, then the _ex entry.
+ *
+ * The host entry validates like pmx_align_pairs (strand bytes included; before any GPU work when both sets carry host offsets),
+ * uploads 32 + 1 bytes per pair and, for CIGAR, sizes the device text at half a byte per symbol + 16 per pair and runs once more at
+ * the exact size when the text did not fit.  *cigar_buf is a block released with pmx_free (NULL on failure), cigar_off has n + 1
+ * entries.  The device entry is asynchronous on `stream` under the rule of the other set entries (with strand bytes the chunk scratch
+ * is one byte per pair larger; the CIGAR road adds the scratch of pmx_align_batch_cigar_device for one chunk).  pmx_last_kernel() is
+ * what the last chunk's road left. */
+void pmx_complement_table(uint8_t table[256]);
+int pmx_align_pairs_ex_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                              int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand /* n bytes; NULL: all forward */,
+                              int32_t max_qlen, int32_t max_rlen,
+                              pmx_record_t *d_out, pmx_stats_t *d_stats_out,
+                              int32_t *d_beg /* 2 n: beg_query, beg_ref; optional, PMX_WANT_CIGAR only */,
+                              char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off /* n + 1; PMX_WANT_CIGAR only */,
+                              void *stream, const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_ex(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                       int64_t n, const pmx_pair_t *pairs, const uint8_t *strand,
+                       pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg,
+                       char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts);
+/* Building block and test hook: the resolved windows themselves (strand applied), packed back to back into d_qout / d_rout.  d_qoff /
+ * d_roff receive n + 1 offsets from 0; a window whose end would cross its capacity is not written (the pmx_gather_refs_device rule);
+ * a bad pair's placeholder is one zero byte on either side and d_ok[k] = 0 (d_ok: n validity bytes, optional).  No byte outside a
+ * set's buffer is read.  Asynchronous on `stream`. */
+int pmx_gather_pairs_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                            const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
+                            uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                            uint8_t *d_ok /* n validity bytes, optional */, void *stream);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

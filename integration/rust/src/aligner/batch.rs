@@ -157,6 +157,25 @@ extern "C" {
         max_qlen: i32, max_rlen: i32, d_out: *mut PmxRecord, d_stats_out: *mut PmxStats, stream: *mut c_void,
         opts: *const PmxPairsOpts,
     ) -> c_int;
+    /// The 256-byte complement a strand-1 query window is mapped through.
+    pub fn pmx_complement_table(table: *mut u8);
+    /// Set batches with one strand byte per pair (NULL: all forward) and, with PMX_WANT_CIGAR, CIGAR text (a block released with
+    /// pmx_free, `cigar_off` n + 1 entries) and the begins of the paths (2 n, optional).
+    pub fn pmx_align_pairs_ex(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, n: i64, pairs: *const PmxPair, strand: *const u8,
+        out: *mut PmxRecord, stats_out: *mut PmxStats, beg: *mut i32, cigar_buf: *mut *mut c_char, cigar_off: *mut i64,
+        opts: *const PmxPairsOpts,
+    ) -> c_int;
+    pub fn pmx_align_pairs_ex_device(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, n: i64, d_pairs: *const PmxPair, d_strand: *const u8,
+        max_qlen: i32, max_rlen: i32, d_out: *mut PmxRecord, d_stats_out: *mut PmxStats, d_beg: *mut i32,
+        d_cigar_text: *mut c_char, cigar_capacity: i64, d_cigar_off: *mut i64, stream: *mut c_void, opts: *const PmxPairsOpts,
+    ) -> c_int;
+    pub fn pmx_gather_pairs_device(
+        q: *const PmxSeqSet, r: *const PmxSeqSet, n: i64, d_pairs: *const PmxPair, d_strand: *const u8, max_qlen: i32, max_rlen: i32,
+        d_qout: *mut u8, q_capacity: i64, d_qoff: *mut i64, d_rout: *mut u8, r_capacity: i64, d_roff: *mut i64, d_ok: *mut u8,
+        stream: *mut c_void,
+    ) -> c_int;
     fn pmx_all_pairs_count(nseq: i64) -> i64;
     fn pmx_all_pairs_index(nseq: i64, p: i64, i: *mut i64, j: *mut i64) -> c_int;
     fn pmx_align_all_pairs(

@@ -209,6 +209,13 @@ _sig("pmx_align_pairs", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p
      C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_align_pairs_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_complement_table", None, C.c_void_p)
+_sig("pmx_align_pairs_ex", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_ex_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_gather_pairs_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_all_pairs_count", C.c_int64, C.c_int64)
 _sig("pmx_all_pairs_index", C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 _sig("pmx_align_all_pairs", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
@@ -840,11 +847,13 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return (out, stats) if stats is not None else out
 
-    def align_pairs(self, Q, R, pairs, chunk_pairs=0):
+    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False):
         """Pairs by index and window into device-resident sequence sets (SeqSet; Q may be R).  `pairs`: a PAIR_DTYPE array, or
         an iterable of (q, r) / (q, r, q_beg, q_len, r_beg, r_len) tuples (len -1: to the sequence's end).  Record k is the record
         of the pair (query window, reference window) k, end positions relative to the windows.  A bad descriptor raises BatchError
-        naming the first."""
+        naming the first.  `strand`: one byte per pair, 1 = the query window reverse-complemented (complement_table(); every
+        position of such a pair is relative to the reverse-complemented window).  cigar=True returns (records, CIGAR strings,
+        int32 [n, 2] begins of the paths) instead."""
         if not self._profile.is_null():
             raise BatchError("align_pairs takes no profile")
         pairs = as_pairs(pairs)
@@ -853,11 +862,32 @@ class Aligner:
         out = np.zeros(n, dtype=RECORD_DTYPE)
         stats = np.zeros(n, dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
         opts = pmx_pairs_opts_t(int(chunk_pairs))
-        rc = lib.pmx_align_pairs(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, out.ctypes.data,
-                                 stats.ctypes.data if stats is not None else None, C.byref(opts))
+        if strand is None and not cigar:
+            rc = lib.pmx_align_pairs(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, out.ctypes.data,
+                                     stats.ctypes.data if stats is not None else None, C.byref(opts))
+            if rc:
+                raise BatchError(lib.pmx_last_error().decode())
+            return (out, stats) if stats is not None else out
+        if strand is not None:
+            strand = np.ascontiguousarray(strand, dtype=np.uint8)
+            if len(strand) != n:
+                raise BatchError("strand and pairs differ in count")
+        sp = strand.ctypes.data if strand is not None else None
+        if not cigar:
+            rc = lib.pmx_align_pairs_ex(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, sp, out.ctypes.data,
+                                        stats.ctypes.data if stats is not None else None, None, None, None, C.byref(opts))
+            if rc:
+                raise BatchError(lib.pmx_last_error().decode())
+            return (out, stats) if stats is not None else out
+        cfg.want |= WANT_CIGAR
+        beg = np.zeros((n, 2), dtype=np.int32)
+        coff = np.zeros(n + 1, dtype=np.int64)
+        cbuf = C.c_void_p()
+        rc = lib.pmx_align_pairs_ex(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, sp, out.ctypes.data, None,
+                                    beg.ctypes.data, C.byref(cbuf), coff.ctypes.data, C.byref(opts))
         if rc:
             raise BatchError(lib.pmx_last_error().decode())
-        return (out, stats) if stats is not None else out
+        return out, _take_cigars(cbuf, coff), beg
 
     def align_all_pairs(self, S, first=0, count=None, chunk_pairs=0):
         """Pairs [first, first + count) of the strict upper triangle of S x S (row-major; all_pairs_index gives (i, j) of a
@@ -1196,6 +1226,33 @@ def align_pairs_device(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats
     opts = pmx_pairs_opts_t(int(chunk_pairs))
     rc = lib.pmx_align_pairs_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, max_qlen, max_rlen, d_out, d_stats, stream,
                                     C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def complement_table():
+    """The 256-byte complement a strand-1 query window is mapped through (uint8 [256])."""
+    tab = np.zeros(256, dtype=np.uint8)
+    lib.pmx_complement_table(tab.ctypes.data)
+    return tab
+
+
+def align_pairs_ex_device(cfg, Q, R, n, d_pairs, d_strand, max_qlen, max_rlen, d_out, d_stats=None, d_beg=None, d_text=None, capacity=0,
+                          d_text_off=None, stream=0, chunk_pairs=0):
+    """Device-pointer entry of the set batches with strands (d_strand: n bytes or None) and, with WANT_CIGAR in cfg.want, CIGAR text
+    (d_text / capacity / d_text_off as align_batch_cigar_device) and begins (d_beg: 2 n int32, optional)."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_align_pairs_ex_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, max_qlen, max_rlen, d_out, d_stats,
+                                       d_beg, d_text, capacity, d_text_off, stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def gather_pairs_device(Q, R, n, d_pairs, d_strand, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff,
+                        d_ok=None, stream=0):
+    """The resolved windows of n descriptors (strand applied), packed back to back in device memory; d_qoff / d_roff get n + 1 offsets."""
+    rc = lib.pmx_gather_pairs_device(Q._handle(), R._handle(), n, d_pairs, d_strand, max_qlen, max_rlen, d_qout, q_capacity, d_qoff,
+                                     d_rout, r_capacity, d_roff, d_ok, stream)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

@@ -611,6 +611,47 @@ public:
         if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
         return out;
     }
+    // additive: the same with one strand byte per pair (pmx_align_pairs_ex): 1 = the query window reverse-complemented, and every
+    // position of such a pair is relative to the reverse-complemented window.  A byte other than 0 / 1 throws, naming the pair.
+    std::vector<pmx_record_t> align_pairs(const SeqSet &Q, const SeqSet &R, const std::vector<pmx_pair_t> &pairs, const std::vector<uint8_t> &strand,
+                                          std::vector<pmx_stats_t> *stats = nullptr, int64_t chunk_pairs = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "align_pairs takes no profile");
+        if (strand.size() != pairs.size()) throw Error(ErrorKind::Batch, "strand and pairs differ in count");
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        std::vector<pmx_record_t> out(pairs.size());
+        if (cfg.want & PMX_WANT_STATS) { if (!stats) throw Error(ErrorKind::Batch, "stats aligner needs a stats vector"); stats->resize(pairs.size()); }
+        const pmx_pairs_opts_t opts = {chunk_pairs};
+        const int rc = pmx_align_pairs_ex(&cfg, Q.inner, R.inner, (int64_t)pairs.size(), pairs.data(), strand.data(), out.data(),
+                                          (cfg.want & PMX_WANT_STATS) ? stats->data() : nullptr, nullptr, nullptr, nullptr, &opts);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        return out;
+    }
+    // additive: the CIGAR variant (pmx_align_pairs_ex with PMX_WANT_CIGAR): records, each pair's CIGAR string and, when asked for, the
+    // first cell of each path (2 per pair: query, reference; 0 / 0 for global and semi-global paths).  strand == nullptr: all forward.
+    std::vector<pmx_record_t> align_pairs_cigar(const SeqSet &Q, const SeqSet &R, const std::vector<pmx_pair_t> &pairs,
+                                                const std::vector<uint8_t> *strand, std::vector<std::string> &cigars,
+                                                std::vector<int32_t> *begins = nullptr, int64_t chunk_pairs = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "align_pairs takes no profile");
+        if (strand && strand->size() != pairs.size()) throw Error(ErrorKind::Batch, "strand and pairs differ in count");
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        cfg.want = (cfg.want & ~PMX_WANT_STATS) | PMX_WANT_CIGAR;
+        std::vector<pmx_record_t> out(pairs.size());
+        std::vector<int64_t> coff(pairs.size() + 1);
+        if (begins) begins->resize(2 * pairs.size());
+        const pmx_pairs_opts_t opts = {chunk_pairs};
+        char *text = nullptr;
+        const int rc = pmx_align_pairs_ex(&cfg, Q.inner, R.inner, (int64_t)pairs.size(), pairs.data(), strand ? strand->data() : nullptr, out.data(),
+                                          nullptr, begins ? begins->data() : nullptr, &text, coff.data(), &opts);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        cigars.resize(pairs.size());
+        for (size_t k = 0; k < pairs.size(); ++k) cigars[k].assign(text + coff[k], text + coff[k + 1]);
+        pmx_free(text);
+        return out;
+    }
     // additive: pairs [first, first + count) of the strict upper triangle of S x S, row-major (all_pairs_index), whole sequences,
     // enumerated on the device (pmx_align_all_pairs).  count < 0: to the last pair.
     std::vector<pmx_record_t> align_all_pairs(const SeqSet &S, int64_t first = 0, int64_t count = -1,

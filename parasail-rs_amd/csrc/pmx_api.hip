@@ -1534,11 +1534,13 @@ struct SlotText {
         scan_bytes = text ? pmx_text_scan_scratch_bytes(n) : 0;
         scan = c.take<unsigned char>(scan_bytes);
     }
-    // slot of pair k: slot_qoff[k] + d_roff[k] + k - ops_base
+    // slot of pair k: slot_qoff[k] + d_roff[k] + k - ops_base.  local_off (n + 1 entries of scratch): the batch is a later chunk of a
+    // longer text -- d_text_off[0] already holds the total of the chunks before it and stays, the offsets continue from it
     int render(const int64_t *slot_qoff, const int64_t *d_roff, long long ops_base, int64_t n,
-               char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st) const
+               char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st, int64_t *local_off = nullptr) const
     {
-        int rc = pmx_launch_text_offsets(textlen, n, d_text_off, scan, scan_bytes, st);
+        int rc = pmx_launch_text_offsets(textlen, n, local_off ? local_off : d_text_off, scan, scan_bytes, st);
+        if (!rc && local_off) rc = pmx_launch_text_rebase(local_off, n, d_text_off, st);
         if (rc) { set_err("text offset scan failed (%d)", rc); return rc; }
         rc = pmx_launch_cigar_render_slots(ops, slot_qoff, d_roff, ops_base, nops, d_text_off, d_text, capacity, n, st);
         if (rc) { set_err("cigar render launch failed (%d)", rc); return rc; }
@@ -2487,10 +2489,28 @@ extern "C" int pmx_align_batch_table_device(const pmx_config_t *cfg, int64_t n,
 // run-length ops in per-pair slots and each pair's text length; one scan and one render finish the batch on the caller's stream.
 // 0 done (asynchronously on `st`), 1 not eligible for the packed traceback sweeps, <0 error.
 // The offset arrays are absolute into d_qbuf / d_rbuf; ops_base = qoff[0] + roff[0] (0 when the offsets start at 0).
+// What a set batch adds to the road (pmx_align_pairs_ex_device runs it once per chunk of pairs): the chunk's validity bytes -- a bad
+// pair gets its record, an empty text and begins -1 / -1 between the walk and the text scan --, the begins as an output, and the
+// text continuing behind the chunks before it (d_text_off[0] holds their total; d_text / capacity are the whole batch's).
+struct CigarChunkOf { const uint8_t *ok = nullptr; int32_t *beg = nullptr; bool continues = false; };
+static void set_err_no_cigar_road()
+{
+    set_err("this configuration has no device-resident CIGAR path (width 8, PSSM, open < extend, a matrix whose score + open "
+            "leaves a byte, or queries beyond 1023 symbols): use pmx_align_batch_cigar");
+}
+// The road's window, from the configuration and the maxima alone: true when cigar_device_run takes the batch.
+static bool cigar_device_eligible(const pmx_config_t *cfg, const DevMat &dm, int64_t n, int32_t mq, int32_t mr)
+{
+    if (cfg->width == 8 || cfg->matrix->type != PARASAIL_MATRIX_TYPE_SQUARE) return false;
+    const PmxBatch b = {nullptr, nullptr, nullptr, nullptr, n, mq, mr, 0, nullptr, nullptr, nullptr, 0, 0};
+    int variant = 0, Tmax = 0; size_t tbytes = 0;
+    return pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) == 0 && variant >= 10;
+}
 static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
                             const uint8_t *d_qbuf, const int64_t *d_qoff, const uint8_t *d_rbuf, const int64_t *d_roff,
                             int32_t mq, int32_t mr, long long ops_base,
-                            pmx_record_t *d_out, char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st)
+                            pmx_record_t *d_out, char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st,
+                            const CigarChunkOf &set = CigarChunkOf())
 {
     if (cfg->width == 8 || cfg->matrix->type != PARASAIL_MATRIX_TYPE_SQUARE) return 1;
     PmxBatch b = {d_qbuf, d_qoff, d_rbuf, d_roff, n, mq, mr, 0, nullptr, nullptr, nullptr, 0, 0};
@@ -2501,17 +2521,22 @@ static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n
     // fewer launch tails), at most 15 % of the free HBM each, at least two for the overlap once the batch is worth it
     const int64_t chunk = chunk_pairs(n, (double)tbytes, chunk_budget(12e9, 0.15, pmx_env("PMX_CIGAR_CHUNK_BYTES")), n >= 16384 ? 2 : 1);
     const bool two = chunk < n && !pmx_env("PMX_CIGAR_NO_OVERLAP");     // (diagnostics: sweep and walk back to back on one stream)
-    SlotText t; int32_t *beg = nullptr; int *bflags = nullptr;
+    SlotText t; int32_t *beg = nullptr; int *bflags = nullptr; int64_t *local_off = nullptr;
     if (t.reserve_ops((size_t)n * ((size_t)mq + mr + 1)) ||
         scratch_carve(SCR_CIG, [&](Carver &c) {
             t.carve(c, n);
             beg = c.take<int32_t>(2 * (size_t)n);
             bflags = c.take<int>(2 * trace_flag_stride(chunk));
+            if (set.ok) local_off = c.take<int64_t>((size_t)n + 1);      // (every chunk of a set batch: the largest comes first, no later chunk grows the block)
         })) return -1;
-    const TraceOutputs o = {nullptr, t.ops, ops_base, t.nops, beg, t.textlen};
+    if (!set.continues) local_off = nullptr;
+    const TraceOutputs o = {nullptr, t.ops, ops_base, t.nops, set.beg ? set.beg : beg, t.textlen};
     int rc = trace_chunks(cfg, dm, b, chunk, two, bflags, d_out, o, st, "traceback launch failed", &variant);
     if (rc) return rc;
-    rc = t.render(d_qoff, d_roff, ops_base, n, d_text, capacity, d_text_off, st);
+    if (set.ok && (rc = pmx_launch_pairs_fixup_cigar(set.ok, n, d_out, t.nops, t.textlen, set.beg, st)) != 0) {
+        set_err("bad-pair fix-up launch failed (%d)", rc); return rc;
+    }
+    rc = t.render(d_qoff, d_roff, ops_base, n, d_text, capacity, d_text_off, st, local_off);
     if (rc) return rc;
     g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : nwsg_trace_kernel_name(" + pmx_walkp_kernel");
     return 0;
@@ -2534,8 +2559,7 @@ extern "C" int pmx_align_batch_cigar_device(const pmx_config_t *cfg, int64_t n,
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const int rc = cigar_device_run(cfg, dm, n, d_qbuf, d_qoff, d_rbuf, d_roff, max_qlen, max_rlen, 0, d_out,
                                     d_cigar_text, cigar_capacity, d_cigar_off, (hipStream_t)stream);
-    if (rc == 1) set_err("this configuration has no device-resident CIGAR path (width 8, PSSM, open < extend, a matrix whose score + open "
-                         "leaves a byte, or queries beyond 1023 symbols): use pmx_align_batch_cigar");
+    if (rc == 1) set_err_no_cigar_road();
     return rc == 1 ? -1 : rc;
 }
 
@@ -2712,11 +2736,7 @@ static int cigar_host_pipelined(const pmx_config_t *cfg, const DevMat &dm, int64
     int32_t mq = 0, mr = 0; bool bad = false;
     host_maxlens(n, qoff, &mq, &bad); host_maxlens(n, roff, &mr, &bad);
     if (bad) { set_err("every sequence must have length >= 1"); return -1; }
-    {   // eligibility before anything is staged
-        PmxBatch b = {nullptr, nullptr, nullptr, nullptr, n, mq, mr, 0, nullptr, nullptr, nullptr, 0, 0};
-        int variant = 0, Tmax = 0; size_t tbytes = 0;
-        if (cfg->width == 8 || pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) != 0 || variant < 10) return 1;
-    }
+    if (!cigar_device_eligible(cfg, dm, n, mq, mr)) return 1;          // before anything is staged
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t s_copy = hs.copy, s_comp = hs.comp; hipEvent_t *const s_up = hs.up, *const s_done = hs.done;
@@ -3683,13 +3703,13 @@ static int64_t pairs_chunk(int64_t n, int32_t max_qlen, int32_t max_rlen, const 
     return chunk > n ? n : chunk;
 }
 
-// Everything a set batch refuses before any GPU work, shared by the four entries (R == Q for the all-pairs entries).
+// Everything a set batch refuses before any GPU work, shared by the entries (R == Q for the all-pairs entries).
 static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, const pmx_pairs_opts_t *opts,
-                       int32_t max_qlen, int32_t max_rlen, bool stats_buffer)
+                       int32_t max_qlen, int32_t max_rlen, bool stats_buffer, bool ex = false /* pmx_align_pairs_ex[_device]: CIGAR is taken */)
 {
     if (check_cfg(cfg)) return -1;
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (cfg->want & PMX_WANT_CIGAR) { set_err("set batches have no CIGAR output"); return -1; }
+    if ((cfg->want & PMX_WANT_CIGAR) && !ex) { set_err("this set-batch entry has no CIGAR output: pmx_align_pairs_ex[_device] has"); return -1; }
     if ((cfg->want & PMX_WANT_STATS) && !stats_buffer) { set_err("stats requested without a stats buffer"); return -1; }
     if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
     if (pssm_batch_check(cfg->matrix, max_qlen, max_qlen)) return -1;
@@ -3702,15 +3722,18 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 }
 
 // The pair materialiser and the chunk loop.  Chunk c: (enumerate,) resolve, two offset scans and the gather on `prep` into buffer set
-// c & 1, then -- behind packed[c & 1] -- the alignment and the fix-up of bad pairs on the caller's stream, in chunk order:
-// run_batch_device keeps per-thread scratch and never runs twice at once.  aligned[c & 1] lets chunk c + 2's gather overwrite the set.
-// Everything `prep` does is waited for by `st`, so `st` ends behind the last fix-up and behind `prep`.  One chunk: all on `st`.
-// d_pairs == nullptr: pairs [first, first + n) of the upper triangle of Q x Q, generated per chunk.
-struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok; };
-static int pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first,
-                     int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out, hipStream_t st, int64_t chunk)
+// c & 1, then -- behind packed[c & 1] -- body(c0, cn, buffers), the chunk's alignment, on the caller's stream, in chunk order: the
+// alignment roads keep per-thread scratch (the CIGAR road internal streams too) and never run twice at once.  aligned[c & 1] lets chunk
+// c + 2's gather overwrite the set.  Everything `prep` does is waited for by `st`, so `st` ends behind the last body and behind `prep`.
+// One chunk: all on `st`.  d_pairs == nullptr: pairs [first, first + n) of the upper triangle of Q x Q, generated per chunk.
+// d_strand != nullptr (the _ex entries): the resolve step takes the strand bytes and the gather is the one that can reverse-complement;
+// otherwise the forward-only kernels run, and a forward batch pays nothing for the strands' existence.
+struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; };
+template <typename Body>
+static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first,
+                     const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body)
 {
-    const bool two = chunk < n, stats = (cfg->want & PMX_WANT_STATS) != 0;
+    const bool two = chunk < n, stranded = d_strand != nullptr;
     PairsChunkBufs B[2]; void *scan = nullptr; pmx_pair_t *gen = nullptr;
     const size_t scan_bytes = pmx_text_scan_scratch_bytes(chunk);
     if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
@@ -3721,6 +3744,7 @@ static int pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seq
                 B[s].qoff = c.take<int64_t>((size_t)chunk + 1); B[s].roff = c.take<int64_t>((size_t)chunk + 1);
                 B[s].qsrc = c.take<int64_t>((size_t)chunk); B[s].rsrc = c.take<int64_t>((size_t)chunk);
                 B[s].ok = c.take<uint8_t>((size_t)chunk);
+                B[s].sflag = stranded ? c.take<uint8_t>((size_t)chunk) : nullptr;
             }
             scan = c.take<unsigned char>(scan_bytes);           // (one: the scans of all chunks run in order on one stream)
         })) return -1;
@@ -3736,12 +3760,17 @@ static int pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seq
         const PairsChunkBufs &b = B[slot];
         const pmx_pair_t *pc = d_pairs ? d_pairs + c0 : gen + (size_t)slot * (size_t)chunk;
         int rc = d_pairs ? 0 : pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gen + (size_t)slot * (size_t)chunk, prep);
-        if (!rc) rc = pmx_launch_pairs_resolve(pc, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                               b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
+        if (!rc) rc = stranded ? pmx_launch_pairs_resolve_stranded(pc, d_strand + c0, cn, Q->d_off, Q->count, Q->bytes,
+                                                                   R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                                                   b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
+                               : pmx_launch_pairs_resolve(pc, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                                          b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.qlen, cn, b.qoff, scan, scan_bytes, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.rlen, cn, b.roff, scan, scan_bytes, prep);
-        if (!rc) rc = pmx_launch_pairs_gather(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
-                                              b.qoff, b.roff, b.q, b.r, prep);
+        if (!rc) rc = stranded ? pmx_launch_pairs_gather_stranded(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
+                                                                  b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, prep)
+                               : pmx_launch_pairs_gather(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
+                                                         b.qoff, b.roff, b.q, b.r, prep);
         if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
         if (two) HIP_OR_RET(hipEventRecord(g_pws.packed[slot], prep));
         return 0;
@@ -3758,14 +3787,27 @@ static int pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seq
             if (rc) return rc;
         }
         if (two) HIP_OR_RET(hipStreamWaitEvent(st, g_pws.packed[slot], 0));
-        const PairsChunkBufs &b = B[two ? slot : 0];
-        rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
+        rc = body(c0, cn, B[two ? slot : 0]);
         if (rc) return rc;
-        rc = pmx_launch_pairs_fixup(b.ok, cn, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
-        if (rc) { set_err("bad-pair fix-up launch failed (%d)", rc); return rc; }
         if (two) HIP_OR_RET(hipEventRecord(g_pws.aligned[slot], st));
     }
     return 0;
+}
+
+// The score road of a set batch: every chunk through run_batch_device, then the records (and statistics) of its bad pairs.
+static int pairs_run_scores(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first,
+                            const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
+                            pmx_record_t *d_out, pmx_stats_t *d_stats_out, hipStream_t st, int64_t chunk)
+{
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    return pairs_run(Q, R, n, d_pairs, first, d_strand, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            int rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
+            if (rc) return rc;
+            rc = pmx_launch_pairs_fixup(b.ok, cn, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
+            if (rc) { set_err("bad-pair fix-up launch failed (%d)", rc); return rc; }
+            return 0;
+        });
 }
 
 extern "C" int pmx_align_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -3781,7 +3823,107 @@ extern "C" int pmx_align_pairs_device(const pmx_config_t *cfg, const pmx_seqset_
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run(cfg, Q, R, n, d_pairs, 0, max_qlen, max_rlen, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts));
+    return pairs_run_scores(cfg, Q, R, n, d_pairs, 0, nullptr, max_qlen, max_rlen, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts));
+}
+
+// ---- strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device) ----
+extern "C" void pmx_complement_table(uint8_t table[256]) { if (table) pmx_complement_table_host(table); }
+
+// What the _ex entries refuse about their outputs, before any GPU work.  text: d_cigar_text / cigar_buf.
+static int pairs_ex_outputs_check(const pmx_config_t *cfg, const void *beg, const void *text, int64_t capacity, const void *text_off)
+{
+    if (cfg->want & PMX_WANT_CIGAR) {
+        if (cfg->want & PMX_WANT_STATS) { set_err("PMX_WANT_CIGAR together with PMX_WANT_STATS is not offered by set batches (the walk does one of the two)"); return -1; }
+        if (!text || !text_off) { set_err("null cigar output"); return -1; }
+        if (capacity < 0) { set_err("negative cigar_capacity"); return -1; }
+    } else if (beg || text || text_off) { set_err("begins and CIGAR buffers need PMX_WANT_CIGAR in cfg->want"); return -1; }
+    return 0;
+}
+
+// The CIGAR road of a set batch: every chunk's packed windows through cigar_device_run, which fixes the chunk's bad pairs up and
+// continues the text behind the chunks before it (d_cigar_off[c0], left by the previous chunk on the same stream).  The caller has
+// checked the road's window.
+static int pairs_run_cigar(const pmx_config_t *cfg, const DevMat &dm, const pmx_seqset *Q, const pmx_seqset *R, int64_t n,
+                           const pmx_pair_t *d_pairs, const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
+                           pmx_record_t *d_out, int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st, int64_t chunk)
+{
+    return pairs_run(Q, R, n, d_pairs, 0, d_strand, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            CigarChunkOf set; set.ok = b.ok; set.beg = d_beg ? d_beg + 2 * c0 : nullptr; set.continues = c0 > 0;
+            const int rc = cigar_device_run(cfg, dm, cn, b.q, b.qoff, b.r, b.roff, max_qlen, max_rlen, 0, d_out + c0,
+                                            d_text, capacity, d_text_off + c0, st, set);
+            if (rc == 1) set_err_no_cigar_road();
+            return rc == 1 ? -1 : rc;
+        });
+}
+
+// Both roads behind the checks the two _ex entries share; asynchronous on `st`.
+static int pairs_ex_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
+                        const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out,
+                        int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st, const pmx_pairs_opts_t *opts)
+{
+    const int64_t chunk = pairs_chunk(n, max_qlen, max_rlen, opts);
+    if (!(cfg->want & PMX_WANT_CIGAR))
+        return pairs_run_scores(cfg, Q, R, n, d_pairs, 0, d_strand, max_qlen, max_rlen, d_out, d_stats_out, st, chunk);
+    DevMat dm;
+    if (get_devmat(cfg->matrix, &dm)) return -1;
+    if (!cigar_device_eligible(cfg, dm, chunk, max_qlen, max_rlen)) { set_err_no_cigar_road(); return -1; }
+    return pairs_run_cigar(cfg, dm, Q, R, n, d_pairs, d_strand, max_qlen, max_rlen, d_out, d_beg, d_text, capacity, d_text_off, st, chunk);
+}
+
+extern "C" int pmx_align_pairs_ex_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                         int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
+                                         pmx_record_t *d_out, pmx_stats_t *d_stats_out, int32_t *d_beg,
+                                         char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream, const pmx_pairs_opts_t *opts)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || pairs_ex_outputs_check(cfg, d_beg, d_cigar_text, cigar_capacity, d_cigar_off)) return -1;
+    if (n == 0) return 0;
+    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr, true)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_ex_run(cfg, Q, R, n, d_pairs, d_strand, max_qlen, max_rlen, d_out, d_stats_out, d_beg, d_cigar_text, cigar_capacity, d_cigar_off,
+                        (hipStream_t)stream, opts);
+}
+
+extern "C" int pmx_gather_pairs_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                       const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
+                                       uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                       uint8_t *d_ok, void *stream)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
+    if (!d_qoff || !d_roff || (n > 0 && (!d_pairs || !d_qout || !d_rout))) { set_err("null buffer"); return -1; }
+    if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    if (n == 0) return 0;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (Q->dev != dev || R->dev != dev) {
+        set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev != dev ? Q->dev : R->dev, dev); return -1;
+    }
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    int32_t *qlen = nullptr, *rlen = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
+    const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
+    if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
+            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2);
+            qsrc = c.take<int64_t>((size_t)n); rsrc = c.take<int64_t>((size_t)n);
+            ok = c.take<uint8_t>((size_t)n); sflag = c.take<uint8_t>((size_t)n);
+            scan = c.take<unsigned char>(scan_bytes);
+        })) return -1;
+    if (d_ok) ok = d_ok;
+    int rc = pmx_launch_pairs_resolve_stranded(d_pairs, d_strand, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                               qlen, rlen, qsrc, rsrc, ok, sflag, st);
+    if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_pairs_gather_stranded(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
+                                                   d_qout, q_capacity, d_rout, r_capacity, st);
+    if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
+    return 0;
 }
 
 // The all-pairs window [first, first + count) of a set: 0, or -1 with the cause.
@@ -3810,7 +3952,7 @@ extern "C" int pmx_align_all_pairs_device(const pmx_config_t *cfg, const pmx_seq
     if (pairs_check(cfg, S, S, opts, max_len, max_len, d_stats_out != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run(cfg, S, S, count, nullptr, first, max_len, max_len, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(count, max_len, max_len, opts));
+    return pairs_run_scores(cfg, S, S, count, nullptr, first, nullptr, max_len, max_len, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(count, max_len, max_len, opts));
 }
 
 extern "C" int pmx_all_pairs_enumerate_device(int64_t nseq, int64_t first, int64_t count, pmx_pair_t *d_pairs, void *stream)
@@ -3838,7 +3980,7 @@ static const char *host_resolve_side(const std::vector<int64_t> &off, int64_t co
 }
 
 // Pairs [a, e) against the host offsets: the first bad one (what is wrong with which side), or the extreme window lengths.
-struct PairScan { int64_t bad = -1; const char *what = nullptr, *side = nullptr; int64_t mq = 1, mr = 1, mnr = INT32_MAX; };
+struct PairScan { int64_t bad = -1; const char *what = nullptr, *side = nullptr; int64_t mq = 1, mr = 1, mnr = INT32_MAX, symbols = 0; };
 static PairScan scan_pairs(const pmx_seqset *Q, const pmx_seqset *R, const pmx_pair_t *pairs, int64_t a, int64_t e)
 {
     PairScan s;
@@ -3848,7 +3990,7 @@ static PairScan scan_pairs(const pmx_seqset *Q, const pmx_seqset *R, const pmx_p
         const char *side = "query";
         if (!what) { what = host_resolve_side(R->h_off, R->count, pairs[k].r, pairs[k].r_beg, pairs[k].r_len, &rl); side = "reference"; }
         if (what) { s.bad = k; s.what = what; s.side = side; return s; }
-        s.mq = ql > s.mq ? ql : s.mq; s.mr = rl > s.mr ? rl : s.mr; s.mnr = rl < s.mnr ? rl : s.mnr;
+        s.mq = ql > s.mq ? ql : s.mq; s.mr = rl > s.mr ? rl : s.mr; s.mnr = rl < s.mnr ? rl : s.mnr; s.symbols += ql + rl;
     }
     return s;
 }
@@ -3880,17 +4022,26 @@ static int pairs_copy_back(int64_t n, const pmx_record_t *drec, const pmx_stats_
     return 0;
 }
 
-extern "C" int pmx_align_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
-                               int64_t n, const pmx_pair_t *pairs, pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts)
+// The host entries over listed pairs.  ex: pmx_align_pairs_ex -- strand bytes (may be NULL), and with PMX_WANT_CIGAR the begins (may be
+// NULL) and the text, which follows traced_host_batch: a device buffer of half a byte per symbol + 16 per pair, one more run at the exact
+// size when the text did not fit, a block for the caller released with pmx_free.
+static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *pairs, const uint8_t *strand,
+                      pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts, bool ex)
 {
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
     if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
+    if (ex && pairs_ex_outputs_check(cfg, beg, cigar_buf, 0, cigar_off)) return -1;
+    const bool cigar = ex && (cfg->want & PMX_WANT_CIGAR) != 0;
+    if (cigar) { *cigar_buf = nullptr; cigar_off[0] = 0; }
     if (n == 0) return 0;
+    if (strand)
+        for (int64_t k = 0; k < n; ++k)
+            if (strand[k] > 1) { set_err("pair %lld: strand byte %d is neither 0 nor 1", (long long)k, (int)strand[k]); return -1; }
     const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
-    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
+    int64_t mq = 1, mr = 1, mnr = INT32_MAX, symbols = 0;
     if (host_offsets) {
         // large batches: the scan is a few nanoseconds per pair of random reads into the offsets -- measured at 2.1 ms per million
         // pairs on one core, of a 6.9 ms call -- so it is cut into slices on helper threads, merged in pair order
@@ -3907,18 +4058,23 @@ extern "C" int pmx_align_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
         for (int t = 0; t < T; ++t) {
             const PairScan &s = part[t];
             if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
-            mq = s.mq > mq ? s.mq : mq; mr = s.mr > mr ? s.mr : mr; mnr = s.mnr < mnr ? s.mnr : mnr;
+            mq = s.mq > mq ? s.mq : mq; mr = s.mr > mr ? s.mr : mr; mnr = s.mnr < mnr ? s.mnr : mnr; symbols += s.symbols;
         }
     }
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr)) return -1;
+    if (pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr, ex)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
-    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
-    if (scratch_reserve(sizeof(pmx_pair_t) * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
+    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr; uint8_t *dstrand = nullptr;
+    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the strand bytes
+    if (scratch_reserve(up_bytes + (strand ? (size_t)n : 0), (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
         (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
     HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (strand) {
+        dstrand = (uint8_t *)dp + up_bytes;
+        HIP_OR_RET(hipMemcpyAsync(dstrand, strand, (size_t)n, hipMemcpyHostToDevice, st));
+    }
     int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
     pmx_config_t cfg_s = *cfg;
     if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
@@ -3926,10 +4082,53 @@ extern "C" int pmx_align_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
         if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
         if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
     }
-    const int rc = pairs_run(&cfg_s, Q, R, n, dp, 0, q32, r32, drec, dst, st, pairs_chunk(n, q32, r32, opts));
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    return pairs_copy_back(n, drec, dst, out, stats_out, !host_offsets, st);
+    if (!cigar) {
+        const int rc = pairs_ex_run(&cfg_s, Q, R, n, dp, dstrand, q32, r32, drec, dst, nullptr, nullptr, 0, nullptr, st, opts);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        return pairs_copy_back(n, drec, dst, out, stats_out, !host_offsets, st);
+    }
+    if (!host_offsets) symbols = (int64_t)n * ((int64_t)q32 + r32);          // (wrapped sets: the lengths stayed on the device)
+    int64_t capacity = symbols / 2 + 16 * n + 256;
+    DevBuf<int64_t> dtoff; DevBuf<int32_t> dbeg; DevBuf<char> dtext;
+    if (dtoff.try_alloc((size_t)n + 1) || (beg && dbeg.try_alloc(2 * (size_t)n)) || dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    for (int pass = 0; pass < 2; ++pass) {
+        const int rc = pairs_ex_run(&cfg_s, Q, R, n, dp, dstrand, q32, r32, drec, nullptr, dbeg.p, dtext.p, capacity, dtoff.p, st, opts);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_OR_RET(hipMemcpyAsync(cigar_off, dtoff.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipStreamSynchronize(st));
+        if (cigar_off[n] <= capacity) break;
+        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
+        (void)hipFree(dtext.p); dtext.p = nullptr;
+        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    }
+    const int rc = pairs_copy_back(n, drec, nullptr, out, nullptr, !host_offsets, st);
+    if (rc) return rc;
+    if (beg) HIP_OR_RET(hipMemcpy(beg, dbeg.p, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+    TextBuf text;
+    char *dst_text = text.grow((size_t)cigar_off[n]);
+    if (!dst_text) { set_err("out of memory"); return -1; }
+    if (cigar_off[n]) {
+        const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
+    }
+    text.len = (size_t)cigar_off[n];
+    return publish_text(text, cigar_buf);
 }
+
+extern "C" int pmx_align_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                               int64_t n, const pmx_pair_t *pairs, pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts)
+{
+    return pairs_host(cfg, Q, R, n, pairs, nullptr, out, stats_out, nullptr, nullptr, nullptr, opts, false);
+}
+
+extern "C" int pmx_align_pairs_ex(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                  int64_t n, const pmx_pair_t *pairs, const uint8_t *strand,
+                                  pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg,
+                                  char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts)
+{
+    return pairs_host(cfg, Q, R, n, pairs, strand, out, stats_out, beg, cigar_buf, cigar_off, opts, true);
+}
+
 
 extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
                                    pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts)
@@ -3976,7 +4175,7 @@ extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *
         if (device_maxlens(S, S, nullptr, S->count, &m32, &unused, st)) return -1;
         if (pssm_batch_check(cfg->matrix, m32, m32)) return -1;
     }
-    const int rc = pairs_run(&cfg_s, S, S, count, nullptr, first, m32, m32, drec, dst, st, pairs_chunk(count, m32, m32, opts));
+    const int rc = pairs_run_scores(&cfg_s, S, S, count, nullptr, first, nullptr, m32, m32, drec, dst, st, pairs_chunk(count, m32, m32, opts));
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     return pairs_copy_back(count, drec, dst, out, stats_out, !host_offsets, st);
 }

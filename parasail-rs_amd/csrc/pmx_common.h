@@ -265,6 +265,21 @@ int pmx_launch_pairs_gather(long long n, const uint8_t *q_buf, long long q_bytes
                             const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
                             const int64_t *qoff, const int64_t *roff, uint8_t *qout, uint8_t *rout, hipStream_t stream);
 int pmx_launch_pairs_fixup(const uint8_t *ok, long long n, pmx_record_t *rec, pmx_stats_t *stats /* may be NULL */, hipStream_t stream);
+// With strands (the _ex entries).  strand: n bytes or NULL (all forward); sflag[k] = pair k's strand, a byte above 1 makes the pair bad.
+int pmx_launch_pairs_resolve_stranded(const pmx_pair_t *pairs, const uint8_t *strand, long long n,
+                                      const int64_t *q_off, long long q_count, long long q_bytes,
+                                      const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                                      int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream);
+// The gather that can reverse-complement the query side; a window whose end would cross q_cap / r_cap is not written.
+int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
+                                     const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
+                                     const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
+                                     uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, hipStream_t stream);
+// Bad pairs of a chunk on the device CIGAR road, between the walk and the text scan: record, no ops, no text, begins -1 / -1 (beg may be NULL).
+int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *rec, int32_t *nops, int32_t *textlen, int32_t *beg, hipStream_t stream);
+// A chunk's text offsets behind the running total: text_off[j] = text_off[0] + local[j], j = 1 .. n (text_off[0] is the total so far).
+int pmx_launch_text_rebase(const int64_t *local, long long n, int64_t *text_off, hipStream_t stream);
+void pmx_complement_table_host(uint8_t table[256]);
 int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long count, pmx_pair_t *pairs, hipStream_t stream);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,

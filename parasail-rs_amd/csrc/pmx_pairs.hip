@@ -7,6 +7,11 @@
 //   pmx_pairs_fixup_kernel          the records (and statistics) of bad pairs, after the chunk's alignment
 //   pmx_all_pairs_enumerate_kernel  p -> (i, j) of the strict upper triangle, whole-sequence descriptors
 //   pmx_pairs_maxlen_kernel         the longest resolved window per side (host entries over wrapped sets)
+// and, for the entries with strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device):
+//   pmx_pairs_resolve_stranded_kernel   the resolve step with the pair's strand byte
+//   pmx_pairs_gather_stranded_kernel    the gather that can reverse-complement a query window
+//   pmx_pairs_fixup_cigar_kernel        bad pairs on the CIGAR road: record, empty text, begins
+//   pmx_text_rebase_kernel              a chunk's text offsets behind the running total of the chunks before it
 //
 // All of them are bandwidth kernels in plain C++: vector loads and stores only.
 #include "pmx_common.h"
@@ -90,6 +95,133 @@ void pmx_pairs_gather_kernel(long long n, const uint8_t *__restrict__ q_buf, lon
     }
     const long long done = head + 4 * nd;
     if (lane < len - done) dst[done + lane] = src[done + lane];
+}
+
+// ---- strands (the _ex entries) --------------------------------------------------------------------------------------------------
+// The complement of include/parasail_amd.h: IUPAC letters in both cases, every other byte itself.
+struct PmxCompTable { uint8_t v[256]; };
+static constexpr PmxCompTable pmx_make_comp_table()
+{
+    PmxCompTable t{};
+    for (int i = 0; i < 256; ++i) t.v[i] = (uint8_t)i;
+    const char from[] = "ACGTUMRWSYKVHDBN", to[] = "TGCAAKYWSRMBDHVN";
+    for (int k = 0; k < 16; ++k) {
+        t.v[(unsigned char)from[k]] = (uint8_t)to[k];
+        t.v[(unsigned char)from[k] + 32] = (uint8_t)(to[k] + 32);
+    }
+    return t;
+}
+static constexpr PmxCompTable pmx_comp_host = pmx_make_comp_table();
+__device__ const PmxCompTable pmx_comp_dev = pmx_make_comp_table();
+
+// pmx_pairs_resolve_kernel with the pair's strand byte: 0 / 1 go to sflag, anything else makes the pair bad.
+__global__ __launch_bounds__(256)
+void pmx_pairs_resolve_stranded_kernel(const pmx_pair_t *__restrict__ pairs, const uint8_t *__restrict__ strand, long long n,
+                                       const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
+                                       const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
+                                       int32_t max_qlen, int32_t max_rlen,
+                                       int32_t *__restrict__ qlen, int32_t *__restrict__ rlen,
+                                       int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n + 2) return;
+    if (k >= n) { qlen[k] = 0; rlen[k] = 0; return; }          // (the scan reads n + 1 lengths)
+    const pmx_pair_t p = pairs[k];
+    const unsigned sb = strand ? strand[k] : 0u;
+    long long qs = 0, rs = 0;
+    int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, max_qlen, &qs);
+    int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
+    const bool good = ql > 0 && rl > 0 && sb <= 1u;
+    if (!good) { ql = 1; rl = 1; qs = 0; rs = 0; }
+    qlen[k] = ql; rlen[k] = rl; qsrc[k] = qs; rsrc[k] = rs; ok[k] = good ? 1 : 0; sflag[k] = good ? (uint8_t)sb : 0;
+}
+
+// The four bytes at s (anywhere inside a window of the set [lo_bound, hi_bound)) as the gather kernel above reads them: from the one or
+// two aligned dwords that hold them, or byte by byte where those would reach outside the set.
+static __device__ __forceinline__ uint32_t pmx_window_dword(const uint8_t *s, uintptr_t lo_bound, uintptr_t hi_bound)
+{
+    const uintptr_t sa = (uintptr_t)s & ~(uintptr_t)3;
+    const unsigned sh = (unsigned)((uintptr_t)s & 3);
+    if (sa >= lo_bound && sa + (sh ? 8 : 4) <= hi_bound) {
+        const uint32_t lo = *reinterpret_cast<const uint32_t *>(sa);
+        const uint32_t hi = sh ? *reinterpret_cast<const uint32_t *>(sa + 4) : 0u;
+        return __builtin_amdgcn_alignbyte(hi, lo, sh);
+    }
+    return (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
+}
+
+// The gather of pmx_pairs_gather_kernel for both strands: the same 16-lane group per window, the same forward walk over the
+// destination in aligned dwords.  A strand-1 query window is read backwards: destination byte x is comp[src[len - 1 - x]], so the
+// destination dword at bytes p .. p + 3 holds source bytes len - 4 - p .. len - 1 - p in reversed order -- assembled like a forward
+// dword from the aligned source dwords around them (the same in-bounds test, the same byte-by-byte fallback at a set's first and
+// last bytes), reversed by one v_perm, complemented by four byte reads of the table staged in LDS.  The strand is uniform per group
+// (not per wave: a wave holds four windows), so the branch sits outside the dword loop.  A window whose end would cross its
+// capacity is not written (the chunk pipeline passes no limit).
+__global__ __launch_bounds__(256)
+void pmx_pairs_gather_stranded_kernel(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes, const uint8_t *__restrict__ r_buf, long long r_bytes,
+                                      const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen,
+                                      const int64_t *__restrict__ qsrc, const int64_t *__restrict__ rsrc, const uint8_t *__restrict__ ok,
+                                      const uint8_t *__restrict__ sflag, const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
+                                      uint8_t *__restrict__ qout, long long q_cap, uint8_t *__restrict__ rout, long long r_cap)
+{
+    __shared__ uint8_t comp[256];
+    comp[threadIdx.x] = pmx_comp_dev.v[threadIdx.x];
+    __syncthreads();
+    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
+    const int lane = threadIdx.x & 15;
+    if (g >= 2 * n) return;
+    const long long k = g >> 1;
+    const bool side = (g & 1) != 0;
+    const int64_t o0 = side ? roff[k] : qoff[k], o1 = side ? roff[k + 1] : qoff[k + 1];
+    if (o1 > (side ? r_cap : q_cap)) return;
+    uint8_t *dst = (side ? rout : qout) + o0;
+    if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
+    const uint8_t *buf = side ? r_buf : q_buf;
+    const long long len = side ? rlen[k] : qlen[k];
+    const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
+    const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
+    long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
+    if (head > len) head = len;
+    const long long nd = (len - head) >> 2, done = head + 4 * nd;
+    uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
+    if (!side && sflag[k]) {
+        const uint8_t *last = src + len - 1;                    // destination byte x <- comp[last[-x]]
+        if (lane < head) dst[lane] = comp[last[-lane]];
+        const uint8_t *s0 = last - head - 3;                    // the lowest source byte of destination dword 0
+        for (long long x = lane; x < nd; x += 16) {
+            const uint32_t v = __builtin_amdgcn_perm(0u, pmx_window_dword(s0 - 4 * x, lo_bound, hi_bound), 0x00010203u);      // bytes 3 2 1 0
+            d0[x] = (uint32_t)comp[v & 0xFF] | ((uint32_t)comp[(v >> 8) & 0xFF] << 8) | ((uint32_t)comp[(v >> 16) & 0xFF] << 16) |
+                    ((uint32_t)comp[v >> 24] << 24);
+        }
+        if (lane < len - done) dst[done + lane] = comp[last[-(done + lane)]];
+        return;
+    }
+    if (lane < head) dst[lane] = src[lane];
+    const uint8_t *s0 = src + head;
+    for (long long x = lane; x < nd; x += 16)
+        d0[x] = pmx_window_dword(s0 + 4 * x, lo_bound, hi_bound);
+    if (lane < len - done) dst[done + lane] = src[done + lane];
+}
+
+// Bad pairs on the device CIGAR road, between the walk and the text scan: the record, no ops, no text, begins -1 / -1.
+__global__ __launch_bounds__(256)
+void pmx_pairs_fixup_cigar_kernel(const uint8_t *__restrict__ ok, long long n, pmx_record_t *__restrict__ rec,
+                                  int32_t *__restrict__ nops, int32_t *__restrict__ textlen, int32_t *__restrict__ beg)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n || ok[k]) return;
+    pmx_record_t r; r.score = 0; r.end_query = -1; r.end_ref = -1; r.flags = PMX_FLAG_BAD_PAIR;
+    rec[k] = r; nops[k] = 0; textlen[k] = 0;
+    if (beg) { beg[2 * k] = -1; beg[2 * k + 1] = -1; }
+}
+
+// A later chunk's text offsets: its own scan (from 0) behind the running total the previous chunk left in text_off[0].
+__global__ __launch_bounds__(256)
+void pmx_text_rebase_kernel(const int64_t *__restrict__ local, long long n, int64_t *text_off)
+{
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x + 1;
+    if (j > n) return;
+    text_off[j] = text_off[0] + local[j];
 }
 
 __global__ __launch_bounds__(256)
@@ -176,6 +308,42 @@ int pmx_launch_pairs_fixup(const uint8_t *ok, long long n, pmx_record_t *rec, pm
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_fixup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, rec, stats);
     return pmx_pairs_launched();
+}
+int pmx_launch_pairs_resolve_stranded(const pmx_pair_t *pairs, const uint8_t *strand, long long n,
+                                      const int64_t *q_off, long long q_count, long long q_bytes,
+                                      const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                                      int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_resolve_stranded_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, strand, n,
+                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok, sflag);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
+                                     const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
+                                     const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
+                                     uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_gather_stranded_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                       qlen, rlen, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *rec, int32_t *nops, int32_t *textlen, int32_t *beg, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_fixup_cigar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, rec, nops, textlen, beg);
+    return pmx_pairs_launched();
+}
+int pmx_launch_text_rebase(const int64_t *local, long long n, int64_t *text_off, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_text_rebase_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, local, n, text_off);
+    return pmx_pairs_launched();
+}
+void pmx_complement_table_host(uint8_t table[256])
+{
+    for (int i = 0; i < 256; ++i) table[i] = pmx_comp_host.v[i];
 }
 int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long count, pmx_pair_t *pairs, hipStream_t st)
 {
