@@ -48,6 +48,7 @@ __device__ __forceinline__ v2s pk_max(v2s a, v2s b) { return __builtin_elementwi
 #ifndef PMX_SHARE_PERIOD
 #define PMX_SHARE_PERIOD 16     // steps between two exchanges of the group's score bound (a power of two; see share_bound)
 #endif
+#define PMX_SW16_RETRY_BLOCKS 1024   // workgroups of a retry launch (launch_one), 4 per CU of a 256-CU chip
 #define FLOOR2 0x80008000   // both halves = -32768 = "zero" of the offset domain
 
 template <int G, int R, int VAR>
@@ -67,6 +68,9 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 {
     if (n_dev) n = *n_dev;
     if ((long long)blockIdx.x * (2 * (64 / G)) >= n) return;
+    // Retry launches (VAR 5 behind the perm-table form) start a capped number of workgroups; each then takes every gridDim.x-th
+    // wave of pairs below the device-side count.  Every other launch has one workgroup per wave of pairs and runs the body once.
+    constexpr bool LOOPED = VAR == 5;
     constexpr bool M3 = VAR >= 1;      // biased unsigned lanes, v_pk_maximum3_f16 as integer max3
     constexpr bool V2 = VAR >= 2;      // + full-rate 32-bit VOP2 add/sub on packed lanes (no cross-half carry)
     constexpr bool PT = VAR == 6;      // + no LDS profile at all: alphabets of <= 4 letters (+ wildcard) look the score up with the
@@ -87,7 +91,13 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     constexpr int NP = 2 * SLOTS;        // pairs per wave
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
-    const int lane = threadIdx.x;
+    long long pair0 = (long long)blockIdx.x * NP;
+    do {
+    int lane = threadIdx.x;
+    if (LOOPED) {
+        asm volatile("" : "+v"(lane));     // per trip: nothing derived from the lane is carried (in registers) across the whole body
+        __syncthreads();                   // the staging buffers are rewritten per trip
+    }
     constexpr bool IL = G == 8 && VAR != 7;     // interleaved 8-lane groups (see group_shift_up in pmx_pk16.h); the trace layout keeps plain groups
     const int g = IL ? (lane % 16) / 2 : lane % G;
     const int slot = IL ? (lane / 16) * 2 + (lane & 1) : lane / G;
@@ -96,27 +106,44 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     // LDS carve: [prof NP][shared pad row QP*2][rsym NP*RP][mat msize*msize*2][map 256][pair table NP*4 ints]
     // The pad row sits right behind the last pair's profile; pair p reaches it with the symbol
     // value (NP - p) * msize, so no per-pair copy is needed.
-    // PT: [score tables 32][rsym NP*RP][mat ...]...: the tables sit at a fixed LDS offset, so a staged symbol byte is the
-    // table read's address as it is (immediate offset, no address arithmetic in the sweep).
+    // PT: [score tables 32][rsym NP*RP][mat][pair table][query selector table 256][wildcard flags SLOTS ints][own-row masks][map 256]:
+    // the score tables sit at a fixed LDS offset, so a staged symbol byte is the table read's address as it is (immediate offset,
+    // no address arithmetic in the sweep).
     constexpr int PT_TABS = 32;
     int16_t *prof = reinterpret_cast<int16_t *>(lds);
     unsigned char *rsym = lds + (PT ? PT_TABS : NP * PROF_STRIDE + QP * EB);
     int16_t *mat = reinterpret_cast<int16_t *>(rsym + (FETCH ? 0 : NP * RP));
-    unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((msize * msize * 2) & 7)) & 7));   // per pair: q offset, qlen, r offset, rlen, pair index
+    unsigned char *map0 = reinterpret_cast<unsigned char *>(mat + msize * msize);       // (PT: its table sits behind the pair table, dword-aligned)
+    long long *ptab = reinterpret_cast<long long *>(map0 + (PT ? 0 : 256) + ((8 - ((msize * msize * 2) & 7)) & 7));   // per pair: q offset, qlen, r offset, rlen, pair index
 
     // PT: per reference symbol the 4 query-letter scores (+open), entry msize = pad = 0.  Addressed as LDS address 0: the kernel
     // has no static LDS, so `lds` starts there; a plain integer address folds into the read (the symbol of `lds` does not)
     typedef __attribute__((address_space(3))) int *lds_int;
     auto tab_at = [](int byte) -> int { return *(lds_int)(uintptr_t)byte; };
-    constexpr int QS = (G * R + 3) / 4 * 4;
-    unsigned char *qsym = reinterpret_cast<unsigned char *>(ptab + 5 * NP);   // PT: mapped query letters, QS bytes per pair (0xFF below the query)
-
-    const long long pair0 = (long long)blockIdx.x * NP;
+    // PT, behind the pair table: the query letter -> selector byte table (letter 0..3, 0x0C = "constant 0" for everything else,
+    // with bit 4 set while it still has to be noted as a wildcard), one word per slot that collects "pair A / B has a wildcard
+    // in its query" (bits 0 / 1), and the masks of a lane's own rows (ownmask[i]: 0xFF in the first i - OWN0 bytes, clamped to 0..4)
+    unsigned char *tabq = reinterpret_cast<unsigned char *>(ptab + 5 * NP);
+    unsigned *wildf = reinterpret_cast<unsigned *>(tabq + 256);
+    unsigned *ownmask = wildf + SLOTS;
+    constexpr int OWN0 = 4 * (RS / 4 - 1), OWNN = OWN0 + R + 1;
+    static_assert(!PT || OWNN <= 64, "one lane per mask");
+    unsigned char *map = PT ? reinterpret_cast<unsigned char *>(ownmask + OWNN) : map0;
+    // PT: reference position jr sits at rsym position jr + PADF (a multiple of 4: a staging item of four positions is four
+    // consecutive letters from the start of the reference); every other form keeps G - 1 pad symbols in front
+    static_assert(!PT || (G % 4 == 0 && RS % 4 == 0), "perm-table staging works on dwords");
+    constexpr int PADF = PT ? G : G - 1;
 
     // ---- stage matrix, mapper and the per-pair (offset, length) table -------------------
     for (int i = lane; i < msize * msize; i += 64) mat[i] = gmat[i];
-    for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
+    if (PT) {       // four mapper entries per lane (the mapper is a 256-byte device allocation); msize <= 5: every entry is 0..4
+        const unsigned c4 = reinterpret_cast<const unsigned *>(gmap)[lane];
+        reinterpret_cast<unsigned *>(map)[lane] = c4 << 2;                              // the byte offset of the symbol's score table
+        reinterpret_cast<unsigned *>(tabq)[lane] = c4 + (c4 & 0x04040404u) * 6u;        // 0..3, 4 -> 0x1C: bit 4 marks a wildcard until the staging lane has seen it
+    } else
+        for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
+    if (PT && lane < SLOTS) wildf[lane] = 0;
+    if (PT && lane < OWNN) ownmask[lane] = (unsigned)((0xFFFFFFFFull << (8 * min(max(lane - OWN0, 0), 4))) >> 32);
     if (lane < NP) {
         long long pos = pair0 + lane; if (pos >= n) pos = n - 1;
         const long long pi = perm ? (long long)perm[pos] : pos;
@@ -139,7 +166,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     // flight before anything consumes them (the prologue is latency-bound otherwise), and no
     // index needs a division.
     constexpr int UB = NP < 8 ? NP : 8;
-    for (int p0 = 0; p0 < (FETCH ? 0 : NP); p0 += UB) {
+    for (int p0 = 0; p0 < ((FETCH || PT) ? 0 : NP); p0 += UB) {
         for (int j0 = 0; j0 < RP; j0 += 64) {
             const int j = j0 + lane, jr = j - (G - 1);
             unsigned char raw[UB]; bool ok[UB];
@@ -153,32 +180,93 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 #pragma unroll
                 for (int u = 0; u < UB; ++u) {
                     const int p = p0 + u;
-                    if (PT)     // the slot's pairs A, B side by side, as byte offsets of their table entries
-                        rsym[(p >> 1) * 2 * RP + 2 * j + (p & 1)] = (unsigned char)(4 * (ok[u] ? map[raw[u]] : msize));
-                    else
-                        rsym[p * RP + j] = ok[u] ? map[raw[u]] : (unsigned char)((NP - p) * msize);
+                    rsym[p * RP + j] = ok[u] ? map[raw[u]] : (unsigned char)((NP - p) * msize);
                 }
             }
         }
     }
 
-    if (PT) {          // query letters, staged the same way (coalesced loads; the lanes pick their rows up from LDS)
-        for (int p0 = 0; p0 < NP; p0 += UB) {
-            for (int j0 = 0; j0 < QS; j0 += 64) {
-                const int j = j0 + lane;
-                unsigned char raw[UB]; bool ok[UB];
-#pragma unroll
-                for (int u = 0; u < UB; ++u) {
-                    const int p = p0 + u;
-                    ok[u] = j < (int)ptab[5 * p + 1];
-                    raw[u] = ok[u] ? qbase[ptab[5 * p + 0] + j] : (unsigned char)0;
-                }
-                if (j < QS) {
-#pragma unroll
-                    for (int u = 0; u < UB; ++u) qsym[(p0 + u) * QS + j] = ok[u] ? map[raw[u]] : (unsigned char)0xFF;
-                }
+    int sel[R];       // PT: the per-row v_perm selectors
+    // PT: both sequences are staged by dwords.  One item is four consecutive letters of a slot's pair A and pair B: each side is
+    // assembled from the one or two ALIGNED dwords that hold the letters (v_alignbyte_b32, as pmx_pairs.hip's gather does),
+    // mapped through a 256-byte LDS table and stored as whole dwords.
+    // Read range: a dword is loaded only if it holds at least one letter of the pair itself, i.e. a byte of
+    // [off[pair], off[pair + 1]).  So the kernel reads no byte of qbuf / rbuf outside the aligned dwords that hold a letter
+    // of one of the wave's pairs, and what such a dword holds beyond the pair reaches no result: those letters are replaced by
+    // the pad value (query: in the lane's registers; reference: in LDS, before the sweep).  Pad positions are produced without a load.
+    if constexpr (PT) {
+        // four letters that start `sh` bytes (0..3) into the aligned dword at `dw`; `left` = letters of the sequence from there on
+        // (<= 0: none, nothing is read).  Bytes that were not read hold whatever the registers held: the callers replace them
+        auto load4 = [](const uint8_t *dw, unsigned sh, int left) -> unsigned {
+            const unsigned *d = reinterpret_cast<const unsigned *>(dw);
+            unsigned lo, hi;
+            asm("" : "=v"(lo)); asm("" : "=v"(hi));
+            if (left > 0) lo = d[0];
+            if (left > 4 - (int)sh) hi = d[1];               // the next dword holds a letter of this sequence too
+            return __builtin_amdgcn_alignbyte(hi, lo, sh);
+        };
+        auto lookup4 = [](const unsigned char *tab, unsigned raw) -> unsigned {
+            const unsigned t0 = tab[raw & 0xFF], t1 = tab[(raw >> 8) & 0xFF], t2 = tab[(raw >> 16) & 0xFF], t3 = tab[raw >> 24];
+            return __builtin_amdgcn_perm(t1, t0, 0x0C0C0400u) | __builtin_amdgcn_perm(t3, t2, 0x04000C0Cu);
+        };
+        // reference symbols: the slot's pairs A, B side by side (A0 B0 A1 B1 | A2 B2 A3 B3), as byte offsets of their table entries.
+        // An item with no letter is the pad; the item that holds a reference's last letters is stored with up to three bytes
+        // from behind the reference, which the pass below overwrites with the pad.
+        constexpr int SPT = SLOTS < 4 ? SLOTS : 4, LW = 64 / SPT;        // slots per trip, lanes per slot
+        const unsigned pad4 = (unsigned)(4 * msize) * 0x01010101u;
+        for (int s0 = 0; s0 < SLOTS; s0 += SPT) {
+            const int s = s0 + lane / LW;
+            const uint8_t *ra = rbase + ptab[5 * (2 * s) + 2], *rb = rbase + ptab[5 * (2 * s + 1) + 2];
+            const unsigned ha = (unsigned)(uintptr_t)ra & 3u, hb = (unsigned)(uintptr_t)rb & 3u;      // an item starts this far into a dword
+            const int la = (int)ptab[5 * (2 * s) + 3], lb = (int)ptab[5 * (2 * s + 1) + 3];
+            uint2 *dst = reinterpret_cast<uint2 *>(rsym + s * 2 * RP);
+            if (lane % LW < PADF / 4) dst[lane % LW] = make_uint2(pad4, pad4);                        // the pad in front: whole items
+            for (int jr = 4 * (lane % LW); jr < RP - PADF; jr += 4 * LW) {
+                const int na = la - jr, nb = lb - jr;
+                const unsigned wa = load4(ra - ha + (unsigned)jr, ha, na), wb = load4(rb - hb + (unsigned)jr, hb, nb);   // (four loads in flight)
+                const unsigned xa = na > 0 ? lookup4(map, wa) : pad4, xb = nb > 0 ? lookup4(map, wb) : pad4;
+                dst[(jr + PADF) / 4] = make_uint2(__builtin_amdgcn_perm(xb, xa, 0x05010400u), __builtin_amdgcn_perm(xb, xa, 0x07030602u));
             }
         }
+        __syncthreads();
+        if (lane < 3 * NP) {                // (pair, k): position rlen + k, while it lies in the item of the last letter
+            const int p = lane / 3, len = (int)ptab[5 * p + 3], pos = len + lane % 3;
+            if ((len & 3) != 0 && (pos >> 2) == (len >> 2))
+                rsym[(p >> 1) * 2 * RP + 2 * (PADF + pos) + (p & 1)] = (unsigned char)(4 * msize);
+        }
+        // query letters: a lane stages the rows it sweeps itself, RD + 1 aligned dwords per pair; they never pass through LDS.
+        // Row k's selector: byte 0 = pair A's letter 0..3 -> table A = v_perm source bytes 0..3, byte 2 = 4 + pair B's letter ->
+        // table B = bytes 4..7, bytes 1 and 3 = 0x0C = constant 0.  A wildcard and a row below the query select the constant 0,
+        // i.e. score -open: harmless below the query, wrong for a wildcard -> the lane notes the pair in its slot's flag word.
+        constexpr int RD = RS / 4;
+        unsigned xq[2][RD], wq[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int p = 2 * slot + h;
+            const uint8_t *qp = qbase + ptab[5 * p + 0] + g * R;
+            const int left = (int)ptab[5 * p + 1] - g * R;              // letters of the query from the lane's first row on
+            const unsigned sh = (unsigned)(uintptr_t)qp & 3u;
+            const unsigned *d = reinterpret_cast<const unsigned *>(qp - sh);
+            unsigned w[RD + 1];
+#pragma unroll
+            for (int x = 0; x <= RD; ++x) {
+                asm("" : "=v"(w[x]));                                   // (not read: whatever the register held, masked below)
+                if (left + (int)sh > 4 * x) w[x] = d[x];                // the dword holds a letter of this query
+            }
+            const unsigned *mk = ownmask + min(max(left, 0), R);        // [4 * (RD - 1) - 4 * k]: 0xFF in the first (own rows - 4 k) bytes
+            wq[h] = 0;
+#pragma unroll
+            for (int k = 0; k < RD; ++k) {
+                const unsigned x = (unsigned)bfi((int)mk[4 * (RD - 1) - 4 * k], (int)lookup4(tabq, __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh)), 0x0C0C0C0C);
+                const unsigned wild = x & 0x10101010u;
+                wq[h] |= wild;
+                xq[h][k] = x ^ wild;
+            }
+        }
+        if (wq[0] | wq[1]) atomicOr(&wildf[slot], (wq[0] ? 1u : 0u) | (wq[1] ? 2u : 0u));
+#pragma unroll
+        for (int k = 0; k < R; ++k)         // one v_perm_b32 moves A's and B's selector byte into place, the OR sets B's 4 and bytes 1 and 3
+            sel[k] = (int)(__builtin_amdgcn_perm(xq[1][k / 4], xq[0][k / 4], 0x0C040C00u | (unsigned)(k & 3) * 0x00010001u) | 0x0C040C00u);
     }
 
     // ---- query profiles: one (pair, row pair) item per lane and iteration -----------------
@@ -225,11 +313,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         for (int idx = lane; idx < QP * EB / 4; idx += 64)
             reinterpret_cast<int *>(lds + NP * PROF_STRIDE)[idx] = V2 ? 0 : FLOOR2;
     }
-    // PT: score tables and the per-row selectors (byte 0: pair A's letter 0..3 -> table A = v_perm source bytes 0..3,
-    // byte 2: 4 + pair B's letter -> table B = bytes 4..7, bytes 1 and 3: 0x0C = constant 0; padding rows and wildcard
-    // rows select the constant 0, i.e. score -open: harmless below the query, wrong for a wildcard -> the pair is flagged)
-    int sel[R];
-    int wild = 0;
+    // PT: the score tables (the per-row selectors were built while the query was staged)
     if (PT) {
         if (lane <= msize) {
             int v = 0;
@@ -239,17 +323,6 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         }
     }
     __syncthreads();
-    if (PT) {
-        const unsigned char *qa = qsym + (2 * slot) * QS + g * R, *qb = qa + QS;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const int ca = qa[k], cb = qb[k];          // 0..3 letter, 4.. wildcard, 0xFF below the query
-            wild |= ((ca >= 4 && ca != 0xFF) ? 1 : 0) | ((cb >= 4 && cb != 0xFF) ? 2 : 0);
-            sel[k] = (ca < 4 ? ca : 0x0C) | 0x0C00 | ((cb < 4 ? 4 + cb : 0x0C) << 16) | 0x0C000000;
-        }
-        asm volatile("" : "+v"(wild));     // computed here: otherwise the compiler sinks it behind the sweep and spills the letters
-    }
-    __syncthreads();
 
     // ---- systolic sweep ---------------------------------------------------------------
     const int pA = 2 * slot, pB = 2 * slot + 1;
@@ -257,7 +330,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     const unsigned char *profB = lds + pB * PROF_STRIDE + g * (RS * EB);
     // PT: A and B of a step are adjacent bytes (SS = 2 bytes per step), already table offsets
     constexpr int SS = PT ? 2 : 1;
-    const unsigned char *rsA = PT ? rsym + slot * 2 * RP + 2 * ((G - 1) - g) : rsym + pA * RP + (G - 1) - g;
+    const unsigned char *rsA = PT ? rsym + slot * 2 * RP + 2 * (PADF - g) : rsym + pA * RP + (G - 1) - g;
     const unsigned char *rsB = PT ? rsA + 1 : rsym + pB * RP + (G - 1) - g;
     const int SYMSTRIDE = QP * EB;
 
@@ -280,15 +353,16 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     const v2s vC = PK(I32(vOpen) - I32(vExt));                               // open - ext, per half
     const v2s vInitH = V2 ? PK(ZERO2 - I32(vOpen) + skew0) : vZero;
 #pragma unroll
-    for (int k = 0; k < R; ++k) { HA[k] = vInitH; HB[k] = vInitH; E[k] = V2 ? vInitH : (M3 ? PK(0) : vZero); Hsave[k] = vZero; }
+    for (int k = 0; k < R; ++k) { HA[k] = vInitH; E[k] = V2 ? vInitH : (M3 ? PK(0) : vZero); Hsave[k] = vZero; }    // (HB: written by step 0)
     v2s best = PK(ZERO2 + skew0 - (SK ? I32(vC) : 0));     // SK: X form
     int bestcol = g * 0x00010001;             // STEP at which the best was first exceeded (column = step - g; initially column 0)
     int vprev = 0, fake = 0;                  // see share_bound
-    int Zv = ZERO2 + skew0 + I32(vExt);       // SK: "F^ = 0" of the current column; += ext per step
+    const int Zv0 = ZERO2 + skew0 + I32(vExt);      // SK: "F^ = 0" of the current column is Zv0 + step * ext: a lane constant plus a
+                                                    // wave-uniform term, so the sweep carries no register for it (the scalar unit counts)
     const int HNEUTRAL = V2 ? ZERO2 - I32(vOpen) : ZERO2;
     // last-row H (V2: H - open) and outgoing F of the previous step; SK: what lane g+1 reads at step 0
     // belongs to ITS first column -(g+1), one ext below this lane's own column
-    int Hout = SK ? Zv - I32(vExt) - I32(vOpen) : HNEUTRAL, Fout = SK ? Zv - I32(vExt) : ZERO2;
+    int Hout = SK ? Zv0 - I32(vExt) - I32(vOpen) : HNEUTRAL, Fout = SK ? Zv0 - I32(vExt) : ZERO2;
     v2s diag0 = PK(SK ? I32(vInitH) : HNEUTRAL);   // H(i0-1, j-1)   (V2: minus open)
 
     auto load_scores = [&](int symA, int symB, int (&wa)[RS / WR], int (&wb)[RS / WR]) {
@@ -310,7 +384,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         pl = PK(r);
     };
     auto step = [&](const v2s (&Hold)[R], v2s (&Hnew)[R], const int (&wa)[RS / WR], const int (&wb)[RS / WR], int t) {
-        const int Hin = group_shift_up<G, IL>(Hout, SK ? Zv - I32(vOpen) : HNEUTRAL, g); // H(i0-1, j)
+        const int Zv = Zv0 + t * I32(vExt);
         const int Fin = group_shift_up<G, IL>(Fout, SK ? Zv : ZERO2, g);                  // F(i0, j)
         v2s F = PK(Fin);
         v2s colmax = SK ? PK(0) : vZero;
@@ -399,6 +473,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             w.w = __builtin_amdgcn_perm(I32(plane[2]), I32(plane[3]), 0x02030607);
             *reinterpret_cast<uint4 *>(tw + (size_t)t * t_ss) = w;
         }
+        // H(i0-1, j), the next step's diagonal source: taken from lane g-1's previous step only here, where it is first needed
+        const int Hin = group_shift_up<G, IL>(Hout, SK ? Zv - I32(vOpen) : HNEUTRAL, g);
         diag0 = PK(Hin);
         Hout = I32(Hnew[R - 1]);
         Fout = I32(F);
@@ -425,7 +501,6 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             for (int k = 0; k < R; ++k) Hsave[k] = PK(bfi(m, I32((V2 && !SK) ? Hcur[k] : Hnew[k]), I32(Hsave[k])));
         }
         best = SK ? PK(I32(nb) + I32(vExt)) : nb;                           // SK: carried into the next column's skew
-        if (SK) Zv += I32(vExt);
     };
 
     // software pipeline: scores of step t+1 are fetched from LDS while step t computes
@@ -472,7 +547,9 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         vprev = v;
     };
     const unsigned char *rcur = rsA;            // PT: rsA + SS * t, advanced once per iteration; the reads take immediate offsets
-    for (int t = 0; t + 1 < T; t += 2) {
+    // One loop for both parities of T: an odd count leaves after the first half of the last trip (a wave-uniform branch; that
+    // half's prefetches read staged pad positions and are dropped).  Nothing behind the loop reads HA / HB.
+    for (int t = 0;; t += 2) {
         if (SK && G > 1 && (t & (SHP - 1)) == 0 && t) share_bound();
         load_scores(nsA, nsB, w1a, w1b);
         if (FETCH) { nsA = symA_of(m2a); nsB = symB_of(m2b); fetch(t + 4, m2a, m2b); }
@@ -481,15 +558,18 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         __builtin_amdgcn_sched_barrier(0);      // keep the LDS reads ahead of the step they overlap with
         step(HA, HB, w0a, w0b, t);
         __builtin_amdgcn_sched_barrier(0);
-        load_scores(nsA, nsB, w0a, w0b);
-        if (FETCH) { nsA = symA_of(m3a); nsB = symB_of(m3b); fetch(t + 5, m3a, m3b); }
-        else if (PT) { nsA = rcur[3 * SS]; nsB = rcur[3 * SS + 1]; asm("" : "+v"(nsA), "+v"(nsB)); rcur += 2 * SS; }
-        else { nsA = rsA[t + 3]; nsB = rsB[t + 3]; }
-        __builtin_amdgcn_sched_barrier(0);
-        step(HB, HA, w1a, w1b, t + 1);
-        __builtin_amdgcn_sched_barrier(0);
+        if (t + 1 < T) {                        // (wave-uniform)
+            load_scores(nsA, nsB, w0a, w0b);
+            if (FETCH) { nsA = symA_of(m3a); nsB = symB_of(m3b); fetch(t + 5, m3a, m3b); }
+            else if (PT) { nsA = rcur[3 * SS]; nsB = rcur[3 * SS + 1]; asm("" : "+v"(nsA), "+v"(nsB)); rcur += 2 * SS; }
+            else { nsA = rsA[t + 3]; nsB = rsB[t + 3]; }
+            __builtin_amdgcn_sched_barrier(0);
+            step(HB, HA, w1a, w1b, t + 1);
+            __builtin_amdgcn_sched_barrier(0);
+        } else
+            asm("" : "=v"(Hout));               // dead (the loop ends here): spares the move that would join it with the other path's
+        if (t + 2 >= T) break;
     }
-    if (T & 1) step(HA, HB, w0a, w0b, T - 1);                   // odd step count: one more (its scores are already loaded)
 
     // ---- per lane: first row of the saved strip that holds the best ---------------------
     unsigned long long keyA, keyB;
@@ -519,7 +599,6 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         const unsigned long long oa = __shfl_xor(keyA, lo, 64), ob = __shfl_xor(keyB, lo, 64);
         keyA = oa > keyA ? oa : keyA;
         keyB = ob > keyB ? ob : keyB;
-        if (PT) wild |= __shfl_xor(wild, lo, 64);
     }
     if (g == 0) {
 #pragma unroll
@@ -534,7 +613,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
                 if (M3) rec.flags = (rec.score + PK16_SW_BIAS >= limit) ? PMX_FLAG_RERUN : 0; // left the exact range: redo in 32 bits
                 else rec.flags = rec.score > 32767 ? PMX_FLAG_SATURATED : 0;
                 if (rec.score > sat_above) rec.flags |= PMX_FLAG_SATURATED;
-                if (PT && ((wild >> h) & 1)) {                                              // wildcard in the query: redo with the LDS profile
+                if (PT && ((wildf[slot] >> h) & 1)) {                                              // wildcard in the query: redo with the LDS profile
                     rec.flags = PMX_FLAG_RETRY16;
                     retry_list[atomicAdd(retry_count, 1)] = (unsigned)pi;
                 }
@@ -542,6 +621,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             }
         }
     }
+    pair0 += (long long)gridDim.x * NP;
+    } while (LOOPED && n_dev && pair0 < n);
 }
 
 // ------------------------------------------------------------------------ host side ----
@@ -555,12 +636,15 @@ static int launch_one(const PmxBatch &b, const PmxDevMatrix &m, int open, int ex
     constexpr int QP = G * RS, NP = 2 * (64 / G);
     if (NP * m.msize > 255) return 1;                 // per-pair pad symbol must fit a byte
     const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
-    const size_t lds = (PT ? (size_t)NP * ((G * R + 3) / 4 * 4) : (size_t)NP * m.msize * QP * EB + (size_t)QP * EB) + (VAR == 8 ? 0 : (size_t)NP * RP) +
+    const size_t lds = (PT ? (size_t)256 + 4 * (64 / G) + 4 * (4 * (RS / 4 - 1) + R + 1) : (size_t)NP * m.msize * QP * EB + (size_t)QP * EB) + (VAR == 8 ? 0 : (size_t)NP * RP) +
                        (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40 + 32;
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_sw16_kernel<G, R, VAR>)); if (rc) return rc; }
-    const long long blocks = (b.n + NP - 1) / NP;
+    long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
+    // a launch driven by a device-side count (the retry behind the perm-table form, usually of an empty list) starts a few
+    // workgroups per CU, and each loops over the waves of pairs below the count
+    if (n_dev && VAR == 5 && blocks > PMX_SW16_RETRY_BLOCKS) blocks = PMX_SW16_RETRY_BLOCKS;
     if (PT) {
         hipError_t e = hipMemsetAsync(b.retry_count, 0, sizeof(int), stream);
         if (e != hipSuccess) return -(int)e;
