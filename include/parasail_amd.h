@@ -523,6 +523,69 @@ int pmx_gather_pairs_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_
                             uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
                             uint8_t *d_ok /* n validity bytes, optional */, void *stream);
 
+/* Set search (extension): the thresholded, compacted form of the set batches.  The pairs of an enumeration -- a window of the strict
+ * upper triangle of Q x Q, a window of the rectangle Q x R, or a descriptor list -- are aligned chunk by chunk by the kernels of the set
+ * batches, and only the pairs with score >= min_score leave their chunk, as one compact hit list in enumeration order.  Device memory is
+ * bounded by the chunk scratch and the hit buffers, not by the number of pairs: an all-vs-all of 100 000 sequences (5 10^9 pairs, 80 GB
+ * of records) runs in the memory of one chunk plus its hits.
+ *
+ * The hit set.  Let record k be what pmx_align_pairs_device / pmx_align_all_pairs_device write for pair k of the enumeration (RECT: for
+ * the descriptor pmx_rect_pairs_enumerate_device generates).  The hits are { k : record_k.score >= min_score } in ascending k: only the
+ * score is looked at, as in pmx_select_hits_device, so a bad descriptor's record {0, -1, -1, PMX_FLAG_BAD_PAIR} is a hit when
+ * min_score <= 0 and keeps its flag (the host entry refuses bad pairs, as pmx_align_pairs does).
+ *
+ * The outputs of hit x, a structure of arrays: d_hit_pairs[x] the pair's descriptor -- for the enumerated shapes exactly what the
+ * enumerator generated, for PMX_PAIRS_LIST the caller's descriptor with its windows; d_hit_index[x] its absolute number p in the
+ * enumeration (first + k; LIST: k); d_hit_recs[x] the record, byte for byte; d_hit_stats[x] its statistics.  d_hit_pairs is a valid
+ * d_pairs argument: the CIGAR pass over the hits is pmx_align_pairs_ex_device(..., n = d_counts[1], d_hit_pairs, ...) with nothing in
+ * between, which is why PMX_WANT_CIGAR is refused here.  min(passing, capacity) hits are written, the first ones in enumeration order;
+ * entries beyond them are untouched; d_counts[0] is the full number passing and d_counts[1] the number written; capacity == 0 counts
+ * only.  d_hit_pairs and d_hit_index are optional (NULL: not written).
+ *
+ * Determinism.  The output is bit-identical from run to run, and chunk_pairs / slice_pairs never change a byte of any output: a
+ * chunk's hit positions come from the selection's scan (ascending index), its hits go behind the running total, which lives on the
+ * device (in d_counts) and advances in chunk order on the caller's stream.  No position depends on which workgroup finishes first.
+ *
+ * Every mode, width and matrix of pmx_align_pairs_device is accepted, a PSSM under its rule; PMX_WANT_SORTED is passed on.  Refused with
+ * -1 and a pmx_last_error() text before any GPU work: everything pmx_align_pairs_device / pmx_align_all_pairs_device refuse; an unknown
+ * shape; TRIANGLE with an R that is neither NULL nor Q; RECT or LIST without R; LIST with first != 0 or NULL pairs; another shape with
+ * non-NULL pairs; first + n beyond the shape's count; a rectangle whose count overflows; a negative capacity, max_hits or slice_pairs;
+ * NULL d_hit_recs with capacity > 0; NULL d_counts; PMX_WANT_STATS without d_hit_stats, or d_hit_stats without PMX_WANT_STATS;
+ * PMX_WANT_CIGAR.  n == 0 succeeds and writes zero counts (d_counts may then be NULL).
+ *
+ * The device entry is asynchronous on `stream` under the rule of the other set entries: no host synchronisation once the calling
+ * thread's scratch is large enough -- the chunk buffers of pmx_align_pairs_device and, per pair of a chunk, 16 bytes of record, 12 of
+ * statistics (PMX_WANT_STATS), 8 of hit position and the selection's block counts: about 45 bytes.
+ *
+ * The host entry works in slices of opts->slice_pairs pairs (0: 2^24): device hit buffers are sized to the slice (to max_hits when that
+ * is smaller), so they cannot overflow; one stream synchronisation per slice reads the slice's count, then its hits are copied behind
+ * those of the slices before.  Those buffers are thread scratch of 56 bytes per pair of a slice (68 with PMX_WANT_STATS): 0.94 GB
+ * (1.14 GB) at the default slice once n reaches 2^24, however few pairs pass -- a smaller slice_pairs, or max_hits, bounds them.  It validates as pmx_align_pairs / pmx_align_all_pairs do and names the first bad pair (RECT: "pair k
+ * (i, j): side: cause", the all-pairs rule): before any GPU work when both sets carry host offsets, otherwise at the end of the slice
+ * whose device pass met it.  max_hits > 0 stops storing after that many hits, in enumeration order, and goes on counting n_passing;
+ * max_hits == 0: no limit.  LIST descriptors are uploaded slice by slice, 32 bytes per pair; the enumerated shapes upload nothing.
+ * *result is one callee-allocated block (NULL on failure) released with pmx_pair_hits_free: pairs, index and recs hold n_hits entries,
+ * stats too with PMX_WANT_STATS (else NULL).  Zero hits is success with empty arrays. */
+#define PMX_PAIRS_LIST     0   /* the n descriptors of pairs / d_pairs (first must be 0) */
+#define PMX_PAIRS_TRIANGLE 1   /* pairs [first, first + n) of the strict upper triangle of Q (R NULL or == Q): pmx_all_pairs_index numbering */
+#define PMX_PAIRS_RECT     2   /* pairs [first, first + n) of Q x R, row-major: p = i * |R| + j, query = Q[i], reference = R[j], whole
+                                  sequences; Q == R allowed (i == j included) */
+int64_t pmx_rect_pairs_count(int64_t nq, int64_t nr);          /* nq * nr, -1 if negative or beyond INT64_MAX */
+/* Test hook, like pmx_all_pairs_enumerate_device: the descriptors PMX_PAIRS_RECT generates. */
+int pmx_rect_pairs_enumerate_device(int64_t nq, int64_t nr, int64_t first, int64_t count, pmx_pair_t *d_pairs, void *stream);
+int pmx_search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                            int64_t first, int64_t n, const pmx_pair_t *d_pairs /* LIST only, else NULL */,
+                            int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                            pmx_pair_t *d_hit_pairs /* optional */, int64_t *d_hit_index /* optional */,
+                            pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats /* iff PMX_WANT_STATS */, int64_t capacity,
+                            int64_t *d_counts /* [0] passing, [1] written = min(passing, capacity) */,
+                            void *stream, const pmx_pairs_opts_t *opts);
+typedef struct pmx_pair_search_opts { int32_t min_score, shape; int64_t max_hits, chunk_pairs, slice_pairs; } pmx_pair_search_opts_t;   /* 32 bytes */
+typedef struct pmx_pair_hits { int64_t n_hits, n_passing; pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; } pmx_pair_hits_t;
+int  pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                      const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, pmx_pair_hits_t **result);
+void pmx_pair_hits_free(pmx_pair_hits_t *hits);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -136,6 +136,33 @@ pub struct PmxPairsOpts {
 /// Record flag of the set-batch device entries: the descriptor was bad, nothing was aligned.
 pub const PMX_FLAG_BAD_PAIR: i32 = 8;
 
+/// Shapes of a set search: a descriptor list, a window of the strict upper triangle of Q, a window of the row-major rectangle Q x R.
+pub const PMX_PAIRS_LIST: c_int = 0;
+pub const PMX_PAIRS_TRIANGLE: c_int = 1;
+pub const PMX_PAIRS_RECT: c_int = 2;
+
+/// `pmx_pair_search_opts_t` (32 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct PmxPairSearchOpts {
+    pub min_score: i32,
+    pub shape: i32,
+    pub max_hits: i64,    // 0 = no limit
+    pub chunk_pairs: i64, // 0 = default; never changes a result
+    pub slice_pairs: i64, // 0 = 2^24; never changes a result
+}
+
+/// `pmx_pair_hits_t`: one callee-allocated block, released with `pmx_pair_hits_free`.
+#[repr(C)]
+pub struct PmxPairHits {
+    pub n_hits: i64,
+    pub n_passing: i64,
+    pub pairs: *mut PmxPair,
+    pub index: *mut i64,
+    pub recs: *mut PmxRecord,
+    pub stats: *mut PmxStats,
+}
+
 /// Opaque `pmx_seqset_t`.
 #[repr(C)]
 pub struct PmxSeqSet {
@@ -187,6 +214,19 @@ extern "C" {
         d_out: *mut PmxRecord, d_stats_out: *mut PmxStats, stream: *mut c_void, opts: *const PmxPairsOpts,
     ) -> c_int;
     pub fn pmx_all_pairs_enumerate_device(nseq: i64, first: i64, count: i64, d_pairs: *mut PmxPair, stream: *mut c_void) -> c_int;
+    fn pmx_rect_pairs_count(nq: i64, nr: i64) -> i64;
+    pub fn pmx_rect_pairs_enumerate_device(nq: i64, nr: i64, first: i64, count: i64, d_pairs: *mut PmxPair, stream: *mut c_void) -> c_int;
+    /// Set search into caller buffers on the device: `d_counts[0]` pairs pass, `d_counts[1] = min(passing, capacity)` are written.
+    pub fn pmx_search_pairs_device(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, shape: c_int, first: i64, n: i64, d_pairs: *const PmxPair,
+        max_qlen: i32, max_rlen: i32, min_score: i32, d_hit_pairs: *mut PmxPair, d_hit_index: *mut i64, d_hit_recs: *mut PmxRecord,
+        d_hit_stats: *mut PmxStats, capacity: i64, d_counts: *mut i64, stream: *mut c_void, opts: *const PmxPairsOpts,
+    ) -> c_int;
+    fn pmx_search_pairs(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, first: i64, n: i64, pairs: *const PmxPair,
+        opts: *const PmxPairSearchOpts, result: *mut *mut PmxPairHits,
+    ) -> c_int;
+    fn pmx_pair_hits_free(hits: *mut PmxPairHits);
     fn pmx_align_batch(
         cfg: *const PmxConfig, n: i64,
         qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
@@ -416,6 +456,72 @@ impl Drop for SearchHits {
 }
 
 unsafe impl Send for SearchHits {}
+
+/// Hits of a set search: the callee's block, released with `pmx_pair_hits_free` on drop.  Hit `x` is the x-th pair of the
+/// enumeration that reached `min_score`.
+pub struct PairHits {
+    inner: *mut PmxPairHits,
+}
+
+impl PairHits {
+    fn r(&self) -> &PmxPairHits {
+        unsafe { &*self.inner }
+    }
+    pub fn len(&self) -> usize {
+        self.r().n_hits as usize
+    }
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+    /// Pairs that reached `min_score`, before `max_hits` cut them.
+    pub fn passing(&self) -> i64 {
+        self.r().n_passing
+    }
+    /// The hits' descriptors: a valid pair list for `Aligner::align_pairs`.
+    pub fn pairs(&self) -> &[PmxPair] {
+        if self.is_empty() { &[] } else { unsafe { std::slice::from_raw_parts(self.r().pairs, self.len()) } }
+    }
+    /// The hits' numbers in the enumeration.
+    pub fn index(&self) -> &[i64] {
+        if self.is_empty() { &[] } else { unsafe { std::slice::from_raw_parts(self.r().index, self.len()) } }
+    }
+    pub fn records(&self) -> &[PmxRecord] {
+        if self.is_empty() { &[] } else { unsafe { std::slice::from_raw_parts(self.r().recs, self.len()) } }
+    }
+    pub fn stats(&self) -> Option<&[PmxStats]> {
+        let p = self.r().stats;
+        if p.is_null() { None } else { Some(unsafe { std::slice::from_raw_parts(p, self.len()) }) }
+    }
+}
+
+impl Drop for PairHits {
+    fn drop(&mut self) {
+        if !self.inner.is_null() {
+            unsafe { pmx_pair_hits_free(self.inner) }
+        }
+    }
+}
+
+unsafe impl Send for PairHits {}
+
+/// What a set search enumerates.
+pub enum PairShape<'a> {
+    /// These descriptors of `q x r`.
+    List(&'a [PmxPair]),
+    /// Pairs `[first, first + count)` of the strict upper triangle of `q` (`all_pairs_index`); `count` `None`: to the last pair.
+    Triangle { first: i64, count: Option<i64> },
+    /// Pairs `[first, first + count)` of `q x r`, row-major: pair `p` is `(p / r.len(), p % r.len())`.
+    Rect { first: i64, count: Option<i64> },
+}
+
+/// Pairs of the rectangle `nq x nr`.
+pub fn rect_pairs_count(nq: i64, nr: i64) -> Result<i64> {
+    let v = unsafe { pmx_rect_pairs_count(nq, nr) };
+    if v < 0 {
+        return Err(last_error());
+    }
+    Ok(v)
+}
 
 fn last_error() -> Error {
     Error::Batch(unsafe { CStr::from_ptr(pmx_last_error()) }.to_string_lossy().into_owned())
@@ -699,6 +805,34 @@ impl Aligner {
             return Err(last_error());
         }
         Ok(BatchResult { records, stats })
+    }
+
+    /// Set search: the pairs of the enumeration that score at least `min_score`, in enumeration order, with their descriptors,
+    /// numbers, records and (stats aligner) statistics.  Only the hits leave the device.  `r` `None`: `q` (lists, rectangles) --
+    /// a triangle takes one set.  `max_hits > 0` keeps the first `max_hits` hits and goes on counting `passing()`.
+    pub fn search_pairs(&self, q: &SeqSet, r: Option<&SeqSet>, shape: PairShape, min_score: i32, max_hits: i64, chunk_pairs: i64,
+                        slice_pairs: i64) -> Result<PairHits> {
+        assert!(self.profile.is_null(), "search_pairs takes no profile");
+        let rset = r.unwrap_or(q);
+        let (code, first, count, list, rptr) = match shape {
+            PairShape::List(p) => (PMX_PAIRS_LIST, 0, p.len() as i64, if p.is_empty() { std::ptr::null() } else { p.as_ptr() }, rset.inner as *const PmxSeqSet),
+            PairShape::Triangle { first, count } => {
+                let c = match count { Some(c) => c, None => all_pairs_count(q.len() as i64)? - first };
+                (PMX_PAIRS_TRIANGLE, first, c, std::ptr::null(), std::ptr::null())
+            }
+            PairShape::Rect { first, count } => {
+                let c = match count { Some(c) => c, None => rect_pairs_count(q.len() as i64, rset.len() as i64)? - first };
+                (PMX_PAIRS_RECT, first, c, std::ptr::null(), rset.inner as *const PmxSeqSet)
+            }
+        };
+        let cfg = self.pmx_config(if self.want_stats { PMX_WANT_STATS } else { 0 });
+        let opts = PmxPairSearchOpts { min_score, shape: code, max_hits, chunk_pairs, slice_pairs };
+        let mut inner: *mut PmxPairHits = std::ptr::null_mut();
+        let rc = unsafe { pmx_search_pairs(&cfg, q.inner, rptr, first, count, list, &opts, &mut inner) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok(PairHits { inner })
     }
 
     /// 2-bit packed DNA (base b in byte b / 4 at bits 2 * (b % 4); code c = letter c of the matrix alphabet; offsets count

@@ -85,12 +85,23 @@ class pmx_pairs_opts_t(C.Structure):
     _fields_ = [("chunk_pairs", C.c_int64)]
 
 
+class pmx_pair_search_opts_t(C.Structure):
+    _fields_ = [("min_score", C.c_int32), ("shape", C.c_int32), ("max_hits", C.c_int64), ("chunk_pairs", C.c_int64),
+                ("slice_pairs", C.c_int64)]
+
+
+class pmx_pair_hits_t(C.Structure):
+    _fields_ = [("n_hits", C.c_int64), ("n_passing", C.c_int64), ("pairs", C.c_void_p), ("index", C.c_void_p),
+                ("recs", C.c_void_p), ("stats", C.c_void_p)]
+
+
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
 STATS_DTYPE = np.dtype([("matches", "<i4"), ("similar", "<i4"), ("length", "<i4")])
 HIT_DTYPE = np.dtype([("index", "<i8"), ("first", RECORD_DTYPE), ("diag", "<i4"), ("beg_query", "<i4"), ("beg_ref", "<i4"),
                       ("reserved", "<i4")])
 HITS_BY_INDEX, HITS_BY_SCORE = 0, 1
 PAIR_DTYPE = np.dtype([("q", "<i8"), ("r", "<i8"), ("q_beg", "<i4"), ("q_len", "<i4"), ("r_beg", "<i4"), ("r_len", "<i4")])
+PAIRS_LIST, PAIRS_TRIANGLE, PAIRS_RECT = 0, 1, 2
 
 MODE_NW, MODE_SG, MODE_SW = 0, 1, 2
 SG_QB, SG_QE, SG_DB, SG_DE, SG_ALL = 1, 2, 4, 8, 15
@@ -223,6 +234,14 @@ _sig("pmx_align_all_pairs", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_in
 _sig("pmx_align_all_pairs_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
      C.c_void_p, C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_all_pairs_enumerate_device", C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
+_sig("pmx_rect_pairs_count", C.c_int64, C.c_int64, C.c_int64)
+_sig("pmx_rect_pairs_enumerate_device", C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
+_sig("pmx_search_pairs_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_search_pairs", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+     C.POINTER(pmx_pair_search_opts_t), C.POINTER(C.POINTER(pmx_pair_hits_t)))
+_sig("pmx_pair_hits_free", None, C.POINTER(pmx_pair_hits_t))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -906,6 +925,42 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return (out, stats) if stats is not None else out
 
+    def search_pairs(self, Q, R=None, min_score=0, pairs=None, first=0, count=None, stats=False, max_hits=0, chunk_pairs=0,
+                     slice_pairs=0):
+        """Set search: the pairs of an enumeration that score at least min_score, as a PairHits in enumeration order.  `pairs`
+        given: those descriptors of Q x R (as align_pairs takes them; R None: Q); else R None: pairs [first, first + count) of the
+        strict upper triangle of Q (the numbering of align_all_pairs); else the same window of the rectangle Q x R, row-major
+        (pair p = (p // len(R), p % len(R)); R may be Q, the diagonal included).  count None: to the last pair.  stats=True adds the
+        hits' statistics.  max_hits > 0 keeps the first max_hits hits and goes on counting n_passing.  Only the hits leave the
+        device; chunk_pairs and slice_pairs never change the result."""
+        if not self._profile.is_null():
+            raise BatchError("search_pairs takes no profile")
+        cfg = self._config()
+        if stats:
+            cfg.want |= WANT_STATS
+        if pairs is not None:
+            shape, R = PAIRS_LIST, (Q if R is None else R)
+            pairs = as_pairs(pairs)
+            first, count = 0, len(pairs)
+        elif R is None:
+            shape = PAIRS_TRIANGLE
+            if count is None:
+                count = all_pairs_count(len(Q)) - int(first)
+        else:
+            shape = PAIRS_RECT
+            if count is None:
+                count = rect_pairs_count(len(Q), len(R)) - int(first)
+        opts = pmx_pair_search_opts_t(int(min_score), shape, int(max_hits), int(chunk_pairs), int(slice_pairs))
+        res = C.POINTER(pmx_pair_hits_t)()
+        rc = lib.pmx_search_pairs(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
+                                  pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts), C.byref(res))
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        try:
+            return PairHits(res.contents)
+        finally:
+            lib.pmx_pair_hits_free(res)
+
     def align_batch_2bit(self, q2, qoff, r2, roff, out=None):
         """2-bit packed input (see pack_2bit): offsets count bases.  `out` as in align_batch_packed."""
         n = len(roff) - 1
@@ -1098,6 +1153,28 @@ class SearchHits:
         return self.n_hits
 
 
+class PairHits:
+    """Result of Aligner.search_pairs: n_hits, n_passing (all pairs at or above min_score, stored or not) and, per hit in
+    enumeration order, pairs (PAIR_DTYPE: the descriptor, fit for align_pairs), index (int64: the pair's number in the
+    enumeration), records (RECORD_DTYPE) and stats (STATS_DTYPE, or None when not asked for)."""
+
+    def __init__(self, r):
+        h = int(r.n_hits)
+        self.n_hits, self.n_passing = h, int(r.n_passing)
+
+        def take(ptr, dtype):
+            if not ptr or not h:
+                return np.zeros(h, dtype=dtype)
+            return np.frombuffer(C.string_at(ptr, h * np.dtype(dtype).itemsize), dtype=dtype).copy()
+        self.pairs = take(r.pairs, PAIR_DTYPE)
+        self.index = take(r.index, np.int64)
+        self.records = take(r.recs, RECORD_DTYPE)
+        self.stats = take(r.stats, STATS_DTYPE) if r.stats else None
+
+    def __len__(self):
+        return self.n_hits
+
+
 def _take_cigars(cbuf, coff):
     """The per-pair CIGAR strings out of a callee-allocated text block (offsets coff[n + 1]); the block is released."""
     n = len(coff) - 1
@@ -1268,6 +1345,33 @@ def align_all_pairs_device(cfg, S, first, count, max_len, d_out, d_stats=None, s
 def all_pairs_enumerate_device(nseq, first, count, d_pairs, stream=0):
     """The descriptors the all-pairs entries generate, into `count` PAIR_DTYPE slots of device memory (test hook)."""
     if lib.pmx_all_pairs_enumerate_device(int(nseq), int(first), int(count), d_pairs, stream):
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def rect_pairs_count(nq, nr):
+    """Pairs of the rectangle nq x nr."""
+    v = lib.pmx_rect_pairs_count(int(nq), int(nr))
+    if v < 0:
+        raise BatchError(lib.pmx_last_error().decode())
+    return int(v)
+
+
+def rect_pairs_enumerate_device(nq, nr, first, count, d_pairs, stream=0):
+    """The descriptors a rectangular set search generates, into `count` PAIR_DTYPE slots of device memory (test hook)."""
+    if lib.pmx_rect_pairs_enumerate_device(int(nq), int(nr), int(first), int(count), d_pairs, stream):
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs,
+                        d_hit_stats, capacity, d_counts, stream=0, chunk_pairs=0):
+    """Device-pointer entry of the set search: the pairs of the enumeration (shape PAIRS_LIST / PAIRS_TRIANGLE / PAIRS_RECT) with
+    score >= min_score, compacted in enumeration order into d_hit_pairs / d_hit_index (optional), d_hit_recs and d_hit_stats
+    (`capacity` entries each); d_counts gets [passing, written]."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_search_pairs_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(shape), int(first), int(n),
+                                     d_pairs, max_qlen, max_rlen, int(min_score), d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                                     int(capacity), d_counts, stream, C.byref(opts))
+    if rc:
         raise BatchError(lib.pmx_last_error().decode())
 
 

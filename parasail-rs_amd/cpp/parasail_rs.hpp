@@ -670,6 +670,46 @@ public:
         return out;
     }
 
+    // additive: set search (pmx_search_pairs): the pairs of an enumeration that score at least min_score, in enumeration order, with
+    // their descriptors (fit for align_pairs / align_pairs_cigar), their numbers in the enumeration, their records and -- for a stats
+    // aligner -- their statistics.  Only the hits leave the device.  shape PMX_PAIRS_LIST: `pairs` of Q x R; PMX_PAIRS_TRIANGLE: pairs
+    // [first, first + count) of the strict upper triangle of Q (R == nullptr); PMX_PAIRS_RECT: the same window of Q x R, row-major.
+    // count < 0: to the last pair.  max_hits > 0 keeps the first max_hits hits and goes on counting n_passing.
+    struct PairHits {
+        int64_t n_passing = 0;
+        std::vector<pmx_pair_t> pairs;
+        std::vector<int64_t> index;
+        std::vector<pmx_record_t> recs;
+        std::vector<pmx_stats_t> stats;
+    };
+    PairHits search_pairs(const SeqSet &Q, const SeqSet *R, int shape, int32_t min_score, const std::vector<pmx_pair_t> *pairs = nullptr,
+                          int64_t first = 0, int64_t count = -1, int64_t max_hits = 0, int64_t chunk_pairs = 0, int64_t slice_pairs = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "search_pairs takes no profile");
+        if (shape == PMX_PAIRS_LIST) { if (!pairs) throw Error(ErrorKind::Batch, "PMX_PAIRS_LIST needs pairs"); first = 0; count = (int64_t)pairs->size(); }
+        else if (count < 0) {
+            const int64_t total = shape == PMX_PAIRS_TRIANGLE ? all_pairs_count(Q.len()) : pmx_rect_pairs_count(Q.len(), R ? R->len() : -1);
+            if (total < 0) throw Error(ErrorKind::Batch, pmx_last_error());
+            count = total - first;
+        }
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        const pmx_pair_search_opts_t opts = {min_score, shape, max_hits, chunk_pairs, slice_pairs};
+        pmx_pair_hits_t *res = nullptr;
+        const int rc = pmx_search_pairs(&cfg, Q.inner, R ? R->inner : nullptr, first, count,
+                                        shape == PMX_PAIRS_LIST && !pairs->empty() ? pairs->data() : nullptr, &opts, &res);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        PairHits out;
+        const size_t h = (size_t)res->n_hits;
+        out.n_passing = res->n_passing;
+        out.pairs.assign(res->pairs, res->pairs + h);
+        out.index.assign(res->index, res->index + h);
+        out.recs.assign(res->recs, res->recs + h);
+        if (res->stats) out.stats.assign(res->stats, res->stats + h);
+        pmx_pair_hits_free(res);
+        return out;
+    }
+
     std::shared_ptr<Matrix> matrix;
     int gap_open = 0, gap_extend = 0;
     std::string vec_strategy;

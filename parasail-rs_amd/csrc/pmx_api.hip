@@ -1373,7 +1373,9 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_SRCH = 18, SCR_GREF = 19,                                                     // profile search: hit list / diagonals / lengths / offsets / begins; gathered references
        SCR_PAIRS = 20, SCR_PGEN = 21,                                                    // set batches: two sets of chunk buffers (pmx_pairs.hip); enumerated descriptors
        SCR_PUP = 22, SCR_PREC = 23, SCR_PST = 24,                                        // set batches, host entries: uploaded descriptors, records, statistics
-       SCR_SLOTS = 25 };
+       SCR_PSRCH = 25,                                                                   // set search: a chunk's records, statistics, hit positions, counts and select scratch
+       SCR_PHIT = 26,                                                                    // set search, host entry: a slice's hit arrays, counts, first bad pair
+       SCR_SLOTS = 27 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -3725,12 +3727,13 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 // c & 1, then -- behind packed[c & 1] -- body(c0, cn, buffers), the chunk's alignment, on the caller's stream, in chunk order: the
 // alignment roads keep per-thread scratch (the CIGAR road internal streams too) and never run twice at once.  aligned[c & 1] lets chunk
 // c + 2's gather overwrite the set.  Everything `prep` does is waited for by `st`, so `st` ends behind the last body and behind `prep`.
-// One chunk: all on `st`.  d_pairs == nullptr: pairs [first, first + n) of the upper triangle of Q x Q, generated per chunk.
+// One chunk: all on `st`.  shape PMX_PAIRS_TRIANGLE / PMX_PAIRS_RECT: pairs [first, first + n) of the upper triangle of Q x Q / of the
+// rectangle Q x R, generated per chunk; the body finds the chunk's descriptors, listed or generated, in PairsChunkBufs::pairs.
 // d_strand != nullptr (the _ex entries): the resolve step takes the strand bytes and the gather is the one that can reverse-complement;
 // otherwise the forward-only kernels run, and a forward batch pays nothing for the strands' existence.
-struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; };
+struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; };
 template <typename Body>
-static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first,
+static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first, int shape,
                      const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body)
 {
     const bool two = chunk < n, stranded = d_strand != nullptr;
@@ -3748,7 +3751,8 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
             }
             scan = c.take<unsigned char>(scan_bytes);           // (one: the scans of all chunks run in order on one stream)
         })) return -1;
-    if (!d_pairs && scratch_reserve(sizeof(pmx_pair_t) * (size_t)chunk * (two ? 2 : 1), (void **)&gen, SCR_PGEN)) return -1;
+    const bool listed = shape == PMX_PAIRS_LIST;
+    if (!listed && scratch_reserve(sizeof(pmx_pair_t) * (size_t)chunk * (two ? 2 : 1), (void **)&gen, SCR_PGEN)) return -1;
     hipStream_t prep = st;
     if (two) {
         if (pairs_ws_init()) return -1;
@@ -3757,9 +3761,12 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         HIP_OR_RET(hipStreamWaitEvent(prep, g_pws.start, 0));
     }
     auto pack = [&](int64_t c0, int64_t cn, int slot) -> int {
+        pmx_pair_t *gc = gen ? gen + (size_t)slot * (size_t)chunk : nullptr;
+        const pmx_pair_t *pc = listed ? d_pairs + c0 : gc;
+        B[slot].pairs = pc;
         const PairsChunkBufs &b = B[slot];
-        const pmx_pair_t *pc = d_pairs ? d_pairs + c0 : gen + (size_t)slot * (size_t)chunk;
-        int rc = d_pairs ? 0 : pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gen + (size_t)slot * (size_t)chunk, prep);
+        int rc = listed ? 0 : shape == PMX_PAIRS_TRIANGLE ? pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gc, prep)
+                                                          : pmx_launch_rect_pairs_enumerate(R->count, first + c0, cn, gc, prep);
         if (!rc) rc = stranded ? pmx_launch_pairs_resolve_stranded(pc, d_strand + c0, cn, Q->d_off, Q->count, Q->bytes,
                                                                    R->d_off, R->count, R->bytes, max_qlen, max_rlen,
                                                                    b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
@@ -3800,7 +3807,7 @@ static int pairs_run_scores(const pmx_config_t *cfg, const pmx_seqset *Q, const 
                             pmx_record_t *d_out, pmx_stats_t *d_stats_out, hipStream_t st, int64_t chunk)
 {
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    return pairs_run(Q, R, n, d_pairs, first, d_strand, max_qlen, max_rlen, st, chunk,
+    return pairs_run(Q, R, n, d_pairs, first, d_pairs ? PMX_PAIRS_LIST : PMX_PAIRS_TRIANGLE, d_strand, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             int rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
             if (rc) return rc;
@@ -3847,7 +3854,7 @@ static int pairs_run_cigar(const pmx_config_t *cfg, const DevMat &dm, const pmx_
                            const pmx_pair_t *d_pairs, const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
                            pmx_record_t *d_out, int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st, int64_t chunk)
 {
-    return pairs_run(Q, R, n, d_pairs, 0, d_strand, max_qlen, max_rlen, st, chunk,
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, d_strand, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             CigarChunkOf set; set.ok = b.ok; set.beg = d_beg ? d_beg + 2 * c0 : nullptr; set.continues = c0 > 0;
             const int rc = cigar_device_run(cfg, dm, cn, b.q, b.qoff, b.r, b.roff, max_qlen, max_rlen, 0, d_out + c0,
@@ -4178,4 +4185,276 @@ extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *
     const int rc = pairs_run_scores(&cfg_s, S, S, count, nullptr, first, nullptr, m32, m32, drec, dst, st, pairs_chunk(count, m32, m32, opts));
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     return pairs_copy_back(count, drec, dst, out, stats_out, !host_offsets, st);
+}
+
+// ==================================================================== set search ===
+// pmx_search_pairs[_device] (semantics: include/parasail_amd.h): the chunk loop of the set batches with a body that keeps
+// the chunk's records in scratch, asks pmx_launch_select for the positions of those at or above min_score and appends them -- descriptor,
+// absolute index, record, statistics -- behind the hits of the chunks before, whose number lives in d_counts.  Everything of a chunk runs
+// on the caller's stream in chunk order; nothing but the hits is proportional to the number of pairs.
+extern "C" int64_t pmx_rect_pairs_count(int64_t nq, int64_t nr)
+{
+    int64_t total = 0;
+    if (nq < 0 || nr < 0) { set_err("negative set size %lld x %lld", (long long)nq, (long long)nr); return -1; }
+    if (__builtin_mul_overflow(nq, nr, &total)) { set_err("%lld x %lld pairs overflow 2^63 - 1", (long long)nq, (long long)nr); return -1; }
+    return total;
+}
+
+// The window [first, first + count) of the rectangle nq x nr: 0, or -1 with the cause.
+static int rect_pairs_window(int64_t nq, int64_t nr, int64_t first, int64_t count)
+{
+    if (first < 0 || count < 0) { set_err("negative first or count"); return -1; }
+    const int64_t total = pmx_rect_pairs_count(nq, nr);
+    if (total < 0) return -1;
+    if (first > total || count > total - first) {
+        set_err("pairs %lld .. %lld are beyond the %lld pairs of %lld x %lld sequences", (long long)first, (long long)first + (long long)count - 1,
+                (long long)total, (long long)nq, (long long)nr);
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int pmx_rect_pairs_enumerate_device(int64_t nq, int64_t nr, int64_t first, int64_t count, pmx_pair_t *d_pairs, void *stream)
+{
+    if (rect_pairs_window(nq, nr, first, count)) return -1;
+    if (count == 0) return 0;
+    if (!d_pairs) { set_err("null pairs"); return -1; }
+    const int rc = pmx_launch_rect_pairs_enumerate(nr, first, count, d_pairs, (hipStream_t)stream);
+    if (rc) { set_err("pair enumeration launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
+    return 0;
+}
+
+// What both entries refuse about the enumeration.  *R: the reference-side set on return (TRIANGLE: Q).
+static int search_pairs_shape_check(const pmx_seqset *Q, const pmx_seqset **R, int shape, int64_t first, int64_t n, const void *pairs)
+{
+    if (!Q) { set_err("null sequence set"); return -1; }
+    if (shape != PMX_PAIRS_LIST && shape != PMX_PAIRS_TRIANGLE && shape != PMX_PAIRS_RECT) { set_err("unknown pair shape %d", shape); return -1; }
+    if (shape == PMX_PAIRS_TRIANGLE) {
+        if (*R && *R != Q) { set_err("PMX_PAIRS_TRIANGLE takes one set: R must be NULL or Q"); return -1; }
+        *R = Q;
+    } else if (!*R) { set_err("null sequence set"); return -1; }
+    if (first < 0 || n < 0) { set_err("negative first or n"); return -1; }
+    if (shape == PMX_PAIRS_LIST) {
+        if (first != 0) { set_err("PMX_PAIRS_LIST: first must be 0"); return -1; }
+        if (n > 0 && !pairs) { set_err("PMX_PAIRS_LIST: null pairs"); return -1; }
+        return 0;
+    }
+    if (pairs) { set_err("an enumerated shape takes no pair list: pairs must be NULL"); return -1; }
+    return shape == PMX_PAIRS_TRIANGLE ? all_pairs_window(Q->count, first, n) : rect_pairs_window(Q->count, (*R)->count, first, n);
+}
+
+static int search_pairs_want_check(const pmx_config_t *cfg, bool stats_buffer)
+{
+    if (cfg->want & PMX_WANT_CIGAR) {
+        set_err("set search has no CIGAR output: its hit list is a pair list -- pass the hit pairs to pmx_align_pairs_ex[_device] with PMX_WANT_CIGAR");
+        return -1;
+    }
+    if ((cfg->want & PMX_WANT_STATS) && !stats_buffer) { set_err("stats requested without a stats buffer"); return -1; }
+    if (!(cfg->want & PMX_WANT_STATS) && stats_buffer) { set_err("a stats buffer without PMX_WANT_STATS in cfg->want"); return -1; }
+    return 0;
+}
+
+// The outputs of one run, all device pointers: counts[0] = passing, counts[1] = written; first_bad (host entry over wrapped sets, else
+// nullptr) keeps the lowest absolute index of a bad pair.
+struct PairHitBufs { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *counts, *first_bad; };
+
+// n > 0 pairs behind the checks; asynchronous on `st`.  index0: the absolute number of the run's first pair (what d_hit_index counts from).
+static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int shape, int64_t first, int64_t n,
+                            const pmx_pair_t *d_pairs, int64_t index0, int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                            const PairHitBufs &o, hipStream_t st, int64_t chunk)
+{
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    pmx_record_t *crec = nullptr; pmx_stats_t *cst = nullptr; int64_t *cidx = nullptr, *ccnt = nullptr; void *sel = nullptr;
+    const size_t sel_bytes = pmx_select_scratch_bytes(chunk, 0, PMX_HITS_BY_INDEX);
+    if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
+            crec = c.take<pmx_record_t>((size_t)chunk);
+            cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
+            cidx = c.take<int64_t>((size_t)chunk); ccnt = c.take<int64_t>(2);
+            sel = c.take<unsigned char>(sel_bytes);
+        })) return -1;
+    HIP_OR_RET(hipMemsetAsync(o.counts, 0, 2 * sizeof(int64_t), st));
+    return pairs_run(Q, R, n, d_pairs, first, shape, nullptr, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            int rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
+            if (rc) return rc;
+            rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
+            if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, index0 + c0, o.first_bad, st);
+            if (!rc) rc = pmx_launch_select(crec, cn, min_score, 0, PMX_HITS_BY_INDEX, cidx, cn, ccnt, sel, st);
+            if (!rc) rc = pmx_launch_pairs_append_hits(cidx, ccnt, cn, o.capacity, index0 + c0, b.pairs, crec, cst,
+                                                       o.pairs, o.index, o.recs, o.stats, o.counts, st);
+            if (rc) { set_err("hit compaction of a chunk failed (%d)", rc); return rc; }
+            return 0;
+        });
+}
+
+extern "C" int pmx_search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                       int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                       int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                       pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                       int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts)
+{
+    if (search_pairs_shape_check(Q, &R, shape, first, n, d_pairs)) return -1;
+    if (capacity < 0) { set_err("negative capacity"); return -1; }
+    if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr)) return -1;
+    if (n == 0) {
+        if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
+        return 0;
+    }
+    if (!d_counts) { set_err("null counts"); return -1; }
+    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    const PairHitBufs o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_counts, nullptr};
+    return search_pairs_run(cfg, Q, R, shape, first, n, d_pairs, first, max_qlen, max_rlen, min_score, o, (hipStream_t)stream,
+                            pairs_chunk(n, max_qlen, max_rlen, opts));
+}
+
+extern "C" void pmx_pair_hits_free(pmx_pair_hits_t *hits) { free(hits); }
+
+// The extreme lengths of a set's sequences; *odd: some sequence cannot be a whole-sequence window (empty, or beyond 2^31 - 1).
+static void seqset_host_lengths(const pmx_seqset *S, int64_t *mx, int64_t *mn, bool *odd)
+{
+    for (int64_t k = 0; k < S->count; ++k) {
+        const int64_t l = S->h_off[k + 1] - S->h_off[k];
+        if (l < 1 || l > INT32_MAX) *odd = true;
+        *mx = l > *mx ? l : *mx; *mn = l < *mn ? l : *mn;
+    }
+}
+
+extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, pmx_pair_hits_t **result)
+{
+    if (!result) { set_err("null result pointer"); return -1; }
+    *result = nullptr;
+    if (!opts) { set_err("null opts"); return -1; }
+    const int shape = opts->shape;
+    const bool listed = shape == PMX_PAIRS_LIST;
+    if (search_pairs_shape_check(Q, &R, shape, first, n, pairs)) return -1;
+    if (opts->max_hits < 0 || opts->slice_pairs < 0) { set_err("max_hits and slice_pairs must not be negative"); return -1; }
+    if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg)) return -1;
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    if (search_pairs_want_check(cfg, stats)) return -1;
+    // the result: one block -- header, descriptors, indices, records, statistics
+    auto publish = [&](int64_t h, int64_t passing, pmx_pair_hits_t **out) -> int {
+        auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        const size_t o_pairs = up(sizeof(pmx_pair_hits_t)), o_index = o_pairs + up(sizeof(pmx_pair_t) * (size_t)h);
+        const size_t o_recs = o_index + up(sizeof(int64_t) * (size_t)h), o_stats = o_recs + up(sizeof(pmx_record_t) * (size_t)h);
+        const size_t total = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0) + 16;
+        char *blk = (char *)calloc(1, total);
+        if (!blk) { set_err("out of memory"); return -1; }
+        pmx_pair_hits_t *r = (pmx_pair_hits_t *)blk;
+        r->n_hits = h; r->n_passing = passing;
+        r->pairs = (pmx_pair_t *)(blk + o_pairs); r->index = (int64_t *)(blk + o_index); r->recs = (pmx_record_t *)(blk + o_recs);
+        r->stats = stats ? (pmx_stats_t *)(blk + o_stats) : nullptr;
+        *out = r;
+        return 0;
+    };
+    if (n == 0) return publish(0, 0, result);
+    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
+    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
+    if (host_offsets && listed) {
+        const PairScan s = scan_pairs(Q, R, pairs, 0, n);
+        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
+        mq = s.mq; mr = s.mr; mnr = s.mnr;
+    } else if (host_offsets) {
+        bool odd = false; int64_t unused = INT32_MAX;
+        seqset_host_lengths(Q, &mq, &unused, &odd);
+        if (R != Q) seqset_host_lengths(R, &mr, &mnr, &odd); else { mr = mq; mnr = unused; }
+        if (odd) {                                // (rare) the first pair of the window that touches such a sequence, row by row
+            mq = mq > INT32_MAX ? INT32_MAX : mq; mr = mr > INT32_MAX ? INT32_MAX : mr;
+            std::vector<int64_t> oddr;              // the reference-side sequences that cannot be whole-sequence windows, ascending
+            try {
+                for (int64_t k = 0; k < R->count; ++k) {
+                    const int64_t l = R->h_off[k + 1] - R->h_off[k];
+                    if (l < 1 || l > INT32_MAX) oddr.push_back(k);
+                }
+            } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+            const bool tri = shape == PMX_PAIRS_TRIANGLE;
+            int64_t i = tri ? 0 : first / R->count, j = tri ? 0 : first - i * R->count, l = 0;
+            if (tri) (void)pmx_all_pairs_index(Q->count, first, &i, &j);
+            for (int64_t p = first, end = first + n; p < end; ++i, j = tri ? i + 1 : 0) {
+                const int64_t jb = std::min<int64_t>(R->count, j + (end - p));      // columns [j, jb) of row i are pairs [p, p + jb - j)
+                const char *what = host_resolve_side(Q->h_off, Q->count, i, 0, -1, &l);
+                const char *side = "query";
+                int64_t jbad = j;
+                if (!what) {
+                    const auto it = std::lower_bound(oddr.begin(), oddr.end(), j);
+                    if (it != oddr.end() && *it < jb) { jbad = *it; what = host_resolve_side(R->h_off, R->count, jbad, 0, -1, &l); side = "reference"; }
+                }
+                if (what) { set_err("pair %lld (%lld, %lld): %s: %s", (long long)(p + (jbad - j) - first), (long long)i, (long long)jbad, side, what); return -1; }
+                p += jb - j;
+            }
+        }
+        if (mnr < 1) mnr = 1;
+    }
+    const pmx_pairs_opts_t popts = {opts->chunk_pairs};
+    if (pairs_check(cfg, Q, R, &popts, (int32_t)mq, (int32_t)mr, stats)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    StreamGuard guard(st);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr, unused32 = 0;
+    pmx_config_t cfg_s = *cfg;
+    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
+    else if (!listed) {                           // wrapped sets: the longest sequence of either set, found on the device
+        if (device_maxlens(Q, Q, nullptr, Q->count, &q32, &unused32, st)) return -1;
+        r32 = q32;
+        if (R != Q && device_maxlens(R, R, nullptr, R->count, &r32, &unused32, st)) return -1;
+        if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
+    }
+    const int64_t slice = std::min<int64_t>(opts->slice_pairs > 0 ? opts->slice_pairs : (int64_t)1 << 24, n);
+    const int64_t cap_buf = opts->max_hits > 0 ? std::min<int64_t>(slice, opts->max_hits) : slice;
+    pmx_pair_t *dhp = nullptr, *dp = nullptr; int64_t *dhi = nullptr, *dcnt = nullptr; pmx_record_t *dhr = nullptr; pmx_stats_t *dhs = nullptr;
+    if (scratch_carve(SCR_PHIT, [&](Carver &c) {
+            dhp = c.take<pmx_pair_t>((size_t)cap_buf); dhi = c.take<int64_t>((size_t)cap_buf); dhr = c.take<pmx_record_t>((size_t)cap_buf);
+            dhs = stats ? c.take<pmx_stats_t>((size_t)cap_buf) : nullptr;
+            dcnt = c.take<int64_t>(3);                   // passing, written, first bad pair
+        })) return -1;
+    if (listed && scratch_reserve(sizeof(pmx_pair_t) * (size_t)slice, (void **)&dp, SCR_PUP)) return -1;
+    if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 2, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
+    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs;
+    int64_t stored = 0, passing = 0;
+    for (int64_t s0 = 0; s0 < n; s0 += slice) {
+        const int64_t sn = std::min<int64_t>(slice, n - s0);
+        const int64_t cap = opts->max_hits > 0 ? std::min<int64_t>(sn, opts->max_hits - stored) : sn;
+        if (listed) {
+            HIP_OR_RET(hipMemcpyAsync(dp, pairs + s0, sizeof(pmx_pair_t) * (size_t)sn, hipMemcpyHostToDevice, st));
+            if (!host_offsets) {
+                if (device_maxlens(Q, R, dp, sn, &q32, &r32, st)) return -1;
+                if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
+            }
+        }
+        const int64_t p0 = listed ? s0 : first + s0;     // the slice's first pair in the enumeration
+        const PairHitBufs o = {dhp, dhi, dhr, dhs, cap, dcnt, host_offsets ? nullptr : dcnt + 2};
+        int64_t h[3] = {0, 0, 0};
+        int rc = search_pairs_run(&cfg_s, Q, R, shape, listed ? 0 : p0, sn, dp, p0, q32, r32, opts->min_score, o, st, pairs_chunk(sn, q32, r32, &popts));
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipStreamSynchronize(st));
+        if (!host_offsets && h[2] != -1) { set_err("pair %lld: bad descriptor (index, window or length)", (long long)(h[2] - (listed ? 0 : first))); return -1; }
+        passing += h[0];
+        const int64_t w = h[1];
+        if (w > 0) {
+            try { vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w)); }
+            catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+            HIP_OR_RET(hipMemcpy(vp.data() + stored, dhp, sizeof(pmx_pair_t) * (size_t)w, hipMemcpyDeviceToHost));
+            HIP_OR_RET(hipMemcpy(vi.data() + stored, dhi, sizeof(int64_t) * (size_t)w, hipMemcpyDeviceToHost));
+            HIP_OR_RET(hipMemcpy(vr.data() + stored, dhr, sizeof(pmx_record_t) * (size_t)w, hipMemcpyDeviceToHost));
+            if (stats) HIP_OR_RET(hipMemcpy(vs.data() + stored, dhs, sizeof(pmx_stats_t) * (size_t)w, hipMemcpyDeviceToHost));
+            stored += w;
+        }
+    }
+    pmx_pair_hits_t *r = nullptr;
+    if (publish(stored, passing, &r)) return -1;
+    if (stored) {
+        memcpy(r->pairs, vp.data(), sizeof(pmx_pair_t) * (size_t)stored); memcpy(r->index, vi.data(), sizeof(int64_t) * (size_t)stored);
+        memcpy(r->recs, vr.data(), sizeof(pmx_record_t) * (size_t)stored);
+        if (stats) memcpy(r->stats, vs.data(), sizeof(pmx_stats_t) * (size_t)stored);
+    }
+    *result = r;
+    return 0;
 }

@@ -281,6 +281,15 @@ int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *r
 int pmx_launch_text_rebase(const int64_t *local, long long n, int64_t *text_off, hipStream_t stream);
 void pmx_complement_table_host(uint8_t table[256]);
 int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long count, pmx_pair_t *pairs, hipStream_t stream);
+// Set search.  rect: pair first + t of Q x nr, row-major.  append_hits: the chunk's hits idx[0 .. chunk_counts[0]) (chunk-local,
+// ascending; n = the chunk's pairs) go behind the counts[0] hits before them, below `capacity`: descriptor (hit_pairs, optional), index0 +
+// position (hit_index, optional), record, statistics (optional); then counts[0] += chunk_counts[0], counts[1] = min(counts[0], capacity),
+// in that order on `stream`.  first_bad[0] = min(first_bad[0], index0 + k) over the bad pairs of a chunk.
+int pmx_launch_rect_pairs_enumerate(long long nr, long long first, long long count, pmx_pair_t *pairs, hipStream_t stream);
+int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts, long long n, long long capacity, long long index0,
+                                 const pmx_pair_t *pairs, const pmx_record_t *rec, const pmx_stats_t *stats,
+                                 pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t stream);
+int pmx_launch_pairs_first_bad(const uint8_t *ok, long long n, long long index0, int64_t *first_bad, hipStream_t stream);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);

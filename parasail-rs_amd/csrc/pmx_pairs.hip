@@ -7,6 +7,12 @@
 //   pmx_pairs_fixup_kernel          the records (and statistics) of bad pairs, after the chunk's alignment
 //   pmx_all_pairs_enumerate_kernel  p -> (i, j) of the strict upper triangle, whole-sequence descriptors
 //   pmx_pairs_maxlen_kernel         the longest resolved window per side (host entries over wrapped sets)
+// for set search (pmx_search_pairs[_device]):
+//   pmx_rect_pairs_enumerate_kernel p -> (p / |R|, p % |R|) of Q x R, whole-sequence descriptors
+//   pmx_pairs_append_hits_kernel    a chunk's hits (positions from pmx_launch_select) behind the running total: descriptor, absolute
+//                                   index, record, statistics
+//   pmx_pairs_advance_hits_kernel   one thread, behind the append: the running total and the two public counts
+//   pmx_pairs_first_bad_kernel      the lowest absolute index of a bad pair (host entry over wrapped sets)
 // and, for the entries with strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device):
 //   pmx_pairs_resolve_stranded_kernel   the resolve step with the pair's strand byte
 //   pmx_pairs_gather_stranded_kernel    the gather that can reverse-complement a query window
@@ -261,6 +267,66 @@ void pmx_all_pairs_enumerate_kernel(long long nseq, long long first, long long c
     pairs[t] = d;
 }
 
+// Row-major Q x R: pair p is (p / nr, p % nr), the descriptor form of the kernel above.  p < nq * nr <= INT64_MAX, in unsigned 64-bit.
+__global__ __launch_bounds__(256)
+void pmx_rect_pairs_enumerate_kernel(unsigned long long nr, long long first, long long count, pmx_pair_t *__restrict__ pairs)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const unsigned long long p = (unsigned long long)(first + t), i = p / nr;
+    pmx_pair_t d; d.q = (int64_t)i; d.r = (int64_t)(p - i * nr); d.q_beg = 0; d.q_len = -1; d.r_beg = 0; d.r_len = -1;
+    pairs[t] = d;
+}
+
+// ---- set search: a chunk's hits behind the hits of the chunks before it ----------------------------------------------------------
+// idx[0 .. chunk_counts[0]) are the chunk-local positions of the chunk's hits in ascending order (pmx_launch_select, by index, no
+// limit); counts[0] is the number of hits of the earlier chunks.  Hit x of the chunk goes to position counts[0] + x when that lies
+// below `capacity`: where a hit lands depends on the selection's scan and the total alone, never on which block runs first.  counts is
+// only read here; pmx_pairs_advance_hits_kernel moves it, behind this kernel on the same stream.  A descriptor is 32 bytes: two
+// 16-byte accesses where both sides are 16-byte aligned (they are for hipMalloc'ed arrays), four 8-byte ones otherwise.
+__global__ __launch_bounds__(256)
+void pmx_pairs_append_hits_kernel(const int64_t *__restrict__ idx, const int64_t *__restrict__ chunk_counts, const int64_t *__restrict__ counts,
+                                  long long capacity, long long index0, const pmx_pair_t *__restrict__ pairs,
+                                  const pmx_record_t *__restrict__ rec, const pmx_stats_t *__restrict__ stats,
+                                  pmx_pair_t *__restrict__ hit_pairs, int64_t *__restrict__ hit_index,
+                                  pmx_record_t *__restrict__ hit_recs, pmx_stats_t *__restrict__ hit_stats)
+{
+    const long long h = chunk_counts[0], base = counts[0];
+    const bool wide = (((uintptr_t)pairs | (uintptr_t)hit_pairs) & 15) == 0;
+    for (long long x = (long long)blockIdx.x * 256 + threadIdx.x; x < h; x += (long long)gridDim.x * 256) {
+        const long long pos = base + x;
+        if (pos >= capacity) return;                              // (positions ascend with x)
+        const long long k = idx[x];
+        if (hit_pairs) {
+            if (wide) {
+                const uint4 *s = reinterpret_cast<const uint4 *>(pairs + k);
+                uint4 *d = reinterpret_cast<uint4 *>(hit_pairs + pos);
+                const uint4 a = s[0], b = s[1];
+                d[0] = a; d[1] = b;
+            } else
+                hit_pairs[pos] = pairs[k];
+        }
+        if (hit_index) hit_index[pos] = index0 + k;
+        hit_recs[pos] = rec[k];
+        if (hit_stats) hit_stats[pos] = stats[k];
+    }
+}
+
+__global__ void pmx_pairs_advance_hits_kernel(const int64_t *__restrict__ chunk_counts, long long capacity, int64_t *__restrict__ counts)
+{
+    const long long total = counts[0] + chunk_counts[0];
+    counts[0] = total; counts[1] = total < capacity ? total : capacity;
+}
+
+// first_bad[0] (the caller sets it to INT64_MAX) = the lowest index0 + k with ok[k] == 0.  One atomic per wave that holds a bad pair.
+__global__ __launch_bounds__(256)
+void pmx_pairs_first_bad_kernel(const uint8_t *__restrict__ ok, long long n, long long index0, unsigned long long *__restrict__ first_bad)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long bad = __ballot(k < n && !ok[k]);
+    if (bad && (threadIdx.x & 63) == 0) atomicMin(first_bad, (unsigned long long)(index0 + k + __ffsll((long long)bad) - 1));
+}
+
 // out[0] / out[1] = the longest good query / reference window (0: none), the caller zeroes them.  pairs == nullptr: the n whole
 // sequences of the query-side set.  One atomic per wave and side.
 __global__ __launch_bounds__(256)
@@ -349,6 +415,31 @@ int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long co
 {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(pmx_all_pairs_enumerate_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, nseq, first, count, pairs);
+    return pmx_pairs_launched();
+}
+int pmx_launch_rect_pairs_enumerate(long long nr, long long first, long long count, pmx_pair_t *pairs, hipStream_t st)
+{
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL(pmx_rect_pairs_enumerate_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (unsigned long long)nr, first, count, pairs);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts, long long n, long long capacity, long long index0,
+                                 const pmx_pair_t *pairs, const pmx_record_t *rec, const pmx_stats_t *stats,
+                                 pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    if (capacity > 0) {                                            // (the hit count is on the device: a grid for the chunk, capped; the loop strides)
+        const long long blocks = (n + 255) / 256;
+        hipLaunchKernelGGL(pmx_pairs_append_hits_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, idx, chunk_counts,
+                           (const int64_t *)counts, capacity, index0, pairs, rec, stats, hit_pairs, hit_index, hit_recs, hit_stats);
+    }
+    hipLaunchKernelGGL(pmx_pairs_advance_hits_kernel, dim3(1), dim3(1), 0, st, chunk_counts, capacity, counts);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_first_bad(const uint8_t *ok, long long n, long long index0, int64_t *first_bad, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_first_bad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, index0, (unsigned long long *)first_bad);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
