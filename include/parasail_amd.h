@@ -586,6 +586,63 @@ int  pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_
                       const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, pmx_pair_hits_t **result);
 void pmx_pair_hits_free(pmx_pair_hits_t *hits);
 
+/* Per-query top-K set search (extension): for every query row of the rectangle Q x R the best k references, selected on the device
+ * while the rows' pairs go through the chunk pipeline of the set batches.  Set search above keeps what passes ONE score for the whole
+ * enumeration; many queries against a database want the best k of EACH query, which no single threshold gives.  Device memory is
+ * bounded by the chunk scratch, k entries per row and the hits, not by the number of pairs.
+ *
+ * Inputs.  The query rows [q_first, q_first + nq) of Q against all of R (R == Q allowed; R == NULL means Q), whole sequences; min_score
+ * (INT32_MIN: pure top-K); k, 1 .. PMX_TOPK_MAX; skip_self (R must be Q: the pair (i, i) is never a candidate); chunk_pairs as in the
+ * other set entries.  |R| <= 2^31 - 1.
+ *
+ * Candidates and the cut.  Let rec(i, j) be the record pmx_align_pairs_device writes for the descriptor
+ * pmx_rect_pairs_enumerate_device generates for pair p = i |R| + j.  P_i = { j : rec(i, j).score >= min_score } (without j == i under
+ * skip_self): only the score is looked at, as in pmx_select_hits_device, so a bad descriptor's record {0, -1, -1, PMX_FLAG_BAD_PAIR} is
+ * a candidate when min_score <= 0 and keeps its flag.  Row i keeps the first min(k, |P_i|) members of P_i under (score descending, j
+ * ascending): the cut falls inside the tie run at the k-th score by ascending j, the rule of pmx_select_hits_device applied per row.
+ *
+ * Outputs of the device entry, CSR: d_row_off receives nq + 1 offsets starting at 0 and is always written in full; row i's hits lie at
+ * [off[i - q_first], off[i - q_first + 1]) in (score descending, j ascending) order.  Per hit, a structure of arrays like set
+ * search's: d_hit_pairs (optional) the descriptor {i, j, 0, -1, 0, -1}, a valid d_pairs argument for pmx_align_pairs_ex_device;
+ * d_hit_index (optional) p, absolute; d_hit_recs the record, byte for byte; d_hit_stats the statistics, iff PMX_WANT_STATS.
+ * d_row_passing (optional): nq values of |P_i|.  d_counts[0] = hits kept in total (= off[nq]), d_counts[1] = hits written
+ * (min(kept, capacity)), d_counts[2] = the sum of |P_i|.  Only hit positions below `capacity` are written, entries behind them are
+ * untouched; capacity == 0 counts only.
+ *
+ * Determinism.  The output is bit-identical from run to run and chunk_pairs / slice_rows never change a byte: (score, j) orders a row
+ * totally, the kept set is the k first under that order whatever the order of arrival, and every output position comes from the sorted
+ * lists and a scan of their lengths.  The selection kernels contain no atomic.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: everything pmx_search_pairs_device refuses for PMX_PAIRS_RECT
+ * (PMX_WANT_CIGAR with the same text: the hit pairs go to pmx_align_pairs_ex[_device]); k outside 1 .. PMX_TOPK_MAX (larger k:
+ * pmx_search_pairs over the rows, then pmx_select_hits_device per row); a negative q_first or nq, rows beyond |Q|; |R| above
+ * 2^31 - 1; skip_self with R != Q; a negative capacity; NULL d_hit_recs with capacity > 0; NULL d_row_off or d_counts with nq > 0;
+ * PMX_WANT_STATS without d_hit_stats, or d_hit_stats without PMX_WANT_STATS.  nq == 0 succeeds and writes zero counts (and
+ * d_row_off[0] = 0) where those pointers are given.
+ *
+ * The device entry is asynchronous on `stream` under the rule of the other set entries.  Scratch of the calling thread: the chunk
+ * buffers of pmx_align_pairs_device; per pair of a chunk 16 bytes of record, 12 of statistics (PMX_WANT_STATS) and at most 8 of tile
+ * survivors; per row min(k, |R|) x (8 + 16 (+ 12)) bytes of running state.
+ *
+ * The host entry validates as pmx_search_pairs does for a rectangle and names the first bad pair "pair x (i, j): side: cause" (x counts
+ * from the first pair of row q_first): before any GPU work when both sets carry host offsets, otherwise at the end of the slice whose
+ * device pass met it.  It works in slices of opts->slice_rows rows (0: as many as keep a slice's running state within 256 MiB, the
+ * bound of the chunk buffers), one stream synchronisation per slice.  *result is one callee-allocated block (NULL on failure) released
+ * with pmx_topk_hits_free: row_off holds n_rows + 1 entries, row_passing n_rows, pairs / index / recs n_hits, stats too with
+ * PMX_WANT_STATS (else NULL); n_passing is the sum of row_passing. */
+#define PMX_TOPK_MAX 1024
+int pmx_search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                           int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                           pmx_pair_t *d_hit_pairs /* optional */, int64_t *d_hit_index /* optional */,
+                           pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats /* iff PMX_WANT_STATS */, int64_t capacity,
+                           int64_t *d_row_off /* nq + 1 */, int64_t *d_row_passing /* nq, optional */,
+                           int64_t *d_counts /* [0] kept, [1] written, [2] passing */, void *stream, const pmx_pairs_opts_t *opts);
+typedef struct pmx_topk_opts { int32_t min_score, k, skip_self; int64_t chunk_pairs, slice_rows; } pmx_topk_opts_t;   /* 32 bytes */
+typedef struct pmx_topk_hits { int64_t n_rows, n_hits, n_passing; int64_t *row_off, *row_passing; pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; } pmx_topk_hits_t;
+int  pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                     const pmx_topk_opts_t *opts, pmx_topk_hits_t **result);
+void pmx_topk_hits_free(pmx_topk_hits_t *hits);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -163,6 +163,33 @@ pub struct PmxPairHits {
     pub stats: *mut PmxStats,
 }
 
+/// `pmx_topk_opts_t` (32 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct PmxTopkOpts {
+    pub min_score: i32,   // i32::MIN = pure top-K
+    pub k: i32,           // 1 ..= PMX_TOPK_MAX
+    pub skip_self: i32,   // R must be Q: the pair (i, i) is never a candidate
+    pub chunk_pairs: i64, // 0 = default; never changes a result
+    pub slice_rows: i64,  // 0 = default; never changes a result
+}
+
+pub const PMX_TOPK_MAX: i32 = 1024;
+
+/// `pmx_topk_hits_t`: one callee-allocated block, released with `pmx_topk_hits_free`.
+#[repr(C)]
+pub struct PmxTopkHits {
+    pub n_rows: i64,
+    pub n_hits: i64,
+    pub n_passing: i64,
+    pub row_off: *mut i64,
+    pub row_passing: *mut i64,
+    pub pairs: *mut PmxPair,
+    pub index: *mut i64,
+    pub recs: *mut PmxRecord,
+    pub stats: *mut PmxStats,
+}
+
 /// Opaque `pmx_seqset_t`.
 #[repr(C)]
 pub struct PmxSeqSet {
@@ -227,6 +254,18 @@ extern "C" {
         opts: *const PmxPairSearchOpts, result: *mut *mut PmxPairHits,
     ) -> c_int;
     fn pmx_pair_hits_free(hits: *mut PmxPairHits);
+    /// Per-query top-K into caller buffers on the device, CSR: `d_row_off` gets `nq + 1` offsets, `d_counts` kept / written / passing.
+    pub fn pmx_search_topk_device(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, q_first: i64, nq: i64, max_qlen: i32, max_rlen: i32,
+        min_score: i32, k: i32, skip_self: i32, d_hit_pairs: *mut PmxPair, d_hit_index: *mut i64, d_hit_recs: *mut PmxRecord,
+        d_hit_stats: *mut PmxStats, capacity: i64, d_row_off: *mut i64, d_row_passing: *mut i64, d_counts: *mut i64,
+        stream: *mut c_void, opts: *const PmxPairsOpts,
+    ) -> c_int;
+    fn pmx_search_topk(
+        cfg: *const PmxConfig, q: *const PmxSeqSet, r: *const PmxSeqSet, q_first: i64, nq: i64, opts: *const PmxTopkOpts,
+        result: *mut *mut PmxTopkHits,
+    ) -> c_int;
+    fn pmx_topk_hits_free(hits: *mut PmxTopkHits);
     fn pmx_align_batch(
         cfg: *const PmxConfig, n: i64,
         qbuf: *const u8, qoff: *const i64, rbuf: *const u8, roff: *const i64,
@@ -503,6 +542,67 @@ impl Drop for PairHits {
 }
 
 unsafe impl Send for PairHits {}
+
+/// Hits of a per-query top-K search, CSR by query row: the callee's block, released with `pmx_topk_hits_free` on drop.  Row `i`'s hits
+/// are `row_off()[i] .. row_off()[i + 1]`, in (score descending, reference index ascending) order.
+pub struct TopKHits {
+    inner: *mut PmxTopkHits,
+}
+
+impl TopKHits {
+    fn r(&self) -> &PmxTopkHits {
+        unsafe { &*self.inner }
+    }
+    pub fn len(&self) -> usize {
+        self.r().n_hits as usize
+    }
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+    pub fn rows(&self) -> usize {
+        self.r().n_rows as usize
+    }
+    /// References at or above `min_score`, summed over the rows, kept or not.
+    pub fn passing(&self) -> i64 {
+        self.r().n_passing
+    }
+    pub fn row_off(&self) -> &[i64] {
+        unsafe { std::slice::from_raw_parts(self.r().row_off, self.rows() + 1) }
+    }
+    pub fn row_passing(&self) -> &[i64] {
+        if self.rows() == 0 { &[] } else { unsafe { std::slice::from_raw_parts(self.r().row_passing, self.rows()) } }
+    }
+    /// The hits of local row `i` as a range into `pairs()` / `index()` / `records()` / `stats()`.
+    pub fn row(&self, i: usize) -> std::ops::Range<usize> {
+        let off = self.row_off();
+        off[i] as usize..off[i + 1] as usize
+    }
+    /// The hits' descriptors: a valid pair list for `Aligner::align_pairs`.
+    pub fn pairs(&self) -> &[PmxPair] {
+        if self.is_empty() { &[] } else { unsafe { std::slice::from_raw_parts(self.r().pairs, self.len()) } }
+    }
+    /// `p = i * |R| + j` of every hit.
+    pub fn index(&self) -> &[i64] {
+        if self.is_empty() { &[] } else { unsafe { std::slice::from_raw_parts(self.r().index, self.len()) } }
+    }
+    pub fn records(&self) -> &[PmxRecord] {
+        if self.is_empty() { &[] } else { unsafe { std::slice::from_raw_parts(self.r().recs, self.len()) } }
+    }
+    pub fn stats(&self) -> Option<&[PmxStats]> {
+        let p = self.r().stats;
+        if p.is_null() { None } else { Some(unsafe { std::slice::from_raw_parts(p, self.len()) }) }
+    }
+}
+
+impl Drop for TopKHits {
+    fn drop(&mut self) {
+        if !self.inner.is_null() {
+            unsafe { pmx_topk_hits_free(self.inner) }
+        }
+    }
+}
+
+unsafe impl Send for TopKHits {}
 
 /// What a set search enumerates.
 pub enum PairShape<'a> {
@@ -833,6 +933,24 @@ impl Aligner {
             return Err(last_error());
         }
         Ok(PairHits { inner })
+    }
+
+    /// Per-query top-K: for every query row `first_row .. first_row + rows` of `q` (`rows` `None`: to the last) the best `k`
+    /// references of `r` (`None`: `q`) with score at least `min_score` (`i32::MIN`: pure top-K), in (score descending, reference
+    /// index ascending) order.  `skip_self` (`r` is `q`) leaves the pair (i, i) out.  Only the hits leave the device.
+    pub fn search_topk(&self, q: &SeqSet, r: Option<&SeqSet>, k: i32, min_score: i32, skip_self: bool, first_row: i64, rows: Option<i64>,
+                       chunk_pairs: i64, slice_rows: i64) -> Result<TopKHits> {
+        assert!(self.profile.is_null(), "search_topk takes no profile");
+        let nq = rows.unwrap_or(q.len() as i64 - first_row);
+        let rptr = r.map_or(std::ptr::null(), |s| s.inner as *const PmxSeqSet);
+        let cfg = self.pmx_config(if self.want_stats { PMX_WANT_STATS } else { 0 });
+        let opts = PmxTopkOpts { min_score, k, skip_self: skip_self as i32, chunk_pairs, slice_rows };
+        let mut inner: *mut PmxTopkHits = std::ptr::null_mut();
+        let rc = unsafe { pmx_search_topk(&cfg, q.inner, rptr, first_row, nq, &opts, &mut inner) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok(TopKHits { inner })
     }
 
     /// 2-bit packed DNA (base b in byte b / 4 at bits 2 * (b % 4); code c = letter c of the matrix alphabet; offsets count

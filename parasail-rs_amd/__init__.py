@@ -95,6 +95,19 @@ class pmx_pair_hits_t(C.Structure):
                 ("recs", C.c_void_p), ("stats", C.c_void_p)]
 
 
+class pmx_topk_opts_t(C.Structure):
+    _fields_ = [("min_score", C.c_int32), ("k", C.c_int32), ("skip_self", C.c_int32), ("chunk_pairs", C.c_int64),
+                ("slice_rows", C.c_int64)]
+
+
+class pmx_topk_hits_t(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_hits", C.c_int64), ("n_passing", C.c_int64), ("row_off", C.c_void_p),
+                ("row_passing", C.c_void_p), ("pairs", C.c_void_p), ("index", C.c_void_p), ("recs", C.c_void_p),
+                ("stats", C.c_void_p)]
+
+
+TOPK_MAX = 1024
+INT32_MIN = -(1 << 31)
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
 STATS_DTYPE = np.dtype([("matches", "<i4"), ("similar", "<i4"), ("length", "<i4")])
 HIT_DTYPE = np.dtype([("index", "<i8"), ("first", RECORD_DTYPE), ("diag", "<i4"), ("beg_query", "<i4"), ("beg_ref", "<i4"),
@@ -242,6 +255,12 @@ _sig("pmx_search_pairs_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.
 _sig("pmx_search_pairs", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
      C.POINTER(pmx_pair_search_opts_t), C.POINTER(C.POINTER(pmx_pair_hits_t)))
 _sig("pmx_pair_hits_free", None, C.POINTER(pmx_pair_hits_t))
+_sig("pmx_search_topk_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_search_topk", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+     C.POINTER(pmx_topk_opts_t), C.POINTER(C.POINTER(pmx_topk_hits_t)))
+_sig("pmx_topk_hits_free", None, C.POINTER(pmx_topk_hits_t))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -961,6 +980,30 @@ class Aligner:
         finally:
             lib.pmx_pair_hits_free(res)
 
+    def search_topk(self, Q, R=None, k=10, min_score=INT32_MIN, skip_self=False, first_row=0, rows=None, stats=False, chunk_pairs=0,
+                    slice_rows=0):
+        """Per-query top-K: for each query row [first_row, first_row + rows) of Q the best k references of R (None: Q) with score
+        >= min_score, in (score descending, reference index ascending) order, as a TopKHits.  rows None: to the last row.
+        skip_self (R is Q) leaves the pair (i, i) out.  stats=True adds the hits' statistics.  Only the hits leave the device;
+        chunk_pairs and slice_rows never change the result."""
+        if not self._profile.is_null():
+            raise BatchError("search_topk takes no profile")
+        cfg = self._config()
+        if stats:
+            cfg.want |= WANT_STATS
+        if rows is None:
+            rows = len(Q) - int(first_row)
+        opts = pmx_topk_opts_t(int(min_score), int(k), 1 if skip_self else 0, int(chunk_pairs), int(slice_rows))
+        res = C.POINTER(pmx_topk_hits_t)()
+        rc = lib.pmx_search_topk(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows),
+                                 C.byref(opts), C.byref(res))
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        try:
+            return TopKHits(res.contents)
+        finally:
+            lib.pmx_topk_hits_free(res)
+
     def align_batch_2bit(self, q2, qoff, r2, roff, out=None):
         """2-bit packed input (see pack_2bit): offsets count bases.  `out` as in align_batch_packed."""
         n = len(roff) - 1
@@ -1175,6 +1218,36 @@ class PairHits:
         return self.n_hits
 
 
+class TopKHits:
+    """Result of Aligner.search_topk, CSR by query row: row_off (int64, n_rows + 1), row_passing (int64: the references at or above
+    min_score per row, kept or not), n_passing (their sum) and, per hit, pairs (PAIR_DTYPE: the descriptor, fit for align_pairs),
+    index (int64: p = i * len(R) + j), records (RECORD_DTYPE) and stats (STATS_DTYPE, or None when not asked for).  A row's hits
+    are in (score descending, reference index ascending) order; row(i) slices them out."""
+
+    def __init__(self, r):
+        h, n = int(r.n_hits), int(r.n_rows)
+        self.n_rows, self.n_hits, self.n_passing = n, h, int(r.n_passing)
+
+        def take(ptr, count, dtype):
+            if not ptr or not count:
+                return np.zeros(count, dtype=dtype)
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype).copy()
+        self.row_off = take(r.row_off, n + 1, np.int64)
+        self.row_passing = take(r.row_passing, n, np.int64)
+        self.pairs = take(r.pairs, h, PAIR_DTYPE)
+        self.index = take(r.index, h, np.int64)
+        self.records = take(r.recs, h, RECORD_DTYPE)
+        self.stats = take(r.stats, h, STATS_DTYPE) if r.stats else None
+
+    def __len__(self):
+        return self.n_hits
+
+    def row(self, i):
+        """(pairs, index, records, stats) of local row i (0 = first_row)."""
+        a, b = int(self.row_off[i]), int(self.row_off[i + 1])
+        return self.pairs[a:b], self.index[a:b], self.records[a:b], (self.stats[a:b] if self.stats is not None else None)
+
+
 def _take_cigars(cbuf, coff):
     """The per-pair CIGAR strings out of a callee-allocated text block (offsets coff[n + 1]); the block is released."""
     n = len(coff) - 1
@@ -1371,6 +1444,20 @@ def search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen,
     rc = lib.pmx_search_pairs_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(shape), int(first), int(n),
                                      d_pairs, max_qlen, max_rlen, int(min_score), d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                                      int(capacity), d_counts, stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs,
+                       d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, stream=0, chunk_pairs=0):
+    """Device-pointer entry of the per-query top-K: rows [q_first, q_first + nq) of Q against R (None: Q); per row the best k
+    references with score >= min_score, CSR: d_row_off gets nq + 1 offsets, the hits go to d_hit_pairs / d_hit_index (optional),
+    d_hit_recs and d_hit_stats (`capacity` entries each), d_row_passing (optional) the rows' passing counts and d_counts
+    [kept, written, passing]."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_search_topk_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
+                                    max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
+                                    d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream, C.byref(opts))
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

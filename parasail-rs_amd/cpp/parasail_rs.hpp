@@ -710,6 +710,42 @@ public:
         return out;
     }
 
+    // additive: per-query top-K (pmx_search_topk): for every query row [first_row, first_row + rows) of Q the best k references of R
+    // (nullptr: Q) with score >= min_score, in (score descending, reference index ascending) order; CSR by row: row i's hits are
+    // [row_off[i], row_off[i + 1]).  rows < 0: to the last row.  skip_self (R is Q) leaves the pair (i, i) out.  Only the hits leave the
+    // device; chunk_pairs and slice_rows never change the result.
+    struct TopKHits {
+        int64_t n_passing = 0;
+        std::vector<int64_t> row_off, row_passing;
+        std::vector<pmx_pair_t> pairs;
+        std::vector<int64_t> index;
+        std::vector<pmx_record_t> recs;
+        std::vector<pmx_stats_t> stats;
+    };
+    TopKHits search_topk(const SeqSet &Q, const SeqSet *R, int32_t k, int32_t min_score = INT32_MIN, bool skip_self = false,
+                         int64_t first_row = 0, int64_t rows = -1, int64_t chunk_pairs = 0, int64_t slice_rows = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "search_topk takes no profile");
+        if (rows < 0) rows = Q.len() - first_row;
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        const pmx_topk_opts_t opts = {min_score, k, skip_self ? 1 : 0, chunk_pairs, slice_rows};
+        pmx_topk_hits_t *res = nullptr;
+        const int rc = pmx_search_topk(&cfg, Q.inner, R ? R->inner : nullptr, first_row, rows, &opts, &res);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        TopKHits out;
+        const size_t h = (size_t)res->n_hits, n = (size_t)res->n_rows;
+        out.n_passing = res->n_passing;
+        out.row_off.assign(res->row_off, res->row_off + n + 1);
+        out.row_passing.assign(res->row_passing, res->row_passing + n);
+        out.pairs.assign(res->pairs, res->pairs + h);
+        out.index.assign(res->index, res->index + h);
+        out.recs.assign(res->recs, res->recs + h);
+        if (res->stats) out.stats.assign(res->stats, res->stats + h);
+        pmx_topk_hits_free(res);
+        return out;
+    }
+
     std::shared_ptr<Matrix> matrix;
     int gap_open = 0, gap_extend = 0;
     std::string vec_strategy;

@@ -1375,7 +1375,9 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_PUP = 22, SCR_PREC = 23, SCR_PST = 24,                                        // set batches, host entries: uploaded descriptors, records, statistics
        SCR_PSRCH = 25,                                                                   // set search: a chunk's records, statistics, hit positions, counts and select scratch
        SCR_PHIT = 26,                                                                    // set search, host entry: a slice's hit arrays, counts, first bad pair
-       SCR_SLOTS = 27 };
+       SCR_PTOPK = 27,                                                                   // per-query top-K: a chunk's records and statistics, tile survivors, the rows' running state, scan scratch
+       SCR_PTHIT = 28,                                                                   // per-query top-K, host entry: a slice's CSR arrays, counts, first bad pair
+       SCR_SLOTS = 29 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -4450,6 +4452,236 @@ extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
     }
     pmx_pair_hits_t *r = nullptr;
     if (publish(stored, passing, &r)) return -1;
+    if (stored) {
+        memcpy(r->pairs, vp.data(), sizeof(pmx_pair_t) * (size_t)stored); memcpy(r->index, vi.data(), sizeof(int64_t) * (size_t)stored);
+        memcpy(r->recs, vr.data(), sizeof(pmx_record_t) * (size_t)stored);
+        if (stats) memcpy(r->stats, vs.data(), sizeof(pmx_stats_t) * (size_t)stored);
+    }
+    *result = r;
+    return 0;
+}
+
+// ==================================================================== per-query top-K ===
+// pmx_search_topk[_device] (semantics: include/parasail_amd.h): the chunk loop of the set batches over whole rows of the
+// rectangle Q x R with a body that keeps the chunk's records in scratch and merges them into one list of at most k entries per row
+// (pmx_topk.hip); the lists live in scratch until the last chunk, then go to their CSR positions.  Everything of a chunk runs on the
+// caller's stream in chunk order.
+struct TopkOut { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *row_off, *row_passing, *counts, *first_bad; };
+
+// What both entries refuse about the rows, k and the flag.  *R: the reference-side set on return.
+static int topk_shape_check(const pmx_seqset *Q, const pmx_seqset **R, int64_t q_first, int64_t nq, int64_t k, int skip_self)
+{
+    if (!Q) { set_err("null sequence set"); return -1; }
+    if (!*R) *R = Q;
+    if (skip_self && *R != Q) { set_err("skip_self needs R to be Q (or NULL): there is no self pair between two sets"); return -1; }
+    if (q_first < 0 || nq < 0) { set_err("negative q_first or nq"); return -1; }
+    if (q_first > Q->count || nq > Q->count - q_first) {
+        set_err("rows %lld .. %lld are beyond the %lld sequences of Q", (long long)q_first, (long long)q_first + (long long)nq - 1, (long long)Q->count);
+        return -1;
+    }
+    if ((*R)->count > INT32_MAX) { set_err("nseq %lld of R is outside 0 .. 2^31 - 1", (long long)(*R)->count); return -1; }
+    if (pmx_rect_pairs_count(Q->count, (*R)->count) < 0) return -1;
+    if (k < 1 || k > PMX_TOPK_MAX) {
+        set_err("k %lld is outside 1 .. %d (a row's list is sorted in LDS): for more hits per query run pmx_search_pairs over the rows and "
+                "pmx_select_hits_device per row", (long long)k, PMX_TOPK_MAX);
+        return -1;
+    }
+    return 0;
+}
+
+// nq > 0 rows behind the checks; asynchronous on `st`.
+static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t max_rlen,
+                    int32_t min_score, int32_t k, int skip_self, const TopkOut &o, hipStream_t st, const pmx_pairs_opts_t *opts)
+{
+    const int64_t nr = R->count;
+    if (nr == 0) {                                    // no pairs: every row is empty
+        HIP_OR_RET(hipMemsetAsync(o.row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st));
+        if (o.row_passing) HIP_OR_RET(hipMemsetAsync(o.row_passing, 0, sizeof(int64_t) * (size_t)nq, st));
+        HIP_OR_RET(hipMemsetAsync(o.counts, 0, 3 * sizeof(int64_t), st));
+        return 0;
+    }
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    const int ks = (int)std::min<int64_t>(k, nr);     // a row has |R| candidates at most
+    const int64_t n = nq * nr, first = q_first * nr;
+    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts), (int64_t)1 << 26);      // (a chunk's positions fit 32 bits)
+    long long rows = 0, tps = 0, tstride = 0;
+    pmx_topk_geometry(chunk, nr, ks, &rows, &tps, &tstride);
+    pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr;
+    uint64_t *tkeys = nullptr, *skeys = nullptr; int32_t *tcnt = nullptr, *tpass = nullptr, *sheld = nullptr; int64_t *spass = nullptr; void *scan = nullptr;
+    const size_t scan_bytes = pmx_text_scan_scratch_bytes(nq);
+    if (scratch_carve(SCR_PTOPK, [&](Carver &c) {
+            crec = c.take<pmx_record_t>((size_t)chunk);
+            cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
+            tkeys = c.take<uint64_t>((size_t)rows * (size_t)tps * (size_t)tstride);
+            tcnt = c.take<int32_t>((size_t)rows * (size_t)tps); tpass = c.take<int32_t>((size_t)rows * (size_t)tps);
+            skeys = c.take<uint64_t>((size_t)nq * (size_t)ks); srec = c.take<pmx_record_t>((size_t)nq * (size_t)ks);
+            sst = stats ? c.take<pmx_stats_t>((size_t)nq * (size_t)ks) : nullptr;
+            sheld = c.take<int32_t>((size_t)nq + 2); spass = c.take<int64_t>((size_t)nq);
+            scan = c.take<unsigned char>(scan_bytes);
+        })) return -1;
+    HIP_OR_RET(hipMemsetAsync(sheld, 0, sizeof(int32_t) * ((size_t)nq + 2), st));
+    HIP_OR_RET(hipMemsetAsync(spass, 0, sizeof(int64_t) * (size_t)nq, st));
+    int rc = pairs_run(Q, R, n, nullptr, first, PMX_PAIRS_RECT, nullptr, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            int rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
+            if (rc) return rc;
+            rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
+            if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, first + c0, o.first_bad, st);
+            if (!rc) rc = pmx_launch_topk_merge(crec, cst, first + c0, cn, nr, q_first, ks, min_score, skip_self, tps, tstride, tkeys, tcnt, tpass,
+                                                skeys, srec, sst, sheld, spass, st);
+            if (rc) { set_err("top-K merge of a chunk failed (%d)", rc); return rc; }
+            return 0;
+        });
+    if (rc) return rc;
+    rc = pmx_launch_text_offsets(sheld, nq, o.row_off, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_topk_emit(nq, q_first, nr, ks, skeys, srec, sst, sheld, spass, o.row_off, o.capacity, o.pairs, o.index, o.recs, o.stats,
+                                       o.row_passing, o.counts, st);
+    if (rc) { set_err("top-K emit failed (%d)", rc); return rc; }
+    return 0;
+}
+
+extern "C" int pmx_search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                      int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                      pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                      int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                      void *stream, const pmx_pairs_opts_t *opts)
+{
+    if (topk_shape_check(Q, &R, q_first, nq, k, skip_self)) return -1;
+    if (capacity < 0) { set_err("negative capacity"); return -1; }
+    if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr)) return -1;
+    if (nq == 0) {
+        if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), (hipStream_t)stream));
+        if (d_row_off) HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), (hipStream_t)stream));
+        return 0;
+    }
+    if (!d_row_off) { set_err("null row offsets"); return -1; }
+    if (!d_counts) { set_err("null counts"); return -1; }
+    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    const TopkOut o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, nullptr};
+    return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts);
+}
+
+extern "C" void pmx_topk_hits_free(pmx_topk_hits_t *hits) { free(hits); }
+
+extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                               const pmx_topk_opts_t *opts, pmx_topk_hits_t **result)
+{
+    if (!result) { set_err("null result pointer"); return -1; }
+    *result = nullptr;
+    if (!opts) { set_err("null opts"); return -1; }
+    if (topk_shape_check(Q, &R, q_first, nq, opts->k, opts->skip_self)) return -1;
+    if (opts->slice_rows < 0) { set_err("slice_rows must not be negative"); return -1; }
+    if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg)) return -1;
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    if (search_pairs_want_check(cfg, stats)) return -1;
+    // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics
+    auto publish = [&](int64_t rows, int64_t h, pmx_topk_hits_t **out) -> int {
+        auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        const size_t o_off = up(sizeof(pmx_topk_hits_t)), o_pass = o_off + up(sizeof(int64_t) * (size_t)(rows + 1));
+        const size_t o_pairs = o_pass + up(sizeof(int64_t) * (size_t)rows), o_index = o_pairs + up(sizeof(pmx_pair_t) * (size_t)h);
+        const size_t o_recs = o_index + up(sizeof(int64_t) * (size_t)h), o_stats = o_recs + up(sizeof(pmx_record_t) * (size_t)h);
+        const size_t total = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0) + 16;
+        char *blk = (char *)calloc(1, total);
+        if (!blk) { set_err("out of memory"); return -1; }
+        pmx_topk_hits_t *r = (pmx_topk_hits_t *)blk;
+        r->n_rows = rows; r->n_hits = h; r->n_passing = 0;
+        r->row_off = (int64_t *)(blk + o_off); r->row_passing = (int64_t *)(blk + o_pass);
+        r->pairs = (pmx_pair_t *)(blk + o_pairs); r->index = (int64_t *)(blk + o_index); r->recs = (pmx_record_t *)(blk + o_recs);
+        r->stats = stats ? (pmx_stats_t *)(blk + o_stats) : nullptr;
+        *out = r;
+        return 0;
+    };
+    if (nq == 0) return publish(0, 0, result);
+    const int64_t nr = R->count;
+    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
+    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
+    if (host_offsets && nr > 0) {
+        bool odd = false; int64_t unused = INT32_MAX;
+        seqset_host_lengths(Q, &mq, &unused, &odd);
+        if (R != Q) seqset_host_lengths(R, &mr, &mnr, &odd); else { mr = mq; mnr = unused; }
+        if (odd) {                                // (rare) the first pair of the rows, row-major, that touches a sequence no whole-sequence window fits
+            mq = mq > INT32_MAX ? INT32_MAX : mq; mr = mr > INT32_MAX ? INT32_MAX : mr;
+            int64_t jbad = -1, l = 0;             // the first such reference: it spoils every row
+            for (int64_t j = 0; j < nr && jbad < 0; ++j)
+                if (host_resolve_side(R->h_off, nr, j, 0, -1, &l)) jbad = j;
+            for (int64_t i = q_first; i < q_first + nq; ++i) {
+                const char *what = host_resolve_side(Q->h_off, Q->count, i, 0, -1, &l), *side = "query";
+                int64_t j = 0;
+                if (!what && jbad >= 0) { j = jbad; what = host_resolve_side(R->h_off, nr, j, 0, -1, &l); side = "reference"; }
+                if (what) { set_err("pair %lld (%lld, %lld): %s: %s", (long long)((i - q_first) * nr + j), (long long)i, (long long)j, side, what); return -1; }
+            }
+        }
+        if (mnr < 1) mnr = 1;
+    }
+    const pmx_pairs_opts_t popts = {opts->chunk_pairs};
+    if (pairs_check(cfg, Q, R, &popts, (int32_t)mq, (int32_t)mr, stats)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    StreamGuard guard(st);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr, unused32 = 0;
+    pmx_config_t cfg_s = *cfg;
+    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, nq * nr);
+    else if (nr > 0) {                            // wrapped sets: the longest sequence of either set, found on the device
+        if (device_maxlens(Q, Q, nullptr, Q->count, &q32, &unused32, st)) return -1;
+        r32 = q32;
+        if (R != Q && device_maxlens(R, R, nullptr, R->count, &r32, &unused32, st)) return -1;
+        if (q32 < 1 || r32 < 1) { q32 = q32 < 1 ? 1 : q32; r32 = r32 < 1 ? 1 : r32; }
+        if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
+    }
+    // a slice's running state (key, record, statistics per kept entry) stays within the bound of the chunk buffers
+    const int64_t ks = std::max<int64_t>(1, std::min<int64_t>(opts->k, nr));
+    const int64_t per_row = ks * (int64_t)(8 + sizeof(pmx_record_t) + (stats ? sizeof(pmx_stats_t) : 0)) + 12;
+    const int64_t slice = std::min<int64_t>(opts->slice_rows > 0 ? opts->slice_rows : std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / per_row), nq);
+    const int64_t cap_buf = slice * ks;
+    pmx_pair_t *dhp = nullptr; int64_t *dhi = nullptr, *doff = nullptr, *dpass = nullptr, *dcnt = nullptr; pmx_record_t *dhr = nullptr; pmx_stats_t *dhs = nullptr;
+    if (scratch_carve(SCR_PTHIT, [&](Carver &c) {
+            dhp = c.take<pmx_pair_t>((size_t)cap_buf); dhi = c.take<int64_t>((size_t)cap_buf); dhr = c.take<pmx_record_t>((size_t)cap_buf);
+            dhs = stats ? c.take<pmx_stats_t>((size_t)cap_buf) : nullptr;
+            doff = c.take<int64_t>((size_t)slice + 1); dpass = c.take<int64_t>((size_t)slice);
+            dcnt = c.take<int64_t>(4);                   // kept, written, passing, first bad pair
+        })) return -1;
+    if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 3, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
+    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi, voff, vpass; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs;
+    try { voff.assign((size_t)nq + 1, 0); vpass.assign((size_t)nq, 0); } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+    int64_t stored = 0, passing = 0;
+    for (int64_t s0 = 0; s0 < nq; s0 += slice) {
+        const int64_t sn = std::min<int64_t>(slice, nq - s0);
+        const TopkOut o = {dhp, dhi, dhr, dhs, sn * ks, doff, dpass, dcnt, host_offsets ? nullptr : dcnt + 3};
+        int64_t h[4] = {0, 0, 0, 0};
+        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, q32, r32, opts->min_score, opts->k, opts->skip_self, o, st, &popts);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipStreamSynchronize(st));
+        if (!host_offsets && h[3] != -1) {
+            set_err("pair %lld (%lld, %lld): bad descriptor (index, window or length)", (long long)(h[3] - q_first * nr), (long long)(h[3] / nr), (long long)(h[3] % nr));
+            return -1;
+        }
+        passing += h[2];
+        const int64_t w = h[1];
+        HIP_OR_RET(hipMemcpy(voff.data() + s0 + 1, doff + 1, sizeof(int64_t) * (size_t)sn, hipMemcpyDeviceToHost));
+        HIP_OR_RET(hipMemcpy(vpass.data() + s0, dpass, sizeof(int64_t) * (size_t)sn, hipMemcpyDeviceToHost));
+        for (int64_t x = 1; x <= sn; ++x) voff[(size_t)(s0 + x)] += stored;
+        if (w > 0) {
+            try { vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w)); }
+            catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+            HIP_OR_RET(hipMemcpy(vp.data() + stored, dhp, sizeof(pmx_pair_t) * (size_t)w, hipMemcpyDeviceToHost));
+            HIP_OR_RET(hipMemcpy(vi.data() + stored, dhi, sizeof(int64_t) * (size_t)w, hipMemcpyDeviceToHost));
+            HIP_OR_RET(hipMemcpy(vr.data() + stored, dhr, sizeof(pmx_record_t) * (size_t)w, hipMemcpyDeviceToHost));
+            if (stats) HIP_OR_RET(hipMemcpy(vs.data() + stored, dhs, sizeof(pmx_stats_t) * (size_t)w, hipMemcpyDeviceToHost));
+            stored += w;
+        }
+    }
+    pmx_topk_hits_t *r = nullptr;
+    if (publish(nq, stored, &r)) return -1;
+    r->n_passing = passing;
+    memcpy(r->row_off, voff.data(), sizeof(int64_t) * (size_t)(nq + 1)); memcpy(r->row_passing, vpass.data(), sizeof(int64_t) * (size_t)nq);
     if (stored) {
         memcpy(r->pairs, vp.data(), sizeof(pmx_pair_t) * (size_t)stored); memcpy(r->index, vi.data(), sizeof(int64_t) * (size_t)stored);
         memcpy(r->recs, vr.data(), sizeof(pmx_record_t) * (size_t)stored);

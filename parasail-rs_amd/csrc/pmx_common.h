@@ -290,6 +290,22 @@ int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts
                                  const pmx_pair_t *pairs, const pmx_record_t *rec, const pmx_stats_t *stats,
                                  pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t stream);
 int pmx_launch_pairs_first_bad(const uint8_t *ok, long long n, long long index0, int64_t *first_bad, hipStream_t stream);
+// Per-query top-K (pmx_topk.hip; semantics: include/parasail_amd.h).  ks = min(k, |R|).  The running state of local row
+// li: st_keys / st_recs / st_stats[li * ks ..) hold st_held[li] entries in (score descending, j ascending) order, st_passing[li] = |P_i|
+// so far; the caller zeroes st_held (nq + 1 entries, the scan's input) and st_passing before the first chunk.  geometry: what the tile
+// buffers of a run with chunks of `chunk` pairs hold -- rows * tps slots of tstride keys (t_keys), one count and one passing count per
+// slot.  merge: a chunk's records [p0, p0 + cn) of the rectangle (p0 absolute) into the lists of its rows; chunks in ascending p0 on
+// one stream.  emit: the lists to row_off[li] + x below `capacity` (row_off: the exclusive scan of st_held), row_passing (optional)
+// and counts[3] = kept, written, passing.
+void pmx_topk_geometry(long long chunk, long long nr, int ks, long long *rows, long long *tps, long long *tstride);
+int pmx_launch_topk_merge(const pmx_record_t *rec, const pmx_stats_t *stats /* may be NULL */, long long p0, long long cn, long long nr, long long q_first,
+                          int ks, int32_t min_score, int skip_self, long long tps, long long tstride,
+                          uint64_t *t_keys, int32_t *t_cnt, int32_t *t_pass,
+                          uint64_t *st_keys, pmx_record_t *st_recs, pmx_stats_t *st_stats, int32_t *st_held, int64_t *st_passing, hipStream_t stream);
+int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, const uint64_t *st_keys, const pmx_record_t *st_recs,
+                         const pmx_stats_t *st_stats, const int32_t *st_held, const int64_t *st_passing, const int64_t *row_off, long long capacity,
+                         pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *row_passing,
+                         int64_t *counts, hipStream_t stream);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);
