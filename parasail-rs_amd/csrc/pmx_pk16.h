@@ -112,6 +112,35 @@ __device__ __forceinline__ int group_shift_up(int x, int neutral, int g)
     return (G == 16 || G == 64) ? r : (g == 0 ? neutral : r);
 }
 
+// The hand-off and the first thing done with it in one DPP VOP2, for the groups whose shift needs no select (interleaved 8,
+// 16, 64): member g gets (x of member g - 1) + y resp. - y.  A lane without a source is not written and keeps `keep`, so the
+// caller preloads what member 0 shall see.  Same control, row and bank masks as group_shift_up.  A DPP instruction must not
+// read a VGPR that one of the two VALU instructions before it wrote; the compiler cannot see into the string, so the two
+// wait states are part of it.  They are spent even where the scheduler happens to put independent instructions in front: the
+// string cannot know its neighbours, so the wait is conservative by design (measured as a gain with it).
+template <int G, bool IL>
+constexpr bool group_shift_fusable = IL || G == 16 || G == 64;
+#define PMX_DPP_VOP2(OP, CTRL) asm("s_nop 1\n\t" OP "_dpp %0, %1, %2 " CTRL " row_mask:0xf bank_mask:0xf" : "+v"(keep) : "v"(x), "v"(y))
+template <int G, bool IL>
+__device__ __forceinline__ int group_shift_up_add(int keep, int x, int y)
+{
+    static_assert(group_shift_fusable<G, IL>, "the other groups need a select behind the move");
+    if constexpr (IL) PMX_DPP_VOP2("v_add_u32", "row_shr:2");
+    else if constexpr (G == 16) PMX_DPP_VOP2("v_add_u32", "row_shr:1");
+    else PMX_DPP_VOP2("v_add_u32", "wave_shr:1");
+    return keep;
+}
+template <int G, bool IL>
+__device__ __forceinline__ int group_shift_up_sub(int keep, int x, int y)
+{
+    static_assert(group_shift_fusable<G, IL>, "the other groups need a select behind the move");
+    if constexpr (IL) PMX_DPP_VOP2("v_sub_u32", "row_shr:2");
+    else if constexpr (G == 16) PMX_DPP_VOP2("v_sub_u32", "row_shr:1");
+    else PMX_DPP_VOP2("v_sub_u32", "wave_shr:1");
+    return keep;
+}
+#undef PMX_DPP_VOP2
+
 // value of lane + 1 (row_shl:1 / wave_shl:1); a lane without a source keeps its own value
 template <int G>
 __device__ __forceinline__ int lane_next(int x)

@@ -48,6 +48,9 @@ __device__ __forceinline__ v2s pk_max(v2s a, v2s b) { return __builtin_elementwi
 #ifndef PMX_SHARE_PERIOD
 #define PMX_SHARE_PERIOD 16     // steps between two exchanges of the group's score bound (a power of two; see share_bound)
 #endif
+#ifndef PMX_SW16_FUSED_HANDOFF
+#define PMX_SW16_FUSED_HANDOFF 1  // 0: the skewed variants hand F and H to the next lane with plain DPP moves, as the other groups do
+#endif
 #define PMX_SW16_RETRY_BLOCKS 1024   // workgroups of a retry launch (launch_one), 4 per CU of a 256-CU chip
 #define FLOOR2 0x80008000   // both halves = -32768 = "zero" of the offset domain
 
@@ -354,6 +357,15 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     const v2s vInitH = V2 ? PK(ZERO2 - I32(vOpen) + skew0) : vZero;
 #pragma unroll
     for (int k = 0; k < R; ++k) { HA[k] = vInitH; E[k] = V2 ? vInitH : (M3 ? PK(0) : vZero); Hsave[k] = vZero; }    // (HB: written by step 0)
+    // FUSED (skewed variants, groups whose shift needs no select): the two hand-offs to the next lane are DPP VOP2 that do row 0's
+    // first operation on the way (group_shift_up_add / _sub in pmx_pk16.h).
+    //   F: row 0's Fe = (Fout of lane g-1) - ext.  Member 0 needs Zv - ext, which is the previous step's Zv: that register is dead
+    //      by then, so it is the destination and nothing has to be preloaded.
+    //   H: row 0's T = (last-row X of lane g-1, two steps back) + s0.  That X still sits in the strip this step is about to
+    //      overwrite (Hnew[R-1]); member 0 needs s0 + (previous Zv - open), one add3.  Step 1 finds the initial strip there,
+    //      which is what lane g-1 hands on at the start; step 0 reads HB, whose last row is set up for it here.
+    constexpr bool FUSED = SK && PMX_SW16_FUSED_HANDOFF && group_shift_fusable<G, IL>;
+    if (FUSED) HB[R - 1] = PK(I32(vInitH) - I32(vExt));      // lane g's first column is one ext below lane g-1's
     v2s best = PK(ZERO2 + skew0 - (SK ? I32(vC) : 0));     // SK: X form
     int bestcol = g * 0x00010001;             // STEP at which the best was first exceeded (column = step - g; initially column 0)
     int vprev = 0, fake = 0;                  // see share_bound
@@ -363,6 +375,9 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     // last-row H (V2: H - open) and outgoing F of the previous step; SK: what lane g+1 reads at step 0
     // belongs to ITS first column -(g+1), one ext below this lane's own column
     int Hout = SK ? Zv0 - I32(vExt) - I32(vOpen) : HNEUTRAL, Fout = SK ? Zv0 - I32(vExt) : ZERO2;
+    int Zprev = Zv0 - I32(vExt);                    // FUSED: Zv of the previous step
+    int extV = I32(vExt);                           // FUSED: a DPP VOP2 takes no scalar operand; opaque, so it stays in its VGPR
+    if (FUSED) asm("" : "+v"(extV));
     v2s diag0 = PK(SK ? I32(vInitH) : HNEUTRAL);   // H(i0-1, j-1)   (V2: minus open)
 
     auto load_scores = [&](int symA, int symB, int (&wa)[RS / WR], int (&wb)[RS / WR]) {
@@ -385,8 +400,9 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     };
     auto step = [&](const v2s (&Hold)[R], v2s (&Hnew)[R], const int (&wa)[RS / WR], const int (&wb)[RS / WR], int t) {
         const int Zv = Zv0 + t * I32(vExt);
-        const int Fin = group_shift_up<G, IL>(Fout, SK ? Zv : ZERO2, g);                  // F(i0, j)
-        v2s F = PK(Fin);
+        v2s F = PK(0), Fe0 = PK(0);
+        if constexpr (FUSED) { Fe0 = PK((group_shift_up_sub<G, IL>(Zprev, Fout, extV))); Zprev = Zv; }    // F~(i0, j)
+        else F = PK((group_shift_up<G, IL>(Fout, SK ? Zv : ZERO2, g)));                                     // F(i0, j)
         v2s colmax = SK ? PK(0) : vZero;
         v2s Hcur[R];                                           // V2 only: this column's H (the strips hold H - open)
         v2s Tpre[R], Epre[R];                                  // V2 only: hoisted independent adds / subtracts
@@ -402,7 +418,11 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
                             : U8 ? PK(__builtin_amdgcn_perm(wb[k / 4], wa[k / 4], 0x0C000C00u | (unsigned)(k & 3) | ((4u + (unsigned)(k & 3)) << 16)))
                                : PK(__builtin_amdgcn_perm(wb[k / 2], wa[k / 2], (k & 1) ? 0x07060302 : 0x05040100));
                 const v2s d = (k == 0) ? diag0 : Hold[k - 1];
-                Tpre[k] = PK(I32(d) + I32(s));
+                if constexpr (FUSED) {
+                    if (k == 0) Tpre[0] = PK((group_shift_up_add<G, IL>(I32(s) + (Zv - I32(vExt) - I32(vOpen)), I32(Hnew[R - 1]), I32(s))));
+                    else Tpre[k] = PK(I32(d) + I32(s));
+                } else
+                    Tpre[k] = PK(I32(d) + I32(s));
                 if (!SK) Epre[k] = PK(I32(E[k]) - I32(vExt));
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -415,7 +435,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             const v2s d = (k == 0) ? diag0 : Hold[k - 1];
             v2s H;
             if (SK) {
-                const v2s Fe = PK(I32(F) - I32(vExt));            // F~ of this row (F^ - ext), also F^'s extension
+                const v2s Fe = (FUSED && k == 0) ? Fe0 : PK(I32(F) - I32(vExt));   // F~ of this row (F^ - ext), also F^'s extension
                 H = pk_max3(Tpre[k], E[k], Fe);
                 const v2s X = PK(I32(H) - I32(vC));
                 if (TR) {
@@ -474,9 +494,11 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
             *reinterpret_cast<uint4 *>(tw + (size_t)t * t_ss) = w;
         }
         // H(i0-1, j), the next step's diagonal source: taken from lane g-1's previous step only here, where it is first needed
-        const int Hin = group_shift_up<G, IL>(Hout, SK ? Zv - I32(vOpen) : HNEUTRAL, g);
-        diag0 = PK(Hin);
-        Hout = I32(Hnew[R - 1]);
+        if constexpr (!FUSED) {
+            const int Hin = group_shift_up<G, IL>(Hout, SK ? Zv - I32(vOpen) : HNEUTRAL, g);
+            diag0 = PK(Hin);
+            Hout = I32(Hnew[R - 1]);
+        }
         Fout = I32(F);
         // end-position bookkeeping: strictly greater than the lane's best so far?
         constexpr bool FOLDED = SK && (R & 1);          // colmax already holds max(best, column maximum)
