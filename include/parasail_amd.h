@@ -643,6 +643,77 @@ int  pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_s
                      const pmx_topk_opts_t *opts, pmx_topk_hits_t **result);
 void pmx_topk_hits_free(pmx_topk_hits_t *hits);
 
+/* Both strands (extension): the set entries for DNA whose orientation is unknown.  Every pair is aligned on the forward and on the
+ * reverse strand inside its chunk and the two records become one BEFORE selection, so hits, counts, top-K cuts and device memory
+ * are per pair, not per (pair, strand).
+ *
+ * Semantics, through pmx_align_pairs_ex_device.  Let rec0(k) / stats0(k) be what it writes for descriptor k with strand byte 0 and
+ * rec1(k) / stats1(k) with strand byte 1 (for the enumerated shapes descriptor k is the one the enumerator generates).  The folded
+ * record of PMX_STRAND_BOTH is the winner's record BYTE FOR BYTE, flags included, its statistics are the winner's and its strand byte
+ * says which one won.  Only the score is compared (the rule of pmx_select_hits_device).  All positions of a strand-1 winner are relative
+ * to the reverse-complemented window, exactly as the _ex entries document; pmx_complement_table is applied to the raw bytes whatever
+ * the matrix.  A bad descriptor is bad on both strands: {0, -1, -1, PMX_FLAG_BAD_PAIR}, zero statistics, strand byte 0 (in every mode).
+ * Selection (min_score, max_hits, capacity) and the top-K order work on the FOLDED records; the top-K order stays (score descending,
+ * reference index ascending), the strand is not part of the key: a pair is one candidate and a reference appears at most once in a
+ * row.  Outputs are bit-identical from run to run; chunk_pairs, slice_pairs and slice_rows count LOGICAL pairs or rows and never
+ * change a byte.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: a strand mode outside 0 .. 2; a mode other than PMX_STRAND_FORWARD
+ * with a PSSM matrix (a reversed query has no PSSM); everything the corresponding entry without strands refuses, with the same texts.
+ * n == 0 / nq == 0 behave as there.
+ *
+ * Scratch.  PMX_STRAND_BOTH keeps two alignment slots per logical pair -- slot 2 k is pair k as stored, slot 2 k + 1 pair k with its
+ * query window reverse-complemented -- in the chunk buffers of pmx_align_pairs_device, so the default chunk, derived from the 256 MiB
+ * bound, is half as many logical pairs; beside them per pair of a chunk 2 x 16 bytes of slot records, 2 x 12 of slot statistics
+ * (PMX_WANT_STATS), one validity byte and 2 strand bytes.  PMX_STRAND_REVERSE has one slot per pair.  PMX_STRAND_FORWARD launches
+ * exactly what the entries without strands launch.  pmx_last_kernel() names what the last chunk's alignment ran. */
+#define PMX_STRAND_FORWARD 0   /* rec0, strand byte 0 */
+#define PMX_STRAND_REVERSE 1   /* rec1, strand byte 1 */
+#define PMX_STRAND_BOTH    2   /* rec1 if rec1.score > rec0.score, else rec0: the higher score, a tie goes to the forward strand */
+/* Listed pairs, always PMX_STRAND_BOTH: the arguments of pmx_align_pairs[_device] and strand_out / d_strand_out, n bytes, required.
+ * PMX_WANT_CIGAR is refused: the CIGAR pass is pmx_align_pairs_ex[_device] with the returned strand bytes.  The device entry gives bad
+ * pairs their record and strand 0; the host entry refuses them as pmx_align_pairs does. */
+int pmx_align_pairs_both_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                int64_t n, const pmx_pair_t *d_pairs, int32_t max_qlen, int32_t max_rlen,
+                                pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_strand_out /* n bytes */, void *stream,
+                                const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_both(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                         int64_t n, const pmx_pair_t *pairs,
+                         pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */, uint8_t *strand_out /* n bytes */,
+                         const pmx_pairs_opts_t *opts);
+/* Set search with a strand mode: the argument list of pmx_search_pairs_device, then strand_mode and d_hit_strand (optional: one byte
+ * per written hit, parallel to d_hit_recs).  With PMX_STRAND_FORWARD every output is byte-identical to pmx_search_pairs_device's and
+ * the strand bytes are 0; with PMX_STRAND_REVERSE it is byte-identical to pmx_search_pairs_device over a query set whose sequences
+ * were reverse-complemented (whole-sequence shapes), strand bytes 1.  The CIGAR pass over the hits needs nothing new:
+ * pmx_align_pairs_ex_device(..., n = d_counts[1], d_hit_pairs, d_hit_strand, ...).  The host result is a pmx_strand_hits_t: the fields
+ * of pmx_pair_hits_t followed by the strand bytes (n_hits of them), one block released with pmx_strand_hits_free. */
+int pmx_search_pairs_stranded_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                     int64_t first, int64_t n, const pmx_pair_t *d_pairs /* LIST only, else NULL */,
+                                     int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                     pmx_pair_t *d_hit_pairs /* optional */, int64_t *d_hit_index /* optional */,
+                                     pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats /* iff PMX_WANT_STATS */, int64_t capacity,
+                                     int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                     int strand_mode, uint8_t *d_hit_strand /* optional */);
+typedef struct pmx_strand_hits { int64_t n_hits, n_passing; pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; uint8_t *strand; } pmx_strand_hits_t;
+int  pmx_search_pairs_stranded(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                               const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, pmx_strand_hits_t **result);
+void pmx_strand_hits_free(pmx_strand_hits_t *hits);
+/* Per-query top-K with a strand mode: the argument list of pmx_search_topk_device, then strand_mode and d_hit_strand (optional, one
+ * byte per written hit).  skip_self is unchanged: (i, i) is never a candidate, on either strand.  PMX_STRAND_FORWARD is byte-identical
+ * to pmx_search_topk_device.  The hit pairs and strand bytes feed pmx_align_pairs_ex_device as above.  The host result is a
+ * pmx_topk_strand_hits_t: the fields of pmx_topk_hits_t followed by the strand bytes, released with pmx_topk_strand_hits_free. */
+int pmx_search_topk_stranded_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                    int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                    pmx_pair_t *d_hit_pairs /* optional */, int64_t *d_hit_index /* optional */,
+                                    pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats /* iff PMX_WANT_STATS */, int64_t capacity,
+                                    int64_t *d_row_off /* nq + 1 */, int64_t *d_row_passing /* nq, optional */,
+                                    int64_t *d_counts /* [0] kept, [1] written, [2] passing */, void *stream, const pmx_pairs_opts_t *opts,
+                                    int strand_mode, uint8_t *d_hit_strand /* optional */);
+typedef struct pmx_topk_strand_hits { int64_t n_rows, n_hits, n_passing; int64_t *row_off, *row_passing; pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; uint8_t *strand; } pmx_topk_strand_hits_t;
+int  pmx_search_topk_stranded(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                              const pmx_topk_opts_t *opts, int strand_mode, pmx_topk_strand_hits_t **result);
+void pmx_topk_strand_hits_free(pmx_topk_strand_hits_t *hits);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -106,6 +106,14 @@ class pmx_topk_hits_t(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class pmx_strand_hits_t(C.Structure):
+    _fields_ = pmx_pair_hits_t._fields_ + [("strand", C.c_void_p)]
+
+
+class pmx_topk_strand_hits_t(C.Structure):
+    _fields_ = pmx_topk_hits_t._fields_ + [("strand", C.c_void_p)]
+
+
 TOPK_MAX = 1024
 INT32_MIN = -(1 << 31)
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
@@ -115,6 +123,7 @@ HIT_DTYPE = np.dtype([("index", "<i8"), ("first", RECORD_DTYPE), ("diag", "<i4")
 HITS_BY_INDEX, HITS_BY_SCORE = 0, 1
 PAIR_DTYPE = np.dtype([("q", "<i8"), ("r", "<i8"), ("q_beg", "<i4"), ("q_len", "<i4"), ("r_beg", "<i4"), ("r_len", "<i4")])
 PAIRS_LIST, PAIRS_TRIANGLE, PAIRS_RECT = 0, 1, 2
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
 
 MODE_NW, MODE_SG, MODE_SW = 0, 1, 2
 SG_QB, SG_QE, SG_DB, SG_DE, SG_ALL = 1, 2, 4, 8, 15
@@ -261,6 +270,22 @@ _sig("pmx_search_topk_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c
 _sig("pmx_search_topk", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.POINTER(C.POINTER(pmx_topk_hits_t)))
 _sig("pmx_topk_hits_free", None, C.POINTER(pmx_topk_hits_t))
+_sig("pmx_align_pairs_both", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_both_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_search_pairs_stranded_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p)
+_sig("pmx_search_pairs_stranded", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+     C.POINTER(pmx_pair_search_opts_t), C.c_int, C.POINTER(C.POINTER(pmx_strand_hits_t)))
+_sig("pmx_strand_hits_free", None, C.POINTER(pmx_strand_hits_t))
+_sig("pmx_search_topk_stranded_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p)
+_sig("pmx_search_topk_stranded", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+     C.POINTER(pmx_topk_opts_t), C.c_int, C.POINTER(C.POINTER(pmx_topk_strand_hits_t)))
+_sig("pmx_topk_strand_hits_free", None, C.POINTER(pmx_topk_strand_hits_t))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -891,7 +916,9 @@ class Aligner:
         of the pair (query window, reference window) k, end positions relative to the windows.  A bad descriptor raises BatchError
         naming the first.  `strand`: one byte per pair, 1 = the query window reverse-complemented (complement_table(); every
         position of such a pair is relative to the reverse-complemented window).  cigar=True returns (records, CIGAR strings,
-        int32 [n, 2] begins of the paths) instead."""
+        int32 [n, 2] begins of the paths) instead.  strand="both": every pair on both strands, the better one kept (a tie: the
+        forward strand) -- (records, strand) or (records, stats, strand), strand a uint8 array saying which one won; with
+        cigar=True the CIGARs of the winners, (records, cigars, begins, strand)."""
         if not self._profile.is_null():
             raise BatchError("align_pairs takes no profile")
         pairs = as_pairs(pairs)
@@ -900,6 +927,20 @@ class Aligner:
         out = np.zeros(n, dtype=RECORD_DTYPE)
         stats = np.zeros(n, dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
         opts = pmx_pairs_opts_t(int(chunk_pairs))
+        if isinstance(strand, str):
+            if strand != "both":
+                raise BatchError("strand is a byte per pair or \"both\"")
+            won = np.zeros(n, dtype=np.uint8)
+            if cigar:                                   # the fold needs scores only; the CIGAR pass runs the winners' strands
+                cfg.want &= ~WANT_STATS
+                stats = None
+            rc = lib.pmx_align_pairs_both(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, out.ctypes.data,
+                                          stats.ctypes.data if stats is not None else None, won.ctypes.data, C.byref(opts))
+            if rc:
+                raise BatchError(lib.pmx_last_error().decode())
+            if cigar:
+                return self.align_pairs(Q, R, pairs, chunk_pairs=chunk_pairs, strand=won, cigar=True) + (won,)
+            return (out, stats, won) if stats is not None else (out, won)
         if strand is None and not cigar:
             rc = lib.pmx_align_pairs(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, out.ctypes.data,
                                      stats.ctypes.data if stats is not None else None, C.byref(opts))
@@ -945,13 +986,14 @@ class Aligner:
         return (out, stats) if stats is not None else out
 
     def search_pairs(self, Q, R=None, min_score=0, pairs=None, first=0, count=None, stats=False, max_hits=0, chunk_pairs=0,
-                     slice_pairs=0):
+                     slice_pairs=0, strand=0):
         """Set search: the pairs of an enumeration that score at least min_score, as a PairHits in enumeration order.  `pairs`
         given: those descriptors of Q x R (as align_pairs takes them; R None: Q); else R None: pairs [first, first + count) of the
         strict upper triangle of Q (the numbering of align_all_pairs); else the same window of the rectangle Q x R, row-major
         (pair p = (p // len(R), p % len(R)); R may be Q, the diagonal included).  count None: to the last pair.  stats=True adds the
         hits' statistics.  max_hits > 0 keeps the first max_hits hits and goes on counting n_passing.  Only the hits leave the
-        device; chunk_pairs and slice_pairs never change the result."""
+        device; chunk_pairs and slice_pairs never change the result.  strand: 0 the queries as stored, 1 reverse-complemented,
+        "both" (or STRAND_BOTH) the better strand of every pair, chosen before the threshold; PairHits.strand tells which."""
         if not self._profile.is_null():
             raise BatchError("search_pairs takes no profile")
         cfg = self._config()
@@ -970,6 +1012,18 @@ class Aligner:
             if count is None:
                 count = rect_pairs_count(len(Q), len(R)) - int(first)
         opts = pmx_pair_search_opts_t(int(min_score), shape, int(max_hits), int(chunk_pairs), int(slice_pairs))
+        mode = _strand_mode(strand)
+        if mode != STRAND_FORWARD:
+            res = C.POINTER(pmx_strand_hits_t)()
+            rc = lib.pmx_search_pairs_stranded(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
+                                               pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts), mode,
+                                               C.byref(res))
+            if rc:
+                raise BatchError(lib.pmx_last_error().decode())
+            try:
+                return PairHits(res.contents)
+            finally:
+                lib.pmx_strand_hits_free(res)
         res = C.POINTER(pmx_pair_hits_t)()
         rc = lib.pmx_search_pairs(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
                                   pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts), C.byref(res))
@@ -981,11 +1035,12 @@ class Aligner:
             lib.pmx_pair_hits_free(res)
 
     def search_topk(self, Q, R=None, k=10, min_score=INT32_MIN, skip_self=False, first_row=0, rows=None, stats=False, chunk_pairs=0,
-                    slice_rows=0):
+                    slice_rows=0, strand=0):
         """Per-query top-K: for each query row [first_row, first_row + rows) of Q the best k references of R (None: Q) with score
         >= min_score, in (score descending, reference index ascending) order, as a TopKHits.  rows None: to the last row.
         skip_self (R is Q) leaves the pair (i, i) out.  stats=True adds the hits' statistics.  Only the hits leave the device;
-        chunk_pairs and slice_rows never change the result."""
+        chunk_pairs and slice_rows never change the result.  strand as in search_pairs: with "both" a reference is one
+        candidate with its better strand, and TopKHits.strand tells which."""
         if not self._profile.is_null():
             raise BatchError("search_topk takes no profile")
         cfg = self._config()
@@ -994,6 +1049,17 @@ class Aligner:
         if rows is None:
             rows = len(Q) - int(first_row)
         opts = pmx_topk_opts_t(int(min_score), int(k), 1 if skip_self else 0, int(chunk_pairs), int(slice_rows))
+        mode = _strand_mode(strand)
+        if mode != STRAND_FORWARD:
+            res = C.POINTER(pmx_topk_strand_hits_t)()
+            rc = lib.pmx_search_topk_stranded(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows),
+                                              C.byref(opts), mode, C.byref(res))
+            if rc:
+                raise BatchError(lib.pmx_last_error().decode())
+            try:
+                return TopKHits(res.contents)
+            finally:
+                lib.pmx_topk_strand_hits_free(res)
         res = C.POINTER(pmx_topk_hits_t)()
         rc = lib.pmx_search_topk(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows),
                                  C.byref(opts), C.byref(res))
@@ -1196,10 +1262,21 @@ class SearchHits:
         return self.n_hits
 
 
+def _strand_mode(strand):
+    """0 / 1 / 2 or "forward" / "reverse" / "both" -> STRAND_*."""
+    names = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
+    if isinstance(strand, str):
+        if strand not in names:
+            raise BatchError("strand is 0, 1 or \"both\"")
+        return names[strand]
+    return int(strand)
+
+
 class PairHits:
     """Result of Aligner.search_pairs: n_hits, n_passing (all pairs at or above min_score, stored or not) and, per hit in
     enumeration order, pairs (PAIR_DTYPE: the descriptor, fit for align_pairs), index (int64: the pair's number in the
-    enumeration), records (RECORD_DTYPE) and stats (STATS_DTYPE, or None when not asked for)."""
+    enumeration), records (RECORD_DTYPE), stats (STATS_DTYPE, or None when not asked for) and strand (uint8: the strand of the
+    record, all 0 for a forward search)."""
 
     def __init__(self, r):
         h = int(r.n_hits)
@@ -1213,6 +1290,7 @@ class PairHits:
         self.index = take(r.index, np.int64)
         self.records = take(r.recs, RECORD_DTYPE)
         self.stats = take(r.stats, STATS_DTYPE) if r.stats else None
+        self.strand = take(getattr(r, "strand", None), np.uint8)
 
     def __len__(self):
         return self.n_hits
@@ -1222,7 +1300,8 @@ class TopKHits:
     """Result of Aligner.search_topk, CSR by query row: row_off (int64, n_rows + 1), row_passing (int64: the references at or above
     min_score per row, kept or not), n_passing (their sum) and, per hit, pairs (PAIR_DTYPE: the descriptor, fit for align_pairs),
     index (int64: p = i * len(R) + j), records (RECORD_DTYPE) and stats (STATS_DTYPE, or None when not asked for).  A row's hits
-    are in (score descending, reference index ascending) order; row(i) slices them out."""
+    are in (score descending, reference index ascending) order; row(i) slices them out.  strand (uint8 per hit): the strand of the
+    record, all 0 for a forward search."""
 
     def __init__(self, r):
         h, n = int(r.n_hits), int(r.n_rows)
@@ -1238,6 +1317,7 @@ class TopKHits:
         self.index = take(r.index, h, np.int64)
         self.records = take(r.recs, h, RECORD_DTYPE)
         self.stats = take(r.stats, h, STATS_DTYPE) if r.stats else None
+        self.strand = take(getattr(r, "strand", None), h, np.uint8)
 
     def __len__(self):
         return self.n_hits
@@ -1458,6 +1538,42 @@ def search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k,
     rc = lib.pmx_search_topk_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
                                     max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
                                     d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_both_device(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats, d_strand_out, stream=0, chunk_pairs=0):
+    """align_pairs_device on both strands: record k (and its statistics) is the better strand's, byte for byte, a tie going to the
+    forward strand; d_strand_out (n bytes) says which one won."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_align_pairs_both_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, max_qlen, max_rlen, d_out, d_stats,
+                                         d_strand_out, stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_pairs_stranded_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs,
+                                 d_hit_stats, capacity, d_counts, strand_mode, d_hit_strand=None, stream=0, chunk_pairs=0):
+    """search_pairs_device with a strand mode (STRAND_*): the threshold looks at the folded records; d_hit_strand (optional, one byte
+    per hit) receives the hits' strands.  d_hit_pairs and d_hit_strand feed align_pairs_ex_device unchanged."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_search_pairs_stranded_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(shape), int(first),
+                                              int(n), d_pairs, max_qlen, max_rlen, int(min_score), d_hit_pairs, d_hit_index, d_hit_recs,
+                                              d_hit_stats, int(capacity), d_counts, stream, C.byref(opts), int(strand_mode), d_hit_strand)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_topk_stranded_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs,
+                                d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, strand_mode, d_hit_strand=None, stream=0,
+                                chunk_pairs=0):
+    """search_topk_device with a strand mode (STRAND_*): a reference is one candidate with its folded record; d_hit_strand
+    (optional, one byte per hit) receives the hits' strands."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    rc = lib.pmx_search_topk_stranded_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
+                                             max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
+                                             d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream,
+                                             C.byref(opts), int(strand_mode), d_hit_strand)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

@@ -681,6 +681,7 @@ public:
         std::vector<int64_t> index;
         std::vector<pmx_record_t> recs;
         std::vector<pmx_stats_t> stats;
+        std::vector<uint8_t> strand;          // the strand of every record: all 0 from search_pairs, the winner's from search_pairs_stranded
     };
     PairHits search_pairs(const SeqSet &Q, const SeqSet *R, int shape, int32_t min_score, const std::vector<pmx_pair_t> *pairs = nullptr,
                           int64_t first = 0, int64_t count = -1, int64_t max_hits = 0, int64_t chunk_pairs = 0, int64_t slice_pairs = 0) const
@@ -706,7 +707,40 @@ public:
         out.index.assign(res->index, res->index + h);
         out.recs.assign(res->recs, res->recs + h);
         if (res->stats) out.stats.assign(res->stats, res->stats + h);
+        out.strand.assign(h, 0);
         pmx_pair_hits_free(res);
+        return out;
+    }
+    // the same with a strand mode (pmx_search_pairs_stranded): PMX_STRAND_FORWARD, PMX_STRAND_REVERSE (every query reverse-complemented)
+    // or PMX_STRAND_BOTH -- every pair on both strands, the better record kept (a tie: the forward strand) BEFORE the threshold, so a
+    // pair is one hit at most; strand[x] tells which strand hit x is on.  pairs and strand feed align_pairs_cigar unchanged.
+    PairHits search_pairs_stranded(const SeqSet &Q, const SeqSet *R, int shape, int32_t min_score, int strand_mode,
+                                   const std::vector<pmx_pair_t> *pairs = nullptr, int64_t first = 0, int64_t count = -1, int64_t max_hits = 0,
+                                   int64_t chunk_pairs = 0, int64_t slice_pairs = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "search_pairs takes no profile");
+        if (shape == PMX_PAIRS_LIST) { if (!pairs) throw Error(ErrorKind::Batch, "PMX_PAIRS_LIST needs pairs"); first = 0; count = (int64_t)pairs->size(); }
+        else if (count < 0) {
+            const int64_t total = shape == PMX_PAIRS_TRIANGLE ? all_pairs_count(Q.len()) : pmx_rect_pairs_count(Q.len(), R ? R->len() : -1);
+            if (total < 0) throw Error(ErrorKind::Batch, pmx_last_error());
+            count = total - first;
+        }
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        const pmx_pair_search_opts_t opts = {min_score, shape, max_hits, chunk_pairs, slice_pairs};
+        pmx_strand_hits_t *res = nullptr;
+        const int rc = pmx_search_pairs_stranded(&cfg, Q.inner, R ? R->inner : nullptr, first, count,
+                                                 shape == PMX_PAIRS_LIST && !pairs->empty() ? pairs->data() : nullptr, &opts, strand_mode, &res);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        PairHits out;
+        const size_t h = (size_t)res->n_hits;
+        out.n_passing = res->n_passing;
+        out.pairs.assign(res->pairs, res->pairs + h);
+        out.index.assign(res->index, res->index + h);
+        out.recs.assign(res->recs, res->recs + h);
+        if (res->stats) out.stats.assign(res->stats, res->stats + h);
+        out.strand.assign(res->strand, res->strand + h);
+        pmx_strand_hits_free(res);
         return out;
     }
 
@@ -721,6 +755,7 @@ public:
         std::vector<int64_t> index;
         std::vector<pmx_record_t> recs;
         std::vector<pmx_stats_t> stats;
+        std::vector<uint8_t> strand;          // as in PairHits
     };
     TopKHits search_topk(const SeqSet &Q, const SeqSet *R, int32_t k, int32_t min_score = INT32_MIN, bool skip_self = false,
                          int64_t first_row = 0, int64_t rows = -1, int64_t chunk_pairs = 0, int64_t slice_rows = 0) const
@@ -742,7 +777,34 @@ public:
         out.index.assign(res->index, res->index + h);
         out.recs.assign(res->recs, res->recs + h);
         if (res->stats) out.stats.assign(res->stats, res->stats + h);
+        out.strand.assign(h, 0);
         pmx_topk_hits_free(res);
+        return out;
+    }
+    // the same with a strand mode (pmx_search_topk_stranded): with PMX_STRAND_BOTH a reference is ONE candidate of its row, with the
+    // better of its two records; the order stays (score descending, reference index ascending) and strand[x] tells the hit's strand.
+    TopKHits search_topk_stranded(const SeqSet &Q, const SeqSet *R, int32_t k, int strand_mode, int32_t min_score = INT32_MIN, bool skip_self = false,
+                                  int64_t first_row = 0, int64_t rows = -1, int64_t chunk_pairs = 0, int64_t slice_rows = 0) const
+    {
+        if (profile_ && !profile_->is_null()) throw Error(ErrorKind::Batch, "search_topk takes no profile");
+        if (rows < 0) rows = Q.len() - first_row;
+        pmx_config_t cfg = config_;
+        cfg.matrix = matrix->inner;
+        const pmx_topk_opts_t opts = {min_score, k, skip_self ? 1 : 0, chunk_pairs, slice_rows};
+        pmx_topk_strand_hits_t *res = nullptr;
+        const int rc = pmx_search_topk_stranded(&cfg, Q.inner, R ? R->inner : nullptr, first_row, rows, &opts, strand_mode, &res);
+        if (rc) throw Error(ErrorKind::Batch, pmx_last_error());
+        TopKHits out;
+        const size_t h = (size_t)res->n_hits, n = (size_t)res->n_rows;
+        out.n_passing = res->n_passing;
+        out.row_off.assign(res->row_off, res->row_off + n + 1);
+        out.row_passing.assign(res->row_passing, res->row_passing + n);
+        out.pairs.assign(res->pairs, res->pairs + h);
+        out.index.assign(res->index, res->index + h);
+        out.recs.assign(res->recs, res->recs + h);
+        if (res->stats) out.stats.assign(res->stats, res->stats + h);
+        out.strand.assign(res->strand, res->strand + h);
+        pmx_topk_strand_hits_free(res);
         return out;
     }
 

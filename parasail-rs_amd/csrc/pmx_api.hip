@@ -3696,10 +3696,11 @@ static int pairs_ws_init()
 // 3.09, 3.09 and 3.13 ms -- the six launches a chunk adds cost more than the overlap returns, so chunks are as large as the scratch
 // allows, and 2 x 256 MiB is small beside the HBM of the cards this runs on.
 static const double PMX_PAIRS_CHUNK_BYTES = 256.0 * 1024 * 1024;
-static int64_t pairs_chunk(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_pairs_opts_t *opts)
+// per: alignment slots per logical pair (2 in PMX_STRAND_BOTH, where the buffers hold every pair twice: half as many pairs by default).
+static int64_t pairs_chunk(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_pairs_opts_t *opts, int per = 1)
 {
     if (opts && opts->chunk_pairs > 0) return opts->chunk_pairs < n ? opts->chunk_pairs : n;
-    int64_t chunk = (int64_t)(PMX_PAIRS_CHUNK_BYTES / ((double)max_qlen + (double)max_rlen + 16.0));
+    int64_t chunk = (int64_t)(PMX_PAIRS_CHUNK_BYTES / ((double)per * ((double)max_qlen + (double)max_rlen + 16.0)));
     if (chunk < 1) chunk = 1;
     if (chunk >= n) return n;
     const int64_t nchunks = (n + chunk - 1) / chunk;
@@ -3733,23 +3734,30 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 // rectangle Q x R, generated per chunk; the body finds the chunk's descriptors, listed or generated, in PairsChunkBufs::pairs.
 // d_strand != nullptr (the _ex entries): the resolve step takes the strand bytes and the gather is the one that can reverse-complement;
 // otherwise the forward-only kernels run, and a forward batch pays nothing for the strands' existence.
+// strand_mode PMX_STRAND_REVERSE / PMX_STRAND_BOTH (the entries that choose the strand themselves; d_strand is then nullptr):
+// a chunk of cn pairs is per = 1 / 2 alignment slots per pair -- BOTH: slot 2 k is pair k as stored, slot 2 k + 1 pair k with its query
+// reverse-complemented -- and the buffers hold per * cn windows; the body still gets c0 and cn in logical pairs.
+static int strand_slots(int strand_mode) { return strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
 struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; };
 template <typename Body>
 static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first, int shape,
-                     const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body)
+                     const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body,
+                     int strand_mode = PMX_STRAND_FORWARD)
 {
-    const bool two = chunk < n, stranded = d_strand != nullptr;
+    const bool two = chunk < n, chosen = strand_mode != PMX_STRAND_FORWARD, stranded = d_strand != nullptr || chosen;
+    const int per = strand_slots(strand_mode);
+    const size_t slots = (size_t)chunk * (size_t)per;
     PairsChunkBufs B[2]; void *scan = nullptr; pmx_pair_t *gen = nullptr;
-    const size_t scan_bytes = pmx_text_scan_scratch_bytes(chunk);
+    const size_t scan_bytes = pmx_text_scan_scratch_bytes((int64_t)slots);
     if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
             for (int s = 0; s < (two ? 2 : 1); ++s) {
-                B[s].q = c.take<uint8_t>((size_t)chunk * (size_t)max_qlen + 16);      // (the slack of the host entries' staged copies)
-                B[s].r = c.take<uint8_t>((size_t)chunk * (size_t)max_rlen + 16);
-                B[s].qlen = c.take<int32_t>((size_t)chunk + 2); B[s].rlen = c.take<int32_t>((size_t)chunk + 2);
-                B[s].qoff = c.take<int64_t>((size_t)chunk + 1); B[s].roff = c.take<int64_t>((size_t)chunk + 1);
-                B[s].qsrc = c.take<int64_t>((size_t)chunk); B[s].rsrc = c.take<int64_t>((size_t)chunk);
-                B[s].ok = c.take<uint8_t>((size_t)chunk);
-                B[s].sflag = stranded ? c.take<uint8_t>((size_t)chunk) : nullptr;
+                B[s].q = c.take<uint8_t>(slots * (size_t)max_qlen + 16);      // (the slack of the host entries' staged copies)
+                B[s].r = c.take<uint8_t>(slots * (size_t)max_rlen + 16);
+                B[s].qlen = c.take<int32_t>(slots + 2); B[s].rlen = c.take<int32_t>(slots + 2);
+                B[s].qoff = c.take<int64_t>(slots + 1); B[s].roff = c.take<int64_t>(slots + 1);
+                B[s].qsrc = c.take<int64_t>(slots); B[s].rsrc = c.take<int64_t>(slots);
+                B[s].ok = c.take<uint8_t>(slots);
+                B[s].sflag = stranded ? c.take<uint8_t>(slots) : nullptr;
             }
             scan = c.take<unsigned char>(scan_bytes);           // (one: the scans of all chunks run in order on one stream)
         })) return -1;
@@ -3769,14 +3777,17 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         const PairsChunkBufs &b = B[slot];
         int rc = listed ? 0 : shape == PMX_PAIRS_TRIANGLE ? pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gc, prep)
                                                           : pmx_launch_rect_pairs_enumerate(R->count, first + c0, cn, gc, prep);
-        if (!rc) rc = stranded ? pmx_launch_pairs_resolve_stranded(pc, d_strand + c0, cn, Q->d_off, Q->count, Q->bytes,
+        const int64_t sn = cn * per;                              // the chunk's alignment slots
+        if (!rc) rc = chosen   ? pmx_launch_pairs_resolve_both(pc, cn, per, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                                               b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
+                    : stranded ? pmx_launch_pairs_resolve_stranded(pc, d_strand + c0, cn, Q->d_off, Q->count, Q->bytes,
                                                                    R->d_off, R->count, R->bytes, max_qlen, max_rlen,
                                                                    b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
                                : pmx_launch_pairs_resolve(pc, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
                                                           b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
-        if (!rc) rc = pmx_launch_text_offsets(b.qlen, cn, b.qoff, scan, scan_bytes, prep);
-        if (!rc) rc = pmx_launch_text_offsets(b.rlen, cn, b.roff, scan, scan_bytes, prep);
-        if (!rc) rc = stranded ? pmx_launch_pairs_gather_stranded(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
+        if (!rc) rc = pmx_launch_text_offsets(b.qlen, sn, b.qoff, scan, scan_bytes, prep);
+        if (!rc) rc = pmx_launch_text_offsets(b.rlen, sn, b.roff, scan, scan_bytes, prep);
+        if (!rc) rc = stranded ? pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
                                                                   b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, prep)
                                : pmx_launch_pairs_gather(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
                                                          b.qoff, b.roff, b.q, b.r, prep);
@@ -3833,6 +3844,68 @@ extern "C" int pmx_align_pairs_device(const pmx_config_t *cfg, const pmx_seqset_
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     return pairs_run_scores(cfg, Q, R, n, d_pairs, 0, nullptr, max_qlen, max_rlen, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts));
+}
+
+// ---- the strand chosen by the entry ----
+// What every entry with a strand mode refuses about it, before any GPU work.
+static int strand_mode_check(const pmx_config_t *cfg, int strand_mode)
+{
+    if (strand_mode < PMX_STRAND_FORWARD || strand_mode > PMX_STRAND_BOTH) {
+        set_err("strand mode %d is outside 0 .. 2 (PMX_STRAND_FORWARD, PMX_STRAND_REVERSE, PMX_STRAND_BOTH)", strand_mode); return -1;
+    }
+    if (strand_mode != PMX_STRAND_FORWARD && cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {
+        set_err("a strand mode other than PMX_STRAND_FORWARD takes no PSSM matrix: a reversed query has no PSSM"); return -1;
+    }
+    return 0;
+}
+static int pairs_both_want_check(const pmx_config_t *cfg)
+{
+    if (cfg->want & PMX_WANT_CIGAR) {
+        set_err("pmx_align_pairs_both[_device] has no CIGAR output: pass the returned strand bytes to pmx_align_pairs_ex[_device] with PMX_WANT_CIGAR");
+        return -1;
+    }
+    return 0;
+}
+
+// The score road in PMX_STRAND_BOTH: every chunk's 2 cn slots through run_batch_device into scratch, then the fold straight into the
+// caller's arrays (it writes the bad pairs' records too).
+static int pairs_run_both(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
+                          int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_strand_out,
+                          hipStream_t st, int64_t chunk)
+{
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    pmx_record_t *srec = nullptr; pmx_stats_t *sst = nullptr;
+    if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
+            srec = c.take<pmx_record_t>(2 * (size_t)chunk);
+            sst = stats ? c.take<pmx_stats_t>(2 * (size_t)chunk) : nullptr;
+        })) return -1;
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            int rc = run_batch_device(cfg, 2 * cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, srec, sst, st);
+            if (rc) return rc;
+            rc = pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, 2, 0, d_out + c0, stats ? d_stats_out + c0 : nullptr, d_strand_out + c0, nullptr, st);
+            if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
+            return 0;
+        }, PMX_STRAND_BOTH);
+}
+
+extern "C" int pmx_align_pairs_both_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                           int64_t n, const pmx_pair_t *d_pairs, int32_t max_qlen, int32_t max_rlen,
+                                           pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_strand_out, void *stream,
+                                           const pmx_pairs_opts_t *opts)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
+    if (n > 0 && !d_strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || pairs_both_want_check(cfg) || strand_mode_check(cfg, PMX_STRAND_BOTH)) return -1;
+    if (n == 0) return 0;
+    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run_both(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats_out, d_strand_out, (hipStream_t)stream,
+                          pairs_chunk(n, max_qlen, max_rlen, opts, 2));
 }
 
 // ---- strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device) ----
@@ -4034,14 +4107,19 @@ static int pairs_copy_back(int64_t n, const pmx_record_t *drec, const pmx_stats_
 // The host entries over listed pairs.  ex: pmx_align_pairs_ex -- strand bytes (may be NULL), and with PMX_WANT_CIGAR the begins (may be
 // NULL) and the text, which follows traced_host_batch: a device buffer of half a byte per symbol + 16 per pair, one more run at the exact
 // size when the text did not fit, a block for the caller released with pmx_free.
+// both: pmx_align_pairs_both -- PMX_STRAND_BOTH, the winners' strand bytes into strand_out (n more bytes of scratch, copied back
+// behind the records).
 static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *pairs, const uint8_t *strand,
-                      pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts, bool ex)
+                      pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts, bool ex,
+                      bool both = false, uint8_t *strand_out = nullptr)
 {
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
     if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
+    if (both && n > 0 && !strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
+    if (both && (pairs_both_want_check(cfg) || strand_mode_check(cfg, PMX_STRAND_BOTH))) return -1;
     if (ex && pairs_ex_outputs_check(cfg, beg, cigar_buf, 0, cigar_off)) return -1;
     const bool cigar = ex && (cfg->want & PMX_WANT_CIGAR) != 0;
     if (cigar) { *cigar_buf = nullptr; cigar_off[0] = 0; }
@@ -4077,7 +4155,7 @@ static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_
     const hipStream_t st = hs.comp;
     pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr; uint8_t *dstrand = nullptr;
     const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the strand bytes
-    if (scratch_reserve(up_bytes + (strand ? (size_t)n : 0), (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
+    if (scratch_reserve(up_bytes + (strand || both ? (size_t)n : 0), (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
         (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
     HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
     if (strand) {
@@ -4090,6 +4168,13 @@ static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_
     else {
         if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
         if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
+    }
+    if (both) {
+        dstrand = (uint8_t *)dp + up_bytes;               // (the winners' strands, written by the fold)
+        int rc = pairs_run_both(&cfg_s, Q, R, n, dp, q32, r32, drec, dst, dstrand, st, pairs_chunk(n, q32, r32, opts, 2));
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_OR_RET(hipMemcpyAsync(strand_out, dstrand, (size_t)n, hipMemcpyDeviceToHost, st));
+        return pairs_copy_back(n, drec, dst, out, stats_out, !host_offsets, st);
     }
     if (!cigar) {
         const int rc = pairs_ex_run(&cfg_s, Q, R, n, dp, dstrand, q32, r32, drec, dst, nullptr, nullptr, 0, nullptr, st, opts);
@@ -4136,6 +4221,13 @@ extern "C" int pmx_align_pairs_ex(const pmx_config_t *cfg, const pmx_seqset_t *Q
                                   char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts)
 {
     return pairs_host(cfg, Q, R, n, pairs, strand, out, stats_out, beg, cigar_buf, cigar_off, opts, true);
+}
+
+extern "C" int pmx_align_pairs_both(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                    int64_t n, const pmx_pair_t *pairs, pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *strand_out,
+                                    const pmx_pairs_opts_t *opts)
+{
+    return pairs_host(cfg, Q, R, n, pairs, nullptr, out, stats_out, nullptr, nullptr, nullptr, opts, false, true, strand_out);
 }
 
 
@@ -4258,48 +4350,64 @@ static int search_pairs_want_check(const pmx_config_t *cfg, bool stats_buffer)
 
 // The outputs of one run, all device pointers: counts[0] = passing, counts[1] = written; first_bad (host entry over wrapped sets, else
 // nullptr) keeps the lowest absolute index of a bad pair.
-struct PairHitBufs { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *counts, *first_bad; };
+struct PairHitBufs { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *counts, *first_bad; uint8_t *strand = nullptr; };
 
 // n > 0 pairs behind the checks; asynchronous on `st`.  index0: the absolute number of the run's first pair (what d_hit_index counts from).
 static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int shape, int64_t first, int64_t n,
                             const pmx_pair_t *d_pairs, int64_t index0, int32_t max_qlen, int32_t max_rlen, int32_t min_score,
-                            const PairHitBufs &o, hipStream_t st, int64_t chunk)
+                            const PairHitBufs &o, hipStream_t st, int64_t chunk, int strand_mode = PMX_STRAND_FORWARD)
 {
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    pmx_record_t *crec = nullptr; pmx_stats_t *cst = nullptr; int64_t *cidx = nullptr, *ccnt = nullptr; void *sel = nullptr;
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0, chosen = strand_mode != PMX_STRAND_FORWARD;
+    const int per = strand_slots(strand_mode);
+    pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr; int64_t *cidx = nullptr, *ccnt = nullptr; void *sel = nullptr;
+    uint8_t *okf = nullptr;
     const size_t sel_bytes = pmx_select_scratch_bytes(chunk, 0, PMX_HITS_BY_INDEX);
     if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
             crec = c.take<pmx_record_t>((size_t)chunk);
             cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
             cidx = c.take<int64_t>((size_t)chunk); ccnt = c.take<int64_t>(2);
             sel = c.take<unsigned char>(sel_bytes);
+            if (chosen) {                                       // the slots' records before the fold, the folded validity bytes
+                srec = c.take<pmx_record_t>((size_t)chunk * per);
+                sst = stats ? c.take<pmx_stats_t>((size_t)chunk * per) : nullptr;
+                okf = c.take<uint8_t>((size_t)chunk);
+            }
         })) return -1;
     HIP_OR_RET(hipMemsetAsync(o.counts, 0, 2 * sizeof(int64_t), st));
     return pairs_run(Q, R, n, d_pairs, first, shape, nullptr, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
-            if (rc) return rc;
-            rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
-            if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, index0 + c0, o.first_bad, st);
+            int rc = 0;
+            if (chosen) {                                       // per * cn slots aligned, folded to cn records that carry their strand
+                rc = run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, srec, sst, st);
+                if (rc) return rc;
+                rc = pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st);
+                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(okf, cn, index0 + c0, o.first_bad, st);
+            } else {
+                rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
+                if (rc) return rc;
+                rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
+                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, index0 + c0, o.first_bad, st);
+            }
             if (!rc) rc = pmx_launch_select(crec, cn, min_score, 0, PMX_HITS_BY_INDEX, cidx, cn, ccnt, sel, st);
             if (!rc) rc = pmx_launch_pairs_append_hits(cidx, ccnt, cn, o.capacity, index0 + c0, b.pairs, crec, cst,
-                                                       o.pairs, o.index, o.recs, o.stats, o.counts, st);
+                                                       o.pairs, o.index, o.recs, o.stats, o.counts, st, o.strand, chosen ? 1 : 0);
             if (rc) { set_err("hit compaction of a chunk failed (%d)", rc); return rc; }
             return 0;
-        });
+        }, strand_mode);
 }
 
-extern "C" int pmx_search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
-                                       int64_t first, int64_t n, const pmx_pair_t *d_pairs,
-                                       int32_t max_qlen, int32_t max_rlen, int32_t min_score,
-                                       pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
-                                       int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts)
+// Both device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.
+static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                               int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                               int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                               pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                               int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand)
 {
     if (search_pairs_shape_check(Q, &R, shape, first, n, d_pairs)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr)) return -1;
+    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (n == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
         return 0;
@@ -4308,9 +4416,30 @@ extern "C" int pmx_search_pairs_device(const pmx_config_t *cfg, const pmx_seqset
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    const PairHitBufs o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_counts, nullptr};
+    const PairHitBufs o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_counts, nullptr, d_hit_strand};
     return search_pairs_run(cfg, Q, R, shape, first, n, d_pairs, first, max_qlen, max_rlen, min_score, o, (hipStream_t)stream,
-                            pairs_chunk(n, max_qlen, max_rlen, opts));
+                            pairs_chunk(n, max_qlen, max_rlen, opts, strand_slots(strand_mode)), strand_mode);
+}
+
+extern "C" int pmx_search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                       int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                       int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                       pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                       int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts)
+{
+    return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                               capacity, d_counts, stream, opts, PMX_STRAND_FORWARD, nullptr);
+}
+
+extern "C" int pmx_search_pairs_stranded_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                                int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                                int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                                pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                                int strand_mode, uint8_t *d_hit_strand)
+{
+    return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                               capacity, d_counts, stream, opts, strand_mode, d_hit_strand);
 }
 
 extern "C" void pmx_pair_hits_free(pmx_pair_hits_t *hits) { free(hits); }
@@ -4325,8 +4454,10 @@ static void seqset_host_lengths(const pmx_seqset *S, int64_t *mx, int64_t *mn, b
     }
 }
 
-extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
-                                const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, pmx_pair_hits_t **result)
+// Both host entries.  with_strand (pmx_search_pairs_stranded): the block is a pmx_strand_hits_t -- the fields of pmx_pair_hits_t, then the
+// strand bytes -- and the slices' hit buffers hold one more byte per hit; without it the block and the kernels are pmx_search_pairs'.
+static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                             const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, bool with_strand, pmx_pair_hits_t **result)
 {
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
@@ -4338,19 +4469,21 @@ extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (search_pairs_want_check(cfg, stats)) return -1;
-    // the result: one block -- header, descriptors, indices, records, statistics
+    if (search_pairs_want_check(cfg, stats) || strand_mode_check(cfg, strand_mode)) return -1;
+    // the result: one block -- header, descriptors, indices, records, statistics (, strand bytes)
     auto publish = [&](int64_t h, int64_t passing, pmx_pair_hits_t **out) -> int {
         auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        const size_t o_pairs = up(sizeof(pmx_pair_hits_t)), o_index = o_pairs + up(sizeof(pmx_pair_t) * (size_t)h);
+        const size_t o_pairs = up(with_strand ? sizeof(pmx_strand_hits_t) : sizeof(pmx_pair_hits_t)), o_index = o_pairs + up(sizeof(pmx_pair_t) * (size_t)h);
         const size_t o_recs = o_index + up(sizeof(int64_t) * (size_t)h), o_stats = o_recs + up(sizeof(pmx_record_t) * (size_t)h);
-        const size_t total = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0) + 16;
+        const size_t o_strand = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0);
+        const size_t total = o_strand + (with_strand ? up((size_t)h) : 0) + 16;
         char *blk = (char *)calloc(1, total);
         if (!blk) { set_err("out of memory"); return -1; }
         pmx_pair_hits_t *r = (pmx_pair_hits_t *)blk;
         r->n_hits = h; r->n_passing = passing;
         r->pairs = (pmx_pair_t *)(blk + o_pairs); r->index = (int64_t *)(blk + o_index); r->recs = (pmx_record_t *)(blk + o_recs);
         r->stats = stats ? (pmx_stats_t *)(blk + o_stats) : nullptr;
+        if (with_strand) ((pmx_strand_hits_t *)blk)->strand = (uint8_t *)(blk + o_strand);
         *out = r;
         return 0;
     };
@@ -4411,14 +4544,17 @@ extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
     const int64_t slice = std::min<int64_t>(opts->slice_pairs > 0 ? opts->slice_pairs : (int64_t)1 << 24, n);
     const int64_t cap_buf = opts->max_hits > 0 ? std::min<int64_t>(slice, opts->max_hits) : slice;
     pmx_pair_t *dhp = nullptr, *dp = nullptr; int64_t *dhi = nullptr, *dcnt = nullptr; pmx_record_t *dhr = nullptr; pmx_stats_t *dhs = nullptr;
+    uint8_t *dhb = nullptr;
     if (scratch_carve(SCR_PHIT, [&](Carver &c) {
             dhp = c.take<pmx_pair_t>((size_t)cap_buf); dhi = c.take<int64_t>((size_t)cap_buf); dhr = c.take<pmx_record_t>((size_t)cap_buf);
             dhs = stats ? c.take<pmx_stats_t>((size_t)cap_buf) : nullptr;
             dcnt = c.take<int64_t>(3);                   // passing, written, first bad pair
+            dhb = with_strand ? c.take<uint8_t>((size_t)cap_buf) : nullptr;
         })) return -1;
     if (listed && scratch_reserve(sizeof(pmx_pair_t) * (size_t)slice, (void **)&dp, SCR_PUP)) return -1;
     if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 2, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
-    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs;
+    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs; std::vector<uint8_t> vb;
+    const int per = strand_slots(strand_mode);
     int64_t stored = 0, passing = 0;
     for (int64_t s0 = 0; s0 < n; s0 += slice) {
         const int64_t sn = std::min<int64_t>(slice, n - s0);
@@ -4431,9 +4567,9 @@ extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
             }
         }
         const int64_t p0 = listed ? s0 : first + s0;     // the slice's first pair in the enumeration
-        const PairHitBufs o = {dhp, dhi, dhr, dhs, cap, dcnt, host_offsets ? nullptr : dcnt + 2};
+        const PairHitBufs o = {dhp, dhi, dhr, dhs, cap, dcnt, host_offsets ? nullptr : dcnt + 2, dhb};
         int64_t h[3] = {0, 0, 0};
-        int rc = search_pairs_run(&cfg_s, Q, R, shape, listed ? 0 : p0, sn, dp, p0, q32, r32, opts->min_score, o, st, pairs_chunk(sn, q32, r32, &popts));
+        int rc = search_pairs_run(&cfg_s, Q, R, shape, listed ? 0 : p0, sn, dp, p0, q32, r32, opts->min_score, o, st, pairs_chunk(sn, q32, r32, &popts, per), strand_mode);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
@@ -4441,12 +4577,15 @@ extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
         passing += h[0];
         const int64_t w = h[1];
         if (w > 0) {
-            try { vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w)); }
-            catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+            try {
+                vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w));
+                if (with_strand) vb.resize((size_t)(stored + w));
+            } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
             HIP_OR_RET(hipMemcpy(vp.data() + stored, dhp, sizeof(pmx_pair_t) * (size_t)w, hipMemcpyDeviceToHost));
             HIP_OR_RET(hipMemcpy(vi.data() + stored, dhi, sizeof(int64_t) * (size_t)w, hipMemcpyDeviceToHost));
             HIP_OR_RET(hipMemcpy(vr.data() + stored, dhr, sizeof(pmx_record_t) * (size_t)w, hipMemcpyDeviceToHost));
             if (stats) HIP_OR_RET(hipMemcpy(vs.data() + stored, dhs, sizeof(pmx_stats_t) * (size_t)w, hipMemcpyDeviceToHost));
+            if (with_strand) HIP_OR_RET(hipMemcpy(vb.data() + stored, dhb, (size_t)w, hipMemcpyDeviceToHost));
             stored += w;
         }
     }
@@ -4456,17 +4595,31 @@ extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
         memcpy(r->pairs, vp.data(), sizeof(pmx_pair_t) * (size_t)stored); memcpy(r->index, vi.data(), sizeof(int64_t) * (size_t)stored);
         memcpy(r->recs, vr.data(), sizeof(pmx_record_t) * (size_t)stored);
         if (stats) memcpy(r->stats, vs.data(), sizeof(pmx_stats_t) * (size_t)stored);
+        if (with_strand) memcpy(((pmx_strand_hits_t *)r)->strand, vb.data(), (size_t)stored);
     }
     *result = r;
     return 0;
 }
+
+extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, pmx_pair_hits_t **result)
+{
+    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, PMX_STRAND_FORWARD, false, result);
+}
+
+extern "C" int pmx_search_pairs_stranded(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                         const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, pmx_strand_hits_t **result)
+{
+    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, strand_mode, true, (pmx_pair_hits_t **)result);
+}
+extern "C" void pmx_strand_hits_free(pmx_strand_hits_t *hits) { free(hits); }
 
 // ==================================================================== per-query top-K ===
 // pmx_search_topk[_device] (semantics: include/parasail_amd.h): the chunk loop of the set batches over whole rows of the
 // rectangle Q x R with a body that keeps the chunk's records in scratch and merges them into one list of at most k entries per row
 // (pmx_topk.hip); the lists live in scratch until the last chunk, then go to their CSR positions.  Everything of a chunk runs on the
 // caller's stream in chunk order.
-struct TopkOut { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *row_off, *row_passing, *counts, *first_bad; };
+struct TopkOut { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *row_off, *row_passing, *counts, *first_bad; uint8_t *strand = nullptr; };
 
 // What both entries refuse about the rows, k and the flag.  *R: the reference-side set on return.
 static int topk_shape_check(const pmx_seqset *Q, const pmx_seqset **R, int64_t q_first, int64_t nq, int64_t k, int skip_self)
@@ -4491,7 +4644,8 @@ static int topk_shape_check(const pmx_seqset *Q, const pmx_seqset **R, int64_t q
 
 // nq > 0 rows behind the checks; asynchronous on `st`.
 static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t max_rlen,
-                    int32_t min_score, int32_t k, int skip_self, const TopkOut &o, hipStream_t st, const pmx_pairs_opts_t *opts)
+                    int32_t min_score, int32_t k, int skip_self, const TopkOut &o, hipStream_t st, const pmx_pairs_opts_t *opts,
+                    int strand_mode = PMX_STRAND_FORWARD)
 {
     const int64_t nr = R->count;
     if (nr == 0) {                                    // no pairs: every row is empty
@@ -4503,10 +4657,12 @@ static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqs
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
     const int ks = (int)std::min<int64_t>(k, nr);     // a row has |R| candidates at most
     const int64_t n = nq * nr, first = q_first * nr;
-    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts), (int64_t)1 << 26);      // (a chunk's positions fit 32 bits)
+    const bool chosen = strand_mode != PMX_STRAND_FORWARD;
+    const int per = strand_slots(strand_mode);
+    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, per), (int64_t)1 << 26);      // (a chunk's positions fit 32 bits)
     long long rows = 0, tps = 0, tstride = 0;
     pmx_topk_geometry(chunk, nr, ks, &rows, &tps, &tstride);
-    pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr;
+    pmx_record_t *crec = nullptr, *srec = nullptr, *arec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr, *ast = nullptr; uint8_t *okf = nullptr;
     uint64_t *tkeys = nullptr, *skeys = nullptr; int32_t *tcnt = nullptr, *tpass = nullptr, *sheld = nullptr; int64_t *spass = nullptr; void *scan = nullptr;
     const size_t scan_bytes = pmx_text_scan_scratch_bytes(nq);
     if (scratch_carve(SCR_PTOPK, [&](Carver &c) {
@@ -4518,39 +4674,53 @@ static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqs
             sst = stats ? c.take<pmx_stats_t>((size_t)nq * (size_t)ks) : nullptr;
             sheld = c.take<int32_t>((size_t)nq + 2); spass = c.take<int64_t>((size_t)nq);
             scan = c.take<unsigned char>(scan_bytes);
+            if (chosen) {                                       // the slots' records before the fold, the folded validity bytes
+                arec = c.take<pmx_record_t>((size_t)chunk * per);
+                ast = stats ? c.take<pmx_stats_t>((size_t)chunk * per) : nullptr;
+                okf = c.take<uint8_t>((size_t)chunk);
+            }
         })) return -1;
     HIP_OR_RET(hipMemsetAsync(sheld, 0, sizeof(int32_t) * ((size_t)nq + 2), st));
     HIP_OR_RET(hipMemsetAsync(spass, 0, sizeof(int64_t) * (size_t)nq, st));
     int rc = pairs_run(Q, R, n, nullptr, first, PMX_PAIRS_RECT, nullptr, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
-            if (rc) return rc;
-            rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
-            if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, first + c0, o.first_bad, st);
+            int rc = 0;
+            if (chosen) {                                       // per * cn slots aligned, folded to cn records that carry their strand into the lists
+                rc = run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, arec, ast, st);
+                if (rc) return rc;
+                rc = pmx_launch_pairs_fold_strands(arec, ast, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st);
+                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(okf, cn, first + c0, o.first_bad, st);
+            } else {
+                rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
+                if (rc) return rc;
+                rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
+                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, first + c0, o.first_bad, st);
+            }
             if (!rc) rc = pmx_launch_topk_merge(crec, cst, first + c0, cn, nr, q_first, ks, min_score, skip_self, tps, tstride, tkeys, tcnt, tpass,
                                                 skeys, srec, sst, sheld, spass, st);
             if (rc) { set_err("top-K merge of a chunk failed (%d)", rc); return rc; }
             return 0;
-        });
+        }, strand_mode);
     if (rc) return rc;
     rc = pmx_launch_text_offsets(sheld, nq, o.row_off, scan, scan_bytes, st);
     if (!rc) rc = pmx_launch_topk_emit(nq, q_first, nr, ks, skeys, srec, sst, sheld, spass, o.row_off, o.capacity, o.pairs, o.index, o.recs, o.stats,
-                                       o.row_passing, o.counts, st);
+                                       o.row_passing, o.counts, st, o.strand, chosen ? 1 : 0);
     if (rc) { set_err("top-K emit failed (%d)", rc); return rc; }
     return 0;
 }
 
-extern "C" int pmx_search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
-                                      int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
-                                      pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
-                                      int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
-                                      void *stream, const pmx_pairs_opts_t *opts)
+// Both device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.
+static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                              int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                              pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                              int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                              void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand)
 {
     if (topk_shape_check(Q, &R, q_first, nq, k, skip_self)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr)) return -1;
+    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), (hipStream_t)stream));
         if (d_row_off) HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), (hipStream_t)stream));
@@ -4561,14 +4731,36 @@ extern "C" int pmx_search_topk_device(const pmx_config_t *cfg, const pmx_seqset_
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    const TopkOut o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, nullptr};
-    return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts);
+    const TopkOut o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, nullptr, d_hit_strand};
+    return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts, strand_mode);
+}
+
+extern "C" int pmx_search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                      int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                      pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                      int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                      void *stream, const pmx_pairs_opts_t *opts)
+{
+    return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, PMX_STRAND_FORWARD, nullptr);
+}
+
+extern "C" int pmx_search_topk_stranded_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                               int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                               pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                               int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                               void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand)
+{
+    return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, strand_mode, d_hit_strand);
 }
 
 extern "C" void pmx_topk_hits_free(pmx_topk_hits_t *hits) { free(hits); }
 
-extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
-                               const pmx_topk_opts_t *opts, pmx_topk_hits_t **result)
+// Both host entries.  with_strand (pmx_search_topk_stranded): the block is a pmx_topk_strand_hits_t -- the fields of pmx_topk_hits_t, then
+// the strand bytes; without it the block and the kernels are pmx_search_topk's.
+static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                            const pmx_topk_opts_t *opts, int strand_mode, bool with_strand, pmx_topk_hits_t **result)
 {
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
@@ -4578,17 +4770,19 @@ extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (search_pairs_want_check(cfg, stats)) return -1;
-    // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics
+    if (search_pairs_want_check(cfg, stats) || strand_mode_check(cfg, strand_mode)) return -1;
+    // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics (, strand bytes)
     auto publish = [&](int64_t rows, int64_t h, pmx_topk_hits_t **out) -> int {
         auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        const size_t o_off = up(sizeof(pmx_topk_hits_t)), o_pass = o_off + up(sizeof(int64_t) * (size_t)(rows + 1));
+        const size_t o_off = up(with_strand ? sizeof(pmx_topk_strand_hits_t) : sizeof(pmx_topk_hits_t)), o_pass = o_off + up(sizeof(int64_t) * (size_t)(rows + 1));
         const size_t o_pairs = o_pass + up(sizeof(int64_t) * (size_t)rows), o_index = o_pairs + up(sizeof(pmx_pair_t) * (size_t)h);
         const size_t o_recs = o_index + up(sizeof(int64_t) * (size_t)h), o_stats = o_recs + up(sizeof(pmx_record_t) * (size_t)h);
-        const size_t total = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0) + 16;
+        const size_t o_strand = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0);
+        const size_t total = o_strand + (with_strand ? up((size_t)h) : 0) + 16;
         char *blk = (char *)calloc(1, total);
         if (!blk) { set_err("out of memory"); return -1; }
         pmx_topk_hits_t *r = (pmx_topk_hits_t *)blk;
+        if (with_strand) ((pmx_topk_strand_hits_t *)blk)->strand = (uint8_t *)(blk + o_strand);
         r->n_rows = rows; r->n_hits = h; r->n_passing = 0;
         r->row_off = (int64_t *)(blk + o_off); r->row_passing = (int64_t *)(blk + o_pass);
         r->pairs = (pmx_pair_t *)(blk + o_pairs); r->index = (int64_t *)(blk + o_index); r->recs = (pmx_record_t *)(blk + o_recs);
@@ -4641,21 +4835,23 @@ extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
     const int64_t slice = std::min<int64_t>(opts->slice_rows > 0 ? opts->slice_rows : std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / per_row), nq);
     const int64_t cap_buf = slice * ks;
     pmx_pair_t *dhp = nullptr; int64_t *dhi = nullptr, *doff = nullptr, *dpass = nullptr, *dcnt = nullptr; pmx_record_t *dhr = nullptr; pmx_stats_t *dhs = nullptr;
+    uint8_t *dhb = nullptr;
     if (scratch_carve(SCR_PTHIT, [&](Carver &c) {
             dhp = c.take<pmx_pair_t>((size_t)cap_buf); dhi = c.take<int64_t>((size_t)cap_buf); dhr = c.take<pmx_record_t>((size_t)cap_buf);
             dhs = stats ? c.take<pmx_stats_t>((size_t)cap_buf) : nullptr;
             doff = c.take<int64_t>((size_t)slice + 1); dpass = c.take<int64_t>((size_t)slice);
             dcnt = c.take<int64_t>(4);                   // kept, written, passing, first bad pair
+            dhb = with_strand ? c.take<uint8_t>((size_t)cap_buf) : nullptr;
         })) return -1;
     if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 3, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
-    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi, voff, vpass; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs;
+    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi, voff, vpass; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs; std::vector<uint8_t> vb;
     try { voff.assign((size_t)nq + 1, 0); vpass.assign((size_t)nq, 0); } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
     int64_t stored = 0, passing = 0;
     for (int64_t s0 = 0; s0 < nq; s0 += slice) {
         const int64_t sn = std::min<int64_t>(slice, nq - s0);
-        const TopkOut o = {dhp, dhi, dhr, dhs, sn * ks, doff, dpass, dcnt, host_offsets ? nullptr : dcnt + 3};
+        const TopkOut o = {dhp, dhi, dhr, dhs, sn * ks, doff, dpass, dcnt, host_offsets ? nullptr : dcnt + 3, dhb};
         int64_t h[4] = {0, 0, 0, 0};
-        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, q32, r32, opts->min_score, opts->k, opts->skip_self, o, st, &popts);
+        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, q32, r32, opts->min_score, opts->k, opts->skip_self, o, st, &popts, strand_mode);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
@@ -4669,12 +4865,15 @@ extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
         HIP_OR_RET(hipMemcpy(vpass.data() + s0, dpass, sizeof(int64_t) * (size_t)sn, hipMemcpyDeviceToHost));
         for (int64_t x = 1; x <= sn; ++x) voff[(size_t)(s0 + x)] += stored;
         if (w > 0) {
-            try { vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w)); }
-            catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+            try {
+                vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w));
+                if (with_strand) vb.resize((size_t)(stored + w));
+            } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
             HIP_OR_RET(hipMemcpy(vp.data() + stored, dhp, sizeof(pmx_pair_t) * (size_t)w, hipMemcpyDeviceToHost));
             HIP_OR_RET(hipMemcpy(vi.data() + stored, dhi, sizeof(int64_t) * (size_t)w, hipMemcpyDeviceToHost));
             HIP_OR_RET(hipMemcpy(vr.data() + stored, dhr, sizeof(pmx_record_t) * (size_t)w, hipMemcpyDeviceToHost));
             if (stats) HIP_OR_RET(hipMemcpy(vs.data() + stored, dhs, sizeof(pmx_stats_t) * (size_t)w, hipMemcpyDeviceToHost));
+            if (with_strand) HIP_OR_RET(hipMemcpy(vb.data() + stored, dhb, (size_t)w, hipMemcpyDeviceToHost));
             stored += w;
         }
     }
@@ -4686,7 +4885,21 @@ extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
         memcpy(r->pairs, vp.data(), sizeof(pmx_pair_t) * (size_t)stored); memcpy(r->index, vi.data(), sizeof(int64_t) * (size_t)stored);
         memcpy(r->recs, vr.data(), sizeof(pmx_record_t) * (size_t)stored);
         if (stats) memcpy(r->stats, vs.data(), sizeof(pmx_stats_t) * (size_t)stored);
+        if (with_strand) memcpy(((pmx_topk_strand_hits_t *)r)->strand, vb.data(), (size_t)stored);
     }
     *result = r;
     return 0;
 }
+
+extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                               const pmx_topk_opts_t *opts, pmx_topk_hits_t **result)
+{
+    return search_topk_host(cfg, Q, R, q_first, nq, opts, PMX_STRAND_FORWARD, false, result);
+}
+
+extern "C" int pmx_search_topk_stranded(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                        const pmx_topk_opts_t *opts, int strand_mode, pmx_topk_strand_hits_t **result)
+{
+    return search_topk_host(cfg, Q, R, q_first, nq, opts, strand_mode, true, (pmx_topk_hits_t **)result);
+}
+extern "C" void pmx_topk_strand_hits_free(pmx_topk_strand_hits_t *hits) { free(hits); }

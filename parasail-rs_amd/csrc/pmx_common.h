@@ -38,6 +38,7 @@ struct PmxBatch {
                              //   marks the blocks (of 2 * 64 / G pairs) it leaves to the LDS-profile form; the walk reads the flags too
 };
 #define PMX_FLAG_RETRY16 4   // internal record flag: redo with the LDS-profile variant of the fast kernel
+#define PMX_FLAG_STRAND1 0x40000000   // internal record flag, chunk scratch of the stranded searches only: the record is the reverse strand's
 
 // Fast path: local alignment, score + end positions, packed int16 lanes.
 // Returns 0 if launched, 1 if the shape is not supported by any instantiation (caller falls
@@ -288,7 +289,18 @@ int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long co
 int pmx_launch_rect_pairs_enumerate(long long nr, long long first, long long count, pmx_pair_t *pairs, hipStream_t stream);
 int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts, long long n, long long capacity, long long index0,
                                  const pmx_pair_t *pairs, const pmx_record_t *rec, const pmx_stats_t *stats,
-                                 pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t stream);
+                                 pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t stream,
+                                 uint8_t *hit_strand = nullptr /* optional: the strand byte of every hit written */,
+                                 int marked = 0 /* the records carry PMX_FLAG_STRAND1, to be taken out */);
+// The strand chosen by the entry.  resolve_both: n descriptors -> per * n slots (per 1: all reverse; per 2: slot 2 k forward,
+// 2 k + 1 reverse), arrays sized per * n (+ 2 for the lengths).  fold_strands: per * n slot records (statistics optional) -> n records,
+// statistics, strand bytes (optional) and validity bytes (optional); bad pairs get their record here; mark: PMX_FLAG_STRAND1 is set in
+// the records of reverse winners.
+int pmx_launch_pairs_resolve_both(const pmx_pair_t *pairs, long long n, int per, const int64_t *q_off, long long q_count, long long q_bytes,
+                                  const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                                  int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream);
+int pmx_launch_pairs_fold_strands(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
+                                  long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *strand, uint8_t *okf, hipStream_t stream);
 int pmx_launch_pairs_first_bad(const uint8_t *ok, long long n, long long index0, int64_t *first_bad, hipStream_t stream);
 // Per-query top-K (pmx_topk.hip; semantics: include/parasail_amd.h).  ks = min(k, |R|).  The running state of local row
 // li: st_keys / st_recs / st_stats[li * ks ..) hold st_held[li] entries in (score descending, j ascending) order, st_passing[li] = |P_i|
@@ -305,7 +317,7 @@ int pmx_launch_topk_merge(const pmx_record_t *rec, const pmx_stats_t *stats /* m
 int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, const uint64_t *st_keys, const pmx_record_t *st_recs,
                          const pmx_stats_t *st_stats, const int32_t *st_held, const int64_t *st_passing, const int64_t *row_off, long long capacity,
                          pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *row_passing,
-                         int64_t *counts, hipStream_t stream);
+                         int64_t *counts, hipStream_t stream, uint8_t *hit_strand = nullptr, int marked = 0 /* as in append_hits */);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);

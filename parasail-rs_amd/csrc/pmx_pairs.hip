@@ -18,6 +18,9 @@
 //   pmx_pairs_gather_stranded_kernel    the gather that can reverse-complement a query window
 //   pmx_pairs_fixup_cigar_kernel        bad pairs on the CIGAR road: record, empty text, begins
 //   pmx_text_rebase_kernel              a chunk's text offsets behind the running total of the chunks before it
+// and, for the entries that choose the strand themselves (pmx_align_pairs_both[_device], the _stranded searches):
+//   pmx_pairs_resolve_both_kernel       one descriptor -> `per` alignment slots: per 1 the reverse strand, per 2 forward then reverse
+//   pmx_pairs_fold_strands_kernel       the slots' records (and statistics) -> one record, statistics and strand per logical pair
 //
 // All of them are bandwidth kernels in plain C++: vector loads and stores only.
 #include "pmx_common.h"
@@ -209,6 +212,81 @@ void pmx_pairs_gather_stranded_kernel(long long n, const uint8_t *__restrict__ q
     if (lane < len - done) dst[done + lane] = src[done + lane];
 }
 
+// ---- both strands (pmx_align_pairs_both[_device], pmx_search_pairs_stranded[_device], pmx_search_topk_stranded[_device]) -----------
+// The resolve step for a strand the entry chooses: logical pair k becomes `per` alignment slots.  per == 1 (PMX_STRAND_REVERSE): slot k,
+// reverse-complemented.  per == 2 (PMX_STRAND_BOTH): slot 2 k the pair as stored, slot 2 k + 1 the pair with its query window
+// reverse-complemented -- the same lengths and sources twice, so the gather and every alignment kernel see an ordinary batch of 2 n
+// pairs.  A bad descriptor is bad in every slot (1 x 1, ok = 0, sflag = 0).  The scans read per * n + 1 lengths.
+__global__ __launch_bounds__(256)
+void pmx_pairs_resolve_both_kernel(const pmx_pair_t *__restrict__ pairs, long long n, int per,
+                                   const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
+                                   const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
+                                   int32_t max_qlen, int32_t max_rlen,
+                                   int32_t *__restrict__ qlen, int32_t *__restrict__ rlen,
+                                   int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n + 2) return;
+    if (k >= n) { const long long t = (long long)per * n + (k - n); qlen[t] = 0; rlen[t] = 0; return; }
+    const pmx_pair_t p = pairs[k];
+    long long qs = 0, rs = 0;
+    int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, max_qlen, &qs);
+    int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
+    const bool good = ql > 0 && rl > 0;
+    if (!good) { ql = 1; rl = 1; qs = 0; rs = 0; }
+    const uint8_t g = good ? 1 : 0;
+    const long long s = (long long)per * k;
+    qlen[s] = ql; rlen[s] = rl; qsrc[s] = qs; rsrc[s] = rs; ok[s] = g;
+    if (per == 2) {
+        sflag[s] = 0;
+        qlen[s + 1] = ql; rlen[s + 1] = rl; qsrc[s + 1] = qs; rsrc[s + 1] = rs; ok[s + 1] = g; sflag[s + 1] = g;
+    } else
+        sflag[s] = g;
+}
+
+// The slots of logical pair k back to one record: per == 2 the reverse slot's when its score is higher, else the forward slot's (only
+// the score is compared, a tie goes to the forward strand); per == 1 the one slot's.  The record is the winner's sixteen bytes, the
+// statistics are the winner's, the strand is the winner's sflag.  A bad pair gets {0, -1, -1, PMX_FLAG_BAD_PAIR}, zero statistics and
+// strand 0 here: no fix-up pass follows.  mark: the strand also rides in the record as PMX_FLAG_STRAND1, for records that stay in
+// chunk scratch on their way through selection or the top-K lists; the kernels that write a caller's hit arrays strip it.  okf
+// (optional): the logical pair's validity byte.  One thread per logical pair; slot records are read as 16-byte vectors (scratch is
+// 16-byte aligned), records are stored that way where the destination is aligned.
+__global__ __launch_bounds__(256)
+void pmx_pairs_fold_strands_kernel(const pmx_record_t *__restrict__ slot_rec, const pmx_stats_t *__restrict__ slot_stats,
+                                   const uint8_t *__restrict__ ok, const uint8_t *__restrict__ sflag, long long n, int per, int mark,
+                                   pmx_record_t *__restrict__ rec, pmx_stats_t *__restrict__ stats, uint8_t *__restrict__ strand,
+                                   uint8_t *__restrict__ okf)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const long long s = (long long)per * k;
+    const bool good = ok[s] != 0;
+    uint4 w = make_uint4(0u, 0xFFFFFFFFu, 0xFFFFFFFFu, (uint32_t)PMX_FLAG_BAD_PAIR);
+    pmx_stats_t ws; ws.matches = 0; ws.similar = 0; ws.length = 0;
+    unsigned sb = 0;
+    if (good) {
+        const uint4 *sr = reinterpret_cast<const uint4 *>(slot_rec + s);
+        long long from = s;
+        w = sr[0];
+        if (per == 2) {
+            const uint4 b = sr[1];
+            if ((int32_t)b.x > (int32_t)w.x) { w = b; from = s + 1; }
+        }
+        sb = sflag[from];
+        if (stats) ws = slot_stats[from];
+    }
+    if (mark && sb) w.w |= (uint32_t)PMX_FLAG_STRAND1;
+    if (((uintptr_t)rec & 15) == 0)
+        *reinterpret_cast<uint4 *>(rec + k) = w;
+    else {
+        pmx_record_t r; r.score = (int32_t)w.x; r.end_query = (int32_t)w.y; r.end_ref = (int32_t)w.z; r.flags = (int32_t)w.w;
+        rec[k] = r;
+    }
+    if (stats) stats[k] = ws;
+    if (strand) strand[k] = (uint8_t)sb;
+    if (okf) okf[k] = good ? 1 : 0;
+}
+
 // Bad pairs on the device CIGAR road, between the walk and the text scan: the record, no ops, no text, begins -1 / -1.
 __global__ __launch_bounds__(256)
 void pmx_pairs_fixup_cigar_kernel(const uint8_t *__restrict__ ok, long long n, pmx_record_t *__restrict__ rec,
@@ -284,12 +362,15 @@ void pmx_rect_pairs_enumerate_kernel(unsigned long long nr, long long first, lon
 // below `capacity`: where a hit lands depends on the selection's scan and the total alone, never on which block runs first.  counts is
 // only read here; pmx_pairs_advance_hits_kernel moves it, behind this kernel on the same stream.  A descriptor is 32 bytes: two
 // 16-byte accesses where both sides are 16-byte aligned (they are for hipMalloc'ed arrays), four 8-byte ones otherwise.
+// The stranded searches: `marked` says the chunk's records carry their strand as PMX_FLAG_STRAND1, which is taken out of the record on
+// its way to the caller; hit_strand (optional) receives it as a byte.  A launch without either copies the record as it is.
 __global__ __launch_bounds__(256)
 void pmx_pairs_append_hits_kernel(const int64_t *__restrict__ idx, const int64_t *__restrict__ chunk_counts, const int64_t *__restrict__ counts,
                                   long long capacity, long long index0, const pmx_pair_t *__restrict__ pairs,
                                   const pmx_record_t *__restrict__ rec, const pmx_stats_t *__restrict__ stats,
                                   pmx_pair_t *__restrict__ hit_pairs, int64_t *__restrict__ hit_index,
-                                  pmx_record_t *__restrict__ hit_recs, pmx_stats_t *__restrict__ hit_stats)
+                                  pmx_record_t *__restrict__ hit_recs, pmx_stats_t *__restrict__ hit_stats,
+                                  uint8_t *__restrict__ hit_strand, int marked)
 {
     const long long h = chunk_counts[0], base = counts[0];
     const bool wide = (((uintptr_t)pairs | (uintptr_t)hit_pairs) & 15) == 0;
@@ -307,7 +388,10 @@ void pmx_pairs_append_hits_kernel(const int64_t *__restrict__ idx, const int64_t
                 hit_pairs[pos] = pairs[k];
         }
         if (hit_index) hit_index[pos] = index0 + k;
-        hit_recs[pos] = rec[k];
+        pmx_record_t r = rec[k];
+        if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_STRAND1) != 0);
+        if (marked) r.flags &= ~PMX_FLAG_STRAND1;
+        hit_recs[pos] = r;
         if (hit_stats) hit_stats[pos] = stats[k];
     }
 }
@@ -395,6 +479,23 @@ int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long lon
                        qlen, rlen, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap);
     return pmx_pairs_launched();
 }
+int pmx_launch_pairs_resolve_both(const pmx_pair_t *pairs, long long n, int per, const int64_t *q_off, long long q_count, long long q_bytes,
+                                  const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                                  int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_resolve_both_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, n, per,
+                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok, sflag);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_fold_strands(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
+                                  long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *strand, uint8_t *okf, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_fold_strands_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slot_rec, slot_stats, ok, sflag,
+                       n, per, mark, rec, stats, strand, okf);
+    return pmx_pairs_launched();
+}
 int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *rec, int32_t *nops, int32_t *textlen, int32_t *beg, hipStream_t st)
 {
     if (n <= 0) return 0;
@@ -425,13 +526,14 @@ int pmx_launch_rect_pairs_enumerate(long long nr, long long first, long long cou
 }
 int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts, long long n, long long capacity, long long index0,
                                  const pmx_pair_t *pairs, const pmx_record_t *rec, const pmx_stats_t *stats,
-                                 pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t st)
+                                 pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t st,
+                                 uint8_t *hit_strand, int marked)
 {
     if (n <= 0) return 0;
     if (capacity > 0) {                                            // (the hit count is on the device: a grid for the chunk, capped; the loop strides)
         const long long blocks = (n + 255) / 256;
         hipLaunchKernelGGL(pmx_pairs_append_hits_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, idx, chunk_counts,
-                           (const int64_t *)counts, capacity, index0, pairs, rec, stats, hit_pairs, hit_index, hit_recs, hit_stats);
+                           (const int64_t *)counts, capacity, index0, pairs, rec, stats, hit_pairs, hit_index, hit_recs, hit_stats, hit_strand, marked);
     }
     hipLaunchKernelGGL(pmx_pairs_advance_hits_kernel, dim3(1), dim3(1), 0, st, chunk_counts, capacity, counts);
     return pmx_pairs_launched();

@@ -217,13 +217,15 @@ void pmx_topk_row_kernel(const pmx_record_t *__restrict__ rec, const pmx_stats_t
     if (threadIdx.x == 0) st_held[li] = (int32_t)b.count;
 }
 
-// One wave per row.  Stores to the caller's hit arrays only at positions below `capacity`.
+// One wave per row.  Stores to the caller's hit arrays only at positions below `capacity`.  The stranded search: the lists' records carry
+// their strand as PMX_FLAG_STRAND1 (`marked`), taken out here; hit_strand (optional) receives it as a byte.
 __global__ __launch_bounds__(256)
 void pmx_topk_emit_kernel(long long nq, long long q_first, unsigned long long nr, unsigned ks,
                           const uint64_t *__restrict__ st_keys, const pmx_record_t *__restrict__ st_recs, const pmx_stats_t *__restrict__ st_stats,
                           const int32_t *__restrict__ st_held, const int64_t *__restrict__ st_passing, const int64_t *__restrict__ row_off,
                           long long capacity, pmx_pair_t *__restrict__ hit_pairs, int64_t *__restrict__ hit_index,
-                          pmx_record_t *__restrict__ hit_recs, pmx_stats_t *__restrict__ hit_stats, int64_t *__restrict__ row_passing)
+                          pmx_record_t *__restrict__ hit_recs, pmx_stats_t *__restrict__ hit_stats, int64_t *__restrict__ row_passing,
+                          uint8_t *__restrict__ hit_strand, int marked)
 {
     const long long li = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
     const unsigned lane = threadIdx.x & 63;
@@ -239,7 +241,10 @@ void pmx_topk_emit_kernel(long long nq, long long q_first, unsigned long long nr
         const long long j = (long long)(0x7FFFFFFFu - (uint32_t)st_keys[l0 + x]);
         if (hit_pairs) { pmx_pair_t d; d.q = ai; d.r = j; d.q_beg = 0; d.q_len = -1; d.r_beg = 0; d.r_len = -1; hit_pairs[pos] = d; }
         if (hit_index) hit_index[pos] = (int64_t)((unsigned long long)ai * nr + (unsigned long long)j);
-        hit_recs[pos] = st_recs[l0 + x];
+        pmx_record_t r = st_recs[l0 + x];
+        if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_STRAND1) != 0);
+        if (marked) r.flags &= ~PMX_FLAG_STRAND1;
+        hit_recs[pos] = r;
         if (hit_stats) hit_stats[pos] = st_stats[l0 + x];
     }
 }
@@ -294,11 +299,11 @@ int pmx_launch_topk_merge(const pmx_record_t *rec, const pmx_stats_t *stats, lon
 int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, const uint64_t *st_keys, const pmx_record_t *st_recs,
                          const pmx_stats_t *st_stats, const int32_t *st_held, const int64_t *st_passing, const int64_t *row_off, long long capacity,
                          pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *row_passing,
-                         int64_t *counts, hipStream_t st)
+                         int64_t *counts, hipStream_t st, uint8_t *hit_strand, int marked)
 {
     if (nq <= 0) return 0;
     hipLaunchKernelGGL(pmx_topk_emit_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, nq, q_first, (unsigned long long)nr, (unsigned)ks,
-                       st_keys, st_recs, st_stats, st_held, st_passing, row_off, capacity, hit_pairs, hit_index, hit_recs, hit_stats, row_passing);
+                       st_keys, st_recs, st_stats, st_held, st_passing, row_off, capacity, hit_pairs, hit_index, hit_recs, hit_stats, row_passing, hit_strand, marked);
     hipLaunchKernelGGL(pmx_topk_counts_kernel, dim3(1), dim3(256), 0, st, nq, st_passing, row_off, capacity, counts);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
