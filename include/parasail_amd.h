@@ -642,6 +642,25 @@ typedef struct pmx_topk_hits { int64_t n_rows, n_hits, n_passing; int64_t *row_o
 int  pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
                      const pmx_topk_opts_t *opts, pmx_topk_hits_t **result);
 void pmx_topk_hits_free(pmx_topk_hits_t *hits);
+/* Test hook of the top-K kernels (parasail-rs_amd/csrc/pmx_topk.hip; reference: tests/topk_ref.py): the selection of
+ * pmx_search_topk[_stranded]_device on records the caller supplies instead of alignments, so that scores over all of int32, rows of
+ * hundreds of tiles and any flag bits reach the tile, row and emit kernels.  d_rec[li * nr + j] (and d_stats, optional) is the record of
+ * pair (q_first + li, j).  The nq * nr records are walked in consecutive chunks of chunk_pairs (0: PMX_TOPK_RECORDS_CHUNK; at most 2^26,
+ * the entries' bound), each chunk goes through the entries' merge with the entries' geometry, and the run ends in their offsets scan,
+ * emit and counts: the outputs are those documented for pmx_search_topk_device.  skip_self leaves out j == q_first + li.  marked != 0 is
+ * the stranded entries' emit: flag bit 0x40000000, their internal mark of a reverse-strand record, is cleared in the emitted records and
+ * every other bit is kept; d_hit_strand (optional, one byte per written hit) receives that bit whatever `marked`.  Refused with -1 and a pmx_last_error() text before any GPU work: a negative q_first, nq or nr;
+ * nr above 2^31 - 1; (q_first + nq) * nr beyond 2^63 - 1; k outside 1 .. PMX_TOPK_MAX; NULL d_rec, d_row_off or d_counts; a negative
+ * capacity or chunk_pairs; NULL d_hit_recs with capacity > 0; d_hit_stats without d_stats.  Asynchronous on `stream`; scratch of the
+ * calling thread, the one of pmx_search_topk_device without the chunk buffers. */
+#define PMX_TOPK_RECORDS_CHUNK ((int64_t)1 << 22)
+int pmx_topk_records_device(const pmx_record_t *d_rec, const pmx_stats_t *d_stats /* optional */,
+                            int64_t q_first, int64_t nq, int64_t nr,
+                            int32_t min_score, int32_t k, int32_t skip_self, int64_t chunk_pairs /* 0: PMX_TOPK_RECORDS_CHUNK */,
+                            int32_t marked, uint8_t *d_hit_strand /* optional */,
+                            pmx_pair_t *d_hit_pairs /* optional */, int64_t *d_hit_index /* optional */, pmx_record_t *d_hit_recs,
+                            pmx_stats_t *d_hit_stats /* optional, needs d_stats */, int64_t capacity, int64_t *d_row_off /* nq + 1 */,
+                            int64_t *d_row_passing /* nq, optional */, int64_t *d_counts, void *stream);
 
 /* Both strands (extension): the set entries for DNA whose orientation is unknown.  Every pair is aligned on the forward and on the
  * reverse strand inside its chunk and the two records become one BEFORE selection, so hits, counts, top-K cuts and device memory

@@ -270,6 +270,8 @@ _sig("pmx_search_topk_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c
 _sig("pmx_search_topk", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.POINTER(C.POINTER(pmx_topk_hits_t)))
 _sig("pmx_topk_hits_free", None, C.POINTER(pmx_topk_hits_t))
+_sig("pmx_topk_records_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_align_pairs_both", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_align_pairs_both_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
@@ -1538,6 +1540,17 @@ def search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k,
     rc = lib.pmx_search_topk_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
                                     max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
                                     d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def topk_records_device(d_rec, d_stats, q_first, nq, nr, min_score, k, skip_self, chunk_pairs, marked, d_hit_strand, d_hit_pairs, d_hit_index,
+                        d_hit_recs, d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, stream=0):
+    """The selection of search_topk_device on the caller's nq * nr records (d_rec[li * nr + j]: pair (q_first + li, j)) instead of
+    alignments, through the same kernels (test hook).  marked: flag bit 0x40000000 is taken out of the emitted records."""
+    rc = lib.pmx_topk_records_device(d_rec, d_stats, int(q_first), int(nq), int(nr), int(min_score), int(k), 1 if skip_self else 0,
+                                     int(chunk_pairs), 1 if marked else 0, d_hit_strand, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                                     int(capacity), d_row_off, d_row_passing, d_counts, stream)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

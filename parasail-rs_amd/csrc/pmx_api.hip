@@ -4642,46 +4642,89 @@ static int topk_shape_check(const pmx_seqset *Q, const pmx_seqset **R, int64_t q
     return 0;
 }
 
+// What the top-K kernels keep between the chunks of a run, shared by topk_run and the record-level hook: the tiles' survivors of one
+// chunk, the rows' lists (keys, records, statistics, numbers held, |P_i|) and the scan scratch of the tail.
+struct TopkLists {
+    int ks = 0; long long rows = 0, tps = 0, tstride = 0;
+    uint64_t *tkeys = nullptr, *skeys = nullptr; int32_t *tcnt = nullptr, *tpass = nullptr, *sheld = nullptr; int64_t *spass = nullptr;
+    pmx_record_t *srec = nullptr; pmx_stats_t *sst = nullptr; void *scan = nullptr; size_t scan_bytes = 0;
+    // ks: min(k, |R|), a row has |R| candidates at most; chunk: the most pairs one merge sees
+    void shape(int64_t chunk, int64_t nr, int64_t nq, int32_t k)
+    {
+        ks = (int)std::min<int64_t>(k, nr);
+        pmx_topk_geometry(chunk, nr, ks, &rows, &tps, &tstride);
+        scan_bytes = pmx_text_scan_scratch_bytes(nq);
+    }
+    void carve(Carver &c, int64_t nq, bool stats)
+    {
+        tkeys = c.take<uint64_t>((size_t)rows * (size_t)tps * (size_t)tstride);
+        tcnt = c.take<int32_t>((size_t)rows * (size_t)tps); tpass = c.take<int32_t>((size_t)rows * (size_t)tps);
+        skeys = c.take<uint64_t>((size_t)nq * (size_t)ks); srec = c.take<pmx_record_t>((size_t)nq * (size_t)ks);
+        sst = stats ? c.take<pmx_stats_t>((size_t)nq * (size_t)ks) : nullptr;
+        sheld = c.take<int32_t>((size_t)nq + 2); spass = c.take<int64_t>((size_t)nq);
+        scan = c.take<unsigned char>(scan_bytes);
+    }
+    int clear(int64_t nq, hipStream_t st) const                     // every list empty, before the first chunk
+    {
+        HIP_OR_RET(hipMemsetAsync(sheld, 0, sizeof(int32_t) * ((size_t)nq + 2), st));
+        HIP_OR_RET(hipMemsetAsync(spass, 0, sizeof(int64_t) * (size_t)nq, st));
+        return 0;
+    }
+    // crec / cst: the records (statistics) of pairs [p0, p0 + cn) of the rectangle, p0 absolute
+    int merge(const pmx_record_t *crec, const pmx_stats_t *cst, int64_t p0, int64_t cn, int64_t nr, int64_t q_first, int32_t min_score,
+              int skip_self, hipStream_t st) const
+    {
+        const int rc = pmx_launch_topk_merge(crec, cst, p0, cn, nr, q_first, ks, min_score, skip_self, tps, tstride, tkeys, tcnt, tpass,
+                                             skeys, srec, sst, sheld, spass, st);
+        if (rc) set_err("top-K merge of a chunk failed (%d)", rc);
+        return rc;
+    }
+    // after the last chunk: the rows' offsets, the lists to their CSR positions, the counts
+    int finish(int64_t nq, int64_t q_first, int64_t nr, const TopkOut &o, int marked, hipStream_t st) const
+    {
+        int rc = pmx_launch_text_offsets(sheld, nq, o.row_off, scan, scan_bytes, st);
+        if (!rc) rc = pmx_launch_topk_emit(nq, q_first, nr, ks, skeys, srec, sst, sheld, spass, o.row_off, o.capacity, o.pairs, o.index, o.recs, o.stats,
+                                           o.row_passing, o.counts, st, o.strand, marked);
+        if (rc) { set_err("top-K emit failed (%d)", rc); return rc; }
+        return 0;
+    }
+};
+// |R| == 0: no pairs, every row is empty
+static int topk_no_pairs(int64_t nq, const TopkOut &o, hipStream_t st)
+{
+    HIP_OR_RET(hipMemsetAsync(o.row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st));
+    if (o.row_passing) HIP_OR_RET(hipMemsetAsync(o.row_passing, 0, sizeof(int64_t) * (size_t)nq, st));
+    HIP_OR_RET(hipMemsetAsync(o.counts, 0, 3 * sizeof(int64_t), st));
+    return 0;
+}
+static const int64_t TOPK_CHUNK_MAX = (int64_t)1 << 26;            // (a chunk's positions fit 32 bits)
+
 // nq > 0 rows behind the checks; asynchronous on `st`.
 static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t max_rlen,
                     int32_t min_score, int32_t k, int skip_self, const TopkOut &o, hipStream_t st, const pmx_pairs_opts_t *opts,
                     int strand_mode = PMX_STRAND_FORWARD)
 {
     const int64_t nr = R->count;
-    if (nr == 0) {                                    // no pairs: every row is empty
-        HIP_OR_RET(hipMemsetAsync(o.row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st));
-        if (o.row_passing) HIP_OR_RET(hipMemsetAsync(o.row_passing, 0, sizeof(int64_t) * (size_t)nq, st));
-        HIP_OR_RET(hipMemsetAsync(o.counts, 0, 3 * sizeof(int64_t), st));
-        return 0;
-    }
+    if (nr == 0) return topk_no_pairs(nq, o, st);
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    const int ks = (int)std::min<int64_t>(k, nr);     // a row has |R| candidates at most
     const int64_t n = nq * nr, first = q_first * nr;
     const bool chosen = strand_mode != PMX_STRAND_FORWARD;
     const int per = strand_slots(strand_mode);
-    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, per), (int64_t)1 << 26);      // (a chunk's positions fit 32 bits)
-    long long rows = 0, tps = 0, tstride = 0;
-    pmx_topk_geometry(chunk, nr, ks, &rows, &tps, &tstride);
-    pmx_record_t *crec = nullptr, *srec = nullptr, *arec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr, *ast = nullptr; uint8_t *okf = nullptr;
-    uint64_t *tkeys = nullptr, *skeys = nullptr; int32_t *tcnt = nullptr, *tpass = nullptr, *sheld = nullptr; int64_t *spass = nullptr; void *scan = nullptr;
-    const size_t scan_bytes = pmx_text_scan_scratch_bytes(nq);
+    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, per), TOPK_CHUNK_MAX);
+    TopkLists L;
+    L.shape(chunk, nr, nq, k);
+    pmx_record_t *crec = nullptr, *arec = nullptr; pmx_stats_t *cst = nullptr, *ast = nullptr; uint8_t *okf = nullptr;
     if (scratch_carve(SCR_PTOPK, [&](Carver &c) {
             crec = c.take<pmx_record_t>((size_t)chunk);
             cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
-            tkeys = c.take<uint64_t>((size_t)rows * (size_t)tps * (size_t)tstride);
-            tcnt = c.take<int32_t>((size_t)rows * (size_t)tps); tpass = c.take<int32_t>((size_t)rows * (size_t)tps);
-            skeys = c.take<uint64_t>((size_t)nq * (size_t)ks); srec = c.take<pmx_record_t>((size_t)nq * (size_t)ks);
-            sst = stats ? c.take<pmx_stats_t>((size_t)nq * (size_t)ks) : nullptr;
-            sheld = c.take<int32_t>((size_t)nq + 2); spass = c.take<int64_t>((size_t)nq);
-            scan = c.take<unsigned char>(scan_bytes);
+            L.carve(c, nq, stats);
             if (chosen) {                                       // the slots' records before the fold, the folded validity bytes
                 arec = c.take<pmx_record_t>((size_t)chunk * per);
                 ast = stats ? c.take<pmx_stats_t>((size_t)chunk * per) : nullptr;
                 okf = c.take<uint8_t>((size_t)chunk);
             }
         })) return -1;
-    HIP_OR_RET(hipMemsetAsync(sheld, 0, sizeof(int32_t) * ((size_t)nq + 2), st));
-    HIP_OR_RET(hipMemsetAsync(spass, 0, sizeof(int64_t) * (size_t)nq, st));
+    if (L.clear(nq, st)) return -1;
     int rc = pairs_run(Q, R, n, nullptr, first, PMX_PAIRS_RECT, nullptr, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             int rc = 0;
@@ -4696,17 +4739,11 @@ static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqs
                 rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
                 if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, first + c0, o.first_bad, st);
             }
-            if (!rc) rc = pmx_launch_topk_merge(crec, cst, first + c0, cn, nr, q_first, ks, min_score, skip_self, tps, tstride, tkeys, tcnt, tpass,
-                                                skeys, srec, sst, sheld, spass, st);
             if (rc) { set_err("top-K merge of a chunk failed (%d)", rc); return rc; }
-            return 0;
+            return L.merge(crec, cst, first + c0, cn, nr, q_first, min_score, skip_self, st);
         }, strand_mode);
     if (rc) return rc;
-    rc = pmx_launch_text_offsets(sheld, nq, o.row_off, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_topk_emit(nq, q_first, nr, ks, skeys, srec, sst, sheld, spass, o.row_off, o.capacity, o.pairs, o.index, o.recs, o.stats,
-                                       o.row_passing, o.counts, st, o.strand, chosen ? 1 : 0);
-    if (rc) { set_err("top-K emit failed (%d)", rc); return rc; }
-    return 0;
+    return L.finish(nq, q_first, nr, o, chosen ? 1 : 0, st);
 }
 
 // Both device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.
@@ -4753,6 +4790,52 @@ extern "C" int pmx_search_topk_stranded_device(const pmx_config_t *cfg, const pm
 {
     return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                               capacity, d_row_off, d_row_passing, d_counts, stream, opts, strand_mode, d_hit_strand);
+}
+
+// Test hook (include/parasail_amd.h): the chunk loop of topk_run over records the caller made up instead of alignments -- the same
+// geometry, merges and tail, so scores over all of int32 and rows of any length reach the kernels of pmx_topk.hip.
+extern "C" int pmx_topk_records_device(const pmx_record_t *d_rec, const pmx_stats_t *d_stats, int64_t q_first, int64_t nq, int64_t nr,
+                                       int32_t min_score, int32_t k, int32_t skip_self, int64_t chunk_pairs,
+                                       int32_t marked, uint8_t *d_hit_strand,
+                                       pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                       int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts, void *stream)
+{
+    int64_t last = 0;
+    if (q_first < 0 || nq < 0 || nr < 0) { set_err("negative q_first, nq or nr"); return -1; }
+    if (nr > INT32_MAX) { set_err("nr %lld is outside 0 .. 2^31 - 1", (long long)nr); return -1; }
+    if (__builtin_add_overflow(q_first, nq, &last) || pmx_rect_pairs_count(last, nr) < 0) {
+        set_err("%lld + %lld rows of %lld pairs overflow 2^63 - 1", (long long)q_first, (long long)nq, (long long)nr); return -1;
+    }
+    if (k < 1 || k > PMX_TOPK_MAX) { set_err("k %lld is outside 1 .. %d (a row's list is sorted in LDS)", (long long)k, PMX_TOPK_MAX); return -1; }
+    if (!d_rec) { set_err("null records"); return -1; }
+    if (!d_row_off) { set_err("null row offsets"); return -1; }
+    if (!d_counts) { set_err("null counts"); return -1; }
+    if (capacity < 0) { set_err("negative capacity"); return -1; }
+    if (chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
+    if (d_hit_stats && !d_stats) { set_err("hit statistics without statistics"); return -1; }
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    const TopkOut o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, nullptr, d_hit_strand};
+    if (nq == 0) {
+        HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), st));
+        HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), st));
+        return 0;
+    }
+    if (nr == 0) return topk_no_pairs(nq, o, st);
+    const int64_t n = nq * nr, first = q_first * nr;
+    const int64_t chunk = std::min<int64_t>(std::min<int64_t>(chunk_pairs > 0 ? chunk_pairs : PMX_TOPK_RECORDS_CHUNK, n), TOPK_CHUNK_MAX);
+    TopkLists L;
+    L.shape(chunk, nr, nq, k);
+    if (scratch_carve(SCR_PTOPK, [&](Carver &c) { L.carve(c, nq, d_stats != nullptr); })) return -1;
+    if (L.clear(nq, st)) return -1;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int rc = L.merge(d_rec + c0, d_stats ? d_stats + c0 : nullptr, first + c0, std::min<int64_t>(chunk, n - c0), nr, q_first, min_score,
+                               skip_self ? 1 : 0, st);
+        if (rc) return rc;
+    }
+    return L.finish(nq, q_first, nr, o, marked ? 1 : 0, st);
 }
 
 extern "C" void pmx_topk_hits_free(pmx_topk_hits_t *hits) { free(hits); }

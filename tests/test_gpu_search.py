@@ -93,6 +93,78 @@ def test_selection_looks_at_the_score_only_and_takes_extreme_scores(pkg):
                 assert counts.tolist() == [len(want), wp] and (got[:len(want)] == want).all()
 
 
+def _tie_run_end(scores, min_score):
+    """a max_hits that ends exactly behind a tie run of the passing scores: the rank the pick looks for is the last of its bin in every
+    pass (0 when nothing would be cut there)"""
+    s = np.sort(scores[scores >= min_score])[::-1]
+    if len(s) < 2:
+        return 0
+    k = int((s >= s[len(s) // 2]).sum())
+    return k if k < len(s) else 0
+
+
+def _selection_cases(pkg, scores, d_rec, thresholds, cuts):
+    """test_selection_equals_reference's checks on every (min_score, max_hits, order): exact against search_ref.select, the sentinel
+    behind the hits, a second run byte-identical, a capacity below the number selected; max_hits: none, one, a cut inside a tie run, one
+    exactly behind a tie run, |P| - 1, |P|, |P| + 1 and `cuts`"""
+    n = len(scores)
+    small_capacity_done = 0
+    for min_score in thresholds:
+        npass = int((scores >= min_score).sum())
+        for max_hits in sorted({0, 1, _tie_run_cut(scores, min_score), _tie_run_end(scores, min_score), max(npass - 1, 0), npass, npass + 1} | set(cuts)):
+            for order in (search_ref.BY_INDEX, search_ref.BY_SCORE):
+                want, wp = search_ref.select(scores, min_score, max_hits, order)
+                got, counts = _select(pkg, d_rec, n, min_score, max_hits, order, n)
+                ctx = (n, min_score, max_hits, order)
+                assert counts.tolist() == [len(want), wp], (ctx, counts)
+                assert (got[:len(want)] == want).all(), ctx
+                assert (got[len(want):] == SENTINEL).all(), ctx
+                again, counts2 = _select(pkg, d_rec, n, min_score, max_hits, order, n)
+                assert again.tobytes() == got.tobytes() and counts2.tobytes() == counts.tobytes(), ctx
+                if len(want) >= 2:
+                    cap = len(want) // 2
+                    part, pc = _select(pkg, d_rec, n, min_score, max_hits, order, cap)
+                    assert pc.tolist() == [len(want), wp], ctx
+                    assert (part[:cap] == want[:cap]).all() and (part[cap:] == SENTINEL).all(), ctx
+                    small_capacity_done += 1
+    return small_capacity_done
+
+
+@pytest.mark.parametrize("n", [257, 2047, 2048, 2049, 100003])
+@pytest.mark.parametrize("name", sorted(search_ref.WIDE_SCORES))
+def test_selection_over_the_whole_key_range(pkg, name, n):
+    """scores that spread over the radix select's digits -- all of int32, the top digit only, the middle digit only, the low digit
+    only, clusters at the digit borders and the ends of int32 -- where tied_scores() fills two bins of the first pass and one per sign
+    of the second: the choice among bins and what the passes hand on (krem, gt, prefix, mask) decide the result here"""
+    rng = np.random.default_rng(5400 + n % 977)
+    scores = search_ref.WIDE_SCORES[name](rng, n)
+    values = np.unique(scores)
+    top = int(values[-1])
+    thresholds = (int(values[0]), int(values[len(values) // 2]), top + 1 if top < search_ref.INT32_MAX else top)
+    assert (int((scores >= thresholds[2]).sum()) == 0) == (top < search_ref.INT32_MAX)         # (nothing lies above INT32_MAX)
+    T, above, E = search_ref.radix_select_model(scores, thresholds[0], n // 2)
+    assert T is not None and above + E == n // 2
+    d_rec = _up(search_ref.records(scores, rng))
+    assert _selection_cases(pkg, scores, d_rec, thresholds, (n // 2,))
+
+
+@pytest.mark.parametrize("which", ["top", "middle"])
+def test_selection_kth_score_in_bin_0(pkg, which):
+    """the K-th score in bin 0 of the first pass / of the second pass: the bin the pick loop takes without looking at it"""
+    scores = search_ref.bin0_scores(which)
+    n = len(scores)
+    shift, bits = search_ref.DIGITS[0 if which == "top" else 1]
+    cuts = (601, 900, 1800, n - 1)
+    for k in cuts:
+        T, above, E = search_ref.radix_select_model(scores, INT32_MIN, k)
+        Tu = (T & 0xFFFFFFFF) ^ 0x80000000
+        assert (Tu >> shift) & ((1 << bits) - 1) == 0 and above >= 600 and above + E == k
+        assert which == "top" or Tu >> 21 != 0
+    d_rec = _up(search_ref.records(scores, np.random.default_rng(5500)))
+    median = int(np.sort(scores)[n // 2])
+    assert _selection_cases(pkg, scores, d_rec, (INT32_MIN, median), cuts)
+
+
 # ------------------------------------------------------------------------------------------------------------------- 2. gather
 def _gather(pkg, d_rbuf_ptr, d_roff, n, index, out_capacity):
     import torch

@@ -69,6 +69,96 @@ def test_table_kernel_protein_1000_by_1000_and_rowcol_only(pkg, orc):
             assert tuple(out[k, :3]) == (w.score, w.end_query, w.end_ref)
 
 
+# The plain (no trace) kernel at 4 and 8 columns per lane.  Width 4 -- every reference of the batch within 256 columns -- stores a lane's
+# four cells with one 16-byte store straight at the row's address; width 8 -- within 512 -- turns a row in LDS first, like width 16.
+WIDTH_REFS = {4: [1, 3, 4, 5, 63, 252, 253, 255, 256], 8: [257, 259, 260, 505, 511, 512]}
+
+
+def _exact_len(rng, q, rl, letters):
+    """a reference of exactly rl symbols, related to q where q is long enough to matter"""
+    rnd = random_seqs(rng, 1, rl, rl, letters)[0]
+    return (mutate(rng, q, 0.1, 0.05, letters) + rnd)[:rl] if len(q) > 20 and rng.random() < 0.6 else rnd
+
+
+def _width_batch(rng, width, letters=DNA):
+    """queries of 1 .. 80 against every edge length of the width, twice, and shorter references of odd and even lengths in between:
+    the tables follow each other without padding, so they and their rows start at every offset mod 4 cells"""
+    rls = []
+    for rl in WIDTH_REFS[width]:
+        rls += [rl, int(rng.integers(1, WIDTH_REFS[width][-1])), rl, int(rng.integers(1, 40))]
+    qls = [int(x) for x in rng.integers(1, 81, size=len(rls))]
+    qls[0], qls[1], qls[-1], qls[-2] = 80, 1, 1, 80
+    qs = [random_seqs(rng, 1, ql, ql, letters)[0] for ql in qls]
+    rs = [_exact_len(rng, q, rl, letters) for q, rl in zip(qs, rls)]
+    lo, hi = (1, 256) if width == 4 else (257, 512)
+    assert lo <= max(rls) <= hi and max(qls) == 80
+    return qs, rs
+
+
+def _check_width_batch(pkg, orc, cfg, om, qs, rs, ctx):
+    mode, sg, go, ge = cfg.mode, cfg.sg_flags, cfg.open, cfg.extend
+    table, row, col, out, toff, qo, ro = _batch_tables(pkg, cfg, qs, rs)
+    assert pkg.lib.pmx_last_kernel().decode() == "pmx_table_kernel"
+    _, row2, col2, out2, _, _, _ = _batch_tables(pkg, cfg, qs, rs, want_table=False)          # the row / column-only form
+    assert pkg.lib.pmx_last_kernel().decode() == "pmx_table_kernel"
+    starts = set()
+    for k in range(len(qs)):
+        w = orc.align(mode, qs[k], rs[k], go, ge, om, sg_flags=sg, table=True, rowcol=True)
+        ql, rl = len(qs[k]), len(rs[k])
+        starts |= {int(toff[k] + i * rl) % 4 for i in range(ql)}
+        t = table[toff[k]:toff[k + 1]].reshape(ql, rl)
+        bad = np.argwhere(t != w.score_table)
+        assert len(bad) == 0, (ctx, k, ql, rl, bad[:3], t[tuple(bad[0])], w.score_table[tuple(bad[0])])
+        for r_, c_, o_ in ((row, col, out), (row2, col2, out2)):
+            assert (r_[ro[k]:ro[k + 1]] == w.score_row).all() and (c_[qo[k]:qo[k + 1]] == w.score_col).all(), (ctx, k, ql, rl)
+            assert tuple(o_[k, :3]) == (w.score, w.end_query, w.end_ref), (ctx, k, ql, rl)
+    assert starts == {0, 1, 2, 3}                                                             # rows at every alignment mod 16 bytes
+
+
+@pytest.mark.parametrize("width", [4, 8])
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("gaps", [(5, 2), (0, 0), (3, 3), (11, 1)])
+def test_table_kernel_widths_4_and_8_cell_by_cell(pkg, orc, mode, gaps, width):
+    """every batch of test_table_kernel_cell_by_cell holds a reference beyond 512 columns and so runs 16 columns per lane"""
+    rng = np.random.default_rng(9600 + 100 * width + mode * 10 + gaps[0])
+    pm, om = pkg.Matrix.create(b"ACGT", 2, -3), orc.Matrix.create("ACGT", 2, -3)
+    qs, rs = _width_batch(rng, width)
+    for sg in ((15,) if mode != 1 else (15, 0, 1 | 8, 2 | 4, 2)):
+        cfg = pkg.pmx_config_t(mode, sg, gaps[0], gaps[1], 32, 0, pm.inner)
+        _check_width_batch(pkg, orc, cfg, om, qs, rs, (width, mode, sg, gaps))
+
+
+@pytest.mark.parametrize("width", [4, 8])
+def test_table_kernel_widths_4_and_8_blosum62(pkg, orc, width):
+    rng = np.random.default_rng(9700 + width)
+    pm, om = pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
+    qs, rs = _width_batch(rng, width, AA)
+    for mode in (0, 1, 2):
+        cfg = pkg.pmx_config_t(mode, 15, 11, 1, 32, 0, pm.inner)
+        _check_width_batch(pkg, orc, cfg, om, qs, rs, (width, mode, "blosum62"))
+
+
+@pytest.mark.parametrize("shape", [(150, 150), (100, 400)])
+def test_single_pair_table_at_widths_4_and_8(pkg, orc, shape):
+    """Aligner::use_table / use_last_rowcol on one pair whose reference fits 4 / 8 columns per lane"""
+    rng = np.random.default_rng(9800 + shape[1])
+    pm, om = pkg.Matrix.create(b"ACGT", 3, -2), orc.Matrix.create("ACGT", 3, -2)
+    q = random_seqs(rng, 1, shape[0], shape[0])[0]
+    r = (mutate(rng, q, 0.1, 0.03) + random_seqs(rng, 1, shape[1], shape[1])[0])[:shape[1]]
+    for sel, mode in (("global_", 0), ("semi_global", 1), ("local", 2)):
+        b = pkg.Aligner.new().matrix(pm).gap_open(4).gap_extend(1).use_table(); getattr(b, sel)()
+        res = b.build().align(q, r)
+        assert pkg.lib.pmx_last_kernel().decode() == "pmx_table_kernel"
+        w = orc.align(mode, q, r, 4, 1, om, table=True, rowcol=True)
+        t = res.get_score_table()
+        assert (t.rows(), t.cols()) == shape and (np.array(t.as_slice()).reshape(shape) == w.score_table).all()
+        assert (res.get_score(), res.get_end_query(), res.get_end_ref()) == (w.score, w.end_query, w.end_ref)
+        b = pkg.Aligner.new().matrix(pm).gap_open(4).gap_extend(1).use_last_rowcol(); getattr(b, sel)()
+        res = b.build().align(q, r)
+        assert pkg.lib.pmx_last_kernel().decode() == "pmx_table_kernel"
+        assert (np.array(res.get_score_row()) == w.score_row).all() and (np.array(res.get_score_col()) == w.score_col).all()
+
+
 @pytest.mark.parametrize("chunk_bytes", [None, "1", "71000", "142000"])
 def test_table_batches_beyond_the_table_kernel_in_chunks(pkg, orc, monkeypatch, chunk_bytes):
     """References beyond the row-by-row kernel's 1 024 columns: the general kernel, in chunks of bounded scratch.  Chunks of

@@ -36,6 +36,50 @@ def test_reference_select_cuts_inside_the_tie_run():
     assert search_ref.select(scores, 2, 0, search_ref.BY_SCORE)[0].tolist() == [1, 4, 0, 2, 3, 6, 7]
 
 
+def _wide_thresholds(scores):
+    """the minimum, a median value, and one above the maximum (the maximum itself where that is INT32_MAX: no threshold lies above)"""
+    values = np.unique(scores)
+    return (int(values[0]), int(values[len(values) // 2]), min(int(values[-1]) + 1, search_ref.INT32_MAX))
+
+
+@pytest.mark.parametrize("name", sorted(search_ref.WIDE_SCORES))
+def test_radix_select_model_equals_the_reference(name):
+    """the three narrowing passes of the device's select, restated in numpy, choose what select() chooses on every generator of wide
+    scores -- and the generators spread over the digits they are named for"""
+    rng = np.random.default_rng(4200)
+    for n in (1, 2, 257, 2049, 20011):
+        scores = search_ref.WIDE_SCORES[name](rng, n)
+        assert scores.dtype == np.int32
+        u = (scores.astype(np.int64) & 0xFFFFFFFF) ^ 0x80000000
+        bins = [len(np.unique((u >> shift) & ((1 << bits) - 1))) for shift, bits in search_ref.DIGITS]
+        if n >= 2049:
+            spread = {"full-range": (1000, 1000, 500), "top-digit": (30, 1, 1), "middle-digit": (1, 30, 1), "low-digit": (1, 1, 30),
+                      "clusters": (6, 4, 3)}[name]
+            assert all(b >= w for b, w in zip(bins, spread)) and (name in ("full-range", "clusters") or sorted(bins)[:2] == [1, 1])
+        for min_score in _wide_thresholds(scores):
+            npass = int((scores >= min_score).sum())
+            s = np.sort(scores[scores >= min_score])[::-1]
+            inside = int((s > s[len(s) // 2]).sum()) + int((s == s[len(s) // 2]).sum()) // 2 if npass else 0
+            for max_hits in sorted({0, 1, inside, max(npass - 1, 0), npass, npass + 1}):
+                want, wp = search_ref.select(scores, min_score, max_hits, search_ref.BY_INDEX)
+                T, above, E = search_ref.radix_select_model(scores, min_score, max_hits)
+                ctx = (name, n, min_score, max_hits)
+                assert search_ref.model_selection(scores, min_score, max_hits).tolist() == want.tolist(), ctx
+                if T is None:
+                    assert (max_hits == 0 or npass <= max_hits) and above == npass == wp and E == 0, ctx
+                else:
+                    assert npass > max_hits and T == s[max_hits - 1] and above == int((scores > T).sum()) and above + E == max_hits, ctx
+                    assert 1 <= E <= int((scores == T).sum()), ctx
+
+
+def test_radix_select_model_takes_bin_0():
+    """the K-th score in bin 0 of the first pass (a biased key below 2^21) and in bin 0 of the second: the pick loop falls through"""
+    for scores, k in ((search_ref.bin0_scores("top"), 900), (search_ref.bin0_scores("middle"), 900)):
+        T, above, E = search_ref.radix_select_model(scores, search_ref.INT32_MIN, k)
+        want, _ = search_ref.select(scores, search_ref.INT32_MIN, k, search_ref.BY_INDEX)
+        assert search_ref.model_selection(scores, search_ref.INT32_MIN, k).tolist() == want.tolist() and above + E == k
+
+
 def _header_struct(name):
     text = open(os.path.join(ROOT, "include", "parasail_amd.h")).read()
     m = re.search(r"typedef struct %s \{(.*?)\} %s_t;" % (name, name), text, flags=re.S)

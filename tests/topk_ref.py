@@ -24,15 +24,25 @@ def row_cut(scores, k, min_score=INT32_MIN, skip=None):
 def topk(records, nr, q_first, nq, k, min_score=INT32_MIN, skip_self=False, stats=None, capacity=None):
     """records: int32 [nq * nr, 4] of the full entry on pairs [q_first * nr, (q_first + nq) * nr) of the rectangle.  -> dict: row_off
     (nq + 1, in full), row_passing, counts [kept, written, passing] and index (absolute p), pairs, records, stats of the hits written
-    (the first `capacity` in CSR order)."""
+    (the first `capacity` in CSR order).  row_cut() on every row at once: one sort of the passing records by (row, score descending, j
+    ascending), then the first k of every row (tests/test_topk_records_args.py holds the two against each other)."""
     records = np.asarray(records).reshape(nq * nr, 4)
-    keep, row_off, row_passing = [], [0], []
-    for li in range(nq):
-        j, passing = row_cut(records[li * nr:(li + 1) * nr, 0], k, min_score, q_first + li if skip_self else None)
-        keep.extend((li * nr + j).tolist())
-        row_off.append(len(keep))
-        row_passing.append(passing)
-    keep = np.array(keep, dtype=np.int64)
+    s = records[:, 0].astype(np.int64)
+    ok = s >= int(min_score)
+    if skip_self:
+        rows = np.arange(nq, dtype=np.int64)
+        own = rows[(q_first + rows >= 0) & (q_first + rows < nr)]
+        ok[own * nr + q_first + own] = False
+    p = np.nonzero(ok)[0]                                               # local positions li * nr + j of the candidates
+    li, j = p // max(nr, 1), p % max(nr, 1)
+    p = p[np.lexsort((j, -s[p], li))]                                   # (last key first)
+    row_passing = np.bincount(li, minlength=nq).astype(np.int64)[:nq]
+    start = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum(row_passing, out=start[1:])
+    rank = np.arange(len(p), dtype=np.int64) - np.repeat(start[:-1], row_passing)
+    keep = p[rank < k]
+    row_off = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum(np.minimum(row_passing, k), out=row_off[1:])
     kept = len(keep)
     if capacity is not None:
         keep = keep[:capacity]
@@ -41,9 +51,21 @@ def topk(records, nr, q_first, nq, k, min_score=INT32_MIN, skip_self=False, stat
     pairs["q"], pairs["r"] = index // max(nr, 1), index % max(nr, 1)
     pairs["q_len"] = -1
     pairs["r_len"] = -1
-    return {"row_off": np.array(row_off, dtype=np.int64), "row_passing": np.array(row_passing, dtype=np.int64),
-            "counts": [kept, len(keep), int(sum(row_passing))], "index": index, "pairs": pairs, "records": records[keep],
+    return {"row_off": row_off, "row_passing": row_passing,
+            "counts": [kept, len(keep), int(row_passing.sum())], "index": index, "pairs": pairs, "records": records[keep],
             "stats": stats[keep] if stats is not None else None}
+
+
+def topk_by_rows(records, nr, q_first, nq, k, min_score=INT32_MIN, skip_self=False):
+    """topk() row by row through row_cut(): -> (local positions kept, row_off, row_passing)"""
+    records = np.asarray(records).reshape(nq * nr, 4)
+    keep, row_off, row_passing = [], [0], []
+    for li in range(nq):
+        j, passing = row_cut(records[li * nr:(li + 1) * nr, 0], k, min_score, q_first + li if skip_self else None)
+        keep.extend((li * nr + j).tolist())
+        row_off.append(len(keep))
+        row_passing.append(passing)
+    return keep, row_off, row_passing
 
 
 def chunked_rows(scores, nr, k, chunk, min_score=INT32_MIN, skip_self=False, q_first=0):
