@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 from tests.pssm_oracle import check, encode
-from tests.util import AA, B62_LETTERS, consensus_pssm, golden, mutate, random_seqs
+from tests.util import AA, B62_LETTERS, consensus_pssm, edge_lengths, families, golden, longest_by_launch, mutate, random_seqs, tile, window_hint
 
 pytestmark = pytest.mark.gpu
 
@@ -51,38 +51,12 @@ def _hook(pkg, qlen, rlen, msize, smin, smax, open_, ext, rows=0):
 
 
 def _hint(pkg, qlen, msize, smin, smax, open_, ext):
-    """the window hook's longest reference: where the search by launching looks first"""
-    lo, hi = 0, 30000
-    while hi - lo > 0:
-        mid = (lo + hi + 1) // 2
-        lo, hi = (mid, hi) if _hook(pkg, qlen, mid, msize, smin, smax, open_, ext) else (lo, mid - 1)
-    return lo
+    """the window hook's longest reference (row-offset form): where the search by launching looks first"""
+    return window_hint(pkg, qlen, msize, smin, smax, open_, ext, rowx=1)
 
 
-def _longest_by_launch(fast, hint=0):
-    """The longest reference for which fast(rlen) holds -- a launch, pmx_last_kernel() tells whether the packed kernel ran.  The
-    hook's answer is tried first (two launches when it is right: taken at `hint`, not taken one beyond); bisection otherwise.
-    A kernel that is never taken is a failure, not a skip."""
-    assert fast(1), "the packed kernel did not take a reference of one letter"
-    if hint >= 1 and fast(hint) and not fast(hint + 1):
-        return hint
-    lo, hi = 1, 30001                                                # (no packed kernel takes more than 30 000 columns)
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if fast(mid) else (lo, mid)
-    return lo
-
-
-def _families(rng, q, rlen, alphabet=AA, hot=b"W", cold=b"*"):
-    """the references that stretch the value range for query q: the hottest letter throughout (poly-W against poly-W when q is),
-    q repeated, q behind a long unrelated prefix, q in front of a long suffix, the coldest letter throughout, random"""
-    far = random_seqs(rng, 1, rlen, rlen, alphabet)[0]
-    return [hot * rlen, (q * (rlen // len(q) + 1))[:rlen], far[:rlen - len(q)] + q if rlen > len(q) else far,
-            q + far[:rlen - len(q)] if rlen > len(q) else far, cold * rlen, far]
-
-
-def _tile(seqs, n):
-    return [seqs[i % len(seqs)] for i in range(n)]
+# (shared with tests/test_gpu_stats_window_edges.py: they live in tests/util.py)
+_longest_by_launch, _families, _tile = longest_by_launch, families, tile
 
 
 def _records(got):
@@ -105,8 +79,7 @@ def _b62(pkg, orc):
     return pkg.Matrix.from_name("blosum62"), orc.Matrix.from_file(golden("blosum62.txt"))
 
 
-def _lengths(longest):
-    return [longest, max(1, longest - 1), max(1, longest // 2)]
+_lengths = edge_lengths
 
 
 # ------------------------------------------------------------------------------------------------------------- A: scores ----

@@ -78,3 +78,47 @@ def consensus_pssm(rng, L, top, bottom, lo=-6, hi=9, by_letter=None):
     vals[np.arange(L), cons] = top
     vals[:, 23] = bottom
     return vals, bytes(B62_LETTERS[c] for c in cons), square
+
+
+# ---- the edges of a packed kernel's host-side proof, found by launching (tests/test_gpu_nwsg_proof_edges.py, test_gpu_stats_window_edges.py) ----
+def window_hint(pkg, qlen, msize, smin, smax, open_, ext, rowx=1, rows=0):
+    """the longest reference the window hook (pmx_window_nwsgv) admits: where the search by launching looks first"""
+    import ctypes as C
+    pkg.lib.pmx_window_nwsgv.restype = C.c_int
+    lo, hi = 0, 30000
+    while hi - lo > 0:
+        mid = (lo + hi + 1) // 2
+        ok = pkg.lib.pmx_window_nwsgv(int(qlen), int(mid), int(msize), int(smin), int(smax), int(open_), int(ext), int(rowx), int(rows))
+        lo, hi = (mid, hi) if ok else (lo, mid - 1)
+    return lo
+
+
+def longest_by_launch(fast, hint=0):
+    """The longest reference for which fast(rlen) holds -- a launch, pmx_last_kernel() tells whether the packed kernel ran.  The
+    hint is tried first (two launches when it is right: taken at `hint`, not taken one beyond); bisection otherwise.
+    A kernel that is never taken is a failure, not a skip."""
+    assert fast(1), "the packed kernel did not take a reference of one letter"
+    if hint >= 1 and fast(hint) and not fast(hint + 1):
+        return hint
+    lo, hi = 1, 30001                                                # (no packed kernel takes more than 30 000 columns)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fast(mid) else (lo, mid)
+    return lo
+
+
+def families(rng, q, rlen, alphabet=AA, hot=b"W", cold=b"*"):
+    """the references that stretch the value range for query q: the hottest letter throughout (poly-W against poly-W when q is),
+    q repeated, q behind a long unrelated prefix, q in front of a long suffix, the coldest letter throughout, random"""
+    far = random_seqs(rng, 1, rlen, rlen, alphabet)[0]
+    return [hot * rlen, (q * (rlen // len(q) + 1))[:rlen], far[:rlen - len(q)] + q if rlen > len(q) else far,
+            q + far[:rlen - len(q)] if rlen > len(q) else far, cold * rlen, far]
+
+
+def tile(seqs, n):
+    return [seqs[i % len(seqs)] for i in range(n)]
+
+
+def edge_lengths(longest):
+    """the longest reference a kernel takes, one short of it, half of it"""
+    return [longest, max(1, longest - 1), max(1, longest // 2)]
