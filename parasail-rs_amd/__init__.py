@@ -1014,27 +1014,12 @@ class Aligner:
             if count is None:
                 count = rect_pairs_count(len(Q), len(R)) - int(first)
         opts = pmx_pair_search_opts_t(int(min_score), shape, int(max_hits), int(chunk_pairs), int(slice_pairs))
+        args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
+                pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts))
         mode = _strand_mode(strand)
         if mode != STRAND_FORWARD:
-            res = C.POINTER(pmx_strand_hits_t)()
-            rc = lib.pmx_search_pairs_stranded(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
-                                               pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts), mode,
-                                               C.byref(res))
-            if rc:
-                raise BatchError(lib.pmx_last_error().decode())
-            try:
-                return PairHits(res.contents)
-            finally:
-                lib.pmx_strand_hits_free(res)
-        res = C.POINTER(pmx_pair_hits_t)()
-        rc = lib.pmx_search_pairs(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
-                                  pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts), C.byref(res))
-        if rc:
-            raise BatchError(lib.pmx_last_error().decode())
-        try:
-            return PairHits(res.contents)
-        finally:
-            lib.pmx_pair_hits_free(res)
+            return _hits_call(lib.pmx_search_pairs_stranded, args + (mode,), pmx_strand_hits_t, PairHits, lib.pmx_strand_hits_free)
+        return _hits_call(lib.pmx_search_pairs, args, pmx_pair_hits_t, PairHits, lib.pmx_pair_hits_free)
 
     def search_topk(self, Q, R=None, k=10, min_score=INT32_MIN, skip_self=False, first_row=0, rows=None, stats=False, chunk_pairs=0,
                     slice_rows=0, strand=0):
@@ -1051,26 +1036,11 @@ class Aligner:
         if rows is None:
             rows = len(Q) - int(first_row)
         opts = pmx_topk_opts_t(int(min_score), int(k), 1 if skip_self else 0, int(chunk_pairs), int(slice_rows))
+        args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows), C.byref(opts))
         mode = _strand_mode(strand)
         if mode != STRAND_FORWARD:
-            res = C.POINTER(pmx_topk_strand_hits_t)()
-            rc = lib.pmx_search_topk_stranded(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows),
-                                              C.byref(opts), mode, C.byref(res))
-            if rc:
-                raise BatchError(lib.pmx_last_error().decode())
-            try:
-                return TopKHits(res.contents)
-            finally:
-                lib.pmx_topk_strand_hits_free(res)
-        res = C.POINTER(pmx_topk_hits_t)()
-        rc = lib.pmx_search_topk(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows),
-                                 C.byref(opts), C.byref(res))
-        if rc:
-            raise BatchError(lib.pmx_last_error().decode())
-        try:
-            return TopKHits(res.contents)
-        finally:
-            lib.pmx_topk_hits_free(res)
+            return _hits_call(lib.pmx_search_topk_stranded, args + (mode,), pmx_topk_strand_hits_t, TopKHits, lib.pmx_topk_strand_hits_free)
+        return _hits_call(lib.pmx_search_topk, args, pmx_topk_hits_t, TopKHits, lib.pmx_topk_hits_free)
 
     def align_batch_2bit(self, q2, qoff, r2, roff, out=None):
         """2-bit packed input (see pack_2bit): offsets count bases.  `out` as in align_batch_packed."""
@@ -1272,6 +1242,17 @@ def _strand_mode(strand):
             raise BatchError("strand is 0, 1 or \"both\"")
         return names[strand]
     return int(strand)
+
+
+def _hits_call(entry, args, block_t, wrap, free):
+    """entry(*args, &block) of the host search entries: BatchError on failure, else wrap(block) with the block released."""
+    res = C.POINTER(block_t)()
+    if entry(*args, C.byref(res)):
+        raise BatchError(lib.pmx_last_error().decode())
+    try:
+        return wrap(res.contents)
+    finally:
+        free(res)
 
 
 class PairHits:

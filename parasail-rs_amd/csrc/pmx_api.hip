@@ -1373,10 +1373,10 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_SRCH = 18, SCR_GREF = 19,                                                     // profile search: hit list / diagonals / lengths / offsets / begins; gathered references
        SCR_PAIRS = 20, SCR_PGEN = 21,                                                    // set batches: two sets of chunk buffers (pmx_pairs.hip); enumerated descriptors
        SCR_PUP = 22, SCR_PREC = 23, SCR_PST = 24,                                        // set batches, host entries: uploaded descriptors, records, statistics
-       SCR_PSRCH = 25,                                                                   // set search: a chunk's records, statistics, hit positions, counts and select scratch
-       SCR_PHIT = 26,                                                                    // set search, host entry: a slice's hit arrays, counts, first bad pair
-       SCR_PTOPK = 27,                                                                   // per-query top-K: a chunk's records and statistics, tile survivors, the rows' running state, scan scratch
-       SCR_PTHIT = 28,                                                                   // per-query top-K, host entry: a slice's CSR arrays, counts, first bad pair
+       SCR_PSRCH = 25,                                                                   // set search: a chunk's records and statistics (ChunkAlign: with a chosen strand its slots' too), hit positions, counts, select scratch
+       SCR_PHIT = 26,                                                                    // set search, host entry: a slice's hit columns (HitCols), counts, first bad pair
+       SCR_PTOPK = 27,                                                                   // per-query top-K: a chunk's records and statistics (ChunkAlign), tile survivors, the rows' running state, scan scratch
+       SCR_PTHIT = 28,                                                                   // per-query top-K, host entry: a slice's hit columns (HitCols) and row arrays, counts, first bad pair
        SCR_SLOTS = 29 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
@@ -1506,15 +1506,15 @@ static int64_t chunk_pairs(int64_t n, double trace_bytes, double budget, int64_t
     return chunk > n ? n : chunk;
 }
 
-// Typed arrays carved out of one block, each starting on a 256-byte boundary (the block's base is one: hipMalloc).  The same
-// sequence of take() calls runs twice -- over no block for the size, then over the reserved block -- so size and layout cannot
-// disagree.
+// Typed arrays carved out of one block, each starting on a 256-byte boundary (the block's base is one: hipMalloc; align: another
+// power of two for a host block).  The same sequence of take() calls runs twice -- over no block for the size, then over the reserved
+// block -- so size and layout cannot disagree.
 struct Carver {
-    unsigned char *base = nullptr; size_t used = 0;
+    unsigned char *base = nullptr; size_t used = 0, align = 256;
     template <typename T> T *take(size_t count)
     {
         T *p = base ? (T *)(base + used) : nullptr;
-        used = (used + count * sizeof(T) + 255) & ~(size_t)255;
+        used = (used + count * sizeof(T) + align - 1) & ~(align - 1);
         return p;
     }
 };
@@ -4091,6 +4091,56 @@ static int device_maxlens(const pmx_seqset *Q, const pmx_seqset *R, const pmx_pa
     return 0;
 }
 
+// The lengths an enumerated window -- pairs [first, first + n) of shape PMX_PAIRS_TRIANGLE (R == Q) / PMX_PAIRS_RECT, whole sequences --
+// is run with, both ways the enumerating host entries (pmx_align_all_pairs, pmx_search_pairs, pmx_search_topk) find them.
+// Sets with host offsets: the longest query and reference (at most 2^31 - 1) and the shortest reference (at least 1) of the whole sets.
+// When some sequence cannot be a whole-sequence window, the window is walked row by row for the first pair that touches one -- the query
+// before the reference, the row's first such column -- and that pair, numbered from `first`, is the call's failure.
+struct SetLens { int32_t mq = 1, mr = 1, mnr = INT32_MAX; };           // (as created: wrapped sets before the device pass; with_sort_hint sees nothing to sort by)
+static int window_host_lens(const pmx_seqset *Q, const pmx_seqset *R, int shape, int64_t first, int64_t n, SetLens *m)
+{
+    std::vector<int64_t> oddq, oddr; int64_t mq = 1, mnq = INT32_MAX, mr = 1, mnr = INT32_MAX;
+    // a set's extreme lengths; odd: the sequences that cannot be whole-sequence windows (empty, or beyond 2^31 - 1), ascending
+    auto lengths = [](const pmx_seqset *S, int64_t *mx, int64_t *mn, std::vector<int64_t> *odd) {
+        for (int64_t k = 0; k < S->count; ++k) {
+            const int64_t l = S->h_off[k + 1] - S->h_off[k];
+            if (l < 1 || l > INT32_MAX) odd->push_back(k);
+            *mx = l > *mx ? l : *mx; *mn = l < *mn ? l : *mn;
+        }
+    };
+    try {
+        lengths(Q, &mq, &mnq, &oddq);
+        if (R != Q) lengths(R, &mr, &mnr, &oddr); else { mr = mq; mnr = mnq; oddr = oddq; }
+    } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+    m->mq = (int32_t)std::min<int64_t>(mq, INT32_MAX); m->mr = (int32_t)std::min<int64_t>(mr, INT32_MAX); m->mnr = (int32_t)std::max<int64_t>(mnr, 1);
+    if (oddq.empty() && oddr.empty()) return 0;
+    const bool tri = shape == PMX_PAIRS_TRIANGLE;
+    int64_t i = tri ? 0 : first / R->count, j = tri ? 0 : first - i * R->count, l = 0;
+    if (tri) (void)pmx_all_pairs_index(Q->count, first, &i, &j);
+    for (int64_t p = first, end = first + n; p < end; ++i, j = tri ? i + 1 : 0) {
+        const int64_t jb = std::min<int64_t>(R->count, j + (end - p));      // columns [j, jb) of row i are pairs [p, p + jb - j)
+        const char *what = host_resolve_side(Q->h_off, Q->count, i, 0, -1, &l);
+        const char *side = "query";
+        int64_t jbad = j;
+        if (!what) {
+            const auto it = std::lower_bound(oddr.begin(), oddr.end(), j);
+            if (it != oddr.end() && *it < jb) { jbad = *it; what = host_resolve_side(R->h_off, R->count, jbad, 0, -1, &l); side = "reference"; }
+        }
+        if (what) { set_err("pair %lld (%lld, %lld): %s: %s", (long long)(p + (jbad - j) - first), (long long)i, (long long)jbad, side, what); return -1; }
+        p += jb - j;
+    }
+    return 0;
+}
+// Wrapped sets: the longest sequence of either set, found on the device, and what a PSSM refuses about it.
+static int window_device_lens(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, SetLens *m, hipStream_t st)
+{
+    int32_t unused = 0;
+    if (device_maxlens(Q, Q, nullptr, Q->count, &m->mq, &unused, st)) return -1;
+    m->mr = m->mq;
+    if (R != Q && device_maxlens(R, R, nullptr, R->count, &m->mr, &unused, st)) return -1;
+    return pssm_batch_check(cfg->matrix, m->mq, m->mq);
+}
+
 // Device records (and statistics) back to the host; a flagged record -- a set without host offsets was validated on the device -- is
 // the call's failure.
 static int pairs_copy_back(int64_t n, const pmx_record_t *drec, const pmx_stats_t *dst, pmx_record_t *out, pmx_stats_t *stats_out, bool scan_flags, hipStream_t st)
@@ -4241,42 +4291,19 @@ extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *
     if (check_cfg(cfg)) return -1;
     if (count == 0) return 0;
     const bool host_offsets = !S->h_off.empty();
-    int64_t mx = 1, mn = INT32_MAX;
-    if (host_offsets) {
-        int64_t empty = -1;                       // the first sequence that cannot be a whole-sequence window
-        for (int64_t k = 0; k < S->count; ++k) {
-            const int64_t l = S->h_off[k + 1] - S->h_off[k];
-            if ((l < 1 || l > INT32_MAX) && empty < 0) empty = k;
-            mx = l > mx ? l : mx; mn = l < mn ? l : mn;
-        }
-        if (empty >= 0) {                         // (rare: walk the window for the first pair that touches such a sequence)
-            if (mx > INT32_MAX) mx = INT32_MAX;
-            for (int64_t p = first; p < first + count; ++p) {
-                int64_t i = 0, j = 0, l = 0;
-                (void)pmx_all_pairs_index(S->count, p, &i, &j);
-                const char *what = host_resolve_side(S->h_off, S->count, i, 0, -1, &l);
-                const char *side = "query";
-                if (!what) { what = host_resolve_side(S->h_off, S->count, j, 0, -1, &l); side = "reference"; }
-                if (what) { set_err("pair %lld (%lld, %lld): %s: %s", (long long)(p - first), (long long)i, (long long)j, side, what); return -1; }
-            }
-        }
-    }
+    SetLens m;
+    if (host_offsets && window_host_lens(S, S, PMX_PAIRS_TRIANGLE, first, count, &m)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (pairs_check(cfg, S, S, opts, (int32_t)mx, (int32_t)mx, stats_out != nullptr)) return -1;
+    if (pairs_check(cfg, S, S, opts, m.mq, m.mq, stats_out != nullptr)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
     pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
     if (scratch_reserve(sizeof(pmx_record_t) * (size_t)count, (void **)&drec, SCR_PREC) ||
         (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)count, (void **)&dst, SCR_PST))) return -1;
-    int32_t m32 = (int32_t)mx, unused = 0;
-    pmx_config_t cfg_s = *cfg;
-    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)(mn < 1 ? 1 : mn), m32, count);
-    else {
-        if (device_maxlens(S, S, nullptr, S->count, &m32, &unused, st)) return -1;
-        if (pssm_batch_check(cfg->matrix, m32, m32)) return -1;
-    }
-    const int rc = pairs_run_scores(&cfg_s, S, S, count, nullptr, first, nullptr, m32, m32, drec, dst, st, pairs_chunk(count, m32, m32, opts));
+    const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mq, count);      // (wrapped sets: no host lengths yet, and no hint from them)
+    if (!host_offsets && window_device_lens(cfg, S, S, &m, st)) return -1;
+    const int rc = pairs_run_scores(&cfg_s, S, S, count, nullptr, first, nullptr, m.mq, m.mq, drec, dst, st, pairs_chunk(count, m.mq, m.mq, opts));
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     return pairs_copy_back(count, drec, dst, out, stats_out, !host_offsets, st);
 }
@@ -4348,49 +4375,74 @@ static int search_pairs_want_check(const pmx_config_t *cfg, bool stats_buffer)
     return 0;
 }
 
+// The five columns of a hit list, on the device or in a host block: descriptor, absolute index, record, statistics and strand byte
+// (nullptr: a column the call does not keep).
+struct HitCols {
+    pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; uint8_t *strand;
+    void carve(Carver &c, size_t n, bool with_stats, bool with_strand)
+    {
+        pairs = c.take<pmx_pair_t>(n); index = c.take<int64_t>(n); recs = c.take<pmx_record_t>(n);
+        stats = with_stats ? c.take<pmx_stats_t>(n) : nullptr;
+        strand = with_strand ? c.take<uint8_t>(n) : nullptr;
+    }
+};
+
 // The outputs of one run, all device pointers: counts[0] = passing, counts[1] = written; first_bad (host entry over wrapped sets, else
 // nullptr) keeps the lowest absolute index of a bad pair.
-struct PairHitBufs { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *counts, *first_bad; uint8_t *strand = nullptr; };
+struct PairHitBufs { HitCols hit; int64_t capacity; int64_t *counts, *first_bad; };
+
+// A chunk's alignment for the entries that keep its records in scratch (set search, top-K): the records (and statistics) of the chunk's
+// pairs and, when the entry chooses the strand, those of its alignment slots before the fold and the folded validity bytes.
+struct ChunkAlign {
+    bool stats, chosen; int per;
+    pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr; uint8_t *okf = nullptr;
+    ChunkAlign(const pmx_config_t *cfg, int strand_mode)
+        : stats((cfg->want & PMX_WANT_STATS) != 0), chosen(strand_mode != PMX_STRAND_FORWARD), per(strand_slots(strand_mode)) {}
+    void carve(Carver &c, int64_t chunk)
+    {
+        crec = c.take<pmx_record_t>((size_t)chunk);
+        cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
+        if (!chosen) return;                                    // the slots' records before the fold, the folded validity bytes
+        srec = c.take<pmx_record_t>((size_t)chunk * per);
+        sst = stats ? c.take<pmx_stats_t>((size_t)chunk * per) : nullptr;
+        okf = c.take<uint8_t>((size_t)chunk);
+    }
+    // The cn pairs of b into crec / cst: forward, the alignment and the bad pairs' fix-up; chosen strand, per * cn slots aligned and folded
+    // to cn records that carry their strand.  first_bad != nullptr: the lowest index of a bad pair, the chunk's first pair being p0.
+    int run(const pmx_config_t *cfg, const PairsChunkBufs &b, int64_t cn, int32_t max_qlen, int32_t max_rlen, int64_t p0, int64_t *first_bad,
+            hipStream_t st) const
+    {
+        int rc = run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, chosen ? srec : crec, chosen ? sst : cst, st);
+        if (rc) return rc;
+        rc = chosen ? pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
+                    : pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
+        if (!rc && first_bad) rc = pmx_launch_pairs_first_bad(chosen ? okf : b.ok, cn, p0, first_bad, st);
+        if (rc) set_err("bad-pair fix-up or strand fold of a chunk failed (%d)", rc);
+        return rc;
+    }
+};
 
 // n > 0 pairs behind the checks; asynchronous on `st`.  index0: the absolute number of the run's first pair (what d_hit_index counts from).
 static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int shape, int64_t first, int64_t n,
                             const pmx_pair_t *d_pairs, int64_t index0, int32_t max_qlen, int32_t max_rlen, int32_t min_score,
                             const PairHitBufs &o, hipStream_t st, int64_t chunk, int strand_mode = PMX_STRAND_FORWARD)
 {
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0, chosen = strand_mode != PMX_STRAND_FORWARD;
-    const int per = strand_slots(strand_mode);
-    pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr; int64_t *cidx = nullptr, *ccnt = nullptr; void *sel = nullptr;
-    uint8_t *okf = nullptr;
+    ChunkAlign A(cfg, strand_mode);
+    int64_t *cidx = nullptr, *ccnt = nullptr; void *sel = nullptr;
     const size_t sel_bytes = pmx_select_scratch_bytes(chunk, 0, PMX_HITS_BY_INDEX);
     if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
-            crec = c.take<pmx_record_t>((size_t)chunk);
-            cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
+            A.carve(c, chunk);
             cidx = c.take<int64_t>((size_t)chunk); ccnt = c.take<int64_t>(2);
             sel = c.take<unsigned char>(sel_bytes);
-            if (chosen) {                                       // the slots' records before the fold, the folded validity bytes
-                srec = c.take<pmx_record_t>((size_t)chunk * per);
-                sst = stats ? c.take<pmx_stats_t>((size_t)chunk * per) : nullptr;
-                okf = c.take<uint8_t>((size_t)chunk);
-            }
         })) return -1;
     HIP_OR_RET(hipMemsetAsync(o.counts, 0, 2 * sizeof(int64_t), st));
     return pairs_run(Q, R, n, d_pairs, first, shape, nullptr, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = 0;
-            if (chosen) {                                       // per * cn slots aligned, folded to cn records that carry their strand
-                rc = run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, srec, sst, st);
-                if (rc) return rc;
-                rc = pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st);
-                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(okf, cn, index0 + c0, o.first_bad, st);
-            } else {
-                rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
-                if (rc) return rc;
-                rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
-                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, index0 + c0, o.first_bad, st);
-            }
-            if (!rc) rc = pmx_launch_select(crec, cn, min_score, 0, PMX_HITS_BY_INDEX, cidx, cn, ccnt, sel, st);
-            if (!rc) rc = pmx_launch_pairs_append_hits(cidx, ccnt, cn, o.capacity, index0 + c0, b.pairs, crec, cst,
-                                                       o.pairs, o.index, o.recs, o.stats, o.counts, st, o.strand, chosen ? 1 : 0);
+            int rc = A.run(cfg, b, cn, max_qlen, max_rlen, index0 + c0, o.first_bad, st);
+            if (rc) return rc;
+            rc = pmx_launch_select(A.crec, cn, min_score, 0, PMX_HITS_BY_INDEX, cidx, cn, ccnt, sel, st);
+            if (!rc) rc = pmx_launch_pairs_append_hits(cidx, ccnt, cn, o.capacity, index0 + c0, b.pairs, A.crec, A.cst,
+                                                       o.hit.pairs, o.hit.index, o.hit.recs, o.hit.stats, o.counts, st, o.hit.strand, A.chosen ? 1 : 0);
             if (rc) { set_err("hit compaction of a chunk failed (%d)", rc); return rc; }
             return 0;
         }, strand_mode);
@@ -4416,7 +4468,7 @@ static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    const PairHitBufs o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_counts, nullptr, d_hit_strand};
+    const PairHitBufs o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_counts, nullptr};
     return search_pairs_run(cfg, Q, R, shape, first, n, d_pairs, first, max_qlen, max_rlen, min_score, o, (hipStream_t)stream,
                             pairs_chunk(n, max_qlen, max_rlen, opts, strand_slots(strand_mode)), strand_mode);
 }
@@ -4444,15 +4496,50 @@ extern "C" int pmx_search_pairs_stranded_device(const pmx_config_t *cfg, const p
 
 extern "C" void pmx_pair_hits_free(pmx_pair_hits_t *hits) { free(hits); }
 
-// The extreme lengths of a set's sequences; *odd: some sequence cannot be a whole-sequence window (empty, or beyond 2^31 - 1).
-static void seqset_host_lengths(const pmx_seqset *S, int64_t *mx, int64_t *mn, bool *odd)
-{
-    for (int64_t k = 0; k < S->count; ++k) {
-        const int64_t l = S->h_off[k + 1] - S->h_off[k];
-        if (l < 1 || l > INT32_MAX) *odd = true;
-        *mx = l > *mx ? l : *mx; *mn = l < *mn ? l : *mn;
+// The host entries' hit stage: the hits of the slices so far, column by column, until the result block can be sized.
+struct HostHits {
+    std::vector<pmx_pair_t> pairs; std::vector<int64_t> index; std::vector<pmx_record_t> recs; std::vector<pmx_stats_t> stats; std::vector<uint8_t> strand;
+    std::vector<int64_t> row_off, row_passing;                  // top-K: rows + 1 and rows entries; a pair search has none
+    int64_t stored = 0, passing = 0;                            // hits held; pairs at or above min_score, held or not
+    // the first w hits of a slice's device columns (d.stats / d.strand nullptr: columns the call does not keep) behind those held
+    int append(const HitCols &d, int64_t w)
+    {
+        if (w <= 0) return 0;
+        const size_t at = (size_t)stored, n = at + (size_t)w;
+        try { pairs.resize(n); index.resize(n); recs.resize(n); if (d.stats) stats.resize(n); if (d.strand) strand.resize(n); }
+        catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
+        HIP_OR_RET(hipMemcpy(pairs.data() + at, d.pairs, sizeof(pmx_pair_t) * (size_t)w, hipMemcpyDeviceToHost));
+        HIP_OR_RET(hipMemcpy(index.data() + at, d.index, sizeof(int64_t) * (size_t)w, hipMemcpyDeviceToHost));
+        HIP_OR_RET(hipMemcpy(recs.data() + at, d.recs, sizeof(pmx_record_t) * (size_t)w, hipMemcpyDeviceToHost));
+        if (d.stats) HIP_OR_RET(hipMemcpy(stats.data() + at, d.stats, sizeof(pmx_stats_t) * (size_t)w, hipMemcpyDeviceToHost));
+        if (d.strand) HIP_OR_RET(hipMemcpy(strand.data() + at, d.strand, (size_t)w, hipMemcpyDeviceToHost));
+        stored += w;
+        return 0;
     }
-}
+    // The call's result, one zero-filled block released with free(): the header (its size: the result type's; the caller fills it), the
+    // row arrays if any, then the descriptors, indices, records, statistics (with_stats) and strand bytes (with_strand) of the hits held,
+    // each on a 16-byte boundary, and 16 spare bytes.  *c, *ro, *rp: where the arrays lie.  nullptr: out of memory.
+    void *block(size_t header, bool with_stats, bool with_strand, HitCols *c, int64_t **ro = nullptr, int64_t **rp = nullptr) const
+    {
+        Carver lay; lay.align = 16;
+        const size_t h = (size_t)stored, rows = row_passing.size();                 // (no rows: row_off may be empty, the block has its one zero)
+        for (int pass = 0; pass < 2; ++pass) {                    // (Carver's two passes: the size, then the block)
+            lay.used = 0;
+            (void)lay.take<char>(header);
+            if (ro) { *ro = lay.take<int64_t>(rows + 1); *rp = lay.take<int64_t>(rows); }
+            c->carve(lay, h, with_stats, with_strand);
+            if (!lay.base && !(lay.base = (unsigned char *)calloc(1, lay.used + 16))) { set_err("out of memory"); return nullptr; }
+        }
+        if (ro && rows) { memcpy(*ro, row_off.data(), sizeof(int64_t) * (rows + 1)); memcpy(*rp, row_passing.data(), sizeof(int64_t) * rows); }
+        if (h) {
+            memcpy(c->pairs, pairs.data(), sizeof(pmx_pair_t) * h); memcpy(c->index, index.data(), sizeof(int64_t) * h);
+            memcpy(c->recs, recs.data(), sizeof(pmx_record_t) * h);
+            if (with_stats) memcpy(c->stats, stats.data(), sizeof(pmx_stats_t) * h);
+            if (with_strand) memcpy(c->strand, strand.data(), h);
+        }
+        return lay.base;
+    }
+};
 
 // Both host entries.  with_strand (pmx_search_pairs_stranded): the block is a pmx_strand_hits_t -- the fields of pmx_pair_hits_t, then the
 // strand bytes -- and the slices' hit buffers hold one more byte per hit; without it the block and the kernels are pmx_search_pairs'.
@@ -4470,135 +4557,67 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
     if (search_pairs_want_check(cfg, stats) || strand_mode_check(cfg, strand_mode)) return -1;
+    HostHits hh;
     // the result: one block -- header, descriptors, indices, records, statistics (, strand bytes)
-    auto publish = [&](int64_t h, int64_t passing, pmx_pair_hits_t **out) -> int {
-        auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        const size_t o_pairs = up(with_strand ? sizeof(pmx_strand_hits_t) : sizeof(pmx_pair_hits_t)), o_index = o_pairs + up(sizeof(pmx_pair_t) * (size_t)h);
-        const size_t o_recs = o_index + up(sizeof(int64_t) * (size_t)h), o_stats = o_recs + up(sizeof(pmx_record_t) * (size_t)h);
-        const size_t o_strand = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0);
-        const size_t total = o_strand + (with_strand ? up((size_t)h) : 0) + 16;
-        char *blk = (char *)calloc(1, total);
-        if (!blk) { set_err("out of memory"); return -1; }
-        pmx_pair_hits_t *r = (pmx_pair_hits_t *)blk;
-        r->n_hits = h; r->n_passing = passing;
-        r->pairs = (pmx_pair_t *)(blk + o_pairs); r->index = (int64_t *)(blk + o_index); r->recs = (pmx_record_t *)(blk + o_recs);
-        r->stats = stats ? (pmx_stats_t *)(blk + o_stats) : nullptr;
-        if (with_strand) ((pmx_strand_hits_t *)blk)->strand = (uint8_t *)(blk + o_strand);
-        *out = r;
+    auto publish = [&]() -> int {
+        HitCols c;
+        pmx_pair_hits_t *r = (pmx_pair_hits_t *)hh.block(with_strand ? sizeof(pmx_strand_hits_t) : sizeof(pmx_pair_hits_t), stats, with_strand, &c);
+        if (!r) return -1;
+        r->n_hits = hh.stored; r->n_passing = hh.passing;
+        r->pairs = c.pairs; r->index = c.index; r->recs = c.recs; r->stats = c.stats;
+        if (with_strand) ((pmx_strand_hits_t *)r)->strand = c.strand;
+        *result = r;
         return 0;
     };
-    if (n == 0) return publish(0, 0, result);
+    if (n == 0) return publish();
     const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
-    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
+    SetLens m;
     if (host_offsets && listed) {
         const PairScan s = scan_pairs(Q, R, pairs, 0, n);
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
-        mq = s.mq; mr = s.mr; mnr = s.mnr;
-    } else if (host_offsets) {
-        bool odd = false; int64_t unused = INT32_MAX;
-        seqset_host_lengths(Q, &mq, &unused, &odd);
-        if (R != Q) seqset_host_lengths(R, &mr, &mnr, &odd); else { mr = mq; mnr = unused; }
-        if (odd) {                                // (rare) the first pair of the window that touches such a sequence, row by row
-            mq = mq > INT32_MAX ? INT32_MAX : mq; mr = mr > INT32_MAX ? INT32_MAX : mr;
-            std::vector<int64_t> oddr;              // the reference-side sequences that cannot be whole-sequence windows, ascending
-            try {
-                for (int64_t k = 0; k < R->count; ++k) {
-                    const int64_t l = R->h_off[k + 1] - R->h_off[k];
-                    if (l < 1 || l > INT32_MAX) oddr.push_back(k);
-                }
-            } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
-            const bool tri = shape == PMX_PAIRS_TRIANGLE;
-            int64_t i = tri ? 0 : first / R->count, j = tri ? 0 : first - i * R->count, l = 0;
-            if (tri) (void)pmx_all_pairs_index(Q->count, first, &i, &j);
-            for (int64_t p = first, end = first + n; p < end; ++i, j = tri ? i + 1 : 0) {
-                const int64_t jb = std::min<int64_t>(R->count, j + (end - p));      // columns [j, jb) of row i are pairs [p, p + jb - j)
-                const char *what = host_resolve_side(Q->h_off, Q->count, i, 0, -1, &l);
-                const char *side = "query";
-                int64_t jbad = j;
-                if (!what) {
-                    const auto it = std::lower_bound(oddr.begin(), oddr.end(), j);
-                    if (it != oddr.end() && *it < jb) { jbad = *it; what = host_resolve_side(R->h_off, R->count, jbad, 0, -1, &l); side = "reference"; }
-                }
-                if (what) { set_err("pair %lld (%lld, %lld): %s: %s", (long long)(p + (jbad - j) - first), (long long)i, (long long)jbad, side, what); return -1; }
-                p += jb - j;
-            }
-        }
-        if (mnr < 1) mnr = 1;
-    }
+        m.mq = (int32_t)s.mq; m.mr = (int32_t)s.mr; m.mnr = (int32_t)s.mnr;
+    } else if (host_offsets && window_host_lens(Q, R, shape, first, n, &m)) return -1;
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if (pairs_check(cfg, Q, R, &popts, (int32_t)mq, (int32_t)mr, stats)) return -1;
+    if (pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
     StreamGuard guard(st);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr, unused32 = 0;
-    pmx_config_t cfg_s = *cfg;
-    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
-    else if (!listed) {                           // wrapped sets: the longest sequence of either set, found on the device
-        if (device_maxlens(Q, Q, nullptr, Q->count, &q32, &unused32, st)) return -1;
-        r32 = q32;
-        if (R != Q && device_maxlens(R, R, nullptr, R->count, &r32, &unused32, st)) return -1;
-        if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
-    }
+    const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mr, n);          // (wrapped sets: no host lengths yet, and no hint from them)
+    if (!host_offsets && !listed && window_device_lens(cfg, Q, R, &m, st)) return -1;
     const int64_t slice = std::min<int64_t>(opts->slice_pairs > 0 ? opts->slice_pairs : (int64_t)1 << 24, n);
     const int64_t cap_buf = opts->max_hits > 0 ? std::min<int64_t>(slice, opts->max_hits) : slice;
-    pmx_pair_t *dhp = nullptr, *dp = nullptr; int64_t *dhi = nullptr, *dcnt = nullptr; pmx_record_t *dhr = nullptr; pmx_stats_t *dhs = nullptr;
-    uint8_t *dhb = nullptr;
+    HitCols d = {}; pmx_pair_t *dp = nullptr; int64_t *dcnt = nullptr;
     if (scratch_carve(SCR_PHIT, [&](Carver &c) {
-            dhp = c.take<pmx_pair_t>((size_t)cap_buf); dhi = c.take<int64_t>((size_t)cap_buf); dhr = c.take<pmx_record_t>((size_t)cap_buf);
-            dhs = stats ? c.take<pmx_stats_t>((size_t)cap_buf) : nullptr;
+            d.carve(c, (size_t)cap_buf, stats, with_strand);
             dcnt = c.take<int64_t>(3);                   // passing, written, first bad pair
-            dhb = with_strand ? c.take<uint8_t>((size_t)cap_buf) : nullptr;
         })) return -1;
     if (listed && scratch_reserve(sizeof(pmx_pair_t) * (size_t)slice, (void **)&dp, SCR_PUP)) return -1;
     if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 2, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
-    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs; std::vector<uint8_t> vb;
-    const int per = strand_slots(strand_mode);
-    int64_t stored = 0, passing = 0;
     for (int64_t s0 = 0; s0 < n; s0 += slice) {
         const int64_t sn = std::min<int64_t>(slice, n - s0);
-        const int64_t cap = opts->max_hits > 0 ? std::min<int64_t>(sn, opts->max_hits - stored) : sn;
+        const int64_t cap = opts->max_hits > 0 ? std::min<int64_t>(sn, opts->max_hits - hh.stored) : sn;
         if (listed) {
             HIP_OR_RET(hipMemcpyAsync(dp, pairs + s0, sizeof(pmx_pair_t) * (size_t)sn, hipMemcpyHostToDevice, st));
             if (!host_offsets) {
-                if (device_maxlens(Q, R, dp, sn, &q32, &r32, st)) return -1;
-                if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
+                if (device_maxlens(Q, R, dp, sn, &m.mq, &m.mr, st)) return -1;
+                if (pssm_batch_check(cfg->matrix, m.mq, m.mq)) return -1;
             }
         }
         const int64_t p0 = listed ? s0 : first + s0;     // the slice's first pair in the enumeration
-        const PairHitBufs o = {dhp, dhi, dhr, dhs, cap, dcnt, host_offsets ? nullptr : dcnt + 2, dhb};
+        const PairHitBufs o = {d, cap, dcnt, host_offsets ? nullptr : dcnt + 2};
         int64_t h[3] = {0, 0, 0};
-        int rc = search_pairs_run(&cfg_s, Q, R, shape, listed ? 0 : p0, sn, dp, p0, q32, r32, opts->min_score, o, st, pairs_chunk(sn, q32, r32, &popts, per), strand_mode);
+        int rc = search_pairs_run(&cfg_s, Q, R, shape, listed ? 0 : p0, sn, dp, p0, m.mq, m.mr, opts->min_score, o, st,
+                                  pairs_chunk(sn, m.mq, m.mr, &popts, strand_slots(strand_mode)), strand_mode);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
         if (!host_offsets && h[2] != -1) { set_err("pair %lld: bad descriptor (index, window or length)", (long long)(h[2] - (listed ? 0 : first))); return -1; }
-        passing += h[0];
-        const int64_t w = h[1];
-        if (w > 0) {
-            try {
-                vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w));
-                if (with_strand) vb.resize((size_t)(stored + w));
-            } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
-            HIP_OR_RET(hipMemcpy(vp.data() + stored, dhp, sizeof(pmx_pair_t) * (size_t)w, hipMemcpyDeviceToHost));
-            HIP_OR_RET(hipMemcpy(vi.data() + stored, dhi, sizeof(int64_t) * (size_t)w, hipMemcpyDeviceToHost));
-            HIP_OR_RET(hipMemcpy(vr.data() + stored, dhr, sizeof(pmx_record_t) * (size_t)w, hipMemcpyDeviceToHost));
-            if (stats) HIP_OR_RET(hipMemcpy(vs.data() + stored, dhs, sizeof(pmx_stats_t) * (size_t)w, hipMemcpyDeviceToHost));
-            if (with_strand) HIP_OR_RET(hipMemcpy(vb.data() + stored, dhb, (size_t)w, hipMemcpyDeviceToHost));
-            stored += w;
-        }
+        hh.passing += h[0];
+        if (hh.append(d, h[1])) return -1;
     }
-    pmx_pair_hits_t *r = nullptr;
-    if (publish(stored, passing, &r)) return -1;
-    if (stored) {
-        memcpy(r->pairs, vp.data(), sizeof(pmx_pair_t) * (size_t)stored); memcpy(r->index, vi.data(), sizeof(int64_t) * (size_t)stored);
-        memcpy(r->recs, vr.data(), sizeof(pmx_record_t) * (size_t)stored);
-        if (stats) memcpy(r->stats, vs.data(), sizeof(pmx_stats_t) * (size_t)stored);
-        if (with_strand) memcpy(((pmx_strand_hits_t *)r)->strand, vb.data(), (size_t)stored);
-    }
-    *result = r;
-    return 0;
+    return publish();
 }
 
 extern "C" int pmx_search_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
@@ -4619,7 +4638,7 @@ extern "C" void pmx_strand_hits_free(pmx_strand_hits_t *hits) { free(hits); }
 // rectangle Q x R with a body that keeps the chunk's records in scratch and merges them into one list of at most k entries per row
 // (pmx_topk.hip); the lists live in scratch until the last chunk, then go to their CSR positions.  Everything of a chunk runs on the
 // caller's stream in chunk order.
-struct TopkOut { pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; int64_t capacity; int64_t *row_off, *row_passing, *counts, *first_bad; uint8_t *strand = nullptr; };
+struct TopkOut { HitCols hit; int64_t capacity; int64_t *row_off, *row_passing, *counts, *first_bad; };
 
 // What both entries refuse about the rows, k and the flag.  *R: the reference-side set on return.
 static int topk_shape_check(const pmx_seqset *Q, const pmx_seqset **R, int64_t q_first, int64_t nq, int64_t k, int skip_self)
@@ -4683,8 +4702,8 @@ struct TopkLists {
     int finish(int64_t nq, int64_t q_first, int64_t nr, const TopkOut &o, int marked, hipStream_t st) const
     {
         int rc = pmx_launch_text_offsets(sheld, nq, o.row_off, scan, scan_bytes, st);
-        if (!rc) rc = pmx_launch_topk_emit(nq, q_first, nr, ks, skeys, srec, sst, sheld, spass, o.row_off, o.capacity, o.pairs, o.index, o.recs, o.stats,
-                                           o.row_passing, o.counts, st, o.strand, marked);
+        if (!rc) rc = pmx_launch_topk_emit(nq, q_first, nr, ks, skeys, srec, sst, sheld, spass, o.row_off, o.capacity, o.hit.pairs, o.hit.index, o.hit.recs, o.hit.stats,
+                                           o.row_passing, o.counts, st, o.hit.strand, marked);
         if (rc) { set_err("top-K emit failed (%d)", rc); return rc; }
         return 0;
     }
@@ -4706,44 +4725,20 @@ static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqs
 {
     const int64_t nr = R->count;
     if (nr == 0) return topk_no_pairs(nq, o, st);
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
     const int64_t n = nq * nr, first = q_first * nr;
-    const bool chosen = strand_mode != PMX_STRAND_FORWARD;
-    const int per = strand_slots(strand_mode);
-    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, per), TOPK_CHUNK_MAX);
+    ChunkAlign A(cfg, strand_mode);
+    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, A.per), TOPK_CHUNK_MAX);
     TopkLists L;
     L.shape(chunk, nr, nq, k);
-    pmx_record_t *crec = nullptr, *arec = nullptr; pmx_stats_t *cst = nullptr, *ast = nullptr; uint8_t *okf = nullptr;
-    if (scratch_carve(SCR_PTOPK, [&](Carver &c) {
-            crec = c.take<pmx_record_t>((size_t)chunk);
-            cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
-            L.carve(c, nq, stats);
-            if (chosen) {                                       // the slots' records before the fold, the folded validity bytes
-                arec = c.take<pmx_record_t>((size_t)chunk * per);
-                ast = stats ? c.take<pmx_stats_t>((size_t)chunk * per) : nullptr;
-                okf = c.take<uint8_t>((size_t)chunk);
-            }
-        })) return -1;
+    if (scratch_carve(SCR_PTOPK, [&](Carver &c) { A.carve(c, chunk); L.carve(c, nq, A.stats); })) return -1;
     if (L.clear(nq, st)) return -1;
     int rc = pairs_run(Q, R, n, nullptr, first, PMX_PAIRS_RECT, nullptr, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = 0;
-            if (chosen) {                                       // per * cn slots aligned, folded to cn records that carry their strand into the lists
-                rc = run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, arec, ast, st);
-                if (rc) return rc;
-                rc = pmx_launch_pairs_fold_strands(arec, ast, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st);
-                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(okf, cn, first + c0, o.first_bad, st);
-            } else {
-                rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, crec, cst, st);
-                if (rc) return rc;
-                rc = pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
-                if (!rc && o.first_bad) rc = pmx_launch_pairs_first_bad(b.ok, cn, first + c0, o.first_bad, st);
-            }
-            if (rc) { set_err("top-K merge of a chunk failed (%d)", rc); return rc; }
-            return L.merge(crec, cst, first + c0, cn, nr, q_first, min_score, skip_self, st);
+            const int rc = A.run(cfg, b, cn, max_qlen, max_rlen, first + c0, o.first_bad, st);
+            return rc ? rc : L.merge(A.crec, A.cst, first + c0, cn, nr, q_first, min_score, skip_self, st);
         }, strand_mode);
     if (rc) return rc;
-    return L.finish(nq, q_first, nr, o, chosen ? 1 : 0, st);
+    return L.finish(nq, q_first, nr, o, A.chosen ? 1 : 0, st);
 }
 
 // Both device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.
@@ -4768,7 +4763,7 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    const TopkOut o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, nullptr, d_hit_strand};
+    const TopkOut o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_row_off, d_row_passing, d_counts, nullptr};
     return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts, strand_mode);
 }
 
@@ -4817,7 +4812,7 @@ extern "C" int pmx_topk_records_device(const pmx_record_t *d_rec, const pmx_stat
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     hipStream_t st = (hipStream_t)stream;
-    const TopkOut o = {d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, nullptr, d_hit_strand};
+    const TopkOut o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_row_off, d_row_passing, d_counts, nullptr};
     if (nq == 0) {
         HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), st));
         HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), st));
@@ -4854,87 +4849,53 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
     if (search_pairs_want_check(cfg, stats) || strand_mode_check(cfg, strand_mode)) return -1;
+    HostHits hh;
     // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics (, strand bytes)
-    auto publish = [&](int64_t rows, int64_t h, pmx_topk_hits_t **out) -> int {
-        auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        const size_t o_off = up(with_strand ? sizeof(pmx_topk_strand_hits_t) : sizeof(pmx_topk_hits_t)), o_pass = o_off + up(sizeof(int64_t) * (size_t)(rows + 1));
-        const size_t o_pairs = o_pass + up(sizeof(int64_t) * (size_t)rows), o_index = o_pairs + up(sizeof(pmx_pair_t) * (size_t)h);
-        const size_t o_recs = o_index + up(sizeof(int64_t) * (size_t)h), o_stats = o_recs + up(sizeof(pmx_record_t) * (size_t)h);
-        const size_t o_strand = o_stats + (stats ? up(sizeof(pmx_stats_t) * (size_t)h) : 0);
-        const size_t total = o_strand + (with_strand ? up((size_t)h) : 0) + 16;
-        char *blk = (char *)calloc(1, total);
-        if (!blk) { set_err("out of memory"); return -1; }
-        pmx_topk_hits_t *r = (pmx_topk_hits_t *)blk;
-        if (with_strand) ((pmx_topk_strand_hits_t *)blk)->strand = (uint8_t *)(blk + o_strand);
-        r->n_rows = rows; r->n_hits = h; r->n_passing = 0;
-        r->row_off = (int64_t *)(blk + o_off); r->row_passing = (int64_t *)(blk + o_pass);
-        r->pairs = (pmx_pair_t *)(blk + o_pairs); r->index = (int64_t *)(blk + o_index); r->recs = (pmx_record_t *)(blk + o_recs);
-        r->stats = stats ? (pmx_stats_t *)(blk + o_stats) : nullptr;
-        *out = r;
+    auto publish = [&]() -> int {
+        HitCols c;
+        int64_t *row_off = nullptr, *row_passing = nullptr;
+        pmx_topk_hits_t *r = (pmx_topk_hits_t *)hh.block(with_strand ? sizeof(pmx_topk_strand_hits_t) : sizeof(pmx_topk_hits_t), stats, with_strand, &c,
+                                                         &row_off, &row_passing);
+        if (!r) return -1;
+        r->n_rows = nq; r->n_hits = hh.stored; r->n_passing = hh.passing;
+        r->row_off = row_off; r->row_passing = row_passing;
+        r->pairs = c.pairs; r->index = c.index; r->recs = c.recs; r->stats = c.stats;
+        if (with_strand) ((pmx_topk_strand_hits_t *)r)->strand = c.strand;
+        *result = r;
         return 0;
     };
-    if (nq == 0) return publish(0, 0, result);
+    if (nq == 0) return publish();
     const int64_t nr = R->count;
     const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
-    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
-    if (host_offsets && nr > 0) {
-        bool odd = false; int64_t unused = INT32_MAX;
-        seqset_host_lengths(Q, &mq, &unused, &odd);
-        if (R != Q) seqset_host_lengths(R, &mr, &mnr, &odd); else { mr = mq; mnr = unused; }
-        if (odd) {                                // (rare) the first pair of the rows, row-major, that touches a sequence no whole-sequence window fits
-            mq = mq > INT32_MAX ? INT32_MAX : mq; mr = mr > INT32_MAX ? INT32_MAX : mr;
-            int64_t jbad = -1, l = 0;             // the first such reference: it spoils every row
-            for (int64_t j = 0; j < nr && jbad < 0; ++j)
-                if (host_resolve_side(R->h_off, nr, j, 0, -1, &l)) jbad = j;
-            for (int64_t i = q_first; i < q_first + nq; ++i) {
-                const char *what = host_resolve_side(Q->h_off, Q->count, i, 0, -1, &l), *side = "query";
-                int64_t j = 0;
-                if (!what && jbad >= 0) { j = jbad; what = host_resolve_side(R->h_off, nr, j, 0, -1, &l); side = "reference"; }
-                if (what) { set_err("pair %lld (%lld, %lld): %s: %s", (long long)((i - q_first) * nr + j), (long long)i, (long long)j, side, what); return -1; }
-            }
-        }
-        if (mnr < 1) mnr = 1;
-    }
+    SetLens m;
+    if (host_offsets && nr > 0 && window_host_lens(Q, R, PMX_PAIRS_RECT, q_first * nr, nq * nr, &m)) return -1;
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if (pairs_check(cfg, Q, R, &popts, (int32_t)mq, (int32_t)mr, stats)) return -1;
+    if (pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
     StreamGuard guard(st);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr, unused32 = 0;
-    pmx_config_t cfg_s = *cfg;
-    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, nq * nr);
-    else if (nr > 0) {                            // wrapped sets: the longest sequence of either set, found on the device
-        if (device_maxlens(Q, Q, nullptr, Q->count, &q32, &unused32, st)) return -1;
-        r32 = q32;
-        if (R != Q && device_maxlens(R, R, nullptr, R->count, &r32, &unused32, st)) return -1;
-        if (q32 < 1 || r32 < 1) { q32 = q32 < 1 ? 1 : q32; r32 = r32 < 1 ? 1 : r32; }
-        if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
-    }
+    const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mr, nq * nr);    // (wrapped sets: no host lengths yet, and no hint from them)
+    if (!host_offsets && nr > 0 && window_device_lens(cfg, Q, R, &m, st)) return -1;
     // a slice's running state (key, record, statistics per kept entry) stays within the bound of the chunk buffers
     const int64_t ks = std::max<int64_t>(1, std::min<int64_t>(opts->k, nr));
     const int64_t per_row = ks * (int64_t)(8 + sizeof(pmx_record_t) + (stats ? sizeof(pmx_stats_t) : 0)) + 12;
     const int64_t slice = std::min<int64_t>(opts->slice_rows > 0 ? opts->slice_rows : std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / per_row), nq);
     const int64_t cap_buf = slice * ks;
-    pmx_pair_t *dhp = nullptr; int64_t *dhi = nullptr, *doff = nullptr, *dpass = nullptr, *dcnt = nullptr; pmx_record_t *dhr = nullptr; pmx_stats_t *dhs = nullptr;
-    uint8_t *dhb = nullptr;
+    HitCols d = {}; int64_t *doff = nullptr, *dpass = nullptr, *dcnt = nullptr;
     if (scratch_carve(SCR_PTHIT, [&](Carver &c) {
-            dhp = c.take<pmx_pair_t>((size_t)cap_buf); dhi = c.take<int64_t>((size_t)cap_buf); dhr = c.take<pmx_record_t>((size_t)cap_buf);
-            dhs = stats ? c.take<pmx_stats_t>((size_t)cap_buf) : nullptr;
+            d.carve(c, (size_t)cap_buf, stats, with_strand);
             doff = c.take<int64_t>((size_t)slice + 1); dpass = c.take<int64_t>((size_t)slice);
             dcnt = c.take<int64_t>(4);                   // kept, written, passing, first bad pair
-            dhb = with_strand ? c.take<uint8_t>((size_t)cap_buf) : nullptr;
         })) return -1;
     if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 3, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
-    std::vector<pmx_pair_t> vp; std::vector<int64_t> vi, voff, vpass; std::vector<pmx_record_t> vr; std::vector<pmx_stats_t> vs; std::vector<uint8_t> vb;
-    try { voff.assign((size_t)nq + 1, 0); vpass.assign((size_t)nq, 0); } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
-    int64_t stored = 0, passing = 0;
+    try { hh.row_off.assign((size_t)nq + 1, 0); hh.row_passing.assign((size_t)nq, 0); } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
     for (int64_t s0 = 0; s0 < nq; s0 += slice) {
         const int64_t sn = std::min<int64_t>(slice, nq - s0);
-        const TopkOut o = {dhp, dhi, dhr, dhs, sn * ks, doff, dpass, dcnt, host_offsets ? nullptr : dcnt + 3, dhb};
+        const TopkOut o = {d, sn * ks, doff, dpass, dcnt, host_offsets ? nullptr : dcnt + 3};
         int64_t h[4] = {0, 0, 0, 0};
-        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, q32, r32, opts->min_score, opts->k, opts->skip_self, o, st, &popts, strand_mode);
+        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, m.mq, m.mr, opts->min_score, opts->k, opts->skip_self, o, st, &popts, strand_mode);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
@@ -4942,36 +4903,13 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
             set_err("pair %lld (%lld, %lld): bad descriptor (index, window or length)", (long long)(h[3] - q_first * nr), (long long)(h[3] / nr), (long long)(h[3] % nr));
             return -1;
         }
-        passing += h[2];
-        const int64_t w = h[1];
-        HIP_OR_RET(hipMemcpy(voff.data() + s0 + 1, doff + 1, sizeof(int64_t) * (size_t)sn, hipMemcpyDeviceToHost));
-        HIP_OR_RET(hipMemcpy(vpass.data() + s0, dpass, sizeof(int64_t) * (size_t)sn, hipMemcpyDeviceToHost));
-        for (int64_t x = 1; x <= sn; ++x) voff[(size_t)(s0 + x)] += stored;
-        if (w > 0) {
-            try {
-                vp.resize((size_t)(stored + w)); vi.resize((size_t)(stored + w)); vr.resize((size_t)(stored + w)); if (stats) vs.resize((size_t)(stored + w));
-                if (with_strand) vb.resize((size_t)(stored + w));
-            } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
-            HIP_OR_RET(hipMemcpy(vp.data() + stored, dhp, sizeof(pmx_pair_t) * (size_t)w, hipMemcpyDeviceToHost));
-            HIP_OR_RET(hipMemcpy(vi.data() + stored, dhi, sizeof(int64_t) * (size_t)w, hipMemcpyDeviceToHost));
-            HIP_OR_RET(hipMemcpy(vr.data() + stored, dhr, sizeof(pmx_record_t) * (size_t)w, hipMemcpyDeviceToHost));
-            if (stats) HIP_OR_RET(hipMemcpy(vs.data() + stored, dhs, sizeof(pmx_stats_t) * (size_t)w, hipMemcpyDeviceToHost));
-            if (with_strand) HIP_OR_RET(hipMemcpy(vb.data() + stored, dhb, (size_t)w, hipMemcpyDeviceToHost));
-            stored += w;
-        }
+        hh.passing += h[2];
+        HIP_OR_RET(hipMemcpy(hh.row_off.data() + s0 + 1, doff + 1, sizeof(int64_t) * (size_t)sn, hipMemcpyDeviceToHost));
+        HIP_OR_RET(hipMemcpy(hh.row_passing.data() + s0, dpass, sizeof(int64_t) * (size_t)sn, hipMemcpyDeviceToHost));
+        for (int64_t x = 1; x <= sn; ++x) hh.row_off[(size_t)(s0 + x)] += hh.stored;
+        if (hh.append(d, h[1])) return -1;
     }
-    pmx_topk_hits_t *r = nullptr;
-    if (publish(nq, stored, &r)) return -1;
-    r->n_passing = passing;
-    memcpy(r->row_off, voff.data(), sizeof(int64_t) * (size_t)(nq + 1)); memcpy(r->row_passing, vpass.data(), sizeof(int64_t) * (size_t)nq);
-    if (stored) {
-        memcpy(r->pairs, vp.data(), sizeof(pmx_pair_t) * (size_t)stored); memcpy(r->index, vi.data(), sizeof(int64_t) * (size_t)stored);
-        memcpy(r->recs, vr.data(), sizeof(pmx_record_t) * (size_t)stored);
-        if (stats) memcpy(r->stats, vs.data(), sizeof(pmx_stats_t) * (size_t)stored);
-        if (with_strand) memcpy(((pmx_topk_strand_hits_t *)r)->strand, vb.data(), (size_t)stored);
-    }
-    *result = r;
-    return 0;
+    return publish();
 }
 
 extern "C" int pmx_search_topk(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,

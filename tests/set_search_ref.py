@@ -53,3 +53,13 @@ def hits(records, min_score, first=0, descs=None, stats=None, capacity=None):
         keep = keep[:capacity]
     return {"passing": passing, "written": len(keep), "index": keep.astype(np.int64) + first, "records": records[keep],
             "pairs": descs[keep] if descs is not None else None, "stats": stats[keep] if stats is not None else None}
+
+
+def first_empty_pair(shape, qlens, rlens, first, count):
+    """Brute force over pairs [first, first + count) of an enumerated shape (TRIANGLE: rlens is qlens): (x, i, j, side) of the first
+    pair whose query -- checked first -- or reference is an empty sequence, x counted from the window's first pair; None without one."""
+    for p in range(first, first + count):
+        i, j = pairs_ref.all_pairs_index(len(qlens), p) if shape == PAIRS_TRIANGLE else rect_pairs_index(len(rlens), p)
+        if qlens[i] < 1 or rlens[j] < 1:
+            return p - first, i, j, "query" if qlens[i] < 1 else "reference"
+    return None
