@@ -733,6 +733,99 @@ int  pmx_search_topk_stranded(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
                               const pmx_topk_opts_t *opts, int strand_mode, pmx_topk_strand_hits_t **result);
 void pmx_topk_strand_hits_free(pmx_topk_strand_hits_t *hits);
 
+/* Translated set search (extension): nucleotide queries against a protein set, the query window translated in up to six frames
+ * inside its chunk and the frames' records folded to one BEFORE selection, so hits, counts, top-K cuts and device memory are per
+ * pair, not per (pair, frame).  Nothing below the gather changes: the alignment kernels see protein against protein.
+ *
+ * Genetic code.  pmx_genetic_code_table exports the standard code (NCBI table 1) in NCBI order: index = 16 b0 + 4 b1 + b2 with
+ * T = 0, C = 1, A = 2, G = 3, "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG".  A base is one of "ACGTU" or
+ * "acgtu", U reads as T; a codon holding any other byte translates to 'X', a stop to '*'; output letters are upper case.  `code`
+ * (every translated entry; a host pointer, read during the call) carries a caller's own 64 letters in the same order, written as
+ * they are; NULL: the standard code.  One genetic code per call.
+ *
+ * Frames.  One byte f.  f = 0, 1, 2: the query window as stored, read from offset off = f.  f = 3, 4, 5: the query window
+ * reverse-complemented exactly as the _ex entries define it (pmx_complement_table, then reversed), read from offset off = f - 3.
+ * Any other byte is a bad descriptor.  With W the window's length in nucleotides the translated query has L = (W - off) / 3 letters
+ * (integer division; 0 for W < off); letter p is the codon at positions off + 3 p .. off + 3 p + 2 of that (possibly
+ * reverse-complemented) window.  A frame with L = 0 does not exist for the pair.  The reference window is never translated.
+ * ALL POSITIONS OF A RECORD (end_query, begins of a CIGAR pass) ARE IN LETTERS OF THE TRANSLATED QUERY.  Back to stored bytes:
+ * letter p of a forward frame is sequence bytes q_beg + off + 3 p .. q_beg + off + 3 p + 2; letter p of a reverse frame is sequence
+ * bytes q_beg + W - 1 - (off + 3 p) downwards (three bytes, complemented).  max_qlen of the device entries bounds L -- what the
+ * alignment kernels see -- so the nucleotide window may be up to 3 max_qlen + 2 bytes; a frame of the call's mode whose L exceeds
+ * max_qlen makes the pair bad.
+ *
+ * Frame modes.  0 .. 5: that one frame for every pair, one alignment slot.  PMX_FRAMES_FORWARD / _REVERSE / _ALL: the best of
+ * frames 0 1 2 / 3 4 5 / all six, 3 / 3 / 6 slots per pair.  Fold rule: among the frames that exist for the pair the highest score
+ * wins, only the score is compared, a tie goes to the lowest frame number.  The folded record is the winner's record BYTE FOR BYTE,
+ * flags included, the statistics are the winner's, one frame byte says which frame won.  A pair with no existing frame, or a bad
+ * descriptor, gets {0, -1, -1, PMX_FLAG_BAD_PAIR}, zero statistics and frame 0.  Selection (min_score, max_hits, capacity) and the
+ * top-K order (score descending, reference index ascending) work on folded records; the frame is not part of the key, so a
+ * reference appears at most once in a row and row_passing counts pairs.  chunk_pairs, slice_pairs and slice_rows count logical
+ * pairs or rows and never change a byte; outputs are bit-identical from run to run.
+ *
+ * The defining equivalence.  In a single-frame mode every output of a translated entry is byte-identical to the corresponding
+ * untranslated entry (pmx_align_pairs_device, pmx_search_pairs_device, pmx_search_topk_device) over a query set whose sequences
+ * were translated on the host in that frame (whole-sequence descriptors; a window: against the translated window).  In a
+ * multi-frame mode every output equals the fold rule applied to the single-frame results.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: a frame mode outside the defined values; a PSSM matrix;
+ * PMX_WANT_CIGAR (the CIGAR route: pmx_gather_pairs_translated_device over the pairs and their frame bytes, then
+ * pmx_align_batch_cigar_device over the packed buffers); everything the corresponding untranslated entry refuses, with the same
+ * texts.  n == 0 behaves as it does there.  The host entries name the first pair that is bad or has no frame.
+ *
+ * Scratch.  The chunk buffers hold `slots` windows per pair (1, 3 or 6; the default chunk holds that many fewer pairs), and per
+ * pair of a chunk 46 bytes per slot, 16 (+ 12 with statistics) per slot for the slots' records in the search entries, and one
+ * validity byte.  pmx_last_kernel() names what the last chunk's alignment ran. */
+#define PMX_FRAMES_FORWARD 6   /* the best of frames 0, 1, 2 */
+#define PMX_FRAMES_REVERSE 7   /* the best of frames 3, 4, 5 */
+#define PMX_FRAMES_ALL     8   /* the best of all six */
+void pmx_genetic_code_table(uint8_t table[64]);
+/* Building block, test hook and the CIGAR route: pmx_gather_pairs_device with the query windows translated.  d_frame: one frame
+ * byte per pair (NULL: all frame 0).  d_qout receives the translated query windows, d_rout the reference windows, packed back to
+ * back; d_qoff / d_roff receive n + 1 offsets from 0; a window whose end would cross its capacity is not written; a pair that is
+ * bad or whose frame does not exist has a one-zero-byte placeholder on either side and d_ok[k] = 0.  No byte outside a set's buffer
+ * is read.  Asynchronous on `stream`. */
+int pmx_gather_pairs_translated_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                       const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                       uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                       uint8_t *d_ok /* n validity bytes, optional */, void *stream);
+/* Listed pairs.  d_frame / frame: a frame byte per pair (then frame_mode must be 0), or NULL and a frame mode for all pairs.
+ * d_frame_out / frame_out (n bytes; required in a multi-frame mode, else optional): the frame of every record. */
+int pmx_align_pairs_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                      int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_frame, int frame_mode, const uint8_t *code,
+                                      int32_t max_qlen, int32_t max_rlen,
+                                      pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
+                                      const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                               int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
+                               pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */, uint8_t *frame_out,
+                               const pmx_pairs_opts_t *opts);
+/* Set search and per-query top-K: the argument lists of the stranded entries with frame_mode, code and d_hit_frame (optional, one
+ * byte per written hit) in place of the strand arguments.  The hit descriptors stay valid d_pairs: with the frame bytes they feed
+ * pmx_gather_pairs_translated_device.  The host results are laid out like pmx_strand_hits_t / pmx_topk_strand_hits_t with `frame`
+ * bytes, one block each, released with their own free functions. */
+int pmx_search_pairs_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                       int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                       int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                       pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                       int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                       int frame_mode, const uint8_t *code, uint8_t *d_hit_frame /* optional */);
+typedef struct pmx_frame_hits { int64_t n_hits, n_passing; pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; uint8_t *frame; } pmx_frame_hits_t;
+int  pmx_search_pairs_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                 const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int frame_mode, const uint8_t *code,
+                                 pmx_frame_hits_t **result);
+void pmx_frame_hits_free(pmx_frame_hits_t *hits);
+int pmx_search_topk_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                      int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                      pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                      int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                      void *stream, const pmx_pairs_opts_t *opts,
+                                      int frame_mode, const uint8_t *code, uint8_t *d_hit_frame /* optional */);
+typedef struct pmx_topk_frame_hits { int64_t n_rows, n_hits, n_passing; int64_t *row_off, *row_passing; pmx_pair_t *pairs; int64_t *index; pmx_record_t *recs; pmx_stats_t *stats; uint8_t *frame; } pmx_topk_frame_hits_t;
+int  pmx_search_topk_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result);
+void pmx_topk_frame_hits_free(pmx_topk_frame_hits_t *hits);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -114,6 +114,14 @@ class pmx_topk_strand_hits_t(C.Structure):
     _fields_ = pmx_topk_hits_t._fields_ + [("strand", C.c_void_p)]
 
 
+class pmx_frame_hits_t(C.Structure):
+    _fields_ = pmx_pair_hits_t._fields_ + [("frame", C.c_void_p)]
+
+
+class pmx_topk_frame_hits_t(C.Structure):
+    _fields_ = pmx_topk_hits_t._fields_ + [("frame", C.c_void_p)]
+
+
 TOPK_MAX = 1024
 INT32_MIN = -(1 << 31)
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
@@ -124,6 +132,7 @@ HITS_BY_INDEX, HITS_BY_SCORE = 0, 1
 PAIR_DTYPE = np.dtype([("q", "<i8"), ("r", "<i8"), ("q_beg", "<i4"), ("q_len", "<i4"), ("r_beg", "<i4"), ("r_len", "<i4")])
 PAIRS_LIST, PAIRS_TRIANGLE, PAIRS_RECT = 0, 1, 2
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
+FRAMES_FORWARD, FRAMES_REVERSE, FRAMES_ALL = 6, 7, 8          # frame modes beside the single frames 0 .. 5
 
 MODE_NW, MODE_SG, MODE_SW = 0, 1, 2
 SG_QB, SG_QE, SG_DB, SG_DE, SG_ALL = 1, 2, 4, 8, 15
@@ -288,6 +297,25 @@ _sig("pmx_search_topk_stranded_device", C.c_int, C.POINTER(pmx_config_t), C.c_vo
 _sig("pmx_search_topk_stranded", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.c_int, C.POINTER(C.POINTER(pmx_topk_strand_hits_t)))
 _sig("pmx_topk_strand_hits_free", None, C.POINTER(pmx_topk_strand_hits_t))
+_sig("pmx_genetic_code_table", None, C.c_void_p)
+_sig("pmx_gather_pairs_translated_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_align_pairs_translated_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_translated", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_search_pairs_translated_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_void_p)
+_sig("pmx_search_pairs_translated", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+     C.POINTER(pmx_pair_search_opts_t), C.c_int, C.c_void_p, C.POINTER(C.POINTER(pmx_frame_hits_t)))
+_sig("pmx_frame_hits_free", None, C.POINTER(pmx_frame_hits_t))
+_sig("pmx_search_topk_translated_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_void_p)
+_sig("pmx_search_topk_translated", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+     C.POINTER(pmx_topk_opts_t), C.c_int, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_frame_hits_t)))
+_sig("pmx_topk_frame_hits_free", None, C.POINTER(pmx_topk_frame_hits_t))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -912,7 +940,7 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return (out, stats) if stats is not None else out
 
-    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False):
+    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False, frame=None, code=None):
         """Pairs by index and window into device-resident sequence sets (SeqSet; Q may be R).  `pairs`: a PAIR_DTYPE array, or
         an iterable of (q, r) / (q, r, q_beg, q_len, r_beg, r_len) tuples (len -1: to the sequence's end).  Record k is the record
         of the pair (query window, reference window) k, end positions relative to the windows.  A bad descriptor raises BatchError
@@ -920,7 +948,11 @@ class Aligner:
         position of such a pair is relative to the reverse-complemented window).  cigar=True returns (records, CIGAR strings,
         int32 [n, 2] begins of the paths) instead.  strand="both": every pair on both strands, the better one kept (a tie: the
         forward strand) -- (records, strand) or (records, stats, strand), strand a uint8 array saying which one won; with
-        cigar=True the CIGARs of the winners, (records, cigars, begins, strand)."""
+        cigar=True the CIGARs of the winners, (records, cigars, begins, strand).  `frame` (not together with strand): Q holds
+        nucleotides, R proteins, and the query windows are translated (translate() restates the rule) -- a frame 0 .. 5, "forward" /
+        "reverse" / "all" (FRAMES_*: the best of those frames, a tie to the lowest) or one frame byte per pair; positions are in
+        letters of the translated query; returns (records, frames) or (records, stats, frames).  code: 64 letters that replace
+        genetic_code_table()."""
         if not self._profile.is_null():
             raise BatchError("align_pairs takes no profile")
         pairs = as_pairs(pairs)
@@ -929,6 +961,21 @@ class Aligner:
         out = np.zeros(n, dtype=RECORD_DTYPE)
         stats = np.zeros(n, dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
         opts = pmx_pairs_opts_t(int(chunk_pairs))
+        if frame is not None:
+            if strand is not None:
+                raise BatchError("frame and strand exclude each other: a reverse frame is the reverse strand translated")
+            if cigar:
+                cfg.want |= WANT_CIGAR                   # (refused by the entry, which names the route)
+            mode, per_pair = _frame_mode(frame, n)
+            code = _code_arg(code)
+            won = np.zeros(n, dtype=np.uint8)
+            rc = lib.pmx_align_pairs_translated(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
+                                                per_pair.ctypes.data if per_pair is not None else None, mode,
+                                                code.ctypes.data if code is not None else None, out.ctypes.data,
+                                                stats.ctypes.data if stats is not None else None, won.ctypes.data, C.byref(opts))
+            if rc:
+                raise BatchError(lib.pmx_last_error().decode())
+            return (out, stats, won) if stats is not None else (out, won)
         if isinstance(strand, str):
             if strand != "both":
                 raise BatchError("strand is a byte per pair or \"both\"")
@@ -988,14 +1035,16 @@ class Aligner:
         return (out, stats) if stats is not None else out
 
     def search_pairs(self, Q, R=None, min_score=0, pairs=None, first=0, count=None, stats=False, max_hits=0, chunk_pairs=0,
-                     slice_pairs=0, strand=0):
+                     slice_pairs=0, strand=0, frame=None, code=None):
         """Set search: the pairs of an enumeration that score at least min_score, as a PairHits in enumeration order.  `pairs`
         given: those descriptors of Q x R (as align_pairs takes them; R None: Q); else R None: pairs [first, first + count) of the
         strict upper triangle of Q (the numbering of align_all_pairs); else the same window of the rectangle Q x R, row-major
         (pair p = (p // len(R), p % len(R)); R may be Q, the diagonal included).  count None: to the last pair.  stats=True adds the
         hits' statistics.  max_hits > 0 keeps the first max_hits hits and goes on counting n_passing.  Only the hits leave the
         device; chunk_pairs and slice_pairs never change the result.  strand: 0 the queries as stored, 1 reverse-complemented,
-        "both" (or STRAND_BOTH) the better strand of every pair, chosen before the threshold; PairHits.strand tells which."""
+        "both" (or STRAND_BOTH) the better strand of every pair, chosen before the threshold; PairHits.strand tells which.
+        frame (not together with strand): nucleotide queries against proteins, translated in frame 0 .. 5 or the best of "forward" /
+        "reverse" / "all" frames, chosen before the threshold; PairHits.frame tells which (code: as in align_pairs)."""
         if not self._profile.is_null():
             raise BatchError("search_pairs takes no profile")
         cfg = self._config()
@@ -1017,17 +1066,24 @@ class Aligner:
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
                 pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts))
         mode = _strand_mode(strand)
+        if frame is not None:
+            if mode != STRAND_FORWARD:
+                raise BatchError("frame and strand exclude each other: a reverse frame is the reverse strand translated")
+            code = _code_arg(code)
+            return _hits_call(lib.pmx_search_pairs_translated, args + (_frame_mode(frame)[0], code.ctypes.data if code is not None else None),
+                              pmx_frame_hits_t, PairHits, lib.pmx_frame_hits_free)
         if mode != STRAND_FORWARD:
             return _hits_call(lib.pmx_search_pairs_stranded, args + (mode,), pmx_strand_hits_t, PairHits, lib.pmx_strand_hits_free)
         return _hits_call(lib.pmx_search_pairs, args, pmx_pair_hits_t, PairHits, lib.pmx_pair_hits_free)
 
     def search_topk(self, Q, R=None, k=10, min_score=INT32_MIN, skip_self=False, first_row=0, rows=None, stats=False, chunk_pairs=0,
-                    slice_rows=0, strand=0):
+                    slice_rows=0, strand=0, frame=None, code=None):
         """Per-query top-K: for each query row [first_row, first_row + rows) of Q the best k references of R (None: Q) with score
         >= min_score, in (score descending, reference index ascending) order, as a TopKHits.  rows None: to the last row.
         skip_self (R is Q) leaves the pair (i, i) out.  stats=True adds the hits' statistics.  Only the hits leave the device;
         chunk_pairs and slice_rows never change the result.  strand as in search_pairs: with "both" a reference is one
-        candidate with its better strand, and TopKHits.strand tells which."""
+        candidate with its better strand, and TopKHits.strand tells which.  frame as in search_pairs: a reference is one candidate
+        with its best frame, and TopKHits.frame tells which."""
         if not self._profile.is_null():
             raise BatchError("search_topk takes no profile")
         cfg = self._config()
@@ -1038,6 +1094,12 @@ class Aligner:
         opts = pmx_topk_opts_t(int(min_score), int(k), 1 if skip_self else 0, int(chunk_pairs), int(slice_rows))
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows), C.byref(opts))
         mode = _strand_mode(strand)
+        if frame is not None:
+            if mode != STRAND_FORWARD:
+                raise BatchError("frame and strand exclude each other: a reverse frame is the reverse strand translated")
+            code = _code_arg(code)
+            return _hits_call(lib.pmx_search_topk_translated, args + (_frame_mode(frame)[0], code.ctypes.data if code is not None else None),
+                              pmx_topk_frame_hits_t, TopKHits, lib.pmx_topk_frame_hits_free)
         if mode != STRAND_FORWARD:
             return _hits_call(lib.pmx_search_topk_stranded, args + (mode,), pmx_topk_strand_hits_t, TopKHits, lib.pmx_topk_strand_hits_free)
         return _hits_call(lib.pmx_search_topk, args, pmx_topk_hits_t, TopKHits, lib.pmx_topk_hits_free)
@@ -1244,6 +1306,61 @@ def _strand_mode(strand):
     return int(strand)
 
 
+def _frame_mode(frame, n=None):
+    """A frame argument -> (frame mode, frame bytes per pair or None): 0 .. 5, FRAMES_* or "forward" / "reverse" / "all"; with n
+    (align_pairs) also one frame byte per pair."""
+    names = {"forward": FRAMES_FORWARD, "reverse": FRAMES_REVERSE, "all": FRAMES_ALL}
+    if isinstance(frame, str):
+        if frame not in names:
+            raise BatchError("frame is 0 .. 5, \"forward\", \"reverse\" or \"all\"")
+        return names[frame], None
+    if np.ndim(frame) == 0:
+        return int(frame), None
+    if n is None:
+        raise BatchError("a frame byte per pair is for align_pairs: a search takes one frame mode")
+    per_pair = np.ascontiguousarray(frame, dtype=np.uint8)
+    if len(per_pair) != n:
+        raise BatchError("frame and pairs differ in count")
+    return 0, per_pair
+
+
+def _code_arg(code):
+    """A caller's genetic code (64 letters in NCBI order) as a uint8 array, or None for the standard one."""
+    if code is None:
+        return None
+    code = np.frombuffer(code.encode() if isinstance(code, str) else bytes(code), dtype=np.uint8).copy()
+    if len(code) != 64:
+        raise BatchError("a genetic code has 64 letters, not %d" % len(code))
+    return code
+
+
+def genetic_code_table():
+    """The standard genetic code (NCBI table 1) in NCBI order: 64 bytes, index 16 b0 + 4 b1 + b2 with T = 0, C = 1, A = 2, G = 3."""
+    tab = np.zeros(64, dtype=np.uint8)
+    lib.pmx_genetic_code_table(tab.ctypes.data)
+    return tab.tobytes()
+
+
+def translate(seq, frame, code=None):
+    """The translation of a nucleotide window as the _translated entries define it, on the host: frame 0 .. 2 reads `seq` from offset
+    frame, frame 3 .. 5 its reverse complement (complement_table(), then reversed) from offset frame - 3; (len - offset) // 3 letters;
+    a codon with a byte outside ACGTUacgtu is X.  b"" when the frame does not exist."""
+    frame = int(frame)
+    if not 0 <= frame <= 5:
+        raise BatchError("frame %d is outside 0 .. 5" % frame)
+    code = genetic_code_table() if code is None else _code_arg(code).tobytes()
+    s = np.frombuffer(bytes(seq), dtype=np.uint8)
+    if frame >= 3:
+        s = complement_table()[s[::-1]]
+    off = frame % 3
+    cls = {ord(c): v for c, v in zip("TCAGUtcagu", (0, 1, 2, 3, 0) * 2)}
+    out = bytearray()
+    for p in range(max(len(s) - off, 0) // 3):
+        b = [cls.get(int(x), 64) for x in s[off + 3 * p: off + 3 * p + 3]]
+        out.append(code[16 * b[0] + 4 * b[1] + b[2]] if max(b) < 64 else ord("X"))
+    return bytes(out)
+
+
 def _hits_call(entry, args, block_t, wrap, free):
     """entry(*args, &block) of the host search entries: BatchError on failure, else wrap(block) with the block released."""
     res = C.POINTER(block_t)()
@@ -1258,8 +1375,8 @@ def _hits_call(entry, args, block_t, wrap, free):
 class PairHits:
     """Result of Aligner.search_pairs: n_hits, n_passing (all pairs at or above min_score, stored or not) and, per hit in
     enumeration order, pairs (PAIR_DTYPE: the descriptor, fit for align_pairs), index (int64: the pair's number in the
-    enumeration), records (RECORD_DTYPE), stats (STATS_DTYPE, or None when not asked for) and strand (uint8: the strand of the
-    record, all 0 for a forward search)."""
+    enumeration), records (RECORD_DTYPE), stats (STATS_DTYPE, or None when not asked for), strand (uint8: the strand of the
+    record, all 0 for a forward search) and frame (uint8: the frame of the record of a translated search, else all 0)."""
 
     def __init__(self, r):
         h = int(r.n_hits)
@@ -1274,6 +1391,7 @@ class PairHits:
         self.records = take(r.recs, RECORD_DTYPE)
         self.stats = take(r.stats, STATS_DTYPE) if r.stats else None
         self.strand = take(getattr(r, "strand", None), np.uint8)
+        self.frame = take(getattr(r, "frame", None), np.uint8)
 
     def __len__(self):
         return self.n_hits
@@ -1284,7 +1402,7 @@ class TopKHits:
     min_score per row, kept or not), n_passing (their sum) and, per hit, pairs (PAIR_DTYPE: the descriptor, fit for align_pairs),
     index (int64: p = i * len(R) + j), records (RECORD_DTYPE) and stats (STATS_DTYPE, or None when not asked for).  A row's hits
     are in (score descending, reference index ascending) order; row(i) slices them out.  strand (uint8 per hit): the strand of the
-    record, all 0 for a forward search."""
+    record, all 0 for a forward search; frame (uint8 per hit): the frame of the record of a translated search, else all 0."""
 
     def __init__(self, r):
         h, n = int(r.n_hits), int(r.n_rows)
@@ -1301,6 +1419,7 @@ class TopKHits:
         self.records = take(r.recs, h, RECORD_DTYPE)
         self.stats = take(r.stats, h, STATS_DTYPE) if r.stats else None
         self.strand = take(getattr(r, "strand", None), h, np.uint8)
+        self.frame = take(getattr(r, "frame", None), h, np.uint8)
 
     def __len__(self):
         return self.n_hits
@@ -1568,6 +1687,59 @@ def search_topk_stranded_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_
                                              max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
                                              d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream,
                                              C.byref(opts), int(strand_mode), d_hit_strand)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def gather_pairs_translated_device(Q, R, n, d_pairs, d_frame, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff,
+                                   d_ok=None, stream=0, code=None):
+    """gather_pairs_device with the query windows translated (d_frame: a frame byte per pair or None for frame 0; max_qlen bounds the
+    translated length): the building block of a CIGAR pass over translated hits."""
+    code = _code_arg(code)
+    rc = lib.pmx_gather_pairs_translated_device(Q._handle(), R._handle(), n, d_pairs, d_frame, code.ctypes.data if code is not None else None,
+                                                max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_translated_device(cfg, Q, R, n, d_pairs, d_frame, frame_mode, max_qlen, max_rlen, d_out, d_stats=None, d_frame_out=None,
+                                  stream=0, chunk_pairs=0, code=None):
+    """align_pairs_device with translated queries: d_frame (a frame byte per pair, frame_mode 0) or None and a frame mode (0 .. 5,
+    FRAMES_*); record k is the best frame's, byte for byte, d_frame_out (n bytes) says which."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_align_pairs_translated_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_frame, int(frame_mode),
+                                               code.ctypes.data if code is not None else None, max_qlen, max_rlen, d_out, d_stats, d_frame_out,
+                                               stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_pairs_translated_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs,
+                                   d_hit_stats, capacity, d_counts, frame_mode, d_hit_frame=None, stream=0, chunk_pairs=0, code=None):
+    """search_pairs_device with translated queries and a frame mode: the threshold looks at the folded records; d_hit_frame (optional,
+    one byte per hit) receives the hits' frames.  d_hit_pairs and d_hit_frame feed gather_pairs_translated_device unchanged."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_search_pairs_translated_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(shape), int(first),
+                                                int(n), d_pairs, max_qlen, max_rlen, int(min_score), d_hit_pairs, d_hit_index, d_hit_recs,
+                                                d_hit_stats, int(capacity), d_counts, stream, C.byref(opts), int(frame_mode),
+                                                code.ctypes.data if code is not None else None, d_hit_frame)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_topk_translated_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs,
+                                  d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, frame_mode, d_hit_frame=None, stream=0,
+                                  chunk_pairs=0, code=None):
+    """search_topk_device with translated queries and a frame mode: a reference is one candidate with its folded record; d_hit_frame
+    (optional, one byte per hit) receives the hits' frames."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_search_topk_translated_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
+                                               max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
+                                               d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream,
+                                               C.byref(opts), int(frame_mode), code.ctypes.data if code is not None else None, d_hit_frame)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

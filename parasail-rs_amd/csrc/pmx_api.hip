@@ -3737,15 +3737,25 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 // strand_mode PMX_STRAND_REVERSE / PMX_STRAND_BOTH (the entries that choose the strand themselves; d_strand is then nullptr):
 // a chunk of cn pairs is per = 1 / 2 alignment slots per pair -- BOTH: slot 2 k is pair k as stored, slot 2 k + 1 pair k with its query
 // reverse-complemented -- and the buffers hold per * cn windows; the body still gets c0 and cn in logical pairs.
+// fr != nullptr (the _translated entries; d_strand is then nullptr and the strand mode forward): the query windows are
+// nucleotides translated on their way into the buffers, per = fr->per alignment slots per pair, one per frame; max_qlen bounds the
+// translated length, so the query buffer holds per * cn * max_qlen letters.
 static int strand_slots(int strand_mode) { return strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
-struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; };
+struct FrameRun {
+    int first = 0, per = 1;                 // the frames first .. first + per - 1 for every pair ...
+    const uint8_t *d_frame = nullptr;       // ... or (listed pairs, per 1) a frame byte per pair
+    PmxCodeTable code;
+    int min_off() const { return per == 1 && !d_frame ? first % 3 : 0; }      // the smallest offset a frame of the call reads from
+    int32_t letters(int32_t w) const { return std::max<int32_t>(1, (w - min_off()) / 3); }   // the longest translation of w nucleotides
+};
+struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; int32_t *qw; };
 template <typename Body>
 static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first, int shape,
                      const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body,
-                     int strand_mode = PMX_STRAND_FORWARD)
+                     int strand_mode = PMX_STRAND_FORWARD, const FrameRun *fr = nullptr)
 {
-    const bool two = chunk < n, chosen = strand_mode != PMX_STRAND_FORWARD, stranded = d_strand != nullptr || chosen;
-    const int per = strand_slots(strand_mode);
+    const bool two = chunk < n, chosen = strand_mode != PMX_STRAND_FORWARD, stranded = d_strand != nullptr || chosen || fr != nullptr;
+    const int per = fr ? fr->per : strand_slots(strand_mode);
     const size_t slots = (size_t)chunk * (size_t)per;
     PairsChunkBufs B[2]; void *scan = nullptr; pmx_pair_t *gen = nullptr;
     const size_t scan_bytes = pmx_text_scan_scratch_bytes((int64_t)slots);
@@ -3758,6 +3768,7 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
                 B[s].qsrc = c.take<int64_t>(slots); B[s].rsrc = c.take<int64_t>(slots);
                 B[s].ok = c.take<uint8_t>(slots);
                 B[s].sflag = stranded ? c.take<uint8_t>(slots) : nullptr;
+                B[s].qw = fr ? c.take<int32_t>(slots) : nullptr;
             }
             scan = c.take<unsigned char>(scan_bytes);           // (one: the scans of all chunks run in order on one stream)
         })) return -1;
@@ -3778,7 +3789,10 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         int rc = listed ? 0 : shape == PMX_PAIRS_TRIANGLE ? pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gc, prep)
                                                           : pmx_launch_rect_pairs_enumerate(R->count, first + c0, cn, gc, prep);
         const int64_t sn = cn * per;                              // the chunk's alignment slots
-        if (!rc) rc = chosen   ? pmx_launch_pairs_resolve_both(pc, cn, per, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+        if (!rc) rc = fr       ? pmx_launch_pairs_resolve_frames(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
+                                                                 R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                                                 b.qlen, b.rlen, b.qw, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
+                    : chosen   ? pmx_launch_pairs_resolve_both(pc, cn, per, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
                                                                b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
                     : stranded ? pmx_launch_pairs_resolve_stranded(pc, d_strand + c0, cn, Q->d_off, Q->count, Q->bytes,
                                                                    R->d_off, R->count, R->bytes, max_qlen, max_rlen,
@@ -3787,7 +3801,9 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
                                                           b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.qlen, sn, b.qoff, scan, scan_bytes, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.rlen, sn, b.roff, scan, scan_bytes, prep);
-        if (!rc) rc = stranded ? pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
+        if (!rc) rc = fr       ? pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qw, b.qsrc, b.rsrc, b.ok,
+                                                                    b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep)
+                    : stranded ? pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
                                                                   b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, prep)
                                : pmx_launch_pairs_gather(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
                                                          b.qoff, b.roff, b.q, b.r, prep);
@@ -3906,6 +3922,112 @@ extern "C" int pmx_align_pairs_both_device(const pmx_config_t *cfg, const pmx_se
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     return pairs_run_both(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats_out, d_strand_out, (hipStream_t)stream,
                           pairs_chunk(n, max_qlen, max_rlen, opts, 2));
+}
+
+// ---- translated queries ----
+extern "C" void pmx_genetic_code_table(uint8_t table[64]) { if (table) pmx_genetic_code_host(table); }
+
+// What every translated entry refuses about its frames, matrix and outputs, before any GPU work.  *fr: the run's frames and code.
+static int frames_check(const pmx_config_t *cfg, int frame_mode, const uint8_t *d_frame, const uint8_t *code, FrameRun *fr)
+{
+    if (frame_mode < 0 || frame_mode > PMX_FRAMES_ALL) {
+        set_err("frame mode %d is outside 0 .. 8 (a frame 0 .. 5, PMX_FRAMES_FORWARD, PMX_FRAMES_REVERSE, PMX_FRAMES_ALL)", frame_mode); return -1;
+    }
+    if (d_frame && frame_mode != 0) { set_err("a frame byte per pair takes frame mode 0, not %d", frame_mode); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("a translated query takes no PSSM matrix: a profile belongs to one protein query"); return -1; }
+    if (cfg->want & PMX_WANT_CIGAR) {
+        set_err("the translated entries have no CIGAR output: pass the pairs and their frame bytes to pmx_gather_pairs_translated_device, "
+                "then run pmx_align_batch_cigar_device over the packed buffers");
+        return -1;
+    }
+    fr->first = frame_mode <= 5 ? frame_mode : frame_mode == PMX_FRAMES_REVERSE ? 3 : 0;
+    fr->per = frame_mode <= 5 ? 1 : frame_mode == PMX_FRAMES_ALL ? 6 : 3;
+    fr->d_frame = d_frame;
+    if (code) memcpy(fr->code.v, code, 64); else pmx_genetic_code_host(fr->code.v);
+    return 0;
+}
+
+// The score road of a translated batch: every chunk's per * cn slots through run_batch_device into scratch, then the fold straight into
+// the caller's arrays (it writes the bad pairs' records too; per 1: the one slot's record).
+static int pairs_run_frames(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
+                            int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out,
+                            hipStream_t st, int64_t chunk, const FrameRun &fr)
+{
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    pmx_record_t *srec = nullptr; pmx_stats_t *sst = nullptr;
+    if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
+            srec = c.take<pmx_record_t>((size_t)fr.per * (size_t)chunk);
+            sst = stats ? c.take<pmx_stats_t>((size_t)fr.per * (size_t)chunk) : nullptr;
+        })) return -1;
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            int rc = run_batch_device(cfg, fr.per * cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, srec, sst, st);
+            if (rc) return rc;
+            rc = pmx_launch_pairs_fold_frames(srec, sst, b.ok, b.sflag, cn, fr.per, 0, d_out + c0, stats ? d_stats_out + c0 : nullptr,
+                                              d_frame_out ? d_frame_out + c0 : nullptr, nullptr, st);
+            if (rc) { set_err("frame fold launch failed (%d)", rc); return rc; }
+            return 0;
+        }, PMX_STRAND_FORWARD, &fr);
+}
+
+extern "C" int pmx_align_pairs_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                 int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_frame, int frame_mode, const uint8_t *code,
+                                                 int32_t max_qlen, int32_t max_rlen,
+                                                 pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
+                                                 const pmx_pairs_opts_t *opts)
+{
+    FrameRun fr;
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || frames_check(cfg, frame_mode, d_frame, code, &fr)) return -1;
+    if (n > 0 && fr.per > 1 && !d_frame_out) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
+    if (n == 0) return 0;
+    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run_frames(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats_out, d_frame_out, (hipStream_t)stream,
+                            pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
+}
+
+extern "C" int pmx_gather_pairs_translated_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                                  const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                  uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                                  uint8_t *d_ok, void *stream)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
+    if (!d_qoff || !d_roff || (n > 0 && (!d_pairs || !d_qout || !d_rout))) { set_err("null buffer"); return -1; }
+    if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    if (n == 0) return 0;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (Q->dev != dev || R->dev != dev) {
+        set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev != dev ? Q->dev : R->dev, dev); return -1;
+    }
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    PmxCodeTable ct;
+    if (code) memcpy(ct.v, code, 64); else pmx_genetic_code_host(ct.v);
+    int32_t *qlen = nullptr, *rlen = nullptr, *qw = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
+    const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
+    if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
+            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2); qw = c.take<int32_t>((size_t)n);
+            qsrc = c.take<int64_t>((size_t)n); rsrc = c.take<int64_t>((size_t)n);
+            ok = c.take<uint8_t>((size_t)n); sflag = c.take<uint8_t>((size_t)n);
+            scan = c.take<unsigned char>(scan_bytes);
+        })) return -1;
+    if (d_ok) ok = d_ok;
+    int rc = pmx_launch_pairs_resolve_frames(d_pairs, d_frame, 0, 1, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                             qlen, rlen, qw, qsrc, rsrc, ok, sflag, st);
+    if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_pairs_gather_translated(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, qw, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
+                                                     d_qout, q_capacity, d_rout, r_capacity, ct, st);
+    if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
+    return 0;
 }
 
 // ---- strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device) ----
@@ -4281,6 +4403,54 @@ extern "C" int pmx_align_pairs_both(const pmx_config_t *cfg, const pmx_seqset_t 
 }
 
 
+// The host entry over listed pairs with translated queries: pairs_host's score road -- validation against host offsets, the upload of
+// 32 (+ 1) bytes per pair, the records back -- with the frames' run in the middle.  A pair without a frame is found on the device only,
+// so the records' flags are always scanned.
+extern "C" int pmx_align_pairs_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                          int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
+                                          pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *frame_out, const pmx_pairs_opts_t *opts)
+{
+    FrameRun fr;
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || frames_check(cfg, frame_mode, frame, code, &fr)) return -1;
+    if (n > 0 && fr.per > 1 && !frame_out) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
+    if (n == 0) return 0;
+    if (frame)
+        for (int64_t k = 0; k < n; ++k)
+            if (frame[k] > 5) { set_err("pair %lld: frame byte %d is outside 0 .. 5", (long long)k, (int)frame[k]); return -1; }
+    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
+    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
+    if (host_offsets) {
+        const PairScan s = scan_pairs(Q, R, pairs, 0, n);
+        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
+        mq = s.mq; mr = s.mr; mnr = s.mnr;
+    }
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    if (pairs_check(cfg, Q, R, opts, fr.letters((int32_t)mq), (int32_t)mr, stats_out != nullptr)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
+    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the frame bytes in, then out
+    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
+        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
+    uint8_t *dfin = (uint8_t *)dp + up_bytes, *dfout = dfin + n;
+    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (frame) { HIP_OR_RET(hipMemcpyAsync(dfin, frame, (size_t)n, hipMemcpyHostToDevice, st)); fr.d_frame = dfin; }
+    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
+    pmx_config_t cfg_s = *cfg;
+    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
+    else if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
+    q32 = fr.letters(q32);
+    const int rc = pairs_run_frames(&cfg_s, Q, R, n, dp, q32, r32, drec, dst, dfout, st, pairs_chunk(n, q32, r32, opts, fr.per), fr);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    if (frame_out) HIP_OR_RET(hipMemcpyAsync(frame_out, dfout, (size_t)n, hipMemcpyDeviceToHost, st));
+    return pairs_copy_back(n, drec, dst, out, stats_out, true, st);
+}
+
 extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
                                    pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts)
 {
@@ -4394,10 +4564,12 @@ struct PairHitBufs { HitCols hit; int64_t capacity; int64_t *counts, *first_bad;
 // A chunk's alignment for the entries that keep its records in scratch (set search, top-K): the records (and statistics) of the chunk's
 // pairs and, when the entry chooses the strand, those of its alignment slots before the fold and the folded validity bytes.
 struct ChunkAlign {
-    bool stats, chosen; int per;
+    bool stats, chosen; int per; const FrameRun *fr;              // fr != nullptr: the slots are frames of a translated query
     pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr; uint8_t *okf = nullptr;
-    ChunkAlign(const pmx_config_t *cfg, int strand_mode)
-        : stats((cfg->want & PMX_WANT_STATS) != 0), chosen(strand_mode != PMX_STRAND_FORWARD), per(strand_slots(strand_mode)) {}
+    ChunkAlign(const pmx_config_t *cfg, int strand_mode, const FrameRun *frames = nullptr)
+        : stats((cfg->want & PMX_WANT_STATS) != 0), chosen(strand_mode != PMX_STRAND_FORWARD || frames != nullptr),
+          per(frames ? frames->per : strand_slots(strand_mode)), fr(frames) {}
+    int marked() const { return fr ? 2 : chosen ? 1 : 0; }       // what the chunk's records carry in their flags (append_hits, emit)
     void carve(Carver &c, int64_t chunk)
     {
         crec = c.take<pmx_record_t>((size_t)chunk);
@@ -4414,7 +4586,8 @@ struct ChunkAlign {
     {
         int rc = run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, chosen ? srec : crec, chosen ? sst : cst, st);
         if (rc) return rc;
-        rc = chosen ? pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
+        rc = fr     ? pmx_launch_pairs_fold_frames(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
+           : chosen ? pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
                     : pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
         if (!rc && first_bad) rc = pmx_launch_pairs_first_bad(chosen ? okf : b.ok, cn, p0, first_bad, st);
         if (rc) set_err("bad-pair fix-up or strand fold of a chunk failed (%d)", rc);
@@ -4425,9 +4598,9 @@ struct ChunkAlign {
 // n > 0 pairs behind the checks; asynchronous on `st`.  index0: the absolute number of the run's first pair (what d_hit_index counts from).
 static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int shape, int64_t first, int64_t n,
                             const pmx_pair_t *d_pairs, int64_t index0, int32_t max_qlen, int32_t max_rlen, int32_t min_score,
-                            const PairHitBufs &o, hipStream_t st, int64_t chunk, int strand_mode = PMX_STRAND_FORWARD)
+                            const PairHitBufs &o, hipStream_t st, int64_t chunk, int strand_mode = PMX_STRAND_FORWARD, const FrameRun *fr = nullptr)
 {
-    ChunkAlign A(cfg, strand_mode);
+    ChunkAlign A(cfg, strand_mode, fr);
     int64_t *cidx = nullptr, *ccnt = nullptr; void *sel = nullptr;
     const size_t sel_bytes = pmx_select_scratch_bytes(chunk, 0, PMX_HITS_BY_INDEX);
     if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
@@ -4442,24 +4615,28 @@ static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const 
             if (rc) return rc;
             rc = pmx_launch_select(A.crec, cn, min_score, 0, PMX_HITS_BY_INDEX, cidx, cn, ccnt, sel, st);
             if (!rc) rc = pmx_launch_pairs_append_hits(cidx, ccnt, cn, o.capacity, index0 + c0, b.pairs, A.crec, A.cst,
-                                                       o.hit.pairs, o.hit.index, o.hit.recs, o.hit.stats, o.counts, st, o.hit.strand, A.chosen ? 1 : 0);
+                                                       o.hit.pairs, o.hit.index, o.hit.recs, o.hit.stats, o.counts, st, o.hit.strand, A.marked());
             if (rc) { set_err("hit compaction of a chunk failed (%d)", rc); return rc; }
             return 0;
-        }, strand_mode);
+        }, strand_mode, fr);
 }
 
-// Both device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.
+// The device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.  translated: frame_mode
+// and code of the _translated entry (strand_mode is then forward, d_hit_strand receives the frames).
 static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
                                int64_t first, int64_t n, const pmx_pair_t *d_pairs,
                                int32_t max_qlen, int32_t max_rlen, int32_t min_score,
                                pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
-                               int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand)
+                               int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
+                               bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
 {
+    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (search_pairs_shape_check(Q, &R, shape, first, n, d_pairs)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
+    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) ||
+        search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (n == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
         return 0;
@@ -4470,7 +4647,7 @@ static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const PairHitBufs o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_counts, nullptr};
     return search_pairs_run(cfg, Q, R, shape, first, n, d_pairs, first, max_qlen, max_rlen, min_score, o, (hipStream_t)stream,
-                            pairs_chunk(n, max_qlen, max_rlen, opts, strand_slots(strand_mode)), strand_mode);
+                            pairs_chunk(n, max_qlen, max_rlen, opts, fr ? fr->per : strand_slots(strand_mode)), strand_mode, fr);
 }
 
 extern "C" int pmx_search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
@@ -4492,6 +4669,17 @@ extern "C" int pmx_search_pairs_stranded_device(const pmx_config_t *cfg, const p
 {
     return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                                capacity, d_counts, stream, opts, strand_mode, d_hit_strand);
+}
+
+extern "C" int pmx_search_pairs_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                                  int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                                  int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                                  pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                  int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                                  int frame_mode, const uint8_t *code, uint8_t *d_hit_frame)
+{
+    return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                               capacity, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, true, frame_mode, code);
 }
 
 extern "C" void pmx_pair_hits_free(pmx_pair_hits_t *hits) { free(hits); }
@@ -4543,9 +4731,13 @@ struct HostHits {
 
 // Both host entries.  with_strand (pmx_search_pairs_stranded): the block is a pmx_strand_hits_t -- the fields of pmx_pair_hits_t, then the
 // strand bytes -- and the slices' hit buffers hold one more byte per hit; without it the block and the kernels are pmx_search_pairs'.
+// translated (pmx_search_pairs_translated): the block is a pmx_frame_hits_t, the same layout with the frames in the last column; a pair
+// without a frame is found on the device only, so the lowest bad pair is always asked for.
 static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
-                             const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, bool with_strand, pmx_pair_hits_t **result)
+                             const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, bool with_strand, pmx_pair_hits_t **result,
+                             bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
 {
+    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
     if (!opts) { set_err("null opts"); return -1; }
@@ -4556,7 +4748,8 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (search_pairs_want_check(cfg, stats) || strand_mode_check(cfg, strand_mode)) return -1;
+    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) || search_pairs_want_check(cfg, stats) ||
+        strand_mode_check(cfg, strand_mode)) return -1;
     HostHits hh;
     // the result: one block -- header, descriptors, indices, records, statistics (, strand bytes)
     auto publish = [&]() -> int {
@@ -4577,6 +4770,9 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
         m.mq = (int32_t)s.mq; m.mr = (int32_t)s.mr; m.mnr = (int32_t)s.mnr;
     } else if (host_offsets && window_host_lens(Q, R, shape, first, n, &m)) return -1;
+    if (fr) m.mq = fr->letters(m.mq);
+    const bool find_bad = !host_offsets || fr != nullptr;
+    const int per = fr ? fr->per : strand_slots(strand_mode);
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
     if (pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
@@ -4585,7 +4781,10 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     StreamGuard guard(st);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mr, n);          // (wrapped sets: no host lengths yet, and no hint from them)
-    if (!host_offsets && !listed && window_device_lens(cfg, Q, R, &m, st)) return -1;
+    if (!host_offsets && !listed) {
+        if (window_device_lens(cfg, Q, R, &m, st)) return -1;
+        if (fr) m.mq = fr->letters(m.mq);
+    }
     const int64_t slice = std::min<int64_t>(opts->slice_pairs > 0 ? opts->slice_pairs : (int64_t)1 << 24, n);
     const int64_t cap_buf = opts->max_hits > 0 ? std::min<int64_t>(slice, opts->max_hits) : slice;
     HitCols d = {}; pmx_pair_t *dp = nullptr; int64_t *dcnt = nullptr;
@@ -4594,7 +4793,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
             dcnt = c.take<int64_t>(3);                   // passing, written, first bad pair
         })) return -1;
     if (listed && scratch_reserve(sizeof(pmx_pair_t) * (size_t)slice, (void **)&dp, SCR_PUP)) return -1;
-    if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 2, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
+    if (find_bad) HIP_OR_RET(hipMemsetAsync(dcnt + 2, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
     for (int64_t s0 = 0; s0 < n; s0 += slice) {
         const int64_t sn = std::min<int64_t>(slice, n - s0);
         const int64_t cap = opts->max_hits > 0 ? std::min<int64_t>(sn, opts->max_hits - hh.stored) : sn;
@@ -4602,18 +4801,23 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
             HIP_OR_RET(hipMemcpyAsync(dp, pairs + s0, sizeof(pmx_pair_t) * (size_t)sn, hipMemcpyHostToDevice, st));
             if (!host_offsets) {
                 if (device_maxlens(Q, R, dp, sn, &m.mq, &m.mr, st)) return -1;
+                if (fr) m.mq = fr->letters(m.mq);
                 if (pssm_batch_check(cfg->matrix, m.mq, m.mq)) return -1;
             }
         }
         const int64_t p0 = listed ? s0 : first + s0;     // the slice's first pair in the enumeration
-        const PairHitBufs o = {d, cap, dcnt, host_offsets ? nullptr : dcnt + 2};
+        const PairHitBufs o = {d, cap, dcnt, find_bad ? dcnt + 2 : nullptr};
         int64_t h[3] = {0, 0, 0};
         int rc = search_pairs_run(&cfg_s, Q, R, shape, listed ? 0 : p0, sn, dp, p0, m.mq, m.mr, opts->min_score, o, st,
-                                  pairs_chunk(sn, m.mq, m.mr, &popts, strand_slots(strand_mode)), strand_mode);
+                                  pairs_chunk(sn, m.mq, m.mr, &popts, per), strand_mode, fr);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
-        if (!host_offsets && h[2] != -1) { set_err("pair %lld: bad descriptor (index, window or length)", (long long)(h[2] - (listed ? 0 : first))); return -1; }
+        if (find_bad && h[2] != -1) {
+            set_err(fr ? "pair %lld: bad descriptor (index, window or length) or no frame to translate" : "pair %lld: bad descriptor (index, window or length)",
+                    (long long)(h[2] - (listed ? 0 : first)));
+            return -1;
+        }
         hh.passing += h[0];
         if (hh.append(d, h[1])) return -1;
     }
@@ -4632,6 +4836,15 @@ extern "C" int pmx_search_pairs_stranded(const pmx_config_t *cfg, const pmx_seqs
     return search_pairs_host(cfg, Q, R, first, n, pairs, opts, strand_mode, true, (pmx_pair_hits_t **)result);
 }
 extern "C" void pmx_strand_hits_free(pmx_strand_hits_t *hits) { free(hits); }
+
+extern "C" int pmx_search_pairs_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                           const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int frame_mode, const uint8_t *code,
+                                           pmx_frame_hits_t **result)
+{
+    static_assert(sizeof(pmx_frame_hits_t) == sizeof(pmx_strand_hits_t) && offsetof(pmx_frame_hits_t, frame) == offsetof(pmx_strand_hits_t, strand), "one layout");
+    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, PMX_STRAND_FORWARD, true, (pmx_pair_hits_t **)result, true, frame_mode, code);
+}
+extern "C" void pmx_frame_hits_free(pmx_frame_hits_t *hits) { free(hits); }
 
 // ==================================================================== per-query top-K ===
 // pmx_search_topk[_device] (semantics: include/parasail_amd.h): the chunk loop of the set batches over whole rows of the
@@ -4721,12 +4934,12 @@ static const int64_t TOPK_CHUNK_MAX = (int64_t)1 << 26;            // (a chunk's
 // nq > 0 rows behind the checks; asynchronous on `st`.
 static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t max_rlen,
                     int32_t min_score, int32_t k, int skip_self, const TopkOut &o, hipStream_t st, const pmx_pairs_opts_t *opts,
-                    int strand_mode = PMX_STRAND_FORWARD)
+                    int strand_mode = PMX_STRAND_FORWARD, const FrameRun *fr = nullptr)
 {
     const int64_t nr = R->count;
     if (nr == 0) return topk_no_pairs(nq, o, st);
     const int64_t n = nq * nr, first = q_first * nr;
-    ChunkAlign A(cfg, strand_mode);
+    ChunkAlign A(cfg, strand_mode, fr);
     const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, A.per), TOPK_CHUNK_MAX);
     TopkLists L;
     L.shape(chunk, nr, nq, k);
@@ -4736,9 +4949,9 @@ static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqs
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             const int rc = A.run(cfg, b, cn, max_qlen, max_rlen, first + c0, o.first_bad, st);
             return rc ? rc : L.merge(A.crec, A.cst, first + c0, cn, nr, q_first, min_score, skip_self, st);
-        }, strand_mode);
+        }, strand_mode, fr);
     if (rc) return rc;
-    return L.finish(nq, q_first, nr, o, A.chosen ? 1 : 0, st);
+    return L.finish(nq, q_first, nr, o, A.marked(), st);
 }
 
 // Both device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.
@@ -4746,13 +4959,16 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
                               int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
                               pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
                               int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
-                              void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand)
+                              void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
+                              bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
 {
+    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (topk_shape_check(Q, &R, q_first, nq, k, skip_self)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
+    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) ||
+        search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), (hipStream_t)stream));
         if (d_row_off) HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), (hipStream_t)stream));
@@ -4764,7 +4980,7 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const TopkOut o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_row_off, d_row_passing, d_counts, nullptr};
-    return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts, strand_mode);
+    return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts, strand_mode, fr);
 }
 
 extern "C" int pmx_search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
@@ -4785,6 +5001,16 @@ extern "C" int pmx_search_topk_stranded_device(const pmx_config_t *cfg, const pm
 {
     return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                               capacity, d_row_off, d_row_passing, d_counts, stream, opts, strand_mode, d_hit_strand);
+}
+
+extern "C" int pmx_search_topk_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                                 int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                                 pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                 int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                                 void *stream, const pmx_pairs_opts_t *opts, int frame_mode, const uint8_t *code, uint8_t *d_hit_frame)
+{
+    return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, true, frame_mode, code);
 }
 
 // Test hook (include/parasail_amd.h): the chunk loop of topk_run over records the caller made up instead of alignments -- the same
@@ -4837,9 +5063,12 @@ extern "C" void pmx_topk_hits_free(pmx_topk_hits_t *hits) { free(hits); }
 
 // Both host entries.  with_strand (pmx_search_topk_stranded): the block is a pmx_topk_strand_hits_t -- the fields of pmx_topk_hits_t, then
 // the strand bytes; without it the block and the kernels are pmx_search_topk's.
+// translated (pmx_search_topk_translated): a pmx_topk_frame_hits_t, the same layout with the frames in the last column.
 static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
-                            const pmx_topk_opts_t *opts, int strand_mode, bool with_strand, pmx_topk_hits_t **result)
+                            const pmx_topk_opts_t *opts, int strand_mode, bool with_strand, pmx_topk_hits_t **result,
+                            bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
 {
+    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
     if (!opts) { set_err("null opts"); return -1; }
@@ -4848,7 +5077,8 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (search_pairs_want_check(cfg, stats) || strand_mode_check(cfg, strand_mode)) return -1;
+    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) || search_pairs_want_check(cfg, stats) ||
+        strand_mode_check(cfg, strand_mode)) return -1;
     HostHits hh;
     // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics (, strand bytes)
     auto publish = [&]() -> int {
@@ -4869,6 +5099,8 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
     SetLens m;
     if (host_offsets && nr > 0 && window_host_lens(Q, R, PMX_PAIRS_RECT, q_first * nr, nq * nr, &m)) return -1;
+    if (fr) m.mq = fr->letters(m.mq);
+    const bool find_bad = !host_offsets || fr != nullptr;
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
     if (pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
@@ -4877,7 +5109,10 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     StreamGuard guard(st);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mr, nq * nr);    // (wrapped sets: no host lengths yet, and no hint from them)
-    if (!host_offsets && nr > 0 && window_device_lens(cfg, Q, R, &m, st)) return -1;
+    if (!host_offsets && nr > 0) {
+        if (window_device_lens(cfg, Q, R, &m, st)) return -1;
+        if (fr) m.mq = fr->letters(m.mq);
+    }
     // a slice's running state (key, record, statistics per kept entry) stays within the bound of the chunk buffers
     const int64_t ks = std::max<int64_t>(1, std::min<int64_t>(opts->k, nr));
     const int64_t per_row = ks * (int64_t)(8 + sizeof(pmx_record_t) + (stats ? sizeof(pmx_stats_t) : 0)) + 12;
@@ -4889,18 +5124,19 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
             doff = c.take<int64_t>((size_t)slice + 1); dpass = c.take<int64_t>((size_t)slice);
             dcnt = c.take<int64_t>(4);                   // kept, written, passing, first bad pair
         })) return -1;
-    if (!host_offsets) HIP_OR_RET(hipMemsetAsync(dcnt + 3, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
+    if (find_bad) HIP_OR_RET(hipMemsetAsync(dcnt + 3, 0xFF, sizeof(int64_t), st));        // (no bad pair yet: the largest unsigned value)
     try { hh.row_off.assign((size_t)nq + 1, 0); hh.row_passing.assign((size_t)nq, 0); } catch (const std::bad_alloc &) { set_err("out of memory"); return -1; }
     for (int64_t s0 = 0; s0 < nq; s0 += slice) {
         const int64_t sn = std::min<int64_t>(slice, nq - s0);
-        const TopkOut o = {d, sn * ks, doff, dpass, dcnt, host_offsets ? nullptr : dcnt + 3};
+        const TopkOut o = {d, sn * ks, doff, dpass, dcnt, find_bad ? dcnt + 3 : nullptr};
         int64_t h[4] = {0, 0, 0, 0};
-        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, m.mq, m.mr, opts->min_score, opts->k, opts->skip_self, o, st, &popts, strand_mode);
+        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, m.mq, m.mr, opts->min_score, opts->k, opts->skip_self, o, st, &popts, strand_mode, fr);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
-        if (!host_offsets && h[3] != -1) {
-            set_err("pair %lld (%lld, %lld): bad descriptor (index, window or length)", (long long)(h[3] - q_first * nr), (long long)(h[3] / nr), (long long)(h[3] % nr));
+        if (find_bad && h[3] != -1) {
+            set_err(fr ? "pair %lld (%lld, %lld): bad descriptor (index, window or length) or no frame to translate"
+                       : "pair %lld (%lld, %lld): bad descriptor (index, window or length)", (long long)(h[3] - q_first * nr), (long long)(h[3] / nr), (long long)(h[3] % nr));
             return -1;
         }
         hh.passing += h[2];
@@ -4924,3 +5160,11 @@ extern "C" int pmx_search_topk_stranded(const pmx_config_t *cfg, const pmx_seqse
     return search_topk_host(cfg, Q, R, q_first, nq, opts, strand_mode, true, (pmx_topk_hits_t **)result);
 }
 extern "C" void pmx_topk_strand_hits_free(pmx_topk_strand_hits_t *hits) { free(hits); }
+
+extern "C" int pmx_search_topk_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                          const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result)
+{
+    static_assert(sizeof(pmx_topk_frame_hits_t) == sizeof(pmx_topk_strand_hits_t) && offsetof(pmx_topk_frame_hits_t, frame) == offsetof(pmx_topk_strand_hits_t, strand), "one layout");
+    return search_topk_host(cfg, Q, R, q_first, nq, opts, PMX_STRAND_FORWARD, true, (pmx_topk_hits_t **)result, true, frame_mode, code);
+}
+extern "C" void pmx_topk_frame_hits_free(pmx_topk_frame_hits_t *hits) { free(hits); }

@@ -39,6 +39,9 @@ struct PmxBatch {
 };
 #define PMX_FLAG_RETRY16 4   // internal record flag: redo with the LDS-profile variant of the fast kernel
 #define PMX_FLAG_STRAND1 0x40000000   // internal record flag, chunk scratch of the stranded searches only: the record is the reverse strand's
+// internal record flags, chunk scratch of the translated searches only: three bits that hold the frame of the record
+#define PMX_FLAG_FRAME_SHIFT 27
+#define PMX_FLAG_FRAME_MASK 0x38000000
 
 // Fast path: local alignment, score + end positions, packed int16 lanes.
 // Returns 0 if launched, 1 if the shape is not supported by any instantiation (caller falls
@@ -291,7 +294,7 @@ int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts
                                  const pmx_pair_t *pairs, const pmx_record_t *rec, const pmx_stats_t *stats,
                                  pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t stream,
                                  uint8_t *hit_strand = nullptr /* optional: the strand byte of every hit written */,
-                                 int marked = 0 /* the records carry PMX_FLAG_STRAND1, to be taken out */);
+                                 int marked = 0 /* 1: the records carry PMX_FLAG_STRAND1, 2: their frame in PMX_FLAG_FRAME_MASK; to be taken out */);
 // The strand chosen by the entry.  resolve_both: n descriptors -> per * n slots (per 1: all reverse; per 2: slot 2 k forward,
 // 2 k + 1 reverse), arrays sized per * n (+ 2 for the lengths).  fold_strands: per * n slot records (statistics optional) -> n records,
 // statistics, strand bytes (optional) and validity bytes (optional); bad pairs get their record here; mark: PMX_FLAG_STRAND1 is set in
@@ -302,6 +305,23 @@ int pmx_launch_pairs_resolve_both(const pmx_pair_t *pairs, long long n, int per,
 int pmx_launch_pairs_fold_strands(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
                                   long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *strand, uint8_t *okf, hipStream_t stream);
 int pmx_launch_pairs_first_bad(const uint8_t *ok, long long n, long long index0, int64_t *first_bad, hipStream_t stream);
+// Translated queries.  resolve_frames: n descriptors -> per * n slots, slot per * k + i the frame (frame ? frame[k] : first
+// + i); qlen = the translated length L, qw = the nucleotide window's length W, qsrc = its first byte, sflag = the frame byte, ok = the
+// slot is a candidate (a frame that does not exist, and every slot of a bad pair, is a 1 x 1 placeholder with ok = 0); arrays sized
+// per * n (+ 2 for the lengths).  gather_translated: the stranded gather with codon -> letter on the query side.  fold_frames: per * n
+// slot records -> n records, statistics, frame bytes (optional) and validity bytes (optional); mark: the frame rides in the record.
+struct PmxCodeTable { uint8_t v[64]; };
+void pmx_genetic_code_host(uint8_t table[64]);
+int pmx_launch_pairs_resolve_frames(const pmx_pair_t *pairs, const uint8_t *frame, int first, int per, long long n,
+                                    const int64_t *q_off, long long q_count, long long q_bytes,
+                                    const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                                    int32_t *qlen, int32_t *rlen, int32_t *qw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream);
+int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
+                                       const int32_t *qlen, const int32_t *rlen, const int32_t *qw, const int64_t *qsrc, const int64_t *rsrc,
+                                       const uint8_t *ok, const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
+                                       uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t stream);
+int pmx_launch_pairs_fold_frames(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
+                                 long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *frame, uint8_t *okf, hipStream_t stream);
 // Per-query top-K (pmx_topk.hip; semantics: include/parasail_amd.h).  ks = min(k, |R|).  The running state of local row
 // li: st_keys / st_recs / st_stats[li * ks ..) hold st_held[li] entries in (score descending, j ascending) order, st_passing[li] = |P_i|
 // so far; the caller zeroes st_held (nq + 1 entries, the scan's input) and st_passing before the first chunk.  geometry: what the tile

@@ -21,6 +21,10 @@
 // and, for the entries that choose the strand themselves (pmx_align_pairs_both[_device], the _stranded searches):
 //   pmx_pairs_resolve_both_kernel       one descriptor -> `per` alignment slots: per 1 the reverse strand, per 2 forward then reverse
 //   pmx_pairs_fold_strands_kernel       the slots' records (and statistics) -> one record, statistics and strand per logical pair
+// and, for translated queries (the _translated entries, pmx_gather_pairs_translated_device):
+//   pmx_pairs_resolve_frames_kernel     one descriptor -> `per` slots (1, 3 or 6), one per frame: translated length, nucleotide window
+//   pmx_pairs_gather_translated_kernel  the gather that turns codons of the query window into amino acids, on either strand
+//   pmx_pairs_fold_frames_kernel        the slots' records (and statistics) -> one record, statistics and frame per logical pair
 //
 // All of them are bandwidth kernels in plain C++: vector loads and stores only.
 #include "pmx_common.h"
@@ -287,6 +291,191 @@ void pmx_pairs_fold_strands_kernel(const pmx_record_t *__restrict__ slot_rec, co
     if (okf) okf[k] = good ? 1 : 0;
 }
 
+// ---- translated queries (pmx_align_pairs_translated[_device], the _translated searches, pmx_gather_pairs_translated_device) --
+// The standard genetic code in NCBI order and the base classes its index is made of: T / U = 0, C = 1, A = 2, G = 3 in both cases,
+// every other byte 64 -- one such base lifts the index 16 b0 + 4 b1 + b2 to 64 or above, which is how a codon becomes 'X'.  The
+// complement of a base is its class ^ 2 and leaves every other byte what it was, so a reverse frame is the forward look-up with the
+// three bases read downwards and the index ^ 42.
+static const char pmx_code_std[65] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+struct PmxBaseTable { uint8_t v[256]; };
+static constexpr PmxBaseTable pmx_make_base_table()
+{
+    PmxBaseTable t{};
+    for (int i = 0; i < 256; ++i) t.v[i] = 64;
+    const char from[] = "TCAGU"; const uint8_t to[] = {0, 1, 2, 3, 0};
+    for (int k = 0; k < 5; ++k) { t.v[(unsigned char)from[k]] = to[k]; t.v[(unsigned char)from[k] + 32] = to[k]; }
+    return t;
+}
+__device__ const PmxBaseTable pmx_base_dev = pmx_make_base_table();
+
+// The resolve step for translated queries: logical pair k becomes `per` alignment slots, slot per * k + i in frame f = (frame ?
+// frame[k] : first + i).  The query side resolves to its nucleotide window (W bytes, any length); slot i then holds L = (W - off) / 3
+// letters, off = f % 3.  A frame with L = 0 does not exist: a 1 x 1 placeholder with ok = 0, which the fold passes over.  A bad
+// descriptor, a frame byte above 5 and a frame of the call whose L exceeds max_qlen make every slot of the pair such a placeholder.
+// The scans read per * n + 1 lengths.
+__global__ __launch_bounds__(256)
+void pmx_pairs_resolve_frames_kernel(const pmx_pair_t *__restrict__ pairs, const uint8_t *__restrict__ frame, int first, int per, long long n,
+                                     const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
+                                     const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
+                                     int32_t max_qlen, int32_t max_rlen,
+                                     int32_t *__restrict__ qlen, int32_t *__restrict__ rlen, int32_t *__restrict__ qw,
+                                     int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n + 2) return;
+    if (k >= n) { const long long t = (long long)per * n + (k - n); qlen[t] = 0; rlen[t] = 0; return; }
+    const pmx_pair_t p = pairs[k];
+    const unsigned f0 = frame ? frame[k] : (unsigned)first;
+    long long qs = 0, rs = 0;
+    const int32_t W = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, INT32_MAX, &qs);
+    const int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
+    bool good = W > 0 && rl > 0 && f0 + (unsigned)per <= 6u;
+    for (int i = 0; i < per; ++i) {                                // (the shortest offset of the call's frames has the longest L)
+        const int off = (int)((f0 + (unsigned)i) % 3u);
+        if (W > off && (W - off) / 3 > max_qlen) good = false;
+    }
+    const long long s = (long long)per * k;
+    for (int i = 0; i < per; ++i) {
+        const unsigned f = f0 + (unsigned)i;
+        const int off = (int)(f % 3u);
+        const int32_t L = good && W > off ? (W - off) / 3 : 0;
+        const bool have = L > 0;
+        qlen[s + i] = have ? L : 1; rlen[s + i] = have ? rl : 1; qw[s + i] = have ? W : 0;
+        qsrc[s + i] = have ? qs : 0; rsrc[s + i] = have ? rs : 0;
+        ok[s + i] = have ? 1 : 0; sflag[s + i] = good ? (uint8_t)f : 0;
+    }
+}
+
+// One amino acid: the three bases' classes to the index of the code, `flip` 0 for a forward frame and 42 for a reverse one.
+static __device__ __forceinline__ uint32_t pmx_codon(const uint8_t *cls, const uint8_t *cod, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t flip)
+{
+    const uint32_t i = ((uint32_t)cls[b0] << 4) | ((uint32_t)cls[b1] << 2) | (uint32_t)cls[b2];
+    return i < 64u ? (uint32_t)cod[i ^ flip] : (uint32_t)'X';
+}
+
+// The gather of pmx_pairs_gather_stranded_kernel with a translated query side: the same 16-lane group per window, the same forward
+// walk over the destination in aligned dwords, the reference side copied as there.  A query destination dword holds four letters,
+// twelve source bytes: three calls of pmx_window_dword (the same in-bounds test, the same byte-by-byte fallback at a set's first and
+// last bytes).  Forward frame `off`: letter p is the codon at window bytes off + 3 p ..; reverse frame: the codon at bytes W - 1 - off
+// - 3 p downwards, complemented -- the reversal is the order the twelve bytes are taken in, the complement the index ^ 42.  Classes
+// (256 bytes) and code (64 bytes, a kernel argument: a caller may bring its own) are staged in LDS.  The frame is uniform per group,
+// so the branch sits outside the dword loop.  A window whose end would cross its capacity is not written.
+__global__ __launch_bounds__(256)
+void pmx_pairs_gather_translated_kernel(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes, const uint8_t *__restrict__ r_buf, long long r_bytes,
+                                        const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen, const int32_t *__restrict__ qw,
+                                        const int64_t *__restrict__ qsrc, const int64_t *__restrict__ rsrc, const uint8_t *__restrict__ ok,
+                                        const uint8_t *__restrict__ sflag, const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
+                                        uint8_t *__restrict__ qout, long long q_cap, uint8_t *__restrict__ rout, long long r_cap, PmxCodeTable code)
+{
+    __shared__ uint8_t cls[256];
+    __shared__ uint8_t cod[64];
+    cls[threadIdx.x] = pmx_base_dev.v[threadIdx.x];
+    if (threadIdx.x < 64) cod[threadIdx.x] = code.v[threadIdx.x];
+    __syncthreads();
+    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
+    const int lane = threadIdx.x & 15;
+    if (g >= 2 * n) return;
+    const long long k = g >> 1;
+    const bool side = (g & 1) != 0;
+    const int64_t o0 = side ? roff[k] : qoff[k], o1 = side ? roff[k + 1] : qoff[k + 1];
+    if (o1 > (side ? r_cap : q_cap)) return;
+    uint8_t *dst = (side ? rout : qout) + o0;
+    if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
+    const uint8_t *buf = side ? r_buf : q_buf;
+    const long long len = side ? rlen[k] : qlen[k];             // destination bytes: letters on the query side
+    const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
+    const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
+    long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
+    if (head > len) head = len;
+    const long long nd = (len - head) >> 2, done = head + 4 * nd;
+    uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
+    if (side) {
+        if (lane < head) dst[lane] = src[lane];
+        const uint8_t *s0 = src + head;
+        for (long long x = lane; x < nd; x += 16)
+            d0[x] = pmx_window_dword(s0 + 4 * x, lo_bound, hi_bound);
+        if (lane < len - done) dst[done + lane] = src[done + lane];
+        return;
+    }
+    const unsigned f = sflag[k];
+    if (f >= 3) {
+        const uint8_t *top = src + qw[k] - 1 - (f - 3);         // letter p: top[-3 p], top[-3 p - 1], top[-3 p - 2], complemented
+        if (lane < head) dst[lane] = (uint8_t)pmx_codon(cls, cod, top[-3 * lane], top[-3 * lane - 1], top[-3 * lane - 2], 42u);
+        const uint8_t *s0 = top - 3 * head - 11;                // the lowest source byte of destination dword 0
+        for (long long x = lane; x < nd; x += 16) {
+            const uint8_t *s = s0 - 12 * x;
+            const uint32_t a = pmx_window_dword(s, lo_bound, hi_bound), b = pmx_window_dword(s + 4, lo_bound, hi_bound),
+                           c = pmx_window_dword(s + 8, lo_bound, hi_bound);
+            d0[x] = pmx_codon(cls, cod, c >> 24, (c >> 16) & 0xFF, (c >> 8) & 0xFF, 42u) |
+                    (pmx_codon(cls, cod, c & 0xFF, b >> 24, (b >> 16) & 0xFF, 42u) << 8) |
+                    (pmx_codon(cls, cod, (b >> 8) & 0xFF, b & 0xFF, a >> 24, 42u) << 16) |
+                    (pmx_codon(cls, cod, (a >> 16) & 0xFF, (a >> 8) & 0xFF, a & 0xFF, 42u) << 24);
+        }
+        if (lane < len - done) {
+            const uint8_t *t = top - 3 * (done + lane);
+            dst[done + lane] = (uint8_t)pmx_codon(cls, cod, t[0], t[-1], t[-2], 42u);
+        }
+        return;
+    }
+    const uint8_t *base = src + f;                              // letter p: base[3 p], base[3 p + 1], base[3 p + 2]
+    if (lane < head) dst[lane] = (uint8_t)pmx_codon(cls, cod, base[3 * lane], base[3 * lane + 1], base[3 * lane + 2], 0u);
+    const uint8_t *s0 = base + 3 * head;
+    for (long long x = lane; x < nd; x += 16) {
+        const uint8_t *s = s0 + 12 * x;
+        const uint32_t a = pmx_window_dword(s, lo_bound, hi_bound), b = pmx_window_dword(s + 4, lo_bound, hi_bound),
+                       c = pmx_window_dword(s + 8, lo_bound, hi_bound);
+        d0[x] = pmx_codon(cls, cod, a & 0xFF, (a >> 8) & 0xFF, (a >> 16) & 0xFF, 0u) |
+                (pmx_codon(cls, cod, a >> 24, b & 0xFF, (b >> 8) & 0xFF, 0u) << 8) |
+                (pmx_codon(cls, cod, (b >> 16) & 0xFF, b >> 24, c & 0xFF, 0u) << 16) |
+                (pmx_codon(cls, cod, (c >> 8) & 0xFF, (c >> 16) & 0xFF, c >> 24, 0u) << 24);
+    }
+    if (lane < len - done) {
+        const uint8_t *t = base + 3 * (done + lane);
+        dst[done + lane] = (uint8_t)pmx_codon(cls, cod, t[0], t[1], t[2], 0u);
+    }
+}
+
+// The slots of logical pair k back to one record: among the slots with ok != 0 the highest score, the lowest slot -- the lowest
+// frame -- on a tie (only the score is compared).  The record is the winner's sixteen bytes, the statistics are the winner's, the
+// frame is the winner's sflag.  No candidate (a bad descriptor, or no frame exists): {0, -1, -1, PMX_FLAG_BAD_PAIR}, zero statistics,
+// frame 0.  mark: the frame also rides in the record (PMX_FLAG_FRAME_MASK), for records that stay in chunk scratch on their way
+// through selection or the top-K lists; the kernels that write a caller's hit arrays strip it.  okf (optional): the logical pair's
+// validity byte.  One thread per logical pair, as pmx_pairs_fold_strands_kernel.
+__global__ __launch_bounds__(256)
+void pmx_pairs_fold_frames_kernel(const pmx_record_t *__restrict__ slot_rec, const pmx_stats_t *__restrict__ slot_stats,
+                                  const uint8_t *__restrict__ ok, const uint8_t *__restrict__ sflag, long long n, int per, int mark,
+                                  pmx_record_t *__restrict__ rec, pmx_stats_t *__restrict__ stats, uint8_t *__restrict__ frame,
+                                  uint8_t *__restrict__ okf)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const long long s = (long long)per * k;
+    uint4 w = make_uint4(0u, 0xFFFFFFFFu, 0xFFFFFFFFu, (uint32_t)PMX_FLAG_BAD_PAIR);
+    pmx_stats_t ws; ws.matches = 0; ws.similar = 0; ws.length = 0;
+    const uint4 *sr = reinterpret_cast<const uint4 *>(slot_rec + s);
+    long long from = -1;
+    for (int i = 0; i < per; ++i) {
+        if (!ok[s + i]) continue;
+        const uint4 b = sr[i];
+        if (from < 0 || (int32_t)b.x > (int32_t)w.x) { w = b; from = s + i; }
+    }
+    unsigned fb = 0;
+    if (from >= 0) {
+        fb = sflag[from];
+        if (stats) ws = slot_stats[from];
+    }
+    if (mark) w.w |= fb << PMX_FLAG_FRAME_SHIFT;
+    if (((uintptr_t)rec & 15) == 0)
+        *reinterpret_cast<uint4 *>(rec + k) = w;
+    else {
+        pmx_record_t r; r.score = (int32_t)w.x; r.end_query = (int32_t)w.y; r.end_ref = (int32_t)w.z; r.flags = (int32_t)w.w;
+        rec[k] = r;
+    }
+    if (stats) stats[k] = ws;
+    if (frame) frame[k] = (uint8_t)fb;
+    if (okf) okf[k] = from >= 0 ? 1 : 0;
+}
+
 // Bad pairs on the device CIGAR road, between the walk and the text scan: the record, no ops, no text, begins -1 / -1.
 __global__ __launch_bounds__(256)
 void pmx_pairs_fixup_cigar_kernel(const uint8_t *__restrict__ ok, long long n, pmx_record_t *__restrict__ rec,
@@ -364,6 +553,7 @@ void pmx_rect_pairs_enumerate_kernel(unsigned long long nr, long long first, lon
 // 16-byte accesses where both sides are 16-byte aligned (they are for hipMalloc'ed arrays), four 8-byte ones otherwise.
 // The stranded searches: `marked` says the chunk's records carry their strand as PMX_FLAG_STRAND1, which is taken out of the record on
 // its way to the caller; hit_strand (optional) receives it as a byte.  A launch without either copies the record as it is.
+// marked == 2 (the translated searches): the records carry their frame in PMX_FLAG_FRAME_MASK instead, and the byte is the frame.
 __global__ __launch_bounds__(256)
 void pmx_pairs_append_hits_kernel(const int64_t *__restrict__ idx, const int64_t *__restrict__ chunk_counts, const int64_t *__restrict__ counts,
                                   long long capacity, long long index0, const pmx_pair_t *__restrict__ pairs,
@@ -389,8 +579,13 @@ void pmx_pairs_append_hits_kernel(const int64_t *__restrict__ idx, const int64_t
         }
         if (hit_index) hit_index[pos] = index0 + k;
         pmx_record_t r = rec[k];
-        if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_STRAND1) != 0);
-        if (marked) r.flags &= ~PMX_FLAG_STRAND1;
+        if (marked == 2) {                                        // (the translated searches: the byte is the frame)
+            if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_FRAME_MASK) >> PMX_FLAG_FRAME_SHIFT);
+            r.flags &= ~PMX_FLAG_FRAME_MASK;
+        } else {
+            if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_STRAND1) != 0);
+            if (marked) r.flags &= ~PMX_FLAG_STRAND1;
+        }
         hit_recs[pos] = r;
         if (hit_stats) hit_stats[pos] = stats[k];
     }
@@ -494,6 +689,35 @@ int pmx_launch_pairs_fold_strands(const pmx_record_t *slot_rec, const pmx_stats_
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_fold_strands_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slot_rec, slot_stats, ok, sflag,
                        n, per, mark, rec, stats, strand, okf);
+    return pmx_pairs_launched();
+}
+void pmx_genetic_code_host(uint8_t table[64]) { for (int i = 0; i < 64; ++i) table[i] = (uint8_t)pmx_code_std[i]; }
+int pmx_launch_pairs_resolve_frames(const pmx_pair_t *pairs, const uint8_t *frame, int first, int per, long long n,
+                                    const int64_t *q_off, long long q_count, long long q_bytes,
+                                    const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
+                                    int32_t *qlen, int32_t *rlen, int32_t *qw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_resolve_frames_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, frame, first, per, n,
+                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qw, qsrc, rsrc, ok, sflag);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
+                                       const int32_t *qlen, const int32_t *rlen, const int32_t *qw, const int64_t *qsrc, const int64_t *rsrc,
+                                       const uint8_t *ok, const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
+                                       uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_gather_translated_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                       qlen, rlen, qw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
+    return pmx_pairs_launched();
+}
+int pmx_launch_pairs_fold_frames(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
+                                 long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *frame, uint8_t *okf, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_pairs_fold_frames_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slot_rec, slot_stats, ok, sflag,
+                       n, per, mark, rec, stats, frame, okf);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *rec, int32_t *nops, int32_t *textlen, int32_t *beg, hipStream_t st)

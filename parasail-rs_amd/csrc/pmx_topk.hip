@@ -218,7 +218,8 @@ void pmx_topk_row_kernel(const pmx_record_t *__restrict__ rec, const pmx_stats_t
 }
 
 // One wave per row.  Stores to the caller's hit arrays only at positions below `capacity`.  The stranded search: the lists' records carry
-// their strand as PMX_FLAG_STRAND1 (`marked`), taken out here; hit_strand (optional) receives it as a byte.
+// their strand as PMX_FLAG_STRAND1 (`marked`), taken out here; hit_strand (optional) receives it as a byte.  marked == 2 (the
+// translated search): they carry their frame in PMX_FLAG_FRAME_MASK instead, and the byte is the frame.
 __global__ __launch_bounds__(256)
 void pmx_topk_emit_kernel(long long nq, long long q_first, unsigned long long nr, unsigned ks,
                           const uint64_t *__restrict__ st_keys, const pmx_record_t *__restrict__ st_recs, const pmx_stats_t *__restrict__ st_stats,
@@ -242,8 +243,13 @@ void pmx_topk_emit_kernel(long long nq, long long q_first, unsigned long long nr
         if (hit_pairs) { pmx_pair_t d; d.q = ai; d.r = j; d.q_beg = 0; d.q_len = -1; d.r_beg = 0; d.r_len = -1; hit_pairs[pos] = d; }
         if (hit_index) hit_index[pos] = (int64_t)((unsigned long long)ai * nr + (unsigned long long)j);
         pmx_record_t r = st_recs[l0 + x];
-        if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_STRAND1) != 0);
-        if (marked) r.flags &= ~PMX_FLAG_STRAND1;
+        if (marked == 2) {                                             // (the translated search: the byte is the frame)
+            if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_FRAME_MASK) >> PMX_FLAG_FRAME_SHIFT);
+            r.flags &= ~PMX_FLAG_FRAME_MASK;
+        } else {
+            if (hit_strand) hit_strand[pos] = (uint8_t)((r.flags & PMX_FLAG_STRAND1) != 0);
+            if (marked) r.flags &= ~PMX_FLAG_STRAND1;
+        }
         hit_recs[pos] = r;
         if (hit_stats) hit_stats[pos] = st_stats[l0 + x];
     }
