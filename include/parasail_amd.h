@@ -826,6 +826,73 @@ int  pmx_search_topk_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
                                 const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result);
 void pmx_topk_frame_hits_free(pmx_topk_frame_hits_t *hits);
 
+/* Reference-side translation (extension): protein queries against a set of nucleotide sequences -- genes, transcripts, contigs --,
+ * the tblastn pairing.  The text above holds with the sides exchanged; what follows states it in full.
+ *
+ * Q holds proteins and R holds nucleotides.  The genetic code, the `code` argument, the base classes ("ACGTUacgtu"; any other byte in
+ * a codon gives 'X'; stops give '*'), the tables and the frame modes (0 .. 5, PMX_FRAMES_FORWARD / _REVERSE / _ALL) are the ones
+ * above.  Frame f = 0, 1, 2 reads the REFERENCE window as stored, from offset off = f; f = 3, 4, 5 reads the reference window
+ * reverse-complemented as pmx_complement_table defines it (complemented, then reversed), from offset off = f - 3.  A window of W
+ * nucleotides has L = (W - off) / 3 letters (integer division; 0 for W < off); a frame with L = 0 does not exist for the pair.
+ * max_rlen bounds L -- what the alignment kernels see -- so the nucleotide window may be up to 3 max_rlen + 2 bytes; a frame of the
+ * call's mode with L > max_rlen makes the pair bad.  The query window is bounded by max_qlen as in the untranslated entries and is
+ * never translated: no entry takes two frame arguments.
+ * ALL POSITIONS OF A RECORD (end_ref, begins of a CIGAR pass) ARE IN LETTERS OF THE TRANSLATED REFERENCE.  Back to stored bytes:
+ * letter p of a forward frame is sequence bytes r_beg + off + 3 p .. r_beg + off + 3 p + 2; letter p of a reverse frame is sequence
+ * bytes r_beg + W - 1 - (off + 3 p) downwards (three bytes, complemented).
+ *
+ * The fold rule is the one above: among the frames that exist the highest score wins, only the score is compared, a tie goes to the
+ * lowest frame; record and statistics are the winner's, byte for byte; no frame, or a bad descriptor: {0, -1, -1,
+ * PMX_FLAG_BAD_PAIR}, zero statistics, frame 0.  Selection, the counts and the top-K order (score descending, reference index
+ * ascending) work on folded records, so a reference appears at most once in a row.  The frame byte of a record or hit names the
+ * REFERENCE's frame.
+ *
+ * The defining equivalence.  In a single-frame mode every output is byte-identical to the corresponding untranslated entry
+ * (pmx_align_pairs_device, pmx_search_pairs_device, pmx_search_topk_device) over a reference set whose sequences -- for a windowed
+ * descriptor: whose window -- were translated on the host in that frame.  In a multi-frame mode every output equals the fold rule
+ * applied to the single-frame results.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: a frame mode outside 0 .. 8; a frame byte per pair together with
+ * a frame mode other than 0; a PSSM matrix (it would belong to the protein query, but the batch PSSM forms are not wired through
+ * these entries); PMX_WANT_CIGAR (the CIGAR route: hit pairs + frame bytes -> pmx_gather_pairs_translated_ref_device ->
+ * pmx_align_batch_cigar_device); a multi-frame mode without a frame output (the device search entries: with capacity > 0);
+ * everything the corresponding untranslated entry refuses, with the same texts.  The host entries size max_rlen from the longest
+ * nucleotide reference window and name the first pair that is bad or has no frame.
+ *
+ * The argument lists are those of the _translated entries; d_frame / frame_mode / d_frame_out / d_hit_frame speak of the reference's
+ * frame; the result blocks pmx_frame_hits_t and pmx_topk_frame_hits_t and their free functions are reused.
+ * pmx_gather_pairs_translated_ref_device: d_qout receives the query windows as they are, d_rout the translated reference windows. */
+int pmx_gather_pairs_translated_ref_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                           const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                           uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                           uint8_t *d_ok /* n validity bytes, optional */, void *stream);
+int pmx_align_pairs_translated_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                          int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_frame, int frame_mode, const uint8_t *code,
+                                          int32_t max_qlen, int32_t max_rlen,
+                                          pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
+                                          const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                   int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
+                                   pmx_record_t *out, pmx_stats_t *stats_out /* NULL unless WANT_STATS */, uint8_t *frame_out,
+                                   const pmx_pairs_opts_t *opts);
+int pmx_search_pairs_translated_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                           int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                           int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                           pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                           int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                           int frame_mode, const uint8_t *code, uint8_t *d_hit_frame);
+int pmx_search_pairs_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                    const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int frame_mode, const uint8_t *code,
+                                    pmx_frame_hits_t **result);
+int pmx_search_topk_translated_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                          int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                          pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                          int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                          void *stream, const pmx_pairs_opts_t *opts,
+                                          int frame_mode, const uint8_t *code, uint8_t *d_hit_frame);
+int pmx_search_topk_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                   const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -316,6 +316,22 @@ _sig("pmx_search_topk_translated_device", C.c_int, C.POINTER(pmx_config_t), C.c_
 _sig("pmx_search_topk_translated", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.c_int, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_frame_hits_t)))
 _sig("pmx_topk_frame_hits_free", None, C.POINTER(pmx_topk_frame_hits_t))
+_sig("pmx_gather_pairs_translated_ref_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_align_pairs_translated_ref_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_translated_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_search_pairs_translated_ref_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_void_p)
+_sig("pmx_search_pairs_translated_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+     C.POINTER(pmx_pair_search_opts_t), C.c_int, C.c_void_p, C.POINTER(C.POINTER(pmx_frame_hits_t)))
+_sig("pmx_search_topk_translated_ref_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_void_p)
+_sig("pmx_search_topk_translated_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+     C.POINTER(pmx_topk_opts_t), C.c_int, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_frame_hits_t)))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -940,7 +956,7 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return (out, stats) if stats is not None else out
 
-    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False, frame=None, code=None):
+    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False, frame=None, code=None, ref_frame=None):
         """Pairs by index and window into device-resident sequence sets (SeqSet; Q may be R).  `pairs`: a PAIR_DTYPE array, or
         an iterable of (q, r) / (q, r, q_beg, q_len, r_beg, r_len) tuples (len -1: to the sequence's end).  Record k is the record
         of the pair (query window, reference window) k, end positions relative to the windows.  A bad descriptor raises BatchError
@@ -952,7 +968,9 @@ class Aligner:
         nucleotides, R proteins, and the query windows are translated (translate() restates the rule) -- a frame 0 .. 5, "forward" /
         "reverse" / "all" (FRAMES_*: the best of those frames, a tie to the lowest) or one frame byte per pair; positions are in
         letters of the translated query; returns (records, frames) or (records, stats, frames).  code: 64 letters that replace
-        genetic_code_table()."""
+        genetic_code_table().  `ref_frame` (not together with frame or strand): the opposite pairing -- Q holds proteins, R
+        nucleotides, the REFERENCE windows are translated; the same values and results, positions in letters of the translated
+        reference, the frames are the reference's."""
         if not self._profile.is_null():
             raise BatchError("align_pairs takes no profile")
         pairs = as_pairs(pairs)
@@ -961,18 +979,17 @@ class Aligner:
         out = np.zeros(n, dtype=RECORD_DTYPE)
         stats = np.zeros(n, dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
         opts = pmx_pairs_opts_t(int(chunk_pairs))
+        entry, frame = _frame_side(frame, ref_frame, strand is not None, lib.pmx_align_pairs_translated, lib.pmx_align_pairs_translated_ref)
         if frame is not None:
-            if strand is not None:
-                raise BatchError("frame and strand exclude each other: a reverse frame is the reverse strand translated")
             if cigar:
                 cfg.want |= WANT_CIGAR                   # (refused by the entry, which names the route)
             mode, per_pair = _frame_mode(frame, n)
             code = _code_arg(code)
             won = np.zeros(n, dtype=np.uint8)
-            rc = lib.pmx_align_pairs_translated(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
-                                                per_pair.ctypes.data if per_pair is not None else None, mode,
-                                                code.ctypes.data if code is not None else None, out.ctypes.data,
-                                                stats.ctypes.data if stats is not None else None, won.ctypes.data, C.byref(opts))
+            rc = entry(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
+                       per_pair.ctypes.data if per_pair is not None else None, mode,
+                       code.ctypes.data if code is not None else None, out.ctypes.data,
+                       stats.ctypes.data if stats is not None else None, won.ctypes.data, C.byref(opts))
             if rc:
                 raise BatchError(lib.pmx_last_error().decode())
             return (out, stats, won) if stats is not None else (out, won)
@@ -1035,7 +1052,7 @@ class Aligner:
         return (out, stats) if stats is not None else out
 
     def search_pairs(self, Q, R=None, min_score=0, pairs=None, first=0, count=None, stats=False, max_hits=0, chunk_pairs=0,
-                     slice_pairs=0, strand=0, frame=None, code=None):
+                     slice_pairs=0, strand=0, frame=None, code=None, ref_frame=None):
         """Set search: the pairs of an enumeration that score at least min_score, as a PairHits in enumeration order.  `pairs`
         given: those descriptors of Q x R (as align_pairs takes them; R None: Q); else R None: pairs [first, first + count) of the
         strict upper triangle of Q (the numbering of align_all_pairs); else the same window of the rectangle Q x R, row-major
@@ -1044,7 +1061,9 @@ class Aligner:
         device; chunk_pairs and slice_pairs never change the result.  strand: 0 the queries as stored, 1 reverse-complemented,
         "both" (or STRAND_BOTH) the better strand of every pair, chosen before the threshold; PairHits.strand tells which.
         frame (not together with strand): nucleotide queries against proteins, translated in frame 0 .. 5 or the best of "forward" /
-        "reverse" / "all" frames, chosen before the threshold; PairHits.frame tells which (code: as in align_pairs)."""
+        "reverse" / "all" frames, chosen before the threshold; PairHits.frame tells which (code: as in align_pairs).  ref_frame (not
+        together with frame or strand): protein queries against nucleotide references, the references translated the same way;
+        PairHits.frame is then the reference's frame."""
         if not self._profile.is_null():
             raise BatchError("search_pairs takes no profile")
         cfg = self._config()
@@ -1066,24 +1085,23 @@ class Aligner:
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
                 pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts))
         mode = _strand_mode(strand)
+        entry, frame = _frame_side(frame, ref_frame, mode != STRAND_FORWARD, lib.pmx_search_pairs_translated, lib.pmx_search_pairs_translated_ref)
         if frame is not None:
-            if mode != STRAND_FORWARD:
-                raise BatchError("frame and strand exclude each other: a reverse frame is the reverse strand translated")
             code = _code_arg(code)
-            return _hits_call(lib.pmx_search_pairs_translated, args + (_frame_mode(frame)[0], code.ctypes.data if code is not None else None),
+            return _hits_call(entry, args + (_frame_mode(frame)[0], code.ctypes.data if code is not None else None),
                               pmx_frame_hits_t, PairHits, lib.pmx_frame_hits_free)
         if mode != STRAND_FORWARD:
             return _hits_call(lib.pmx_search_pairs_stranded, args + (mode,), pmx_strand_hits_t, PairHits, lib.pmx_strand_hits_free)
         return _hits_call(lib.pmx_search_pairs, args, pmx_pair_hits_t, PairHits, lib.pmx_pair_hits_free)
 
     def search_topk(self, Q, R=None, k=10, min_score=INT32_MIN, skip_self=False, first_row=0, rows=None, stats=False, chunk_pairs=0,
-                    slice_rows=0, strand=0, frame=None, code=None):
+                    slice_rows=0, strand=0, frame=None, code=None, ref_frame=None):
         """Per-query top-K: for each query row [first_row, first_row + rows) of Q the best k references of R (None: Q) with score
         >= min_score, in (score descending, reference index ascending) order, as a TopKHits.  rows None: to the last row.
         skip_self (R is Q) leaves the pair (i, i) out.  stats=True adds the hits' statistics.  Only the hits leave the device;
         chunk_pairs and slice_rows never change the result.  strand as in search_pairs: with "both" a reference is one
         candidate with its better strand, and TopKHits.strand tells which.  frame as in search_pairs: a reference is one candidate
-        with its best frame, and TopKHits.frame tells which."""
+        with its best frame, and TopKHits.frame tells which.  ref_frame as in search_pairs: the references are the translated side."""
         if not self._profile.is_null():
             raise BatchError("search_topk takes no profile")
         cfg = self._config()
@@ -1094,11 +1112,10 @@ class Aligner:
         opts = pmx_topk_opts_t(int(min_score), int(k), 1 if skip_self else 0, int(chunk_pairs), int(slice_rows))
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows), C.byref(opts))
         mode = _strand_mode(strand)
+        entry, frame = _frame_side(frame, ref_frame, mode != STRAND_FORWARD, lib.pmx_search_topk_translated, lib.pmx_search_topk_translated_ref)
         if frame is not None:
-            if mode != STRAND_FORWARD:
-                raise BatchError("frame and strand exclude each other: a reverse frame is the reverse strand translated")
             code = _code_arg(code)
-            return _hits_call(lib.pmx_search_topk_translated, args + (_frame_mode(frame)[0], code.ctypes.data if code is not None else None),
+            return _hits_call(entry, args + (_frame_mode(frame)[0], code.ctypes.data if code is not None else None),
                               pmx_topk_frame_hits_t, TopKHits, lib.pmx_topk_frame_hits_free)
         if mode != STRAND_FORWARD:
             return _hits_call(lib.pmx_search_topk_stranded, args + (mode,), pmx_topk_strand_hits_t, TopKHits, lib.pmx_topk_strand_hits_free)
@@ -1304,6 +1321,20 @@ def _strand_mode(strand):
             raise BatchError("strand is 0, 1 or \"both\"")
         return names[strand]
     return int(strand)
+
+
+def _frame_side(frame, ref_frame, stranded, query_entry, ref_entry):
+    """frame= / ref_frame= of align_pairs, search_pairs and search_topk -> (the entry that translates that side, the frame argument);
+    (None, None) without either."""
+    if ref_frame is not None and frame is not None:
+        raise BatchError("frame and ref_frame exclude each other: no entry translates both sides")
+    if ref_frame is not None and stranded:
+        raise BatchError("ref_frame and strand exclude each other: a strand is the query's, and the query is protein")
+    if frame is not None and stranded:
+        raise BatchError("frame and strand exclude each other: a reverse frame is the reverse strand translated")
+    if ref_frame is not None:
+        return ref_entry, ref_frame
+    return (query_entry, frame) if frame is not None else (None, None)
 
 
 def _frame_mode(frame, n=None):
@@ -1737,6 +1768,60 @@ def search_topk_translated_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, mi
     opts = pmx_pairs_opts_t(int(chunk_pairs))
     code = _code_arg(code)
     rc = lib.pmx_search_topk_translated_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
+                                               max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
+                                               d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream,
+                                               C.byref(opts), int(frame_mode), code.ctypes.data if code is not None else None, d_hit_frame)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def gather_pairs_translated_ref_device(Q, R, n, d_pairs, d_frame, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff,
+                                   d_ok=None, stream=0, code=None):
+    """gather_pairs_device with the reference windows translated (d_frame: a frame byte per pair or None for frame 0; max_rlen bounds
+    the translated length): the building block of a CIGAR pass over the hits of a reference-side translated search."""
+    code = _code_arg(code)
+    rc = lib.pmx_gather_pairs_translated_ref_device(Q._handle(), R._handle(), n, d_pairs, d_frame, code.ctypes.data if code is not None else None,
+                                                max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_translated_ref_device(cfg, Q, R, n, d_pairs, d_frame, frame_mode, max_qlen, max_rlen, d_out, d_stats=None, d_frame_out=None,
+                                  stream=0, chunk_pairs=0, code=None):
+    """align_pairs_device with translated references (Q proteins, R nucleotides): d_frame (a frame byte per pair, frame_mode 0) or None and a frame mode (0 .. 5,
+    FRAMES_*); record k is the best frame's, byte for byte, d_frame_out (n bytes) says which."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_align_pairs_translated_ref_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_frame, int(frame_mode),
+                                               code.ctypes.data if code is not None else None, max_qlen, max_rlen, d_out, d_stats, d_frame_out,
+                                               stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_pairs_translated_ref_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs,
+                                   d_hit_stats, capacity, d_counts, frame_mode, d_hit_frame=None, stream=0, chunk_pairs=0, code=None):
+    """search_pairs_device with translated references and a frame mode: the threshold looks at the folded records; d_hit_frame (one
+    byte per hit; required in a multi-frame mode with capacity > 0) receives the hits' frames.  d_hit_pairs and d_hit_frame feed
+    gather_pairs_translated_ref_device unchanged."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_search_pairs_translated_ref_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(shape), int(first),
+                                                int(n), d_pairs, max_qlen, max_rlen, int(min_score), d_hit_pairs, d_hit_index, d_hit_recs,
+                                                d_hit_stats, int(capacity), d_counts, stream, C.byref(opts), int(frame_mode),
+                                                code.ctypes.data if code is not None else None, d_hit_frame)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_topk_translated_ref_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs,
+                                  d_hit_stats, capacity, d_row_off, d_row_passing, d_counts, frame_mode, d_hit_frame=None, stream=0,
+                                  chunk_pairs=0, code=None):
+    """search_topk_device with translated references and a frame mode: a reference is one candidate with its folded record;
+    d_hit_frame (one byte per hit; required in a multi-frame mode with capacity > 0) receives the hits' frames."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_search_topk_translated_ref_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
                                                max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
                                                d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream,
                                                C.byref(opts), int(frame_mode), code.ctypes.data if code is not None else None, d_hit_frame)

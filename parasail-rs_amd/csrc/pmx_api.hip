@@ -3739,16 +3739,20 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 // reverse-complemented -- and the buffers hold per * cn windows; the body still gets c0 and cn in logical pairs.
 // fr != nullptr (the _translated entries; d_strand is then nullptr and the strand mode forward): the query windows are
 // nucleotides translated on their way into the buffers, per = fr->per alignment slots per pair, one per frame; max_qlen bounds the
-// translated length, so the query buffer holds per * cn * max_qlen letters.
+// translated length, so the query buffer holds per * cn * max_qlen letters.  fr->ref (the _translated_ref entries): the
+// same with the sides exchanged -- the reference windows are the nucleotides, max_rlen bounds their translated length, and the
+// reference buffer holds per * cn * max_rlen letters.
 static int strand_slots(int strand_mode) { return strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
+enum { TR_NONE = 0, TR_QUERY = 1, TR_REF = 2 };      // which side an entry translates (the search and top-K entries' `translated`)
 struct FrameRun {
     int first = 0, per = 1;                 // the frames first .. first + per - 1 for every pair ...
     const uint8_t *d_frame = nullptr;       // ... or (listed pairs, per 1) a frame byte per pair
     PmxCodeTable code;
+    bool ref = false;                       // the translated side: the query's windows, or (true) the reference's
     int min_off() const { return per == 1 && !d_frame ? first % 3 : 0; }      // the smallest offset a frame of the call reads from
     int32_t letters(int32_t w) const { return std::max<int32_t>(1, (w - min_off()) / 3); }   // the longest translation of w nucleotides
 };
-struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; int32_t *qw; };
+struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; int32_t *tw /* the translated side's W */; };
 template <typename Body>
 static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first, int shape,
                      const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body,
@@ -3768,7 +3772,7 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
                 B[s].qsrc = c.take<int64_t>(slots); B[s].rsrc = c.take<int64_t>(slots);
                 B[s].ok = c.take<uint8_t>(slots);
                 B[s].sflag = stranded ? c.take<uint8_t>(slots) : nullptr;
-                B[s].qw = fr ? c.take<int32_t>(slots) : nullptr;
+                B[s].tw = fr ? c.take<int32_t>(slots) : nullptr;
             }
             scan = c.take<unsigned char>(scan_bytes);           // (one: the scans of all chunks run in order on one stream)
         })) return -1;
@@ -3791,7 +3795,7 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         const int64_t sn = cn * per;                              // the chunk's alignment slots
         if (!rc) rc = fr       ? pmx_launch_pairs_resolve_frames(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
                                                                  R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                                                 b.qlen, b.rlen, b.qw, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
+                                                                 b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep, fr->ref)
                     : chosen   ? pmx_launch_pairs_resolve_both(pc, cn, per, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
                                                                b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
                     : stranded ? pmx_launch_pairs_resolve_stranded(pc, d_strand + c0, cn, Q->d_off, Q->count, Q->bytes,
@@ -3801,8 +3805,8 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
                                                           b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.qlen, sn, b.qoff, scan, scan_bytes, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.rlen, sn, b.roff, scan, scan_bytes, prep);
-        if (!rc) rc = fr       ? pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qw, b.qsrc, b.rsrc, b.ok,
-                                                                    b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep)
+        if (!rc) rc = fr       ? pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
+                                                                    b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep, fr->ref)
                     : stranded ? pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
                                                                   b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, prep)
                                : pmx_launch_pairs_gather(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
@@ -3924,22 +3928,29 @@ extern "C" int pmx_align_pairs_both_device(const pmx_config_t *cfg, const pmx_se
                           pairs_chunk(n, max_qlen, max_rlen, opts, 2));
 }
 
-// ---- translated queries ----
+// ---- a translated side: the query's or the reference's (2.5j) ----
 extern "C" void pmx_genetic_code_table(uint8_t table[64]) { if (table) pmx_genetic_code_host(table); }
 
-// What every translated entry refuses about its frames, matrix and outputs, before any GPU work.  *fr: the run's frames and code.
-static int frames_check(const pmx_config_t *cfg, int frame_mode, const uint8_t *d_frame, const uint8_t *code, FrameRun *fr)
+// What every translated entry refuses about its frames, matrix and outputs, before any GPU work.  *fr: the run's frames, code and side
+// (ref: the _translated_ref entries).
+static int frames_check(const pmx_config_t *cfg, int frame_mode, const uint8_t *d_frame, const uint8_t *code, FrameRun *fr, bool ref = false)
 {
     if (frame_mode < 0 || frame_mode > PMX_FRAMES_ALL) {
         set_err("frame mode %d is outside 0 .. 8 (a frame 0 .. 5, PMX_FRAMES_FORWARD, PMX_FRAMES_REVERSE, PMX_FRAMES_ALL)", frame_mode); return -1;
     }
     if (d_frame && frame_mode != 0) { set_err("a frame byte per pair takes frame mode 0, not %d", frame_mode); return -1; }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("a translated query takes no PSSM matrix: a profile belongs to one protein query"); return -1; }
-    if (cfg->want & PMX_WANT_CIGAR) {
-        set_err("the translated entries have no CIGAR output: pass the pairs and their frame bytes to pmx_gather_pairs_translated_device, "
-                "then run pmx_align_batch_cigar_device over the packed buffers");
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {
+        set_err(ref ? "a translated reference takes no PSSM matrix: the profile would belong to the protein query, but the batch PSSM forms are not wired "
+                      "through the translated entries"
+                    : "a translated query takes no PSSM matrix: a profile belongs to one protein query");
         return -1;
     }
+    if (cfg->want & PMX_WANT_CIGAR) {
+        set_err("the translated entries have no CIGAR output: pass the pairs and their frame bytes to %s, "
+                "then run pmx_align_batch_cigar_device over the packed buffers", ref ? "pmx_gather_pairs_translated_ref_device" : "pmx_gather_pairs_translated_device");
+        return -1;
+    }
+    fr->ref = ref;
     fr->first = frame_mode <= 5 ? frame_mode : frame_mode == PMX_FRAMES_REVERSE ? 3 : 0;
     fr->per = frame_mode <= 5 ? 1 : frame_mode == PMX_FRAMES_ALL ? 6 : 3;
     fr->d_frame = d_frame;
@@ -3970,18 +3981,19 @@ static int pairs_run_frames(const pmx_config_t *cfg, const pmx_seqset *Q, const 
         }, PMX_STRAND_FORWARD, &fr);
 }
 
-extern "C" int pmx_align_pairs_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
-                                                 int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_frame, int frame_mode, const uint8_t *code,
-                                                 int32_t max_qlen, int32_t max_rlen,
-                                                 pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
-                                                 const pmx_pairs_opts_t *opts)
+// Both device entries over listed pairs: ref false pmx_align_pairs_translated_device, true pmx_align_pairs_translated_ref_device.
+static int align_pairs_frames_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                     int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_frame, int frame_mode, const uint8_t *code,
+                                     int32_t max_qlen, int32_t max_rlen,
+                                     pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
+                                     const pmx_pairs_opts_t *opts, bool ref)
 {
     FrameRun fr;
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
     if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frames_check(cfg, frame_mode, d_frame, code, &fr)) return -1;
+    if (check_cfg(cfg) || frames_check(cfg, frame_mode, d_frame, code, &fr, ref)) return -1;
     if (n > 0 && fr.per > 1 && !d_frame_out) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
     if (n == 0) return 0;
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
@@ -3991,10 +4003,29 @@ extern "C" int pmx_align_pairs_translated_device(const pmx_config_t *cfg, const 
                             pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
 }
 
-extern "C" int pmx_gather_pairs_translated_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
-                                                  const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
-                                                  uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
-                                                  uint8_t *d_ok, void *stream)
+extern "C" int pmx_align_pairs_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                 int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_frame, int frame_mode, const uint8_t *code,
+                                                 int32_t max_qlen, int32_t max_rlen,
+                                                 pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
+                                                 const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frames_device(cfg, Q, R, n, d_pairs, d_frame, frame_mode, code, max_qlen, max_rlen, d_out, d_stats_out, d_frame_out, stream, opts, false);
+}
+
+extern "C" int pmx_align_pairs_translated_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                     int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_frame, int frame_mode, const uint8_t *code,
+                                                     int32_t max_qlen, int32_t max_rlen,
+                                                     pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
+                                                     const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frames_device(cfg, Q, R, n, d_pairs, d_frame, frame_mode, code, max_qlen, max_rlen, d_out, d_stats_out, d_frame_out, stream, opts, true);
+}
+
+// Both gather hooks: ref false pmx_gather_pairs_translated_device, true pmx_gather_pairs_translated_ref_device.
+static int gather_pairs_frames_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                      const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                      uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                      uint8_t *d_ok, void *stream, bool ref)
 {
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
@@ -4011,23 +4042,39 @@ extern "C" int pmx_gather_pairs_translated_device(const pmx_seqset_t *Q, const p
     hipStream_t st = (hipStream_t)stream;
     PmxCodeTable ct;
     if (code) memcpy(ct.v, code, 64); else pmx_genetic_code_host(ct.v);
-    int32_t *qlen = nullptr, *rlen = nullptr, *qw = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
+    int32_t *qlen = nullptr, *rlen = nullptr, *tw = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
     const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
     if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
-            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2); qw = c.take<int32_t>((size_t)n);
+            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2); tw = c.take<int32_t>((size_t)n);
             qsrc = c.take<int64_t>((size_t)n); rsrc = c.take<int64_t>((size_t)n);
             ok = c.take<uint8_t>((size_t)n); sflag = c.take<uint8_t>((size_t)n);
             scan = c.take<unsigned char>(scan_bytes);
         })) return -1;
     if (d_ok) ok = d_ok;
     int rc = pmx_launch_pairs_resolve_frames(d_pairs, d_frame, 0, 1, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                             qlen, rlen, qw, qsrc, rsrc, ok, sflag, st);
+                                             qlen, rlen, tw, qsrc, rsrc, ok, sflag, st, ref);
     if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
     if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_pairs_gather_translated(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, qw, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
-                                                     d_qout, q_capacity, d_rout, r_capacity, ct, st);
+    if (!rc) rc = pmx_launch_pairs_gather_translated(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, tw, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
+                                                     d_qout, q_capacity, d_rout, r_capacity, ct, st, ref);
     if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
     return 0;
+}
+
+extern "C" int pmx_gather_pairs_translated_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                                  const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                  uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                                  uint8_t *d_ok, void *stream)
+{
+    return gather_pairs_frames_device(Q, R, n, d_pairs, d_frame, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, false);
+}
+
+extern "C" int pmx_gather_pairs_translated_ref_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                                      const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                      uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                                      uint8_t *d_ok, void *stream)
+{
+    return gather_pairs_frames_device(Q, R, n, d_pairs, d_frame, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, true);
 }
 
 // ---- strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device) ----
@@ -4403,19 +4450,19 @@ extern "C" int pmx_align_pairs_both(const pmx_config_t *cfg, const pmx_seqset_t 
 }
 
 
-// The host entry over listed pairs with translated queries: pairs_host's score road -- validation against host offsets, the upload of
-// 32 (+ 1) bytes per pair, the records back -- with the frames' run in the middle.  A pair without a frame is found on the device only,
-// so the records' flags are always scanned.
-extern "C" int pmx_align_pairs_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
-                                          int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
-                                          pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *frame_out, const pmx_pairs_opts_t *opts)
+// The host entries over listed pairs with a translated side (ref false: pmx_align_pairs_translated, true: pmx_align_pairs_translated_ref):
+// pairs_host's score road -- validation against host offsets, the upload of 32 (+ 1) bytes per pair, the records back -- with the
+// frames' run in the middle.  A pair without a frame is found on the device only, so the records' flags are always scanned.
+static int align_pairs_frames_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                   int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
+                                   pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *frame_out, const pmx_pairs_opts_t *opts, bool ref)
 {
     FrameRun fr;
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
     if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frames_check(cfg, frame_mode, frame, code, &fr)) return -1;
+    if (check_cfg(cfg) || frames_check(cfg, frame_mode, frame, code, &fr, ref)) return -1;
     if (n > 0 && fr.per > 1 && !frame_out) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
     if (n == 0) return 0;
     if (frame)
@@ -4429,7 +4476,8 @@ extern "C" int pmx_align_pairs_translated(const pmx_config_t *cfg, const pmx_seq
         mq = s.mq; mr = s.mr; mnr = s.mnr;
     }
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (pairs_check(cfg, Q, R, opts, fr.letters((int32_t)mq), (int32_t)mr, stats_out != nullptr)) return -1;
+    if (host_offsets) { if (ref) { mr = fr.letters((int32_t)mr); mnr = fr.letters((int32_t)mnr); } else mq = fr.letters((int32_t)mq); }
+    if (pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
@@ -4443,12 +4491,28 @@ extern "C" int pmx_align_pairs_translated(const pmx_config_t *cfg, const pmx_seq
     int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
     pmx_config_t cfg_s = *cfg;
     if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
-    else if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
-    q32 = fr.letters(q32);
+    else {
+        if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
+        if (ref) r32 = fr.letters(r32); else q32 = fr.letters(q32);
+    }
     const int rc = pairs_run_frames(&cfg_s, Q, R, n, dp, q32, r32, drec, dst, dfout, st, pairs_chunk(n, q32, r32, opts, fr.per), fr);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     if (frame_out) HIP_OR_RET(hipMemcpyAsync(frame_out, dfout, (size_t)n, hipMemcpyDeviceToHost, st));
     return pairs_copy_back(n, drec, dst, out, stats_out, true, st);
+}
+
+extern "C" int pmx_align_pairs_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                          int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
+                                          pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *frame_out, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frames_host(cfg, Q, R, n, pairs, frame, frame_mode, code, out, stats_out, frame_out, opts, false);
+}
+
+extern "C" int pmx_align_pairs_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                              int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
+                                              pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *frame_out, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frames_host(cfg, Q, R, n, pairs, frame, frame_mode, code, out, stats_out, frame_out, opts, true);
 }
 
 extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
@@ -4564,7 +4628,7 @@ struct PairHitBufs { HitCols hit; int64_t capacity; int64_t *counts, *first_bad;
 // A chunk's alignment for the entries that keep its records in scratch (set search, top-K): the records (and statistics) of the chunk's
 // pairs and, when the entry chooses the strand, those of its alignment slots before the fold and the folded validity bytes.
 struct ChunkAlign {
-    bool stats, chosen; int per; const FrameRun *fr;              // fr != nullptr: the slots are frames of a translated query
+    bool stats, chosen; int per; const FrameRun *fr;              // fr != nullptr: the slots are frames of a translated side
     pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr; uint8_t *okf = nullptr;
     ChunkAlign(const pmx_config_t *cfg, int strand_mode, const FrameRun *frames = nullptr)
         : stats((cfg->want & PMX_WANT_STATS) != 0), chosen(strand_mode != PMX_STRAND_FORWARD || frames != nullptr),
@@ -4621,22 +4685,23 @@ static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const 
         }, strand_mode, fr);
 }
 
-// The device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.  translated: frame_mode
-// and code of the _translated entry (strand_mode is then forward, d_hit_strand receives the frames).
+// The device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.  translated (TR_QUERY /
+// TR_REF): frame_mode and code of the _translated / _translated_ref entry (strand_mode is then forward, d_hit_strand receives the frames).
 static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
                                int64_t first, int64_t n, const pmx_pair_t *d_pairs,
                                int32_t max_qlen, int32_t max_rlen, int32_t min_score,
                                pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
                                int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
-                               bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
+                               int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (search_pairs_shape_check(Q, &R, shape, first, n, d_pairs)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) ||
+    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) ||
         search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
+    if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
     if (n == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
         return 0;
@@ -4679,7 +4744,18 @@ extern "C" int pmx_search_pairs_translated_device(const pmx_config_t *cfg, const
                                                   int frame_mode, const uint8_t *code, uint8_t *d_hit_frame)
 {
     return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
-                               capacity, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, true, frame_mode, code);
+                               capacity, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, TR_QUERY, frame_mode, code);
+}
+
+extern "C" int pmx_search_pairs_translated_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                                      int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                                      int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                                      pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                      int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                                      int frame_mode, const uint8_t *code, uint8_t *d_hit_frame)
+{
+    return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                               capacity, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, TR_REF, frame_mode, code);
 }
 
 extern "C" void pmx_pair_hits_free(pmx_pair_hits_t *hits) { free(hits); }
@@ -4735,7 +4811,7 @@ struct HostHits {
 // without a frame is found on the device only, so the lowest bad pair is always asked for.
 static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
                              const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, bool with_strand, pmx_pair_hits_t **result,
-                             bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
+                             int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (!result) { set_err("null result pointer"); return -1; }
@@ -4748,7 +4824,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) || search_pairs_want_check(cfg, stats) ||
+    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) || search_pairs_want_check(cfg, stats) ||
         strand_mode_check(cfg, strand_mode)) return -1;
     HostHits hh;
     // the result: one block -- header, descriptors, indices, records, statistics (, strand bytes)
@@ -4770,7 +4846,8 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
         m.mq = (int32_t)s.mq; m.mr = (int32_t)s.mr; m.mnr = (int32_t)s.mnr;
     } else if (host_offsets && window_host_lens(Q, R, shape, first, n, &m)) return -1;
-    if (fr) m.mq = fr->letters(m.mq);
+    auto to_letters = [&]() { if (!fr) return; if (fr->ref) { m.mr = fr->letters(m.mr); m.mnr = fr->letters(m.mnr); } else m.mq = fr->letters(m.mq); };
+    to_letters();
     const bool find_bad = !host_offsets || fr != nullptr;
     const int per = fr ? fr->per : strand_slots(strand_mode);
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
@@ -4783,7 +4860,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mr, n);          // (wrapped sets: no host lengths yet, and no hint from them)
     if (!host_offsets && !listed) {
         if (window_device_lens(cfg, Q, R, &m, st)) return -1;
-        if (fr) m.mq = fr->letters(m.mq);
+        to_letters();
     }
     const int64_t slice = std::min<int64_t>(opts->slice_pairs > 0 ? opts->slice_pairs : (int64_t)1 << 24, n);
     const int64_t cap_buf = opts->max_hits > 0 ? std::min<int64_t>(slice, opts->max_hits) : slice;
@@ -4801,7 +4878,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
             HIP_OR_RET(hipMemcpyAsync(dp, pairs + s0, sizeof(pmx_pair_t) * (size_t)sn, hipMemcpyHostToDevice, st));
             if (!host_offsets) {
                 if (device_maxlens(Q, R, dp, sn, &m.mq, &m.mr, st)) return -1;
-                if (fr) m.mq = fr->letters(m.mq);
+                to_letters();
                 if (pssm_batch_check(cfg->matrix, m.mq, m.mq)) return -1;
             }
         }
@@ -4842,7 +4919,13 @@ extern "C" int pmx_search_pairs_translated(const pmx_config_t *cfg, const pmx_se
                                            pmx_frame_hits_t **result)
 {
     static_assert(sizeof(pmx_frame_hits_t) == sizeof(pmx_strand_hits_t) && offsetof(pmx_frame_hits_t, frame) == offsetof(pmx_strand_hits_t, strand), "one layout");
-    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, PMX_STRAND_FORWARD, true, (pmx_pair_hits_t **)result, true, frame_mode, code);
+    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, PMX_STRAND_FORWARD, true, (pmx_pair_hits_t **)result, TR_QUERY, frame_mode, code);
+}
+extern "C" int pmx_search_pairs_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                               const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int frame_mode, const uint8_t *code,
+                                               pmx_frame_hits_t **result)
+{
+    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, PMX_STRAND_FORWARD, true, (pmx_pair_hits_t **)result, TR_REF, frame_mode, code);
 }
 extern "C" void pmx_frame_hits_free(pmx_frame_hits_t *hits) { free(hits); }
 
@@ -4960,15 +5043,16 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
                               pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
                               int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
                               void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
-                              bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
+                              int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (topk_shape_check(Q, &R, q_first, nq, k, skip_self)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) ||
+    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) ||
         search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
+    if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), (hipStream_t)stream));
         if (d_row_off) HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), (hipStream_t)stream));
@@ -5010,7 +5094,17 @@ extern "C" int pmx_search_topk_translated_device(const pmx_config_t *cfg, const 
                                                  void *stream, const pmx_pairs_opts_t *opts, int frame_mode, const uint8_t *code, uint8_t *d_hit_frame)
 {
     return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
-                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, true, frame_mode, code);
+                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, TR_QUERY, frame_mode, code);
+}
+
+extern "C" int pmx_search_topk_translated_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                                     int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                                     pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                     int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                                     void *stream, const pmx_pairs_opts_t *opts, int frame_mode, const uint8_t *code, uint8_t *d_hit_frame)
+{
+    return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, TR_REF, frame_mode, code);
 }
 
 // Test hook (include/parasail_amd.h): the chunk loop of topk_run over records the caller made up instead of alignments -- the same
@@ -5066,7 +5160,7 @@ extern "C" void pmx_topk_hits_free(pmx_topk_hits_t *hits) { free(hits); }
 // translated (pmx_search_topk_translated): a pmx_topk_frame_hits_t, the same layout with the frames in the last column.
 static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
                             const pmx_topk_opts_t *opts, int strand_mode, bool with_strand, pmx_topk_hits_t **result,
-                            bool translated = false, int frame_mode = 0, const uint8_t *code = nullptr)
+                            int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (!result) { set_err("null result pointer"); return -1; }
@@ -5077,7 +5171,7 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames)) || search_pairs_want_check(cfg, stats) ||
+    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) || search_pairs_want_check(cfg, stats) ||
         strand_mode_check(cfg, strand_mode)) return -1;
     HostHits hh;
     // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics (, strand bytes)
@@ -5099,7 +5193,8 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
     SetLens m;
     if (host_offsets && nr > 0 && window_host_lens(Q, R, PMX_PAIRS_RECT, q_first * nr, nq * nr, &m)) return -1;
-    if (fr) m.mq = fr->letters(m.mq);
+    auto to_letters = [&]() { if (!fr) return; if (fr->ref) { m.mr = fr->letters(m.mr); m.mnr = fr->letters(m.mnr); } else m.mq = fr->letters(m.mq); };
+    to_letters();
     const bool find_bad = !host_offsets || fr != nullptr;
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
     if (pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
@@ -5111,7 +5206,7 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mr, nq * nr);    // (wrapped sets: no host lengths yet, and no hint from them)
     if (!host_offsets && nr > 0) {
         if (window_device_lens(cfg, Q, R, &m, st)) return -1;
-        if (fr) m.mq = fr->letters(m.mq);
+        to_letters();
     }
     // a slice's running state (key, record, statistics per kept entry) stays within the bound of the chunk buffers
     const int64_t ks = std::max<int64_t>(1, std::min<int64_t>(opts->k, nr));
@@ -5165,6 +5260,11 @@ extern "C" int pmx_search_topk_translated(const pmx_config_t *cfg, const pmx_seq
                                           const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result)
 {
     static_assert(sizeof(pmx_topk_frame_hits_t) == sizeof(pmx_topk_strand_hits_t) && offsetof(pmx_topk_frame_hits_t, frame) == offsetof(pmx_topk_strand_hits_t, strand), "one layout");
-    return search_topk_host(cfg, Q, R, q_first, nq, opts, PMX_STRAND_FORWARD, true, (pmx_topk_hits_t **)result, true, frame_mode, code);
+    return search_topk_host(cfg, Q, R, q_first, nq, opts, PMX_STRAND_FORWARD, true, (pmx_topk_hits_t **)result, TR_QUERY, frame_mode, code);
+}
+extern "C" int pmx_search_topk_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                              const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result)
+{
+    return search_topk_host(cfg, Q, R, q_first, nq, opts, PMX_STRAND_FORWARD, true, (pmx_topk_hits_t **)result, TR_REF, frame_mode, code);
 }
 extern "C" void pmx_topk_frame_hits_free(pmx_topk_frame_hits_t *hits) { free(hits); }

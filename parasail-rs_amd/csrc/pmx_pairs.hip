@@ -21,9 +21,9 @@
 // and, for the entries that choose the strand themselves (pmx_align_pairs_both[_device], the _stranded searches):
 //   pmx_pairs_resolve_both_kernel       one descriptor -> `per` alignment slots: per 1 the reverse strand, per 2 forward then reverse
 //   pmx_pairs_fold_strands_kernel       the slots' records (and statistics) -> one record, statistics and strand per logical pair
-// and, for translated queries (the _translated entries, pmx_gather_pairs_translated_device):
+// and, for a translated side (the _translated entries: the query; the _translated_ref entries: the reference, 2.5j):
 //   pmx_pairs_resolve_frames_kernel     one descriptor -> `per` slots (1, 3 or 6), one per frame: translated length, nucleotide window
-//   pmx_pairs_gather_translated_kernel  the gather that turns codons of the query window into amino acids, on either strand
+//   pmx_pairs_gather_translated_kernel  the gather that turns codons of that side's window into amino acids, on either strand
 //   pmx_pairs_fold_frames_kernel        the slots' records (and statistics) -> one record, statistics and frame per logical pair
 //
 // All of them are bandwidth kernels in plain C++: vector loads and stores only.
@@ -308,17 +308,19 @@ static constexpr PmxBaseTable pmx_make_base_table()
 }
 __device__ const PmxBaseTable pmx_base_dev = pmx_make_base_table();
 
-// The resolve step for translated queries: logical pair k becomes `per` alignment slots, slot per * k + i in frame f = (frame ?
-// frame[k] : first + i).  The query side resolves to its nucleotide window (W bytes, any length); slot i then holds L = (W - off) / 3
-// letters, off = f % 3.  A frame with L = 0 does not exist: a 1 x 1 placeholder with ok = 0, which the fold passes over.  A bad
-// descriptor, a frame byte above 5 and a frame of the call whose L exceeds max_qlen make every slot of the pair such a placeholder.
-// The scans read per * n + 1 lengths.
+// The resolve step for a translated side (REF false: the query, true: the reference): logical pair k becomes `per` alignment slots,
+// slot per * k + i in frame f = (frame ? frame[k] : first + i).  The translated side resolves to its nucleotide window (W bytes, any
+// length), the other side against its maximum; slot i then holds L = (W - off) / 3 letters on the translated side, off = f % 3.  A
+// frame with L = 0 does not exist: a 1 x 1 placeholder with ok = 0, which the fold passes over.  A bad descriptor, a frame byte above
+// 5 and a frame of the call whose L exceeds the translated side's maximum make every slot of the pair such a placeholder.  tw: the
+// translated side's W per slot.  The scans read per * n + 1 lengths.
+template <bool REF>
 __global__ __launch_bounds__(256)
 void pmx_pairs_resolve_frames_kernel(const pmx_pair_t *__restrict__ pairs, const uint8_t *__restrict__ frame, int first, int per, long long n,
                                      const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
                                      const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
                                      int32_t max_qlen, int32_t max_rlen,
-                                     int32_t *__restrict__ qlen, int32_t *__restrict__ rlen, int32_t *__restrict__ qw,
+                                     int32_t *__restrict__ qlen, int32_t *__restrict__ rlen, int32_t *__restrict__ tw,
                                      int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
 {
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -327,12 +329,13 @@ void pmx_pairs_resolve_frames_kernel(const pmx_pair_t *__restrict__ pairs, const
     const pmx_pair_t p = pairs[k];
     const unsigned f0 = frame ? frame[k] : (unsigned)first;
     long long qs = 0, rs = 0;
-    const int32_t W = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, INT32_MAX, &qs);
-    const int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
-    bool good = W > 0 && rl > 0 && f0 + (unsigned)per <= 6u;
+    const int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, REF ? max_qlen : INT32_MAX, &qs);
+    const int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, REF ? INT32_MAX : max_rlen, &rs);
+    const int32_t W = REF ? rl : ql, plain = REF ? ql : rl, max_l = REF ? max_rlen : max_qlen;
+    bool good = W > 0 && plain > 0 && f0 + (unsigned)per <= 6u;
     for (int i = 0; i < per; ++i) {                                // (the shortest offset of the call's frames has the longest L)
         const int off = (int)((f0 + (unsigned)i) % 3u);
-        if (W > off && (W - off) / 3 > max_qlen) good = false;
+        if (W > off && (W - off) / 3 > max_l) good = false;
     }
     const long long s = (long long)per * k;
     for (int i = 0; i < per; ++i) {
@@ -340,7 +343,7 @@ void pmx_pairs_resolve_frames_kernel(const pmx_pair_t *__restrict__ pairs, const
         const int off = (int)(f % 3u);
         const int32_t L = good && W > off ? (W - off) / 3 : 0;
         const bool have = L > 0;
-        qlen[s + i] = have ? L : 1; rlen[s + i] = have ? rl : 1; qw[s + i] = have ? W : 0;
+        (REF ? rlen : qlen)[s + i] = have ? L : 1; (REF ? qlen : rlen)[s + i] = have ? plain : 1; tw[s + i] = have ? W : 0;
         qsrc[s + i] = have ? qs : 0; rsrc[s + i] = have ? rs : 0;
         ok[s + i] = have ? 1 : 0; sflag[s + i] = good ? (uint8_t)f : 0;
     }
@@ -353,16 +356,18 @@ static __device__ __forceinline__ uint32_t pmx_codon(const uint8_t *cls, const u
     return i < 64u ? (uint32_t)cod[i ^ flip] : (uint32_t)'X';
 }
 
-// The gather of pmx_pairs_gather_stranded_kernel with a translated query side: the same 16-lane group per window, the same forward
-// walk over the destination in aligned dwords, the reference side copied as there.  A query destination dword holds four letters,
-// twelve source bytes: three calls of pmx_window_dword (the same in-bounds test, the same byte-by-byte fallback at a set's first and
-// last bytes).  Forward frame `off`: letter p is the codon at window bytes off + 3 p ..; reverse frame: the codon at bytes W - 1 - off
-// - 3 p downwards, complemented -- the reversal is the order the twelve bytes are taken in, the complement the index ^ 42.  Classes
-// (256 bytes) and code (64 bytes, a kernel argument: a caller may bring its own) are staged in LDS.  The frame is uniform per group,
-// so the branch sits outside the dword loop.  A window whose end would cross its capacity is not written.
+// The gather of pmx_pairs_gather_stranded_kernel with one side translated (REF false: the query, true: the reference): the same
+// 16-lane group per window, the same forward walk over the destination in aligned dwords, the other side copied as there.  A
+// destination dword of the translated side holds four letters, twelve source bytes: three calls of pmx_window_dword (the same
+// in-bounds test, the same byte-by-byte fallback at a set's first and last bytes).  Forward frame `off`: letter p is the codon at
+// window bytes off + 3 p ..; reverse frame: the codon at bytes W - 1 - off - 3 p downwards, complemented -- the reversal is the order
+// the twelve bytes are taken in, the complement the index ^ 42.  Classes (256 bytes) and code (64 bytes, a kernel argument: a caller
+// may bring its own) are staged in LDS.  The frame is uniform per group, so the branch sits outside the dword loop.  A window whose
+// end would cross its capacity is not written.  tw: the translated side's W per slot.
+template <bool REF>
 __global__ __launch_bounds__(256)
 void pmx_pairs_gather_translated_kernel(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes, const uint8_t *__restrict__ r_buf, long long r_bytes,
-                                        const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen, const int32_t *__restrict__ qw,
+                                        const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen, const int32_t *__restrict__ tw,
                                         const int64_t *__restrict__ qsrc, const int64_t *__restrict__ rsrc, const uint8_t *__restrict__ ok,
                                         const uint8_t *__restrict__ sflag, const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
                                         uint8_t *__restrict__ qout, long long q_cap, uint8_t *__restrict__ rout, long long r_cap, PmxCodeTable code)
@@ -382,14 +387,14 @@ void pmx_pairs_gather_translated_kernel(long long n, const uint8_t *__restrict__
     uint8_t *dst = (side ? rout : qout) + o0;
     if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
     const uint8_t *buf = side ? r_buf : q_buf;
-    const long long len = side ? rlen[k] : qlen[k];             // destination bytes: letters on the query side
+    const long long len = side ? rlen[k] : qlen[k];             // destination bytes: letters on the translated side
     const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
     const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
     long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
     if (head > len) head = len;
     const long long nd = (len - head) >> 2, done = head + 4 * nd;
     uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
-    if (side) {
+    if (side != REF) {
         if (lane < head) dst[lane] = src[lane];
         const uint8_t *s0 = src + head;
         for (long long x = lane; x < nd; x += 16)
@@ -399,7 +404,7 @@ void pmx_pairs_gather_translated_kernel(long long n, const uint8_t *__restrict__
     }
     const unsigned f = sflag[k];
     if (f >= 3) {
-        const uint8_t *top = src + qw[k] - 1 - (f - 3);         // letter p: top[-3 p], top[-3 p - 1], top[-3 p - 2], complemented
+        const uint8_t *top = src + tw[k] - 1 - (f - 3);         // letter p: top[-3 p], top[-3 p - 1], top[-3 p - 2], complemented
         if (lane < head) dst[lane] = (uint8_t)pmx_codon(cls, cod, top[-3 * lane], top[-3 * lane - 1], top[-3 * lane - 2], 42u);
         const uint8_t *s0 = top - 3 * head - 11;                // the lowest source byte of destination dword 0
         for (long long x = lane; x < nd; x += 16) {
@@ -695,21 +700,33 @@ void pmx_genetic_code_host(uint8_t table[64]) { for (int i = 0; i < 64; ++i) tab
 int pmx_launch_pairs_resolve_frames(const pmx_pair_t *pairs, const uint8_t *frame, int first, int per, long long n,
                                     const int64_t *q_off, long long q_count, long long q_bytes,
                                     const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                                    int32_t *qlen, int32_t *rlen, int32_t *qw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
+                                    int32_t *qlen, int32_t *rlen, int32_t *tw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st,
+                                    bool ref)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_resolve_frames_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, frame, first, per, n,
-                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qw, qsrc, rsrc, ok, sflag);
+    const dim3 grid((unsigned)((n + 2 + 255) / 256));
+    if (ref)
+        hipLaunchKernelGGL(pmx_pairs_resolve_frames_kernel<true>, grid, dim3(256), 0, st, pairs, frame, first, per, n,
+                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
+    else
+        hipLaunchKernelGGL(pmx_pairs_resolve_frames_kernel<false>, grid, dim3(256), 0, st, pairs, frame, first, per, n,
+                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
-                                       const int32_t *qlen, const int32_t *rlen, const int32_t *qw, const int64_t *qsrc, const int64_t *rsrc,
+                                       const int32_t *qlen, const int32_t *rlen, const int32_t *tw, const int64_t *qsrc, const int64_t *rsrc,
                                        const uint8_t *ok, const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
-                                       uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t st)
+                                       uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t st,
+                                       bool ref)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_gather_translated_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
-                       qlen, rlen, qw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
+    const dim3 grid((unsigned)((2 * n + 15) / 16));
+    if (ref)
+        hipLaunchKernelGGL(pmx_pairs_gather_translated_kernel<true>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
+    else
+        hipLaunchKernelGGL(pmx_pairs_gather_translated_kernel<false>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_fold_frames(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
