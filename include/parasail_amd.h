@@ -826,6 +826,103 @@ int  pmx_search_topk_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, 
                                 const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result);
 void pmx_topk_frame_hits_free(pmx_topk_frame_hits_t *hits);
 
+/* Frameshift-aware translated search (extension): nucleotide queries against a protein set, aligned by a three-frame local DP so
+ * that one alignment may change its reading frame.  The translated entries above align every frame on its own: one inserted or
+ * deleted nucleotide cuts an alignment in two and the fold keeps the better half.  Here a path may step over two or four nucleotides
+ * instead of three, at the price of a penalty `frameshift`.  The pipeline around the kernel is the one of the stranded entries.
+ *
+ * Q holds nucleotides and R holds proteins.  The genetic code, the base classes and the `code` argument are those of the translated
+ * entries above.
+ *
+ * The codon stream.  A query window of W nucleotides is read as stored (strand 0) or reverse-complemented exactly as the _ex entries
+ * define it (strand 1: pmx_complement_table, then reversed): the oriented window.  Its codon stream T has N = W - 2 letters; T[i] is
+ * the translation of oriented bytes i, i + 1, i + 2.  Rows i = f, f + 3, f + 6, .. of T are exactly frame f (strand 0) or frame 3 + f
+ * (strand 1) of the translated entries.  A window with W < 3 has no stream: the pair is treated as a pair without an existing frame
+ * is there -- the bad record {0, -1, -1, PMX_FLAG_BAD_PAIR}, strand 0.
+ *
+ * The recurrence.  Local alignment only.  Rows i = 0 .. N - 1 of T, columns j = 0 .. m - 1 of reference r, s the matrix score, open
+ * and extend the call's gap penalties (a gap of length g costs open + (g - 1) extend), fs = frameshift >= 0:
+ *     D(i,j) = max(0, H(i-3,j-1), H(i-2,j-1) - fs, H(i-4,j-1) - fs)
+ *     M(i,j) = D(i,j) + s(T[i], r[j])
+ *     E(i,j) = max(H(i,j-1) - open, E(i,j-1) - extend)          a reference letter against a gap
+ *     F(i,j) = max(H(i-3,j) - open, F(i-3,j) - extend)          a whole codon against a gap
+ *     H(i,j) = max(0, M, E, F)
+ * A term with a negative index does not exist: for H it counts as 0, for E and F as minus infinity.  The i - 2 predecessor is a path
+ * that found one nucleotide missing from the read, the i - 4 predecessor one nucleotide too many; gaps keep their frame.  With the
+ * two frameshift terms taken out, the score is the best plain local score over T[0::3], T[1::3] and T[2::3]: the
+ * PMX_FRAMES_FORWARD (strand 1: PMX_FRAMES_REVERSE) fold of the translated entries, which a large `frameshift` therefore returns.
+ *
+ * The record.  score = the maximum H; end_ref = its j; end_query = its i + 2, THE LAST NUCLEOTIDE OF THE LAST CODON, 0-BASED
+ * INCLUSIVE, IN THE ORIENTED WINDOW -- IN NUCLEOTIDES, UNLIKE THE TRANSLATED ENTRIES, WHOSE POSITIONS ARE LETTERS.  Back to stored
+ * bytes: oriented byte x of a strand-0 window is sequence byte q_beg + x, of a strand-1 window sequence byte q_beg + W - 1 - x
+ * (complemented).  Ties: the first maximum in column-major order, that is the smallest end_ref, then the smallest end_query; a zero
+ * maximum therefore ends at end_query 2, end_ref 0.  flags = 0.
+ *
+ * Strand modes.  PMX_STRAND_FORWARD, PMX_STRAND_REVERSE and PMX_STRAND_BOTH mean what they mean for the stranded entries: one or two
+ * alignment slots per pair, the better strand kept BEFORE the threshold and the top-K cut (only the score is compared, a tie goes to
+ * the forward strand), the strand byte beside each record or hit.  The listed-pairs entry also takes one strand byte per pair
+ * (d_strand / strand; the strand mode must then be PMX_STRAND_FORWARD; a byte above 1 makes the pair bad).  chunk_pairs, slice_pairs
+ * and slice_rows count logical pairs or rows and never change a byte; outputs are bit-identical from run to run.
+ *
+ * Limits.  cfg->mode PMX_MODE_SW; cfg->width 0 or 32, both exact: the kernel computes in 32 bits, and open, extend and frameshift
+ * above 2^28 are read as 2^28, which is above every score a window can reach, so nothing wraps.  Windows of up to
+ * PMX_FRAMESHIFT_MAX_WINDOW nucleotides.  max_qlen of the device entries bounds N = W - 2, the rows the kernel sees; a window whose N
+ * exceeds max_qlen makes the pair bad.  The host entries size max_qlen from the longest window.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: any other mode or width; PMX_WANT_STATS and PMX_WANT_CIGAR (there
+ * is no traceback with frameshift operators); a PSSM matrix; a matrix of more than 128 symbols; frameshift < 0; a strand mode outside
+ * 0 .. 2; strand bytes per pair together with a strand mode other than PMX_STRAND_FORWARD; max_qlen above
+ * PMX_FRAMESHIFT_MAX_WINDOW - 2 (host entries: a window above PMX_FRAMESHIFT_MAX_WINDOW); everything the corresponding stranded or
+ * untranslated entry refuses, with the same texts.  n == 0 / nq == 0 behave as there.  The host entries name the first pair that is
+ * bad or has no stream.
+ *
+ * Scratch.  The chunk buffers of the stranded entries with N + m bytes per slot, 16 bytes of slot record per slot and, for windows of
+ * more than 162 nucleotides, 64 bytes per reference column and slot for the strips' boundary columns, at most 256 MiB of them (the
+ * kernel then runs over a chunk's slots in parts).  pmx_last_kernel() names the instantiation of the last chunk's alignment. */
+#define PMX_FRAMESHIFT_MAX_WINDOW 4096
+int32_t pmx_frameshift_max_window(void);            /* PMX_FRAMESHIFT_MAX_WINDOW of the library loaded */
+/* Building block and test hook: pmx_gather_pairs_translated_device in its stride-1 form, with d_strand (one strand byte per pair;
+ * NULL: all forward) in place of d_frame.  d_qout receives the codon streams (W - 2 letters each), d_rout the reference windows;
+ * max_qlen bounds W - 2.  A pair that is bad or has W < 3 has a one-zero-byte placeholder on either side and d_ok[k] = 0.  No byte
+ * outside a set's buffer is read.  Asynchronous on `stream`. */
+int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                   const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                   uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                   uint8_t *d_ok /* n validity bytes, optional */, void *stream);
+/* Listed pairs.  d_strand / strand: a strand byte per pair (then strand_mode must be PMX_STRAND_FORWARD), or NULL and a strand mode
+ * for all pairs.  d_strand_out / strand_out (n bytes; required with PMX_STRAND_BOTH, else optional): the strand of every record.
+ * The device entry gives bad pairs their record and strand 0; the host entry refuses them, naming the first. */
+int pmx_align_pairs_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                      int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                      int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                      pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                               int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                               int32_t frameshift, const uint8_t *code,
+                               pmx_record_t *out, uint8_t *strand_out, const pmx_pairs_opts_t *opts);
+/* Set search and per-query top-K: the argument lists of the stranded entries, then frameshift and code.  d_hit_stats must be NULL.
+ * The hit descriptors stay valid d_pairs: with the strand bytes they feed pmx_align_pairs_frameshift_device and
+ * pmx_gather_pairs_codons_device.  The host results are pmx_strand_hits_t / pmx_topk_strand_hits_t, released with their free
+ * functions. */
+int pmx_search_pairs_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                       int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                       int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                       pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                       int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                       int strand_mode, uint8_t *d_hit_strand /* optional */, int32_t frameshift, const uint8_t *code);
+int pmx_search_pairs_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode,
+                                int32_t frameshift, const uint8_t *code, pmx_strand_hits_t **result);
+int pmx_search_topk_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                      int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                      pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                      int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                      void *stream, const pmx_pairs_opts_t *opts,
+                                      int strand_mode, uint8_t *d_hit_strand /* optional */, int32_t frameshift, const uint8_t *code);
+int pmx_search_topk_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                               const pmx_topk_opts_t *opts, int strand_mode, int32_t frameshift, const uint8_t *code,
+                               pmx_topk_strand_hits_t **result);
+
 /* Reference-side translation (extension): protein queries against a set of nucleotide sequences -- genes, transcripts, contigs --,
  * the tblastn pairing.  The text above holds with the sides exchanged; what follows states it in full.
  *

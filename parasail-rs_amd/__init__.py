@@ -332,6 +332,23 @@ _sig("pmx_search_topk_translated_ref_device", C.c_int, C.POINTER(pmx_config_t), 
      C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_void_p)
 _sig("pmx_search_topk_translated_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.c_int, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_frame_hits_t)))
+_sig("pmx_frameshift_max_window", C.c_int32)
+_sig("pmx_gather_pairs_codons_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_align_pairs_frameshift_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_frameshift", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_search_pairs_frameshift_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
+_sig("pmx_search_pairs_frameshift", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+     C.POINTER(pmx_pair_search_opts_t), C.c_int, C.c_int32, C.c_void_p, C.POINTER(C.POINTER(pmx_strand_hits_t)))
+_sig("pmx_search_topk_frameshift_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
+_sig("pmx_search_topk_frameshift", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+     C.POINTER(pmx_topk_opts_t), C.c_int, C.c_int32, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_strand_hits_t)))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -956,7 +973,7 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return (out, stats) if stats is not None else out
 
-    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False, frame=None, code=None, ref_frame=None):
+    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False, frame=None, code=None, ref_frame=None, frameshift=None):
         """Pairs by index and window into device-resident sequence sets (SeqSet; Q may be R).  `pairs`: a PAIR_DTYPE array, or
         an iterable of (q, r) / (q, r, q_beg, q_len, r_beg, r_len) tuples (len -1: to the sequence's end).  Record k is the record
         of the pair (query window, reference window) k, end positions relative to the windows.  A bad descriptor raises BatchError
@@ -970,7 +987,10 @@ class Aligner:
         letters of the translated query; returns (records, frames) or (records, stats, frames).  code: 64 letters that replace
         genetic_code_table().  `ref_frame` (not together with frame or strand): the opposite pairing -- Q holds proteins, R
         nucleotides, the REFERENCE windows are translated; the same values and results, positions in letters of the translated
-        reference, the frames are the reference's."""
+        reference, the frames are the reference's.  `frameshift` (a penalty >= 0; not together with frame or ref_frame): Q holds
+        nucleotides, R proteins, and every pair is aligned by the three-frame local DP that may change its reading frame
+        (codon_stream() restates the query side) -- strand None or 0: as stored, 1: reverse-complemented, "both", or one byte per
+        pair; end_query is in NUCLEOTIDES of the oriented window; returns (records, strand)."""
         if not self._profile.is_null():
             raise BatchError("align_pairs takes no profile")
         pairs = as_pairs(pairs)
@@ -979,6 +999,25 @@ class Aligner:
         out = np.zeros(n, dtype=RECORD_DTYPE)
         stats = np.zeros(n, dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
         opts = pmx_pairs_opts_t(int(chunk_pairs))
+        if frameshift is not None:
+            _frameshift_side(frame, ref_frame)
+            if cigar:
+                cfg.want |= WANT_CIGAR                   # (refused by the entry)
+            per_pair = None
+            if strand is None or isinstance(strand, str) or np.ndim(strand) == 0:
+                mode = _strand_mode(0 if strand is None else strand)
+            else:
+                mode, per_pair = STRAND_FORWARD, np.ascontiguousarray(strand, dtype=np.uint8)
+                if len(per_pair) != n:
+                    raise BatchError("strand and pairs differ in count")
+            code = _code_arg(code)
+            won = np.zeros(n, dtype=np.uint8)
+            rc = lib.pmx_align_pairs_frameshift(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
+                                                per_pair.ctypes.data if per_pair is not None else None, mode, int(frameshift),
+                                                code.ctypes.data if code is not None else None, out.ctypes.data, won.ctypes.data, C.byref(opts))
+            if rc:
+                raise BatchError(lib.pmx_last_error().decode())
+            return out, won
         entry, frame = _frame_side(frame, ref_frame, strand is not None, lib.pmx_align_pairs_translated, lib.pmx_align_pairs_translated_ref)
         if frame is not None:
             if cigar:
@@ -1052,7 +1091,7 @@ class Aligner:
         return (out, stats) if stats is not None else out
 
     def search_pairs(self, Q, R=None, min_score=0, pairs=None, first=0, count=None, stats=False, max_hits=0, chunk_pairs=0,
-                     slice_pairs=0, strand=0, frame=None, code=None, ref_frame=None):
+                     slice_pairs=0, strand=0, frame=None, code=None, ref_frame=None, frameshift=None):
         """Set search: the pairs of an enumeration that score at least min_score, as a PairHits in enumeration order.  `pairs`
         given: those descriptors of Q x R (as align_pairs takes them; R None: Q); else R None: pairs [first, first + count) of the
         strict upper triangle of Q (the numbering of align_all_pairs); else the same window of the rectangle Q x R, row-major
@@ -1063,7 +1102,9 @@ class Aligner:
         frame (not together with strand): nucleotide queries against proteins, translated in frame 0 .. 5 or the best of "forward" /
         "reverse" / "all" frames, chosen before the threshold; PairHits.frame tells which (code: as in align_pairs).  ref_frame (not
         together with frame or strand): protein queries against nucleotide references, the references translated the same way;
-        PairHits.frame is then the reference's frame."""
+        PairHits.frame is then the reference's frame.  frameshift (a penalty >= 0; with strand, not together with frame or
+        ref_frame): nucleotide queries against proteins by the three-frame DP of align_pairs(frameshift=); PairHits.strand tells the
+        strand, end_query is in nucleotides."""
         if not self._profile.is_null():
             raise BatchError("search_pairs takes no profile")
         cfg = self._config()
@@ -1085,6 +1126,11 @@ class Aligner:
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
                 pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts))
         mode = _strand_mode(strand)
+        if frameshift is not None:
+            _frameshift_side(frame, ref_frame)
+            code = _code_arg(code)
+            return _hits_call(lib.pmx_search_pairs_frameshift, args + (mode, int(frameshift), code.ctypes.data if code is not None else None),
+                              pmx_strand_hits_t, PairHits, lib.pmx_strand_hits_free)
         entry, frame = _frame_side(frame, ref_frame, mode != STRAND_FORWARD, lib.pmx_search_pairs_translated, lib.pmx_search_pairs_translated_ref)
         if frame is not None:
             code = _code_arg(code)
@@ -1095,13 +1141,14 @@ class Aligner:
         return _hits_call(lib.pmx_search_pairs, args, pmx_pair_hits_t, PairHits, lib.pmx_pair_hits_free)
 
     def search_topk(self, Q, R=None, k=10, min_score=INT32_MIN, skip_self=False, first_row=0, rows=None, stats=False, chunk_pairs=0,
-                    slice_rows=0, strand=0, frame=None, code=None, ref_frame=None):
+                    slice_rows=0, strand=0, frame=None, code=None, ref_frame=None, frameshift=None):
         """Per-query top-K: for each query row [first_row, first_row + rows) of Q the best k references of R (None: Q) with score
         >= min_score, in (score descending, reference index ascending) order, as a TopKHits.  rows None: to the last row.
         skip_self (R is Q) leaves the pair (i, i) out.  stats=True adds the hits' statistics.  Only the hits leave the device;
         chunk_pairs and slice_rows never change the result.  strand as in search_pairs: with "both" a reference is one
         candidate with its better strand, and TopKHits.strand tells which.  frame as in search_pairs: a reference is one candidate
-        with its best frame, and TopKHits.frame tells which.  ref_frame as in search_pairs: the references are the translated side."""
+        with its best frame, and TopKHits.frame tells which.  ref_frame as in search_pairs: the references are the translated side.
+        frameshift as in search_pairs: a reference is one candidate with its better strand under the three-frame DP."""
         if not self._profile.is_null():
             raise BatchError("search_topk takes no profile")
         cfg = self._config()
@@ -1112,6 +1159,11 @@ class Aligner:
         opts = pmx_topk_opts_t(int(min_score), int(k), 1 if skip_self else 0, int(chunk_pairs), int(slice_rows))
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows), C.byref(opts))
         mode = _strand_mode(strand)
+        if frameshift is not None:
+            _frameshift_side(frame, ref_frame)
+            code = _code_arg(code)
+            return _hits_call(lib.pmx_search_topk_frameshift, args + (mode, int(frameshift), code.ctypes.data if code is not None else None),
+                              pmx_topk_strand_hits_t, TopKHits, lib.pmx_topk_strand_hits_free)
         entry, frame = _frame_side(frame, ref_frame, mode != STRAND_FORWARD, lib.pmx_search_topk_translated, lib.pmx_search_topk_translated_ref)
         if frame is not None:
             code = _code_arg(code)
@@ -1337,6 +1389,12 @@ def _frame_side(frame, ref_frame, stranded, query_entry, ref_entry):
     return (query_entry, frame) if frame is not None else (None, None)
 
 
+def _frameshift_side(frame, ref_frame):
+    """frameshift= of align_pairs, search_pairs and search_topk excludes the two frame arguments."""
+    if frame is not None or ref_frame is not None:
+        raise BatchError("frameshift excludes frame and ref_frame: the three-frame alignment reads every frame of a strand at once")
+
+
 def _frame_mode(frame, n=None):
     """A frame argument -> (frame mode, frame bytes per pair or None): 0 .. 5, FRAMES_* or "forward" / "reverse" / "all"; with n
     (align_pairs) also one frame byte per pair."""
@@ -1390,6 +1448,33 @@ def translate(seq, frame, code=None):
         b = [cls.get(int(x), 64) for x in s[off + 3 * p: off + 3 * p + 3]]
         out.append(code[16 * b[0] + 4 * b[1] + b[2]] if max(b) < 64 else ord("X"))
     return bytes(out)
+
+
+def codon_stream(seq, strand=0, code=None):
+    """The codon stream of a nucleotide window as the _frameshift entries define it, on the host: `seq` as stored (strand 0) or its
+    reverse complement (strand 1: complement_table(), then reversed); letter i is the translation of oriented bytes i, i + 1, i + 2,
+    len - 2 letters, so codon_stream(seq, s)[f::3] == translate(seq, 3 * s + f).  b"" for fewer than three bytes."""
+    strand = int(strand)
+    if strand not in (0, 1):
+        raise BatchError("strand %d is neither 0 nor 1" % strand)
+    code = genetic_code_table() if code is None else _code_arg(code).tobytes()
+    s = np.frombuffer(bytes(seq), dtype=np.uint8)
+    if strand:
+        s = complement_table()[s[::-1]]
+    cls = np.full(256, 64, dtype=np.int64)
+    for c, v in zip(b"TCAGUtcagu", (0, 1, 2, 3, 0) * 2):
+        cls[c] = v
+    if len(s) < 3:
+        return b""
+    b = cls[s]
+    idx = 16 * b[:-2] + 4 * b[1:-1] + b[2:]
+    lut = np.frombuffer(bytes(code), dtype=np.uint8)
+    return np.where(idx < 64, lut[np.minimum(idx, 63)], ord("X")).astype(np.uint8).tobytes()
+
+
+def frameshift_max_window():
+    """The longest query window, in nucleotides, the _frameshift entries take (PMX_FRAMESHIFT_MAX_WINDOW of the library)."""
+    return int(lib.pmx_frameshift_max_window())
 
 
 def _hits_call(entry, args, block_t, wrap, free):
@@ -1771,6 +1856,60 @@ def search_topk_translated_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, mi
                                                max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
                                                d_hit_recs, d_hit_stats, int(capacity), d_row_off, d_row_passing, d_counts, stream,
                                                C.byref(opts), int(frame_mode), code.ctypes.data if code is not None else None, d_hit_frame)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def gather_pairs_codons_device(Q, R, n, d_pairs, d_strand, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff,
+                               d_ok=None, stream=0, code=None):
+    """gather_pairs_translated_device in its stride-1 form: the query windows become codon streams (codon_stream(); d_strand: a strand
+    byte per pair or None for forward; max_qlen bounds the stream's length, the window's minus 2)."""
+    code = _code_arg(code)
+    rc = lib.pmx_gather_pairs_codons_device(Q._handle(), R._handle(), n, d_pairs, d_strand, code.ctypes.data if code is not None else None,
+                                            max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_frameshift_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, max_qlen, max_rlen, d_out, d_strand_out=None,
+                                  stream=0, chunk_pairs=0, code=None):
+    """align_pairs_device by the three-frame local DP: d_strand (a strand byte per pair, strand_mode STRAND_FORWARD) or None and a
+    strand mode; record k is the better strand's, d_strand_out (n bytes) says which.  max_qlen bounds the codon stream, W - 2."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_align_pairs_frameshift_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, int(strand_mode), int(frameshift),
+                                               code.ctypes.data if code is not None else None, max_qlen, max_rlen, d_out, d_strand_out,
+                                               stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_pairs_frameshift_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs,
+                                   capacity, d_counts, strand_mode, frameshift, d_hit_strand=None, stream=0, chunk_pairs=0, code=None):
+    """search_pairs_stranded_device by the three-frame local DP (no statistics): the threshold looks at the folded records;
+    d_hit_strand (optional, one byte per hit) receives the hits' strands."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_search_pairs_frameshift_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(shape), int(first),
+                                                int(n), d_pairs, max_qlen, max_rlen, int(min_score), d_hit_pairs, d_hit_index, d_hit_recs,
+                                                None, int(capacity), d_counts, stream, C.byref(opts), int(strand_mode), d_hit_strand,
+                                                int(frameshift), code.ctypes.data if code is not None else None)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def search_topk_frameshift_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs,
+                                  capacity, d_row_off, d_row_passing, d_counts, strand_mode, frameshift, d_hit_strand=None, stream=0,
+                                  chunk_pairs=0, code=None):
+    """search_topk_stranded_device by the three-frame local DP (no statistics): a reference is one candidate with its folded record;
+    d_hit_strand (optional, one byte per hit) receives the hits' strands."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_search_topk_frameshift_device(C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(q_first), int(nq),
+                                               max_qlen, max_rlen, int(min_score), int(k), 1 if skip_self else 0, d_hit_pairs, d_hit_index,
+                                               d_hit_recs, None, int(capacity), d_row_off, d_row_passing, d_counts, stream,
+                                               C.byref(opts), int(strand_mode), d_hit_strand, int(frameshift),
+                                               code.ctypes.data if code is not None else None)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

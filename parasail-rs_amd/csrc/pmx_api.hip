@@ -1377,7 +1377,8 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_PHIT = 26,                                                                    // set search, host entry: a slice's hit columns (HitCols), counts, first bad pair
        SCR_PTOPK = 27,                                                                   // per-query top-K: a chunk's records and statistics (ChunkAlign), tile survivors, the rows' running state, scan scratch
        SCR_PTHIT = 28,                                                                   // per-query top-K, host entry: a slice's hit columns (HitCols) and row arrays, counts, first bad pair
-       SCR_SLOTS = 29 };
+       SCR_SWFS = 29,                                                                    // frameshift entries: the strips' boundary columns (pmx_swfs.hip)
+       SCR_SLOTS = 30 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -3741,16 +3742,20 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 // nucleotides translated on their way into the buffers, per = fr->per alignment slots per pair, one per frame; max_qlen bounds the
 // translated length, so the query buffer holds per * cn * max_qlen letters.  fr->ref (the _translated_ref entries): the
 // same with the sides exchanged -- the reference windows are the nucleotides, max_rlen bounds their translated length, and the
-// reference buffer holds per * cn * max_rlen letters.
+// reference buffer holds per * cn * max_rlen letters.  fr->codons (the _frameshift entries): the query windows become
+// codon streams of W - 2 letters, one slot per strand; max_qlen bounds the stream, and the body aligns the slots with pmx_swfs.
 static int strand_slots(int strand_mode) { return strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
-enum { TR_NONE = 0, TR_QUERY = 1, TR_REF = 2 };      // which side an entry translates (the search and top-K entries' `translated`)
+enum { TR_NONE = 0, TR_QUERY = 1, TR_REF = 2, TR_CODONS = 3 };      // which side an entry translates (the search and top-K entries' `translated`); TR_CODONS: the _frameshift entries
 struct FrameRun {
     int first = 0, per = 1;                 // the frames first .. first + per - 1 for every pair ...
     const uint8_t *d_frame = nullptr;       // ... or (listed pairs, per 1) a frame byte per pair
     PmxCodeTable code;
     bool ref = false;                       // the translated side: the query's windows, or (true) the reference's
+    // codons (the _frameshift entries): the query slots are codon streams, one per strand -- first .. first + per - 1, or
+    // d_frame's byte per pair -- and a chunk's alignment is pmx_swfs with this frameshift penalty
+    bool codons = false; int frameshift = 0;
     int min_off() const { return per == 1 && !d_frame ? first % 3 : 0; }      // the smallest offset a frame of the call reads from
-    int32_t letters(int32_t w) const { return std::max<int32_t>(1, (w - min_off()) / 3); }   // the longest translation of w nucleotides
+    int32_t letters(int32_t w) const { return std::max<int32_t>(1, codons ? w - 2 : (w - min_off()) / 3); }   // the longest translation of w nucleotides
 };
 struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; int32_t *tw /* the translated side's W */; };
 template <typename Body>
@@ -3793,7 +3798,10 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         int rc = listed ? 0 : shape == PMX_PAIRS_TRIANGLE ? pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gc, prep)
                                                           : pmx_launch_rect_pairs_enumerate(R->count, first + c0, cn, gc, prep);
         const int64_t sn = cn * per;                              // the chunk's alignment slots
-        if (!rc) rc = fr       ? pmx_launch_pairs_resolve_frames(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
+        if (!rc) rc = fr && fr->codons ? pmx_launch_pairs_resolve_codons(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
+                                                                         R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                                                         b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
+                    : fr       ? pmx_launch_pairs_resolve_frames(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
                                                                  R->d_off, R->count, R->bytes, max_qlen, max_rlen,
                                                                  b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep, fr->ref)
                     : chosen   ? pmx_launch_pairs_resolve_both(pc, cn, per, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
@@ -3805,7 +3813,9 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
                                                           b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.qlen, sn, b.qoff, scan, scan_bytes, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.rlen, sn, b.roff, scan, scan_bytes, prep);
-        if (!rc) rc = fr       ? pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
+        if (!rc) rc = fr && fr->codons ? pmx_launch_pairs_gather_codons(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
+                                                                        b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep)
+                    : fr       ? pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
                                                                     b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep, fr->ref)
                     : stranded ? pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
                                                                   b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, prep)
@@ -4075,6 +4085,142 @@ extern "C" int pmx_gather_pairs_translated_ref_device(const pmx_seqset_t *Q, con
                                                       uint8_t *d_ok, void *stream)
 {
     return gather_pairs_frames_device(Q, R, n, d_pairs, d_frame, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, true);
+}
+
+// ---- frameshift-aware translated search: codon streams through pmx_swfs ----
+extern "C" int32_t pmx_frameshift_max_window(void) { return PMX_FRAMESHIFT_MAX_WINDOW; }
+
+// What every _frameshift entry refuses about its strand mode, penalty, matrix, mode, width and outputs, before any GPU work.  *fr: the
+// run's strands (d_strand: a strand byte per pair, listed pairs only), code and penalty.
+static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint8_t *d_strand, int32_t frameshift, const uint8_t *code, FrameRun *fr)
+{
+    if (strand_mode < PMX_STRAND_FORWARD || strand_mode > PMX_STRAND_BOTH) {
+        set_err("strand mode %d is outside 0 .. 2 (PMX_STRAND_FORWARD, PMX_STRAND_REVERSE, PMX_STRAND_BOTH)", strand_mode); return -1;
+    }
+    if (d_strand && strand_mode != PMX_STRAND_FORWARD) { set_err("a strand byte per pair takes strand mode PMX_STRAND_FORWARD, not %d", strand_mode); return -1; }
+    if (frameshift < 0) { set_err("the frameshift penalty is passed as a non-negative number, not %d", (int)frameshift); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("the frameshift entries take no PSSM matrix: a profile belongs to one protein query"); return -1; }
+    if (cfg->mode != PMX_MODE_SW) { set_err("the frameshift entries align locally: mode %d is not PMX_MODE_SW", cfg->mode); return -1; }
+    if (cfg->width != 0 && cfg->width != 32) { set_err("the frameshift entries compute in 32 bits: width %d is neither 0 nor 32", cfg->width); return -1; }
+    if (cfg->want & PMX_WANT_STATS) { set_err("the frameshift entries have no statistics (PMX_WANT_STATS)"); return -1; }
+    if (cfg->want & PMX_WANT_CIGAR) { set_err("the frameshift entries have no CIGAR output (PMX_WANT_CIGAR): there is no traceback with frameshift operators"); return -1; }
+    if (cfg->matrix->size > pmx_swfs_max_msize()) {
+        set_err("the frameshift kernel keeps the matrix in LDS: %d symbols exceed %d", cfg->matrix->size, pmx_swfs_max_msize()); return -1;
+    }
+    fr->ref = false; fr->codons = true; fr->frameshift = frameshift;
+    fr->first = strand_mode == PMX_STRAND_REVERSE ? 1 : 0;
+    fr->per = strand_slots(strand_mode);
+    fr->d_frame = d_strand;
+    if (code) memcpy(fr->code.v, code, 64); else pmx_genetic_code_host(fr->code.v);
+    return 0;
+}
+// max_qlen bounds N = W - 2, the rows the kernel sees.
+static int frameshift_rows_check(int32_t max_qlen)
+{
+    if (max_qlen > PMX_FRAMESHIFT_MAX_WINDOW - 2) {
+        set_err("a codon stream of %d letters exceeds the %d of the longest window, PMX_FRAMESHIFT_MAX_WINDOW = %d nucleotides",
+                (int)max_qlen, PMX_FRAMESHIFT_MAX_WINDOW - 2, PMX_FRAMESHIFT_MAX_WINDOW);
+        return -1;
+    }
+    return 0;
+}
+
+// A chunk's alignment: `slots` codon streams of b against their proteins into d_out.  Streams longer than one strip keep their
+// boundary columns in scratch, at most 256 MiB of it: the launcher then runs the slots in parts.
+static int swfs_chunk(const pmx_config_t *cfg, const FrameRun &fr, int64_t slots, const PairsChunkBufs &b, int32_t max_qlen, int32_t max_rlen,
+                      pmx_record_t *d_out, hipStream_t st)
+{
+    DevMat dm;
+    if (get_devmat(cfg->matrix, &dm)) return -1;
+    PmxBatch pb = {b.q, b.qoff, b.r, b.roff, slots, max_qlen, max_rlen, 0, nullptr, nullptr, nullptr, 0, 0};
+    void *bnd = nullptr; long long bnd_slots = 0;
+    if (max_qlen > pmx_swfs_strip_rows()) {
+        const size_t per_slot = pmx_swfs_bound_bytes_per_slot(max_rlen);
+        bnd_slots = std::max<long long>(4, (long long)(PMX_PAIRS_CHUNK_BYTES / (double)per_slot) / 4 * 4);
+        bnd_slots = std::min<long long>(bnd_slots, (slots + 3) / 4 * 4);
+        if (scratch_reserve(per_slot * (size_t)bnd_slots, &bnd, SCR_SWFS)) return -1;
+    }
+    const int rc = pmx_launch_swfs(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, bnd_slots, d_out, st, &g_last_kernel);
+    if (rc) { set_err(rc < 0 ? "frameshift kernel launch failed: %s" : "the frameshift kernel does not take this batch%s", rc < 0 ? hipGetErrorString((hipError_t)(-rc)) : ""); return -1; }
+    return 0;
+}
+
+// The score road of a frameshift batch over listed pairs: every chunk's per * cn streams through pmx_swfs into scratch, then the strand
+// fold straight into the caller's arrays (it writes the bad pairs' records too; per 1: the one slot's record and strand).
+static int pairs_run_codons(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
+                            int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out,
+                            hipStream_t st, int64_t chunk, const FrameRun &fr)
+{
+    pmx_record_t *srec = nullptr;
+    if (scratch_carve(SCR_PSRCH, [&](Carver &c) { srec = c.take<pmx_record_t>((size_t)fr.per * (size_t)chunk); })) return -1;
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            int rc = swfs_chunk(cfg, fr, fr.per * cn, b, max_qlen, max_rlen, srec, st);
+            if (rc) return rc;
+            rc = pmx_launch_pairs_fold_strands(srec, nullptr, b.ok, b.sflag, cn, fr.per, 0, d_out + c0, nullptr,
+                                               d_strand_out ? d_strand_out + c0 : nullptr, nullptr, st);
+            if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
+            return 0;
+        }, PMX_STRAND_FORWARD, &fr);
+}
+
+extern "C" int pmx_align_pairs_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                 int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                 int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                 pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts)
+{
+    FrameRun fr;
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr)) return -1;
+    if (n > 0 && fr.per > 1 && !d_strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    if (n == 0) return 0;
+    if (frameshift_rows_check(max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, false)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run_codons(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, (hipStream_t)stream,
+                            pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
+}
+
+extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                              const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                              uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                              uint8_t *d_ok, void *stream)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
+    if (!d_qoff || !d_roff || (n > 0 && (!d_pairs || !d_qout || !d_rout))) { set_err("null buffer"); return -1; }
+    if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    if (n == 0) return 0;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (Q->dev != dev || R->dev != dev) {
+        set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev != dev ? Q->dev : R->dev, dev); return -1;
+    }
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    hipStream_t st = (hipStream_t)stream;
+    PmxCodeTable ct;
+    if (code) memcpy(ct.v, code, 64); else pmx_genetic_code_host(ct.v);
+    int32_t *qlen = nullptr, *rlen = nullptr, *tw = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
+    const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
+    if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
+            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2); tw = c.take<int32_t>((size_t)n);
+            qsrc = c.take<int64_t>((size_t)n); rsrc = c.take<int64_t>((size_t)n);
+            ok = c.take<uint8_t>((size_t)n); sflag = c.take<uint8_t>((size_t)n);
+            scan = c.take<unsigned char>(scan_bytes);
+        })) return -1;
+    if (d_ok) ok = d_ok;
+    int rc = pmx_launch_pairs_resolve_codons(d_pairs, d_strand, 0, 1, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                             qlen, rlen, tw, qsrc, rsrc, ok, sflag, st);
+    if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_pairs_gather_codons(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, tw, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
+                                                 d_qout, q_capacity, d_rout, r_capacity, ct, st);
+    if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
+    return 0;
 }
 
 // ---- strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device) ----
@@ -4515,6 +4661,66 @@ extern "C" int pmx_align_pairs_translated_ref(const pmx_config_t *cfg, const pmx
     return align_pairs_frames_host(cfg, Q, R, n, pairs, frame, frame_mode, code, out, stats_out, frame_out, opts, true);
 }
 
+// Listed pairs over a set with host offsets, the descriptors below `end` good: the first whose query window has fewer than three
+// nucleotides -- no codon stream --, refused with its number; 0 when there is none.
+static int short_window_check(const pmx_seqset *Q, const pmx_pair_t *pairs, int64_t end)
+{
+    for (int64_t k = 0; k < end; ++k) {
+        const pmx_pair_t &p = pairs[k];
+        const int64_t W = p.q_len < 0 ? Q->h_off[(size_t)p.q + 1] - Q->h_off[(size_t)p.q] - p.q_beg : p.q_len;
+        if (W < 3) { set_err("pair %lld: query: a window of %lld nucleotides has no codon", (long long)k, (long long)W); return -1; }
+    }
+    return 0;
+}
+
+// pmx_align_pairs_frameshift: the host entry over listed pairs of the frameshift-aware alignment, laid out as
+// align_pairs_frames_host.  A window shorter than three nucleotides is found on the device only, so the records' flags are always scanned.
+extern "C" int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                          int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                          int32_t frameshift, const uint8_t *code,
+                                          pmx_record_t *out, uint8_t *strand_out, const pmx_pairs_opts_t *opts)
+{
+    FrameRun fr;
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr)) return -1;
+    if (n > 0 && fr.per > 1 && !strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    if (n == 0) return 0;
+    if (strand)
+        for (int64_t k = 0; k < n; ++k)
+            if (strand[k] > 1) { set_err("pair %lld: strand byte %d is neither 0 nor 1", (long long)k, (int)strand[k]); return -1; }
+    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
+    int64_t mq = 1, mr = 1;
+    if (host_offsets) {
+        const PairScan s = scan_pairs(Q, R, pairs, 0, n);
+        if (short_window_check(Q, pairs, s.bad >= 0 ? s.bad : n)) return -1;
+        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
+        mq = fr.letters((int32_t)s.mq); mr = s.mr;
+    }
+    if (frameshift_rows_check((int32_t)mq) || pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, false)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr;
+    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the strand bytes in, then out
+    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC)) return -1;
+    uint8_t *dsin = (uint8_t *)dp + up_bytes, *dsout = dsin + n;
+    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (strand) { HIP_OR_RET(hipMemcpyAsync(dsin, strand, (size_t)n, hipMemcpyHostToDevice, st)); fr.d_frame = dsin; }
+    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
+    if (!host_offsets) {
+        if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
+        q32 = fr.letters(q32);
+        if (frameshift_rows_check(q32)) return -1;
+    }
+    const int rc = pairs_run_codons(cfg, Q, R, n, dp, q32, r32, drec, dsout, st, pairs_chunk(n, q32, r32, opts, fr.per), fr);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    if (strand_out) HIP_OR_RET(hipMemcpyAsync(strand_out, dsout, (size_t)n, hipMemcpyDeviceToHost, st));
+    return pairs_copy_back(n, drec, nullptr, out, nullptr, true, st);
+}
+
 extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,
                                    pmx_record_t *out, pmx_stats_t *stats_out, const pmx_pairs_opts_t *opts)
 {
@@ -4628,12 +4834,12 @@ struct PairHitBufs { HitCols hit; int64_t capacity; int64_t *counts, *first_bad;
 // A chunk's alignment for the entries that keep its records in scratch (set search, top-K): the records (and statistics) of the chunk's
 // pairs and, when the entry chooses the strand, those of its alignment slots before the fold and the folded validity bytes.
 struct ChunkAlign {
-    bool stats, chosen; int per; const FrameRun *fr;              // fr != nullptr: the slots are frames of a translated side
+    bool stats, chosen; int per; const FrameRun *fr;              // fr != nullptr: the slots are frames of a translated side, or (fr->codons) the strands' codon streams
     pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr; uint8_t *okf = nullptr;
     ChunkAlign(const pmx_config_t *cfg, int strand_mode, const FrameRun *frames = nullptr)
         : stats((cfg->want & PMX_WANT_STATS) != 0), chosen(strand_mode != PMX_STRAND_FORWARD || frames != nullptr),
           per(frames ? frames->per : strand_slots(strand_mode)), fr(frames) {}
-    int marked() const { return fr ? 2 : chosen ? 1 : 0; }       // what the chunk's records carry in their flags (append_hits, emit)
+    int marked() const { return fr && !fr->codons ? 2 : chosen ? 1 : 0; }       // what the chunk's records carry in their flags (append_hits, emit): a frame, a strand
     void carve(Carver &c, int64_t chunk)
     {
         crec = c.take<pmx_record_t>((size_t)chunk);
@@ -4648,9 +4854,11 @@ struct ChunkAlign {
     int run(const pmx_config_t *cfg, const PairsChunkBufs &b, int64_t cn, int32_t max_qlen, int32_t max_rlen, int64_t p0, int64_t *first_bad,
             hipStream_t st) const
     {
-        int rc = run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, chosen ? srec : crec, chosen ? sst : cst, st);
+        int rc = fr && fr->codons ? swfs_chunk(cfg, *fr, cn * per, b, max_qlen, max_rlen, srec, st)
+                                  : run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, chosen ? srec : crec, chosen ? sst : cst, st);
         if (rc) return rc;
-        rc = fr     ? pmx_launch_pairs_fold_frames(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
+        rc = fr && fr->codons ? pmx_launch_pairs_fold_strands(srec, nullptr, b.ok, b.sflag, cn, per, 1, crec, nullptr, nullptr, okf, st)
+           : fr     ? pmx_launch_pairs_fold_frames(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
            : chosen ? pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
                     : pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
         if (!rc && first_bad) rc = pmx_launch_pairs_first_bad(chosen ? okf : b.ok, cn, p0, first_bad, st);
@@ -4685,6 +4893,18 @@ static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const 
         }, strand_mode, fr);
 }
 
+// The side an entry translates, checked and turned into the run's FrameRun.  TR_NONE: nothing.  TR_QUERY / TR_REF: frame_mode and code.
+// TR_CODONS (the _frameshift entries): *strand_mode and frameshift; the strands become the run's slots, so the mode the pipeline
+// below sees is PMX_STRAND_FORWARD.
+static int side_check(const pmx_config_t *cfg, int translated, int frame_mode, const uint8_t *code, int *strand_mode, int32_t frameshift, FrameRun *fr)
+{
+    if (translated == TR_NONE) return 0;
+    if (translated != TR_CODONS) return frames_check(cfg, frame_mode, nullptr, code, fr, translated == TR_REF);
+    if (frameshift_check(cfg, *strand_mode, nullptr, frameshift, code, fr)) return -1;
+    *strand_mode = PMX_STRAND_FORWARD;
+    return 0;
+}
+
 // The device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.  translated (TR_QUERY /
 // TR_REF): frame_mode and code of the _translated / _translated_ref entry (strand_mode is then forward, d_hit_strand receives the frames).
 static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
@@ -4692,14 +4912,14 @@ static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
                                int32_t max_qlen, int32_t max_rlen, int32_t min_score,
                                pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
                                int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
-                               int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
+                               int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (search_pairs_shape_check(Q, &R, shape, first, n, d_pairs)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) ||
+    if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) ||
         search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
     if (n == 0) {
@@ -4707,7 +4927,7 @@ static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
         return 0;
     }
     if (!d_counts) { set_err("null counts"); return -1; }
-    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    if ((translated == TR_CODONS && frameshift_rows_check(max_qlen)) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const PairHitBufs o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_counts, nullptr};
@@ -4756,6 +4976,17 @@ extern "C" int pmx_search_pairs_translated_ref_device(const pmx_config_t *cfg, c
 {
     return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                                capacity, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, TR_REF, frame_mode, code);
+}
+
+extern "C" int pmx_search_pairs_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                                  int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                                  int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                                  pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                  int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                                  int strand_mode, uint8_t *d_hit_strand, int32_t frameshift, const uint8_t *code)
+{
+    return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                               capacity, d_counts, stream, opts, strand_mode, d_hit_strand, TR_CODONS, 0, code, frameshift);
 }
 
 extern "C" void pmx_pair_hits_free(pmx_pair_hits_t *hits) { free(hits); }
@@ -4811,7 +5042,7 @@ struct HostHits {
 // without a frame is found on the device only, so the lowest bad pair is always asked for.
 static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
                              const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, bool with_strand, pmx_pair_hits_t **result,
-                             int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
+                             int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (!result) { set_err("null result pointer"); return -1; }
@@ -4824,7 +5055,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) || search_pairs_want_check(cfg, stats) ||
+    if (side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) || search_pairs_want_check(cfg, stats) ||
         strand_mode_check(cfg, strand_mode)) return -1;
     HostHits hh;
     // the result: one block -- header, descriptors, indices, records, statistics (, strand bytes)
@@ -4843,6 +5074,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     SetLens m;
     if (host_offsets && listed) {
         const PairScan s = scan_pairs(Q, R, pairs, 0, n);
+        if (translated == TR_CODONS && short_window_check(Q, pairs, s.bad >= 0 ? s.bad : n)) return -1;
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
         m.mq = (int32_t)s.mq; m.mr = (int32_t)s.mr; m.mnr = (int32_t)s.mnr;
     } else if (host_offsets && window_host_lens(Q, R, shape, first, n, &m)) return -1;
@@ -4851,7 +5083,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     const bool find_bad = !host_offsets || fr != nullptr;
     const int per = fr ? fr->per : strand_slots(strand_mode);
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if (pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
+    if ((translated == TR_CODONS && frameshift_rows_check(m.mq)) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
@@ -4879,7 +5111,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
             if (!host_offsets) {
                 if (device_maxlens(Q, R, dp, sn, &m.mq, &m.mr, st)) return -1;
                 to_letters();
-                if (pssm_batch_check(cfg->matrix, m.mq, m.mq)) return -1;
+                if (pssm_batch_check(cfg->matrix, m.mq, m.mq) || (translated == TR_CODONS && frameshift_rows_check(m.mq))) return -1;
             }
         }
         const int64_t p0 = listed ? s0 : first + s0;     // the slice's first pair in the enumeration
@@ -4928,6 +5160,12 @@ extern "C" int pmx_search_pairs_translated_ref(const pmx_config_t *cfg, const pm
     return search_pairs_host(cfg, Q, R, first, n, pairs, opts, PMX_STRAND_FORWARD, true, (pmx_pair_hits_t **)result, TR_REF, frame_mode, code);
 }
 extern "C" void pmx_frame_hits_free(pmx_frame_hits_t *hits) { free(hits); }
+extern "C" int pmx_search_pairs_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                           const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode,
+                                           int32_t frameshift, const uint8_t *code, pmx_strand_hits_t **result)
+{
+    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, strand_mode, true, (pmx_pair_hits_t **)result, TR_CODONS, 0, code, frameshift);
+}
 
 // ==================================================================== per-query top-K ===
 // pmx_search_topk[_device] (semantics: include/parasail_amd.h): the chunk loop of the set batches over whole rows of the
@@ -5043,14 +5281,14 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
                               pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
                               int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
                               void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
-                              int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
+                              int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (topk_shape_check(Q, &R, q_first, nq, k, skip_self)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || (translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) ||
+    if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) ||
         search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
     if (nq == 0) {
@@ -5060,7 +5298,7 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
     }
     if (!d_row_off) { set_err("null row offsets"); return -1; }
     if (!d_counts) { set_err("null counts"); return -1; }
-    if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    if ((translated == TR_CODONS && frameshift_rows_check(max_qlen)) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const TopkOut o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_row_off, d_row_passing, d_counts, nullptr};
@@ -5105,6 +5343,17 @@ extern "C" int pmx_search_topk_translated_ref_device(const pmx_config_t *cfg, co
 {
     return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                               capacity, d_row_off, d_row_passing, d_counts, stream, opts, PMX_STRAND_FORWARD, d_hit_frame, TR_REF, frame_mode, code);
+}
+
+extern "C" int pmx_search_topk_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                                 int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                                 pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                 int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                                 void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
+                                                 int32_t frameshift, const uint8_t *code)
+{
+    return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, strand_mode, d_hit_strand, TR_CODONS, 0, code, frameshift);
 }
 
 // Test hook (include/parasail_amd.h): the chunk loop of topk_run over records the caller made up instead of alignments -- the same
@@ -5160,7 +5409,7 @@ extern "C" void pmx_topk_hits_free(pmx_topk_hits_t *hits) { free(hits); }
 // translated (pmx_search_topk_translated): a pmx_topk_frame_hits_t, the same layout with the frames in the last column.
 static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
                             const pmx_topk_opts_t *opts, int strand_mode, bool with_strand, pmx_topk_hits_t **result,
-                            int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr)
+                            int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
     FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
     if (!result) { set_err("null result pointer"); return -1; }
@@ -5171,7 +5420,7 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if ((translated && frames_check(cfg, frame_mode, nullptr, code, &frames, translated == TR_REF)) || search_pairs_want_check(cfg, stats) ||
+    if (side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) || search_pairs_want_check(cfg, stats) ||
         strand_mode_check(cfg, strand_mode)) return -1;
     HostHits hh;
     // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics (, strand bytes)
@@ -5197,7 +5446,7 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     to_letters();
     const bool find_bad = !host_offsets || fr != nullptr;
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if (pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
+    if ((translated == TR_CODONS && frameshift_rows_check(m.mq)) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
@@ -5268,3 +5517,9 @@ extern "C" int pmx_search_topk_translated_ref(const pmx_config_t *cfg, const pmx
     return search_topk_host(cfg, Q, R, q_first, nq, opts, PMX_STRAND_FORWARD, true, (pmx_topk_hits_t **)result, TR_REF, frame_mode, code);
 }
 extern "C" void pmx_topk_frame_hits_free(pmx_topk_frame_hits_t *hits) { free(hits); }
+extern "C" int pmx_search_topk_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                          const pmx_topk_opts_t *opts, int strand_mode, int32_t frameshift, const uint8_t *code,
+                                          pmx_topk_strand_hits_t **result)
+{
+    return search_topk_host(cfg, Q, R, q_first, nq, opts, strand_mode, true, (pmx_topk_hits_t **)result, TR_CODONS, 0, code, frameshift);
+}

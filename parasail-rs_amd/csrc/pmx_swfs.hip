@@ -1,0 +1,184 @@
+// pmx_swfs.hip -- frameshift-aware local alignment of a codon stream against a protein: the three-frame DP of DESIGN 2.5k
+// (semantics: include/parasail_amd.h, "Frameshift-aware translated search").  gfx950 only.
+//
+// A slot is one codon stream T (N = W - 2 letters, letter i the translation of oriented nucleotides i .. i + 2, written by
+// pmx_pairs_gather_codons_kernel) against one protein of m letters:
+//
+//   D(i,j) = max(0, H(i-3,j-1), H(i-2,j-1) - fs, H(i-4,j-1) - fs)        M = D + s(T[i], r[j])
+//   E(i,j) = max(H(i,j-1) - open, E(i,j-1) - ext)                        F(i,j) = max(H(i-3,j) - open, F(i-3,j) - ext)
+//   H(i,j) = max(0, M, E, F)
+//
+// Mapping (pmx_sw16m.hip's): a group of G lanes per slot, R consecutive rows per lane in registers, lane g on column t - g in step t,
+// the transposed matrix in LDS, group_shift_up<G> for the lane hand-offs.  What differs is the reach of a cell: three rows up in its
+// own column (H and F) and two to four rows up in the column before (H).  So a step hands SEVEN values to the lane below -- the last
+// four H and the last three F of the column the lane above has just finished -- and every lane keeps the four H it was handed one
+// step earlier: they are the column before, the diagonal's history.  R >= 4 keeps every such source inside one lane.
+//
+// Strips.  A window of more than G * R rows runs in strips of G * R rows, top to bottom.  The last lane of a strip stores its four
+// H and three F per column (two int4) into the slot's boundary scratch, member 0 of the next strip loads them where the first strip
+// takes the matrix's edge (H = 0, F = -inf).  Two boundary buffers alternate by strip parity, so a strip never reads the buffer it
+// writes; a workgroup barrier with a fence separates the strips (one wave per workgroup).
+//
+// Arithmetic: 32-bit integers, one slot per lane group.  The largest score, 4 094 rows x 32 767, is below 2^28; penalties are clamped
+// to 2^28 by the launcher (a penalty above every score acts as infinity: H >= 0, and a negative E, F or D term never wins), -inf is
+// -2^29, so nothing can wrap and width 0 and width 32 are the same exact kernel.
+// Plain C++, vector loads and stores only.
+#include "pmx_common.h"
+#include "pmx_pk16.h"
+
+#define PMX_SWFS_NEG (-(1 << 29))
+
+template <int G, int R>
+__global__ __launch_bounds__(64)
+void pmx_swfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff,
+                     const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff,
+                     long long n, int max_rows, int max_rlen,
+                     const int16_t *__restrict__ gmat, const uint8_t *__restrict__ gmap, int msize,
+                     int open, int ext, int fs,
+                     int4 *bnd /* per slot of the launch: 2 buffers x max_rlen columns x 2 int4 */,
+                     pmx_record_t *__restrict__ out)
+{
+    static_assert(R >= 4, "the rows a cell reaches lie in its own lane or the lane above");
+    static_assert(G == 16 || G == 64, "group_shift_up without a select");
+    constexpr int NPW = 64 / G;                 // slots per wave = per workgroup
+    constexpr int NEG = PMX_SWFS_NEG;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    int16_t *matT = reinterpret_cast<int16_t *>(lds);              // matT[r * msize + q] = score(q, r)
+    unsigned char *map = lds + (size_t)msize * msize * 2;
+
+    const int lane = threadIdx.x;
+    const int g = lane % G, slotw = lane / G;
+    for (int i = lane; i < msize * msize; i += 64) matT[i] = gmat[(i % msize) * msize + i / msize];
+    for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
+    __syncthreads();
+
+    long long slot = (long long)blockIdx.x * NPW + slotw;
+    const bool live = slot < n;
+    if (!live) slot = n - 1;
+    const long long qb = qoff[slot], rb = roff[slot];
+    int N = (int)(qoff[slot + 1] - qb), m = (int)(roff[slot + 1] - rb);
+    N = min(N, max_rows); m = min(m, max_rlen);                    // (resolve keeps both inside; scratch and loops rely on it)
+    const uint8_t *qs = qbuf + qb, *ref = rbuf + rb;
+    int4 *bslot = bnd ? bnd + ((size_t)blockIdx.x * NPW + slotw) * 4 * (size_t)max_rlen : nullptr;
+
+    int wN = N, wm = m;                                            // the wave's longest window and reference: uniform trip counts
+#pragma unroll
+    for (int d = 32; d >= G; d >>= 1) { wN = max(wN, __shfl_xor(wN, d)); wm = max(wm, __shfl_xor(wm, d)); }
+    const int nstrips = (wN + G * R - 1) / (G * R), T_ = wm + G - 1;
+
+    int best = 0, bi = 0, bj = 0;                                   // a zero maximum ends at row 0, column 0
+    for (int s = 0; s < nstrips; ++s) {
+        const int row0 = s * G * R + g * R;
+        int ql[R], vm[R];                                          // the rows' letters; -1 for a row of the stream, 0 for one beyond it
+#pragma unroll
+        for (int k = 0; k < R; ++k) { vm[k] = row0 + k < N ? -1 : 0; ql[k] = row0 + k < N ? (int)map[qs[row0 + k]] : 0; }
+        int Hp[R], E[R], d4[4], oH[4], oF[3];
+#pragma unroll
+        for (int k = 0; k < R; ++k) { Hp[k] = 0; E[k] = NEG; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { d4[k] = 0; oH[k] = 0; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) oF[k] = NEG;
+        const int4 *brd = s > 0 ? bslot + (size_t)((s - 1) & 1) * 2 * max_rlen : nullptr;
+        int4 *bwr = s + 1 < nstrips ? bslot + (size_t)(s & 1) * 2 * max_rlen : nullptr;
+
+        for (int t = 0; t < T_; ++t) {
+            const int col = t - g;
+            int uH[4], uF[3];                                      // the lane above: its last four H, last three F of column `col`
+#pragma unroll
+            for (int k = 0; k < 4; ++k) uH[k] = group_shift_up<G>(oH[k], 0, g);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) uF[k] = group_shift_up<G>(oF[k], NEG, g);
+            const bool valid = col >= 0 && col < m;
+            if (valid) {
+                if (g == 0 && brd) {                               // member 0 of a later strip: the strip above left the column here
+                    const int4 a = brd[2 * col], b = brd[2 * col + 1];
+                    uH[0] = a.x; uH[1] = a.y; uH[2] = a.z; uH[3] = a.w;
+                    uF[0] = b.x; uF[1] = b.y; uF[2] = b.z;
+                }
+                const int16_t *mrow = matT + (int)map[ref[col]] * msize;
+                int Hc[R], Fc[R];
+                int cm = 0;                                        // the column's maximum over the rows of the stream (H >= 0)
+#pragma unroll
+                for (int k = 0; k < R; ++k) {
+                    // column j - 1, rows i - 2, i - 3, i - 4: d4[0 .. 3] are rows -4 .. -1 of this lane, Hp[] rows 0 ..
+                    const int hm2 = k >= 2 ? Hp[k - 2] : d4[k + 2];
+                    const int hm3 = k >= 3 ? Hp[k - 3] : d4[k + 1];
+                    const int hm4 = k >= 4 ? Hp[k - 4] : d4[k];
+                    const int D = max(max(0, hm3), max(hm2, hm4) - fs);
+                    const int M = D + (int)mrow[ql[k]];
+                    const int e = max(Hp[k] - open, E[k] - ext);
+                    // column j, row i - 3: uH[1 .. 3] / uF[0 .. 2] are rows -3 .. -1
+                    const int h3 = k >= 3 ? Hc[k - 3] : uH[k + 1];
+                    const int f3 = k >= 3 ? Fc[k - 3] : uF[k];
+                    const int f = max(h3 - open, f3 - ext);
+                    const int h = max(max(0, M), max(e, f));
+                    Hc[k] = h; Fc[k] = f; E[k] = e;
+                    cm = max(cm, h & vm[k]);
+                }
+                // a new best is rare: one branch per column.  Columns ascend within a strip, so an equal score wins only from a
+                // later strip at a smaller column; within the column the first row that holds the maximum.
+                if (cm > best || (cm == best && col < bj)) {
+                    best = cm; bj = col;
+#pragma unroll
+                    for (int k = R - 1; k >= 0; --k) if ((Hc[k] & vm[k]) == cm) bi = row0 + k;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { d4[k] = uH[k]; oH[k] = Hc[R - 4 + k]; }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) oF[k] = Fc[R - 3 + k];
+#pragma unroll
+                for (int k = 0; k < R; ++k) Hp[k] = Hc[k];
+                if (g == G - 1 && bwr) {
+                    bwr[2 * col] = make_int4(oH[0], oH[1], oH[2], oH[3]);
+                    bwr[2 * col + 1] = make_int4(oF[0], oF[1], oF[2], 0);
+                }
+            }
+        }
+        if (s + 1 < nstrips) { __threadfence_block(); __syncthreads(); }
+    }
+
+    // the group's winner: highest score, then lowest column, then lowest row (the first maximum in column-major order)
+#pragma unroll
+    for (int d = G / 2; d >= 1; d >>= 1) {
+        const int os = __shfl_xor(best, d), oj = __shfl_xor(bj, d), oi = __shfl_xor(bi, d);
+        if (os > best || (os == best && (oj < bj || (oj == bj && oi < bi)))) { best = os; bj = oj; bi = oi; }
+    }
+    if (g == 0 && live) {
+        pmx_record_t rec;
+        rec.score = best; rec.end_query = bi + 2; rec.end_ref = bj; rec.flags = 0;
+        out[slot] = rec;
+    }
+}
+
+// LDS of a launch: the transposed matrix as int16 and the byte map.
+static size_t swfs_lds_bytes(int msize) { return (size_t)msize * msize * 2 + 256; }
+
+int pmx_swfs_max_msize() { return 128; }
+size_t pmx_swfs_bound_bytes_per_slot(int max_rlen) { return sizeof(int4) * 4 * (size_t)max_rlen; }
+int pmx_swfs_strip_rows() { return 16 * 10; }
+
+// n slots of up to max_rows x max_rlen.  bnd: boundary scratch for `bnd_slots` slots (needed when max_rows exceeds one strip; the
+// launch then runs in parts of bnd_slots slots, one behind the other on `stream`).  0 launched, 1 not eligible, <0 HIP error.
+int pmx_launch_swfs(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
+                    pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
+{
+    constexpr int G = 16, R = 10, NPW = 64 / G;
+    if (m.pssm || m.msize > pmx_swfs_max_msize() || b.q_shared) return 1;
+    if (b.n <= 0) return 0;
+    const int cap = 1 << 28;
+    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
+    const bool strips = b.max_qlen > G * R;
+    if (strips && (!bnd || bnd_slots < NPW)) return 1;
+    const long long part = strips ? bnd_slots / NPW * NPW : b.n;
+    for (long long p0 = 0; p0 < b.n; p0 += part) {
+        const long long pn = b.n - p0 < part ? b.n - p0 : part;
+        hipLaunchKernelGGL((pmx_swfs_kernel<G, R>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfs_lds_bytes(m.msize), stream,
+                           b.qbuf, b.qoff + p0, b.rbuf, b.roff + p0, pn, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
+                           open, ext, fs, strips ? (int4 *)bnd : nullptr, d_out + p0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return -(int)e;
+    }
+    if (kernel_name) *kernel_name = strips ? "pmx_swfs_kernel<16,10>/strips" : "pmx_swfs_kernel<16,10>";
+    return 0;
+}
