@@ -869,8 +869,8 @@ void pmx_topk_frame_hits_free(pmx_topk_frame_hits_t *hits);
  * PMX_FRAMESHIFT_MAX_WINDOW nucleotides.  max_qlen of the device entries bounds N = W - 2, the rows the kernel sees; a window whose N
  * exceeds max_qlen makes the pair bad.  The host entries size max_qlen from the longest window.
  *
- * Refused with -1 and a pmx_last_error() text before any GPU work: any other mode or width; PMX_WANT_STATS and PMX_WANT_CIGAR (there
- * is no traceback with frameshift operators); a PSSM matrix; a matrix of more than 128 symbols; frameshift < 0; a strand mode outside
+ * Refused with -1 and a pmx_last_error() text before any GPU work: any other mode or width; PMX_WANT_STATS and PMX_WANT_CIGAR (these
+ * entries have no traceback with frameshift operators: the _frameshift_cigar entries below are the pass that has); a PSSM matrix; a matrix of more than 128 symbols; frameshift < 0; a strand mode outside
  * 0 .. 2; strand bytes per pair together with a strand mode other than PMX_STRAND_FORWARD; max_qlen above
  * PMX_FRAMESHIFT_MAX_WINDOW - 2 (host entries: a window above PMX_FRAMESHIFT_MAX_WINDOW); everything the corresponding stranded or
  * untranslated entry refuses, with the same texts.  n == 0 / nq == 0 behave as there.  The host entries name the first pair that is
@@ -922,6 +922,80 @@ int pmx_search_topk_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_
 int pmx_search_topk_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
                                const pmx_topk_opts_t *opts, int strand_mode, int32_t frameshift, const uint8_t *code,
                                pmx_topk_strand_hits_t **result);
+
+/* Frameshift traceback (extension): the alignment behind a frameshift record -- CIGAR text with frameshift operators, the begin of the
+ * path, and statistics -- as a second pass over listed pairs, typically the hit pairs and strand bytes a frameshift search returned
+ * (the hit list is the interface, as for every other search here).  The recurrence, the codon stream, the record, the strand rules
+ * and the limits are those of the section above; records and strand bytes are byte-identical to pmx_align_pairs_frameshift[_device].
+ * New is the path.  It is deterministic and follows the precedence of the project's other tracebacks, carried over to the wider
+ * recurrence.
+ *
+ * Decisions at cell (i, j).
+ *   H source.  If M >= E and M >= F the source is M; otherwise if F >= E it is F; otherwise it is E.  If the resulting H <= 0 the cell
+ *     is ZERO: H = 0 and no path passes through it.
+ *   D source (where the H source is M).  With h3 = H(i-3,j-1), h2 = H(i-2,j-1) - fs, h4 = H(i-4,j-1) - fs, D = max(0, h3, h2, h4):
+ *     START if D == 0 (zero wins every tie: a path never begins with a frameshift that buys nothing); otherwise IN-FRAME if h3 == D;
+ *     otherwise SHORT (2 rows) if h2 == D; otherwise LONG (4 rows).  Terms with a negative index are 0 for H, as in the recurrence.
+ *   E opened iff H(i,j-1) - open > E(i,j-1) - extend, strictly; otherwise it is extended.
+ *   F opened iff H(i-3,j) - open > F(i-3,j) - extend, strictly.
+ *
+ * The walk starts at cell (end_query - 2, end_ref) in state H.
+ *   State H, M source: emit a match column -- '=' if the two letters map to the same matrix index, otherwise 'X' -- then: START: the
+ *     path begins at this cell, stop; IN-FRAME: go to (i-3, j-1); SHORT: emit '/' and go to (i-2, j-1); LONG: emit '\' and go to
+ *     (i-4, j-1).
+ *   State H, F source / E source: switch to state F / E at the same cell.
+ *   State F at (i, j): emit one codon-against-gap op and go to (i-3, j); the state becomes H if F(i, j) was opened, else stays F.
+ *   State E at (i, j): emit one reference-letter-against-gap op and go to (i, j-1); the state becomes H if E(i, j) was opened.
+ *
+ * The text is in path order from begin to end, run-length encoded as <count><op> like every CIGAR here.  '=' and 'X' stand for one
+ * codon against one reference letter.  The codon-gap op is the letter of the F / DEL state and the reference-gap op the letter of the
+ * E / INS state: 'I' and 'D' by default, following PMX_CIGAR_SWAP_ID (pmx_conventions.h).  '/' means one nucleotide is missing from
+ * the read -- the next codon overlaps the previous one by one base; '\' means one nucleotide too many.  A frameshift op sits directly
+ * in front of the match column it leads into; two of them are never adjacent, so their count is always 1.
+ * UNITS: '=', 'X' AND THE CODON-GAP OP CONSUME THREE QUERY NUCLEOTIDES; '/' TAKES ONE BACK; '\' ADDS ONE.  '=', 'X' AND THE
+ * REFERENCE-GAP OP CONSUME ONE REFERENCE LETTER.
+ *
+ * Begins.  beg[2k] = beg_query is the first nucleotide of the first codon -- row i of the START cell -- in the oriented window,
+ * beg[2k+1] = beg_ref its column.  A zero-score record has an empty text and begins (end_query + 1, end_ref + 1) = (3, 1), what the
+ * other local walks report for an empty path.  A bad pair has the bad record, strand 0, an empty text, begins -1 / -1 and zero
+ * statistics; its neighbours are unaffected.
+ *
+ * Statistics (pmx_stats_t).  matches = the number of '=' columns; similar = the number of match columns with a positive matrix score;
+ * length = match columns + gap columns, a codon gap counting 1.  Frameshift ops are not columns.
+ *
+ * What follows, for every non-empty text:
+ *   - its first and its last op are match columns;
+ *   - end_query - beg_query + 1 == 3 (match columns + codon gaps) - #'/' + #'\';
+ *   - end_ref - beg_ref + 1 == match columns + reference gaps;
+ *   - re-scoring the text from (beg_query, beg_ref) -- matrix scores, open / extend per gap run of one kind, fs per frameshift op --
+ *     gives exactly the record's score and end cell;
+ *   - it has at most N + m ops.
+ *
+ * cfg->want must hold PMX_WANT_CIGAR, optionally with PMX_WANT_STATS (here the two may be combined: one walk produces both); the
+ * statistics buffer is present iff PMX_WANT_STATS is set.  Everything else is refused as pmx_align_pairs_frameshift[_device] refuses
+ * it, with the same texts, before any GPU work.  Strand modes and strand bytes are those of the score entry; with PMX_STRAND_BOTH both
+ * strands are swept and the walk runs over the winner's trace.  d_beg (2 n) is optional.  The text buffer follows
+ * pmx_align_pairs_ex_device: offsets start at 0, d_cigar_off[n] is the number of bytes needed, a pair whose text would cross
+ * cigar_capacity is not written, chunk_pairs never changes a byte; the host entry sizes the buffer, runs once more at the exact size
+ * if the text did not fit, and *cigar_buf is released with pmx_free.
+ *
+ * Scratch.  Beside the score entry's: 192 bytes of trace per reference column and strip of 160 rows for each slot, bounded at 256 MiB
+ * per chunk (the value switch PMX_CIGAR_CHUNK_BYTES sets another bound): a chunk whose slots need more runs in parts, sweep then walk,
+ * and no byte of any output depends on the parts.  A call in which four slots -- one workgroup -- exceed the bound is refused before
+ * any GPU work.  pmx_last_kernel() names the trace instantiation of the last part, with "/strips" for windows beyond 162 nucleotides. */
+int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                            int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                            int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                            pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats /* iff PMX_WANT_STATS */,
+                                            int32_t *d_beg /* 2 n, optional */,
+                                            char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off /* n + 1 */,
+                                            void *stream, const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_frameshift_cigar(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                     int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                     int32_t frameshift, const uint8_t *code,
+                                     pmx_record_t *out, uint8_t *strand_out, pmx_stats_t *stats_out /* iff PMX_WANT_STATS */,
+                                     int32_t *beg /* 2 n, optional */, char **cigar_buf, int64_t *cigar_off /* n + 1 */,
+                                     const pmx_pairs_opts_t *opts);
 
 /* Reference-side translation (extension): protein queries against a set of nucleotide sequences -- genes, transcripts, contigs --,
  * the tblastn pairing.  The text above holds with the sides exchanged; what follows states it in full.

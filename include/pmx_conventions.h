@@ -25,4 +25,14 @@
 #define PMX_BAM_OP_FOR_INS_STATE (PMX_CIGAR_LETTER_FOR_INS_STATE == 'D' ? 2u : 1u)
 #define PMX_BAM_OP_FOR_DEL_STATE (PMX_CIGAR_LETTER_FOR_DEL_STATE == 'I' ? 1u : 2u)
 
+/* Frameshift traceback (pmx_align_pairs_frameshift_cigar[_device]; parasail_amd.h, "Frameshift traceback"): two ops beyond BAM's nine,
+ * with the free codes behind "MIDNSHP=X".  '/' -- the path steps over TWO query nucleotides into its next match column: one nucleotide is
+ * missing from the read; '\' -- it steps over FOUR: one nucleotide too many.  DIAMOND and LAST write frameshifts with the same two
+ * characters, '\' for +1 and '/' for -1.  In such a text '=', 'X' and the codon-gap letter (PMX_CIGAR_LETTER_FOR_DEL_STATE) stand for
+ * three query nucleotides; PMX_CIGAR_SWAP_ID exchanges I and D there as everywhere and leaves the two frameshift letters alone. */
+#define PMX_CIGAR_LETTER_FRAMESHIFT_SHORT '/'    /* op code 9  */
+#define PMX_CIGAR_LETTER_FRAMESHIFT_LONG  '\\'   /* op code 10 */
+#define PMX_OP_FRAMESHIFT_SHORT 9u
+#define PMX_OP_FRAMESHIFT_LONG 10u
+
 #endif

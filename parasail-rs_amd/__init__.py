@@ -339,6 +339,11 @@ _sig("pmx_align_pairs_frameshift_device", C.c_int, C.POINTER(pmx_config_t), C.c_
      C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_align_pairs_frameshift", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_frameshift_cigar_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_frameshift_cigar", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_search_pairs_frameshift_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
      C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
      C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
@@ -1073,6 +1078,45 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return out, _take_cigars(cbuf, coff), beg
 
+    def align_pairs_frameshift_cigar(self, Q, R, pairs, frameshift, strand=0, code=None, stats=False, chunk_pairs=0):
+        """The alignments behind align_pairs(..., frameshift=): the same records and strand bytes, and for every pair the CIGAR text
+        of its path -- '=' / 'X' one codon against one reference letter, 'I' a codon against a gap, 'D' a reference letter against
+        a gap, '/' one nucleotide missing from the read, '\\' one too many (include/parasail_amd.h, "Frameshift traceback") -- and
+        the path's begin, int32 [n, 2]: the first nucleotide of the first codon in the oriented window, and its reference column.
+        `strand` is 0, 1, "both" or one byte per pair, as align_pairs(frameshift=) takes it: PairHits.pairs and PairHits.strand of
+        search_pairs(frameshift=) or search_topk(frameshift=) are accepted as they are.  Returns (records, cigars, begins, strand)
+        or, with stats=True, (records, cigars, begins, strand, stats): matches, similar and length along the path."""
+        if not self._profile.is_null():
+            raise BatchError("align_pairs_frameshift_cigar takes no profile")
+        pairs = as_pairs(pairs)
+        n = len(pairs)
+        cfg = self._config()
+        cfg.want = (cfg.want & ~WANT_STATS) | WANT_CIGAR | (WANT_STATS if stats else 0)
+        per_pair = None
+        if strand is None or isinstance(strand, str) or np.ndim(strand) == 0:
+            mode = _strand_mode(0 if strand is None else strand)
+        else:
+            mode, per_pair = STRAND_FORWARD, np.ascontiguousarray(strand, dtype=np.uint8)
+            if len(per_pair) != n:
+                raise BatchError("strand and pairs differ in count")
+        code = _code_arg(code)
+        out = np.zeros(n, dtype=RECORD_DTYPE)
+        won = np.zeros(n, dtype=np.uint8)
+        st = np.zeros(n, dtype=STATS_DTYPE) if stats else None
+        beg = np.zeros((n, 2), dtype=np.int32)
+        coff = np.zeros(n + 1, dtype=np.int64)
+        cbuf = C.c_void_p()
+        opts = pmx_pairs_opts_t(int(chunk_pairs))
+        rc = lib.pmx_align_pairs_frameshift_cigar(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
+                                                  per_pair.ctypes.data if per_pair is not None else None, mode, int(frameshift),
+                                                  code.ctypes.data if code is not None else None, out.ctypes.data, won.ctypes.data,
+                                                  st.ctypes.data if st is not None else None, beg.ctypes.data, C.byref(cbuf),
+                                                  coff.ctypes.data, C.byref(opts))
+        if rc:
+            raise BatchError(lib.pmx_last_error().decode())
+        res = (out, _take_cigars(cbuf, coff), beg, won)
+        return res + (st,) if stats else res
+
     def align_all_pairs(self, S, first=0, count=None, chunk_pairs=0):
         """Pairs [first, first + count) of the strict upper triangle of S x S (row-major; all_pairs_index gives (i, j) of a
         pair), whole sequences, enumerated on the device.  count None: to the last pair."""
@@ -1104,7 +1148,8 @@ class Aligner:
         together with frame or strand): protein queries against nucleotide references, the references translated the same way;
         PairHits.frame is then the reference's frame.  frameshift (a penalty >= 0; with strand, not together with frame or
         ref_frame): nucleotide queries against proteins by the three-frame DP of align_pairs(frameshift=); PairHits.strand tells the
-        strand, end_query is in nucleotides."""
+        strand, end_query is in nucleotides; align_pairs_frameshift_cigar(Q, R, hits.pairs, frameshift, strand=hits.strand) gives the
+        hits' alignments."""
         if not self._profile.is_null():
             raise BatchError("search_pairs takes no profile")
         cfg = self._config()
@@ -1148,7 +1193,8 @@ class Aligner:
         chunk_pairs and slice_rows never change the result.  strand as in search_pairs: with "both" a reference is one
         candidate with its better strand, and TopKHits.strand tells which.  frame as in search_pairs: a reference is one candidate
         with its best frame, and TopKHits.frame tells which.  ref_frame as in search_pairs: the references are the translated side.
-        frameshift as in search_pairs: a reference is one candidate with its better strand under the three-frame DP."""
+        frameshift as in search_pairs: a reference is one candidate with its better strand under the three-frame DP, and
+        align_pairs_frameshift_cigar takes TopKHits.pairs and TopKHits.strand as they are."""
         if not self._profile.is_null():
             raise BatchError("search_topk takes no profile")
         cfg = self._config()
@@ -1880,6 +1926,21 @@ def align_pairs_frameshift_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, 
     rc = lib.pmx_align_pairs_frameshift_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, int(strand_mode), int(frameshift),
                                                code.ctypes.data if code is not None else None, max_qlen, max_rlen, d_out, d_strand_out,
                                                stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_frameshift_cigar_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, max_qlen, max_rlen, d_out, d_strand_out,
+                                        d_stats, d_beg, d_cigar_text, cigar_capacity, d_cigar_off, stream=0, chunk_pairs=0, code=None):
+    """align_pairs_frameshift_device with the traceback behind it (cfg.want: WANT_CIGAR, with WANT_STATS iff d_stats): the same records
+    and strand bytes, the CIGAR text with the frameshift ops '/' and '\\' at d_cigar_off[k] of d_cigar_text (align_pairs_ex_device's
+    buffer rules), begins in d_beg (2 n int32, optional), the paths' statistics in d_stats."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_align_pairs_frameshift_cigar_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, int(strand_mode),
+                                                     int(frameshift), code.ctypes.data if code is not None else None, max_qlen, max_rlen,
+                                                     d_out, d_strand_out, d_stats, d_beg, d_cigar_text, int(cigar_capacity), d_cigar_off,
+                                                     stream, C.byref(opts))
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

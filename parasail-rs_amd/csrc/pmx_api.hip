@@ -4092,7 +4092,8 @@ extern "C" int32_t pmx_frameshift_max_window(void) { return PMX_FRAMESHIFT_MAX_W
 
 // What every _frameshift entry refuses about its strand mode, penalty, matrix, mode, width and outputs, before any GPU work.  *fr: the
 // run's strands (d_strand: a strand byte per pair, listed pairs only), code and penalty.
-static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint8_t *d_strand, int32_t frameshift, const uint8_t *code, FrameRun *fr)
+static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint8_t *d_strand, int32_t frameshift, const uint8_t *code, FrameRun *fr,
+                            bool traceback = false /* the _frameshift_cigar entries: the outputs are theirs to check */)
 {
     if (strand_mode < PMX_STRAND_FORWARD || strand_mode > PMX_STRAND_BOTH) {
         set_err("strand mode %d is outside 0 .. 2 (PMX_STRAND_FORWARD, PMX_STRAND_REVERSE, PMX_STRAND_BOTH)", strand_mode); return -1;
@@ -4102,8 +4103,8 @@ static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint
     if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("the frameshift entries take no PSSM matrix: a profile belongs to one protein query"); return -1; }
     if (cfg->mode != PMX_MODE_SW) { set_err("the frameshift entries align locally: mode %d is not PMX_MODE_SW", cfg->mode); return -1; }
     if (cfg->width != 0 && cfg->width != 32) { set_err("the frameshift entries compute in 32 bits: width %d is neither 0 nor 32", cfg->width); return -1; }
-    if (cfg->want & PMX_WANT_STATS) { set_err("the frameshift entries have no statistics (PMX_WANT_STATS)"); return -1; }
-    if (cfg->want & PMX_WANT_CIGAR) { set_err("the frameshift entries have no CIGAR output (PMX_WANT_CIGAR): there is no traceback with frameshift operators"); return -1; }
+    if (!traceback && (cfg->want & PMX_WANT_STATS)) { set_err("the frameshift entries have no statistics (PMX_WANT_STATS)"); return -1; }
+    if (!traceback && (cfg->want & PMX_WANT_CIGAR)) { set_err("the frameshift entries have no CIGAR output (PMX_WANT_CIGAR): there is no traceback with frameshift operators"); return -1; }
     if (cfg->matrix->size > pmx_swfs_max_msize()) {
         set_err("the frameshift kernel keeps the matrix in LDS: %d symbols exceed %d", cfg->matrix->size, pmx_swfs_max_msize()); return -1;
     }
@@ -4182,6 +4183,112 @@ extern "C" int pmx_align_pairs_frameshift_device(const pmx_config_t *cfg, const 
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     return pairs_run_codons(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, (hipStream_t)stream,
                             pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
+}
+
+// ---- frameshift traceback: the trace form of pmx_swfs, the walk of pmx_walkfs.hip, the device text rendering ----
+// What the _frameshift_cigar entries refuse about their outputs, before any GPU work.  text: d_cigar_text / cigar_buf.
+static int frameshift_cigar_outputs_check(const pmx_config_t *cfg, const void *stats, const void *text, int64_t capacity, const void *text_off)
+{
+    if (!(cfg->want & PMX_WANT_CIGAR)) { set_err("the frameshift traceback entries write CIGAR text: cfg->want must hold PMX_WANT_CIGAR"); return -1; }
+    if ((cfg->want & PMX_WANT_STATS) && !stats) { set_err("stats requested without a stats buffer"); return -1; }
+    if (!(cfg->want & PMX_WANT_STATS) && stats) { set_err("stats buffer without PMX_WANT_STATS"); return -1; }
+    if (!text || !text_off) { set_err("null cigar output"); return -1; }
+    if (capacity < 0) { set_err("negative cigar_capacity"); return -1; }
+    return 0;
+}
+// The bound on a chunk's trace scratch: 256 MiB, or what the value switch PMX_CIGAR_CHUNK_BYTES says.  One workgroup of the sweep is
+// four slots: a call whose four slots exceed the bound is refused.
+static double frameshift_trace_bound()
+{
+    const char *forced = pmx_env("PMX_CIGAR_CHUNK_BYTES");
+    return forced ? atof(forced) : PMX_PAIRS_CHUNK_BYTES;
+}
+static int frameshift_trace_bound_check(int32_t max_qlen, int32_t max_rlen)
+{
+    const double four = 4.0 * (double)pmx_swfs_trace_bytes_per_slot(max_qlen, max_rlen), bound = frameshift_trace_bound();
+    if (four > bound) {
+        set_err("four slots of frameshift trace, %.0f bytes at max_qlen %d and max_rlen %d, exceed the bound of %.0f bytes on a chunk's trace "
+                "scratch (256 MiB, or PMX_CIGAR_CHUNK_BYTES)", four, (int)max_qlen, (int)max_rlen, bound);
+        return -1;
+    }
+    return 0;
+}
+
+// The traceback road of a frameshift batch over listed pairs.  A chunk's per * cn slots run in parts that keep the trace under the
+// bound, whole workgroups of four slots: the trace sweep of a part, the strand fold into the caller's arrays (it writes the bad pairs'
+// records too), the walk over the winners' traces -- so both slots of a pair keep their trace until the walk -- and the render, all on
+// `st`: a part's scratch is free when the next part begins.  The text continues behind the parts and chunks before it
+// (d_text_off[c0 + p0], left by the part before on the same stream), so neither chunk_pairs nor the bound changes a byte.
+// Scratch: the trace in SCR_TRACE, the op slots in SCR_OPS and the walk's counts in SCR_CIG, which no other road of this call uses.
+static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
+                                  int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats,
+                                  int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off,
+                                  hipStream_t st, int64_t chunk, const FrameRun &fr)
+{
+    DevMat dm;
+    if (get_devmat(cfg->matrix, &dm)) return -1;
+    const int per = fr.per;
+    const size_t tps = pmx_swfs_trace_bytes_per_slot(max_qlen, max_rlen);
+    const bool strips = max_qlen > pmx_swfs_strip_rows();
+    int64_t part_slots = (int64_t)(frameshift_trace_bound() / (double)tps) / 4 * 4;           // (at least four: the caller has checked)
+    part_slots = std::min<int64_t>(part_slots, ((int64_t)per * chunk + 3) / 4 * 4);
+    const int64_t part = part_slots / per;
+    void *trace = nullptr, *bnd = nullptr;
+    pmx_record_t *srec = nullptr; int64_t *local_off = nullptr, *pair_qoff = nullptr, *pair_roff = nullptr;
+    SlotText t;
+    // a path has at most N + m ops (matches + reference gaps <= m, 2 matches + 3 codon gaps <= N + 2, frameshift ops <= matches - 1), so
+    // the implicit op slot of N + m + 1 entries that pmx_launch_cigar_render_slots assumes per alignment slot holds it
+    if (scratch_reserve(tps * (size_t)part_slots, &trace, SCR_TRACE) ||
+        (strips && scratch_reserve(pmx_swfs_bound_bytes_per_slot(max_rlen) * (size_t)part_slots, &bnd, SCR_SWFS)) ||
+        t.reserve_ops((size_t)part_slots * ((size_t)max_qlen + (size_t)max_rlen + 1)) ||
+        scratch_carve(SCR_PSRCH, [&](Carver &c) { srec = c.take<pmx_record_t>((size_t)per * (size_t)chunk); }) ||
+        scratch_carve(SCR_CIG, [&](Carver &c) {
+            t.carve(c, part);
+            local_off = c.take<int64_t>((size_t)part + 1); pair_qoff = c.take<int64_t>((size_t)part + 1); pair_roff = c.take<int64_t>((size_t)part + 1);
+        })) return -1;
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            for (int64_t p0 = 0; p0 < cn; p0 += part) {
+                const int64_t pn = std::min<int64_t>(part, cn - p0), s0 = per * p0, g0 = c0 + p0;
+                const PmxBatch pb = {b.q, b.qoff + s0, b.r, b.roff + s0, per * pn, max_qlen, max_rlen, 0, nullptr, nullptr, nullptr, 0, 0};
+                int rc = pmx_launch_swfs_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, trace, srec + s0, st, &g_last_kernel);
+                if (rc) { set_err(rc < 0 ? "frameshift trace kernel launch failed: %s" : "the frameshift trace kernel does not take this batch%s", rc < 0 ? hipGetErrorString((hipError_t)(-rc)) : ""); return -1; }
+                uint8_t *won = d_strand_out ? d_strand_out + g0 : nullptr;
+                rc = pmx_launch_pairs_fold_strands(srec + s0, nullptr, b.ok + s0, b.sflag + s0, pn, per, 0, d_out + g0, nullptr, won, nullptr, st);
+                if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
+                rc = pmx_launch_walkfs(dm.d, pn, per, per == 2 ? won : nullptr, b.q, b.qoff + s0, b.r, b.roff + s0, max_rlen, d_out + g0,
+                                       (const uint8_t *)trace, (long long)tps, t.ops, t.nops, t.textlen, pair_qoff, pair_roff,
+                                       d_beg ? d_beg + 2 * g0 : nullptr, d_stats ? d_stats + g0 : nullptr, st);
+                if (rc) { set_err("frameshift walk launch failed (%d)", rc); return rc < 0 ? rc : -1; }
+                rc = t.render(pair_qoff, pair_roff, 0, pn, d_text, capacity, d_text_off + g0, st, g0 > 0 ? local_off : nullptr);
+                if (rc) return rc;
+            }
+            return 0;
+        }, PMX_STRAND_FORWARD, &fr);
+}
+
+extern "C" int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                       int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                       int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                       pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats, int32_t *d_beg,
+                                                       char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off,
+                                                       void *stream, const pmx_pairs_opts_t *opts)
+{
+    FrameRun fr;
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, true) ||
+        frameshift_cigar_outputs_check(cfg, d_stats, d_cigar_text, cigar_capacity, d_cigar_off)) return -1;
+    if (n > 0 && fr.per > 1 && !d_strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    if (n == 0) return 0;
+    if (frameshift_rows_check(max_qlen) || frameshift_trace_bound_check(max_qlen, max_rlen) ||
+        pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats != nullptr, true)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run_codons_cigar(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, d_stats, d_beg, d_cigar_text, cigar_capacity,
+                                  d_cigar_off, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
 }
 
 extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
@@ -4673,20 +4780,25 @@ static int short_window_check(const pmx_seqset *Q, const pmx_pair_t *pairs, int6
     return 0;
 }
 
-// pmx_align_pairs_frameshift: the host entry over listed pairs of the frameshift-aware alignment, laid out as
-// align_pairs_frames_host.  A window shorter than three nucleotides is found on the device only, so the records' flags are always scanned.
-extern "C" int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
-                                          int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
-                                          int32_t frameshift, const uint8_t *code,
-                                          pmx_record_t *out, uint8_t *strand_out, const pmx_pairs_opts_t *opts)
+// The host entries over listed pairs of the frameshift-aware alignment, laid out as align_pairs_frames_host.  A window shorter than three
+// nucleotides is found on the device only, so the records' flags are always scanned.  traceback (pmx_align_pairs_frameshift_cigar, DESIGN
+// 2.5l): the traceback road in place of the score road, and the text tail of pairs_host -- a text buffer sized by estimate, and one more
+// run at the exact size where the text did not fit.
+static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                       int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                       int32_t frameshift, const uint8_t *code, pmx_record_t *out, uint8_t *strand_out,
+                                       const pmx_pairs_opts_t *opts, bool traceback,
+                                       pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off)
 {
     FrameRun fr;
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
     if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr)) return -1;
+    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr, traceback) ||
+        (traceback && frameshift_cigar_outputs_check(cfg, stats_out, cigar_buf, 0, cigar_off))) return -1;
     if (n > 0 && fr.per > 1 && !strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    if (traceback) { *cigar_buf = nullptr; cigar_off[0] = 0; }
     if (n == 0) return 0;
     if (strand)
         for (int64_t k = 0; k < n; ++k)
@@ -4699,13 +4811,16 @@ extern "C" int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seq
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
         mq = fr.letters((int32_t)s.mq); mr = s.mr;
     }
-    if (frameshift_rows_check((int32_t)mq) || pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, false)) return -1;
+    if (frameshift_rows_check((int32_t)mq) || (traceback && host_offsets && frameshift_trace_bound_check((int32_t)mq, (int32_t)mr)) ||
+        pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr, traceback)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
-    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr;
+    const bool stats = traceback && (cfg->want & PMX_WANT_STATS) != 0;
+    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
     const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the strand bytes in, then out
-    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC)) return -1;
+    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
+        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
     uint8_t *dsin = (uint8_t *)dp + up_bytes, *dsout = dsin + n;
     HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
     if (strand) { HIP_OR_RET(hipMemcpyAsync(dsin, strand, (size_t)n, hipMemcpyHostToDevice, st)); fr.d_frame = dsin; }
@@ -4713,12 +4828,60 @@ extern "C" int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seq
     if (!host_offsets) {
         if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
         q32 = fr.letters(q32);
-        if (frameshift_rows_check(q32)) return -1;
+        if (frameshift_rows_check(q32) || (traceback && frameshift_trace_bound_check(q32, r32))) return -1;
     }
-    const int rc = pairs_run_codons(cfg, Q, R, n, dp, q32, r32, drec, dsout, st, pairs_chunk(n, q32, r32, opts, fr.per), fr);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    const int64_t chunk = pairs_chunk(n, q32, r32, opts, fr.per);
+    if (!traceback) {
+        const int rc = pairs_run_codons(cfg, Q, R, n, dp, q32, r32, drec, dsout, st, chunk, fr);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        if (strand_out) HIP_OR_RET(hipMemcpyAsync(strand_out, dsout, (size_t)n, hipMemcpyDeviceToHost, st));
+        return pairs_copy_back(n, drec, nullptr, out, nullptr, true, st);
+    }
+    int64_t capacity = 32 * n + 256;                      // (the run-length text of a hit is a few runs; a batch of noise runs twice)
+    DevBuf<int64_t> dtoff; DevBuf<int32_t> dbeg; DevBuf<char> dtext;
+    if (dtoff.try_alloc((size_t)n + 1) || (beg && dbeg.try_alloc(2 * (size_t)n)) || dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    for (int pass = 0; pass < 2; ++pass) {
+        const int rc = pairs_run_codons_cigar(cfg, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_OR_RET(hipMemcpyAsync(cigar_off, dtoff.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipStreamSynchronize(st));
+        if (cigar_off[n] <= capacity) break;
+        capacity = cigar_off[n];                          // the text did not fit the estimate -- again with the exact size
+        (void)hipFree(dtext.p); dtext.p = nullptr;
+        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+    }
     if (strand_out) HIP_OR_RET(hipMemcpyAsync(strand_out, dsout, (size_t)n, hipMemcpyDeviceToHost, st));
-    return pairs_copy_back(n, drec, nullptr, out, nullptr, true, st);
+    const int rc = pairs_copy_back(n, drec, dst, out, stats_out, true, st);
+    if (rc) return rc;
+    if (beg) HIP_OR_RET(hipMemcpy(beg, dbeg.p, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+    TextBuf text;
+    char *dst_text = text.grow((size_t)cigar_off[n]);
+    if (!dst_text) { set_err("out of memory"); return -1; }
+    if (cigar_off[n]) {
+        const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
+    }
+    text.len = (size_t)cigar_off[n];
+    return publish_text(text, cigar_buf);
+}
+
+extern "C" int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                          int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                          int32_t frameshift, const uint8_t *code,
+                                          pmx_record_t *out, uint8_t *strand_out, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, false,
+                                       nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int pmx_align_pairs_frameshift_cigar(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                                int32_t frameshift, const uint8_t *code,
+                                                pmx_record_t *out, uint8_t *strand_out, pmx_stats_t *stats_out, int32_t *beg,
+                                                char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, true,
+                                       stats_out, beg, cigar_buf, cigar_off);
 }
 
 extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,

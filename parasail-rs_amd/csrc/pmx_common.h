@@ -345,6 +345,26 @@ int pmx_swfs_strip_rows();
 size_t pmx_swfs_bound_bytes_per_slot(int max_rlen);
 int pmx_launch_swfs(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
                     pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
+// The trace form of the sweep and its walk (semantics: include/parasail_amd.h, "Frameshift traceback").  A cell's decision
+// byte: bits 0 .. 2 where H came from (START .. LONG: from M, and which term D was), bit 3 E was opened, bit 4 F was opened.  The byte of
+// row i, column j of a slot: ((i / STRIP_ROWS * max_rlen + j) * COL_BYTES) + i % STRIP_ROWS / LANE_ROWS * 12 + i % LANE_ROWS.
+enum { PMX_FSTR_START = 0, PMX_FSTR_INFRAME = 1, PMX_FSTR_SHORT = 2, PMX_FSTR_LONG = 3, PMX_FSTR_F = 4, PMX_FSTR_E = 5, PMX_FSTR_ZERO = 6,
+       PMX_FSTR_EO = 8, PMX_FSTR_FO = 16,
+       PMX_FSTR_LANE_ROWS = 10, PMX_FSTR_STRIP_ROWS = 160, PMX_FSTR_COL_BYTES = 192 };
+size_t pmx_swfs_trace_bytes_per_slot(int max_rows, int max_rlen);
+// One launch over b.n slots; trace (and bnd, when b.max_qlen exceeds one strip) hold the bytes of b.n slots rounded up to a multiple of four.
+int pmx_launch_swfs_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
+                          pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
+// The walk over that trace (pmx_walkfs.hip), one lane per logical pair k of n: its record recs[k] (a bad pair's is flagged), its slot
+// per * k + (win ? win[k] : 0) of the sweep's launch; qoff / roff are the launch's, per * n + 1 entries.  ops: run-length ops
+// (len << 4 | op; '/' = 9, '\\' = 10) from the end of the PAIR's op slots backwards -- a pair owns the qlen + rlen + 1 entries of each of
+// its slots -- with nops and textlen; pair_qoff / pair_roff [n + 1]: the offsets with which pmx_launch_cigar_render_slots (ops_base 0)
+// finds the pairs' op slots; beg (2 n) and stats_out are optional.
+int pmx_launch_walkfs(const PmxDevMatrix &m, long long n, int per, const uint8_t *win,
+                      const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, int max_rlen,
+                      const pmx_record_t *recs, const uint8_t *trace, long long trace_bytes_per_slot,
+                      uint32_t *ops, int32_t *nops, int32_t *textlen, int64_t *pair_qoff, int64_t *pair_roff,
+                      int32_t *beg, pmx_stats_t *stats_out, hipStream_t stream);
 // Per-query top-K (pmx_topk.hip; semantics: include/parasail_amd.h).  ks = min(k, |R|).  The running state of local row
 // li: st_keys / st_recs / st_stats[li * ks ..) hold st_held[li] entries in (score descending, j ascending) order, st_passing[li] = |P_i|
 // so far; the caller zeroes st_held (nq + 1 entries, the scan's input) and st_passing before the first chunk.  geometry: what the tile

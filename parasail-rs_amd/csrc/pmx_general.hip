@@ -864,7 +864,7 @@ int pmx_launch_collect_saturated(const pmx_record_t *rec, long long n, int64_t *
 }
 
 // CIGAR text on the device: pass 1 measures each pair's text, pass 2 writes it at the caller's offsets
-// ("<len><op>" per run, ops = BAM codes, "MIDNSHP=X").
+// ("<len><op>" per run, ops = BAM codes, "MIDNSHP=X", then 9 = '/' and 10 = '\\', the frameshift ops of pmx_walkfs.hip).
 __device__ __forceinline__ int pmx_digits(uint32_t v) { int d = 1; while (v >= 10) { v /= 10; ++d; } return d; }
 __global__ void pmx_cigar_textlen_kernel(const uint32_t *ops, const int64_t *ops_off, const int32_t *nops, int32_t *textlen, long long n)
 {
@@ -879,7 +879,7 @@ __global__ void pmx_cigar_textlen_kernel(const uint32_t *ops, const int64_t *ops
 __global__ void pmx_cigar_render_kernel(const uint32_t *ops, const int64_t *ops_off, const int32_t *nops,
                                         const int64_t *text_off, char *text, long long n, int swap)
 {
-    const char *letters = swap ? "MDINSHP=X" : "MIDNSHP=X";
+    const char *letters = swap ? "MDINSHP=X/\\" : "MIDNSHP=X/\\";
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const uint32_t *src = ops + ops_off[k];
@@ -918,7 +918,7 @@ int pmx_launch_cigar_render(const uint32_t *ops, const int64_t *ops_off, const i
 __global__ void pmx_cigar_render_slots_kernel(const uint32_t *ops, const int64_t *qoff, const int64_t *roff, long long ops_base,
                                               const int32_t *nops, const int64_t *text_off, char *text, long long capacity, long long n, int swap)
 {
-    const char *letters = swap ? "MDINSHP=X" : "MIDNSHP=X";
+    const char *letters = swap ? "MDINSHP=X/\\" : "MIDNSHP=X/\\";
     const long long k = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
     const int l = threadIdx.x & 7;
     if (k >= n) return;

@@ -28,7 +28,12 @@
 
 #define PMX_SWFS_NEG (-(1 << 29))
 
-template <int G, int R>
+// The trace form (TR; semantics: include/parasail_amd.h, "Frameshift traceback") stores one decision byte per cell
+// beside the same sweep: bits 0 .. 2 say where H came from -- PMX_FSTR_START / _INFRAME / _SHORT / _LONG: from M, and which term D was;
+// PMX_FSTR_F, PMX_FSTR_E; PMX_FSTR_ZERO -- bit 3 that E of the cell was opened, bit 4 that F was (pmx_common.h).  Layout, per slot of
+// the launch: column-major, 12 bytes per lane and column -- the lane's R = 10 rows and two bytes of padding, three dword stores --
+// so row i of column j is byte ((i / (G R) * max_rlen + j) * G + i % (G R) / R) * 12 + i % R of the slot's region.
+template <int G, int R, bool TR>
 __global__ __launch_bounds__(64)
 void pmx_swfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff,
                      const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff,
@@ -36,8 +41,10 @@ void pmx_swfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
                      const int16_t *__restrict__ gmat, const uint8_t *__restrict__ gmap, int msize,
                      int open, int ext, int fs,
                      int4 *bnd /* per slot of the launch: 2 buffers x max_rlen columns x 2 int4 */,
-                     pmx_record_t *__restrict__ out)
+                     pmx_record_t *__restrict__ out,
+                     uint32_t *__restrict__ trace /* TR: per slot of the launch, trace_stride dwords; else unused */, long long trace_stride)
 {
+    static_assert(!TR || R == 10, "the trace's 12 bytes per lane and column hold ten rows");
     static_assert(R >= 4, "the rows a cell reaches lie in its own lane or the lane above");
     static_assert(G == 16 || G == 64, "group_shift_up without a select");
     constexpr int NPW = 64 / G;                 // slots per wave = per workgroup
@@ -60,6 +67,7 @@ void pmx_swfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     N = min(N, max_rows); m = min(m, max_rlen);                    // (resolve keeps both inside; scratch and loops rely on it)
     const uint8_t *qs = qbuf + qb, *ref = rbuf + rb;
     int4 *bslot = bnd ? bnd + ((size_t)blockIdx.x * NPW + slotw) * 4 * (size_t)max_rlen : nullptr;
+    uint32_t *tslot = TR ? trace + ((size_t)blockIdx.x * NPW + slotw) * (size_t)trace_stride : nullptr;
 
     int wN = N, wm = m;                                            // the wave's longest window and reference: uniform trip counts
 #pragma unroll
@@ -99,6 +107,7 @@ void pmx_swfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
                 const int16_t *mrow = matT + (int)map[ref[col]] * msize;
                 int Hc[R], Fc[R];
                 int cm = 0;                                        // the column's maximum over the rows of the stream (H >= 0)
+                uint32_t tw[3] = {0u, 0u, 0u};                     // TR: the lane's ten decision bytes of this column
 #pragma unroll
                 for (int k = 0; k < R; ++k) {
                     // column j - 1, rows i - 2, i - 3, i - 4: d4[0 .. 3] are rows -4 .. -1 of this lane, Hp[] rows 0 ..
@@ -113,8 +122,19 @@ void pmx_swfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
                     const int f3 = k >= 3 ? Fc[k - 3] : uF[k];
                     const int f = max(h3 - open, f3 - ext);
                     const int h = max(max(0, M), max(e, f));
+                    if (TR) {                                      // the compares of the contract, on the values at hand
+                        const uint32_t ds = D == 0 ? PMX_FSTR_START : hm3 == D ? PMX_FSTR_INFRAME : hm2 - fs == D ? PMX_FSTR_SHORT : PMX_FSTR_LONG;
+                        uint32_t c = (M >= e && M >= f) ? ds : f >= e ? PMX_FSTR_F : PMX_FSTR_E;
+                        c = h <= 0 ? PMX_FSTR_ZERO : c;
+                        c |= (Hp[k] - open > E[k] - ext ? PMX_FSTR_EO : 0u) | (h3 - open > f3 - ext ? PMX_FSTR_FO : 0u);
+                        tw[k / 4] |= c << (8 * (k % 4));
+                    }
                     Hc[k] = h; Fc[k] = f; E[k] = e;
                     cm = max(cm, h & vm[k]);
+                }
+                if (TR) {
+                    uint32_t *tc = tslot + (((size_t)s * max_rlen + col) * G + g) * 3;
+                    tc[0] = tw[0]; tc[1] = tw[1]; tc[2] = tw[2];
                 }
                 // a new best is rare: one branch per column.  Columns ascend within a strip, so an equal score wins only from a
                 // later strip at a smaller column; within the column the first row that holds the maximum.
@@ -173,12 +193,42 @@ int pmx_launch_swfs(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
     const long long part = strips ? bnd_slots / NPW * NPW : b.n;
     for (long long p0 = 0; p0 < b.n; p0 += part) {
         const long long pn = b.n - p0 < part ? b.n - p0 : part;
-        hipLaunchKernelGGL((pmx_swfs_kernel<G, R>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfs_lds_bytes(m.msize), stream,
+        hipLaunchKernelGGL((pmx_swfs_kernel<G, R, false>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfs_lds_bytes(m.msize), stream,
                            b.qbuf, b.qoff + p0, b.rbuf, b.roff + p0, pn, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
-                           open, ext, fs, strips ? (int4 *)bnd : nullptr, d_out + p0);
+                           open, ext, fs, strips ? (int4 *)bnd : nullptr, d_out + p0, (uint32_t *)nullptr, 0LL);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return -(int)e;
     }
     if (kernel_name) *kernel_name = strips ? "pmx_swfs_kernel<16,10>/strips" : "pmx_swfs_kernel<16,10>";
+    return 0;
+}
+
+// The trace form over n slots: the same sweep and records, and every cell's decision byte into `trace`, which holds
+// pmx_swfs_trace_bytes_per_slot bytes for each of the launch's slots ROUNDED UP TO WHOLE WORKGROUPS of four (the idle slots of the
+// last workgroup repeat slot n - 1 into their own regions).  bnd: boundary scratch for as many slots when max_rows exceeds one strip.
+// One launch: the caller cuts a chunk into parts that fit its scratch.  0 launched, 1 not eligible, <0 HIP error.
+size_t pmx_swfs_trace_bytes_per_slot(int max_rows, int max_rlen)
+{
+    const int strips = (max_rows + pmx_swfs_strip_rows() - 1) / pmx_swfs_strip_rows();
+    return (size_t)strips * (size_t)max_rlen * PMX_FSTR_COL_BYTES;
+}
+int pmx_launch_swfs_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
+                          pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
+{
+    constexpr int G = 16, R = 10, NPW = 64 / G;
+    static_assert(PMX_FSTR_COL_BYTES == G * 12 && PMX_FSTR_LANE_ROWS == R && PMX_FSTR_STRIP_ROWS == G * R, "the walk's addressing (pmx_walkfs.hip)");
+    if (m.pssm || m.msize > pmx_swfs_max_msize() || b.q_shared || !trace) return 1;
+    if (b.n <= 0) return 0;
+    const int cap = 1 << 28;
+    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
+    const bool strips = b.max_qlen > G * R;
+    if (strips && !bnd) return 1;
+    hipLaunchKernelGGL((pmx_swfs_kernel<G, R, true>), dim3((unsigned)((b.n + NPW - 1) / NPW)), dim3(64), swfs_lds_bytes(m.msize), stream,
+                       b.qbuf, b.qoff, b.rbuf, b.roff, b.n, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
+                       open, ext, fs, strips ? (int4 *)bnd : nullptr, d_out,
+                       (uint32_t *)trace, (long long)(pmx_swfs_trace_bytes_per_slot(b.max_qlen, b.max_rlen) / 4));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return -(int)e;
+    if (kernel_name) *kernel_name = strips ? "pmx_swfs_kernel<16,10,trace>/strips" : "pmx_swfs_kernel<16,10,trace>";
     return 0;
 }

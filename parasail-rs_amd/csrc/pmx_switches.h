@@ -48,7 +48,7 @@ struct PmxSwitchDoc { const char *name, *kind, *what; };
     X("PMX_TRACE16_GEN1",             "force", "traceback: first-generation packed kernel and one-lane walk") \
     X("PMX_TRACE_NO_BFI",             "force", "traceback: three-instruction decision merge instead of the bounded-difference v_bfi merge") \
     X("PMX_TRACE_FETCH",              "force", "traceback <16,16>: fetch references from HBM instead of staging them") \
-    X("PMX_CIGAR_CHUNK_BYTES",        "value", "batch CIGAR and banded traceback: bytes of trace scratch per chunk (tests force several chunks)") \
+    X("PMX_CIGAR_CHUNK_BYTES",        "value", "batch CIGAR and banded traceback: bytes of trace scratch per chunk (tests force several chunks); frameshift traceback: the bound on a chunk's trace scratch, default 256 MiB (tests force several parts)") \
     X("PMX_CIGAR_NO_OVERLAP",         "force", "batch CIGAR: sweep and walk back to back on one stream (no double buffering)") \
     X("PMX_NO_FAST_BANDED",           "force", "banded: general kernel with a band mask instead of the band-only kernel") \
     X("PMX_BANDED_NO_STRIP",          "force", "banded, alphabets of <= 4 letters: the anti-diagonal kernels of pmx_banded.hip instead of the band-strip kernel (C offsets per lane)") \
