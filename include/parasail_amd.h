@@ -1064,6 +1064,111 @@ int pmx_search_topk_translated_ref_device(const pmx_config_t *cfg, const pmx_seq
 int pmx_search_topk_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
                                    const pmx_topk_opts_t *opts, int frame_mode, const uint8_t *code, pmx_topk_frame_hits_t **result);
 
+/* Frameshift-aware translated search, reference side (extension): protein queries against a set of nucleotide sequences -- genes,
+ * transcripts, contigs -- aligned by the three-frame local DP, so that one alignment may change its reading frame: tblastn with
+ * frameshifts.  The reference-side translated entries above align every frame on its own, and one inserted or deleted base in a
+ * contig cuts a hit in two.  Exchanging the sets and calling the query-side frameshift entries transposes the records, turns the
+ * per-query top-K into "best proteins per contig" and bounds the nucleotide side by PMX_FRAMESHIFT_MAX_WINDOW.  Here the nucleotide
+ * reference is streamed one letter per step AT ANY LENGTH and the protein sits on the rows.
+ *
+ * Q holds proteins and R holds nucleotides.  The genetic code, the base classes and the `code` argument are those of the translated
+ * entries.
+ *
+ * The codon stream.  A REFERENCE window of W nucleotides is read as stored (strand 0) or reverse-complemented (strand 1) exactly as
+ * frames 3 .. 5 of the reference-side translated entries read it (pmx_complement_table, from the window's end downwards): the
+ * oriented window.  Its codon stream T has N = W - 2 letters; T[j] is the translation of oriented bytes j, j + 1, j + 2.  Columns
+ * j = f, f + 3, f + 6, .. of T are exactly frame f (strand 0) or frame 3 + f (strand 1) of the reference-side translated entries.  A
+ * window with W < 3 has no stream: the pair gets the bad record {0, -1, -1, PMX_FLAG_BAD_PAIR} and strand 0.
+ *
+ * The recurrence.  Local alignment only.  Rows i = 0 .. m - 1 of the query protein q, columns j = 0 .. N - 1 of T, s the matrix
+ * score INDEXED (QUERY LETTER, REFERENCE LETTER), open and extend the call's gap penalties, fs = frameshift >= 0:
+ *     D(i,j) = max(0, H(i-1,j-3), H(i-1,j-2) - fs, H(i-1,j-4) - fs)
+ *     M(i,j) = D(i,j) + s(q[i], T[j])
+ *     E(i,j) = max(H(i,j-3) - open, E(i,j-3) - extend)          a whole reference codon against a gap
+ *     F(i,j) = max(H(i-1,j) - open, F(i-1,j) - extend)          a query letter against a gap
+ *     H(i,j) = max(0, M, E, F)
+ * A term with a negative index does not exist: for H it counts as 0, for E and F as minus infinity.  The j - 2 predecessor is a path
+ * that found one nucleotide missing from the reference, the j - 4 predecessor one nucleotide too many; gaps keep their frame.
+ * Two identities follow.  (1) The recurrence is the transpose of the query-side one: the score equals the query-side score of the
+ * same stream with the roles exchanged and the matrix transposed; only the end cell may differ, by the tie rule.  (2) With the two
+ * frameshift terms taken out, the score is the best plain local score over T[0::3], T[1::3] and T[2::3]: the PMX_FRAMES_FORWARD
+ * (strand 1: PMX_FRAMES_REVERSE) fold of the reference-side translated entries, which a large `frameshift` therefore returns.
+ *
+ * The record.  score = the maximum H; end_query = its i, in letters; end_ref = its j + 2, THE LAST NUCLEOTIDE OF THE LAST CODON,
+ * 0-BASED INCLUSIVE, IN THE ORIENTED REFERENCE WINDOW -- IN NUCLEOTIDES.  Back to stored bytes: oriented byte x of a strand-0 window
+ * is sequence byte r_beg + x, of a strand-1 window sequence byte r_beg + W - 1 - x (complemented).  Ties: the first maximum in
+ * column-major order, that is the smallest end_ref, then the smallest end_query; a zero maximum therefore ends at end_query 0,
+ * end_ref 2.  flags = 0.
+ *
+ * Strand modes.  PMX_STRAND_FORWARD, PMX_STRAND_REVERSE and PMX_STRAND_BOTH behave as for the stranded and the query-side frameshift
+ * entries, but THE STRAND IS THE REFERENCE'S: one or two alignment slots per pair, the better strand kept BEFORE the threshold and
+ * the top-K cut (only the score is compared, a tie goes to the forward strand), the strand byte beside each record or hit.  The
+ * listed-pairs entry also takes one strand byte per pair (the strand mode must then be PMX_STRAND_FORWARD; a byte above 1 makes the
+ * pair bad).  chunk_pairs, slice_pairs and slice_rows never change a byte; outputs are bit-identical from run to run.
+ *
+ * Limits.  cfg->mode PMX_MODE_SW; cfg->width 0 or 32, both exact: the kernel computes in 32 bits, and open, extend and frameshift
+ * above 2^28 are read as 2^28.  Query windows of up to PMX_FRAMESHIFT_REF_MAX_QUERY letters: 4 096 x 32 767 < 2^28, so nothing wraps
+ * however long the reference is.  REFERENCE WINDOWS HAVE NO CAP OF THEIR OWN: max_rlen of the device entries bounds N = W - 2, the
+ * columns the kernel sees, and a window whose N exceeds it makes the pair bad; max_qlen bounds the query window as in the untranslated
+ * entries.  The host entries size both from the longest windows.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: any other mode or width; PMX_WANT_STATS and PMX_WANT_CIGAR (this
+ * side has no traceback yet; the hit list is the interface for the pass that will have); a PSSM matrix; a matrix of more than 128
+ * symbols; frameshift < 0; a strand mode outside 0 .. 2; strand bytes per pair together with a strand mode other than
+ * PMX_STRAND_FORWARD; max_qlen above PMX_FRAMESHIFT_REF_MAX_QUERY; a device search with PMX_STRAND_BOTH, capacity > 0 and no strand
+ * output; everything the corresponding stranded or untranslated entry refuses, with the same texts.  n == 0 / nq == 0 behave as
+ * there.  The device entries give bad pairs their record and strand 0; the host entries name the first pair that is bad or has no
+ * stream.
+ *
+ * Scratch.  The chunk buffers of the stranded entries with m + N bytes per slot (two slots per pair in PMX_STRAND_BOTH), 16 bytes of
+ * slot record per slot and, for queries of more than pmx_swfsc_strip_rows() letters, 16 bytes per reference column and slot for the
+ * strips' boundary rows, at most 256 MiB of them (the kernel then runs over a chunk's slots in parts).  pmx_last_kernel() names the
+ * instantiation of the last chunk's alignment, with "/strips" for queries beyond one strip.
+ *
+ * The argument lists are those of the query-side frameshift entries; d_strand / strand_mode / d_strand_out / d_hit_strand speak of
+ * the reference's strand; the result blocks pmx_strand_hits_t and pmx_topk_strand_hits_t and their free functions are reused.  Hit
+ * descriptors plus strand bytes are valid input to the listed entry and to the gather hook.
+ * pmx_gather_pairs_codons_ref_device: pmx_gather_pairs_codons_device with the sides exchanged -- d_qout receives the query windows as
+ * they are, d_rout the reference windows' codon streams (W - 2 letters each), d_strand applies to R, max_rlen bounds W - 2. */
+#define PMX_FRAMESHIFT_REF_MAX_QUERY 4096
+int32_t pmx_frameshift_ref_max_query(void);         /* PMX_FRAMESHIFT_REF_MAX_QUERY of the library loaded */
+int pmx_gather_pairs_codons_ref_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                       const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                       uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                       uint8_t *d_ok /* n validity bytes, optional */, void *stream);
+int pmx_align_pairs_frameshift_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                          int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                          int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                          pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_frameshift_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                   int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                   int32_t frameshift, const uint8_t *code,
+                                   pmx_record_t *out, uint8_t *strand_out, const pmx_pairs_opts_t *opts);
+int pmx_search_pairs_frameshift_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                           int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                           int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                           pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                           int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                           int strand_mode, uint8_t *d_hit_strand, int32_t frameshift, const uint8_t *code);
+int pmx_search_pairs_frameshift_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                    const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode,
+                                    int32_t frameshift, const uint8_t *code, pmx_strand_hits_t **result);
+int pmx_search_topk_frameshift_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                          int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                          pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                          int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                          void *stream, const pmx_pairs_opts_t *opts,
+                                          int strand_mode, uint8_t *d_hit_strand, int32_t frameshift, const uint8_t *code);
+int pmx_search_topk_frameshift_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                   const pmx_topk_opts_t *opts, int strand_mode, int32_t frameshift, const uint8_t *code,
+                                   pmx_topk_strand_hits_t **result);
+/* Test hooks of the kernel (parasail-rs_amd/csrc/pmx_swfsc.hip; model: tests/swfsc_model.c): the rows of one strip and of one lane,
+ * the boundary scratch of one slot for streams of up to max_rlen letters, the largest matrix. */
+int pmx_swfsc_strip_rows(void);
+int pmx_swfsc_lane_rows(void);
+long long pmx_swfsc_bound_bytes_per_slot(int max_rlen);
+int pmx_swfsc_max_msize(void);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

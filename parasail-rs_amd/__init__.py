@@ -354,6 +354,27 @@ _sig("pmx_search_topk_frameshift_device", C.c_int, C.POINTER(pmx_config_t), C.c_
      C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
 _sig("pmx_search_topk_frameshift", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.c_int, C.c_int32, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_strand_hits_t)))
+_sig("pmx_frameshift_ref_max_query", C.c_int32)
+_sig("pmx_swfsc_strip_rows", C.c_int)
+_sig("pmx_swfsc_lane_rows", C.c_int)
+_sig("pmx_swfsc_bound_bytes_per_slot", C.c_longlong, C.c_int)
+_sig("pmx_swfsc_max_msize", C.c_int)
+_sig("pmx_gather_pairs_codons_ref_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_align_pairs_frameshift_ref_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_frameshift_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_search_pairs_frameshift_ref_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
+_sig("pmx_search_pairs_frameshift_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+     C.POINTER(pmx_pair_search_opts_t), C.c_int, C.c_int32, C.c_void_p, C.POINTER(C.POINTER(pmx_strand_hits_t)))
+_sig("pmx_search_topk_frameshift_ref_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+     C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
+_sig("pmx_search_topk_frameshift_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+     C.POINTER(pmx_topk_opts_t), C.c_int, C.c_int32, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_strand_hits_t)))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -978,7 +999,8 @@ class Aligner:
             raise BatchError(lib.pmx_last_error().decode())
         return (out, stats) if stats is not None else out
 
-    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False, frame=None, code=None, ref_frame=None, frameshift=None):
+    def align_pairs(self, Q, R, pairs, chunk_pairs=0, strand=None, cigar=False, frame=None, code=None, ref_frame=None, frameshift=None,
+                    ref_frameshift=None, ref_strand=None):
         """Pairs by index and window into device-resident sequence sets (SeqSet; Q may be R).  `pairs`: a PAIR_DTYPE array, or
         an iterable of (q, r) / (q, r, q_beg, q_len, r_beg, r_len) tuples (len -1: to the sequence's end).  Record k is the record
         of the pair (query window, reference window) k, end positions relative to the windows.  A bad descriptor raises BatchError
@@ -995,7 +1017,11 @@ class Aligner:
         reference, the frames are the reference's.  `frameshift` (a penalty >= 0; not together with frame or ref_frame): Q holds
         nucleotides, R proteins, and every pair is aligned by the three-frame local DP that may change its reading frame
         (codon_stream() restates the query side) -- strand None or 0: as stored, 1: reverse-complemented, "both", or one byte per
-        pair; end_query is in NUCLEOTIDES of the oriented window; returns (records, strand)."""
+        pair; end_query is in NUCLEOTIDES of the oriented window; returns (records, strand).  `ref_frameshift` (a penalty >= 0; not
+        together with frame, ref_frame, frameshift, strand or cigar): the opposite pairing -- Q holds proteins, R nucleotides of any
+        length, and the three-frame DP runs over the REFERENCE window's codon stream; ref_strand None or 0: the reference as stored,
+        1: reverse-complemented, "both", or one byte per pair; end_ref is in NUCLEOTIDES of the oriented reference window, end_query
+        in letters; returns (records, strand), the strand being the reference's."""
         if not self._profile.is_null():
             raise BatchError("align_pairs takes no profile")
         pairs = as_pairs(pairs)
@@ -1004,8 +1030,12 @@ class Aligner:
         out = np.zeros(n, dtype=RECORD_DTYPE)
         stats = np.zeros(n, dtype=STATS_DTYPE) if cfg.want & WANT_STATS else None
         opts = pmx_pairs_opts_t(int(chunk_pairs))
-        if frameshift is not None:
-            _frameshift_side(frame, ref_frame)
+        ref_side = _ref_frameshift_side(ref_frameshift, ref_strand, frame, ref_frame, frameshift, strand is not None, cigar)
+        if frameshift is not None or ref_side:
+            if ref_side:
+                frameshift, strand = ref_frameshift, ref_strand
+            else:
+                _frameshift_side(frame, ref_frame)
             if cigar:
                 cfg.want |= WANT_CIGAR                   # (refused by the entry)
             per_pair = None
@@ -1017,9 +1047,10 @@ class Aligner:
                     raise BatchError("strand and pairs differ in count")
             code = _code_arg(code)
             won = np.zeros(n, dtype=np.uint8)
-            rc = lib.pmx_align_pairs_frameshift(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
-                                                per_pair.ctypes.data if per_pair is not None else None, mode, int(frameshift),
-                                                code.ctypes.data if code is not None else None, out.ctypes.data, won.ctypes.data, C.byref(opts))
+            entry = lib.pmx_align_pairs_frameshift_ref if ref_side else lib.pmx_align_pairs_frameshift
+            rc = entry(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
+                       per_pair.ctypes.data if per_pair is not None else None, mode, int(frameshift),
+                       code.ctypes.data if code is not None else None, out.ctypes.data, won.ctypes.data, C.byref(opts))
             if rc:
                 raise BatchError(lib.pmx_last_error().decode())
             return out, won
@@ -1135,7 +1166,7 @@ class Aligner:
         return (out, stats) if stats is not None else out
 
     def search_pairs(self, Q, R=None, min_score=0, pairs=None, first=0, count=None, stats=False, max_hits=0, chunk_pairs=0,
-                     slice_pairs=0, strand=0, frame=None, code=None, ref_frame=None, frameshift=None):
+                     slice_pairs=0, strand=0, frame=None, code=None, ref_frame=None, frameshift=None, ref_frameshift=None, ref_strand=None):
         """Set search: the pairs of an enumeration that score at least min_score, as a PairHits in enumeration order.  `pairs`
         given: those descriptors of Q x R (as align_pairs takes them; R None: Q); else R None: pairs [first, first + count) of the
         strict upper triangle of Q (the numbering of align_all_pairs); else the same window of the rectangle Q x R, row-major
@@ -1149,7 +1180,9 @@ class Aligner:
         PairHits.frame is then the reference's frame.  frameshift (a penalty >= 0; with strand, not together with frame or
         ref_frame): nucleotide queries against proteins by the three-frame DP of align_pairs(frameshift=); PairHits.strand tells the
         strand, end_query is in nucleotides; align_pairs_frameshift_cigar(Q, R, hits.pairs, frameshift, strand=hits.strand) gives the
-        hits' alignments."""
+        hits' alignments.  ref_frameshift (a penalty >= 0; with ref_strand -- 0, 1 or "both" --, not together with frame, ref_frame,
+        frameshift or strand): protein queries against nucleotide references of any length by the three-frame DP of
+        align_pairs(ref_frameshift=); PairHits.strand tells the REFERENCE's strand, end_ref is in nucleotides."""
         if not self._profile.is_null():
             raise BatchError("search_pairs takes no profile")
         cfg = self._config()
@@ -1171,6 +1204,11 @@ class Aligner:
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first), int(count),
                 pairs.ctypes.data if pairs is not None and len(pairs) else None, C.byref(opts))
         mode = _strand_mode(strand)
+        if _ref_frameshift_side(ref_frameshift, ref_strand, frame, ref_frame, frameshift, mode != STRAND_FORWARD, False):
+            code = _code_arg(code)
+            return _hits_call(lib.pmx_search_pairs_frameshift_ref, args + (_strand_mode(0 if ref_strand is None else ref_strand), int(ref_frameshift),
+                                                                           code.ctypes.data if code is not None else None),
+                              pmx_strand_hits_t, PairHits, lib.pmx_strand_hits_free)
         if frameshift is not None:
             _frameshift_side(frame, ref_frame)
             code = _code_arg(code)
@@ -1186,7 +1224,7 @@ class Aligner:
         return _hits_call(lib.pmx_search_pairs, args, pmx_pair_hits_t, PairHits, lib.pmx_pair_hits_free)
 
     def search_topk(self, Q, R=None, k=10, min_score=INT32_MIN, skip_self=False, first_row=0, rows=None, stats=False, chunk_pairs=0,
-                    slice_rows=0, strand=0, frame=None, code=None, ref_frame=None, frameshift=None):
+                    slice_rows=0, strand=0, frame=None, code=None, ref_frame=None, frameshift=None, ref_frameshift=None, ref_strand=None):
         """Per-query top-K: for each query row [first_row, first_row + rows) of Q the best k references of R (None: Q) with score
         >= min_score, in (score descending, reference index ascending) order, as a TopKHits.  rows None: to the last row.
         skip_self (R is Q) leaves the pair (i, i) out.  stats=True adds the hits' statistics.  Only the hits leave the device;
@@ -1194,7 +1232,8 @@ class Aligner:
         candidate with its better strand, and TopKHits.strand tells which.  frame as in search_pairs: a reference is one candidate
         with its best frame, and TopKHits.frame tells which.  ref_frame as in search_pairs: the references are the translated side.
         frameshift as in search_pairs: a reference is one candidate with its better strand under the three-frame DP, and
-        align_pairs_frameshift_cigar takes TopKHits.pairs and TopKHits.strand as they are."""
+        align_pairs_frameshift_cigar takes TopKHits.pairs and TopKHits.strand as they are.  ref_frameshift with ref_strand as in
+        search_pairs: a nucleotide reference is one candidate with its better strand, the best loci per protein."""
         if not self._profile.is_null():
             raise BatchError("search_topk takes no profile")
         cfg = self._config()
@@ -1205,6 +1244,11 @@ class Aligner:
         opts = pmx_topk_opts_t(int(min_score), int(k), 1 if skip_self else 0, int(chunk_pairs), int(slice_rows))
         args = (C.byref(cfg), Q._handle(), R._handle() if R is not None else None, int(first_row), int(rows), C.byref(opts))
         mode = _strand_mode(strand)
+        if _ref_frameshift_side(ref_frameshift, ref_strand, frame, ref_frame, frameshift, mode != STRAND_FORWARD, False):
+            code = _code_arg(code)
+            return _hits_call(lib.pmx_search_topk_frameshift_ref, args + (_strand_mode(0 if ref_strand is None else ref_strand), int(ref_frameshift),
+                                                                          code.ctypes.data if code is not None else None),
+                              pmx_topk_strand_hits_t, TopKHits, lib.pmx_topk_strand_hits_free)
         if frameshift is not None:
             _frameshift_side(frame, ref_frame)
             code = _code_arg(code)
@@ -1441,6 +1485,24 @@ def _frameshift_side(frame, ref_frame):
         raise BatchError("frameshift excludes frame and ref_frame: the three-frame alignment reads every frame of a strand at once")
 
 
+def _ref_frameshift_side(ref_frameshift, ref_strand, frame, ref_frame, frameshift, stranded, cigar):
+    """ref_frameshift= / ref_strand= of align_pairs, search_pairs and search_topk: True when the reference-side three-frame
+    alignment is asked for, after what it excludes."""
+    if ref_frameshift is None:
+        if ref_strand is not None:
+            raise BatchError("ref_strand belongs to ref_frameshift: the reference has a strand only where it is the nucleotide side")
+        return False
+    if frame is not None or ref_frame is not None:
+        raise BatchError("ref_frameshift excludes frame and ref_frame: the three-frame alignment reads every frame of a strand at once")
+    if frameshift is not None:
+        raise BatchError("ref_frameshift and frameshift exclude each other: no entry translates both sides")
+    if stranded:
+        raise BatchError("ref_frameshift and strand exclude each other: a strand is the query's, and the query is protein; ref_strand is the reference's")
+    if cigar:
+        raise BatchError("ref_frameshift excludes cigar: the reference side has no traceback with frameshift operators yet")
+    return True
+
+
 def _frame_mode(frame, n=None):
     """A frame argument -> (frame mode, frame bytes per pair or None): 0 .. 5, FRAMES_* or "forward" / "reverse" / "all"; with n
     (align_pairs) also one frame byte per pair."""
@@ -1516,6 +1578,11 @@ def codon_stream(seq, strand=0, code=None):
     idx = 16 * b[:-2] + 4 * b[1:-1] + b[2:]
     lut = np.frombuffer(bytes(code), dtype=np.uint8)
     return np.where(idx < 64, lut[np.minimum(idx, 63)], ord("X")).astype(np.uint8).tobytes()
+
+
+def frameshift_ref_max_query():
+    """The longest query window, in letters, the _frameshift_ref entries take (PMX_FRAMESHIFT_REF_MAX_QUERY of the library)."""
+    return int(lib.pmx_frameshift_ref_max_query())
 
 
 def frameshift_max_window():
@@ -1926,6 +1993,30 @@ def align_pairs_frameshift_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, 
     rc = lib.pmx_align_pairs_frameshift_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, int(strand_mode), int(frameshift),
                                                code.ctypes.data if code is not None else None, max_qlen, max_rlen, d_out, d_strand_out,
                                                stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def gather_pairs_codons_ref_device(Q, R, n, d_pairs, d_strand, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff,
+                                   d_ok=None, stream=0, code=None):
+    """gather_pairs_codons_device with the sides exchanged: the REFERENCE windows become codon streams (d_strand: the reference's
+    strand byte per pair or None for forward; max_rlen bounds the stream's length, the window's minus 2), the queries are copied."""
+    code = _code_arg(code)
+    rc = lib.pmx_gather_pairs_codons_ref_device(Q._handle(), R._handle(), n, d_pairs, d_strand, code.ctypes.data if code is not None else None,
+                                                max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_frameshift_ref_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, max_qlen, max_rlen, d_out, d_strand_out=None,
+                                      stream=0, chunk_pairs=0, code=None):
+    """align_pairs_frameshift_device with the sides exchanged: protein queries of up to max_qlen letters against the codon streams of
+    nucleotide reference windows; the strands are the reference's, max_rlen bounds the stream, W - 2, and has no cap."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_align_pairs_frameshift_ref_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, int(strand_mode), int(frameshift),
+                                                   code.ctypes.data if code is not None else None, max_qlen, max_rlen, d_out, d_strand_out,
+                                                   stream, C.byref(opts))
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

@@ -3744,15 +3744,18 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 // same with the sides exchanged -- the reference windows are the nucleotides, max_rlen bounds their translated length, and the
 // reference buffer holds per * cn * max_rlen letters.  fr->codons (the _frameshift entries): the query windows become
 // codon streams of W - 2 letters, one slot per strand; max_qlen bounds the stream, and the body aligns the slots with pmx_swfs.
+// fr->codons with fr->ref (the _frameshift_ref entries): the REFERENCE windows become the codon streams, max_rlen bounds
+// the stream, the queries are proteins, and the body aligns the slots with pmx_swfsc.
 static int strand_slots(int strand_mode) { return strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
-enum { TR_NONE = 0, TR_QUERY = 1, TR_REF = 2, TR_CODONS = 3 };      // which side an entry translates (the search and top-K entries' `translated`); TR_CODONS: the _frameshift entries
+enum { TR_NONE = 0, TR_QUERY = 1, TR_REF = 2, TR_CODONS = 3, TR_CODONS_REF = 4 };      // which side an entry translates (the search and top-K entries' `translated`); TR_CODONS: the _frameshift entries, TR_CODONS_REF: the _frameshift_ref entries
 struct FrameRun {
     int first = 0, per = 1;                 // the frames first .. first + per - 1 for every pair ...
     const uint8_t *d_frame = nullptr;       // ... or (listed pairs, per 1) a frame byte per pair
     PmxCodeTable code;
     bool ref = false;                       // the translated side: the query's windows, or (true) the reference's
     // codons (the _frameshift entries): the query slots are codon streams, one per strand -- first .. first + per - 1, or
-    // d_frame's byte per pair -- and a chunk's alignment is pmx_swfs with this frameshift penalty
+    // d_frame's byte per pair -- and a chunk's alignment is pmx_swfs with this frameshift penalty.  codons with ref: the
+    // reference slots are the streams, and the alignment is pmx_swfsc
     bool codons = false; int frameshift = 0;
     int min_off() const { return per == 1 && !d_frame ? first % 3 : 0; }      // the smallest offset a frame of the call reads from
     int32_t letters(int32_t w) const { return std::max<int32_t>(1, codons ? w - 2 : (w - min_off()) / 3); }   // the longest translation of w nucleotides
@@ -3800,7 +3803,7 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         const int64_t sn = cn * per;                              // the chunk's alignment slots
         if (!rc) rc = fr && fr->codons ? pmx_launch_pairs_resolve_codons(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
                                                                          R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                                                         b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
+                                                                         b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep, fr->ref)
                     : fr       ? pmx_launch_pairs_resolve_frames(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
                                                                  R->d_off, R->count, R->bytes, max_qlen, max_rlen,
                                                                  b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep, fr->ref)
@@ -3814,7 +3817,7 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         if (!rc) rc = pmx_launch_text_offsets(b.qlen, sn, b.qoff, scan, scan_bytes, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.rlen, sn, b.roff, scan, scan_bytes, prep);
         if (!rc) rc = fr && fr->codons ? pmx_launch_pairs_gather_codons(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
-                                                                        b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep)
+                                                                        b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep, fr->ref)
                     : fr       ? pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
                                                                     b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep, fr->ref)
                     : stranded ? pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
@@ -4093,31 +4096,49 @@ extern "C" int32_t pmx_frameshift_max_window(void) { return PMX_FRAMESHIFT_MAX_W
 // What every _frameshift entry refuses about its strand mode, penalty, matrix, mode, width and outputs, before any GPU work.  *fr: the
 // run's strands (d_strand: a strand byte per pair, listed pairs only), code and penalty.
 static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint8_t *d_strand, int32_t frameshift, const uint8_t *code, FrameRun *fr,
-                            bool traceback = false /* the _frameshift_cigar entries: the outputs are theirs to check */)
+                            bool traceback = false /* the _frameshift_cigar entries: the outputs are theirs to check */,
+                            bool ref = false /* the _frameshift_ref entries: the strands and the stream are the reference's */)
 {
     if (strand_mode < PMX_STRAND_FORWARD || strand_mode > PMX_STRAND_BOTH) {
         set_err("strand mode %d is outside 0 .. 2 (PMX_STRAND_FORWARD, PMX_STRAND_REVERSE, PMX_STRAND_BOTH)", strand_mode); return -1;
     }
     if (d_strand && strand_mode != PMX_STRAND_FORWARD) { set_err("a strand byte per pair takes strand mode PMX_STRAND_FORWARD, not %d", strand_mode); return -1; }
     if (frameshift < 0) { set_err("the frameshift penalty is passed as a non-negative number, not %d", (int)frameshift); return -1; }
-    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("the frameshift entries take no PSSM matrix: a profile belongs to one protein query"); return -1; }
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {
+        set_err(ref ? "the reference-side frameshift entries take no PSSM matrix: the profile would belong to the protein query, but the kernel has no PSSM form"
+                    : "the frameshift entries take no PSSM matrix: a profile belongs to one protein query");
+        return -1;
+    }
     if (cfg->mode != PMX_MODE_SW) { set_err("the frameshift entries align locally: mode %d is not PMX_MODE_SW", cfg->mode); return -1; }
     if (cfg->width != 0 && cfg->width != 32) { set_err("the frameshift entries compute in 32 bits: width %d is neither 0 nor 32", cfg->width); return -1; }
     if (!traceback && (cfg->want & PMX_WANT_STATS)) { set_err("the frameshift entries have no statistics (PMX_WANT_STATS)"); return -1; }
-    if (!traceback && (cfg->want & PMX_WANT_CIGAR)) { set_err("the frameshift entries have no CIGAR output (PMX_WANT_CIGAR): there is no traceback with frameshift operators"); return -1; }
-    if (cfg->matrix->size > pmx_swfs_max_msize()) {
-        set_err("the frameshift kernel keeps the matrix in LDS: %d symbols exceed %d", cfg->matrix->size, pmx_swfs_max_msize()); return -1;
+    if (!traceback && (cfg->want & PMX_WANT_CIGAR)) {
+        set_err(ref ? "the reference-side frameshift entries have no CIGAR output (PMX_WANT_CIGAR): this side has no traceback yet, the hit list is the interface"
+                    : "the frameshift entries have no CIGAR output (PMX_WANT_CIGAR): there is no traceback with frameshift operators");
+        return -1;
     }
-    fr->ref = false; fr->codons = true; fr->frameshift = frameshift;
+    const int max_msize = ref ? pmx_swfsc_max_msize() : pmx_swfs_max_msize();
+    if (cfg->matrix->size > max_msize) {
+        set_err("the frameshift kernel keeps the matrix in LDS: %d symbols exceed %d", cfg->matrix->size, max_msize); return -1;
+    }
+    fr->ref = ref; fr->codons = true; fr->frameshift = frameshift;
     fr->first = strand_mode == PMX_STRAND_REVERSE ? 1 : 0;
     fr->per = strand_slots(strand_mode);
     fr->d_frame = d_strand;
     if (code) memcpy(fr->code.v, code, 64); else pmx_genetic_code_host(fr->code.v);
     return 0;
 }
-// max_qlen bounds N = W - 2, the rows the kernel sees.
-static int frameshift_rows_check(int32_t max_qlen)
+// max_qlen bounds N = W - 2, the rows the kernel sees.  ref (the _frameshift_ref entries): max_qlen bounds the protein's letters, the
+// rows of pmx_swfsc; the stream on the columns has no cap of its own.
+static int frameshift_rows_check(int32_t max_qlen, bool ref = false)
 {
+    if (ref) {
+        if (max_qlen > PMX_FRAMESHIFT_REF_MAX_QUERY) {
+            set_err("a query of %d letters exceeds PMX_FRAMESHIFT_REF_MAX_QUERY = %d letters", (int)max_qlen, PMX_FRAMESHIFT_REF_MAX_QUERY);
+            return -1;
+        }
+        return 0;
+    }
     if (max_qlen > PMX_FRAMESHIFT_MAX_WINDOW - 2) {
         set_err("a codon stream of %d letters exceeds the %d of the longest window, PMX_FRAMESHIFT_MAX_WINDOW = %d nucleotides",
                 (int)max_qlen, PMX_FRAMESHIFT_MAX_WINDOW - 2, PMX_FRAMESHIFT_MAX_WINDOW);
@@ -4125,9 +4146,15 @@ static int frameshift_rows_check(int32_t max_qlen)
     }
     return 0;
 }
+// The search and top-K entries: the rows' bound of the side `translated` names, nothing for the other entries.
+static int codons_rows_check(int translated, int32_t max_qlen)
+{
+    return translated == TR_CODONS || translated == TR_CODONS_REF ? frameshift_rows_check(max_qlen, translated == TR_CODONS_REF) : 0;
+}
 
 // A chunk's alignment: `slots` codon streams of b against their proteins into d_out.  Streams longer than one strip keep their
-// boundary columns in scratch, at most 256 MiB of it: the launcher then runs the slots in parts.
+// boundary columns in scratch, at most 256 MiB of it: the launcher then runs the slots in parts.  fr.ref: the streams are the
+// reference slots and the kernel is pmx_swfsc, whose strips are cut from the protein's rows.
 static int swfs_chunk(const pmx_config_t *cfg, const FrameRun &fr, int64_t slots, const PairsChunkBufs &b, int32_t max_qlen, int32_t max_rlen,
                       pmx_record_t *d_out, hipStream_t st)
 {
@@ -4135,13 +4162,14 @@ static int swfs_chunk(const pmx_config_t *cfg, const FrameRun &fr, int64_t slots
     if (get_devmat(cfg->matrix, &dm)) return -1;
     PmxBatch pb = {b.q, b.qoff, b.r, b.roff, slots, max_qlen, max_rlen, 0, nullptr, nullptr, nullptr, 0, 0};
     void *bnd = nullptr; long long bnd_slots = 0;
-    if (max_qlen > pmx_swfs_strip_rows()) {
-        const size_t per_slot = pmx_swfs_bound_bytes_per_slot(max_rlen);
+    if (max_qlen > (fr.ref ? pmx_swfsc_strip_rows() : pmx_swfs_strip_rows())) {
+        const size_t per_slot = fr.ref ? (size_t)pmx_swfsc_bound_bytes_per_slot(max_rlen) : pmx_swfs_bound_bytes_per_slot(max_rlen);
         bnd_slots = std::max<long long>(4, (long long)(PMX_PAIRS_CHUNK_BYTES / (double)per_slot) / 4 * 4);
         bnd_slots = std::min<long long>(bnd_slots, (slots + 3) / 4 * 4);
         if (scratch_reserve(per_slot * (size_t)bnd_slots, &bnd, SCR_SWFS)) return -1;
     }
-    const int rc = pmx_launch_swfs(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, bnd_slots, d_out, st, &g_last_kernel);
+    const int rc = fr.ref ? pmx_launch_swfsc(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, bnd_slots, d_out, st, &g_last_kernel)
+                          : pmx_launch_swfs(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, bnd_slots, d_out, st, &g_last_kernel);
     if (rc) { set_err(rc < 0 ? "frameshift kernel launch failed: %s" : "the frameshift kernel does not take this batch%s", rc < 0 ? hipGetErrorString((hipError_t)(-rc)) : ""); return -1; }
     return 0;
 }
@@ -4165,24 +4193,44 @@ static int pairs_run_codons(const pmx_config_t *cfg, const pmx_seqset *Q, const 
         }, PMX_STRAND_FORWARD, &fr);
 }
 
-extern "C" int pmx_align_pairs_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
-                                                 int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
-                                                 int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
-                                                 pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts)
+// Both device entries over listed pairs: ref false pmx_align_pairs_frameshift_device, true pmx_align_pairs_frameshift_ref_device.
+static int align_pairs_codons_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                     int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                     int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                     pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts, bool ref)
 {
     FrameRun fr;
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
     if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr)) return -1;
+    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, false, ref)) return -1;
     if (n > 0 && fr.per > 1 && !d_strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
     if (n == 0) return 0;
-    if (frameshift_rows_check(max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, false)) return -1;
+    if (frameshift_rows_check(max_qlen, ref) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, false)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     return pairs_run_codons(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, (hipStream_t)stream,
                             pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
+}
+
+extern "C" int pmx_align_pairs_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                 int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                 int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                 pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_codons_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, code, max_qlen, max_rlen, d_out, d_strand_out, stream, opts, false);
+}
+
+// ---- frameshift-aware translated search, reference side: the reference windows' codon streams through pmx_swfsc ----
+extern "C" int32_t pmx_frameshift_ref_max_query(void) { return PMX_FRAMESHIFT_REF_MAX_QUERY; }
+
+extern "C" int pmx_align_pairs_frameshift_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                     int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                     int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                     pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_codons_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, code, max_qlen, max_rlen, d_out, d_strand_out, stream, opts, true);
 }
 
 // ---- frameshift traceback: the trace form of pmx_swfs, the walk of pmx_walkfs.hip, the device text rendering ----
@@ -4291,10 +4339,11 @@ extern "C" int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, 
                                   d_cigar_off, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
 }
 
-extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
-                                              const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
-                                              uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
-                                              uint8_t *d_ok, void *stream)
+// Both gather hooks: ref false pmx_gather_pairs_codons_device, true pmx_gather_pairs_codons_ref_device.
+static int gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                      const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                      uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                      uint8_t *d_ok, void *stream, bool ref)
 {
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
@@ -4321,13 +4370,29 @@ extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_s
         })) return -1;
     if (d_ok) ok = d_ok;
     int rc = pmx_launch_pairs_resolve_codons(d_pairs, d_strand, 0, 1, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                             qlen, rlen, tw, qsrc, rsrc, ok, sflag, st);
+                                             qlen, rlen, tw, qsrc, rsrc, ok, sflag, st, ref);
     if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
     if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
     if (!rc) rc = pmx_launch_pairs_gather_codons(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, tw, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
-                                                 d_qout, q_capacity, d_rout, r_capacity, ct, st);
+                                                 d_qout, q_capacity, d_rout, r_capacity, ct, st, ref);
     if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
     return 0;
+}
+
+extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                              const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                              uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                              uint8_t *d_ok, void *stream)
+{
+    return gather_pairs_codons_device(Q, R, n, d_pairs, d_strand, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, false);
+}
+
+extern "C" int pmx_gather_pairs_codons_ref_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                                                  const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                  uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                                                  uint8_t *d_ok, void *stream)
+{
+    return gather_pairs_codons_device(Q, R, n, d_pairs, d_strand, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, true);
 }
 
 // ---- strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device) ----
@@ -4769,13 +4834,15 @@ extern "C" int pmx_align_pairs_translated_ref(const pmx_config_t *cfg, const pmx
 }
 
 // Listed pairs over a set with host offsets, the descriptors below `end` good: the first whose query window has fewer than three
-// nucleotides -- no codon stream --, refused with its number; 0 when there is none.
-static int short_window_check(const pmx_seqset *Q, const pmx_pair_t *pairs, int64_t end)
+// nucleotides -- no codon stream --, refused with its number; 0 when there is none.  ref (the _frameshift_ref entries): S is the
+// reference set and the window the reference's.
+static int short_window_check(const pmx_seqset *S, const pmx_pair_t *pairs, int64_t end, bool ref = false)
 {
     for (int64_t k = 0; k < end; ++k) {
         const pmx_pair_t &p = pairs[k];
-        const int64_t W = p.q_len < 0 ? Q->h_off[(size_t)p.q + 1] - Q->h_off[(size_t)p.q] - p.q_beg : p.q_len;
-        if (W < 3) { set_err("pair %lld: query: a window of %lld nucleotides has no codon", (long long)k, (long long)W); return -1; }
+        const int64_t idx = ref ? p.r : p.q, beg = ref ? p.r_beg : p.q_beg, len = ref ? p.r_len : p.q_len;
+        const int64_t W = len < 0 ? S->h_off[(size_t)idx + 1] - S->h_off[(size_t)idx] - beg : len;
+        if (W < 3) { set_err("pair %lld: %s: a window of %lld nucleotides has no codon", (long long)k, ref ? "reference" : "query", (long long)W); return -1; }
     }
     return 0;
 }
@@ -4788,14 +4855,15 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
                                        int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
                                        int32_t frameshift, const uint8_t *code, pmx_record_t *out, uint8_t *strand_out,
                                        const pmx_pairs_opts_t *opts, bool traceback,
-                                       pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off)
+                                       pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off,
+                                       bool ref = false /* pmx_align_pairs_frameshift_ref (no traceback): the stream is the reference's */)
 {
     FrameRun fr;
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
     if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr, traceback) ||
+    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr, traceback, ref) ||
         (traceback && frameshift_cigar_outputs_check(cfg, stats_out, cigar_buf, 0, cigar_off))) return -1;
     if (n > 0 && fr.per > 1 && !strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
     if (traceback) { *cigar_buf = nullptr; cigar_off[0] = 0; }
@@ -4807,11 +4875,11 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
     int64_t mq = 1, mr = 1;
     if (host_offsets) {
         const PairScan s = scan_pairs(Q, R, pairs, 0, n);
-        if (short_window_check(Q, pairs, s.bad >= 0 ? s.bad : n)) return -1;
+        if (short_window_check(ref ? R : Q, pairs, s.bad >= 0 ? s.bad : n, ref)) return -1;
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
-        mq = fr.letters((int32_t)s.mq); mr = s.mr;
+        mq = ref ? s.mq : fr.letters((int32_t)s.mq); mr = ref ? fr.letters((int32_t)s.mr) : s.mr;
     }
-    if (frameshift_rows_check((int32_t)mq) || (traceback && host_offsets && frameshift_trace_bound_check((int32_t)mq, (int32_t)mr)) ||
+    if (frameshift_rows_check((int32_t)mq, ref) || (traceback && host_offsets && frameshift_trace_bound_check((int32_t)mq, (int32_t)mr)) ||
         pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr, traceback)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
@@ -4827,8 +4895,8 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
     int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
     if (!host_offsets) {
         if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
-        q32 = fr.letters(q32);
-        if (frameshift_rows_check(q32) || (traceback && frameshift_trace_bound_check(q32, r32))) return -1;
+        if (ref) r32 = fr.letters(r32); else q32 = fr.letters(q32);
+        if (frameshift_rows_check(q32, ref) || (traceback && frameshift_trace_bound_check(q32, r32))) return -1;
     }
     const int64_t chunk = pairs_chunk(n, q32, r32, opts, fr.per);
     if (!traceback) {
@@ -4872,6 +4940,15 @@ extern "C" int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seq
 {
     return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, false,
                                        nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int pmx_align_pairs_frameshift_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                              int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                              int32_t frameshift, const uint8_t *code,
+                                              pmx_record_t *out, uint8_t *strand_out, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, false,
+                                       nullptr, nullptr, nullptr, nullptr, true);
 }
 
 extern "C" int pmx_align_pairs_frameshift_cigar(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -5057,13 +5134,13 @@ static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const 
 }
 
 // The side an entry translates, checked and turned into the run's FrameRun.  TR_NONE: nothing.  TR_QUERY / TR_REF: frame_mode and code.
-// TR_CODONS (the _frameshift entries): *strand_mode and frameshift; the strands become the run's slots, so the mode the pipeline
-// below sees is PMX_STRAND_FORWARD.
+// TR_CODONS / TR_CODONS_REF (the _frameshift / _frameshift_ref entries): *strand_mode and frameshift; the strands become the run's
+// slots, so the mode the pipeline below sees is PMX_STRAND_FORWARD.
 static int side_check(const pmx_config_t *cfg, int translated, int frame_mode, const uint8_t *code, int *strand_mode, int32_t frameshift, FrameRun *fr)
 {
     if (translated == TR_NONE) return 0;
-    if (translated != TR_CODONS) return frames_check(cfg, frame_mode, nullptr, code, fr, translated == TR_REF);
-    if (frameshift_check(cfg, *strand_mode, nullptr, frameshift, code, fr)) return -1;
+    if (translated != TR_CODONS && translated != TR_CODONS_REF) return frames_check(cfg, frame_mode, nullptr, code, fr, translated == TR_REF);
+    if (frameshift_check(cfg, *strand_mode, nullptr, frameshift, code, fr, false, translated == TR_CODONS_REF)) return -1;
     *strand_mode = PMX_STRAND_FORWARD;
     return 0;
 }
@@ -5085,12 +5162,13 @@ static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
     if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) ||
         search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
+    if (translated == TR_CODONS_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null strand output: both strands report which one won"); return -1; }
     if (n == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
         return 0;
     }
     if (!d_counts) { set_err("null counts"); return -1; }
-    if ((translated == TR_CODONS && frameshift_rows_check(max_qlen)) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    if (codons_rows_check(translated, max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const PairHitBufs o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_counts, nullptr};
@@ -5150,6 +5228,17 @@ extern "C" int pmx_search_pairs_frameshift_device(const pmx_config_t *cfg, const
 {
     return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                                capacity, d_counts, stream, opts, strand_mode, d_hit_strand, TR_CODONS, 0, code, frameshift);
+}
+
+extern "C" int pmx_search_pairs_frameshift_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
+                                                      int64_t first, int64_t n, const pmx_pair_t *d_pairs,
+                                                      int32_t max_qlen, int32_t max_rlen, int32_t min_score,
+                                                      pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                      int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts,
+                                                      int strand_mode, uint8_t *d_hit_strand, int32_t frameshift, const uint8_t *code)
+{
+    return search_pairs_device(cfg, Q, R, shape, first, n, d_pairs, max_qlen, max_rlen, min_score, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                               capacity, d_counts, stream, opts, strand_mode, d_hit_strand, TR_CODONS_REF, 0, code, frameshift);
 }
 
 extern "C" void pmx_pair_hits_free(pmx_pair_hits_t *hits) { free(hits); }
@@ -5237,7 +5326,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     SetLens m;
     if (host_offsets && listed) {
         const PairScan s = scan_pairs(Q, R, pairs, 0, n);
-        if (translated == TR_CODONS && short_window_check(Q, pairs, s.bad >= 0 ? s.bad : n)) return -1;
+        if ((translated == TR_CODONS || translated == TR_CODONS_REF) && short_window_check(translated == TR_CODONS_REF ? R : Q, pairs, s.bad >= 0 ? s.bad : n, translated == TR_CODONS_REF)) return -1;
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
         m.mq = (int32_t)s.mq; m.mr = (int32_t)s.mr; m.mnr = (int32_t)s.mnr;
     } else if (host_offsets && window_host_lens(Q, R, shape, first, n, &m)) return -1;
@@ -5246,7 +5335,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     const bool find_bad = !host_offsets || fr != nullptr;
     const int per = fr ? fr->per : strand_slots(strand_mode);
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if ((translated == TR_CODONS && frameshift_rows_check(m.mq)) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
+    if (codons_rows_check(translated, m.mq) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
@@ -5274,7 +5363,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
             if (!host_offsets) {
                 if (device_maxlens(Q, R, dp, sn, &m.mq, &m.mr, st)) return -1;
                 to_letters();
-                if (pssm_batch_check(cfg->matrix, m.mq, m.mq) || (translated == TR_CODONS && frameshift_rows_check(m.mq))) return -1;
+                if (pssm_batch_check(cfg->matrix, m.mq, m.mq) || codons_rows_check(translated, m.mq)) return -1;
             }
         }
         const int64_t p0 = listed ? s0 : first + s0;     // the slice's first pair in the enumeration
@@ -5328,6 +5417,13 @@ extern "C" int pmx_search_pairs_frameshift(const pmx_config_t *cfg, const pmx_se
                                            int32_t frameshift, const uint8_t *code, pmx_strand_hits_t **result)
 {
     return search_pairs_host(cfg, Q, R, first, n, pairs, opts, strand_mode, true, (pmx_pair_hits_t **)result, TR_CODONS, 0, code, frameshift);
+}
+
+extern "C" int pmx_search_pairs_frameshift_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t first, int64_t n,
+                                               const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode,
+                                               int32_t frameshift, const uint8_t *code, pmx_strand_hits_t **result)
+{
+    return search_pairs_host(cfg, Q, R, first, n, pairs, opts, strand_mode, true, (pmx_pair_hits_t **)result, TR_CODONS_REF, 0, code, frameshift);
 }
 
 // ==================================================================== per-query top-K ===
@@ -5454,6 +5550,7 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
     if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) ||
         search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
     if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
+    if (translated == TR_CODONS_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null strand output: both strands report which one won"); return -1; }
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), (hipStream_t)stream));
         if (d_row_off) HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), (hipStream_t)stream));
@@ -5461,7 +5558,7 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
     }
     if (!d_row_off) { set_err("null row offsets"); return -1; }
     if (!d_counts) { set_err("null counts"); return -1; }
-    if ((translated == TR_CODONS && frameshift_rows_check(max_qlen)) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    if (codons_rows_check(translated, max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const TopkOut o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_row_off, d_row_passing, d_counts, nullptr};
@@ -5517,6 +5614,17 @@ extern "C" int pmx_search_topk_frameshift_device(const pmx_config_t *cfg, const 
 {
     return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
                               capacity, d_row_off, d_row_passing, d_counts, stream, opts, strand_mode, d_hit_strand, TR_CODONS, 0, code, frameshift);
+}
+
+extern "C" int pmx_search_topk_frameshift_ref_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                                 int32_t max_qlen, int32_t max_rlen, int32_t min_score, int32_t k, int32_t skip_self,
+                                                 pmx_pair_t *d_hit_pairs, int64_t *d_hit_index, pmx_record_t *d_hit_recs, pmx_stats_t *d_hit_stats,
+                                                 int64_t capacity, int64_t *d_row_off, int64_t *d_row_passing, int64_t *d_counts,
+                                                 void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
+                                                 int32_t frameshift, const uint8_t *code)
+{
+    return search_topk_device(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats,
+                              capacity, d_row_off, d_row_passing, d_counts, stream, opts, strand_mode, d_hit_strand, TR_CODONS_REF, 0, code, frameshift);
 }
 
 // Test hook (include/parasail_amd.h): the chunk loop of topk_run over records the caller made up instead of alignments -- the same
@@ -5609,7 +5717,7 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     to_letters();
     const bool find_bad = !host_offsets || fr != nullptr;
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if ((translated == TR_CODONS && frameshift_rows_check(m.mq)) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
+    if (codons_rows_check(translated, m.mq) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
@@ -5685,4 +5793,11 @@ extern "C" int pmx_search_topk_frameshift(const pmx_config_t *cfg, const pmx_seq
                                           pmx_topk_strand_hits_t **result)
 {
     return search_topk_host(cfg, Q, R, q_first, nq, opts, strand_mode, true, (pmx_topk_hits_t **)result, TR_CODONS, 0, code, frameshift);
+}
+
+extern "C" int pmx_search_topk_frameshift_ref(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
+                                          const pmx_topk_opts_t *opts, int strand_mode, int32_t frameshift, const uint8_t *code,
+                                          pmx_topk_strand_hits_t **result)
+{
+    return search_topk_host(cfg, Q, R, q_first, nq, opts, strand_mode, true, (pmx_topk_hits_t **)result, TR_CODONS_REF, 0, code, frameshift);
 }

@@ -328,15 +328,18 @@ int pmx_launch_pairs_fold_frames(const pmx_record_t *slot_rec, const pmx_stats_t
 // Codon streams (the _frameshift entries).  resolve_codons: n descriptors -> per * n slots, one per strand (strand ? strand[k]
 // : per == 2 ? forward, reverse : first); the query's length = the stream's N = W - 2, tw = W, sflag = the strand; W < 3, a strand byte
 // above 1 and N > max_qlen make every slot a 1 x 1 placeholder with ok = 0.  gather_codons: letter p of a query slot = the codon at
-// oriented bytes p .. p + 2.  The slots' records fold with pmx_launch_pairs_fold_strands.
+// oriented bytes p .. p + 2.  The slots' records fold with pmx_launch_pairs_fold_strands.  ref (the _frameshift_ref
+// entries): the sides exchanged -- the reference's window becomes the stream, N <= max_rlen, and the query is copied.
 int pmx_launch_pairs_resolve_codons(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
                                     const int64_t *q_off, long long q_count, long long q_bytes,
                                     const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                                    int32_t *qlen, int32_t *rlen, int32_t *tw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream);
+                                    int32_t *qlen, int32_t *rlen, int32_t *tw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream,
+                                    bool ref = false);
 int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                                    const int32_t *qlen, const int32_t *rlen, const int32_t *tw, const int64_t *qsrc, const int64_t *rsrc,
                                    const uint8_t *ok, const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
-                                   uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t stream);
+                                   uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t stream,
+                                   bool ref = false);
 // The three-frame local DP over codon streams (pmx_swfs.hip): n slots of up to b.max_qlen rows x b.max_rlen columns, 32-bit scores.
 // bnd: boundary scratch of bnd_slots * pmx_swfs_bound_bytes_per_slot(b.max_rlen) bytes, needed when b.max_qlen exceeds
 // pmx_swfs_strip_rows() (the launch then runs in parts of bnd_slots slots).  0 launched, 1 not eligible, <0 HIP error.
@@ -345,6 +348,15 @@ int pmx_swfs_strip_rows();
 size_t pmx_swfs_bound_bytes_per_slot(int max_rlen);
 int pmx_launch_swfs(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
                     pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
+// The same DP with the codon stream on the columns (pmx_swfsc.hip): n slots of up to b.max_qlen protein rows x b.max_rlen
+// stream columns.  bnd: bnd_slots * pmx_swfsc_bound_bytes_per_slot(b.max_rlen) bytes, needed when b.max_qlen exceeds
+// pmx_swfsc_strip_rows() (the launch then runs in parts of bnd_slots slots).  0 launched, 1 not eligible, <0 HIP error.
+extern "C" int pmx_swfsc_max_msize();
+extern "C" int pmx_swfsc_lane_rows();
+extern "C" int pmx_swfsc_strip_rows();
+extern "C" long long pmx_swfsc_bound_bytes_per_slot(int max_rlen);
+int pmx_launch_swfsc(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
+                     pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
 // The trace form of the sweep and its walk (semantics: include/parasail_amd.h, "Frameshift traceback").  A cell's decision
 // byte: bits 0 .. 2 where H came from (START .. LONG: from M, and which term D was), bit 3 E was opened, bit 4 F was opened.  The byte of
 // row i, column j of a slot: ((i / STRIP_ROWS * max_rlen + j) * COL_BYTES) + i % STRIP_ROWS / LANE_ROWS * 12 + i % LANE_ROWS.

@@ -481,11 +481,14 @@ void pmx_pairs_fold_frames_kernel(const pmx_record_t *__restrict__ slot_rec, con
     if (okf) okf[k] = from >= 0 ? 1 : 0;
 }
 
-// ---- codon streams (the _frameshift entries, pmx_gather_pairs_codons_device) ----------------------------------------
+// ---- codon streams (the _frameshift entries, pmx_gather_pairs_codons_device; REF: the _frameshift_ref entries, 2.5m) ----
 // The resolve step of the frameshift-aware entries: logical pair k becomes `per` alignment slots, one per strand -- strand ?
-// strand[k] (per 1) : per == 2 ? forward then reverse : `first` (0 or 1).  The query resolves to its nucleotide window (W bytes, any
-// length), the reference against its maximum; a slot holds the codon stream's N = W - 2 letters.  W < 3 has no stream: 1 x 1
-// placeholders with ok = 0, as a bad descriptor, a strand byte above 1 and N > max_qlen give.  tw: W per slot, sflag: the strand.
+// strand[k] (per 1) : per == 2 ? forward then reverse : `first` (0 or 1).  REF false: the query resolves to its nucleotide window (W
+// bytes, any length), the reference against its maximum; a slot holds the codon stream's N = W - 2 letters.  W < 3 has no stream: 1 x 1
+// placeholders with ok = 0, as a bad descriptor, a strand byte above 1 and N > max_qlen give.  REF true: the sides exchanged -- the
+// reference resolves to its nucleotide window with no bound but N <= max_rlen, the query against max_qlen.  tw: W per slot, sflag: the
+// strand.
+template <bool REF>
 __global__ __launch_bounds__(256)
 void pmx_pairs_resolve_codons_kernel(const pmx_pair_t *__restrict__ pairs, const uint8_t *__restrict__ strand, int first, int per, long long n,
                                      const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
@@ -500,12 +503,13 @@ void pmx_pairs_resolve_codons_kernel(const pmx_pair_t *__restrict__ pairs, const
     const pmx_pair_t p = pairs[k];
     const unsigned s0 = strand ? strand[k] : (unsigned)first;
     long long qs = 0, rs = 0;
-    const int32_t W = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, INT32_MAX, &qs);
-    const int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
-    const bool good = W >= 3 && rl > 0 && s0 + (unsigned)per <= 2u && W - 2 <= max_qlen;
+    const int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, REF ? max_qlen : INT32_MAX, &qs);
+    const int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, REF ? INT32_MAX : max_rlen, &rs);
+    const int32_t W = REF ? rl : ql, plain = REF ? ql : rl;
+    const bool good = W >= 3 && plain > 0 && s0 + (unsigned)per <= 2u && W - 2 <= (REF ? max_rlen : max_qlen);
     const long long s = (long long)per * k;
     for (int i = 0; i < per; ++i) {
-        qlen[s + i] = good ? W - 2 : 1; rlen[s + i] = good ? rl : 1; tw[s + i] = good ? W : 0;
+        (REF ? rlen : qlen)[s + i] = good ? W - 2 : 1; (REF ? qlen : rlen)[s + i] = good ? plain : 1; tw[s + i] = good ? W : 0;
         qsrc[s + i] = good ? qs : 0; rsrc[s + i] = good ? rs : 0;
         ok[s + i] = good ? 1 : 0; sflag[s + i] = good ? (uint8_t)(s0 + (unsigned)i) : 0;
     }
@@ -515,7 +519,9 @@ void pmx_pairs_resolve_codons_kernel(const pmx_pair_t *__restrict__ pairs, const
 // p, p + 1, p + 2 of the window, so the N = W - 2 letters hold all three forward frames of the strand interleaved.  A destination
 // dword is four letters from six source bytes: one pmx_window_dword (its four bytes lie inside the window) and two byte reads -- the
 // last letter's third base is the window's last byte, and no byte outside a set's buffer is read.  Strand 1 walks the window
-// downwards with the index ^ 42, as the reverse frames there.  The reference side is copied.
+// downwards with the index ^ 42, as the reverse frames there.  The reference side is copied.  REF true: the sides exchanged -- the
+// reference slot receives its window's stream, the query is copied.
+template <bool REF>
 __global__ __launch_bounds__(256)
 void pmx_pairs_gather_codons_kernel(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes, const uint8_t *__restrict__ r_buf, long long r_bytes,
                                     const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen, const int32_t *__restrict__ tw,
@@ -538,14 +544,14 @@ void pmx_pairs_gather_codons_kernel(long long n, const uint8_t *__restrict__ q_b
     uint8_t *dst = (side ? rout : qout) + o0;
     if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
     const uint8_t *buf = side ? r_buf : q_buf;
-    const long long len = side ? rlen[k] : qlen[k];             // destination bytes: letters of the stream on the query side
+    const long long len = side ? rlen[k] : qlen[k];             // destination bytes: letters of the stream on the translated side
     const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
     const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
     long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
     if (head > len) head = len;
     const long long nd = (len - head) >> 2, done = head + 4 * nd;
     uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
-    if (side) {
+    if (side != REF) {
         if (lane < head) dst[lane] = src[lane];
         const uint8_t *s0 = src + head;
         for (long long x = lane; x < nd; x += 16)
@@ -834,21 +840,33 @@ int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long l
 int pmx_launch_pairs_resolve_codons(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
                                     const int64_t *q_off, long long q_count, long long q_bytes,
                                     const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                                    int32_t *qlen, int32_t *rlen, int32_t *tw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
+                                    int32_t *qlen, int32_t *rlen, int32_t *tw, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st,
+                                    bool ref)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_resolve_codons_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, strand, first, per, n,
-                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
+    const dim3 grid((unsigned)((n + 2 + 255) / 256));
+    if (ref)
+        hipLaunchKernelGGL(pmx_pairs_resolve_codons_kernel<true>, grid, dim3(256), 0, st, pairs, strand, first, per, n,
+                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
+    else
+        hipLaunchKernelGGL(pmx_pairs_resolve_codons_kernel<false>, grid, dim3(256), 0, st, pairs, strand, first, per, n,
+                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                                    const int32_t *qlen, const int32_t *rlen, const int32_t *tw, const int64_t *qsrc, const int64_t *rsrc,
                                    const uint8_t *ok, const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
-                                   uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t st)
+                                   uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t st,
+                                   bool ref)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_gather_codons_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
-                       qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
+    const dim3 grid((unsigned)((2 * n + 15) / 16));
+    if (ref)
+        hipLaunchKernelGGL(pmx_pairs_gather_codons_kernel<true>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
+    else
+        hipLaunchKernelGGL(pmx_pairs_gather_codons_kernel<false>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_fold_frames(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,

@@ -1,0 +1,180 @@
+// pmx_swfsc.hip -- frameshift-aware local alignment of a protein against a codon stream, "codons on columns": the three-frame DP of
+// DESIGN 2.5m (semantics: include/parasail_amd.h, "Frameshift-aware translated search, reference side").  gfx950 only.
+//
+// A slot is one protein q of m letters (the rows) against one codon stream T of a nucleotide REFERENCE window (the columns: N = W - 2
+// letters, letter j the translation of oriented nucleotides j .. j + 2, written by pmx_pairs_gather_codons_kernel<true>):
+//
+//   D(i,j) = max(0, H(i-1,j-3), H(i-1,j-2) - fs, H(i-1,j-4) - fs)        M = D + s(q[i], T[j])
+//   E(i,j) = max(H(i,j-3) - open, E(i,j-3) - ext)                        F(i,j) = max(H(i-1,j) - open, F(i-1,j) - ext)
+//   H(i,j) = max(0, M, E, F)
+//
+// It is pmx_swfs.hip's recurrence transposed, and the transposition moves the reach of a cell from the rows into the columns: one row
+// up, and two to four columns back.  Mapping: a group of G lanes per slot, R consecutive rows per lane in registers, lane g on column
+// t - g in step t, the transposed matrix in LDS (one stream letter selects the LDS row per step), group_shift_up<G> for the hand-off.
+//   - A step hands TWO values to the lane below: H and F of the lane's last row in the column it has just finished (pmx_swfs: seven).
+//   - The columns a cell reaches back to live in the lane: a ring of the last four columns' H (j - 1 .. j - 4) and a ring of E, R
+//     values each.  Both rings are indexed by the step t & 3 -- every lane advances one column per step, so the step number and the
+//     lane's column differ by a constant -- and the column loop is unrolled by four, which makes every ring index static: the rings
+//     are registers and nothing is moved.  E of column j is read once, at column j + 3, and its slot is rewritten at column j + 4, so
+//     three of the four E slots are live at a time.  A lane whose column is still negative does not write its rings: they keep the
+//     matrix's edge (H = 0, E = -inf) for the columns that do not exist.
+//   - The lane keeps the last four H it was handed in a ring of the same kind: the history of the row above its first row.
+//
+// Strips.  A query of more than G * R rows runs in strips of G * R rows, top to bottom.  The last lane of a strip stores (H, F) of its
+// last row per column (one int2, 8 bytes) into the slot's boundary scratch, member 0 of the next strip loads the pair where the first
+// strip takes the matrix's edge (H = 0, F = -inf) and keeps its own history of them.  Two boundary buffers alternate by strip parity,
+// so a strip never reads the buffer it writes; a workgroup barrier with a fence separates the strips (one wave per workgroup).
+// The stream has no cap: its length only sets the trip count and the boundary buffers' size.
+//
+// Arithmetic: 32-bit integers, one slot per lane group.  The largest score, 4 096 rows x 32 767, is below 2^28 however long the
+// stream; penalties are clamped to 2^28 by the launcher (a penalty above every score acts as infinity: H >= 0, and a negative E, F or
+// D term never wins), -inf is -2^29, so nothing can wrap and width 0 and width 32 are the same exact kernel.
+// Plain C++, vector loads and stores only.
+#include "pmx_common.h"
+#include "pmx_pk16.h"
+
+#define PMX_SWFSC_NEG (-(1 << 29))
+
+template <int G, int R>
+__global__ __launch_bounds__(64)
+void pmx_swfsc_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff,
+                      const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff,
+                      long long n, int max_qlen, int max_cols,
+                      const int16_t *__restrict__ gmat, const uint8_t *__restrict__ gmap, int msize,
+                      int open, int ext, int fs,
+                      int2 *bnd /* per slot of the launch: 2 buffers x max_cols columns */,
+                      pmx_record_t *__restrict__ out)
+{
+    static_assert(G == 16 || G == 64, "group_shift_up without a select");
+    constexpr int NPW = 64 / G;                 // slots per wave = per workgroup
+    constexpr int NEG = PMX_SWFSC_NEG;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    int16_t *matT = reinterpret_cast<int16_t *>(lds);              // matT[t * msize + q] = score(q, t): the row of a stream letter
+    unsigned char *map = lds + (size_t)msize * msize * 2;
+
+    const int lane = threadIdx.x;
+    const int g = lane % G, slotw = lane / G;
+    for (int i = lane; i < msize * msize; i += 64) matT[i] = gmat[(i % msize) * msize + i / msize];
+    for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
+    __syncthreads();
+
+    long long slot = (long long)blockIdx.x * NPW + slotw;
+    const bool live = slot < n;
+    if (!live) slot = n - 1;
+    const long long qb = qoff[slot], rb = roff[slot];
+    int m = (int)(qoff[slot + 1] - qb), N = (int)(roff[slot + 1] - rb);
+    m = min(m, max_qlen); N = min(N, max_cols);                    // (resolve keeps both inside; scratch and loops rely on it)
+    const uint8_t *qs = qbuf + qb, *ts = rbuf + rb;
+    int2 *bslot = bnd ? bnd + ((size_t)blockIdx.x * NPW + slotw) * 2 * (size_t)max_cols : nullptr;
+
+    int wm = m, wN = N;                                            // the wave's longest query and stream: uniform trip counts
+#pragma unroll
+    for (int d = 32; d >= G; d >>= 1) { wm = max(wm, __shfl_xor(wm, d)); wN = max(wN, __shfl_xor(wN, d)); }
+    const int nstrips = (wm + G * R - 1) / (G * R), T_ = wN + G - 1;
+
+    int best = 0, bi = 0, bj = 0;                                   // a zero maximum ends at row 0, column 0
+    for (int s = 0; s < nstrips; ++s) {
+        const int row0 = s * G * R + g * R;
+        int ql[R], vm[R];                                          // the rows' letters; -1 for a row of the query, 0 for one beyond it
+#pragma unroll
+        for (int k = 0; k < R; ++k) { vm[k] = row0 + k < m ? -1 : 0; ql[k] = row0 + k < m ? (int)map[qs[row0 + k]] : 0; }
+        int Hh[4][R], Eh[4][R], top[4];                            // rings by t & 3: the lane's last four columns, the row above them
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            top[p] = 0;
+#pragma unroll
+            for (int k = 0; k < R; ++k) { Hh[p][k] = 0; Eh[p][k] = NEG; }
+        }
+        int oH = 0, oF = NEG;                                      // H and F of the lane's last row in the column it finished last
+        const int2 *brd = s > 0 ? bslot + (size_t)((s - 1) & 1) * max_cols : nullptr;
+        int2 *bwr = s + 1 < nstrips ? bslot + (size_t)(s & 1) * max_cols : nullptr;
+
+        for (int t0 = 0; t0 < T_; t0 += 4) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {                          // t & 3 == p: slot p holds column j - 4 and receives column j,
+                const int p3 = (p + 1) & 3, p2 = (p + 2) & 3;      // slots p3 and p2 hold columns j - 3 and j - 2
+                const int col = t0 + p - g;
+                int uH = group_shift_up<G>(oH, 0, g), uF = group_shift_up<G>(oF, NEG, g);   // the lane above, column `col`
+                const bool valid = col >= 0 && col < N;            // (t >= T_ of the last round: col >= wN, no lane is valid)
+                if (valid) {
+                    if (g == 0 && brd) { const int2 a = brd[col]; uH = a.x; uF = a.y; }   // the strip above left the column here
+                    const int16_t *mrow = matT + (int)map[ts[col]] * msize;
+                    int a4 = top[p], a3 = top[p3], a2 = top[p2];   // row i - 1 in columns j - 4, j - 3, j - 2
+                    int hu = uH, fu = uF;                          // row i - 1 in column j
+                    top[p] = uH;
+                    int cm = 0;                                    // the column's maximum over the rows of the query (H >= 0)
+#pragma unroll
+                    for (int k = 0; k < R; ++k) {
+                        const int o4 = Hh[p][k], o3 = Hh[p3][k], o2 = Hh[p2][k];
+                        const int D = max(max(0, a3), max(a2, a4) - fs);
+                        const int M = D + (int)mrow[ql[k]];
+                        const int e = max(o3 - open, Eh[p3][k] - ext);
+                        const int f = max(hu - open, fu - ext);
+                        const int h = max(max(0, M), max(e, f));
+                        Hh[p][k] = h; Eh[p][k] = e;
+                        cm = max(cm, h & vm[k]);
+                        a4 = o4; a3 = o3; a2 = o2; hu = h; fu = f;
+                    }
+                    // a new best is rare: one branch per column.  Columns ascend within a strip, so an equal score wins only from a
+                    // later strip at a smaller column; within the column the first row that holds the maximum.
+                    if (cm > best || (cm == best && col < bj)) {
+                        best = cm; bj = col;
+#pragma unroll
+                        for (int k = R - 1; k >= 0; --k) if ((Hh[p][k] & vm[k]) == cm) bi = row0 + k;
+                    }
+                    oH = hu; oF = fu;
+                    if (g == G - 1 && bwr) bwr[col] = make_int2(oH, oF);
+                }
+            }
+        }
+        if (s + 1 < nstrips) { __threadfence_block(); __syncthreads(); }
+    }
+
+    // the group's winner: highest score, then lowest column, then lowest row (the first maximum in column-major order)
+#pragma unroll
+    for (int d = G / 2; d >= 1; d >>= 1) {
+        const int os = __shfl_xor(best, d), oj = __shfl_xor(bj, d), oi = __shfl_xor(bi, d);
+        if (os > best || (os == best && (oj < bj || (oj == bj && oi < bi)))) { best = os; bj = oj; bi = oi; }
+    }
+    if (g == 0 && live) {
+        pmx_record_t rec;
+        rec.score = best; rec.end_query = bi; rec.end_ref = bj + 2; rec.flags = 0;
+        out[slot] = rec;
+    }
+}
+
+// LDS of a launch: the transposed matrix as int16 and the byte map.
+static size_t swfsc_lds_bytes(int msize) { return (size_t)msize * msize * 2 + 256; }
+
+#define PMX_SWFSC_G 16
+#define PMX_SWFSC_R 10
+extern "C" int pmx_swfsc_max_msize() { return 128; }
+extern "C" int pmx_swfsc_lane_rows() { return PMX_SWFSC_R; }
+extern "C" int pmx_swfsc_strip_rows() { return PMX_SWFSC_G * PMX_SWFSC_R; }
+extern "C" long long pmx_swfsc_bound_bytes_per_slot(int max_rlen) { return (long long)sizeof(int2) * 2 * (long long)max_rlen; }
+
+// n slots of up to b.max_qlen rows x b.max_rlen columns.  bnd: boundary scratch for `bnd_slots` slots (needed when b.max_qlen exceeds
+// one strip; the launch then runs in parts of bnd_slots slots, one behind the other on `stream`).  0 launched, 1 not eligible, <0 HIP
+// error.
+int pmx_launch_swfsc(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
+                     pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
+{
+    constexpr int G = PMX_SWFSC_G, R = PMX_SWFSC_R, NPW = 64 / G;
+    if (m.pssm || m.msize > pmx_swfsc_max_msize() || b.q_shared) return 1;
+    if (b.n <= 0) return 0;
+    const int cap = 1 << 28;
+    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
+    const bool strips = b.max_qlen > G * R;
+    if (strips && (!bnd || bnd_slots < NPW)) return 1;
+    const long long part = strips ? bnd_slots / NPW * NPW : b.n;
+    for (long long p0 = 0; p0 < b.n; p0 += part) {
+        const long long pn = b.n - p0 < part ? b.n - p0 : part;
+        hipLaunchKernelGGL((pmx_swfsc_kernel<G, R>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfsc_lds_bytes(m.msize), stream,
+                           b.qbuf, b.qoff + p0, b.rbuf, b.roff + p0, pn, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
+                           open, ext, fs, strips ? (int2 *)bnd : nullptr, d_out + p0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return -(int)e;
+    }
+    if (kernel_name) *kernel_name = strips ? "pmx_swfsc_kernel<16,10>/strips" : "pmx_swfsc_kernel<16,10>";
+    return 0;
+}
