@@ -3733,41 +3733,106 @@ static int pairs_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_s
 // c + 2's gather overwrite the set.  Everything `prep` does is waited for by `st`, so `st` ends behind the last body and behind `prep`.
 // One chunk: all on `st`.  shape PMX_PAIRS_TRIANGLE / PMX_PAIRS_RECT: pairs [first, first + n) of the upper triangle of Q x Q / of the
 // rectangle Q x R, generated per chunk; the body finds the chunk's descriptors, listed or generated, in PairsChunkBufs::pairs.
-// d_strand != nullptr (the _ex entries): the resolve step takes the strand bytes and the gather is the one that can reverse-complement;
-// otherwise the forward-only kernels run, and a forward batch pays nothing for the strands' existence.
-// strand_mode PMX_STRAND_REVERSE / PMX_STRAND_BOTH (the entries that choose the strand themselves; d_strand is then nullptr):
-// a chunk of cn pairs is per = 1 / 2 alignment slots per pair -- BOTH: slot 2 k is pair k as stored, slot 2 k + 1 pair k with its query
-// reverse-complemented -- and the buffers hold per * cn windows; the body still gets c0 and cn in logical pairs.
-// fr != nullptr (the _translated entries; d_strand is then nullptr and the strand mode forward): the query windows are
-// nucleotides translated on their way into the buffers, per = fr->per alignment slots per pair, one per frame; max_qlen bounds the
-// translated length, so the query buffer holds per * cn * max_qlen letters.  fr->ref (the _translated_ref entries): the
-// same with the sides exchanged -- the reference windows are the nucleotides, max_rlen bounds their translated length, and the
-// reference buffer holds per * cn * max_rlen letters.  fr->codons (the _frameshift entries): the query windows become
-// codon streams of W - 2 letters, one slot per strand; max_qlen bounds the stream, and the body aligns the slots with pmx_swfs.
-// fr->codons with fr->ref (the _frameshift_ref entries): the REFERENCE windows become the codon streams, max_rlen bounds
-// the stream, the queries are proteins, and the body aligns the slots with pmx_swfsc.
-static int strand_slots(int strand_mode) { return strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
+// What a chunk's cn pairs become is the run's SlotPlan: per alignment slots per pair, so the buffers hold per * cn windows; the body
+// still gets c0 and cn in logical pairs.  max_qlen / max_rlen bound what the buffers hold: on a translated side the letters.
 enum { TR_NONE = 0, TR_QUERY = 1, TR_REF = 2, TR_CODONS = 3, TR_CODONS_REF = 4 };      // which side an entry translates (the search and top-K entries' `translated`); TR_CODONS: the _frameshift entries, TR_CODONS_REF: the _frameshift_ref entries
-struct FrameRun {
-    int first = 0, per = 1;                 // the frames first .. first + per - 1 for every pair ...
-    const uint8_t *d_frame = nullptr;       // ... or (listed pairs, per 1) a frame byte per pair
-    PmxCodeTable code;
-    bool ref = false;                       // the translated side: the query's windows, or (true) the reference's
-    // codons (the _frameshift entries): the query slots are codon streams, one per strand -- first .. first + per - 1, or
-    // d_frame's byte per pair -- and a chunk's alignment is pmx_swfs with this frameshift penalty.  codons with ref: the
-    // reference slots are the streams, and the alignment is pmx_swfsc
-    bool codons = false; int frameshift = 0;
-    int min_off() const { return per == 1 && !d_frame ? first % 3 : 0; }      // the smallest offset a frame of the call reads from
-    int32_t letters(int32_t w) const { return std::max<int32_t>(1, codons ? w - 2 : (w - min_off()) / 3); }   // the longest translation of w nucleotides
-};
 struct PairsChunkBufs { uint8_t *q, *r; int32_t *qlen, *rlen; int64_t *qoff, *roff, *qsrc, *rsrc; uint8_t *ok, *sflag; const pmx_pair_t *pairs; int32_t *tw /* the translated side's W */; };
+struct SlotPlan;
+static int swfs_chunk(const pmx_config_t *cfg, const SlotPlan &plan, int64_t slots, const PairsChunkBufs &b, int32_t max_qlen, int32_t max_rlen,
+                      pmx_record_t *d_out, hipStream_t st);
+
+// What the alignment slots of a run's pairs are -- the one place that knows, and the one place a new kind of slot is added: how a pair
+// resolves to slots, how a slot's windows reach the chunk buffers, which kernel aligns the slots and how the winner is marked.
+//   PLAIN     one slot, the pair as stored: the forward-only kernels, and a forward batch pays nothing for the other kinds' existence.
+//   BYTES     one slot on the strand of the pair's byte (the _ex entries, pmx_gather_pairs_device; d_byte NULL: all forward): the
+//             gather that can reverse-complement a query window.
+//   STRANDS   the strand chosen by the entry: PMX_STRAND_REVERSE one slot, reverse-complemented; PMX_STRAND_BOTH slot 2 k
+//             pair k as stored, slot 2 k + 1 with its query reverse-complemented.  The slots fold, the strand is the mark.
+//   FRAMES    a translated side (DESIGN 2.5i the query; ref, 2.5j: the reference): that side's windows are nucleotides translated on
+//             their way into the buffers, one slot per frame first .. first + per - 1 (1, 3 or 6), or d_byte's frame per pair.  The
+//             frame is the mark.
+//   CODONS    codon streams (DESIGN 2.5k the query's, aligned by pmx_swfs; ref, 2.5m: the reference's, by pmx_swfsc) of W - 2 letters,
+//             one slot per strand first .. first + per - 1, or d_byte's strand per pair, with this frameshift penalty.
+struct SlotPlan {
+    enum Kind { PLAIN, BYTES, STRANDS, FRAMES, CODONS };
+    Kind kind = PLAIN;
+    bool ref = false;                       // FRAMES, CODONS: the translated side is the reference's
+    int first = 0, per = 1;                 // the slots' flag bytes first .. first + per - 1 for every pair ...
+    const uint8_t *d_byte = nullptr;        // ... or (listed pairs, per 1) a byte per pair
+    PmxCodeTable code; int frameshift = 0;
+    SlotPlan() {}
+    explicit SlotPlan(const uint8_t *d_strand) : kind(d_strand ? BYTES : PLAIN), d_byte(d_strand) {}       // the _ex entries: BYTES where there are strand bytes
+    void strands(int strand_mode) { kind = STRANDS; first = strand_mode == PMX_STRAND_REVERSE ? 1 : 0; per = strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
+    void set_code(const uint8_t *c) { if (c) memcpy(code.v, c, 64); else pmx_genetic_code_host(code.v); }
+    bool translates() const { return kind == FRAMES || kind == CODONS; }
+    bool folds() const { return kind >= STRANDS; }                          // the slots' records go through the fold
+    int marked() const { return kind == FRAMES ? 2 : folds() ? 1 : 0; }     // what folded records carry in their flags (fold, append_hits, emit): a frame, a strand
+    int min_off() const { return per == 1 && !d_byte ? first % 3 : 0; }     // the smallest offset a frame of the call reads from
+    // the longest translation of w nucleotides
+    int32_t letters(int32_t w) const { return std::max<int32_t>(1, kind == CODONS ? w - 2 : (w - min_off()) / 3); }
+    // the maxima in letters (mnr: the shortest reference, or NULL)
+    void to_letters(int32_t *mq, int32_t *mr, int32_t *mnr = nullptr) const
+    {
+        if (!translates()) return;
+        if (!ref) { *mq = letters(*mq); return; }
+        *mr = letters(*mr);
+        if (mnr) *mnr = letters(*mnr);
+    }
+    // cn descriptors at pc (pairs c0 .. of the run) -> per * cn slots in b's columns
+    int resolve(const pmx_pair_t *pc, int64_t c0, int64_t cn, const pmx_seqset *Q, const pmx_seqset *R, int32_t max_qlen, int32_t max_rlen,
+                const PairsChunkBufs &b, hipStream_t st) const
+    {
+        const uint8_t *byte = d_byte ? d_byte + c0 : nullptr;
+        switch (kind) {
+        case FRAMES:
+            return pmx_launch_pairs_resolve_frames(pc, byte, first, per, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                                   b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, st, ref);
+        case CODONS:
+            return pmx_launch_pairs_resolve_codons(pc, byte, first, per, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                                   b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, st, ref);
+        default:
+            return pmx_launch_pairs_resolve(pc, byte, first, per, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
+                                            b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, st);
+        }
+    }
+    // the sn slots' windows into b.q / b.r at b.qoff / b.roff; a window whose end would cross its capacity is not written
+    int gather(int64_t sn, const pmx_seqset *Q, const pmx_seqset *R, const PairsChunkBufs &b, int64_t q_cap, int64_t r_cap, hipStream_t st) const
+    {
+        switch (kind) {
+        case PLAIN:
+            return pmx_launch_pairs_gather(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.qoff, b.roff, b.q, b.r, st);
+        case FRAMES:
+            return pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
+                                                      b.sflag, b.qoff, b.roff, b.q, q_cap, b.r, r_cap, code, st, ref);
+        case CODONS:
+            return pmx_launch_pairs_gather_codons(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
+                                                  b.sflag, b.qoff, b.roff, b.q, q_cap, b.r, r_cap, code, st, ref);
+        default:
+            return pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
+                                                    b.sflag, b.qoff, b.roff, b.q, q_cap, b.r, r_cap, st);
+        }
+    }
+    // the sn slots of b aligned into rec (and stats); the error is set
+    int align(const pmx_config_t *cfg, int64_t sn, const PairsChunkBufs &b, int32_t max_qlen, int32_t max_rlen, pmx_record_t *rec, pmx_stats_t *stats,
+              hipStream_t st) const
+    {
+        if (kind == CODONS) return swfs_chunk(cfg, *this, sn, b, max_qlen, max_rlen, rec, st);
+        return run_batch_device(cfg, sn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, rec, stats, st);
+    }
+    // the per * cn slot records (and statistics) -> cn records, statistics, winners' bytes and validity bytes (each optional); mark: the
+    // winner's byte also rides in the record, as marked() says
+    int fold(const PairsChunkBufs &b, int64_t cn, bool mark, const pmx_record_t *srec, const pmx_stats_t *sst, pmx_record_t *rec, pmx_stats_t *stats,
+             uint8_t *byte_out, uint8_t *okf, hipStream_t st) const
+    {
+        return pmx_launch_pairs_fold(srec, sst, b.ok, b.sflag, cn, per, mark ? marked() : 0, rec, stats, byte_out, okf, st);
+    }
+};
 template <typename Body>
 static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first, int shape,
-                     const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body,
-                     int strand_mode = PMX_STRAND_FORWARD, const FrameRun *fr = nullptr)
+                     const SlotPlan &plan, int32_t max_qlen, int32_t max_rlen, hipStream_t st, int64_t chunk, Body body)
 {
-    const bool two = chunk < n, chosen = strand_mode != PMX_STRAND_FORWARD, stranded = d_strand != nullptr || chosen || fr != nullptr;
-    const int per = fr ? fr->per : strand_slots(strand_mode);
+    const bool two = chunk < n;
+    const int per = plan.per;
     const size_t slots = (size_t)chunk * (size_t)per;
     PairsChunkBufs B[2]; void *scan = nullptr; pmx_pair_t *gen = nullptr;
     const size_t scan_bytes = pmx_text_scan_scratch_bytes((int64_t)slots);
@@ -3779,8 +3844,8 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
                 B[s].qoff = c.take<int64_t>(slots + 1); B[s].roff = c.take<int64_t>(slots + 1);
                 B[s].qsrc = c.take<int64_t>(slots); B[s].rsrc = c.take<int64_t>(slots);
                 B[s].ok = c.take<uint8_t>(slots);
-                B[s].sflag = stranded ? c.take<uint8_t>(slots) : nullptr;
-                B[s].tw = fr ? c.take<int32_t>(slots) : nullptr;
+                B[s].sflag = plan.kind != SlotPlan::PLAIN ? c.take<uint8_t>(slots) : nullptr;
+                B[s].tw = plan.translates() ? c.take<int32_t>(slots) : nullptr;
             }
             scan = c.take<unsigned char>(scan_bytes);           // (one: the scans of all chunks run in order on one stream)
         })) return -1;
@@ -3801,29 +3866,10 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
         int rc = listed ? 0 : shape == PMX_PAIRS_TRIANGLE ? pmx_launch_all_pairs_enumerate(Q->count, first + c0, cn, gc, prep)
                                                           : pmx_launch_rect_pairs_enumerate(R->count, first + c0, cn, gc, prep);
         const int64_t sn = cn * per;                              // the chunk's alignment slots
-        if (!rc) rc = fr && fr->codons ? pmx_launch_pairs_resolve_codons(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
-                                                                         R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                                                         b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep, fr->ref)
-                    : fr       ? pmx_launch_pairs_resolve_frames(pc, fr->d_frame ? fr->d_frame + c0 : nullptr, fr->first, per, cn, Q->d_off, Q->count, Q->bytes,
-                                                                 R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                                                 b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok, b.sflag, prep, fr->ref)
-                    : chosen   ? pmx_launch_pairs_resolve_both(pc, cn, per, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                                               b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
-                    : stranded ? pmx_launch_pairs_resolve_stranded(pc, d_strand + c0, cn, Q->d_off, Q->count, Q->bytes,
-                                                                   R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                                                   b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, b.sflag, prep)
-                               : pmx_launch_pairs_resolve(pc, cn, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                                          b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok, prep);
+        if (!rc) rc = plan.resolve(pc, c0, cn, Q, R, max_qlen, max_rlen, b, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.qlen, sn, b.qoff, scan, scan_bytes, prep);
         if (!rc) rc = pmx_launch_text_offsets(b.rlen, sn, b.roff, scan, scan_bytes, prep);
-        if (!rc) rc = fr && fr->codons ? pmx_launch_pairs_gather_codons(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
-                                                                        b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep, fr->ref)
-                    : fr       ? pmx_launch_pairs_gather_translated(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.tw, b.qsrc, b.rsrc, b.ok,
-                                                                    b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, fr->code, prep, fr->ref)
-                    : stranded ? pmx_launch_pairs_gather_stranded(sn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
-                                                                  b.sflag, b.qoff, b.roff, b.q, INT64_MAX, b.r, INT64_MAX, prep)
-                               : pmx_launch_pairs_gather(cn, Q->d_buf, Q->bytes, R->d_buf, R->bytes, b.qlen, b.rlen, b.qsrc, b.rsrc, b.ok,
-                                                         b.qoff, b.roff, b.q, b.r, prep);
+        if (!rc) rc = plan.gather(sn, Q, R, b, INT64_MAX, INT64_MAX, prep);
         if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
         if (two) HIP_OR_RET(hipEventRecord(g_pws.packed[slot], prep));
         return 0;
@@ -3847,15 +3893,36 @@ static int pairs_run(const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const 
     return 0;
 }
 
-// The score road of a set batch: every chunk through run_batch_device, then the records (and statistics) of its bad pairs.
+// A run of several slots per pair reports which one won: refused where that output is `wanted` and missing.
+static int byte_out_check(const SlotPlan &plan, bool wanted, const void *byte_out)
+{
+    if (!wanted || plan.per < 2 || byte_out) return 0;
+    set_err(plan.kind == SlotPlan::FRAMES ? "null frame output: a multi-frame mode reports which frame won" : "null strand output: both strands report which one won");
+    return -1;
+}
+// What every entry over listed pairs, device or host, refuses first, in this order.  both (pmx_align_pairs_both[_device], whose plan is
+// known before its configuration is looked at): the strand output, checked ahead of the options.
+static int listed_entry_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const void *pairs, const void *out,
+                              const pmx_pairs_opts_t *opts, const SlotPlan *both = nullptr, const void *strand_out = nullptr)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
+    if (both && byte_out_check(*both, n > 0, strand_out)) return -1;
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    return check_cfg(cfg);
+}
+
+// The score road of a set batch of one slot per pair that needs no fold (PLAIN, BYTES): every chunk through run_batch_device, then the
+// records (and statistics) of its bad pairs.
 static int pairs_run_scores(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, int64_t first,
-                            const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
+                            const SlotPlan &plan, int32_t max_qlen, int32_t max_rlen,
                             pmx_record_t *d_out, pmx_stats_t *d_stats_out, hipStream_t st, int64_t chunk)
 {
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    return pairs_run(Q, R, n, d_pairs, first, d_pairs ? PMX_PAIRS_LIST : PMX_PAIRS_TRIANGLE, d_strand, max_qlen, max_rlen, st, chunk,
+    return pairs_run(Q, R, n, d_pairs, first, d_pairs ? PMX_PAIRS_LIST : PMX_PAIRS_TRIANGLE, plan, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = run_batch_device(cfg, cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
+            int rc = plan.align(cfg, cn, b, max_qlen, max_rlen, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
             if (rc) return rc;
             rc = pmx_launch_pairs_fixup(b.ok, cn, d_out + c0, stats ? d_stats_out + c0 : nullptr, st);
             if (rc) { set_err("bad-pair fix-up launch failed (%d)", rc); return rc; }
@@ -3863,25 +3930,44 @@ static int pairs_run_scores(const pmx_config_t *cfg, const pmx_seqset *Q, const 
         });
 }
 
+// The score road of a set batch over listed pairs whose slots fold (STRANDS, FRAMES, CODONS): every chunk's per * cn slots aligned into
+// scratch, then the fold straight into the caller's arrays (it writes the bad pairs' records too; per 1: the one slot's record and byte).
+static int pairs_run_folded(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
+                            const SlotPlan &plan, int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_byte_out,
+                            hipStream_t st, int64_t chunk)
+{
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    pmx_record_t *srec = nullptr; pmx_stats_t *sst = nullptr;
+    if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
+            srec = c.take<pmx_record_t>((size_t)plan.per * (size_t)chunk);
+            sst = stats ? c.take<pmx_stats_t>((size_t)plan.per * (size_t)chunk) : nullptr;
+        })) return -1;
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, plan, max_qlen, max_rlen, st, chunk,
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            int rc = plan.align(cfg, plan.per * cn, b, max_qlen, max_rlen, srec, sst, st);
+            if (rc) return rc;
+            rc = plan.fold(b, cn, false, srec, sst, d_out + c0, stats ? d_stats_out + c0 : nullptr, d_byte_out ? d_byte_out + c0 : nullptr, nullptr, st);
+            if (rc) set_err("%s fold launch failed (%d)", plan.kind == SlotPlan::FRAMES ? "frame" : "strand", rc);
+            return rc;
+        });
+}
+
 extern "C" int pmx_align_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
                                       int64_t n, const pmx_pair_t *d_pairs, int32_t max_qlen, int32_t max_rlen,
                                       pmx_record_t *d_out, pmx_stats_t *d_stats_out, void *stream, const pmx_pairs_opts_t *opts)
 {
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg)) return -1;
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts)) return -1;
     if (n == 0) return 0;
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run_scores(cfg, Q, R, n, d_pairs, 0, nullptr, max_qlen, max_rlen, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts));
+    return pairs_run_scores(cfg, Q, R, n, d_pairs, 0, SlotPlan(), max_qlen, max_rlen, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts));
 }
 
 // ---- the strand chosen by the entry ----
-// What every entry with a strand mode refuses about it, before any GPU work.
-static int strand_mode_check(const pmx_config_t *cfg, int strand_mode)
+// What every entry with a strand mode refuses about it, before any GPU work.  *plan: a mode other than PMX_STRAND_FORWARD makes the run's
+// slots the strands (forward leaves the plan what it is: PLAIN, or what side_check made of it).
+static int strand_mode_check(const pmx_config_t *cfg, int strand_mode, SlotPlan *plan)
 {
     if (strand_mode < PMX_STRAND_FORWARD || strand_mode > PMX_STRAND_BOTH) {
         set_err("strand mode %d is outside 0 .. 2 (PMX_STRAND_FORWARD, PMX_STRAND_REVERSE, PMX_STRAND_BOTH)", strand_mode); return -1;
@@ -3889,6 +3975,7 @@ static int strand_mode_check(const pmx_config_t *cfg, int strand_mode)
     if (strand_mode != PMX_STRAND_FORWARD && cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {
         set_err("a strand mode other than PMX_STRAND_FORWARD takes no PSSM matrix: a reversed query has no PSSM"); return -1;
     }
+    if (strand_mode != PMX_STRAND_FORWARD) plan->strands(strand_mode);
     return 0;
 }
 static int pairs_both_want_check(const pmx_config_t *cfg)
@@ -3900,45 +3987,21 @@ static int pairs_both_want_check(const pmx_config_t *cfg)
     return 0;
 }
 
-// The score road in PMX_STRAND_BOTH: every chunk's 2 cn slots through run_batch_device into scratch, then the fold straight into the
-// caller's arrays (it writes the bad pairs' records too).
-static int pairs_run_both(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
-                          int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_strand_out,
-                          hipStream_t st, int64_t chunk)
-{
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    pmx_record_t *srec = nullptr; pmx_stats_t *sst = nullptr;
-    if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
-            srec = c.take<pmx_record_t>(2 * (size_t)chunk);
-            sst = stats ? c.take<pmx_stats_t>(2 * (size_t)chunk) : nullptr;
-        })) return -1;
-    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
-        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = run_batch_device(cfg, 2 * cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, srec, sst, st);
-            if (rc) return rc;
-            rc = pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, 2, 0, d_out + c0, stats ? d_stats_out + c0 : nullptr, d_strand_out + c0, nullptr, st);
-            if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
-            return 0;
-        }, PMX_STRAND_BOTH);
-}
-
 extern "C" int pmx_align_pairs_both_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
                                            int64_t n, const pmx_pair_t *d_pairs, int32_t max_qlen, int32_t max_rlen,
                                            pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_strand_out, void *stream,
                                            const pmx_pairs_opts_t *opts)
 {
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
-    if (n > 0 && !d_strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || pairs_both_want_check(cfg) || strand_mode_check(cfg, PMX_STRAND_BOTH)) return -1;
+    SlotPlan plan;
+    plan.strands(PMX_STRAND_BOTH);
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts, &plan, d_strand_out) || pairs_both_want_check(cfg) ||
+        strand_mode_check(cfg, PMX_STRAND_BOTH, &plan)) return -1;
     if (n == 0) return 0;
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run_both(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats_out, d_strand_out, (hipStream_t)stream,
-                          pairs_chunk(n, max_qlen, max_rlen, opts, 2));
+    return pairs_run_folded(cfg, Q, R, n, d_pairs, plan, max_qlen, max_rlen, d_out, d_stats_out, d_strand_out, (hipStream_t)stream,
+                            pairs_chunk(n, max_qlen, max_rlen, opts, plan.per));
 }
 
 // ---- a translated side: the query's or the reference's (2.5j) ----
@@ -3946,7 +4009,7 @@ extern "C" void pmx_genetic_code_table(uint8_t table[64]) { if (table) pmx_genet
 
 // What every translated entry refuses about its frames, matrix and outputs, before any GPU work.  *fr: the run's frames, code and side
 // (ref: the _translated_ref entries).
-static int frames_check(const pmx_config_t *cfg, int frame_mode, const uint8_t *d_frame, const uint8_t *code, FrameRun *fr, bool ref = false)
+static int frames_check(const pmx_config_t *cfg, int frame_mode, const uint8_t *d_frame, const uint8_t *code, SlotPlan *fr, bool ref = false)
 {
     if (frame_mode < 0 || frame_mode > PMX_FRAMES_ALL) {
         set_err("frame mode %d is outside 0 .. 8 (a frame 0 .. 5, PMX_FRAMES_FORWARD, PMX_FRAMES_REVERSE, PMX_FRAMES_ALL)", frame_mode); return -1;
@@ -3963,35 +4026,12 @@ static int frames_check(const pmx_config_t *cfg, int frame_mode, const uint8_t *
                 "then run pmx_align_batch_cigar_device over the packed buffers", ref ? "pmx_gather_pairs_translated_ref_device" : "pmx_gather_pairs_translated_device");
         return -1;
     }
-    fr->ref = ref;
+    fr->kind = SlotPlan::FRAMES; fr->ref = ref;
     fr->first = frame_mode <= 5 ? frame_mode : frame_mode == PMX_FRAMES_REVERSE ? 3 : 0;
     fr->per = frame_mode <= 5 ? 1 : frame_mode == PMX_FRAMES_ALL ? 6 : 3;
-    fr->d_frame = d_frame;
-    if (code) memcpy(fr->code.v, code, 64); else pmx_genetic_code_host(fr->code.v);
+    fr->d_byte = d_frame;
+    fr->set_code(code);
     return 0;
-}
-
-// The score road of a translated batch: every chunk's per * cn slots through run_batch_device into scratch, then the fold straight into
-// the caller's arrays (it writes the bad pairs' records too; per 1: the one slot's record).
-static int pairs_run_frames(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
-                            int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out,
-                            hipStream_t st, int64_t chunk, const FrameRun &fr)
-{
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    pmx_record_t *srec = nullptr; pmx_stats_t *sst = nullptr;
-    if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
-            srec = c.take<pmx_record_t>((size_t)fr.per * (size_t)chunk);
-            sst = stats ? c.take<pmx_stats_t>((size_t)fr.per * (size_t)chunk) : nullptr;
-        })) return -1;
-    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
-        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = run_batch_device(cfg, fr.per * cn, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, srec, sst, st);
-            if (rc) return rc;
-            rc = pmx_launch_pairs_fold_frames(srec, sst, b.ok, b.sflag, cn, fr.per, 0, d_out + c0, stats ? d_stats_out + c0 : nullptr,
-                                              d_frame_out ? d_frame_out + c0 : nullptr, nullptr, st);
-            if (rc) { set_err("frame fold launch failed (%d)", rc); return rc; }
-            return 0;
-        }, PMX_STRAND_FORWARD, &fr);
 }
 
 // Both device entries over listed pairs: ref false pmx_align_pairs_translated_device, true pmx_align_pairs_translated_ref_device.
@@ -4001,19 +4041,15 @@ static int align_pairs_frames_device(const pmx_config_t *cfg, const pmx_seqset_t
                                      pmx_record_t *d_out, pmx_stats_t *d_stats_out, uint8_t *d_frame_out, void *stream,
                                      const pmx_pairs_opts_t *opts, bool ref)
 {
-    FrameRun fr;
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frames_check(cfg, frame_mode, d_frame, code, &fr, ref)) return -1;
-    if (n > 0 && fr.per > 1 && !d_frame_out) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
+    SlotPlan fr;
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts) || frames_check(cfg, frame_mode, d_frame, code, &fr, ref) ||
+        byte_out_check(fr, n > 0, d_frame_out)) return -1;
     if (n == 0) return 0;
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run_frames(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_stats_out, d_frame_out, (hipStream_t)stream,
-                            pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
+    return pairs_run_folded(cfg, Q, R, n, d_pairs, fr, max_qlen, max_rlen, d_out, d_stats_out, d_frame_out, (hipStream_t)stream,
+                            pairs_chunk(n, max_qlen, max_rlen, opts, fr.per));
 }
 
 extern "C" int pmx_align_pairs_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -4034,11 +4070,12 @@ extern "C" int pmx_align_pairs_translated_ref_device(const pmx_config_t *cfg, co
     return align_pairs_frames_device(cfg, Q, R, n, d_pairs, d_frame, frame_mode, code, max_qlen, max_rlen, d_out, d_stats_out, d_frame_out, stream, opts, true);
 }
 
-// Both gather hooks: ref false pmx_gather_pairs_translated_device, true pmx_gather_pairs_translated_ref_device.
-static int gather_pairs_frames_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
-                                      const uint8_t *d_frame, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
-                                      uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
-                                      uint8_t *d_ok, void *stream, bool ref)
+// The five gather hooks (pmx_gather_pairs_device: BYTES; _translated[_ref]: FRAMES; _codons[_ref]: CODONS): one slot per pair with the
+// pair's byte (d_byte NULL: all 0), resolved, scanned and gathered into the caller's buffers up to their capacities.
+static int gather_pairs_hook(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
+                             SlotPlan::Kind kind, bool ref, const uint8_t *d_byte, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                             uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
+                             uint8_t *d_ok, void *stream)
 {
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
@@ -4053,23 +4090,24 @@ static int gather_pairs_frames_device(const pmx_seqset_t *Q, const pmx_seqset_t 
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     hipStream_t st = (hipStream_t)stream;
-    PmxCodeTable ct;
-    if (code) memcpy(ct.v, code, 64); else pmx_genetic_code_host(ct.v);
-    int32_t *qlen = nullptr, *rlen = nullptr, *tw = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
+    SlotPlan plan;
+    plan.kind = kind; plan.ref = ref; plan.d_byte = d_byte;
+    if (plan.translates()) plan.set_code(code);
+    PairsChunkBufs b = {d_qout, d_rout, nullptr, nullptr, d_qoff, d_roff, nullptr, nullptr, nullptr, nullptr, d_pairs, nullptr};
+    void *scan = nullptr;
     const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
     if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
-            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2); tw = c.take<int32_t>((size_t)n);
-            qsrc = c.take<int64_t>((size_t)n); rsrc = c.take<int64_t>((size_t)n);
-            ok = c.take<uint8_t>((size_t)n); sflag = c.take<uint8_t>((size_t)n);
+            b.qlen = c.take<int32_t>((size_t)n + 2); b.rlen = c.take<int32_t>((size_t)n + 2);
+            b.tw = plan.translates() ? c.take<int32_t>((size_t)n) : nullptr;
+            b.qsrc = c.take<int64_t>((size_t)n); b.rsrc = c.take<int64_t>((size_t)n);
+            b.ok = c.take<uint8_t>((size_t)n); b.sflag = c.take<uint8_t>((size_t)n);
             scan = c.take<unsigned char>(scan_bytes);
         })) return -1;
-    if (d_ok) ok = d_ok;
-    int rc = pmx_launch_pairs_resolve_frames(d_pairs, d_frame, 0, 1, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                             qlen, rlen, tw, qsrc, rsrc, ok, sflag, st, ref);
-    if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_pairs_gather_translated(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, tw, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
-                                                     d_qout, q_capacity, d_rout, r_capacity, ct, st, ref);
+    if (d_ok) b.ok = d_ok;
+    int rc = plan.resolve(d_pairs, 0, n, Q, R, max_qlen, max_rlen, b, st);
+    if (!rc) rc = pmx_launch_text_offsets(b.qlen, n, d_qoff, scan, scan_bytes, st);
+    if (!rc) rc = pmx_launch_text_offsets(b.rlen, n, d_roff, scan, scan_bytes, st);
+    if (!rc) rc = plan.gather(n, Q, R, b, q_capacity, r_capacity, st);
     if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
     return 0;
 }
@@ -4079,7 +4117,7 @@ extern "C" int pmx_gather_pairs_translated_device(const pmx_seqset_t *Q, const p
                                                   uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
                                                   uint8_t *d_ok, void *stream)
 {
-    return gather_pairs_frames_device(Q, R, n, d_pairs, d_frame, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, false);
+    return gather_pairs_hook(Q, R, n, d_pairs, SlotPlan::FRAMES, false, d_frame, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream);
 }
 
 extern "C" int pmx_gather_pairs_translated_ref_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
@@ -4087,7 +4125,7 @@ extern "C" int pmx_gather_pairs_translated_ref_device(const pmx_seqset_t *Q, con
                                                       uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
                                                       uint8_t *d_ok, void *stream)
 {
-    return gather_pairs_frames_device(Q, R, n, d_pairs, d_frame, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, true);
+    return gather_pairs_hook(Q, R, n, d_pairs, SlotPlan::FRAMES, true, d_frame, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream);
 }
 
 // ---- frameshift-aware translated search: codon streams through pmx_swfs ----
@@ -4095,7 +4133,7 @@ extern "C" int32_t pmx_frameshift_max_window(void) { return PMX_FRAMESHIFT_MAX_W
 
 // What every _frameshift entry refuses about its strand mode, penalty, matrix, mode, width and outputs, before any GPU work.  *fr: the
 // run's strands (d_strand: a strand byte per pair, listed pairs only), code and penalty.
-static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint8_t *d_strand, int32_t frameshift, const uint8_t *code, FrameRun *fr,
+static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint8_t *d_strand, int32_t frameshift, const uint8_t *code, SlotPlan *fr,
                             bool traceback = false /* the _frameshift_cigar entries: the outputs are theirs to check */,
                             bool ref = false /* the _frameshift_ref entries: the strands and the stream are the reference's */)
 {
@@ -4121,11 +4159,10 @@ static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint
     if (cfg->matrix->size > max_msize) {
         set_err("the frameshift kernel keeps the matrix in LDS: %d symbols exceed %d", cfg->matrix->size, max_msize); return -1;
     }
-    fr->ref = ref; fr->codons = true; fr->frameshift = frameshift;
-    fr->first = strand_mode == PMX_STRAND_REVERSE ? 1 : 0;
-    fr->per = strand_slots(strand_mode);
-    fr->d_frame = d_strand;
-    if (code) memcpy(fr->code.v, code, 64); else pmx_genetic_code_host(fr->code.v);
+    fr->strands(strand_mode);                                     // (first and per of the mode; forward: strand 0, one slot)
+    fr->kind = SlotPlan::CODONS; fr->ref = ref; fr->frameshift = frameshift;
+    fr->d_byte = d_strand;
+    fr->set_code(code);
     return 0;
 }
 // max_qlen bounds N = W - 2, the rows the kernel sees.  ref (the _frameshift_ref entries): max_qlen bounds the protein's letters, the
@@ -4146,16 +4183,16 @@ static int frameshift_rows_check(int32_t max_qlen, bool ref = false)
     }
     return 0;
 }
-// The search and top-K entries: the rows' bound of the side `translated` names, nothing for the other entries.
-static int codons_rows_check(int translated, int32_t max_qlen)
+// The search and top-K entries: the rows' bound of the plan's streams, nothing for the other kinds.
+static int codons_rows_check(const SlotPlan &plan, int32_t max_qlen)
 {
-    return translated == TR_CODONS || translated == TR_CODONS_REF ? frameshift_rows_check(max_qlen, translated == TR_CODONS_REF) : 0;
+    return plan.kind == SlotPlan::CODONS ? frameshift_rows_check(max_qlen, plan.ref) : 0;
 }
 
 // A chunk's alignment: `slots` codon streams of b against their proteins into d_out.  Streams longer than one strip keep their
 // boundary columns in scratch, at most 256 MiB of it: the launcher then runs the slots in parts.  fr.ref: the streams are the
 // reference slots and the kernel is pmx_swfsc, whose strips are cut from the protein's rows.
-static int swfs_chunk(const pmx_config_t *cfg, const FrameRun &fr, int64_t slots, const PairsChunkBufs &b, int32_t max_qlen, int32_t max_rlen,
+static int swfs_chunk(const pmx_config_t *cfg, const SlotPlan &fr, int64_t slots, const PairsChunkBufs &b, int32_t max_qlen, int32_t max_rlen,
                       pmx_record_t *d_out, hipStream_t st)
 {
     DevMat dm;
@@ -4174,44 +4211,21 @@ static int swfs_chunk(const pmx_config_t *cfg, const FrameRun &fr, int64_t slots
     return 0;
 }
 
-// The score road of a frameshift batch over listed pairs: every chunk's per * cn streams through pmx_swfs into scratch, then the strand
-// fold straight into the caller's arrays (it writes the bad pairs' records too; per 1: the one slot's record and strand).
-static int pairs_run_codons(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
-                            int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out,
-                            hipStream_t st, int64_t chunk, const FrameRun &fr)
-{
-    pmx_record_t *srec = nullptr;
-    if (scratch_carve(SCR_PSRCH, [&](Carver &c) { srec = c.take<pmx_record_t>((size_t)fr.per * (size_t)chunk); })) return -1;
-    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
-        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            int rc = swfs_chunk(cfg, fr, fr.per * cn, b, max_qlen, max_rlen, srec, st);
-            if (rc) return rc;
-            rc = pmx_launch_pairs_fold_strands(srec, nullptr, b.ok, b.sflag, cn, fr.per, 0, d_out + c0, nullptr,
-                                               d_strand_out ? d_strand_out + c0 : nullptr, nullptr, st);
-            if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
-            return 0;
-        }, PMX_STRAND_FORWARD, &fr);
-}
-
 // Both device entries over listed pairs: ref false pmx_align_pairs_frameshift_device, true pmx_align_pairs_frameshift_ref_device.
 static int align_pairs_codons_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
                                      int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
                                      int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
                                      pmx_record_t *d_out, uint8_t *d_strand_out, void *stream, const pmx_pairs_opts_t *opts, bool ref)
 {
-    FrameRun fr;
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, false, ref)) return -1;
-    if (n > 0 && fr.per > 1 && !d_strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    SlotPlan fr;
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, false, ref) ||
+        byte_out_check(fr, n > 0, d_strand_out)) return -1;
     if (n == 0) return 0;
     if (frameshift_rows_check(max_qlen, ref) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, false)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run_codons(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, (hipStream_t)stream,
-                            pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
+    return pairs_run_folded(cfg, Q, R, n, d_pairs, fr, max_qlen, max_rlen, d_out, nullptr, d_strand_out, (hipStream_t)stream,
+                            pairs_chunk(n, max_qlen, max_rlen, opts, fr.per));
 }
 
 extern "C" int pmx_align_pairs_frameshift_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -4271,7 +4285,7 @@ static int frameshift_trace_bound_check(int32_t max_qlen, int32_t max_rlen)
 static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
                                   int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats,
                                   int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off,
-                                  hipStream_t st, int64_t chunk, const FrameRun &fr)
+                                  hipStream_t st, int64_t chunk, const SlotPlan &fr)
 {
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
@@ -4294,7 +4308,7 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
             t.carve(c, part);
             local_off = c.take<int64_t>((size_t)part + 1); pair_qoff = c.take<int64_t>((size_t)part + 1); pair_roff = c.take<int64_t>((size_t)part + 1);
         })) return -1;
-    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, nullptr, max_qlen, max_rlen, st, chunk,
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, fr, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             for (int64_t p0 = 0; p0 < cn; p0 += part) {
                 const int64_t pn = std::min<int64_t>(part, cn - p0), s0 = per * p0, g0 = c0 + p0;
@@ -4302,7 +4316,7 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
                 int rc = pmx_launch_swfs_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, trace, srec + s0, st, &g_last_kernel);
                 if (rc) { set_err(rc < 0 ? "frameshift trace kernel launch failed: %s" : "the frameshift trace kernel does not take this batch%s", rc < 0 ? hipGetErrorString((hipError_t)(-rc)) : ""); return -1; }
                 uint8_t *won = d_strand_out ? d_strand_out + g0 : nullptr;
-                rc = pmx_launch_pairs_fold_strands(srec + s0, nullptr, b.ok + s0, b.sflag + s0, pn, per, 0, d_out + g0, nullptr, won, nullptr, st);
+                rc = pmx_launch_pairs_fold(srec + s0, nullptr, b.ok + s0, b.sflag + s0, pn, per, 0, d_out + g0, nullptr, won, nullptr, st);
                 if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
                 rc = pmx_launch_walkfs(dm.d, pn, per, per == 2 ? won : nullptr, b.q, b.qoff + s0, b.r, b.roff + s0, max_rlen, d_out + g0,
                                        (const uint8_t *)trace, (long long)tps, t.ops, t.nops, t.textlen, pair_qoff, pair_roff,
@@ -4312,7 +4326,7 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
                 if (rc) return rc;
             }
             return 0;
-        }, PMX_STRAND_FORWARD, &fr);
+        });
 }
 
 extern "C" int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -4322,14 +4336,9 @@ extern "C" int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, 
                                                        char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off,
                                                        void *stream, const pmx_pairs_opts_t *opts)
 {
-    FrameRun fr;
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, true) ||
-        frameshift_cigar_outputs_check(cfg, d_stats, d_cigar_text, cigar_capacity, d_cigar_off)) return -1;
-    if (n > 0 && fr.per > 1 && !d_strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    SlotPlan fr;
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, true) ||
+        frameshift_cigar_outputs_check(cfg, d_stats, d_cigar_text, cigar_capacity, d_cigar_off) || byte_out_check(fr, n > 0, d_strand_out)) return -1;
     if (n == 0) return 0;
     if (frameshift_rows_check(max_qlen) || frameshift_trace_bound_check(max_qlen, max_rlen) ||
         pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats != nullptr, true)) return -1;
@@ -4339,52 +4348,12 @@ extern "C" int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, 
                                   d_cigar_off, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
 }
 
-// Both gather hooks: ref false pmx_gather_pairs_codons_device, true pmx_gather_pairs_codons_ref_device.
-static int gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
-                                      const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
-                                      uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
-                                      uint8_t *d_ok, void *stream, bool ref)
-{
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
-    if (!d_qoff || !d_roff || (n > 0 && (!d_pairs || !d_qout || !d_rout))) { set_err("null buffer"); return -1; }
-    if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
-    if (n == 0) return 0;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
-    if (Q->dev != dev || R->dev != dev) {
-        set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev != dev ? Q->dev : R->dev, dev); return -1;
-    }
-    StreamGuard guard(stream);
-    if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    hipStream_t st = (hipStream_t)stream;
-    PmxCodeTable ct;
-    if (code) memcpy(ct.v, code, 64); else pmx_genetic_code_host(ct.v);
-    int32_t *qlen = nullptr, *rlen = nullptr, *tw = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
-    const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
-    if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
-            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2); tw = c.take<int32_t>((size_t)n);
-            qsrc = c.take<int64_t>((size_t)n); rsrc = c.take<int64_t>((size_t)n);
-            ok = c.take<uint8_t>((size_t)n); sflag = c.take<uint8_t>((size_t)n);
-            scan = c.take<unsigned char>(scan_bytes);
-        })) return -1;
-    if (d_ok) ok = d_ok;
-    int rc = pmx_launch_pairs_resolve_codons(d_pairs, d_strand, 0, 1, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                             qlen, rlen, tw, qsrc, rsrc, ok, sflag, st, ref);
-    if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_pairs_gather_codons(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, tw, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
-                                                 d_qout, q_capacity, d_rout, r_capacity, ct, st, ref);
-    if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
-    return 0;
-}
-
 extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
                                               const uint8_t *d_strand, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
                                               uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
                                               uint8_t *d_ok, void *stream)
 {
-    return gather_pairs_codons_device(Q, R, n, d_pairs, d_strand, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, false);
+    return gather_pairs_hook(Q, R, n, d_pairs, SlotPlan::CODONS, false, d_strand, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream);
 }
 
 extern "C" int pmx_gather_pairs_codons_ref_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
@@ -4392,7 +4361,7 @@ extern "C" int pmx_gather_pairs_codons_ref_device(const pmx_seqset_t *Q, const p
                                                   uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
                                                   uint8_t *d_ok, void *stream)
 {
-    return gather_pairs_codons_device(Q, R, n, d_pairs, d_strand, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream, true);
+    return gather_pairs_hook(Q, R, n, d_pairs, SlotPlan::CODONS, true, d_strand, code, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream);
 }
 
 // ---- strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device) ----
@@ -4416,7 +4385,7 @@ static int pairs_run_cigar(const pmx_config_t *cfg, const DevMat &dm, const pmx_
                            const pmx_pair_t *d_pairs, const uint8_t *d_strand, int32_t max_qlen, int32_t max_rlen,
                            pmx_record_t *d_out, int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off, hipStream_t st, int64_t chunk)
 {
-    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, d_strand, max_qlen, max_rlen, st, chunk,
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, SlotPlan(d_strand), max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             CigarChunkOf set; set.ok = b.ok; set.beg = d_beg ? d_beg + 2 * c0 : nullptr; set.continues = c0 > 0;
             const int rc = cigar_device_run(cfg, dm, cn, b.q, b.qoff, b.r, b.roff, max_qlen, max_rlen, 0, d_out + c0,
@@ -4433,7 +4402,7 @@ static int pairs_ex_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_
 {
     const int64_t chunk = pairs_chunk(n, max_qlen, max_rlen, opts);
     if (!(cfg->want & PMX_WANT_CIGAR))
-        return pairs_run_scores(cfg, Q, R, n, d_pairs, 0, d_strand, max_qlen, max_rlen, d_out, d_stats_out, st, chunk);
+        return pairs_run_scores(cfg, Q, R, n, d_pairs, 0, SlotPlan(d_strand), max_qlen, max_rlen, d_out, d_stats_out, st, chunk);
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
     if (!cigar_device_eligible(cfg, dm, chunk, max_qlen, max_rlen)) { set_err_no_cigar_road(); return -1; }
@@ -4445,11 +4414,7 @@ extern "C" int pmx_align_pairs_ex_device(const pmx_config_t *cfg, const pmx_seqs
                                          pmx_record_t *d_out, pmx_stats_t *d_stats_out, int32_t *d_beg,
                                          char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off, void *stream, const pmx_pairs_opts_t *opts)
 {
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!d_pairs || !d_out)) { set_err("null pairs or records"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || pairs_ex_outputs_check(cfg, d_beg, d_cigar_text, cigar_capacity, d_cigar_off)) return -1;
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts) || pairs_ex_outputs_check(cfg, d_beg, d_cigar_text, cigar_capacity, d_cigar_off)) return -1;
     if (n == 0) return 0;
     if (pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats_out != nullptr, true)) return -1;
     StreamGuard guard(stream);
@@ -4463,36 +4428,7 @@ extern "C" int pmx_gather_pairs_device(const pmx_seqset_t *Q, const pmx_seqset_t
                                        uint8_t *d_qout, int64_t q_capacity, int64_t *d_qoff, uint8_t *d_rout, int64_t r_capacity, int64_t *d_roff,
                                        uint8_t *d_ok, void *stream)
 {
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0 || q_capacity < 0 || r_capacity < 0) { set_err("negative n or capacity"); return -1; }
-    if (!d_qoff || !d_roff || (n > 0 && (!d_pairs || !d_qout || !d_rout))) { set_err("null buffer"); return -1; }
-    if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
-    if (n == 0) return 0;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
-    if (Q->dev != dev || R->dev != dev) {
-        set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev != dev ? Q->dev : R->dev, dev); return -1;
-    }
-    StreamGuard guard(stream);
-    if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    hipStream_t st = (hipStream_t)stream;
-    int32_t *qlen = nullptr, *rlen = nullptr; int64_t *qsrc = nullptr, *rsrc = nullptr; uint8_t *ok = nullptr, *sflag = nullptr; void *scan = nullptr;
-    const size_t scan_bytes = pmx_text_scan_scratch_bytes(n);
-    if (scratch_carve(SCR_PAIRS, [&](Carver &c) {
-            qlen = c.take<int32_t>((size_t)n + 2); rlen = c.take<int32_t>((size_t)n + 2);
-            qsrc = c.take<int64_t>((size_t)n); rsrc = c.take<int64_t>((size_t)n);
-            ok = c.take<uint8_t>((size_t)n); sflag = c.take<uint8_t>((size_t)n);
-            scan = c.take<unsigned char>(scan_bytes);
-        })) return -1;
-    if (d_ok) ok = d_ok;
-    int rc = pmx_launch_pairs_resolve_stranded(d_pairs, d_strand, n, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes, max_qlen, max_rlen,
-                                               qlen, rlen, qsrc, rsrc, ok, sflag, st);
-    if (!rc) rc = pmx_launch_text_offsets(qlen, n, d_qoff, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_text_offsets(rlen, n, d_roff, scan, scan_bytes, st);
-    if (!rc) rc = pmx_launch_pairs_gather_stranded(n, Q->d_buf, Q->bytes, R->d_buf, R->bytes, qlen, rlen, qsrc, rsrc, ok, sflag, d_qoff, d_roff,
-                                                   d_qout, q_capacity, d_rout, r_capacity, st);
-    if (rc) { set_err("pair materialisation failed (%d)", rc); return rc; }
-    return 0;
+    return gather_pairs_hook(Q, R, n, d_pairs, SlotPlan::BYTES, false, d_strand, nullptr, max_qlen, max_rlen, d_qout, q_capacity, d_qoff, d_rout, r_capacity, d_roff, d_ok, stream);
 }
 
 // The all-pairs window [first, first + count) of a set: 0, or -1 with the cause.
@@ -4521,7 +4457,7 @@ extern "C" int pmx_align_all_pairs_device(const pmx_config_t *cfg, const pmx_seq
     if (pairs_check(cfg, S, S, opts, max_len, max_len, d_stats_out != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run_scores(cfg, S, S, count, nullptr, first, nullptr, max_len, max_len, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(count, max_len, max_len, opts));
+    return pairs_run_scores(cfg, S, S, count, nullptr, first, SlotPlan(), max_len, max_len, d_out, d_stats_out, (hipStream_t)stream, pairs_chunk(count, max_len, max_len, opts));
 }
 
 extern "C" int pmx_all_pairs_enumerate_device(int64_t nseq, int64_t first, int64_t count, pmx_pair_t *d_pairs, void *stream)
@@ -4650,13 +4586,10 @@ static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_
                       pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts, bool ex,
                       bool both = false, uint8_t *strand_out = nullptr)
 {
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
-    if (both && n > 0 && !strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg)) return -1;
-    if (both && (pairs_both_want_check(cfg) || strand_mode_check(cfg, PMX_STRAND_BOTH))) return -1;
+    SlotPlan plan;                                        // both: the two strands; else PLAIN until the strand bytes are on the device
+    if (both) plan.strands(PMX_STRAND_BOTH);
+    if (listed_entry_check(cfg, Q, R, n, pairs, out, opts, both ? &plan : nullptr, strand_out)) return -1;
+    if (both && (pairs_both_want_check(cfg) || strand_mode_check(cfg, PMX_STRAND_BOTH, &plan))) return -1;
     if (ex && pairs_ex_outputs_check(cfg, beg, cigar_buf, 0, cigar_off)) return -1;
     const bool cigar = ex && (cfg->want & PMX_WANT_CIGAR) != 0;
     if (cigar) { *cigar_buf = nullptr; cigar_off[0] = 0; }
@@ -4708,7 +4641,7 @@ static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_
     }
     if (both) {
         dstrand = (uint8_t *)dp + up_bytes;               // (the winners' strands, written by the fold)
-        int rc = pairs_run_both(&cfg_s, Q, R, n, dp, q32, r32, drec, dst, dstrand, st, pairs_chunk(n, q32, r32, opts, 2));
+        int rc = pairs_run_folded(&cfg_s, Q, R, n, dp, plan, q32, r32, drec, dst, dstrand, st, pairs_chunk(n, q32, r32, opts, plan.per));
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(strand_out, dstrand, (size_t)n, hipMemcpyDeviceToHost, st));
         return pairs_copy_back(n, drec, dst, out, stats_out, !host_offsets, st);
@@ -4768,55 +4701,86 @@ extern "C" int pmx_align_pairs_both(const pmx_config_t *cfg, const pmx_seqset_t 
 }
 
 
-// The host entries over listed pairs with a translated side (ref false: pmx_align_pairs_translated, true: pmx_align_pairs_translated_ref):
-// pairs_host's score road -- validation against host offsets, the upload of 32 (+ 1) bytes per pair, the records back -- with the
-// frames' run in the middle.  A pair without a frame is found on the device only, so the records' flags are always scanned.
+// Listed pairs over a set with host offsets, the descriptors below `end` good: the first whose query window has fewer than three
+// nucleotides -- no codon stream --, refused with its number; 0 when there is none.  ref (the _frameshift_ref entries): S is the
+// reference set and the window the reference's.
+static int short_window_check(const pmx_seqset *S, const pmx_pair_t *pairs, int64_t end, bool ref = false)
+{
+    for (int64_t k = 0; k < end; ++k) {
+        const pmx_pair_t &p = pairs[k];
+        const int64_t idx = ref ? p.r : p.q, beg = ref ? p.r_beg : p.q_beg, len = ref ? p.r_len : p.q_len;
+        const int64_t W = len < 0 ? S->h_off[(size_t)idx + 1] - S->h_off[(size_t)idx] - beg : len;
+        if (W < 3) { set_err("pair %lld: %s: a window of %lld nucleotides has no codon", (long long)k, ref ? "reference" : "query", (long long)W); return -1; }
+    }
+    return 0;
+}
+
+// What the host entries over listed pairs with a translated side (FRAMES, CODONS) share, behind their own argument checks: pairs_host's
+// score road -- the bytes' validation, the descriptors against host offsets, the maxima in letters, the upload of 32 (+ 1) bytes per
+// pair, the maxima of wrapped sets from the device -- then run(cfg, d_pairs, max_qlen, max_rlen, d_rec, d_stats, d_byte_out, st), then
+// the winners' bytes and the records back.  A pair without a frame or a codon is found on the device only, so the records' flags are
+// always scanned.  lens_check(max_qlen, max_rlen, known): what the entry refuses about the maxima, asked before any GPU work (known:
+// the sets have host offsets) and again for wrapped sets.  hint: the run's configuration carries the sort hint of the host lengths.
+template <typename LensCheck, typename Run>
+static int translated_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *pairs,
+                                 const uint8_t *byte_in, SlotPlan &plan, pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *byte_out,
+                                 const pmx_pairs_opts_t *opts, bool ex, bool hint, LensCheck lens_check, Run run)
+{
+    const bool codons = plan.kind == SlotPlan::CODONS;
+    if (byte_in)
+        for (int64_t k = 0; k < n; ++k)
+            if (byte_in[k] > (codons ? 1 : 5)) {
+                set_err(codons ? "pair %lld: strand byte %d is neither 0 nor 1" : "pair %lld: frame byte %d is outside 0 .. 5", (long long)k, (int)byte_in[k]);
+                return -1;
+            }
+    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
+    int32_t q32 = 1, r32 = 1, mnr = INT32_MAX;
+    if (host_offsets) {
+        const PairScan s = scan_pairs(Q, R, pairs, 0, n);
+        if (codons && short_window_check(plan.ref ? R : Q, pairs, s.bad >= 0 ? s.bad : n, plan.ref)) return -1;
+        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
+        q32 = (int32_t)s.mq; r32 = (int32_t)s.mr; mnr = (int32_t)s.mnr;
+        plan.to_letters(&q32, &r32, &mnr);
+    }
+    if (lens_check(q32, r32, host_offsets) || pairs_check(cfg, Q, R, opts, q32, r32, stats_out != nullptr, ex)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
+    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the bytes in, then out
+    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
+        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
+    uint8_t *dbin = (uint8_t *)dp + up_bytes, *dbout = dbin + n;
+    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (byte_in) { HIP_OR_RET(hipMemcpyAsync(dbin, byte_in, (size_t)n, hipMemcpyHostToDevice, st)); plan.d_byte = dbin; }
+    pmx_config_t cfg_s = *cfg;
+    if (host_offsets) { if (hint) cfg_s = with_sort_hint(cfg, mnr, r32, n); }
+    else {
+        if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
+        plan.to_letters(&q32, &r32);
+        if (lens_check(q32, r32, true)) return -1;
+    }
+    const int rc = run(&cfg_s, dp, q32, r32, drec, dst, dbout, st);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    if (byte_out) HIP_OR_RET(hipMemcpyAsync(byte_out, dbout, (size_t)n, hipMemcpyDeviceToHost, st));
+    return pairs_copy_back(n, drec, dst, out, stats_out, true, st);
+}
+
+// The host entries over listed pairs with a translated side (ref false: pmx_align_pairs_translated, true: pmx_align_pairs_translated_ref).
 static int align_pairs_frames_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
                                    int64_t n, const pmx_pair_t *pairs, const uint8_t *frame, int frame_mode, const uint8_t *code,
                                    pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *frame_out, const pmx_pairs_opts_t *opts, bool ref)
 {
-    FrameRun fr;
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frames_check(cfg, frame_mode, frame, code, &fr, ref)) return -1;
-    if (n > 0 && fr.per > 1 && !frame_out) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
+    SlotPlan fr;
+    if (listed_entry_check(cfg, Q, R, n, pairs, out, opts) || frames_check(cfg, frame_mode, frame, code, &fr, ref) ||
+        byte_out_check(fr, n > 0, frame_out)) return -1;
     if (n == 0) return 0;
-    if (frame)
-        for (int64_t k = 0; k < n; ++k)
-            if (frame[k] > 5) { set_err("pair %lld: frame byte %d is outside 0 .. 5", (long long)k, (int)frame[k]); return -1; }
-    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
-    int64_t mq = 1, mr = 1, mnr = INT32_MAX;
-    if (host_offsets) {
-        const PairScan s = scan_pairs(Q, R, pairs, 0, n);
-        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
-        mq = s.mq; mr = s.mr; mnr = s.mnr;
-    }
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (host_offsets) { if (ref) { mr = fr.letters((int32_t)mr); mnr = fr.letters((int32_t)mnr); } else mq = fr.letters((int32_t)mq); }
-    if (pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr)) return -1;
-    static thread_local HostStreams hs;
-    if (hs.init(false)) return -1;
-    const hipStream_t st = hs.comp;
-    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
-    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the frame bytes in, then out
-    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
-        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
-    uint8_t *dfin = (uint8_t *)dp + up_bytes, *dfout = dfin + n;
-    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (frame) { HIP_OR_RET(hipMemcpyAsync(dfin, frame, (size_t)n, hipMemcpyHostToDevice, st)); fr.d_frame = dfin; }
-    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
-    pmx_config_t cfg_s = *cfg;
-    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
-    else {
-        if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
-        if (ref) r32 = fr.letters(r32); else q32 = fr.letters(q32);
-    }
-    const int rc = pairs_run_frames(&cfg_s, Q, R, n, dp, q32, r32, drec, dst, dfout, st, pairs_chunk(n, q32, r32, opts, fr.per), fr);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    if (frame_out) HIP_OR_RET(hipMemcpyAsync(frame_out, dfout, (size_t)n, hipMemcpyDeviceToHost, st));
-    return pairs_copy_back(n, drec, dst, out, stats_out, true, st);
+    return translated_pairs_host(cfg, Q, R, n, pairs, frame, fr, out, stats_out, frame_out, opts, false, true,
+        [](int32_t, int32_t, bool) { return 0; },
+        [&](const pmx_config_t *c, const pmx_pair_t *dp, int32_t q32, int32_t r32, pmx_record_t *drec, pmx_stats_t *dst, uint8_t *dfout, hipStream_t st) {
+            return pairs_run_folded(c, Q, R, n, dp, fr, q32, r32, drec, dst, dfout, st, pairs_chunk(n, q32, r32, opts, fr.per));
+        });
 }
 
 extern "C" int pmx_align_pairs_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -4833,24 +4797,9 @@ extern "C" int pmx_align_pairs_translated_ref(const pmx_config_t *cfg, const pmx
     return align_pairs_frames_host(cfg, Q, R, n, pairs, frame, frame_mode, code, out, stats_out, frame_out, opts, true);
 }
 
-// Listed pairs over a set with host offsets, the descriptors below `end` good: the first whose query window has fewer than three
-// nucleotides -- no codon stream --, refused with its number; 0 when there is none.  ref (the _frameshift_ref entries): S is the
-// reference set and the window the reference's.
-static int short_window_check(const pmx_seqset *S, const pmx_pair_t *pairs, int64_t end, bool ref = false)
-{
-    for (int64_t k = 0; k < end; ++k) {
-        const pmx_pair_t &p = pairs[k];
-        const int64_t idx = ref ? p.r : p.q, beg = ref ? p.r_beg : p.q_beg, len = ref ? p.r_len : p.q_len;
-        const int64_t W = len < 0 ? S->h_off[(size_t)idx + 1] - S->h_off[(size_t)idx] - beg : len;
-        if (W < 3) { set_err("pair %lld: %s: a window of %lld nucleotides has no codon", (long long)k, ref ? "reference" : "query", (long long)W); return -1; }
-    }
-    return 0;
-}
-
-// The host entries over listed pairs of the frameshift-aware alignment, laid out as align_pairs_frames_host.  A window shorter than three
-// nucleotides is found on the device only, so the records' flags are always scanned.  traceback (pmx_align_pairs_frameshift_cigar, DESIGN
-// 2.5l): the traceback road in place of the score road, and the text tail of pairs_host -- a text buffer sized by estimate, and one more
-// run at the exact size where the text did not fit.
+// The host entries over listed pairs of the frameshift-aware alignment.  traceback (pmx_align_pairs_frameshift_cigar): the
+// traceback road in place of the score road, and the text tail of pairs_host -- a text buffer sized by estimate, and one more run at the
+// exact size where the text did not fit.
 static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
                                        int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
                                        int32_t frameshift, const uint8_t *code, pmx_record_t *out, uint8_t *strand_out,
@@ -4858,69 +4807,32 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
                                        pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off,
                                        bool ref = false /* pmx_align_pairs_frameshift_ref (no traceback): the stream is the reference's */)
 {
-    FrameRun fr;
-    if (!Q || !R) { set_err("null sequence set"); return -1; }
-    if (n < 0) { set_err("negative n"); return -1; }
-    if (n > 0 && (!pairs || !out)) { set_err("null pairs or records"); return -1; }
-    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr, traceback, ref) ||
-        (traceback && frameshift_cigar_outputs_check(cfg, stats_out, cigar_buf, 0, cigar_off))) return -1;
-    if (n > 0 && fr.per > 1 && !strand_out) { set_err("null strand output: both strands report which one won"); return -1; }
+    SlotPlan fr;
+    if (listed_entry_check(cfg, Q, R, n, pairs, out, opts) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr, traceback, ref) ||
+        (traceback && frameshift_cigar_outputs_check(cfg, stats_out, cigar_buf, 0, cigar_off)) || byte_out_check(fr, n > 0, strand_out)) return -1;
     if (traceback) { *cigar_buf = nullptr; cigar_off[0] = 0; }
     if (n == 0) return 0;
-    if (strand)
-        for (int64_t k = 0; k < n; ++k)
-            if (strand[k] > 1) { set_err("pair %lld: strand byte %d is neither 0 nor 1", (long long)k, (int)strand[k]); return -1; }
-    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
-    int64_t mq = 1, mr = 1;
-    if (host_offsets) {
-        const PairScan s = scan_pairs(Q, R, pairs, 0, n);
-        if (short_window_check(ref ? R : Q, pairs, s.bad >= 0 ? s.bad : n, ref)) return -1;
-        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
-        mq = ref ? s.mq : fr.letters((int32_t)s.mq); mr = ref ? fr.letters((int32_t)s.mr) : s.mr;
-    }
-    if (frameshift_rows_check((int32_t)mq, ref) || (traceback && host_offsets && frameshift_trace_bound_check((int32_t)mq, (int32_t)mr)) ||
-        pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr, traceback)) return -1;
-    static thread_local HostStreams hs;
-    if (hs.init(false)) return -1;
-    const hipStream_t st = hs.comp;
-    const bool stats = traceback && (cfg->want & PMX_WANT_STATS) != 0;
-    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
-    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the strand bytes in, then out
-    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
-        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
-    uint8_t *dsin = (uint8_t *)dp + up_bytes, *dsout = dsin + n;
-    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (strand) { HIP_OR_RET(hipMemcpyAsync(dsin, strand, (size_t)n, hipMemcpyHostToDevice, st)); fr.d_frame = dsin; }
-    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
-    if (!host_offsets) {
-        if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
-        if (ref) r32 = fr.letters(r32); else q32 = fr.letters(q32);
-        if (frameshift_rows_check(q32, ref) || (traceback && frameshift_trace_bound_check(q32, r32))) return -1;
-    }
-    const int64_t chunk = pairs_chunk(n, q32, r32, opts, fr.per);
-    if (!traceback) {
-        const int rc = pairs_run_codons(cfg, Q, R, n, dp, q32, r32, drec, dsout, st, chunk, fr);
-        if (rc) { (void)hipStreamSynchronize(st); return rc; }
-        if (strand_out) HIP_OR_RET(hipMemcpyAsync(strand_out, dsout, (size_t)n, hipMemcpyDeviceToHost, st));
-        return pairs_copy_back(n, drec, nullptr, out, nullptr, true, st);
-    }
     int64_t capacity = 32 * n + 256;                      // (the run-length text of a hit is a few runs; a batch of noise runs twice)
     DevBuf<int64_t> dtoff; DevBuf<int32_t> dbeg; DevBuf<char> dtext;
-    if (dtoff.try_alloc((size_t)n + 1) || (beg && dbeg.try_alloc(2 * (size_t)n)) || dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    for (int pass = 0; pass < 2; ++pass) {
-        const int rc = pairs_run_codons_cigar(cfg, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr);
-        if (rc) { (void)hipStreamSynchronize(st); return rc; }
-        HIP_OR_RET(hipMemcpyAsync(cigar_off, dtoff.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
-        HIP_OR_RET(hipStreamSynchronize(st));
-        if (cigar_off[n] <= capacity) break;
-        capacity = cigar_off[n];                          // the text did not fit the estimate -- again with the exact size
-        (void)hipFree(dtext.p); dtext.p = nullptr;
-        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    }
-    if (strand_out) HIP_OR_RET(hipMemcpyAsync(strand_out, dsout, (size_t)n, hipMemcpyDeviceToHost, st));
-    const int rc = pairs_copy_back(n, drec, dst, out, stats_out, true, st);
-    if (rc) return rc;
+    const int rc = translated_pairs_host(cfg, Q, R, n, pairs, strand, fr, out, stats_out, strand_out, opts, traceback, false,
+        [&](int32_t mq, int32_t mr, bool known) { return frameshift_rows_check(mq, ref) || (traceback && known && frameshift_trace_bound_check(mq, mr)) ? -1 : 0; },
+        [&](const pmx_config_t *c, const pmx_pair_t *dp, int32_t q32, int32_t r32, pmx_record_t *drec, pmx_stats_t *dst, uint8_t *dsout, hipStream_t st) -> int {
+            const int64_t chunk = pairs_chunk(n, q32, r32, opts, fr.per);
+            if (!traceback) return pairs_run_folded(c, Q, R, n, dp, fr, q32, r32, drec, nullptr, dsout, st, chunk);
+            if (dtoff.try_alloc((size_t)n + 1) || (beg && dbeg.try_alloc(2 * (size_t)n)) || dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+            for (int pass = 0; pass < 2; ++pass) {
+                const int rc = pairs_run_codons_cigar(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr);
+                if (rc) return rc;
+                HIP_OR_RET(hipMemcpyAsync(cigar_off, dtoff.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
+                HIP_OR_RET(hipStreamSynchronize(st));
+                if (cigar_off[n] <= capacity) break;
+                capacity = cigar_off[n];                          // the text did not fit the estimate -- again with the exact size
+                (void)hipFree(dtext.p); dtext.p = nullptr;
+                if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+            }
+            return 0;
+        });
+    if (rc || !traceback) return rc;
     if (beg) HIP_OR_RET(hipMemcpy(beg, dbeg.p, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost));
     TextBuf text;
     char *dst_text = text.grow((size_t)cigar_off[n]);
@@ -4983,7 +4895,7 @@ extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *
         (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)count, (void **)&dst, SCR_PST))) return -1;
     const pmx_config_t cfg_s = with_sort_hint(cfg, m.mnr, m.mq, count);      // (wrapped sets: no host lengths yet, and no hint from them)
     if (!host_offsets && window_device_lens(cfg, S, S, &m, st)) return -1;
-    const int rc = pairs_run_scores(&cfg_s, S, S, count, nullptr, first, nullptr, m.mq, m.mq, drec, dst, st, pairs_chunk(count, m.mq, m.mq, opts));
+    const int rc = pairs_run_scores(&cfg_s, S, S, count, nullptr, first, SlotPlan(), m.mq, m.mq, drec, dst, st, pairs_chunk(count, m.mq, m.mq, opts));
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     return pairs_copy_back(count, drec, dst, out, stats_out, !host_offsets, st);
 }
@@ -5074,34 +4986,28 @@ struct PairHitBufs { HitCols hit; int64_t capacity; int64_t *counts, *first_bad;
 // A chunk's alignment for the entries that keep its records in scratch (set search, top-K): the records (and statistics) of the chunk's
 // pairs and, when the entry chooses the strand, those of its alignment slots before the fold and the folded validity bytes.
 struct ChunkAlign {
-    bool stats, chosen; int per; const FrameRun *fr;              // fr != nullptr: the slots are frames of a translated side, or (fr->codons) the strands' codon streams
+    bool stats; const SlotPlan &plan;
     pmx_record_t *crec = nullptr, *srec = nullptr; pmx_stats_t *cst = nullptr, *sst = nullptr; uint8_t *okf = nullptr;
-    ChunkAlign(const pmx_config_t *cfg, int strand_mode, const FrameRun *frames = nullptr)
-        : stats((cfg->want & PMX_WANT_STATS) != 0), chosen(strand_mode != PMX_STRAND_FORWARD || frames != nullptr),
-          per(frames ? frames->per : strand_slots(strand_mode)), fr(frames) {}
-    int marked() const { return fr && !fr->codons ? 2 : chosen ? 1 : 0; }       // what the chunk's records carry in their flags (append_hits, emit): a frame, a strand
+    ChunkAlign(const pmx_config_t *cfg, const SlotPlan &p) : stats((cfg->want & PMX_WANT_STATS) != 0), plan(p) {}
     void carve(Carver &c, int64_t chunk)
     {
         crec = c.take<pmx_record_t>((size_t)chunk);
         cst = stats ? c.take<pmx_stats_t>((size_t)chunk) : nullptr;
-        if (!chosen) return;                                    // the slots' records before the fold, the folded validity bytes
-        srec = c.take<pmx_record_t>((size_t)chunk * per);
-        sst = stats ? c.take<pmx_stats_t>((size_t)chunk * per) : nullptr;
+        if (!plan.folds()) return;                              // the slots' records before the fold, the folded validity bytes
+        srec = c.take<pmx_record_t>((size_t)chunk * plan.per);
+        sst = stats ? c.take<pmx_stats_t>((size_t)chunk * plan.per) : nullptr;
         okf = c.take<uint8_t>((size_t)chunk);
     }
-    // The cn pairs of b into crec / cst: forward, the alignment and the bad pairs' fix-up; chosen strand, per * cn slots aligned and folded
-    // to cn records that carry their strand.  first_bad != nullptr: the lowest index of a bad pair, the chunk's first pair being p0.
+    // The cn pairs of b into crec / cst: a plan without a fold, the alignment and the bad pairs' fix-up; else per * cn slots aligned and
+    // folded to cn records that carry their strand or frame.  first_bad != nullptr: the lowest index of a bad pair, the chunk's first pair being p0.
     int run(const pmx_config_t *cfg, const PairsChunkBufs &b, int64_t cn, int32_t max_qlen, int32_t max_rlen, int64_t p0, int64_t *first_bad,
             hipStream_t st) const
     {
-        int rc = fr && fr->codons ? swfs_chunk(cfg, *fr, cn * per, b, max_qlen, max_rlen, srec, st)
-                                  : run_batch_device(cfg, cn * per, b.q, b.qoff, 0, b.r, b.roff, max_qlen, max_rlen, chosen ? srec : crec, chosen ? sst : cst, st);
+        const bool folds = plan.folds();
+        int rc = plan.align(cfg, cn * plan.per, b, max_qlen, max_rlen, folds ? srec : crec, folds ? sst : cst, st);
         if (rc) return rc;
-        rc = fr && fr->codons ? pmx_launch_pairs_fold_strands(srec, nullptr, b.ok, b.sflag, cn, per, 1, crec, nullptr, nullptr, okf, st)
-           : fr     ? pmx_launch_pairs_fold_frames(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
-           : chosen ? pmx_launch_pairs_fold_strands(srec, sst, b.ok, b.sflag, cn, per, 1, crec, cst, nullptr, okf, st)
-                    : pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
-        if (!rc && first_bad) rc = pmx_launch_pairs_first_bad(chosen ? okf : b.ok, cn, p0, first_bad, st);
+        rc = folds ? plan.fold(b, cn, true, srec, sst, crec, cst, nullptr, okf, st) : pmx_launch_pairs_fixup(b.ok, cn, crec, cst, st);
+        if (!rc && first_bad) rc = pmx_launch_pairs_first_bad(folds ? okf : b.ok, cn, p0, first_bad, st);
         if (rc) set_err("bad-pair fix-up or strand fold of a chunk failed (%d)", rc);
         return rc;
     }
@@ -5110,9 +5016,9 @@ struct ChunkAlign {
 // n > 0 pairs behind the checks; asynchronous on `st`.  index0: the absolute number of the run's first pair (what d_hit_index counts from).
 static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int shape, int64_t first, int64_t n,
                             const pmx_pair_t *d_pairs, int64_t index0, int32_t max_qlen, int32_t max_rlen, int32_t min_score,
-                            const PairHitBufs &o, hipStream_t st, int64_t chunk, int strand_mode = PMX_STRAND_FORWARD, const FrameRun *fr = nullptr)
+                            const PairHitBufs &o, hipStream_t st, int64_t chunk, const SlotPlan &plan)
 {
-    ChunkAlign A(cfg, strand_mode, fr);
+    ChunkAlign A(cfg, plan);
     int64_t *cidx = nullptr, *ccnt = nullptr; void *sel = nullptr;
     const size_t sel_bytes = pmx_select_scratch_bytes(chunk, 0, PMX_HITS_BY_INDEX);
     if (scratch_carve(SCR_PSRCH, [&](Carver &c) {
@@ -5121,22 +5027,22 @@ static int search_pairs_run(const pmx_config_t *cfg, const pmx_seqset *Q, const 
             sel = c.take<unsigned char>(sel_bytes);
         })) return -1;
     HIP_OR_RET(hipMemsetAsync(o.counts, 0, 2 * sizeof(int64_t), st));
-    return pairs_run(Q, R, n, d_pairs, first, shape, nullptr, max_qlen, max_rlen, st, chunk,
+    return pairs_run(Q, R, n, d_pairs, first, shape, plan, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             int rc = A.run(cfg, b, cn, max_qlen, max_rlen, index0 + c0, o.first_bad, st);
             if (rc) return rc;
             rc = pmx_launch_select(A.crec, cn, min_score, 0, PMX_HITS_BY_INDEX, cidx, cn, ccnt, sel, st);
             if (!rc) rc = pmx_launch_pairs_append_hits(cidx, ccnt, cn, o.capacity, index0 + c0, b.pairs, A.crec, A.cst,
-                                                       o.hit.pairs, o.hit.index, o.hit.recs, o.hit.stats, o.counts, st, o.hit.strand, A.marked());
+                                                       o.hit.pairs, o.hit.index, o.hit.recs, o.hit.stats, o.counts, st, o.hit.strand, plan.marked());
             if (rc) { set_err("hit compaction of a chunk failed (%d)", rc); return rc; }
             return 0;
-        }, strand_mode, fr);
+        });
 }
 
-// The side an entry translates, checked and turned into the run's FrameRun.  TR_NONE: nothing.  TR_QUERY / TR_REF: frame_mode and code.
+// The side an entry translates, checked and turned into the run's SlotPlan.  TR_NONE: nothing.  TR_QUERY / TR_REF: frame_mode and code.
 // TR_CODONS / TR_CODONS_REF (the _frameshift / _frameshift_ref entries): *strand_mode and frameshift; the strands become the run's
 // slots, so the mode the pipeline below sees is PMX_STRAND_FORWARD.
-static int side_check(const pmx_config_t *cfg, int translated, int frame_mode, const uint8_t *code, int *strand_mode, int32_t frameshift, FrameRun *fr)
+static int side_check(const pmx_config_t *cfg, int translated, int frame_mode, const uint8_t *code, int *strand_mode, int32_t frameshift, SlotPlan *fr)
 {
     if (translated == TR_NONE) return 0;
     if (translated != TR_CODONS && translated != TR_CODONS_REF) return frames_check(cfg, frame_mode, nullptr, code, fr, translated == TR_REF);
@@ -5154,26 +5060,25 @@ static int search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
                                int64_t capacity, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
                                int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
-    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
+    SlotPlan plan;
     if (search_pairs_shape_check(Q, &R, shape, first, n, d_pairs)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) ||
-        search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
-    if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
-    if (translated == TR_CODONS_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null strand output: both strands report which one won"); return -1; }
+    if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &plan) ||
+        search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode, &plan)) return -1;
+    if (byte_out_check(plan, plan.ref && capacity > 0, d_hit_strand)) return -1;       // (only the reference-side entries ask for the column)
     if (n == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
         return 0;
     }
     if (!d_counts) { set_err("null counts"); return -1; }
-    if (codons_rows_check(translated, max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    if (codons_rows_check(plan, max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const PairHitBufs o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_counts, nullptr};
     return search_pairs_run(cfg, Q, R, shape, first, n, d_pairs, first, max_qlen, max_rlen, min_score, o, (hipStream_t)stream,
-                            pairs_chunk(n, max_qlen, max_rlen, opts, fr ? fr->per : strand_slots(strand_mode)), strand_mode, fr);
+                            pairs_chunk(n, max_qlen, max_rlen, opts, plan.per), plan);
 }
 
 extern "C" int pmx_search_pairs_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int shape,
@@ -5296,7 +5201,7 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
                              const pmx_pair_t *pairs, const pmx_pair_search_opts_t *opts, int strand_mode, bool with_strand, pmx_pair_hits_t **result,
                              int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
-    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
+    SlotPlan plan;
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
     if (!opts) { set_err("null opts"); return -1; }
@@ -5307,8 +5212,8 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) || search_pairs_want_check(cfg, stats) ||
-        strand_mode_check(cfg, strand_mode)) return -1;
+    if (side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &plan) || search_pairs_want_check(cfg, stats) ||
+        strand_mode_check(cfg, strand_mode, &plan)) return -1;
     HostHits hh;
     // the result: one block -- header, descriptors, indices, records, statistics (, strand bytes)
     auto publish = [&]() -> int {
@@ -5326,16 +5231,15 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
     SetLens m;
     if (host_offsets && listed) {
         const PairScan s = scan_pairs(Q, R, pairs, 0, n);
-        if ((translated == TR_CODONS || translated == TR_CODONS_REF) && short_window_check(translated == TR_CODONS_REF ? R : Q, pairs, s.bad >= 0 ? s.bad : n, translated == TR_CODONS_REF)) return -1;
+        if (plan.kind == SlotPlan::CODONS && short_window_check(plan.ref ? R : Q, pairs, s.bad >= 0 ? s.bad : n, plan.ref)) return -1;
         if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
         m.mq = (int32_t)s.mq; m.mr = (int32_t)s.mr; m.mnr = (int32_t)s.mnr;
     } else if (host_offsets && window_host_lens(Q, R, shape, first, n, &m)) return -1;
-    auto to_letters = [&]() { if (!fr) return; if (fr->ref) { m.mr = fr->letters(m.mr); m.mnr = fr->letters(m.mnr); } else m.mq = fr->letters(m.mq); };
+    auto to_letters = [&]() { plan.to_letters(&m.mq, &m.mr, &m.mnr); };
     to_letters();
-    const bool find_bad = !host_offsets || fr != nullptr;
-    const int per = fr ? fr->per : strand_slots(strand_mode);
+    const bool find_bad = !host_offsets || plan.translates();
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if (codons_rows_check(translated, m.mq) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
+    if (codons_rows_check(plan, m.mq) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
@@ -5363,19 +5267,19 @@ static int search_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, con
             if (!host_offsets) {
                 if (device_maxlens(Q, R, dp, sn, &m.mq, &m.mr, st)) return -1;
                 to_letters();
-                if (pssm_batch_check(cfg->matrix, m.mq, m.mq) || codons_rows_check(translated, m.mq)) return -1;
+                if (pssm_batch_check(cfg->matrix, m.mq, m.mq) || codons_rows_check(plan, m.mq)) return -1;
             }
         }
         const int64_t p0 = listed ? s0 : first + s0;     // the slice's first pair in the enumeration
         const PairHitBufs o = {d, cap, dcnt, find_bad ? dcnt + 2 : nullptr};
         int64_t h[3] = {0, 0, 0};
         int rc = search_pairs_run(&cfg_s, Q, R, shape, listed ? 0 : p0, sn, dp, p0, m.mq, m.mr, opts->min_score, o, st,
-                                  pairs_chunk(sn, m.mq, m.mr, &popts, per), strand_mode, fr);
+                                  pairs_chunk(sn, m.mq, m.mr, &popts, plan.per), plan);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
         if (find_bad && h[2] != -1) {
-            set_err(fr ? "pair %lld: bad descriptor (index, window or length) or no frame to translate" : "pair %lld: bad descriptor (index, window or length)",
+            set_err(plan.translates() ? "pair %lld: bad descriptor (index, window or length) or no frame to translate" : "pair %lld: bad descriptor (index, window or length)",
                     (long long)(h[2] - (listed ? 0 : first)));
             return -1;
         }
@@ -5514,24 +5418,24 @@ static const int64_t TOPK_CHUNK_MAX = (int64_t)1 << 26;            // (a chunk's
 // nq > 0 rows behind the checks; asynchronous on `st`.
 static int topk_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t max_rlen,
                     int32_t min_score, int32_t k, int skip_self, const TopkOut &o, hipStream_t st, const pmx_pairs_opts_t *opts,
-                    int strand_mode = PMX_STRAND_FORWARD, const FrameRun *fr = nullptr)
+                    const SlotPlan &plan)
 {
     const int64_t nr = R->count;
     if (nr == 0) return topk_no_pairs(nq, o, st);
     const int64_t n = nq * nr, first = q_first * nr;
-    ChunkAlign A(cfg, strand_mode, fr);
-    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, A.per), TOPK_CHUNK_MAX);
+    ChunkAlign A(cfg, plan);
+    const int64_t chunk = std::min<int64_t>(pairs_chunk(n, max_qlen, max_rlen, opts, plan.per), TOPK_CHUNK_MAX);
     TopkLists L;
     L.shape(chunk, nr, nq, k);
     if (scratch_carve(SCR_PTOPK, [&](Carver &c) { A.carve(c, chunk); L.carve(c, nq, A.stats); })) return -1;
     if (L.clear(nq, st)) return -1;
-    int rc = pairs_run(Q, R, n, nullptr, first, PMX_PAIRS_RECT, nullptr, max_qlen, max_rlen, st, chunk,
+    int rc = pairs_run(Q, R, n, nullptr, first, PMX_PAIRS_RECT, plan, max_qlen, max_rlen, st, chunk,
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
             const int rc = A.run(cfg, b, cn, max_qlen, max_rlen, first + c0, o.first_bad, st);
             return rc ? rc : L.merge(A.crec, A.cst, first + c0, cn, nr, q_first, min_score, skip_self, st);
-        }, strand_mode, fr);
+        });
     if (rc) return rc;
-    return L.finish(nq, q_first, nr, o, A.marked(), st);
+    return L.finish(nq, q_first, nr, o, plan.marked(), st);
 }
 
 // Both device entries; the plain one passes PMX_STRAND_FORWARD and no strand array, and runs what it always ran.
@@ -5542,15 +5446,14 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
                               void *stream, const pmx_pairs_opts_t *opts, int strand_mode, uint8_t *d_hit_strand,
                               int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
-    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
+    SlotPlan plan;
     if (topk_shape_check(Q, &R, q_first, nq, k, skip_self)) return -1;
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (capacity > 0 && !d_hit_recs) { set_err("null hit records with capacity > 0"); return -1; }
     if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
-    if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) ||
-        search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode)) return -1;
-    if (translated == TR_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null frame output: a multi-frame mode reports which frame won"); return -1; }
-    if (translated == TR_CODONS_REF && frames.per > 1 && capacity > 0 && !d_hit_strand) { set_err("null strand output: both strands report which one won"); return -1; }
+    if (check_cfg(cfg) || side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &plan) ||
+        search_pairs_want_check(cfg, d_hit_stats != nullptr) || strand_mode_check(cfg, strand_mode, &plan)) return -1;
+    if (byte_out_check(plan, plan.ref && capacity > 0, d_hit_strand)) return -1;       // (only the reference-side entries ask for the column)
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), (hipStream_t)stream));
         if (d_row_off) HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), (hipStream_t)stream));
@@ -5558,11 +5461,11 @@ static int search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, co
     }
     if (!d_row_off) { set_err("null row offsets"); return -1; }
     if (!d_counts) { set_err("null counts"); return -1; }
-    if (codons_rows_check(translated, max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
+    if (codons_rows_check(plan, max_qlen) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_hit_stats != nullptr)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const TopkOut o = {{d_hit_pairs, d_hit_index, d_hit_recs, d_hit_stats, d_hit_strand}, capacity, d_row_off, d_row_passing, d_counts, nullptr};
-    return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts, strand_mode, fr);
+    return topk_run(cfg, Q, R, q_first, nq, max_qlen, max_rlen, min_score, k, skip_self, o, (hipStream_t)stream, opts, plan);
 }
 
 extern "C" int pmx_search_topk_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t q_first, int64_t nq,
@@ -5682,7 +5585,7 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
                             const pmx_topk_opts_t *opts, int strand_mode, bool with_strand, pmx_topk_hits_t **result,
                             int translated = TR_NONE, int frame_mode = 0, const uint8_t *code = nullptr, int32_t frameshift = 0)
 {
-    FrameRun frames; const FrameRun *fr = translated ? &frames : nullptr;
+    SlotPlan plan;
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
     if (!opts) { set_err("null opts"); return -1; }
@@ -5691,8 +5594,8 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     if (opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
     if (check_cfg(cfg)) return -1;
     const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &frames) || search_pairs_want_check(cfg, stats) ||
-        strand_mode_check(cfg, strand_mode)) return -1;
+    if (side_check(cfg, translated, frame_mode, code, &strand_mode, frameshift, &plan) || search_pairs_want_check(cfg, stats) ||
+        strand_mode_check(cfg, strand_mode, &plan)) return -1;
     HostHits hh;
     // the result: one block -- header, row offsets, passing counts, descriptors, indices, records, statistics (, strand bytes)
     auto publish = [&]() -> int {
@@ -5713,11 +5616,11 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
     const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
     SetLens m;
     if (host_offsets && nr > 0 && window_host_lens(Q, R, PMX_PAIRS_RECT, q_first * nr, nq * nr, &m)) return -1;
-    auto to_letters = [&]() { if (!fr) return; if (fr->ref) { m.mr = fr->letters(m.mr); m.mnr = fr->letters(m.mnr); } else m.mq = fr->letters(m.mq); };
+    auto to_letters = [&]() { plan.to_letters(&m.mq, &m.mr, &m.mnr); };
     to_letters();
-    const bool find_bad = !host_offsets || fr != nullptr;
+    const bool find_bad = !host_offsets || plan.translates();
     const pmx_pairs_opts_t popts = {opts->chunk_pairs};
-    if (codons_rows_check(translated, m.mq) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
+    if (codons_rows_check(plan, m.mq) || pairs_check(cfg, Q, R, &popts, m.mq, m.mr, stats)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
@@ -5745,12 +5648,12 @@ static int search_topk_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, cons
         const int64_t sn = std::min<int64_t>(slice, nq - s0);
         const TopkOut o = {d, sn * ks, doff, dpass, dcnt, find_bad ? dcnt + 3 : nullptr};
         int64_t h[4] = {0, 0, 0, 0};
-        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, m.mq, m.mr, opts->min_score, opts->k, opts->skip_self, o, st, &popts, strand_mode, fr);
+        int rc = topk_run(&cfg_s, Q, R, q_first + s0, sn, m.mq, m.mr, opts->min_score, opts->k, opts->skip_self, o, st, &popts, plan);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
         if (find_bad && h[3] != -1) {
-            set_err(fr ? "pair %lld (%lld, %lld): bad descriptor (index, window or length) or no frame to translate"
+            set_err(plan.translates() ? "pair %lld (%lld, %lld): bad descriptor (index, window or length) or no frame to translate"
                        : "pair %lld (%lld, %lld): bad descriptor (index, window or length)", (long long)(h[3] - q_first * nr), (long long)(h[3] / nr), (long long)(h[3] % nr));
             return -1;
         }

@@ -261,20 +261,20 @@ int pmx_launch_gather_refs(const uint8_t *rbuf, const int64_t *roff, long long n
                            uint8_t *out, const int64_t *ooff, long long out_cap, hipStream_t stream);
 
 // Sequence-set batches (pmx_pairs.hip; semantics: include/parasail_amd.h).  All asynchronous on `stream`; 0 launched, <0 HIP error.
-// resolve: qlen / rlen hold n + 2 entries (the scan's input), qsrc / rsrc / ok n; a bad pair is 1 x 1 with ok = 0.
-int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
+// resolve: n descriptors -> per * n alignment slots (per 1 or 2), slot per * k + i on the strand s0 + i, s0 = strand ? strand[k] : first
+// (strand: n bytes or NULL).  qlen / rlen hold per * n + 2 entries (the scan's input), qsrc / rsrc / ok / sflag per * n; sflag = the
+// slot's strand, NULL where none is kept (the plain entries: strand NULL, first 0, per 1).  A bad descriptor and a strand s0 + per > 2
+// make every slot of the pair 1 x 1 with ok = 0.  The _ex entries: a strand byte per pair, per 1.  The strand chosen by the entry
+// (DESIGN 2.5h): per 1 all reverse (first 1); per 2 slot 2 k forward, 2 k + 1 reverse (first 0).
+int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
+                             const int64_t *q_off, long long q_count, long long q_bytes,
                              const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                             int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, hipStream_t stream);
+                             int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream);
 int pmx_launch_pairs_gather(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                             const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
                             const int64_t *qoff, const int64_t *roff, uint8_t *qout, uint8_t *rout, hipStream_t stream);
 int pmx_launch_pairs_fixup(const uint8_t *ok, long long n, pmx_record_t *rec, pmx_stats_t *stats /* may be NULL */, hipStream_t stream);
-// With strands (the _ex entries).  strand: n bytes or NULL (all forward); sflag[k] = pair k's strand, a byte above 1 makes the pair bad.
-int pmx_launch_pairs_resolve_stranded(const pmx_pair_t *pairs, const uint8_t *strand, long long n,
-                                      const int64_t *q_off, long long q_count, long long q_bytes,
-                                      const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                                      int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream);
-// The gather that can reverse-complement the query side; a window whose end would cross q_cap / r_cap is not written.
+// The gather that can reverse-complement the query side (sflag); a window whose end would cross q_cap / r_cap is not written.
 int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                                      const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
                                      const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
@@ -295,22 +295,18 @@ int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts
                                  pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *counts, hipStream_t stream,
                                  uint8_t *hit_strand = nullptr /* optional: the strand byte of every hit written */,
                                  int marked = 0 /* 1: the records carry PMX_FLAG_STRAND1, 2: their frame in PMX_FLAG_FRAME_MASK; to be taken out */);
-// The strand chosen by the entry.  resolve_both: n descriptors -> per * n slots (per 1: all reverse; per 2: slot 2 k forward,
-// 2 k + 1 reverse), arrays sized per * n (+ 2 for the lengths).  fold_strands: per * n slot records (statistics optional) -> n records,
-// statistics, strand bytes (optional) and validity bytes (optional); bad pairs get their record here; mark: PMX_FLAG_STRAND1 is set in
-// the records of reverse winners.
-int pmx_launch_pairs_resolve_both(const pmx_pair_t *pairs, long long n, int per, const int64_t *q_off, long long q_count, long long q_bytes,
-                                  const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                                  int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t stream);
-int pmx_launch_pairs_fold_strands(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
-                                  long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *strand, uint8_t *okf, hipStream_t stream);
+// fold: per * n slot records (statistics optional) -> n records, statistics, the winners' sflag bytes -- a strand or a frame -- (optional)
+// and validity bytes (optional): of the slots with ok != 0 the highest score, the lowest slot on a tie; a pair without one gets its
+// bad-pair record here.  mark 1: PMX_FLAG_STRAND1 is set in the records of winners with a byte other than 0; mark 2: the byte rides
+// in PMX_FLAG_FRAME_MASK (the `marked` of pmx_launch_pairs_append_hits).
+int pmx_launch_pairs_fold(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
+                          long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *byte, uint8_t *okf, hipStream_t stream);
 int pmx_launch_pairs_first_bad(const uint8_t *ok, long long n, long long index0, int64_t *first_bad, hipStream_t stream);
 // A translated side (the query; 2.5j, ref = true: the reference).  resolve_frames: n descriptors -> per * n slots, slot
 // per * k + i the frame (frame ? frame[k] : first + i); the translated side's length = the translated length L, tw = its nucleotide
 // window's length W, its source = the window's first byte, sflag = the frame byte, ok = the slot is a candidate (a frame that does not
 // exist, and every slot of a bad pair, is a 1 x 1 placeholder with ok = 0); arrays sized per * n (+ 2 for the lengths).
-// gather_translated: the stranded gather with codon -> letter on the translated side.  fold_frames: per * n slot records -> n records,
-// statistics, frame bytes (optional) and validity bytes (optional); mark: the frame rides in the record.
+// gather_translated: the stranded gather with codon -> letter on the translated side.  The slots' records fold with pmx_launch_pairs_fold.
 struct PmxCodeTable { uint8_t v[64]; };
 void pmx_genetic_code_host(uint8_t table[64]);
 int pmx_launch_pairs_resolve_frames(const pmx_pair_t *pairs, const uint8_t *frame, int first, int per, long long n,
@@ -323,12 +319,10 @@ int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long l
                                        const uint8_t *ok, const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
                                        uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t stream,
                                        bool ref = false);
-int pmx_launch_pairs_fold_frames(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
-                                 long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *frame, uint8_t *okf, hipStream_t stream);
 // Codon streams (the _frameshift entries).  resolve_codons: n descriptors -> per * n slots, one per strand (strand ? strand[k]
 // : per == 2 ? forward, reverse : first); the query's length = the stream's N = W - 2, tw = W, sflag = the strand; W < 3, a strand byte
 // above 1 and N > max_qlen make every slot a 1 x 1 placeholder with ok = 0.  gather_codons: letter p of a query slot = the codon at
-// oriented bytes p .. p + 2.  The slots' records fold with pmx_launch_pairs_fold_strands.  ref (the _frameshift_ref
+// oriented bytes p .. p + 2.  The slots' records fold with pmx_launch_pairs_fold.  ref (the _frameshift_ref
 // entries): the sides exchanged -- the reference's window becomes the stream, N <= max_rlen, and the query is copied.
 int pmx_launch_pairs_resolve_codons(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
                                     const int64_t *q_off, long long q_count, long long q_bytes,

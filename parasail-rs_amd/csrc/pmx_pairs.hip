@@ -1,7 +1,8 @@
 // pmx_pairs.hip -- sequence-set batches: pair descriptors (index + window into device-resident sequence sets) -> the packed chunk
 // buffers every alignment kernel reads (semantics: include/parasail_amd.h; pipeline: pmx_api.hip).
 //
-//   pmx_pairs_resolve_kernel        descriptor -> two lengths, two source byte offsets, a validity byte (a bad pair: 1 x 1)
+//   pmx_pairs_resolve_kernel        descriptor -> `per` alignment slots (1 or 2, one per strand): two lengths, two source byte offsets, a
+//                                   validity byte, a strand byte (a bad pair: 1 x 1 placeholders)
 //   (pmx_launch_text_offsets        the chunk's packed qoff / roff from the lengths: pmx_sort.hip)
 //   pmx_pairs_gather_kernel         the windows into the chunk's packed buffers, a 16-lane group per sequence
 //   pmx_pairs_fixup_kernel          the records (and statistics) of bad pairs, after the chunk's alignment
@@ -14,17 +15,19 @@
 //   pmx_pairs_advance_hits_kernel   one thread, behind the append: the running total and the two public counts
 //   pmx_pairs_first_bad_kernel      the lowest absolute index of a bad pair (host entry over wrapped sets)
 // and, for the entries with strands and CIGAR output (pmx_align_pairs_ex[_device], pmx_gather_pairs_device):
-//   pmx_pairs_resolve_stranded_kernel   the resolve step with the pair's strand byte
 //   pmx_pairs_gather_stranded_kernel    the gather that can reverse-complement a query window
 //   pmx_pairs_fixup_cigar_kernel        bad pairs on the CIGAR road: record, empty text, begins
 //   pmx_text_rebase_kernel              a chunk's text offsets behind the running total of the chunks before it
-// and, for the entries that choose the strand themselves (pmx_align_pairs_both[_device], the _stranded searches):
-//   pmx_pairs_resolve_both_kernel       one descriptor -> `per` alignment slots: per 1 the reverse strand, per 2 forward then reverse
-//   pmx_pairs_fold_strands_kernel       the slots' records (and statistics) -> one record, statistics and strand per logical pair
-// and, for a translated side (the _translated entries: the query; the _translated_ref entries: the reference, 2.5j):
+// and, for every entry whose pairs are more than one slot or whose slot is chosen by the entry (both strands; a translated
+// side, 2.5i / 2.5j; codon streams, 2.5k / 2.5m):
+//   pmx_pairs_fold_kernel               the slots' records (and statistics) -> one record, statistics and strand or frame per logical pair
+// and, for a translated side (the _translated entries: the query; the _translated_ref entries: the reference):
 //   pmx_pairs_resolve_frames_kernel     one descriptor -> `per` slots (1, 3 or 6), one per frame: translated length, nucleotide window
 //   pmx_pairs_gather_translated_kernel  the gather that turns codons of that side's window into amino acids, on either strand
-//   pmx_pairs_fold_frames_kernel        the slots' records (and statistics) -> one record, statistics and frame per logical pair
+// and, for codon streams (the _frameshift entries: the query's; the _frameshift_ref entries: the reference's):
+//   pmx_pairs_resolve_codons_kernel     one descriptor -> `per` slots (1 or 2), one per strand: the stream's length, nucleotide window
+//   pmx_pairs_gather_codons_kernel      the gather that writes the stride-1 codon stream of that side's window, on either strand
+// The resolve kernels share pmx_resolve_pair / pmx_slot_store, the gather kernels pmx_gather_group / pmx_gather_copy.
 //
 // All of them are bandwidth kernels in plain C++: vector loads and stores only.
 #include "pmx_common.h"
@@ -44,31 +47,123 @@ static __device__ __forceinline__ int32_t pmx_resolve_side(const int64_t *__rest
     return (int32_t)l;
 }
 
+// What the three resolve kernels share.  Both sides of descriptor p against their sets and maxima: true when both windows are good.
+static __device__ __forceinline__ bool pmx_resolve_pair(const pmx_pair_t &p, const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
+                                                        const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
+                                                        int32_t max_qlen, int32_t max_rlen, int32_t *ql, int32_t *rl, long long *qs, long long *rs)
+{
+    *ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, max_qlen, qs);
+    *rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, rs);
+    return *ql > 0 && *rl > 0;
+}
+// The columns of a chunk's alignment slots, and the two threads behind the last pair: the scans read per * n + 1 lengths.
+struct PmxSlotCols { int32_t *qlen, *rlen; int64_t *qsrc, *rsrc; uint8_t *ok, *sflag; };
+static __device__ __forceinline__ void pmx_slot_tail(const PmxSlotCols &c, long long n, int per, long long k)
+{
+    const long long t = (long long)per * n + (k - n);
+    c.qlen[t] = 0; c.rlen[t] = 0;
+}
+// Slot t: the two windows and the slot's flag byte, or (have false) the 1 x 1 placeholder with ok = 0.  sflag may be NULL (no flags kept).
+static __device__ __forceinline__ void pmx_slot_store(const PmxSlotCols &c, long long t, bool have, int32_t ql, int32_t rl, long long qs, long long rs,
+                                                      uint8_t flag)
+{
+    c.qlen[t] = have ? ql : 1; c.rlen[t] = have ? rl : 1; c.qsrc[t] = have ? qs : 0; c.rsrc[t] = have ? rs : 0;
+    c.ok[t] = have ? 1 : 0;
+    if (c.sflag) c.sflag[t] = flag;
+}
+
+// Logical pair k becomes `per` alignment slots per * k + i with the strand s0 + i in sflag, s0 = strand ? strand[k] : first -- the same
+// lengths and sources in every slot, so the gather and every alignment kernel see an ordinary batch of per * n pairs.  The plain
+// entries: no strand, first 0, per 1, sflag NULL.  A strand byte per pair (the _ex entries): per 1.  The strand chosen by the entry
+// (DESIGN 2.5h): PMX_STRAND_REVERSE first 1, per 1; PMX_STRAND_BOTH first 0, per 2 -- slot 2 k the pair as stored, slot 2 k + 1 the pair
+// with its query window reverse-complemented.  A bad descriptor and s0 + per > 2 -- a strand byte above 1 -- make every slot of the
+// pair a 1 x 1 placeholder with ok = 0 and sflag = 0.
 __global__ __launch_bounds__(256)
-void pmx_pairs_resolve_kernel(const pmx_pair_t *__restrict__ pairs, long long n,
+void pmx_pairs_resolve_kernel(const pmx_pair_t *__restrict__ pairs, const uint8_t *__restrict__ strand, int first, int per, long long n,
                               const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
                               const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
                               int32_t max_qlen, int32_t max_rlen,
                               int32_t *__restrict__ qlen, int32_t *__restrict__ rlen,
-                              int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok)
+                              int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
 {
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    const PmxSlotCols c = {qlen, rlen, qsrc, rsrc, ok, sflag};
     if (k >= n + 2) return;
-    if (k >= n) { qlen[k] = 0; rlen[k] = 0; return; }          // (the scan reads n + 1 lengths)
-    const pmx_pair_t p = pairs[k];
-    long long qs = 0, rs = 0;
-    int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, max_qlen, &qs);
-    int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
-    const bool good = ql > 0 && rl > 0;
-    if (!good) { ql = 1; rl = 1; qs = 0; rs = 0; }
-    qlen[k] = ql; rlen[k] = rl; qsrc[k] = qs; rsrc[k] = rs; ok[k] = good ? 1 : 0;
+    if (k >= n) { pmx_slot_tail(c, n, per, k); return; }
+    const unsigned s0 = strand ? strand[k] : (unsigned)first;
+    long long qs = 0, rs = 0; int32_t ql = 0, rl = 0;
+    const bool good = pmx_resolve_pair(pairs[k], q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, &ql, &rl, &qs, &rs) &&
+                      s0 + (unsigned)per <= 2u;
+    for (int i = 0; i < per; ++i)
+        pmx_slot_store(c, (long long)per * k + i, good, ql, rl, qs, rs, good ? (uint8_t)(s0 + (unsigned)i) : 0);
 }
 
-// Group g = 2 * pair + side copies one window: four sequences per wave, both sides of a pair in neighbouring groups.  Up to three head
-// bytes bring the destination to a dword boundary; each destination dword is then assembled from the two aligned source dwords that
-// hold its four bytes (one when the source is aligned too); the tail goes byte by byte.  A dword whose aligned source dwords would
-// reach outside [buf, buf + bytes) -- the first or last few bytes of a set, which has no promised slack -- is assembled from its own
-// four bytes.  Destinations lie inside the chunk buffer by construction: every length is at most the maximum the buffer was sized by.
+// The four bytes at s (anywhere inside a window of the set [lo_bound, hi_bound)): from the one or two aligned dwords that hold them, or
+// byte by byte where those would reach outside the set -- the first or last few bytes of a set, which has no promised slack.
+static __device__ __forceinline__ uint32_t pmx_window_dword(const uint8_t *s, uintptr_t lo_bound, uintptr_t hi_bound)
+{
+    const uintptr_t sa = (uintptr_t)s & ~(uintptr_t)3;
+    const unsigned sh = (unsigned)((uintptr_t)s & 3);
+    if (sa >= lo_bound && sa + (sh ? 8 : 4) <= hi_bound) {
+        const uint32_t lo = *reinterpret_cast<const uint32_t *>(sa);
+        const uint32_t hi = sh ? *reinterpret_cast<const uint32_t *>(sa + 4) : 0u;
+        return __builtin_amdgcn_alignbyte(hi, lo, sh);
+    }
+    return (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
+}
+
+// What the four gather kernels share.  Group g = 2 * slot + side writes one window: four windows per wave, both sides of a slot in
+// neighbouring groups.  Up to three head bytes bring the destination to a dword boundary, `nd` aligned destination dwords follow, the
+// tail goes byte by byte.  pmx_gather_group finds the calling thread's group and returns false where it has nothing more to do: behind
+// the last group, a window whose end would cross its side's capacity (not written), and a bad slot (its one byte is written here).
+// Without a capacity (INT64_MAX: the chunk pipeline) destinations lie inside the chunk buffer by construction: every length is at
+// most the maximum the buffer was sized by.
+struct PmxGatherGroup {
+    long long k; bool side; int lane;                           // the slot, its side (true: the reference) and the thread's lane of 16
+    uint8_t *dst; const uint8_t *src;                           // the packed window; the window's first byte in the set
+    uintptr_t lo_bound, hi_bound;                               // the set's buffer
+    long long len, head, nd, done;                              // destination bytes; head bytes, dwords, bytes before the tail
+    uint32_t *d0;                                               // destination dword 0
+};
+static __device__ __forceinline__ bool pmx_gather_group(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes,
+                                                        const uint8_t *__restrict__ r_buf, long long r_bytes,
+                                                        const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen,
+                                                        const int64_t *__restrict__ qsrc, const int64_t *__restrict__ rsrc, const uint8_t *__restrict__ ok,
+                                                        const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
+                                                        uint8_t *__restrict__ qout, long long q_cap, uint8_t *__restrict__ rout, long long r_cap,
+                                                        PmxGatherGroup *out)
+{
+    PmxGatherGroup g;
+    const long long group = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
+    g.lane = threadIdx.x & 15;
+    if (group >= 2 * n) return false;
+    g.k = group >> 1;
+    g.side = (group & 1) != 0;
+    if ((g.side ? roff[g.k + 1] : qoff[g.k + 1]) > (g.side ? r_cap : q_cap)) return false;     // (never with INT64_MAX: the load goes too)
+    g.dst = g.side ? rout + roff[g.k] : qout + qoff[g.k];
+    if (!ok[g.k]) { if (g.lane == 0) g.dst[0] = 0; return false; }
+    const uint8_t *buf = g.side ? r_buf : q_buf;
+    g.len = g.side ? rlen[g.k] : qlen[g.k];
+    g.src = buf + (g.side ? rsrc[g.k] : qsrc[g.k]);
+    g.lo_bound = (uintptr_t)buf; g.hi_bound = (uintptr_t)(buf + (g.side ? r_bytes : q_bytes));
+    g.head = (4 - (long long)((uintptr_t)g.dst & 3)) & 3;
+    if (g.head > g.len) g.head = g.len;
+    g.nd = (g.len - g.head) >> 2; g.done = g.head + 4 * g.nd;
+    g.d0 = reinterpret_cast<uint32_t *>(g.dst + g.head);
+    *out = g;
+    return true;
+}
+// The window as it is stored: each destination dword from the aligned source dwords that hold its four bytes.
+static __device__ __forceinline__ void pmx_gather_copy(const PmxGatherGroup &g)
+{
+    if (g.lane < g.head) g.dst[g.lane] = g.src[g.lane];
+    const uint8_t *s0 = g.src + g.head;
+    for (long long x = g.lane; x < g.nd; x += 16)
+        g.d0[x] = pmx_window_dword(s0 + 4 * x, g.lo_bound, g.hi_bound);
+    if (g.lane < g.len - g.done) g.dst[g.done + g.lane] = g.src[g.done + g.lane];
+}
+
+// The gather every untranslated forward batch runs: both windows copied, no table in LDS, no capacities, no flags.
 __global__ __launch_bounds__(256)
 void pmx_pairs_gather_kernel(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes, const uint8_t *__restrict__ r_buf, long long r_bytes,
                              const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen,
@@ -76,38 +171,9 @@ void pmx_pairs_gather_kernel(long long n, const uint8_t *__restrict__ q_buf, lon
                              const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
                              uint8_t *__restrict__ qout, uint8_t *__restrict__ rout)
 {
-    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
-    const int lane = threadIdx.x & 15;
-    if (g >= 2 * n) return;
-    const long long k = g >> 1;
-    const bool side = (g & 1) != 0;
-    uint8_t *dst = side ? rout + roff[k] : qout + qoff[k];
-    if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
-    const uint8_t *buf = side ? r_buf : q_buf;
-    const long long len = side ? rlen[k] : qlen[k];
-    const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
-    const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
-    long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
-    if (head > len) head = len;
-    if (lane < head) dst[lane] = src[lane];
-    const long long nd = (len - head) >> 2;
-    const uint8_t *s0 = src + head;
-    uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
-    for (long long x = lane; x < nd; x += 16) {
-        const uint8_t *s = s0 + 4 * x;
-        const uintptr_t sa = (uintptr_t)s & ~(uintptr_t)3;
-        const unsigned sh = (unsigned)((uintptr_t)s & 3);
-        uint32_t v;
-        if (sa >= lo_bound && sa + (sh ? 8 : 4) <= hi_bound) {
-            const uint32_t lo = *reinterpret_cast<const uint32_t *>(sa);
-            const uint32_t hi = sh ? *reinterpret_cast<const uint32_t *>(sa + 4) : 0u;
-            v = __builtin_amdgcn_alignbyte(hi, lo, sh);
-        } else
-            v = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
-        d0[x] = v;
-    }
-    const long long done = head + 4 * nd;
-    if (lane < len - done) dst[done + lane] = src[done + lane];
+    PmxGatherGroup g;
+    if (!pmx_gather_group(n, q_buf, q_bytes, r_buf, r_bytes, qlen, rlen, qsrc, rsrc, ok, qoff, roff, qout, INT64_MAX, rout, INT64_MAX, &g)) return;
+    pmx_gather_copy(g);
 }
 
 // ---- strands (the _ex entries) --------------------------------------------------------------------------------------------------
@@ -127,49 +193,11 @@ static constexpr PmxCompTable pmx_make_comp_table()
 static constexpr PmxCompTable pmx_comp_host = pmx_make_comp_table();
 __device__ const PmxCompTable pmx_comp_dev = pmx_make_comp_table();
 
-// pmx_pairs_resolve_kernel with the pair's strand byte: 0 / 1 go to sflag, anything else makes the pair bad.
-__global__ __launch_bounds__(256)
-void pmx_pairs_resolve_stranded_kernel(const pmx_pair_t *__restrict__ pairs, const uint8_t *__restrict__ strand, long long n,
-                                       const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
-                                       const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
-                                       int32_t max_qlen, int32_t max_rlen,
-                                       int32_t *__restrict__ qlen, int32_t *__restrict__ rlen,
-                                       int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n + 2) return;
-    if (k >= n) { qlen[k] = 0; rlen[k] = 0; return; }          // (the scan reads n + 1 lengths)
-    const pmx_pair_t p = pairs[k];
-    const unsigned sb = strand ? strand[k] : 0u;
-    long long qs = 0, rs = 0;
-    int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, max_qlen, &qs);
-    int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
-    const bool good = ql > 0 && rl > 0 && sb <= 1u;
-    if (!good) { ql = 1; rl = 1; qs = 0; rs = 0; }
-    qlen[k] = ql; rlen[k] = rl; qsrc[k] = qs; rsrc[k] = rs; ok[k] = good ? 1 : 0; sflag[k] = good ? (uint8_t)sb : 0;
-}
-
-// The four bytes at s (anywhere inside a window of the set [lo_bound, hi_bound)) as the gather kernel above reads them: from the one or
-// two aligned dwords that hold them, or byte by byte where those would reach outside the set.
-static __device__ __forceinline__ uint32_t pmx_window_dword(const uint8_t *s, uintptr_t lo_bound, uintptr_t hi_bound)
-{
-    const uintptr_t sa = (uintptr_t)s & ~(uintptr_t)3;
-    const unsigned sh = (unsigned)((uintptr_t)s & 3);
-    if (sa >= lo_bound && sa + (sh ? 8 : 4) <= hi_bound) {
-        const uint32_t lo = *reinterpret_cast<const uint32_t *>(sa);
-        const uint32_t hi = sh ? *reinterpret_cast<const uint32_t *>(sa + 4) : 0u;
-        return __builtin_amdgcn_alignbyte(hi, lo, sh);
-    }
-    return (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
-}
-
-// The gather of pmx_pairs_gather_kernel for both strands: the same 16-lane group per window, the same forward walk over the
-// destination in aligned dwords.  A strand-1 query window is read backwards: destination byte x is comp[src[len - 1 - x]], so the
-// destination dword at bytes p .. p + 3 holds source bytes len - 4 - p .. len - 1 - p in reversed order -- assembled like a forward
-// dword from the aligned source dwords around them (the same in-bounds test, the same byte-by-byte fallback at a set's first and
-// last bytes), reversed by one v_perm, complemented by four byte reads of the table staged in LDS.  The strand is uniform per group
-// (not per wave: a wave holds four windows), so the branch sits outside the dword loop.  A window whose end would cross its
-// capacity is not written (the chunk pipeline passes no limit).
+// The gather of pmx_pairs_gather_kernel for both strands: the same group per window, the reference and a strand-0 query copied as
+// there.  A strand-1 query window is read backwards: destination byte x is comp[src[len - 1 - x]], so the destination dword at bytes
+// p .. p + 3 holds source bytes len - 4 - p .. len - 1 - p in reversed order -- assembled like a forward dword from the aligned source
+// dwords around them, reversed by one v_perm, complemented by four byte reads of the table staged in LDS.  The strand is uniform per
+// group (not per wave: a wave holds four windows), so the branch sits outside the dword loop.
 __global__ __launch_bounds__(256)
 void pmx_pairs_gather_stranded_kernel(long long n, const uint8_t *__restrict__ q_buf, long long q_bytes, const uint8_t *__restrict__ r_buf, long long r_bytes,
                                       const int32_t *__restrict__ qlen, const int32_t *__restrict__ rlen,
@@ -180,106 +208,56 @@ void pmx_pairs_gather_stranded_kernel(long long n, const uint8_t *__restrict__ q
     __shared__ uint8_t comp[256];
     comp[threadIdx.x] = pmx_comp_dev.v[threadIdx.x];
     __syncthreads();
-    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
-    const int lane = threadIdx.x & 15;
-    if (g >= 2 * n) return;
-    const long long k = g >> 1;
-    const bool side = (g & 1) != 0;
-    const int64_t o0 = side ? roff[k] : qoff[k], o1 = side ? roff[k + 1] : qoff[k + 1];
-    if (o1 > (side ? r_cap : q_cap)) return;
-    uint8_t *dst = (side ? rout : qout) + o0;
-    if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
-    const uint8_t *buf = side ? r_buf : q_buf;
-    const long long len = side ? rlen[k] : qlen[k];
-    const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
-    const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
-    long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
-    if (head > len) head = len;
-    const long long nd = (len - head) >> 2, done = head + 4 * nd;
-    uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
-    if (!side && sflag[k]) {
-        const uint8_t *last = src + len - 1;                    // destination byte x <- comp[last[-x]]
-        if (lane < head) dst[lane] = comp[last[-lane]];
-        const uint8_t *s0 = last - head - 3;                    // the lowest source byte of destination dword 0
-        for (long long x = lane; x < nd; x += 16) {
-            const uint32_t v = __builtin_amdgcn_perm(0u, pmx_window_dword(s0 - 4 * x, lo_bound, hi_bound), 0x00010203u);      // bytes 3 2 1 0
-            d0[x] = (uint32_t)comp[v & 0xFF] | ((uint32_t)comp[(v >> 8) & 0xFF] << 8) | ((uint32_t)comp[(v >> 16) & 0xFF] << 16) |
-                    ((uint32_t)comp[v >> 24] << 24);
-        }
-        if (lane < len - done) dst[done + lane] = comp[last[-(done + lane)]];
-        return;
+    PmxGatherGroup g;
+    if (!pmx_gather_group(n, q_buf, q_bytes, r_buf, r_bytes, qlen, rlen, qsrc, rsrc, ok, qoff, roff, qout, q_cap, rout, r_cap, &g)) return;
+    if (g.side || !sflag[g.k]) { pmx_gather_copy(g); return; }
+    const int lane = g.lane;
+    const uint8_t *last = g.src + g.len - 1;                    // destination byte x <- comp[last[-x]]
+    if (lane < g.head) g.dst[lane] = comp[last[-lane]];
+    const uint8_t *s0 = last - g.head - 3;                      // the lowest source byte of destination dword 0
+    for (long long x = lane; x < g.nd; x += 16) {
+        const uint32_t v = __builtin_amdgcn_perm(0u, pmx_window_dword(s0 - 4 * x, g.lo_bound, g.hi_bound), 0x00010203u);      // bytes 3 2 1 0
+        g.d0[x] = (uint32_t)comp[v & 0xFF] | ((uint32_t)comp[(v >> 8) & 0xFF] << 8) | ((uint32_t)comp[(v >> 16) & 0xFF] << 16) |
+                  ((uint32_t)comp[v >> 24] << 24);
     }
-    if (lane < head) dst[lane] = src[lane];
-    const uint8_t *s0 = src + head;
-    for (long long x = lane; x < nd; x += 16)
-        d0[x] = pmx_window_dword(s0 + 4 * x, lo_bound, hi_bound);
-    if (lane < len - done) dst[done + lane] = src[done + lane];
+    if (lane < g.len - g.done) g.dst[g.done + lane] = comp[last[-(g.done + lane)]];
 }
 
-// ---- both strands (pmx_align_pairs_both[_device], pmx_search_pairs_stranded[_device], pmx_search_topk_stranded[_device]) -----------
-// The resolve step for a strand the entry chooses: logical pair k becomes `per` alignment slots.  per == 1 (PMX_STRAND_REVERSE): slot k,
-// reverse-complemented.  per == 2 (PMX_STRAND_BOTH): slot 2 k the pair as stored, slot 2 k + 1 the pair with its query window
-// reverse-complemented -- the same lengths and sources twice, so the gather and every alignment kernel see an ordinary batch of 2 n
-// pairs.  A bad descriptor is bad in every slot (1 x 1, ok = 0, sflag = 0).  The scans read per * n + 1 lengths.
+// ---- the fold (every entry whose pairs are several slots, or whose one slot the entry chose) ---------------------------------------
+// The slots of logical pair k back to one record: among the slots with ok != 0 the highest score, the lowest slot -- the forward
+// strand, the lowest frame -- on a tie (only the score is compared).  The record is the winner's sixteen bytes, the statistics are the
+// winner's, the byte (a strand or a frame) is the winner's sflag.  No candidate (a bad descriptor, or no frame exists): {0, -1, -1,
+// PMX_FLAG_BAD_PAIR}, zero statistics, byte 0 -- no fix-up pass follows.  mark: the byte also rides in the record -- 1 as
+// PMX_FLAG_STRAND1, 2 in PMX_FLAG_FRAME_MASK, what pmx_pairs_append_hits_kernel reads as `marked` -- for records that stay in chunk
+// scratch on their way through selection or the top-K lists; the kernels that write a caller's hit arrays strip it.  okf (optional):
+// the logical pair's validity byte.  The strand and codon resolves give every slot of a pair the same ok, so for them "the slots
+// with ok != 0" is all or none, and this is the fold that looked at the first slot's ok alone.  One thread per logical pair; slot
+// records are read as 16-byte vectors (scratch is 16-byte aligned), records are stored that way where the destination is aligned.
 __global__ __launch_bounds__(256)
-void pmx_pairs_resolve_both_kernel(const pmx_pair_t *__restrict__ pairs, long long n, int per,
-                                   const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
-                                   const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
-                                   int32_t max_qlen, int32_t max_rlen,
-                                   int32_t *__restrict__ qlen, int32_t *__restrict__ rlen,
-                                   int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n + 2) return;
-    if (k >= n) { const long long t = (long long)per * n + (k - n); qlen[t] = 0; rlen[t] = 0; return; }
-    const pmx_pair_t p = pairs[k];
-    long long qs = 0, rs = 0;
-    int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, max_qlen, &qs);
-    int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, max_rlen, &rs);
-    const bool good = ql > 0 && rl > 0;
-    if (!good) { ql = 1; rl = 1; qs = 0; rs = 0; }
-    const uint8_t g = good ? 1 : 0;
-    const long long s = (long long)per * k;
-    qlen[s] = ql; rlen[s] = rl; qsrc[s] = qs; rsrc[s] = rs; ok[s] = g;
-    if (per == 2) {
-        sflag[s] = 0;
-        qlen[s + 1] = ql; rlen[s + 1] = rl; qsrc[s + 1] = qs; rsrc[s + 1] = rs; ok[s + 1] = g; sflag[s + 1] = g;
-    } else
-        sflag[s] = g;
-}
-
-// The slots of logical pair k back to one record: per == 2 the reverse slot's when its score is higher, else the forward slot's (only
-// the score is compared, a tie goes to the forward strand); per == 1 the one slot's.  The record is the winner's sixteen bytes, the
-// statistics are the winner's, the strand is the winner's sflag.  A bad pair gets {0, -1, -1, PMX_FLAG_BAD_PAIR}, zero statistics and
-// strand 0 here: no fix-up pass follows.  mark: the strand also rides in the record as PMX_FLAG_STRAND1, for records that stay in
-// chunk scratch on their way through selection or the top-K lists; the kernels that write a caller's hit arrays strip it.  okf
-// (optional): the logical pair's validity byte.  One thread per logical pair; slot records are read as 16-byte vectors (scratch is
-// 16-byte aligned), records are stored that way where the destination is aligned.
-__global__ __launch_bounds__(256)
-void pmx_pairs_fold_strands_kernel(const pmx_record_t *__restrict__ slot_rec, const pmx_stats_t *__restrict__ slot_stats,
-                                   const uint8_t *__restrict__ ok, const uint8_t *__restrict__ sflag, long long n, int per, int mark,
-                                   pmx_record_t *__restrict__ rec, pmx_stats_t *__restrict__ stats, uint8_t *__restrict__ strand,
-                                   uint8_t *__restrict__ okf)
+void pmx_pairs_fold_kernel(const pmx_record_t *__restrict__ slot_rec, const pmx_stats_t *__restrict__ slot_stats,
+                           const uint8_t *__restrict__ ok, const uint8_t *__restrict__ sflag, long long n, int per, int mark,
+                           pmx_record_t *__restrict__ rec, pmx_stats_t *__restrict__ stats, uint8_t *__restrict__ byte,
+                           uint8_t *__restrict__ okf)
 {
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     const long long s = (long long)per * k;
-    const bool good = ok[s] != 0;
     uint4 w = make_uint4(0u, 0xFFFFFFFFu, 0xFFFFFFFFu, (uint32_t)PMX_FLAG_BAD_PAIR);
     pmx_stats_t ws; ws.matches = 0; ws.similar = 0; ws.length = 0;
-    unsigned sb = 0;
-    if (good) {
-        const uint4 *sr = reinterpret_cast<const uint4 *>(slot_rec + s);
-        long long from = s;
-        w = sr[0];
-        if (per == 2) {
-            const uint4 b = sr[1];
-            if ((int32_t)b.x > (int32_t)w.x) { w = b; from = s + 1; }
-        }
-        sb = sflag[from];
+    const uint4 *sr = reinterpret_cast<const uint4 *>(slot_rec + s);
+    long long from = -1;
+    for (int i = 0; i < per; ++i) {
+        if (!ok[s + i]) continue;
+        const uint4 b = sr[i];
+        if (from < 0 || (int32_t)b.x > (int32_t)w.x) { w = b; from = s + i; }
+    }
+    unsigned fb = 0;
+    if (from >= 0) {
+        fb = sflag[from];
         if (stats) ws = slot_stats[from];
     }
-    if (mark && sb) w.w |= (uint32_t)PMX_FLAG_STRAND1;
+    if (mark == 1 && fb) w.w |= (uint32_t)PMX_FLAG_STRAND1;
+    if (mark == 2) w.w |= fb << PMX_FLAG_FRAME_SHIFT;
     if (((uintptr_t)rec & 15) == 0)
         *reinterpret_cast<uint4 *>(rec + k) = w;
     else {
@@ -287,8 +265,8 @@ void pmx_pairs_fold_strands_kernel(const pmx_record_t *__restrict__ slot_rec, co
         rec[k] = r;
     }
     if (stats) stats[k] = ws;
-    if (strand) strand[k] = (uint8_t)sb;
-    if (okf) okf[k] = good ? 1 : 0;
+    if (byte) byte[k] = (uint8_t)fb;
+    if (okf) okf[k] = from >= 0 ? 1 : 0;
 }
 
 // ---- translated queries (pmx_align_pairs_translated[_device], the _translated searches, pmx_gather_pairs_translated_device) --
@@ -324,15 +302,14 @@ void pmx_pairs_resolve_frames_kernel(const pmx_pair_t *__restrict__ pairs, const
                                      int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
 {
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    const PmxSlotCols c = {qlen, rlen, qsrc, rsrc, ok, sflag};
     if (k >= n + 2) return;
-    if (k >= n) { const long long t = (long long)per * n + (k - n); qlen[t] = 0; rlen[t] = 0; return; }
-    const pmx_pair_t p = pairs[k];
+    if (k >= n) { pmx_slot_tail(c, n, per, k); return; }
     const unsigned f0 = frame ? frame[k] : (unsigned)first;
-    long long qs = 0, rs = 0;
-    const int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, REF ? max_qlen : INT32_MAX, &qs);
-    const int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, REF ? INT32_MAX : max_rlen, &rs);
-    const int32_t W = REF ? rl : ql, plain = REF ? ql : rl, max_l = REF ? max_rlen : max_qlen;
-    bool good = W > 0 && plain > 0 && f0 + (unsigned)per <= 6u;
+    long long qs = 0, rs = 0; int32_t ql = 0, rl = 0;
+    bool good = pmx_resolve_pair(pairs[k], q_off, q_count, q_bytes, r_off, r_count, r_bytes, REF ? max_qlen : INT32_MAX, REF ? INT32_MAX : max_rlen,
+                                 &ql, &rl, &qs, &rs) && f0 + (unsigned)per <= 6u;
+    const int32_t W = REF ? rl : ql, max_l = REF ? max_rlen : max_qlen;
     for (int i = 0; i < per; ++i) {                                // (the shortest offset of the call's frames has the longest L)
         const int off = (int)((f0 + (unsigned)i) % 3u);
         if (W > off && (W - off) / 3 > max_l) good = false;
@@ -342,10 +319,8 @@ void pmx_pairs_resolve_frames_kernel(const pmx_pair_t *__restrict__ pairs, const
         const unsigned f = f0 + (unsigned)i;
         const int off = (int)(f % 3u);
         const int32_t L = good && W > off ? (W - off) / 3 : 0;
-        const bool have = L > 0;
-        (REF ? rlen : qlen)[s + i] = have ? L : 1; (REF ? qlen : rlen)[s + i] = have ? plain : 1; tw[s + i] = have ? W : 0;
-        qsrc[s + i] = have ? qs : 0; rsrc[s + i] = have ? rs : 0;
-        ok[s + i] = have ? 1 : 0; sflag[s + i] = good ? (uint8_t)f : 0;
+        pmx_slot_store(c, s + i, L > 0, REF ? ql : L, REF ? L : rl, qs, rs, good ? (uint8_t)f : 0);
+        tw[s + i] = L > 0 ? W : 0;
     }
 }
 
@@ -377,31 +352,13 @@ void pmx_pairs_gather_translated_kernel(long long n, const uint8_t *__restrict__
     cls[threadIdx.x] = pmx_base_dev.v[threadIdx.x];
     if (threadIdx.x < 64) cod[threadIdx.x] = code.v[threadIdx.x];
     __syncthreads();
-    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
-    const int lane = threadIdx.x & 15;
-    if (g >= 2 * n) return;
-    const long long k = g >> 1;
-    const bool side = (g & 1) != 0;
-    const int64_t o0 = side ? roff[k] : qoff[k], o1 = side ? roff[k + 1] : qoff[k + 1];
-    if (o1 > (side ? r_cap : q_cap)) return;
-    uint8_t *dst = (side ? rout : qout) + o0;
-    if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
-    const uint8_t *buf = side ? r_buf : q_buf;
-    const long long len = side ? rlen[k] : qlen[k];             // destination bytes: letters on the translated side
-    const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
-    const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
-    long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
-    if (head > len) head = len;
-    const long long nd = (len - head) >> 2, done = head + 4 * nd;
-    uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
-    if (side != REF) {
-        if (lane < head) dst[lane] = src[lane];
-        const uint8_t *s0 = src + head;
-        for (long long x = lane; x < nd; x += 16)
-            d0[x] = pmx_window_dword(s0 + 4 * x, lo_bound, hi_bound);
-        if (lane < len - done) dst[done + lane] = src[done + lane];
-        return;
-    }
+    PmxGatherGroup g;
+    if (!pmx_gather_group(n, q_buf, q_bytes, r_buf, r_bytes, qlen, rlen, qsrc, rsrc, ok, qoff, roff, qout, q_cap, rout, r_cap, &g)) return;
+    if (g.side != REF) { pmx_gather_copy(g); return; }
+    const int lane = g.lane;
+    const long long k = g.k, len = g.len, head = g.head, nd = g.nd, done = g.done;      // len: letters on the translated side
+    uint8_t *dst = g.dst; const uint8_t *src = g.src; uint32_t *d0 = g.d0;
+    const uintptr_t lo_bound = g.lo_bound, hi_bound = g.hi_bound;
     const unsigned f = sflag[k];
     if (f >= 3) {
         const uint8_t *top = src + tw[k] - 1 - (f - 3);         // letter p: top[-3 p], top[-3 p - 1], top[-3 p - 2], complemented
@@ -440,47 +397,6 @@ void pmx_pairs_gather_translated_kernel(long long n, const uint8_t *__restrict__
     }
 }
 
-// The slots of logical pair k back to one record: among the slots with ok != 0 the highest score, the lowest slot -- the lowest
-// frame -- on a tie (only the score is compared).  The record is the winner's sixteen bytes, the statistics are the winner's, the
-// frame is the winner's sflag.  No candidate (a bad descriptor, or no frame exists): {0, -1, -1, PMX_FLAG_BAD_PAIR}, zero statistics,
-// frame 0.  mark: the frame also rides in the record (PMX_FLAG_FRAME_MASK), for records that stay in chunk scratch on their way
-// through selection or the top-K lists; the kernels that write a caller's hit arrays strip it.  okf (optional): the logical pair's
-// validity byte.  One thread per logical pair, as pmx_pairs_fold_strands_kernel.
-__global__ __launch_bounds__(256)
-void pmx_pairs_fold_frames_kernel(const pmx_record_t *__restrict__ slot_rec, const pmx_stats_t *__restrict__ slot_stats,
-                                  const uint8_t *__restrict__ ok, const uint8_t *__restrict__ sflag, long long n, int per, int mark,
-                                  pmx_record_t *__restrict__ rec, pmx_stats_t *__restrict__ stats, uint8_t *__restrict__ frame,
-                                  uint8_t *__restrict__ okf)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    const long long s = (long long)per * k;
-    uint4 w = make_uint4(0u, 0xFFFFFFFFu, 0xFFFFFFFFu, (uint32_t)PMX_FLAG_BAD_PAIR);
-    pmx_stats_t ws; ws.matches = 0; ws.similar = 0; ws.length = 0;
-    const uint4 *sr = reinterpret_cast<const uint4 *>(slot_rec + s);
-    long long from = -1;
-    for (int i = 0; i < per; ++i) {
-        if (!ok[s + i]) continue;
-        const uint4 b = sr[i];
-        if (from < 0 || (int32_t)b.x > (int32_t)w.x) { w = b; from = s + i; }
-    }
-    unsigned fb = 0;
-    if (from >= 0) {
-        fb = sflag[from];
-        if (stats) ws = slot_stats[from];
-    }
-    if (mark) w.w |= fb << PMX_FLAG_FRAME_SHIFT;
-    if (((uintptr_t)rec & 15) == 0)
-        *reinterpret_cast<uint4 *>(rec + k) = w;
-    else {
-        pmx_record_t r; r.score = (int32_t)w.x; r.end_query = (int32_t)w.y; r.end_ref = (int32_t)w.z; r.flags = (int32_t)w.w;
-        rec[k] = r;
-    }
-    if (stats) stats[k] = ws;
-    if (frame) frame[k] = (uint8_t)fb;
-    if (okf) okf[k] = from >= 0 ? 1 : 0;
-}
-
 // ---- codon streams (the _frameshift entries, pmx_gather_pairs_codons_device; REF: the _frameshift_ref entries, 2.5m) ----
 // The resolve step of the frameshift-aware entries: logical pair k becomes `per` alignment slots, one per strand -- strand ?
 // strand[k] (per 1) : per == 2 ? forward then reverse : `first` (0 or 1).  REF false: the query resolves to its nucleotide window (W
@@ -498,20 +414,19 @@ void pmx_pairs_resolve_codons_kernel(const pmx_pair_t *__restrict__ pairs, const
                                      int64_t *__restrict__ qsrc, int64_t *__restrict__ rsrc, uint8_t *__restrict__ ok, uint8_t *__restrict__ sflag)
 {
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    const PmxSlotCols c = {qlen, rlen, qsrc, rsrc, ok, sflag};
     if (k >= n + 2) return;
-    if (k >= n) { const long long t = (long long)per * n + (k - n); qlen[t] = 0; rlen[t] = 0; return; }
-    const pmx_pair_t p = pairs[k];
+    if (k >= n) { pmx_slot_tail(c, n, per, k); return; }
     const unsigned s0 = strand ? strand[k] : (unsigned)first;
-    long long qs = 0, rs = 0;
-    const int32_t ql = pmx_resolve_side(q_off, q_count, q_bytes, p.q, p.q_beg, p.q_len, REF ? max_qlen : INT32_MAX, &qs);
-    const int32_t rl = pmx_resolve_side(r_off, r_count, r_bytes, p.r, p.r_beg, p.r_len, REF ? INT32_MAX : max_rlen, &rs);
-    const int32_t W = REF ? rl : ql, plain = REF ? ql : rl;
-    const bool good = W >= 3 && plain > 0 && s0 + (unsigned)per <= 2u && W - 2 <= (REF ? max_rlen : max_qlen);
+    long long qs = 0, rs = 0; int32_t ql = 0, rl = 0;
+    bool good = pmx_resolve_pair(pairs[k], q_off, q_count, q_bytes, r_off, r_count, r_bytes, REF ? max_qlen : INT32_MAX, REF ? INT32_MAX : max_rlen,
+                                 &ql, &rl, &qs, &rs) && s0 + (unsigned)per <= 2u;
+    const int32_t W = REF ? rl : ql;
+    good = good && W >= 3 && W - 2 <= (REF ? max_rlen : max_qlen);
     const long long s = (long long)per * k;
     for (int i = 0; i < per; ++i) {
-        (REF ? rlen : qlen)[s + i] = good ? W - 2 : 1; (REF ? qlen : rlen)[s + i] = good ? plain : 1; tw[s + i] = good ? W : 0;
-        qsrc[s + i] = good ? qs : 0; rsrc[s + i] = good ? rs : 0;
-        ok[s + i] = good ? 1 : 0; sflag[s + i] = good ? (uint8_t)(s0 + (unsigned)i) : 0;
+        pmx_slot_store(c, s + i, good, REF ? ql : W - 2, REF ? W - 2 : rl, qs, rs, good ? (uint8_t)(s0 + (unsigned)i) : 0);
+        tw[s + i] = good ? W : 0;
     }
 }
 
@@ -534,31 +449,13 @@ void pmx_pairs_gather_codons_kernel(long long n, const uint8_t *__restrict__ q_b
     cls[threadIdx.x] = pmx_base_dev.v[threadIdx.x];
     if (threadIdx.x < 64) cod[threadIdx.x] = code.v[threadIdx.x];
     __syncthreads();
-    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
-    const int lane = threadIdx.x & 15;
-    if (g >= 2 * n) return;
-    const long long k = g >> 1;
-    const bool side = (g & 1) != 0;
-    const int64_t o0 = side ? roff[k] : qoff[k], o1 = side ? roff[k + 1] : qoff[k + 1];
-    if (o1 > (side ? r_cap : q_cap)) return;
-    uint8_t *dst = (side ? rout : qout) + o0;
-    if (!ok[k]) { if (lane == 0) dst[0] = 0; return; }
-    const uint8_t *buf = side ? r_buf : q_buf;
-    const long long len = side ? rlen[k] : qlen[k];             // destination bytes: letters of the stream on the translated side
-    const uint8_t *src = buf + (side ? rsrc[k] : qsrc[k]);
-    const uintptr_t lo_bound = (uintptr_t)buf, hi_bound = (uintptr_t)(buf + (side ? r_bytes : q_bytes));
-    long long head = (4 - (long long)((uintptr_t)dst & 3)) & 3;
-    if (head > len) head = len;
-    const long long nd = (len - head) >> 2, done = head + 4 * nd;
-    uint32_t *d0 = reinterpret_cast<uint32_t *>(dst + head);
-    if (side != REF) {
-        if (lane < head) dst[lane] = src[lane];
-        const uint8_t *s0 = src + head;
-        for (long long x = lane; x < nd; x += 16)
-            d0[x] = pmx_window_dword(s0 + 4 * x, lo_bound, hi_bound);
-        if (lane < len - done) dst[done + lane] = src[done + lane];
-        return;
-    }
+    PmxGatherGroup g;
+    if (!pmx_gather_group(n, q_buf, q_bytes, r_buf, r_bytes, qlen, rlen, qsrc, rsrc, ok, qoff, roff, qout, q_cap, rout, r_cap, &g)) return;
+    if (g.side != REF) { pmx_gather_copy(g); return; }
+    const int lane = g.lane;
+    const long long k = g.k, len = g.len, head = g.head, nd = g.nd, done = g.done;      // len: letters of the stream
+    uint8_t *dst = g.dst; const uint8_t *src = g.src; uint32_t *d0 = g.d0;
+    const uintptr_t lo_bound = g.lo_bound, hi_bound = g.hi_bound;
     if (sflag[k]) {
         const uint8_t *top = src + tw[k] - 1;                   // letter p: top[-p], top[-p - 1], top[-p - 2], complemented
         if (lane < head) dst[lane] = (uint8_t)pmx_codon(cls, cod, top[-lane], top[-lane - 1], top[-lane - 2], 42u);
@@ -743,13 +640,14 @@ void pmx_pairs_maxlen_kernel(const pmx_pair_t *__restrict__ pairs, long long n,
 
 static int pmx_pairs_launched() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
 
-int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
+int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
+                             const int64_t *q_off, long long q_count, long long q_bytes,
                              const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                             int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, hipStream_t st)
+                             int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_resolve_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, n, q_off, q_count, q_bytes,
-                       r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok);
+    hipLaunchKernelGGL(pmx_pairs_resolve_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, strand, first, per, n,
+                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok, sflag);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_gather(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
@@ -767,16 +665,6 @@ int pmx_launch_pairs_fixup(const uint8_t *ok, long long n, pmx_record_t *rec, pm
     hipLaunchKernelGGL(pmx_pairs_fixup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, rec, stats);
     return pmx_pairs_launched();
 }
-int pmx_launch_pairs_resolve_stranded(const pmx_pair_t *pairs, const uint8_t *strand, long long n,
-                                      const int64_t *q_off, long long q_count, long long q_bytes,
-                                      const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                                      int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
-{
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_resolve_stranded_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, strand, n,
-                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok, sflag);
-    return pmx_pairs_launched();
-}
 int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                                      const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
                                      const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
@@ -787,24 +675,16 @@ int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long lon
                        qlen, rlen, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap);
     return pmx_pairs_launched();
 }
-int pmx_launch_pairs_resolve_both(const pmx_pair_t *pairs, long long n, int per, const int64_t *q_off, long long q_count, long long q_bytes,
-                                  const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
-                                  int32_t *qlen, int32_t *rlen, int64_t *qsrc, int64_t *rsrc, uint8_t *ok, uint8_t *sflag, hipStream_t st)
+int pmx_launch_pairs_fold(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
+                          long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *byte, uint8_t *okf, hipStream_t st)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_resolve_both_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, n, per,
-                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok, sflag);
-    return pmx_pairs_launched();
-}
-int pmx_launch_pairs_fold_strands(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
-                                  long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *strand, uint8_t *okf, hipStream_t st)
-{
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_fold_strands_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slot_rec, slot_stats, ok, sflag,
-                       n, per, mark, rec, stats, strand, okf);
+    hipLaunchKernelGGL(pmx_pairs_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slot_rec, slot_stats, ok, sflag,
+                       n, per, mark, rec, stats, byte, okf);
     return pmx_pairs_launched();
 }
 void pmx_genetic_code_host(uint8_t table[64]) { for (int i = 0; i < 64; ++i) table[i] = (uint8_t)pmx_code_std[i]; }
+// (the translated side is a template argument of these four kernels: the launcher picks the instance)
 int pmx_launch_pairs_resolve_frames(const pmx_pair_t *pairs, const uint8_t *frame, int first, int per, long long n,
                                     const int64_t *q_off, long long q_count, long long q_bytes,
                                     const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
@@ -812,13 +692,9 @@ int pmx_launch_pairs_resolve_frames(const pmx_pair_t *pairs, const uint8_t *fram
                                     bool ref)
 {
     if (n <= 0) return 0;
-    const dim3 grid((unsigned)((n + 2 + 255) / 256));
-    if (ref)
-        hipLaunchKernelGGL(pmx_pairs_resolve_frames_kernel<true>, grid, dim3(256), 0, st, pairs, frame, first, per, n,
-                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
-    else
-        hipLaunchKernelGGL(pmx_pairs_resolve_frames_kernel<false>, grid, dim3(256), 0, st, pairs, frame, first, per, n,
-                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
+    const auto kernel = ref ? pmx_pairs_resolve_frames_kernel<true> : pmx_pairs_resolve_frames_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, frame, first, per, n,
+                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
@@ -828,13 +704,9 @@ int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long l
                                        bool ref)
 {
     if (n <= 0) return 0;
-    const dim3 grid((unsigned)((2 * n + 15) / 16));
-    if (ref)
-        hipLaunchKernelGGL(pmx_pairs_gather_translated_kernel<true>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
-                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
-    else
-        hipLaunchKernelGGL(pmx_pairs_gather_translated_kernel<false>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
-                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
+    const auto kernel = ref ? pmx_pairs_gather_translated_kernel<true> : pmx_pairs_gather_translated_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                       qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_resolve_codons(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
@@ -844,13 +716,9 @@ int pmx_launch_pairs_resolve_codons(const pmx_pair_t *pairs, const uint8_t *stra
                                     bool ref)
 {
     if (n <= 0) return 0;
-    const dim3 grid((unsigned)((n + 2 + 255) / 256));
-    if (ref)
-        hipLaunchKernelGGL(pmx_pairs_resolve_codons_kernel<true>, grid, dim3(256), 0, st, pairs, strand, first, per, n,
-                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
-    else
-        hipLaunchKernelGGL(pmx_pairs_resolve_codons_kernel<false>, grid, dim3(256), 0, st, pairs, strand, first, per, n,
-                           q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
+    const auto kernel = ref ? pmx_pairs_resolve_codons_kernel<true> : pmx_pairs_resolve_codons_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, strand, first, per, n,
+                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
@@ -860,21 +728,9 @@ int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long 
                                    bool ref)
 {
     if (n <= 0) return 0;
-    const dim3 grid((unsigned)((2 * n + 15) / 16));
-    if (ref)
-        hipLaunchKernelGGL(pmx_pairs_gather_codons_kernel<true>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
-                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
-    else
-        hipLaunchKernelGGL(pmx_pairs_gather_codons_kernel<false>, grid, dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
-                           qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
-    return pmx_pairs_launched();
-}
-int pmx_launch_pairs_fold_frames(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
-                                 long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *frame, uint8_t *okf, hipStream_t st)
-{
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_pairs_fold_frames_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slot_rec, slot_stats, ok, sflag,
-                       n, per, mark, rec, stats, frame, okf);
+    const auto kernel = ref ? pmx_pairs_gather_codons_kernel<true> : pmx_pairs_gather_codons_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
+                       qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
     return pmx_pairs_launched();
 }
 int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *rec, int32_t *nops, int32_t *textlen, int32_t *beg, hipStream_t st)
