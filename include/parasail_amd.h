@@ -1112,8 +1112,8 @@ int pmx_search_topk_translated_ref(const pmx_config_t *cfg, const pmx_seqset_t *
  * columns the kernel sees, and a window whose N exceeds it makes the pair bad; max_qlen bounds the query window as in the untranslated
  * entries.  The host entries size both from the longest windows.
  *
- * Refused with -1 and a pmx_last_error() text before any GPU work: any other mode or width; PMX_WANT_STATS and PMX_WANT_CIGAR (this
- * side has no traceback yet; the hit list is the interface for the pass that will have); a PSSM matrix; a matrix of more than 128
+ * Refused with -1 and a pmx_last_error() text before any GPU work: any other mode or width; PMX_WANT_STATS and PMX_WANT_CIGAR (these
+ * entries have no traceback; the hit list is the interface for the pass that has: the _frameshift_ref_cigar entries below); a PSSM matrix; a matrix of more than 128
  * symbols; frameshift < 0; a strand mode outside 0 .. 2; strand bytes per pair together with a strand mode other than
  * PMX_STRAND_FORWARD; max_qlen above PMX_FRAMESHIFT_REF_MAX_QUERY; a device search with PMX_STRAND_BOTH, capacity > 0 and no strand
  * output; everything the corresponding stranded or untranslated entry refuses, with the same texts.  n == 0 / nq == 0 behave as
@@ -1168,6 +1168,90 @@ int pmx_swfsc_strip_rows(void);
 int pmx_swfsc_lane_rows(void);
 long long pmx_swfsc_bound_bytes_per_slot(int max_rlen);
 int pmx_swfsc_max_msize(void);
+
+/* Frameshift traceback, reference side (extension): the alignment behind a reference-side frameshift record -- CIGAR text with
+ * frameshift operators, the begin of the path, and statistics -- as a second pass over listed pairs, typically the hit pairs and strand
+ * bytes a pmx_search_*_frameshift_ref search returned (the hit list is the interface).  It tells WHERE in a contig the frameshift is.
+ * The recurrence, the codon stream, the record, the strand rules and the limits are those of "Frameshift-aware translated search,
+ * reference side" above: rows i are the query protein's letters, columns j the letters of the oriented reference window's codon stream
+ * T, s is indexed (query letter, stream letter); records and strand bytes are byte-identical to
+ * pmx_align_pairs_frameshift_ref[_device].  New is the path.  It is deterministic and keeps the precedence of the query-side
+ * "Frameshift traceback" section, state by state.
+ *
+ * Decisions at cell (i, j).
+ *   H source.  If M >= E and M >= F the source is M; otherwise if F >= E it is F; otherwise it is E.  If the resulting H <= 0 the cell
+ *     is ZERO: H = 0 and no path passes through it.
+ *   D source (where the H source is M).  With h3 = H(i-1,j-3), h2 = H(i-1,j-2) - fs, h4 = H(i-1,j-4) - fs, D = max(0, h3, h2, h4):
+ *     START if D == 0 (zero wins every tie); otherwise IN-FRAME if h3 == D; otherwise SHORT (2 columns) if h2 == D; otherwise LONG
+ *     (4 columns).  Terms with a negative index are 0 for H, as in the recurrence.
+ *   E opened iff H(i,j-3) - open > E(i,j-3) - extend, strictly; otherwise it is extended.
+ *   F opened iff H(i-1,j) - open > F(i-1,j) - extend, strictly.
+ *
+ * The walk starts at cell (end_query, end_ref - 2) in state H.
+ *   State H, M source: emit a match column -- '=' if the two letters map to the same matrix index, otherwise 'X' -- then: START: the
+ *     path begins at this cell, stop; IN-FRAME: go to (i-1, j-3); SHORT: emit '/' and go to (i-1, j-2); LONG: emit '\' and go to
+ *     (i-1, j-4).
+ *   State H, F source / E source: switch to state F / E at the same cell.
+ *   State F at (i, j): one query letter against a gap -- emit the query-gap op and go to (i-1, j); the state becomes H if F(i, j) was
+ *     opened, else stays F.
+ *   State E at (i, j): one whole reference codon against a gap -- emit the codon-gap op and go to (i, j-3); the state becomes H if
+ *     E(i, j) was opened.
+ *
+ * The text is in path order from begin to end, run-length encoded as <count><op>.  '=' and 'X' stand for one query letter against one
+ * reference codon.  The query-gap op is the letter of the F / DEL state and the codon-gap op the letter of the E / INS state: 'I' and
+ * 'D' by default, following PMX_CIGAR_SWAP_ID (pmx_conventions.h) -- so 'I' is, as everywhere here, query material the reference lacks
+ * and 'D' reference material the query lacks.  '/' means one nucleotide is missing from the reference -- the next codon overlaps the
+ * previous one by one base; '\' means one nucleotide too many.  A frameshift op sits directly in front of the match column it leads
+ * into; two of them are never adjacent, so their count is always 1.
+ * UNITS: '=', 'X' AND THE CODON-GAP OP CONSUME THREE REFERENCE NUCLEOTIDES; '/' TAKES ONE BACK; '\' ADDS ONE.  '=', 'X' AND THE
+ * QUERY-GAP OP CONSUME ONE QUERY LETTER.
+ *
+ * Begins.  beg[2k] = beg_query is the row of the START cell, in letters; beg[2k+1] = beg_ref its column: the first nucleotide of the
+ * first codon in the oriented reference window.  A zero-score record has an empty text and begins (end_query + 1, end_ref + 1) =
+ * (1, 3).  A bad pair has the bad record, strand 0, an empty text, begins -1 / -1 and zero statistics; its neighbours are unaffected.
+ *
+ * Statistics (pmx_stats_t).  matches = the number of '=' columns; similar = the number of match columns with a positive matrix score;
+ * length = match columns + gap columns, a codon gap counting 1.  Frameshift ops are not columns.
+ *
+ * What follows, for every non-empty text:
+ *   - its first and its last op are match columns;
+ *   - end_query - beg_query + 1 == match columns + query gaps;
+ *   - end_ref - beg_ref + 1 == 3 (match columns + codon gaps) - #'/' + #'\';
+ *   - re-scoring the text from (beg_query, beg_ref) -- matrix scores, open / extend per gap run of one kind, fs per frameshift op --
+ *     gives exactly the record's score and end cell;
+ *   - it has at most m + N ops.
+ *
+ * cfg->want must hold PMX_WANT_CIGAR, optionally with PMX_WANT_STATS; the statistics buffer is present iff PMX_WANT_STATS is set.
+ * Refused with -1 and the existing pmx_last_error() texts before any GPU work: everything pmx_align_pairs_frameshift_ref[_device]
+ * refuses (max_qlen above PMX_FRAMESHIFT_REF_MAX_QUERY among it), everything the query-side traceback entries refuse about their
+ * outputs, and a call in which four slots -- one workgroup -- exceed the bound on a chunk's trace.  The score and search entries of
+ * this side keep refusing PMX_WANT_CIGAR.  Strand arguments speak of the REFERENCE's strand; with PMX_STRAND_BOTH both strands are
+ * swept and the walk runs over the winner's trace.  d_beg (2 n) is optional.  The text buffer follows
+ * pmx_align_pairs_frameshift_cigar[_device]: offsets start at 0, d_cigar_off[n] is the number of bytes needed, a pair whose text would
+ * cross cigar_capacity is not written, chunk_pairs never changes a byte; the host entry sizes the text at 32 bytes per pair, runs once
+ * more at the exact size if that was too little, and *cigar_buf is released with pmx_free.
+ *
+ * Scratch.  Beside the score entry's: 192 bytes of trace per step and strip of 160 query letters for each slot, a strip having
+ * max_rlen + 15 steps -- pmx_swfsc_trace_bytes_per_slot(max_qlen, max_rlen), EVERY CELL OF THE m x N MATRIX, so the bound is what
+ * limits a long reference -- bounded at 256 MiB per chunk (the value switch PMX_CIGAR_CHUNK_BYTES sets another bound): a chunk whose
+ * slots need more runs in parts, sweep then walk, and no byte of any output depends on the parts.  pmx_last_kernel() names the trace
+ * instantiation of the last part, "pmx_swfsc_kernel<16,10,trace>", with "/strips" for queries beyond one strip. */
+int pmx_align_pairs_frameshift_ref_cigar_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats /* iff PMX_WANT_STATS */,
+                                                int32_t *d_beg /* 2 n, optional */,
+                                                char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off /* n + 1 */,
+                                                void *stream, const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_frameshift_ref_cigar(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                         int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                         int32_t frameshift, const uint8_t *code,
+                                         pmx_record_t *out, uint8_t *strand_out, pmx_stats_t *stats_out /* iff PMX_WANT_STATS */,
+                                         int32_t *beg /* 2 n, optional */, char **cigar_buf, int64_t *cigar_off /* n + 1 */,
+                                         const pmx_pairs_opts_t *opts);
+/* Test hook: the trace scratch of one slot of the reference-side trace sweep for queries of up to max_qlen letters and streams of up
+ * to max_rlen letters. */
+long long pmx_swfsc_trace_bytes_per_slot(int max_qlen, int max_rlen);
 
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).

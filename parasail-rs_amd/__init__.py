@@ -375,6 +375,12 @@ _sig("pmx_search_topk_frameshift_ref_device", C.c_int, C.POINTER(pmx_config_t), 
      C.c_void_p, C.POINTER(pmx_pairs_opts_t), C.c_int, C.c_void_p, C.c_int32, C.c_void_p)
 _sig("pmx_search_topk_frameshift_ref", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.c_int, C.c_int32, C.c_void_p, C.POINTER(C.POINTER(pmx_topk_strand_hits_t)))
+_sig("pmx_swfsc_trace_bytes_per_slot", C.c_longlong, C.c_int, C.c_int)
+_sig("pmx_align_pairs_frameshift_ref_cigar_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_frameshift_ref_cigar", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -1117,8 +1123,25 @@ class Aligner:
         `strand` is 0, 1, "both" or one byte per pair, as align_pairs(frameshift=) takes it: PairHits.pairs and PairHits.strand of
         search_pairs(frameshift=) or search_topk(frameshift=) are accepted as they are.  Returns (records, cigars, begins, strand)
         or, with stats=True, (records, cigars, begins, strand, stats): matches, similar and length along the path."""
+        return self._frameshift_cigar(lib.pmx_align_pairs_frameshift_cigar, "align_pairs_frameshift_cigar", Q, R, pairs, frameshift, strand,
+                                      code, stats, chunk_pairs)
+
+    def align_pairs_frameshift_ref_cigar(self, Q, R, pairs, ref_frameshift, ref_strand=0, code=None, stats=False, chunk_pairs=0):
+        """The alignments behind align_pairs(..., ref_frameshift=): the same records and strand bytes, and for every pair the CIGAR
+        text of its path -- '=' / 'X' one query letter against one reference codon, 'I' a query letter against a gap, 'D' a whole
+        reference codon against a gap, '/' one nucleotide missing from the REFERENCE, '\\' one too many (include/parasail_amd.h,
+        "Frameshift traceback, reference side") -- and the path's begin, int32 [n, 2]: the query letter, and the first nucleotide of
+        the first codon in the oriented reference window.  `ref_strand` is 0, 1, "both" or one byte per pair, as
+        align_pairs(ref_frameshift=) takes it: PairHits.pairs and PairHits.strand of search_pairs(ref_frameshift=) or
+        search_topk(ref_frameshift=) are accepted as they are.  Returns (records, cigars, begins, strand) or, with stats=True,
+        (records, cigars, begins, strand, stats): matches, similar and length along the path."""
+        return self._frameshift_cigar(lib.pmx_align_pairs_frameshift_ref_cigar, "align_pairs_frameshift_ref_cigar", Q, R, pairs, ref_frameshift,
+                                      ref_strand, code, stats, chunk_pairs)
+
+    def _frameshift_cigar(self, entry, name, Q, R, pairs, frameshift, strand, code, stats, chunk_pairs):
+        """The host traceback entry of either side (`entry`) over listed pairs."""
         if not self._profile.is_null():
-            raise BatchError("align_pairs_frameshift_cigar takes no profile")
+            raise BatchError(name + " takes no profile")
         pairs = as_pairs(pairs)
         n = len(pairs)
         cfg = self._config()
@@ -1138,11 +1161,11 @@ class Aligner:
         coff = np.zeros(n + 1, dtype=np.int64)
         cbuf = C.c_void_p()
         opts = pmx_pairs_opts_t(int(chunk_pairs))
-        rc = lib.pmx_align_pairs_frameshift_cigar(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
-                                                  per_pair.ctypes.data if per_pair is not None else None, mode, int(frameshift),
-                                                  code.ctypes.data if code is not None else None, out.ctypes.data, won.ctypes.data,
-                                                  st.ctypes.data if st is not None else None, beg.ctypes.data, C.byref(cbuf),
-                                                  coff.ctypes.data, C.byref(opts))
+        rc = entry(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data,
+                   per_pair.ctypes.data if per_pair is not None else None, mode, int(frameshift),
+                   code.ctypes.data if code is not None else None, out.ctypes.data, won.ctypes.data,
+                   st.ctypes.data if st is not None else None, beg.ctypes.data, C.byref(cbuf),
+                   coff.ctypes.data, C.byref(opts))
         if rc:
             raise BatchError(lib.pmx_last_error().decode())
         res = (out, _take_cigars(cbuf, coff), beg, won)
@@ -2032,6 +2055,21 @@ def align_pairs_frameshift_cigar_device(cfg, Q, R, n, d_pairs, d_strand, strand_
                                                      int(frameshift), code.ctypes.data if code is not None else None, max_qlen, max_rlen,
                                                      d_out, d_strand_out, d_stats, d_beg, d_cigar_text, int(cigar_capacity), d_cigar_off,
                                                      stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_frameshift_ref_cigar_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, max_qlen, max_rlen, d_out, d_strand_out,
+                                            d_stats, d_beg, d_cigar_text, cigar_capacity, d_cigar_off, stream=0, chunk_pairs=0, code=None):
+    """align_pairs_frameshift_ref_device with the traceback behind it (cfg.want: WANT_CIGAR, with WANT_STATS iff d_stats): the same
+    records and strand bytes -- the REFERENCE's strand --, the CIGAR text at d_cigar_off[k] of d_cigar_text, begins in d_beg (2 n int32,
+    optional: query letter, reference nucleotide), the paths' statistics in d_stats.  max_rlen bounds W - 2, the stream's letters."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_align_pairs_frameshift_ref_cigar_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, int(strand_mode),
+                                                         int(frameshift), code.ctypes.data if code is not None else None, max_qlen, max_rlen,
+                                                         d_out, d_strand_out, d_stats, d_beg, d_cigar_text, int(cigar_capacity), d_cigar_off,
+                                                         stream, C.byref(opts))
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

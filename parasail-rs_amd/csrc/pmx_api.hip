@@ -4265,9 +4265,14 @@ static double frameshift_trace_bound()
     const char *forced = pmx_env("PMX_CIGAR_CHUNK_BYTES");
     return forced ? atof(forced) : PMX_PAIRS_CHUNK_BYTES;
 }
-static int frameshift_trace_bound_check(int32_t max_qlen, int32_t max_rlen)
+// The trace bytes of one slot: the query side's sweep stores by column, the reference side's by step (pmx_swfs.hip, pmx_swfsc.hip).
+static size_t frameshift_trace_bytes_per_slot(bool ref, int32_t max_qlen, int32_t max_rlen)
 {
-    const double four = 4.0 * (double)pmx_swfs_trace_bytes_per_slot(max_qlen, max_rlen), bound = frameshift_trace_bound();
+    return ref ? (size_t)pmx_swfsc_trace_bytes_per_slot(max_qlen, max_rlen) : pmx_swfs_trace_bytes_per_slot(max_qlen, max_rlen);
+}
+static int frameshift_trace_bound_check(size_t bytes_per_slot, int32_t max_qlen, int32_t max_rlen)
+{
+    const double four = 4.0 * (double)bytes_per_slot, bound = frameshift_trace_bound();
     if (four > bound) {
         set_err("four slots of frameshift trace, %.0f bytes at max_qlen %d and max_rlen %d, exceed the bound of %.0f bytes on a chunk's trace "
                 "scratch (256 MiB, or PMX_CIGAR_CHUNK_BYTES)", four, (int)max_qlen, (int)max_rlen, bound);
@@ -4282,6 +4287,8 @@ static int frameshift_trace_bound_check(int32_t max_qlen, int32_t max_rlen)
 // `st`: a part's scratch is free when the next part begins.  The text continues behind the parts and chunks before it
 // (d_text_off[c0 + p0], left by the part before on the same stream), so neither chunk_pairs nor the bound changes a byte.
 // Scratch: the trace in SCR_TRACE, the op slots in SCR_OPS and the walk's counts in SCR_CIG, which no other road of this call uses.
+// fr.ref: the side comes with the plan -- pmx_swfsc's trace form, strip test and boundary bytes, and the walk's <true>
+// form; the bound, the parts, the fold, the scan, the render and the text rebase are the same code.
 static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
                                   int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats,
                                   int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off,
@@ -4290,8 +4297,10 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
     const int per = fr.per;
-    const size_t tps = pmx_swfs_trace_bytes_per_slot(max_qlen, max_rlen);
-    const bool strips = max_qlen > pmx_swfs_strip_rows();
+    const bool ref = fr.ref;
+    const size_t tps = frameshift_trace_bytes_per_slot(ref, max_qlen, max_rlen);
+    const bool strips = max_qlen > (ref ? pmx_swfsc_strip_rows() : pmx_swfs_strip_rows());
+    const size_t bps = ref ? (size_t)pmx_swfsc_bound_bytes_per_slot(max_rlen) : pmx_swfs_bound_bytes_per_slot(max_rlen);
     int64_t part_slots = (int64_t)(frameshift_trace_bound() / (double)tps) / 4 * 4;           // (at least four: the caller has checked)
     part_slots = std::min<int64_t>(part_slots, ((int64_t)per * chunk + 3) / 4 * 4);
     const int64_t part = part_slots / per;
@@ -4301,7 +4310,7 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
     // a path has at most N + m ops (matches + reference gaps <= m, 2 matches + 3 codon gaps <= N + 2, frameshift ops <= matches - 1), so
     // the implicit op slot of N + m + 1 entries that pmx_launch_cigar_render_slots assumes per alignment slot holds it
     if (scratch_reserve(tps * (size_t)part_slots, &trace, SCR_TRACE) ||
-        (strips && scratch_reserve(pmx_swfs_bound_bytes_per_slot(max_rlen) * (size_t)part_slots, &bnd, SCR_SWFS)) ||
+        (strips && scratch_reserve(bps * (size_t)part_slots, &bnd, SCR_SWFS)) ||
         t.reserve_ops((size_t)part_slots * ((size_t)max_qlen + (size_t)max_rlen + 1)) ||
         scratch_carve(SCR_PSRCH, [&](Carver &c) { srec = c.take<pmx_record_t>((size_t)per * (size_t)chunk); }) ||
         scratch_carve(SCR_CIG, [&](Carver &c) {
@@ -4313,20 +4322,41 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
             for (int64_t p0 = 0; p0 < cn; p0 += part) {
                 const int64_t pn = std::min<int64_t>(part, cn - p0), s0 = per * p0, g0 = c0 + p0;
                 const PmxBatch pb = {b.q, b.qoff + s0, b.r, b.roff + s0, per * pn, max_qlen, max_rlen, 0, nullptr, nullptr, nullptr, 0, 0};
-                int rc = pmx_launch_swfs_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, trace, srec + s0, st, &g_last_kernel);
+                int rc = ref ? pmx_launch_swfsc_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, trace, srec + s0, st, &g_last_kernel)
+                             : pmx_launch_swfs_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, trace, srec + s0, st, &g_last_kernel);
                 if (rc) { set_err(rc < 0 ? "frameshift trace kernel launch failed: %s" : "the frameshift trace kernel does not take this batch%s", rc < 0 ? hipGetErrorString((hipError_t)(-rc)) : ""); return -1; }
                 uint8_t *won = d_strand_out ? d_strand_out + g0 : nullptr;
                 rc = pmx_launch_pairs_fold(srec + s0, nullptr, b.ok + s0, b.sflag + s0, pn, per, 0, d_out + g0, nullptr, won, nullptr, st);
                 if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
                 rc = pmx_launch_walkfs(dm.d, pn, per, per == 2 ? won : nullptr, b.q, b.qoff + s0, b.r, b.roff + s0, max_rlen, d_out + g0,
                                        (const uint8_t *)trace, (long long)tps, t.ops, t.nops, t.textlen, pair_qoff, pair_roff,
-                                       d_beg ? d_beg + 2 * g0 : nullptr, d_stats ? d_stats + g0 : nullptr, st);
+                                       d_beg ? d_beg + 2 * g0 : nullptr, d_stats ? d_stats + g0 : nullptr, st, ref);
                 if (rc) { set_err("frameshift walk launch failed (%d)", rc); return rc < 0 ? rc : -1; }
                 rc = t.render(pair_qoff, pair_roff, 0, pn, d_text, capacity, d_text_off + g0, st, g0 > 0 ? local_off : nullptr);
                 if (rc) return rc;
             }
             return 0;
         });
+}
+
+// Both device traceback entries: ref false pmx_align_pairs_frameshift_cigar_device, true pmx_align_pairs_frameshift_ref_cigar_device.
+static int align_pairs_codons_cigar_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                           int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                           int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                           pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats, int32_t *d_beg,
+                                           char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off,
+                                           void *stream, const pmx_pairs_opts_t *opts, bool ref)
+{
+    SlotPlan fr;
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, true, ref) ||
+        frameshift_cigar_outputs_check(cfg, d_stats, d_cigar_text, cigar_capacity, d_cigar_off) || byte_out_check(fr, n > 0, d_strand_out)) return -1;
+    if (n == 0) return 0;
+    if (frameshift_rows_check(max_qlen, ref) || frameshift_trace_bound_check(frameshift_trace_bytes_per_slot(ref, max_qlen, max_rlen), max_qlen, max_rlen) ||
+        pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats != nullptr, true)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run_codons_cigar(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, d_stats, d_beg, d_cigar_text, cigar_capacity,
+                                  d_cigar_off, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
 }
 
 extern "C" int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -4336,16 +4366,20 @@ extern "C" int pmx_align_pairs_frameshift_cigar_device(const pmx_config_t *cfg, 
                                                        char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off,
                                                        void *stream, const pmx_pairs_opts_t *opts)
 {
-    SlotPlan fr;
-    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, true) ||
-        frameshift_cigar_outputs_check(cfg, d_stats, d_cigar_text, cigar_capacity, d_cigar_off) || byte_out_check(fr, n > 0, d_strand_out)) return -1;
-    if (n == 0) return 0;
-    if (frameshift_rows_check(max_qlen) || frameshift_trace_bound_check(max_qlen, max_rlen) ||
-        pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats != nullptr, true)) return -1;
-    StreamGuard guard(stream);
-    if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return pairs_run_codons_cigar(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, d_stats, d_beg, d_cigar_text, cigar_capacity,
-                                  d_cigar_off, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
+    return align_pairs_codons_cigar_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, code, max_qlen, max_rlen, d_out, d_strand_out,
+                                           d_stats, d_beg, d_cigar_text, cigar_capacity, d_cigar_off, stream, opts, false);
+}
+
+// ---- frameshift traceback, reference side: the trace form of pmx_swfsc, the <true> form of the walk, the same road ----
+extern "C" int pmx_align_pairs_frameshift_ref_cigar_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                           int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                           int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                           pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats, int32_t *d_beg,
+                                                           char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off,
+                                                           void *stream, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_codons_cigar_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, code, max_qlen, max_rlen, d_out, d_strand_out,
+                                           d_stats, d_beg, d_cigar_text, cigar_capacity, d_cigar_off, stream, opts, true);
 }
 
 extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
@@ -4805,7 +4839,7 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
                                        int32_t frameshift, const uint8_t *code, pmx_record_t *out, uint8_t *strand_out,
                                        const pmx_pairs_opts_t *opts, bool traceback,
                                        pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off,
-                                       bool ref = false /* pmx_align_pairs_frameshift_ref (no traceback): the stream is the reference's */)
+                                       bool ref = false /* pmx_align_pairs_frameshift_ref[_cigar]: the stream is the reference's */)
 {
     SlotPlan fr;
     if (listed_entry_check(cfg, Q, R, n, pairs, out, opts) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr, traceback, ref) ||
@@ -4815,7 +4849,9 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
     int64_t capacity = 32 * n + 256;                      // (the run-length text of a hit is a few runs; a batch of noise runs twice)
     DevBuf<int64_t> dtoff; DevBuf<int32_t> dbeg; DevBuf<char> dtext;
     const int rc = translated_pairs_host(cfg, Q, R, n, pairs, strand, fr, out, stats_out, strand_out, opts, traceback, false,
-        [&](int32_t mq, int32_t mr, bool known) { return frameshift_rows_check(mq, ref) || (traceback && known && frameshift_trace_bound_check(mq, mr)) ? -1 : 0; },
+        [&](int32_t mq, int32_t mr, bool known) {
+            return frameshift_rows_check(mq, ref) || (traceback && known && frameshift_trace_bound_check(frameshift_trace_bytes_per_slot(ref, mq, mr), mq, mr)) ? -1 : 0;
+        },
         [&](const pmx_config_t *c, const pmx_pair_t *dp, int32_t q32, int32_t r32, pmx_record_t *drec, pmx_stats_t *dst, uint8_t *dsout, hipStream_t st) -> int {
             const int64_t chunk = pairs_chunk(n, q32, r32, opts, fr.per);
             if (!traceback) return pairs_run_folded(c, Q, R, n, dp, fr, q32, r32, drec, nullptr, dsout, st, chunk);
@@ -4871,6 +4907,16 @@ extern "C" int pmx_align_pairs_frameshift_cigar(const pmx_config_t *cfg, const p
 {
     return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, true,
                                        stats_out, beg, cigar_buf, cigar_off);
+}
+
+extern "C" int pmx_align_pairs_frameshift_ref_cigar(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                    int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                                    int32_t frameshift, const uint8_t *code,
+                                                    pmx_record_t *out, uint8_t *strand_out, pmx_stats_t *stats_out, int32_t *beg,
+                                                    char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, true,
+                                       stats_out, beg, cigar_buf, cigar_off, true);
 }
 
 extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,

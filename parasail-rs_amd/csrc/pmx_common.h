@@ -358,6 +358,17 @@ enum { PMX_FSTR_START = 0, PMX_FSTR_INFRAME = 1, PMX_FSTR_SHORT = 2, PMX_FSTR_LO
        PMX_FSTR_EO = 8, PMX_FSTR_FO = 16,
        PMX_FSTR_LANE_ROWS = 10, PMX_FSTR_STRIP_ROWS = 160, PMX_FSTR_COL_BYTES = 192 };
 size_t pmx_swfs_trace_bytes_per_slot(int max_rows, int max_rlen);
+// The reference side's trace (pmx_swfsc.hip; semantics: "Frameshift traceback, reference side"): the same decision bytes,
+// STORED BY STEP.  Lane g of a slot's group finishes its ten rows of column t - g in step t, so a strip of a slot has
+// max_cols + PMX_FSTRC_SKEW steps of COL_BYTES bytes, and the byte of row i (a protein letter), column j (a stream letter) is
+// PMX_FSTRC_CELL(i, j, max_cols): ((strip * (max_cols + 15) + j + lane) * 16 + lane) * 12 + i % 10, strip = i / 160, lane = i % 160 / 10.
+enum { PMX_FSTRC_SKEW = PMX_FSTR_COL_BYTES / 12 - 1 };
+#define PMX_FSTRC_CELL(i, j, max_cols)                                                                                                      \
+    ((((size_t)((i) / PMX_FSTR_STRIP_ROWS) * (size_t)((max_cols) + PMX_FSTRC_SKEW) + (size_t)((j) + (i) % PMX_FSTR_STRIP_ROWS / PMX_FSTR_LANE_ROWS)) \
+          * (PMX_FSTR_COL_BYTES / 12) + (size_t)((i) % PMX_FSTR_STRIP_ROWS / PMX_FSTR_LANE_ROWS)) * 12 + (size_t)((i) % PMX_FSTR_LANE_ROWS))
+extern "C" long long pmx_swfsc_trace_bytes_per_slot(int max_qlen, int max_rlen);
+int pmx_launch_swfsc_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
+                           pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
 // One launch over b.n slots; trace (and bnd, when b.max_qlen exceeds one strip) hold the bytes of b.n slots rounded up to a multiple of four.
 int pmx_launch_swfs_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
                           pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
@@ -365,12 +376,12 @@ int pmx_launch_swfs_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, in
 // per * k + (win ? win[k] : 0) of the sweep's launch; qoff / roff are the launch's, per * n + 1 entries.  ops: run-length ops
 // (len << 4 | op; '/' = 9, '\\' = 10) from the end of the PAIR's op slots backwards -- a pair owns the qlen + rlen + 1 entries of each of
 // its slots -- with nops and textlen; pair_qoff / pair_roff [n + 1]: the offsets with which pmx_launch_cigar_render_slots (ops_base 0)
-// finds the pairs' op slots; beg (2 n) and stats_out are optional.
+// finds the pairs' op slots; beg (2 n) and stats_out are optional.  ref: the trace is pmx_launch_swfsc_trace's, rows the query protein.
 int pmx_launch_walkfs(const PmxDevMatrix &m, long long n, int per, const uint8_t *win,
                       const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, int max_rlen,
                       const pmx_record_t *recs, const uint8_t *trace, long long trace_bytes_per_slot,
                       uint32_t *ops, int32_t *nops, int32_t *textlen, int64_t *pair_qoff, int64_t *pair_roff,
-                      int32_t *beg, pmx_stats_t *stats_out, hipStream_t stream);
+                      int32_t *beg, pmx_stats_t *stats_out, hipStream_t stream, bool ref = false);
 // Per-query top-K (pmx_topk.hip; semantics: include/parasail_amd.h).  ks = min(k, |R|).  The running state of local row
 // li: st_keys / st_recs / st_stats[li * ks ..) hold st_held[li] entries in (score descending, j ascending) order, st_passing[li] = |P_i|
 // so far; the caller zeroes st_held (nq + 1 entries, the scan's input) and st_passing before the first chunk.  geometry: what the tile

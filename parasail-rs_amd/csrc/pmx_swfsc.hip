@@ -35,7 +35,14 @@
 
 #define PMX_SWFSC_NEG (-(1 << 29))
 
-template <int G, int R>
+// The trace form (TR; semantics: include/parasail_amd.h, "Frameshift traceback, reference side") stores one decision byte
+// per cell beside the same sweep, in PMX_FSTR_*'s encoding (pmx_common.h): bits 0 .. 2 where H came from -- START / INFRAME / SHORT /
+// LONG: from M, and which term D was; F; E; ZERO -- bit 3 that E of the cell was opened, bit 4 that F was.  Layout, per slot of the
+// launch: BY STEP, not by column.  In step t the group's lane g finishes its R = 10 rows of column t - g, so the 16 lanes' 12-byte
+// pieces (ten decisions, two bytes of padding, three dword stores) of one step are 192 contiguous bytes: row i of column j is byte
+// PMX_FSTRC_CELL(i, j, max_cols) = ((strip * (max_cols + G - 1) + j + lane) * G + lane) * 12 + i % R with strip = i / (G R) and
+// lane = i % (G R) / R.  A step of a strip is j + lane <= max_cols - 1 + G - 1: inside the strip's max_cols + G - 1 steps.
+template <int G, int R, bool TR>
 __global__ __launch_bounds__(64)
 void pmx_swfsc_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff,
                       const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff,
@@ -43,8 +50,10 @@ void pmx_swfsc_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
                       const int16_t *__restrict__ gmat, const uint8_t *__restrict__ gmap, int msize,
                       int open, int ext, int fs,
                       int2 *bnd /* per slot of the launch: 2 buffers x max_cols columns */,
-                      pmx_record_t *__restrict__ out)
+                      pmx_record_t *__restrict__ out,
+                      uint32_t *__restrict__ trace /* TR: per slot of the launch, trace_stride dwords; else unused */, long long trace_stride)
 {
+    static_assert(!TR || (R == PMX_FSTR_LANE_ROWS && G * R == PMX_FSTR_STRIP_ROWS), "the trace's 12 bytes per lane and step hold ten rows");
     static_assert(G == 16 || G == 64, "group_shift_up without a select");
     constexpr int NPW = 64 / G;                 // slots per wave = per workgroup
     constexpr int NEG = PMX_SWFSC_NEG;
@@ -66,6 +75,7 @@ void pmx_swfsc_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     m = min(m, max_qlen); N = min(N, max_cols);                    // (resolve keeps both inside; scratch and loops rely on it)
     const uint8_t *qs = qbuf + qb, *ts = rbuf + rb;
     int2 *bslot = bnd ? bnd + ((size_t)blockIdx.x * NPW + slotw) * 2 * (size_t)max_cols : nullptr;
+    uint32_t *tslot = TR ? trace + ((size_t)blockIdx.x * NPW + slotw) * (size_t)trace_stride : nullptr;
 
     int wm = m, wN = N;                                            // the wave's longest query and stream: uniform trip counts
 #pragma unroll
@@ -103,6 +113,7 @@ void pmx_swfsc_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
                     int hu = uH, fu = uF;                          // row i - 1 in column j
                     top[p] = uH;
                     int cm = 0;                                    // the column's maximum over the rows of the query (H >= 0)
+                    uint32_t tw[3] = {0u, 0u, 0u};                 // TR: the lane's ten decision bytes of this column
 #pragma unroll
                     for (int k = 0; k < R; ++k) {
                         const int o4 = Hh[p][k], o3 = Hh[p3][k], o2 = Hh[p2][k];
@@ -111,9 +122,20 @@ void pmx_swfsc_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
                         const int e = max(o3 - open, Eh[p3][k] - ext);
                         const int f = max(hu - open, fu - ext);
                         const int h = max(max(0, M), max(e, f));
+                        if (TR) {                                  // the compares of the contract, on the values at hand
+                            const uint32_t ds = D == 0 ? PMX_FSTR_START : a3 == D ? PMX_FSTR_INFRAME : a2 - fs == D ? PMX_FSTR_SHORT : PMX_FSTR_LONG;
+                            uint32_t c = (M >= e && M >= f) ? ds : f >= e ? PMX_FSTR_F : PMX_FSTR_E;
+                            c = h <= 0 ? PMX_FSTR_ZERO : c;
+                            c |= (o3 - open > Eh[p3][k] - ext ? PMX_FSTR_EO : 0u) | (hu - open > fu - ext ? PMX_FSTR_FO : 0u);
+                            tw[k / 4] |= c << (8 * (k % 4));
+                        }
                         Hh[p][k] = h; Eh[p][k] = e;
                         cm = max(cm, h & vm[k]);
                         a4 = o4; a3 = o3; a2 = o2; hu = h; fu = f;
+                    }
+                    if (TR) {                                      // step t0 + p = col + g of strip s: the group's 192 contiguous bytes
+                        uint32_t *tc = tslot + (((size_t)s * (size_t)(max_cols + G - 1) + (size_t)(col + g)) * G + g) * 3;
+                        tc[0] = tw[0]; tc[1] = tw[1]; tc[2] = tw[2];
                     }
                     // a new best is rare: one branch per column.  Columns ascend within a strip, so an equal score wins only from a
                     // later strip at a smaller column; within the column the first row that holds the maximum.
@@ -169,12 +191,43 @@ int pmx_launch_swfsc(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext
     const long long part = strips ? bnd_slots / NPW * NPW : b.n;
     for (long long p0 = 0; p0 < b.n; p0 += part) {
         const long long pn = b.n - p0 < part ? b.n - p0 : part;
-        hipLaunchKernelGGL((pmx_swfsc_kernel<G, R>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfsc_lds_bytes(m.msize), stream,
+        hipLaunchKernelGGL((pmx_swfsc_kernel<G, R, false>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfsc_lds_bytes(m.msize), stream,
                            b.qbuf, b.qoff + p0, b.rbuf, b.roff + p0, pn, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
-                           open, ext, fs, strips ? (int2 *)bnd : nullptr, d_out + p0);
+                           open, ext, fs, strips ? (int2 *)bnd : nullptr, d_out + p0, (uint32_t *)nullptr, 0LL);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return -(int)e;
     }
     if (kernel_name) *kernel_name = strips ? "pmx_swfsc_kernel<16,10>/strips" : "pmx_swfsc_kernel<16,10>";
+    return 0;
+}
+
+// The trace form over n slots: the same sweep and records, and every cell's decision byte into `trace`, which holds
+// pmx_swfsc_trace_bytes_per_slot bytes for each of the launch's slots ROUNDED UP TO WHOLE WORKGROUPS of four (the idle slots of the
+// last workgroup repeat slot n - 1 into their own regions).  bnd: boundary scratch for as many slots when b.max_qlen exceeds one strip.
+// One launch: the caller cuts a chunk into parts that fit its scratch.  0 launched, 1 not eligible, <0 HIP error.
+extern "C" long long pmx_swfsc_trace_bytes_per_slot(int max_qlen, int max_rlen)
+{
+    const int strips = (max_qlen + pmx_swfsc_strip_rows() - 1) / pmx_swfsc_strip_rows();
+    return (long long)strips * ((long long)max_rlen + PMX_SWFSC_G - 1) * PMX_FSTR_COL_BYTES;
+}
+int pmx_launch_swfsc_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
+                           pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
+{
+    constexpr int G = PMX_SWFSC_G, R = PMX_SWFSC_R, NPW = 64 / G;
+    static_assert(PMX_FSTR_COL_BYTES == G * 12 && PMX_FSTR_LANE_ROWS == R && PMX_FSTR_STRIP_ROWS == G * R && PMX_FSTRC_SKEW == G - 1,
+                  "the walk's addressing (PMX_FSTRC_CELL, pmx_walkfs.hip)");
+    if (m.pssm || m.msize > pmx_swfsc_max_msize() || b.q_shared || !trace) return 1;
+    if (b.n <= 0) return 0;
+    const int cap = 1 << 28;
+    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
+    const bool strips = b.max_qlen > G * R;
+    if (strips && !bnd) return 1;
+    hipLaunchKernelGGL((pmx_swfsc_kernel<G, R, true>), dim3((unsigned)((b.n + NPW - 1) / NPW)), dim3(64), swfsc_lds_bytes(m.msize), stream,
+                       b.qbuf, b.qoff, b.rbuf, b.roff, b.n, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
+                       open, ext, fs, strips ? (int2 *)bnd : nullptr, d_out,
+                       (uint32_t *)trace, pmx_swfsc_trace_bytes_per_slot(b.max_qlen, b.max_rlen) / 4);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return -(int)e;
+    if (kernel_name) *kernel_name = strips ? "pmx_swfsc_kernel<16,10,trace>/strips" : "pmx_swfsc_kernel<16,10,trace>";
     return 0;
 }

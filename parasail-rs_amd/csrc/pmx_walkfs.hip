@@ -11,6 +11,11 @@
 // One lane per logical pair: the hits are few and a path is at most N / 3 + m dependent reads of one byte.  A pair's trace is the one of
 // the slot that won the strand fold.  The walk reads only cells inside the slot's N x m matrix and stores at most as many ops as the
 // pair's op slots hold; a step that would leave either ends the walk (the sweep's decisions never ask for one).
+//
+// REF (semantics: "Frameshift traceback, reference side"): the trace of pmx_swfsc_kernel<16,10,true>, the recurrence
+// transposed.  The state machine is the same; the side changes four things -- the step vectors (a match column goes one row up and two
+// to four columns back, F goes one row up, E three columns back), the start cell (end_query, end_ref - 2), the cell's address (stored by
+// step: PMX_FSTRC_CELL) and which buffer holds the protein (the query's; the stream is the reference's).
 // Plain C++, vector loads and stores only.
 #include "pmx_common.h"
 
@@ -18,9 +23,10 @@
 #define OP_X 8u
 #define OP_FS_SHORT PMX_OP_FRAMESHIFT_SHORT           // '/': one nucleotide missing from the read
 #define OP_FS_LONG PMX_OP_FRAMESHIFT_LONG             // the backslash: one nucleotide too many
-#define OP_FOR_INS_STATE PMX_BAM_OP_FOR_INS_STATE    // E: a reference letter against a gap (include/pmx_conventions.h)
-#define OP_FOR_DEL_STATE PMX_BAM_OP_FOR_DEL_STATE    // F: a codon against a gap
+#define OP_FOR_INS_STATE PMX_BAM_OP_FOR_INS_STATE    // E: a reference letter (REF: a whole reference codon) against a gap (include/pmx_conventions.h)
+#define OP_FOR_DEL_STATE PMX_BAM_OP_FOR_DEL_STATE    // F: a codon (REF: a query letter) against a gap
 
+template <bool REF>
 __global__ __launch_bounds__(256)
 void pmx_walkfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff,
                        const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff, long long n, int per,
@@ -50,6 +56,7 @@ void pmx_walkfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
     const uint8_t *tb = trace + (size_t)slot * (size_t)trace_stride;
     // the decision byte of cell (i, j) (layout: pmx_common.h)
     auto cell = [&](int i, int j) -> unsigned {
+        if (REF) return tb[PMX_FSTRC_CELL(i, j, max_rlen)];
         const int strip = i / PMX_FSTR_STRIP_ROWS, in = i - strip * PMX_FSTR_STRIP_ROWS, lane = in / PMX_FSTR_LANE_ROWS;
         return tb[((size_t)strip * max_rlen + j) * PMX_FSTR_COL_BYTES + lane * 12 + (in - lane * PMX_FSTR_LANE_ROWS)];
     };
@@ -65,7 +72,7 @@ void pmx_walkfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
 
     int bi = -1, bj = -1;
     if (!(rec.flags & PMX_FLAG_BAD_PAIR)) {
-        int i = rec.end_query - 2, j = rec.end_ref;
+        int i = REF ? rec.end_query : rec.end_query - 2, j = REF ? rec.end_ref - 2 : rec.end_ref;
         bi = rec.end_query + 1; bj = rec.end_ref + 1;      // an empty path, as the local walks report it
         int where = 0;                                   // 0 H, 1 E, 2 F
         bool open_path = rec.score > 0;
@@ -80,18 +87,18 @@ void pmx_walkfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
                 nM += a == b; nS += scores[a * msize + b] > 0; nL += 1;
                 bi = i; bj = j;
                 if (src == PMX_FSTR_START) open_path = false;
-                else if (src == PMX_FSTR_INFRAME) i -= 3;
-                else if (src == PMX_FSTR_SHORT) { add(OP_FS_SHORT); i -= 2; }
-                else { add(OP_FS_LONG); i -= 4; }
-                --j;
+                else if (src == PMX_FSTR_INFRAME) (REF ? j : i) -= 3;
+                else if (src == PMX_FSTR_SHORT) { add(OP_FS_SHORT); (REF ? j : i) -= 2; }
+                else { add(OP_FS_LONG); (REF ? j : i) -= 4; }
+                --(REF ? i : j);
             } else if (where == 1) {
                 add(OP_FOR_INS_STATE); nL += 1;
                 if (t & PMX_FSTR_EO) where = 0;
-                --j;
+                j -= REF ? 3 : 1;
             } else {
                 add(OP_FOR_DEL_STATE); nL += 1;
                 if (t & PMX_FSTR_FO) where = 0;
-                i -= 3;
+                i -= REF ? 1 : 3;
             }
         }
     }
@@ -106,11 +113,12 @@ int pmx_launch_walkfs(const PmxDevMatrix &m, long long n, int per, const uint8_t
                       const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, int max_rlen,
                       const pmx_record_t *recs, const uint8_t *trace, long long trace_bytes_per_slot,
                       uint32_t *ops, int32_t *nops, int32_t *textlen, int64_t *pair_qoff, int64_t *pair_roff,
-                      int32_t *beg, pmx_stats_t *stats_out, hipStream_t stream)
+                      int32_t *beg, pmx_stats_t *stats_out, hipStream_t stream, bool ref)
 {
     if (m.pssm || (per != 1 && per != 2)) return 1;
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(pmx_walkfs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, qbuf, qoff, rbuf, roff, n, per, win,
+    hipLaunchKernelGGL(ref ? pmx_walkfs_kernel<true> : pmx_walkfs_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       qbuf, qoff, rbuf, roff, n, per, win,
                        m.mapper, m.scores, m.msize, max_rlen, recs, trace, trace_bytes_per_slot, ops, nops, textlen, pair_qoff, pair_roff,
                        beg, stats_out);
     const hipError_t e = hipGetLastError();
