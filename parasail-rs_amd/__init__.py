@@ -915,14 +915,19 @@ class Aligner:
         self._fn, self.fn_name = fn, fn_name
         self.matrix, self.gap_open, self.gap_extend = matrix, gap_open, gap_extend
         self._profile, self.vec_strategy, self._bandwidth = profile, vec_strategy, bandwidth
+        # batch entries of a semi-global aligner only: a set of SG_* flags that replaces the one the function name spells
+        # (a name cannot say "no free end": without a specifier it means all four)
+        self.sg_flags = None
 
     @staticmethod
     def new():
         return AlignerBuilder()
 
     def clone(self):
-        return Aligner(self._fn, self.fn_name, self.matrix, self.gap_open, self.gap_extend, self._profile,
-                       self.vec_strategy, self._bandwidth)
+        al = Aligner(self._fn, self.fn_name, self.matrix, self.gap_open, self.gap_extend, self._profile,
+                     self.vec_strategy, self._bandwidth)
+        al.sg_flags = self.sg_flags
+        return al
 
     def align(self, query, reference):           # :397-452
         ref_len = len(reference)
@@ -970,6 +975,8 @@ class Aligner:
                 for t in q + d:
                     flags |= {"_qb": SG_QB, "_qe": SG_QE, "_qx": SG_QB | SG_QE,
                               "_db": SG_DB, "_de": SG_DE, "_dx": SG_DB | SG_DE}[t]
+            if self.sg_flags is not None:
+                flags = int(self.sg_flags) & SG_ALL
         width = name.rsplit("_", 1)[1]
         if "_stats" in name:
             want |= WANT_STATS

@@ -7,6 +7,7 @@
 // owns handles, dispatch-name parsing, device staging and result marshalling only.
 #include "pmx_common.h"
 #include "pmx_switches.h"
+#include "pmx_strip.h"
 #include <chrono>
 #include <future>
 #include "pmx_matrices.h"
@@ -1695,8 +1696,7 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
     }
     uint32_t *tbuf = nullptr;
     if (scratch_reserve(cbytes * (two ? 2 : 1) + rbytes, (void **)&tbuf, SCR_TRACE)) return -1;
-    const bool sg = cfg->mode == PMX_MODE_SG;
-    const int col_pen = !(sg && (cfg->sg_flags & PMX_SG_QB)), row_pen = !(sg && (cfg->sg_flags & PMX_SG_DB));
+    const PmxEnds ends = pmx_ends(cfg->mode, cfg->sg_flags);      // (nw or sg: the plan above takes no other mode)
     // one chunk: positions [t.c0, t.c0 + t.n) of the batch; sweep into the t.buf-th trace buffer (of tb_bytes), the walk behind it
     auto run_chunk = [&](const ChunkTurn &t, size_t tb_bytes, bool short_waves) -> int {
         const long long c0 = t.c0;
@@ -1720,7 +1720,7 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
         int rc = pmx_launch_nwsgq_trace(variant_k, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, out_k, tb, Tmax_k, t.sweep);
         if (rc) { set_err("shared-profile traceback sweep failed (%d)", rc); return rc < 0 ? rc : -1; }
         if ((rc = chunk_sweep_launched(t)) != 0) return rc;
-        rc = pmx_launch_walkp(gsel_k, R_k, bk, dm.d, cfg->mode, cfg->open, cfg->extend, Tmax_k, 0, st_k, row_pen, col_pen,
+        rc = pmx_launch_walkp(gsel_k, R_k, bk, dm.d, cfg->mode, cfg->open, cfg->extend, Tmax_k, 0, st_k, ends.row_pen, ends.col_pen,
                               tb, out_k, nullptr, nullptr, 0, nullptr, nullptr, nullptr, t.walk);
         if (rc) { set_err("statistics walk failed (%d)", rc); return rc < 0 ? rc : -1; }
         return chunk_walk_launched(t);
@@ -1817,9 +1817,9 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
     const int wmax = cfg->width == 8 ? 127 : cfg->width == 16 ? 32767 : 2147483647;
     if (cfg->mode == PMX_MODE_SW) sat_above = wmax;
     else if (cfg->width == 8 || cfg->width == 16) {
-        const bool pen_col = cfg->mode == PMX_MODE_NW || !(cfg->sg_flags & PMX_SG_QB), pen_row = cfg->mode == PMX_MODE_NW || !(cfg->sg_flags & PMX_SG_DB);
-        const long long lo = std::min(pen_col ? -((long long)cfg->open + (long long)(max_qlen - 1) * cfg->extend) : 0LL,
-                                      pen_row ? -((long long)cfg->open + (long long)(max_rlen - 1) * cfg->extend) : 0LL);
+        const PmxEnds ends = pmx_ends(cfg->mode, cfg->sg_flags);
+        const long long lo = std::min(ends.col_pen ? -((long long)cfg->open + (long long)(max_qlen - 1) * cfg->extend) : 0LL,
+                                      ends.row_pen ? -((long long)cfg->open + (long long)(max_rlen - 1) * cfg->extend) : 0LL);
         if (n == 1 && lo < -(long long)wmax - 1) force_sat = 1; else return 1;     // (inside the range: the general kernel tracks min / max H)
     }
     // R = 4 (256-row bands) also for batches that fill the chip: 1 024-row bands (R = 16) share a step's fixed work among four

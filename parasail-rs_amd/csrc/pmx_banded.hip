@@ -16,6 +16,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <algorithm>
 
 #define B_NEG (INT32_MIN / 2)
@@ -80,10 +81,9 @@ void pmx_banded_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
     const int ql = q_shared ? q_shared : (int)(qoff[pp + 1] - qb), rl = (int)(roff[pp + 1] - rb);
     const uint8_t *q = qbuf + qb, *r = rbuf + rb;
     const int d0 = diag ? diag[pp] : 0;
-    const bool sw = mode == PMX_MODE_SW, sg = mode == PMX_MODE_SG;
-    const bool s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
-    const bool col_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_QB));   // H(i, -1) penalised
-    const bool row_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_DB));   // H(-1, j) penalised
+    const bool sw = mode == PMX_MODE_SW;
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
+    const bool s1_end = ends.s1_end, s2_end = ends.s2_end, col_pen = ends.col_pen, row_pen = ends.row_pen;
     auto rowB = [&](int j) -> int { return sw ? 0 : (row_pen ? -(open + j * ext) : 0); };
     auto colB = [&](int i) -> int { return sw ? 0 : (col_pen ? -(open + i * ext) : 0); };
 
@@ -252,10 +252,8 @@ void pmx_banded_staged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *_
     const long long qb = q_shared ? 0 : qoff[pp], rb = roff[pp];
     const int ql = min(q_shared ? q_shared : (int)(qoff[pp + 1] - qb), QC), rl = min((int)(roff[pp + 1] - rb), RC);
     const int d0 = diag ? diag[pp] : 0;
-    const bool sg = mode == PMX_MODE_SG;
-    const bool s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
-    const bool col_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_QB));
-    const bool row_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_DB));
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
+    const bool s1_end = ends.s1_end, s2_end = ends.s2_end, col_pen = ends.col_pen, row_pen = ends.row_pen;
     auto rowB = [&](int j) -> int { return SW ? 0 : (row_pen ? -(open + j * ext) : 0); };
     auto colB = [&](int i) -> int { return SW ? 0 : (col_pen ? -(open + i * ext) : 0); };
 
@@ -812,8 +810,7 @@ int pmx_launch_banded(int mode, int sg_flags, int open, int ext, const PmxDevMat
 #undef LPK
             if (kernel_name) *kernel_name = shared_rows ? "pmx_banded_packed_kernel/shared query rows"
                                            : (m.msize <= 7 && !pmx_env("PMX_BANDED_NO_ROWPERM")) ? "pmx_banded_packed_kernel/matrix rows" : "pmx_banded_packed_kernel";
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? 0 : -(int)e;
+            return pmx_launched();
         }
     }
 #define LB(LP) hipLaunchKernelGGL((pmx_banded_kernel<LP>), dim3((unsigned)((n + 64 / LP - 1) / (64 / LP))), dim3(64), 0, stream, \
@@ -832,8 +829,7 @@ int pmx_launch_banded(int mode, int sg_flags, int open, int ext, const PmxDevMat
 #undef LB
 #undef LS
     if (kernel_name) *kernel_name = staged ? "pmx_banded_staged_kernel" : "pmx_banded_kernel";
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // ---- trace form: geometry and launch -----------------------------------------------------------------------------------
@@ -892,6 +888,5 @@ int pmx_launch_banded_trace(int mode, int sg_flags, int open, int ext, const Pmx
 #undef LBT
 #undef LST
     if (kernel_name) *kernel_name = staged ? "pmx_banded_staged_kernel/trace" : "pmx_banded_kernel/trace";
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

@@ -36,6 +36,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -129,10 +130,8 @@ void pmx_bstrip_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
 
     const int lane = threadIdx.x;
     const int l16 = lane & 15, g = l16 / SUBG, sub = l16 % SUBG, grp = (lane >> 4) * SUBG + sub;
-    const bool sg = k.mode == PMX_MODE_SG;
-    const bool s1_end = sg && (k.sg_flags & PMX_SG_QE), s2_end = sg && (k.sg_flags & PMX_SG_DE);
-    const bool col_pen = k.mode == PMX_MODE_NW || (sg && !(k.sg_flags & PMX_SG_QB));   // H(i, -1) penalised
-    const bool row_pen = k.mode == PMX_MODE_NW || (sg && !(k.sg_flags & PMX_SG_DB));   // H(-1, j) penalised
+    const PmxEnds ends = pmx_ends(k.mode, k.sg_flags);
+    const bool s1_end = ends.s1_end, s2_end = ends.s2_end, col_pen = ends.col_pen, row_pen = ends.row_pen;
     const int W = 2 * k.band + 1, eL = G * C - W, gLo = eL / C, cLoFirst = eL % C;
     const int open = k.open, ext = k.ext, Cg = open - ext;
     const int OB = Cg + A_ * ext;                    // score byte = score + OB
@@ -691,8 +690,7 @@ static int bs_launch(int guard /* 0: one leading cell, 1: every cell, 2: the fir
     if (guard == 2) { if constexpr (G == 8 && C == 13) BS_GO(-7); else return 1; }
     else if (guard == 1) BS_GO(C); else BS_GO(1);
 #undef BS_GO
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // 0 launched (retry pairs included), 1 not eligible, < 0 HIP error
@@ -752,6 +750,5 @@ int pmx_launch_bstrip(int mode, int sg_flags, int open, int ext, const PmxDevMat
     // pairs with a reference letter beyond the first four: the band-only kernel of pmx_banded.hip, driven by the device-side count
     pmx_banded_retry(mode, sg_flags, open, ext, m, n, qbuf, qoff, q_shared, rbuf, roff, band, diag, retry_list, retry_count, out, stream);
     if (kernel_name) *kernel_name = modev == 2 ? "pmx_bstrip_kernel/local" : modev == 1 ? "pmx_bstrip_kernel/double skew" : "pmx_bstrip_kernel/one skew";
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

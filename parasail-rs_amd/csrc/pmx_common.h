@@ -10,6 +10,9 @@
 // Raise the dynamic-LDS limit of a kernel once per (kernel, device); thread-safe.
 int pmx_ensure_lds_attr(const void *kernel, int bytes = 160 * 1024);
 
+// What a launcher returns behind its launch: 0, or the launch's HIP error negated.
+static inline int pmx_launched() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
+
 // Device-side view of a substitution matrix (built once per parasail_matrix_t, cached).
 struct PmxDevMatrix {
     const int16_t *scores;   // [rows*msize]: scores[qsym*msize + rsym], or for a PSSM scores[i*msize + rsym] (query row i)  (device)

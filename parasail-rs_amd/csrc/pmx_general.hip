@@ -21,6 +21,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 
 #define NEG_INF (INT32_MIN / 2)
 #ifndef PMX_MW_MAX_PAIRS
@@ -100,12 +101,8 @@ void pmx_general_kernel(const PmxGeneralArgs a)
 
     const int mode = a.mode, open = a.open, ext = a.ext, band_w = a.band;
     const int band_d = a.diag ? a.diag[pair] : 0;             // band centre: cells with |(j - i) - band_d| > band_w are excluded
-    const bool s1_beg = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_QB);
-    const bool s1_end = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_QE);
-    const bool s2_beg = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_DB);
-    const bool s2_end = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_DE);
-    const bool col_pen = mode == PMX_MODE_NW || (mode == PMX_MODE_SG && !s1_beg);  // H(i,-1) penalised
-    const bool row_pen = mode == PMX_MODE_NW || (mode == PMX_MODE_SG && !s2_beg);  // H(-1,j) penalised
+    const PmxEnds ends = pmx_ends(mode, a.sg_flags);
+    const bool s1_end = ends.s1_end, s2_end = ends.s2_end, col_pen = ends.col_pen, row_pen = ends.row_pen;
 
     Cand best_sw = {NEG_INF, 0, 0, 0, 0, 0};      // sw: global best
     Cand best_row = {NEG_INF, 0, 0, 0, 0, 0};     // sg: best of the last row
@@ -405,12 +402,8 @@ void pmx_general_mw_kernel(const PmxGeneralArgs a)
 
     const int mode = a.mode, open = a.open, ext = a.ext, band_w = a.band;
     const int band_d = a.diag ? a.diag[pair] : 0;             // band centre: cells with |(j - i) - band_d| > band_w are excluded
-    const bool s1_beg = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_QB);
-    const bool s1_end = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_QE);
-    const bool s2_beg = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_DB);
-    const bool s2_end = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_DE);
-    const bool col_pen = mode == PMX_MODE_NW || (mode == PMX_MODE_SG && !s1_beg);  // H(i,-1) penalised
-    const bool row_pen = mode == PMX_MODE_NW || (mode == PMX_MODE_SG && !s2_beg);  // H(-1,j) penalised
+    const PmxEnds ends = pmx_ends(mode, a.sg_flags);
+    const bool s1_end = ends.s1_end, s2_end = ends.s2_end, col_pen = ends.col_pen, row_pen = ends.row_pen;
 
     Cand best_sw = {NEG_INF, 0, 0, 0, 0, 0};      // sw: global best
     Cand best_row = {NEG_INF, 0, 0, 0, 0, 0};     // sg: best of the last row
@@ -775,8 +768,7 @@ int pmx_launch_general(const PmxGeneralArgs &a_in, bool want_stats, hipStream_t 
         if (out) hipLaunchKernelGGL((pmx_general_kernel<false, true>), grid, block, lds, stream, a);
         else     hipLaunchKernelGGL((pmx_general_kernel<false, false>), grid, block, lds, stream, a);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // ---- traceback walk on the device: one lane per pair ---------------------------------------
@@ -843,8 +835,7 @@ int pmx_launch_walk(const PmxWalkArgs &a, hipStream_t stream)
     if (a.n <= 0) return 0;
     const unsigned blocks = (unsigned)((a.n + 63) / 64);
     hipLaunchKernelGGL(pmx_walk_kernel, dim3(blocks), dim3(64), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 __global__ void pmx_collect_saturated_kernel(const pmx_record_t *rec, long long n, int64_t *list, int *count, int mask)
@@ -859,8 +850,7 @@ int pmx_launch_collect_saturated(const pmx_record_t *rec, long long n, int64_t *
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int), stream);
     if (e != hipSuccess) return -(int)e;
     hipLaunchKernelGGL(pmx_collect_saturated_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, rec, n, list, count, mask);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // CIGAR text on the device: pass 1 measures each pair's text, pass 2 writes it at the caller's offsets
@@ -897,8 +887,7 @@ int pmx_launch_cigar_textlen(const uint32_t *ops, const int64_t *ops_off, const 
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_cigar_textlen_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, ops, ops_off, nops, textlen, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 int pmx_launch_cigar_render(const uint32_t *ops, const int64_t *ops_off, const int32_t *nops,
                             const int64_t *text_off, char *text, long long n, hipStream_t stream)
@@ -906,8 +895,7 @@ int pmx_launch_cigar_render(const uint32_t *ops, const int64_t *ops_off, const i
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_cigar_render_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, ops, ops_off, nops, text_off, text, n,
                        pmx_cigar_swapped());
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 
@@ -951,6 +939,5 @@ int pmx_launch_cigar_render_slots(const uint32_t *ops, const int64_t *qoff, cons
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_cigar_render_slots_kernel, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, stream,
                        ops, qoff, roff, ops_base, nops, text_off, text, capacity, n, pmx_cigar_swapped());
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

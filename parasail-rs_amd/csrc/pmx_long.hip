@@ -29,10 +29,11 @@
 //
 // End positions by the oracle's rules (oracle/pmx_oracle.c): sw -- first maximum in column-major order: every lane keeps its
 // running best, the step at which it was first strictly exceeded and its strip at that step; the bands' winners are merged by
-// (score, column, row) in a finalize kernel.  nw -- the corner.  sg -- first maximum of the last row by ascending column,
-// then the last column (smallest row) only if strictly greater; free begins are boundary values.
+// (score, column, row) in a finalize kernel.  nw / sg -- pmx_sg_end over the bands' last-row and last-column candidates
+// (DESIGN.md 2.1a); free begins are boundary values.
 #include "pmx_common.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <type_traits>
 
 #define LONG_NEG (-(1 << 30))
@@ -96,6 +97,7 @@ void pmx_long32_kernel(PmxLongArgs a)
     }
     __syncthreads();
 
+    // (the sweeps spell staging and boundary flags out, not pmx_strip.h's helpers: the sg leg of profiles/r19 ran above the parent's range)
     const bool pen_col = MODE == PMX_MODE_NW || (SG && !(a.sg_flags & PMX_SG_QB));      // column -1 (query begin) is penalised
     const bool pen_row = MODE == PMX_MODE_NW || (SG && !(a.sg_flags & PMX_SG_DB));      // row -1 (reference begin) is penalised
     auto left = [&](int i) -> int { return i < 0 ? 0 : (pen_col ? -(open + i * ext) : 0); };      // H(i, -1); H(-1, -1) = 0
@@ -594,18 +596,13 @@ __global__ void pmx_long_finalize_kernel(PmxLongArgs a, int mode, int R)
         if (sc > a.sat_above) rec.flags |= PMX_FLAG_SATURATED;
     } else {
         const int *last = cand + 8 * (NB - 1);
-        const bool s1_end = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_QE), s2_end = mode == PMX_MODE_SG && (a.sg_flags & PMX_SG_DE);
-        if (!s1_end && !s2_end) { rec.score = last[7]; rec.end_query = ql - 1; rec.end_ref = rl - 1; }
-        else {
-            int sc = LONG_NEG * 2 + 1, eq = 0, er = 0;
-            if (s2_end) { sc = last[5]; eq = ql - 1; er = last[6]; }
-            if (s1_end) {
-                int cs = LONG_NEG * 2 + 1, crow = 0;
-                for (int b = 0; b < NB; ++b) if (cand[8 * b + 3] > cs) { cs = cand[8 * b + 3]; crow = cand[8 * b + 4]; }
-                if (cs > sc) { sc = cs; eq = crow; er = rl - 1; }
-            }
-            rec.score = sc; rec.end_query = eq; rec.end_ref = er;
-        }
+        const PmxEnds ends = pmx_ends(mode, a.sg_flags);
+        // the last column's best over the bands, the upper band first (every band writes a candidate of at least LONG_NEG for its
+        // rows of the last column, so with a free query end cs always leaves its initial value)
+        int cs = LONG_NEG * 2 + 1, crow = 0;
+        if (ends.s1_end) for (int b = 0; b < NB; ++b) if (cand[8 * b + 3] > cs) { cs = cand[8 * b + 3]; crow = cand[8 * b + 4]; }
+        const PmxEnd e = pmx_sg_end(ends.s1_end, ends.s2_end, ql, rl, last[7], last[5], last[6], cs, crow);
+        rec.score = e.score; rec.end_query = e.end_query; rec.end_ref = e.end_ref;
         if (a.force_sat) rec.flags |= PMX_FLAG_SATURATED;
     }
     a.out[pair] = rec;
@@ -693,6 +690,5 @@ int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_f
     e = hipGetLastError();
     if (e != hipSuccess) return -(int)e;
     hipLaunchKernelGGL(pmx_long_finalize_kernel, dim3((unsigned)((b.n + 63) / 64)), dim3(64), 0, stream, a, mode, R);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

@@ -22,11 +22,12 @@
 //     (needs open >= extend, which the reference asks for: src/aligner/mod.rs:139-153).
 //     No lane ever needs a special case: lane 0's "row above" is the constant pair (H = 0, F = -inf).
 //   * Results are captured, not tracked: nw reads the last row at column rlen-1; sg keeps the first
-//     maximum of the last row (reference end free) and of the last column (query end free; last column
-//     wins only if strictly greater -- oracle/pmx_oracle.c states the rule).
+//     maximum of the last row (reference end free) and of the last column (query end free); pmx_sg_end
+//     chooses among them (which also states the pair table and the virtual columns).
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <cstdlib>
 
 #ifndef PMX_QSTAGE
@@ -89,22 +90,11 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
     unsigned char *rsym = lds + NP * PROF_STRIDE;
     int16_t *mat = reinterpret_cast<int16_t *>(rsym + NP * RP);
     unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((msize * msize * 2) & 7)) & 7));   // per pair: q offset, qlen, r offset, rlen, pair index
+    const PmxPairTab ptab{reinterpret_cast<long long *>(pmx_after_matrix(map, msize * msize))};
 
     const long long pair0 = (long long)blockIdx.x * NP;
-
-    for (int i = lane; i < msize * msize; i += 64) mat[i] = gmat[i];
-    for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
-    if (lane < NP) {
-        long long pos = pair0 + lane; if (pos >= n) pos = n - 1;
-        const long long pi = perm ? (long long)perm[pos] : pos;
-        const long long qb = q_shared ? 0 : qoff[pi], rb = roff[pi];
-        ptab[5 * lane + 0] = qb;
-        ptab[5 * lane + 1] = q_shared ? q_shared : (qoff[pi + 1] - qb);
-        ptab[5 * lane + 2] = rb;
-        ptab[5 * lane + 3] = roff[pi + 1] - rb;
-        ptab[5 * lane + 4] = (pair0 + lane < n) ? pi : -1;
-    }
+    pmx_stage_matrix(mat, map, gmat, gmap, msize * msize, lane, 64);
+    if (lane < NP) ptab.fill(lane, pair0, n, perm, qoff, roff, q_shared);
     __syncthreads();
     const uint8_t *qbase = qbuf;
     const uint8_t *rbase = rbuf;
@@ -112,24 +102,9 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
     // ---- reference symbols, G-1 virtual columns in front, pad behind ---------------------
     int max_rlen = 0;
 #pragma unroll
-    for (int p = 0; p < NP; ++p) max_rlen = max(max_rlen, (int)ptab[5 * p + 3]);
-    constexpr int UB = 8;
-    for (int item0 = 0; item0 < NP * RP; item0 += 64 * UB) {
-        unsigned char raw[UB]; bool ok[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            const int item = item0 + u * 64 + lane;
-            const int p = min(item / RP, NP - 1), j = item - p * RP;
-            const int jj = j - (G - 1);
-            ok[u] = item < NP * RP && jj >= 0 && jj < (int)ptab[5 * p + 3];
-            raw[u] = ok[u] ? rbase[ptab[5 * p + 2] + jj] : (unsigned char)0;
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            const int item = item0 + u * 64 + lane;
-            if (item < NP * RP) rsym[item] = ok[u] ? map[raw[u]] : (unsigned char)msize;
-        }
-    }
+    for (int p = 0; p < NP; ++p) max_rlen = max(max_rlen, ptab.rlen(p));
+    for (int p = 0; p < NP; ++p)
+        pmx_stage_ref_symbols<G, 8>(rsym + p * RP, RP, rbase + ptab.rbeg(p), ptab.rlen(p), map, msize, lane, 64);
 
     // ---- extended profiles: P virtual rows on top of the qlen real rows --------------------
     const int vrow_score = row_pen ? NEGS : 0;     // virtual row  x real symbol
@@ -142,8 +117,8 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
         for (int u = 0; u < QB; ++u) {
             const int item = (it0 + u) * 64 + lane;
             const int p = min(item / QP2, NP - 1), rp = item - p * QP2;
-            const int P = QP - (int)ptab[5 * p + 1];
-            const uint8_t *qp = qbase + ptab[5 * p + 0];
+            const int P = QP - ptab.qlen(p);
+            const uint8_t *qp = qbase + ptab.qbeg(p);
             v0[u] = item < NP * QP2 && 2 * rp >= P; v1[u] = item < NP * QP2 && 2 * rp + 1 >= P;
             r0[u] = v0[u] ? qp[2 * rp - P] : (unsigned char)0;
             r1[u] = v1[u] ? qp[2 * rp + 1 - P] : (unsigned char)0;
@@ -176,8 +151,8 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
     const unsigned char *rsB = rsym + pB * RP + (G - 1) - g;
     const int SYMSTRIDE = QP * 2;
 
-    const int PvA = QP - (int)ptab[5 * pA + 1], PvB = QP - (int)ptab[5 * pB + 1];   // virtual rows per half
-    const int rlA = (int)ptab[5 * pA + 3], rlB = (int)ptab[5 * pB + 3];
+    const int PvA = QP - ptab.qlen(pA), PvB = QP - ptab.qlen(pB);   // virtual rows per half
+    const int rlA = ptab.rlen(pA), rlB = ptab.rlen(pB);
     const v2s vOpen = PK((open & 0xFFFF) | (open << 16));
     const v2s vExt = PK((ext & 0xFFFF) | (ext << 16));
     const v2us one2 = {1, 1};
@@ -287,14 +262,8 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
 
     // ---- combine -----------------------------------------------------------------------
     // last-column candidates: reduce (value desc, extended row asc) over the slot's lanes
-    unsigned keyA = ((unsigned)(I32(bestcol) & 0xFFFF) << 16) | (0xFFFFu - (unsigned)(bestcoli & 0xFFFF));
-    unsigned keyB = ((unsigned)((unsigned)I32(bestcol) >> 16) << 16) | (0xFFFFu - ((unsigned)bestcoli >> 16));
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-        const unsigned oa = __shfl_xor(keyA, off, 64), ob = __shfl_xor(keyB, off, 64);
-        keyA = oa > keyA ? oa : keyA;
-        keyB = ob > keyB ? ob : keyB;
-    }
+    const unsigned keyA = pmx_slot_best_key<G>(pmx_slot_key(pmx_half(I32(bestcol), 0), pmx_half(bestcoli, 0)));
+    const unsigned keyB = pmx_slot_best_key<G>(pmx_slot_key(pmx_half(I32(bestcol), 1), pmx_half(bestcoli, 1)));
     // the last lane of the slot owns the last row: corner value and last-row maximum
     const int lastlane = slot * G + G - 1;
     const int resL = __shfl(res, lastlane, 64);
@@ -302,27 +271,15 @@ void pmx_nwsg16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restri
     if (g == 0) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const long long pi = ptab[5 * (2 * slot + h) + 4];
+            const long long pi = ptab.index(2 * slot + h);
             if (pi >= 0) {
-                const int ql = (int)ptab[5 * (2 * slot + h) + 1], rl = (int)ptab[5 * (2 * slot + h) + 3];
+                const int ql = ptab.qlen(2 * slot + h), rl = ptab.rlen(2 * slot + h);
                 const int P = QP - ql;
-                const int corner = ((h ? ((unsigned)resL >> 16) : (resL & 0xFFFF))) - NB;
+                const unsigned key = h ? keyB : keyA;
+                const PmxEnd e = pmx_sg_end(s1_end, s2_end, ql, rl, pmx_half(resL, h) - NB, pmx_half(browL, h) - NB, pmx_half(browjL, h),
+                                            pmx_key_value(key) - NB, pmx_key_row(key) - P);
                 pmx_record_t rec;
-                rec.flags = 0;
-                if (!s1_end && !s2_end) { rec.score = corner; rec.end_query = ql - 1; rec.end_ref = rl - 1; }
-                else {
-                    int best = -2147483647 - 1, ei = 0, ej = 0;
-                    if (s2_end) {
-                        best = (int)(h ? ((unsigned)browL >> 16) : (browL & 0xFFFF)) - NB;
-                        ei = ql - 1; ej = (int)(h ? ((unsigned)browjL >> 16) : (browjL & 0xFFFF));
-                    }
-                    if (s1_end) {
-                        const unsigned key = h ? keyB : keyA;
-                        const int cv = (int)(key >> 16) - NB;
-                        if (cv > best) { best = cv; ei = (int)(0xFFFFu - (key & 0xFFFFu)) - P; ej = rl - 1; }
-                    }
-                    rec.score = best; rec.end_query = ei; rec.end_ref = ej;
-                }
+                rec.score = e.score; rec.end_query = e.end_query; rec.end_ref = e.end_ref; rec.flags = 0;
                 out[pi] = rec;
             }
         }
@@ -796,6 +753,9 @@ void pmx_nwsg16v_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
     }
 
     // ---- combine (all captured values -> true scores) ---------------------------------------
+    // (This kernel, pmx_nwsg16q_kernel and pmx_nwsg16m_kernel keep their own text of what pmx_strip.h holds -- pair table, staging,
+    //  slot reduction, end rule, DESIGN.md 2.1a: with the helpers the same instructions came out in another order, three
+    //  instantiations of this kernel lost a wave per SIMD and score legs of all three ran 0.3 - 1.3 % slower, profiles/r19.)
     unsigned keyA = ((unsigned)(I32(bestcol) & 0xFFFF) << 16) | (0xFFFFu - (unsigned)(bestcoli & 0xFFFF));
     unsigned keyB = ((unsigned)((unsigned)I32(bestcol) >> 16) << 16) | (0xFFFFu - ((unsigned)bestcoli >> 16));
 #pragma unroll
@@ -1137,6 +1097,7 @@ void pmx_nwsg16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
         }
     }
 
+    // (this kernel keeps its own text of what pmx_strip.h holds: see the note at pmx_nwsg16v_kernel's combine)
     unsigned keyA = ((unsigned)(I32(bestcol) & 0xFFFF) << 16) | (0xFFFFu - (unsigned)(bestcoli & 0xFFFF));
     unsigned keyB = ((unsigned)((unsigned)I32(bestcol) >> 16) << 16) | (0xFFFFu - ((unsigned)bestcoli >> 16));
 #pragma unroll
@@ -1398,6 +1359,7 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         __builtin_amdgcn_sched_barrier(0);
     }
 
+    // (this kernel keeps its own text of what pmx_strip.h holds: see the note at pmx_nwsg16v_kernel's combine)
     unsigned keyA = ((unsigned)(I32(bestcol) & 0xFFFF) << 16) | (0xFFFFu - (unsigned)(bestcoli & 0xFFFF));
     unsigned keyB = ((unsigned)((unsigned)I32(bestcol) >> 16) << 16) | (0xFFFFu - ((unsigned)bestcoli >> 16));
 #pragma unroll
@@ -1446,18 +1408,15 @@ static int launch_nwsgm(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
                         pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf = nullptr, int Tmax = 0)
 {
     constexpr int NP = 2 * (64 / G);
-    const size_t lds = (size_t)(m.msize + 1) * 32 + 256 + (size_t)NP * 40;
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = !(sg && (sg_flags & PMX_SG_QB)), row_pen = !(sg && (sg_flags & PMX_SG_DB));
-    const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
+    const size_t lds = (size_t)(m.msize + 1) * 32 + 256 + (size_t)NP * PMX_PAIRTAB_BYTES;
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
     if (TR) g_nwsg_trace_form = 2;
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_nwsg16m_kernel<G, R, TR>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
-                       col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb, b.perm, d_out, tbuf, Tmax);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+                       ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax);
+    return pmx_launched();
 }
 
 template <int G, int R, bool TR, bool PSSM>
@@ -1480,27 +1439,23 @@ static int launch_nwsgq_form(const PmxBatch &b, const PmxDevMatrix &m, int mode,
     const size_t lds = (size_t)(m.msize + 1) * G * RS + 8 + (PSSM ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)NP * 24 +
                        (TR ? (size_t)WAVES * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4 : 0);
     if (lds > 160 * 1024) return 1;
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = !(sg && (sg_flags & PMX_SG_QB)), row_pen = !(sg && (sg_flags & PMX_SG_DB));
-    const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
     if constexpr (TR && R >= 19) {
-        if (!s1_end && !s2_end && !pmx_env("PMX_NWSGQ_ENDS_ALWAYS")) {       // no free end: the instance without captures (three waves per SIMD)
+        if (!ends.s1_end && !ends.s2_end && !pmx_env("PMX_NWSGQ_ENDS_ALWAYS")) {       // no free end: the instance without captures (three waves per SIMD)
             { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16q_kernel<G, R, WAVES, TR, false, PSSM>)); if (rc) return rc; }
             hipLaunchKernelGGL((pmx_nwsg16q_kernel<G, R, WAVES, TR, false, PSSM>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                                b.qbuf, b.q_shared, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
-                               col_pen, row_pen, 0, 0, nb, b.perm, d_out, tbuf, Tmax);
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? 0 : -(int)e;
+                               ends.col_pen, ends.row_pen, 0, 0, nb, b.perm, d_out, tbuf, Tmax);
+            return pmx_launched();
         }
     }
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16q_kernel<G, R, WAVES, TR, true, PSSM>)); if (rc) return rc; }
     hipLaunchKernelGGL((pmx_nwsg16q_kernel<G, R, WAVES, TR, true, PSSM>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                        b.qbuf, b.q_shared, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
-                       col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb, b.perm, d_out, tbuf, Tmax);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+                       ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax);
+    return pmx_launched();
 }
 
 // Traceback with a shared query (profile arm): shapes <16,10> <16,16> <32,10> <32,16> <64,16>, one virtual row at least on top
@@ -1590,21 +1545,18 @@ static int launch_nwsg(const PmxBatch &b, const PmxDevMatrix &m, int mode, int s
                        pmx_record_t *d_out, hipStream_t stream)
 {
     constexpr int QP = G * R, NP = 2 * (64 / G);
-    const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
+    const int RP = pmx_strip_ref_cols(b.max_rlen, G);
     const size_t lds = (size_t)NP * (m.msize + 1) * QP * 2 + (size_t)NP * RP +
-                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40;
+                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES;
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16_kernel<G, R>)); if (rc) return rc; }
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = !(sg && (sg_flags & PMX_SG_QB)), row_pen = !(sg && (sg_flags & PMX_SG_DB));
-    const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_nwsg16_kernel<G, R>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                       m.msize, open, ext, RP, b.q_shared, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, b.perm, d_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+                       m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, b.perm, d_out);
+    return pmx_launched();
 }
 
 static thread_local bool g_nwsgv_pt = false;          // the last launch_nwsgv of this thread ran the perm-table form first (kernel names)
@@ -1632,14 +1584,12 @@ static int launch_nwsgv(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
         return launch_nwsgv<G, R, TR, FETCH, TR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
     if (TR) g_nwsg_trace_form = TRB ? 1 : 0;
     constexpr int RS = (R + 3) / 4 * 4, NP = 2 * (64 / G);
-    const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
+    const int RP = pmx_strip_ref_cols(b.max_rlen, G);
     const size_t lds = (size_t)NP * (m.msize + 1) * G * RS + (FETCH ? 0 : (size_t)NP * RP) +
-                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40;
+                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES;
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB>)); if (rc) return rc; }
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = !(sg && (sg_flags & PMX_SG_QB)), row_pen = !(sg && (sg_flags & PMX_SG_DB));
-    const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
     if constexpr (!TR) {
@@ -1652,12 +1602,12 @@ static int launch_nwsgv(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
             g_nwsgv_pt = false;
             if constexpr (NwsgPtShape<G, R, TR>::value && !FETCH) {
                 const int nb_rowx = pmx_nwsgv_bias(b, m, open, ext, 1);      // (the caller's nb is the tracking form's: no row offset)
-                if (nb_rowx && m.msize <= 5 && b.blockflag && !b.q_shared && (col_pen || row_pen) && !pmx_env("PMX_NWSG16_NO_PERMTABLE")) {
-                    const size_t lds_pt = (size_t)NP * RP + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40 + 160 + (size_t)NP * ((G * R + 3) / 4 * 4) + 32;
+                if (nb_rowx && m.msize <= 5 && b.blockflag && !b.q_shared && (ends.col_pen || ends.row_pen) && !pmx_env("PMX_NWSG16_NO_PERMTABLE")) {
+                    const size_t lds_pt = (size_t)NP * RP + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 160 + (size_t)NP * ((G * R + 3) / 4 * 4) + 32;
                   if (lds_pt <= 160 * 1024 && (lds_pt <= 48 * 1024 || pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>)) == 0)) {
                     hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>), dim3((unsigned)blocks), dim3(64), lds_pt, stream,
                                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                                       m.msize, open, ext, RP, b.q_shared, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb_rowx, b.perm, d_out, tbuf, Tmax,
+                                       m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb_rowx, b.perm, d_out, tbuf, Tmax,
                                        1, b.blockflag, (const int *)nullptr);
                     const hipError_t e = hipGetLastError();
                     if (e != hipSuccess) return -(int)e;
@@ -1670,10 +1620,9 @@ static int launch_nwsgv(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
             if (!only8 && b.blockflag) { const hipError_t e = hipMemsetAsync(b.blockflag, 0xFF, (size_t)blocks * sizeof(int), stream); if (e != hipSuccess) return -(int)e; }
             hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB, false, false>), dim3((unsigned)blocks), dim3(64), lds, stream,
                                b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                               m.msize, open, ext, RP, b.q_shared, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb, b.perm, d_out, tbuf, Tmax,
+                               m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
                                b.track8, (int *)nullptr, only8);
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? 0 : -(int)e;
+            return pmx_launched();
         }
     }
     // Alphabets of <= 4 letters (+ wildcard): the perm-table form first (no LDS profile: see PT at the kernel); it marks the blocks
@@ -1683,14 +1632,14 @@ static int launch_nwsgv(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     g_nwsgv_pt = false;
     if constexpr (NwsgPtShape<G, R, TR>::value && !FETCH && (!TR || TRB)) {
         if (m.msize <= 5 && b.blockflag && !b.track8 && !b.q_shared && !pmx_env("PMX_NWSG16_NO_PERMTABLE")) {
-            const size_t lds_pt = (size_t)NP * RP + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40 + 160 + (size_t)NP * ((G * R + 3) / 4 * 4) + 32 +
+            const size_t lds_pt = (size_t)NP * RP + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 160 + (size_t)NP * ((G * R + 3) / 4 * 4) + 32 +
                                   (TR ? (size_t)64 * 33 * 4 : 0);
             // (more than the default 48 KB of dynamic LDS -- short queries against references of several kbp -- needs the opt-in; where the
             //  staged references do not fit at all, or the opt-in fails, the LDS-profile form below takes every block)
             if (lds_pt <= 160 * 1024 && (lds_pt <= 48 * 1024 || pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>)) == 0)) {
                 hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>), dim3((unsigned)blocks), dim3(64), lds_pt, stream,
                                    b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                                   m.msize, open, ext, RP, b.q_shared, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb, b.perm, d_out, tbuf, Tmax,
+                                   m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
                                    0, b.blockflag, (const int *)nullptr);
                 hipError_t e = hipGetLastError();
                 if (e != hipSuccess) return -(int)e;
@@ -1705,10 +1654,9 @@ static int launch_nwsgv(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     }
     hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                       m.msize, open, ext, RP, b.q_shared, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb, b.perm, d_out, tbuf, Tmax,
+                       m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
                        0, (int *)nullptr, only);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // Second-generation eligibility: the profile byte score + open must fit, and the proven value range plus
@@ -1774,7 +1722,7 @@ int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int
     for (int v = 0; v < 4 && !G; ++v) {                  // the first shape that holds the query and fits the LDS (launch_nwsgv's condition)
         const int g = 8 << v, np = 2 * (64 / g);
         const size_t lds = (size_t)np * (m.msize + 1) * g * 16 + (size_t)np * (b.max_rlen + 2 * g + 12) +
-                           (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)np * 40;
+                           (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)np * PMX_PAIRTAB_BYTES;
         if (b.max_qlen <= g * 16 - 1 && lds <= 160 * 1024) { *variant = v; G = g; }
     }
     if (!G) return 1;

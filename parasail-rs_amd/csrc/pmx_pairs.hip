@@ -638,8 +638,6 @@ void pmx_pairs_maxlen_kernel(const pmx_pair_t *__restrict__ pairs, long long n,
     if ((threadIdx.x & 63) == 0) { if (ql > 0) atomicMax(&out[0], ql); if (rl > 0) atomicMax(&out[1], rl); }
 }
 
-static int pmx_pairs_launched() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : -(int)e; }
-
 int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
                              const int64_t *q_off, long long q_count, long long q_bytes,
                              const int64_t *r_off, long long r_count, long long r_bytes, int32_t max_qlen, int32_t max_rlen,
@@ -648,7 +646,7 @@ int pmx_launch_pairs_resolve(const pmx_pair_t *pairs, const uint8_t *strand, int
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_resolve_kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, strand, first, per, n,
                        q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, qsrc, rsrc, ok, sflag);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_gather(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                             const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
@@ -657,13 +655,13 @@ int pmx_launch_pairs_gather(long long n, const uint8_t *q_buf, long long q_bytes
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_gather_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
                        qlen, rlen, qsrc, rsrc, ok, qoff, roff, qout, rout);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_fixup(const uint8_t *ok, long long n, pmx_record_t *rec, pmx_stats_t *stats, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_fixup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, rec, stats);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                                      const int32_t *qlen, const int32_t *rlen, const int64_t *qsrc, const int64_t *rsrc, const uint8_t *ok,
@@ -673,7 +671,7 @@ int pmx_launch_pairs_gather_stranded(long long n, const uint8_t *q_buf, long lon
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_gather_stranded_kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
                        qlen, rlen, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_fold(const pmx_record_t *slot_rec, const pmx_stats_t *slot_stats, const uint8_t *ok, const uint8_t *sflag,
                           long long n, int per, int mark, pmx_record_t *rec, pmx_stats_t *stats, uint8_t *byte, uint8_t *okf, hipStream_t st)
@@ -681,7 +679,7 @@ int pmx_launch_pairs_fold(const pmx_record_t *slot_rec, const pmx_stats_t *slot_
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slot_rec, slot_stats, ok, sflag,
                        n, per, mark, rec, stats, byte, okf);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 void pmx_genetic_code_host(uint8_t table[64]) { for (int i = 0; i < 64; ++i) table[i] = (uint8_t)pmx_code_std[i]; }
 // (the translated side is a template argument of these four kernels: the launcher picks the instance)
@@ -695,7 +693,7 @@ int pmx_launch_pairs_resolve_frames(const pmx_pair_t *pairs, const uint8_t *fram
     const auto kernel = ref ? pmx_pairs_resolve_frames_kernel<true> : pmx_pairs_resolve_frames_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, frame, first, per, n,
                        q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                                        const int32_t *qlen, const int32_t *rlen, const int32_t *tw, const int64_t *qsrc, const int64_t *rsrc,
@@ -707,7 +705,7 @@ int pmx_launch_pairs_gather_translated(long long n, const uint8_t *q_buf, long l
     const auto kernel = ref ? pmx_pairs_gather_translated_kernel<true> : pmx_pairs_gather_translated_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
                        qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_resolve_codons(const pmx_pair_t *pairs, const uint8_t *strand, int first, int per, long long n,
                                     const int64_t *q_off, long long q_count, long long q_bytes,
@@ -719,7 +717,7 @@ int pmx_launch_pairs_resolve_codons(const pmx_pair_t *pairs, const uint8_t *stra
     const auto kernel = ref ? pmx_pairs_resolve_codons_kernel<true> : pmx_pairs_resolve_codons_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, st, pairs, strand, first, per, n,
                        q_off, q_count, q_bytes, r_off, r_count, r_bytes, max_qlen, max_rlen, qlen, rlen, tw, qsrc, rsrc, ok, sflag);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long q_bytes, const uint8_t *r_buf, long long r_bytes,
                                    const int32_t *qlen, const int32_t *rlen, const int32_t *tw, const int64_t *qsrc, const int64_t *rsrc,
@@ -731,19 +729,19 @@ int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long 
     const auto kernel = ref ? pmx_pairs_gather_codons_kernel<true> : pmx_pairs_gather_codons_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
                        qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *rec, int32_t *nops, int32_t *textlen, int32_t *beg, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_fixup_cigar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, rec, nops, textlen, beg);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_text_rebase(const int64_t *local, long long n, int64_t *text_off, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_text_rebase_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, local, n, text_off);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 void pmx_complement_table_host(uint8_t table[256])
 {
@@ -753,13 +751,13 @@ int pmx_launch_all_pairs_enumerate(long long nseq, long long first, long long co
 {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(pmx_all_pairs_enumerate_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, nseq, first, count, pairs);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_rect_pairs_enumerate(long long nr, long long first, long long count, pmx_pair_t *pairs, hipStream_t st)
 {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(pmx_rect_pairs_enumerate_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (unsigned long long)nr, first, count, pairs);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts, long long n, long long capacity, long long index0,
                                  const pmx_pair_t *pairs, const pmx_record_t *rec, const pmx_stats_t *stats,
@@ -773,13 +771,13 @@ int pmx_launch_pairs_append_hits(const int64_t *idx, const int64_t *chunk_counts
                            (const int64_t *)counts, capacity, index0, pairs, rec, stats, hit_pairs, hit_index, hit_recs, hit_stats, hit_strand, marked);
     }
     hipLaunchKernelGGL(pmx_pairs_advance_hits_kernel, dim3(1), dim3(1), 0, st, chunk_counts, capacity, counts);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_first_bad(const uint8_t *ok, long long n, long long index0, int64_t *first_bad, hipStream_t st)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_first_bad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ok, n, index0, (unsigned long long *)first_bad);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t st)
@@ -787,7 +785,7 @@ int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t 
     if (n <= 0) return 0;
     hipLaunchKernelGGL(pmx_pairs_maxlen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pairs, n, q_off, q_count, q_bytes,
                        r_off, r_count, r_bytes, out);
-    return pmx_pairs_launched();
+    return pmx_launched();
 }
 void pmx_all_pairs_index_host(unsigned long long nseq, unsigned long long p, unsigned long long *i, unsigned long long *j)
 {

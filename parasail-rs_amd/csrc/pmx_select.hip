@@ -296,22 +296,19 @@ int pmx_launch_hit_lengths(const int64_t *idx, const int64_t *counts, long long 
                            int32_t *diag, int32_t *hlen, hipStream_t st)
 {
     hipLaunchKernelGGL(pmx_select_hitlen_kernel, dim3((unsigned)((cap + 2 + 255) / 256)), dim3(256), 0, st, idx, counts, cap, recs, roff, diag, hlen);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 int pmx_launch_hit_records(const int64_t *idx, const pmx_record_t *recs, const int32_t *diag, long long h, pmx_hit_t *hits, hipStream_t st)
 {
     if (h <= 0) return 0;
     hipLaunchKernelGGL(pmx_select_hits_kernel, dim3((unsigned)((h + 255) / 256)), dim3(256), 0, st, idx, recs, diag, h, hits);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 int pmx_launch_hit_begins(const int32_t *beg, long long h, pmx_hit_t *hits, hipStream_t st)
 {
     if (h <= 0) return 0;
     hipLaunchKernelGGL(pmx_select_begins_kernel, dim3((unsigned)((h + 255) / 256)), dim3(256), 0, st, beg, h, hits);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // ---- gather: reference idx[p] -> out[ooff[p] .. ooff[p + 1]) ------------------------------------------------------------------------
@@ -361,6 +358,5 @@ int pmx_launch_gather_refs(const uint8_t *rbuf, const int64_t *roff, long long n
 {
     if (h <= 0) return 0;
     hipLaunchKernelGGL(pmx_gather_refs_kernel, dim3((unsigned)((h + 3) / 4)), dim3(256), 0, st, rbuf, roff, n, idx, h, out, ooff, out_cap);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

@@ -113,6 +113,5 @@ int pmx_launch_unpack2(const uint8_t *in, uint8_t *out, long long lo, long long 
     if (hi <= lo) return 0;
     const long long lo4 = lo / 4, n4 = (hi + 3) / 4 - lo4;
     hipLaunchKernelGGL(pmx_unpack2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, in, out, lo4, hi, letters);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

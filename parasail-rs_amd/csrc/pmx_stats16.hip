@@ -19,7 +19,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
-#include <cstdlib>
+#include "pmx_strip.h"
 
 #define SB 32768
 #define SNEG (-16384)
@@ -60,47 +60,21 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
     unsigned char *rsym = reinterpret_cast<unsigned char *>(psc + NPROF * MS1 * QP);
     int16_t *mat = reinterpret_cast<int16_t *>(rsym + NP * RP);
     unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((msize * msize * 2) & 7)) & 7));
+    const PmxPairTab ptab{reinterpret_cast<long long *>(pmx_after_matrix(map, msize * msize))};
 
     const long long pair0 = (long long)blockIdx.x * NP;
-    for (int i = tid; i < msize * msize; i += 64 * WAVES) mat[i] = gmat[i];
-    for (int i = tid; i < 256; i += 64 * WAVES) map[i] = gmap[i];
-    if (tid < NP) {
-        long long pos = pair0 + tid; if (pos >= n) pos = n - 1;
-        const long long pi = perm ? (long long)perm[pos] : pos;
-        const long long qb = q_shared ? 0 : qoff[pi], rb = roff[pi];
-        ptab[5 * tid + 0] = qb;
-        ptab[5 * tid + 1] = q_shared ? q_shared : (qoff[pi + 1] - qb);
-        ptab[5 * tid + 2] = rb;
-        ptab[5 * tid + 3] = roff[pi + 1] - rb;
-        ptab[5 * tid + 4] = (pair0 + tid < n) ? pi : -1;
-    }
+    pmx_stage_matrix(mat, map, gmat, gmap, msize * msize, tid, 64 * WAVES);
+    if (tid < NP) ptab.fill(tid, pair0, n, perm, qoff, roff, q_shared);
     __syncthreads();
     const uint8_t *qbase = qbuf;
     const uint8_t *rbase = rbuf;
 
-    for (int p = 0; p < NP; ++p) {
-        const int rlp = (int)ptab[5 * p + 3];
-        const uint8_t *rp = rbase + ptab[5 * p + 2];
-        for (int j0 = 0; j0 < RP; j0 += 64 * WAVES * 4) {
-            unsigned char raw[4]; bool ok[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * 64 * WAVES + tid, jj = j - (G - 1);
-                ok[u] = j < RP && jj >= 0 && jj < rlp;
-                raw[u] = ok[u] ? rp[jj] : (unsigned char)0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * 64 * WAVES + tid;
-                if (j < RP) rsym[p * RP + j] = ok[u] ? map[raw[u]] : (unsigned char)msize;
-            }
-        }
-    }
+    for (int p = 0; p < NP; ++p)
+        pmx_stage_ref_symbols<G, 4>(rsym + p * RP, RP, rbase + ptab.rbeg(p), ptab.rlen(p), map, msize, tid, 64 * WAVES);
     const int vcol_score = col_pen ? SNEG : 0;
     for (int p = 0; p < NPROF; ++p) {
-        const int qlp = (int)ptab[5 * p + 1];
-        const uint8_t *qp = qbase + ptab[5 * p + 0];
+        const int qlp = ptab.qlen(p);
+        const uint8_t *qp = qbase + ptab.qbeg(p);
         for (int er = tid; er < QP; er += 64 * WAVES) {
             const int q0 = (er < qlp) ? (int)map[qp[er]] : -1;
             for (int sym = 0; sym < msize; ++sym) {
@@ -119,7 +93,7 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
     const unsigned short *scL = psc + pslot * MS1 * QP + g * R;
     const unsigned *incL = pinc + pslot * MS1 * QP + g * R;
     const unsigned char *rs = rsym + slot * RP + (G - 1) - g;
-    const int ql = (int)ptab[5 * slot + 1], rl = (int)ptab[5 * slot + 3];
+    const int ql = ptab.qlen(slot), rl = ptab.rlen(slot);
     const unsigned vOpen = (unsigned)open, vExt = (unsigned)ext;
     const int gL = (ql - 1) / R, kL = (ql - 1) % R;       // owner of the last query row
 
@@ -229,7 +203,7 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 
     int max_rlen = 0;
 #pragma unroll
-    for (int p = 0; p < NPW; ++p) max_rlen = max(max_rlen, (int)ptab[5 * (wave * NPW + p) + 3]);
+    for (int p = 0; p < NPW; ++p) max_rlen = max(max_rlen, ptab.rlen(wave * NPW + p));
     const int T = (max_rlen + G - 1 + 1) & ~1;
     unsigned w0[R], wi0[R], w1[R], wi1[R];
     load_scores(rs[0], w0, wi0);
@@ -253,18 +227,12 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         for (int k = R - 1; k >= 0; --k) if ((svH[k] & 0xFFFFu) == swbest) { krow = k; kMS = svMS[k]; kL = svL[k]; }
         const unsigned long long mykey = ((unsigned long long)swbest << 32) | ((unsigned long long)(0xFFFFu - (swcol & 0xFFFFu)) << 16) |
                                          (unsigned long long)(0xFFFFu - (unsigned)(g * R + krow));
-        unsigned long long key = mykey;
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(key, off, 64);
-            key = o > key ? o : key;
-        }
+        const unsigned long long key = pmx_slot_best_key<G>(mykey);
         const unsigned long long win = __ballot(key == mykey);
-        const unsigned long long slotmask = (G == 64) ? ~0ULL : (((1ULL << G) - 1ULL) << ((lane / G) * G));
-        const int wl = __builtin_ctzll(win & slotmask);
+        const int wl = __builtin_ctzll(win & pmx_slot_mask<G>(lane));
         const unsigned wMS = __shfl(kMS, wl, 64), wL = __shfl(kL, wl, 64);
         if (g == 0) {
-            const long long pi = ptab[5 * slot + 4];
+            const long long pi = ptab.index(slot);
             if (pi >= 0) {
                 pmx_record_t rec; rec.flags = 0;
                 rec.score = (int)(key >> 32) - SB;
@@ -277,18 +245,11 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         }
         return;
     }
-    // ---- combine: last-column candidates over the slot (value desc, row asc), then the oracle's rule ----
-    unsigned key = ((unsigned)(bcol.H < 0 ? 0 : bcol.H) << 16) | (0xFFFFu - (unsigned)bcol.i);
-    unsigned best = key;
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-        const unsigned o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-    }
-    const unsigned long long win = __ballot(best == key && bcol.H >= 0);
-    // lanes of this slot only
-    const unsigned long long slotmask = (G == 64) ? ~0ULL : (((1ULL << G) - 1ULL) << ((lane / G) * G));
-    const int wl = (win & slotmask) ? __builtin_ctzll(win & slotmask) : (lane / G) * G;
+    // ---- combine: last-column candidates over the slot, then the end rule ----
+    const unsigned key = pmx_slot_key((unsigned)(bcol.H < 0 ? 0 : bcol.H), (unsigned)bcol.i);
+    const unsigned best = pmx_slot_best_key<G>(key);
+    const unsigned long long win = __ballot(best == key && bcol.H >= 0) & pmx_slot_mask<G>(lane);
+    const int wl = win ? __builtin_ctzll(win) : (lane / G) * G;
     SCand bc;
     bc.H = __shfl(bcol.H, wl, 64); bc.i = __shfl(bcol.i, wl, 64); bc.j = __shfl(bcol.j, wl, 64);
     bc.MS = __shfl(bcol.MS, wl, 64); bc.L = __shfl(bcol.L, wl, 64);
@@ -299,15 +260,10 @@ void pmx_stats16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
     br.H = __shfl(brow.H, ll, 64); br.i = __shfl(brow.i, ll, 64); br.j = __shfl(brow.j, ll, 64);
     br.MS = __shfl(brow.MS, ll, 64); br.L = __shfl(brow.L, ll, 64);
     if (g == 0) {
-        const long long pi = ptab[5 * slot + 4];
+        const long long pi = ptab.index(slot);
         if (pi >= 0) {
-            SCand res;
-            if (!s1_end && !s2_end) res = co;
-            else {
-                res.H = -(1 << 30); res.i = res.j = 0; res.MS = res.L = 0;
-                if (s2_end) res = br;
-                if (s1_end && bc.H > res.H) res = bc;
-            }
+            const int c = pmx_sg_choice(s1_end, s2_end, br.H, bc.H);
+            const SCand res = c == 0 ? co : c == 1 ? br : bc;
             pmx_record_t rec; rec.score = res.H - SB; rec.end_query = res.i; rec.end_ref = res.j; rec.flags = 0;
             out[pi] = rec;
             pmx_stats_t st; st.matches = (int)(res.MS & 0xFFFF); st.similar = (int)(res.MS >> 16); st.length = (int)res.L;
@@ -322,22 +278,19 @@ static int launch_stats(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
                         pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t stream)
 {
     constexpr int QP = G * R, NP = (64 / G) * WAVES;
-    const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
+    const int RP = pmx_strip_ref_cols(b.max_rlen, G);
     const int nprof = b.q_shared ? 1 : NP;
     const size_t lds = (size_t)nprof * (m.msize + 1) * QP * 6 + (size_t)NP * RP +
-                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40;
+                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES;
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_stats16_kernel<G, R, WAVES, SW>)); if (rc) return rc; }
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = SW ? 0 : !(sg && (sg_flags & PMX_SG_QB)), row_pen = SW ? 0 : !(sg && (sg_flags & PMX_SG_DB));
-    const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
     hipLaunchKernelGGL((pmx_stats16_kernel<G, R, WAVES, SW>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                       m.msize, open, ext, RP, b.q_shared, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0,
+                       m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end,
                        b.perm, d_out, d_stats);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // 0 launched, 1 not eligible (caller uses the general kernel), <0 HIP error

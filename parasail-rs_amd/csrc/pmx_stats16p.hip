@@ -20,7 +20,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
-#include <cstdlib>
+#include "pmx_strip.h"
 
 struct PCand { int H; int i; int jL; int MS; };                  // true score, row, column | length << 16, matches | similar << 16
 
@@ -57,21 +57,11 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
     unsigned char *psc = lds, *pim = lds + PLANE, *pis = lds + 2 * PLANE;
     int16_t *mat = reinterpret_cast<int16_t *>(lds + ((3 * PLANE + 7) & ~7));
     unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((msize * msize * 2) & 7)) & 7));
+    const PmxPairTab ptab{reinterpret_cast<long long *>(pmx_after_matrix(map, msize * msize))};
 
     const long long pair0 = (long long)blockIdx.x * NP;
-    for (int i = tid; i < msize * msize; i += NT) mat[i] = gmat[i];
-    for (int i = tid; i < 256; i += NT) map[i] = gmap[i];
-    if (tid < NP) {
-        long long pos = pair0 + tid; if (pos >= n) pos = n - 1;
-        const long long pi = perm ? (long long)perm[pos] : pos;
-        const long long qb = q_shared ? 0 : qoff[pi], rb = roff[pi];
-        ptab[5 * tid + 0] = qb;
-        ptab[5 * tid + 1] = q_shared ? q_shared : (qoff[pi + 1] - qb);
-        ptab[5 * tid + 2] = rb;
-        ptab[5 * tid + 3] = roff[pi + 1] - rb;
-        ptab[5 * tid + 4] = (pair0 + tid < n) ? pi : -1;
-    }
+    pmx_stage_matrix(mat, map, gmat, gmap, msize * msize, tid, NT);
+    if (tid < NP) ptab.fill(tid, pair0, n, perm, qoff, roff, q_shared);
     __syncthreads();
 
     // ---- profile planes: query row i = l * R + k sits at byte l * RS + k (rows >= qlen score 0, no increments)
@@ -83,8 +73,8 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
         }
     }
     for (int p = 0; p < NPROF; ++p) {
-        const int qlp = (int)ptab[5 * p + 1];
-        const uint8_t *qp = qbuf + ptab[5 * p + 0];
+        const int qlp = ptab.qlen(p);
+        const uint8_t *qp = qbuf + ptab.qbeg(p);
         for (int er = tid; er < G * R; er += NT) {
             const int q0 = (er < qlp) ? (int)map[qp[er]] : -1;
             const int pos = (er / R) * RS + er % R;
@@ -104,9 +94,9 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
     // ---- per-lane state ------------------------------------------------------------------
     const int prA = (q_shared || ML) ? 0 : pA, prB = (q_shared || ML) ? 0 : pB;
     const unsigned char *scA = psc + (size_t)prA * MS1 * QPS + g * RS, *scB = psc + (size_t)prB * MS1 * QPS + g * RS;
-    const int qlA = (int)ptab[5 * pA + 1], qlB = (int)ptab[5 * pB + 1];
-    const int rlA = (int)ptab[5 * pA + 3], rlB = (int)ptab[5 * pB + 3];
-    const uint8_t *refA = rbuf + ptab[5 * pA + 2], *refB = rbuf + ptab[5 * pB + 2];
+    const int qlA = ptab.qlen(pA), qlB = ptab.qlen(pB);
+    const int rlA = ptab.rlen(pA), rlB = ptab.rlen(pB);
+    const uint8_t *refA = rbuf + ptab.rbeg(pA), *refB = rbuf + ptab.rbeg(pB);
     // symbol of step x for this lane: column x - g of the reference, the pad symbol outside it
     auto fetch = [&](int x, int &ra, int &rb) {
         const int col = x - g;
@@ -117,7 +107,7 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
     // ML: letter codes of this lane's rows (msize beyond the query): LDS offsets inside a matT row, and packed for the match test
     int qa[ML ? R : 1], qb_[ML ? R : 1], qc[ML ? R : 1];
     if (ML) {
-        const uint8_t *qA = qbuf + ptab[5 * pA + 0] + g * R, *qB = qbuf + ptab[5 * pB + 0] + g * R;
+        const uint8_t *qA = qbuf + ptab.qbeg(pA) + g * R, *qB = qbuf + ptab.qbeg(pB) + g * R;
         unsigned char ra[R], rb[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -283,7 +273,7 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
 
     int max_rlen = 0;
 #pragma unroll
-    for (int p = 0; p < NPW; ++p) max_rlen = max(max_rlen, (int)ptab[5 * (wave * NPW + p) + 3]);
+    for (int p = 0; p < NPW; ++p) max_rlen = max(max_rlen, ptab.rlen(wave * NPW + p));
     const int T_ = (max_rlen + G - 1 + 1) & ~1;
     // pipeline: raw bytes two steps ahead (HBM / L2 latency), mapped symbols one step ahead, profile words for the next step
     int r0a, r0b, r1a, r1b, r2a, r2b, r3a, r3b;
@@ -306,35 +296,24 @@ void pmx_stats16p_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__rest
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    // ---- combine per pair half: last-column candidates over the slot (value desc, row asc), then the oracle's rule ----
-    const unsigned long long slotmask = (G == 64) ? ~0ULL : (((1ULL << G) - 1ULL) << (slotw * G));
+    // ---- combine per pair half: last-column candidates over the slot, then the end rule ----
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int gL = h ? gLB : gLA;
-        const unsigned key = ((unsigned)(bcol[h].H < -16000 ? 0 : bcol[h].H + 16384) << 16) | (0xFFFFu - (unsigned)bcol[h].i);
-        unsigned best = key;
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) {
-            const unsigned o = __shfl_xor(best, off, 64);
-            best = o > best ? o : best;
-        }
-        const unsigned long long win = __ballot(best == key && bcol[h].H > -(1 << 29));
-        const int wl = (win & slotmask) ? __builtin_ctzll(win & slotmask) : slotw * G;
+        const unsigned key = pmx_slot_key((unsigned)(bcol[h].H < -16000 ? 0 : bcol[h].H + 16384), (unsigned)bcol[h].i);
+        const unsigned best = pmx_slot_best_key<G>(key);
+        const unsigned long long win = __ballot(best == key && bcol[h].H > -(1 << 29)) & pmx_slot_mask<G>(lane);
+        const int wl = win ? __builtin_ctzll(win) : slotw * G;
         PCand bc, co, br;
         bc.H = __shfl(bcol[h].H, wl, 64); bc.i = __shfl(bcol[h].i, wl, 64); bc.jL = __shfl(bcol[h].jL, wl, 64); bc.MS = __shfl(bcol[h].MS, wl, 64);
         const int ll = slotw * G + gL;
         co.H = __shfl(corner[h].H, ll, 64); co.i = __shfl(corner[h].i, ll, 64); co.jL = __shfl(corner[h].jL, ll, 64); co.MS = __shfl(corner[h].MS, ll, 64);
         br.H = __shfl(brow[h].H, ll, 64); br.i = __shfl(brow[h].i, ll, 64); br.jL = __shfl(brow[h].jL, ll, 64); br.MS = __shfl(brow[h].MS, ll, 64);
         if (g == 0) {
-            const long long pi = ptab[5 * ((h ? pB : pA)) + 4];
+            const long long pi = ptab.index((h ? pB : pA));
             if (pi >= 0) {
-                PCand res;
-                if (!s1_end && !s2_end) res = co;
-                else {
-                    res.H = -(1 << 30); res.i = 0; res.jL = 0; res.MS = 0;
-                    if (s2_end) res = br;
-                    if (s1_end && bc.H > res.H) res = bc;
-                }
+                const int c = pmx_sg_choice(s1_end, s2_end, br.H, bc.H);
+                const PCand res = c == 0 ? co : c == 1 ? br : bc;
                 pmx_record_t rec; rec.score = res.H; rec.end_query = res.i; rec.end_ref = res.jL & 0xFFFF; rec.flags = 0;
                 out[pi] = rec;
                 pmx_stats_t st; st.matches = res.MS & 0xFFFF; st.similar = (int)((unsigned)res.MS >> 16); st.length = (int)((unsigned)res.jL >> 16);
@@ -350,23 +329,20 @@ static int launch_statsp(const PmxBatch &b, const PmxDevMatrix &m, int mode, int
                          pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t stream)
 {
     constexpr int RS = (R + 3) / 4 * 4, NP = 2 * (64 / G) * WAVES;
-    const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
+    const int RP = pmx_strip_ref_cols(b.max_rlen, G);
     const int nprof = b.q_shared ? 1 : NP;
     const size_t lds = (ML ? (size_t)(m.msize + 1) * 32 + 8 : (size_t)3 * nprof * (m.msize + 1) * G * RS) + 8 +
-                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40;
+                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES;
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_stats16p_kernel<G, R, WAVES, ML>)); if (rc) return rc; }
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = !(sg && (sg_flags & PMX_SG_QB)), row_pen = !(sg && (sg_flags & PMX_SG_DB));
-    const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
+    const PmxEnds ends = pmx_ends(mode, sg_flags);            // (nw or sg: pmx_launch_stats16p takes no other mode)
     const long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_stats16p_kernel<G, R, WAVES, ML>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                       m.msize, open, ext, RP, b.q_shared, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, nb,
+                       m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb,
                        b.perm, d_out, d_stats);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // 0 launched, 1 not eligible (caller tries pmx_stats16), <0 HIP error

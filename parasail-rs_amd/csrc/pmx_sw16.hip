@@ -39,6 +39,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <cstdlib>
 
 __device__ __forceinline__ v2s pk_adds(v2s a, v2s b) { return __builtin_elementwise_add_sat(a, b); }
@@ -117,7 +118,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     unsigned char *rsym = lds + (PT ? PT_TABS : NP * PROF_STRIDE + QP * EB);
     int16_t *mat = reinterpret_cast<int16_t *>(rsym + (FETCH ? 0 : NP * RP));
     unsigned char *map0 = reinterpret_cast<unsigned char *>(mat + msize * msize);       // (PT: its table sits behind the pair table, dword-aligned)
-    long long *ptab = reinterpret_cast<long long *>(map0 + (PT ? 0 : 256) + ((8 - ((msize * msize * 2) & 7)) & 7));   // per pair: q offset, qlen, r offset, rlen, pair index
+    const PmxPairTab ptab{reinterpret_cast<long long *>(pmx_after_matrix(map0, msize * msize) - (PT ? 256 : 0))};
 
     // PT: per reference symbol the 4 query-letter scores (+open), entry msize = pad = 0.  Addressed as LDS address 0: the kernel
     // has no static LDS, so `lds` starts there; a plain integer address folds into the read (the symbol of `lds` does not)
@@ -126,7 +127,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     // PT, behind the pair table: the query letter -> selector byte table (letter 0..3, 0x0C = "constant 0" for everything else,
     // with bit 4 set while it still has to be noted as a wildcard), one word per slot that collects "pair A / B has a wildcard
     // in its query" (bits 0 / 1), and the masks of a lane's own rows (ownmask[i]: 0xFF in the first i - OWN0 bytes, clamped to 0..4)
-    unsigned char *tabq = reinterpret_cast<unsigned char *>(ptab + 5 * NP);
+    unsigned char *tabq = reinterpret_cast<unsigned char *>(ptab.behind(NP));
     unsigned *wildf = reinterpret_cast<unsigned *>(tabq + 256);
     unsigned *ownmask = wildf + SLOTS;
     constexpr int OWN0 = 4 * (RS / 4 - 1), OWNN = OWN0 + R + 1;
@@ -147,16 +148,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
     if (PT && lane < SLOTS) wildf[lane] = 0;
     if (PT && lane < OWNN) ownmask[lane] = (unsigned)((0xFFFFFFFFull << (8 * min(max(lane - OWN0, 0), 4))) >> 32);
-    if (lane < NP) {
-        long long pos = pair0 + lane; if (pos >= n) pos = n - 1;
-        const long long pi = perm ? (long long)perm[pos] : pos;
-        const long long qb = q_shared ? 0 : qoff[pi], rb = roff[pi];
-        ptab[5 * lane + 0] = qb;
-        ptab[5 * lane + 1] = q_shared ? q_shared : (qoff[pi + 1] - qb);
-        ptab[5 * lane + 2] = rb;
-        ptab[5 * lane + 3] = roff[pi + 1] - rb;
-        ptab[5 * lane + 4] = (pair0 + lane < n) ? pi : -1;
-    }
+    if (lane < NP) ptab.fill(lane, pair0, n, perm, qoff, roff, q_shared);
     __syncthreads();
     const uint8_t *qbase = qbuf;
     const uint8_t *rbase = rbuf;
@@ -164,7 +156,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     // ---- reference symbols (with G-1 pad symbols on both sides) -------------------------
     int max_rlen = 0;
 #pragma unroll
-    for (int p = 0; p < NP; ++p) max_rlen = max(max_rlen, (int)ptab[5 * p + 3]);
+    for (int p = 0; p < NP; ++p) max_rlen = max(max_rlen, ptab.rlen(p));
     // Pairs in batches of UB, lanes over positions: UB independent global loads per lane are in
     // flight before anything consumes them (the prologue is latency-bound otherwise), and no
     // index needs a division.
@@ -176,8 +168,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 const int p = p0 + u;
-                ok[u] = jr >= 0 && jr < (int)ptab[5 * p + 3];
-                raw[u] = ok[u] ? rbase[ptab[5 * p + 2] + jr] : (unsigned char)0;
+                ok[u] = jr >= 0 && jr < ptab.rlen(p);
+                raw[u] = ok[u] ? rbase[ptab.rbeg(p) + jr] : (unsigned char)0;
             }
             if (j < RP) {
 #pragma unroll
@@ -219,9 +211,9 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         const unsigned pad4 = (unsigned)(4 * msize) * 0x01010101u;
         for (int s0 = 0; s0 < SLOTS; s0 += SPT) {
             const int s = s0 + lane / LW;
-            const uint8_t *ra = rbase + ptab[5 * (2 * s) + 2], *rb = rbase + ptab[5 * (2 * s + 1) + 2];
+            const uint8_t *ra = rbase + ptab.rbeg(2 * s), *rb = rbase + ptab.rbeg(2 * s + 1);
             const unsigned ha = (unsigned)(uintptr_t)ra & 3u, hb = (unsigned)(uintptr_t)rb & 3u;      // an item starts this far into a dword
-            const int la = (int)ptab[5 * (2 * s) + 3], lb = (int)ptab[5 * (2 * s + 1) + 3];
+            const int la = ptab.rlen(2 * s), lb = ptab.rlen(2 * s + 1);
             uint2 *dst = reinterpret_cast<uint2 *>(rsym + s * 2 * RP);
             if (lane % LW < PADF / 4) dst[lane % LW] = make_uint2(pad4, pad4);                        // the pad in front: whole items
             for (int jr = 4 * (lane % LW); jr < RP - PADF; jr += 4 * LW) {
@@ -233,7 +225,7 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         }
         __syncthreads();
         if (lane < 3 * NP) {                // (pair, k): position rlen + k, while it lies in the item of the last letter
-            const int p = lane / 3, len = (int)ptab[5 * p + 3], pos = len + lane % 3;
+            const int p = lane / 3, len = ptab.rlen(p), pos = len + lane % 3;
             if ((len & 3) != 0 && (pos >> 2) == (len >> 2))
                 rsym[(p >> 1) * 2 * RP + 2 * (PADF + pos) + (p & 1)] = (unsigned char)(4 * msize);
         }
@@ -246,8 +238,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int p = 2 * slot + h;
-            const uint8_t *qp = qbase + ptab[5 * p + 0] + g * R;
-            const int left = (int)ptab[5 * p + 1] - g * R;              // letters of the query from the lane's first row on
+            const uint8_t *qp = qbase + ptab.qbeg(p) + g * R;
+            const int left = ptab.qlen(p) - g * R;              // letters of the query from the lane's first row on
             const unsigned sh = (unsigned)(uintptr_t)qp & 3u;
             const unsigned *d = reinterpret_cast<const unsigned *>(qp - sh);
             unsigned w[RD + 1];
@@ -281,8 +273,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         for (int u = 0; u < QB; ++u) {
             const int item = (it0 + u) * 64 + lane;
             const int p = min(item / QP2, NP - 1), rp = item - p * QP2;
-            const int ql = (int)ptab[5 * p + 1];
-            const uint8_t *qp = qbase + ptab[5 * p + 0];
+            const int ql = ptab.qlen(p);
+            const uint8_t *qp = qbase + ptab.qbeg(p);
             // profile position -> query row (lane l keeps rows [l * R, l * R + R) at positions l * RS + k)
             const int p0 = 2 * rp, p1 = 2 * rp + 1;
             const int k0 = p0 % RS, k1 = p1 % RS;
@@ -529,8 +521,8 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     const int T = __builtin_amdgcn_readfirstlane(max_rlen) + G - 1;   // steps: the last lane's last real column (uniform: SALU loop test)
     int w0a[RS / WR], w0b[RS / WR], w1a[RS / WR], w1b[RS / WR];
     // FETCH: raw byte of step x (column x - g), -1 outside the reference; the pad symbol is the pair's own
-    const int rlA_ = (int)ptab[5 * pA + 3], rlB_ = (int)ptab[5 * pB + 3];
-    const uint8_t *refA = rbase + ptab[5 * pA + 2], *refB = rbase + ptab[5 * pB + 2];
+    const int rlA_ = ptab.rlen(pA), rlB_ = ptab.rlen(pB);
+    const uint8_t *refA = rbase + ptab.rbeg(pA), *refB = rbase + ptab.rbeg(pB);
     auto fetch = [&](int x, int &ra, int &rb) {
         const int col = x - g;
         ra = (col >= 0 && col < rlA_) ? (int)refA[col] : -1;
@@ -615,17 +607,11 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
         if (fake & 0xFFFF) keyA = 0;            // a bound taken over from the group, never reached by this lane
         if (fake >> 16) keyB = 0;
     }
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-        const int lo = IL ? 2 * off : off;              // lane distance of group members `off` apart
-        const unsigned long long oa = __shfl_xor(keyA, lo, 64), ob = __shfl_xor(keyB, lo, 64);
-        keyA = oa > keyA ? oa : keyA;
-        keyB = ob > keyB ? ob : keyB;
-    }
+    keyA = pmx_slot_best_key<G, IL ? 2 : 1>(keyA); keyB = pmx_slot_best_key<G, IL ? 2 : 1>(keyB);
     if (g == 0) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const long long pi = ptab[5 * (2 * slot + h) + 4];
+            const long long pi = ptab.index(2 * slot + h);
             if (pi >= 0) {
                 const unsigned long long key = h ? keyB : keyA;
                 pmx_record_t rec;
@@ -657,9 +643,9 @@ static int launch_one(const PmxBatch &b, const PmxDevMatrix &m, int open, int ex
     constexpr int EB = (VAR == 3 || VAR == 5 || VAR == 7 || VAR == 8 || PT) ? 1 : 2, WR = 4 / EB, RS = (R + WR - 1) / WR * WR;
     constexpr int QP = G * RS, NP = 2 * (64 / G);
     if (NP * m.msize > 255) return 1;                 // per-pair pad symbol must fit a byte
-    const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
+    const int RP = pmx_strip_ref_cols(b.max_rlen, G);
     const size_t lds = (PT ? (size_t)256 + 4 * (64 / G) + 4 * (4 * (RS / 4 - 1) + R + 1) : (size_t)NP * m.msize * QP * EB + (size_t)QP * EB) + (VAR == 8 ? 0 : (size_t)NP * RP) +
-                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * 40 + 32;
+                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 32;
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_sw16_kernel<G, R, VAR>)); if (rc) return rc; }
     long long blocks = (b.n + NP - 1) / NP;
@@ -713,7 +699,7 @@ int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int 
     for (int v = 0; v < 4 && !G; ++v) {                  // the first shape that holds the query, whose per-pair pad symbols fit a
         const int g = 8 << v, np = 2 * (64 / g);         // byte and whose profiles fit the LDS (the launcher's own conditions)
         const size_t lds = (size_t)np * m.msize * g * 16 + (size_t)g * 16 + (size_t)np * (b.max_rlen + 2 * g + 12) +
-                           (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)np * 40 + 32;
+                           (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)np * PMX_PAIRTAB_BYTES + 32;
         if (b.max_qlen <= g * 16 && np * m.msize <= 255 && lds <= 160 * 1024) { *variant = v; G = g; }
     }
     if (!G) return 1;

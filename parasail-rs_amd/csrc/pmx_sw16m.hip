@@ -12,6 +12,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <cstdlib>
 
 // TR: also writes the 4-bit traceback cells (bits and layout of pmx_nwsg16v_kernel<..,true>; rows top-aligned).
@@ -38,7 +39,7 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     // = open (score 0); row msize (outside the reference) = 0 (score -open) -- [map 256][ptab]
     unsigned char *matT = lds;
     unsigned char *map = lds + (msize + 1) * MSTR;
-    long long *ptab = reinterpret_cast<long long *>(map + 256);       // per pair: q offset, qlen, r offset, rlen, pair index
+    const PmxPairTab ptab{reinterpret_cast<long long *>(map + 256)};
 
     const long long pair0 = (long long)blockIdx.x * NPW;
     for (int i = lane; i < (msize + 1) * MSTR; i += 64) {
@@ -46,23 +47,16 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
         matT[i] = (unsigned char)(r == msize ? 0 : q < msize ? gmat[q * msize + r] + open : open);
     }
     for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
-    if (lane < NPW) {
-        long long pos = pair0 + lane; if (pos >= n) pos = n - 1;
-        const long long pi = perm ? (long long)perm[pos] : pos;
-        const long long qb = qoff[pi], rb = roff[pi];
-        ptab[5 * lane + 0] = qb; ptab[5 * lane + 1] = qoff[pi + 1] - qb;
-        ptab[5 * lane + 2] = rb; ptab[5 * lane + 3] = roff[pi + 1] - rb;
-        ptab[5 * lane + 4] = (pair0 + lane < n) ? pi : -1;
-    }
+    if (lane < NPW) ptab.fill(lane, pair0, n, perm, qoff, roff, 0);
     __syncthreads();
 
-    const int qlA = (int)ptab[5 * pA + 1], qlB = (int)ptab[5 * pB + 1];
-    const int rlA = (int)ptab[5 * pA + 3], rlB = (int)ptab[5 * pB + 3];
-    const uint8_t *refA = rbuf + ptab[5 * pA + 2], *refB = rbuf + ptab[5 * pB + 2];
+    const int qlA = ptab.qlen(pA), qlB = ptab.qlen(pB);
+    const int rlA = ptab.rlen(pA), rlB = ptab.rlen(pB);
+    const uint8_t *refA = rbuf + ptab.rbeg(pA), *refB = rbuf + ptab.rbeg(pB);
     // LDS offsets of this lane's query letters inside a matT row (column msize beyond the query)
     int qa[R], qb_[R];
     {
-        const uint8_t *qA = qbuf + ptab[5 * pA + 0] + g * R, *qB = qbuf + ptab[5 * pB + 0] + g * R;
+        const uint8_t *qA = qbuf + ptab.qbeg(pA) + g * R, *qB = qbuf + ptab.qbeg(pB) + g * R;
         unsigned char ra[R], rb[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -171,7 +165,7 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
 
     int max_rlen = 0;
 #pragma unroll
-    for (int p = 0; p < NPW; ++p) max_rlen = max(max_rlen, (int)ptab[5 * p + 3]);
+    for (int p = 0; p < NPW; ++p) max_rlen = max(max_rlen, ptab.rlen(p));
     const int T_ = (max_rlen + G - 1 + 1) & ~1;
     int r0a, r0b, r1a, r1b, m2a, m2b, m3a, m3b;
     fetch(0, r0a, r0b); fetch(1, r1a, r1b); fetch(2, m2a, m2b); fetch(3, m3a, m3b);
@@ -211,16 +205,11 @@ void pmx_sw16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
         keyA = ((unsigned long long)sA << 32) | ((0xFFFFu - cA) << 16) | (0xFFFFu - rA);
         keyB = ((unsigned long long)sB << 32) | ((0xFFFFu - cB) << 16) | (0xFFFFu - rB);
     }
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-        const unsigned long long oa = __shfl_xor(keyA, off, 64), ob = __shfl_xor(keyB, off, 64);
-        keyA = oa > keyA ? oa : keyA;
-        keyB = ob > keyB ? ob : keyB;
-    }
+    keyA = pmx_slot_best_key<G>(keyA); keyB = pmx_slot_best_key<G>(keyB);
     if (g == 0) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const long long pi = ptab[5 * (h ? pB : pA) + 4];
+            const long long pi = ptab.index(h ? pB : pA);
             if (pi >= 0) {
                 const unsigned long long key = h ? keyB : keyA;
                 pmx_record_t rec;
@@ -240,14 +229,13 @@ static int launch_m(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                     uint32_t *tbuf = nullptr, int Tmax = 0)
 {
     constexpr int NP = 2 * (64 / G);
-    const size_t lds = (size_t)(m.msize + 1) * 32 + 256 + (size_t)NP * 40;
+    const size_t lds = (size_t)(m.msize + 1) * 32 + 256 + (size_t)NP * PMX_PAIRTAB_BYTES;
     const long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_sw16m_kernel<G, R, TR>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
                        PK16_RERUN_LIMIT(m.max) - (b.max_rlen + 2 * G + 4) * ext, b.sat_above > 0 ? b.sat_above : 2147483647, b.perm, d_out, tbuf, Tmax);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // traceback variant, lane groups of 16 / 32 / 64 (variant 1..3 of pmx_sw16_trace_plan)

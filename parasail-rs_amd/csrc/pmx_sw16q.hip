@@ -16,6 +16,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <cstdlib>
 
 template <int G, int R, int WAVES, bool PSSM = false>
@@ -45,11 +46,11 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
     int16_t *mat = reinterpret_cast<int16_t *>(lds + ((MS1 * QPS + 7) & ~7));
     const int mcells = PSSM ? 0 : msize * msize;    // (PSSM: no staged matrix)
     unsigned char *map = reinterpret_cast<unsigned char *>(mat + mcells);
-    long long *ptab = reinterpret_cast<long long *>(map + 256 + ((8 - ((mcells * 2) & 7)) & 7));   // per pair: r offset, rlen, pair index
+    // per pair: r offset, rlen, pair index (one shared query: three entries, not the five of PmxPairTab)
+    long long *ptab = reinterpret_cast<long long *>(pmx_after_matrix(map, mcells));
 
     const long long pair0 = (long long)blockIdx.x * NP;
-    for (int i = tid; i < mcells; i += NT) mat[i] = gmat[i];
-    for (int i = tid; i < 256; i += NT) map[i] = gmap[i];
+    pmx_stage_matrix(mat, map, gmat, gmap, mcells, tid, NT);
     if (tid < NP) {
         long long pos = pair0 + tid; if (pos >= n) pos = n - 1;
         const long long pi = perm ? (long long)perm[pos] : pos;
@@ -181,12 +182,7 @@ void pmx_sw16q_kernel(const uint8_t *__restrict__ qbuf, int qlen,
         keyA = ((unsigned long long)sA << 32) | ((0xFFFFu - cA) << 16) | (0xFFFFu - rA);
         keyB = ((unsigned long long)sB << 32) | ((0xFFFFu - cB) << 16) | (0xFFFFu - rB);
     }
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-        const unsigned long long oa = __shfl_xor(keyA, off, 64), ob = __shfl_xor(keyB, off, 64);
-        keyA = oa > keyA ? oa : keyA;
-        keyB = ob > keyB ? ob : keyB;
-    }
+    keyA = pmx_slot_best_key<G>(keyA); keyB = pmx_slot_best_key<G>(keyB);
     if (g == 0) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -217,8 +213,7 @@ static int launch_q(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
     hipLaunchKernelGGL((pmx_sw16q_kernel<G, R, WAVES, PSSM>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, stream,
                        b.qbuf, b.q_shared, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
                        PK16_RERUN_LIMIT(m.max) - (b.max_rlen + 2 * G + 4) * ext, b.sat_above > 0 ? b.sat_above : 2147483647, b.perm, d_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // 0 launched, 1 not eligible (the caller goes on with pmx_sw16's own variants), <0 HIP error.

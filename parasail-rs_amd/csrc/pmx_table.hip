@@ -18,6 +18,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <cstdlib>
 
 #define TNEG (INT32_MIN / 2)
@@ -65,10 +66,9 @@ void pmx_table_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     const uint8_t *q = qbuf + qb, *r = rbuf + rb;
     for (int x = lane; x < msize * msize; x += 64) mat[(x % msize) * msize + x / msize] = gmat[x];
     for (int x = lane; x < ql; x += 64) qs[x] = gmap[q[x]];
-    const bool sw = mode == PMX_MODE_SW, sg = mode == PMX_MODE_SG;
-    const bool s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
-    const bool col_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_QB));
-    const bool row_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_DB));
+    const bool sw = mode == PMX_MODE_SW;
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
+    const bool s1_end = ends.s1_end, s2_end = ends.s2_end, col_pen = ends.col_pen, row_pen = ends.row_pen;
     auto colB = [&](int i) -> int { return (!sw && col_pen) ? -(open + i * ext) : 0; };
 
     const int j0 = lane * C;
@@ -255,6 +255,5 @@ int pmx_launch_table(int mode, int sg_flags, int open, int ext, const PmxDevMatr
         else LT(16, false);
     }
 #undef LT
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

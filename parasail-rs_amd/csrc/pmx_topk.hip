@@ -298,8 +298,7 @@ int pmx_launch_topk_merge(const pmx_record_t *rec, const pmx_stats_t *stats, lon
     hipLaunchKernelGGL(pmx_topk_row_kernel, dim3((unsigned)rows), dim3(256), lds, st, rec, stats, (unsigned long long)p0, (unsigned long long)cn,
                        (unsigned long long)nr, q_first, (unsigned)ks, kp, (unsigned)tps, (unsigned)tstride, t_keys, t_cnt, t_pass,
                        st_keys, st_recs, st_stats, st_held, st_passing);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, const uint64_t *st_keys, const pmx_record_t *st_recs,
@@ -311,6 +310,5 @@ int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, 
     hipLaunchKernelGGL(pmx_topk_emit_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, nq, q_first, (unsigned long long)nr, (unsigned)ks,
                        st_keys, st_recs, st_stats, st_held, st_passing, row_off, capacity, hit_pairs, hit_index, hit_recs, hit_stats, row_passing, hit_strand, marked);
     hipLaunchKernelGGL(pmx_topk_counts_kernel, dim3(1), dim3(256), 0, st, nq, st_passing, row_off, capacity, counts);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

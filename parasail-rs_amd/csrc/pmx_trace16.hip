@@ -23,6 +23,7 @@
 #include "pmx_common.h"
 #include "pmx_switches.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 #include <cstdlib>
 
 #define TB 32768                 // bias of the u16 lanes
@@ -65,11 +66,11 @@ void pmx_trace16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
     unsigned char *rsym = lds + NP * PROF_STRIDE;
     int16_t *mat = reinterpret_cast<int16_t *>(rsym + NP * RP);
     unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
+    // per pair four ints relative to the block's first pair, dword-aligned: 16 bytes, not the 40 of PmxPairTab
     int *ptab = reinterpret_cast<int *>(map + 256 + ((4 - ((msize * msize * 2) & 3)) & 3));
 
     const long long pair0 = (long long)blockIdx.x * NP;
-    for (int i = lane; i < msize * msize; i += 64) mat[i] = gmat[i];
-    for (int i = lane; i < 256; i += 64) map[i] = gmap[i];
+    pmx_stage_matrix(mat, map, gmat, gmap, msize * msize, lane, 64);
     if (lane < NP) {
         long long pi = pair0 + lane; if (pi >= n) pi = n - 1;
         const long long qb = qoff[pi], rb = roff[pi];
@@ -86,25 +87,8 @@ void pmx_trace16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 #pragma unroll
     for (int p = 0; p < NP; ++p) max_rlen = max(max_rlen, ptab[4 * p + 3]);
 
-    // reference symbols: G-1 virtual columns in front, pad symbol behind
-    for (int p = 0; p < NP; ++p) {
-        const int rl = ptab[4 * p + 3];
-        const uint8_t *rp = rbase + ptab[4 * p + 2];
-        for (int j0 = 0; j0 < RP; j0 += 64 * 4) {
-            unsigned char raw[4]; bool ok[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * 64 + lane, jj = j - (G - 1);
-                ok[u] = j < RP && jj >= 0 && jj < rl;
-                raw[u] = ok[u] ? rp[jj] : (unsigned char)0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * 64 + lane;
-                if (j < RP) rsym[p * RP + j] = ok[u] ? map[raw[u]] : (unsigned char)msize;
-            }
-        }
-    }
+    for (int p = 0; p < NP; ++p)
+        pmx_stage_ref_symbols<G, 4>(rsym + p * RP, RP, rbase + ptab[4 * p + 2], ptab[4 * p + 3], map, msize, lane, 64);
     // extended profile: P virtual rows on top, then the qlen real rows
     const int vrow_score = row_pen ? TNEG : 0, vcol_score = col_pen ? TNEG : 0;
     for (int p = 0; p < NP; ++p) {
@@ -243,13 +227,8 @@ void pmx_trace16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         int krow = 0;
 #pragma unroll
         for (int k = R - 1; k >= 0; --k) if ((swsave[k] & 0xFFFFu) == swbest) krow = k;
-        unsigned long long key = ((unsigned long long)swbest << 32) | ((unsigned long long)(0xFFFFu - (swcol & 0xFFFFu)) << 16) |
-                                 (unsigned long long)(0xFFFFu - (unsigned)(g * R + krow));
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(key, off, 64);
-            key = o > key ? o : key;
-        }
+        const unsigned long long key = pmx_slot_best_key<G>(((unsigned long long)swbest << 32) | ((unsigned long long)(0xFFFFu - (swcol & 0xFFFFu)) << 16) |
+                                                             (unsigned long long)(0xFFFFu - (unsigned)(g * R + krow)));
         if (g == 0) {
             const long long pi = pair0 + slot;
             if (pi < n) {
@@ -263,29 +242,15 @@ void pmx_trace16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
         }
         return;
     }
-    // ---- combine (same rules as pmx_nwsg16.hip / the oracle) ---------------------------------
-    unsigned key = ((unsigned)bestcol << 16) | (0xFFFFu - (unsigned)bestcoli);
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-        const unsigned o = __shfl_xor(key, off, 64);
-        key = o > key ? o : key;
-    }
+    // ---- combine: the end rule of DESIGN.md 2.1a ------------------------------------------------
+    const unsigned key = pmx_slot_best_key<G>(pmx_slot_key((unsigned)bestcol, (unsigned)bestcoli));
     const int lastlane = slot * G + G - 1;
     const int resL = __shfl(res, lastlane, 64), browL = __shfl(bestrow, lastlane, 64), browjL = __shfl(bestrowj, lastlane, 64);
     if (g == 0) {
         const long long pi = pair0 + slot;
         if (pi < n) {
-            pmx_record_t rec; rec.flags = 0;
-            if (!s1_end && !s2_end) { rec.score = resL - TB; rec.end_query = ql - 1; rec.end_ref = rl - 1; }
-            else {
-                int best = -2147483647 - 1, ei = 0, ej = 0;
-                if (s2_end) { best = browL - TB; ei = ql - 1; ej = browjL; }
-                if (s1_end) {
-                    const int cv = (int)(key >> 16) - TB;
-                    if (cv > best) { best = cv; ei = (int)(0xFFFFu - (key & 0xFFFFu)) - P; ej = rl - 1; }
-                }
-                rec.score = best; rec.end_query = ei; rec.end_ref = ej;
-            }
+            const PmxEnd e = pmx_sg_end(s1_end, s2_end, ql, rl, resL - TB, browL - TB, browjL, pmx_key_value(key) - TB, pmx_key_row(key) - P);
+            pmx_record_t rec; rec.score = e.score; rec.end_query = e.end_query; rec.end_ref = e.end_ref; rec.flags = 0;
             out[pi] = rec;
         }
     }
@@ -429,27 +394,24 @@ static int launch_trace(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
                         uint32_t *ops, const int64_t *ops_off, int32_t *nops, int32_t *beg, pmx_stats_t *stats_out, hipStream_t stream)
 {
     constexpr int QP = G * R, NP = 64 / G;
-    const int RP = ((b.max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4;
+    const int RP = pmx_strip_ref_cols(b.max_rlen, G);
     const size_t lds = (size_t)NP * (m.msize + 1) * QP * 2 + (size_t)NP * RP +
                        (size_t)m.msize * m.msize * 2 + 256 + 4 + (size_t)NP * 16;
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_trace16_kernel<G, R, SW>)); if (rc) return rc; }
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = SW ? 0 : !(sg && (sg_flags & PMX_SG_QB)), row_pen = SW ? 0 : !(sg && (sg_flags & PMX_SG_DB));
-    const int s1_end = sg && (sg_flags & PMX_SG_QE), s2_end = sg && (sg_flags & PMX_SG_DE);
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
     hipLaunchKernelGGL((pmx_trace16_kernel<G, R, SW>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                       m.msize, open, ext, RP, Tmax, col_pen, row_pen, s1_end ? 1 : 0, s2_end ? 1 : 0, d_out, tbuf);
+                       m.msize, open, ext, RP, Tmax, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, d_out, tbuf);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return -(int)e;
     const int stage = walk_stage_bytes(b);
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_walk16_kernel<G, R, false>), 128 * 1024); if (rc) return rc; }
     hipLaunchKernelGGL((pmx_walk16_kernel<G, R, false>), dim3((unsigned)((b.n + 63) / 64)), dim3(64), 2 * (size_t)stage, stream,
-                       b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.mapper, m.scores, m.msize, open, ext, mode, Tmax, stage, 0, stats_out, row_pen, col_pen,
+                       b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.mapper, m.scores, m.msize, open, ext, mode, Tmax, stage, 0, stats_out, ends.row_pen, ends.col_pen,
                        (const uint32_t *)tbuf, (const pmx_record_t *)d_out, ops, ops_off, 0LL, nops, beg, (int32_t *)nullptr);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 // Picks the instantiation; *trace_bytes / *Tmax tell the caller how much trace scratch to provide
@@ -494,8 +456,7 @@ int pmx_launch_trace16(int variant, const PmxBatch &b, const PmxDevMatrix &m, in
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     const bool sw = mode == PMX_MODE_SW;
-    const bool sg_ = mode == PMX_MODE_SG;
-    const int col_pen_ = sw ? 0 : !(sg_ && (sg_flags & PMX_SG_QB)), row_pen_ = sw ? 0 : !(sg_ && (sg_flags & PMX_SG_DB));
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     if (variant >= 10) {
         const int top = variant >= 20 ? 1 : 0;
         // (Tmax is a multiple of 16 -- the plans round it -- so a walk window never crosses into the next lane's stream)
@@ -512,7 +473,7 @@ int pmx_launch_trace16(int variant, const PmxBatch &b, const PmxDevMatrix &m, in
         const long long ops_base = split ? split->ops_base : 0;
         int32_t *textlen = split ? split->textlen : nullptr;
         // (Tmax is a multiple of 16 -- the plans round it -- so a walk window never crosses into the next lane's stream)
-        rc = pmx_launch_walkp((variant % 10) & 3, 16, b, m, mode, open, ext, Tmax, top, stats_out, row_pen_, col_pen_,
+        rc = pmx_launch_walkp((variant % 10) & 3, 16, b, m, mode, open, ext, Tmax, top, stats_out, ends.row_pen, ends.col_pen,
                               (const uint32_t *)tbuf, (const pmx_record_t *)d_out, ops, ops_off, ops_base, nops, beg, textlen, wstream,
                               (!top && variant - 10 < 4) ? b.blockflag : nullptr);      // (the nwsgv shapes: their launcher fills the flags)
         if (rc) return rc;

@@ -12,6 +12,7 @@
 // region, LP bytes apart: eight or more consecutive cells share a cache line.  The walk reads only cells of the band inside the
 // matrix; a step that would leave them ends the walk.
 #include "pmx_common.h"
+#include "pmx_strip.h"
 
 #define OP_EQ 7u
 #define OP_X 8u
@@ -132,21 +133,18 @@ int pmx_launch_walkb(int mode, int sg_flags, int open, int ext, const PmxDevMatr
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (n <= 0) return 0;
-    const bool sg = mode == PMX_MODE_SG;
-    const int col_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_QB));   // H(i, -1) penalised
-    const int row_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_DB));   // H(-1, j) penalised
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
     const int LP = pmx_bandtr_geometry_of(1, 1, band).LP;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
 #define WB2(STV, SWV, BGV) hipLaunchKernelGGL((pmx_walkb_kernel<STV, SWV, BGV>), grid, block, 0, stream, qbuf, qoff, q_shared, rbuf, roff, n, \
-        m.mapper, m.scores, m.msize, open, ext, mode, row_pen, col_pen, band, diag, recs, tr, LP, slot_qoff, ops_base, ops, nops, textlen, stats_out, beg)
+        m.mapper, m.scores, m.msize, open, ext, mode, ends.row_pen, ends.col_pen, band, diag, recs, tr, LP, slot_qoff, ops_base, ops, nops, textlen, stats_out, beg)
 #define WB(STV, SWV) do { if (beg) WB2(STV, SWV, true); else WB2(STV, SWV, false); } while (0)
     const bool sw = mode == PMX_MODE_SW;
     if (stats_out) { if (sw) WB(true, true); else WB(true, false); }
     else { if (sw) WB(false, true); else WB(false, false); }
 #undef WB
 #undef WB2
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
 
 __global__ void pmx_shared_offsets_kernel(int64_t *off, long long n, int qlen)
@@ -157,6 +155,5 @@ __global__ void pmx_shared_offsets_kernel(int64_t *off, long long n, int qlen)
 int pmx_launch_shared_offsets(int64_t *off, long long n, int qlen, hipStream_t stream)
 {
     hipLaunchKernelGGL(pmx_shared_offsets_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, stream, off, n, qlen);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

@@ -121,6 +121,5 @@ int pmx_launch_walkfs(const PmxDevMatrix &m, long long n, int per, const uint8_t
                        qbuf, qoff, rbuf, roff, n, per, win,
                        m.mapper, m.scores, m.msize, max_rlen, recs, trace, trace_bytes_per_slot, ops, nops, textlen, pair_qoff, pair_roff,
                        beg, stats_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

@@ -254,6 +254,5 @@ int pmx_launch_walkp(int gsel, int R, const PmxBatch &b, const PmxDevMatrix &m, 
 #undef WALKP
 #undef WALKP4
 #undef WALKP5
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }

@@ -22,6 +22,7 @@
 // empty outputs, and the host turns that into an error.
 #include "pmx_common.h"
 #include "pmx_pk16.h"
+#include "pmx_strip.h"
 
 #define OP_EQ 7u
 #define OP_X 8u
@@ -197,9 +198,8 @@ int pmx_launch_walkt(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_
     PmxWalktArgs a;
     a.qbuf = b.qbuf; a.qoff = b.qoff; a.rbuf = b.rbuf; a.roff = b.roff; a.n = b.n;
     a.mapper = m.mapper; a.scores = m.scores; a.msize = m.msize; a.open = open; a.ext = ext; a.mode = mode;
-    const bool sg = mode == PMX_MODE_SG;
-    a.col_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_QB));
-    a.row_pen = mode == PMX_MODE_NW || (sg && !(sg_flags & PMX_SG_DB));
+    const PmxEnds ends = pmx_ends(mode, sg_flags);
+    a.col_pen = ends.col_pen; a.row_pen = ends.row_pen;
     a.recs = recs;
     long long bstride = 0; int nbmax = 0;
     (void)pmx_long_scratch_bytes(b.n, b.max_qlen, b.max_rlen, R, &bstride, &nbmax);
@@ -219,6 +219,5 @@ int pmx_launch_walkt(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_
         const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_walkt_kernel<false>)); if (rc) return rc;
         hipLaunchKernelGGL((pmx_walkt_kernel<false>), dim3((unsigned)b.n), dim3(64), lds, stream, a);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return pmx_launched();
 }
