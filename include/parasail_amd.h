@@ -1253,6 +1253,54 @@ int pmx_align_pairs_frameshift_ref_cigar(const pmx_config_t *cfg, const pmx_seqs
  * to max_rlen letters. */
 long long pmx_swfsc_trace_bytes_per_slot(int max_qlen, int max_rlen);
 
+/* Windowed frameshift traceback, reference side (extension): pmx_align_pairs_frameshift_ref_cigar[_device] for LONG REFERENCES --
+ * contigs, chromosomes' worth of window -- whose m x N matrix of decision bytes does not fit the bound on a chunk's trace.  The
+ * arguments are exactly those of pmx_align_pairs_frameshift_ref_cigar[_device], and EVERY OUTPUT -- records, strand bytes, statistics,
+ * begins, text and offsets -- IS BYTE-IDENTICAL to what that entry writes for the same arguments, wherever that entry runs.
+ *
+ * How.  A local path behind a record (score S, end cell (end_query, end_ref)) has paid for every codon gap and every frameshift
+ * operator out of S, so it spans few columns.  With rows = end_query + 1, P = the sum over query letters 0 .. end_query of
+ * max(0, the largest score of the letter's matrix row), slack = P - S and gmin = min(open, extend), a path of score S that ends at the
+ * end cell spans at most
+ *     W = 3 rows + 3 floor(slack / gmin) + min(rows - 1, floor(slack / frameshift))         (frameshift 0: the last term is rows - 1)
+ * nucleotides (gmin = 0 bounds nothing: the whole window).  The entry runs the score road of pmx_align_pairs_frameshift_ref_device over
+ * the full windows, cuts every pair down to query letters [0, end_query] and oriented nucleotides [max(0, end_ref + 1 - W), end_ref]
+ * on the device, runs the trace sweep and the walk of the _ref_cigar entries over those windows on the winner's strand, and moves
+ * end_ref and beg_ref back into the pair's own oriented window.  Every decision on the walked path, and the end cell under the tie
+ * rule, are those of the full matrix (DESIGN 2.5o has the proof); the entry holds the second pass's record against the first pass's,
+ * and a difference ends the call with -1 and "window proof violated" -- a bug to report, not an input condition.
+ *
+ * Refusals.  Everything pmx_align_pairs_frameshift_ref_cigar[_device] refuses, with the same texts, EXCEPT the bound on four slots of
+ * the un-narrowed shape: 4 096 letters x 100 kb is taken.  Behind the score pass of a chunk, a pair whose own narrowed window exceeds
+ * the bound with four slots is refused with that bound's text, naming the narrowed figures.
+ *
+ * Scratch and parts.  The trace pass runs a chunk in parts of consecutive pairs, cut on the host so that a part's slots times
+ * pmx_swfsc_trace_bytes_per_slot(the part's longest narrowed query, the part's longest narrowed stream) stay under the bound (256 MiB,
+ * or the value switch PMX_CIGAR_CHUNK_BYTES): a weak hit with a wide window shrinks its own part only.  Beside the score entry's
+ * scratch, 61 bytes per pair of a chunk.  chunk_pairs, the bound and the parts never change an output byte.
+ * THE DEVICE ENTRY SYNCHRONISES THE CALLER'S STREAM ONCE PER CHUNK (the narrowed lengths come to the host, which cuts the parts) AND
+ * ONCE BEHIND THE LAST CHUNK (the proof's check): when it returns 0 all outputs are written.  pmx_last_kernel() names the trace
+ * instantiation of the last part, as the _ref_cigar entries do.
+ * pmx_frameshift_ref_cigar_long_parts(): the number of parts the calling thread's last call of either entry ran, over all chunks (the
+ * host entry: of its last pass). */
+int pmx_align_pairs_frameshift_ref_cigar_long_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                     int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                     int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                     pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats /* iff PMX_WANT_STATS */,
+                                                     int32_t *d_beg /* 2 n, optional */,
+                                                     char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off /* n + 1 */,
+                                                     void *stream, const pmx_pairs_opts_t *opts);
+int pmx_align_pairs_frameshift_ref_cigar_long(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                              int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                              int32_t frameshift, const uint8_t *code,
+                                              pmx_record_t *out, uint8_t *strand_out, pmx_stats_t *stats_out /* iff PMX_WANT_STATS */,
+                                              int32_t *beg /* 2 n, optional */, char **cigar_buf, int64_t *cigar_off /* n + 1 */,
+                                              const pmx_pairs_opts_t *opts);
+int64_t pmx_frameshift_ref_cigar_long_parts(void);
+/* Test hook: W of the bound above (parasail-rs_amd/csrc/pmx_fswin.h, the function the kernel runs) for P = rowmax_prefix, S = score and
+ * rows = end_query + 1; 2^63 - 1 where nothing is bounded (min(open, extend) = 0). */
+long long pmx_swfsc_window_cols(long long rowmax_prefix, long long score, long long rows, long long open, long long extend, long long fs);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -381,6 +381,13 @@ _sig("pmx_align_pairs_frameshift_ref_cigar_device", C.c_int, C.POINTER(pmx_confi
      C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_align_pairs_frameshift_ref_cigar", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_frameshift_ref_cigar_long_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+     C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_align_pairs_frameshift_ref_cigar_long", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_frameshift_ref_cigar_long_parts", C.c_int64)
+_sig("pmx_swfsc_window_cols", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong)
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -1144,6 +1151,14 @@ class Aligner:
         (records, cigars, begins, strand, stats): matches, similar and length along the path."""
         return self._frameshift_cigar(lib.pmx_align_pairs_frameshift_ref_cigar, "align_pairs_frameshift_ref_cigar", Q, R, pairs, ref_frameshift,
                                       ref_strand, code, stats, chunk_pairs)
+
+    def align_pairs_frameshift_ref_cigar_long(self, Q, R, pairs, ref_frameshift, ref_strand=0, code=None, stats=False, chunk_pairs=0):
+        """align_pairs_frameshift_ref_cigar for long references: the same arguments and, byte for byte, the same results, but the
+        traceback runs only over the window of each reference that a path of the record's score can span (include/parasail_amd.h,
+        "Windowed frameshift traceback, reference side"), so a protein against a 100 kb contig is taken where
+        align_pairs_frameshift_ref_cigar refuses the trace of the whole matrix."""
+        return self._frameshift_cigar(lib.pmx_align_pairs_frameshift_ref_cigar_long, "align_pairs_frameshift_ref_cigar_long", Q, R, pairs,
+                                      ref_frameshift, ref_strand, code, stats, chunk_pairs)
 
     def _frameshift_cigar(self, entry, name, Q, R, pairs, frameshift, strand, code, stats, chunk_pairs):
         """The host traceback entry of either side (`entry`) over listed pairs."""
@@ -2077,6 +2092,20 @@ def align_pairs_frameshift_ref_cigar_device(cfg, Q, R, n, d_pairs, d_strand, str
                                                          int(frameshift), code.ctypes.data if code is not None else None, max_qlen, max_rlen,
                                                          d_out, d_strand_out, d_stats, d_beg, d_cigar_text, int(cigar_capacity), d_cigar_off,
                                                          stream, C.byref(opts))
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def align_pairs_frameshift_ref_cigar_long_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, max_qlen, max_rlen, d_out, d_strand_out,
+                                                 d_stats, d_beg, d_cigar_text, cigar_capacity, d_cigar_off, stream=0, chunk_pairs=0, code=None):
+    """align_pairs_frameshift_ref_cigar_device for long references: the same arguments and byte-identical outputs, the traceback over
+    each record's window only.  Synchronises `stream` once per chunk and once at the end."""
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    code = _code_arg(code)
+    rc = lib.pmx_align_pairs_frameshift_ref_cigar_long_device(C.byref(cfg), Q._handle(), R._handle(), n, d_pairs, d_strand, int(strand_mode),
+                                                              int(frameshift), code.ctypes.data if code is not None else None, max_qlen,
+                                                              max_rlen, d_out, d_strand_out, d_stats, d_beg, d_cigar_text,
+                                                              int(cigar_capacity), d_cigar_off, stream, C.byref(opts))
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

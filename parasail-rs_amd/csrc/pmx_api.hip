@@ -1379,7 +1379,8 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_PTOPK = 27,                                                                   // per-query top-K: a chunk's records and statistics (ChunkAlign), tile survivors, the rows' running state, scan scratch
        SCR_PTHIT = 28,                                                                   // per-query top-K, host entry: a slice's hit columns (HitCols) and row arrays, counts, first bad pair
        SCR_SWFS = 29,                                                                    // frameshift entries: the strips' boundary columns (pmx_swfs.hip)
-       SCR_SLOTS = 30 };
+       SCR_FSWIN = 30,                                                                   // windowed frameshift traceback: a chunk's first-pass records and strands, narrowed descriptors, shifts, lengths, the violation count
+       SCR_SLOTS = 31 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -4292,7 +4293,8 @@ static int frameshift_trace_bound_check(size_t bytes_per_slot, int32_t max_qlen,
 static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
                                   int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats,
                                   int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off,
-                                  hipStream_t st, int64_t chunk, const SlotPlan &fr)
+                                  hipStream_t st, int64_t chunk, const SlotPlan &fr,
+                                  bool continues = false /* the pairs are a later stretch of a longer text: d_text_off[0] holds its total so far */)
 {
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
@@ -4332,7 +4334,7 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
                                        (const uint8_t *)trace, (long long)tps, t.ops, t.nops, t.textlen, pair_qoff, pair_roff,
                                        d_beg ? d_beg + 2 * g0 : nullptr, d_stats ? d_stats + g0 : nullptr, st, ref);
                 if (rc) { set_err("frameshift walk launch failed (%d)", rc); return rc < 0 ? rc : -1; }
-                rc = t.render(pair_qoff, pair_roff, 0, pn, d_text, capacity, d_text_off + g0, st, g0 > 0 ? local_off : nullptr);
+                rc = t.render(pair_qoff, pair_roff, 0, pn, d_text, capacity, d_text_off + g0, st, g0 > 0 || continues ? local_off : nullptr);
                 if (rc) return rc;
             }
             return 0;
@@ -4380,6 +4382,109 @@ extern "C" int pmx_align_pairs_frameshift_ref_cigar_device(const pmx_config_t *c
 {
     return align_pairs_codons_cigar_device(cfg, Q, R, n, d_pairs, d_strand, strand_mode, frameshift, code, max_qlen, max_rlen, d_out, d_strand_out,
                                            d_stats, d_beg, d_cigar_text, cigar_capacity, d_cigar_off, stream, opts, true);
+}
+
+// ---- windowed frameshift traceback, reference side: the score road, the window of every record, the trace road over it ----
+static thread_local int64_t g_fswin_parts = 0;
+extern "C" int64_t pmx_frameshift_ref_cigar_long_parts(void) { return g_fswin_parts; }
+
+// The road of the _frameshift_ref_cigar_long entries.  Per chunk of `chunk` pairs, all on `st`:
+//   1. the score road of pmx_align_pairs_frameshift_ref_device over the full windows (both strands swept and folded in
+//      PMX_STRAND_BOTH) into scratch: the chunk's records, and the winners' strands;
+//   2. pmx_fsref_window_kernel: every record's narrowed descriptor, column shift and narrowed lengths;
+//   3. the lengths to the host -- THE ONE SYNCHRONISATION OF `st` PER CHUNK;
+//   4. pairs_run_codons_cigar over the narrowed descriptors, one slot per pair on the winner's strand, in parts of consecutive pairs
+//      cut greedily so that a part's slots (whole workgroups of four) times the trace of its own narrowed maxima stay under the bound:
+//      a weak hit with a wide window shrinks its own part only, and op slots, boundary scratch and trace stride are the part's;
+//   5. pmx_fsref_rebase_kernel: end_ref and beg_ref back into the pair's window, and the rebased record held against step 1's.
+// A record that differs is a bug in the window's proof, not an input condition: the call returns -1 ("window proof violated"); the count
+// is read with the next chunk's lengths and once behind the last chunk.  A pair whose narrowed window alone exceeds the bound with four
+// slots is refused behind the score pass of its chunk.  The text continues behind the parts and chunks before it, so neither
+// chunk_pairs nor the bound nor the parts change a byte.
+static int pairs_run_codons_cigar_windowed(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
+                                           int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats,
+                                           int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off,
+                                           hipStream_t st, int64_t chunk, const SlotPlan &fr)
+{
+    DevMat dm;
+    if (get_devmat(cfg->matrix, &dm)) return -1;
+    pmx_record_t *rec1 = nullptr; pmx_pair_t *npairs = nullptr; int32_t *ashift = nullptr, *nlen = nullptr; uint8_t *sbuf = nullptr; unsigned *viol = nullptr;
+    if (scratch_carve(SCR_FSWIN, [&](Carver &c) {
+            rec1 = c.take<pmx_record_t>((size_t)chunk); npairs = c.take<pmx_pair_t>((size_t)chunk);
+            ashift = c.take<int32_t>((size_t)chunk); nlen = c.take<int32_t>(2 * (size_t)chunk);
+            sbuf = c.take<uint8_t>((size_t)chunk); viol = c.take<unsigned>(1);
+        })) return -1;
+    std::vector<int32_t> h_nlen(2 * (size_t)chunk);
+    unsigned h_viol = 0;
+    pmx_config_t cfg1 = *cfg;
+    cfg1.want &= ~(PMX_WANT_STATS | PMX_WANT_CIGAR);            // (the score pass)
+    const double bound = frameshift_trace_bound();
+    g_fswin_parts = 0;
+    HIP_OR_RET(hipMemsetAsync(viol, 0, sizeof(unsigned), st));
+    auto violated = [&]() -> int {
+        if (!h_viol) return 0;
+        set_err("window proof violated: %u records of the narrowed trace pass differ from the score pass", h_viol);
+        return -1;
+    };
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int64_t cn = std::min<int64_t>(chunk, n - c0);
+        SlotPlan p1 = fr;
+        if (p1.d_byte) p1.d_byte += c0;
+        uint8_t *won = d_strand_out ? d_strand_out + c0 : sbuf;
+        int rc = pairs_run_folded(&cfg1, Q, R, cn, d_pairs + c0, p1, max_qlen, max_rlen, rec1, nullptr, won, st, cn);
+        if (rc) return rc;
+        rc = pmx_launch_fsref_window(d_pairs + c0, rec1, won, cn, Q->d_buf, Q->d_off, Q->count, Q->bytes, R->d_off, R->count, R->bytes,
+                                     dm.d, cfg->open, cfg->extend, fr.frameshift, npairs, ashift, nlen, st);
+        if (rc) { set_err("frameshift window kernel launch failed (%d)", rc); return rc < 0 ? rc : -1; }
+        HIP_OR_RET(hipMemcpyAsync(h_nlen.data(), nlen, sizeof(int32_t) * 2 * (size_t)cn, hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipMemcpyAsync(&h_viol, viol, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipStreamSynchronize(st));
+        if (violated()) return -1;
+        for (int64_t k = 0; k < cn; ++k) {
+            const int32_t nq = std::max<int32_t>(1, h_nlen[2 * k]), nr = std::max<int32_t>(1, h_nlen[2 * k + 1]);
+            const size_t tps = frameshift_trace_bytes_per_slot(true, nq, nr);
+            if (4.0 * (double)tps > bound) { (void)frameshift_trace_bound_check(tps, nq, nr); return -1; }      // (the existing text, the narrowed figures)
+        }
+        SlotPlan p2 = fr;
+        p2.first = 0; p2.per = 1;
+        for (int64_t p0 = 0; p0 < cn;) {
+            int32_t mq = 1, mr = 1; int64_t pn = 0;
+            while (p0 + pn < cn) {
+                const int32_t nq = std::max(mq, h_nlen[2 * (p0 + pn)]), nr = std::max(mr, h_nlen[2 * (p0 + pn) + 1]);
+                if (pn > 0 && (double)((pn + 4) / 4 * 4) * (double)frameshift_trace_bytes_per_slot(true, nq, nr) > bound) break;
+                mq = nq; mr = nr; ++pn;
+            }
+            const int64_t g0 = c0 + p0;
+            p2.d_byte = won + p0;
+            rc = pairs_run_codons_cigar(cfg, Q, R, pn, npairs + p0, mq, mr, d_out + g0, nullptr, d_stats ? d_stats + g0 : nullptr,
+                                        d_beg ? d_beg + 2 * g0 : nullptr, d_text, capacity, d_text_off + g0, st, pn, p2, g0 > 0);
+            if (rc) return rc;
+            p0 += pn; ++g_fswin_parts;
+        }
+        rc = pmx_launch_fsref_rebase(rec1, ashift, cn, d_out + c0, d_beg ? d_beg + 2 * c0 : nullptr, viol, st);
+        if (rc) { set_err("frameshift rebase kernel launch failed (%d)", rc); return rc; }
+    }
+    HIP_OR_RET(hipMemcpyAsync(&h_viol, viol, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    return violated();
+}
+
+extern "C" int pmx_align_pairs_frameshift_ref_cigar_long_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                                int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_strand, int strand_mode,
+                                                                int32_t frameshift, const uint8_t *code, int32_t max_qlen, int32_t max_rlen,
+                                                                pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats, int32_t *d_beg,
+                                                                char *d_cigar_text, int64_t cigar_capacity, int64_t *d_cigar_off,
+                                                                void *stream, const pmx_pairs_opts_t *opts)
+{
+    SlotPlan fr;
+    if (listed_entry_check(cfg, Q, R, n, d_pairs, d_out, opts) || frameshift_check(cfg, strand_mode, d_strand, frameshift, code, &fr, true, true) ||
+        frameshift_cigar_outputs_check(cfg, d_stats, d_cigar_text, cigar_capacity, d_cigar_off) || byte_out_check(fr, n > 0, d_strand_out)) return -1;
+    if (n == 0) return 0;
+    if (frameshift_rows_check(max_qlen, true) || pairs_check(cfg, Q, R, opts, max_qlen, max_rlen, d_stats != nullptr, true)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return pairs_run_codons_cigar_windowed(cfg, Q, R, n, d_pairs, max_qlen, max_rlen, d_out, d_strand_out, d_stats, d_beg, d_cigar_text, cigar_capacity,
+                                           d_cigar_off, (hipStream_t)stream, pairs_chunk(n, max_qlen, max_rlen, opts, fr.per), fr);
 }
 
 extern "C" int pmx_gather_pairs_codons_device(const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs,
@@ -4839,7 +4944,8 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
                                        int32_t frameshift, const uint8_t *code, pmx_record_t *out, uint8_t *strand_out,
                                        const pmx_pairs_opts_t *opts, bool traceback,
                                        pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off,
-                                       bool ref = false /* pmx_align_pairs_frameshift_ref[_cigar]: the stream is the reference's */)
+                                       bool ref = false /* pmx_align_pairs_frameshift_ref[_cigar]: the stream is the reference's */,
+                                       bool windowed = false /* pmx_align_pairs_frameshift_ref_cigar_long: the windowed road, no bound on the un-narrowed shape */)
 {
     SlotPlan fr;
     if (listed_entry_check(cfg, Q, R, n, pairs, out, opts) || frameshift_check(cfg, strand_mode, strand, frameshift, code, &fr, traceback, ref) ||
@@ -4850,14 +4956,15 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
     DevBuf<int64_t> dtoff; DevBuf<int32_t> dbeg; DevBuf<char> dtext;
     const int rc = translated_pairs_host(cfg, Q, R, n, pairs, strand, fr, out, stats_out, strand_out, opts, traceback, false,
         [&](int32_t mq, int32_t mr, bool known) {
-            return frameshift_rows_check(mq, ref) || (traceback && known && frameshift_trace_bound_check(frameshift_trace_bytes_per_slot(ref, mq, mr), mq, mr)) ? -1 : 0;
+            return frameshift_rows_check(mq, ref) || (traceback && !windowed && known && frameshift_trace_bound_check(frameshift_trace_bytes_per_slot(ref, mq, mr), mq, mr)) ? -1 : 0;
         },
         [&](const pmx_config_t *c, const pmx_pair_t *dp, int32_t q32, int32_t r32, pmx_record_t *drec, pmx_stats_t *dst, uint8_t *dsout, hipStream_t st) -> int {
             const int64_t chunk = pairs_chunk(n, q32, r32, opts, fr.per);
             if (!traceback) return pairs_run_folded(c, Q, R, n, dp, fr, q32, r32, drec, nullptr, dsout, st, chunk);
             if (dtoff.try_alloc((size_t)n + 1) || (beg && dbeg.try_alloc(2 * (size_t)n)) || dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
             for (int pass = 0; pass < 2; ++pass) {
-                const int rc = pairs_run_codons_cigar(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr);
+                const int rc = windowed ? pairs_run_codons_cigar_windowed(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr)
+                                        : pairs_run_codons_cigar(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr);
                 if (rc) return rc;
                 HIP_OR_RET(hipMemcpyAsync(cigar_off, dtoff.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
                 HIP_OR_RET(hipStreamSynchronize(st));
@@ -4917,6 +5024,16 @@ extern "C" int pmx_align_pairs_frameshift_ref_cigar(const pmx_config_t *cfg, con
 {
     return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, true,
                                        stats_out, beg, cigar_buf, cigar_off, true);
+}
+
+extern "C" int pmx_align_pairs_frameshift_ref_cigar_long(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
+                                                         int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
+                                                         int32_t frameshift, const uint8_t *code,
+                                                         pmx_record_t *out, uint8_t *strand_out, pmx_stats_t *stats_out, int32_t *beg,
+                                                         char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts)
+{
+    return align_pairs_frameshift_host(cfg, Q, R, n, pairs, strand, strand_mode, frameshift, code, out, strand_out, opts, true,
+                                       stats_out, beg, cigar_buf, cigar_off, true, true);
 }
 
 extern "C" int pmx_align_all_pairs(const pmx_config_t *cfg, const pmx_seqset_t *S, int64_t first, int64_t count,

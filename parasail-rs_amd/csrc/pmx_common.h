@@ -385,6 +385,17 @@ int pmx_launch_walkfs(const PmxDevMatrix &m, long long n, int per, const uint8_t
                       const pmx_record_t *recs, const uint8_t *trace, long long trace_bytes_per_slot,
                       uint32_t *ops, int32_t *nops, int32_t *textlen, int64_t *pair_qoff, int64_t *pair_roff,
                       int32_t *beg, pmx_stats_t *stats_out, hipStream_t stream, bool ref = false);
+// The windowed form of that traceback (pmx_pairs.hip; the bound: pmx_fswin.h).  window: n folded records of the score
+// pass with their strand bytes and descriptors -> npairs, the descriptors of the sub-windows the records' paths lie in (a bad record: a
+// descriptor that is bad whatever the maxima), ashift, the oriented column each narrowed window starts at, and nlen (2 n), the narrowed
+// query letters and stream letters (0 / 0 for a bad record).  rebase: ashift onto end_ref of rec and onto beg[2 k + 1] (beg may be
+// NULL), and violations[0] += the records that then differ from `first`.  0 launched, 1 not eligible, <0 HIP error.
+extern "C" long long pmx_swfsc_window_cols(long long rowmax_prefix, long long score, long long rows, long long open, long long extend, long long fs);
+int pmx_launch_fsref_window(const pmx_pair_t *pairs, const pmx_record_t *rec, const uint8_t *strand, long long n, const uint8_t *q_buf,
+                            const int64_t *q_off, long long q_count, long long q_bytes, const int64_t *r_off, long long r_count, long long r_bytes,
+                            const PmxDevMatrix &m, int open, int ext, int fs, pmx_pair_t *npairs, int32_t *ashift, int32_t *nlen, hipStream_t stream);
+int pmx_launch_fsref_rebase(const pmx_record_t *first, const int32_t *ashift, long long n, pmx_record_t *rec, int32_t *beg, unsigned *violations,
+                            hipStream_t stream);
 // Per-query top-K (pmx_topk.hip; semantics: include/parasail_amd.h).  ks = min(k, |R|).  The running state of local row
 // li: st_keys / st_recs / st_stats[li * ks ..) hold st_held[li] entries in (score descending, j ascending) order, st_passing[li] = |P_i|
 // so far; the caller zeroes st_held (nq + 1 entries, the scan's input) and st_passing before the first chunk.  geometry: what the tile

@@ -27,10 +27,14 @@
 // and, for codon streams (the _frameshift entries: the query's; the _frameshift_ref entries: the reference's):
 //   pmx_pairs_resolve_codons_kernel     one descriptor -> `per` slots (1 or 2), one per strand: the stream's length, nucleotide window
 //   pmx_pairs_gather_codons_kernel      the gather that writes the stride-1 codon stream of that side's window, on either strand
+// and, for the windowed reference-side frameshift traceback (the _frameshift_ref_cigar_long entries):
+//   pmx_fsref_window_kernel             a folded record and its strand -> the descriptor of the sub-window its path lies in, the shift
+//   pmx_fsref_rebase_kernel             the trace pass's end_ref and beg_ref back into the pair's window; the proof's check
 // The resolve kernels share pmx_resolve_pair / pmx_slot_store, the gather kernels pmx_gather_group / pmx_gather_copy.
 //
 // All of them are bandwidth kernels in plain C++: vector loads and stores only.
 #include "pmx_common.h"
+#include "pmx_fswin.h"
 
 // One side of a descriptor against its set.  0 = bad; otherwise the window's length, *src = its first byte in the set's buffer.
 // A set wrapped around caller buffers has unchecked offsets: a window is good only when it lies inside [0, bytes).
@@ -486,6 +490,82 @@ void pmx_pairs_gather_codons_kernel(long long n, const uint8_t *__restrict__ q_b
     }
 }
 
+// ---- the windowed reference-side frameshift traceback (the _frameshift_ref_cigar_long entries) -------------------------
+// Between the score pass and the trace pass: pair k's folded record (score S, end cell (eq, er) in the oriented reference window) and
+// strand byte become the descriptor of the only sub-window a path of that record can lie in -- query rows [0, eq], oriented nucleotides
+// [a, er + 1) with a = max(0, er + 1 - W), W = pmx_fswin_cols (pmx_fswin.h) -- in stored coordinates: oriented [a, b) of a strand-1
+// window is stored [r_beg + rl - b, r_beg + rl - a), rl the resolved length (r_len -1 is resolved here).  A 16-lane group per pair:
+// the lanes sum max(0, max_b s(q_i, b)) over the query letters 0 .. eq, lane-strided, from a table of the matrix's row maxima staged
+// in LDS, and a shuffle reduction over the group leaves P in lane 0.  A zero-score record (eq 0, er 2) gets the 1 x 3 window the
+// formula gives, which scores zero again.  A bad record, or one whose end cell lies outside its resolved windows, gets a descriptor
+// that is bad whatever the maxima (q = -1), shift 0 and lengths 0.  A narrowed r_beg that would not fit 32 bits leaves the pair's
+// descriptor as it is (shift 0): the whole window is a sound window.  nlen[2 k], nlen[2 k + 1]: the narrowed query letters and the
+// narrowed stream's letters, what the host cuts the parts of the trace pass by.
+__global__ __launch_bounds__(256)
+void pmx_fsref_window_kernel(const pmx_pair_t *__restrict__ pairs, const pmx_record_t *__restrict__ rec, const uint8_t *__restrict__ strand,
+                             long long n, const uint8_t *__restrict__ q_buf,
+                             const int64_t *__restrict__ q_off, long long q_count, long long q_bytes,
+                             const int64_t *__restrict__ r_off, long long r_count, long long r_bytes,
+                             const int16_t *__restrict__ scores, const uint8_t *__restrict__ mapper, int msize, int open, int ext, int fs,
+                             pmx_pair_t *__restrict__ npairs, int32_t *__restrict__ ashift, int32_t *__restrict__ nlen)
+{
+    __shared__ int rowmax[256];                                   // max(0, the row's largest score); 0 for an index the matrix does not have
+    __shared__ uint8_t map[256];
+    {
+        const int t = threadIdx.x;
+        int v = 0;
+        if (t < msize) for (int b = 0; b < msize; ++b) v = max(v, (int)scores[t * msize + b]);
+        rowmax[t] = v; map[t] = mapper[t];
+    }
+    __syncthreads();
+    const long long k = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
+    const int lane = threadIdx.x & 15;
+    const bool live = k < n;                                      // (uniform per group; every lane reaches the shuffles)
+    pmx_pair_t p = {}; pmx_record_t r = {};
+    long long qs = 0, rs = 0; int32_t ql = 0, rl = 0;
+    bool good = false;
+    if (live) {
+        p = pairs[k]; r = rec[k];
+        good = !(r.flags & PMX_FLAG_BAD_PAIR) &&
+               pmx_resolve_pair(p, q_off, q_count, q_bytes, r_off, r_count, r_bytes, INT32_MAX, INT32_MAX, &ql, &rl, &qs, &rs) &&
+               r.end_query >= 0 && r.end_query < ql && r.end_ref >= 2 && r.end_ref < rl;
+    }
+    int P = 0;                                                    // (at most 4 096 rows x 32 767)
+    if (good) for (int i = lane; i <= r.end_query; i += 16) P += rowmax[map[q_buf[qs + i]]];
+#pragma unroll
+    for (int d = 8; d >= 1; d >>= 1) P += __shfl_xor(P, d, 16);
+    if (!live || lane) return;
+    pmx_pair_t o = p; int32_t a = 0, nq = 0, nr = 0;
+    if (!good) o.q = -1;
+    else {
+        const long long W = pmx_fswin_cols(P, r.score, (long long)r.end_query + 1, open, ext, fs);
+        const long long b = (long long)r.end_ref + 1, lo = W >= b ? 0 : b - W;
+        const long long beg = (long long)p.r_beg + (strand[k] ? (long long)rl - b : lo);
+        if (beg <= (long long)INT32_MAX) {
+            a = (int32_t)lo;
+            o.q_len = r.end_query + 1; o.r_beg = (int32_t)beg; o.r_len = (int32_t)(b - lo);
+            nq = o.q_len; nr = o.r_len - 2;
+        } else { nq = ql; nr = rl - 2; }
+    }
+    npairs[k] = o; ashift[k] = a; nlen[2 * k] = nq; nlen[2 * k + 1] = nr;
+}
+
+// Behind the trace pass over the narrowed descriptors: end_ref and beg_ref back into the pair's own oriented window (+ a), and the proof
+// of DESIGN 2.5o held against the score pass -- the rebased record equals the first pass's record field by field, or the pair is
+// counted in violations[0].  A bad pair and a zero-score record have a = 0.
+__global__ __launch_bounds__(256)
+void pmx_fsref_rebase_kernel(const pmx_record_t *__restrict__ first, const int32_t *__restrict__ ashift, long long n,
+                             pmx_record_t *__restrict__ rec, int32_t *__restrict__ beg, unsigned *__restrict__ violations)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    pmx_record_t r = rec[k];
+    const pmx_record_t f = first[k];
+    const int32_t a = ashift[k];
+    if (a) { r.end_ref += a; rec[k] = r; if (beg) beg[2 * k + 1] += a; }
+    if (r.score != f.score || r.end_query != f.end_query || r.end_ref != f.end_ref || r.flags != f.flags) atomicAdd(violations, 1u);
+}
+
 // Bad pairs on the device CIGAR road, between the walk and the text scan: the record, no ops, no text, begins -1 / -1.
 __global__ __launch_bounds__(256)
 void pmx_pairs_fixup_cigar_kernel(const uint8_t *__restrict__ ok, long long n, pmx_record_t *__restrict__ rec,
@@ -729,6 +809,27 @@ int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long 
     const auto kernel = ref ? pmx_pairs_gather_codons_kernel<true> : pmx_pairs_gather_codons_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((2 * n + 15) / 16)), dim3(256), 0, st, n, q_buf, q_bytes, r_buf, r_bytes,
                        qlen, rlen, tw, qsrc, rsrc, ok, sflag, qoff, roff, qout, q_cap, rout, r_cap, code);
+    return pmx_launched();
+}
+extern "C" long long pmx_swfsc_window_cols(long long rowmax_prefix, long long score, long long rows, long long open, long long extend, long long fs)
+{
+    return pmx_fswin_cols(rowmax_prefix, score, rows, open, extend, fs);
+}
+int pmx_launch_fsref_window(const pmx_pair_t *pairs, const pmx_record_t *rec, const uint8_t *strand, long long n, const uint8_t *q_buf,
+                            const int64_t *q_off, long long q_count, long long q_bytes, const int64_t *r_off, long long r_count, long long r_bytes,
+                            const PmxDevMatrix &m, int open, int ext, int fs, pmx_pair_t *npairs, int32_t *ashift, int32_t *nlen, hipStream_t st)
+{
+    if (m.pssm || m.msize > 256) return 1;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_fsref_window_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, pairs, rec, strand, n, q_buf,
+                       q_off, q_count, q_bytes, r_off, r_count, r_bytes, m.scores, m.mapper, m.msize, open, ext, fs, npairs, ashift, nlen);
+    return pmx_launched();
+}
+int pmx_launch_fsref_rebase(const pmx_record_t *first, const int32_t *ashift, long long n, pmx_record_t *rec, int32_t *beg, unsigned *violations,
+                            hipStream_t st)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(pmx_fsref_rebase_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, first, ashift, n, rec, beg, violations);
     return pmx_launched();
 }
 int pmx_launch_pairs_fixup_cigar(const uint8_t *ok, long long n, pmx_record_t *rec, int32_t *nops, int32_t *textlen, int32_t *beg, hipStream_t st)
