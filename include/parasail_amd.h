@@ -1301,6 +1301,79 @@ int64_t pmx_frameshift_ref_cigar_long_parts(void);
  * rows = end_query + 1; 2^63 - 1 where nothing is bounded (min(open, extend) = 0). */
 long long pmx_swfsc_window_cols(long long rowmax_prefix, long long score, long long rows, long long open, long long extend, long long fs);
 
+/* K-mer seeding (extension): the stage in front of the _ex entries -- which windows of a resident reference a read is worth aligning
+ * against.  An index of the k-mers of a DNA set, and an entry that turns the exact k-mer matches of queries into diagonal clusters and
+ * the clusters into window descriptors and strand bytes, on the device (kernels: parasail-rs_amd/csrc/pmx_seed.hip).
+ *
+ * Letters: A/a = 0, C/c = 1, G/g = 2, T/t/U/u = 3, every other byte is invalid (pmx_complement_table maps valid letters to valid ones
+ * and invalid bytes to invalid ones).  Sequence r has a k-mer at position j iff j + k <= len(r) and its k letters are valid; its key
+ * holds 2 bits per letter, the first letter most significant.  k is 8 .. 31.
+ *
+ * The index is every k-mer of R at stride 1 as (kmer, seq, pos), ascending in that lexicographic order: 16 bytes per entry on the
+ * device, a bucket table of at most 16 MiB, and while it is built twice that again.  pmx_seed_index_build synchronises (it allocates
+ * and reads the number of entries back); `stream` is where its kernels run.  R must outlive the index, which belongs to R's device.
+ * Refused (NULL, pmx_last_error()): a NULL set, k outside 8 .. 31, a set of another device than the current one, a set of more than
+ * 2^31 - 1 bytes or sequences.  Wrapped sets are read under the rule of the set batches: no byte outside `bytes`, whatever the offsets.
+ *
+ * Seeding.  The oriented query of (q, strand) is Q[q] as stored (strand 0) or w'[x] = comp[w[L - 1 - x]] (strand 1, the _ex entries'
+ * rule); all positions are relative to it.  opts->strand is a PMX_STRAND_* mode; PMX_STRAND_BOTH seeds both strands and lists them
+ * separately (a candidate is a locus on a strand, nothing is folded).  A match of (q, s, r) is a pair (i, j): the oriented query has a
+ * k-mer at i, R[r] has the same k-mer at j, and that k-mer has at most max_occ entries in the whole index (one with more is ignored
+ * entirely; 1 .. 65535).  Its diagonal is d = j - i.  The matches of (q, s, r) ordered by d fall into clusters, maximal runs whose
+ * consecutive diagonals differ by at most `band` (0 .. 2^20); matches of different r never share one.  A cluster of at least min_seeds
+ * matches is a candidate:
+ *   d_hit_pairs   {q, r, 0, -1, r_beg, r_len}: r_beg = max(0, diag_min - pad), r_end = min(len(r), diag_max + qlen + pad)
+ *   d_hit_strand  the strand byte
+ *   d_hit_seeds   {n_seeds, diag_min, diag_max, 0}, diagonals relative to the whole reference (optional)
+ * d_hit_pairs / d_hit_strand are valid d_pairs / d_strand arguments of pmx_align_pairs_ex_device with nothing in between, and
+ * diag - r_beg is the banded entries' diag for the gathered window.  Row q's candidates are ascending in (strand, r, diag_min).
+ * d_row_off receives nq + 1 offsets from 0 and is always written in full, uncapped; only positions below `capacity` are written, entries
+ * behind them are untouched; capacity == 0 counts only.  d_counts[0] = candidates, d_counts[1] = written.  A query longer than max_qlen
+ * has no candidates.
+ *
+ * Determinism.  The output is bit-identical from run to run and slice_rows never changes a byte: matches are sorted per (row, strand)
+ * by (r, d), clusters are runs of that order, and every output position is a scan over it plus the running total, which lives on the
+ * device (d_counts[0]) and advances in row order on the caller's stream.
+ *
+ * Slices.  The number of matches is known only on the device, so the entry works in slices of rows: a count pass (one index lookup
+ * per query position), a scan, and a cut -- the longest prefix of the slice whose matches fit the match buffer -- that THE ENTRY READS
+ * BACK: pmx_seed_pairs_device synchronises `stream` once per slice and is not asynchronous.  opts->slice_rows bounds a slice
+ * (0: as many rows as 256 MiB of position scratch hold, 16 bytes per (row, strand, position)).  Thread scratch: that, and the match
+ * buffer of 256 MiB at 24 bytes per match.  Refused before any GPU work when one row's worst case, max_qlen x strands x max_occ x 24
+ * bytes, does not fit the match buffer.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: a NULL set, index or opts; NULL d_row_off or d_counts with nq > 0; a
+ * set or index of another device than the current one; a negative q_first, nq, capacity, max_hits or slice_rows; rows beyond |Q|;
+ * max_qlen < 1; an unknown strand mode; min_seeds < 1; band or pad negative or above 2^20; max_occ outside 1 .. 65535; non-zero
+ * reserved; NULL d_hit_pairs or d_hit_strand with capacity > 0; the per-row budget above.  nq == 0 succeeds and writes zero counts and
+ * d_row_off[0] = 0 where those pointers are given.
+ *
+ * The host entry runs the device entry on a stream of its own with room for two candidates per row (max_hits when that is less)
+ * and, where more have to be stored, once more with buffers of the exact size.  It
+ * returns one callee-allocated block released with pmx_seed_hits_free: row_off holds n_rows + 1 uncapped offsets, pairs / strand / seeds
+ * n_hits entries, n_passing is the number of candidates.  max_hits > 0 stops storing after that many candidates, in row order, and
+ * goes on counting (n_hits = min(n_passing, max_hits)); 0: no limit.  max_qlen is the longest query of the rows. */
+typedef struct pmx_seed_index pmx_seed_index_t;
+pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t k, void *stream);
+void    pmx_seed_index_free(pmx_seed_index_t *index);
+int64_t pmx_seed_index_count(const pmx_seed_index_t *index);          /* entries; -1 for NULL */
+/* Test hook: entries [first, first + count) in index order (each output optional); asynchronous on `stream`. */
+int pmx_seed_index_entries_device(const pmx_seed_index_t *index, int64_t first, int64_t count,
+                                  uint64_t *d_kmer, int64_t *d_seq, int32_t *d_pos, void *stream);
+typedef struct pmx_seed_hit { int32_t n_seeds, diag_min, diag_max, reserved; } pmx_seed_hit_t;   /* 16 bytes */
+typedef struct pmx_seed_opts { int32_t strand, min_seeds, band, pad, max_occ, reserved; int64_t max_hits, slice_rows; } pmx_seed_opts_t;   /* 40 bytes */
+int pmx_seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq, int32_t max_qlen,
+                          const pmx_seed_opts_t *opts,
+                          pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds /* optional */, int64_t capacity,
+                          int64_t *d_row_off /* nq + 1 */, int64_t *d_counts /* [0] candidates, [1] written */, void *stream);
+typedef struct pmx_seed_hits { int64_t n_rows, n_hits, n_passing; int64_t *row_off; pmx_pair_t *pairs; uint8_t *strand; pmx_seed_hit_t *seeds; } pmx_seed_hits_t;
+int  pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq,
+                    const pmx_seed_opts_t *opts, pmx_seed_hits_t **result);
+void pmx_seed_hits_free(pmx_seed_hits_t *hits);
+/* Test hook: the calling thread's match buffer in bytes for the calls that follow (0: the default of 256 MiB); returns the bound it
+ * replaces.  A small bound makes the cut of a slice fall after a few rows. */
+int64_t pmx_seed_match_budget(int64_t bytes);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

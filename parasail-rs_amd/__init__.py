@@ -122,6 +122,21 @@ class pmx_topk_frame_hits_t(C.Structure):
     _fields_ = pmx_topk_hits_t._fields_ + [("frame", C.c_void_p)]
 
 
+class pmx_seed_hit_t(C.Structure):
+    _fields_ = [("n_seeds", C.c_int32), ("diag_min", C.c_int32), ("diag_max", C.c_int32), ("reserved", C.c_int32)]
+
+
+class pmx_seed_opts_t(C.Structure):
+    _fields_ = [("strand", C.c_int32), ("min_seeds", C.c_int32), ("band", C.c_int32), ("pad", C.c_int32), ("max_occ", C.c_int32),
+                ("reserved", C.c_int32), ("max_hits", C.c_int64), ("slice_rows", C.c_int64)]
+
+
+class pmx_seed_hits_t(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_hits", C.c_int64), ("n_passing", C.c_int64), ("row_off", C.c_void_p),
+                ("pairs", C.c_void_p), ("strand", C.c_void_p), ("seeds", C.c_void_p)]
+
+
+SEED_HIT_DTYPE = np.dtype([("n_seeds", "<i4"), ("diag_min", "<i4"), ("diag_max", "<i4"), ("reserved", "<i4")])
 TOPK_MAX = 1024
 INT32_MIN = -(1 << 31)
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
@@ -279,6 +294,16 @@ _sig("pmx_search_topk_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c
 _sig("pmx_search_topk", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
      C.POINTER(pmx_topk_opts_t), C.POINTER(C.POINTER(pmx_topk_hits_t)))
 _sig("pmx_topk_hits_free", None, C.POINTER(pmx_topk_hits_t))
+_sig("pmx_seed_index_build", C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)
+_sig("pmx_seed_index_free", None, C.c_void_p)
+_sig("pmx_seed_index_count", C.c_int64, C.c_void_p)
+_sig("pmx_seed_index_entries_device", C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_pairs_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(pmx_seed_opts_t),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_pairs", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(pmx_seed_opts_t),
+     C.POINTER(C.POINTER(pmx_seed_hits_t)))
+_sig("pmx_seed_hits_free", None, C.POINTER(pmx_seed_hits_t))
+_sig("pmx_seed_match_budget", C.c_int64, C.c_int64)
 _sig("pmx_topk_records_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_align_pairs_both", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1792,6 +1817,106 @@ class SeqSet:
             self.close()
         except Exception:
             pass
+
+
+class SeedIndex:
+    """The k-mer index of a DNA set (pmx_seed_index_t): every k-mer of R as (kmer, seq, pos), sorted, on R's device.  R is held:
+    it outlives the index.  len(): the entries.  Released by close() or on deletion."""
+
+    def __init__(self, inner, R, k):
+        self.inner, self.R, self.k = inner, R, int(k)
+
+    @classmethod
+    def build(cls, R, k, stream=0):
+        inner = lib.pmx_seed_index_build(R._handle(), int(k), stream)
+        if not inner:
+            raise BatchError(lib.pmx_last_error().decode())
+        return cls(inner, R, k)
+
+    def _handle(self):
+        if not self.inner:
+            raise BatchError("the seed index is closed")
+        return self.inner
+
+    def __len__(self):
+        return int(lib.pmx_seed_index_count(self._handle()))
+
+    def close(self):
+        if self.inner:
+            lib.pmx_seed_index_free(self.inner)
+            self.inner = None
+            self.R = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SeedHits:
+    """Result of seed_pairs, CSR by query row: row_off (int64, n_rows + 1, never capped by max_hits), n_passing (the candidates)
+    and, per stored candidate, pairs (PAIR_DTYPE: query, reference and reference window, fit for Aligner.align_pairs), strand
+    (uint8) and seeds (SEED_HIT_DTYPE: matches and the diagonals' range).  A row's candidates are in (strand, reference,
+    diag_min) order; row(i) slices out those that were stored."""
+
+    def __init__(self, r):
+        h, n = int(r.n_hits), int(r.n_rows)
+        self.n_rows, self.n_hits, self.n_passing = n, h, int(r.n_passing)
+
+        def take(ptr, count, dtype):
+            if not ptr or not count:
+                return np.zeros(count, dtype=dtype)
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype).copy()
+        self.row_off = take(r.row_off, n + 1, np.int64)
+        self.pairs = take(r.pairs, h, PAIR_DTYPE)
+        self.strand = take(r.strand, h, np.uint8)
+        self.seeds = take(r.seeds, h, SEED_HIT_DTYPE)
+
+    def __len__(self):
+        return self.n_hits
+
+    def row(self, i):
+        """(pairs, strand, seeds) of local row i (0 = first_row)."""
+        a, b = min(int(self.row_off[i]), self.n_hits), min(int(self.row_off[i + 1]), self.n_hits)
+        return self.pairs[a:b], self.strand[a:b], self.seeds[a:b]
+
+
+def _seed_opts(strand, min_seeds, band, pad, max_occ, max_hits=0, slice_rows=0):
+    return pmx_seed_opts_t(_strand_mode(strand), int(min_seeds), int(band), int(pad), int(max_occ), 0, int(max_hits), int(slice_rows))
+
+
+def seed_pairs(Q, index, strand="both", min_seeds=2, band=8, pad=16, max_occ=64, first_row=0, rows=None, max_hits=0, slice_rows=0):
+    """Candidate windows of the queries Q[first_row : first_row + rows] in the indexed reference: exact k-mer matches, clustered
+    by diagonal (consecutive diagonals at most `band` apart), clusters of at least min_seeds matches widened by `pad`.
+    hits.pairs and hits.strand go unchanged into Aligner.align_pairs(Q, R, pairs, strand=, cigar=True)."""
+    if rows is None:
+        rows = max(0, len(Q) - int(first_row))
+    opts = _seed_opts(strand, min_seeds, band, pad, max_occ, max_hits, slice_rows)
+    res = C.POINTER(pmx_seed_hits_t)()
+    if lib.pmx_seed_pairs(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), C.byref(res)):
+        raise BatchError(lib.pmx_last_error().decode())
+    try:
+        return SeedHits(res.contents)
+    finally:
+        lib.pmx_seed_hits_free(res)
+
+
+def seed_pairs_device(Q, index, q_first, nq, max_qlen, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts,
+                      strand="both", min_seeds=2, band=8, pad=16, max_occ=64, slice_rows=0, stream=0):
+    """Device-pointer entry of seed_pairs: the candidates go to d_hit_pairs / d_hit_strand / d_hit_seeds (optional), `capacity`
+    entries each, d_row_off gets nq + 1 offsets and d_counts [candidates, written].  Synchronises `stream` once per slice."""
+    opts = _seed_opts(strand, min_seeds, band, pad, max_occ, 0, slice_rows)
+    rc = lib.pmx_seed_pairs_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), d_hit_pairs,
+                                   d_hit_strand, d_hit_seeds, int(capacity), d_row_off, d_counts, stream)
+    if rc:
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def seed_index_entries_device(index, first, count, d_kmer, d_seq, d_pos, stream=0):
+    """Entries [first, first + count) of the index in its order: key (uint64), sequence (int64), position (int32) (test hook)."""
+    if lib.pmx_seed_index_entries_device(index._handle(), int(first), int(count), d_kmer, d_seq, d_pos, stream):
+        raise BatchError(lib.pmx_last_error().decode())
 
 
 def as_pairs(pairs):

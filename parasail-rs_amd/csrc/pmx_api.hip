@@ -1380,7 +1380,9 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_PTHIT = 28,                                                                   // per-query top-K, host entry: a slice's hit columns (HitCols) and row arrays, counts, first bad pair
        SCR_SWFS = 29,                                                                    // frameshift entries: the strips' boundary columns (pmx_swfs.hip)
        SCR_FSWIN = 30,                                                                   // windowed frameshift traceback: a chunk's first-pass records and strands, narrowed descriptors, shifts, lengths, the violation count
-       SCR_SLOTS = 31 };
+       SCR_SEED = 31,                                                                    // k-mer seeding: a slice's position slots, match buffers, cluster flags, cut, rocPRIM scratch (pmx_seed.hip)
+       SCR_SEEDHIT = 32,                                                                 // k-mer seeding, host entry: counts, row offsets, the candidates' columns
+       SCR_SLOTS = 33 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -5866,4 +5868,289 @@ extern "C" int pmx_search_topk_frameshift_ref(const pmx_config_t *cfg, const pmx
                                           pmx_topk_strand_hits_t **result)
 {
     return search_topk_host(cfg, Q, R, q_first, nq, opts, strand_mode, true, (pmx_topk_hits_t **)result, TR_CODONS_REF, 0, code, frameshift);
+}
+
+// ---- k-mer seeding (semantics: include/parasail_amd.h; kernels: pmx_seed.hip) -------------------------------------------
+struct pmx_seed_index {
+    const pmx_seqset *R = nullptr;
+    int k = 0, shift = 0, dev = -1;        // bucket of a key: key >> shift
+    int64_t n = 0, nb = 0;                 // entries; buckets (the table holds nb + 1 numbers)
+    uint64_t *keys = nullptr, *vals = nullptr; uint32_t *bucket = nullptr;
+};
+static const int PMX_SEED_BUCKET_BITS = 22;            // 2^22 + 1 numbers of 4 bytes: 16 MiB, resident in the Infinity Cache
+static const int32_t PMX_SEED_BAND_MAX = 1 << 20;
+static thread_local int64_t g_seed_budget = 0;         // the test hook's match buffer; 0: PMX_PAIRS_CHUNK_BYTES
+static int64_t seed_match_budget() { return g_seed_budget > 0 ? g_seed_budget : (int64_t)PMX_PAIRS_CHUNK_BYTES; }
+extern "C" int64_t pmx_seed_match_budget(int64_t bytes)
+{
+    const int64_t was = seed_match_budget();
+    g_seed_budget = bytes > 0 ? std::min<int64_t>(bytes, (int64_t)1 << 34) : 0;
+    return was;
+}
+
+extern "C" void pmx_seed_index_free(pmx_seed_index_t *ix)
+{
+    if (!ix) return;
+    if (ix->keys || ix->vals || ix->bucket) {
+        int dev = -1;
+        const bool move = hipGetDevice(&dev) == hipSuccess && dev != ix->dev;
+        if (move) (void)hipSetDevice(ix->dev);
+        (void)hipFree(ix->keys); (void)hipFree(ix->vals); (void)hipFree(ix->bucket);
+        if (move) (void)hipSetDevice(dev);
+    }
+    delete ix;
+}
+
+extern "C" int64_t pmx_seed_index_count(const pmx_seed_index_t *ix) { return ix ? ix->n : -1; }
+
+extern "C" pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t k, void *stream)
+{
+    if (!R) { set_err("null sequence set"); return nullptr; }
+    if (k < 8 || k > 31) { set_err("k %d is outside 8 .. 31", (int)k); return nullptr; }
+    if (R->bytes > INT32_MAX || R->count > INT32_MAX) {
+        set_err("a seed index holds a set of at most 2^31 - 1 bytes and sequences (this one: %lld bytes, %lld sequences): index parts of it",
+                (long long)R->bytes, (long long)R->count);
+        return nullptr;
+    }
+    pmx_seed_index *ix = new (std::nothrow) pmx_seed_index();
+    if (!ix) { set_err("out of memory"); return nullptr; }
+    ix->R = R; ix->k = k; ix->dev = R->dev;
+    const int bbits = std::min(2 * k, PMX_SEED_BUCKET_BITS);
+    ix->shift = 2 * k - bbits; ix->nb = (int64_t)1 << bbits;
+    if (R->bytes == 0 || R->count == 0) return ix;               // nothing to index: no entry, no device memory, no GPU work
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); delete ix; return nullptr; }
+    if (R->dev != dev) { set_err("a sequence set of device %d cannot be used on the current device %d", R->dev, dev); delete ix; return nullptr; }
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t nbytes = (size_t)R->bytes, temp_bytes = pmx_seed_index_sort_bytes(R->bytes, k);
+    uint64_t *kin = nullptr, *vin = nullptr; void *temp = nullptr; unsigned long long *d_n = nullptr, h_n = 0;
+    hipError_t e = hipMalloc((void **)&ix->keys, nbytes * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ix->vals, nbytes * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ix->bucket, sizeof(uint32_t) * (size_t)(ix->nb + 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&kin, nbytes * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&vin, nbytes * 8);
+    if (e == hipSuccess) e = hipMalloc(&temp, temp_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_n, sizeof h_n);
+    if (e == hipSuccess) e = hipMemsetAsync(d_n, 0, sizeof h_n, st);
+    int rc = 0;
+    if (e == hipSuccess) rc = pmx_launch_seed_index(R->d_buf, R->d_off, R->count, R->bytes, k, kin, vin, ix->keys, ix->vals, temp, temp_bytes, d_n, st);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(&h_n, d_n, sizeof h_n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && !rc) { ix->n = (int64_t)h_n; rc = pmx_launch_seed_buckets(ix->keys, ix->n, ix->shift, ix->nb, ix->bucket, st); }
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+    (void)hipFree(kin); (void)hipFree(vin); (void)hipFree(temp); (void)hipFree(d_n);
+    if (e != hipSuccess || rc) {
+        set_err("seed index build failed: %s", e != hipSuccess ? hipGetErrorString(e) : "kernel launch");
+        pmx_seed_index_free(ix); return nullptr;
+    }
+    return ix;
+}
+
+extern "C" int pmx_seed_index_entries_device(const pmx_seed_index_t *ix, int64_t first, int64_t count, uint64_t *d_kmer, int64_t *d_seq,
+                                             int32_t *d_pos, void *stream)
+{
+    if (!ix) { set_err("null seed index"); return -1; }
+    if (first < 0 || count < 0) { set_err("negative first or count"); return -1; }
+    if (first > ix->n || count > ix->n - first) {
+        set_err("entries %lld .. %lld are beyond the %lld entries of the index", (long long)first, (long long)first + (long long)count - 1, (long long)ix->n);
+        return -1;
+    }
+    if (count == 0) return 0;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (ix->dev != dev) { set_err("a seed index of device %d cannot be used on the current device %d", ix->dev, dev); return -1; }
+    const int rc = pmx_launch_seed_entries(ix->keys, ix->vals, first, count, d_kmer, d_seq, d_pos, (hipStream_t)stream);
+    if (rc) set_err("seed index entries failed (%d)", rc);
+    return rc;
+}
+
+// What both seeding entries refuse about their arguments; lens_known false: the host entry before it has looked at the lengths
+// (max_qlen and the budget rule are checked in its second call).
+static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t *o,
+                      int64_t capacity, bool lens_known = true)
+{
+    if (!lens_known) max_qlen = 1;
+    if (!Q) { set_err("null sequence set"); return -1; }
+    if (!ix) { set_err("null seed index"); return -1; }
+    if (!o) { set_err("null opts"); return -1; }
+    if (q_first < 0 || nq < 0) { set_err("negative q_first or nq"); return -1; }
+    if (capacity < 0) { set_err("negative capacity"); return -1; }
+    if (o->max_hits < 0) { set_err("max_hits must not be negative"); return -1; }
+    if (o->slice_rows < 0) { set_err("slice_rows must not be negative"); return -1; }
+    if (q_first > Q->count || nq > Q->count - q_first) {
+        set_err("rows %lld .. %lld are beyond the %lld sequences of Q", (long long)q_first, (long long)q_first + (long long)nq - 1, (long long)Q->count);
+        return -1;
+    }
+    if (max_qlen < 1) { set_err("max_qlen must be positive"); return -1; }
+    if (o->strand < PMX_STRAND_FORWARD || o->strand > PMX_STRAND_BOTH) { set_err("strand mode %d is outside 0 .. 2", (int)o->strand); return -1; }
+    if (o->min_seeds < 1) { set_err("min_seeds %d is below 1", (int)o->min_seeds); return -1; }
+    if (o->band < 0 || o->band > PMX_SEED_BAND_MAX) { set_err("band %d is outside 0 .. 2^20", (int)o->band); return -1; }
+    if (o->pad < 0 || o->pad > PMX_SEED_BAND_MAX) { set_err("pad %d is outside 0 .. 2^20", (int)o->pad); return -1; }
+    if (o->max_occ < 1 || o->max_occ > 65535) { set_err("max_occ %d is outside 1 .. 65535", (int)o->max_occ); return -1; }
+    if (o->reserved != 0) { set_err("reserved must be 0"); return -1; }
+    const int64_t strands = o->strand == PMX_STRAND_BOTH ? 2 : 1;
+    const double worst = (double)max_qlen * (double)strands * (double)o->max_occ * (double)PMX_SEED_MATCH_BYTES;
+    if (worst > (double)seed_match_budget()) {
+        set_err("one row's worst case of %d positions x %d strand(s) x max_occ %d x %d bytes per match does not fit the match buffer of %lld bytes: "
+                "lower max_occ or split the queries", (int)max_qlen, (int)strands, (int)o->max_occ, PMX_SEED_MATCH_BYTES, (long long)seed_match_budget());
+        return -1;
+    }
+    return 0;
+}
+
+static int seed_device_check(const pmx_seqset *Q, const pmx_seed_index *ix)
+{
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (Q->dev != dev) { set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev, dev); return -1; }
+    if (ix->dev != dev) { set_err("a seed index of device %d cannot be used on the current device %d", ix->dev, dev); return -1; }
+    return 0;
+}
+
+// nq > 0 rows behind the checks.  Synchronises `st` once per slice: the cut is read back.
+static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t *o,
+                    pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off,
+                    int64_t *d_counts, hipStream_t st)
+{
+    HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), st));
+    if (ix->n == 0) { HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st)); return 0; }
+    HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), st));
+    const int strands = o->strand == PMX_STRAND_BOTH ? 2 : 1, strand0 = o->strand == PMX_STRAND_REVERSE ? 1 : 0;
+    const int64_t per_row = (int64_t)strands * max_qlen;
+    int64_t slice = std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / (per_row * PMX_SEED_POS_BYTES));
+    if (o->slice_rows > 0) slice = std::min(slice, o->slice_rows);
+    slice = std::min(slice, nq);
+    // the match buffer: the budget, or the slice's worst case when that is smaller (positions fit 32 bits)
+    const double worst = (double)slice * (double)per_row * (double)o->max_occ;
+    const int64_t cap_m = (int64_t)std::min<double>(std::min<double>((double)(seed_match_budget() / PMX_SEED_MATCH_BYTES), worst), 2147483646.0);
+    const int64_t positions = slice * per_row, slots = slice * strands;
+    const size_t temp_bytes = pmx_seed_temp_bytes(positions, cap_m, slots);
+    uint32_t *lo = nullptr, *cnt = nullptr, *head = nullptr, *flag = nullptr; int64_t *moff = nullptr, *cut = nullptr;
+    uint64_t *ka = nullptr, *kb = nullptr; unsigned char *temp = nullptr;
+    if (scratch_carve(SCR_SEED, [&](Carver &c) {
+            lo = c.take<uint32_t>((size_t)positions); cnt = c.take<uint32_t>((size_t)positions + 1); moff = c.take<int64_t>((size_t)positions + 1);
+            ka = c.take<uint64_t>((size_t)cap_m); kb = c.take<uint64_t>((size_t)cap_m);
+            head = c.take<uint32_t>((size_t)cap_m); flag = c.take<uint32_t>((size_t)cap_m + 1);
+            cut = c.take<int64_t>(2); temp = c.take<unsigned char>(temp_bytes);
+        })) return -1;
+    int key_bits = 33;                                   // the diagonal and the bits of a reference index
+    while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < ix->R->count) ++key_bits;
+    for (int64_t row = 0; row < nq;) {
+        const int64_t rows = std::min(slice, nq - row);
+        int rc = pmx_launch_seed_count(Q->d_buf, Q->d_off, Q->bytes, q_first + row, rows, strands, strand0, max_qlen, ix->k, ix->keys, ix->bucket,
+                                       ix->shift, o->max_occ, lo, cnt, moff, cap_m, cut, temp, temp_bytes, st);
+        if (rc) { set_err("seed count pass failed (%d)", rc); return rc; }
+        int64_t h[2] = {0, 0};
+        HIP_OR_RET(hipMemcpyAsync(h, cut, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipStreamSynchronize(st));
+        if (h[0] < 1 || h[0] > rows || h[1] < 0 || h[1] > cap_m) { set_err("seed cut of rows %lld .. is inconsistent", (long long)(q_first + row)); return -1; }
+        rc = pmx_launch_seed_cluster(q_first + row, h[0], strands, strand0, max_qlen, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb, head, flag,
+                                     o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand, d_hit_seeds,
+                                     d_row_off + row, d_counts, temp, temp_bytes, st);
+        if (rc) { set_err("seed cluster pass failed (%d)", rc); return rc; }
+        row += h[0];
+    }
+    return 0;
+}
+
+extern "C" int pmx_seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
+                                     const pmx_seed_opts_t *opts, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds,
+                                     int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
+{
+    if (seed_check(Q, ix, q_first, nq, max_qlen, opts, capacity)) return -1;
+    if (capacity > 0 && (!d_hit_pairs || !d_hit_strand)) { set_err("null hit pairs or strand bytes with capacity > 0"); return -1; }
+    if (nq == 0) {
+        if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
+        if (d_row_off) HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), (hipStream_t)stream));
+        return 0;
+    }
+    if (!d_row_off) { set_err("null row offsets"); return -1; }
+    if (!d_counts) { set_err("null counts"); return -1; }
+    if (seed_device_check(Q, ix)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return seed_run(Q, ix, q_first, nq, max_qlen, opts, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts, (hipStream_t)stream);
+}
+
+extern "C" void pmx_seed_hits_free(pmx_seed_hits_t *hits) { free(hits); }
+
+extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
+                              pmx_seed_hits_t **result)
+{
+    if (!result) { set_err("null result pointer"); return -1; }
+    *result = nullptr;
+    if (seed_check(Q, ix, q_first, nq, 0, opts, 0, false)) return -1;
+    // the result: one block -- header, row offsets, descriptors, seed records, strand bytes
+    auto block = [&](int64_t stored, int64_t passing) -> pmx_seed_hits_t * {
+        Carver c; c.align = 16;
+        c.take<pmx_seed_hits_t>(1); c.take<int64_t>((size_t)nq + 1); c.take<pmx_pair_t>((size_t)stored); c.take<pmx_seed_hit_t>((size_t)stored);
+        c.take<uint8_t>((size_t)stored);
+        unsigned char *p = (unsigned char *)calloc(1, c.used ? c.used : 16);
+        if (!p) { set_err("out of memory"); return nullptr; }
+        Carver d; d.align = 16; d.base = p;
+        pmx_seed_hits_t *r = d.take<pmx_seed_hits_t>(1);
+        r->n_rows = nq; r->n_hits = stored; r->n_passing = passing;
+        r->row_off = d.take<int64_t>((size_t)nq + 1); r->pairs = d.take<pmx_pair_t>((size_t)stored);
+        r->seeds = d.take<pmx_seed_hit_t>((size_t)stored); r->strand = d.take<uint8_t>((size_t)stored);
+        return r;
+    };
+    if (nq == 0) { *result = block(0, 0); return *result ? 0 : -1; }
+    if (seed_device_check(Q, ix)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    StreamGuard guard(st);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    // the longest query of the rows: from the host's offsets, else (a wrapped set) the longest sequence of Q, found on the device
+    int32_t mq = 0;
+    if (!Q->h_off.empty()) {
+        int64_t m = 0;
+        for (int64_t r = q_first; r < q_first + nq; ++r) m = std::max(m, Q->h_off[(size_t)r + 1] - Q->h_off[(size_t)r]);
+        if (m > INT32_MAX) { set_err("a query of %lld letters is beyond 2^31 - 1", (long long)m); return -1; }
+        mq = (int32_t)m;
+    } else {
+        int32_t *d_m = nullptr, h_m[2] = {0, 0};
+        if (scratch_reserve(2 * sizeof(int32_t), (void **)&d_m, SCR_SEEDHIT)) return -1;
+        HIP_OR_RET(hipMemsetAsync(d_m, 0, sizeof h_m, st));
+        const int rc = pmx_launch_pairs_maxlen(nullptr, Q->count, Q->d_off, Q->count, Q->bytes, Q->d_off, Q->count, Q->bytes, d_m, st);
+        if (rc) { set_err("length scan failed (%d)", rc); return rc; }
+        HIP_OR_RET(hipMemcpyAsync(h_m, d_m, sizeof h_m, hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipStreamSynchronize(st));
+        mq = h_m[0];
+    }
+    if (mq < 1) mq = 1;
+    if (seed_check(Q, ix, q_first, nq, mq, opts, 0)) return -1;
+    int64_t *d_off = nullptr, *d_cnt = nullptr; pmx_pair_t *d_pairs = nullptr; pmx_seed_hit_t *d_seeds = nullptr; uint8_t *d_strand = nullptr;
+    auto carve = [&](int64_t stored) {
+        return scratch_carve(SCR_SEEDHIT, [&](Carver &c) {
+            d_cnt = c.take<int64_t>(2); d_off = c.take<int64_t>((size_t)nq + 1);
+            d_pairs = c.take<pmx_pair_t>((size_t)stored); d_seeds = c.take<pmx_seed_hit_t>((size_t)stored); d_strand = c.take<uint8_t>((size_t)stored);
+        });
+    };
+    // the number of candidates is known only behind a run: room for two per row first (max_hits when that is less), and where more
+    // have to be stored a second run with room for exactly those -- the first run's counts are the same either way
+    int64_t h[2] = {0, 0};
+    int64_t room = 2 * nq + 16;
+    if (opts->max_hits > 0) room = std::min(room, opts->max_hits);
+    if (carve(room)) return -1;
+    int rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, room, d_off, d_cnt, st);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    HIP_OR_RET(hipMemcpyAsync(h, d_cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    const int64_t passing = h[0], stored = opts->max_hits > 0 ? std::min(passing, opts->max_hits) : passing;
+    if (stored > room) {
+        if (carve(stored)) return -1;
+        rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, stored, d_off, d_cnt, st);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_OR_RET(hipStreamSynchronize(st));
+    }
+    pmx_seed_hits_t *r = block(stored, passing);
+    if (!r) return -1;
+    hipError_t e = hipMemcpy(r->row_off, d_off, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && stored > 0) e = hipMemcpy(r->pairs, d_pairs, sizeof(pmx_pair_t) * (size_t)stored, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && stored > 0) e = hipMemcpy(r->seeds, d_seeds, sizeof(pmx_seed_hit_t) * (size_t)stored, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && stored > 0) e = hipMemcpy(r->strand, d_strand, (size_t)stored, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_err("copying the candidates back failed: %s", hipGetErrorString(e)); free(r); return -1; }
+    *result = r;
+    return 0;
 }

@@ -412,6 +412,31 @@ int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, 
                          const pmx_stats_t *st_stats, const int32_t *st_held, const int64_t *st_passing, const int64_t *row_off, long long capacity,
                          pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *row_passing,
                          int64_t *counts, hipStream_t stream, uint8_t *hit_strand = nullptr, int marked = 0 /* as in append_hits */);
+// K-mer seeding (pmx_seed.hip; semantics: include/parasail_amd.h).  index: one entry per byte of the set's buffer into
+// keys_in / vals_in, sorted into keys_out / vals_out (the k-mers in front, *n_valid of them; val = seq << 32 | pos); buckets: the table
+// of nb + 1 first-entry numbers on the keys' top bits (key >> shift).  count: lookups of the slice's rows, the scan of their matches
+// into moff and cut[0 .. 1] = the rows that fit cap_matches / their matches.  cluster: those rows' matches emitted, sorted per (row,
+// strand) and turned into candidates behind counts[0], row offsets and counts.
+#define PMX_SEED_MATCH_BYTES 24        // per match: two sort buffers of 8-byte keys, the head index, the candidate flag / position
+#define PMX_SEED_POS_BYTES   16        // per (row, strand, position): first entry, occurrences, match offset
+size_t pmx_seed_index_sort_bytes(long long bytes, int k);
+int pmx_launch_seed_index(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k,
+                          uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out, void *temp, size_t temp_bytes,
+                          unsigned long long *n_valid, hipStream_t stream);
+int pmx_launch_seed_buckets(const uint64_t *keys, long long n, int shift, long long nb, uint32_t *bucket, hipStream_t stream);
+int pmx_launch_seed_entries(const uint64_t *keys, const uint64_t *vals, long long first, long long count, uint64_t *kmer, int64_t *seq,
+                            int32_t *pos, hipStream_t stream);
+size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots);
+int pmx_launch_seed_count(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int strands, int strand0,
+                          int max_qlen, int k, const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
+                          uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
+                          hipStream_t stream);
+int pmx_launch_seed_cluster(long long row0, long long rows, int strands, int strand0, int max_qlen, long long m, int key_bits,
+                            const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
+                            uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
+                            const int64_t *qoff, const int64_t *roff, long long capacity,
+                            pmx_pair_t *hit_pairs, uint8_t *hit_strand, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
+                            void *temp, size_t temp_bytes, hipStream_t stream);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);

@@ -1,0 +1,373 @@
+// pmx_seed.hip -- k-mer seeding (semantics: include/parasail_amd.h): the k-mer index of a DNA set and the candidate
+// windows of queries against it -- exact k-mer matches, clustered by diagonal, as descriptors for pmx_align_pairs_ex_device.
+//
+// Index.  Every byte position of the reference buffer gets one entry: the 2k-bit key of the k-mer that starts there, or the key
+// 1 << 2k where no k-mer starts (a sequence end inside, an invalid letter, no sequence).  rocPRIM's stable radix sort on bits
+// [0, 2k + 1) leaves the k-mers in (kmer, seq, pos) order in front and the empty positions behind them, so nothing is compacted.  A
+// bucket table on the top min(2k, 22) bits (16 MiB at most: it stays in the Infinity Cache) turns a lookup into one table read and a
+// binary search inside one bucket.
+//
+// Seeding, per slice of rows.  A position slot is (row, strand, i): count looks the slot's k-mer up (first entry, occurrences; 0 above
+// max_occ), a scan gives every slot its place in the match buffer, emit writes a match as the key (r << 32) | biased diagonal, a
+// segmented radix sort orders each (row, strand) segment by (r, d).  Clusters are then runs of the sorted keys: a head flag per match, a
+// max-scan that carries each head's index to its run, a candidate flag at each run's last match, a scan of those flags for the output
+// positions.  Every position comes from a scan over sorted data; the only atomic in this file counts the index's entries.
+#include <algorithm>
+#include <cstring>
+#include <cstdlib>
+#include "pmx_common.h"
+#include <rocprim/rocprim.hpp>
+
+// letter -> 2-bit code, A/a 0, C/c 1, G/g 2, T/t/U/u 3; -1: not a nucleotide
+__device__ __forceinline__ int pmx_seed_code(uint32_t b)
+{
+    const uint32_t u = b & 0xDFu;
+    const bool ok = u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'U';
+    const int c = (int)((u >> 1) & 3u);
+    return ok ? (c ^ (c >> 1)) : -1;
+}
+
+// ---- index build ---------------------------------------------------------------------------------------------------------------------
+#define PMX_SEED_TILE 16        // positions per thread of the extraction: one rolling key over 16 + k - 1 bytes
+
+// keys[p] / vals[p] for every p < bytes; *n_valid += the k-mers found.  Offsets are read at indices 0 .. count only and a byte only
+// below `bytes`, whatever a wrapped set's offsets hold.
+__global__ void __launch_bounds__(256) pmx_seed_extract_kernel(const uint8_t *__restrict__ buf, const int64_t *__restrict__ off, long long count,
+                                                               long long bytes, int k, uint64_t *__restrict__ keys, uint64_t *__restrict__ vals,
+                                                               unsigned long long *n_valid)
+{
+    const long long p0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * PMX_SEED_TILE;
+    unsigned found = 0;
+    if (p0 < bytes) {
+        const uint64_t invalid = (uint64_t)1 << (2 * k), mask = invalid - 1;
+        // region r: -1 before the first sequence, count behind the last one, else sequence r = [off[r], off[r + 1])
+        long long lo = 0, hi = count + 1;
+        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (off[mid] <= p0) lo = mid + 1; else hi = mid; }
+        long long r = lo - 1;
+        long long e = r < count ? off[r + 1] : INT64_MAX;
+        long long b = r >= 0 ? off[r] : 0;
+        const long long pend = min(p0 + PMX_SEED_TILE, bytes), xend = min(pend + k - 1, bytes);
+        uint64_t key = 0; int run = 0;
+        for (long long x = p0; x < xend; ++x) {
+            while (x >= e && r < count) { ++r; b = e; e = r < count ? off[r + 1] : INT64_MAX; run = 0; }
+            const bool inside = r >= 0 && r < count && b >= 0 && b <= x && x < e && e <= bytes;
+            const int c = inside ? pmx_seed_code(buf[x]) : -1;
+            if (c < 0) { run = 0; key = 0; } else { key = (key << 2) | (uint64_t)c; ++run; }
+            const long long s = x - k + 1;
+            if (s >= p0) {
+                const bool have = run >= k && s >= b;
+                keys[s] = have ? (key & mask) : invalid;
+                vals[s] = have ? ((uint64_t)r << 32) | (uint64_t)(uint32_t)(s - b) : (uint64_t)s;
+                found += have ? 1u : 0u;
+            }
+        }
+        for (long long s = max(p0, xend - k + 1); s < pend; ++s) { keys[s] = invalid; vals[s] = (uint64_t)s; }
+    }
+    // one add per block: the sum does not depend on the order of arrival
+    __shared__ unsigned total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    if (found) atomicAdd(&total, found);
+    __syncthreads();
+    if (threadIdx.x == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+}
+
+// bucket[b] = the first entry whose key's top bits are >= b, for b in 0 .. nb (bucket[nb] = n); n > 0
+__global__ void __launch_bounds__(256) pmx_seed_buckets_kernel(const uint64_t *__restrict__ keys, long long n, int shift, long long nb,
+                                                               uint32_t *__restrict__ bucket)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long b = (long long)(keys[i] >> shift), prev = i ? (long long)(keys[i - 1] >> shift) : -1;
+    for (long long x = prev + 1; x <= b; ++x) bucket[x] = (uint32_t)i;
+    if (i == n - 1) for (long long x = b + 1; x <= nb; ++x) bucket[x] = (uint32_t)n;
+}
+
+__global__ void __launch_bounds__(256) pmx_seed_entries_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ vals,
+                                                               long long first, long long count, uint64_t *kmer, int64_t *seq, int32_t *pos)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t v = vals[first + i];
+    if (kmer) kmer[i] = keys[first + i];
+    if (seq) seq[i] = (int64_t)(v >> 32);
+    if (pos) pos[i] = (int32_t)(uint32_t)v;
+}
+
+size_t pmx_seed_index_sort_bytes(long long bytes, int k)
+{
+    size_t temp = 0;
+    uint64_t *nul = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, temp, nul, nul, nul, nul, (size_t)bytes, 0, 2 * k + 1, nullptr);
+    return temp + 256;
+}
+
+// keys_out / vals_out: the sorted index; keys_in / vals_in: `bytes` entries of scratch; n_valid: one zeroed counter on the device
+int pmx_launch_seed_index(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k,
+                          uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out, void *temp, size_t temp_bytes,
+                          unsigned long long *n_valid, hipStream_t stream)
+{
+    if (bytes <= 0) return 0;
+    const long long threads = (bytes + PMX_SEED_TILE - 1) / PMX_SEED_TILE;
+    hipLaunchKernelGGL(pmx_seed_extract_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, buf, off, count, bytes, k,
+                       keys_in, vals_in, n_valid);
+    int rc = pmx_launched();
+    if (rc) return rc;
+    const hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)bytes, 0, 2 * k + 1, stream);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+int pmx_launch_seed_buckets(const uint64_t *keys, long long n, int shift, long long nb, uint32_t *bucket, hipStream_t stream)
+{
+    if (n <= 0) return hipMemsetAsync(bucket, 0, sizeof(uint32_t) * (size_t)(nb + 1), stream) == hipSuccess ? 0 : -1;
+    hipLaunchKernelGGL(pmx_seed_buckets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, keys, n, shift, nb, bucket);
+    return pmx_launched();
+}
+
+int pmx_launch_seed_entries(const uint64_t *keys, const uint64_t *vals, long long first, long long count, uint64_t *kmer, int64_t *seq,
+                            int32_t *pos, hipStream_t stream)
+{
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL(pmx_seed_entries_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, keys, vals, first, count, kmer, seq, pos);
+    return pmx_launched();
+}
+
+// ---- seeding -------------------------------------------------------------------------------------------------------------------------
+// Position slot p = (row_local * strands + s) * max_qlen + i.  lo[p]: the first index entry of the slot's k-mer, cnt[p]: its
+// occurrences, 0 where the oriented query has no k-mer at i, the k-mer is absent or it occurs more than max_occ times.  cnt has one
+// entry more than there are slots (0: the scan's total).
+__global__ void __launch_bounds__(256) pmx_seed_count_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
+                                                             long long row0, long long slots, int strands, int strand0, int max_qlen, int k,
+                                                             const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
+                                                             int max_occ, uint32_t *__restrict__ lo_out, uint32_t *__restrict__ cnt_out)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = slots * max_qlen;
+    if (p > total) return;
+    if (p == total) { cnt_out[p] = 0; return; }
+    const long long t = p / max_qlen;
+    const int i = (int)(p - t * max_qlen);
+    const long long row = row0 + t / strands;
+    const int strand = strands == 2 ? (int)(t & 1) : strand0;
+    const long long b = qoff[row], e = qoff[row + 1];
+    uint32_t lo = 0, cnt = 0;
+    if (b >= 0 && e >= b && e <= q_bytes && e - b <= max_qlen && i + k <= e - b) {
+        const uint8_t *w = qbuf + b;
+        const int L = (int)(e - b);
+        uint64_t key = 0; bool ok = true;
+        for (int x = 0; x < k; ++x) {
+            const int c = strand ? pmx_seed_code(w[L - 1 - (i + x)]) : pmx_seed_code(w[i + x]);
+            ok = ok && c >= 0;
+            key = (key << 2) | (uint64_t)((strand ? 3 - c : c) & 3);
+        }
+        if (ok) {
+            const uint32_t s = bucket[key >> shift], t1 = bucket[(key >> shift) + 1];
+            uint32_t a = s, z = t1;
+            while (a < z) { const uint32_t mid = a + ((z - a) >> 1); if (keys[mid] < key) a = mid + 1; else z = mid; }
+            if (a < t1 && keys[a] == key) {
+                lo = a;
+                const uint32_t lim = (uint32_t)min((unsigned long long)t1, (unsigned long long)a + (unsigned long long)max_occ);
+                if (!(lim < t1 && keys[lim] == key)) {                 // (else: more than max_occ occurrences, ignored entirely)
+                    uint32_t u = a + 1; z = lim;
+                    while (u < z) { const uint32_t mid = u + ((z - u) >> 1); if (keys[mid] == key) u = mid + 1; else z = mid; }
+                    cnt = u - a;
+                }
+            }
+        }
+    }
+    lo_out[p] = lo; cnt_out[p] = cnt;
+}
+
+// out[0] = the largest m <= rows whose matches moff[m * stride] fit `cap`; out[1] = that number of matches
+__global__ void pmx_seed_cut_kernel(const int64_t *__restrict__ moff, long long rows, long long stride, long long cap, int64_t *out)
+{
+    long long a = 0, z = rows;                  // moff[a * stride] <= cap holds for a == 0
+    while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= cap) a = mid; else z = mid - 1; }
+    out[0] = a; out[1] = moff[a * stride];
+}
+
+__global__ void __launch_bounds__(256) pmx_seed_emit_kernel(long long total, int max_qlen, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ cnt,
+                                                            const int64_t *__restrict__ moff, const uint64_t *__restrict__ vals,
+                                                            uint64_t *__restrict__ mkeys)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const uint32_t n = cnt[p];
+    if (!n) return;
+    const int i = (int)(p % max_qlen);
+    const uint32_t first = lo[p];
+    uint64_t *out = mkeys + moff[p];
+    for (uint32_t x = 0; x < n; ++x) {
+        const uint64_t v = vals[first + x];
+        const int32_t d = (int32_t)(uint32_t)v - i;
+        out[x] = (v & 0xFFFFFFFF00000000ull) | (uint64_t)((uint32_t)d ^ 0x80000000u);
+    }
+}
+
+// segment t of the sort: the matches of (row, strand) slot t
+struct PmxSeedSegOff {
+    const int64_t *moff; long long stride;
+    __device__ __host__ unsigned operator()(unsigned t) const { return (unsigned)moff[(long long)t * stride]; }
+};
+
+__device__ __forceinline__ int32_t pmx_seed_diag(uint64_t key) { return (int32_t)((uint32_t)key ^ 0x80000000u); }
+
+// flag[x] = 1 where a (row, strand) segment starts (flag zeroed before)
+__global__ void __launch_bounds__(256) pmx_seed_segstart_kernel(const int64_t *__restrict__ moff, long long slots, long long stride, uint32_t *flag)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= slots) return;
+    const int64_t a = moff[t * stride], z = moff[(t + 1) * stride];
+    if (z > a) flag[a] = 1;
+}
+
+// head[x] = x where match x opens a cluster (a new segment, another reference, a diagonal more than `band` past the previous one), else 0
+__global__ void __launch_bounds__(256) pmx_seed_heads_kernel(const uint64_t *__restrict__ mkeys, long long m, int band, const uint32_t *__restrict__ segstart,
+                                                             uint32_t *__restrict__ head)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= m) return;
+    bool h = x == 0 || segstart[x] != 0;
+    if (!h) {
+        const uint64_t a = mkeys[x - 1], b = mkeys[x];
+        h = (a >> 32) != (b >> 32) || (long long)pmx_seed_diag(b) - (long long)pmx_seed_diag(a) > band;
+    }
+    head[x] = h ? (uint32_t)x : 0u;
+}
+
+// head: after the max-scan, the index of the head of x's cluster.  flag[x] = 1 where x closes a cluster of at least min_seeds matches.
+__global__ void __launch_bounds__(256) pmx_seed_flags_kernel(const uint32_t *__restrict__ head, long long m, int min_seeds, uint32_t *__restrict__ flag)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= m) return;
+    const bool tail = x == m - 1 || head[x + 1] == (uint32_t)(x + 1);
+    flag[x] = tail && x - (long long)head[x] + 1 >= min_seeds ? 1u : 0u;
+}
+
+// candidate tails -> outputs at base + pos[x], below `capacity`; base = counts[0], the candidates of the slices before
+__global__ void __launch_bounds__(256) pmx_seed_hits_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ pos,
+                                                            long long m, const int64_t *__restrict__ moff, long long slots, long long stride,
+                                                            long long row0, int strands, int strand0, int pad,
+                                                            const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
+                                                            const int64_t *__restrict__ counts, long long capacity,
+                                                            pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_strand, pmx_seed_hit_t *__restrict__ hit_seeds)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= m || pos[x + 1] == pos[x]) return;
+    const long long at = counts[0] + (long long)pos[x];
+    if (at >= capacity) return;
+    long long a = 0, z = slots - 1;             // the slot of x: the last t with moff[t * stride] <= x (empty segments share a start)
+    while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= x) a = mid; else z = mid - 1; }
+    const long long row = row0 + a / strands;
+    const int strand = strands == 2 ? (int)(a & 1) : strand0;
+    const uint32_t h = head[x];
+    const uint64_t kh = mkeys[h], kt = mkeys[x];
+    const long long r = (long long)(kt >> 32), dmin = pmx_seed_diag(kh), dmax = pmx_seed_diag(kt);
+    const long long qlen = qoff[row + 1] - qoff[row], rlen = roff[r + 1] - roff[r];
+    const long long beg = max(0ll, dmin - pad), end = min(rlen, dmax + qlen + pad);
+    pmx_pair_t pr; pr.q = row; pr.r = r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)beg; pr.r_len = (int32_t)(end - beg);
+    hit_pairs[at] = pr;
+    hit_strand[at] = (uint8_t)strand;
+    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = (int32_t)(x - h + 1); s.diag_min = (int32_t)dmin; s.diag_max = (int32_t)dmax; s.reserved = 0; hit_seeds[at] = s; }
+}
+
+// row_off[x + 1] = base + the candidates of the slice's rows 0 .. x (pos == NULL: the slice has no match)
+__global__ void __launch_bounds__(256) pmx_seed_rowoff_kernel(const uint32_t *__restrict__ pos, const int64_t *__restrict__ moff, long long rows, long long stride,
+                                                              const int64_t *__restrict__ counts, int64_t *__restrict__ row_off)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= rows) return;
+    row_off[x + 1] = counts[0] + (pos ? (int64_t)pos[moff[(x + 1) * stride]] : 0);
+}
+
+// behind the slice: counts[0] += its candidates, counts[1] = what is written so far
+__global__ void pmx_seed_advance_kernel(const uint32_t *pos, long long m, long long capacity, int64_t *counts)
+{
+    const int64_t total = counts[0] + (pos ? (int64_t)pos[m] : 0);
+    counts[0] = total; counts[1] = total < capacity ? total : capacity;
+}
+
+struct PmxMaxU32 { __device__ __host__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
+struct PmxWidenU32 { __device__ __host__ int64_t operator()(uint32_t v) const { return (int64_t)v; } };
+
+// rocPRIM scratch of one slice: the scan over `positions` + 1 slot counts, the sort of `matches` keys in `slots` segments, the two scans
+// over the matches -- used one after the other, so the largest counts
+size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots)
+{
+    size_t a = 0, b = 0, c = 0, d = 0;
+    auto in = rocprim::make_transform_iterator((const uint32_t *)nullptr, PmxWidenU32());
+    (void)rocprim::exclusive_scan(nullptr, a, in, (int64_t *)nullptr, (int64_t)0, (size_t)(positions + 1), rocprim::plus<int64_t>(), nullptr);
+    auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{nullptr, 1});
+    (void)rocprim::segmented_radix_sort_keys(nullptr, b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (unsigned)matches, (unsigned)slots, seg, seg, 0, 64,
+                                             nullptr);
+    (void)rocprim::inclusive_scan(nullptr, c, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)matches, PmxMaxU32(), nullptr);
+    (void)rocprim::exclusive_scan(nullptr, d, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)(matches + 1), rocprim::plus<uint32_t>(), nullptr);
+    return std::max(std::max(a, b), std::max(c, d)) + 256;
+}
+
+// The slice's count pass, scan and cut: rows row0 .. row0 + rows of Q; cut (device, 2 entries) receives how many of them fit
+// `cap_matches` and their matches.
+int pmx_launch_seed_count(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int strands, int strand0,
+                          int max_qlen, int k, const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
+                          uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
+                          hipStream_t stream)
+{
+    const long long slots = rows * strands, total = slots * max_qlen;
+    hipLaunchKernelGGL(pmx_seed_count_kernel, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, stream, qbuf, qoff, q_bytes, row0, slots, strands,
+                       strand0, max_qlen, k, keys, bucket, shift, max_occ, lo, cnt);
+    int rc = pmx_launched();
+    if (rc) return rc;
+    auto in = rocprim::make_transform_iterator((const uint32_t *)cnt, PmxWidenU32());
+    const hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, in, moff, (int64_t)0, (size_t)(total + 1), rocprim::plus<int64_t>(), stream);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(pmx_seed_cut_kernel, dim3(1), dim3(1), 0, stream, moff, rows, (long long)strands * max_qlen, cap_matches, cut);
+    return pmx_launched();
+}
+
+// The slice's `rows` rows (what the cut kept) with their m matches: emit, sort, clusters, outputs behind counts[0]; row_off points at
+// the entry of the slice's first row.
+int pmx_launch_seed_cluster(long long row0, long long rows, int strands, int strand0, int max_qlen, long long m, int key_bits,
+                            const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
+                            uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
+                            const int64_t *qoff, const int64_t *roff, long long capacity,
+                            pmx_pair_t *hit_pairs, uint8_t *hit_strand, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
+                            void *temp, size_t temp_bytes, hipStream_t stream)
+{
+    const long long slots = rows * strands, stride = max_qlen, total = slots * stride;
+    const unsigned rb = (unsigned)((rows + 255) / 256);
+    int rc = 0;
+    if (m > 0) {
+        const unsigned mb = (unsigned)((m + 255) / 256);
+        hipLaunchKernelGGL(pmx_seed_emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, max_qlen, lo, cnt, moff, vals, mkeys_a);
+        if ((rc = pmx_launched())) return rc;
+        auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{moff, stride});
+        size_t tb = temp_bytes;
+        hipError_t e = rocprim::segmented_radix_sort_keys(temp, tb, (const uint64_t *)mkeys_a, mkeys_b, (unsigned)m, (unsigned)slots, seg, seg + 1, 0, key_bits,
+                                                          stream);
+        if (e != hipSuccess) return -(int)e;
+        if (hipMemsetAsync(flag, 0, sizeof(uint32_t) * (size_t)(m + 1), stream) != hipSuccess) return -1;
+        hipLaunchKernelGGL(pmx_seed_segstart_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, moff, slots, stride, flag);
+        if ((rc = pmx_launched())) return rc;
+        hipLaunchKernelGGL(pmx_seed_heads_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)mkeys_b, m, band, (const uint32_t *)flag, head);
+        if ((rc = pmx_launched())) return rc;
+        tb = temp_bytes;
+        e = rocprim::inclusive_scan(temp, tb, head, head, (size_t)m, PmxMaxU32(), stream);
+        if (e != hipSuccess) return -(int)e;
+        hipLaunchKernelGGL(pmx_seed_flags_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t *)head, m, min_seeds, flag);
+        if ((rc = pmx_launched())) return rc;
+        tb = temp_bytes;
+        e = rocprim::exclusive_scan(temp, tb, flag, flag, 0u, (size_t)(m + 1), rocprim::plus<uint32_t>(), stream);
+        if (e != hipSuccess) return -(int)e;
+        if (capacity > 0) {
+            hipLaunchKernelGGL(pmx_seed_hits_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag, m,
+                               moff, slots, stride, row0, strands, strand0, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_strand,
+                               hit_seeds);
+            if ((rc = pmx_launched())) return rc;
+        }
+    }
+    hipLaunchKernelGGL(pmx_seed_rowoff_kernel, dim3(rb), dim3(256), 0, stream, m > 0 ? (const uint32_t *)flag : nullptr, moff, rows, (long long)strands * stride,
+                       (const int64_t *)counts, row_off);
+    if ((rc = pmx_launched())) return rc;
+    hipLaunchKernelGGL(pmx_seed_advance_kernel, dim3(1), dim3(1), 0, stream, m > 0 ? (const uint32_t *)flag : nullptr, m, capacity, counts);
+    return pmx_launched();
+}
