@@ -2633,6 +2633,51 @@ static int publish_text(TextBuf &text, char **cigar_buf)
     return 0;
 }
 
+// The text stage of a host entry whose device run renders CIGAR text: a device buffer sized by the entry's estimate, one more run at the
+// exact size where the text did not fit, then the text into a block of the caller's.
+struct HostText {
+    DevBuf<char> text; DevBuf<int64_t> off; int64_t capacity = 0;
+    // buffers for n texts of `estimate` bytes together; 0, or -2 with the error set
+    int alloc(int64_t n, int64_t estimate)
+    {
+        capacity = estimate;
+        if (off.try_alloc((size_t)n + 1) || text.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+        return 0;
+    }
+    // fn(d_text, capacity, d_off) is the device run (its error is the stage's); the n + 1 offsets come back into host_off behind it -- on
+    // *stream, which is then synchronised, or with a blocking copy (stream NULL) -- and a text of more than `capacity` bytes runs again at
+    // its size.  Without alloc -- an entry whose call wants no text -- fn runs once without buffers.
+    template <typename Fn>
+    int run(int64_t n, int64_t *host_off, const hipStream_t *stream, Fn fn)
+    {
+        for (int pass = 0; pass < 2; ++pass) {
+            const int rc = fn(text.p, capacity, off.p);
+            if (rc || !off.p) return rc;
+            if (stream) {
+                HIP_OR_RET(hipMemcpyAsync(host_off, off.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, *stream));
+                HIP_OR_RET(hipStreamSynchronize(*stream));
+            } else HIP_OR_RET(hipMemcpy(host_off, off.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost));
+            if (host_off[n] <= capacity) break;
+            capacity = host_off[n];                           // rare: the text did not fit the estimate -- again with the exact size
+            (void)hipFree(text.p); text.p = nullptr;
+            if (text.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
+        }
+        return 0;
+    }
+    hipError_t copy_to(char *dst, int64_t bytes) const { return bytes ? hipMemcpy(dst, text.p, (size_t)bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+    // the finished text of `bytes` bytes as a block of the caller's (released with pmx_free)
+    int to_block(int64_t bytes, char **cigar_buf) const
+    {
+        TextBuf t;
+        char *dst = t.grow((size_t)bytes);
+        if (!dst) { set_err("out of memory"); return -1; }
+        const hipError_t e = copy_to(dst, bytes);
+        if (e != hipSuccess) { free(t.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
+        t.len = (size_t)bytes;
+        return publish_text(t, cigar_buf);
+    }
+};
+
 // CIGAR for a batch.  Fast path: pmx_trace16 (4-bit trace in HBM, on-device walk); otherwise the general
 // kernel with byte trace tables and pmx_walk_kernel.  Only the run-length ops come back to the host, which
 // renders the text.  One chunk = one set of launches; chunks bound the trace scratch.
@@ -2898,31 +2943,14 @@ static int traced_host_batch(const pmx_config_t *cfg, const parasail_profile_t *
     if (rc) return rc;
     const int64_t qbytes = profile ? (int64_t)n * profile->s1Len : qoff[n];
     // text capacity: half a byte per symbol + 16 per pair covers related pairs many times over; a batch that needs more runs again
-    int64_t capacity = want_cigar ? ((qbytes + roff[n]) / 2 + 16 * n + 256) : 0;
-    DevBuf<int64_t> dtoff; DevBuf<pmx_stats_t> dst; DevBuf<char> dtext;
-    if ((want_stats && dst.try_alloc(n)) || (want_cigar && (dtoff.try_alloc(n + 1) || dtext.try_alloc((size_t)capacity + 1)))) { set_err("out of device memory"); return -2; }
-    for (int pass = 0; pass < 2; ++pass) {
-        rc = run(s, dst.p, dtext.p, capacity, dtoff.p);
-        if (rc) return rc;
-        if (!want_cigar) break;
-        HIP_OR_RET(hipMemcpy(cigar_off, dtoff.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
-        if (cigar_off[n] <= capacity) break;
-        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
-        (void)hipFree(dtext.p); dtext.p = nullptr;
-        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    }
+    DevBuf<pmx_stats_t> dst; HostText text;
+    if (want_stats && dst.try_alloc(n)) { set_err("out of device memory"); return -2; }
+    if (want_cigar && text.alloc(n, (qbytes + roff[n]) / 2 + 16 * n + 256)) return -2;
+    rc = text.run(n, cigar_off, nullptr, [&](char *d_text, int64_t capacity, int64_t *d_text_off) { return run(s, dst.p, d_text, capacity, d_text_off); });
+    if (rc) return rc;
     if ((rc = s.records(out)) != 0) return rc;
     if (want_stats) HIP_OR_RET(hipMemcpy(stats_out, dst.p, sizeof(pmx_stats_t) * n, hipMemcpyDeviceToHost));
-    if (!want_cigar) return 0;
-    TextBuf text;
-    char *dst_text = text.grow((size_t)cigar_off[n]);
-    if (!dst_text) { set_err("out of memory"); return -1; }
-    if (cigar_off[n]) {
-        const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
-    }
-    text.len = (size_t)cigar_off[n];
-    return publish_text(text, cigar_buf);
+    return want_cigar ? text.to_block(cigar_off[n], cigar_buf) : 0;
 }
 
 // ---- banded batches with traceback (extension) ---------------------------------------------------------------------------
@@ -3268,23 +3296,17 @@ extern "C" int pmx_search_profile(const pmx_config_t *cfg, const parasail_profil
     if (rc) { (void)hipStreamSynchronize(s_comp); return rc; }
     const int64_t h = sh.h;
     // text capacity as in traced_host_batch: half a byte per symbol + 16 per hit; a search that needs more runs its second pass again
-    int64_t capacity = want_cigar ? (((int64_t)h * profile->s1Len + sh.bytes) / 2 + 16 * h + 256) : 0;
-    DevBuf<pmx_hit_t> dhits; DevBuf<pmx_record_t> drecs; DevBuf<pmx_stats_t> dst; DevBuf<char> dtext; DevBuf<int64_t> dtoff;
-    if (dhits.try_alloc(h) || dtoff.try_alloc(h + 1) || (second && drecs.try_alloc(h)) || (want_stats && dst.try_alloc(h)) ||
-        (want_cigar && dtext.try_alloc((size_t)capacity + 1))) { set_err("out of device memory"); return -2; }
+    DevBuf<pmx_hit_t> dhits; DevBuf<pmx_record_t> drecs; DevBuf<pmx_stats_t> dst; HostText text;
+    if (dhits.try_alloc(h) || (second && drecs.try_alloc(h)) || (want_stats && dst.try_alloc(h))) { set_err("out of device memory"); return -2; }
+    if (want_cigar && text.alloc(h, ((int64_t)h * profile->s1Len + sh.bytes) / 2 + 16 * h + 256)) return -2;
     std::vector<int64_t> toff((size_t)h + 1, 0);
-    for (int pass = 0; pass < 2; ++pass) {
-        rc = search_second(cfg, profile, dq, n, dr, dro, mr, opts, dfirst, sh, dhits.p, drecs.p, dst.p, dtext.p, capacity,
-                           want_cigar ? dtoff.p : nullptr, s_comp);
-        if (rc) { (void)hipStreamSynchronize(s_comp); return rc; }
+    rc = text.run(h, toff.data(), nullptr, [&](char *d_text, int64_t capacity, int64_t *d_text_off) -> int {
+        const int rc2 = search_second(cfg, profile, dq, n, dr, dro, mr, opts, dfirst, sh, dhits.p, drecs.p, dst.p, d_text, capacity, d_text_off, s_comp);
+        if (rc2) { (void)hipStreamSynchronize(s_comp); return rc2; }
         HIP_OR_RET(hipStreamSynchronize(s_comp));
-        if (!want_cigar) break;
-        HIP_OR_RET(hipMemcpy(toff.data(), dtoff.p, sizeof(int64_t) * (size_t)(h + 1), hipMemcpyDeviceToHost));
-        if (toff[h] <= capacity) break;
-        capacity = toff[h];
-        (void)hipFree(dtext.p); dtext.p = nullptr;
-        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    }
+        return 0;
+    });
+    if (rc) return rc;
     pmx_search_result_t *r = nullptr;
     if (publish(h, sh.passing, toff[h], &r)) return -1;
     hipError_t e = hipSuccess;
@@ -3292,7 +3314,7 @@ extern "C" int pmx_search_profile(const pmx_config_t *cfg, const parasail_profil
         e = hipMemcpy(r->hits, dhits.p, sizeof(pmx_hit_t) * (size_t)h, hipMemcpyDeviceToHost);
         if (e == hipSuccess && second) e = hipMemcpy(r->recs, drecs.p, sizeof(pmx_record_t) * (size_t)h, hipMemcpyDeviceToHost);
         if (e == hipSuccess && want_stats) e = hipMemcpy(r->stats, dst.p, sizeof(pmx_stats_t) * (size_t)h, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && want_cigar && toff[h]) e = hipMemcpy(r->cigar, dtext.p, (size_t)toff[h], hipMemcpyDeviceToHost);
+        if (e == hipSuccess && want_cigar) e = text.copy_to(r->cigar, toff[h]);
     }
     if (e != hipSuccess) { free(r); set_err("%s", hipGetErrorString(e)); return -(int)e; }
     memcpy(r->cigar_off, toff.data(), sizeof(int64_t) * (size_t)(h + 1));
@@ -3763,6 +3785,7 @@ struct SlotPlan {
     int first = 0, per = 1;                 // the slots' flag bytes first .. first + per - 1 for every pair ...
     const uint8_t *d_byte = nullptr;        // ... or (listed pairs, per 1) a byte per pair
     PmxCodeTable code; int frameshift = 0;
+    const PmxFsSide &side() const { return pmx_fs_side(ref); }              // CODONS: the sweep of the plan's side
     SlotPlan() {}
     explicit SlotPlan(const uint8_t *d_strand) : kind(d_strand ? BYTES : PLAIN), d_byte(d_strand) {}       // the _ex entries: BYTES where there are strand bytes
     void strands(int strand_mode) { kind = STRANDS; first = strand_mode == PMX_STRAND_REVERSE ? 1 : 0; per = strand_mode == PMX_STRAND_BOTH ? 2 : 1; }
@@ -4158,9 +4181,8 @@ static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint
                     : "the frameshift entries have no CIGAR output (PMX_WANT_CIGAR): there is no traceback with frameshift operators");
         return -1;
     }
-    const int max_msize = ref ? pmx_swfsc_max_msize() : pmx_swfs_max_msize();
-    if (cfg->matrix->size > max_msize) {
-        set_err("the frameshift kernel keeps the matrix in LDS: %d symbols exceed %d", cfg->matrix->size, max_msize); return -1;
+    if (cfg->matrix->size > pmx_fs_side(ref).max_msize) {
+        set_err("the frameshift kernel keeps the matrix in LDS: %d symbols exceed %d", cfg->matrix->size, pmx_fs_side(ref).max_msize); return -1;
     }
     fr->strands(strand_mode);                                     // (first and per of the mode; forward: strand 0, one slot)
     fr->kind = SlotPlan::CODONS; fr->ref = ref; fr->frameshift = frameshift;
@@ -4172,19 +4194,12 @@ static int frameshift_check(const pmx_config_t *cfg, int strand_mode, const uint
 // rows of pmx_swfsc; the stream on the columns has no cap of its own.
 static int frameshift_rows_check(int32_t max_qlen, bool ref = false)
 {
-    if (ref) {
-        if (max_qlen > PMX_FRAMESHIFT_REF_MAX_QUERY) {
-            set_err("a query of %d letters exceeds PMX_FRAMESHIFT_REF_MAX_QUERY = %d letters", (int)max_qlen, PMX_FRAMESHIFT_REF_MAX_QUERY);
-            return -1;
-        }
-        return 0;
-    }
-    if (max_qlen > PMX_FRAMESHIFT_MAX_WINDOW - 2) {
-        set_err("a codon stream of %d letters exceeds the %d of the longest window, PMX_FRAMESHIFT_MAX_WINDOW = %d nucleotides",
-                (int)max_qlen, PMX_FRAMESHIFT_MAX_WINDOW - 2, PMX_FRAMESHIFT_MAX_WINDOW);
-        return -1;
-    }
-    return 0;
+    const int max_rows = pmx_fs_side(ref).max_rows;
+    if (max_qlen <= max_rows) return 0;
+    if (ref) set_err("a query of %d letters exceeds PMX_FRAMESHIFT_REF_MAX_QUERY = %d letters", (int)max_qlen, max_rows);
+    else set_err("a codon stream of %d letters exceeds the %d of the longest window, PMX_FRAMESHIFT_MAX_WINDOW = %d nucleotides",
+                 (int)max_qlen, max_rows, PMX_FRAMESHIFT_MAX_WINDOW);
+    return -1;
 }
 // The search and top-K entries: the rows' bound of the plan's streams, nothing for the other kinds.
 static int codons_rows_check(const SlotPlan &plan, int32_t max_qlen)
@@ -4202,14 +4217,14 @@ static int swfs_chunk(const pmx_config_t *cfg, const SlotPlan &fr, int64_t slots
     if (get_devmat(cfg->matrix, &dm)) return -1;
     PmxBatch pb = {b.q, b.qoff, b.r, b.roff, slots, max_qlen, max_rlen, 0, nullptr, nullptr, nullptr, 0, 0};
     void *bnd = nullptr; long long bnd_slots = 0;
-    if (max_qlen > (fr.ref ? pmx_swfsc_strip_rows() : pmx_swfs_strip_rows())) {
-        const size_t per_slot = fr.ref ? (size_t)pmx_swfsc_bound_bytes_per_slot(max_rlen) : pmx_swfs_bound_bytes_per_slot(max_rlen);
+    const PmxFsSide &side = fr.side();
+    if (max_qlen > side.strip_rows) {
+        const size_t per_slot = (size_t)side.bound_bytes_per_slot(max_rlen);
         bnd_slots = std::max<long long>(4, (long long)(PMX_PAIRS_CHUNK_BYTES / (double)per_slot) / 4 * 4);
         bnd_slots = std::min<long long>(bnd_slots, (slots + 3) / 4 * 4);
         if (scratch_reserve(per_slot * (size_t)bnd_slots, &bnd, SCR_SWFS)) return -1;
     }
-    const int rc = fr.ref ? pmx_launch_swfsc(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, bnd_slots, d_out, st, &g_last_kernel)
-                          : pmx_launch_swfs(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, bnd_slots, d_out, st, &g_last_kernel);
+    const int rc = side.launch(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, bnd_slots, nullptr, d_out, st, &g_last_kernel);
     if (rc) { set_err(rc < 0 ? "frameshift kernel launch failed: %s" : "the frameshift kernel does not take this batch%s", rc < 0 ? hipGetErrorString((hipError_t)(-rc)) : ""); return -1; }
     return 0;
 }
@@ -4271,7 +4286,7 @@ static double frameshift_trace_bound()
 // The trace bytes of one slot: the query side's sweep stores by column, the reference side's by step (pmx_swfs.hip, pmx_swfsc.hip).
 static size_t frameshift_trace_bytes_per_slot(bool ref, int32_t max_qlen, int32_t max_rlen)
 {
-    return ref ? (size_t)pmx_swfsc_trace_bytes_per_slot(max_qlen, max_rlen) : pmx_swfs_trace_bytes_per_slot(max_qlen, max_rlen);
+    return (size_t)pmx_fs_side(ref).trace_bytes_per_slot(max_qlen, max_rlen);
 }
 static int frameshift_trace_bound_check(size_t bytes_per_slot, int32_t max_qlen, int32_t max_rlen)
 {
@@ -4290,8 +4305,7 @@ static int frameshift_trace_bound_check(size_t bytes_per_slot, int32_t max_qlen,
 // `st`: a part's scratch is free when the next part begins.  The text continues behind the parts and chunks before it
 // (d_text_off[c0 + p0], left by the part before on the same stream), so neither chunk_pairs nor the bound changes a byte.
 // Scratch: the trace in SCR_TRACE, the op slots in SCR_OPS and the walk's counts in SCR_CIG, which no other road of this call uses.
-// fr.ref: the side comes with the plan -- pmx_swfsc's trace form, strip test and boundary bytes, and the walk's <true>
-// form; the bound, the parts, the fold, the scan, the render and the text rebase are the same code.
+// fr.side(): the side comes with the plan -- its trace form, strip test and boundary bytes, and the walk's form; the bound, the parts, the fold, the scan, the render and the text rebase are the same code.
 static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs,
                                   int32_t max_qlen, int32_t max_rlen, pmx_record_t *d_out, uint8_t *d_strand_out, pmx_stats_t *d_stats,
                                   int32_t *d_beg, char *d_text, int64_t capacity, int64_t *d_text_off,
@@ -4301,10 +4315,10 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
     const int per = fr.per;
-    const bool ref = fr.ref;
-    const size_t tps = frameshift_trace_bytes_per_slot(ref, max_qlen, max_rlen);
-    const bool strips = max_qlen > (ref ? pmx_swfsc_strip_rows() : pmx_swfs_strip_rows());
-    const size_t bps = ref ? (size_t)pmx_swfsc_bound_bytes_per_slot(max_rlen) : pmx_swfs_bound_bytes_per_slot(max_rlen);
+    const PmxFsSide &side = fr.side();
+    const size_t tps = (size_t)side.trace_bytes_per_slot(max_qlen, max_rlen);
+    const bool strips = max_qlen > side.strip_rows;
+    const size_t bps = (size_t)side.bound_bytes_per_slot(max_rlen);
     int64_t part_slots = (int64_t)(frameshift_trace_bound() / (double)tps) / 4 * 4;           // (at least four: the caller has checked)
     part_slots = std::min<int64_t>(part_slots, ((int64_t)per * chunk + 3) / 4 * 4);
     const int64_t part = part_slots / per;
@@ -4326,15 +4340,14 @@ static int pairs_run_codons_cigar(const pmx_config_t *cfg, const pmx_seqset *Q, 
             for (int64_t p0 = 0; p0 < cn; p0 += part) {
                 const int64_t pn = std::min<int64_t>(part, cn - p0), s0 = per * p0, g0 = c0 + p0;
                 const PmxBatch pb = {b.q, b.qoff + s0, b.r, b.roff + s0, per * pn, max_qlen, max_rlen, 0, nullptr, nullptr, nullptr, 0, 0};
-                int rc = ref ? pmx_launch_swfsc_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, trace, srec + s0, st, &g_last_kernel)
-                             : pmx_launch_swfs_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, trace, srec + s0, st, &g_last_kernel);
+                int rc = side.launch_trace(pb, dm.d, cfg->open, cfg->extend, fr.frameshift, bnd, 0, trace, srec + s0, st, &g_last_kernel);
                 if (rc) { set_err(rc < 0 ? "frameshift trace kernel launch failed: %s" : "the frameshift trace kernel does not take this batch%s", rc < 0 ? hipGetErrorString((hipError_t)(-rc)) : ""); return -1; }
                 uint8_t *won = d_strand_out ? d_strand_out + g0 : nullptr;
                 rc = pmx_launch_pairs_fold(srec + s0, nullptr, b.ok + s0, b.sflag + s0, pn, per, 0, d_out + g0, nullptr, won, nullptr, st);
                 if (rc) { set_err("strand fold launch failed (%d)", rc); return rc; }
                 rc = pmx_launch_walkfs(dm.d, pn, per, per == 2 ? won : nullptr, b.q, b.qoff + s0, b.r, b.roff + s0, max_rlen, d_out + g0,
                                        (const uint8_t *)trace, (long long)tps, t.ops, t.nops, t.textlen, pair_qoff, pair_roff,
-                                       d_beg ? d_beg + 2 * g0 : nullptr, d_stats ? d_stats + g0 : nullptr, st, ref);
+                                       d_beg ? d_beg + 2 * g0 : nullptr, d_stats ? d_stats + g0 : nullptr, st, side.ref);
                 if (rc) { set_err("frameshift walk launch failed (%d)", rc); return rc < 0 ? rc : -1; }
                 rc = t.render(pair_qoff, pair_roff, 0, pn, d_text, capacity, d_text_off + g0, st, g0 > 0 || continues ? local_off : nullptr);
                 if (rc) return rc;
@@ -4718,33 +4731,48 @@ static int pairs_copy_back(int64_t n, const pmx_record_t *drec, const pmx_stats_
     return 0;
 }
 
-// The host entries over listed pairs.  ex: pmx_align_pairs_ex -- strand bytes (may be NULL), and with PMX_WANT_CIGAR the begins (may be
-// NULL) and the text, which follows traced_host_batch: a device buffer of half a byte per symbol + 16 per pair, one more run at the exact
-// size when the text did not fit, a block for the caller released with pmx_free.
-// both: pmx_align_pairs_both -- PMX_STRAND_BOTH, the winners' strand bytes into strand_out (n more bytes of scratch, copied back
-// behind the records).
-static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *pairs, const uint8_t *strand,
-                      pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts, bool ex,
-                      bool both = false, uint8_t *strand_out = nullptr)
+// Listed pairs over a set with host offsets, the descriptors below `end` good: the first whose query window has fewer than three
+// nucleotides -- no codon stream --, refused with its number; 0 when there is none.  ref (the _frameshift_ref entries): S is the
+// reference set and the window the reference's.
+static int short_window_check(const pmx_seqset *S, const pmx_pair_t *pairs, int64_t end, bool ref = false)
 {
-    SlotPlan plan;                                        // both: the two strands; else PLAIN until the strand bytes are on the device
-    if (both) plan.strands(PMX_STRAND_BOTH);
-    if (listed_entry_check(cfg, Q, R, n, pairs, out, opts, both ? &plan : nullptr, strand_out)) return -1;
-    if (both && (pairs_both_want_check(cfg) || strand_mode_check(cfg, PMX_STRAND_BOTH, &plan))) return -1;
-    if (ex && pairs_ex_outputs_check(cfg, beg, cigar_buf, 0, cigar_off)) return -1;
-    const bool cigar = ex && (cfg->want & PMX_WANT_CIGAR) != 0;
-    if (cigar) { *cigar_buf = nullptr; cigar_off[0] = 0; }
-    if (n == 0) return 0;
-    if (strand)
+    for (int64_t k = 0; k < end; ++k) {
+        const pmx_pair_t &p = pairs[k];
+        const int64_t idx = ref ? p.r : p.q, beg = ref ? p.r_beg : p.q_beg, len = ref ? p.r_len : p.q_len;
+        const int64_t W = len < 0 ? S->h_off[(size_t)idx + 1] - S->h_off[(size_t)idx] - beg : len;
+        if (W < 3) { set_err("pair %lld: %s: a window of %lld nucleotides has no codon", (long long)k, ref ? "reference" : "query", (long long)W); return -1; }
+    }
+    return 0;
+}
+
+// The one host road over listed pairs, behind the entries' own argument checks: the validation of the bytes per pair (strands; FRAMES:
+// frames), the descriptors against host offsets -- the scan cut into slices on helper threads for large batches, merged in pair order, so
+// the lowest bad pair is the one named --, the maxima in letters, the upload of 32 (+ 1) bytes per pair, the maxima of wrapped sets from
+// the device -- then run(cfg, d_pairs, max_qlen, max_rlen, d_rec, d_stats, d_byte_out, st), then the winners' bytes (byte_out, may be
+// NULL) and the records back.  plan.d_byte: the uploaded bytes, where there are any.  scan_flags: the records' flags are scanned for
+// bad pairs even with host offsets -- a pair without a frame or a codon is found on the device only.  lens_check(max_qlen, max_rlen,
+// known): what the entry refuses about the maxima, asked before any GPU work (known: the sets have host offsets) and again for wrapped
+// sets.  hint: the run's configuration carries the sort hint of the host lengths.  *symbols (may be NULL): the letters of all windows,
+// for wrapped sets n times the maxima -- what a text estimate starts from.
+template <typename LensCheck, typename Run>
+static int listed_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *pairs,
+                             const uint8_t *byte_in, SlotPlan &plan, pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *byte_out,
+                             const pmx_pairs_opts_t *opts, bool ex, bool hint, bool scan_flags, int64_t *symbols, LensCheck lens_check, Run run)
+{
+    const bool codons = plan.kind == SlotPlan::CODONS, frames = plan.kind == SlotPlan::FRAMES;
+    if (byte_in)
         for (int64_t k = 0; k < n; ++k)
-            if (strand[k] > 1) { set_err("pair %lld: strand byte %d is neither 0 nor 1", (long long)k, (int)strand[k]); return -1; }
+            if (byte_in[k] > (frames ? 5 : 1)) {
+                set_err(frames ? "pair %lld: frame byte %d is outside 0 .. 5" : "pair %lld: strand byte %d is neither 0 nor 1", (long long)k, (int)byte_in[k]);
+                return -1;
+            }
     const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
-    int64_t mq = 1, mr = 1, mnr = INT32_MAX, symbols = 0;
+    int32_t q32 = 1, r32 = 1, mnr = INT32_MAX;
     if (host_offsets) {
         // large batches: the scan is a few nanoseconds per pair of random reads into the offsets -- measured at 2.1 ms per million
         // pairs on one core, of a 6.9 ms call -- so it is cut into slices on helper threads, merged in pair order
         const int T = n >= 262144 ? 4 : 1;
-        PairScan part[4];
+        PairScan part[4], s;
         std::future<void> helper[4];
         for (int t = 1; t < T; ++t) {
             const int64_t a = n * t / T, e = n * (t + 1) / T;
@@ -4753,71 +4781,73 @@ static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_
         }
         part[0] = scan_pairs(Q, R, pairs, 0, n / T);
         for (int t = 1; t < T; ++t) if (helper[t].valid()) helper[t].get();
-        for (int t = 0; t < T; ++t) {
-            const PairScan &s = part[t];
-            if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
-            mq = s.mq > mq ? s.mq : mq; mr = s.mr > mr ? s.mr : mr; mnr = s.mnr < mnr ? s.mnr : mnr; symbols += s.symbols;
+        for (int t = 0; t < T && s.bad < 0; ++t) {
+            s.bad = part[t].bad; s.side = part[t].side; s.what = part[t].what;
+            s.mq = std::max(s.mq, part[t].mq); s.mr = std::max(s.mr, part[t].mr); s.mnr = std::min(s.mnr, part[t].mnr); s.symbols += part[t].symbols;
         }
+        if (codons && short_window_check(plan.ref ? R : Q, pairs, s.bad >= 0 ? s.bad : n, plan.ref)) return -1;
+        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
+        q32 = (int32_t)s.mq; r32 = (int32_t)s.mr; mnr = (int32_t)s.mnr;
+        if (symbols) *symbols = s.symbols;
+        plan.to_letters(&q32, &r32, &mnr);
     }
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    if (pairs_check(cfg, Q, R, opts, (int32_t)mq, (int32_t)mr, stats_out != nullptr, ex)) return -1;
+    if (lens_check(q32, r32, host_offsets) || pairs_check(cfg, Q, R, opts, q32, r32, stats_out != nullptr, ex)) return -1;
     static thread_local HostStreams hs;
     if (hs.init(false)) return -1;
     const hipStream_t st = hs.comp;
-    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr; uint8_t *dstrand = nullptr;
-    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the strand bytes
-    if (scratch_reserve(up_bytes + (strand || both ? (size_t)n : 0), (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
+    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
+    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
+    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the bytes in, then out
+    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
         (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
+    uint8_t *dbin = (uint8_t *)dp + up_bytes, *dbout = dbin + n;
     HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (strand) {
-        dstrand = (uint8_t *)dp + up_bytes;
-        HIP_OR_RET(hipMemcpyAsync(dstrand, strand, (size_t)n, hipMemcpyHostToDevice, st));
-    }
-    int32_t q32 = (int32_t)mq, r32 = (int32_t)mr;
+    if (byte_in) { HIP_OR_RET(hipMemcpyAsync(dbin, byte_in, (size_t)n, hipMemcpyHostToDevice, st)); plan.d_byte = dbin; }
     pmx_config_t cfg_s = *cfg;
-    if (host_offsets) cfg_s = with_sort_hint(cfg, (int32_t)mnr, r32, n);
+    if (host_offsets) { if (hint) cfg_s = with_sort_hint(cfg, mnr, r32, n); }
     else {
         if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
-        if (pssm_batch_check(cfg->matrix, q32, q32)) return -1;
+        if (symbols) *symbols = (int64_t)n * ((int64_t)q32 + r32);           // (wrapped sets: the lengths stayed on the device)
+        plan.to_letters(&q32, &r32);
+        if (lens_check(q32, r32, true) || pssm_batch_check(cfg->matrix, q32, q32)) return -1;
     }
-    if (both) {
-        dstrand = (uint8_t *)dp + up_bytes;               // (the winners' strands, written by the fold)
-        int rc = pairs_run_folded(&cfg_s, Q, R, n, dp, plan, q32, r32, drec, dst, dstrand, st, pairs_chunk(n, q32, r32, opts, plan.per));
-        if (rc) { (void)hipStreamSynchronize(st); return rc; }
-        HIP_OR_RET(hipMemcpyAsync(strand_out, dstrand, (size_t)n, hipMemcpyDeviceToHost, st));
-        return pairs_copy_back(n, drec, dst, out, stats_out, !host_offsets, st);
-    }
-    if (!cigar) {
-        const int rc = pairs_ex_run(&cfg_s, Q, R, n, dp, dstrand, q32, r32, drec, dst, nullptr, nullptr, 0, nullptr, st, opts);
-        if (rc) { (void)hipStreamSynchronize(st); return rc; }
-        return pairs_copy_back(n, drec, dst, out, stats_out, !host_offsets, st);
-    }
-    if (!host_offsets) symbols = (int64_t)n * ((int64_t)q32 + r32);          // (wrapped sets: the lengths stayed on the device)
-    int64_t capacity = symbols / 2 + 16 * n + 256;
-    DevBuf<int64_t> dtoff; DevBuf<int32_t> dbeg; DevBuf<char> dtext;
-    if (dtoff.try_alloc((size_t)n + 1) || (beg && dbeg.try_alloc(2 * (size_t)n)) || dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    for (int pass = 0; pass < 2; ++pass) {
-        const int rc = pairs_ex_run(&cfg_s, Q, R, n, dp, dstrand, q32, r32, drec, nullptr, dbeg.p, dtext.p, capacity, dtoff.p, st, opts);
-        if (rc) { (void)hipStreamSynchronize(st); return rc; }
-        HIP_OR_RET(hipMemcpyAsync(cigar_off, dtoff.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
-        HIP_OR_RET(hipStreamSynchronize(st));
-        if (cigar_off[n] <= capacity) break;
-        capacity = cigar_off[n];                          // rare: the text did not fit the estimate -- again with the exact size
-        (void)hipFree(dtext.p); dtext.p = nullptr;
-        if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-    }
-    const int rc = pairs_copy_back(n, drec, nullptr, out, nullptr, !host_offsets, st);
-    if (rc) return rc;
+    const int rc = run(&cfg_s, dp, q32, r32, drec, dst, dbout, st);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    if (byte_out) HIP_OR_RET(hipMemcpyAsync(byte_out, dbout, (size_t)n, hipMemcpyDeviceToHost, st));
+    return pairs_copy_back(n, drec, dst, out, stats_out, scan_flags || !host_offsets, st);
+}
+
+// The host entries over listed pairs.  ex: pmx_align_pairs_ex -- strand bytes (may be NULL), and with PMX_WANT_CIGAR the begins (may be
+// NULL) and the text, a HostText stage of half a byte per symbol + 16 per pair.
+// both: pmx_align_pairs_both -- PMX_STRAND_BOTH, the winners' strand bytes into strand_out.
+static int pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *pairs, const uint8_t *strand,
+                      pmx_record_t *out, pmx_stats_t *stats_out, int32_t *beg, char **cigar_buf, int64_t *cigar_off, const pmx_pairs_opts_t *opts, bool ex,
+                      bool both = false, uint8_t *strand_out = nullptr)
+{
+    SlotPlan plan;                                        // both: the two strands; else PLAIN, and d_byte the strand bytes once they are on the device
+    if (both) plan.strands(PMX_STRAND_BOTH);
+    if (listed_entry_check(cfg, Q, R, n, pairs, out, opts, both ? &plan : nullptr, strand_out)) return -1;
+    if (both && (pairs_both_want_check(cfg) || strand_mode_check(cfg, PMX_STRAND_BOTH, &plan))) return -1;
+    if (ex && pairs_ex_outputs_check(cfg, beg, cigar_buf, 0, cigar_off)) return -1;
+    const bool cigar = ex && (cfg->want & PMX_WANT_CIGAR) != 0;
+    if (cigar) { *cigar_buf = nullptr; cigar_off[0] = 0; }
+    if (n == 0) return 0;
+    int64_t symbols = 0;
+    HostText text; DevBuf<int32_t> dbeg;
+    const int rc = listed_pairs_host(cfg, Q, R, n, pairs, strand, plan, out, stats_out, strand_out, opts, ex, true, false, &symbols,
+        [](int32_t, int32_t, bool) { return 0; },
+        [&](const pmx_config_t *c, const pmx_pair_t *dp, int32_t q32, int32_t r32, pmx_record_t *drec, pmx_stats_t *dst, uint8_t *dsout, hipStream_t st) -> int {
+            if (both) return pairs_run_folded(c, Q, R, n, dp, plan, q32, r32, drec, dst, dsout, st, pairs_chunk(n, q32, r32, opts, plan.per));
+            if (!cigar) return pairs_ex_run(c, Q, R, n, dp, plan.d_byte, q32, r32, drec, dst, nullptr, nullptr, 0, nullptr, st, opts);
+            if (beg && dbeg.try_alloc(2 * (size_t)n)) { set_err("out of device memory"); return -2; }
+            if (text.alloc(n, symbols / 2 + 16 * n + 256)) return -2;
+            return text.run(n, cigar_off, &st, [&](char *d_text, int64_t capacity, int64_t *d_text_off) {
+                return pairs_ex_run(c, Q, R, n, dp, plan.d_byte, q32, r32, drec, nullptr, dbeg.p, d_text, capacity, d_text_off, st, opts);
+            });
+        });
+    if (rc || !cigar) return rc;
     if (beg) HIP_OR_RET(hipMemcpy(beg, dbeg.p, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost));
-    TextBuf text;
-    char *dst_text = text.grow((size_t)cigar_off[n]);
-    if (!dst_text) { set_err("out of memory"); return -1; }
-    if (cigar_off[n]) {
-        const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
-    }
-    text.len = (size_t)cigar_off[n];
-    return publish_text(text, cigar_buf);
+    return text.to_block(cigar_off[n], cigar_buf);
 }
 
 extern "C" int pmx_align_pairs(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -4842,71 +4872,6 @@ extern "C" int pmx_align_pairs_both(const pmx_config_t *cfg, const pmx_seqset_t 
 }
 
 
-// Listed pairs over a set with host offsets, the descriptors below `end` good: the first whose query window has fewer than three
-// nucleotides -- no codon stream --, refused with its number; 0 when there is none.  ref (the _frameshift_ref entries): S is the
-// reference set and the window the reference's.
-static int short_window_check(const pmx_seqset *S, const pmx_pair_t *pairs, int64_t end, bool ref = false)
-{
-    for (int64_t k = 0; k < end; ++k) {
-        const pmx_pair_t &p = pairs[k];
-        const int64_t idx = ref ? p.r : p.q, beg = ref ? p.r_beg : p.q_beg, len = ref ? p.r_len : p.q_len;
-        const int64_t W = len < 0 ? S->h_off[(size_t)idx + 1] - S->h_off[(size_t)idx] - beg : len;
-        if (W < 3) { set_err("pair %lld: %s: a window of %lld nucleotides has no codon", (long long)k, ref ? "reference" : "query", (long long)W); return -1; }
-    }
-    return 0;
-}
-
-// What the host entries over listed pairs with a translated side (FRAMES, CODONS) share, behind their own argument checks: pairs_host's
-// score road -- the bytes' validation, the descriptors against host offsets, the maxima in letters, the upload of 32 (+ 1) bytes per
-// pair, the maxima of wrapped sets from the device -- then run(cfg, d_pairs, max_qlen, max_rlen, d_rec, d_stats, d_byte_out, st), then
-// the winners' bytes and the records back.  A pair without a frame or a codon is found on the device only, so the records' flags are
-// always scanned.  lens_check(max_qlen, max_rlen, known): what the entry refuses about the maxima, asked before any GPU work (known:
-// the sets have host offsets) and again for wrapped sets.  hint: the run's configuration carries the sort hint of the host lengths.
-template <typename LensCheck, typename Run>
-static int translated_pairs_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *pairs,
-                                 const uint8_t *byte_in, SlotPlan &plan, pmx_record_t *out, pmx_stats_t *stats_out, uint8_t *byte_out,
-                                 const pmx_pairs_opts_t *opts, bool ex, bool hint, LensCheck lens_check, Run run)
-{
-    const bool codons = plan.kind == SlotPlan::CODONS;
-    if (byte_in)
-        for (int64_t k = 0; k < n; ++k)
-            if (byte_in[k] > (codons ? 1 : 5)) {
-                set_err(codons ? "pair %lld: strand byte %d is neither 0 nor 1" : "pair %lld: frame byte %d is outside 0 .. 5", (long long)k, (int)byte_in[k]);
-                return -1;
-            }
-    const bool host_offsets = !Q->h_off.empty() && !R->h_off.empty();
-    int32_t q32 = 1, r32 = 1, mnr = INT32_MAX;
-    if (host_offsets) {
-        const PairScan s = scan_pairs(Q, R, pairs, 0, n);
-        if (codons && short_window_check(plan.ref ? R : Q, pairs, s.bad >= 0 ? s.bad : n, plan.ref)) return -1;
-        if (s.bad >= 0) { set_err("pair %lld: %s: %s", (long long)s.bad, s.side, s.what); return -1; }
-        q32 = (int32_t)s.mq; r32 = (int32_t)s.mr; mnr = (int32_t)s.mnr;
-        plan.to_letters(&q32, &r32, &mnr);
-    }
-    if (lens_check(q32, r32, host_offsets) || pairs_check(cfg, Q, R, opts, q32, r32, stats_out != nullptr, ex)) return -1;
-    static thread_local HostStreams hs;
-    if (hs.init(false)) return -1;
-    const hipStream_t st = hs.comp;
-    const bool stats = (cfg->want & PMX_WANT_STATS) != 0;
-    pmx_pair_t *dp = nullptr; pmx_record_t *drec = nullptr; pmx_stats_t *dst = nullptr;
-    const size_t up_bytes = (sizeof(pmx_pair_t) * (size_t)n + 255) & ~(size_t)255;          // descriptors, then the bytes in, then out
-    if (scratch_reserve(up_bytes + 2 * (size_t)n, (void **)&dp, SCR_PUP) || scratch_reserve(sizeof(pmx_record_t) * (size_t)n, (void **)&drec, SCR_PREC) ||
-        (stats && scratch_reserve(sizeof(pmx_stats_t) * (size_t)n, (void **)&dst, SCR_PST))) return -1;
-    uint8_t *dbin = (uint8_t *)dp + up_bytes, *dbout = dbin + n;
-    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (byte_in) { HIP_OR_RET(hipMemcpyAsync(dbin, byte_in, (size_t)n, hipMemcpyHostToDevice, st)); plan.d_byte = dbin; }
-    pmx_config_t cfg_s = *cfg;
-    if (host_offsets) { if (hint) cfg_s = with_sort_hint(cfg, mnr, r32, n); }
-    else {
-        if (device_maxlens(Q, R, dp, n, &q32, &r32, st)) return -1;
-        plan.to_letters(&q32, &r32);
-        if (lens_check(q32, r32, true)) return -1;
-    }
-    const int rc = run(&cfg_s, dp, q32, r32, drec, dst, dbout, st);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    if (byte_out) HIP_OR_RET(hipMemcpyAsync(byte_out, dbout, (size_t)n, hipMemcpyDeviceToHost, st));
-    return pairs_copy_back(n, drec, dst, out, stats_out, true, st);
-}
 
 // The host entries over listed pairs with a translated side (ref false: pmx_align_pairs_translated, true: pmx_align_pairs_translated_ref).
 static int align_pairs_frames_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
@@ -4917,7 +4882,7 @@ static int align_pairs_frames_host(const pmx_config_t *cfg, const pmx_seqset_t *
     if (listed_entry_check(cfg, Q, R, n, pairs, out, opts) || frames_check(cfg, frame_mode, frame, code, &fr, ref) ||
         byte_out_check(fr, n > 0, frame_out)) return -1;
     if (n == 0) return 0;
-    return translated_pairs_host(cfg, Q, R, n, pairs, frame, fr, out, stats_out, frame_out, opts, false, true,
+    return listed_pairs_host(cfg, Q, R, n, pairs, frame, fr, out, stats_out, frame_out, opts, false, true, true, nullptr,
         [](int32_t, int32_t, bool) { return 0; },
         [&](const pmx_config_t *c, const pmx_pair_t *dp, int32_t q32, int32_t r32, pmx_record_t *drec, pmx_stats_t *dst, uint8_t *dfout, hipStream_t st) {
             return pairs_run_folded(c, Q, R, n, dp, fr, q32, r32, drec, dst, dfout, st, pairs_chunk(n, q32, r32, opts, fr.per));
@@ -4939,8 +4904,7 @@ extern "C" int pmx_align_pairs_translated_ref(const pmx_config_t *cfg, const pmx
 }
 
 // The host entries over listed pairs of the frameshift-aware alignment.  traceback (pmx_align_pairs_frameshift_cigar): the
-// traceback road in place of the score road, and the text tail of pairs_host -- a text buffer sized by estimate, and one more run at the
-// exact size where the text did not fit.
+// traceback road in place of the score road, and a HostText stage of 32 bytes per pair.
 static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,
                                        int64_t n, const pmx_pair_t *pairs, const uint8_t *strand, int strand_mode,
                                        int32_t frameshift, const uint8_t *code, pmx_record_t *out, uint8_t *strand_out,
@@ -4954,40 +4918,24 @@ static int align_pairs_frameshift_host(const pmx_config_t *cfg, const pmx_seqset
         (traceback && frameshift_cigar_outputs_check(cfg, stats_out, cigar_buf, 0, cigar_off)) || byte_out_check(fr, n > 0, strand_out)) return -1;
     if (traceback) { *cigar_buf = nullptr; cigar_off[0] = 0; }
     if (n == 0) return 0;
-    int64_t capacity = 32 * n + 256;                      // (the run-length text of a hit is a few runs; a batch of noise runs twice)
-    DevBuf<int64_t> dtoff; DevBuf<int32_t> dbeg; DevBuf<char> dtext;
-    const int rc = translated_pairs_host(cfg, Q, R, n, pairs, strand, fr, out, stats_out, strand_out, opts, traceback, false,
+    HostText text; DevBuf<int32_t> dbeg;
+    const int rc = listed_pairs_host(cfg, Q, R, n, pairs, strand, fr, out, stats_out, strand_out, opts, traceback, false, true, nullptr,
         [&](int32_t mq, int32_t mr, bool known) {
             return frameshift_rows_check(mq, ref) || (traceback && !windowed && known && frameshift_trace_bound_check(frameshift_trace_bytes_per_slot(ref, mq, mr), mq, mr)) ? -1 : 0;
         },
         [&](const pmx_config_t *c, const pmx_pair_t *dp, int32_t q32, int32_t r32, pmx_record_t *drec, pmx_stats_t *dst, uint8_t *dsout, hipStream_t st) -> int {
             const int64_t chunk = pairs_chunk(n, q32, r32, opts, fr.per);
             if (!traceback) return pairs_run_folded(c, Q, R, n, dp, fr, q32, r32, drec, nullptr, dsout, st, chunk);
-            if (dtoff.try_alloc((size_t)n + 1) || (beg && dbeg.try_alloc(2 * (size_t)n)) || dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-            for (int pass = 0; pass < 2; ++pass) {
-                const int rc = windowed ? pairs_run_codons_cigar_windowed(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr)
-                                        : pairs_run_codons_cigar(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, dtext.p, capacity, dtoff.p, st, chunk, fr);
-                if (rc) return rc;
-                HIP_OR_RET(hipMemcpyAsync(cigar_off, dtoff.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
-                HIP_OR_RET(hipStreamSynchronize(st));
-                if (cigar_off[n] <= capacity) break;
-                capacity = cigar_off[n];                          // the text did not fit the estimate -- again with the exact size
-                (void)hipFree(dtext.p); dtext.p = nullptr;
-                if (dtext.try_alloc((size_t)capacity + 1)) { set_err("out of device memory"); return -2; }
-            }
-            return 0;
+            if (beg && dbeg.try_alloc(2 * (size_t)n)) { set_err("out of device memory"); return -2; }
+            if (text.alloc(n, 32 * n + 256)) return -2;             // (the run-length text of a hit is a few runs; a batch of noise runs twice)
+            return text.run(n, cigar_off, &st, [&](char *d_text, int64_t capacity, int64_t *d_text_off) {
+                return windowed ? pairs_run_codons_cigar_windowed(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, d_text, capacity, d_text_off, st, chunk, fr)
+                                : pairs_run_codons_cigar(c, Q, R, n, dp, q32, r32, drec, dsout, dst, dbeg.p, d_text, capacity, d_text_off, st, chunk, fr);
+            });
         });
     if (rc || !traceback) return rc;
     if (beg) HIP_OR_RET(hipMemcpy(beg, dbeg.p, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost));
-    TextBuf text;
-    char *dst_text = text.grow((size_t)cigar_off[n]);
-    if (!dst_text) { set_err("out of memory"); return -1; }
-    if (cigar_off[n]) {
-        const hipError_t e = hipMemcpy(dst_text, dtext.p, (size_t)cigar_off[n], hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(text.p); set_err("%s", hipGetErrorString(e)); return -(int)e; }
-    }
-    text.len = (size_t)cigar_off[n];
-    return publish_text(text, cigar_buf);
+    return text.to_block(cigar_off[n], cigar_buf);
 }
 
 extern "C" int pmx_align_pairs_frameshift(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R,

@@ -337,30 +337,36 @@ int pmx_launch_pairs_gather_codons(long long n, const uint8_t *q_buf, long long 
                                    const uint8_t *ok, const uint8_t *sflag, const int64_t *qoff, const int64_t *roff,
                                    uint8_t *qout, long long q_cap, uint8_t *rout, long long r_cap, const PmxCodeTable &code, hipStream_t stream,
                                    bool ref = false);
-// The three-frame local DP over codon streams (pmx_swfs.hip): n slots of up to b.max_qlen rows x b.max_rlen columns, 32-bit scores.
-// bnd: boundary scratch of bnd_slots * pmx_swfs_bound_bytes_per_slot(b.max_rlen) bytes, needed when b.max_qlen exceeds
-// pmx_swfs_strip_rows() (the launch then runs in parts of bnd_slots slots).  0 launched, 1 not eligible, <0 HIP error.
-int pmx_swfs_max_msize();
-int pmx_swfs_strip_rows();
-size_t pmx_swfs_bound_bytes_per_slot(int max_rlen);
-int pmx_launch_swfs(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
-                    pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
-// The same DP with the codon stream on the columns (pmx_swfsc.hip): n slots of up to b.max_qlen protein rows x b.max_rlen
-// stream columns.  bnd: bnd_slots * pmx_swfsc_bound_bytes_per_slot(b.max_rlen) bytes, needed when b.max_qlen exceeds
-// pmx_swfsc_strip_rows() (the launch then runs in parts of bnd_slots slots).  0 launched, 1 not eligible, <0 HIP error.
-extern "C" int pmx_swfsc_max_msize();
-extern "C" int pmx_swfsc_lane_rows();
-extern "C" int pmx_swfsc_strip_rows();
-extern "C" long long pmx_swfsc_bound_bytes_per_slot(int max_rlen);
-int pmx_launch_swfsc(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
-                     pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
+// The three-frame local DP over codon streams, one description per side.  Query side (pmx_swfs.hip): the stream on the rows,
+// n slots of up to b.max_qlen stream rows x b.max_rlen protein columns.  Reference side (pmx_swfsc.hip): the same DP with the
+// stream on the columns, b.max_qlen protein rows x b.max_rlen stream columns.  32-bit scores.  Both launchers are pmx_fs.h's.
+struct PmxFsSide {
+    bool ref;                // the reference's side: the walk's `ref`, pmx_launch_pairs_resolve_codons' and _gather_codons'
+    int max_msize;           // the kernel keeps the matrix in LDS
+    int strip_rows;          // b.max_qlen above this: the sweep runs in strips and needs boundary scratch
+    int lane_rows;           // rows per lane; strip_rows / lane_rows lanes per slot
+    int max_rows;            // the cap on b.max_qlen: PMX_FRAMESHIFT_MAX_WINDOW - 2 stream letters, PMX_FRAMESHIFT_REF_MAX_QUERY protein letters
+    // boundary scratch of one slot of a launch whose b.max_qlen exceeds strip_rows: two buffers of max_rlen columns
+    long long (*bound_bytes_per_slot)(int max_rlen);
+    // the trace form's scratch of one slot: the query side's sweep stores by column, the reference side's by step (below)
+    long long (*trace_bytes_per_slot)(int max_qlen, int max_rlen);
+    // launch: the score form, trace NULL; bnd holds bnd_slots slots and the launch runs in parts of as many.  launch_trace: one launch
+    // over b.n slots; trace (and bnd, when strips are needed) hold the bytes of b.n slots rounded up to a multiple of four, bnd_slots is
+    // not read.  0 launched, 1 not eligible, <0 HIP error.
+    int (*launch)(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots, void *trace,
+                  pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
+    decltype(launch) launch_trace;
+    const char *names[2][2]; // pmx_last_kernel(): [trace form][several strips]
+};
+const PmxFsSide &pmx_fs_query_side();     // pmx_swfs.hip
+const PmxFsSide &pmx_fs_ref_side();       // pmx_swfsc.hip
+static inline const PmxFsSide &pmx_fs_side(bool ref) { return ref ? pmx_fs_ref_side() : pmx_fs_query_side(); }
 // The trace form of the sweep and its walk (semantics: include/parasail_amd.h, "Frameshift traceback").  A cell's decision
 // byte: bits 0 .. 2 where H came from (START .. LONG: from M, and which term D was), bit 3 E was opened, bit 4 F was opened.  The byte of
 // row i, column j of a slot: ((i / STRIP_ROWS * max_rlen + j) * COL_BYTES) + i % STRIP_ROWS / LANE_ROWS * 12 + i % LANE_ROWS.
 enum { PMX_FSTR_START = 0, PMX_FSTR_INFRAME = 1, PMX_FSTR_SHORT = 2, PMX_FSTR_LONG = 3, PMX_FSTR_F = 4, PMX_FSTR_E = 5, PMX_FSTR_ZERO = 6,
        PMX_FSTR_EO = 8, PMX_FSTR_FO = 16,
        PMX_FSTR_LANE_ROWS = 10, PMX_FSTR_STRIP_ROWS = 160, PMX_FSTR_COL_BYTES = 192 };
-size_t pmx_swfs_trace_bytes_per_slot(int max_rows, int max_rlen);
 // The reference side's trace (pmx_swfsc.hip; semantics: "Frameshift traceback, reference side"): the same decision bytes,
 // STORED BY STEP.  Lane g of a slot's group finishes its ten rows of column t - g in step t, so a strip of a slot has
 // max_cols + PMX_FSTRC_SKEW steps of COL_BYTES bytes, and the byte of row i (a protein letter), column j (a stream letter) is
@@ -369,17 +375,11 @@ enum { PMX_FSTRC_SKEW = PMX_FSTR_COL_BYTES / 12 - 1 };
 #define PMX_FSTRC_CELL(i, j, max_cols)                                                                                                      \
     ((((size_t)((i) / PMX_FSTR_STRIP_ROWS) * (size_t)((max_cols) + PMX_FSTRC_SKEW) + (size_t)((j) + (i) % PMX_FSTR_STRIP_ROWS / PMX_FSTR_LANE_ROWS)) \
           * (PMX_FSTR_COL_BYTES / 12) + (size_t)((i) % PMX_FSTR_STRIP_ROWS / PMX_FSTR_LANE_ROWS)) * 12 + (size_t)((i) % PMX_FSTR_LANE_ROWS))
-extern "C" long long pmx_swfsc_trace_bytes_per_slot(int max_qlen, int max_rlen);
-int pmx_launch_swfsc_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
-                           pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
-// One launch over b.n slots; trace (and bnd, when b.max_qlen exceeds one strip) hold the bytes of b.n slots rounded up to a multiple of four.
-int pmx_launch_swfs_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
-                          pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
 // The walk over that trace (pmx_walkfs.hip), one lane per logical pair k of n: its record recs[k] (a bad pair's is flagged), its slot
 // per * k + (win ? win[k] : 0) of the sweep's launch; qoff / roff are the launch's, per * n + 1 entries.  ops: run-length ops
 // (len << 4 | op; '/' = 9, '\\' = 10) from the end of the PAIR's op slots backwards -- a pair owns the qlen + rlen + 1 entries of each of
 // its slots -- with nops and textlen; pair_qoff / pair_roff [n + 1]: the offsets with which pmx_launch_cigar_render_slots (ops_base 0)
-// finds the pairs' op slots; beg (2 n) and stats_out are optional.  ref: the trace is pmx_launch_swfsc_trace's, rows the query protein.
+// finds the pairs' op slots; beg (2 n) and stats_out are optional.  ref: the trace is the reference side's (PmxFsSide::launch_trace of pmx_swfsc.hip), rows the query protein.
 int pmx_launch_walkfs(const PmxDevMatrix &m, long long n, int per, const uint8_t *win,
                       const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, int max_rlen,
                       const pmx_record_t *recs, const uint8_t *trace, long long trace_bytes_per_slot,

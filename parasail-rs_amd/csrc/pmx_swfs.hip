@@ -25,6 +25,7 @@
 // Plain C++, vector loads and stores only.
 #include "pmx_common.h"
 #include "pmx_pk16.h"
+#include "pmx_fs.h"
 
 #define PMX_SWFS_NEG (-(1 << 29))
 
@@ -171,64 +172,19 @@ void pmx_swfs_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
     }
 }
 
-// LDS of a launch: the transposed matrix as int16 and the byte map.
-static size_t swfs_lds_bytes(int msize) { return (size_t)msize * msize * 2 + 256; }
-
-int pmx_swfs_max_msize() { return 128; }
-size_t pmx_swfs_bound_bytes_per_slot(int max_rlen) { return sizeof(int4) * 4 * (size_t)max_rlen; }
-int pmx_swfs_strip_rows() { return 16 * 10; }
-
-// n slots of up to max_rows x max_rlen.  bnd: boundary scratch for `bnd_slots` slots (needed when max_rows exceeds one strip; the
-// launch then runs in parts of bnd_slots slots, one behind the other on `stream`).  0 launched, 1 not eligible, <0 HIP error.
-int pmx_launch_swfs(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
-                    pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
+// The side's description (pmx_common.h): the launchers are pmx_fs.h's over the two forms of the kernel.
+static long long swfs_bound_bytes_per_slot(int max_rlen) { return (long long)sizeof(int4) * 4 * (long long)max_rlen; }
+static long long swfs_trace_bytes_per_slot(int max_rows, int max_rlen)
 {
-    constexpr int G = 16, R = 10, NPW = 64 / G;
-    if (m.pssm || m.msize > pmx_swfs_max_msize() || b.q_shared) return 1;
-    if (b.n <= 0) return 0;
-    const int cap = 1 << 28;
-    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
-    const bool strips = b.max_qlen > G * R;
-    if (strips && (!bnd || bnd_slots < NPW)) return 1;
-    const long long part = strips ? bnd_slots / NPW * NPW : b.n;
-    for (long long p0 = 0; p0 < b.n; p0 += part) {
-        const long long pn = b.n - p0 < part ? b.n - p0 : part;
-        hipLaunchKernelGGL((pmx_swfs_kernel<G, R, false>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfs_lds_bytes(m.msize), stream,
-                           b.qbuf, b.qoff + p0, b.rbuf, b.roff + p0, pn, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
-                           open, ext, fs, strips ? (int4 *)bnd : nullptr, d_out + p0, (uint32_t *)nullptr, 0LL);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
-    }
-    if (kernel_name) *kernel_name = strips ? "pmx_swfs_kernel<16,10>/strips" : "pmx_swfs_kernel<16,10>";
-    return 0;
+    const int strips = (max_rows + PMX_FSTR_STRIP_ROWS - 1) / PMX_FSTR_STRIP_ROWS;
+    return (long long)strips * (long long)max_rlen * PMX_FSTR_COL_BYTES;
 }
-
-// The trace form over n slots: the same sweep and records, and every cell's decision byte into `trace`, which holds
-// pmx_swfs_trace_bytes_per_slot bytes for each of the launch's slots ROUNDED UP TO WHOLE WORKGROUPS of four (the idle slots of the
-// last workgroup repeat slot n - 1 into their own regions).  bnd: boundary scratch for as many slots when max_rows exceeds one strip.
-// One launch: the caller cuts a chunk into parts that fit its scratch.  0 launched, 1 not eligible, <0 HIP error.
-size_t pmx_swfs_trace_bytes_per_slot(int max_rows, int max_rlen)
+static_assert(PMX_FSTR_COL_BYTES == 16 * 12 && PMX_FSTR_LANE_ROWS == 10 && PMX_FSTR_STRIP_ROWS == 16 * 10, "the walk's addressing (pmx_walkfs.hip)");
+const PmxFsSide &pmx_fs_query_side()
 {
-    const int strips = (max_rows + pmx_swfs_strip_rows() - 1) / pmx_swfs_strip_rows();
-    return (size_t)strips * (size_t)max_rlen * PMX_FSTR_COL_BYTES;
-}
-int pmx_launch_swfs_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
-                          pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
-{
-    constexpr int G = 16, R = 10, NPW = 64 / G;
-    static_assert(PMX_FSTR_COL_BYTES == G * 12 && PMX_FSTR_LANE_ROWS == R && PMX_FSTR_STRIP_ROWS == G * R, "the walk's addressing (pmx_walkfs.hip)");
-    if (m.pssm || m.msize > pmx_swfs_max_msize() || b.q_shared || !trace) return 1;
-    if (b.n <= 0) return 0;
-    const int cap = 1 << 28;
-    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
-    const bool strips = b.max_qlen > G * R;
-    if (strips && !bnd) return 1;
-    hipLaunchKernelGGL((pmx_swfs_kernel<G, R, true>), dim3((unsigned)((b.n + NPW - 1) / NPW)), dim3(64), swfs_lds_bytes(m.msize), stream,
-                       b.qbuf, b.qoff, b.rbuf, b.roff, b.n, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
-                       open, ext, fs, strips ? (int4 *)bnd : nullptr, d_out,
-                       (uint32_t *)trace, (long long)(pmx_swfs_trace_bytes_per_slot(b.max_qlen, b.max_rlen) / 4));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return -(int)e;
-    if (kernel_name) *kernel_name = strips ? "pmx_swfs_kernel<16,10,trace>/strips" : "pmx_swfs_kernel<16,10,trace>";
-    return 0;
+    static const PmxFsSide side = {
+        false, 128, 16 * 10, 10, PMX_FRAMESHIFT_MAX_WINDOW - 2, swfs_bound_bytes_per_slot, swfs_trace_bytes_per_slot,
+        pmx_fs_launch<int4, pmx_swfs_kernel<16, 10, false>, false, false>, pmx_fs_launch<int4, pmx_swfs_kernel<16, 10, true>, true, false>,
+        {{"pmx_swfs_kernel<16,10>", "pmx_swfs_kernel<16,10>/strips"}, {"pmx_swfs_kernel<16,10,trace>", "pmx_swfs_kernel<16,10,trace>/strips"}}};
+    return side;
 }

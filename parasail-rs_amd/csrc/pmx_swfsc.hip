@@ -32,6 +32,7 @@
 // Plain C++, vector loads and stores only.
 #include "pmx_common.h"
 #include "pmx_pk16.h"
+#include "pmx_fs.h"
 
 #define PMX_SWFSC_NEG (-(1 << 29))
 
@@ -165,69 +166,27 @@ void pmx_swfsc_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     }
 }
 
-// LDS of a launch: the transposed matrix as int16 and the byte map.
-static size_t swfsc_lds_bytes(int msize) { return (size_t)msize * msize * 2 + 256; }
-
 #define PMX_SWFSC_G 16
 #define PMX_SWFSC_R 10
 extern "C" int pmx_swfsc_max_msize() { return 128; }
 extern "C" int pmx_swfsc_lane_rows() { return PMX_SWFSC_R; }
 extern "C" int pmx_swfsc_strip_rows() { return PMX_SWFSC_G * PMX_SWFSC_R; }
 extern "C" long long pmx_swfsc_bound_bytes_per_slot(int max_rlen) { return (long long)sizeof(int2) * 2 * (long long)max_rlen; }
-
-// n slots of up to b.max_qlen rows x b.max_rlen columns.  bnd: boundary scratch for `bnd_slots` slots (needed when b.max_qlen exceeds
-// one strip; the launch then runs in parts of bnd_slots slots, one behind the other on `stream`).  0 launched, 1 not eligible, <0 HIP
-// error.
-int pmx_launch_swfsc(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, long long bnd_slots,
-                     pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
-{
-    constexpr int G = PMX_SWFSC_G, R = PMX_SWFSC_R, NPW = 64 / G;
-    if (m.pssm || m.msize > pmx_swfsc_max_msize() || b.q_shared) return 1;
-    if (b.n <= 0) return 0;
-    const int cap = 1 << 28;
-    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
-    const bool strips = b.max_qlen > G * R;
-    if (strips && (!bnd || bnd_slots < NPW)) return 1;
-    const long long part = strips ? bnd_slots / NPW * NPW : b.n;
-    for (long long p0 = 0; p0 < b.n; p0 += part) {
-        const long long pn = b.n - p0 < part ? b.n - p0 : part;
-        hipLaunchKernelGGL((pmx_swfsc_kernel<G, R, false>), dim3((unsigned)((pn + NPW - 1) / NPW)), dim3(64), swfsc_lds_bytes(m.msize), stream,
-                           b.qbuf, b.qoff + p0, b.rbuf, b.roff + p0, pn, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
-                           open, ext, fs, strips ? (int2 *)bnd : nullptr, d_out + p0, (uint32_t *)nullptr, 0LL);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
-    }
-    if (kernel_name) *kernel_name = strips ? "pmx_swfsc_kernel<16,10>/strips" : "pmx_swfsc_kernel<16,10>";
-    return 0;
-}
-
-// The trace form over n slots: the same sweep and records, and every cell's decision byte into `trace`, which holds
-// pmx_swfsc_trace_bytes_per_slot bytes for each of the launch's slots ROUNDED UP TO WHOLE WORKGROUPS of four (the idle slots of the
-// last workgroup repeat slot n - 1 into their own regions).  bnd: boundary scratch for as many slots when b.max_qlen exceeds one strip.
-// One launch: the caller cuts a chunk into parts that fit its scratch.  0 launched, 1 not eligible, <0 HIP error.
 extern "C" long long pmx_swfsc_trace_bytes_per_slot(int max_qlen, int max_rlen)
 {
     const int strips = (max_qlen + pmx_swfsc_strip_rows() - 1) / pmx_swfsc_strip_rows();
     return (long long)strips * ((long long)max_rlen + PMX_SWFSC_G - 1) * PMX_FSTR_COL_BYTES;
 }
-int pmx_launch_swfsc_trace(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int fs, void *bnd, void *trace,
-                           pmx_record_t *d_out, hipStream_t stream, const char **kernel_name)
+
+// The side's description (pmx_common.h): the exported hooks' values, and the launchers are pmx_fs.h's over the two forms of the kernel.
+static_assert(PMX_FSTR_COL_BYTES == PMX_SWFSC_G * 12 && PMX_FSTR_LANE_ROWS == PMX_SWFSC_R && PMX_FSTR_STRIP_ROWS == PMX_SWFSC_G * PMX_SWFSC_R &&
+              PMX_FSTRC_SKEW == PMX_SWFSC_G - 1, "the walk's addressing (PMX_FSTRC_CELL, pmx_walkfs.hip)");
+const PmxFsSide &pmx_fs_ref_side()
 {
-    constexpr int G = PMX_SWFSC_G, R = PMX_SWFSC_R, NPW = 64 / G;
-    static_assert(PMX_FSTR_COL_BYTES == G * 12 && PMX_FSTR_LANE_ROWS == R && PMX_FSTR_STRIP_ROWS == G * R && PMX_FSTRC_SKEW == G - 1,
-                  "the walk's addressing (PMX_FSTRC_CELL, pmx_walkfs.hip)");
-    if (m.pssm || m.msize > pmx_swfsc_max_msize() || b.q_shared || !trace) return 1;
-    if (b.n <= 0) return 0;
-    const int cap = 1 << 28;
-    open = open < cap ? open : cap; ext = ext < cap ? ext : cap; fs = fs < cap ? fs : cap;
-    const bool strips = b.max_qlen > G * R;
-    if (strips && !bnd) return 1;
-    hipLaunchKernelGGL((pmx_swfsc_kernel<G, R, true>), dim3((unsigned)((b.n + NPW - 1) / NPW)), dim3(64), swfsc_lds_bytes(m.msize), stream,
-                       b.qbuf, b.qoff, b.rbuf, b.roff, b.n, b.max_qlen, b.max_rlen, m.scores, m.mapper, m.msize,
-                       open, ext, fs, strips ? (int2 *)bnd : nullptr, d_out,
-                       (uint32_t *)trace, pmx_swfsc_trace_bytes_per_slot(b.max_qlen, b.max_rlen) / 4);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return -(int)e;
-    if (kernel_name) *kernel_name = strips ? "pmx_swfsc_kernel<16,10,trace>/strips" : "pmx_swfsc_kernel<16,10,trace>";
-    return 0;
+    static const PmxFsSide side = {
+        true, 128, PMX_SWFSC_G * PMX_SWFSC_R, PMX_SWFSC_R, PMX_FRAMESHIFT_REF_MAX_QUERY, pmx_swfsc_bound_bytes_per_slot, pmx_swfsc_trace_bytes_per_slot,
+        pmx_fs_launch<int2, pmx_swfsc_kernel<PMX_SWFSC_G, PMX_SWFSC_R, false>, false, true>,
+        pmx_fs_launch<int2, pmx_swfsc_kernel<PMX_SWFSC_G, PMX_SWFSC_R, true>, true, true>,
+        {{"pmx_swfsc_kernel<16,10>", "pmx_swfsc_kernel<16,10>/strips"}, {"pmx_swfsc_kernel<16,10,trace>", "pmx_swfsc_kernel<16,10,trace>/strips"}}};
+    return side;
 }

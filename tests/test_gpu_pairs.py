@@ -440,3 +440,39 @@ def test_two_identical_calls_give_identical_bytes(pkg):
     b, bst = _pairs_device(pkg, cfg, S, S, pairs, 200, 200, 1024)
     assert a.tobytes() == b.tobytes() and ast.tobytes() == bst.tobytes()
     assert (a[:, 3] == 0).all() and (a != SENTINEL).all()
+
+
+# ------------------------------------------------------------------------------- 8. the host road's scan on helper threads
+def _big_list(rng, n=262144 + 3, nseq=16):
+    """n whole-sequence descriptors over a set of nseq sequences: from 262 144 pairs on, the host road scans in four slices"""
+    pairs = np.zeros(n, dtype=pairs_ref.PAIR_DTYPE)
+    pairs["q"], pairs["r"] = rng.integers(0, nseq, size=n), rng.integers(0, nseq, size=n)
+    pairs["q_len"] = pairs["r_len"] = -1
+    return pairs
+
+
+def test_host_entries_equal_device_entries_where_the_scan_is_threaded(pkg):
+    import torch
+    rng = np.random.default_rng(7950)
+    seqs = random_seqs(rng, 16, 8, 8)
+    pairs = _big_list(rng)
+    n = len(pairs)
+    S = pkg.SeqSet.new(seqs)
+    pm = pkg.Matrix.create(b"ACGT", 2, -3)
+    cfg = pkg.pmx_config_t(pkg.MODE_SW, 0, 5, 2, 0, 0, pm.inner)
+    want, _ = _pairs_device(pkg, cfg, S, S, pairs, 8, 8)
+    al = pkg.Aligner.new().local().matrix(pm).gap_open(5).gap_extend(2).build()
+    assert al.align_pairs(S, S, pairs).tobytes() == want.tobytes()
+    assert len({tuple(r) for r in want[:4096].tolist()}) > 8              # (records that differ: an order mixed up would show)
+    # the same list through a frameshift host entry: the nucleotides' eight letters are amino-acid letters too
+    b62 = pkg.Matrix.from_name("blosum62")
+    fcfg = pkg.pmx_config_t(pkg.MODE_SW, 0, 11, 1, 0, 0, b62.inner)
+    rec = torch.full((n, 4), SENTINEL, dtype=torch.int32, device=_dev())
+    won = torch.full((n,), 9, dtype=torch.uint8, device=_dev())
+    d_pairs = _up_pairs(pairs)
+    pkg.align_pairs_frameshift_device(fcfg, S, S, n, d_pairs.data_ptr(), None, pkg.STRAND_BOTH, 4, 6, 8, rec.data_ptr(), won.data_ptr(), _stream(), 0)
+    torch.cuda.synchronize()
+    fal = pkg.Aligner.new().local().matrix(b62).gap_open(11).gap_extend(1).build()
+    got, gwon = fal.align_pairs(S, S, pairs, frameshift=4, strand="both")
+    assert got.tobytes() == rec.cpu().numpy().tobytes() and gwon.tobytes() == won.cpu().numpy().tobytes()
+    assert (gwon <= 1).all() and gwon.any() and not gwon.all()

@@ -480,6 +480,24 @@ def test_search_device_cigar_capacity_too_small(pkg, orc, cfg5):
     assert dv["recs"][:40].tobytes() == host.recs.tobytes() and dv["hits"][:40].tobytes() == host.hits.tobytes()
 
 
+def test_search_text_beyond_the_estimate(pkg):
+    """the host entry's second text pass: references that alternate match and mismatch against the query ("1=1X..." is two bytes of
+    text per column) push the hits' text past the first capacity, (hits x query letters + hit bytes) / 2 + 16 per hit + 256, and the
+    second pass runs again at the exact size; texts and records equal the device entry's into a generous buffer"""
+    rng = np.random.default_rng(5700)
+    q = b"AC" * 50
+    rs = [(b"AG" * 60)[:int(L)] for L in rng.integers(94, 107, size=30)]
+    pm = pkg.Matrix.create(b"ACGT", 2, -1)
+    al = pkg.Aligner.new().global_().profile(pkg.Profile.new(q, False, pm)).matrix(pm).gap_open(5).gap_extend(2).build()
+    hits = al.search_profile(rs, -1000, order=1, band=31, stats=True)
+    h = hits.n_hits
+    assert h == len(rs) and sorted(hits.index.tolist()) == list(range(h))
+    assert hits.cigar_off[h] > (h * len(q) + sum(len(r) for r in rs)) // 2 + 16 * h + 256      # the first pass cannot have held it
+    assert hits.cigar_off[h] == sum(len(c) for c in hits.cigars) and all(c.count("1=1X") >= 40 for c in hits.cigars)
+    ds = _DeviceSearch(pkg, al, *pkg.pack(rs))
+    _same_as_host(pkg, ds.run(-1000, 0, 1, 31, stats=True), hits, 31, True)
+
+
 def test_search_want_sorted_changes_nothing(pkg, orc, cfg5):
     c = cfg5
     host = c["al"].search_profile_packed(c["rbuf"], c["roff"], 200, band=48, stats=True)

@@ -199,3 +199,33 @@ def test_python_mirror_refuses_a_profile_and_builds_descriptors(pkg):
     a = pkg.as_pairs([(0, 1), (2, 1, 3, 4, 5, -1)])
     assert a.dtype == pkg.PAIR_DTYPE and a.tolist() == [(0, 1, 0, -1, 0, -1), (2, 1, 3, 4, 5, -1)]
     assert a.tolist() == pairs_ref.pairs_array([(0, 1), (2, 1, 3, 4, 5, -1)]).tolist()
+
+
+@pytest.mark.gpu                      # the refusals happen before any GPU work, but a set with host offsets is uploaded when it is created
+def test_lowest_bad_pair_across_the_slices_of_the_scan(pkg):
+    """262 144 + 3 listed pairs are scanned in four slices on helper threads: the pair named is the lowest bad one of the list,
+    whichever slice found it, on the plain host entry and on a frameshift one; a window without a codon below it is named first"""
+    rng = np.random.default_rng(6200)
+    n, nseq = 262144 + 3, 16
+    S = pkg.SeqSet.new([bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=8)) for _ in range(nseq)])
+    pairs = np.zeros(n, dtype=pkg.PAIR_DTYPE)
+    pairs["q"], pairs["r"] = rng.integers(0, nseq, size=n), rng.integers(0, nseq, size=n)
+    pairs["q_len"] = pairs["r_len"] = -1
+    plain = pkg.Aligner.new().local().matrix(pkg.Matrix.create(b"ACGT", 2, -3)).gap_open(5).gap_extend(2).build()
+    shift = pkg.Aligner.new().local().matrix(pkg.Matrix.from_name("blosum62")).gap_open(11).gap_extend(1).build()
+    entries = (lambda p: plain.align_pairs(S, S, p), lambda p: shift.align_pairs(S, S, p, frameshift=4, strand="both"))
+    last, second = n - 1000, n // 4 + 5
+    assert last >= n * 3 // 4 and n // 4 <= second < n // 2
+    pairs[last]["r"] = nseq                                         # the last quarter: the fourth slice
+    for entry in entries:
+        with pytest.raises(pkg.BatchError, match=r"^pair %d: reference: index outside the set$" % last):
+            entry(pairs)
+    pairs[second]["q_beg"] = 7; pairs[second]["q_len"] = 2          # the second quarter: the second slice
+    for entry in entries:
+        with pytest.raises(pkg.BatchError, match=r"^pair %d: query: window reaches past the end of the sequence$" % second):
+            entry(pairs)
+    pairs[100]["q_beg"] = 3; pairs[100]["q_len"] = 2                # a good descriptor whose W < 3, below both
+    with pytest.raises(pkg.BatchError, match=r"^pair 100: query: a window of 2 nucleotides has no codon$"):
+        entries[1](pairs)
+    with pytest.raises(pkg.BatchError, match=r"^pair %d: query: window reaches past" % second):
+        entries[0](pairs)                                           # (the plain entry takes a window of two letters)
