@@ -1502,6 +1502,14 @@ int pmx_bandtr_geometry(int max_qlen, int max_rlen, int band, int q_shared, int 
  * the bias nb of the stored form when the int16 window holds every pair of up to max_qlen x max_rlen under this scoring in a shape of
  * shape_rows rows (0: the dispatcher's estimate before a shape is picked), else 0.  rowx: the row-offset form (every width but 8). */
 int pmx_window_nwsgv(int max_qlen, int max_rlen, int msize, int score_min, int score_max, int open, int extend, int rowx, int shape_rows);
+/* Test hook of the traceback planners (host arithmetic only, no device needed; expected values: tests/golden/trace_plans.json): the
+ * sweep planned for n pairs of up to max_qlen x max_rlen under this scoring -- the per-pair plan (packed_ok 0: first-generation sweeps
+ * only), or with q_shared > 0 the shared-query plan (short_waves 1: without the shapes of 19 and 20 rows per lane).  Returns 0 with the
+ * family (0 trace16, 1 nwsg16v, 2 nwsg16m, 3 sw16, 4 sw16m, 5 nwsg16q), lanes per pair G, rows per lane R, steps Tmax and the trace
+ * scratch in bytes; or 1, not eligible, with all five 0. */
+int pmx_trace_plan_probe(int mode, int msize, int score_min, int score_max, int pssm, int open, int extend, long long n,
+                         int max_qlen, int max_rlen, int q_shared, int short_waves, int packed_ok,
+                         int *family, int *G, int *R, int *Tmax, long long *trace_bytes);
 
 #ifdef __cplusplus
 }

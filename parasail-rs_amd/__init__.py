@@ -413,6 +413,7 @@ _sig("pmx_align_pairs_frameshift_ref_cigar_long", C.c_int, C.POINTER(pmx_config_
      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_frameshift_ref_cigar_long_parts", C.c_int64)
 _sig("pmx_swfsc_window_cols", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong)
+_sig("pmx_trace_plan_probe", C.c_int, *([C.c_int] * 7 + [C.c_longlong] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)]))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 

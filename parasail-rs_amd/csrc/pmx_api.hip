@@ -1404,14 +1404,14 @@ static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 
 static thread_local const char *g_last_kernel = "";
 extern "C" const char *pmx_last_kernel(void) { return g_last_kernel; }
-// the per-pair global / semi-global traceback roads: the sweep as its launcher named it (kernel, decision form) + the walk
-static const char *nwsg_trace_kernel_name(const char *walk)
+// the packed traceback roads: the sweep as its launcher named it (kernel, decision form) + the walk the plan names
+static const char *trace_road_name(const char *sweep, const PmxTracePlan &p, const DevMat &dm, bool stats)
 {
     static thread_local char name[160];
-    snprintf(name, sizeof name, "%s%s", pmx_nwsg_trace_name(), walk);
+    snprintf(name, sizeof name, "%s + %s%s", sweep, p.walk == PMX_TRACE_WALK16 ? "pmx_walk16_kernel" : dm.d.pssm ? "pmx_walkp_kernel<pssm>" : "pmx_walkp_kernel",
+             stats ? "/stats" : "");
     return name;
 }
-
 
 // What every general-kernel batch shares: the n pairs, the matrix (a PSSM by query row), the gap model, the configured width, no band.
 static PmxGeneralArgs general_args(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
@@ -1596,35 +1596,38 @@ template <typename Body> static int overlap_chunks(int64_t n, int64_t chunk, boo
 }
 
 // Per-pair packed traceback over a batch the plan takes, in chunks of `chunk` pairs overlapped as overlap_chunks describes: the
-// sweep's shape (*variant) and trace bytes are planned for one chunk, with two trace buffers and two sets of block flags, or one.
+// sweep and its trace bytes are planned for one chunk, with two trace buffers and two sets of block flags, or one.
 // Per pair the walk leaves either the path's statistics (stats) or run-length ops in implicit slots (ops / ops_base) with their
-// count, begins and CIGAR text length.
+// count, begins and CIGAR text length.  g_last_kernel: the last chunk's sweep + the walk.
 struct TraceOutputs { pmx_stats_t *stats; uint32_t *ops; long long ops_base; int32_t *nops, *beg, *textlen; };
 static size_t trace_flag_stride(int64_t chunk) { return (size_t)chunk / 2 + 16; }    // ints of one set of per-block flags
 static int trace_chunks(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch &b, int64_t chunk, bool two, int *bflags,
-                        pmx_record_t *d_out, const TraceOutputs &o, hipStream_t st, const char *what, int *variant)
+                        pmx_record_t *d_out, const TraceOutputs &o, hipStream_t st, const char *what)
 {
     PmxBatch bc = b; bc.n = chunk;
-    int Tmax = 0; size_t cbytes = 0;
-    (void)pmx_trace16_plan(bc, dm.d, cfg->mode, cfg->open, cfg->extend, variant, &Tmax, &cbytes);
-    cbytes = (cbytes + 255) & ~(size_t)255;
+    PmxTracePlan plan;
+    if (pmx_trace16_plan(bc, dm.d, cfg->mode, cfg->open, cfg->extend, &plan) != 0 || plan.walk != PMX_TRACE_WALKP) return 1;
+    const size_t cbytes = (plan.trace_bytes + 255) & ~(size_t)255;
     uint32_t *tbuf = nullptr;
     if (scratch_reserve(cbytes * (two ? 2 : 1), (void **)&tbuf, SCR_TRACE)) return -1;
     const size_t fstride = trace_flag_stride(chunk);
-    return overlap_chunks(b.n, chunk, two, st, [&](const ChunkTurn &t) -> int {
+    const char *sweep = "";
+    const int rc = overlap_chunks(b.n, chunk, two, st, [&](const ChunkTurn &t) -> int {
         const int64_t c0 = t.c0;
         PmxBatch bk = b;
         bk.n = t.n;
         bk.qoff = b.qoff + c0; bk.roff = b.roff + c0;
         bk.blockflag = bflags + (size_t)(t.idx & 1) * fstride;
         PmxWalkSplit sp = {t.walk, t.sweep_done, t.walk_done, o.ops_base - c0, o.textlen ? o.textlen + c0 : nullptr};
-        const int rc = pmx_launch_trace16(*variant, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out + c0,
-                                          (uint32_t *)((unsigned char *)tbuf + (size_t)t.buf * cbytes), Tmax,
-                                          o.ops, nullptr, o.nops ? o.nops + c0 : nullptr, o.beg ? o.beg + 2 * c0 : nullptr, t.sweep,
+        const int rc = pmx_launch_trace16(plan, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, d_out + c0,
+                                          (uint32_t *)((unsigned char *)tbuf + (size_t)t.buf * cbytes),
+                                          o.ops, nullptr, o.nops ? o.nops + c0 : nullptr, o.beg ? o.beg + 2 * c0 : nullptr, t.sweep, &sweep,
                                           o.stats ? o.stats + c0 : nullptr, &sp);
         if (rc) { set_err("%s (%d)", what, rc); return rc < 0 ? rc : -1; }
         return 0;
     });
+    if (rc == 0) g_last_kernel = trace_road_name(sweep, plan, dm, o.stats != nullptr);
+    return rc;
 }
 
 // 0 done (asynchronously on st), 1 not eligible, <0 error
@@ -1650,13 +1653,13 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
                                  pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t st)
 {
     if (pmx_env("PMX_NO_STATS_BY_TRACE")) return 1;
-    int variant = 0, Tmax = 0, G = 0, R = 0; size_t tbytes = 0;
-    if (pmx_nwsgq_trace_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes, &G, &R) != 0) return 1;
+    PmxTracePlan plan;
+    if (pmx_nwsgq_trace_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &plan) != 0) return 1;
     if (trace_ws_init()) return -1;
-    const long long NP = 2 * (64 / G) * 4;                     // pairs per workgroup of the sweep
+    const long long NP = plan.pairs_per_wg;
     // (measured on cfg 3: 8 GB chunks 55.0 ms, 24 GB 53.1 ms, 40 GB 51.0 ms)
     const double chunk_bytes = chunk_budget(40e9, 0.2, pmx_env("PMX_STATS_CHUNK_BYTES"));
-    const double per_pair = (double)tbytes / (double)b.n;
+    const double per_pair = (double)plan.trace_bytes / (double)b.n;
     long long chunk = (long long)(chunk_bytes / per_pair) / NP * NP;
     if (chunk < NP) chunk = NP;
     bool by_rounds = false;
@@ -1666,7 +1669,7 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
         // so a launch of N workgroups runs for ceil(N / resident) rounds -- cfg 3 in three equal chunks of 1 042 workgroups each
         // (512 resident) ran 5 + 3 rounds where 6.1 were needed: 45.2 -> 42.5 ms (the remainder chunk first instead of last: 42.8).
         // Otherwise (a round does not fit a chunk): equal shares.
-        const long long round = pmx_env("PMX_STATS_EQUAL_CHUNKS") ? 0 : pmx_nwsgq_trace_round_pairs(variant, dm.d, cfg->mode, cfg->sg_flags);
+        const long long round = pmx_env("PMX_STATS_EQUAL_CHUNKS") ? 0 : pmx_nwsgq_trace_round_pairs(plan, dm.d, cfg->mode, cfg->sg_flags);
         if (round > 0 && chunk >= round) {
             chunk = chunk / round * round; by_rounds = true;
             if (g_upload) chunk = round;                       // (host entry: the references arrive in slices -- a sweep starts as soon as ONE round's worth is up)
@@ -1677,9 +1680,8 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
         }
     }
     PmxBatch bc = b; bc.n = chunk;
-    size_t cbytes = 0;
-    (void)pmx_nwsgq_trace_plan(bc, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &cbytes, &G, &R);
-    cbytes = (cbytes + 255) & ~(size_t)255;
+    (void)pmx_nwsgq_trace_plan(bc, dm.d, cfg->mode, cfg->open, cfg->extend, &plan);     // (the same shape: the bytes of one chunk)
+    const size_t cbytes = (plan.trace_bytes + 255) & ~(size_t)255;
     // (PMX_STATS_NO_OVERLAP: sweep and walk of every chunk back to back on the caller's stream, one trace buffer -- the form the
     //  serialised kernel traces under profiles/ are taken in: per-launch durations of overlapping launches cannot be added up)
     const bool two = chunk < b.n && !pmx_env("PMX_STATS_NO_OVERLAP");
@@ -1691,16 +1693,17 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
     size_t rbytes = 0;
     if (rem_n) {
         PmxBatch br = b; br.n = rem_n;
-        int v_ = 0, T_ = 0, G_ = 0, R_ = 0;
-        (void)pmx_nwsgq_trace_plan(br, dm.d, cfg->mode, cfg->open, cfg->extend, &v_, &T_, &rbytes, &G_, &R_);
-        size_t r2 = 0;
-        if (pmx_nwsgq_trace_plan(br, dm.d, cfg->mode, cfg->open, cfg->extend, &v_, &T_, &r2, &G_, &R_, 1) == 0 && r2 > rbytes) rbytes = r2;
+        PmxTracePlan pr = plan;
+        (void)pmx_nwsgq_trace_plan(br, dm.d, cfg->mode, cfg->open, cfg->extend, &pr);
+        rbytes = pr.trace_bytes;
+        if (pmx_nwsgq_trace_plan(br, dm.d, cfg->mode, cfg->open, cfg->extend, &pr, 1) == 0 && pr.trace_bytes > rbytes) rbytes = pr.trace_bytes;
         rbytes = (rbytes + 255) & ~(size_t)255;
     }
     uint32_t *tbuf = nullptr;
     if (scratch_reserve(cbytes * (two ? 2 : 1) + rbytes, (void **)&tbuf, SCR_TRACE)) return -1;
     const PmxEnds ends = pmx_ends(cfg->mode, cfg->sg_flags);      // (nw or sg: the plan above takes no other mode)
     // one chunk: positions [t.c0, t.c0 + t.n) of the batch; sweep into the t.buf-th trace buffer (of tb_bytes), the walk behind it
+    const char *sweep = "", *tail_sweep = "";                  // (the road's name is the whole chunks' sweep, not the short tail's)
     auto run_chunk = [&](const ChunkTurn &t, size_t tb_bytes, bool short_waves) -> int {
         const long long c0 = t.c0;
         uint32_t *tb = (uint32_t *)((unsigned char *)tbuf + (size_t)t.buf * cbytes);
@@ -1712,18 +1715,13 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
         if (!b.perm && upload_wait(c0 + bk.n, t.sweep, t.sweep == st ? 0 : 1)) return -1;                  // (host entry: this chunk's references are up)
         // The remainder after the whole rounds is less than one round: it runs on the shape with half the rows per lane (<32,10> for
         // <16,20> / <16,19>) -- twice the waves, each half as long
-        int variant_k = variant, Tmax_k = Tmax, G_k = G, R_k = R;
-        if (short_waves && R >= 19 && !pmx_env("PMX_STATS_NO_SHORT_TAIL")) {
-            int v2 = 0, T2 = 0, G2 = 0, R2 = 0; size_t tb2 = 0;
-            if (pmx_nwsgq_trace_plan(bk, dm.d, cfg->mode, cfg->open, cfg->extend, &v2, &T2, &tb2, &G2, &R2, 1) == 0 && tb2 <= tb_bytes) {
-                variant_k = v2; Tmax_k = T2; G_k = G2; R_k = R2;
-            }
-        }
-        const int gsel_k = G_k == 16 ? 1 : G_k == 32 ? 2 : 3;
-        int rc = pmx_launch_nwsgq_trace(variant_k, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, out_k, tb, Tmax_k, t.sweep);
+        PmxTracePlan pk = plan, p2;
+        if (short_waves && plan.R >= 19 && !pmx_env("PMX_STATS_NO_SHORT_TAIL") &&
+            pmx_nwsgq_trace_plan(bk, dm.d, cfg->mode, cfg->open, cfg->extend, &p2, 1) == 0 && p2.trace_bytes <= tb_bytes) pk = p2;
+        int rc = pmx_launch_nwsgq_trace(pk, bk, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, out_k, tb, t.sweep, short_waves ? &tail_sweep : &sweep);
         if (rc) { set_err("shared-profile traceback sweep failed (%d)", rc); return rc < 0 ? rc : -1; }
         if ((rc = chunk_sweep_launched(t)) != 0) return rc;
-        rc = pmx_launch_walkp(gsel_k, R_k, bk, dm.d, cfg->mode, cfg->open, cfg->extend, Tmax_k, 0, st_k, ends.row_pen, ends.col_pen,
+        rc = pmx_launch_walkp(pk.G, pk.R, bk, dm.d, cfg->mode, cfg->open, cfg->extend, pk.Tmax, pk.top_aligned, st_k, ends.row_pen, ends.col_pen,
                               tb, out_k, nullptr, nullptr, 0, nullptr, nullptr, nullptr, t.walk);
         if (rc) { set_err("statistics walk failed (%d)", rc); return rc < 0 ? rc : -1; }
         return chunk_walk_launched(t);
@@ -1739,10 +1737,7 @@ static int stats_by_trace_shared(const pmx_config_t *cfg, const DevMat &dm, cons
         return run_chunk(t, cbytes, by_rounds && two && t.n < chunk);
     });
     if (rc) return rc;
-    static thread_local char name[112];
-    if (dm.d.pssm) snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d,pssm>/shared PSSM profile/packed trace/bfi + pmx_walkp_kernel<pssm>/stats", G, R);
-    else snprintf(name, sizeof name, "pmx_nwsg16q_kernel<%d,%d>/shared profile/packed trace/bfi + pmx_walkp_kernel/stats", G, R);
-    g_last_kernel = name;
+    g_last_kernel = trace_road_name(sweep, plan, dm, true);
     return 0;
 }
 
@@ -1756,11 +1751,11 @@ static int stats_by_trace_pairs(const pmx_config_t *cfg, const DevMat &dm, const
     if (b.q_shared || !(b.n >= 2048 || pmx_env("PMX_STATS_BY_TRACE")) || pmx_env("PMX_NO_STATS_BY_TRACE")) return 1;
     const int64_t n = b.n;
     PmxBatch bt = b; bt.perm = nullptr;
-    int variant = 0, Tmax = 0; size_t tbytes = 0;
-    if (pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) != 0 || variant < 10) return 1;
+    PmxTracePlan plan;
+    if (pmx_trace16_plan(bt, dm.d, cfg->mode, cfg->open, cfg->extend, &plan) != 0 || plan.walk != PMX_TRACE_WALKP) return 1;
     const double budget = chunk_budget(8e9, 0.15, nullptr);
-    const double per_pair = (double)tbytes / (double)n + 1.0;
-    int64_t nchunks = (int64_t)((double)tbytes / budget) + 1;
+    const double per_pair = (double)plan.trace_bytes / (double)n + 1.0;
+    int64_t nchunks = (int64_t)((double)plan.trace_bytes / budget) + 1;
     if (nchunks < 2 && n >= 16384) nchunks = 2;            // two chunks at least: the walk of one runs beside the sweep of the next
     int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
     if ((double)chunk * per_pair > budget) chunk = (int64_t)(budget / per_pair) / 64 * 64;
@@ -1771,10 +1766,7 @@ static int stats_by_trace_pairs(const pmx_config_t *cfg, const DevMat &dm, const
     int *bflags = nullptr;
     if (scratch_reserve(2 * trace_flag_stride(chunk) * sizeof(int), (void **)&bflags, SCR_RETRY)) return -1;
     const TraceOutputs o = {d_stats, nullptr, 0, nullptr, nullptr, nullptr};
-    const int rc = trace_chunks(cfg, dm, bt, chunk, two, bflags, d_out, o, st, "stats-by-traceback launch failed", &variant);
-    if (rc) return rc;
-    g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel/stats" : nwsg_trace_kernel_name(" + pmx_walkp_kernel/stats");
-    return 0;
+    return trace_chunks(cfg, dm, bt, chunk, two, bflags, d_out, o, st, "stats-by-traceback launch failed");
 }
 
 // The long-pair sweep's switches and scratch budget as both of its roads read them (long_batch, long_cigar_device); which form runs
@@ -2511,8 +2503,8 @@ static bool cigar_device_eligible(const pmx_config_t *cfg, const DevMat &dm, int
 {
     if (cfg->width == 8 || cfg->matrix->type != PARASAIL_MATRIX_TYPE_SQUARE) return false;
     const PmxBatch b = {nullptr, nullptr, nullptr, nullptr, n, mq, mr, 0, nullptr, nullptr, nullptr, 0, 0};
-    int variant = 0, Tmax = 0; size_t tbytes = 0;
-    return pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) == 0 && variant >= 10;
+    PmxTracePlan plan;
+    return pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &plan) == 0 && plan.walk == PMX_TRACE_WALKP;
 }
 static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
                             const uint8_t *d_qbuf, const int64_t *d_qoff, const uint8_t *d_rbuf, const int64_t *d_roff,
@@ -2522,12 +2514,12 @@ static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n
 {
     if (cfg->width == 8 || cfg->matrix->type != PARASAIL_MATRIX_TYPE_SQUARE) return 1;
     PmxBatch b = {d_qbuf, d_qoff, d_rbuf, d_roff, n, mq, mr, 0, nullptr, nullptr, nullptr, 0, 0};
-    int variant = 0, Tmax = 0; size_t tbytes = 0;
-    if (pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes) != 0 || variant < 10) return 1;
+    PmxTracePlan plan;
+    if (pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &plan) != 0 || plan.walk != PMX_TRACE_WALKP) return 1;
     if (trace_ws_init()) return -1;
     // chunks: at most ~12 GB of trace each (two buffers; measured on 1.25 M pairs of 250 x 250: 3 GB chunks 27.8 ms, 12 GB 26.2 ms --
     // fewer launch tails), at most 15 % of the free HBM each, at least two for the overlap once the batch is worth it
-    const int64_t chunk = chunk_pairs(n, (double)tbytes, chunk_budget(12e9, 0.15, pmx_env("PMX_CIGAR_CHUNK_BYTES")), n >= 16384 ? 2 : 1);
+    const int64_t chunk = chunk_pairs(n, (double)plan.trace_bytes, chunk_budget(12e9, 0.15, pmx_env("PMX_CIGAR_CHUNK_BYTES")), n >= 16384 ? 2 : 1);
     const bool two = chunk < n && !pmx_env("PMX_CIGAR_NO_OVERLAP");     // (diagnostics: sweep and walk back to back on one stream)
     SlotText t; int32_t *beg = nullptr; int *bflags = nullptr; int64_t *local_off = nullptr;
     if (t.reserve_ops((size_t)n * ((size_t)mq + mr + 1)) ||
@@ -2539,15 +2531,12 @@ static int cigar_device_run(const pmx_config_t *cfg, const DevMat &dm, int64_t n
         })) return -1;
     if (!set.continues) local_off = nullptr;
     const TraceOutputs o = {nullptr, t.ops, ops_base, t.nops, set.beg ? set.beg : beg, t.textlen};
-    int rc = trace_chunks(cfg, dm, b, chunk, two, bflags, d_out, o, st, "traceback launch failed", &variant);
+    int rc = trace_chunks(cfg, dm, b, chunk, two, bflags, d_out, o, st, "traceback launch failed");
     if (rc) return rc;
     if (set.ok && (rc = pmx_launch_pairs_fixup_cigar(set.ok, n, d_out, t.nops, t.textlen, set.beg, st)) != 0) {
         set_err("bad-pair fix-up launch failed (%d)", rc); return rc;
     }
-    rc = t.render(d_qoff, d_roff, ops_base, n, d_text, capacity, d_text_off, st, local_off);
-    if (rc) return rc;
-    g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : nwsg_trace_kernel_name(" + pmx_walkp_kernel");
-    return 0;
+    return t.render(d_qoff, d_roff, ops_base, n, d_text, capacity, d_text_off, st, local_off);
 }
 
 extern "C" int pmx_align_batch_cigar_device(const pmx_config_t *cfg, int64_t n,
@@ -2715,15 +2704,16 @@ static int cigar_chunk(const pmx_config_t *cfg, const DevMat &dm, int64_t n,
 
     tm.done("H2D");
     PmxBatch b = {dq.p, dqo.p, dr.p, dro.p, n, mq, mr, 0, nullptr, nullptr, nullptr, 0, 0};
-    int variant = 0, Tmax = 0; size_t tbytes = 0;
+    PmxTracePlan plan;
     int rc;
     if (cfg->width != 8 && cfg->matrix->type == PARASAIL_MATRIX_TYPE_SQUARE &&
-        pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &variant, &Tmax, &tbytes, false) == 0) {   // (packed sweeps: the pipelined path)
+        pmx_trace16_plan(b, dm.d, cfg->mode, cfg->open, cfg->extend, &plan, false) == 0) {   // (packed sweeps: the pipelined path)
         uint32_t *tbuf = nullptr;
-        if (scratch_reserve(tbytes, (void **)&tbuf, SCR_TRACE)) return -1;
-        rc = pmx_launch_trace16(variant, b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, drec.p, tbuf, Tmax,
-                                dops, doo.p, dnops.p, dbeg.p, nullptr);
-        g_last_kernel = variant >= 20 ? "pmx_sw16_kernel/packed trace + pmx_walkp_kernel" : variant >= 10 ? nwsg_trace_kernel_name(" + pmx_walkp_kernel") : "pmx_trace16_kernel + pmx_walk16_kernel";
+        if (scratch_reserve(plan.trace_bytes, (void **)&tbuf, SCR_TRACE)) return -1;
+        const char *sweep = "pmx_trace16_kernel";
+        rc = pmx_launch_trace16(plan, b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, drec.p, tbuf,
+                                dops, doo.p, dnops.p, dbeg.p, nullptr, &sweep);
+        g_last_kernel = trace_road_name(sweep, plan, dm, false);
         if (rc) { set_err("trace16 launch failed (%d)", rc); return rc < 0 ? rc : -1; }
     } else {
         std::vector<int64_t> tab_off(n + 1);

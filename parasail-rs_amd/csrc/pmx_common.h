@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/parasail_amd.h"
 #include "../../include/pmx_conventions.h"
 
@@ -52,10 +53,45 @@ struct PmxBatch {
 int pmx_launch_sw16(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                     pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
 
-// Traceback variant of the local kernel (pmx_sw16.hip, VAR 7): same trace layout, rows top-aligned.
-int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int *variant, int *Tmax, size_t *trace_bytes);
-int pmx_launch_sw16_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
-                          pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream);
+// A planned traceback sweep: what its launcher, the walk behind it and the caller's chunking need to know.  The planners fill it
+// (0 planned, 1 not eligible: *p untouched) and call no HIP function; the launch entries take it back (0 launched, 1 not eligible,
+// <0 HIP error) and name the sweep that really ran through *kernel_name.  GEN1: pmx_trace16_kernel, one pair per lane group, R / 8
+// trace words per lane and step; the others, packed: two pairs per group, (R + 3) / 4 * 4 bytes per lane and step (SW16: VAR 7).
+enum PmxTraceFamily { PMX_TRACE_GEN1, PMX_TRACE_NWSG16V, PMX_TRACE_NWSG16M, PMX_TRACE_SW16, PMX_TRACE_SW16M, PMX_TRACE_NWSG16Q };
+enum PmxTraceWalk { PMX_TRACE_WALK16, PMX_TRACE_WALKP };     // pmx_walk16_kernel (pmx_trace16.hip) / pmx_walkp_kernel (pmx_walkp.hip)
+struct PmxTracePlan {
+    PmxTraceFamily family;
+    int G, R;                // lanes per pair (group), query rows per lane
+    int pairs_per_wg;
+    int Tmax;                // steps of a lane's trace stream (the packed sweeps: a multiple of 16, the walk reads windows of 16 records)
+    size_t trace_bytes;      // trace scratch for the planned b.n pairs
+    bool top_aligned;        // the query's rows start at the first lane's first row (local sweeps); else they end at the last lane's last
+    bool fills_blockflag;    // the launcher fills PmxBatch::blockflag (0 = a block with top-aligned rows) and the walk reads it
+    PmxTraceWalk walk;
+};
+// The plan of a packed sweep of shape <G, R> with `waves` waves per workgroup over n pairs whose longest reference takes `steps` steps.
+static inline PmxTracePlan pmx_packed_trace_plan(PmxTraceFamily family, int G, int R, int waves, int steps, long long n)
+{
+    PmxTracePlan p;
+    p.family = family; p.G = G; p.R = R; p.pairs_per_wg = 2 * (64 / G) * waves;
+    p.Tmax = (steps + 15) & ~15;
+    p.trace_bytes = (size_t)((n + p.pairs_per_wg - 1) / p.pairs_per_wg) * (size_t)waves * (size_t)p.Tmax * 64 * (size_t)((R + 3) / 4 * 4);
+    p.top_aligned = family == PMX_TRACE_SW16 || family == PMX_TRACE_SW16M; p.fills_blockflag = family == PMX_TRACE_NWSG16V; p.walk = PMX_TRACE_WALKP;
+    return p;
+}
+
+// The lane groups G0, 2 G0, .. 64 of the per-pair packed trace shapes <G, 16>, smallest first: f(G) with G an integral constant until
+// one returns true.  Planner and launcher of a family walk the same list.
+template <int G0, typename F> static inline bool pmx_for_each_trace_group(F &&f)
+{
+    if constexpr (G0 <= 64) return f(std::integral_constant<int, G0>{}) || pmx_for_each_trace_group<2 * G0>(f);
+    else return false;
+}
+
+// Traceback variant of the local kernel (pmx_sw16.hip, VAR 7; large alphabets: pmx_sw16m.hip): same trace layout, rows top-aligned.
+int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, PmxTracePlan *p);
+int pmx_launch_sw16_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
+                          pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream, const char **kernel_name);
 
 // Bias of the second-generation nw/sg arithmetic (0: its exact window does not hold for this batch).
 int pmx_nwsgv_bias(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int rowx = 0, int shape_rows = 0 /* > 0: the rows of the shape that will run */);
@@ -64,19 +100,16 @@ int pmx_launch_stats16p(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
                         pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t stream, const char **kernel_name);
 
 // Traceback variant of the second-generation nw/sg kernel (pmx_nwsg16.hip); the walk lives in pmx_trace16.hip.
-int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
-                         int *variant, int *Tmax, size_t *trace_bytes);
-int pmx_launch_nwsgv_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
-                           pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream);
-// the sweep pmx_launch_nwsgv_trace launched last on this thread: kernel + "/packed trace" + the decision form ("/bfi", "/shift")
-const char *pmx_nwsg_trace_name();
+// (*kernel_name: kernel + "/packed trace" + the decision form, "/bfi" or "/shift", + "/permtable ..." where that form ran first)
+int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, PmxTracePlan *p);
+int pmx_launch_nwsgv_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
+                           pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream, const char **kernel_name);
 
 // Traceback with a shared query (pmx_nwsg16q_kernel<..., TR>): statistics of the profile arm are counted along the path.
-long long pmx_nwsgq_trace_round_pairs(int variant, const PmxDevMatrix &m, int mode, int sg_flags);
-int pmx_nwsgq_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
-                         int *variant, int *Tmax, size_t *trace_bytes, int *G_out, int *R_out, int short_waves = 0);
-int pmx_launch_nwsgq_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
-                           pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream);
+long long pmx_nwsgq_trace_round_pairs(const PmxTracePlan &p, const PmxDevMatrix &m, int mode, int sg_flags);
+int pmx_nwsgq_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, PmxTracePlan *p, int short_waves = 0);
+int pmx_launch_nwsgq_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
+                           pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream, const char **kernel_name);
 
 // Shared-query variant of the local kernel (pmx_sw16q.hip); called by pmx_launch_sw16 once the skewed byte-profile
 // variant's conditions hold.  0 launched, 1 not eligible, <0 HIP error.
@@ -87,8 +120,8 @@ int pmx_launch_sw16q(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext
 int pmx_launch_sw16m(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                      pmx_record_t *d_out, hipStream_t stream, const char **kernel_name);
 
-int pmx_launch_sw16m_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
-                           pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream);
+int pmx_launch_sw16m_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
+                           pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream);
 
 // 2-bit packed input -> ASCII letters (pmx_sort.hip)
 int pmx_launch_unpack2(const uint8_t *in, uint8_t *out, long long lo, long long hi, uint32_t letters, hipStream_t stream);
@@ -109,11 +142,10 @@ int pmx_launch_stats16(const PmxBatch &b, const PmxDevMatrix &m, int mode, int s
                        pmx_record_t *d_out, pmx_stats_t *d_stats, hipStream_t stream, const char **kernel_name);
 
 // Fast path with traceback (pmx_trace16.hip): 4-bit trace in HBM + on-device walk -> run-length ops.
-int pmx_trace16_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
-                     int *variant, int *Tmax, size_t *trace_bytes, bool packed_ok = true /* false: first-generation kernels only */);
+int pmx_trace16_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, PmxTracePlan *p, bool packed_ok = true /* false: first generation only */);
 // Walk over the packed records (pmx_walkp.hip).  ops: run-length BAM ops written from the END of the pair's slot backwards
 // (slot = ops_off[k] .. + qlen + rlen + 1, or implicit: qoff[k] + roff[k] + k - ops_base): the forward list is the last nops[k] entries.
-int pmx_launch_walkp(int gsel, int R, const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, int Tmax, int top_aligned,
+int pmx_launch_walkp(int G, int R, const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, int Tmax, int top_aligned,
                      pmx_stats_t *stats_out, int row_pen, int col_pen, const uint32_t *tbuf, const pmx_record_t *recs,
                      uint32_t *ops, const int64_t *ops_off, long long ops_base, int32_t *nops, int32_t *beg, int32_t *textlen,
                      hipStream_t stream, const int *blockflag = nullptr /* per sweep block: 0 = top-aligned rows (perm-table sweep) */);
@@ -125,10 +157,10 @@ struct PmxWalkSplit {
     long long ops_base;        // ops_off == nullptr: slot of pair k starts at qoff[k] + roff[k] + k - ops_base
     int32_t *textlen;          // optional, per pair: bytes of its CIGAR text
 };
-int pmx_launch_trace16(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
-                       pmx_record_t *d_out, uint32_t *tbuf, int Tmax,
-                       uint32_t *ops, const int64_t *ops_off, int32_t *nops, int32_t *beg, hipStream_t stream,
-                       pmx_stats_t *stats_out = nullptr /* count the path's statistics instead of emitting ops */,
+// The planned sweep and its walk; *sweep_name: the sweep as its launcher named it.
+int pmx_launch_trace16(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
+                       pmx_record_t *d_out, uint32_t *tbuf, uint32_t *ops, const int64_t *ops_off, int32_t *nops, int32_t *beg, hipStream_t stream,
+                       const char **sweep_name, pmx_stats_t *stats_out = nullptr /* count the path's statistics instead of emitting ops */,
                        const PmxWalkSplit *split = nullptr);
 
 // ---- general kernel (all modes, stats, tables, rows/cols, trace, band) -------------------

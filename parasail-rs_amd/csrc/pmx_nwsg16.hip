@@ -1401,8 +1401,6 @@ void pmx_nwsg16m_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
     }
 }
 
-// which per-pair packed-traceback sweep this thread launched last (pmx_nwsg_trace_name below): 0 nwsg16v shift, 1 nwsg16v bfi, 2 nwsg16m
-static thread_local int g_nwsg_trace_form = 0;
 template <int G, int R, bool TR = false>
 static int launch_nwsgm(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
                         pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf = nullptr, int Tmax = 0)
@@ -1411,7 +1409,6 @@ static int launch_nwsgm(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     const size_t lds = (size_t)(m.msize + 1) * 32 + 256 + (size_t)NP * PMX_PAIRTAB_BYTES;
     const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
-    if (TR) g_nwsg_trace_form = 2;
     if (blocks <= 0) return 0;
     hipLaunchKernelGGL((pmx_nwsg16m_kernel<G, R, TR>), dim3((unsigned)blocks), dim3(64), lds, stream,
                        b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper, m.msize, open, ext,
@@ -1419,25 +1416,21 @@ static int launch_nwsgm(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     return pmx_launched();
 }
 
-template <int G, int R, bool TR, bool PSSM>
-static int launch_nwsgq_form(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
-                             pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf, int Tmax);
-// (a PSSM, m.pssm: the instance with PSSM = true; its LDS holds no matrix)
-template <int G, int R, bool TR = false>
-static int launch_nwsgq(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
-                        pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf = nullptr, int Tmax = 0)
+// Dynamic LDS of the shared-profile form <G, R>: the byte profile, the matrix (a PSSM: none), the mapper, the workgroup's pair table
+// and, in the trace form, the four waves' record staging.
+static size_t nwsgq_lds(const PmxDevMatrix &m, int G, int R, bool TR)
 {
-    if (m.pssm) return launch_nwsgq_form<G, R, TR, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    return launch_nwsgq_form<G, R, TR, false>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
+    const int RS = (R + 3) / 4 * 4, WAVES = 4, NP = 2 * (64 / G) * WAVES;
+    return (size_t)(m.msize + 1) * G * RS + 8 + (m.pssm ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)NP * 24 +
+           (TR ? (size_t)WAVES * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4 : 0);
 }
 template <int G, int R, bool TR, bool PSSM>
 static int launch_nwsgq_form(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
                              pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf, int Tmax)
 {
-    constexpr int RS = (R + 3) / 4 * 4, WAVES = 4, NP = 2 * (64 / G) * WAVES;
+    constexpr int WAVES = 4, NP = 2 * (64 / G) * WAVES;
     if (PSSM && m.rows != b.q_shared) return 1;
-    const size_t lds = (size_t)(m.msize + 1) * G * RS + 8 + (PSSM ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)NP * 24 +
-                       (TR ? (size_t)WAVES * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4 : 0);
+    const size_t lds = nwsgq_lds(m, G, R, TR);             // (PSSM == m.pssm: launch_nwsgq)
     if (lds > 160 * 1024) return 1;
     const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
@@ -1458,38 +1451,45 @@ static int launch_nwsgq_form(const PmxBatch &b, const PmxDevMatrix &m, int mode,
     return pmx_launched();
 }
 
+// (a PSSM, m.pssm: the instance with PSSM = true; its LDS holds no matrix)
+template <int G, int R, bool TR = false>
+static int launch_nwsgq(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
+                        pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf = nullptr, int Tmax = 0)
+{
+    if (m.pssm) return launch_nwsgq_form<G, R, TR, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
+    return launch_nwsgq_form<G, R, TR, false>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
+}
+
 // Traceback with a shared query (profile arm): shapes <16,10> <16,16> <32,10> <32,16> <64,16>, one virtual row at least on top
-// (the walk needs row -1), bounded differences for the one-instruction decision merge.  *variant = 30 + shape index.
+// (the walk needs row -1), bounded differences for the one-instruction decision merge.
 // <16,20>: 320 rows like <32,10>, but twice the rows per lane -- the per-step work that is not per row (hand-off, captures, record
 // assembly, staging flush) is shared by twice the cells -- and a record of exactly 20 bytes instead of 12 for half the cells.
 // (<16,19>, round 4: a 300-row query -- the typical protein -- fills 300 of 304 rows instead of 300 of 320; tried before <16,20>)
-static const int kQShapeG[7] = {16, 16, 16, 32, 32, 64, 16}, kQShapeR[7] = {10, 16, 20, 10, 16, 16, 19}, kQShapeOrder[7] = {0, 1, 6, 2, 3, 4, 5};
-int pmx_nwsgq_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
-                         int *variant, int *Tmax, size_t *trace_bytes, int *G_out, int *R_out, int short_waves)
+// The shapes in try order: f(G, R, the sweep's name, its name with a PSSM), G and R integral constants, until one returns true.
+template <typename F> static bool for_each_nwsgq_trace_shape(F &&f)
+{
+#define QSHAPE(G, R) f(std::integral_constant<int, G>{}, std::integral_constant<int, R>{}, "pmx_nwsg16q_kernel<" #G "," #R ">/shared profile/packed trace/bfi", \
+                       "pmx_nwsg16q_kernel<" #G "," #R ",pssm>/shared PSSM profile/packed trace/bfi")
+    return QSHAPE(16, 10) || QSHAPE(16, 16) || QSHAPE(16, 19) || QSHAPE(16, 20) || QSHAPE(32, 10) || QSHAPE(32, 16) || QSHAPE(64, 16);
+#undef QSHAPE
+}
+int pmx_nwsgq_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, PmxTracePlan *p, int short_waves)
 {
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG) return 1;
     if (!b.q_shared || !pmx_nwsgv_bias(b, m, open, ext, 1)) return 1;
     if ((m.max > 0 ? m.max : 0) + 2 * open > 250) return 1;
     if (m.pssm && m.rows != b.q_shared) return 1;
-    for (int vo = 0; vo < 7; ++vo) {
-        const int v = kQShapeOrder[vo];
-        const int G = kQShapeG[v], R = kQShapeR[v];
-        if (b.q_shared > G * R - 1) continue;
-        if (R >= 19 && (short_waves || pmx_env("PMX_NWSGQ_NO_R20"))) continue;      // (short_waves: half the rows per lane = half the time per wave)
-        if (R == 19 && pmx_env("PMX_NWSGQ_NO_R19")) continue;
-        const size_t lds = (size_t)(m.msize + 1) * G * ((R + 3) / 4 * 4) + 8 + (m.pssm ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)(2 * (64 / G) * 4) * 24 +
-                           (size_t)4 * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4;
-        if (lds > 160 * 1024) continue;
-        const long long NP = 2 * (64 / G) * 4;
-        *variant = 30 + v; *G_out = G; *R_out = R;
-        *Tmax = (b.max_rlen + G - 1 + 1 + 15) & ~15;
-        *trace_bytes = (size_t)((b.n + NP - 1) / NP) * 4 * (size_t)*Tmax * 64 * (size_t)((R + 3) / 4) * 4;
-        return 0;
-    }
-    return 1;
+    return for_each_nwsgq_trace_shape([&](auto g, auto r, const char *, const char *) {
+        if (b.q_shared > g * r - 1) return false;
+        if (r >= 19 && (short_waves || pmx_env("PMX_NWSGQ_NO_R20"))) return false;      // (short_waves: half the rows per lane = half the time per wave)
+        if (r == 19 && pmx_env("PMX_NWSGQ_NO_R19")) return false;
+        if (nwsgq_lds(m, g, r, true) > 160 * 1024) return false;
+        *p = pmx_packed_trace_plan(PMX_TRACE_NWSG16Q, g, r, 4, b.max_rlen + g - 1 + 1, b.n);
+        return true;
+    }) ? 0 : 1;
 }
 
-// Pairs that are resident at once (workgroups per CU x CUs x pairs per workgroup) in the sweep `variant` would launch: waves of one
+// Pairs that are resident at once (workgroups per CU x CUs x pairs per workgroup) in the sweep the plan would launch: waves of one
 // launch over equally long references all take the same time, so a launch of N workgroups runs for ceil(N / resident) "rounds" --
 // the caller sizes its chunks in whole rounds (pmx_api.hip, stats_by_trace_shared).  0: unknown.
 template <int G, int R, bool ENDS>
@@ -1502,41 +1502,36 @@ static long long nwsgq_round_pairs(size_t lds)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, reinterpret_cast<const void *>(&pmx_nwsg16q_kernel<G, R, 4, true, ENDS>), 256, lds) != hipSuccess || nblk <= 0) return 0;
     return (long long)nblk * cus * (2 * (64 / G) * 4);
 }
-long long pmx_nwsgq_trace_round_pairs(int variant, const PmxDevMatrix &m, int mode, int sg_flags)
+long long pmx_nwsgq_trace_round_pairs(const PmxTracePlan &p, const PmxDevMatrix &m, int mode, int sg_flags)
 {
-    const int v = variant - 30;
-    if (v < 0 || v >= 7) return 0;
-    const int G = kQShapeG[v], R = kQShapeR[v];
-    const size_t lds = (size_t)(m.msize + 1) * G * ((R + 3) / 4 * 4) + 8 + (m.pssm ? 0 : (size_t)m.msize * m.msize * 2) + 256 + 8 + (size_t)(2 * (64 / G) * 4) * 24 +
-                       (size_t)4 * 64 * (PMX_QSTAGE * ((R + 3) / 4) + 1) * 4;
+    if (p.family != PMX_TRACE_NWSG16Q) return 0;
     const bool ends = mode == PMX_MODE_SG && (sg_flags & (PMX_SG_QE | PMX_SG_DE));
-    switch (v) {
-    case 0: return nwsgq_round_pairs<16, 10, true>(lds);
-    case 1: return nwsgq_round_pairs<16, 16, true>(lds);
-    case 2: return (ends || pmx_env("PMX_NWSGQ_ENDS_ALWAYS")) ? nwsgq_round_pairs<16, 20, true>(lds) : nwsgq_round_pairs<16, 20, false>(lds);
-    case 3: return nwsgq_round_pairs<32, 10, true>(lds);
-    case 4: return nwsgq_round_pairs<32, 16, true>(lds);
-    case 5: return nwsgq_round_pairs<64, 16, true>(lds);
-    case 6: return (ends || pmx_env("PMX_NWSGQ_ENDS_ALWAYS")) ? nwsgq_round_pairs<16, 19, true>(lds) : nwsgq_round_pairs<16, 19, false>(lds);
-    }
-    return 0;
+    long long pairs = 0;
+    for_each_nwsgq_trace_shape([&](auto g, auto r, const char *, const char *) {
+        if (g != p.G || r != p.R) return false;
+        const size_t lds = nwsgq_lds(m, g, r, true);
+        bool captures = true;                                // (false: the instance launch_nwsgq_form takes when no end is free)
+        if constexpr (r >= 19) captures = ends || pmx_env("PMX_NWSGQ_ENDS_ALWAYS");
+        if (captures) pairs = nwsgq_round_pairs<g, r, true>(lds);
+        else if constexpr (r >= 19) pairs = nwsgq_round_pairs<g, r, false>(lds);
+        return true;
+    });
+    return pairs;
 }
 
-int pmx_launch_nwsgq_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
-                           pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream)
+int pmx_launch_nwsgq_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
+                           pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream, const char **kernel_name)
 {
     const int nb = pmx_nwsgv_bias(b, m, open, ext, 1);
-    if (!nb) return 1;
-    switch (variant - 30) {
-    case 0: return launch_nwsgq<16, 10, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 1: return launch_nwsgq<16, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 2: return launch_nwsgq<16, 20, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 3: return launch_nwsgq<32, 10, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 4: return launch_nwsgq<32, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 5: return launch_nwsgq<64, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 6: return launch_nwsgq<16, 19, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    }
-    return 1;
+    if (!nb || p.family != PMX_TRACE_NWSG16Q) return 1;
+    int rc = 1;
+    for_each_nwsgq_trace_shape([&](auto g, auto r, const char *name, const char *pssm_name) {
+        if (g != p.G || r != p.R) return false;
+        rc = launch_nwsgq<g, r, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, p.Tmax);
+        if (rc == 0) *kernel_name = m.pssm ? pssm_name : name;
+        return true;
+    });
+    return rc;
 }
 
 // ------------------------------------------------------------------------ host side ----
@@ -1559,104 +1554,106 @@ static int launch_nwsg(const PmxBatch &b, const PmxDevMatrix &m, int mode, int s
     return pmx_launched();
 }
 
-static thread_local bool g_nwsgv_pt = false;          // the last launch_nwsgv of this thread ran the perm-table form first (kernel names)
-// the last per-pair packed-traceback sweep of this thread as it really launched (kernel names): /bfi = the one-instruction
-// bounded-difference decision merge (TRB), /shift = the three-instruction merge; /permtable = the perm-table form ran first
-const char *pmx_nwsg_trace_name()
-{
-    if (g_nwsg_trace_form == 2) return "pmx_nwsg16m_kernel/packed trace/shift";
-    if (g_nwsg_trace_form == 1) return g_nwsgv_pt ? "pmx_nwsg16v_kernel/packed trace/bfi/permtable (+ LDS profiles for marked blocks)" : "pmx_nwsg16v_kernel/packed trace/bfi";
-    return "pmx_nwsg16v_kernel/packed trace/shift";
-}
 // PTOK: the shape has a perm-table instantiation (the ones BASELINE-sized DNA batches take; every instantiation costs compile time)
 template <int G, int R, bool TR> struct NwsgPtShape {
     static constexpr bool value = (!TR && G == 8 && (R == 7 || R == 10 || R == 13 || R == 16 || R == 19 || R == 20)) || (G == 16 && R == 16) ||
                                   (!TR && G == 32 && R == 16);
 };
+// Dynamic LDS of pmx_nwsg16v_kernel<G, .>: the LDS-profile form -- 2 * (64 / G) byte profiles of G * RS rows and as many staged
+// references of ref_cols bytes (0: FETCH) -- and the perm-table form, which keeps score tables and selector streams instead of
+// profiles (TR: and stages its trace records).  Matrix, mapper and pair table in both.
+static size_t nwsgv_lds(int msize, int G, int RS, int ref_cols)
+{
+    const int NP = 2 * (64 / G);
+    return (size_t)NP * (msize + 1) * G * RS + (size_t)NP * ref_cols + (size_t)msize * msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES;
+}
+static size_t nwsgv_permtable_lds(int msize, int G, int R, int ref_cols, bool TR)
+{
+    const int NP = 2 * (64 / G);
+    return (size_t)NP * ref_cols + (size_t)msize * msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 160 + (size_t)NP * ((G * R + 3) / 4 * 4) + 32 +
+           (TR ? (size_t)64 * 33 * 4 : 0);
+}
+
+// what launch_nwsgv launched (kernel names): the trace form's one-instruction decision merge (TRB: /bfi, else /shift), the perm-table form first
+struct NwsgvRan { bool bfi = false, permtable = false; };
+
+// The perm-table form ahead of the LDS-profile form, where the shape has the instance and the batch allows it: alphabets of <= 4
+// letters (+ wildcard), per-pair queries, the caller's per-block flags (PmxBatch::blockflag).  It runs over every block with bias nb
+// and marks the blocks it leaves to the LDS-profile form; *only = those flags then, for that form's launch.  0, or a HIP error negated.
+template <int G, int R, bool TR, bool FETCH, bool TRB>
+static int nwsgv_permtable_first(const PmxBatch &b, const PmxDevMatrix &m, const PmxEnds &ends, int open, int ext, int RP, int nb, int track8,
+                                 long long blocks, pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf, int Tmax, const int **only)
+{
+    if constexpr (NwsgPtShape<G, R, TR>::value && !FETCH && (!TR || TRB)) {
+        if (m.msize > 5 || !b.blockflag || b.q_shared || pmx_env("PMX_NWSG16_NO_PERMTABLE")) return 0;
+        const size_t lds_pt = nwsgv_permtable_lds(m.msize, G, R, RP, TR);
+        // (more than the default 48 KB of dynamic LDS -- short queries against references of several kbp -- needs the opt-in; where the
+        //  staged references do not fit at all, or the opt-in fails, the LDS-profile form takes every block)
+        if (lds_pt > 160 * 1024 || (lds_pt > 48 * 1024 && pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>)) != 0)) return 0;
+        hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>), dim3((unsigned)blocks), dim3(64), lds_pt, stream,
+                           b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
+                           m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
+                           track8, b.blockflag, (const int *)nullptr);
+        const int rc = pmx_launched();
+        if (rc) return rc;
+        *only = b.blockflag;
+    }
+    return 0;
+}
 
 template <int G, int R, bool TR = false, bool FETCH = false, bool TRB = false>
 static int launch_nwsgv(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int nb,
-                        pmx_record_t *d_out, hipStream_t stream, uint32_t *tbuf = nullptr, int Tmax = 0)
+                        pmx_record_t *d_out, hipStream_t stream, NwsgvRan *ran, uint32_t *tbuf = nullptr, int Tmax = 0)
 {
     // the window proof once more with THIS shape's rows (round-3 advice: the estimate inside pmx_nwsgv_bias can be smaller than G * R)
     if (!b.track8 && !pmx_nwsgv_bias(b, m, open, ext, 1, G * R)) return 1;
     if (TR && !TRB && (m.max > 0 ? m.max : 0) + 2 * open <= 250 && !pmx_env("PMX_TRACE_NO_BFI"))     // bounded differences: the one-instruction merge
-        return launch_nwsgv<G, R, TR, FETCH, TR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    if (TR) g_nwsg_trace_form = TRB ? 1 : 0;
+        return launch_nwsgv<G, R, TR, FETCH, TR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, ran, tbuf, Tmax);
+    ran->bfi = TRB; ran->permtable = false;
     constexpr int RS = (R + 3) / 4 * 4, NP = 2 * (64 / G);
     const int RP = pmx_strip_ref_cols(b.max_rlen, G);
-    const size_t lds = (size_t)NP * (m.msize + 1) * G * RS + (FETCH ? 0 : (size_t)NP * RP) +
-                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES;
+    const size_t lds = nwsgv_lds(m.msize, G, RS, FETCH ? 0 : RP);
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB>)); if (rc) return rc; }
     const PmxEnds ends = pmx_ends(mode, sg_flags);
     const long long blocks = (b.n + NP - 1) / NP;
     if (blocks <= 0) return 0;
+    const int *only = nullptr;                              // the perm-table form ran first: the blocks it left
+    auto launch_profiles = [&](auto kernel, int track8) -> int {
+        ran->permtable = only != nullptr;
+        if (!only && b.blockflag) {                         // every block bottom-aligned: the walk reads the flags
+            const hipError_t e = hipMemsetAsync(b.blockflag, 0xFF, (size_t)blocks * sizeof(int), stream);
+            if (e != hipSuccess) return -(int)e;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), lds, stream,
+                           b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
+                           m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
+                           track8, (int *)nullptr, only);
+        return pmx_launched();
+    };
     if constexpr (!TR) {
         if (b.track8) {
             // width 8: the range of H decides the saturation flag.  Blocks whose pairs all saturate by a penalised boundary alone (most
             // reads: -(open + 62 extend) < -128 under 5 / 2) need no tracking: they run on the perm-table form with its row offset, at
             // width 16's speed; that launch marks the others, and the tracking form (no row offset: it compares H across rows in
             // every step) runs over exactly those.
-            const int *only8 = nullptr;
-            g_nwsgv_pt = false;
-            if constexpr (NwsgPtShape<G, R, TR>::value && !FETCH) {
-                const int nb_rowx = pmx_nwsgv_bias(b, m, open, ext, 1);      // (the caller's nb is the tracking form's: no row offset)
-                if (nb_rowx && m.msize <= 5 && b.blockflag && !b.q_shared && (ends.col_pen || ends.row_pen) && !pmx_env("PMX_NWSG16_NO_PERMTABLE")) {
-                    const size_t lds_pt = (size_t)NP * RP + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 160 + (size_t)NP * ((G * R + 3) / 4 * 4) + 32;
-                  if (lds_pt <= 160 * 1024 && (lds_pt <= 48 * 1024 || pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>)) == 0)) {
-                    hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>), dim3((unsigned)blocks), dim3(64), lds_pt, stream,
-                                       b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                                       m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb_rowx, b.perm, d_out, tbuf, Tmax,
-                                       1, b.blockflag, (const int *)nullptr);
-                    const hipError_t e = hipGetLastError();
-                    if (e != hipSuccess) return -(int)e;
-                    only8 = b.blockflag;
-                    g_nwsgv_pt = true;
-                  }       // (else: the staged references do not fit beside the tables -- the LDS-profile form takes every block)
-                }
+            const int nb_rowx = (ends.col_pen || ends.row_pen) ? pmx_nwsgv_bias(b, m, open, ext, 1) : 0;      // (the caller's nb is the tracking form's: no row offset)
+            if (nb_rowx) {
+                const int rc = nwsgv_permtable_first<G, R, TR, FETCH, TRB>(b, m, ends, open, ext, RP, nb_rowx, 1, blocks, d_out, stream, tbuf, Tmax, &only);
+                if (rc) return rc;
             }
             { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB, false, false>)); if (rc) return rc; }
-            if (!only8 && b.blockflag) { const hipError_t e = hipMemsetAsync(b.blockflag, 0xFF, (size_t)blocks * sizeof(int), stream); if (e != hipSuccess) return -(int)e; }
-            hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB, false, false>), dim3((unsigned)blocks), dim3(64), lds, stream,
-                               b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                               m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
-                               b.track8, (int *)nullptr, only8);
-            return pmx_launched();
+            return launch_profiles(&pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB, false, false>, b.track8);
         }
     }
     // Alphabets of <= 4 letters (+ wildcard): the perm-table form first (no LDS profile: see PT at the kernel); it marks the blocks
     // it cannot take -- query lengths that differ inside the block, a query letter beyond the first four -- and the LDS-profile form
-    // below then runs over exactly those.  Needs the caller's per-block flags (PmxBatch::blockflag).
-    const int *only = nullptr;
-    g_nwsgv_pt = false;
-    if constexpr (NwsgPtShape<G, R, TR>::value && !FETCH && (!TR || TRB)) {
-        if (m.msize <= 5 && b.blockflag && !b.track8 && !b.q_shared && !pmx_env("PMX_NWSG16_NO_PERMTABLE")) {
-            const size_t lds_pt = (size_t)NP * RP + (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 160 + (size_t)NP * ((G * R + 3) / 4 * 4) + 32 +
-                                  (TR ? (size_t)64 * 33 * 4 : 0);
-            // (more than the default 48 KB of dynamic LDS -- short queries against references of several kbp -- needs the opt-in; where the
-            //  staged references do not fit at all, or the opt-in fails, the LDS-profile form below takes every block)
-            if (lds_pt <= 160 * 1024 && (lds_pt <= 48 * 1024 || pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>)) == 0)) {
-                hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, false, TRB, true>), dim3((unsigned)blocks), dim3(64), lds_pt, stream,
-                                   b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                                   m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
-                                   0, b.blockflag, (const int *)nullptr);
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) return -(int)e;
-                only = b.blockflag;
-                g_nwsgv_pt = true;
-            }
-        }
+    // then runs over exactly those.
+    if (!b.track8) {
+        const int rc = nwsgv_permtable_first<G, R, TR, FETCH, TRB>(b, m, ends, open, ext, RP, nb, 0, blocks, d_out, stream, tbuf, Tmax, &only);
+        if (rc) return rc;
     }
-    if (!only && b.blockflag) {                             // every block bottom-aligned: the walk reads the flags
-        const hipError_t e = hipMemsetAsync(b.blockflag, 0xFF, (size_t)blocks * sizeof(int), stream);
-        if (e != hipSuccess) return -(int)e;
-    }
-    hipLaunchKernelGGL((pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB>), dim3((unsigned)blocks), dim3(64), lds, stream,
-                       b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.scores, m.mapper,
-                       m.msize, open, ext, RP, b.q_shared, ends.col_pen, ends.row_pen, ends.s1_end, ends.s2_end, nb, b.perm, d_out, tbuf, Tmax,
-                       0, (int *)nullptr, only);
-    return pmx_launched();
+    return launch_profiles(&pmx_nwsg16v_kernel<G, R, TR, FETCH, TRB>, 0);
 }
 
 // Second-generation eligibility: the profile byte score + open must fit, and the proven value range plus
@@ -1704,51 +1701,50 @@ extern "C" int pmx_window_nwsgv(int max_qlen, int max_rlen, int msize, int score
 
 // Traceback variant (global / semi-global): shapes with 16 rows per lane.  Trace layout: per block
 // Tmax steps x 64 lanes x 16 bytes.
-int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
-                         int *variant, int *Tmax, size_t *trace_bytes)
+int pmx_nwsgv_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, PmxTracePlan *p)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (mode != PMX_MODE_NW && mode != PMX_MODE_SG) return 1;
     if (b.q_shared || b.perm || !pmx_nwsgv_bias(b, m, open, ext, 1)) return 1;
-    if (m.msize > 8 && m.msize < 32 && !pmx_env("PMX_NWSG16_NO_MATRIX_LOOKUP")) {   // large alphabet: the matrix-lookup kernel (1 KB of LDS)
-        int G = 0;
-        for (int v = 1; v < 4 && !G; ++v) if (b.max_qlen <= (8 << v) * 16 - 1) { *variant = 4 + v; G = 8 << v; }
-        if (!G) return 1;
-        *Tmax = (b.max_rlen + G - 1 + 1 + 15) & ~15;    // multiple of 16: the walk reads a lane's records in windows of 16
-        *trace_bytes = (size_t)((b.n + 2 * (64 / G) - 1) / (2 * (64 / G))) * (size_t)*Tmax * 64 * 16;
-        return 0;
-    }
+    const bool lookup = m.msize > 8 && m.msize < 32 && !pmx_env("PMX_NWSG16_NO_MATRIX_LOOKUP");   // large alphabet: the matrix-lookup kernel (1 KB of LDS)
     int G = 0;
-    for (int v = 0; v < 4 && !G; ++v) {                  // the first shape that holds the query and fits the LDS (launch_nwsgv's condition)
-        const int g = 8 << v, np = 2 * (64 / g);
-        const size_t lds = (size_t)np * (m.msize + 1) * g * 16 + (size_t)np * (b.max_rlen + 2 * g + 12) +
-                           (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)np * PMX_PAIRTAB_BYTES;
-        if (b.max_qlen <= g * 16 - 1 && lds <= 160 * 1024) { *variant = v; G = g; }
-    }
+    if (lookup) pmx_for_each_trace_group<16>([&](auto g) { if (b.max_qlen > g * 16 - 1) return false; G = g; return true; });
+    else pmx_for_each_trace_group<8>([&](auto g) {       // the first shape that holds the query and fits the LDS: launch_nwsgv's condition
+        if (b.max_qlen > g * 16 - 1 || nwsgv_lds(m.msize, g, 16, pmx_strip_ref_cols_plan(b.max_rlen, g)) > 160 * 1024) return false;
+        G = g; return true;
+    });
     if (!G) return 1;
-    const int NP = 2 * (64 / G);
-    *Tmax = (b.max_rlen + G - 1 + 1 + 15) & ~15;    // multiple of 16: the walk reads a lane's records in windows of 16
-    *trace_bytes = (size_t)((b.n + NP - 1) / NP) * (size_t)*Tmax * 64 * 16;
+    *p = pmx_packed_trace_plan(lookup ? PMX_TRACE_NWSG16M : PMX_TRACE_NWSG16V, G, 16, 1, b.max_rlen + G - 1 + 1, b.n);
     return 0;
 }
 
-int pmx_launch_nwsgv_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
-                           pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream)
+int pmx_launch_nwsgv_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
+                           pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream, const char **kernel_name)
 {
-    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
+    if (m.pssm || p.R != 16) return 1;                      // (symbol profiles only: a PSSM takes the general kernel)
     const int nb = pmx_nwsgv_bias(b, m, open, ext, 1);
     if (!nb) return 1;
-    switch (variant) {
-    case 5: return launch_nwsgm<16, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 6: return launch_nwsgm<32, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 7: return launch_nwsgm<64, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 0: return launch_nwsgv<8, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 1: if (pmx_env("PMX_TRACE_FETCH")) return launch_nwsgv<16, 16, true, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-            return launch_nwsgv<16, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 2: return launch_nwsgv<32, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
-    case 3: return launch_nwsgv<64, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, Tmax);
+    int rc = 1;
+    if (p.family == PMX_TRACE_NWSG16M) {
+        pmx_for_each_trace_group<16>([&](auto g) {
+            if (g != p.G) return false;
+            rc = launch_nwsgm<g, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, tbuf, p.Tmax);
+            return true;
+        });
+        if (rc == 0) *kernel_name = "pmx_nwsg16m_kernel/packed trace/shift";
+        return rc;
     }
-    return 1;
+    if (p.family != PMX_TRACE_NWSG16V) return 1;
+    NwsgvRan ran;
+    pmx_for_each_trace_group<8>([&](auto g) {
+        if (g != p.G) return false;
+        if constexpr (g == 16) if (pmx_env("PMX_TRACE_FETCH")) { rc = launch_nwsgv<16, 16, true, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, &ran, tbuf, p.Tmax); return true; }
+        rc = launch_nwsgv<g, 16, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, &ran, tbuf, p.Tmax);
+        return true;
+    });
+    if (rc == 0) *kernel_name = !ran.bfi ? "pmx_nwsg16v_kernel/packed trace/shift"
+                              : ran.permtable ? "pmx_nwsg16v_kernel/packed trace/bfi/permtable (+ LDS profiles for marked blocks)" : "pmx_nwsg16v_kernel/packed trace/bfi";
+    return rc;
 }
 
 // 0 launched, 1 not eligible (caller uses the general kernel), <0 HIP error
@@ -1795,11 +1791,12 @@ int pmx_launch_nwsg16(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg
 #undef TRYM
         }
         const bool longref = b.max_rlen >= 1024 && !pmx_env("PMX_NWSG16_NO_FETCH");   // staged references would dominate the LDS
+        NwsgvRan ran;
 #define TRYV(GG, RR, NAME)                                                      \
         if (q <= (GG) * (RR)) {                                             \
-            int rc = longref ? launch_nwsgv<GG, RR, false, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream) \
-                             : launch_nwsgv<GG, RR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream); \
-            if (rc <= 0) { if (kernel_name) *kernel_name = longref ? NAME "/fetch" : g_nwsgv_pt ? NAME "/permtable (+ LDS profiles for marked blocks)" : NAME; return rc; }   \
+            int rc = longref ? launch_nwsgv<GG, RR, false, true>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, &ran) \
+                             : launch_nwsgv<GG, RR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, &ran); \
+            if (rc <= 0) { if (kernel_name) *kernel_name = longref ? NAME "/fetch" : ran.permtable ? NAME "/permtable (+ LDS profiles for marked blocks)" : NAME; return rc; }   \
         }
         if (b.n > 2048) {       // (few pairs: latency counts, the 16-lane shapes have half the work per step)
             TRYV(8, 7, "pmx_nwsg16v_kernel<8,7>")        // reads of 50 / 75 / 100 / 125 / 150 bp: few padding rows
@@ -1813,7 +1810,7 @@ int pmx_launch_nwsg16(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg
         // (pmx_sw16.hip has the same ladder)
 #define TRYLAT(RR)                                                              \
         if (!longref && b.n <= 64 && q <= 64 * (RR) - 1) {                      \
-            const int rc = launch_nwsgv<64, RR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream); \
+            const int rc = launch_nwsgv<64, RR>(b, m, mode, sg_flags, open, ext, nb, d_out, stream, &ran); \
             if (rc <= 0) { if (kernel_name) *kernel_name = "pmx_nwsg16v_kernel<64," #RR ">"; return rc; } \
         }
         TRYLAT(2) TRYLAT(3) TRYLAT(4) TRYLAT(8)

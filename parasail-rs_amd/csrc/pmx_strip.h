@@ -126,3 +126,6 @@ __host__ __device__ static inline PmxEnds pmx_ends(int mode, int sg_flags)
 
 // bytes of a staged reference row: the virtual columns in front, the pad and the two-step read-ahead behind
 static inline int pmx_strip_ref_cols(int max_rlen, int G) { return ((max_rlen + 2 * (G - 1) + 4 + 7) / 4) * 4; }
+// The width the trace planners put into their launchers' LDS sums: pmx_strip_ref_cols() plus a margin of 3 to 6 bytes, so a plan at
+// the 160 KiB edge moves to the next shape a few reference bytes before its launcher would have to refuse.
+static inline int pmx_strip_ref_cols_plan(int max_rlen, int G) { return max_rlen + 2 * G + 12; }

@@ -635,6 +635,14 @@ void pmx_sw16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict
 
 // ------------------------------------------------------------------------ host side ----
 
+// Dynamic LDS of the forms with an LDS profile: 2 * (64 / G) profiles of QP rows of EB bytes and a pad row, as many staged references
+// of ref_cols bytes (0: fetched from HBM), matrix, mapper, pair table.
+static size_t sw16_profile_lds(int msize, int G, int QP, int EB, int ref_cols)
+{
+    const int NP = 2 * (64 / G);
+    return (size_t)NP * msize * QP * EB + (size_t)QP * EB + (size_t)NP * ref_cols + (size_t)msize * msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 32;
+}
+
 template <int G, int R, int VAR>
 static int launch_one(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
                       pmx_record_t *d_out, hipStream_t stream, const int *n_dev = nullptr, uint32_t *tbuf = nullptr, int Tmax = 0)
@@ -644,8 +652,9 @@ static int launch_one(const PmxBatch &b, const PmxDevMatrix &m, int open, int ex
     constexpr int QP = G * RS, NP = 2 * (64 / G);
     if (NP * m.msize > 255) return 1;                 // per-pair pad symbol must fit a byte
     const int RP = pmx_strip_ref_cols(b.max_rlen, G);
-    const size_t lds = (PT ? (size_t)256 + 4 * (64 / G) + 4 * (4 * (RS / 4 - 1) + R + 1) : (size_t)NP * m.msize * QP * EB + (size_t)QP * EB) + (VAR == 8 ? 0 : (size_t)NP * RP) +
-                       (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 32;
+    const size_t lds = PT ? (size_t)256 + 4 * (64 / G) + 4 * (4 * (RS / 4 - 1) + R + 1) + (size_t)NP * RP +
+                            (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)NP * PMX_PAIRTAB_BYTES + 32
+                          : sw16_profile_lds(m.msize, G, QP, EB, VAR == 8 ? 0 : RP);
     if (lds > 160 * 1024) return 1;
     { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_sw16_kernel<G, R, VAR>)); if (rc) return rc; }
     long long blocks = (b.n + NP - 1) / NP;
@@ -683,44 +692,37 @@ static bool sw16_trace_ok(const PmxBatch &b, const PmxDevMatrix &m, int open, in
     const long long feasible = (long long)(b.max_qlen < b.max_rlen ? b.max_qlen : b.max_rlen) * (m.max > 0 ? m.max : 0);
     return feasible + PK16_SW_BIAS < (long long)PK16_RERUN_LIMIT(m.max) - (long long)(b.max_rlen + 2 * 64 + 4) * ext;
 }
-int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, int *variant, int *Tmax, size_t *trace_bytes)
+int pmx_sw16_trace_plan(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext, PmxTracePlan *p)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (!sw16_trace_ok(b, m, open, ext)) return 1;
-    if (m.msize > 8 && m.msize < 32 && !pmx_env("PMX_SW16_NO_MATRIX_LOOKUP")) {     // large alphabet: the matrix-lookup kernel (no profile, 1 KB of LDS)
-        int G = 0;
-        for (int v = 1; v < 4 && !G; ++v) if (b.max_qlen <= (8 << v) * 16) { *variant = 4 + v; G = 8 << v; }
-        if (!G) return 1;
-        *Tmax = (b.max_rlen + G - 1 + 1 + 15) & ~15;    // that kernel sweeps an even number of steps; the walk reads windows of 16
-        *trace_bytes = (size_t)((b.n + 2 * (64 / G) - 1) / (2 * (64 / G))) * (size_t)*Tmax * 64 * 16;
-        return 0;
-    }
+    const bool lookup = m.msize > 8 && m.msize < 32 && !pmx_env("PMX_SW16_NO_MATRIX_LOOKUP");     // large alphabet: the matrix-lookup kernel (no profile, 1 KB of LDS)
     int G = 0;
-    for (int v = 0; v < 4 && !G; ++v) {                  // the first shape that holds the query, whose per-pair pad symbols fit a
-        const int g = 8 << v, np = 2 * (64 / g);         // byte and whose profiles fit the LDS (the launcher's own conditions)
-        const size_t lds = (size_t)np * m.msize * g * 16 + (size_t)g * 16 + (size_t)np * (b.max_rlen + 2 * g + 12) +
-                           (size_t)m.msize * m.msize * 2 + 256 + 8 + (size_t)np * PMX_PAIRTAB_BYTES + 32;
-        if (b.max_qlen <= g * 16 && np * m.msize <= 255 && lds <= 160 * 1024) { *variant = v; G = g; }
-    }
+    if (lookup) pmx_for_each_trace_group<16>([&](auto g) { if (b.max_qlen > g * 16) return false; G = g; return true; });
+    else pmx_for_each_trace_group<8>([&](auto g) {       // the first shape that holds the query, whose per-pair pad symbols fit a byte and
+        if (b.max_qlen > g * 16 || 2 * (64 / g) * m.msize > 255 ||                       // whose profiles fit the LDS: launch_one's conditions
+            sw16_profile_lds(m.msize, g, g * 16, 1, pmx_strip_ref_cols_plan(b.max_rlen, g)) > 160 * 1024) return false;
+        G = g; return true;
+    });
     if (!G) return 1;
-    const int NP = 2 * (64 / G);
-    *Tmax = (b.max_rlen + G - 1 + 15) & ~15;        // multiple of 16: the walk reads a lane's records in windows of 16
-    *trace_bytes = (size_t)((b.n + NP - 1) / NP) * (size_t)*Tmax * 64 * 16;
+    *p = pmx_packed_trace_plan(lookup ? PMX_TRACE_SW16M : PMX_TRACE_SW16, G, 16, 1, b.max_rlen + G - 1 + (lookup ? 1 : 0) /* that kernel sweeps an even number of steps */, b.n);
     return 0;
 }
-int pmx_launch_sw16_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
-                          pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream)
+int pmx_launch_sw16_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
+                          pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream, const char **kernel_name)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (!sw16_trace_ok(b, m, open, ext)) return 1;
-    if (variant >= 4) return pmx_launch_sw16m_trace(variant - 4, b, m, open, ext, d_out, tbuf, Tmax, stream);
-    switch (variant) {
-    case 0: return launch_one<8, 16, 7>(b, m, open, ext, d_out, stream, nullptr, tbuf, Tmax);
-    case 1: return launch_one<16, 16, 7>(b, m, open, ext, d_out, stream, nullptr, tbuf, Tmax);
-    case 2: return launch_one<32, 16, 7>(b, m, open, ext, d_out, stream, nullptr, tbuf, Tmax);
-    case 3: return launch_one<64, 16, 7>(b, m, open, ext, d_out, stream, nullptr, tbuf, Tmax);
-    }
-    return 1;
+    int rc = 1;
+    if (p.family == PMX_TRACE_SW16M) rc = pmx_launch_sw16m_trace(p, b, m, open, ext, d_out, tbuf, stream);
+    else if (p.family == PMX_TRACE_SW16 && p.R == 16)
+        pmx_for_each_trace_group<8>([&](auto g) {
+            if (g != p.G) return false;
+            rc = launch_one<g, 16, 7>(b, m, open, ext, d_out, stream, nullptr, tbuf, p.Tmax);
+            return true;
+        });
+    if (rc == 0) *kernel_name = "pmx_sw16_kernel/packed trace";      // (the local road's one name, the matrix-lookup sweep included)
+    return rc;
 }
 
 int pmx_launch_sw16(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,

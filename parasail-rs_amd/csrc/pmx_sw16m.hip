@@ -238,17 +238,18 @@ static int launch_m(const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
     return pmx_launched();
 }
 
-// traceback variant, lane groups of 16 / 32 / 64 (variant 1..3 of pmx_sw16_trace_plan)
-int pmx_launch_sw16m_trace(int variant, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
-                           pmx_record_t *d_out, uint32_t *tbuf, int Tmax, hipStream_t stream)
+// traceback variant, lane groups of 16 / 32 / 64 (family PMX_TRACE_SW16M of pmx_sw16_trace_plan)
+int pmx_launch_sw16m_trace(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int open, int ext,
+                           pmx_record_t *d_out, uint32_t *tbuf, hipStream_t stream)
 {
-    if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
-    switch (variant) {
-    case 1: return launch_m<16, 16, true>(b, m, open, ext, d_out, stream, tbuf, Tmax);
-    case 2: return launch_m<32, 16, true>(b, m, open, ext, d_out, stream, tbuf, Tmax);
-    case 3: return launch_m<64, 16, true>(b, m, open, ext, d_out, stream, tbuf, Tmax);
-    }
-    return 1;
+    if (m.pssm || p.R != 16) return 1;                      // (symbol profiles only: a PSSM takes the general kernel)
+    int rc = 1;
+    pmx_for_each_trace_group<16>([&](auto g) {
+        if (g != p.G) return false;
+        rc = launch_m<g, 16, true>(b, m, open, ext, d_out, stream, tbuf, p.Tmax);
+        return true;
+    });
+    return rc;
 }
 
 // 0 launched, 1 not eligible (the caller goes on with pmx_sw16's own variants), <0 HIP error.

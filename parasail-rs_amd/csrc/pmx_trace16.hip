@@ -257,12 +257,11 @@ void pmx_trace16_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restr
 }
 
 // ---- walk over the 4-bit trace ---------------------------------------------------------------
-// PACKED: the layout written by pmx_nwsg16v_kernel<G,16,true> (two pairs per slot, 16 bytes per lane and step).
-template <int G, int R, bool PACKED>
+// (the first-generation layout only: the packed sweeps' records are walked by pmx_walkp.hip)
+template <int G, int R>
 __global__ void pmx_walk16_kernel(const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff,
                                   long long n, const uint8_t *mapper, const int16_t *scores, int msize, int open, int ext,
                                   int mode, int Tmax, int stage /* LDS bytes reserved for each of the block's queries / references, 0 = none */,
-                                  int top_aligned /* query rows start at the first lane's first register (local kernel) */,
                                   pmx_stats_t *stats_out /* != nullptr: count matches / similar / length along the path instead of emitting ops */,
                                   int row_pen, int col_pen /* stats: the begin gaps along the reference / query are part of the alignment */,
                                   const uint32_t *tbuf, const pmx_record_t *recs,
@@ -270,7 +269,7 @@ __global__ void pmx_walk16_kernel(const uint8_t *qbuf, const int64_t *qoff, cons
                                   long long ops_base, int32_t *nops, int32_t *beg, int32_t *textlen /* optional: bytes of the CIGAR text */)
 {
     extern __shared__ unsigned char w_lds[];
-    constexpr int QP = G * R, NP = (PACKED ? 2 : 1) * (64 / G), TW = PACKED ? 4 : R / 8;
+    constexpr int QP = G * R, NP = 64 / G, TW = R / 8;
     // mapper and matrix in LDS: the walk is a chain of dependent loads, keep all but the trace fetch short
     __shared__ unsigned char s_map[256];
     __shared__ int16_t s_scores[PMX_MAX_FAST_MSIZE * PMX_MAX_FAST_MSIZE];
@@ -294,38 +293,17 @@ __global__ void pmx_walk16_kernel(const uint8_t *qbuf, const int64_t *qoff, cons
     const uint8_t *q = qbuf + qb, *r = rbuf + rb;
     const unsigned char *sq = w_lds + (qb - qlo), *sr = w_lds + stage + (rb - rlo);
     const long long block = pair / NP; const int slot = (int)(pair % NP);
-    // PACKED: records of 16 bytes per lane and step, lane-major (a lane's steps are contiguous): [A rows 0-7][A rows 8-15][B rows 0-7]
-    // [B rows 8-15], byte = a row pair, the even row in the high nibble.  A walk moves along a row or a diagonal, i.e. down one
-    // lane's steps: the lane keeps a window of 8 consecutive records (one 128-byte line of that stream) in LDS and goes back to
-    // memory only when the path leaves it.  Unpacked (first generation): R / 8 words per lane and step, step-major.
+    // R / 8 words per lane and step, step-major
     const uint32_t *tb = tbuf + (size_t)block * Tmax * (64 * TW);
-    const int P = top_aligned ? 0 : QP - ql;
-    __shared__ uint4 s_win[PACKED ? 64 * 8 : 1];
-    int w_stream = -1, w_t0 = -1;
+    const int P = QP - ql;
     auto ldw = [&](int i, int j) -> uint32_t {         // the trace word holding cell (i, j); 0 outside i >= -1, j >= 0
         if (i < -1 || j < 0) return 0u;
         const int er = i + P;
         if (er < 0) return 0u;
         const int g = er / R, k = er % R;
-        if (!PACKED) return tb[(size_t)(j + g) * (64 * TW) + (slot * G + g) * TW + (k / 8)];
-        const int stream = (slot >> 1) * G + g, t = j + g, t0 = t & ~7;
-        const int lx = threadIdx.x;
-        if (stream != w_stream || t0 != w_t0) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(tb + ((size_t)stream * Tmax + t0) * 4);
-            uint4 v[8];
-#pragma unroll
-            for (int x = 0; x < 8; ++x) v[x] = src[x];
-#pragma unroll
-            for (int x = 0; x < 8; ++x) s_win[lx * 8 + ((x ^ lx) & 7)] = v[x];
-            w_stream = stream; w_t0 = t0;
-        }
-        const uint32_t *rec4 = reinterpret_cast<const uint32_t *>(&s_win[lx * 8 + (((t & 7) ^ lx) & 7)]);
-        return rec4[(slot & 1) * 2 + (k / 8)];
+        return tb[(size_t)(j + g) * (64 * TW) + (slot * G + g) * TW + (k / 8)];
     };
-    auto nibof = [&](uint32_t w, int i) -> unsigned {
-        const int k8 = ((i + P) % R) % 8;
-        return PACKED ? (w >> (8 * (k8 >> 1) + ((k8 & 1) ? 0 : 4))) & 0xFu : (w >> (28 - 4 * k8)) & 0xFu;
-    };
+    auto nibof = [&](uint32_t w, int i) -> unsigned { return (w >> (28 - 4 * (((i + P) % R) % 8))) & 0xFu; };
     auto nib = [&](int i, int j) -> unsigned { return nibof(ldw(i, j), i); };
     const bool st = stats_out != nullptr;
     uint32_t *o = st ? nullptr : ops + (ops_off ? ops_off[pair] : qb + rb + pair - ops_base);
@@ -388,6 +366,13 @@ static int walk_stage_bytes(const PmxBatch &b)
     return (m <= 60 * 1024) ? (int)((m + 15) / 16 * 16) : 0;
 }
 
+// The first-generation shapes in try order: f(G, R) as integral constants until one returns true.
+template <typename F> static bool for_each_gen1_shape(F &&f)
+{
+    using std::integral_constant;
+    return f(integral_constant<int, 32>{}, integral_constant<int, 8>{}) || f(integral_constant<int, 64>{}, integral_constant<int, 8>{}) || f(integral_constant<int, 64>{}, integral_constant<int, 16>{});
+}
+
 template <int G, int R, bool SW>
 static int launch_trace(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
                         pmx_record_t *d_out, uint32_t *tbuf, int Tmax,
@@ -407,17 +392,15 @@ static int launch_trace(const PmxBatch &b, const PmxDevMatrix &m, int mode, int 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return -(int)e;
     const int stage = walk_stage_bytes(b);
-    { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_walk16_kernel<G, R, false>), 128 * 1024); if (rc) return rc; }
-    hipLaunchKernelGGL((pmx_walk16_kernel<G, R, false>), dim3((unsigned)((b.n + 63) / 64)), dim3(64), 2 * (size_t)stage, stream,
-                       b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.mapper, m.scores, m.msize, open, ext, mode, Tmax, stage, 0, stats_out, ends.row_pen, ends.col_pen,
+    { const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_walk16_kernel<G, R>), 128 * 1024); if (rc) return rc; }
+    hipLaunchKernelGGL((pmx_walk16_kernel<G, R>), dim3((unsigned)((b.n + 63) / 64)), dim3(64), 2 * (size_t)stage, stream,
+                       b.qbuf, b.qoff, b.rbuf, b.roff, (long long)b.n, m.mapper, m.scores, m.msize, open, ext, mode, Tmax, stage, stats_out, ends.row_pen, ends.col_pen,
                        (const uint32_t *)tbuf, (const pmx_record_t *)d_out, ops, ops_off, 0LL, nops, beg, (int32_t *)nullptr);
     return pmx_launched();
 }
 
-// Picks the instantiation; *trace_bytes / *Tmax tell the caller how much trace scratch to provide
-// (call once with tbuf == nullptr to size it).  Returns 1 when the batch is not eligible.
-int pmx_trace16_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext,
-                     int *variant, int *Tmax, size_t *trace_bytes, bool packed_ok)
+// Picks the sweep; p->trace_bytes tells the caller how much trace scratch to provide.  Returns 1 when the batch is not eligible.
+int pmx_trace16_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, PmxTracePlan *p, bool packed_ok)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     if (pmx_env("PMX_NO_FAST_TRACE")) return 1;
@@ -425,43 +408,46 @@ int pmx_trace16_plan(const PmxBatch &b, const PmxDevMatrix &m, int mode, int ope
     if (m.msize > PMX_MAX_FAST_MSIZE - 1) return 1;
     if (open < ext || open < 0 || ext < 0 || open > 4096) return 1;
     if (b.max_rlen > 30000 || b.q_shared) return 1;
-    if (packed_ok && !pmx_env("PMX_TRACE16_GEN1") && pmx_nwsgv_trace_plan(b, m, mode, open, ext, variant, Tmax, trace_bytes) == 0) {
-        *variant += 10;            // packed traceback of the second-generation nw/sg kernel
-        return 0;
-    }
-    if (packed_ok && mode == PMX_MODE_SW && pmx_sw16_trace_plan(b, m, open, ext, variant, Tmax, trace_bytes) == 0) {
-        *variant += 20;            // packed traceback of the local kernel
-        return 0;
-    }
+    // packed traceback of the second-generation nw/sg kernel, of the local kernel
+    if (packed_ok && !pmx_env("PMX_TRACE16_GEN1") && pmx_nwsgv_trace_plan(b, m, mode, open, ext, p) == 0) return 0;
+    if (packed_ok && mode == PMX_MODE_SW && pmx_sw16_trace_plan(b, m, open, ext, p) == 0) return 0;
     const long long lo = mode == PMX_MODE_SW ? -(2LL * open + 2LL * ext + (m.min < 0 ? -m.min : 0))
                                              : -(3LL * open + (long long)(b.max_qlen + b.max_rlen + 2) * ext + (m.min < 0 ? -m.min : 0));
     const long long hi = (long long)(b.max_qlen < b.max_rlen ? b.max_qlen : b.max_rlen) * (m.max > 0 ? m.max : 0) + (m.max > 0 ? m.max : 0);
     if (lo < -15000 || hi > 15000) return 1;
-    int G, R;
-    if (b.max_qlen <= 32 * 8 - 1) { *variant = 0; G = 32; R = 8; }
-    else if (b.max_qlen <= 64 * 8 - 1) { *variant = 1; G = 64; R = 8; }
-    else if (b.max_qlen <= 64 * 16 - 1) { *variant = 2; G = 64; R = 16; }
-    else return 1;
-    const int NP = 64 / G;
-    *Tmax = (b.max_rlen + G - 1 + 1) & ~1;
-    const long long blocks = (b.n + NP - 1) / NP;
-    *trace_bytes = (size_t)blocks * (size_t)*Tmax * 64 * (R / 8) * sizeof(uint32_t);
+    int G = 0, R = 0;
+    for_each_gen1_shape([&](auto g, auto r) { if (b.max_qlen > g * r - 1) return false; G = g; R = r; return true; });
+    if (!G) return 1;
+    p->family = PMX_TRACE_GEN1; p->G = G; p->R = R; p->pairs_per_wg = 64 / G;
+    p->Tmax = (b.max_rlen + G - 1 + 1) & ~1;
+    p->trace_bytes = (size_t)((b.n + p->pairs_per_wg - 1) / p->pairs_per_wg) * (size_t)p->Tmax * 64 * (R / 8) * sizeof(uint32_t);
+    p->top_aligned = false; p->fills_blockflag = false; p->walk = PMX_TRACE_WALK16;
     return 0;
 }
 
-int pmx_launch_trace16(int variant, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
-                       pmx_record_t *d_out, uint32_t *tbuf, int Tmax,
-                       uint32_t *ops, const int64_t *ops_off, int32_t *nops, int32_t *beg, hipStream_t stream, pmx_stats_t *stats_out,
-                       const PmxWalkSplit *split)
+extern "C" int pmx_trace_plan_probe(int mode, int msize, int score_min, int score_max, int pssm, int open, int ext, long long n,
+                                    int max_qlen, int max_rlen, int q_shared, int short_waves, int packed_ok,
+                                    int *family, int *G, int *R, int *Tmax, long long *trace_bytes)
+{
+    PmxBatch b = {}; PmxDevMatrix m = {}; PmxTracePlan p = {};
+    b.n = n; b.max_qlen = max_qlen; b.max_rlen = max_rlen; b.q_shared = q_shared;
+    m.msize = msize; m.min = score_min; m.max = score_max; m.pssm = pssm; m.rows = pssm ? (q_shared ? q_shared : max_qlen) : msize;
+    const int rc = q_shared ? pmx_nwsgq_trace_plan(b, m, mode, open, ext, &p, short_waves) : pmx_trace16_plan(b, m, mode, open, ext, &p, packed_ok != 0);
+    if (rc) p = PmxTracePlan();
+    *family = (int)p.family; *G = p.G; *R = p.R; *Tmax = p.Tmax; *trace_bytes = (long long)p.trace_bytes;
+    return rc;
+}
+
+int pmx_launch_trace16(const PmxTracePlan &p, const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext,
+                       pmx_record_t *d_out, uint32_t *tbuf, uint32_t *ops, const int64_t *ops_off, int32_t *nops, int32_t *beg, hipStream_t stream,
+                       const char **sweep_name, pmx_stats_t *stats_out, const PmxWalkSplit *split)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
     const bool sw = mode == PMX_MODE_SW;
     const PmxEnds ends = pmx_ends(mode, sg_flags);
-    if (variant >= 10) {
-        const int top = variant >= 20 ? 1 : 0;
-        // (Tmax is a multiple of 16 -- the plans round it -- so a walk window never crosses into the next lane's stream)
-        int rc = top ? pmx_launch_sw16_trace(variant - 20, b, m, open, ext, d_out, tbuf, Tmax, stream)
-                     : pmx_launch_nwsgv_trace(variant - 10, b, m, mode, sg_flags, open, ext, d_out, tbuf, Tmax, stream);
+    if (p.walk == PMX_TRACE_WALKP) {
+        int rc = p.top_aligned ? pmx_launch_sw16_trace(p, b, m, open, ext, d_out, tbuf, stream, sweep_name)
+                               : pmx_launch_nwsgv_trace(p, b, m, mode, sg_flags, open, ext, d_out, tbuf, stream, sweep_name);
         if (rc) return rc;
         hipStream_t wstream = stream;
         if (split && split->walk_stream != stream) {      // the walk runs beside the next chunk's sweep
@@ -472,23 +458,22 @@ int pmx_launch_trace16(int variant, const PmxBatch &b, const PmxDevMatrix &m, in
         }
         const long long ops_base = split ? split->ops_base : 0;
         int32_t *textlen = split ? split->textlen : nullptr;
-        // (Tmax is a multiple of 16 -- the plans round it -- so a walk window never crosses into the next lane's stream)
-        rc = pmx_launch_walkp((variant % 10) & 3, 16, b, m, mode, open, ext, Tmax, top, stats_out, ends.row_pen, ends.col_pen,
+        rc = pmx_launch_walkp(p.G, p.R, b, m, mode, open, ext, p.Tmax, p.top_aligned, stats_out, ends.row_pen, ends.col_pen,
                               (const uint32_t *)tbuf, (const pmx_record_t *)d_out, ops, ops_off, ops_base, nops, beg, textlen, wstream,
-                              (!top && variant - 10 < 4) ? b.blockflag : nullptr);      // (the nwsgv shapes: their launcher fills the flags)
+                              p.fills_blockflag ? b.blockflag : nullptr);
         if (rc) return rc;
         hipError_t e = hipGetLastError();
         if (e == hipSuccess && split && split->walk_done) e = hipEventRecord(split->walk_done, wstream);
         return e == hipSuccess ? 0 : -(int)e;
     }
     if (split) return 1;                 // the split form is only built for the packed (second-generation) sweeps
-#define LT(GG, RR) (sw ? launch_trace<GG, RR, true>(b, m, mode, sg_flags, open, ext, d_out, tbuf, Tmax, ops, ops_off, nops, beg, stats_out, stream) \
-                       : launch_trace<GG, RR, false>(b, m, mode, sg_flags, open, ext, d_out, tbuf, Tmax, ops, ops_off, nops, beg, stats_out, stream))
-    switch (variant) {
-    case 0: return LT(32, 8);
-    case 1: return LT(64, 8);
-    case 2: return LT(64, 16);
-    }
-#undef LT
-    return 1;
+    int rc = 1;
+    for_each_gen1_shape([&](auto g, auto r) {
+        if (g != p.G || r != p.R) return false;
+        rc = sw ? launch_trace<g, r, true>(b, m, mode, sg_flags, open, ext, d_out, tbuf, p.Tmax, ops, ops_off, nops, beg, stats_out, stream)
+                : launch_trace<g, r, false>(b, m, mode, sg_flags, open, ext, d_out, tbuf, p.Tmax, ops, ops_off, nops, beg, stats_out, stream);
+        return true;
+    });
+    if (rc == 0) *sweep_name = "pmx_trace16_kernel";
+    return rc;
 }

@@ -214,9 +214,9 @@ void pmx_walkp_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restric
     beg[2 * pair] = i + 1; beg[2 * pair + 1] = j + 1;
 }
 
-// variant: the packed sweep's lane-group size index (0..3 -> G = 8, 16, 32, 64); rows per lane R = 16 or 10.  A PSSM (m.pssm):
-// statistics of global / semi-global paths only (the PS form), 1 otherwise.
-int pmx_launch_walkp(int gsel, int R, const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, int Tmax, int top_aligned,
+// G, R: the packed sweep's lanes per pair and rows per lane (1: a shape no sweep writes).  A PSSM (m.pssm): statistics of global /
+// semi-global paths only (the PS form), 1 otherwise.
+int pmx_launch_walkp(int G, int R, const PmxBatch &b, const PmxDevMatrix &m, int mode, int open, int ext, int Tmax, int top_aligned,
                      pmx_stats_t *stats_out, int row_pen, int col_pen, const uint32_t *tbuf, const pmx_record_t *recs,
                      uint32_t *ops, const int64_t *ops_off, long long ops_base, int32_t *nops, int32_t *beg, int32_t *textlen,
                      hipStream_t stream, const int *blockflag)
@@ -231,26 +231,17 @@ int pmx_launch_walkp(int gsel, int R, const PmxBatch &b, const PmxDevMatrix &m, 
 #define WALKP(GG, RR) do { const bool st_ = stats_out != nullptr, sw_ = mode == PMX_MODE_SW; \
         if (st_) { if (sw_) WALKP4(GG, RR, true, true); else WALKP4(GG, RR, true, false); } \
         else { if (sw_) WALKP4(GG, RR, false, true); else WALKP4(GG, RR, false, false); } } while (0)
-    if (R == 16) {
-        switch (gsel) {
-        case 0: WALKP(8, 16); break;
-        case 1: WALKP(16, 16); break;
-        case 2: WALKP(32, 16); break;
-        default: WALKP(64, 16); break;
-        }
-    } else if (R == 20) {
-        if (gsel != 1) return 1;
-        WALKP(16, 20);
-    } else if (R == 19) {
-        if (gsel != 1) return 1;
-        WALKP(16, 19);
-    } else if (R == 10) {
-        switch (gsel) {
-        case 1: WALKP(16, 10); break;
-        case 2: WALKP(32, 10); break;
-        default: return 1;
-        }
-    } else return 1;
+    switch (G * 100 + R) {
+    case 816: WALKP(8, 16); break;
+    case 1616: WALKP(16, 16); break;
+    case 3216: WALKP(32, 16); break;
+    case 6416: WALKP(64, 16); break;
+    case 1620: WALKP(16, 20); break;
+    case 1619: WALKP(16, 19); break;
+    case 1610: WALKP(16, 10); break;
+    case 3210: WALKP(32, 10); break;
+    default: return 1;
+    }
 #undef WALKP
 #undef WALKP4
 #undef WALKP5
