@@ -1510,6 +1510,15 @@ int pmx_window_nwsgv(int max_qlen, int max_rlen, int msize, int score_min, int s
 int pmx_trace_plan_probe(int mode, int msize, int score_min, int score_max, int pssm, int open, int extend, long long n,
                          int max_qlen, int max_rlen, int q_shared, int short_waves, int packed_ok,
                          int *family, int *G, int *R, int *Tmax, long long *trace_bytes);
+/* Test hook of the long-pair sweep's planning (host arithmetic only, no device needed; expected values: tests/golden/long_plans.json):
+ * the sweep planned for n pairs of up to max_qlen x max_rlen on road 0 (pmx_align_batch's score road: mode feeds its time model) or
+ * road 1 (pmx_align_batch_cigar_long: tile_cols / band_rows as in pmx_long_cigar_opts_t), with what the PMX_LONG_* switches and the
+ * device would say as arguments: the scratch budget of one chunk in bytes and whether it was forced, two_columns / one_column (0 / 1),
+ * rows_per_lane (0 = not set) and chunk_cols (16 or 64).  Returns 0 with out[0 .. 8] = rows per lane, columns per step, steps per
+ * boundary chunk, bands of the longest query, granules per (pair, band) boundary, pairs per chunk, bytes of a chunk's scratch in front
+ * of the checkpoints, bytes of the checkpoints, checkpoint slots per (pair, band); or 1, refused, with all nine 0. */
+int pmx_long_plan_probe(int road, int mode, long long n, int max_qlen, int max_rlen, double budget, int budget_forced,
+                        int two_columns, int one_column, int rows_per_lane, int chunk_cols, int tile_cols, int band_rows, long long *out);
 
 #ifdef __cplusplus
 }

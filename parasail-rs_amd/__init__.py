@@ -414,6 +414,7 @@ _sig("pmx_align_pairs_frameshift_ref_cigar_long", C.c_int, C.POINTER(pmx_config_
 _sig("pmx_frameshift_ref_cigar_long_parts", C.c_int64)
 _sig("pmx_swfsc_window_cols", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong)
 _sig("pmx_trace_plan_probe", C.c_int, *([C.c_int] * 7 + [C.c_longlong] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)]))
+_sig("pmx_long_plan_probe", C.c_int, *([C.c_int] * 2 + [C.c_longlong] + [C.c_int] * 2 + [C.c_double] + [C.c_int] * 7 + [C.POINTER(C.c_longlong)]))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 

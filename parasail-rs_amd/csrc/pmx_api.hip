@@ -1770,34 +1770,72 @@ static int stats_by_trace_pairs(const pmx_config_t *cfg, const DevMat &dm, const
 }
 
 // The long-pair sweep's switches and scratch budget as both of its roads read them (long_batch, long_cigar_device); which form runs
-// without a switch is each road's own decision.
+// without a switch is each road's own decision, and what the form's scratch looks like is the planner's (pmx_long_plan).
+static const size_t LONG_BUDGET_CEILING = ((size_t)4 << 30) + ((size_t)64 << 20);      // the most scratch one chunk of pairs takes
 struct LongKnobs {
-    bool two_columns, one_column;          // PMX_LONG_TWO_COLUMNS / PMX_LONG_ONE_COLUMN: force the form
+    bool two_columns = false, one_column = false;      // PMX_LONG_TWO_COLUMNS / PMX_LONG_ONE_COLUMN: force the form
+    int rows_per_lane = 0;                 // PMX_LONG_ROWS_PER_LANE: 2, 4 or 16 (0: not set)
     // the bands of a pair wait for one another across workgroups; the wait is bounded (pmx_long.hip): ~2 us a poll
     int spin_limit = 1 << 20, chunk_cols = 16;
-    size_t budget; bool budget_forced;     // bytes of scratch one chunk may take (PMX_LONG_CHUNK_BYTES: tests force several chunks)
+    size_t budget = LONG_BUDGET_CEILING; bool budget_forced = false;     // bytes of scratch one chunk may take (PMX_LONG_CHUNK_BYTES: tests force several chunks)
 };
-static LongKnobs long_knobs()
+// The switches alone (no device needed) ...
+static LongKnobs long_env_knobs()
 {
     LongKnobs k;
     k.two_columns = pmx_env("PMX_LONG_TWO_COLUMNS") != nullptr; k.one_column = pmx_env("PMX_LONG_ONE_COLUMN") != nullptr;
+    if (const char *e = pmx_env("PMX_LONG_ROWS_PER_LANE")) k.rows_per_lane = atoi(e) == 2 ? 2 : atoi(e) == 16 ? 16 : 4;
     if (const char *e = pmx_env("PMX_LONG_SPIN_LIMIT")) k.spin_limit = atoi(e);             // tests force the give-up path
     if (const char *e = pmx_env("PMX_LONG_CHUNK_COLS")) k.chunk_cols = atoi(e) == 64 ? 64 : 16;
-    size_t fb = 0, tb = 0;
-    if (hipMemGetInfo(&fb, &tb) != hipSuccess) fb = 0;
-    k.budget = std::min<size_t>((size_t)4 << 30, fb / 4) + ((size_t)64 << 20);
     const char *e = pmx_env("PMX_LONG_CHUNK_BYTES");
     if ((k.budget_forced = e != nullptr)) k.budget = (size_t)atof(e);
     return k;
 }
-// "pmx_long32_kernel<4>/bands across the chip", "pmx_long32_kernel_c2<2,ck>/checkpoint sweep + pmx_walkt_kernel", ...
-static const char *long_kernel_name(int R, int two_cols, bool checkpoints)
+// ... and with the budget a call really has: a quarter of the free device memory, up to the ceiling.
+static LongKnobs long_knobs()
 {
-    static thread_local char name[96];
-    snprintf(name, sizeof name, "pmx_long32_kernel%s<%d%s>/%s%s", two_cols ? "_c2" : "", R, checkpoints ? ",ck" : "",
-             checkpoints ? "checkpoint sweep + pmx_walkt_kernel" : "bands across the chip",
-             two_cols && !checkpoints ? ", two columns per step" : "");
-    return name;
+    LongKnobs k = long_env_knobs();
+    size_t fb = 0, tb = 0;
+    if (hipMemGetInfo(&fb, &tb) != hipSuccess) fb = 0;
+    if (!k.budget_forced) k.budget = std::min<size_t>(LONG_BUDGET_CEILING, fb / 4 + ((size_t)64 << 20));
+    return k;
+}
+// The switches on top of a road's own choice of form.  rows_too: the score road also lets PMX_LONG_ROWS_PER_LANE pick the rows per lane
+// and goes back to 256-row bands under PMX_LONG_ONE_COLUMN; the checkpoint road has its rows from the caller's band_rows and does neither.
+static void long_apply_switches(const LongKnobs &k, bool rows_too, int *R, int *cols)
+{
+    if (k.two_columns) *cols = 2;
+    if (k.one_column) { *cols = 1; if (rows_too) *R = 4; }
+    if (rows_too && k.rows_per_lane) *R = k.rows_per_lane;
+}
+
+// The score road's sweep for n pairs: 0 planned, 1 not eligible.
+static int long_score_plan(int mode, int64_t n, int32_t max_qlen, int32_t max_rlen, int msize, const LongKnobs &knobs, PmxLongPlan *pl)
+{
+    // R = 4 (256-row bands) also for batches that fill the chip: 1 024-row bands (R = 16) share a step's fixed work among four
+    // times the rows, but the longer dependent chain per step costs more (512 x 5 kbp^2: 5.0 ms against 6.5 ms, measured)
+    int R = 4;
+    // The form with two columns per step (pmx_long32_kernel_c2) has the shorter time per column, the one-column form the shorter
+    // lag from band to band, and 128-row bands (R = 2) halve a step at twice the bands.  One call of a few pairs is a latency
+    // problem: time = columns x (ns per column) + bands x (ns of lag per band), constants measured on MI355X per form
+    // (profiles/r04/long_shapes.txt); a batch that fills the chip keeps the one-column form with 256-row bands (throughput, measured).
+    int cols = 1;
+    if (n <= 16) {
+        const bool sw = mode == PMX_MODE_SW;
+        const double nb4 = (max_qlen + 255) / 256, nb2 = (max_qlen + 127) / 128, columns = max_rlen;
+        // (ns per column and ns per band, measured at the end of round 4: local alignment in the plain form, global / semi-global in the
+        //  form with column skew and row offset -- profiles/r04/long_shapes.txt, long_single_forms.txt)
+        const double t1 = columns * (sw ? 156 : 115) + nb4 * (sw ? 18400 : 15700);
+        const double t24 = columns * (sw ? 111 : 78.6) + nb4 * (sw ? 32600 : 20100);
+        const double t22 = columns * (sw ? 85 : 62.4) + nb2 * (sw ? 23100 : 16400);
+        if (t22 < 0.95 * t1 && t22 <= t24) { cols = 2; R = 2; }          // (within 5 %: the first form)
+        else if (t24 < 0.95 * t1) cols = 2;
+    }
+    long_apply_switches(knobs, true, &R, &cols);
+    PmxLongWant w = {};
+    w.n = n; w.max_qlen = max_qlen; w.max_rlen = max_rlen; w.msize = msize; w.R = R; w.cols = cols; w.chunk_cols = knobs.chunk_cols;
+    w.budget = knobs.budget; w.refuse_above_budget = !knobs.budget_forced; w.r16_above_4g = true;
+    return pmx_long_plan(w, pl);
 }
 
 // pmx_long32_kernel over a batch, in chunks of bounded scratch: 0 done, 1 not eligible, < 0 error.  Score and end positions, 32-bit
@@ -1817,46 +1855,19 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
                                       ends.row_pen ? -((long long)cfg->open + (long long)(max_rlen - 1) * cfg->extend) : 0LL);
         if (n == 1 && lo < -(long long)wmax - 1) force_sat = 1; else return 1;     // (inside the range: the general kernel tracks min / max H)
     }
-    // R = 4 (256-row bands) also for batches that fill the chip: 1 024-row bands (R = 16) share a step's fixed work among four
-    // times the rows, but the longer dependent chain per step costs more (512 x 5 kbp^2: 5.0 ms against 6.5 ms, measured)
-    int R = 4; long long bstride = 0; int nbmax = 0;
-    // The form with two columns per step (pmx_long32_kernel_c2) has the shorter time per column, the one-column form the shorter
-    // lag from band to band, and 128-row bands (R = 2) halve a step at twice the bands.  One call of a few pairs is a latency
-    // problem: time = columns x (ns per column) + bands x (ns of lag per band), constants measured on MI355X per form
-    // (profiles/r04/long_shapes.txt); a batch that fills the chip keeps the one-column form with 256-row bands (throughput, measured).
-    int two_cols = 0;
-    if (n <= 16) {
-        const bool sw = cfg->mode == PMX_MODE_SW;
-        const double nb4 = (max_qlen + 255) / 256, nb2 = (max_qlen + 127) / 128, cols = max_rlen;
-        // (ns per column and ns per band, measured at the end of round 4: local alignment in the plain form, global / semi-global in the
-        //  form with column skew and row offset -- profiles/r04/long_shapes.txt, long_single_forms.txt)
-        const double t1 = cols * (sw ? 156 : 115) + nb4 * (sw ? 18400 : 15700);
-        const double t24 = cols * (sw ? 111 : 78.6) + nb4 * (sw ? 32600 : 20100);
-        const double t22 = cols * (sw ? 85 : 62.4) + nb2 * (sw ? 23100 : 16400);
-        if (t22 < 0.95 * t1 && t22 <= t24) { two_cols = 1; R = 2; }          // (within 5 %: the first form)
-        else if (t24 < 0.95 * t1) two_cols = 1;
-    }
     const LongKnobs knobs = long_knobs();
-    if (knobs.two_columns) two_cols = 1;
-    if (knobs.one_column) { two_cols = 0; R = 4; }
-    if (const char *e = pmx_env("PMX_LONG_ROWS_PER_LANE")) R = atoi(e) == 2 ? 2 : atoi(e) == 16 ? 16 : 4;
-    if (R == 16) two_cols = 0;
-    size_t per_pair = pmx_long_scratch_bytes(1, max_qlen, max_rlen, R, &bstride, &nbmax);
-    if (per_pair > ((size_t)4 << 30)) { R = 16; two_cols = 0; per_pair = pmx_long_scratch_bytes(1, max_qlen, max_rlen, R, &bstride, &nbmax); }
-    if (per_pair > knobs.budget && !knobs.budget_forced) return 1;
-    int64_t chunk = (int64_t)(knobs.budget / per_pair);
-    if (chunk < 1) chunk = 1;
-    if (chunk > n) chunk = n;
+    PmxLongPlan pl;
+    if (long_score_plan(cfg->mode, n, max_qlen, max_rlen, dm.d.msize, knobs, &pl)) return 1;
     void *scr = nullptr;
-    if (scratch_reserve((size_t)chunk * per_pair, &scr, SCR_LONG)) return 1;
-    HIP_OR_RET(hipMemsetAsync(scr, 0, 64, st));
-    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+    if (scratch_reserve(pl.total, &scr, SCR_LONG)) return 1;
+    HIP_OR_RET(hipMemsetAsync((unsigned char *)scr + pl.off_abort, 0, pl.abort_bytes, st));
+    for (int64_t c0 = 0; c0 < n; c0 += pl.pairs) {
         PmxBatch b = b0;
         b.perm = nullptr;                                  // (a processing order is a hint: records are indexed by pair)
-        b.n = (n - c0 < chunk) ? n - c0 : chunk;
+        b.n = (n - c0 < pl.pairs) ? n - c0 : pl.pairs;
         if (!b.q_shared) b.qoff = b0.qoff + c0;
         b.roff = b0.roff + c0;
-        const int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, scr, d_out + c0, sat_above, force_sat, st, knobs.spin_limit, knobs.chunk_cols, two_cols);
+        const int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, pl, scr, d_out + c0, sat_above, force_sat, knobs.spin_limit, st);
         if (rc < 0) { set_err("long-pair kernel launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
         if (rc) return c0 == 0 ? 1 : (set_err("long-pair kernel refused a later chunk"), -1);
     }
@@ -1866,7 +1877,7 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
     static thread_local int *pin_flag = nullptr;
     if (!pin_flag) HIP_OR_RET(hipHostMalloc((void **)&pin_flag, 64, hipHostMallocDefault));
     *pin_flag = 0;
-    HIP_OR_RET(hipMemcpyAsync(pin_flag, scr, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipMemcpyAsync(pin_flag, (unsigned char *)scr + pl.off_abort, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_OR_RET(hipStreamSynchronize(st));
     const int gave_up = *pin_flag;
     if (gave_up) {
@@ -1874,7 +1885,7 @@ static int long_batch(const pmx_config_t *cfg, const DevMat &dm, const PmxBatch 
                 "the call was redone on the per-pair kernels");
         return 1;
     }
-    g_last_kernel = long_kernel_name(R, two_cols, false);
+    g_last_kernel = pl.name;
     return 0;
 }
 
@@ -3319,38 +3330,48 @@ extern "C" int pmx_search_profile(const pmx_config_t *cfg, const parasail_profil
 // row and column tile, 4 bytes per op slot.  Chunks of pairs share one scratch; sweep and walk of a chunk run back to back on the
 // caller's stream, so a chunk's checkpoints live until its walk is done and the next chunk's sweep starts behind it.
 static const int LONGCIG_DEFAULT_TILE = 128;
-struct LongCigPlan { int R, tile_cols; size_t sweep_bytes /* of one chunk, rounded to 256 */, ck_bytes; int64_t chunk; };
-static size_t longcig_budget_default() { return ((size_t)4 << 30) + ((size_t)64 << 20); }      // (long_batch's ceiling)
-// 0 fine, -1 refused with a message.  `budget` = bytes one chunk may take (a single pair always gets what it needs).
-static int longcig_plan(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_long_cigar_opts_t *opts, size_t budget, LongCigPlan *pl)
+// The checkpoint road's sweep for n pairs: 0 fine, -1 refused with a message.  A single pair always gets the scratch it needs.
+static int longcig_plan(int64_t n, int32_t max_qlen, int32_t max_rlen, int msize, const pmx_long_cigar_opts_t *opts, const LongKnobs &knobs, PmxLongPlan *pl)
 {
     if (n <= 0 || max_qlen <= 0 || max_rlen <= 0) { set_err("n, max_qlen and max_rlen must be positive"); return -1; }
     int tile = opts ? opts->tile_cols : 0, rows = opts ? opts->band_rows : 0;
     if (tile == 0) tile = LONGCIG_DEFAULT_TILE;
     if (tile != 64 && tile != 128 && tile != 256) { set_err("tile_cols %d is not offered (64, 128, 256; 0 = default)", tile); return -1; }
     if (rows != 0 && rows != 128 && rows != 256 && rows != 1024) { set_err("band_rows %d is not offered (128, 256, 1024; 0 = the dispatcher's choice)", rows); return -1; }
-    long long bstride = 0; int nbmax = 0;
-    auto per_pair = [&](int R) { return pmx_long_scratch_bytes(1, max_qlen, max_rlen, R, &bstride, &nbmax) - 64 + pmx_long_ck_bytes(1, max_qlen, max_rlen, R, tile); };
-    int R = rows ? rows / 64 : 4;
-    if (!rows && per_pair(R) > ((size_t)4 << 30)) R = 16;          // (fewer bands: fewer row granules; as long_batch)
-    const size_t pp = per_pair(R);
-    int64_t chunk = (int64_t)(budget / pp);
-    if (chunk < 1) chunk = 1;
-    if (chunk > n) chunk = n;
-    if (chunk * (int64_t)nbmax > 0x7FFFFFFFLL) chunk = 0x7FFFFFFFLL / nbmax;
-    pl->R = R; pl->tile_cols = tile; pl->chunk = chunk;
-    pl->sweep_bytes = (pmx_long_scratch_bytes(chunk, max_qlen, max_rlen, R, &bstride, &nbmax) + 255) & ~(size_t)255;
-    pl->ck_bytes = pmx_long_ck_bytes(chunk, max_qlen, max_rlen, R, tile);
+    // two columns per step for a chunk of a few pairs (latency), one for a chunk that fills the chip (long_batch, measured)
+    int R = rows ? rows / 64 : 4, cols_many = 1, cols_few = 2;
+    long_apply_switches(knobs, false, &R, &cols_many);
+    long_apply_switches(knobs, false, &R, &cols_few);
+    PmxLongWant w = {};
+    w.n = n; w.max_qlen = max_qlen; w.max_rlen = max_rlen; w.msize = msize; w.R = R; w.cols = cols_many; w.cols_few = cols_few;
+    w.chunk_cols = knobs.chunk_cols; w.tile_cols = tile; w.budget = knobs.budget; w.refuse_above_budget = false; w.r16_above_4g = rows == 0;
+    w.clamp_blocks = true;
+    const int rc = pmx_long_plan(w, pl);
+    if (rc) { set_err("the long-pair sweep does not take this configuration (alphabet above 64 letters, a profile beyond the LDS)"); return -1; }
     return 0;
 }
 
 extern "C" long long pmx_long_cigar_scratch_bytes(int64_t n, int32_t max_qlen, int32_t max_rlen, const pmx_long_cigar_opts_t *opts)
 {
-    LongCigPlan pl;
-    size_t budget = longcig_budget_default();
-    if (const char *e = pmx_env("PMX_LONG_CHUNK_BYTES")) budget = (size_t)atof(e);
-    if (longcig_plan(n, max_qlen, max_rlen, opts, budget, &pl)) return -1;
-    return (long long)(pl.sweep_bytes + pl.ck_bytes);
+    PmxLongPlan pl;
+    if (longcig_plan(n, max_qlen, max_rlen, 0, opts, long_env_knobs(), &pl)) return -1;
+    return (long long)pl.total;
+}
+
+/* Test hook (include/parasail_amd.h): both roads' planning with the knobs as arguments; no device needed. */
+extern "C" int pmx_long_plan_probe(int road, int mode, long long n, int max_qlen, int max_rlen, double budget, int budget_forced,
+                                   int two_columns, int one_column, int rows_per_lane, int chunk_cols, int tile_cols, int band_rows, long long *out)
+{
+    LongKnobs knobs;
+    knobs.two_columns = two_columns != 0; knobs.one_column = one_column != 0; knobs.rows_per_lane = rows_per_lane; knobs.chunk_cols = chunk_cols;
+    knobs.budget = (size_t)budget; knobs.budget_forced = budget_forced != 0;
+    const pmx_long_cigar_opts_t opts = {tile_cols, band_rows};
+    PmxLongPlan pl = {};
+    const int rc = road == 0 ? long_score_plan(mode, n, max_qlen, max_rlen, 4, knobs, &pl) : (longcig_plan(n, max_qlen, max_rlen, 4, &opts, knobs, &pl) ? 1 : 0);
+    if (rc) pl = PmxLongPlan();
+    const long long v[9] = {pl.R, pl.cols, pl.steps, pl.nbmax, pl.bstride, pl.pairs, (long long)pl.off_ck, (long long)pl.ck_bytes, pl.ckslots};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return rc;
 }
 
 static int long_cigar_check(const pmx_config_t *cfg, const pmx_long_cigar_opts_t *opts)
@@ -3359,8 +3380,8 @@ static int long_cigar_check(const pmx_config_t *cfg, const pmx_long_cigar_opts_t
     if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) { set_err("PSSM matrices are not supported by the tiled long-pair traceback"); return -1; }
     if (traced_want_check(cfg, "pmx_align_batch_cigar_long")) return -1;
     if (cfg->matrix->size > 64) { set_err("the long-pair kernels take alphabets of up to 64 letters (matrix size %d)", cfg->matrix->size); return -1; }
-    LongCigPlan pl;
-    return longcig_plan(1, 1, 1, opts, longcig_budget_default(), &pl);          // (the options alone)
+    PmxLongPlan pl;
+    return longcig_plan(1, 1, 1, cfg->matrix->size, opts, LongKnobs(), &pl);          // (the options alone)
 }
 
 // Validated by the caller; offsets start at 0.  Asynchronous on `st`; *d_abort = the launch's abort word (device).
@@ -3374,30 +3395,21 @@ static int long_cigar_device(const pmx_config_t *cfg, int64_t n, const uint8_t *
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
     const LongKnobs knobs = long_knobs();
-    LongCigPlan pl;
-    if (longcig_plan(n, max_qlen, max_rlen, opts, knobs.budget, &pl)) return -1;
-    const int R = pl.R;
-    // two columns per step for a few pairs (latency), one for a batch that fills the chip (long_batch, measured); the switches of the
-    // long-pair sweep act on the shared code as they do there
-    int two_cols = (pl.chunk <= 16 && R != 16) ? 1 : 0;
-    if (knobs.two_columns) two_cols = R != 16;
-    if (knobs.one_column) two_cols = 0;
+    PmxLongPlan pl;
+    if (longcig_plan(n, max_qlen, max_rlen, dm.d.msize, opts, knobs, &pl)) return -1;
     unsigned char *scr = nullptr; SlotText t;
-    if (scratch_reserve(pl.sweep_bytes + pl.ck_bytes, (void **)&scr, SCR_LONG) ||
+    if (scratch_reserve(pl.total, (void **)&scr, SCR_LONG) ||
         (want_cigar && t.reserve_ops(op_slots > 0 ? (size_t)op_slots : (size_t)n * ((size_t)max_qlen + max_rlen + 1))) ||
         scratch_carve(SCR_CIG, [&](Carver &c) { t.carve(c, n, want_cigar); })) return -1;
-    HIP_OR_RET(hipMemsetAsync(scr, 0, 64, st));
-    for (int64_t c0 = 0; c0 < n; c0 += pl.chunk) {
+    HIP_OR_RET(hipMemsetAsync(scr + pl.off_abort, 0, pl.abort_bytes, st));
+    for (int64_t c0 = 0; c0 < n; c0 += pl.pairs) {
         PmxBatch b; memset(&b, 0, sizeof b);
         b.qbuf = d_qbuf; b.qoff = d_qoff + c0; b.rbuf = d_rbuf; b.roff = d_roff + c0;
-        b.n = (n - c0 < pl.chunk) ? n - c0 : pl.chunk; b.max_qlen = max_qlen; b.max_rlen = max_rlen;
-        long long bstride = 0; int nbmax = 0;
-        void *ck = scr + ((pmx_long_scratch_bytes(b.n, max_qlen, max_rlen, R, &bstride, &nbmax) + 255) & ~(size_t)255);
-        int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, scr, d_out + c0, 2147483647, 0, st,
-                                 knobs.spin_limit, knobs.chunk_cols, two_cols, ck, pl.tile_cols);
+        b.n = (n - c0 < pl.pairs) ? n - c0 : pl.pairs; b.max_qlen = max_qlen; b.max_rlen = max_rlen;
+        int rc = pmx_launch_long(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, pl, scr, d_out + c0, 2147483647, 0, knobs.spin_limit, st);
         if (rc < 0) { set_err("checkpoint sweep launch failed: %s", hipGetErrorString((hipError_t)(-rc))); return rc; }
         if (rc) { set_err("the long-pair sweep does not take this configuration (alphabet above 64 letters, scores or gap penalties beyond its 16-bit profile, lengths x penalties beyond 2^29)"); return -1; }
-        rc = pmx_launch_walkt(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, R, pl.tile_cols, scr, ck, d_out + c0,
+        rc = pmx_launch_walkt(b, dm.d, cfg->mode, cfg->sg_flags, cfg->open, cfg->extend, pl, scr, d_out + c0,
                               d_qoff + c0, -c0, t.ops, want_cigar ? t.nops + c0 : nullptr, want_cigar ? t.textlen + c0 : nullptr,
                               want_stats ? d_stats + c0 : nullptr, st);
         if (rc) { set_err("tile walk launch failed (%d)", rc); return rc < 0 ? rc : -1; }
@@ -3406,8 +3418,8 @@ static int long_cigar_device(const pmx_config_t *cfg, int64_t n, const uint8_t *
         const int rc = t.render(d_qoff, d_roff, 0, n, d_text, capacity, d_text_off, st);
         if (rc) return rc;
     }
-    if (d_abort) *d_abort = reinterpret_cast<const int *>(scr);
-    g_last_kernel = long_kernel_name(R, two_cols, true);
+    if (d_abort) *d_abort = reinterpret_cast<const int *>(scr + pl.off_abort);
+    g_last_kernel = pl.name;
     return 0;
 }
 

@@ -476,24 +476,47 @@ int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t 
 void pmx_all_pairs_index_host(unsigned long long nseq, unsigned long long p, unsigned long long *i, unsigned long long *j);
 
 // One long pair (or a few) across the chip: bands of the query on different CUs, pipelined through HBM granules (pmx_long.hip).
-// R = rows per lane (4 or 16).  0 launched, 1 not eligible, <0 HIP error; `scratch` holds pmx_long_scratch_bytes() bytes.
-size_t pmx_long_scratch_bytes(long long n, int max_qlen, int max_rlen, int R, long long *bstride, int *nbmax);
-// The first 64 bytes of `scratch` are the call's abort word: the caller zeroes them before the first launch and reads them after the
-// last (non-zero: a band's bounded wait ran out -- every record of the call is marked PMX_FLAG_RERUN and has to be redone elsewhere).
-int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R,
-                    void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, hipStream_t stream, int spin_limit = 1 << 20,
-                    int chunk_cols = 16 /* boundary columns a band takes over at a time: 16 or 64 (two-column form: steps, 32 or 64) */,
-                    int two_cols = 1 /* rows per lane 2 or 4: the form with two columns per step */,
-                    void *ck = nullptr /* != NULL: the checkpoint forms -- pmx_long_ck_bytes() bytes for the (H, E) of every tile_cols-th column */,
-                    int tile_cols = 0 /* a power of two */);
-long long pmx_long_ck_slots(int max_rlen, int tile_cols);
-size_t pmx_long_ck_bytes(long long n, int max_qlen, int max_rlen, int R, int tile_cols);
+// What a road asks of the sweep (long_batch, long_cigar_device: which form runs without a switch is the road's own decision) ...
+struct PmxLongWant {
+    long long n; int max_qlen, max_rlen, msize;
+    int R;                   // rows per lane: 2, 4 or 16 (bands of 128, 256 or 1 024 query rows)
+    int cols;                // columns per step: 1 or 2 (R = 16 has the one-column form only and gets it)
+    int cols_few;            // 0, or the columns per step when the chunk turns out to be of at most 16 pairs (the chunk does not depend on them)
+    int chunk_cols;          // PMX_LONG_CHUNK_COLS, 16 or 64: boundary columns a band takes over at a time; the two-column form counts steps of two
+                             //   columns and has no chunk below 32 of them, so 16 means 32 steps (64 columns) there and 64 means 64 steps (128 columns)
+    int tile_cols;           // 0: scores only; 64, 128, 256: the checkpoint form -- the (H, E) of every tile_cols-th column stay for pmx_walkt.hip
+    size_t budget;           // bytes of scratch one chunk of pairs may take (one pair always gets what it needs ...
+    bool refuse_above_budget;     // ... unless this is set: then a pair beyond the budget is refused)
+    bool r16_above_4g;       // a pair whose scratch passes 4 GiB takes R = 16 instead (fewer bands: fewer row granules)
+    bool clamp_blocks;       // a chunk of more than 2^31 - 1 (pair, band) workgroups: shorten it (else: refused)
+};
+// ... and the sweep the planner makes of it: what pmx_launch_long, pmx_launch_walkt and the roads' chunk loops need to know.  A chunk's
+// scratch is [abort word, 64 bytes][boundary granules][candidates, 8 ints per (pair, band)][checkpoints, from the next 256-byte boundary];
+// pmx_long_plan is the one place that lays it out.  The first 64 bytes are the call's abort word: the caller zeroes them before the first
+// launch and reads them after the last (non-zero: a band's bounded wait ran out -- every record of the call is marked PMX_FLAG_RERUN and
+// has to be redone elsewhere).
+struct PmxLongPlan {
+    int R, cols, steps;      // rows per lane, columns per step, steps per boundary chunk (16 / 64 one-column, 32 / 64 two-column)
+    bool ck; int tile_cols, ckshift; long long ckslots;     // checkpoint form: tile_cols = 1 << ckshift, slots per (pair, band)
+    int nbmax; long long bstride;                            // bands of the longest query; granules per (pair, band) boundary
+    long long pairs;         // per chunk: a launch takes at most that many
+    int msize, max_qlen, max_rlen;                           // what it was planned for: a launch may not exceed it
+    size_t off_abort, abort_bytes, off_bound, off_cand, off_ck, total;    // bytes within a chunk's scratch (off_ck = total without checkpoints)
+    size_t ck_bytes;         // total - off_ck
+    size_t lds;              // dynamic LDS of the sweep
+    const char *name;        // the instance and its road as pmx_last_kernel() shows them (static storage)
+};
+// 0 planned, 1 refused (no such form, or it cannot be launched: alphabet, LDS, budget); calls no HIP function.
+int pmx_long_plan(const PmxLongWant &w, PmxLongPlan *p);
+// 0 launched, 1 not eligible, <0 HIP error.  b.n <= p.pairs pairs into `scratch` (p.total bytes).
+int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, const PmxLongPlan &p,
+                    void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, int spin_limit, hipStream_t stream);
 // Tiled traceback over what the checkpoint sweep left (pmx_walkt.hip): one wave per pair re-derives the tiles the path enters.  Run-length
 // ops / nops / textlen as pmx_launch_walkb (ops == NULL: none) and / or the path's statistics (stats_out != NULL), in one pass.
-// 0 launched, 1 not eligible (the tile's decision bits do not fit the LDS), <0 HIP error.
+// 0 launched, 1 not eligible (the tile's decision bits do not fit the LDS), <0 HIP error.  `scratch`: what pmx_launch_long filled by `p`.
 size_t pmx_walkt_lds_bytes(int msize, int BR, int tile_cols);
-int pmx_launch_walkt(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R, int tile_cols,
-                     const void *scratch, const void *ck, const pmx_record_t *recs,
+int pmx_launch_walkt(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, const PmxLongPlan &p,
+                     const void *scratch, const pmx_record_t *recs,
                      const int64_t *slot_qoff, long long ops_base, uint32_t *ops, int32_t *nops, int32_t *textlen,
                      pmx_stats_t *stats_out, hipStream_t stream);
 

@@ -56,6 +56,118 @@ struct PmxLongArgs {
     int2 *ck; long long ckslots; int ckshift;          // tile_cols = 1 << ckshift
 };
 
+// One boundary granule: (H, F) leaving a band's last row at one column, data and tag at once (see above).
+__device__ __forceinline__ unsigned long long long_granule_load(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void long_granule_store(unsigned long long *p, int H, int F)
+{
+    __hip_atomic_store(p, ((unsigned long long)(unsigned)F << 32) | (unsigned)H, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int long_granule_h(unsigned long long g) { return (int)(unsigned)(g & 0xFFFFFFFFu); }
+__device__ __forceinline__ int long_granule_f(unsigned long long g) { return (int)(unsigned)(g >> 32); }
+
+// The matrix's first column and row, plain and in the strips' form (H - open, and where SKEW + the cell's offset (i + j) ext).
+// (the sweeps spell the boundary flags out, not pmx_strip.h's helpers: the sg leg of profiles/r19 ran above the parent's range)
+template <int MODE> struct LongEdges {
+    static constexpr bool SKEW = MODE != PMX_MODE_SW;
+    bool pen_col, pen_row; int open, ext;
+    __device__ __forceinline__ LongEdges(int sg_flags, int open_, int ext_) : open(open_), ext(ext_)
+    {
+        pen_col = MODE == PMX_MODE_NW || (MODE == PMX_MODE_SG && !(sg_flags & PMX_SG_QB));      // column -1 (query begin) is penalised
+        pen_row = MODE == PMX_MODE_NW || (MODE == PMX_MODE_SG && !(sg_flags & PMX_SG_DB));      // row -1 (reference begin) is penalised
+    }
+    __device__ __forceinline__ int left(int i) const { return i < 0 ? 0 : (pen_col ? -(open + i * ext) : 0); }      // H(i, -1); H(-1, -1) = 0
+    __device__ __forceinline__ int top(int j) const { return pen_row ? -(open + j * ext) : 0; }                      // H(-1, j)
+    __device__ __forceinline__ int left_strip(int i) const { return left(i) - open + (SKEW ? i * ext : 0); }
+    __device__ __forceinline__ int top_strip(int j) const { return top(j) - open + (SKEW ? j * ext : 0); }
+};
+
+// Matrix and map into the LDS, then the band's query profile (int16 [symbol][row], row msize = the pad symbol); returns the map.
+template <int R, bool SKEW>
+__device__ __forceinline__ unsigned char *long_stage_profile(const PmxLongArgs &a, unsigned char *lds, int lane, int band, const uint8_t *q, int ql)
+{
+    constexpr int BR = 64 * R;
+    const int msize = a.msize, open = a.open, ext = a.ext;
+    int16_t *prof = reinterpret_cast<int16_t *>(lds);                  // [(msize + 1) * BR]: row msize = the pad symbol
+    int16_t *mat = prof + (msize + 1) * BR;                            // [msize * msize]
+    unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
+    for (int i = lane; i < msize * msize; i += 64) mat[i] = a.scores[i];
+    for (int i = lane; i < 256; i += 64) map[i] = a.mapper[i];
+    __syncthreads();
+    for (int row = lane; row < BR; row += 64) {                        // the profile carries score + open (the strips carry H - open)
+        const int i = band * BR + row;
+        const int qs = i < ql ? (int)map[q[i]] : -1;
+        for (int sym = 0; sym < msize; ++sym) prof[sym * BR + row] = (int16_t)(qs < 0 ? LONG_PAD : mat[qs * msize + sym] + open + (SKEW ? ext : 0));
+        prof[msize * BR + row] = (int16_t)LONG_PAD;
+    }
+    __syncthreads();
+    return map;
+}
+
+// This band's candidates behind the sweep, the same in both sweeps.  COLS = columns per step: a lane's column at step t is COLS (t - lane) [+ 1].
+template <int R, int MODE, int COLS>
+__device__ __forceinline__ void long_candidates(int *cand, int lane, int i0, int ql, int rl, int open, int ext, bool lastband, int gstar, int kstar,
+                                                const int (&hs)[R], const int (&lc)[R], int best, int bcol, int rbest, int rcol)
+{
+    constexpr bool SW = MODE == PMX_MODE_SW, SKEW = !SW;
+    if (SW) {
+        int kf = 0;
+#pragma unroll
+        for (int k = R - 1; k >= 0; --k) if (hs[k] == best) kf = k;
+        int sc = best + open, col = bcol - COLS * lane, row = i0 + kf;
+        if (row >= ql) { sc = -1; col = 0x7FFFFFFF; row = 0x7FFFFFFF; }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const int os = __shfl_xor(sc, off, 64), oc = __shfl_xor(col, off, 64), orow = __shfl_xor(row, off, 64);
+            const bool take = os > sc || (os == sc && (oc < col || (oc == col && orow < row)));
+            if (take) { sc = os; col = oc; row = orow; }
+        }
+        if (lane == 0) { cand[0] = sc; cand[1] = col; cand[2] = row; }
+    } else {
+        // last column: this band's best over its rows, smallest row first
+        int sc = LONG_NEG, row = 0x7FFFFFFF;
+#pragma unroll
+        for (int k = R - 1; k >= 0; --k) {
+            const int v = lc[k] + open - (SKEW ? ext + (i0 + k + rl - 1) * ext : 0);      // (the offset of cell (i0 + k, rl - 1) comes off)
+            if (i0 + k < ql && v >= sc) { sc = v; row = i0 + k; }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const int os = __shfl_xor(sc, off, 64), orow = __shfl_xor(row, off, 64);
+            const bool take = os > sc || (os == sc && orow < row);
+            if (take) { sc = os; row = orow; }
+        }
+        if (lane == 0) { cand[3] = sc; cand[4] = row; }
+        if (lastband && lane == gstar) {
+            int corner = lc[0];
+#pragma unroll
+            for (int k = 1; k < R; ++k) corner = (kstar == k) ? lc[k] : corner;
+            cand[7] = corner + open - (SKEW ? ext + (ql - 1 + rl - 1) * ext : 0);
+            cand[5] = rbest + open - (SKEW ? ext + (ql - 1) * ext : 0); cand[6] = rcol;
+        }
+    }
+}
+
+// The wait for the band above, the same in both sweeps.  waiting(): a granule of the chunk is still the fill pattern (wave-uniform);
+// reload(): load the chunk's granules again.  The tight poll is what every band's pipeline lag is made of; the limit and the abort word
+// are looked at once per 64 polls.  A band that gives up does NOT leave (an exit in the middle of the sweep cost global alignment 70 %
+// -- 4.2 -> 7.1 ms at 20 kbp -- whatever the poll looked like): it stops waiting and finishes its sweep on whatever the buffer holds, as
+// does every band that finds the abort word; nothing of the launch counts then (finalize), and nothing waits any more.
+template <typename W, typename L>
+__device__ __forceinline__ void long_wait_for_chunk(bool &dead, int spin_limit, int *abort_word, int lane, W waiting, L reload)
+{
+    for (int spins = 0; !dead && waiting(); spins += 64) {
+        for (int k = 0; k < 64 && waiting(); ++k) {        // the producer is not that far yet
+            __builtin_amdgcn_s_sleep(8);
+            reload();
+        }
+        if (!waiting()) break;
+        if (spins >= spin_limit || __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+            if (lane == 0) __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            dead = true;
+        }
+    }
+}
+
 // The rotating registers move with lane_next_untied: lane 63 has no source and gets 0, and what enters there reaches lane 0 only
 // after 64 shifts, when every rotating register has been reloaded.
 
@@ -71,6 +183,12 @@ void pmx_long32_kernel(PmxLongArgs a)
     // column: + 2 ext, folded into the profile (score + open + ext).  5 instructions per cell instead of 7; boundaries and granules are in
     // the same form (the offset is global), captures take it off.  Local alignment keeps the plain form: its zero floor is per cell.
     constexpr bool SKEW = !SW;
+    // The band frame -- pair, band, lengths, pointers: these lines and those behind `rim` -- stands in both sweeps on purpose.  Staging,
+    // boundary formulas, granules, the bounded wait and the candidates are shared helpers (each held the parent's range on all 56 lines of
+    // profiles/bench_long_shapes.py, six alternating rounds); the frame as one __forceinline__ struct whose members the steps read
+    // (const, built by its constructor; no spill, 116 545 -> 116 066 instructions) put global alignment in the two-column form 2-4 %
+    // above the parent (R = 4, 1 024 x 50 kbp: 3.967-3.977 -> 4.133 ms; R = 2: 3.175-3.184 -> 3.260 ms), 27 of 56 lines outside the margin;
+    // built by an init() with the staging inside it was the one-column form with 256-row bands that lost 5-6 % (5.94-5.98 -> 6.31 ms).
     const int lane = threadIdx.x;
     const long long pair = blockIdx.x / a.nbmax;
     const int band = (int)(blockIdx.x % a.nbmax);
@@ -83,31 +201,15 @@ void pmx_long32_kernel(PmxLongArgs a)
     const int msize = a.msize, open = a.open, ext = a.ext;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    int16_t *prof = reinterpret_cast<int16_t *>(lds);                  // [(msize + 1) * BR]: row msize = the pad symbol
-    int16_t *mat = prof + (msize + 1) * BR;                            // [msize * msize]
-    unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    for (int i = lane; i < msize * msize; i += 64) mat[i] = a.scores[i];
-    for (int i = lane; i < 256; i += 64) map[i] = a.mapper[i];
-    __syncthreads();
-    for (int row = lane; row < BR; row += 64) {                        // the profile carries score + open (the strips carry H - open)
-        const int i = band * BR + row;
-        const int qs = i < ql ? (int)map[q[i]] : -1;
-        for (int sym = 0; sym < msize; ++sym) prof[sym * BR + row] = (int16_t)(qs < 0 ? LONG_PAD : mat[qs * msize + sym] + open + (SKEW ? ext : 0));
-        prof[msize * BR + row] = (int16_t)LONG_PAD;
-    }
-    __syncthreads();
+    unsigned char *map = long_stage_profile<R, SKEW>(a, lds, lane, band, q, ql);
 
-    // (the sweeps spell staging and boundary flags out, not pmx_strip.h's helpers: the sg leg of profiles/r19 ran above the parent's range)
-    const bool pen_col = MODE == PMX_MODE_NW || (SG && !(a.sg_flags & PMX_SG_QB));      // column -1 (query begin) is penalised
-    const bool pen_row = MODE == PMX_MODE_NW || (SG && !(a.sg_flags & PMX_SG_DB));      // row -1 (reference begin) is penalised
-    auto left = [&](int i) -> int { return i < 0 ? 0 : (pen_col ? -(open + i * ext) : 0); };      // H(i, -1); H(-1, -1) = 0
-    auto top = [&](int j) -> int { return pen_row ? -(open + j * ext) : 0; };                      // H(-1, j)
+    const LongEdges<MODE> rim(a.sg_flags, open, ext);
 
     const int i0 = band * BR + lane * R;
     int HA[R], HB[R], E[R], hs[R], lc[R];
 #pragma unroll
-    for (int k = 0; k < R; ++k) { HA[k] = left(i0 + k) - open + (SKEW ? (i0 + k) * ext : 0); HB[k] = HA[k]; E[k] = LONG_NEG; hs[k] = 0; lc[k] = LONG_NEG; }
-    int diag = left(i0 - 1) - open + (SKEW ? (i0 - 1) * ext : 0);
+    for (int k = 0; k < R; ++k) { HA[k] = rim.left_strip(i0 + k); HB[k] = HA[k]; E[k] = LONG_NEG; hs[k] = 0; lc[k] = LONG_NEG; }
+    int diag = rim.left_strip(i0 - 1);
     int Hout = 0, Fout = 0;
     int best = SW ? -open - 1 : 0, bcol = 0;
     // sg, reference end free: the lane and register that hold the query's last row (last band only)
@@ -129,7 +231,7 @@ void pmx_long32_kernel(PmxLongArgs a)
     const int spin_limit = a.spin_limit;
     int *const abort_word = a.abort_word;
     auto prefetch_sym = [&](int base) { const int c = base + lane; nraw = c < rl ? (int)r[c] : -1; };
-    auto prefetch_bound = [&](int base) { if (bin && (CH == 64 || lane < CH)) ngran = __hip_atomic_load(bin + base + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto prefetch_bound = [&](int base) { if (bin && (CH == 64 || lane < CH)) ngran = long_granule_load(bin + base + lane); };
     // symbols of columns [base, base + 64) take over the rotating register (one step BEFORE the first of them is worked on:
     // a step reads the profile row of the NEXT step's symbol ahead of its own arithmetic)
     auto reload_sym = [&](int base) {
@@ -138,26 +240,13 @@ void pmx_long32_kernel(PmxLongArgs a)
     };
     auto reload_bound = [&](int base) {
         if (bin && base < RU) {                            // (the chunk behind the reference is padding on both sides: never written, never needed)
-            // The tight poll is what every band's pipeline lag is made of; the limit and the abort word are looked at once per 64 polls.
-            // A band that gives up does NOT leave (an exit in the middle of the sweep cost global alignment 70 % -- 4.2 -> 7.1 ms at
-            // 20 kbp -- whatever the poll looked like): it stops waiting and finishes its sweep on whatever the buffer holds, as does
-            // every band that finds the abort word; nothing of the launch counts then (finalize), and nothing waits any more.
-            for (int spins = 0; !dead && __builtin_amdgcn_ballot_w64(ngran == LONG_SENT) != 0; spins += 64) {
-                for (int k = 0; k < 64 && __builtin_amdgcn_ballot_w64(ngran == LONG_SENT) != 0; ++k) {      // the producer is not that far yet
-                    __builtin_amdgcn_s_sleep(8);
-                    if (CH == 64 || lane < CH) ngran = __hip_atomic_load(bin + base + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (__builtin_amdgcn_ballot_w64(ngran == LONG_SENT) == 0) break;
-                if (spins >= spin_limit || __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    if (lane == 0) __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    dead = true;
-                }
-            }
-            Hb = (int)(unsigned)(ngran & 0xFFFFFFFFu); Fb = (int)(unsigned)(ngran >> 32);
+            long_wait_for_chunk(dead, spin_limit, abort_word, lane, [&]() -> bool { return __builtin_amdgcn_ballot_w64(ngran == LONG_SENT) != 0; },
+                                [&]() { if (CH == 64 || lane < CH) ngran = long_granule_load(bin + base + lane); });
+            Hb = long_granule_h(ngran); Fb = long_granule_f(ngran);
         } else if (bin) {
             Hb = 0; Fb = 0;
         } else {
-            Hb = top(base + lane) - open + (SKEW ? (base + lane) * ext : 0);      // H(-1, j) - open; F(0, j) = max(-inf, H(-1, j) - open)
+            Hb = rim.top_strip(base + lane);      // H(-1, j) - open; F(0, j) = max(-inf, H(-1, j) - open)
             Fb = SW ? 0 : Hb;
         }
         if (base + CH < T) prefetch_bound(base + CH);
@@ -233,8 +322,7 @@ void pmx_long32_kernel(PmxLongArgs a)
             }
         }
         if (bout && lane == 63 && (!EDGE || t >= 63))
-            __hip_atomic_store(bout + (t - 63), ((unsigned long long)(unsigned)Fout << 32) | (unsigned)Hout, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            long_granule_store(bout + (t - 63), Hout, Fout);
     };
 
     const int tB = rl >= 129 ? ((rl - 1) & ~63) : 64;     // [64, tB): every lane's column is inside the reference and left of its last column
@@ -261,44 +349,7 @@ void pmx_long32_kernel(PmxLongArgs a)
         }
     }
 
-    // ---- this band's candidates -----------------------------------------------------------------------------------------
-    int *cand = a.cand + ((size_t)pair * a.nbmax + band) * 8;
-    if (SW) {
-        int kf = 0;
-#pragma unroll
-        for (int k = R - 1; k >= 0; --k) if (hs[k] == best) kf = k;
-        int sc = best + open, col = bcol - lane, row = i0 + kf;
-        if (row >= ql) { sc = -1; col = 0x7FFFFFFF; row = 0x7FFFFFFF; }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int os = __shfl_xor(sc, off, 64), oc = __shfl_xor(col, off, 64), orow = __shfl_xor(row, off, 64);
-            const bool take = os > sc || (os == sc && (oc < col || (oc == col && orow < row)));
-            if (take) { sc = os; col = oc; row = orow; }
-        }
-        if (lane == 0) { cand[0] = sc; cand[1] = col; cand[2] = row; }
-    } else {
-        // last column: this band's best over its rows, smallest row first
-        int sc = LONG_NEG, row = 0x7FFFFFFF;
-#pragma unroll
-        for (int k = R - 1; k >= 0; --k) {
-            const int v = lc[k] + open - (SKEW ? ext + (i0 + k + rl - 1) * ext : 0);      // (the offset of cell (i0 + k, rl - 1) comes off)
-            if (i0 + k < ql && v >= sc) { sc = v; row = i0 + k; }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int os = __shfl_xor(sc, off, 64), orow = __shfl_xor(row, off, 64);
-            const bool take = os > sc || (os == sc && orow < row);
-            if (take) { sc = os; row = orow; }
-        }
-        if (lane == 0) { cand[3] = sc; cand[4] = row; }
-        if (lastband && lane == gstar) {
-            int corner = lc[0];
-#pragma unroll
-            for (int k = 1; k < R; ++k) corner = (kstar == k) ? lc[k] : corner;
-            cand[7] = corner + open - (SKEW ? ext + (ql - 1 + rl - 1) * ext : 0);
-            cand[5] = rbest + open - (SKEW ? ext + (ql - 1) * ext : 0); cand[6] = rcol;
-        }
-    }
+    long_candidates<R, MODE, 1>(a.cand + ((size_t)pair * a.nbmax + band) * 8, lane, i0, ql, rl, open, ext, lastband, gstar, kstar, hs, lc, best, bcol, rbest, rcol);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -320,6 +371,7 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
     // column: + 2 ext, folded into the profile (score + open + ext).  5 instructions per cell instead of 7; boundaries and granules are in
     // the same form (the offset is global), captures take it off.  Local alignment keeps the plain form: its zero floor is per cell.
     constexpr bool SKEW = !SW;
+    // (the band frame stands here a second time: see pmx_long32_kernel)
     const int lane = threadIdx.x;
     const long long pair = blockIdx.x / a.nbmax;
     const int band = (int)(blockIdx.x % a.nbmax);
@@ -332,30 +384,15 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
     const int msize = a.msize, open = a.open, ext = a.ext;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    int16_t *prof = reinterpret_cast<int16_t *>(lds);                  // [(msize + 1) * BR]: row msize = the pad symbol
-    int16_t *mat = prof + (msize + 1) * BR;                            // [msize * msize]
-    unsigned char *map = reinterpret_cast<unsigned char *>(mat + msize * msize);
-    for (int i = lane; i < msize * msize; i += 64) mat[i] = a.scores[i];
-    for (int i = lane; i < 256; i += 64) map[i] = a.mapper[i];
-    __syncthreads();
-    for (int row = lane; row < BR; row += 64) {                        // the profile carries score + open (the strips carry H - open)
-        const int i = band * BR + row;
-        const int qs = i < ql ? (int)map[q[i]] : -1;
-        for (int sym = 0; sym < msize; ++sym) prof[sym * BR + row] = (int16_t)(qs < 0 ? LONG_PAD : mat[qs * msize + sym] + open + (SKEW ? ext : 0));
-        prof[msize * BR + row] = (int16_t)LONG_PAD;
-    }
-    __syncthreads();
+    unsigned char *map = long_stage_profile<R, SKEW>(a, lds, lane, band, q, ql);
 
-    const bool pen_col = MODE == PMX_MODE_NW || (SG && !(a.sg_flags & PMX_SG_QB));
-    const bool pen_row = MODE == PMX_MODE_NW || (SG && !(a.sg_flags & PMX_SG_DB));
-    auto left = [&](int i) -> int { return i < 0 ? 0 : (pen_col ? -(open + i * ext) : 0); };
-    auto top = [&](int j) -> int { return pen_row ? -(open + j * ext) : 0; };
+    const LongEdges<MODE> rim(a.sg_flags, open, ext);
 
     const int i0 = band * BR + lane * R;
     int H[R], E[R], hs[R], lc[R];
 #pragma unroll
-    for (int k = 0; k < R; ++k) { H[k] = left(i0 + k) - open + (SKEW ? (i0 + k) * ext : 0); E[k] = LONG_NEG; hs[k] = 0; lc[k] = LONG_NEG; }
-    int diag = left(i0 - 1) - open + (SKEW ? (i0 - 1) * ext : 0);
+    for (int k = 0; k < R; ++k) { H[k] = rim.left_strip(i0 + k); E[k] = LONG_NEG; hs[k] = 0; lc[k] = LONG_NEG; }
+    int diag = rim.left_strip(i0 - 1);
     int Hout0 = 0, Hout1 = 0, Fout0 = 0, Fout1 = 0;
     int best = SW ? -open - 1 : 0, bcol = 0;
     const int gstar = ((ql - 1) % BR) / R, kstar = (ql - 1) % R;
@@ -380,8 +417,8 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
     auto prefetch_sym = [&](int base) { const int c = 2 * (base + lane); nraw0 = c < rl ? (int)r[c] : -1; nraw1 = c + 1 < rl ? (int)r[c + 1] : -1; };
     auto load_gran = [&](int base) {
         if (CH == 64 || lane < CH) {
-            ngA = __hip_atomic_load(bin + 2 * (base + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ngB = __hip_atomic_load(bin + 2 * (base + lane) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ngA = long_granule_load(bin + 2 * (base + lane));
+            ngB = long_granule_load(bin + 2 * (base + lane) + 1);
         }
     };
     auto prefetch_bound = [&](int base) { if (bin) load_gran(base); };
@@ -393,24 +430,13 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
     auto waiting = [&]() -> bool { return __builtin_amdgcn_ballot_w64(ngA == LONG_SENT || ngB == LONG_SENT) != 0; };
     auto reload_bound = [&](int base) {
         if (bin && base < CP) {
-            // (bounded wait: see pmx_long32_kernel)
-            for (int spins = 0; !dead && waiting(); spins += 64) {
-                for (int k = 0; k < 64 && waiting(); ++k) {
-                    __builtin_amdgcn_s_sleep(8);
-                    load_gran(base);
-                }
-                if (!waiting()) break;
-                if (spins >= spin_limit || __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    if (lane == 0) __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    dead = true;
-                }
-            }
-            Hb0 = (int)(unsigned)(ngA & 0xFFFFFFFFu); Fb0 = (int)(unsigned)(ngA >> 32);
-            Hb1 = (int)(unsigned)(ngB & 0xFFFFFFFFu); Fb1 = (int)(unsigned)(ngB >> 32);
+            long_wait_for_chunk(dead, spin_limit, abort_word, lane, waiting, [&]() { load_gran(base); });
+            Hb0 = long_granule_h(ngA); Fb0 = long_granule_f(ngA);
+            Hb1 = long_granule_h(ngB); Fb1 = long_granule_f(ngB);
         } else if (bin) {
             Hb0 = 0; Fb0 = 0; Hb1 = 0; Fb1 = 0;
         } else {
-            Hb0 = top(2 * (base + lane)) - open + (SKEW ? 2 * (base + lane) * ext : 0); Hb1 = top(2 * (base + lane) + 1) - open + (SKEW ? (2 * (base + lane) + 1) * ext : 0);
+            Hb0 = rim.top_strip(2 * (base + lane)); Hb1 = rim.top_strip(2 * (base + lane) + 1);
             Fb0 = SW ? 0 : Hb0; Fb1 = SW ? 0 : Hb1;
         }
         if (base + CH < T) prefetch_bound(base + CH);
@@ -503,8 +529,8 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
             }
         }
         if (bout && lane == 63 && (!EDGE || t >= 63)) {
-            __hip_atomic_store(bout + 2 * (t - 63), ((unsigned long long)(unsigned)Fout0 << 32) | (unsigned)Hout0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(bout + 2 * (t - 63) + 1, ((unsigned long long)(unsigned)Fout1 << 32) | (unsigned)Hout1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            long_granule_store(bout + 2 * (t - 63), Hout0, Fout0);
+            long_granule_store(bout + 2 * (t - 63) + 1, Hout1, Fout1);
         }
     };
 
@@ -531,43 +557,7 @@ void pmx_long32_kernel_c2(PmxLongArgs a)
         }
     }
 
-    // ---- this band's candidates (as pmx_long32_kernel; a lane's column of step t is 2 (t - lane) [+ 1]) -----------------------
-    int *cand = a.cand + ((size_t)pair * a.nbmax + band) * 8;
-    if (SW) {
-        int kf = 0;
-#pragma unroll
-        for (int k = R - 1; k >= 0; --k) if (hs[k] == best) kf = k;
-        int sc = best + open, col = bcol - 2 * lane, row = i0 + kf;
-        if (row >= ql) { sc = -1; col = 0x7FFFFFFF; row = 0x7FFFFFFF; }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int os = __shfl_xor(sc, off, 64), oc = __shfl_xor(col, off, 64), orow = __shfl_xor(row, off, 64);
-            const bool take = os > sc || (os == sc && (oc < col || (oc == col && orow < row)));
-            if (take) { sc = os; col = oc; row = orow; }
-        }
-        if (lane == 0) { cand[0] = sc; cand[1] = col; cand[2] = row; }
-    } else {
-        int sc = LONG_NEG, row = 0x7FFFFFFF;
-#pragma unroll
-        for (int k = R - 1; k >= 0; --k) {
-            const int v = lc[k] + open - (SKEW ? ext + (i0 + k + rl - 1) * ext : 0);      // (the offset of cell (i0 + k, rl - 1) comes off)
-            if (i0 + k < ql && v >= sc) { sc = v; row = i0 + k; }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int os = __shfl_xor(sc, off, 64), orow = __shfl_xor(row, off, 64);
-            const bool take = os > sc || (os == sc && orow < row);
-            if (take) { sc = os; row = orow; }
-        }
-        if (lane == 0) { cand[3] = sc; cand[4] = row; }
-        if (lastband && lane == gstar) {
-            int corner = lc[0];
-#pragma unroll
-            for (int k = 1; k < R; ++k) corner = (kstar == k) ? lc[k] : corner;
-            cand[7] = corner + open - (SKEW ? ext + (ql - 1 + rl - 1) * ext : 0);
-            cand[5] = rbest + open - (SKEW ? ext + (ql - 1) * ext : 0); cand[6] = rcol;
-        }
-    }
+    long_candidates<R, MODE, 2>(a.cand + ((size_t)pair * a.nbmax + band) * 8, lane, i0, ql, rl, open, ext, lastband, gstar, kstar, hs, lc, best, bcol, rbest, rcol);
 }
 
 // merges the bands' candidates of every pair into its record
@@ -608,87 +598,124 @@ __global__ void pmx_long_finalize_kernel(PmxLongArgs a, int mode, int R)
     a.out[pair] = rec;
 }
 
-size_t pmx_long_scratch_bytes(long long n, int max_qlen, int max_rlen, int R, long long *bstride, int *nbmax)
+// ---- host: the launchable shapes, the plan, the launch ------------------------------------------------------------------------------
+
+// Every instance there is: rows per lane, columns per step, steps per boundary chunk, checkpoints or not.  f(shape) until one returns
+// true; the planner (is there such an instance?) and the launcher (which one?) walk the same list.
+template <int R_, int COLS_, int STEPS_, bool CK_> struct LongShape { static constexpr int R = R_, cols = COLS_, steps = STEPS_; static constexpr bool ck = CK_; };
+template <int R, int COLS, int STEPS, typename F> static inline bool long_shape(F &f) { return f(LongShape<R, COLS, STEPS, false>{}) || f(LongShape<R, COLS, STEPS, true>{}); }
+template <typename F> static inline bool for_each_long_shape(F &&f)
 {
-    const int BR = 64 * R;
-    *nbmax = (max_qlen + BR - 1) / BR;
-    *bstride = *nbmax > 1 ? (((long long)max_rlen + 127) & ~127LL) + 128 : 0;   // one band per pair: nothing is handed on (the two-column form pads to 128 columns)
-    return (size_t)n * (size_t)*nbmax * ((size_t)*bstride * 8 + 32) + 64;      // + the abort word (the first 64 bytes of the scratch)
+    return long_shape<2, 1, 16>(f) || long_shape<2, 1, 64>(f) || long_shape<4, 1, 16>(f) || long_shape<4, 1, 64>(f) || long_shape<16, 1, 64>(f) ||
+           long_shape<2, 2, 32>(f) || long_shape<2, 2, 64>(f) || long_shape<4, 2, 32>(f) || long_shape<4, 2, 64>(f);
 }
 
-// Column checkpoints of the tiled traceback: slots per (pair, band), and the bytes behind a chunk's other scratch.
-long long pmx_long_ck_slots(int max_rlen, int tile_cols) { return max_rlen / tile_cols + 1; }
-size_t pmx_long_ck_bytes(long long n, int max_qlen, int max_rlen, int R, int tile_cols)
+// What pmx_last_kernel() shows: the instance and its road.
+static const char *long_instance_name(int R, int cols, bool ck)
 {
-    const int BR = 64 * R, nbmax = (max_qlen + BR - 1) / BR;
-    return (size_t)n * nbmax * (size_t)pmx_long_ck_slots(max_rlen, tile_cols) * BR * 8;
+    if (ck) {
+        if (cols == 2) return R == 2 ? "pmx_long32_kernel_c2<2,ck>/checkpoint sweep + pmx_walkt_kernel" : "pmx_long32_kernel_c2<4,ck>/checkpoint sweep + pmx_walkt_kernel";
+        return R == 2 ? "pmx_long32_kernel<2,ck>/checkpoint sweep + pmx_walkt_kernel" : R == 4 ? "pmx_long32_kernel<4,ck>/checkpoint sweep + pmx_walkt_kernel"
+                                                                                               : "pmx_long32_kernel<16,ck>/checkpoint sweep + pmx_walkt_kernel";
+    }
+    if (cols == 2) return R == 2 ? "pmx_long32_kernel_c2<2>/bands across the chip, two columns per step" : "pmx_long32_kernel_c2<4>/bands across the chip, two columns per step";
+    return R == 2 ? "pmx_long32_kernel<2>/bands across the chip" : R == 4 ? "pmx_long32_kernel<4>/bands across the chip" : "pmx_long32_kernel<16>/bands across the chip";
 }
 
-// 0 launched, 1 not eligible, <0 HIP error.  `scratch` = pmx_long_scratch_bytes() bytes.
-// ck != NULL: the checkpoint forms; `ck` = pmx_long_ck_bytes() bytes.
-int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R,
-                    void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, hipStream_t stream, int spin_limit, int chunk_cols, int two_cols,
-                    void *ck, int tile_cols)
+int pmx_long_plan(const PmxLongWant &w, PmxLongPlan *out)
+{
+    if (w.n <= 0 || w.max_qlen <= 0 || w.max_rlen <= 0 || w.msize > 64) return 1;
+    PmxLongPlan p = {};
+    p.msize = w.msize; p.max_qlen = w.max_qlen; p.max_rlen = w.max_rlen;
+    p.ck = w.tile_cols != 0; p.tile_cols = w.tile_cols;
+    if (p.ck) {
+        if (w.tile_cols < 2 || (w.tile_cols & (w.tile_cols - 1))) return 1;
+        while ((1 << p.ckshift) < w.tile_cols) ++p.ckshift;
+        p.ckslots = w.max_rlen / w.tile_cols + 1;
+    }
+    // Per (pair, band): bstride granules of 8 bytes (one band per pair: nothing is handed on; the two-column form pads to 128 columns),
+    // 8 candidate ints, ckslots slots of BR (H, E) pairs.  The score form counts the abort word's 64 bytes with every pair, the checkpoint
+    // form once -- as the roads always have: their chunk sizes stay what they were.
+    size_t band_bytes = 0, band_ck = 0;
+    auto pair_bytes = [&](int R) {
+        const int BR = 64 * R;
+        p.R = R; p.nbmax = (w.max_qlen + BR - 1) / BR;
+        p.bstride = p.nbmax > 1 ? (((long long)w.max_rlen + 127) & ~127LL) + 128 : 0;
+        band_bytes = (size_t)p.bstride * 8 + 32; band_ck = (size_t)p.ckslots * BR * 8;
+        return (size_t)p.nbmax * (band_bytes + band_ck) + (p.ck ? 0 : 64);
+    };
+    size_t pair = pair_bytes(w.R);
+    if (w.r16_above_4g && pair > ((size_t)4 << 30)) pair = pair_bytes(16);
+    if (w.refuse_above_budget && pair > w.budget) return 1;
+    p.pairs = (long long)(w.budget / pair);
+    if (p.pairs < 1) p.pairs = 1;
+    if (p.pairs > w.n) p.pairs = w.n;
+    if (p.pairs * p.nbmax > 0x7FFFFFFFLL) {            // one workgroup per (pair, band)
+        if (!w.clamp_blocks) return 1;
+        p.pairs = 0x7FFFFFFFLL / p.nbmax;
+    }
+
+    const size_t bands = (size_t)p.pairs * p.nbmax;
+    p.off_abort = 0; p.abort_bytes = 64; p.off_bound = p.off_abort + p.abort_bytes;
+    p.off_cand = p.off_bound + bands * (size_t)p.bstride * 8;
+    p.off_ck = p.off_cand + bands * 32;
+    if (p.ck) p.off_ck = (p.off_ck + 255) & ~(size_t)255;
+    p.ck_bytes = bands * band_ck;
+    p.total = p.off_ck + p.ck_bytes;
+
+    p.cols = p.R == 16 ? 1 : (w.cols_few && p.pairs <= 16) ? w.cols_few : w.cols;          // (R = 16 has the one-column form only)
+    p.steps = p.cols == 2 ? (w.chunk_cols == 64 ? 64 : 32) : (p.R != 16 && w.chunk_cols == 16 ? 16 : 64);
+    if (!for_each_long_shape([&](auto s) { return s.R == p.R && s.cols == p.cols && s.steps == p.steps && s.ck == p.ck; })) return 1;
+    p.lds = (size_t)(w.msize + 1) * (64 * p.R) * 2 + (size_t)w.msize * w.msize * 2 + 256 + 16;
+    if (p.lds > 160 * 1024) return 1;
+    p.name = long_instance_name(p.R, p.cols, p.ck);
+    *out = p;
+    return 0;
+}
+
+template <typename S, int MODE> static int launch_long_instance(const PmxLongArgs &a, const PmxLongPlan &p, unsigned blocks, hipStream_t stream)
+{
+    void (*kernel)(PmxLongArgs);
+    if constexpr (S::cols == 2) kernel = &pmx_long32_kernel_c2<S::R, MODE, S::steps, S::ck>;
+    else kernel = &pmx_long32_kernel<S::R, MODE, S::steps, S::ck>;
+    const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(kernel));
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), p.lds, stream, a);
+    return pmx_launched();
+}
+
+int pmx_launch_long(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, const PmxLongPlan &p,
+                    void *scratch, pmx_record_t *d_out, int sat_above, int force_sat, int spin_limit, hipStream_t stream)
 {
     if (m.pssm) return 1;                                   // (symbol profiles only: a PSSM takes the general kernel)
-    if (b.perm || m.msize > 64) return 1;
+    if (b.perm || m.msize != p.msize || b.n <= 0 || b.n > p.pairs || b.max_qlen > p.max_qlen || b.max_rlen > p.max_rlen) return 1;     // (not what was planned)
     if (m.max + open + ext > 32000 || m.min + open < -16000 || open < 0 || ext < 0) return 1;      // int16 profile entries (score + open [+ ext])
     if ((long long)(b.max_qlen + b.max_rlen) * (long long)(ext > open ? ext : open) > (1LL << 29)) return 1;   // boundary values stay above LONG_NEG
+    unsigned char *base = reinterpret_cast<unsigned char *>(scratch);
     PmxLongArgs a;
     a.qbuf = b.qbuf; a.qoff = b.qoff; a.q_shared = b.q_shared; a.rbuf = b.rbuf; a.roff = b.roff; a.n = b.n;
     a.scores = m.scores; a.mapper = m.mapper; a.msize = m.msize; a.sg_flags = sg_flags; a.open = open; a.ext = ext;
-    long long bstride = 0; int nbmax = 0;
-    const size_t bytes = pmx_long_scratch_bytes(b.n, b.max_qlen, b.max_rlen, R, &bstride, &nbmax);
-    a.nbmax = nbmax; a.bstride = bstride;
-    // scratch: [abort word, 64 bytes -- zeroed by the caller before the first launch of a call][boundary granules][candidates]
-    a.abort_word = reinterpret_cast<int *>(scratch);
+    a.nbmax = p.nbmax; a.bstride = p.bstride;
+    a.abort_word = reinterpret_cast<int *>(base + p.off_abort);
     a.spin_limit = spin_limit;
-    a.bound = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(scratch) + 64);
-    const size_t bound_bytes = (size_t)b.n * nbmax * (size_t)bstride * 8;
-    a.cand = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(scratch) + 64 + bound_bytes);
+    a.bound = reinterpret_cast<unsigned long long *>(base + p.off_bound);
+    a.cand = reinterpret_cast<int *>(base + p.off_cand);
     a.out = d_out; a.sat_above = sat_above; a.force_sat = force_sat;
-    a.ck = reinterpret_cast<int2 *>(ck); a.ckslots = 0; a.ckshift = 0;
-    if (ck) {
-        if (tile_cols < 2 || (tile_cols & (tile_cols - 1))) return 1;
-        while ((1 << a.ckshift) < tile_cols) ++a.ckshift;
-        a.ckslots = pmx_long_ck_slots(b.max_rlen, tile_cols);
-    }
-    (void)bytes;
-    hipError_t e = bound_bytes ? hipMemsetAsync(a.bound, 0x80, bound_bytes, stream) : hipSuccess;
+    a.ck = p.ck ? reinterpret_cast<int2 *>(base + p.off_ck) : nullptr; a.ckslots = p.ckslots; a.ckshift = p.ckshift;
+    const size_t bound_bytes = (size_t)b.n * p.nbmax * (size_t)p.bstride * 8;      // (this launch's pairs: a call's last chunk may be shorter)
+    const hipError_t e = bound_bytes ? hipMemsetAsync(a.bound, 0x80, bound_bytes, stream) : hipSuccess;
     if (e != hipSuccess) return -(int)e;
-    const int BR = 64 * R;
-    const size_t lds = (size_t)(m.msize + 1) * BR * 2 + (size_t)m.msize * m.msize * 2 + 256 + 16;
-    if (lds > 160 * 1024) return 1;
-    const long long blocks = b.n * nbmax;
-    if (blocks <= 0 || blocks > 0x7FFFFFFFLL) return 1;
-#define LONG_LAUNCH(RR, MM, CC, KK) do { \
-        const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_long32_kernel<RR, MM, CC, KK>)); if (rc) return rc; \
-        hipLaunchKernelGGL((pmx_long32_kernel<RR, MM, CC, KK>), dim3((unsigned)blocks), dim3(64), lds, stream, a); } while (0)
-#define LONG_MODES(RR, CC, KK) do { \
-        if (mode == PMX_MODE_SW) LONG_LAUNCH(RR, PMX_MODE_SW, CC, KK); else if (mode == PMX_MODE_SG) LONG_LAUNCH(RR, PMX_MODE_SG, CC, KK); else LONG_LAUNCH(RR, PMX_MODE_NW, CC, KK); } while (0)
-#define LONG_LAUNCH2(RR, MM, CC, KK) do { \
-        const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_long32_kernel_c2<RR, MM, CC, KK>)); if (rc) return rc; \
-        hipLaunchKernelGGL((pmx_long32_kernel_c2<RR, MM, CC, KK>), dim3((unsigned)blocks), dim3(64), lds, stream, a); } while (0)
-#define LONG_MODES2(RR, CC, KK) do { \
-        if (mode == PMX_MODE_SW) LONG_LAUNCH2(RR, PMX_MODE_SW, CC, KK); else if (mode == PMX_MODE_SG) LONG_LAUNCH2(RR, PMX_MODE_SG, CC, KK); else LONG_LAUNCH2(RR, PMX_MODE_NW, CC, KK); } while (0)
-    const bool c16 = chunk_cols == 16, c32 = chunk_cols != 64;
-#define LONG_FORMS(KK) do { \
-        if (two_cols && (R == 2 || R == 4)) {                  /* (chunk_cols counts STEPS here: 32 or 64, two columns each) */ \
-            if (R == 2) { if (c32) LONG_MODES2(2, 32, KK); else LONG_MODES2(2, 64, KK); } \
-            else { if (c32) LONG_MODES2(4, 32, KK); else LONG_MODES2(4, 64, KK); } \
-        } \
-        else if (R == 2) { if (c16) LONG_MODES(2, 16, KK); else LONG_MODES(2, 64, KK); } \
-        else if (R == 4) { if (c16) LONG_MODES(4, 16, KK); else LONG_MODES(4, 64, KK); } \
-        else if (R == 16) LONG_MODES(16, 64, KK); \
-        else return 1; } while (0)
-    if (ck) LONG_FORMS(true); else LONG_FORMS(false);
-#undef LONG_FORMS
-#undef LONG_MODES2
-#undef LONG_LAUNCH2
-#undef LONG_MODES
-#undef LONG_LAUNCH
-    e = hipGetLastError();
-    if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(pmx_long_finalize_kernel, dim3((unsigned)((b.n + 63) / 64)), dim3(64), 0, stream, a, mode, R);
+    const unsigned blocks = (unsigned)(b.n * p.nbmax);
+    int rc = 1;
+    for_each_long_shape([&](auto s) {
+        using S = decltype(s);
+        if (S::R != p.R || S::cols != p.cols || S::steps != p.steps || S::ck != p.ck) return false;
+        rc = mode == PMX_MODE_SW ? launch_long_instance<S, PMX_MODE_SW>(a, p, blocks, stream)
+           : mode == PMX_MODE_SG ? launch_long_instance<S, PMX_MODE_SG>(a, p, blocks, stream)
+                                 : launch_long_instance<S, PMX_MODE_NW>(a, p, blocks, stream);
+        return true;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(pmx_long_finalize_kernel, dim3((unsigned)((b.n + 63) / 64)), dim3(64), 0, stream, a, mode, p.R);
     return pmx_launched();
 }

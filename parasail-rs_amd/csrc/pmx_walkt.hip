@@ -188,29 +188,27 @@ size_t pmx_walkt_lds_bytes(int msize, int BR, int tile_cols)
     return (size_t)BR * (tile_cols / 8 + 1) * 4 + (size_t)4 * (tile_cols + 1) * 4 + (size_t)msize * msize * 2 + 256 + BR + tile_cols + 16;
 }
 
-// 0 launched, 1 not eligible (LDS), <0 HIP error.  The scratch is the one pmx_launch_long(.., ck, tile_cols) filled for the same batch.
-int pmx_launch_walkt(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, int R, int tile_cols,
-                     const void *scratch, const void *ck, const pmx_record_t *recs,
+// 0 launched, 1 not eligible (LDS), <0 HIP error.  The scratch is the one pmx_launch_long filled for the same batch by the same plan.
+int pmx_launch_walkt(const PmxBatch &b, const PmxDevMatrix &m, int mode, int sg_flags, int open, int ext, const PmxLongPlan &p,
+                     const void *scratch, const pmx_record_t *recs,
                      const int64_t *slot_qoff, long long ops_base, uint32_t *ops, int32_t *nops, int32_t *textlen,
                      pmx_stats_t *stats_out, hipStream_t stream)
 {
-    if (m.pssm || b.q_shared || b.n <= 0 || b.n > 0x7FFFFFFFLL) return 1;
+    if (m.pssm || b.q_shared || b.n <= 0 || b.n > p.pairs || !p.ck || m.msize != p.msize || b.max_qlen > p.max_qlen || b.max_rlen > p.max_rlen) return 1;
     PmxWalktArgs a;
     a.qbuf = b.qbuf; a.qoff = b.qoff; a.rbuf = b.rbuf; a.roff = b.roff; a.n = b.n;
     a.mapper = m.mapper; a.scores = m.scores; a.msize = m.msize; a.open = open; a.ext = ext; a.mode = mode;
     const PmxEnds ends = pmx_ends(mode, sg_flags);
     a.col_pen = ends.col_pen; a.row_pen = ends.row_pen;
     a.recs = recs;
-    long long bstride = 0; int nbmax = 0;
-    (void)pmx_long_scratch_bytes(b.n, b.max_qlen, b.max_rlen, R, &bstride, &nbmax);
-    a.abort_word = reinterpret_cast<const int *>(scratch);
-    a.bound = reinterpret_cast<const unsigned long long *>(reinterpret_cast<const unsigned char *>(scratch) + 64);
-    a.bstride = bstride; a.nbmax = nbmax;
-    a.ck = reinterpret_cast<const int2 *>(ck); a.ckslots = pmx_long_ck_slots(b.max_rlen, tile_cols); a.ckshift = 0;
-    while ((1 << a.ckshift) < tile_cols) ++a.ckshift;
-    a.BR = 64 * R;
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(scratch);
+    a.abort_word = reinterpret_cast<const int *>(base + p.off_abort);
+    a.bound = reinterpret_cast<const unsigned long long *>(base + p.off_bound);
+    a.bstride = p.bstride; a.nbmax = p.nbmax;
+    a.ck = reinterpret_cast<const int2 *>(base + p.off_ck); a.ckslots = p.ckslots; a.ckshift = p.ckshift;
+    a.BR = 64 * p.R;
     a.slot_qoff = slot_qoff; a.ops_base = ops_base; a.ops = ops; a.nops = nops; a.textlen = textlen; a.stats = stats_out;
-    const size_t lds = pmx_walkt_lds_bytes(m.msize, a.BR, tile_cols);
+    const size_t lds = pmx_walkt_lds_bytes(m.msize, a.BR, p.tile_cols);
     if (lds > 160 * 1024) return 1;
     if (mode == PMX_MODE_SW) {
         const int rc = pmx_ensure_lds_attr(reinterpret_cast<const void *>(&pmx_walkt_kernel<true>)); if (rc) return rc;
