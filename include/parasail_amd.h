@@ -1374,6 +1374,75 @@ void pmx_seed_hits_free(pmx_seed_hits_t *hits);
  * replaces.  A small bound makes the cut of a slice fall after a few rows. */
 int64_t pmx_seed_match_budget(int64_t bytes);
 
+/* Protein seeding (extension): the same stage in front of the translated entries -- a k-mer index of a PROTEIN set over a reduced
+ * alphabet, and a seeding entry whose queries are proteins or nucleotide reads translated on the device in up to six frames.  Its
+ * candidate lists go unchanged into pmx_align_pairs_translated[_device] (a frame byte per pair) and pmx_align_pairs_frameshift[_device]
+ * (a strand byte per pair) (kernels: parasail-rs_amd/csrc/pmx_seed.hip).  pmx_seed_pairs[_device] refuses a letters index
+ * and names this entry; this entry refuses a DNA index and names pmx_seed_pairs.
+ *
+ * Alphabet.  `table` maps a byte to its group 0 .. G - 1 or to 255 (invalid); G = the largest group + 1 must be 2 .. 32 and a letter
+ * takes bits = ceil(log2 G) bits.  pmx_seed_alphabet fills one of the built-in tables (-1: a NULL table, an unknown `which`):
+ * AA20, the twenty amino acids ACDEFGHIKLMNPQRSTVWY, one group each in that order (5 bits), and AA11, the groups KREDQN | C | G | H |
+ * ILV | M | F | Y | W | P | STA in that order (4 bits); either case; '*', 'X', 'B', 'Z' and every other byte are invalid in both.
+ *
+ * Index.  Sequence r has a k-mer at j iff j + k <= len(r) and all k letters are valid.  Its key holds `bits` bits per letter, the first
+ * letter most significant; an empty position's key is 1 << (k * bits).  Order (kmer, seq, pos) ascending, entry layout, the bucket
+ * table (on the top min(k * bits, 22) bits), pmx_seed_index_count, _entries_device and _free: as for a DNA index.  The index owns a
+ * device copy of the table.  pmx_seed_index_bits: the bits per letter, 2 for a DNA index.  Refused before any GPU work (NULL,
+ * pmx_last_error()): a NULL set or table; a table with a group above 31 or with fewer than 2 groups (no valid byte, one group);
+ * k < 2 or k * bits > 62; a set of more than 2^29 - 1 bytes (the nucleotide diagonals below multiply a reference position by 3) or
+ * 2^31 - 1 sequences: index in parts; a set of another device than the current one.
+ *
+ * Queries.  query_mode says what Q holds and which orientations of a row are seeded:
+ *   PMX_SEED_QUERY_LETTERS     Q is in the index's alphabet: one orientation, the row itself, L = W letters; byte 0
+ *   0 .. 5, PMX_FRAMES_*       Q holds nucleotides; an orientation is a FRAME f, candidates per frame; byte = f
+ *   PMX_SEED_CODONS_*          Q holds nucleotides; an orientation is a STRAND s over its three frames 3 s .. 3 s + 2; byte = s
+ * Translation is the translated entries' rule: frame f reads the row as stored (f < 3) or reverse-complemented through
+ * pmx_complement_table (f >= 3) from offset off = f % 3, L_f = (W - off) / 3 letters (none when W < off + 3); `code` (64 letters, NCBI
+ * order) replaces pmx_genetic_code_table, NULL: the standard code; a codon with a byte outside A C G T U (either case) is 'X'.  The
+ * translated letter then goes through the index's table, so 'X' and '*' break a k-mer under the built-in alphabets.
+ *
+ * Frame modes and letters mode.  Position p is a letter of the orientation's translation.  A match is (p, j): the translation has a
+ * k-mer at p, R[r] has a k-mer with the same key at j, and that k-mer has at most max_occ entries in the whole index.  Its diagonal is
+ * d = j - p, in letters.  Clusters, min_seeds, band and pad are the DNA entry's.  The candidate is {q, r, 0, -1, r_beg, r_len} with
+ * r_beg = max(0, d_min - pad), r_end = min(len(r), d_max + L + pad); d_hit_seeds is {n_seeds, d_min, d_max, 0}.  d_hit_pairs /
+ * d_hit_byte are valid d_pairs / d_frame of pmx_align_pairs_translated_device (frame_mode 0) and, in letters mode, d_pairs of
+ * pmx_align_pairs_device, with nothing in between.
+ *
+ * Codon modes.  The matches of frames 3 s, 3 s + 1 and 3 s + 2 are taken TOGETHER, each on its nucleotide diagonal
+ * D = 3 j - (off + 3 p), so D mod 3 tells the frame.  The matches of (q, s, r) ordered by D fall into maximal runs whose consecutive D
+ * differ by at most `band`, in nucleotides here; a run of at least min_seeds matches is a candidate with
+ * r_beg = max(0, floor(D_min / 3) - pad), r_end = min(len(r), floor((D_max + W - 1) / 3) + 1 + pad), floor towards minus infinity,
+ * pad in reference letters; d_hit_seeds is {n_seeds, D_min, D_max, 0}.  A read with one base inserted or deleted therefore yields ONE
+ * candidate whose seeds come from two frames, where the frame modes yield two.  d_hit_pairs / d_hit_byte are valid d_pairs / d_strand
+ * of pmx_align_pairs_frameshift_device.
+ *
+ * max_qlen bounds the letters of the longest translation, W / 3 (letters mode: W); a row above it has no candidates; the host entry
+ * sizes it from the rows.  Position slots are (row, orientation, p), in the codon modes (row, strand, frame, p): max_qlen x 1, 3 or 6
+ * per row (one frame or the row itself; three frames; six), 17 bytes each.  Row q's candidates ascend in (byte, r, diag_min).
+ *
+ * pmx_seed_opts_t and pmx_seed_hits_t are reused: opts->strand must be 0, and the result's `strand` array holds the byte.  capacity,
+ * d_row_off, d_counts, max_hits, slices and the cut read back once per slice, pmx_seed_match_budget, determinism and nq == 0 are what
+ * pmx_seed_pairs[_device] documents.  Refused with -1 before any GPU work: everything pmx_seed_pairs_device refuses, with its texts
+ * (the strand mode apart); opts->strand != 0; a query_mode outside the values below; a DNA index; one row's worst case,
+ * max_qlen x orientations x max_occ x 24 bytes, above the match buffer. */
+#define PMX_SEED_ALPHABET_AA20 0   /* ACDEFGHIKLMNPQRSTVWY, one group each, either case: 5 bits */
+#define PMX_SEED_ALPHABET_AA11 1   /* KREDQN | C | G | H | ILV | M | F | Y | W | P | STA, either case: 4 bits */
+int  pmx_seed_alphabet(int which, uint8_t table[256]);          /* group 0 .. G-1 per byte, 255 = invalid */
+pmx_seed_index_t *pmx_seed_index_build_letters(const pmx_seqset_t *R, int32_t k, const uint8_t table[256], void *stream);
+int32_t pmx_seed_index_bits(const pmx_seed_index_t *index);     /* bits per letter; 2 for a DNA index; -1 for NULL */
+#define PMX_SEED_QUERY_LETTERS  (-1)  /* Q is in the index's alphabet; one orientation, byte 0 */
+/* 0 .. 5, PMX_FRAMES_FORWARD / _REVERSE / _ALL: Q holds nucleotides; candidates per FRAME, byte = frame */
+#define PMX_SEED_CODONS_FORWARD  9    /* Q holds nucleotides; candidates per STRAND over its three frames, byte = strand 0 */
+#define PMX_SEED_CODONS_REVERSE 10    /* ... byte = strand 1 */
+#define PMX_SEED_CODONS_BOTH    11    /* both strands, listed separately */
+int pmx_seed_pairs_letters_device(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq, int32_t max_qlen,
+                                  const pmx_seed_opts_t *opts, int query_mode, const uint8_t *code /* 64 letters or NULL */,
+                                  pmx_pair_t *d_hit_pairs, uint8_t *d_hit_byte, pmx_seed_hit_t *d_hit_seeds, int64_t capacity,
+                                  int64_t *d_row_off, int64_t *d_counts, void *stream);
+int pmx_seed_pairs_letters(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq,
+                           const pmx_seed_opts_t *opts, int query_mode, const uint8_t *code, pmx_seed_hits_t **result);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

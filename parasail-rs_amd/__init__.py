@@ -304,6 +304,13 @@ _sig("pmx_seed_pairs", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.
      C.POINTER(C.POINTER(pmx_seed_hits_t)))
 _sig("pmx_seed_hits_free", None, C.POINTER(pmx_seed_hits_t))
 _sig("pmx_seed_match_budget", C.c_int64, C.c_int64)
+_sig("pmx_seed_alphabet", C.c_int, C.c_int, C.c_void_p)
+_sig("pmx_seed_index_build_letters", C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_index_bits", C.c_int32, C.c_void_p)
+_sig("pmx_seed_pairs_letters_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(pmx_seed_opts_t), C.c_int,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_pairs_letters", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(pmx_seed_opts_t), C.c_int, C.c_void_p,
+     C.POINTER(C.POINTER(pmx_seed_hits_t)))
 _sig("pmx_topk_records_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_align_pairs_both", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1821,19 +1828,56 @@ class SeqSet:
             pass
 
 
-class SeedIndex:
-    """The k-mer index of a DNA set (pmx_seed_index_t): every k-mer of R as (kmer, seq, pos), sorted, on R's device.  R is held:
-    it outlives the index.  len(): the entries.  Released by close() or on deletion."""
+SEED_ALPHABET_AA20, SEED_ALPHABET_AA11 = 0, 1
+SEED_QUERY_LETTERS, SEED_CODONS_FORWARD, SEED_CODONS_REVERSE, SEED_CODONS_BOTH = -1, 9, 10, 11
 
-    def __init__(self, inner, R, k):
-        self.inner, self.R, self.k = inner, R, int(k)
+
+def seed_alphabet(which):
+    """A built-in reduced alphabet as the 256-byte table a letters index takes (uint8 [256]: group per byte, 255 = invalid):
+    "aa20" / SEED_ALPHABET_AA20, the twenty amino acids, or "aa11" / SEED_ALPHABET_AA11, eleven groups of them."""
+    if isinstance(which, str):
+        names = {"aa20": SEED_ALPHABET_AA20, "aa11": SEED_ALPHABET_AA11}
+        if which not in names:
+            raise BatchError("alphabet is \"aa20\", \"aa11\" or a table of 256 bytes")
+        which = names[which]
+    tab = np.zeros(256, dtype=np.uint8)
+    if lib.pmx_seed_alphabet(int(which), tab.ctypes.data):
+        raise BatchError(lib.pmx_last_error().decode())
+    return tab
+
+
+class SeedIndex:
+    """The k-mer index of a set (pmx_seed_index_t): every k-mer of R as (kmer, seq, pos), sorted, on R's device -- of a DNA set, or
+    with `alphabet` of a protein set over a reduced alphabet (a letters index; .letters, .bits per letter).  R is held: it outlives
+    the index.  len(): the entries.  Released by close() or on deletion."""
+
+    def __init__(self, inner, R, k, letters=False):
+        self.inner, self.R, self.k, self.letters = inner, R, int(k), bool(letters)
 
     @classmethod
-    def build(cls, R, k, stream=0):
-        inner = lib.pmx_seed_index_build(R._handle(), int(k), stream)
+    def build(cls, R, k, alphabet=None, stream=0):
+        """alphabet: None (a DNA index), "aa20", "aa11" or 256 bytes that map a byte to its group 0 .. 31 or to 255.  An integer in
+        its place is the stream of a DNA index, build(R, k, stream), as before there were alphabets."""
+        if isinstance(alphabet, (int, np.integer)) and not isinstance(alphabet, bool):
+            alphabet, stream = None, int(alphabet)
+        if alphabet is None:
+            inner = lib.pmx_seed_index_build(R._handle(), int(k), stream)
+        else:
+            if isinstance(alphabet, str):
+                table = seed_alphabet(alphabet)
+            else:
+                table = np.ascontiguousarray(np.frombuffer(alphabet, dtype=np.uint8) if isinstance(alphabet, (bytes, bytearray)) else alphabet,
+                                             dtype=np.uint8)
+                if table.shape != (256,):
+                    raise BatchError("alphabet is \"aa20\", \"aa11\" or a table of 256 bytes")
+            inner = lib.pmx_seed_index_build_letters(R._handle(), int(k), table.ctypes.data, stream)
         if not inner:
             raise BatchError(lib.pmx_last_error().decode())
-        return cls(inner, R, k)
+        return cls(inner, R, k, alphabet is not None)
+
+    @property
+    def bits(self):
+        return int(lib.pmx_seed_index_bits(self._handle()))
 
     def _handle(self):
         if not self.inner:
@@ -1860,9 +1904,11 @@ class SeedHits:
     """Result of seed_pairs, CSR by query row: row_off (int64, n_rows + 1, never capped by max_hits), n_passing (the candidates)
     and, per stored candidate, pairs (PAIR_DTYPE: query, reference and reference window, fit for Aligner.align_pairs), strand
     (uint8) and seeds (SEED_HIT_DTYPE: matches and the diagonals' range).  A row's candidates are in (strand, reference,
-    diag_min) order; row(i) slices out those that were stored."""
+    diag_min) order; row(i) slices out those that were stored.  Of a letters index (seed_pairs(frames=)) the byte per candidate
+    is a frame in the frame modes -- .frame holds it, else .frame is None -- and a strand in the codon modes -- .strand holds it;
+    .strand is zeros in the letters and frame modes."""
 
-    def __init__(self, r):
+    def __init__(self, r, byte_is_frame=False):
         h, n = int(r.n_hits), int(r.n_rows)
         self.n_rows, self.n_hits, self.n_passing = n, h, int(r.n_passing)
 
@@ -1874,6 +1920,9 @@ class SeedHits:
         self.pairs = take(r.pairs, h, PAIR_DTYPE)
         self.strand = take(r.strand, h, np.uint8)
         self.seeds = take(r.seeds, h, SEED_HIT_DTYPE)
+        self.frame = None
+        if byte_is_frame:
+            self.frame, self.strand = self.strand, np.zeros(h, dtype=np.uint8)
 
     def __len__(self):
         return self.n_hits
@@ -1888,29 +1937,75 @@ def _seed_opts(strand, min_seeds, band, pad, max_occ, max_hits=0, slice_rows=0):
     return pmx_seed_opts_t(_strand_mode(strand), int(min_seeds), int(band), int(pad), int(max_occ), 0, int(max_hits), int(slice_rows))
 
 
-def seed_pairs(Q, index, strand="both", min_seeds=2, band=8, pad=16, max_occ=64, first_row=0, rows=None, max_hits=0, slice_rows=0):
+def _seed_query_mode(index, frames, strand):
+    """frames= of seed_pairs -> the query mode of a letters index (None: a DNA index, which takes strand= instead)."""
+    if not index.letters:
+        if frames is not None:
+            raise BatchError("frames= is for a letters index (SeedIndex.build(alphabet=)); a DNA index takes strand=")
+        return None
+    if frames is None:
+        raise BatchError("a letters index needs frames=: \"letters\", a frame 0 .. 5, \"forward\", \"reverse\", \"all\", \"codons\", "
+                         "\"codons-reverse\" or \"codons-both\"")
+    if strand is not None:
+        raise BatchError("strand= is for a DNA index; frames= chooses the orientations of a letters index")
+    names = {"letters": SEED_QUERY_LETTERS, "forward": FRAMES_FORWARD, "reverse": FRAMES_REVERSE, "all": FRAMES_ALL,
+             "codons": SEED_CODONS_FORWARD, "codons-reverse": SEED_CODONS_REVERSE, "codons-both": SEED_CODONS_BOTH}
+    if isinstance(frames, str):
+        if frames not in names:
+            raise BatchError("frames is \"letters\", 0 .. 5, \"forward\", \"reverse\", \"all\", \"codons\", \"codons-reverse\" or \"codons-both\"")
+        return names[frames]
+    if isinstance(frames, (bool, np.bool_)) or not 0 <= int(frames) <= 5:
+        raise BatchError("frames is \"letters\", 0 .. 5, \"forward\", \"reverse\", \"all\", \"codons\", \"codons-reverse\" or \"codons-both\"")
+    return int(frames)
+
+
+def seed_pairs(Q, index, strand=None, min_seeds=2, band=8, pad=16, max_occ=64, first_row=0, rows=None, max_hits=0, slice_rows=0,
+               frames=None, code=None):
     """Candidate windows of the queries Q[first_row : first_row + rows] in the indexed reference: exact k-mer matches, clustered
     by diagonal (consecutive diagonals at most `band` apart), clusters of at least min_seeds matches widened by `pad`.
-    hits.pairs and hits.strand go unchanged into Aligner.align_pairs(Q, R, pairs, strand=, cigar=True)."""
+    hits.pairs and hits.strand go unchanged into Aligner.align_pairs(Q, R, pairs, strand=, cigar=True)  (strand: "both" unless given).
+    With a letters index `frames` says what Q holds: "letters" (proteins in the index's alphabet), a frame 0 .. 5, "forward", "reverse"
+    or "all" (nucleotides, candidates per frame: align_pairs(Q, R, hits.pairs, frame=hits.frame)), "codons", "codons-reverse" or
+    "codons-both" (nucleotides, candidates per strand over its three frames, diagonals and band in nucleotides:
+    align_pairs(Q, R, hits.pairs, frameshift=fs, strand=hits.strand)); code: 64 letters that replace the standard genetic code."""
     if rows is None:
         rows = max(0, len(Q) - int(first_row))
-    opts = _seed_opts(strand, min_seeds, band, pad, max_occ, max_hits, slice_rows)
+    mode = _seed_query_mode(index, frames, strand)
+    opts = _seed_opts(0 if mode is not None else "both" if strand is None else strand, min_seeds, band, pad, max_occ, max_hits, slice_rows)
     res = C.POINTER(pmx_seed_hits_t)()
-    if lib.pmx_seed_pairs(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), C.byref(res)):
+    if mode is None:
+        if code is not None:
+            raise BatchError("code= is for a letters index")
+        rc = lib.pmx_seed_pairs(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), C.byref(res))
+    else:
+        code = _code_arg(code)
+        rc = lib.pmx_seed_pairs_letters(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), mode,
+                                        code.ctypes.data if code is not None else None, C.byref(res))
+    if rc:
         raise BatchError(lib.pmx_last_error().decode())
     try:
-        return SeedHits(res.contents)
+        return SeedHits(res.contents, byte_is_frame=mode is not None and 0 <= mode <= FRAMES_ALL)
     finally:
         lib.pmx_seed_hits_free(res)
 
 
 def seed_pairs_device(Q, index, q_first, nq, max_qlen, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts,
-                      strand="both", min_seeds=2, band=8, pad=16, max_occ=64, slice_rows=0, stream=0):
+                      strand=None, min_seeds=2, band=8, pad=16, max_occ=64, slice_rows=0, stream=0, frames=None, code=None):
     """Device-pointer entry of seed_pairs: the candidates go to d_hit_pairs / d_hit_strand / d_hit_seeds (optional), `capacity`
-    entries each, d_row_off gets nq + 1 offsets and d_counts [candidates, written].  Synchronises `stream` once per slice."""
-    opts = _seed_opts(strand, min_seeds, band, pad, max_occ, 0, slice_rows)
-    rc = lib.pmx_seed_pairs_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), d_hit_pairs,
-                                   d_hit_strand, d_hit_seeds, int(capacity), d_row_off, d_counts, stream)
+    entries each, d_row_off gets nq + 1 offsets and d_counts [candidates, written].  Synchronises `stream` once per slice.  With a
+    letters index (frames=) d_hit_strand receives the frame or strand byte and max_qlen bounds the letters of a translation."""
+    mode = _seed_query_mode(index, frames, strand)
+    opts = _seed_opts(0 if mode is not None else "both" if strand is None else strand, min_seeds, band, pad, max_occ, 0, slice_rows)
+    if mode is None:
+        if code is not None:
+            raise BatchError("code= is for a letters index")
+        rc = lib.pmx_seed_pairs_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), d_hit_pairs,
+                                       d_hit_strand, d_hit_seeds, int(capacity), d_row_off, d_counts, stream)
+    else:
+        code = _code_arg(code)
+        rc = lib.pmx_seed_pairs_letters_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), mode,
+                                               code.ctypes.data if code is not None else None, d_hit_pairs, d_hit_strand, d_hit_seeds,
+                                               int(capacity), d_row_off, d_counts, stream)
     if rc:
         raise BatchError(lib.pmx_last_error().decode())
 

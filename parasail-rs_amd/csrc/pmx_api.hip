@@ -5826,6 +5826,9 @@ struct pmx_seed_index {
     int k = 0, shift = 0, dev = -1;        // bucket of a key: key >> shift
     int64_t n = 0, nb = 0;                 // entries; buckets (the table holds nb + 1 numbers)
     uint64_t *keys = nullptr, *vals = nullptr; uint32_t *bucket = nullptr;
+    int bits = 2;                          // per letter
+    bool letters = false;                  // built by pmx_seed_index_build_letters: `table` holds the groups, d_table their device copy
+    uint8_t table[256] = {0}; uint8_t *d_table = nullptr;
 };
 static const int PMX_SEED_BUCKET_BITS = 22;            // 2^22 + 1 numbers of 4 bytes: 16 MiB, resident in the Infinity Cache
 static const int32_t PMX_SEED_BAND_MAX = 1 << 20;
@@ -5841,11 +5844,11 @@ extern "C" int64_t pmx_seed_match_budget(int64_t bytes)
 extern "C" void pmx_seed_index_free(pmx_seed_index_t *ix)
 {
     if (!ix) return;
-    if (ix->keys || ix->vals || ix->bucket) {
+    if (ix->keys || ix->vals || ix->bucket || ix->d_table) {
         int dev = -1;
         const bool move = hipGetDevice(&dev) == hipSuccess && dev != ix->dev;
         if (move) (void)hipSetDevice(ix->dev);
-        (void)hipFree(ix->keys); (void)hipFree(ix->vals); (void)hipFree(ix->bucket);
+        (void)hipFree(ix->keys); (void)hipFree(ix->vals); (void)hipFree(ix->bucket); (void)hipFree(ix->d_table);
         if (move) (void)hipSetDevice(dev);
     }
     delete ix;
@@ -5853,26 +5856,22 @@ extern "C" void pmx_seed_index_free(pmx_seed_index_t *ix)
 
 extern "C" int64_t pmx_seed_index_count(const pmx_seed_index_t *ix) { return ix ? ix->n : -1; }
 
-extern "C" pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t k, void *stream)
+// The index of R behind the entries' checks; table: the 256 groups of a letters index of `bits` bits per letter, NULL: the DNA index
+static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int32_t k, int bits, const uint8_t *table, void *stream)
 {
-    if (!R) { set_err("null sequence set"); return nullptr; }
-    if (k < 8 || k > 31) { set_err("k %d is outside 8 .. 31", (int)k); return nullptr; }
-    if (R->bytes > INT32_MAX || R->count > INT32_MAX) {
-        set_err("a seed index holds a set of at most 2^31 - 1 bytes and sequences (this one: %lld bytes, %lld sequences): index parts of it",
-                (long long)R->bytes, (long long)R->count);
-        return nullptr;
-    }
     pmx_seed_index *ix = new (std::nothrow) pmx_seed_index();
     if (!ix) { set_err("out of memory"); return nullptr; }
-    ix->R = R; ix->k = k; ix->dev = R->dev;
-    const int bbits = std::min(2 * k, PMX_SEED_BUCKET_BITS);
-    ix->shift = 2 * k - bbits; ix->nb = (int64_t)1 << bbits;
+    ix->R = R; ix->k = k; ix->dev = R->dev; ix->bits = bits; ix->letters = table != nullptr;
+    if (table) memcpy(ix->table, table, 256);
+    const int bbits = std::min(bits * k, PMX_SEED_BUCKET_BITS);
+    ix->shift = bits * k - bbits; ix->nb = (int64_t)1 << bbits;
     if (R->bytes == 0 || R->count == 0) return ix;               // nothing to index: no entry, no device memory, no GPU work
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); delete ix; return nullptr; }
     if (R->dev != dev) { set_err("a sequence set of device %d cannot be used on the current device %d", R->dev, dev); delete ix; return nullptr; }
     const hipStream_t st = (hipStream_t)stream;
-    const size_t nbytes = (size_t)R->bytes, temp_bytes = pmx_seed_index_sort_bytes(R->bytes, k);
+    const size_t nbytes = (size_t)R->bytes;
+    const size_t temp_bytes = table ? pmx_seed_index_sort_bytes_letters(R->bytes, k, bits) : pmx_seed_index_sort_bytes(R->bytes, k);
     uint64_t *kin = nullptr, *vin = nullptr; void *temp = nullptr; unsigned long long *d_n = nullptr, h_n = 0;
     hipError_t e = hipMalloc((void **)&ix->keys, nbytes * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&ix->vals, nbytes * 8);
@@ -5882,8 +5881,13 @@ extern "C" pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t
     if (e == hipSuccess) e = hipMalloc(&temp, temp_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&d_n, sizeof h_n);
     if (e == hipSuccess) e = hipMemsetAsync(d_n, 0, sizeof h_n, st);
+    if (e == hipSuccess && table) e = hipMalloc((void **)&ix->d_table, 256);
+    if (e == hipSuccess && table) e = hipMemcpyAsync(ix->d_table, ix->table, 256, hipMemcpyHostToDevice, st);
     int rc = 0;
-    if (e == hipSuccess) rc = pmx_launch_seed_index(R->d_buf, R->d_off, R->count, R->bytes, k, kin, vin, ix->keys, ix->vals, temp, temp_bytes, d_n, st);
+    if (e == hipSuccess && table)
+        rc = pmx_launch_seed_index_letters(R->d_buf, R->d_off, R->count, R->bytes, k, bits, ix->d_table, kin, vin, ix->keys, ix->vals, temp, temp_bytes, d_n, st);
+    else if (e == hipSuccess)
+        rc = pmx_launch_seed_index(R->d_buf, R->d_off, R->count, R->bytes, k, kin, vin, ix->keys, ix->vals, temp, temp_bytes, d_n, st);
     if (e == hipSuccess && !rc) e = hipMemcpyAsync(&h_n, d_n, sizeof h_n, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
     if (e == hipSuccess && !rc) { ix->n = (int64_t)h_n; rc = pmx_launch_seed_buckets(ix->keys, ix->n, ix->shift, ix->nb, ix->bucket, st); }
@@ -5894,6 +5898,59 @@ extern "C" pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t
         pmx_seed_index_free(ix); return nullptr;
     }
     return ix;
+}
+
+extern "C" pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t k, void *stream)
+{
+    if (!R) { set_err("null sequence set"); return nullptr; }
+    if (k < 8 || k > 31) { set_err("k %d is outside 8 .. 31", (int)k); return nullptr; }
+    if (R->bytes > INT32_MAX || R->count > INT32_MAX) {
+        set_err("a seed index holds a set of at most 2^31 - 1 bytes and sequences (this one: %lld bytes, %lld sequences): index parts of it",
+                (long long)R->bytes, (long long)R->count);
+        return nullptr;
+    }
+    return seed_index_build(R, k, 2, nullptr, stream);
+}
+
+// The built-in reduced alphabets: one string of letters per group
+static const char *const PMX_SEED_AA20[] = {"A", "C", "D", "E", "F", "G", "H", "I", "K", "L", "M", "N", "P", "Q", "R", "S", "T", "V", "W", "Y", nullptr};
+static const char *const PMX_SEED_AA11[] = {"KREDQN", "C", "G", "H", "ILV", "M", "F", "Y", "W", "P", "STA", nullptr};
+
+extern "C" int pmx_seed_alphabet(int which, uint8_t table[256])
+{
+    if (!table) { set_err("null table"); return -1; }
+    if (which != PMX_SEED_ALPHABET_AA20 && which != PMX_SEED_ALPHABET_AA11) {
+        set_err("alphabet %d is neither PMX_SEED_ALPHABET_AA20 (0) nor PMX_SEED_ALPHABET_AA11 (1)", which); return -1;
+    }
+    memset(table, 255, 256);
+    const char *const *groups = which == PMX_SEED_ALPHABET_AA20 ? PMX_SEED_AA20 : PMX_SEED_AA11;
+    for (int g = 0; groups[g]; ++g)
+        for (const char *c = groups[g]; *c; ++c) { table[(unsigned char)*c] = (uint8_t)g; table[(unsigned char)*c + 32] = (uint8_t)g; }
+    return 0;
+}
+
+extern "C" int32_t pmx_seed_index_bits(const pmx_seed_index_t *ix) { return ix ? ix->bits : -1; }
+
+extern "C" pmx_seed_index_t *pmx_seed_index_build_letters(const pmx_seqset_t *R, int32_t k, const uint8_t table[256], void *stream)
+{
+    if (!R) { set_err("null sequence set"); return nullptr; }
+    if (!table) { set_err("null alphabet table"); return nullptr; }
+    int groups = 0;
+    for (int b = 0; b < 256; ++b) {
+        if (table[b] == 255) continue;
+        if (table[b] > 31) { set_err("the alphabet table maps byte %d to group %d: groups are 0 .. 31, 255 marks an invalid byte", b, (int)table[b]); return nullptr; }
+        groups = std::max(groups, (int)table[b] + 1);
+    }
+    if (groups < 2) { set_err("the alphabet table holds %d group(s): an alphabet has 2 .. 32", groups); return nullptr; }
+    int bits = 1;
+    while ((1 << bits) < groups) ++bits;
+    if (k < 2 || (int64_t)k * bits > 62) { set_err("k %d with %d bits per letter is outside k >= 2 and k x bits <= 62", (int)k, bits); return nullptr; }
+    if (R->bytes > ((int64_t)1 << 29) - 1 || R->count > INT32_MAX) {
+        set_err("a letters seed index holds a set of at most 2^29 - 1 bytes and 2^31 - 1 sequences (this one: %lld bytes, %lld sequences): index parts of it",
+                (long long)R->bytes, (long long)R->count);
+        return nullptr;
+    }
+    return seed_index_build(R, k, bits, table, stream);
 }
 
 extern "C" int pmx_seed_index_entries_device(const pmx_seed_index_t *ix, int64_t first, int64_t count, uint64_t *d_kmer, int64_t *d_seq,
@@ -5914,15 +5971,33 @@ extern "C" int pmx_seed_index_entries_device(const pmx_seed_index_t *ix, int64_t
     return rc;
 }
 
-// What both seeding entries refuse about their arguments; lens_known false: the host entry before it has looked at the lengths
-// (max_qlen and the budget rule are checked in its second call).
-static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t *o,
-                      int64_t capacity, bool lens_known = true)
+static bool seed_mode_valid(int query_mode) { return query_mode >= PMX_SEED_QUERY_LETTERS && query_mode <= PMX_SEED_CODONS_BOTH; }
+// orientation slots per row: the row itself, one frame, three frames (one strand's), six
+static int seed_mode_orients(int query_mode)
 {
+    if (query_mode <= 5) return 1;
+    return query_mode == PMX_FRAMES_ALL || query_mode == PMX_SEED_CODONS_BOTH ? 6 : 3;
+}
+
+// How an entry reads its rows.  DNA entries: orients = the strands, first = the first one.  Letters entries: orients =
+// the orientation slots per row, first = the first one's frame (< 0: the rows are letters), codon = the codon modes.
+struct SeedMode {
+    bool letters = false, codon = false; int orients = 1, first = 0; PmxCodeTable code;
+};
+#define PMX_SEED_MODE_DNA INT32_MIN                     // query_mode of the DNA entries inside this file
+
+// What the seeding entries refuse about their arguments; lens_known false: the host entry before it has looked at the lengths
+// (max_qlen and the budget rule are checked in its second call).  query_mode: PMX_SEED_MODE_DNA or the letters entry's mode.
+static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t *o,
+                      int64_t capacity, bool lens_known = true, int query_mode = PMX_SEED_MODE_DNA)
+{
+    const bool dna = query_mode == PMX_SEED_MODE_DNA;
     if (!lens_known) max_qlen = 1;
     if (!Q) { set_err("null sequence set"); return -1; }
     if (!ix) { set_err("null seed index"); return -1; }
     if (!o) { set_err("null opts"); return -1; }
+    if (dna && ix->letters) { set_err("a letters index (pmx_seed_index_build_letters) is seeded by pmx_seed_pairs_letters[_device]"); return -1; }
+    if (!dna && !ix->letters) { set_err("a DNA index (pmx_seed_index_build) is seeded by pmx_seed_pairs[_device]"); return -1; }
     if (q_first < 0 || nq < 0) { set_err("negative q_first or nq"); return -1; }
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (o->max_hits < 0) { set_err("max_hits must not be negative"); return -1; }
@@ -5932,20 +6007,42 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_f
         return -1;
     }
     if (max_qlen < 1) { set_err("max_qlen must be positive"); return -1; }
-    if (o->strand < PMX_STRAND_FORWARD || o->strand > PMX_STRAND_BOTH) { set_err("strand mode %d is outside 0 .. 2", (int)o->strand); return -1; }
+    if (dna && (o->strand < PMX_STRAND_FORWARD || o->strand > PMX_STRAND_BOTH)) { set_err("strand mode %d is outside 0 .. 2", (int)o->strand); return -1; }
+    if (!dna && o->strand != 0) { set_err("opts->strand %d must be 0 with a letters index: query_mode chooses the orientations", (int)o->strand); return -1; }
+    if (!dna && !seed_mode_valid(query_mode)) {
+        set_err("query mode %d is none of PMX_SEED_QUERY_LETTERS (-1), a frame 0 .. 5, PMX_FRAMES_FORWARD / _REVERSE / _ALL (6 .. 8), "
+                "PMX_SEED_CODONS_FORWARD / _REVERSE / _BOTH (9 .. 11)", query_mode);
+        return -1;
+    }
     if (o->min_seeds < 1) { set_err("min_seeds %d is below 1", (int)o->min_seeds); return -1; }
     if (o->band < 0 || o->band > PMX_SEED_BAND_MAX) { set_err("band %d is outside 0 .. 2^20", (int)o->band); return -1; }
     if (o->pad < 0 || o->pad > PMX_SEED_BAND_MAX) { set_err("pad %d is outside 0 .. 2^20", (int)o->pad); return -1; }
     if (o->max_occ < 1 || o->max_occ > 65535) { set_err("max_occ %d is outside 1 .. 65535", (int)o->max_occ); return -1; }
     if (o->reserved != 0) { set_err("reserved must be 0"); return -1; }
-    const int64_t strands = o->strand == PMX_STRAND_BOTH ? 2 : 1;
+    const int64_t strands = dna ? (o->strand == PMX_STRAND_BOTH ? 2 : 1) : seed_mode_orients(query_mode);
     const double worst = (double)max_qlen * (double)strands * (double)o->max_occ * (double)PMX_SEED_MATCH_BYTES;
     if (worst > (double)seed_match_budget()) {
-        set_err("one row's worst case of %d positions x %d strand(s) x max_occ %d x %d bytes per match does not fit the match buffer of %lld bytes: "
-                "lower max_occ or split the queries", (int)max_qlen, (int)strands, (int)o->max_occ, PMX_SEED_MATCH_BYTES, (long long)seed_match_budget());
+        set_err("one row's worst case of %d positions x %d %s x max_occ %d x %d bytes per match does not fit the match buffer of %lld bytes: "
+                "lower max_occ or split the queries", (int)max_qlen, (int)strands, dna ? "strand(s)" : "orientation(s)", (int)o->max_occ,
+                PMX_SEED_MATCH_BYTES, (long long)seed_match_budget());
         return -1;
     }
     return 0;
+}
+
+static SeedMode seed_mode_dna(const pmx_seed_opts_t *o)
+{
+    SeedMode m; m.orients = o->strand == PMX_STRAND_BOTH ? 2 : 1; m.first = o->strand == PMX_STRAND_REVERSE ? 1 : 0;
+    return m;
+}
+static SeedMode seed_mode_letters(int query_mode, const uint8_t *code)
+{
+    SeedMode m; m.letters = true; m.orients = seed_mode_orients(query_mode);
+    m.codon = query_mode >= PMX_SEED_CODONS_FORWARD;
+    m.first = query_mode == PMX_SEED_QUERY_LETTERS ? -1 : query_mode <= 5 ? query_mode
+            : query_mode == PMX_FRAMES_REVERSE || query_mode == PMX_SEED_CODONS_REVERSE ? 3 : 0;
+    if (code) memcpy(m.code.v, code, 64); else pmx_genetic_code_host(m.code.v);
+    return m;
 }
 
 static int seed_device_check(const pmx_seqset *Q, const pmx_seed_index *ix)
@@ -5960,14 +6057,14 @@ static int seed_device_check(const pmx_seqset *Q, const pmx_seed_index *ix)
 // nq > 0 rows behind the checks.  Synchronises `st` once per slice: the cut is read back.
 static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t *o,
                     pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off,
-                    int64_t *d_counts, hipStream_t st)
+                    int64_t *d_counts, hipStream_t st, const SeedMode &mode)
 {
     HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), st));
     if (ix->n == 0) { HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st)); return 0; }
     HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), st));
-    const int strands = o->strand == PMX_STRAND_BOTH ? 2 : 1, strand0 = o->strand == PMX_STRAND_REVERSE ? 1 : 0;
+    const int strands = mode.orients, strand0 = mode.first;
     const int64_t per_row = (int64_t)strands * max_qlen;
-    int64_t slice = std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / (per_row * PMX_SEED_POS_BYTES));
+    int64_t slice = std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / (per_row * (mode.letters ? PMX_SEED_POS_BYTES_LETTERS : PMX_SEED_POS_BYTES)));
     if (o->slice_rows > 0) slice = std::min(slice, o->slice_rows);
     slice = std::min(slice, nq);
     // the match buffer: the budget, or the slice's worst case when that is smaller (positions fit 32 bits)
@@ -5976,38 +6073,47 @@ static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_fir
     const int64_t positions = slice * per_row, slots = slice * strands;
     const size_t temp_bytes = pmx_seed_temp_bytes(positions, cap_m, slots);
     uint32_t *lo = nullptr, *cnt = nullptr, *head = nullptr, *flag = nullptr; int64_t *moff = nullptr, *cut = nullptr;
-    uint64_t *ka = nullptr, *kb = nullptr; unsigned char *temp = nullptr;
+    uint64_t *ka = nullptr, *kb = nullptr; unsigned char *temp = nullptr; uint8_t *codes = nullptr;
     if (scratch_carve(SCR_SEED, [&](Carver &c) {
             lo = c.take<uint32_t>((size_t)positions); cnt = c.take<uint32_t>((size_t)positions + 1); moff = c.take<int64_t>((size_t)positions + 1);
             ka = c.take<uint64_t>((size_t)cap_m); kb = c.take<uint64_t>((size_t)cap_m);
             head = c.take<uint32_t>((size_t)cap_m); flag = c.take<uint32_t>((size_t)cap_m + 1);
             cut = c.take<int64_t>(2); temp = c.take<unsigned char>(temp_bytes);
+            if (mode.letters) codes = c.take<uint8_t>((size_t)positions);
         })) return -1;
     int key_bits = 33;                                   // the diagonal and the bits of a reference index
     while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < ix->R->count) ++key_bits;
     for (int64_t row = 0; row < nq;) {
         const int64_t rows = std::min(slice, nq - row);
-        int rc = pmx_launch_seed_count(Q->d_buf, Q->d_off, Q->bytes, q_first + row, rows, strands, strand0, max_qlen, ix->k, ix->keys, ix->bucket,
-                                       ix->shift, o->max_occ, lo, cnt, moff, cap_m, cut, temp, temp_bytes, st);
+        int rc = mode.letters
+            ? pmx_launch_seed_count_letters(Q->d_buf, Q->d_off, Q->bytes, q_first + row, rows, strands, strand0, max_qlen, ix->k, ix->bits, ix->d_table,
+                                            mode.code, codes, ix->keys, ix->bucket, ix->shift, o->max_occ, lo, cnt, moff, cap_m, cut, temp, temp_bytes, st)
+            : pmx_launch_seed_count(Q->d_buf, Q->d_off, Q->bytes, q_first + row, rows, strands, strand0, max_qlen, ix->k, ix->keys, ix->bucket,
+                                    ix->shift, o->max_occ, lo, cnt, moff, cap_m, cut, temp, temp_bytes, st);
         if (rc) { set_err("seed count pass failed (%d)", rc); return rc; }
         int64_t h[2] = {0, 0};
         HIP_OR_RET(hipMemcpyAsync(h, cut, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
         if (h[0] < 1 || h[0] > rows || h[1] < 0 || h[1] > cap_m) { set_err("seed cut of rows %lld .. is inconsistent", (long long)(q_first + row)); return -1; }
-        rc = pmx_launch_seed_cluster(q_first + row, h[0], strands, strand0, max_qlen, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb, head, flag,
-                                     o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand, d_hit_seeds,
-                                     d_row_off + row, d_counts, temp, temp_bytes, st);
+        rc = mode.letters
+            ? pmx_launch_seed_cluster_letters(q_first + row, h[0], strands, strand0, mode.codon, max_qlen, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb,
+                                              head, flag, o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand,
+                                              d_hit_seeds, d_row_off + row, d_counts, temp, temp_bytes, st)
+            : pmx_launch_seed_cluster(q_first + row, h[0], strands, strand0, max_qlen, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb, head, flag,
+                                      o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand, d_hit_seeds,
+                                      d_row_off + row, d_counts, temp, temp_bytes, st);
         if (rc) { set_err("seed cluster pass failed (%d)", rc); return rc; }
         row += h[0];
     }
     return 0;
 }
 
-extern "C" int pmx_seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
-                                     const pmx_seed_opts_t *opts, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds,
-                                     int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
+// The device entries; query_mode: PMX_SEED_MODE_DNA or the letters entry's mode
+static int seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
+                             const pmx_seed_opts_t *opts, int query_mode, const uint8_t *code, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand,
+                             pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
 {
-    if (seed_check(Q, ix, q_first, nq, max_qlen, opts, capacity)) return -1;
+    if (seed_check(Q, ix, q_first, nq, max_qlen, opts, capacity, true, query_mode)) return -1;
     if (capacity > 0 && (!d_hit_pairs || !d_hit_strand)) { set_err("null hit pairs or strand bytes with capacity > 0"); return -1; }
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
@@ -6019,17 +6125,37 @@ extern "C" int pmx_seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index
     if (seed_device_check(Q, ix)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return seed_run(Q, ix, q_first, nq, max_qlen, opts, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts, (hipStream_t)stream);
+    return seed_run(Q, ix, q_first, nq, max_qlen, opts, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts, (hipStream_t)stream,
+                    query_mode == PMX_SEED_MODE_DNA ? seed_mode_dna(opts) : seed_mode_letters(query_mode, code));
+}
+
+extern "C" int pmx_seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
+                                     const pmx_seed_opts_t *opts, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds,
+                                     int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
+{
+    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, PMX_SEED_MODE_DNA, nullptr, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off,
+                             d_counts, stream);
+}
+
+extern "C" int pmx_seed_pairs_letters_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
+                                             const pmx_seed_opts_t *opts, int query_mode, const uint8_t *code,
+                                             pmx_pair_t *d_hit_pairs, uint8_t *d_hit_byte, pmx_seed_hit_t *d_hit_seeds, int64_t capacity,
+                                             int64_t *d_row_off, int64_t *d_counts, void *stream)
+{
+    if (query_mode == PMX_SEED_MODE_DNA) query_mode = PMX_SEED_MODE_DNA + 1;      // (an invalid mode like any other)
+    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, query_mode, code, d_hit_pairs, d_hit_byte, d_hit_seeds, capacity, d_row_off, d_counts,
+                             stream);
 }
 
 extern "C" void pmx_seed_hits_free(pmx_seed_hits_t *hits) { free(hits); }
 
-extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
-                              pmx_seed_hits_t **result)
+static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
+                           int query_mode, const uint8_t *code, pmx_seed_hits_t **result)
 {
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
-    if (seed_check(Q, ix, q_first, nq, 0, opts, 0, false)) return -1;
+    if (seed_check(Q, ix, q_first, nq, 0, opts, 0, false, query_mode)) return -1;
+    const SeedMode mode = query_mode == PMX_SEED_MODE_DNA ? seed_mode_dna(opts) : seed_mode_letters(query_mode, code);
     // the result: one block -- header, row offsets, descriptors, seed records, strand bytes
     auto block = [&](int64_t stored, int64_t passing) -> pmx_seed_hits_t * {
         Carver c; c.align = 16;
@@ -6068,8 +6194,9 @@ extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix,
         HIP_OR_RET(hipStreamSynchronize(st));
         mq = h_m[0];
     }
+    if (mode.letters && mode.first >= 0) mq /= 3;            // translated rows: the letters of the longest translation
     if (mq < 1) mq = 1;
-    if (seed_check(Q, ix, q_first, nq, mq, opts, 0)) return -1;
+    if (seed_check(Q, ix, q_first, nq, mq, opts, 0, true, query_mode)) return -1;
     int64_t *d_off = nullptr, *d_cnt = nullptr; pmx_pair_t *d_pairs = nullptr; pmx_seed_hit_t *d_seeds = nullptr; uint8_t *d_strand = nullptr;
     auto carve = [&](int64_t stored) {
         return scratch_carve(SCR_SEEDHIT, [&](Carver &c) {
@@ -6083,14 +6210,14 @@ extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix,
     int64_t room = 2 * nq + 16;
     if (opts->max_hits > 0) room = std::min(room, opts->max_hits);
     if (carve(room)) return -1;
-    int rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, room, d_off, d_cnt, st);
+    int rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, room, d_off, d_cnt, st, mode);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     HIP_OR_RET(hipMemcpyAsync(h, d_cnt, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_OR_RET(hipStreamSynchronize(st));
     const int64_t passing = h[0], stored = opts->max_hits > 0 ? std::min(passing, opts->max_hits) : passing;
     if (stored > room) {
         if (carve(stored)) return -1;
-        rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, stored, d_off, d_cnt, st);
+        rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, stored, d_off, d_cnt, st, mode);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipStreamSynchronize(st));
     }
@@ -6103,4 +6230,17 @@ extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix,
     if (e != hipSuccess) { set_err("copying the candidates back failed: %s", hipGetErrorString(e)); free(r); return -1; }
     *result = r;
     return 0;
+}
+
+extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
+                              pmx_seed_hits_t **result)
+{
+    return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_MODE_DNA, nullptr, result);
+}
+
+extern "C" int pmx_seed_pairs_letters(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
+                                      int query_mode, const uint8_t *code, pmx_seed_hits_t **result)
+{
+    if (query_mode == PMX_SEED_MODE_DNA) query_mode = PMX_SEED_MODE_DNA + 1;
+    return seed_pairs_host(Q, ix, q_first, nq, opts, query_mode, code, result);
 }

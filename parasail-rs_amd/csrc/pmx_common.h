@@ -469,6 +469,25 @@ int pmx_launch_seed_cluster(long long row0, long long rows, int strands, int str
                             const int64_t *qoff, const int64_t *roff, long long capacity,
                             pmx_pair_t *hit_pairs, uint8_t *hit_strand, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
                             void *temp, size_t temp_bytes, hipStream_t stream);
+// The same over a letters index: `bits` bits per letter, table: 256 group bytes on the device.  orients: orientation
+// slots per row, the first one's frame `first` (< 0: the rows are letters of the index's alphabet); codes: one byte per position slot;
+// codon: segments of three frames and nucleotide diagonals (orients 3 or 6, first 0 or 3).
+#define PMX_SEED_POS_BYTES_LETTERS (PMX_SEED_POS_BYTES + 1)
+size_t pmx_seed_index_sort_bytes_letters(long long bytes, int k, int bits);
+int pmx_launch_seed_index_letters(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int bits, const uint8_t *table,
+                                  uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out, void *temp, size_t temp_bytes,
+                                  unsigned long long *n_valid, hipStream_t stream);
+int pmx_launch_seed_count_letters(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int orients, int first,
+                                  int max_qlen, int k, int bits, const uint8_t *table, const PmxCodeTable &code, uint8_t *codes,
+                                  const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
+                                  uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
+                                  hipStream_t stream);
+int pmx_launch_seed_cluster_letters(long long row0, long long rows, int orients, int first, bool codon, int max_qlen, long long m, int key_bits,
+                                    const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
+                                    uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
+                                    const int64_t *qoff, const int64_t *roff, long long capacity,
+                                    pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
+                                    void *temp, size_t temp_bytes, hipStream_t stream);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);

@@ -324,6 +324,46 @@ int pmx_launch_seed_count(const uint8_t *qbuf, const int64_t *qoff, long long q_
     return pmx_launched();
 }
 
+// Between emit and hits, whatever the letters were: the m matches of mkeys_a sorted per segment (`slots` segments of `stride` position
+// slots each) into mkeys_b, head[x] = the head of x's cluster, flag[x + 1] - flag[x] = 1 where x closes a candidate (flag: m + 1 entries).
+static int pmx_seed_sort_clusters(long long m, long long slots, long long stride, int key_bits, const int64_t *moff,
+                                  uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds,
+                                  void *temp, size_t temp_bytes, hipStream_t stream)
+{
+    int rc = 0;
+    const unsigned mb = (unsigned)((m + 255) / 256);
+    auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{moff, stride});
+    size_t tb = temp_bytes;
+    hipError_t e = rocprim::segmented_radix_sort_keys(temp, tb, (const uint64_t *)mkeys_a, mkeys_b, (unsigned)m, (unsigned)slots, seg, seg + 1, 0, key_bits,
+                                                      stream);
+    if (e != hipSuccess) return -(int)e;
+    if (hipMemsetAsync(flag, 0, sizeof(uint32_t) * (size_t)(m + 1), stream) != hipSuccess) return -1;
+    hipLaunchKernelGGL(pmx_seed_segstart_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, moff, slots, stride, flag);
+    if ((rc = pmx_launched())) return rc;
+    hipLaunchKernelGGL(pmx_seed_heads_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)mkeys_b, m, band, (const uint32_t *)flag, head);
+    if ((rc = pmx_launched())) return rc;
+    tb = temp_bytes;
+    e = rocprim::inclusive_scan(temp, tb, head, head, (size_t)m, PmxMaxU32(), stream);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(pmx_seed_flags_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t *)head, m, min_seeds, flag);
+    if ((rc = pmx_launched())) return rc;
+    tb = temp_bytes;
+    e = rocprim::exclusive_scan(temp, tb, flag, flag, 0u, (size_t)(m + 1), rocprim::plus<uint32_t>(), stream);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+// Behind the hits: the slice's row offsets (row_stride position slots per row) and the running counts.
+static int pmx_seed_finish(long long rows, long long row_stride, long long m, const int64_t *moff, const uint32_t *flag, long long capacity,
+                           int64_t *row_off, int64_t *counts, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pmx_seed_rowoff_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, m > 0 ? flag : nullptr, moff, rows, row_stride,
+                       (const int64_t *)counts, row_off);
+    const int rc = pmx_launched();
+    if (rc) return rc;
+    hipLaunchKernelGGL(pmx_seed_advance_kernel, dim3(1), dim3(1), 0, stream, m > 0 ? flag : nullptr, m, capacity, counts);
+    return pmx_launched();
+}
+
 // The slice's `rows` rows (what the cut kept) with their m matches: emit, sort, clusters, outputs behind counts[0]; row_off points at
 // the entry of the slice's first row.
 int pmx_launch_seed_cluster(long long row0, long long rows, int strands, int strand0, int max_qlen, long long m, int key_bits,
@@ -334,40 +374,295 @@ int pmx_launch_seed_cluster(long long row0, long long rows, int strands, int str
                             void *temp, size_t temp_bytes, hipStream_t stream)
 {
     const long long slots = rows * strands, stride = max_qlen, total = slots * stride;
-    const unsigned rb = (unsigned)((rows + 255) / 256);
     int rc = 0;
     if (m > 0) {
-        const unsigned mb = (unsigned)((m + 255) / 256);
         hipLaunchKernelGGL(pmx_seed_emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, max_qlen, lo, cnt, moff, vals, mkeys_a);
         if ((rc = pmx_launched())) return rc;
-        auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{moff, stride});
-        size_t tb = temp_bytes;
-        hipError_t e = rocprim::segmented_radix_sort_keys(temp, tb, (const uint64_t *)mkeys_a, mkeys_b, (unsigned)m, (unsigned)slots, seg, seg + 1, 0, key_bits,
-                                                          stream);
-        if (e != hipSuccess) return -(int)e;
-        if (hipMemsetAsync(flag, 0, sizeof(uint32_t) * (size_t)(m + 1), stream) != hipSuccess) return -1;
-        hipLaunchKernelGGL(pmx_seed_segstart_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, moff, slots, stride, flag);
-        if ((rc = pmx_launched())) return rc;
-        hipLaunchKernelGGL(pmx_seed_heads_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)mkeys_b, m, band, (const uint32_t *)flag, head);
-        if ((rc = pmx_launched())) return rc;
-        tb = temp_bytes;
-        e = rocprim::inclusive_scan(temp, tb, head, head, (size_t)m, PmxMaxU32(), stream);
-        if (e != hipSuccess) return -(int)e;
-        hipLaunchKernelGGL(pmx_seed_flags_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t *)head, m, min_seeds, flag);
-        if ((rc = pmx_launched())) return rc;
-        tb = temp_bytes;
-        e = rocprim::exclusive_scan(temp, tb, flag, flag, 0u, (size_t)(m + 1), rocprim::plus<uint32_t>(), stream);
-        if (e != hipSuccess) return -(int)e;
+        if ((rc = pmx_seed_sort_clusters(m, slots, stride, key_bits, moff, mkeys_a, mkeys_b, head, flag, band, min_seeds, temp, temp_bytes, stream))) return rc;
         if (capacity > 0) {
-            hipLaunchKernelGGL(pmx_seed_hits_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag, m,
-                               moff, slots, stride, row0, strands, strand0, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_strand,
-                               hit_seeds);
+            hipLaunchKernelGGL(pmx_seed_hits_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head,
+                               (const uint32_t *)flag, m, moff, slots, stride, row0, strands, strand0, pad, qoff, roff, (const int64_t *)counts, capacity,
+                               hit_pairs, hit_strand, hit_seeds);
             if ((rc = pmx_launched())) return rc;
         }
     }
-    hipLaunchKernelGGL(pmx_seed_rowoff_kernel, dim3(rb), dim3(256), 0, stream, m > 0 ? (const uint32_t *)flag : nullptr, moff, rows, (long long)strands * stride,
-                       (const int64_t *)counts, row_off);
+    return pmx_seed_finish(rows, (long long)strands * stride, m, moff, flag, capacity, row_off, counts, stream);
+}
+
+// ---- letters: a protein index over a reduced alphabet, proteins or translated reads as queries --------------------------
+// The index is the DNA one with a run-time number of bits per letter and the letter's group read from a 256-byte table staged in LDS.
+// Seeding adds one stage in front of the count pass: a code byte per position slot -- the group of the letter there, 255 where there
+// is none -- so that a codon is read and translated once per frame and the count pass forms its keys from k code bytes.  A position
+// slot is p = ((row_local * orients) + o) * max_qlen + i; orientation o of a row is frame `first` + o (letters mode: the row itself).
+// The codon modes' (row, strand, frame, i) is the same number with orients = 3 strands: only the segments of the sort differ, three
+// frames wide there, and with them emit's diagonal and the window.
+
+// keys[p] / vals[p] for every p < bytes, as pmx_seed_extract_kernel: `bits` bits per letter, table[b] = the group of byte b or 255
+__global__ void __launch_bounds__(256) pmx_seedl_extract_kernel(const uint8_t *__restrict__ buf, const int64_t *__restrict__ off, long long count,
+                                                                long long bytes, int k, int bits, const uint8_t *__restrict__ table,
+                                                                uint64_t *__restrict__ keys, uint64_t *__restrict__ vals, unsigned long long *n_valid)
+{
+    __shared__ uint8_t grp[256];
+    __shared__ unsigned total;
+    grp[threadIdx.x] = table[threadIdx.x];
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const long long p0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * PMX_SEED_TILE;
+    unsigned found = 0;
+    if (p0 < bytes) {
+        const uint64_t invalid = (uint64_t)1 << (k * bits), mask = invalid - 1;
+        long long lo = 0, hi = count + 1;
+        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (off[mid] <= p0) lo = mid + 1; else hi = mid; }
+        long long r = lo - 1;
+        long long e = r < count ? off[r + 1] : INT64_MAX;
+        long long b = r >= 0 ? off[r] : 0;
+        const long long pend = min(p0 + PMX_SEED_TILE, bytes), xend = min(pend + k - 1, bytes);
+        uint64_t key = 0; int run = 0;
+        for (long long x = p0; x < xend; ++x) {
+            while (x >= e && r < count) { ++r; b = e; e = r < count ? off[r + 1] : INT64_MAX; run = 0; }
+            const bool inside = r >= 0 && r < count && b >= 0 && b <= x && x < e && e <= bytes;
+            const uint32_t c = inside ? (uint32_t)grp[buf[x]] : 255u;
+            if (c == 255u) { run = 0; key = 0; } else { key = (key << bits) | (uint64_t)c; ++run; }
+            const long long s = x - k + 1;
+            if (s >= p0) {
+                const bool have = run >= k && s >= b;
+                keys[s] = have ? (key & mask) : invalid;
+                vals[s] = have ? ((uint64_t)r << 32) | (uint64_t)(uint32_t)(s - b) : (uint64_t)s;
+                found += have ? 1u : 0u;
+            }
+        }
+        for (long long s = max(p0, xend - k + 1); s < pend; ++s) { keys[s] = invalid; vals[s] = (uint64_t)s; }
+    }
+    if (found) atomicAdd(&total, found);
+    __syncthreads();
+    if (threadIdx.x == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+}
+
+size_t pmx_seed_index_sort_bytes_letters(long long bytes, int k, int bits)
+{
+    size_t temp = 0;
+    uint64_t *nul = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, temp, nul, nul, nul, nul, (size_t)bytes, 0, k * bits + 1, nullptr);
+    return temp + 256;
+}
+
+int pmx_launch_seed_index_letters(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int bits, const uint8_t *table,
+                                  uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out, void *temp, size_t temp_bytes,
+                                  unsigned long long *n_valid, hipStream_t stream)
+{
+    if (bytes <= 0) return 0;
+    const long long threads = (bytes + PMX_SEED_TILE - 1) / PMX_SEED_TILE;
+    hipLaunchKernelGGL(pmx_seedl_extract_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, buf, off, count, bytes, k, bits, table,
+                       keys_in, vals_in, n_valid);
+    int rc = pmx_launched();
+    if (rc) return rc;
+    const hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)bytes, 0, k * bits + 1, stream);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+// base -> its class in the genetic code's order T/U 0, C 1, A 2, G 3 (either case); 4: not a nucleotide
+__device__ __forceinline__ uint32_t pmx_seedl_base(uint32_t b)
+{
+    const uint32_t u = b & 0xDFu;
+    return u == 'T' || u == 'U' ? 0u : u == 'C' ? 1u : u == 'A' ? 2u : u == 'G' ? 3u : 4u;
+}
+
+// codes[p] for every position slot of the slice.  first < 0: letters mode, the slot's letter is the row's byte i.  Else the slot's
+// frame is f = first + o, off = f % 3, and its letter is the codon at bytes off + 3 i .. of the row as stored (f < 3) or of its reverse
+// complement (f >= 3): the three bytes at W - 1 - (off + 3 i) downwards, complemented by the index ^ 42 -- nothing is materialised.
+// A codon with a byte that is no nucleotide is X.  The letter goes through the index's table.  255: no letter there (behind the
+// translation's end, a bad row, a row whose W / 3 (letters mode: W) exceeds max_qlen) or a letter outside the alphabet.
+__global__ void __launch_bounds__(256) pmx_seedl_codes_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
+                                                              long long row0, long long total, int orients, int first, int max_qlen,
+                                                              const uint8_t *__restrict__ table, PmxCodeTable code, uint8_t *__restrict__ codes)
+{
+    __shared__ uint8_t grp[256];
+    __shared__ uint8_t cod[64];
+    grp[threadIdx.x] = table[threadIdx.x];
+    if (threadIdx.x < 64) cod[threadIdx.x] = code.v[threadIdx.x];
+    __syncthreads();
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const long long t = p / max_qlen;
+    const long long i = p - t * max_qlen;
+    const long long row = row0 + t / orients;
+    const long long b = qoff[row], e = qoff[row + 1];
+    uint32_t c = 255u;
+    if (b >= 0 && e >= b && e <= q_bytes) {
+        const long long W = e - b;
+        const uint8_t *w = qbuf + b;
+        if (first < 0) {
+            if (W <= max_qlen && i < W) c = grp[w[i]];
+        } else {
+            const int f = first + (int)(t % orients), off = f % 3;
+            const long long x = off + 3 * i;
+            if (W / 3 <= max_qlen && x + 3 <= W) {
+                uint32_t b0, b1, b2, flip;
+                if (f < 3) { b0 = w[x]; b1 = w[x + 1]; b2 = w[x + 2]; flip = 0u; }
+                else { b0 = w[W - 1 - x]; b1 = w[W - 2 - x]; b2 = w[W - 3 - x]; flip = 42u; }
+                const uint32_t idx = (pmx_seedl_base(b0) << 4) | (pmx_seedl_base(b1) << 2) | pmx_seedl_base(b2);
+                const bool ok = (pmx_seedl_base(b0) | pmx_seedl_base(b1) | pmx_seedl_base(b2)) < 4u;
+                c = grp[ok ? (uint32_t)cod[(idx & 63u) ^ flip] : (uint32_t)'X'];
+            }
+        }
+    }
+    codes[p] = (uint8_t)c;
+}
+
+// pmx_seed_count_kernel with the key formed from the slot's k code bytes (they end at the slot's orientation: i + k <= max_qlen)
+__global__ void __launch_bounds__(256) pmx_seedl_count_kernel(const uint8_t *__restrict__ codes, long long total, int max_qlen, int k, int bits,
+                                                              const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
+                                                              int max_occ, uint32_t *__restrict__ lo_out, uint32_t *__restrict__ cnt_out)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > total) return;
+    if (p == total) { cnt_out[p] = 0; return; }
+    const int i = (int)(p % max_qlen);
+    uint32_t lo = 0, cnt = 0;
+    if (i + k <= max_qlen && codes[p] != 255) {
+        uint64_t key = 0; bool ok = true;
+        for (int x = 0; x < k; ++x) {
+            const uint32_t c = codes[p + x];
+            ok = ok && c != 255u;
+            key = (key << bits) | (uint64_t)(c & 31u);
+        }
+        if (ok) {
+            const uint32_t s = bucket[key >> shift], t1 = bucket[(key >> shift) + 1];
+            uint32_t a = s, z = t1;
+            while (a < z) { const uint32_t mid = a + ((z - a) >> 1); if (keys[mid] < key) a = mid + 1; else z = mid; }
+            if (a < t1 && keys[a] == key) {
+                lo = a;
+                const uint32_t lim = (uint32_t)min((unsigned long long)t1, (unsigned long long)a + (unsigned long long)max_occ);
+                if (!(lim < t1 && keys[lim] == key)) {                 // (else: more than max_occ occurrences, ignored entirely)
+                    uint32_t u = a + 1; z = lim;
+                    while (u < z) { const uint32_t mid = u + ((z - u) >> 1); if (keys[mid] == key) u = mid + 1; else z = mid; }
+                    cnt = u - a;
+                }
+            }
+        }
+    }
+    lo_out[p] = lo; cnt_out[p] = cnt;
+}
+
+// floor(a / 3) for either sign
+__device__ __forceinline__ long long pmx_seedl_floor3(long long a) { return a >= 0 ? a / 3 : -((2 - a) / 3); }
+
+// pmx_seed_emit_kernel with the mode's diagonal.  CODON false: d = j - i in letters.  CODON true: the nucleotide diagonal
+// D = 3 j - (off + 3 i), off = the slot's frame % 3 = its orientation slot % 3 (orients is 3 or 6 and `first` 0 or 3 there).
+// |d| < 2^31 by the slot's i < 2^31 / 3 and the index's j < 2^29.
+template <bool CODON>
+__global__ void __launch_bounds__(256) pmx_seedl_emit_kernel(long long total, int max_qlen, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ cnt,
+                                                             const int64_t *__restrict__ moff, const uint64_t *__restrict__ vals,
+                                                             uint64_t *__restrict__ mkeys)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const uint32_t n = cnt[p];
+    if (!n) return;
+    const long long t = p / max_qlen;
+    const long long i = p - t * max_qlen;
+    const long long sub = CODON ? (long long)(t % 3) + 3 * i : i;
+    const uint32_t first = lo[p];
+    uint64_t *out = mkeys + moff[p];
+    for (uint32_t x = 0; x < n; ++x) {
+        const uint64_t v = vals[first + x];
+        const long long j = (long long)(uint32_t)v;
+        const int32_t d = (int32_t)((CODON ? 3 * j : j) - sub);
+        out[x] = (v & 0xFFFFFFFF00000000ull) | (uint64_t)((uint32_t)d ^ 0x80000000u);
+    }
+}
+
+// pmx_seed_hits_kernel with the mode's window and byte.  A segment is (row, orientation) of `stride` = max_qlen slots (CODON false:
+// byte = the frame, 0 in letters mode; window from the letter diagonals and the translation's length) or (row, strand) of
+// `stride` = 3 max_qlen slots (CODON true: byte = the strand; window from the nucleotide diagonals and W).  segs: segments per row;
+// first: the first segment's frame / strand, < 0 in letters mode.
+template <bool CODON>
+__global__ void __launch_bounds__(256) pmx_seedl_hits_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ pos,
+                                                             long long m, const int64_t *__restrict__ moff, long long slots, long long stride,
+                                                             long long row0, int segs, int first, int pad,
+                                                             const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
+                                                             const int64_t *__restrict__ counts, long long capacity,
+                                                             pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_byte, pmx_seed_hit_t *__restrict__ hit_seeds)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= m || pos[x + 1] == pos[x]) return;
+    const long long at = counts[0] + (long long)pos[x];
+    if (at >= capacity) return;
+    long long a = 0, z = slots - 1;             // the segment of x: the last t with moff[t * stride] <= x (empty segments share a start)
+    while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= x) a = mid; else z = mid - 1; }
+    const long long row = row0 + a / segs;
+    const int byte = first < 0 ? 0 : first + (int)(a % segs);
+    const uint32_t h = head[x];
+    const uint64_t kh = mkeys[h], kt = mkeys[x];
+    const long long r = (long long)(kt >> 32), dmin = pmx_seed_diag(kh), dmax = pmx_seed_diag(kt);
+    const long long W = qoff[row + 1] - qoff[row], rlen = roff[r + 1] - roff[r];
+    long long beg, end;
+    if (CODON) {
+        beg = max(0ll, pmx_seedl_floor3(dmin) - pad);
+        end = min(rlen, pmx_seedl_floor3(dmax + W - 1) + 1 + pad);
+    } else {
+        const long long L = first < 0 ? W : (W - byte % 3) / 3;
+        beg = max(0ll, dmin - pad);
+        end = min(rlen, dmax + L + pad);
+    }
+    pmx_pair_t pr; pr.q = row; pr.r = r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)beg; pr.r_len = (int32_t)(end - beg);
+    hit_pairs[at] = pr;
+    hit_byte[at] = (uint8_t)byte;
+    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = (int32_t)(x - h + 1); s.diag_min = (int32_t)dmin; s.diag_max = (int32_t)dmax; s.reserved = 0; hit_seeds[at] = s; }
+}
+
+// pmx_launch_seed_count for a letters index: the code stage (codes: one byte per position slot), the count pass over it, scan and cut.
+// orients: orientation slots per row; first: the first one's frame, < 0 in letters mode.
+int pmx_launch_seed_count_letters(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int orients, int first,
+                                  int max_qlen, int k, int bits, const uint8_t *table, const PmxCodeTable &code, uint8_t *codes,
+                                  const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
+                                  uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
+                                  hipStream_t stream)
+{
+    const long long total = rows * orients * max_qlen;
+    hipLaunchKernelGGL(pmx_seedl_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, qbuf, qoff, q_bytes, row0, total, orients, first,
+                       max_qlen, table, code, codes);
+    int rc = pmx_launched();
+    if (rc) return rc;
+    hipLaunchKernelGGL(pmx_seedl_count_kernel, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, stream, (const uint8_t *)codes, total, max_qlen, k, bits,
+                       keys, bucket, shift, max_occ, lo, cnt);
     if ((rc = pmx_launched())) return rc;
-    hipLaunchKernelGGL(pmx_seed_advance_kernel, dim3(1), dim3(1), 0, stream, m > 0 ? (const uint32_t *)flag : nullptr, m, capacity, counts);
+    auto in = rocprim::make_transform_iterator((const uint32_t *)cnt, PmxWidenU32());
+    const hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, in, moff, (int64_t)0, (size_t)(total + 1), rocprim::plus<int64_t>(), stream);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(pmx_seed_cut_kernel, dim3(1), dim3(1), 0, stream, moff, rows, (long long)orients * max_qlen, cap_matches, cut);
     return pmx_launched();
+}
+
+// pmx_launch_seed_cluster for a letters index; codon: the codon modes (segments of three frames, nucleotide diagonals).
+int pmx_launch_seed_cluster_letters(long long row0, long long rows, int orients, int first, bool codon, int max_qlen, long long m, int key_bits,
+                                    const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
+                                    uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
+                                    const int64_t *qoff, const int64_t *roff, long long capacity,
+                                    pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
+                                    void *temp, size_t temp_bytes, hipStream_t stream)
+{
+    const int segs = codon ? orients / 3 : orients;
+    const long long slots = rows * segs, stride = (long long)(codon ? 3 : 1) * max_qlen, total = slots * stride;
+    const int seg_first = codon ? first / 3 : first;
+    int rc = 0;
+    if (m > 0) {
+        const dim3 eb((unsigned)((total + 255) / 256)), hb((unsigned)((m + 255) / 256));
+        if (codon) hipLaunchKernelGGL(pmx_seedl_emit_kernel<true>, eb, dim3(256), 0, stream, total, max_qlen, lo, cnt, moff, vals, mkeys_a);
+        else hipLaunchKernelGGL(pmx_seedl_emit_kernel<false>, eb, dim3(256), 0, stream, total, max_qlen, lo, cnt, moff, vals, mkeys_a);
+        if ((rc = pmx_launched())) return rc;
+        if ((rc = pmx_seed_sort_clusters(m, slots, stride, key_bits, moff, mkeys_a, mkeys_b, head, flag, band, min_seeds, temp, temp_bytes, stream))) return rc;
+        if (capacity > 0) {
+            if (codon)
+                hipLaunchKernelGGL(pmx_seedl_hits_kernel<true>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
+                                   m, moff, slots, stride, row0, segs, seg_first, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte,
+                                   hit_seeds);
+            else
+                hipLaunchKernelGGL(pmx_seedl_hits_kernel<false>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
+                                   m, moff, slots, stride, row0, segs, seg_first, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte,
+                                   hit_seeds);
+            if ((rc = pmx_launched())) return rc;
+        }
+    }
+    return pmx_seed_finish(rows, (long long)orients * max_qlen, m, moff, flag, capacity, row_off, counts, stream);
 }
