@@ -1443,6 +1443,72 @@ int pmx_seed_pairs_letters_device(const pmx_seqset_t *Q, const pmx_seed_index_t 
 int pmx_seed_pairs_letters(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq,
                            const pmx_seed_opts_t *opts, int query_mode, const uint8_t *code, pmx_seed_hits_t **result);
 
+/* Seeding translated references (extension): the tblastn pairing -- a six-frame k-mer index of a NUCLEOTIDE set over a reduced
+ * alphabet, seeded by protein queries.  Its candidate lists go unchanged into pmx_align_pairs_translated_ref[_device] (a frame byte per
+ * pair) and pmx_align_pairs_frameshift_ref[_device] and its traceback entries (a strand byte per pair) (kernels:
+ * parasail-rs_amd/csrc/pmx_seed.hip).  Each index kind refuses the other kinds' seeding entries and names its own.
+ *
+ * The set and the strands.  R holds nucleotides.  `table` is the 256-byte table of pmx_seed_index_build_letters (same bits, same
+ * built-ins), `code` 64 letters in NCBI order or NULL for pmx_genetic_code_table.  strand_mode (PMX_STRAND_FORWARD, _REVERSE, _BOTH) is
+ * fixed when the index is built: seeding uses exactly the strands the index holds, there is no per-call filter, and max_occ counts a
+ * k-mer's entries over the index as built.
+ *
+ * Oriented coordinates.  A sequence r of N nucleotides is read as stored (strand s = 0) or reverse-complemented (s = 1): exactly the
+ * reading of frames 3 .. 5 of the reference-side translated entries, through pmx_complement_table from the end downwards; nothing is
+ * materialised.  Oriented position x = 0 .. N - 3 starts the codon of oriented bytes x, x + 1, x + 2; its letter is the translation by
+ * the translated entries' rule (a byte outside A C G T U, either case, gives 'X') put through the table.  'X', '*' and every letter
+ * the table maps to 255 are invalid.  The k-mer at x is the k letters at x, x + 3, ..., x + 3 (k - 1): it needs x + 3 k <= N and k
+ * valid letters, so it never crosses a sequence end.  Keys: `bits` per letter, first letter most significant; an empty position has
+ * the key 1 << (k * bits); the bucket table is on the top min(k * bits, 22) bits.
+ *
+ * Index.  One entry per (s, r, x) with a k-mer, sorted by (kmer, s, r, x); value (s * count + r) << 32 | x, count = the sequences of
+ * R; pmx_seed_index_entries_device reports d_seq = s * count + r and d_pos = x.  The index therefore holds the k-mers of all three
+ * frames of each held strand: x % 3 is the frame's offset and g = 3 s + x % 3 the SEQUENCE FRAME.  Refused before any GPU work
+ * (NULL, pmx_last_error()): what pmx_seed_index_build_letters refuses about set, table and k (k >= 2, k * bits <= 62), with its texts;
+ * a strand mode outside 0 .. 2; more than 2^30 - 1 bytes (two entry slots per byte with both strands; entry numbers and bucket
+ * contents are 32-bit) or more than 2^29 sequences (6 * count fits the upper half of a match key): index in parts.  Resident: 16 bytes
+ * per entry slot -- one slot per byte and held strand, 32 bytes per nucleotide with both -- plus the bucket table (16 MiB at most);
+ * while it is built twice that plus rocPRIM's scratch.  pmx_seed_index_strands: the strand mode; -2 for a DNA or letters index.
+ *
+ * Seeding.  Q holds proteins in the index's alphabet: one orientation, the row itself, m letters (max_qlen bounds m).  A match is
+ * (p, s, r, x): the row has a k-mer at p, the index an entry (s, r, x) with the same key, and that key has at most max_occ entries.
+ *
+ * PMX_SEED_REF_FRAMES: candidates per sequence frame.  The matches of (q, g, r) lie on the letter diagonal d = (x - x % 3) / 3 - p;
+ * runs, band, min_seeds and pad are pmx_seed_pairs', in letters.  With L_g = (N - g % 3) / 3 the letter window of frame g is
+ * [lb, le) = [max(0, d_min - pad), min(L_g, d_max + m + pad)), and the descriptor's reference window is that range in STORED
+ * nucleotides, codon-aligned, off = g % 3: [off + 3 lb, off + 3 le) on strand 0, [N - off - 3 le, N - off - 3 lb) on strand 1.  The
+ * byte is the frame RELATIVE TO THE WINDOW, by the alignment always 0 (strand 0) or 3 (strand 1): d_hit_pairs / d_hit_byte are valid
+ * d_pairs / d_frame of pmx_align_pairs_translated_ref_device.  d_hit_seeds is {n_seeds, d_min, d_max, g}: `reserved` carries the
+ * sequence frame, which tells where in the contig the frame lies.  Row q's candidates ascend in (g, r, d_min).  These candidates --
+ * entries, row offsets, order, n_seeds, d_min, d_max -- equal those of pmx_seed_pairs_letters (PMX_SEED_QUERY_LETTERS) over a letters
+ * index of the protein set R6 whose sequence g * count + r is the translation of R[r] in frame g (held strands only; same table, k,
+ * options), with r' -> (g, r) and the letter window mapped as above.
+ *
+ * PMX_SEED_REF_CODONS: candidates per strand over its three frames.  The matches of (q, s, r) lie on the NUCLEOTIDE diagonal
+ * D = x - 3 p; band and pad are in nucleotides.  The oriented window is [lo, hi) = [max(0, D_min - pad), min(N, D_max + 3 m + pad)),
+ * stored [lo, hi) on strand 0 and [N - hi, N - lo) on strand 1; the byte is the strand: d_hit_pairs / d_hit_byte are valid d_pairs /
+ * d_strand of pmx_align_pairs_frameshift_ref_device and of the frameshift_ref traceback entries.  d_hit_seeds is {n_seeds, D_min,
+ * D_max, 0}.  One base inserted or deleted in the contig moves a hit by one nucleotide diagonal, so it stays ONE candidate carrying
+ * the seeds of both frames where the frame mode gives two shorter ones.  Row q's candidates ascend in (s, r, D_min).
+ *
+ * pmx_seed_opts_t and pmx_seed_hits_t are reused: opts->strand must be 0, the result's `strand` array holds the byte.  Position slots
+ * are (row, p), max_qlen per row, 17 bytes each.  capacity, d_row_off, d_counts, max_hits and the uncapped offsets, slices, the cut
+ * and one stream synchronisation per slice, pmx_seed_match_budget, nq == 0 and determinism are what pmx_seed_pairs[_device] documents,
+ * by the same code.  Refused with -1 before any GPU work: everything pmx_seed_pairs_letters refuses about the shared arguments, with
+ * its texts; opts->strand != 0; a ref_mode outside 0 .. 1; a DNA or letters index; one row's worst case, max_qlen x max_occ x 24
+ * bytes, above the match buffer. */
+pmx_seed_index_t *pmx_seed_index_build_translated(const pmx_seqset_t *R, int32_t k, const uint8_t table[256],
+                                                  const uint8_t *code /* 64 letters or NULL */, int strand_mode, void *stream);
+int32_t pmx_seed_index_strands(const pmx_seed_index_t *index);  /* the PMX_STRAND_* mode of a translated index; -2: a DNA or letters index; -1 for NULL */
+#define PMX_SEED_REF_FRAMES 0   /* candidates per sequence frame, letter diagonals; byte = frame relative to the window (0 or 3) */
+#define PMX_SEED_REF_CODONS 1   /* candidates per strand over its three frames, nucleotide diagonals; byte = strand */
+int pmx_seed_pairs_translated_ref_device(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq, int32_t max_qlen,
+                                         const pmx_seed_opts_t *opts, int ref_mode,
+                                         pmx_pair_t *d_hit_pairs, uint8_t *d_hit_byte, pmx_seed_hit_t *d_hit_seeds, int64_t capacity,
+                                         int64_t *d_row_off, int64_t *d_counts, void *stream);
+int pmx_seed_pairs_translated_ref(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq,
+                                  const pmx_seed_opts_t *opts, int ref_mode, pmx_seed_hits_t **result);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

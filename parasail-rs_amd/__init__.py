@@ -311,6 +311,12 @@ _sig("pmx_seed_pairs_letters_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_seed_pairs_letters", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(pmx_seed_opts_t), C.c_int, C.c_void_p,
      C.POINTER(C.POINTER(pmx_seed_hits_t)))
+_sig("pmx_seed_index_build_translated", C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
+_sig("pmx_seed_index_strands", C.c_int32, C.c_void_p)
+_sig("pmx_seed_pairs_translated_ref_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(pmx_seed_opts_t), C.c_int,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_pairs_translated_ref", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(pmx_seed_opts_t), C.c_int,
+     C.POINTER(C.POINTER(pmx_seed_hits_t)))
 _sig("pmx_topk_records_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_align_pairs_both", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1830,6 +1836,7 @@ class SeqSet:
 
 SEED_ALPHABET_AA20, SEED_ALPHABET_AA11 = 0, 1
 SEED_QUERY_LETTERS, SEED_CODONS_FORWARD, SEED_CODONS_REVERSE, SEED_CODONS_BOTH = -1, 9, 10, 11
+SEED_REF_FRAMES, SEED_REF_CODONS = 0, 1
 
 
 def seed_alphabet(which):
@@ -1848,18 +1855,26 @@ def seed_alphabet(which):
 
 class SeedIndex:
     """The k-mer index of a set (pmx_seed_index_t): every k-mer of R as (kmer, seq, pos), sorted, on R's device -- of a DNA set, or
-    with `alphabet` of a protein set over a reduced alphabet (a letters index; .letters, .bits per letter).  R is held: it outlives
-    the index.  len(): the entries.  Released by close() or on deletion."""
+    with `alphabet` of a protein set over a reduced alphabet (a letters index; .letters, .bits per letter), or with `alphabet` and
+    `translated` of a nucleotide set read in the three frames of the strands named (a translated index; .translated, .strands: the
+    strand mode it holds, else None).  R is held: it outlives the index.  len(): the entries.  Released by close() or on deletion."""
 
-    def __init__(self, inner, R, k, letters=False):
+    def __init__(self, inner, R, k, letters=False, strands=None):
         self.inner, self.R, self.k, self.letters = inner, R, int(k), bool(letters)
+        self.translated, self.strands = strands is not None, strands
 
     @classmethod
-    def build(cls, R, k, alphabet=None, stream=0):
+    def build(cls, R, k, alphabet=None, stream=0, translated=None, code=None):
         """alphabet: None (a DNA index), "aa20", "aa11" or 256 bytes that map a byte to its group 0 .. 31 or to 255.  An integer in
-        its place is the stream of a DNA index, build(R, k, stream), as before there were alphabets."""
+        its place is the stream of a DNA index, build(R, k, stream), as before there were alphabets.  translated: "forward",
+        "reverse" or "both" -- R holds nucleotides and the index their six-frame (or three-frame) k-mers over `alphabet`, for
+        seed_pairs(ref_frames=); code: 64 letters that replace the standard genetic code of a translated index."""
         if isinstance(alphabet, (int, np.integer)) and not isinstance(alphabet, bool):
             alphabet, stream = None, int(alphabet)
+        if translated is not None and alphabet is None:
+            raise BatchError("translated= needs alphabet=: a translated index holds letters of a reduced alphabet")
+        if code is not None and translated is None:
+            raise BatchError("code= is for a translated index (translated=)")
         if alphabet is None:
             inner = lib.pmx_seed_index_build(R._handle(), int(k), stream)
         else:
@@ -1870,10 +1885,17 @@ class SeedIndex:
                                              dtype=np.uint8)
                 if table.shape != (256,):
                     raise BatchError("alphabet is \"aa20\", \"aa11\" or a table of 256 bytes")
-            inner = lib.pmx_seed_index_build_letters(R._handle(), int(k), table.ctypes.data, stream)
+            if translated is not None:
+                if translated not in ("forward", "reverse", "both"):
+                    raise BatchError("translated is \"forward\", \"reverse\" or \"both\"")
+                code = _code_arg(code)
+                inner = lib.pmx_seed_index_build_translated(R._handle(), int(k), table.ctypes.data, code.ctypes.data if code is not None else None,
+                                                            _strand_mode(translated), stream)
+            else:
+                inner = lib.pmx_seed_index_build_letters(R._handle(), int(k), table.ctypes.data, stream)
         if not inner:
             raise BatchError(lib.pmx_last_error().decode())
-        return cls(inner, R, k, alphabet is not None)
+        return cls(inner, R, k, alphabet is not None and translated is None, translated)
 
     @property
     def bits(self):
@@ -1906,7 +1928,8 @@ class SeedHits:
     (uint8) and seeds (SEED_HIT_DTYPE: matches and the diagonals' range).  A row's candidates are in (strand, reference,
     diag_min) order; row(i) slices out those that were stored.  Of a letters index (seed_pairs(frames=)) the byte per candidate
     is a frame in the frame modes -- .frame holds it, else .frame is None -- and a strand in the codon modes -- .strand holds it;
-    .strand is zeros in the letters and frame modes."""
+    .strand is zeros in the letters and frame modes.  Of a translated index (seed_pairs(ref_frames=)) .frame holds the byte with
+    "frames" (0 or 3, relative to the window; seeds["reserved"] is the sequence frame) and .strand holds it with "codons"."""
 
     def __init__(self, r, byte_is_frame=False):
         h, n = int(r.n_hits), int(r.n_rows)
@@ -1937,6 +1960,23 @@ def _seed_opts(strand, min_seeds, band, pad, max_occ, max_hits=0, slice_rows=0):
     return pmx_seed_opts_t(_strand_mode(strand), int(min_seeds), int(band), int(pad), int(max_occ), 0, int(max_hits), int(slice_rows))
 
 
+def _seed_ref_mode(index, ref_frames, frames, strand, code):
+    """ref_frames= of seed_pairs -> the ref_mode of a translated index (None: another index, which does not take it)."""
+    if not getattr(index, "translated", False):
+        if ref_frames is not None:
+            raise BatchError("ref_frames= is for a translated index (SeedIndex.build(alphabet=, translated=))")
+        return None
+    if strand is not None or frames is not None:
+        raise BatchError("a translated index holds the strands it was built with and takes ref_frames= (\"frames\" or \"codons\"), "
+                         "not strand= or frames=")
+    if code is not None:
+        raise BatchError("code= belongs to the build of a translated index; its queries are proteins")
+    names = {"frames": SEED_REF_FRAMES, "codons": SEED_REF_CODONS}
+    if ref_frames not in names:
+        raise BatchError("a translated index needs ref_frames=: \"frames\" or \"codons\"")
+    return names[ref_frames]
+
+
 def _seed_query_mode(index, frames, strand):
     """frames= of seed_pairs -> the query mode of a letters index (None: a DNA index, which takes strand= instead)."""
     if not index.letters:
@@ -1960,16 +2000,29 @@ def _seed_query_mode(index, frames, strand):
 
 
 def seed_pairs(Q, index, strand=None, min_seeds=2, band=8, pad=16, max_occ=64, first_row=0, rows=None, max_hits=0, slice_rows=0,
-               frames=None, code=None):
+               frames=None, code=None, ref_frames=None):
     """Candidate windows of the queries Q[first_row : first_row + rows] in the indexed reference: exact k-mer matches, clustered
     by diagonal (consecutive diagonals at most `band` apart), clusters of at least min_seeds matches widened by `pad`.
     hits.pairs and hits.strand go unchanged into Aligner.align_pairs(Q, R, pairs, strand=, cigar=True)  (strand: "both" unless given).
     With a letters index `frames` says what Q holds: "letters" (proteins in the index's alphabet), a frame 0 .. 5, "forward", "reverse"
     or "all" (nucleotides, candidates per frame: align_pairs(Q, R, hits.pairs, frame=hits.frame)), "codons", "codons-reverse" or
     "codons-both" (nucleotides, candidates per strand over its three frames, diagonals and band in nucleotides:
-    align_pairs(Q, R, hits.pairs, frameshift=fs, strand=hits.strand)); code: 64 letters that replace the standard genetic code."""
+    align_pairs(Q, R, hits.pairs, frameshift=fs, strand=hits.strand)); code: 64 letters that replace the standard genetic code.
+    With a translated index Q holds proteins and `ref_frames` chooses the candidates: "frames" (per sequence frame, letter diagonals:
+    align_pairs(Q, R, hits.pairs, ref_frame=hits.frame)) or "codons" (per strand over its three frames, diagonals, band and pad in
+    nucleotides: align_pairs(Q, R, hits.pairs, ref_frameshift=fs, ref_strand=hits.strand) and the frameshift_ref_cigar entries)."""
     if rows is None:
         rows = max(0, len(Q) - int(first_row))
+    ref_mode = _seed_ref_mode(index, ref_frames, frames, strand, code)
+    if ref_mode is not None:
+        opts = _seed_opts(0, min_seeds, band, pad, max_occ, max_hits, slice_rows)
+        res = C.POINTER(pmx_seed_hits_t)()
+        if lib.pmx_seed_pairs_translated_ref(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), ref_mode, C.byref(res)):
+            raise BatchError(lib.pmx_last_error().decode())
+        try:
+            return SeedHits(res.contents, byte_is_frame=ref_mode == SEED_REF_FRAMES)
+        finally:
+            lib.pmx_seed_hits_free(res)
     mode = _seed_query_mode(index, frames, strand)
     opts = _seed_opts(0 if mode is not None else "both" if strand is None else strand, min_seeds, band, pad, max_occ, max_hits, slice_rows)
     res = C.POINTER(pmx_seed_hits_t)()
@@ -1990,10 +2043,18 @@ def seed_pairs(Q, index, strand=None, min_seeds=2, band=8, pad=16, max_occ=64, f
 
 
 def seed_pairs_device(Q, index, q_first, nq, max_qlen, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts,
-                      strand=None, min_seeds=2, band=8, pad=16, max_occ=64, slice_rows=0, stream=0, frames=None, code=None):
+                      strand=None, min_seeds=2, band=8, pad=16, max_occ=64, slice_rows=0, stream=0, frames=None, code=None, ref_frames=None):
     """Device-pointer entry of seed_pairs: the candidates go to d_hit_pairs / d_hit_strand / d_hit_seeds (optional), `capacity`
     entries each, d_row_off gets nq + 1 offsets and d_counts [candidates, written].  Synchronises `stream` once per slice.  With a
-    letters index (frames=) d_hit_strand receives the frame or strand byte and max_qlen bounds the letters of a translation."""
+    letters index (frames=) d_hit_strand receives the frame or strand byte and max_qlen bounds the letters of a translation; with a
+    translated index (ref_frames=) it receives the window's frame byte or the strand and max_qlen bounds the letters of a protein."""
+    ref_mode = _seed_ref_mode(index, ref_frames, frames, strand, code)
+    if ref_mode is not None:
+        opts = _seed_opts(0, min_seeds, band, pad, max_occ, 0, slice_rows)
+        if lib.pmx_seed_pairs_translated_ref_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), ref_mode,
+                                                    d_hit_pairs, d_hit_strand, d_hit_seeds, int(capacity), d_row_off, d_counts, stream):
+            raise BatchError(lib.pmx_last_error().decode())
+        return
     mode = _seed_query_mode(index, frames, strand)
     opts = _seed_opts(0 if mode is not None else "both" if strand is None else strand, min_seeds, band, pad, max_occ, 0, slice_rows)
     if mode is None:

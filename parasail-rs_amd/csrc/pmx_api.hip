@@ -5829,6 +5829,7 @@ struct pmx_seed_index {
     int bits = 2;                          // per letter
     bool letters = false;                  // built by pmx_seed_index_build_letters: `table` holds the groups, d_table their device copy
     uint8_t table[256] = {0}; uint8_t *d_table = nullptr;
+    int tr_strands = -1;                   // built by pmx_seed_index_build_translated: the PMX_STRAND_* mode it holds (`table` as above); else -1
 };
 static const int PMX_SEED_BUCKET_BITS = 22;            // 2^22 + 1 numbers of 4 bytes: 16 MiB, resident in the Infinity Cache
 static const int32_t PMX_SEED_BAND_MAX = 1 << 20;
@@ -5856,12 +5857,14 @@ extern "C" void pmx_seed_index_free(pmx_seed_index_t *ix)
 
 extern "C" int64_t pmx_seed_index_count(const pmx_seed_index_t *ix) { return ix ? ix->n : -1; }
 
-// The index of R behind the entries' checks; table: the 256 groups of a letters index of `bits` bits per letter, NULL: the DNA index
-static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int32_t k, int bits, const uint8_t *table, void *stream)
+// The index of R behind the entries' checks; table: the 256 groups of a letters index of `bits` bits per letter, NULL: the DNA index;
+// tr_strands >= 0: a translated index of those strands under `code`, one entry slot per byte and strand
+static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int32_t k, int bits, const uint8_t *table, void *stream, int tr_strands = -1,
+                                          const uint8_t *code = nullptr)
 {
     pmx_seed_index *ix = new (std::nothrow) pmx_seed_index();
     if (!ix) { set_err("out of memory"); return nullptr; }
-    ix->R = R; ix->k = k; ix->dev = R->dev; ix->bits = bits; ix->letters = table != nullptr;
+    ix->R = R; ix->k = k; ix->dev = R->dev; ix->bits = bits; ix->letters = table != nullptr && tr_strands < 0; ix->tr_strands = tr_strands;
     if (table) memcpy(ix->table, table, 256);
     const int bbits = std::min(bits * k, PMX_SEED_BUCKET_BITS);
     ix->shift = bits * k - bbits; ix->nb = (int64_t)1 << bbits;
@@ -5870,8 +5873,9 @@ static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int32_t k, int 
     if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); delete ix; return nullptr; }
     if (R->dev != dev) { set_err("a sequence set of device %d cannot be used on the current device %d", R->dev, dev); delete ix; return nullptr; }
     const hipStream_t st = (hipStream_t)stream;
-    const size_t nbytes = (size_t)R->bytes;
-    const size_t temp_bytes = table ? pmx_seed_index_sort_bytes_letters(R->bytes, k, bits) : pmx_seed_index_sort_bytes(R->bytes, k);
+    const int nstr = tr_strands == PMX_STRAND_BOTH ? 2 : 1;
+    const size_t nbytes = (size_t)R->bytes * (size_t)nstr;                  // entry slots
+    const size_t temp_bytes = table ? pmx_seed_index_sort_bytes_letters((long long)nbytes, k, bits) : pmx_seed_index_sort_bytes(R->bytes, k);
     uint64_t *kin = nullptr, *vin = nullptr; void *temp = nullptr; unsigned long long *d_n = nullptr, h_n = 0;
     hipError_t e = hipMalloc((void **)&ix->keys, nbytes * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&ix->vals, nbytes * 8);
@@ -5884,7 +5888,12 @@ static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int32_t k, int 
     if (e == hipSuccess && table) e = hipMalloc((void **)&ix->d_table, 256);
     if (e == hipSuccess && table) e = hipMemcpyAsync(ix->d_table, ix->table, 256, hipMemcpyHostToDevice, st);
     int rc = 0;
-    if (e == hipSuccess && table)
+    if (e == hipSuccess && tr_strands >= 0) {
+        PmxCodeTable ct;
+        if (code) memcpy(ct.v, code, 64); else pmx_genetic_code_host(ct.v);
+        rc = pmx_launch_seed_index_translated(R->d_buf, R->d_off, R->count, R->bytes, k, bits, ix->d_table, ct, nstr, tr_strands == PMX_STRAND_REVERSE ? 1 : 0,
+                                              kin, vin, ix->keys, ix->vals, temp, temp_bytes, d_n, st);
+    } else if (e == hipSuccess && table)
         rc = pmx_launch_seed_index_letters(R->d_buf, R->d_off, R->count, R->bytes, k, bits, ix->d_table, kin, vin, ix->keys, ix->vals, temp, temp_bytes, d_n, st);
     else if (e == hipSuccess)
         rc = pmx_launch_seed_index(R->d_buf, R->d_off, R->count, R->bytes, k, kin, vin, ix->keys, ix->vals, temp, temp_bytes, d_n, st);
@@ -5931,20 +5940,28 @@ extern "C" int pmx_seed_alphabet(int which, uint8_t table[256])
 
 extern "C" int32_t pmx_seed_index_bits(const pmx_seed_index_t *ix) { return ix ? ix->bits : -1; }
 
-extern "C" pmx_seed_index_t *pmx_seed_index_build_letters(const pmx_seqset_t *R, int32_t k, const uint8_t table[256], void *stream)
+// What the letters and the translated build refuse about set, table and k; > 0: the bits per letter
+static int seed_table_bits(const pmx_seqset_t *R, int32_t k, const uint8_t *table)
 {
-    if (!R) { set_err("null sequence set"); return nullptr; }
-    if (!table) { set_err("null alphabet table"); return nullptr; }
+    if (!R) { set_err("null sequence set"); return -1; }
+    if (!table) { set_err("null alphabet table"); return -1; }
     int groups = 0;
     for (int b = 0; b < 256; ++b) {
         if (table[b] == 255) continue;
-        if (table[b] > 31) { set_err("the alphabet table maps byte %d to group %d: groups are 0 .. 31, 255 marks an invalid byte", b, (int)table[b]); return nullptr; }
+        if (table[b] > 31) { set_err("the alphabet table maps byte %d to group %d: groups are 0 .. 31, 255 marks an invalid byte", b, (int)table[b]); return -1; }
         groups = std::max(groups, (int)table[b] + 1);
     }
-    if (groups < 2) { set_err("the alphabet table holds %d group(s): an alphabet has 2 .. 32", groups); return nullptr; }
+    if (groups < 2) { set_err("the alphabet table holds %d group(s): an alphabet has 2 .. 32", groups); return -1; }
     int bits = 1;
     while ((1 << bits) < groups) ++bits;
-    if (k < 2 || (int64_t)k * bits > 62) { set_err("k %d with %d bits per letter is outside k >= 2 and k x bits <= 62", (int)k, bits); return nullptr; }
+    if (k < 2 || (int64_t)k * bits > 62) { set_err("k %d with %d bits per letter is outside k >= 2 and k x bits <= 62", (int)k, bits); return -1; }
+    return bits;
+}
+
+extern "C" pmx_seed_index_t *pmx_seed_index_build_letters(const pmx_seqset_t *R, int32_t k, const uint8_t table[256], void *stream)
+{
+    const int bits = seed_table_bits(R, k, table);
+    if (bits < 0) return nullptr;
     if (R->bytes > ((int64_t)1 << 29) - 1 || R->count > INT32_MAX) {
         set_err("a letters seed index holds a set of at most 2^29 - 1 bytes and 2^31 - 1 sequences (this one: %lld bytes, %lld sequences): index parts of it",
                 (long long)R->bytes, (long long)R->count);
@@ -5952,6 +5969,22 @@ extern "C" pmx_seed_index_t *pmx_seed_index_build_letters(const pmx_seqset_t *R,
     }
     return seed_index_build(R, k, bits, table, stream);
 }
+
+extern "C" pmx_seed_index_t *pmx_seed_index_build_translated(const pmx_seqset_t *R, int32_t k, const uint8_t table[256], const uint8_t *code,
+                                                             int strand_mode, void *stream)
+{
+    const int bits = seed_table_bits(R, k, table);
+    if (bits < 0) return nullptr;
+    if (strand_mode < PMX_STRAND_FORWARD || strand_mode > PMX_STRAND_BOTH) { set_err("strand mode %d is outside 0 .. 2", strand_mode); return nullptr; }
+    if (R->bytes > ((int64_t)1 << 30) - 1 || R->count > ((int64_t)1 << 29)) {
+        set_err("a translated seed index holds a set of at most 2^30 - 1 bytes and 2^29 sequences (this one: %lld bytes, %lld sequences): index parts of it",
+                (long long)R->bytes, (long long)R->count);
+        return nullptr;
+    }
+    return seed_index_build(R, k, bits, table, stream, strand_mode, code);
+}
+
+extern "C" int32_t pmx_seed_index_strands(const pmx_seed_index_t *ix) { return !ix ? -1 : ix->tr_strands >= 0 ? ix->tr_strands : -2; }
 
 extern "C" int pmx_seed_index_entries_device(const pmx_seed_index_t *ix, int64_t first, int64_t count, uint64_t *d_kmer, int64_t *d_seq,
                                              int32_t *d_pos, void *stream)
@@ -5983,8 +6016,11 @@ static int seed_mode_orients(int query_mode)
 // the orientation slots per row, first = the first one's frame (< 0: the rows are letters), codon = the codon modes.
 struct SeedMode {
     bool letters = false, codon = false; int orients = 1, first = 0; PmxCodeTable code;
+    bool ref = false;                      // a translated index: the rows are proteins, codon = PMX_SEED_REF_CODONS
 };
 #define PMX_SEED_MODE_DNA INT32_MIN                     // query_mode of the DNA entries inside this file
+#define PMX_SEED_MODE_REF (INT32_MIN + 2)               // ... of the translated-reference entries: + PMX_SEED_REF_FRAMES / _CODONS, + 2: a bad ref_mode
+static bool seed_mode_ref(int query_mode) { return query_mode >= PMX_SEED_MODE_REF && query_mode <= PMX_SEED_MODE_REF + 2; }
 
 // What the seeding entries refuse about their arguments; lens_known false: the host entry before it has looked at the lengths
 // (max_qlen and the budget rule are checked in its second call).  query_mode: PMX_SEED_MODE_DNA or the letters entry's mode.
@@ -5996,8 +6032,12 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_f
     if (!Q) { set_err("null sequence set"); return -1; }
     if (!ix) { set_err("null seed index"); return -1; }
     if (!o) { set_err("null opts"); return -1; }
-    if (dna && ix->letters) { set_err("a letters index (pmx_seed_index_build_letters) is seeded by pmx_seed_pairs_letters[_device]"); return -1; }
-    if (!dna && !ix->letters) { set_err("a DNA index (pmx_seed_index_build) is seeded by pmx_seed_pairs[_device]"); return -1; }
+    const bool tref = seed_mode_ref(query_mode);
+    if (ix->tr_strands >= 0 && !tref) {
+        set_err("a translated index (pmx_seed_index_build_translated) is seeded by pmx_seed_pairs_translated_ref[_device]"); return -1;
+    }
+    if (ix->letters && (dna || tref)) { set_err("a letters index (pmx_seed_index_build_letters) is seeded by pmx_seed_pairs_letters[_device]"); return -1; }
+    if (!dna && !ix->letters && ix->tr_strands < 0) { set_err("a DNA index (pmx_seed_index_build) is seeded by pmx_seed_pairs[_device]"); return -1; }
     if (q_first < 0 || nq < 0) { set_err("negative q_first or nq"); return -1; }
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (o->max_hits < 0) { set_err("max_hits must not be negative"); return -1; }
@@ -6008,8 +6048,10 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_f
     }
     if (max_qlen < 1) { set_err("max_qlen must be positive"); return -1; }
     if (dna && (o->strand < PMX_STRAND_FORWARD || o->strand > PMX_STRAND_BOTH)) { set_err("strand mode %d is outside 0 .. 2", (int)o->strand); return -1; }
-    if (!dna && o->strand != 0) { set_err("opts->strand %d must be 0 with a letters index: query_mode chooses the orientations", (int)o->strand); return -1; }
-    if (!dna && !seed_mode_valid(query_mode)) {
+    if (tref && o->strand != 0) { set_err("opts->strand %d must be 0 with a translated index: it holds the strands it was built with", (int)o->strand); return -1; }
+    if (tref && query_mode == PMX_SEED_MODE_REF + 2) { set_err("ref_mode is neither PMX_SEED_REF_FRAMES (0) nor PMX_SEED_REF_CODONS (1)"); return -1; }
+    if (!dna && !tref && o->strand != 0) { set_err("opts->strand %d must be 0 with a letters index: query_mode chooses the orientations", (int)o->strand); return -1; }
+    if (!dna && !tref && !seed_mode_valid(query_mode)) {
         set_err("query mode %d is none of PMX_SEED_QUERY_LETTERS (-1), a frame 0 .. 5, PMX_FRAMES_FORWARD / _REVERSE / _ALL (6 .. 8), "
                 "PMX_SEED_CODONS_FORWARD / _REVERSE / _BOTH (9 .. 11)", query_mode);
         return -1;
@@ -6019,7 +6061,7 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_f
     if (o->pad < 0 || o->pad > PMX_SEED_BAND_MAX) { set_err("pad %d is outside 0 .. 2^20", (int)o->pad); return -1; }
     if (o->max_occ < 1 || o->max_occ > 65535) { set_err("max_occ %d is outside 1 .. 65535", (int)o->max_occ); return -1; }
     if (o->reserved != 0) { set_err("reserved must be 0"); return -1; }
-    const int64_t strands = dna ? (o->strand == PMX_STRAND_BOTH ? 2 : 1) : seed_mode_orients(query_mode);
+    const int64_t strands = dna ? (o->strand == PMX_STRAND_BOTH ? 2 : 1) : tref ? 1 : seed_mode_orients(query_mode);
     const double worst = (double)max_qlen * (double)strands * (double)o->max_occ * (double)PMX_SEED_MATCH_BYTES;
     if (worst > (double)seed_match_budget()) {
         set_err("one row's worst case of %d positions x %d %s x max_occ %d x %d bytes per match does not fit the match buffer of %lld bytes: "
@@ -6043,6 +6085,17 @@ static SeedMode seed_mode_letters(int query_mode, const uint8_t *code)
             : query_mode == PMX_FRAMES_REVERSE || query_mode == PMX_SEED_CODONS_REVERSE ? 3 : 0;
     if (code) memcpy(m.code.v, code, 64); else pmx_genetic_code_host(m.code.v);
     return m;
+}
+
+static SeedMode seed_mode_ref_of(int query_mode)
+{
+    SeedMode m; m.letters = m.ref = true; m.first = -1; m.codon = query_mode == PMX_SEED_MODE_REF + PMX_SEED_REF_CODONS;
+    pmx_genetic_code_host(m.code.v);       // (the code stage of rows that are letters reads no codon)
+    return m;
+}
+static SeedMode seed_mode_of(int query_mode, const pmx_seed_opts_t *o, const uint8_t *code)
+{
+    return query_mode == PMX_SEED_MODE_DNA ? seed_mode_dna(o) : seed_mode_ref(query_mode) ? seed_mode_ref_of(query_mode) : seed_mode_letters(query_mode, code);
 }
 
 static int seed_device_check(const pmx_seqset *Q, const pmx_seed_index *ix)
@@ -6082,7 +6135,7 @@ static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_fir
             if (mode.letters) codes = c.take<uint8_t>((size_t)positions);
         })) return -1;
     int key_bits = 33;                                   // the diagonal and the bits of a reference index
-    while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < ix->R->count) ++key_bits;
+    while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < (mode.ref ? 6 : 1) * ix->R->count) ++key_bits;
     for (int64_t row = 0; row < nq;) {
         const int64_t rows = std::min(slice, nq - row);
         int rc = mode.letters
@@ -6095,7 +6148,11 @@ static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_fir
         HIP_OR_RET(hipMemcpyAsync(h, cut, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
         if (h[0] < 1 || h[0] > rows || h[1] < 0 || h[1] > cap_m) { set_err("seed cut of rows %lld .. is inconsistent", (long long)(q_first + row)); return -1; }
-        rc = mode.letters
+        rc = mode.ref
+            ? pmx_launch_seed_cluster_translated(q_first + row, h[0], mode.codon, max_qlen, ix->R->count, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb,
+                                                 head, flag, o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand,
+                                                 d_hit_seeds, d_row_off + row, d_counts, temp, temp_bytes, st)
+            : mode.letters
             ? pmx_launch_seed_cluster_letters(q_first + row, h[0], strands, strand0, mode.codon, max_qlen, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb,
                                               head, flag, o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand,
                                               d_hit_seeds, d_row_off + row, d_counts, temp, temp_bytes, st)
@@ -6126,7 +6183,7 @@ static int seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, 
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     return seed_run(Q, ix, q_first, nq, max_qlen, opts, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts, (hipStream_t)stream,
-                    query_mode == PMX_SEED_MODE_DNA ? seed_mode_dna(opts) : seed_mode_letters(query_mode, code));
+                    seed_mode_of(query_mode, opts, code));
 }
 
 extern "C" int pmx_seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
@@ -6142,7 +6199,7 @@ extern "C" int pmx_seed_pairs_letters_device(const pmx_seqset_t *Q, const pmx_se
                                              pmx_pair_t *d_hit_pairs, uint8_t *d_hit_byte, pmx_seed_hit_t *d_hit_seeds, int64_t capacity,
                                              int64_t *d_row_off, int64_t *d_counts, void *stream)
 {
-    if (query_mode == PMX_SEED_MODE_DNA) query_mode = PMX_SEED_MODE_DNA + 1;      // (an invalid mode like any other)
+    if (query_mode == PMX_SEED_MODE_DNA || seed_mode_ref(query_mode)) query_mode = PMX_SEED_MODE_DNA + 1;      // (an invalid mode like any other)
     return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, query_mode, code, d_hit_pairs, d_hit_byte, d_hit_seeds, capacity, d_row_off, d_counts,
                              stream);
 }
@@ -6155,7 +6212,7 @@ static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, in
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
     if (seed_check(Q, ix, q_first, nq, 0, opts, 0, false, query_mode)) return -1;
-    const SeedMode mode = query_mode == PMX_SEED_MODE_DNA ? seed_mode_dna(opts) : seed_mode_letters(query_mode, code);
+    const SeedMode mode = seed_mode_of(query_mode, opts, code);
     // the result: one block -- header, row offsets, descriptors, seed records, strand bytes
     auto block = [&](int64_t stored, int64_t passing) -> pmx_seed_hits_t * {
         Carver c; c.align = 16;
@@ -6241,6 +6298,21 @@ extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix,
 extern "C" int pmx_seed_pairs_letters(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
                                       int query_mode, const uint8_t *code, pmx_seed_hits_t **result)
 {
-    if (query_mode == PMX_SEED_MODE_DNA) query_mode = PMX_SEED_MODE_DNA + 1;
+    if (query_mode == PMX_SEED_MODE_DNA || seed_mode_ref(query_mode)) query_mode = PMX_SEED_MODE_DNA + 1;
     return seed_pairs_host(Q, ix, q_first, nq, opts, query_mode, code, result);
+}
+
+extern "C" int pmx_seed_pairs_translated_ref_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
+                                                    const pmx_seed_opts_t *opts, int ref_mode, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_byte,
+                                                    pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
+{
+    const int mode = PMX_SEED_MODE_REF + (ref_mode == PMX_SEED_REF_FRAMES || ref_mode == PMX_SEED_REF_CODONS ? ref_mode : 2);
+    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, mode, nullptr, d_hit_pairs, d_hit_byte, d_hit_seeds, capacity, d_row_off, d_counts, stream);
+}
+
+extern "C" int pmx_seed_pairs_translated_ref(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
+                                             int ref_mode, pmx_seed_hits_t **result)
+{
+    const int mode = PMX_SEED_MODE_REF + (ref_mode == PMX_SEED_REF_FRAMES || ref_mode == PMX_SEED_REF_CODONS ? ref_mode : 2);
+    return seed_pairs_host(Q, ix, q_first, nq, opts, mode, nullptr, result);
 }

@@ -488,6 +488,18 @@ int pmx_launch_seed_cluster_letters(long long row0, long long rows, int orients,
                                     const int64_t *qoff, const int64_t *roff, long long capacity,
                                     pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
                                     void *temp, size_t temp_bytes, hipStream_t stream);
+// A translated index: the six-frame k-mers of a nucleotide set, nstr strands from strand0, nstr * bytes entry slots
+// (val = (strand * count + seq) << 32 | oriented position).  Seeding counts with pmx_launch_seed_count_letters (orients 1, first < 0:
+// the rows are proteins); cluster: the mode's id, diagonal and window, codon = PMX_SEED_REF_CODONS; count: the set's sequences.
+int pmx_launch_seed_index_translated(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int bits, const uint8_t *table,
+                                     const PmxCodeTable &code, int nstr, int strand0, uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out,
+                                     uint64_t *vals_out, void *temp, size_t temp_bytes, unsigned long long *n_valid, hipStream_t stream);
+int pmx_launch_seed_cluster_translated(long long row0, long long rows, bool codon, int max_qlen, long long count, long long m, int key_bits,
+                                       const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
+                                       uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
+                                       const int64_t *qoff, const int64_t *roff, long long capacity,
+                                       pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
+                                       void *temp, size_t temp_bytes, hipStream_t stream);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);

@@ -666,3 +666,194 @@ int pmx_launch_seed_cluster_letters(long long row0, long long rows, int orients,
     }
     return pmx_seed_finish(rows, (long long)orients * max_qlen, m, moff, flag, capacity, row_off, counts, stream);
 }
+
+// ---- translated references: a six-frame index of a nucleotide set, proteins as queries ---------------------------------
+// An oriented position x of sequence r on strand s (0: as stored, 1: reverse-complemented, read from the end downwards through the
+// complement, nothing materialised) starts the codon of oriented bytes x .. x + 2; the k-mer at x is the k codons' letters at x, x + 3,
+// ..., so the index holds the k-mers of all three frames of a strand and x % 3 is the frame's offset.  Entry slot of (s, r, x):
+// s_local * bytes + off[r] + x -- the stable sort then leaves (kmer, s, r, x) order with nothing compacted.  Seeding runs the letters
+// road's code stage and count pass on the protein rows; emit and hits below carry the mode's id, diagonal and window.
+#define PMX_SEEDT_TILE 48       // slots per thread: a multiple of 3, so a slot's phase is its place in the step unrolled by three
+
+// keys[sl * bytes + p] / vals[..] for every p < bytes of the nstr strands held (strand of sl: strand0 + sl); *n_valid += the k-mers.
+// A thread owns one strand and PMX_SEEDT_TILE slots, reads 3 k - 1 bytes past them and rolls one key per phase: each byte enters a
+// rolling 6-bit codon index once, the codon's letter goes through the genetic code and the table (both in LDS), and the key of that
+// phase takes it.  Strand 1 rolls the stored bytes' classes and complements the index by ^ 42, as pmx_seedl_codes_kernel.  'X' (a
+// byte that is no nucleotide), '*' and the table's 255 break a k-mer; so does a sequence end.  Offsets are read at 0 .. count only and
+// a byte only below `bytes`.
+__global__ void __launch_bounds__(256) pmx_seedt_extract_kernel(const uint8_t *__restrict__ buf, const int64_t *__restrict__ off, long long count,
+                                                                long long bytes, int k, int bits, const uint8_t *__restrict__ table, PmxCodeTable code,
+                                                                int nstr, int strand0, long long tiles, uint64_t *__restrict__ keys,
+                                                                uint64_t *__restrict__ vals, unsigned long long *n_valid)
+{
+    __shared__ uint8_t grp[256];
+    __shared__ uint8_t cod[64];
+    __shared__ unsigned total;
+    grp[threadIdx.x] = table[threadIdx.x];
+    if (threadIdx.x < 64) cod[threadIdx.x] = code.v[threadIdx.x];
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long sl = t / tiles, p0 = (t - sl * tiles) * PMX_SEEDT_TILE;
+    unsigned found = 0;
+    if (sl < nstr && p0 < bytes) {
+        const int strand = strand0 + (int)sl;
+        const uint32_t flip = strand ? 42u : 0u;
+        const uint64_t invalid = (uint64_t)1 << (k * bits), mask = invalid - 1, id0 = (uint64_t)strand * (uint64_t)count;
+        const long long span = 3ll * k - 1, base = sl * bytes;
+        long long lo = 0, hi = count + 1;
+        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (off[mid] <= p0) lo = mid + 1; else hi = mid; }
+        long long r = lo - 1;
+        long long e = r < count ? off[r + 1] : INT64_MAX;
+        long long b = r >= 0 ? off[r] : 0;
+        const long long pend = min(p0 + PMX_SEEDT_TILE, bytes), xend = min(pend + span, bytes);
+        uint64_t key0 = 0, key1 = 0, key2 = 0;
+        int run0 = 0, run1 = 0, run2 = 0, nrun = 0;
+        uint32_t c6 = 0;
+        long long x = p0;
+        // one slot of the walk: the byte at x closes the codon that starts at x - 2, whose letter the phase's key takes.  An invalid
+        // letter is not cleared out of the key (pmx_seedl_extract_kernel zeroes it): its bits go in as g & 31 and RUN = 0, and a slot is
+        // valid again only after k further letters of the phase, which shift them above `mask`.  No `s >= b` test either: every run is
+        // reset at a sequence end, so RUN >= k means k codons of this phase inside the sequence, the first of them at s
+#define PMX_SEEDT_STEP(KEY, RUN)                                                                                                        \
+        if (x < xend) {                                                                                                                 \
+            while (x >= e && r < count) { ++r; b = e; e = r < count ? off[r + 1] : INT64_MAX; nrun = 0; run0 = run1 = run2 = 0; }       \
+            const bool inside = r >= 0 && r < count && b >= 0 && b <= x && x < e && e <= bytes;                                         \
+            const uint32_t cls = inside ? pmx_seedl_base(buf[strand ? b + e - 1 - x : x]) : 4u;                                         \
+            nrun = cls > 3u ? 0 : nrun + 1;                                                                                             \
+            c6 = ((c6 << 2) | (cls & 3u)) & 63u;                                                                                        \
+            const uint32_t letter = cod[c6 ^ flip];                                                                                     \
+            const uint32_t g = nrun >= 3 && letter != (uint32_t)'X' && letter != (uint32_t)'*' ? (uint32_t)grp[letter] : 255u;          \
+            KEY = (KEY << bits) | (uint64_t)(g & 31u);                                                                                  \
+            RUN = g == 255u ? 0 : RUN + 1;                                                                                              \
+            const long long s = x - span;                                                                                               \
+            if (s >= p0) {                                                                                                              \
+                const bool have = RUN >= k;                                                                                             \
+                keys[base + s] = have ? (KEY & mask) : invalid;                                                                         \
+                vals[base + s] = have ? ((id0 + (uint64_t)r) << 32) | (uint64_t)(uint32_t)(s - b) : (uint64_t)(base + s);               \
+                found += have ? 1u : 0u;                                                                                                \
+            }                                                                                                                           \
+            ++x;                                                                                                                        \
+        }
+        while (x < xend) { PMX_SEEDT_STEP(key0, run0) PMX_SEEDT_STEP(key1, run1) PMX_SEEDT_STEP(key2, run2) }
+#undef PMX_SEEDT_STEP
+        for (long long s = max(p0, xend - span); s < pend; ++s) { keys[base + s] = invalid; vals[base + s] = (uint64_t)(base + s); }
+    }
+    if (found) atomicAdd(&total, found);
+    __syncthreads();
+    if (threadIdx.x == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+}
+
+// keys_in / vals_in / keys_out / vals_out: nstr * bytes entry slots each
+int pmx_launch_seed_index_translated(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int bits, const uint8_t *table,
+                                     const PmxCodeTable &code, int nstr, int strand0, uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out,
+                                     uint64_t *vals_out, void *temp, size_t temp_bytes, unsigned long long *n_valid, hipStream_t stream)
+{
+    if (bytes <= 0) return 0;
+    const long long tiles = (bytes + PMX_SEEDT_TILE - 1) / PMX_SEEDT_TILE, threads = tiles * nstr;
+    hipLaunchKernelGGL(pmx_seedt_extract_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, buf, off, count, bytes, k, bits, table,
+                       code, nstr, strand0, tiles, keys_in, vals_in, n_valid);
+    int rc = pmx_launched();
+    if (rc) return rc;
+    const hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)(bytes * nstr), 0, k * bits + 1, stream);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+// pmx_seedl_emit_kernel for a translated index: an entry's value is (s * count + r) << 32 | x.  CODON false: the match key's id is
+// g * count + r with the sequence frame g = 3 s + x % 3, its diagonal d = x / 3 - i in letters.  CODON true: id = s * count + r and
+// the nucleotide diagonal D = x - 3 i.  |d| < 2^31 by x < 2^30 and 3 i < 2^31 (a row's worst case fits the match buffer).
+template <bool CODON>
+__global__ void __launch_bounds__(256) pmx_seedt_emit_kernel(long long total, int max_qlen, long long count, const uint32_t *__restrict__ lo,
+                                                             const uint32_t *__restrict__ cnt, const int64_t *__restrict__ moff,
+                                                             const uint64_t *__restrict__ vals, uint64_t *__restrict__ mkeys)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const uint32_t n = cnt[p];
+    if (!n) return;
+    const long long i = p % max_qlen;
+    const uint32_t first = lo[p];
+    uint64_t *out = mkeys + moff[p];
+    for (uint32_t y = 0; y < n; ++y) {
+        const uint64_t v = vals[first + y];
+        const long long x = (long long)(uint32_t)v, id0 = (long long)(v >> 32);
+        long long id, d;
+        if (CODON) { id = id0; d = x - 3 * i; }
+        else {
+            const long long s = id0 >= count ? 1 : 0;
+            id = (3 * s + x % 3) * count + (id0 - s * count); d = x / 3 - i;
+        }
+        out[y] = ((uint64_t)id << 32) | (uint64_t)((uint32_t)(int32_t)d ^ 0x80000000u);
+    }
+}
+
+// pmx_seedl_hits_kernel for a translated index; a segment is a row (`stride` = max_qlen slots), m its letters, N = len(r).
+// CODON false: id = g * count + r; the letter window [lb, le) = [max(0, d_min - pad), min((N - g % 3) / 3, d_max + m + pad)) of frame g
+// as stored nucleotides, codon-aligned: [g % 3 + 3 lb, g % 3 + 3 le) on strand 0, [N - g % 3 - 3 le, N - g % 3 - 3 lb) on strand 1, so
+// the frame byte relative to the window is 0 or 3; reserved = g.  CODON true: id = s * count + r; the oriented window
+// [max(0, D_min - pad), min(N, D_max + 3 m + pad)), stored [lo, hi) or [N - hi, N - lo); byte = s; reserved = 0.
+template <bool CODON>
+__global__ void __launch_bounds__(256) pmx_seedt_hits_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ pos,
+                                                             long long m, const int64_t *__restrict__ moff, long long slots, long long stride,
+                                                             long long row0, long long count, int pad,
+                                                             const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
+                                                             const int64_t *__restrict__ counts, long long capacity,
+                                                             pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_byte, pmx_seed_hit_t *__restrict__ hit_seeds)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= m || pos[x + 1] == pos[x]) return;
+    const long long at = counts[0] + (long long)pos[x];
+    if (at >= capacity) return;
+    long long a = 0, z = slots - 1;             // the row of x: the last t with moff[t * stride] <= x (empty segments share a start)
+    while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= x) a = mid; else z = mid - 1; }
+    const long long row = row0 + a;
+    const uint32_t h = head[x];
+    const uint64_t kh = mkeys[h], kt = mkeys[x];
+    const long long id = (long long)(kt >> 32), dmin = pmx_seed_diag(kh), dmax = pmx_seed_diag(kt);
+    const long long o = id / count, r = id - o * count;         // o: the sequence frame g (CODON false), the strand (CODON true)
+    const long long len = qoff[row + 1] - qoff[row], N = roff[r + 1] - roff[r];
+    long long beg, end; int byte, res;
+    if (CODON) {
+        const long long wlo = max(0ll, dmin - pad), whi = min(N, dmax + 3 * len + pad);
+        beg = o ? N - whi : wlo; end = o ? N - wlo : whi;
+        byte = (int)o; res = 0;
+    } else {
+        const long long ph = o % 3, lb = max(0ll, dmin - pad), le = min((N - ph) / 3, dmax + len + pad);
+        beg = o >= 3 ? N - ph - 3 * le : ph + 3 * lb; end = o >= 3 ? N - ph - 3 * lb : ph + 3 * le;
+        byte = o >= 3 ? 3 : 0; res = (int)o;
+    }
+    pmx_pair_t pr; pr.q = row; pr.r = r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)beg; pr.r_len = (int32_t)(end - beg);
+    hit_pairs[at] = pr;
+    hit_byte[at] = (uint8_t)byte;
+    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = (int32_t)(x - h + 1); s.diag_min = (int32_t)dmin; s.diag_max = (int32_t)dmax; s.reserved = res; hit_seeds[at] = s; }
+}
+
+// pmx_launch_seed_cluster for a translated index (the count pass before it: pmx_launch_seed_count_letters in letters mode);
+// count: the sequences of the indexed set; codon: PMX_SEED_REF_CODONS.
+int pmx_launch_seed_cluster_translated(long long row0, long long rows, bool codon, int max_qlen, long long count, long long m, int key_bits,
+                                       const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
+                                       uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
+                                       const int64_t *qoff, const int64_t *roff, long long capacity,
+                                       pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
+                                       void *temp, size_t temp_bytes, hipStream_t stream)
+{
+    const long long slots = rows, stride = max_qlen, total = slots * stride;
+    int rc = 0;
+    if (m > 0) {
+        const dim3 eb((unsigned)((total + 255) / 256)), hb((unsigned)((m + 255) / 256));
+        if (codon) hipLaunchKernelGGL(pmx_seedt_emit_kernel<true>, eb, dim3(256), 0, stream, total, max_qlen, count, lo, cnt, moff, vals, mkeys_a);
+        else hipLaunchKernelGGL(pmx_seedt_emit_kernel<false>, eb, dim3(256), 0, stream, total, max_qlen, count, lo, cnt, moff, vals, mkeys_a);
+        if ((rc = pmx_launched())) return rc;
+        if ((rc = pmx_seed_sort_clusters(m, slots, stride, key_bits, moff, mkeys_a, mkeys_b, head, flag, band, min_seeds, temp, temp_bytes, stream))) return rc;
+        if (capacity > 0) {
+            if (codon)
+                hipLaunchKernelGGL(pmx_seedt_hits_kernel<true>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
+                                   m, moff, slots, stride, row0, count, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte, hit_seeds);
+            else
+                hipLaunchKernelGGL(pmx_seedt_hits_kernel<false>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
+                                   m, moff, slots, stride, row0, count, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte, hit_seeds);
+            if ((rc = pmx_launched())) return rc;
+        }
+    }
+    return pmx_seed_finish(rows, stride, m, moff, flag, capacity, row_off, counts, stream);
+}
