@@ -1654,6 +1654,16 @@ int pmx_trace_plan_probe(int mode, int msize, int score_min, int score_max, int 
  * of the checkpoints, bytes of the checkpoints, checkpoint slots per (pair, band); or 1, refused, with all nine 0. */
 int pmx_long_plan_probe(int road, int mode, long long n, int max_qlen, int max_rlen, double budget, int budget_forced,
                         int two_columns, int one_column, int rows_per_lane, int chunk_cols, int tile_cols, int band_rows, long long *out);
+/* Test hook of the seeding entries' planning (host arithmetic only, no device needed; expected values: tests/golden/seed_plans.json):
+ * the run planned for nq rows of up to max_qlen letters by the entries of an index of `kind` (0 pmx_seed_pairs, 1 pmx_seed_pairs_letters,
+ * 2 pmx_seed_pairs_translated_ref) under `mode` (opts->strand, query_mode, ref_mode) with opts->max_occ and opts->slice_rows, against a
+ * set of ref_count sequences, with what pmx_seed_match_budget would say as an argument (budget in bytes, 0: the default).  Returns 0 with
+ * out[0 .. 10] = orientations per row, the first one's strand or frame (-1 where a letters or translated index reads the rows as they
+ * stand), segments per row, position slots per segment, position slots per row, scratch bytes per position slot, rows per slice, the
+ * match buffer's entries, position slots per slice, rows x orientations per slice, sorted bits of a match key; 1 with all eleven 0
+ * where one row's worst case does not fit the budget; -1 on an argument no entry would plan. */
+int pmx_seed_plan_probe(int kind, int mode, long long nq, int max_qlen, int max_occ, long long slice_rows, long long budget,
+                        long long ref_count, long long *out);
 
 #ifdef __cplusplus
 }

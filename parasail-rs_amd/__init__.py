@@ -428,6 +428,7 @@ _sig("pmx_frameshift_ref_cigar_long_parts", C.c_int64)
 _sig("pmx_swfsc_window_cols", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong)
 _sig("pmx_trace_plan_probe", C.c_int, *([C.c_int] * 7 + [C.c_longlong] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)]))
 _sig("pmx_long_plan_probe", C.c_int, *([C.c_int] * 2 + [C.c_longlong] + [C.c_int] * 2 + [C.c_double] + [C.c_int] * 7 + [C.POINTER(C.c_longlong)]))
+_sig("pmx_seed_plan_probe", C.c_int, *([C.c_int] * 2 + [C.c_longlong] + [C.c_int] * 2 + [C.c_longlong] * 3 + [C.POINTER(C.c_longlong)]))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -1999,6 +2000,24 @@ def _seed_query_mode(index, frames, strand):
     return int(frames)
 
 
+def _seed_entry(index, strand, frames, code, ref_frames, min_seeds, band, pad, max_occ, max_hits, slice_rows):
+    """What seed_pairs and seed_pairs_device call for this index and these arguments: (the host entry, the device entry, opts, the
+    entry's own arguments behind opts, byte_is_frame, what those arguments point into)."""
+    ref_mode = _seed_ref_mode(index, ref_frames, frames, strand, code)
+    if ref_mode is not None:
+        opts = _seed_opts(0, min_seeds, band, pad, max_occ, max_hits, slice_rows)
+        return lib.pmx_seed_pairs_translated_ref, lib.pmx_seed_pairs_translated_ref_device, opts, (ref_mode,), ref_mode == SEED_REF_FRAMES, None
+    mode = _seed_query_mode(index, frames, strand)
+    opts = _seed_opts(0 if mode is not None else "both" if strand is None else strand, min_seeds, band, pad, max_occ, max_hits, slice_rows)
+    if mode is None:
+        if code is not None:
+            raise BatchError("code= is for a letters index")
+        return lib.pmx_seed_pairs, lib.pmx_seed_pairs_device, opts, (), False, None
+    code = _code_arg(code)
+    extra = (mode, code.ctypes.data if code is not None else None)
+    return lib.pmx_seed_pairs_letters, lib.pmx_seed_pairs_letters_device, opts, extra, 0 <= mode <= FRAMES_ALL, code
+
+
 def seed_pairs(Q, index, strand=None, min_seeds=2, band=8, pad=16, max_occ=64, first_row=0, rows=None, max_hits=0, slice_rows=0,
                frames=None, code=None, ref_frames=None):
     """Candidate windows of the queries Q[first_row : first_row + rows] in the indexed reference: exact k-mer matches, clustered
@@ -2013,31 +2032,12 @@ def seed_pairs(Q, index, strand=None, min_seeds=2, band=8, pad=16, max_occ=64, f
     nucleotides: align_pairs(Q, R, hits.pairs, ref_frameshift=fs, ref_strand=hits.strand) and the frameshift_ref_cigar entries)."""
     if rows is None:
         rows = max(0, len(Q) - int(first_row))
-    ref_mode = _seed_ref_mode(index, ref_frames, frames, strand, code)
-    if ref_mode is not None:
-        opts = _seed_opts(0, min_seeds, band, pad, max_occ, max_hits, slice_rows)
-        res = C.POINTER(pmx_seed_hits_t)()
-        if lib.pmx_seed_pairs_translated_ref(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), ref_mode, C.byref(res)):
-            raise BatchError(lib.pmx_last_error().decode())
-        try:
-            return SeedHits(res.contents, byte_is_frame=ref_mode == SEED_REF_FRAMES)
-        finally:
-            lib.pmx_seed_hits_free(res)
-    mode = _seed_query_mode(index, frames, strand)
-    opts = _seed_opts(0 if mode is not None else "both" if strand is None else strand, min_seeds, band, pad, max_occ, max_hits, slice_rows)
+    host, _, opts, extra, byte_is_frame, _keep = _seed_entry(index, strand, frames, code, ref_frames, min_seeds, band, pad, max_occ, max_hits, slice_rows)
     res = C.POINTER(pmx_seed_hits_t)()
-    if mode is None:
-        if code is not None:
-            raise BatchError("code= is for a letters index")
-        rc = lib.pmx_seed_pairs(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), C.byref(res))
-    else:
-        code = _code_arg(code)
-        rc = lib.pmx_seed_pairs_letters(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), mode,
-                                        code.ctypes.data if code is not None else None, C.byref(res))
-    if rc:
+    if host(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), *extra, C.byref(res)):
         raise BatchError(lib.pmx_last_error().decode())
     try:
-        return SeedHits(res.contents, byte_is_frame=mode is not None and 0 <= mode <= FRAMES_ALL)
+        return SeedHits(res.contents, byte_is_frame=byte_is_frame)
     finally:
         lib.pmx_seed_hits_free(res)
 
@@ -2048,26 +2048,9 @@ def seed_pairs_device(Q, index, q_first, nq, max_qlen, d_hit_pairs, d_hit_strand
     entries each, d_row_off gets nq + 1 offsets and d_counts [candidates, written].  Synchronises `stream` once per slice.  With a
     letters index (frames=) d_hit_strand receives the frame or strand byte and max_qlen bounds the letters of a translation; with a
     translated index (ref_frames=) it receives the window's frame byte or the strand and max_qlen bounds the letters of a protein."""
-    ref_mode = _seed_ref_mode(index, ref_frames, frames, strand, code)
-    if ref_mode is not None:
-        opts = _seed_opts(0, min_seeds, band, pad, max_occ, 0, slice_rows)
-        if lib.pmx_seed_pairs_translated_ref_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), ref_mode,
-                                                    d_hit_pairs, d_hit_strand, d_hit_seeds, int(capacity), d_row_off, d_counts, stream):
-            raise BatchError(lib.pmx_last_error().decode())
-        return
-    mode = _seed_query_mode(index, frames, strand)
-    opts = _seed_opts(0 if mode is not None else "both" if strand is None else strand, min_seeds, band, pad, max_occ, 0, slice_rows)
-    if mode is None:
-        if code is not None:
-            raise BatchError("code= is for a letters index")
-        rc = lib.pmx_seed_pairs_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), d_hit_pairs,
-                                       d_hit_strand, d_hit_seeds, int(capacity), d_row_off, d_counts, stream)
-    else:
-        code = _code_arg(code)
-        rc = lib.pmx_seed_pairs_letters_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), mode,
-                                               code.ctypes.data if code is not None else None, d_hit_pairs, d_hit_strand, d_hit_seeds,
-                                               int(capacity), d_row_off, d_counts, stream)
-    if rc:
+    _, device, opts, extra, _, _keep = _seed_entry(index, strand, frames, code, ref_frames, min_seeds, band, pad, max_occ, 0, slice_rows)
+    if device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), *extra, d_hit_pairs, d_hit_strand, d_hit_seeds,
+              int(capacity), d_row_off, d_counts, stream):
         raise BatchError(lib.pmx_last_error().decode())
 
 

@@ -5827,9 +5827,9 @@ struct pmx_seed_index {
     int64_t n = 0, nb = 0;                 // entries; buckets (the table holds nb + 1 numbers)
     uint64_t *keys = nullptr, *vals = nullptr; uint32_t *bucket = nullptr;
     int bits = 2;                          // per letter
-    bool letters = false;                  // built by pmx_seed_index_build_letters: `table` holds the groups, d_table their device copy
-    uint8_t table[256] = {0}; uint8_t *d_table = nullptr;
-    int tr_strands = -1;                   // built by pmx_seed_index_build_translated: the PMX_STRAND_* mode it holds (`table` as above); else -1
+    int kind = PMX_SEED_KIND_DNA;          // PmxSeedKind: which build made it, and with that which entries seed it
+    uint8_t table[256] = {0}; uint8_t *d_table = nullptr;       // letters, translated: the groups and their device copy
+    int strands = -2;                      // translated: the PMX_STRAND_* mode it holds; else -2 (what pmx_seed_index_strands answers)
 };
 static const int PMX_SEED_BUCKET_BITS = 22;            // 2^22 + 1 numbers of 4 bytes: 16 MiB, resident in the Infinity Cache
 static const int32_t PMX_SEED_BAND_MAX = 1 << 20;
@@ -5857,14 +5857,14 @@ extern "C" void pmx_seed_index_free(pmx_seed_index_t *ix)
 
 extern "C" int64_t pmx_seed_index_count(const pmx_seed_index_t *ix) { return ix ? ix->n : -1; }
 
-// The index of R behind the entries' checks; table: the 256 groups of a letters index of `bits` bits per letter, NULL: the DNA index;
-// tr_strands >= 0: a translated index of those strands under `code`, one entry slot per byte and strand
-static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int32_t k, int bits, const uint8_t *table, void *stream, int tr_strands = -1,
+// The index of R behind the entries' checks; table: the 256 groups of a letters or translated index of `bits` bits per letter, NULL:
+// the DNA index; translated: tr_strands is the strand mode held, under `code`, one entry slot per byte and strand
+static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int kind, int32_t k, int bits, const uint8_t *table, void *stream, int tr_strands = -2,
                                           const uint8_t *code = nullptr)
 {
     pmx_seed_index *ix = new (std::nothrow) pmx_seed_index();
     if (!ix) { set_err("out of memory"); return nullptr; }
-    ix->R = R; ix->k = k; ix->dev = R->dev; ix->bits = bits; ix->letters = table != nullptr && tr_strands < 0; ix->tr_strands = tr_strands;
+    ix->R = R; ix->k = k; ix->dev = R->dev; ix->bits = bits; ix->kind = kind; ix->strands = tr_strands;
     if (table) memcpy(ix->table, table, 256);
     const int bbits = std::min(bits * k, PMX_SEED_BUCKET_BITS);
     ix->shift = bits * k - bbits; ix->nb = (int64_t)1 << bbits;
@@ -5888,7 +5888,7 @@ static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int32_t k, int 
     if (e == hipSuccess && table) e = hipMalloc((void **)&ix->d_table, 256);
     if (e == hipSuccess && table) e = hipMemcpyAsync(ix->d_table, ix->table, 256, hipMemcpyHostToDevice, st);
     int rc = 0;
-    if (e == hipSuccess && tr_strands >= 0) {
+    if (e == hipSuccess && kind == PMX_SEED_KIND_TRANSLATED) {
         PmxCodeTable ct;
         if (code) memcpy(ct.v, code, 64); else pmx_genetic_code_host(ct.v);
         rc = pmx_launch_seed_index_translated(R->d_buf, R->d_off, R->count, R->bytes, k, bits, ix->d_table, ct, nstr, tr_strands == PMX_STRAND_REVERSE ? 1 : 0,
@@ -5918,7 +5918,7 @@ extern "C" pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t
                 (long long)R->bytes, (long long)R->count);
         return nullptr;
     }
-    return seed_index_build(R, k, 2, nullptr, stream);
+    return seed_index_build(R, PMX_SEED_KIND_DNA, k, 2, nullptr, stream);
 }
 
 // The built-in reduced alphabets: one string of letters per group
@@ -5967,7 +5967,7 @@ extern "C" pmx_seed_index_t *pmx_seed_index_build_letters(const pmx_seqset_t *R,
                 (long long)R->bytes, (long long)R->count);
         return nullptr;
     }
-    return seed_index_build(R, k, bits, table, stream);
+    return seed_index_build(R, PMX_SEED_KIND_LETTERS, k, bits, table, stream);
 }
 
 extern "C" pmx_seed_index_t *pmx_seed_index_build_translated(const pmx_seqset_t *R, int32_t k, const uint8_t table[256], const uint8_t *code,
@@ -5981,10 +5981,10 @@ extern "C" pmx_seed_index_t *pmx_seed_index_build_translated(const pmx_seqset_t 
                 (long long)R->bytes, (long long)R->count);
         return nullptr;
     }
-    return seed_index_build(R, k, bits, table, stream, strand_mode, code);
+    return seed_index_build(R, PMX_SEED_KIND_TRANSLATED, k, bits, table, stream, strand_mode, code);
 }
 
-extern "C" int32_t pmx_seed_index_strands(const pmx_seed_index_t *ix) { return !ix ? -1 : ix->tr_strands >= 0 ? ix->tr_strands : -2; }
+extern "C" int32_t pmx_seed_index_strands(const pmx_seed_index_t *ix) { return ix ? ix->strands : -1; }
 
 extern "C" int pmx_seed_index_entries_device(const pmx_seed_index_t *ix, int64_t first, int64_t count, uint64_t *d_kmer, int64_t *d_seq,
                                              int32_t *d_pos, void *stream)
@@ -6012,32 +6012,78 @@ static int seed_mode_orients(int query_mode)
     return query_mode == PMX_FRAMES_ALL || query_mode == PMX_SEED_CODONS_BOTH ? 6 : 3;
 }
 
-// How an entry reads its rows.  DNA entries: orients = the strands, first = the first one.  Letters entries: orients =
-// the orientation slots per row, first = the first one's frame (< 0: the rows are letters), codon = the codon modes.
-struct SeedMode {
-    bool letters = false, codon = false; int orients = 1, first = 0; PmxCodeTable code;
-    bool ref = false;                      // a translated index: the rows are proteins, codon = PMX_SEED_REF_CODONS
-};
-#define PMX_SEED_MODE_DNA INT32_MIN                     // query_mode of the DNA entries inside this file
-#define PMX_SEED_MODE_REF (INT32_MIN + 2)               // ... of the translated-reference entries: + PMX_SEED_REF_FRAMES / _CODONS, + 2: a bad ref_mode
-static bool seed_mode_ref(int query_mode) { return query_mode >= PMX_SEED_MODE_REF && query_mode <= PMX_SEED_MODE_REF + 2; }
-
-// What the seeding entries refuse about their arguments; lens_known false: the host entry before it has looked at the lengths
-// (max_qlen and the budget rule are checked in its second call).  query_mode: PMX_SEED_MODE_DNA or the letters entry's mode.
-static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t *o,
-                      int64_t capacity, bool lens_known = true, int query_mode = PMX_SEED_MODE_DNA)
+// The one description of a seeding run (pmx_common.h: PmxSeedPlan; host arithmetic only, pinned by tests/test_seed_plans.py).  kind: the
+// entry's PmxSeedKind, with its own mode argument behind seed_check -- o.strand (DNA), query_mode (letters: `code` replaces the standard
+// genetic code), ref_mode (translated); k, bits, ref_count: the index's; budget: the match buffer in bytes.
+// 0 planned; 1 one row's worst case does not fit the budget: the plan is filled up to the slice, which then has no size.
+static int seed_plan(int kind, int mode, const uint8_t *code, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t &o, int k, int bits, int64_t ref_count,
+                     int64_t budget, PmxSeedPlan *out)
 {
-    const bool dna = query_mode == PMX_SEED_MODE_DNA;
+    PmxSeedPlan p = {};
+    p.kind = kind; p.max_qlen = max_qlen; p.k = k; p.bits = bits; p.ref_count = ref_count;
+    p.band = o.band; p.min_seeds = o.min_seeds; p.pad = o.pad; p.max_occ = o.max_occ;
+    if (code) memcpy(p.code.v, code, 64); else pmx_genetic_code_host(p.code.v);
+    p.orients = p.segs = 1;
+    if (kind == PMX_SEED_KIND_DNA) {
+        p.geom = PMX_SEED_GEOM_DNA;
+        p.orients = p.segs = o.strand == PMX_STRAND_BOTH ? 2 : 1; p.first = o.strand == PMX_STRAND_REVERSE ? 1 : 0;
+    } else if (kind == PMX_SEED_KIND_LETTERS) {
+        const bool codons = mode >= PMX_SEED_CODONS_FORWARD;
+        p.geom = codons ? PMX_SEED_GEOM_CODONS : PMX_SEED_GEOM_FRAMES;
+        p.rows_translated = mode != PMX_SEED_QUERY_LETTERS;
+        p.orients = seed_mode_orients(mode); p.segs = codons ? p.orients / 3 : p.orients;      // a codon segment is a strand: three frames wide
+        p.first = !p.rows_translated ? 0 : mode <= 5 ? mode : mode == PMX_FRAMES_REVERSE || mode == PMX_SEED_CODONS_REVERSE ? 3 : 0;
+    } else
+        p.geom = mode == PMX_SEED_REF_CODONS ? PMX_SEED_GEOM_REF_CODONS : PMX_SEED_GEOM_REF_FRAMES;       // the rows are proteins: one segment each
+    p.row_slots = (int64_t)p.orients * max_qlen; p.seg_slots = p.row_slots / p.segs;
+    p.pos_bytes = kind == PMX_SEED_KIND_DNA ? PMX_SEED_POS_BYTES : PMX_SEED_POS_BYTES_LETTERS;
+    p.key_bits = 33;                                     // the diagonal and the bits of an id: a reference, times the six frames of a translated index
+    while (p.key_bits < 64 && ((int64_t)1 << (p.key_bits - 32)) < (kind == PMX_SEED_KIND_TRANSLATED ? 6 : 1) * ref_count) ++p.key_bits;
+    *out = p;
+    if ((double)p.row_slots * (double)o.max_occ * (double)PMX_SEED_MATCH_BYTES > (double)budget) return 1;
+    int64_t slice = std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / (p.row_slots * p.pos_bytes));
+    if (o.slice_rows > 0) slice = std::min(slice, o.slice_rows);
+    slice = std::min(slice, nq);
+    // the match buffer: the budget, or the slice's worst case when that is smaller (positions fit 32 bits)
+    const double worst = (double)slice * (double)p.row_slots * (double)o.max_occ;
+    p.slice_rows = slice; p.positions = slice * p.row_slots; p.slots = slice * p.orients;
+    p.cap_m = (int64_t)std::min<double>(std::min<double>((double)(budget / PMX_SEED_MATCH_BYTES), worst), 2147483646.0);
+    *out = p;
+    return 0;
+}
+
+/* Test hook (include/parasail_amd.h): the plan with the budget as an argument; no device needed. */
+extern "C" int pmx_seed_plan_probe(int kind, int mode, long long nq, int max_qlen, int max_occ, long long slice_rows, long long budget,
+                                   long long ref_count, long long *out)
+{
+    if (!out || kind < PMX_SEED_KIND_DNA || kind > PMX_SEED_KIND_TRANSLATED || nq < 1 || max_qlen < 1 || max_occ < 1 || slice_rows < 0 || ref_count < 0) return -1;
+    pmx_seed_opts_t o = {};
+    o.strand = kind == PMX_SEED_KIND_DNA ? mode : 0; o.max_occ = max_occ; o.slice_rows = slice_rows;
+    PmxSeedPlan p;
+    const int rc = seed_plan(kind, mode, nullptr, nq, max_qlen, o, 0, 0, ref_count, budget > 0 ? std::min<int64_t>(budget, (int64_t)1 << 34) : (int64_t)PMX_PAIRS_CHUNK_BYTES, &p);
+    const bool oriented = kind == PMX_SEED_KIND_DNA || p.rows_translated;
+    const long long v[11] = {p.orients, oriented ? p.first : -1, p.segs, p.seg_slots, p.row_slots, p.pos_bytes, p.slice_rows, p.cap_m, p.positions, p.slots,
+                             p.key_bits};
+    for (int i = 0; i < 11; ++i) out[i] = rc ? 0 : v[i];
+    return rc;
+}
+
+// What the seeding entries refuse about their arguments, and behind that the run's plan.  kind / mode: the entry's (seed_plan); lens_known
+// false: the host entry before it has looked at the lengths (max_qlen and the budget rule are checked in its second call).
+static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int kind, int mode, const uint8_t *code, int64_t q_first, int64_t nq, int32_t max_qlen,
+                      const pmx_seed_opts_t *o, int64_t capacity, bool lens_known, PmxSeedPlan *plan)
+{
+    const bool dna = kind == PMX_SEED_KIND_DNA, tref = kind == PMX_SEED_KIND_TRANSLATED, letters = kind == PMX_SEED_KIND_LETTERS;
     if (!lens_known) max_qlen = 1;
     if (!Q) { set_err("null sequence set"); return -1; }
     if (!ix) { set_err("null seed index"); return -1; }
     if (!o) { set_err("null opts"); return -1; }
-    const bool tref = seed_mode_ref(query_mode);
-    if (ix->tr_strands >= 0 && !tref) {
-        set_err("a translated index (pmx_seed_index_build_translated) is seeded by pmx_seed_pairs_translated_ref[_device]"); return -1;
+    if (ix->kind != kind) {
+        if (ix->kind == PMX_SEED_KIND_TRANSLATED) set_err("a translated index (pmx_seed_index_build_translated) is seeded by pmx_seed_pairs_translated_ref[_device]");
+        else if (ix->kind == PMX_SEED_KIND_LETTERS) set_err("a letters index (pmx_seed_index_build_letters) is seeded by pmx_seed_pairs_letters[_device]");
+        else set_err("a DNA index (pmx_seed_index_build) is seeded by pmx_seed_pairs[_device]");
+        return -1;
     }
-    if (ix->letters && (dna || tref)) { set_err("a letters index (pmx_seed_index_build_letters) is seeded by pmx_seed_pairs_letters[_device]"); return -1; }
-    if (!dna && !ix->letters && ix->tr_strands < 0) { set_err("a DNA index (pmx_seed_index_build) is seeded by pmx_seed_pairs[_device]"); return -1; }
     if (q_first < 0 || nq < 0) { set_err("negative q_first or nq"); return -1; }
     if (capacity < 0) { set_err("negative capacity"); return -1; }
     if (o->max_hits < 0) { set_err("max_hits must not be negative"); return -1; }
@@ -6049,11 +6095,11 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_f
     if (max_qlen < 1) { set_err("max_qlen must be positive"); return -1; }
     if (dna && (o->strand < PMX_STRAND_FORWARD || o->strand > PMX_STRAND_BOTH)) { set_err("strand mode %d is outside 0 .. 2", (int)o->strand); return -1; }
     if (tref && o->strand != 0) { set_err("opts->strand %d must be 0 with a translated index: it holds the strands it was built with", (int)o->strand); return -1; }
-    if (tref && query_mode == PMX_SEED_MODE_REF + 2) { set_err("ref_mode is neither PMX_SEED_REF_FRAMES (0) nor PMX_SEED_REF_CODONS (1)"); return -1; }
-    if (!dna && !tref && o->strand != 0) { set_err("opts->strand %d must be 0 with a letters index: query_mode chooses the orientations", (int)o->strand); return -1; }
-    if (!dna && !tref && !seed_mode_valid(query_mode)) {
+    if (tref && mode != PMX_SEED_REF_FRAMES && mode != PMX_SEED_REF_CODONS) { set_err("ref_mode is neither PMX_SEED_REF_FRAMES (0) nor PMX_SEED_REF_CODONS (1)"); return -1; }
+    if (letters && o->strand != 0) { set_err("opts->strand %d must be 0 with a letters index: query_mode chooses the orientations", (int)o->strand); return -1; }
+    if (letters && !seed_mode_valid(mode)) {
         set_err("query mode %d is none of PMX_SEED_QUERY_LETTERS (-1), a frame 0 .. 5, PMX_FRAMES_FORWARD / _REVERSE / _ALL (6 .. 8), "
-                "PMX_SEED_CODONS_FORWARD / _REVERSE / _BOTH (9 .. 11)", query_mode);
+                "PMX_SEED_CODONS_FORWARD / _REVERSE / _BOTH (9 .. 11)", mode);
         return -1;
     }
     if (o->min_seeds < 1) { set_err("min_seeds %d is below 1", (int)o->min_seeds); return -1; }
@@ -6061,41 +6107,13 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_f
     if (o->pad < 0 || o->pad > PMX_SEED_BAND_MAX) { set_err("pad %d is outside 0 .. 2^20", (int)o->pad); return -1; }
     if (o->max_occ < 1 || o->max_occ > 65535) { set_err("max_occ %d is outside 1 .. 65535", (int)o->max_occ); return -1; }
     if (o->reserved != 0) { set_err("reserved must be 0"); return -1; }
-    const int64_t strands = dna ? (o->strand == PMX_STRAND_BOTH ? 2 : 1) : tref ? 1 : seed_mode_orients(query_mode);
-    const double worst = (double)max_qlen * (double)strands * (double)o->max_occ * (double)PMX_SEED_MATCH_BYTES;
-    if (worst > (double)seed_match_budget()) {
+    if (seed_plan(kind, mode, code, nq, max_qlen, *o, ix->k, ix->bits, ix->R->count, seed_match_budget(), plan)) {
         set_err("one row's worst case of %d positions x %d %s x max_occ %d x %d bytes per match does not fit the match buffer of %lld bytes: "
-                "lower max_occ or split the queries", (int)max_qlen, (int)strands, dna ? "strand(s)" : "orientation(s)", (int)o->max_occ,
+                "lower max_occ or split the queries", (int)max_qlen, plan->orients, dna ? "strand(s)" : "orientation(s)", (int)o->max_occ,
                 PMX_SEED_MATCH_BYTES, (long long)seed_match_budget());
         return -1;
     }
     return 0;
-}
-
-static SeedMode seed_mode_dna(const pmx_seed_opts_t *o)
-{
-    SeedMode m; m.orients = o->strand == PMX_STRAND_BOTH ? 2 : 1; m.first = o->strand == PMX_STRAND_REVERSE ? 1 : 0;
-    return m;
-}
-static SeedMode seed_mode_letters(int query_mode, const uint8_t *code)
-{
-    SeedMode m; m.letters = true; m.orients = seed_mode_orients(query_mode);
-    m.codon = query_mode >= PMX_SEED_CODONS_FORWARD;
-    m.first = query_mode == PMX_SEED_QUERY_LETTERS ? -1 : query_mode <= 5 ? query_mode
-            : query_mode == PMX_FRAMES_REVERSE || query_mode == PMX_SEED_CODONS_REVERSE ? 3 : 0;
-    if (code) memcpy(m.code.v, code, 64); else pmx_genetic_code_host(m.code.v);
-    return m;
-}
-
-static SeedMode seed_mode_ref_of(int query_mode)
-{
-    SeedMode m; m.letters = m.ref = true; m.first = -1; m.codon = query_mode == PMX_SEED_MODE_REF + PMX_SEED_REF_CODONS;
-    pmx_genetic_code_host(m.code.v);       // (the code stage of rows that are letters reads no codon)
-    return m;
-}
-static SeedMode seed_mode_of(int query_mode, const pmx_seed_opts_t *o, const uint8_t *code)
-{
-    return query_mode == PMX_SEED_MODE_DNA ? seed_mode_dna(o) : seed_mode_ref(query_mode) ? seed_mode_ref_of(query_mode) : seed_mode_letters(query_mode, code);
 }
 
 static int seed_device_check(const pmx_seqset *Q, const pmx_seed_index *ix)
@@ -6107,70 +6125,46 @@ static int seed_device_check(const pmx_seqset *Q, const pmx_seed_index *ix)
     return 0;
 }
 
-// nq > 0 rows behind the checks.  Synchronises `st` once per slice: the cut is read back.
-static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t *o,
-                    pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off,
-                    int64_t *d_counts, hipStream_t st, const SeedMode &mode)
+// nq > 0 rows behind the checks, by their plan.  Synchronises `st` once per slice: the cut is read back.
+static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_first, int64_t nq, const PmxSeedPlan &p, const PmxSeedOut &out, hipStream_t st)
 {
-    HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), st));
-    if (ix->n == 0) { HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st)); return 0; }
-    HIP_OR_RET(hipMemsetAsync(d_row_off, 0, sizeof(int64_t), st));
-    const int strands = mode.orients, strand0 = mode.first;
-    const int64_t per_row = (int64_t)strands * max_qlen;
-    int64_t slice = std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / (per_row * (mode.letters ? PMX_SEED_POS_BYTES_LETTERS : PMX_SEED_POS_BYTES)));
-    if (o->slice_rows > 0) slice = std::min(slice, o->slice_rows);
-    slice = std::min(slice, nq);
-    // the match buffer: the budget, or the slice's worst case when that is smaller (positions fit 32 bits)
-    const double worst = (double)slice * (double)per_row * (double)o->max_occ;
-    const int64_t cap_m = (int64_t)std::min<double>(std::min<double>((double)(seed_match_budget() / PMX_SEED_MATCH_BYTES), worst), 2147483646.0);
-    const int64_t positions = slice * per_row, slots = slice * strands;
-    const size_t temp_bytes = pmx_seed_temp_bytes(positions, cap_m, slots);
-    uint32_t *lo = nullptr, *cnt = nullptr, *head = nullptr, *flag = nullptr; int64_t *moff = nullptr, *cut = nullptr;
-    uint64_t *ka = nullptr, *kb = nullptr; unsigned char *temp = nullptr; uint8_t *codes = nullptr;
+    HIP_OR_RET(hipMemsetAsync(out.counts, 0, 2 * sizeof(int64_t), st));
+    if (ix->n == 0) { HIP_OR_RET(hipMemsetAsync(out.row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st)); return 0; }
+    HIP_OR_RET(hipMemsetAsync(out.row_off, 0, sizeof(int64_t), st));
+    PmxSeedSlice s = {};
+    s.temp_bytes = pmx_seed_temp_bytes(p.positions, p.cap_m, p.slots);
     if (scratch_carve(SCR_SEED, [&](Carver &c) {
-            lo = c.take<uint32_t>((size_t)positions); cnt = c.take<uint32_t>((size_t)positions + 1); moff = c.take<int64_t>((size_t)positions + 1);
-            ka = c.take<uint64_t>((size_t)cap_m); kb = c.take<uint64_t>((size_t)cap_m);
-            head = c.take<uint32_t>((size_t)cap_m); flag = c.take<uint32_t>((size_t)cap_m + 1);
-            cut = c.take<int64_t>(2); temp = c.take<unsigned char>(temp_bytes);
-            if (mode.letters) codes = c.take<uint8_t>((size_t)positions);
+            s.lo = c.take<uint32_t>((size_t)p.positions); s.cnt = c.take<uint32_t>((size_t)p.positions + 1); s.moff = c.take<int64_t>((size_t)p.positions + 1);
+            s.keys_a = c.take<uint64_t>((size_t)p.cap_m); s.keys_b = c.take<uint64_t>((size_t)p.cap_m);
+            s.head = c.take<uint32_t>((size_t)p.cap_m); s.flag = c.take<uint32_t>((size_t)p.cap_m + 1);
+            s.cut = c.take<int64_t>(2); s.temp = c.take<unsigned char>(s.temp_bytes);
+            if (p.kind != PMX_SEED_KIND_DNA) s.codes = c.take<uint8_t>((size_t)p.positions);
         })) return -1;
-    int key_bits = 33;                                   // the diagonal and the bits of a reference index
-    while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < (mode.ref ? 6 : 1) * ix->R->count) ++key_bits;
+    const PmxSeedSource src = {ix->keys, ix->vals, ix->bucket, ix->shift, ix->d_table, ix->R->d_off, Q->d_buf, Q->d_off, Q->bytes};
     for (int64_t row = 0; row < nq;) {
-        const int64_t rows = std::min(slice, nq - row);
-        int rc = mode.letters
-            ? pmx_launch_seed_count_letters(Q->d_buf, Q->d_off, Q->bytes, q_first + row, rows, strands, strand0, max_qlen, ix->k, ix->bits, ix->d_table,
-                                            mode.code, codes, ix->keys, ix->bucket, ix->shift, o->max_occ, lo, cnt, moff, cap_m, cut, temp, temp_bytes, st)
-            : pmx_launch_seed_count(Q->d_buf, Q->d_off, Q->bytes, q_first + row, rows, strands, strand0, max_qlen, ix->k, ix->keys, ix->bucket,
-                                    ix->shift, o->max_occ, lo, cnt, moff, cap_m, cut, temp, temp_bytes, st);
+        const int64_t rows = std::min<int64_t>(p.slice_rows, nq - row);
+        int rc = pmx_launch_seed_count(p, s, src, q_first + row, rows, st);
         if (rc) { set_err("seed count pass failed (%d)", rc); return rc; }
         int64_t h[2] = {0, 0};
-        HIP_OR_RET(hipMemcpyAsync(h, cut, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_OR_RET(hipMemcpyAsync(h, s.cut, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_OR_RET(hipStreamSynchronize(st));
-        if (h[0] < 1 || h[0] > rows || h[1] < 0 || h[1] > cap_m) { set_err("seed cut of rows %lld .. is inconsistent", (long long)(q_first + row)); return -1; }
-        rc = mode.ref
-            ? pmx_launch_seed_cluster_translated(q_first + row, h[0], mode.codon, max_qlen, ix->R->count, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb,
-                                                 head, flag, o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand,
-                                                 d_hit_seeds, d_row_off + row, d_counts, temp, temp_bytes, st)
-            : mode.letters
-            ? pmx_launch_seed_cluster_letters(q_first + row, h[0], strands, strand0, mode.codon, max_qlen, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb,
-                                              head, flag, o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand,
-                                              d_hit_seeds, d_row_off + row, d_counts, temp, temp_bytes, st)
-            : pmx_launch_seed_cluster(q_first + row, h[0], strands, strand0, max_qlen, h[1], key_bits, lo, cnt, moff, ix->vals, ka, kb, head, flag,
-                                      o->band, o->min_seeds, o->pad, Q->d_off, ix->R->d_off, capacity, d_hit_pairs, d_hit_strand, d_hit_seeds,
-                                      d_row_off + row, d_counts, temp, temp_bytes, st);
+        if (h[0] < 1 || h[0] > rows || h[1] < 0 || h[1] > p.cap_m) { set_err("seed cut of rows %lld .. is inconsistent", (long long)(q_first + row)); return -1; }
+        PmxSeedOut part = out;
+        part.row_off += row;
+        rc = pmx_launch_seed_cluster(p, s, part, src, q_first + row, h[0], h[1], st);
         if (rc) { set_err("seed cluster pass failed (%d)", rc); return rc; }
         row += h[0];
     }
     return 0;
 }
 
-// The device entries; query_mode: PMX_SEED_MODE_DNA or the letters entry's mode
+// The device entries; kind / mode / code: the public entry's own (seed_plan)
 static int seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
-                             const pmx_seed_opts_t *opts, int query_mode, const uint8_t *code, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand,
+                             const pmx_seed_opts_t *opts, int kind, int mode, const uint8_t *code, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand,
                              pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
 {
-    if (seed_check(Q, ix, q_first, nq, max_qlen, opts, capacity, true, query_mode)) return -1;
+    PmxSeedPlan plan;
+    if (seed_check(Q, ix, kind, mode, code, q_first, nq, max_qlen, opts, capacity, true, &plan)) return -1;
     if (capacity > 0 && (!d_hit_pairs || !d_hit_strand)) { set_err("null hit pairs or strand bytes with capacity > 0"); return -1; }
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
@@ -6182,15 +6176,15 @@ static int seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, 
     if (seed_device_check(Q, ix)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    return seed_run(Q, ix, q_first, nq, max_qlen, opts, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts, (hipStream_t)stream,
-                    seed_mode_of(query_mode, opts, code));
+    const PmxSeedOut out = {d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts};
+    return seed_run(Q, ix, q_first, nq, plan, out, (hipStream_t)stream);
 }
 
 extern "C" int pmx_seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
                                      const pmx_seed_opts_t *opts, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds,
                                      int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
 {
-    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, PMX_SEED_MODE_DNA, nullptr, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off,
+    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, PMX_SEED_KIND_DNA, 0, nullptr, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off,
                              d_counts, stream);
 }
 
@@ -6199,20 +6193,19 @@ extern "C" int pmx_seed_pairs_letters_device(const pmx_seqset_t *Q, const pmx_se
                                              pmx_pair_t *d_hit_pairs, uint8_t *d_hit_byte, pmx_seed_hit_t *d_hit_seeds, int64_t capacity,
                                              int64_t *d_row_off, int64_t *d_counts, void *stream)
 {
-    if (query_mode == PMX_SEED_MODE_DNA || seed_mode_ref(query_mode)) query_mode = PMX_SEED_MODE_DNA + 1;      // (an invalid mode like any other)
-    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, query_mode, code, d_hit_pairs, d_hit_byte, d_hit_seeds, capacity, d_row_off, d_counts,
-                             stream);
+    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, PMX_SEED_KIND_LETTERS, query_mode, code, d_hit_pairs, d_hit_byte, d_hit_seeds, capacity,
+                             d_row_off, d_counts, stream);
 }
 
 extern "C" void pmx_seed_hits_free(pmx_seed_hits_t *hits) { free(hits); }
 
 static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
-                           int query_mode, const uint8_t *code, pmx_seed_hits_t **result)
+                           int kind, int mode, const uint8_t *code, pmx_seed_hits_t **result)
 {
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
-    if (seed_check(Q, ix, q_first, nq, 0, opts, 0, false, query_mode)) return -1;
-    const SeedMode mode = seed_mode_of(query_mode, opts, code);
+    PmxSeedPlan plan;                                        // of the ask first; of the run once the longest row is known
+    if (seed_check(Q, ix, kind, mode, code, q_first, nq, 0, opts, 0, false, &plan)) return -1;
     // the result: one block -- header, row offsets, descriptors, seed records, strand bytes
     auto block = [&](int64_t stored, int64_t passing) -> pmx_seed_hits_t * {
         Carver c; c.align = 16;
@@ -6251,9 +6244,9 @@ static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, in
         HIP_OR_RET(hipStreamSynchronize(st));
         mq = h_m[0];
     }
-    if (mode.letters && mode.first >= 0) mq /= 3;            // translated rows: the letters of the longest translation
+    if (plan.rows_translated) mq /= 3;                       // the letters of the longest translation
     if (mq < 1) mq = 1;
-    if (seed_check(Q, ix, q_first, nq, mq, opts, 0, true, query_mode)) return -1;
+    if (seed_check(Q, ix, kind, mode, code, q_first, nq, mq, opts, 0, true, &plan)) return -1;
     int64_t *d_off = nullptr, *d_cnt = nullptr; pmx_pair_t *d_pairs = nullptr; pmx_seed_hit_t *d_seeds = nullptr; uint8_t *d_strand = nullptr;
     auto carve = [&](int64_t stored) {
         return scratch_carve(SCR_SEEDHIT, [&](Carver &c) {
@@ -6267,14 +6260,14 @@ static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, in
     int64_t room = 2 * nq + 16;
     if (opts->max_hits > 0) room = std::min(room, opts->max_hits);
     if (carve(room)) return -1;
-    int rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, room, d_off, d_cnt, st, mode);
+    int rc = seed_run(Q, ix, q_first, nq, plan, PmxSeedOut{d_pairs, d_strand, d_seeds, room, d_off, d_cnt}, st);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     HIP_OR_RET(hipMemcpyAsync(h, d_cnt, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_OR_RET(hipStreamSynchronize(st));
     const int64_t passing = h[0], stored = opts->max_hits > 0 ? std::min(passing, opts->max_hits) : passing;
     if (stored > room) {
         if (carve(stored)) return -1;
-        rc = seed_run(Q, ix, q_first, nq, mq, opts, d_pairs, d_strand, d_seeds, stored, d_off, d_cnt, st, mode);
+        rc = seed_run(Q, ix, q_first, nq, plan, PmxSeedOut{d_pairs, d_strand, d_seeds, stored, d_off, d_cnt}, st);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipStreamSynchronize(st));
     }
@@ -6292,27 +6285,25 @@ static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, in
 extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
                               pmx_seed_hits_t **result)
 {
-    return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_MODE_DNA, nullptr, result);
+    return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_KIND_DNA, 0, nullptr, result);
 }
 
 extern "C" int pmx_seed_pairs_letters(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
                                       int query_mode, const uint8_t *code, pmx_seed_hits_t **result)
 {
-    if (query_mode == PMX_SEED_MODE_DNA || seed_mode_ref(query_mode)) query_mode = PMX_SEED_MODE_DNA + 1;
-    return seed_pairs_host(Q, ix, q_first, nq, opts, query_mode, code, result);
+    return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_KIND_LETTERS, query_mode, code, result);
 }
 
 extern "C" int pmx_seed_pairs_translated_ref_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
                                                     const pmx_seed_opts_t *opts, int ref_mode, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_byte,
                                                     pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
 {
-    const int mode = PMX_SEED_MODE_REF + (ref_mode == PMX_SEED_REF_FRAMES || ref_mode == PMX_SEED_REF_CODONS ? ref_mode : 2);
-    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, mode, nullptr, d_hit_pairs, d_hit_byte, d_hit_seeds, capacity, d_row_off, d_counts, stream);
+    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, PMX_SEED_KIND_TRANSLATED, ref_mode, nullptr, d_hit_pairs, d_hit_byte, d_hit_seeds, capacity,
+                             d_row_off, d_counts, stream);
 }
 
 extern "C" int pmx_seed_pairs_translated_ref(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
                                              int ref_mode, pmx_seed_hits_t **result)
 {
-    const int mode = PMX_SEED_MODE_REF + (ref_mode == PMX_SEED_REF_FRAMES || ref_mode == PMX_SEED_REF_CODONS ? ref_mode : 2);
-    return seed_pairs_host(Q, ix, q_first, nq, opts, mode, nullptr, result);
+    return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_KIND_TRANSLATED, ref_mode, nullptr, result);
 }

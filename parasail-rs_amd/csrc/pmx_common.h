@@ -444,13 +444,12 @@ int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, 
                          const pmx_stats_t *st_stats, const int32_t *st_held, const int64_t *st_passing, const int64_t *row_off, long long capacity,
                          pmx_pair_t *hit_pairs, int64_t *hit_index, pmx_record_t *hit_recs, pmx_stats_t *hit_stats, int64_t *row_passing,
                          int64_t *counts, hipStream_t stream, uint8_t *hit_strand = nullptr, int marked = 0 /* as in append_hits */);
-// K-mer seeding (pmx_seed.hip; semantics: include/parasail_amd.h).  index: one entry per byte of the set's buffer into
-// keys_in / vals_in, sorted into keys_out / vals_out (the k-mers in front, *n_valid of them; val = seq << 32 | pos); buckets: the table
-// of nb + 1 first-entry numbers on the keys' top bits (key >> shift).  count: lookups of the slice's rows, the scan of their matches
-// into moff and cut[0 .. 1] = the rows that fit cap_matches / their matches.  cluster: those rows' matches emitted, sorted per (row,
-// strand) and turned into candidates behind counts[0], row offsets and counts.
+// K-mer seeding (pmx_seed.hip; semantics: include/parasail_amd.h, DESIGN 2.5p .. 2.5r).  index: one entry per byte of the set's buffer
+// into keys_in / vals_in, sorted into keys_out / vals_out (the k-mers in front, *n_valid of them; val = seq << 32 | pos); buckets: the
+// table of nb + 1 first-entry numbers on the keys' top bits (key >> shift).
 #define PMX_SEED_MATCH_BYTES 24        // per match: two sort buffers of 8-byte keys, the head index, the candidate flag / position
-#define PMX_SEED_POS_BYTES   16        // per (row, strand, position): first entry, occurrences, match offset
+#define PMX_SEED_POS_BYTES   16        // per position slot: first entry, occurrences, match offset
+#define PMX_SEED_POS_BYTES_LETTERS (PMX_SEED_POS_BYTES + 1)        // ... and the code byte of a letters or translated index
 size_t pmx_seed_index_sort_bytes(long long bytes, int k);
 int pmx_launch_seed_index(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k,
                           uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out, void *temp, size_t temp_bytes,
@@ -458,48 +457,59 @@ int pmx_launch_seed_index(const uint8_t *buf, const int64_t *off, long long coun
 int pmx_launch_seed_buckets(const uint64_t *keys, long long n, int shift, long long nb, uint32_t *bucket, hipStream_t stream);
 int pmx_launch_seed_entries(const uint64_t *keys, const uint64_t *vals, long long first, long long count, uint64_t *kmer, int64_t *seq,
                             int32_t *pos, hipStream_t stream);
-size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots);
-int pmx_launch_seed_count(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int strands, int strand0,
-                          int max_qlen, int k, const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
-                          uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
-                          hipStream_t stream);
-int pmx_launch_seed_cluster(long long row0, long long rows, int strands, int strand0, int max_qlen, long long m, int key_bits,
-                            const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
-                            uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
-                            const int64_t *qoff, const int64_t *roff, long long capacity,
-                            pmx_pair_t *hit_pairs, uint8_t *hit_strand, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
-                            void *temp, size_t temp_bytes, hipStream_t stream);
-// The same over a letters index: `bits` bits per letter, table: 256 group bytes on the device.  orients: orientation
-// slots per row, the first one's frame `first` (< 0: the rows are letters of the index's alphabet); codes: one byte per position slot;
-// codon: segments of three frames and nucleotide diagonals (orients 3 or 6, first 0 or 3).
-#define PMX_SEED_POS_BYTES_LETTERS (PMX_SEED_POS_BYTES + 1)
+// A letters index: `bits` bits per letter, table: 256 group bytes on the device.
 size_t pmx_seed_index_sort_bytes_letters(long long bytes, int k, int bits);
 int pmx_launch_seed_index_letters(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int bits, const uint8_t *table,
                                   uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out, void *temp, size_t temp_bytes,
                                   unsigned long long *n_valid, hipStream_t stream);
-int pmx_launch_seed_count_letters(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int orients, int first,
-                                  int max_qlen, int k, int bits, const uint8_t *table, const PmxCodeTable &code, uint8_t *codes,
-                                  const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
-                                  uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
-                                  hipStream_t stream);
-int pmx_launch_seed_cluster_letters(long long row0, long long rows, int orients, int first, bool codon, int max_qlen, long long m, int key_bits,
-                                    const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
-                                    uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
-                                    const int64_t *qoff, const int64_t *roff, long long capacity,
-                                    pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
-                                    void *temp, size_t temp_bytes, hipStream_t stream);
 // A translated index: the six-frame k-mers of a nucleotide set, nstr strands from strand0, nstr * bytes entry slots
-// (val = (strand * count + seq) << 32 | oriented position).  Seeding counts with pmx_launch_seed_count_letters (orients 1, first < 0:
-// the rows are proteins); cluster: the mode's id, diagonal and window, codon = PMX_SEED_REF_CODONS; count: the set's sequences.
+// (val = (strand * count + seq) << 32 | oriented position).
 int pmx_launch_seed_index_translated(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int bits, const uint8_t *table,
                                      const PmxCodeTable &code, int nstr, int strand0, uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out,
                                      uint64_t *vals_out, void *temp, size_t temp_bytes, unsigned long long *n_valid, hipStream_t stream);
-int pmx_launch_seed_cluster_translated(long long row0, long long rows, bool codon, int max_qlen, long long count, long long m, int key_bits,
-                                       const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
-                                       uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
-                                       const int64_t *qoff, const int64_t *roff, long long capacity,
-                                       pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
-                                       void *temp, size_t temp_bytes, hipStream_t stream);
+// A seeding run, described once (filled by seed_plan of pmx_api.hip, host arithmetic only; pinned by tests/test_seed_plans.py).
+// A row has `orients` orientations of max_qlen position slots each: the strands of a DNA query, the frames of a translated one, the row
+// itself.  The sort's segments -- what one candidate's matches share -- are `segs` per row of seg_slots position slots each, and the
+// geometry says how a match's id and diagonal and a cluster's window and byte are formed:
+//   DNA          segment (row, strand);         id = r;                d = j - i;          byte = strand
+//   FRAMES       segment (row, frame or row);   id = r;                d = j - i letters;  byte = frame (0: rows that are letters)
+//   CODONS       segment (row, strand), its three frames; id = r;      D = 3 j - (f % 3 + 3 i) nucleotides; byte = strand
+//   REF_FRAMES   segment row;  id = g * count + r, g = 3 s + x % 3;    d = x / 3 - i letters; byte 0 / 3, reserved = g
+//   REF_CODONS   segment row;  id = s * count + r;                     D = x - 3 i nucleotides; byte = s
+enum PmxSeedKind { PMX_SEED_KIND_DNA = 0, PMX_SEED_KIND_LETTERS = 1, PMX_SEED_KIND_TRANSLATED = 2 };
+enum PmxSeedGeom { PMX_SEED_GEOM_DNA = 0, PMX_SEED_GEOM_FRAMES = 1, PMX_SEED_GEOM_CODONS = 2, PMX_SEED_GEOM_REF_FRAMES = 3, PMX_SEED_GEOM_REF_CODONS = 4 };
+struct PmxSeedPlan {
+    int kind, geom;                        // PmxSeedKind of the index, PmxSeedGeom of the run
+    bool rows_translated;                  // the rows are nucleotides read as codons (orientation o: frame first + o), else as they stand
+    int orients, first;                    // orientations per row; the first one's strand (DNA) or frame (translated rows), else 0
+    int segs; long long seg_slots;         // segments per row, position slots per segment
+    long long row_slots; int pos_bytes;    // position slots per row (orients * max_qlen); scratch bytes per position slot
+    int max_qlen, k, bits, key_bits;       // bits per letter of the index; the sorted bits of a match key (the diagonal and the id)
+    long long ref_count;                   // the sequences of the indexed set
+    int band, min_seeds, pad, max_occ;
+    PmxCodeTable code;                     // read where rows_translated
+    long long slice_rows, cap_m, positions, slots;      // a slice: its rows at most, matches at most, position slots, rows x orients
+};
+// ... the index and the rows it reads (device) ...
+struct PmxSeedSource {
+    const uint64_t *keys, *vals; const uint32_t *bucket; int shift; const uint8_t *table;     // table: NULL of a DNA index
+    const int64_t *roff;                                                                      // offsets of the indexed set
+    const uint8_t *qbuf; const int64_t *qoff; long long q_bytes;
+};
+// ... a slice's scratch (lo, moff: positions, cnt: positions + 1; keys_a / keys_b / head: cap_m, flag: cap_m + 1; cut: 2; codes:
+// positions, NULL with a DNA index; temp: pmx_seed_temp_bytes(positions, cap_m, slots)) ...
+struct PmxSeedSlice {
+    uint32_t *lo, *cnt; int64_t *moff; uint64_t *keys_a, *keys_b; uint32_t *head, *flag; int64_t *cut; uint8_t *codes; void *temp; size_t temp_bytes;
+};
+// ... and where the candidates go: `capacity` entries each (seeds optional), row offsets, counts[0 .. 1].
+struct PmxSeedOut { pmx_pair_t *pairs; uint8_t *byte; pmx_seed_hit_t *seeds; long long capacity; int64_t *row_off, *counts; };
+size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots);
+// count: the lookups of rows row0 .. row0 + rows of Q (with a letters or translated index behind the code stage), the scan of their
+// matches into moff and cut[0 .. 1] = the rows that fit cap_m / their matches.  cluster: those rows' m matches emitted, sorted per
+// segment and turned into candidates behind counts[0], row offsets (out.row_off points at the entry of the slice's first row) and counts.
+int pmx_launch_seed_count(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedSource &src, long long row0, long long rows, hipStream_t stream);
+int pmx_launch_seed_cluster(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedOut &out, const PmxSeedSource &src, long long row0,
+                            long long rows, long long m, hipStream_t stream);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);

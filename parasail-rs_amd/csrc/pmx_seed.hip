@@ -12,6 +12,9 @@
 // segmented radix sort orders each (row, strand) segment by (r, d).  Clusters are then runs of the sorted keys: a head flag per match, a
 // max-scan that carries each head's index to its run, a candidate flag at each run's last match, a scan of those flags for the output
 // positions.  Every position comes from a scan over sorted data; the only atomic in this file counts the index's entries.
+//
+// The letters and translated indexes run the same pipeline: a run is described once by PmxSeedPlan (pmx_common.h),
+// the two launchers at the end of this file read it, and emit and hits are one template each over the plan's geometry.
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -30,8 +33,47 @@ __device__ __forceinline__ int pmx_seed_code(uint32_t b)
 // ---- index build ---------------------------------------------------------------------------------------------------------------------
 #define PMX_SEED_TILE 16        // positions per thread of the extraction: one rolling key over 16 + k - 1 bytes
 
-// keys[p] / vals[p] for every p < bytes; *n_valid += the k-mers found.  Offsets are read at indices 0 .. count only and a byte only
-// below `bytes`, whatever a wrapped set's offsets hold.
+// What the three extract kernels share.  The sequence a walk is in: region r of byte p0 -- -1 before the first sequence, count behind
+// the last one, else sequence r = [b, e) = [off[r], off[r + 1]).  Offsets are read at indices 0 .. count only and a byte only below
+// `bytes`, whatever a wrapped set's offsets hold.
+struct PmxSeedRegion { long long r, b, e; };
+__device__ __forceinline__ PmxSeedRegion pmx_seed_region(const int64_t *__restrict__ off, long long count, long long p0)
+{
+    long long lo = 0, hi = count + 1;
+    while (lo < hi) { const long long mid = (lo + hi) >> 1; if (off[mid] <= p0) lo = mid + 1; else hi = mid; }
+    PmxSeedRegion g;
+    g.r = lo - 1;
+    g.e = g.r < count ? off[g.r + 1] : INT64_MAX;
+    g.b = g.r >= 0 ? off[g.r] : 0;
+    return g;
+}
+// on to the region of byte x; true: a boundary was crossed (the caller's runs start over)
+__device__ __forceinline__ bool pmx_seed_region_advance(PmxSeedRegion &g, const int64_t *__restrict__ off, long long count, long long x)
+{
+    bool crossed = false;
+    while (x >= g.e && g.r < count) { ++g.r; g.b = g.e; g.e = g.r < count ? off[g.r + 1] : INT64_MAX; crossed = true; }
+    return crossed;
+}
+// byte x lies in a sequence of the set
+__device__ __forceinline__ bool pmx_seed_region_inside(const PmxSeedRegion &g, long long count, long long bytes, long long x)
+{
+    return g.r >= 0 && g.r < count && g.b >= 0 && g.b <= x && x < g.e && g.e <= bytes;
+}
+// entry slots [s0, s1) at which no k-mer starts; base: the slot number of keys[0]
+__device__ __forceinline__ void pmx_seed_no_kmers(uint64_t *__restrict__ keys, uint64_t *__restrict__ vals, long long base, long long s0, long long s1,
+                                                  uint64_t invalid)
+{
+    for (long long s = s0; s < s1; ++s) { keys[s] = invalid; vals[s] = (uint64_t)(base + s); }
+}
+// *n_valid += the block's k-mers, `total` zeroed and a barrier passed before: one add per block, the sum does not depend on the order of arrival
+__device__ __forceinline__ void pmx_seed_block_sum(unsigned &total, unsigned found, unsigned long long *n_valid)
+{
+    if (found) atomicAdd(&total, found);
+    __syncthreads();
+    if (threadIdx.x == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+}
+
+// keys[p] / vals[p] for every p < bytes; *n_valid += the k-mers found.  The key rolls in 2-bit arithmetic: no table.
 __global__ void __launch_bounds__(256) pmx_seed_extract_kernel(const uint8_t *__restrict__ buf, const int64_t *__restrict__ off, long long count,
                                                                long long bytes, int k, uint64_t *__restrict__ keys, uint64_t *__restrict__ vals,
                                                                unsigned long long *n_valid)
@@ -40,36 +82,27 @@ __global__ void __launch_bounds__(256) pmx_seed_extract_kernel(const uint8_t *__
     unsigned found = 0;
     if (p0 < bytes) {
         const uint64_t invalid = (uint64_t)1 << (2 * k), mask = invalid - 1;
-        // region r: -1 before the first sequence, count behind the last one, else sequence r = [off[r], off[r + 1])
-        long long lo = 0, hi = count + 1;
-        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (off[mid] <= p0) lo = mid + 1; else hi = mid; }
-        long long r = lo - 1;
-        long long e = r < count ? off[r + 1] : INT64_MAX;
-        long long b = r >= 0 ? off[r] : 0;
+        PmxSeedRegion g = pmx_seed_region(off, count, p0);
         const long long pend = min(p0 + PMX_SEED_TILE, bytes), xend = min(pend + k - 1, bytes);
         uint64_t key = 0; int run = 0;
         for (long long x = p0; x < xend; ++x) {
-            while (x >= e && r < count) { ++r; b = e; e = r < count ? off[r + 1] : INT64_MAX; run = 0; }
-            const bool inside = r >= 0 && r < count && b >= 0 && b <= x && x < e && e <= bytes;
-            const int c = inside ? pmx_seed_code(buf[x]) : -1;
+            if (pmx_seed_region_advance(g, off, count, x)) run = 0;
+            const int c = pmx_seed_region_inside(g, count, bytes, x) ? pmx_seed_code(buf[x]) : -1;
             if (c < 0) { run = 0; key = 0; } else { key = (key << 2) | (uint64_t)c; ++run; }
             const long long s = x - k + 1;
             if (s >= p0) {
-                const bool have = run >= k && s >= b;
+                const bool have = run >= k && s >= g.b;
                 keys[s] = have ? (key & mask) : invalid;
-                vals[s] = have ? ((uint64_t)r << 32) | (uint64_t)(uint32_t)(s - b) : (uint64_t)s;
+                vals[s] = have ? ((uint64_t)g.r << 32) | (uint64_t)(uint32_t)(s - g.b) : (uint64_t)s;
                 found += have ? 1u : 0u;
             }
         }
-        for (long long s = max(p0, xend - k + 1); s < pend; ++s) { keys[s] = invalid; vals[s] = (uint64_t)s; }
+        pmx_seed_no_kmers(keys, vals, 0, max(p0, xend - k + 1), pend, invalid);
     }
-    // one add per block: the sum does not depend on the order of arrival
     __shared__ unsigned total;
     if (threadIdx.x == 0) total = 0;
     __syncthreads();
-    if (found) atomicAdd(&total, found);
-    __syncthreads();
-    if (threadIdx.x == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+    pmx_seed_block_sum(total, found, n_valid);
 }
 
 // bucket[b] = the first entry whose key's top bits are >= b, for b in 0 .. nb (bucket[nb] = n); n > 0
@@ -133,9 +166,28 @@ int pmx_launch_seed_entries(const uint64_t *keys, const uint64_t *vals, long lon
 }
 
 // ---- seeding -------------------------------------------------------------------------------------------------------------------------
+// The index's entries of `key`: lo = the first one, cnt = how many; 0 / 0 where the k-mer is absent or occurs more than max_occ times.
+// One read of the bucket table, a lower bound inside the bucket, the probe at lo + max_occ, an upper bound below it.
+__device__ __forceinline__ void pmx_seed_lookup(uint64_t key, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
+                                                int max_occ, uint32_t &lo, uint32_t &cnt)
+{
+    const uint32_t s = bucket[key >> shift], t1 = bucket[(key >> shift) + 1];
+    uint32_t a = s, z = t1;
+    while (a < z) { const uint32_t mid = a + ((z - a) >> 1); if (keys[mid] < key) a = mid + 1; else z = mid; }
+    if (a < t1 && keys[a] == key) {
+        lo = a;
+        const uint32_t lim = (uint32_t)min((unsigned long long)t1, (unsigned long long)a + (unsigned long long)max_occ);
+        if (!(lim < t1 && keys[lim] == key)) {                 // (else: more than max_occ occurrences, ignored entirely)
+            uint32_t u = a + 1; z = lim;
+            while (u < z) { const uint32_t mid = u + ((z - u) >> 1); if (keys[mid] == key) u = mid + 1; else z = mid; }
+            cnt = u - a;
+        }
+    }
+}
+
 // Position slot p = (row_local * strands + s) * max_qlen + i.  lo[p]: the first index entry of the slot's k-mer, cnt[p]: its
 // occurrences, 0 where the oriented query has no k-mer at i, the k-mer is absent or it occurs more than max_occ times.  cnt has one
-// entry more than there are slots (0: the scan's total).
+// entry more than there are slots (0: the scan's total).  The key comes straight from the row's bytes: no code stage on this road.
 __global__ void __launch_bounds__(256) pmx_seed_count_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
                                                              long long row0, long long slots, int strands, int strand0, int max_qlen, int k,
                                                              const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
@@ -160,20 +212,7 @@ __global__ void __launch_bounds__(256) pmx_seed_count_kernel(const uint8_t *__re
             ok = ok && c >= 0;
             key = (key << 2) | (uint64_t)((strand ? 3 - c : c) & 3);
         }
-        if (ok) {
-            const uint32_t s = bucket[key >> shift], t1 = bucket[(key >> shift) + 1];
-            uint32_t a = s, z = t1;
-            while (a < z) { const uint32_t mid = a + ((z - a) >> 1); if (keys[mid] < key) a = mid + 1; else z = mid; }
-            if (a < t1 && keys[a] == key) {
-                lo = a;
-                const uint32_t lim = (uint32_t)min((unsigned long long)t1, (unsigned long long)a + (unsigned long long)max_occ);
-                if (!(lim < t1 && keys[lim] == key)) {                 // (else: more than max_occ occurrences, ignored entirely)
-                    uint32_t u = a + 1; z = lim;
-                    while (u < z) { const uint32_t mid = u + ((z - u) >> 1); if (keys[mid] == key) u = mid + 1; else z = mid; }
-                    cnt = u - a;
-                }
-            }
-        }
+        if (ok) pmx_seed_lookup(key, keys, bucket, shift, max_occ, lo, cnt);
     }
     lo_out[p] = lo; cnt_out[p] = cnt;
 }
@@ -186,22 +225,44 @@ __global__ void pmx_seed_cut_kernel(const int64_t *__restrict__ moff, long long 
     out[0] = a; out[1] = moff[a * stride];
 }
 
-__global__ void __launch_bounds__(256) pmx_seed_emit_kernel(long long total, int max_qlen, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ cnt,
-                                                            const int64_t *__restrict__ moff, const uint64_t *__restrict__ vals,
-                                                            uint64_t *__restrict__ mkeys)
+// A match key: (id << 32) | the diagonal, biased so that the keys sort by (id, diagonal).
+__device__ __forceinline__ uint64_t pmx_seed_key(uint64_t id, long long d) { return (id << 32) | (uint64_t)((uint32_t)(int32_t)d ^ 0x80000000u); }
+
+// The match key of index value v met at position i of orientation slot t = p / max_qlen (G: PmxSeedGeom; count: the set's sequences).
+// DNA, FRAMES: v = r << 32 | j, the key's id is r and its diagonal d = j - i, in letters of the index.
+// CODONS: the nucleotide diagonal D = 3 j - (off + 3 i), off = the slot's frame % 3 = its orientation slot % 3 (orients is 3 or 6 and
+//   `first` 0 or 3 there).  |D| < 2^31 by the slot's i < 2^31 / 3 and the index's j < 2^29.
+// A translated index: v = (s * count + r) << 32 | x.  REF_FRAMES: id = g * count + r with the sequence frame g = 3 s + x % 3, and the
+//   diagonal d = x / 3 - i in letters.  REF_CODONS: id = s * count + r and the nucleotide diagonal D = x - 3 i.  |d| < 2^31 by
+//   x < 2^30 and 3 i < 2^31 (a row's worst case fits the match buffer).
+template <int G>
+__device__ __forceinline__ uint64_t pmx_seed_match_key(uint64_t v, long long t, long long i, long long count)
+{
+    const long long j = (long long)(uint32_t)v, id0 = (long long)(v >> 32);
+    if (G == PMX_SEED_GEOM_CODONS) return pmx_seed_key((uint64_t)id0, 3 * j - ((long long)(t % 3) + 3 * i));
+    if (G == PMX_SEED_GEOM_REF_CODONS) return pmx_seed_key((uint64_t)id0, j - 3 * i);
+    if (G == PMX_SEED_GEOM_REF_FRAMES) {
+        const long long s = id0 >= count ? 1 : 0;
+        return pmx_seed_key((uint64_t)((3 * s + j % 3) * count + (id0 - s * count)), j / 3 - i);
+    }
+    return pmx_seed_key((uint64_t)id0, j - i);
+}
+
+// the matches of position slot p, behind moff[p]
+template <int G>
+__global__ void __launch_bounds__(256) pmx_seed_emit_kernel(long long total, int max_qlen, long long count, const uint32_t *__restrict__ lo,
+                                                            const uint32_t *__restrict__ cnt, const int64_t *__restrict__ moff,
+                                                            const uint64_t *__restrict__ vals, uint64_t *__restrict__ mkeys)
 {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= total) return;
     const uint32_t n = cnt[p];
     if (!n) return;
-    const int i = (int)(p % max_qlen);
+    const long long t = p / max_qlen;
+    const long long i = p - t * max_qlen;
     const uint32_t first = lo[p];
     uint64_t *out = mkeys + moff[p];
-    for (uint32_t x = 0; x < n; ++x) {
-        const uint64_t v = vals[first + x];
-        const int32_t d = (int32_t)(uint32_t)v - i;
-        out[x] = (v & 0xFFFFFFFF00000000ull) | (uint64_t)((uint32_t)d ^ 0x80000000u);
-    }
+    for (uint32_t x = 0; x < n; ++x) out[x] = pmx_seed_match_key<G>(vals[first + x], t, i, count);
 }
 
 // segment t of the sort: the matches of (row, strand) slot t
@@ -244,31 +305,82 @@ __global__ void __launch_bounds__(256) pmx_seed_flags_kernel(const uint32_t *__r
     flag[x] = tail && x - (long long)head[x] + 1 >= min_seeds ? 1u : 0u;
 }
 
-// candidate tails -> outputs at base + pos[x], below `capacity`; base = counts[0], the candidates of the slices before
+// floor(a / 3) for either sign
+__device__ __forceinline__ long long pmx_seed_floor3(long long a) { return a >= 0 ? a / 3 : -((2 - a) / 3); }
+
+// What the hits kernel hands a geometry besides the cluster: the rows' layout of the plan and the two sets' offsets.
+struct PmxSeedWindowArgs {
+    long long row0; int segs, first; bool rows_translated; long long count; int pad;
+    const int64_t *__restrict__ qoff, *__restrict__ roff;
+};
+struct PmxSeedWindow { long long row, r, beg, end; int byte, reserved; };
+
+// The candidate of a closed cluster: segment a of the slice, id of its match keys, diagonals dmin .. dmax (G: PmxSeedGeom).
+// DNA, FRAMES: a segment is (row, orientation); byte = the strand / the frame (0 where the rows are letters); the window from the
+//   letter diagonals and the oriented row's letters L: its bytes, or the translation's length (W - frame % 3) / 3.
+// CODONS: a segment is (row, strand), three frames wide; byte = the strand (`first` is the first FRAME, 0 or 3); the window from the
+//   nucleotide diagonals and W, in letters of the reference.
+// A translated index, a segment is a row of m letters, N = len(r).  REF_FRAMES: id = g * count + r; the letter window [lb, le) =
+//   [max(0, d_min - pad), min((N - g % 3) / 3, d_max + m + pad)) of frame g as stored nucleotides, codon-aligned: [g % 3 + 3 lb,
+//   g % 3 + 3 le) on strand 0, [N - g % 3 - 3 le, N - g % 3 - 3 lb) on strand 1, so the frame byte relative to the window is 0 or 3;
+//   reserved = g.  REF_CODONS: id = s * count + r; the oriented window [max(0, D_min - pad), min(N, D_max + 3 m + pad)), stored
+//   [lo, hi) or [N - hi, N - lo); byte = s.
+template <int G>
+__device__ __forceinline__ PmxSeedWindow pmx_seed_window(const PmxSeedWindowArgs &g, long long a, long long id, long long dmin, long long dmax)
+{
+    PmxSeedWindow w; w.reserved = 0;
+    if (G == PMX_SEED_GEOM_REF_FRAMES || G == PMX_SEED_GEOM_REF_CODONS) {
+        w.row = g.row0 + a;
+        const long long o = id / g.count;       // the sequence frame g (REF_FRAMES), the strand (REF_CODONS)
+        w.r = id - o * g.count;
+        const long long len = g.qoff[w.row + 1] - g.qoff[w.row], N = g.roff[w.r + 1] - g.roff[w.r];
+        if (G == PMX_SEED_GEOM_REF_CODONS) {
+            const long long wlo = max(0ll, dmin - g.pad), whi = min(N, dmax + 3 * len + g.pad);
+            w.beg = o ? N - whi : wlo; w.end = o ? N - wlo : whi;
+            w.byte = (int)o;
+        } else {
+            const long long ph = o % 3, lb = max(0ll, dmin - g.pad), le = min((N - ph) / 3, dmax + len + g.pad);
+            w.beg = o >= 3 ? N - ph - 3 * le : ph + 3 * lb; w.end = o >= 3 ? N - ph - 3 * lb : ph + 3 * le;
+            w.byte = o >= 3 ? 3 : 0; w.reserved = (int)o;
+        }
+        return w;
+    }
+    w.row = g.row0 + a / g.segs; w.r = id;
+    w.byte = (G == PMX_SEED_GEOM_CODONS ? g.first / 3 : g.first) + (int)(a % g.segs);
+    const long long W = g.qoff[w.row + 1] - g.qoff[w.row], rlen = g.roff[w.r + 1] - g.roff[w.r];
+    if (G == PMX_SEED_GEOM_CODONS) {
+        w.beg = max(0ll, pmx_seed_floor3(dmin) - g.pad);
+        w.end = min(rlen, pmx_seed_floor3(dmax + W - 1) + 1 + g.pad);
+    } else {
+        const long long L = g.rows_translated ? (W - w.byte % 3) / 3 : W;
+        w.beg = max(0ll, dmin - g.pad);
+        w.end = min(rlen, dmax + L + g.pad);
+    }
+    return w;
+}
+
+// candidate tails -> outputs at base + pos[x], below `capacity`; base = counts[0], the candidates of the slices before.  The
+// segments: `slots` of them, `stride` position slots each.
+template <int G>
 __global__ void __launch_bounds__(256) pmx_seed_hits_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ pos,
                                                             long long m, const int64_t *__restrict__ moff, long long slots, long long stride,
-                                                            long long row0, int strands, int strand0, int pad,
-                                                            const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
-                                                            const int64_t *__restrict__ counts, long long capacity,
-                                                            pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_strand, pmx_seed_hit_t *__restrict__ hit_seeds)
+                                                            PmxSeedWindowArgs g, const int64_t *__restrict__ counts, long long capacity,
+                                                            pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_byte, pmx_seed_hit_t *__restrict__ hit_seeds)
 {
     const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= m || pos[x + 1] == pos[x]) return;
     const long long at = counts[0] + (long long)pos[x];
     if (at >= capacity) return;
-    long long a = 0, z = slots - 1;             // the slot of x: the last t with moff[t * stride] <= x (empty segments share a start)
+    long long a = 0, z = slots - 1;             // the segment of x: the last t with moff[t * stride] <= x (empty segments share a start)
     while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= x) a = mid; else z = mid - 1; }
-    const long long row = row0 + a / strands;
-    const int strand = strands == 2 ? (int)(a & 1) : strand0;
     const uint32_t h = head[x];
     const uint64_t kh = mkeys[h], kt = mkeys[x];
-    const long long r = (long long)(kt >> 32), dmin = pmx_seed_diag(kh), dmax = pmx_seed_diag(kt);
-    const long long qlen = qoff[row + 1] - qoff[row], rlen = roff[r + 1] - roff[r];
-    const long long beg = max(0ll, dmin - pad), end = min(rlen, dmax + qlen + pad);
-    pmx_pair_t pr; pr.q = row; pr.r = r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)beg; pr.r_len = (int32_t)(end - beg);
+    const long long dmin = pmx_seed_diag(kh), dmax = pmx_seed_diag(kt);
+    const PmxSeedWindow w = pmx_seed_window<G>(g, a, (long long)(kt >> 32), dmin, dmax);
+    pmx_pair_t pr; pr.q = w.row; pr.r = w.r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)w.beg; pr.r_len = (int32_t)(w.end - w.beg);
     hit_pairs[at] = pr;
-    hit_strand[at] = (uint8_t)strand;
-    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = (int32_t)(x - h + 1); s.diag_min = (int32_t)dmin; s.diag_max = (int32_t)dmax; s.reserved = 0; hit_seeds[at] = s; }
+    hit_byte[at] = (uint8_t)w.byte;
+    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = (int32_t)(x - h + 1); s.diag_min = (int32_t)dmin; s.diag_max = (int32_t)dmax; s.reserved = w.reserved; hit_seeds[at] = s; }
 }
 
 // row_off[x + 1] = base + the candidates of the slice's rows 0 .. x (pos == NULL: the slice has no match)
@@ -305,97 +417,13 @@ size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slo
     return std::max(std::max(a, b), std::max(c, d)) + 256;
 }
 
-// The slice's count pass, scan and cut: rows row0 .. row0 + rows of Q; cut (device, 2 entries) receives how many of them fit
-// `cap_matches` and their matches.
-int pmx_launch_seed_count(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int strands, int strand0,
-                          int max_qlen, int k, const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
-                          uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
-                          hipStream_t stream)
-{
-    const long long slots = rows * strands, total = slots * max_qlen;
-    hipLaunchKernelGGL(pmx_seed_count_kernel, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, stream, qbuf, qoff, q_bytes, row0, slots, strands,
-                       strand0, max_qlen, k, keys, bucket, shift, max_occ, lo, cnt);
-    int rc = pmx_launched();
-    if (rc) return rc;
-    auto in = rocprim::make_transform_iterator((const uint32_t *)cnt, PmxWidenU32());
-    const hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, in, moff, (int64_t)0, (size_t)(total + 1), rocprim::plus<int64_t>(), stream);
-    if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(pmx_seed_cut_kernel, dim3(1), dim3(1), 0, stream, moff, rows, (long long)strands * max_qlen, cap_matches, cut);
-    return pmx_launched();
-}
-
-// Between emit and hits, whatever the letters were: the m matches of mkeys_a sorted per segment (`slots` segments of `stride` position
-// slots each) into mkeys_b, head[x] = the head of x's cluster, flag[x + 1] - flag[x] = 1 where x closes a candidate (flag: m + 1 entries).
-static int pmx_seed_sort_clusters(long long m, long long slots, long long stride, int key_bits, const int64_t *moff,
-                                  uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds,
-                                  void *temp, size_t temp_bytes, hipStream_t stream)
-{
-    int rc = 0;
-    const unsigned mb = (unsigned)((m + 255) / 256);
-    auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{moff, stride});
-    size_t tb = temp_bytes;
-    hipError_t e = rocprim::segmented_radix_sort_keys(temp, tb, (const uint64_t *)mkeys_a, mkeys_b, (unsigned)m, (unsigned)slots, seg, seg + 1, 0, key_bits,
-                                                      stream);
-    if (e != hipSuccess) return -(int)e;
-    if (hipMemsetAsync(flag, 0, sizeof(uint32_t) * (size_t)(m + 1), stream) != hipSuccess) return -1;
-    hipLaunchKernelGGL(pmx_seed_segstart_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, moff, slots, stride, flag);
-    if ((rc = pmx_launched())) return rc;
-    hipLaunchKernelGGL(pmx_seed_heads_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)mkeys_b, m, band, (const uint32_t *)flag, head);
-    if ((rc = pmx_launched())) return rc;
-    tb = temp_bytes;
-    e = rocprim::inclusive_scan(temp, tb, head, head, (size_t)m, PmxMaxU32(), stream);
-    if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(pmx_seed_flags_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t *)head, m, min_seeds, flag);
-    if ((rc = pmx_launched())) return rc;
-    tb = temp_bytes;
-    e = rocprim::exclusive_scan(temp, tb, flag, flag, 0u, (size_t)(m + 1), rocprim::plus<uint32_t>(), stream);
-    return e == hipSuccess ? 0 : -(int)e;
-}
-
-// Behind the hits: the slice's row offsets (row_stride position slots per row) and the running counts.
-static int pmx_seed_finish(long long rows, long long row_stride, long long m, const int64_t *moff, const uint32_t *flag, long long capacity,
-                           int64_t *row_off, int64_t *counts, hipStream_t stream)
-{
-    hipLaunchKernelGGL(pmx_seed_rowoff_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, m > 0 ? flag : nullptr, moff, rows, row_stride,
-                       (const int64_t *)counts, row_off);
-    const int rc = pmx_launched();
-    if (rc) return rc;
-    hipLaunchKernelGGL(pmx_seed_advance_kernel, dim3(1), dim3(1), 0, stream, m > 0 ? flag : nullptr, m, capacity, counts);
-    return pmx_launched();
-}
-
-// The slice's `rows` rows (what the cut kept) with their m matches: emit, sort, clusters, outputs behind counts[0]; row_off points at
-// the entry of the slice's first row.
-int pmx_launch_seed_cluster(long long row0, long long rows, int strands, int strand0, int max_qlen, long long m, int key_bits,
-                            const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
-                            uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
-                            const int64_t *qoff, const int64_t *roff, long long capacity,
-                            pmx_pair_t *hit_pairs, uint8_t *hit_strand, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
-                            void *temp, size_t temp_bytes, hipStream_t stream)
-{
-    const long long slots = rows * strands, stride = max_qlen, total = slots * stride;
-    int rc = 0;
-    if (m > 0) {
-        hipLaunchKernelGGL(pmx_seed_emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, max_qlen, lo, cnt, moff, vals, mkeys_a);
-        if ((rc = pmx_launched())) return rc;
-        if ((rc = pmx_seed_sort_clusters(m, slots, stride, key_bits, moff, mkeys_a, mkeys_b, head, flag, band, min_seeds, temp, temp_bytes, stream))) return rc;
-        if (capacity > 0) {
-            hipLaunchKernelGGL(pmx_seed_hits_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head,
-                               (const uint32_t *)flag, m, moff, slots, stride, row0, strands, strand0, pad, qoff, roff, (const int64_t *)counts, capacity,
-                               hit_pairs, hit_strand, hit_seeds);
-            if ((rc = pmx_launched())) return rc;
-        }
-    }
-    return pmx_seed_finish(rows, (long long)strands * stride, m, moff, flag, capacity, row_off, counts, stream);
-}
-
 // ---- letters: a protein index over a reduced alphabet, proteins or translated reads as queries --------------------------
 // The index is the DNA one with a run-time number of bits per letter and the letter's group read from a 256-byte table staged in LDS.
 // Seeding adds one stage in front of the count pass: a code byte per position slot -- the group of the letter there, 255 where there
 // is none -- so that a codon is read and translated once per frame and the count pass forms its keys from k code bytes.  A position
-// slot is p = ((row_local * orients) + o) * max_qlen + i; orientation o of a row is frame `first` + o (letters mode: the row itself).
-// The codon modes' (row, strand, frame, i) is the same number with orients = 3 strands: only the segments of the sort differ, three
-// frames wide there, and with them emit's diagonal and the window.
+// slot is p = ((row_local * orients) + o) * max_qlen + i; orientation o of a row is frame `first` + o (rows that are letters: the row
+// itself).  The codon modes' (row, strand, frame, i) is the same number with orients = 3 strands: only the segments of the sort differ,
+// three frames wide there, and with them the geometry (pmx_seed_match_key, pmx_seed_window).
 
 // keys[p] / vals[p] for every p < bytes, as pmx_seed_extract_kernel: `bits` bits per letter, table[b] = the group of byte b or 255
 __global__ void __launch_bounds__(256) pmx_seedl_extract_kernel(const uint8_t *__restrict__ buf, const int64_t *__restrict__ off, long long count,
@@ -411,31 +439,24 @@ __global__ void __launch_bounds__(256) pmx_seedl_extract_kernel(const uint8_t *_
     unsigned found = 0;
     if (p0 < bytes) {
         const uint64_t invalid = (uint64_t)1 << (k * bits), mask = invalid - 1;
-        long long lo = 0, hi = count + 1;
-        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (off[mid] <= p0) lo = mid + 1; else hi = mid; }
-        long long r = lo - 1;
-        long long e = r < count ? off[r + 1] : INT64_MAX;
-        long long b = r >= 0 ? off[r] : 0;
+        PmxSeedRegion g = pmx_seed_region(off, count, p0);
         const long long pend = min(p0 + PMX_SEED_TILE, bytes), xend = min(pend + k - 1, bytes);
         uint64_t key = 0; int run = 0;
         for (long long x = p0; x < xend; ++x) {
-            while (x >= e && r < count) { ++r; b = e; e = r < count ? off[r + 1] : INT64_MAX; run = 0; }
-            const bool inside = r >= 0 && r < count && b >= 0 && b <= x && x < e && e <= bytes;
-            const uint32_t c = inside ? (uint32_t)grp[buf[x]] : 255u;
+            if (pmx_seed_region_advance(g, off, count, x)) run = 0;
+            const uint32_t c = pmx_seed_region_inside(g, count, bytes, x) ? (uint32_t)grp[buf[x]] : 255u;
             if (c == 255u) { run = 0; key = 0; } else { key = (key << bits) | (uint64_t)c; ++run; }
             const long long s = x - k + 1;
             if (s >= p0) {
-                const bool have = run >= k && s >= b;
+                const bool have = run >= k && s >= g.b;
                 keys[s] = have ? (key & mask) : invalid;
-                vals[s] = have ? ((uint64_t)r << 32) | (uint64_t)(uint32_t)(s - b) : (uint64_t)s;
+                vals[s] = have ? ((uint64_t)g.r << 32) | (uint64_t)(uint32_t)(s - g.b) : (uint64_t)s;
                 found += have ? 1u : 0u;
             }
         }
-        for (long long s = max(p0, xend - k + 1); s < pend; ++s) { keys[s] = invalid; vals[s] = (uint64_t)s; }
+        pmx_seed_no_kmers(keys, vals, 0, max(p0, xend - k + 1), pend, invalid);
     }
-    if (found) atomicAdd(&total, found);
-    __syncthreads();
-    if (threadIdx.x == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+    pmx_seed_block_sum(total, found, n_valid);
 }
 
 size_t pmx_seed_index_sort_bytes_letters(long long bytes, int k, int bits)
@@ -467,13 +488,13 @@ __device__ __forceinline__ uint32_t pmx_seedl_base(uint32_t b)
     return u == 'T' || u == 'U' ? 0u : u == 'C' ? 1u : u == 'A' ? 2u : u == 'G' ? 3u : 4u;
 }
 
-// codes[p] for every position slot of the slice.  first < 0: letters mode, the slot's letter is the row's byte i.  Else the slot's
-// frame is f = first + o, off = f % 3, and its letter is the codon at bytes off + 3 i .. of the row as stored (f < 3) or of its reverse
-// complement (f >= 3): the three bytes at W - 1 - (off + 3 i) downwards, complemented by the index ^ 42 -- nothing is materialised.
-// A codon with a byte that is no nucleotide is X.  The letter goes through the index's table.  255: no letter there (behind the
-// translation's end, a bad row, a row whose W / 3 (letters mode: W) exceeds max_qlen) or a letter outside the alphabet.
+// codes[p] for every position slot of the slice.  Rows that are letters (translated false): the slot's letter is the row's byte i.
+// Else the slot's frame is f = first + o, off = f % 3, and its letter is the codon at bytes off + 3 i .. of the row as stored (f < 3) or
+// of its reverse complement (f >= 3): the three bytes at W - 1 - (off + 3 i) downwards, complemented by the index ^ 42 -- nothing is
+// materialised.  A codon with a byte that is no nucleotide is X.  The letter goes through the index's table.  255: no letter there
+// (behind the translation's end, a bad row, a row whose W / 3 (rows that are letters: W) exceeds max_qlen) or a letter outside the alphabet.
 __global__ void __launch_bounds__(256) pmx_seedl_codes_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
-                                                              long long row0, long long total, int orients, int first, int max_qlen,
+                                                              long long row0, long long total, int orients, int first, bool translated, int max_qlen,
                                                               const uint8_t *__restrict__ table, PmxCodeTable code, uint8_t *__restrict__ codes)
 {
     __shared__ uint8_t grp[256];
@@ -491,7 +512,7 @@ __global__ void __launch_bounds__(256) pmx_seedl_codes_kernel(const uint8_t *__r
     if (b >= 0 && e >= b && e <= q_bytes) {
         const long long W = e - b;
         const uint8_t *w = qbuf + b;
-        if (first < 0) {
+        if (!translated) {
             if (W <= max_qlen && i < W) c = grp[w[i]];
         } else {
             const int f = first + (int)(t % orients), off = f % 3;
@@ -526,145 +547,9 @@ __global__ void __launch_bounds__(256) pmx_seedl_count_kernel(const uint8_t *__r
             ok = ok && c != 255u;
             key = (key << bits) | (uint64_t)(c & 31u);
         }
-        if (ok) {
-            const uint32_t s = bucket[key >> shift], t1 = bucket[(key >> shift) + 1];
-            uint32_t a = s, z = t1;
-            while (a < z) { const uint32_t mid = a + ((z - a) >> 1); if (keys[mid] < key) a = mid + 1; else z = mid; }
-            if (a < t1 && keys[a] == key) {
-                lo = a;
-                const uint32_t lim = (uint32_t)min((unsigned long long)t1, (unsigned long long)a + (unsigned long long)max_occ);
-                if (!(lim < t1 && keys[lim] == key)) {                 // (else: more than max_occ occurrences, ignored entirely)
-                    uint32_t u = a + 1; z = lim;
-                    while (u < z) { const uint32_t mid = u + ((z - u) >> 1); if (keys[mid] == key) u = mid + 1; else z = mid; }
-                    cnt = u - a;
-                }
-            }
-        }
+        if (ok) pmx_seed_lookup(key, keys, bucket, shift, max_occ, lo, cnt);
     }
     lo_out[p] = lo; cnt_out[p] = cnt;
-}
-
-// floor(a / 3) for either sign
-__device__ __forceinline__ long long pmx_seedl_floor3(long long a) { return a >= 0 ? a / 3 : -((2 - a) / 3); }
-
-// pmx_seed_emit_kernel with the mode's diagonal.  CODON false: d = j - i in letters.  CODON true: the nucleotide diagonal
-// D = 3 j - (off + 3 i), off = the slot's frame % 3 = its orientation slot % 3 (orients is 3 or 6 and `first` 0 or 3 there).
-// |d| < 2^31 by the slot's i < 2^31 / 3 and the index's j < 2^29.
-template <bool CODON>
-__global__ void __launch_bounds__(256) pmx_seedl_emit_kernel(long long total, int max_qlen, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ cnt,
-                                                             const int64_t *__restrict__ moff, const uint64_t *__restrict__ vals,
-                                                             uint64_t *__restrict__ mkeys)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= total) return;
-    const uint32_t n = cnt[p];
-    if (!n) return;
-    const long long t = p / max_qlen;
-    const long long i = p - t * max_qlen;
-    const long long sub = CODON ? (long long)(t % 3) + 3 * i : i;
-    const uint32_t first = lo[p];
-    uint64_t *out = mkeys + moff[p];
-    for (uint32_t x = 0; x < n; ++x) {
-        const uint64_t v = vals[first + x];
-        const long long j = (long long)(uint32_t)v;
-        const int32_t d = (int32_t)((CODON ? 3 * j : j) - sub);
-        out[x] = (v & 0xFFFFFFFF00000000ull) | (uint64_t)((uint32_t)d ^ 0x80000000u);
-    }
-}
-
-// pmx_seed_hits_kernel with the mode's window and byte.  A segment is (row, orientation) of `stride` = max_qlen slots (CODON false:
-// byte = the frame, 0 in letters mode; window from the letter diagonals and the translation's length) or (row, strand) of
-// `stride` = 3 max_qlen slots (CODON true: byte = the strand; window from the nucleotide diagonals and W).  segs: segments per row;
-// first: the first segment's frame / strand, < 0 in letters mode.
-template <bool CODON>
-__global__ void __launch_bounds__(256) pmx_seedl_hits_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ pos,
-                                                             long long m, const int64_t *__restrict__ moff, long long slots, long long stride,
-                                                             long long row0, int segs, int first, int pad,
-                                                             const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
-                                                             const int64_t *__restrict__ counts, long long capacity,
-                                                             pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_byte, pmx_seed_hit_t *__restrict__ hit_seeds)
-{
-    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= m || pos[x + 1] == pos[x]) return;
-    const long long at = counts[0] + (long long)pos[x];
-    if (at >= capacity) return;
-    long long a = 0, z = slots - 1;             // the segment of x: the last t with moff[t * stride] <= x (empty segments share a start)
-    while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= x) a = mid; else z = mid - 1; }
-    const long long row = row0 + a / segs;
-    const int byte = first < 0 ? 0 : first + (int)(a % segs);
-    const uint32_t h = head[x];
-    const uint64_t kh = mkeys[h], kt = mkeys[x];
-    const long long r = (long long)(kt >> 32), dmin = pmx_seed_diag(kh), dmax = pmx_seed_diag(kt);
-    const long long W = qoff[row + 1] - qoff[row], rlen = roff[r + 1] - roff[r];
-    long long beg, end;
-    if (CODON) {
-        beg = max(0ll, pmx_seedl_floor3(dmin) - pad);
-        end = min(rlen, pmx_seedl_floor3(dmax + W - 1) + 1 + pad);
-    } else {
-        const long long L = first < 0 ? W : (W - byte % 3) / 3;
-        beg = max(0ll, dmin - pad);
-        end = min(rlen, dmax + L + pad);
-    }
-    pmx_pair_t pr; pr.q = row; pr.r = r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)beg; pr.r_len = (int32_t)(end - beg);
-    hit_pairs[at] = pr;
-    hit_byte[at] = (uint8_t)byte;
-    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = (int32_t)(x - h + 1); s.diag_min = (int32_t)dmin; s.diag_max = (int32_t)dmax; s.reserved = 0; hit_seeds[at] = s; }
-}
-
-// pmx_launch_seed_count for a letters index: the code stage (codes: one byte per position slot), the count pass over it, scan and cut.
-// orients: orientation slots per row; first: the first one's frame, < 0 in letters mode.
-int pmx_launch_seed_count_letters(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long rows, int orients, int first,
-                                  int max_qlen, int k, int bits, const uint8_t *table, const PmxCodeTable &code, uint8_t *codes,
-                                  const uint64_t *keys, const uint32_t *bucket, int shift, int max_occ,
-                                  uint32_t *lo, uint32_t *cnt, int64_t *moff, long long cap_matches, int64_t *cut, void *temp, size_t temp_bytes,
-                                  hipStream_t stream)
-{
-    const long long total = rows * orients * max_qlen;
-    hipLaunchKernelGGL(pmx_seedl_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, qbuf, qoff, q_bytes, row0, total, orients, first,
-                       max_qlen, table, code, codes);
-    int rc = pmx_launched();
-    if (rc) return rc;
-    hipLaunchKernelGGL(pmx_seedl_count_kernel, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, stream, (const uint8_t *)codes, total, max_qlen, k, bits,
-                       keys, bucket, shift, max_occ, lo, cnt);
-    if ((rc = pmx_launched())) return rc;
-    auto in = rocprim::make_transform_iterator((const uint32_t *)cnt, PmxWidenU32());
-    const hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, in, moff, (int64_t)0, (size_t)(total + 1), rocprim::plus<int64_t>(), stream);
-    if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(pmx_seed_cut_kernel, dim3(1), dim3(1), 0, stream, moff, rows, (long long)orients * max_qlen, cap_matches, cut);
-    return pmx_launched();
-}
-
-// pmx_launch_seed_cluster for a letters index; codon: the codon modes (segments of three frames, nucleotide diagonals).
-int pmx_launch_seed_cluster_letters(long long row0, long long rows, int orients, int first, bool codon, int max_qlen, long long m, int key_bits,
-                                    const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
-                                    uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
-                                    const int64_t *qoff, const int64_t *roff, long long capacity,
-                                    pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
-                                    void *temp, size_t temp_bytes, hipStream_t stream)
-{
-    const int segs = codon ? orients / 3 : orients;
-    const long long slots = rows * segs, stride = (long long)(codon ? 3 : 1) * max_qlen, total = slots * stride;
-    const int seg_first = codon ? first / 3 : first;
-    int rc = 0;
-    if (m > 0) {
-        const dim3 eb((unsigned)((total + 255) / 256)), hb((unsigned)((m + 255) / 256));
-        if (codon) hipLaunchKernelGGL(pmx_seedl_emit_kernel<true>, eb, dim3(256), 0, stream, total, max_qlen, lo, cnt, moff, vals, mkeys_a);
-        else hipLaunchKernelGGL(pmx_seedl_emit_kernel<false>, eb, dim3(256), 0, stream, total, max_qlen, lo, cnt, moff, vals, mkeys_a);
-        if ((rc = pmx_launched())) return rc;
-        if ((rc = pmx_seed_sort_clusters(m, slots, stride, key_bits, moff, mkeys_a, mkeys_b, head, flag, band, min_seeds, temp, temp_bytes, stream))) return rc;
-        if (capacity > 0) {
-            if (codon)
-                hipLaunchKernelGGL(pmx_seedl_hits_kernel<true>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
-                                   m, moff, slots, stride, row0, segs, seg_first, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte,
-                                   hit_seeds);
-            else
-                hipLaunchKernelGGL(pmx_seedl_hits_kernel<false>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
-                                   m, moff, slots, stride, row0, segs, seg_first, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte,
-                                   hit_seeds);
-            if ((rc = pmx_launched())) return rc;
-        }
-    }
-    return pmx_seed_finish(rows, (long long)orients * max_qlen, m, moff, flag, capacity, row_off, counts, stream);
 }
 
 // ---- translated references: a six-frame index of a nucleotide set, proteins as queries ---------------------------------
@@ -672,7 +557,7 @@ int pmx_launch_seed_cluster_letters(long long row0, long long rows, int orients,
 // complement, nothing materialised) starts the codon of oriented bytes x .. x + 2; the k-mer at x is the k codons' letters at x, x + 3,
 // ..., so the index holds the k-mers of all three frames of a strand and x % 3 is the frame's offset.  Entry slot of (s, r, x):
 // s_local * bytes + off[r] + x -- the stable sort then leaves (kmer, s, r, x) order with nothing compacted.  Seeding runs the letters
-// road's code stage and count pass on the protein rows; emit and hits below carry the mode's id, diagonal and window.
+// road's code stage and count pass on the protein rows; the REF geometries carry the mode's id, diagonal and window.
 #define PMX_SEEDT_TILE 48       // slots per thread: a multiple of 3, so a slot's phase is its place in the step unrolled by three
 
 // keys[sl * bytes + p] / vals[..] for every p < bytes of the nstr strands held (strand of sl: strand0 + sl); *n_valid += the k-mers.
@@ -701,11 +586,7 @@ __global__ void __launch_bounds__(256) pmx_seedt_extract_kernel(const uint8_t *_
         const uint32_t flip = strand ? 42u : 0u;
         const uint64_t invalid = (uint64_t)1 << (k * bits), mask = invalid - 1, id0 = (uint64_t)strand * (uint64_t)count;
         const long long span = 3ll * k - 1, base = sl * bytes;
-        long long lo = 0, hi = count + 1;
-        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (off[mid] <= p0) lo = mid + 1; else hi = mid; }
-        long long r = lo - 1;
-        long long e = r < count ? off[r + 1] : INT64_MAX;
-        long long b = r >= 0 ? off[r] : 0;
+        PmxSeedRegion g = pmx_seed_region(off, count, p0);
         const long long pend = min(p0 + PMX_SEEDT_TILE, bytes), xend = min(pend + span, bytes);
         uint64_t key0 = 0, key1 = 0, key2 = 0;
         int run0 = 0, run1 = 0, run2 = 0, nrun = 0;
@@ -717,31 +598,29 @@ __global__ void __launch_bounds__(256) pmx_seedt_extract_kernel(const uint8_t *_
         // reset at a sequence end, so RUN >= k means k codons of this phase inside the sequence, the first of them at s
 #define PMX_SEEDT_STEP(KEY, RUN)                                                                                                        \
         if (x < xend) {                                                                                                                 \
-            while (x >= e && r < count) { ++r; b = e; e = r < count ? off[r + 1] : INT64_MAX; nrun = 0; run0 = run1 = run2 = 0; }       \
-            const bool inside = r >= 0 && r < count && b >= 0 && b <= x && x < e && e <= bytes;                                         \
-            const uint32_t cls = inside ? pmx_seedl_base(buf[strand ? b + e - 1 - x : x]) : 4u;                                         \
+            if (pmx_seed_region_advance(g, off, count, x)) { nrun = 0; run0 = run1 = run2 = 0; }                                        \
+            const bool inside = pmx_seed_region_inside(g, count, bytes, x);                                                             \
+            const uint32_t cls = inside ? pmx_seedl_base(buf[strand ? g.b + g.e - 1 - x : x]) : 4u;                                     \
             nrun = cls > 3u ? 0 : nrun + 1;                                                                                             \
             c6 = ((c6 << 2) | (cls & 3u)) & 63u;                                                                                        \
             const uint32_t letter = cod[c6 ^ flip];                                                                                     \
-            const uint32_t g = nrun >= 3 && letter != (uint32_t)'X' && letter != (uint32_t)'*' ? (uint32_t)grp[letter] : 255u;          \
-            KEY = (KEY << bits) | (uint64_t)(g & 31u);                                                                                  \
-            RUN = g == 255u ? 0 : RUN + 1;                                                                                              \
+            const uint32_t grpl = nrun >= 3 && letter != (uint32_t)'X' && letter != (uint32_t)'*' ? (uint32_t)grp[letter] : 255u;       \
+            KEY = (KEY << bits) | (uint64_t)(grpl & 31u);                                                                               \
+            RUN = grpl == 255u ? 0 : RUN + 1;                                                                                           \
             const long long s = x - span;                                                                                               \
             if (s >= p0) {                                                                                                              \
                 const bool have = RUN >= k;                                                                                             \
                 keys[base + s] = have ? (KEY & mask) : invalid;                                                                         \
-                vals[base + s] = have ? ((id0 + (uint64_t)r) << 32) | (uint64_t)(uint32_t)(s - b) : (uint64_t)(base + s);               \
+                vals[base + s] = have ? ((id0 + (uint64_t)g.r) << 32) | (uint64_t)(uint32_t)(s - g.b) : (uint64_t)(base + s);           \
                 found += have ? 1u : 0u;                                                                                                \
             }                                                                                                                           \
             ++x;                                                                                                                        \
         }
         while (x < xend) { PMX_SEEDT_STEP(key0, run0) PMX_SEEDT_STEP(key1, run1) PMX_SEEDT_STEP(key2, run2) }
 #undef PMX_SEEDT_STEP
-        for (long long s = max(p0, xend - span); s < pend; ++s) { keys[base + s] = invalid; vals[base + s] = (uint64_t)(base + s); }
+        pmx_seed_no_kmers(keys + base, vals + base, base, max(p0, xend - span), pend, invalid);
     }
-    if (found) atomicAdd(&total, found);
-    __syncthreads();
-    if (threadIdx.x == 0 && total) atomicAdd(n_valid, (unsigned long long)total);
+    pmx_seed_block_sum(total, found, n_valid);
 }
 
 // keys_in / vals_in / keys_out / vals_out: nstr * bytes entry slots each
@@ -759,101 +638,95 @@ int pmx_launch_seed_index_translated(const uint8_t *buf, const int64_t *off, lon
     return e == hipSuccess ? 0 : -(int)e;
 }
 
-// pmx_seedl_emit_kernel for a translated index: an entry's value is (s * count + r) << 32 | x.  CODON false: the match key's id is
-// g * count + r with the sequence frame g = 3 s + x % 3, its diagonal d = x / 3 - i in letters.  CODON true: id = s * count + r and
-// the nucleotide diagonal D = x - 3 i.  |d| < 2^31 by x < 2^30 and 3 i < 2^31 (a row's worst case fits the match buffer).
-template <bool CODON>
-__global__ void __launch_bounds__(256) pmx_seedt_emit_kernel(long long total, int max_qlen, long long count, const uint32_t *__restrict__ lo,
-                                                             const uint32_t *__restrict__ cnt, const int64_t *__restrict__ moff,
-                                                             const uint64_t *__restrict__ vals, uint64_t *__restrict__ mkeys)
+// ---- a slice of a seeding run, by its plan (pmx_common.h: PmxSeedPlan) ---------------------------------------------------------------
+// The slice's count pass, scan and cut: rows row0 .. row0 + rows of Q; s.cut (device, 2 entries) receives how many of them fit p.cap_m
+// matches and their matches.  A DNA index forms its keys from the rows' bytes; the others from the code stage's bytes.
+int pmx_launch_seed_count(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedSource &src, long long row0, long long rows, hipStream_t stream)
 {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= total) return;
-    const uint32_t n = cnt[p];
-    if (!n) return;
-    const long long i = p % max_qlen;
-    const uint32_t first = lo[p];
-    uint64_t *out = mkeys + moff[p];
-    for (uint32_t y = 0; y < n; ++y) {
-        const uint64_t v = vals[first + y];
-        const long long x = (long long)(uint32_t)v, id0 = (long long)(v >> 32);
-        long long id, d;
-        if (CODON) { id = id0; d = x - 3 * i; }
-        else {
-            const long long s = id0 >= count ? 1 : 0;
-            id = (3 * s + x % 3) * count + (id0 - s * count); d = x / 3 - i;
-        }
-        out[y] = ((uint64_t)id << 32) | (uint64_t)((uint32_t)(int32_t)d ^ 0x80000000u);
+    const long long total = rows * p.row_slots;
+    const dim3 cb((unsigned)((total + 1 + 255) / 256));
+    int rc = 0;
+    if (p.kind == PMX_SEED_KIND_DNA)
+        hipLaunchKernelGGL(pmx_seed_count_kernel, cb, dim3(256), 0, stream, src.qbuf, src.qoff, src.q_bytes, row0, rows * p.orients, p.orients, p.first,
+                           p.max_qlen, p.k, src.keys, src.bucket, src.shift, p.max_occ, s.lo, s.cnt);
+    else {
+        hipLaunchKernelGGL(pmx_seedl_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src.qbuf, src.qoff, src.q_bytes, row0, total,
+                           p.orients, p.first, p.rows_translated, p.max_qlen, src.table, p.code, s.codes);
+        if ((rc = pmx_launched())) return rc;
+        hipLaunchKernelGGL(pmx_seedl_count_kernel, cb, dim3(256), 0, stream, (const uint8_t *)s.codes, total, p.max_qlen, p.k, p.bits, src.keys, src.bucket,
+                           src.shift, p.max_occ, s.lo, s.cnt);
     }
+    if ((rc = pmx_launched())) return rc;
+    auto in = rocprim::make_transform_iterator((const uint32_t *)s.cnt, PmxWidenU32());
+    size_t tb = s.temp_bytes;
+    const hipError_t e = rocprim::exclusive_scan(s.temp, tb, in, s.moff, (int64_t)0, (size_t)(total + 1), rocprim::plus<int64_t>(), stream);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(pmx_seed_cut_kernel, dim3(1), dim3(1), 0, stream, (const int64_t *)s.moff, rows, p.row_slots, p.cap_m, s.cut);
+    return pmx_launched();
 }
 
-// pmx_seedl_hits_kernel for a translated index; a segment is a row (`stride` = max_qlen slots), m its letters, N = len(r).
-// CODON false: id = g * count + r; the letter window [lb, le) = [max(0, d_min - pad), min((N - g % 3) / 3, d_max + m + pad)) of frame g
-// as stored nucleotides, codon-aligned: [g % 3 + 3 lb, g % 3 + 3 le) on strand 0, [N - g % 3 - 3 le, N - g % 3 - 3 lb) on strand 1, so
-// the frame byte relative to the window is 0 or 3; reserved = g.  CODON true: id = s * count + r; the oriented window
-// [max(0, D_min - pad), min(N, D_max + 3 m + pad)), stored [lo, hi) or [N - hi, N - lo); byte = s; reserved = 0.
-template <bool CODON>
-__global__ void __launch_bounds__(256) pmx_seedt_hits_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ pos,
-                                                             long long m, const int64_t *__restrict__ moff, long long slots, long long stride,
-                                                             long long row0, long long count, int pad,
-                                                             const int64_t *__restrict__ qoff, const int64_t *__restrict__ roff,
-                                                             const int64_t *__restrict__ counts, long long capacity,
-                                                             pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_byte, pmx_seed_hit_t *__restrict__ hit_seeds)
+// Between emit and hits, whatever the geometry: the m matches of s.keys_a sorted per segment (`segs` segments of p.seg_slots position
+// slots each) into s.keys_b, head[x] = the head of x's cluster, flag[x + 1] - flag[x] = 1 where x closes a candidate (flag: m + 1 entries).
+static int pmx_seed_sort_clusters(const PmxSeedPlan &p, const PmxSeedSlice &s, long long m, long long segs, hipStream_t stream)
 {
-    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= m || pos[x + 1] == pos[x]) return;
-    const long long at = counts[0] + (long long)pos[x];
-    if (at >= capacity) return;
-    long long a = 0, z = slots - 1;             // the row of x: the last t with moff[t * stride] <= x (empty segments share a start)
-    while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= x) a = mid; else z = mid - 1; }
-    const long long row = row0 + a;
-    const uint32_t h = head[x];
-    const uint64_t kh = mkeys[h], kt = mkeys[x];
-    const long long id = (long long)(kt >> 32), dmin = pmx_seed_diag(kh), dmax = pmx_seed_diag(kt);
-    const long long o = id / count, r = id - o * count;         // o: the sequence frame g (CODON false), the strand (CODON true)
-    const long long len = qoff[row + 1] - qoff[row], N = roff[r + 1] - roff[r];
-    long long beg, end; int byte, res;
-    if (CODON) {
-        const long long wlo = max(0ll, dmin - pad), whi = min(N, dmax + 3 * len + pad);
-        beg = o ? N - whi : wlo; end = o ? N - wlo : whi;
-        byte = (int)o; res = 0;
-    } else {
-        const long long ph = o % 3, lb = max(0ll, dmin - pad), le = min((N - ph) / 3, dmax + len + pad);
-        beg = o >= 3 ? N - ph - 3 * le : ph + 3 * lb; end = o >= 3 ? N - ph - 3 * lb : ph + 3 * le;
-        byte = o >= 3 ? 3 : 0; res = (int)o;
-    }
-    pmx_pair_t pr; pr.q = row; pr.r = r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)beg; pr.r_len = (int32_t)(end - beg);
-    hit_pairs[at] = pr;
-    hit_byte[at] = (uint8_t)byte;
-    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = (int32_t)(x - h + 1); s.diag_min = (int32_t)dmin; s.diag_max = (int32_t)dmax; s.reserved = res; hit_seeds[at] = s; }
+    int rc = 0;
+    const unsigned mb = (unsigned)((m + 255) / 256);
+    auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{s.moff, p.seg_slots});
+    size_t tb = s.temp_bytes;
+    hipError_t e = rocprim::segmented_radix_sort_keys(s.temp, tb, (const uint64_t *)s.keys_a, s.keys_b, (unsigned)m, (unsigned)segs, seg, seg + 1, 0, p.key_bits,
+                                                      stream);
+    if (e != hipSuccess) return -(int)e;
+    if (hipMemsetAsync(s.flag, 0, sizeof(uint32_t) * (size_t)(m + 1), stream) != hipSuccess) return -1;
+    hipLaunchKernelGGL(pmx_seed_segstart_kernel, dim3((unsigned)((segs + 255) / 256)), dim3(256), 0, stream, (const int64_t *)s.moff, segs, p.seg_slots, s.flag);
+    if ((rc = pmx_launched())) return rc;
+    hipLaunchKernelGGL(pmx_seed_heads_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)s.keys_b, m, p.band, (const uint32_t *)s.flag, s.head);
+    if ((rc = pmx_launched())) return rc;
+    tb = s.temp_bytes;
+    e = rocprim::inclusive_scan(s.temp, tb, s.head, s.head, (size_t)m, PmxMaxU32(), stream);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL(pmx_seed_flags_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t *)s.head, m, p.min_seeds, s.flag);
+    if ((rc = pmx_launched())) return rc;
+    tb = s.temp_bytes;
+    e = rocprim::exclusive_scan(s.temp, tb, s.flag, s.flag, 0u, (size_t)(m + 1), rocprim::plus<uint32_t>(), stream);
+    return e == hipSuccess ? 0 : -(int)e;
 }
 
-// pmx_launch_seed_cluster for a translated index (the count pass before it: pmx_launch_seed_count_letters in letters mode);
-// count: the sequences of the indexed set; codon: PMX_SEED_REF_CODONS.
-int pmx_launch_seed_cluster_translated(long long row0, long long rows, bool codon, int max_qlen, long long count, long long m, int key_bits,
-                                       const uint32_t *lo, const uint32_t *cnt, const int64_t *moff, const uint64_t *vals,
-                                       uint64_t *mkeys_a, uint64_t *mkeys_b, uint32_t *head, uint32_t *flag, int band, int min_seeds, int pad,
-                                       const int64_t *qoff, const int64_t *roff, long long capacity,
-                                       pmx_pair_t *hit_pairs, uint8_t *hit_byte, pmx_seed_hit_t *hit_seeds, int64_t *row_off, int64_t *counts,
-                                       void *temp, size_t temp_bytes, hipStream_t stream)
+// The slice's `rows` rows (what the cut kept) with their m matches: emit, sort, clusters, outputs behind counts[0], then the slice's
+// row offsets and the running counts.  The geometry chooses the instantiation here and nowhere else; DNA is FRAMES with rows as they
+// stand, bit for bit.
+int pmx_launch_seed_cluster(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedOut &out, const PmxSeedSource &src, long long row0,
+                            long long rows, long long m, hipStream_t stream)
 {
-    const long long slots = rows, stride = max_qlen, total = slots * stride;
+    const long long segs = rows * p.segs, total = rows * p.row_slots;
     int rc = 0;
     if (m > 0) {
-        const dim3 eb((unsigned)((total + 255) / 256)), hb((unsigned)((m + 255) / 256));
-        if (codon) hipLaunchKernelGGL(pmx_seedt_emit_kernel<true>, eb, dim3(256), 0, stream, total, max_qlen, count, lo, cnt, moff, vals, mkeys_a);
-        else hipLaunchKernelGGL(pmx_seedt_emit_kernel<false>, eb, dim3(256), 0, stream, total, max_qlen, count, lo, cnt, moff, vals, mkeys_a);
+        decltype(&pmx_seed_emit_kernel<PMX_SEED_GEOM_FRAMES>) emit = nullptr;
+        decltype(&pmx_seed_hits_kernel<PMX_SEED_GEOM_FRAMES>) hits = nullptr;
+        switch (p.geom) {
+        case PMX_SEED_GEOM_DNA:
+        case PMX_SEED_GEOM_FRAMES:     emit = pmx_seed_emit_kernel<PMX_SEED_GEOM_FRAMES>;     hits = pmx_seed_hits_kernel<PMX_SEED_GEOM_FRAMES>; break;
+        case PMX_SEED_GEOM_CODONS:     emit = pmx_seed_emit_kernel<PMX_SEED_GEOM_CODONS>;     hits = pmx_seed_hits_kernel<PMX_SEED_GEOM_CODONS>; break;
+        case PMX_SEED_GEOM_REF_FRAMES: emit = pmx_seed_emit_kernel<PMX_SEED_GEOM_REF_FRAMES>; hits = pmx_seed_hits_kernel<PMX_SEED_GEOM_REF_FRAMES>; break;
+        case PMX_SEED_GEOM_REF_CODONS: emit = pmx_seed_emit_kernel<PMX_SEED_GEOM_REF_CODONS>; hits = pmx_seed_hits_kernel<PMX_SEED_GEOM_REF_CODONS>; break;
+        default: return -1;
+        }
+        hipLaunchKernelGGL(emit, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, p.max_qlen, p.ref_count, (const uint32_t *)s.lo,
+                           (const uint32_t *)s.cnt, (const int64_t *)s.moff, src.vals, s.keys_a);
         if ((rc = pmx_launched())) return rc;
-        if ((rc = pmx_seed_sort_clusters(m, slots, stride, key_bits, moff, mkeys_a, mkeys_b, head, flag, band, min_seeds, temp, temp_bytes, stream))) return rc;
-        if (capacity > 0) {
-            if (codon)
-                hipLaunchKernelGGL(pmx_seedt_hits_kernel<true>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
-                                   m, moff, slots, stride, row0, count, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte, hit_seeds);
-            else
-                hipLaunchKernelGGL(pmx_seedt_hits_kernel<false>, hb, dim3(256), 0, stream, (const uint64_t *)mkeys_b, (const uint32_t *)head, (const uint32_t *)flag,
-                                   m, moff, slots, stride, row0, count, pad, qoff, roff, (const int64_t *)counts, capacity, hit_pairs, hit_byte, hit_seeds);
+        if ((rc = pmx_seed_sort_clusters(p, s, m, segs, stream))) return rc;
+        if (out.capacity > 0) {
+            const PmxSeedWindowArgs g = {row0, p.segs, p.first, p.rows_translated, p.ref_count, p.pad, src.qoff, src.roff};
+            hipLaunchKernelGGL(hits, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, (const uint64_t *)s.keys_b, (const uint32_t *)s.head,
+                               (const uint32_t *)s.flag, m, (const int64_t *)s.moff, segs, p.seg_slots, g, (const int64_t *)out.counts, out.capacity,
+                               out.pairs, out.byte, out.seeds);
             if ((rc = pmx_launched())) return rc;
         }
     }
-    return pmx_seed_finish(rows, stride, m, moff, flag, capacity, row_off, counts, stream);
+    const uint32_t *pos = m > 0 ? s.flag : nullptr;
+    hipLaunchKernelGGL(pmx_seed_rowoff_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pos, (const int64_t *)s.moff, rows, p.row_slots,
+                       (const int64_t *)out.counts, out.row_off);
+    if ((rc = pmx_launched())) return rc;
+    hipLaunchKernelGGL(pmx_seed_advance_kernel, dim3(1), dim3(1), 0, stream, pos, m, out.capacity, out.counts);
+    return pmx_launched();
 }
+
