@@ -1509,6 +1509,89 @@ int pmx_seed_pairs_translated_ref_device(const pmx_seqset_t *Q, const pmx_seed_i
 int pmx_seed_pairs_translated_ref(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq,
                                   const pmx_seed_opts_t *opts, int ref_mode, pmx_seed_hits_t **result);
 
+/* Ungapped diagonal filter (extension): the stage between a seeding entry and a gapped extension -- the best ungapped local score along
+ * the seeded diagonals of every candidate, a score threshold and the best top_n candidates per query row, all on the device (DESIGN
+ * 2.5s; kernels: parasail-rs_amd/csrc/pmx_ungap.hip).  A filtered list is again a candidate list: it goes unchanged wherever the
+ * unfiltered one goes.
+ *
+ * A candidate is what the seeding entries write: a descriptor {q, r, q_beg, q_len, r_beg, r_len}, one byte and a seed record {n_seeds,
+ * diag_min, diag_max, reserved}.  byte_kind says what the byte is:
+ *   PMX_SEED_BYTE_STRAND   a strand, the _ex entries' rule (d_byte NULL: all forward).  The lists of pmx_seed_pairs[_device], and of
+ *                          pmx_seed_pairs_letters[_device] with PMX_SEED_QUERY_LETTERS, whose byte is 0.  `code` is not read.
+ *   PMX_SEED_BYTE_FRAME    a frame 0 .. 5 of the query (d_byte NULL: all frame 0), translated with `code` (64 letters or NULL, the
+ *                          standard code).  The lists of pmx_seed_pairs_letters[_device] in a frame mode.  max_qlen bounds the letters
+ *                          of a translation, as in pmx_gather_pairs_translated_device.
+ * Let x[0 .. L) be the oriented query window, exactly what pmx_gather_pairs_device (STRAND) or pmx_gather_pairs_translated_device
+ * (FRAME) writes for the pair, and y the reference window [r_beg, r_beg + r_len) as gathered.  Diagonals are in the seeds' coordinates:
+ * d = j - i, j a position in the WHOLE reference sequence, i a position in x.  Cell (i, j) exists iff 0 <= i < L and r_beg <= j <
+ * r_beg + r_len, and scores w = matrix[mapper[x[i]]][mapper[y[j - r_beg]]], the alignment kernels' rule for the same cfg->matrix (of
+ * cfg only the matrix is read besides the usual checks).  For each d in [diag_min, diag_max], along the diagonal's existing cells in
+ * ascending i: h(d, i) = max(0, h(d, i - 1) + w), h = 0 in front of the first cell.  The ungapped score is U = max h over all those
+ * cells, exact in int32.  The record:
+ *   U > 0           {U, d, i, i + d}: among the cells with h = U the lowest d, then the lowest i (end_ref is relative to the whole reference)
+ *   no positive h   {0, diag_min, -1, -1} (also when no cell exists)
+ *   bad candidate   {-1, 0, -1, -1}: a bad descriptor under the gather's own validity rule (with PMX_SEED_BYTE_FRAME also a frame that
+ *                   holds no codon), a byte outside its kind's range, or diag_min > diag_max
+ *
+ * pmx_seed_ungapped[_device]: the records of n listed candidates and nothing else.  The device entry is ASYNCHRONOUS on `stream` (n is
+ * known on the host); a call that needs more thread scratch than any before it allocates, which synchronises.  opts: chunk_pairs as
+ * in the set batches; it never changes a byte.
+ *
+ * pmx_seed_filter[_device]: the selection over a CSR list -- d_row_off holds nq + 1 offsets and the caller passes the COMPLETE list, n =
+ * row_off[nq].  A candidate passes iff score >= max(min_score, 0) (a bad candidate never does).  With top_n > 0 only the top_n best
+ * passing candidates of a row are kept: by score descending, then position in the row ascending.  Kept candidates leave in their input
+ * order, so the output is again ascending in (byte, r, diag_min) per row and a valid input of every entry that takes the unfiltered
+ * list.  Per kept candidate: descriptor, byte, seed record, ungapped record and `source`, its index in the input list (each output
+ * optional).  d_out_row_off receives nq + 1 offsets, uncapped and always written in full; `capacity` and d_counts = [kept, written]
+ * follow pmx_seed_pairs_device: only positions below capacity are written, entries behind them are untouched, capacity == 0 counts
+ * only.  No atomic decides an output position: ranks come from one segmented sort of (score descending, position) keys per row,
+ * positions from one scan of the keep flags in input order, so the output is bit-identical from run to run and under any chunk_pairs.
+ * The device entry is asynchronous on `stream` like the one above.  Offsets that are not those of the list (not ascending, outside
+ * 0 .. n) give an unspecified selection but no access outside the arrays.
+ *
+ * Thread scratch on the device: the chunk buffers of the _ex entries (two sets of at most 256 MiB of packed windows and 34 bytes per
+ * slot), and for the filter 16 bytes per candidate of records, 16 of sort keys with top_n > 0, 4 of flags and rocPRIM's temporary
+ * storage.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: a NULL set, configuration, matrix, d_pairs, d_seeds or record
+ * output with n > 0; negative n, nq, capacity or chunk_pairs; max_qlen or max_rlen below 1; a PSSM; an unknown byte_kind; max |w| x
+ * max_qlen >= 2^31; sets of another device than the current one; for the filter also NULL opts, top_n < 0, min_score < 0, non-zero
+ * reserved fields, NULL d_row_off, d_out_row_off or d_counts, and n above 2^31 - 1.  n == 0 succeeds: zero counts and nq + 1 zero offsets.
+ *
+ * Out of scope, and the C entries cannot tell: the lists of the codon modes (PMX_SEED_CODONS_*) and of a translated index
+ * (pmx_seed_pairs_translated_ref).  Their diagonals are in nucleotides over three frames or belong to frames of the reference; passing
+ * them here scores other cells than the seeds'.
+ *
+ * The host entries run the device entries on a stream of their own over uploaded arrays.  pmx_seed_filter takes a pmx_seed_hits_t and
+ * returns one callee-allocated block released with pmx_seed_filtered_free: hits is a pmx_seed_hits_t of the kept candidates (n_passing
+ * = n_hits = kept), ungapped and source hold n_hits entries.  It refuses a list that max_hits cut (n_hits < n_passing): the selection
+ * needs every row in full. */
+#define PMX_SEED_BYTE_STRAND 0
+#define PMX_SEED_BYTE_FRAME  1
+typedef struct pmx_ungapped { int32_t score, diag, end_query, end_ref; } pmx_ungapped_t;   /* 16 bytes */
+typedef struct pmx_seed_filter_opts { int32_t min_score, top_n, reserved[2]; } pmx_seed_filter_opts_t;   /* 16 bytes; top_n 0: no limit */
+int pmx_seed_ungapped_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                             const pmx_pair_t *d_pairs, const uint8_t *d_byte /* or NULL */, int byte_kind, const uint8_t *code,
+                             const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                             pmx_ungapped_t *d_out /* n */, void *stream, const pmx_pairs_opts_t *opts);
+int pmx_seed_ungapped(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                      const pmx_pair_t *pairs, const uint8_t *byte /* or NULL */, int byte_kind, const uint8_t *code,
+                      const pmx_seed_hit_t *seeds, pmx_ungapped_t *out /* n */, const pmx_pairs_opts_t *opts);
+int pmx_seed_filter_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                           const pmx_pair_t *d_pairs, const uint8_t *d_byte /* or NULL */, int byte_kind, const uint8_t *code,
+                           const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                           int64_t nq, const int64_t *d_row_off /* nq + 1 */, const pmx_seed_filter_opts_t *fopts,
+                           pmx_pair_t *d_out_pairs, uint8_t *d_out_byte, pmx_seed_hit_t *d_out_seeds, pmx_ungapped_t *d_out_ungapped,
+                           int64_t *d_out_source, int64_t capacity, int64_t *d_out_row_off /* nq + 1 */,
+                           int64_t *d_counts /* [0] kept, [1] written */, void *stream, const pmx_pairs_opts_t *opts);
+typedef struct pmx_seed_filtered { pmx_seed_hits_t hits; pmx_ungapped_t *ungapped; int64_t *source; } pmx_seed_filtered_t;
+int  pmx_seed_filter(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, const pmx_seed_hits_t *hits,
+                     int byte_kind, const uint8_t *code, const pmx_seed_filter_opts_t *fopts, const pmx_pairs_opts_t *opts,
+                     pmx_seed_filtered_t **result);
+void pmx_seed_filtered_free(pmx_seed_filtered_t *result);
+/* Test hook: the hot kernel's lanes per candidate and cells per lane step. */
+void pmx_seed_ungapped_shape(int32_t *lanes, int32_t *step);
+
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).
  * This entry keeps tile boundaries only: the long-pair sweep (the bands of a pair spread across the chip) stores the row it hands from

@@ -136,7 +136,21 @@ class pmx_seed_hits_t(C.Structure):
                 ("pairs", C.c_void_p), ("strand", C.c_void_p), ("seeds", C.c_void_p)]
 
 
+class pmx_ungapped_t(C.Structure):
+    _fields_ = [("score", C.c_int32), ("diag", C.c_int32), ("end_query", C.c_int32), ("end_ref", C.c_int32)]
+
+
+class pmx_seed_filter_opts_t(C.Structure):
+    _fields_ = [("min_score", C.c_int32), ("top_n", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class pmx_seed_filtered_t(C.Structure):
+    _fields_ = [("hits", pmx_seed_hits_t), ("ungapped", C.c_void_p), ("source", C.c_void_p)]
+
+
 SEED_HIT_DTYPE = np.dtype([("n_seeds", "<i4"), ("diag_min", "<i4"), ("diag_max", "<i4"), ("reserved", "<i4")])
+UNGAPPED_DTYPE = np.dtype([("score", "<i4"), ("diag", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4")])
+SEED_BYTE_STRAND, SEED_BYTE_FRAME = 0, 1
 TOPK_MAX = 1024
 INT32_MIN = -(1 << 31)
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
@@ -317,6 +331,17 @@ _sig("pmx_seed_pairs_translated_ref_device", C.c_int, C.c_void_p, C.c_void_p, C.
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_seed_pairs_translated_ref", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(pmx_seed_opts_t), C.c_int,
      C.POINTER(C.POINTER(pmx_seed_hits_t)))
+_sig("pmx_seed_ungapped_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_seed_ungapped", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_seed_filter_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(pmx_seed_filter_opts_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_seed_filter", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.POINTER(pmx_seed_hits_t), C.c_int, C.c_void_p,
+     C.POINTER(pmx_seed_filter_opts_t), C.POINTER(pmx_pairs_opts_t), C.POINTER(C.POINTER(pmx_seed_filtered_t)))
+_sig("pmx_seed_filtered_free", None, C.POINTER(pmx_seed_filtered_t))
+_sig("pmx_seed_ungapped_shape", None, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 _sig("pmx_topk_records_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("pmx_align_pairs_both", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1930,9 +1955,13 @@ class SeedHits:
     diag_min) order; row(i) slices out those that were stored.  Of a letters index (seed_pairs(frames=)) the byte per candidate
     is a frame in the frame modes -- .frame holds it, else .frame is None -- and a strand in the codon modes -- .strand holds it;
     .strand is zeros in the letters and frame modes.  Of a translated index (seed_pairs(ref_frames=)) .frame holds the byte with
-    "frames" (0 or 3, relative to the window; seeds["reserved"] is the sequence frame) and .strand holds it with "codons"."""
+    "frames" (0 or 3, relative to the window; seeds["reserved"] is the sequence frame) and .strand holds it with "codons".
+    kind says which list this is: "strand" (a DNA index), "letters", "frame" or "codons" (a letters index), "ref_frames" or
+    "ref_codons" (a translated index); seed_filter reads it.  A list that seed_filter returns has .ungapped (UNGAPPED_DTYPE) and
+    .source (int64: the candidate's index in the list that was filtered) as well."""
 
-    def __init__(self, r, byte_is_frame=False):
+    def __init__(self, r, byte_is_frame=False, kind=None):
+        self.kind = kind
         h, n = int(r.n_hits), int(r.n_rows)
         self.n_rows, self.n_hits, self.n_passing = n, h, int(r.n_passing)
 
@@ -2018,6 +2047,17 @@ def _seed_entry(index, strand, frames, code, ref_frames, min_seeds, band, pad, m
     return lib.pmx_seed_pairs_letters, lib.pmx_seed_pairs_letters_device, opts, extra, 0 <= mode <= FRAMES_ALL, code
 
 
+def _seed_kind(index, frames, ref_frames):
+    """The SeedHits.kind of a seed_pairs call whose arguments _seed_entry has accepted."""
+    if getattr(index, "translated", False):
+        return "ref_frames" if ref_frames == "frames" else "ref_codons"
+    if not index.letters:
+        return "strand"
+    if isinstance(frames, str) and frames.startswith("codons"):
+        return "codons"
+    return "letters" if isinstance(frames, str) and frames == "letters" else "frame"
+
+
 def seed_pairs(Q, index, strand=None, min_seeds=2, band=8, pad=16, max_occ=64, first_row=0, rows=None, max_hits=0, slice_rows=0,
                frames=None, code=None, ref_frames=None):
     """Candidate windows of the queries Q[first_row : first_row + rows] in the indexed reference: exact k-mer matches, clustered
@@ -2037,7 +2077,7 @@ def seed_pairs(Q, index, strand=None, min_seeds=2, band=8, pad=16, max_occ=64, f
     if host(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), *extra, C.byref(res)):
         raise BatchError(lib.pmx_last_error().decode())
     try:
-        return SeedHits(res.contents, byte_is_frame=byte_is_frame)
+        return SeedHits(res.contents, byte_is_frame=byte_is_frame, kind=_seed_kind(index, frames, ref_frames))
     finally:
         lib.pmx_seed_hits_free(res)
 
@@ -2051,6 +2091,121 @@ def seed_pairs_device(Q, index, q_first, nq, max_qlen, d_hit_pairs, d_hit_strand
     _, device, opts, extra, _, _keep = _seed_entry(index, strand, frames, code, ref_frames, min_seeds, band, pad, max_occ, 0, slice_rows)
     if device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), *extra, d_hit_pairs, d_hit_strand, d_hit_seeds,
               int(capacity), d_row_off, d_counts, stream):
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def ungapped_shape():
+    """(lanes per candidate, cells per lane step) of the ungapped filter's kernel (test hook)."""
+    g, st = C.c_int32(), C.c_int32()
+    lib.pmx_seed_ungapped_shape(C.byref(g), C.byref(st))
+    return int(g.value), int(st.value)
+
+
+def _ungapped_config(matrix):
+    """The configuration the ungapped entries read: the matrix, nothing else."""
+    if not isinstance(matrix, Matrix):
+        raise BatchError("matrix: a Matrix")
+    return pmx_config_t(MODE_SW, 0, 0, 0, 0, 0, matrix.inner)
+
+
+def _ungapped_kind(kind):
+    if kind not in ("strand", "frame"):
+        raise BatchError("kind is \"strand\" or \"frame\"")
+    return SEED_BYTE_FRAME if kind == "frame" else SEED_BYTE_STRAND
+
+
+def seed_ungapped(Q, R, pairs, byte, seeds, matrix, kind="strand", code=None, chunk_pairs=0):
+    """The ungapped score of listed candidates (UNGAPPED_DTYPE: score, diag, end_query, end_ref): the best run of matches and
+    mismatches under `matrix` along the diagonals seeds["diag_min"] .. seeds["diag_max"] of each pair's windows.  byte: a strand
+    per candidate (kind "strand"; None: all forward) or a frame 0 .. 5 of the query (kind "frame", with code).  A candidate
+    without a positive cell gets (0, diag_min, -1, -1), a bad one (-1, 0, -1, -1)."""
+    cfg = _ungapped_config(matrix)
+    bk = _ungapped_kind(kind)
+    pairs = as_pairs(pairs)
+    n = len(pairs)
+    seeds = np.ascontiguousarray(seeds, dtype=SEED_HIT_DTYPE)
+    if len(seeds) != n:
+        raise BatchError("seeds and pairs differ in count")
+    if byte is not None:
+        byte = np.ascontiguousarray(byte, dtype=np.uint8)
+        if len(byte) != n:
+            raise BatchError("byte and pairs differ in count")
+    code = _code_arg(code)
+    out = np.zeros(n, dtype=UNGAPPED_DTYPE)
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    if lib.pmx_seed_ungapped(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, byte.ctypes.data if byte is not None else None, bk,
+                             code.ctypes.data if code is not None else None, seeds.ctypes.data, out.ctypes.data, C.byref(opts)):
+        raise BatchError(lib.pmx_last_error().decode())
+    return out
+
+
+def seed_ungapped_device(Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, d_out, kind="strand", code=None, stream=0, chunk_pairs=0):
+    """Device-pointer entry of seed_ungapped: n records into d_out; asynchronous on `stream`."""
+    cfg = _ungapped_config(matrix)
+    code = _code_arg(code)
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    if lib.pmx_seed_ungapped_device(C.byref(cfg), Q._handle(), R._handle(), int(n), d_pairs, d_byte, _ungapped_kind(kind),
+                                    code.ctypes.data if code is not None else None, d_seeds, int(max_qlen), int(max_rlen), d_out, stream,
+                                    C.byref(opts)):
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+_SEED_FILTER_KINDS = {"strand": "strand", "letters": "strand", "frame": "frame"}
+
+
+def seed_filter(Q, R, hits, matrix, min_score=0, top_n=0, code=None, chunk_pairs=0):
+    """The candidates of a seed_pairs result that are worth a gapped extension: every candidate gets its ungapped score
+    (seed_ungapped), one below max(min_score, 0) is dropped, and with top_n > 0 only the top_n best of a query row stay (score
+    descending, then position).  Returns a SeedHits of the kept candidates in their input order -- pairs / strand / frame go into
+    Aligner.align_pairs as those of `hits` would -- with .ungapped and .source added.  hits.kind chooses the byte's meaning; the
+    lists of the codon modes and of a translated index ("codons", "ref_frames", "ref_codons") are refused."""
+    kind = hits.kind if getattr(hits, "kind", None) is not None else ("frame" if hits.frame is not None else "strand")
+    if kind not in _SEED_FILTER_KINDS:
+        raise BatchError("seed_filter does not take a list of kind \"%s\": its diagonals are not letter diagonals of one query frame "
+                         "(supported: \"strand\", \"letters\", \"frame\")" % kind)
+    cfg = _ungapped_config(matrix)
+    byte_kind = _SEED_FILTER_KINDS[kind]
+    byte = np.ascontiguousarray(hits.frame if byte_kind == "frame" else hits.strand, dtype=np.uint8)
+    pairs = np.ascontiguousarray(hits.pairs, dtype=PAIR_DTYPE)
+    seeds = np.ascontiguousarray(hits.seeds, dtype=SEED_HIT_DTYPE)
+    row_off = np.ascontiguousarray(hits.row_off, dtype=np.int64)
+    n = len(pairs)
+    if len(byte) != n or len(seeds) != n or len(row_off) != hits.n_rows + 1:
+        raise BatchError("the arrays of hits differ in length")
+    h = pmx_seed_hits_t(int(hits.n_rows), n, int(hits.n_passing), row_off.ctypes.data, pairs.ctypes.data if n else None,
+                        byte.ctypes.data if n else None, seeds.ctypes.data if n else None)
+    code = _code_arg(code)
+    fopts = pmx_seed_filter_opts_t(int(min_score), int(top_n))
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    res = C.POINTER(pmx_seed_filtered_t)()
+    if lib.pmx_seed_filter(C.byref(cfg), Q._handle(), R._handle(), C.byref(h), _ungapped_kind(byte_kind),
+                           code.ctypes.data if code is not None else None, C.byref(fopts), C.byref(opts), C.byref(res)):
+        raise BatchError(lib.pmx_last_error().decode())
+    try:
+        r = res.contents
+        out = SeedHits(r.hits, byte_is_frame=byte_kind == "frame", kind=kind)
+        k = out.n_hits
+        out.ungapped = (np.frombuffer(C.string_at(r.ungapped, k * UNGAPPED_DTYPE.itemsize), dtype=UNGAPPED_DTYPE).copy() if k
+                        else np.zeros(0, dtype=UNGAPPED_DTYPE))
+        out.source = np.frombuffer(C.string_at(r.source, k * 8), dtype=np.int64).copy() if k else np.zeros(0, dtype=np.int64)
+        return out
+    finally:
+        lib.pmx_seed_filtered_free(res)
+
+
+def seed_filter_device(Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, nq, d_row_off, d_out_pairs, d_out_byte, d_out_seeds,
+                       d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts, kind="strand", code=None, min_score=0, top_n=0,
+                       stream=0, chunk_pairs=0):
+    """Device-pointer entry of seed_filter over the complete list of nq rows (n = row_off[nq]): the kept candidates' columns (each
+    optional, `capacity` entries), d_out_row_off gets nq + 1 offsets and d_counts [kept, written].  Asynchronous on `stream`."""
+    cfg = _ungapped_config(matrix)
+    code = _code_arg(code)
+    fopts = pmx_seed_filter_opts_t(int(min_score), int(top_n))
+    opts = pmx_pairs_opts_t(int(chunk_pairs))
+    if lib.pmx_seed_filter_device(C.byref(cfg), Q._handle(), R._handle(), int(n), d_pairs, d_byte, _ungapped_kind(kind),
+                                  code.ctypes.data if code is not None else None, d_seeds, int(max_qlen), int(max_rlen), int(nq), d_row_off,
+                                  C.byref(fopts), d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source, int(capacity),
+                                  d_out_row_off, d_counts, stream, C.byref(opts)):
         raise BatchError(lib.pmx_last_error().decode())
 
 

@@ -1382,7 +1382,9 @@ enum { SCR_BOUND = 0, SCR_TRACE = 1, SCR_OPS = 2, SCR_SORT = 3, SCR_RETRY = 4,
        SCR_FSWIN = 30,                                                                   // windowed frameshift traceback: a chunk's first-pass records and strands, narrowed descriptors, shifts, lengths, the violation count
        SCR_SEED = 31,                                                                    // k-mer seeding: a slice's position slots, match buffers, cluster flags, cut, rocPRIM scratch (pmx_seed.hip)
        SCR_SEEDHIT = 32,                                                                 // k-mer seeding, host entry: counts, row offsets, the candidates' columns
-       SCR_SLOTS = 33 };
+       SCR_UNGAP = 33,                                                                   // ungapped filter: the list's records, sort keys, keep flags, rocPRIM scratch (pmx_ungap.hip)
+       SCR_UNGAPHIT = 34,                                                                // ungapped filter, host entries: the uploaded list, the kept candidates' columns, counts
+       SCR_SLOTS = 35 };
 static thread_local Scratch g_scratch_pool[SCR_SLOTS];
 static int scratch_reserve(size_t bytes, void **out, int slot = SCR_BOUND)
 {
@@ -6306,4 +6308,257 @@ extern "C" int pmx_seed_pairs_translated_ref(const pmx_seqset_t *Q, const pmx_se
                                              int ref_mode, pmx_seed_hits_t **result)
 {
     return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_KIND_TRANSLATED, ref_mode, nullptr, result);
+}
+
+// ---- the ungapped diagonal filter: pmx_seed_ungapped[_device], pmx_seed_filter[_device] ----
+extern "C" void pmx_seed_ungapped_shape(int32_t *lanes, int32_t *step)
+{
+    if (lanes) *lanes = PMX_UNGAP_LANES;
+    if (step) *step = PMX_UNGAP_STEP;
+}
+
+// What the four entries refuse about the list, the configuration and the byte's kind before any GPU work.  out: the record output
+// where the entry needs one.  *plan: the run's slots -- one per candidate, on the strand or in the frame of its byte.
+static int ungap_list_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const void *pairs, const void *seeds,
+                            const void *out, bool need_out, const uint8_t *d_byte, int byte_kind, const uint8_t *code, const pmx_pairs_opts_t *opts,
+                            SlotPlan *plan)
+{
+    if (!Q || !R) { set_err("null sequence set"); return -1; }
+    if (n < 0) { set_err("negative n"); return -1; }
+    if (n > 0 && (!pairs || (need_out && !out))) { set_err("null pairs or records"); return -1; }
+    if (n > 0 && !seeds) { set_err("null seed records: the diagonals of a candidate are in its pmx_seed_hit_t"); return -1; }
+    if (opts && opts->chunk_pairs < 0) { set_err("chunk_pairs must not be negative"); return -1; }
+    if (check_cfg(cfg)) return -1;
+    if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {
+        set_err("the ungapped filter takes no PSSM matrix: a profile belongs to one query, a candidate list has many"); return -1;
+    }
+    if (byte_kind != PMX_SEED_BYTE_STRAND && byte_kind != PMX_SEED_BYTE_FRAME) {
+        set_err("unknown byte_kind %d (PMX_SEED_BYTE_STRAND 0, PMX_SEED_BYTE_FRAME 1)", byte_kind); return -1;
+    }
+    if (byte_kind == PMX_SEED_BYTE_FRAME) { plan->kind = SlotPlan::FRAMES; plan->set_code(code); }
+    else plan->kind = SlotPlan::BYTES;
+    plan->d_byte = d_byte;
+    return 0;
+}
+// ... about the maxima: an ungapped score is a sum of at most max_qlen cells and has to be exact in int32
+static int ungap_lens_check(const pmx_config_t *cfg, int32_t max_qlen, int32_t max_rlen)
+{
+    if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
+    const int64_t w = std::max<int64_t>(std::abs((int64_t)cfg->matrix->min), std::abs((int64_t)cfg->matrix->max));
+    if (w * (int64_t)max_qlen >= ((int64_t)1 << 31)) {
+        set_err("max |w| x max_qlen = %lld x %d does not fit int32: the ungapped score would not be exact", (long long)w, (int)max_qlen); return -1;
+    }
+    return 0;
+}
+// ... about the selection
+static int ungap_filter_check(int64_t n, int64_t nq, const void *row_off, const pmx_seed_filter_opts_t *fopts, int64_t capacity, const void *out_row_off,
+                              const void *counts)
+{
+    if (!fopts) { set_err("null filter opts"); return -1; }
+    if (fopts->top_n < 0) { set_err("top_n %d is negative (0: no limit)", (int)fopts->top_n); return -1; }
+    if (fopts->min_score < 0) { set_err("min_score %d is negative: a candidate passes from score 0 on", (int)fopts->min_score); return -1; }
+    if (fopts->reserved[0] || fopts->reserved[1]) { set_err("reserved must be 0"); return -1; }
+    if (nq < 0 || capacity < 0) { set_err("negative nq or capacity"); return -1; }
+    if (!row_off || !out_row_off) { set_err("null row offsets"); return -1; }
+    if (!counts) { set_err("null counts"); return -1; }
+    if (n > 0 && nq == 0) { set_err("%lld candidates in no row: the list is the rows' (n = row_off[nq])", (long long)n); return -1; }
+    if (n > INT32_MAX || nq > INT32_MAX) { set_err("a list of %lld candidates in %lld rows is beyond 2^31 - 1: filter it in parts of whole rows", (long long)n, (long long)nq); return -1; }
+    return 0;
+}
+static int ungap_device_check(const pmx_seqset *Q, const pmx_seqset *R)
+{
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (Q->dev != dev || R->dev != dev) {
+        set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev != dev ? Q->dev : R->dev, dev); return -1;
+    }
+    return 0;
+}
+
+// The records of the n > 0 candidates behind the checks: every chunk of the set batches' pipeline through pmx_ungapped_kernel.
+// Asynchronous on `st`.
+static int ungap_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, const SlotPlan &plan,
+                     const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen, pmx_ungapped_t *d_out, hipStream_t st, const pmx_pairs_opts_t *opts)
+{
+    DevMat dm;
+    if (get_devmat(cfg->matrix, &dm)) return -1;
+    return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, plan, max_qlen, max_rlen, st, pairs_chunk(n, max_qlen, max_rlen, opts),
+        [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
+            const int rc = pmx_launch_ungapped(cn, b.q, b.qoff, b.r, b.roff, b.ok, d_pairs + c0, d_seeds + c0, dm.d, d_out + c0, st);
+            if (rc) { set_err("ungapped filter launch failed (%d)", rc); return rc < 0 ? rc : -1; }
+            g_last_kernel = "pmx_ungapped_kernel";
+            return 0;
+        });
+}
+
+extern "C" int pmx_seed_ungapped_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                        const pmx_pair_t *d_pairs, const uint8_t *d_byte, int byte_kind, const uint8_t *code,
+                                        const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                                        pmx_ungapped_t *d_out, void *stream, const pmx_pairs_opts_t *opts)
+{
+    SlotPlan plan;
+    if (ungap_list_check(cfg, Q, R, n, d_pairs, d_seeds, d_out, true, d_byte, byte_kind, code, opts, &plan) || ungap_lens_check(cfg, max_qlen, max_rlen)) return -1;
+    if (n == 0) return 0;
+    if (ungap_device_check(Q, R)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    return ungap_run(cfg, Q, R, n, d_pairs, plan, d_seeds, max_qlen, max_rlen, d_out, (hipStream_t)stream, opts);
+}
+
+// The selection behind the checks; d_byte: the list's bytes as the caller gave them (may be NULL).  Asynchronous on `st`.
+struct UngapFilterOut { pmx_pair_t *pairs; uint8_t *byte; pmx_seed_hit_t *seeds; pmx_ungapped_t *ungapped; int64_t *source; int64_t capacity, *row_off, *counts; };
+static int ungap_filter_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, const SlotPlan &plan,
+                            const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen, int64_t nq, const int64_t *d_row_off,
+                            const pmx_seed_filter_opts_t &f, const UngapFilterOut &o, hipStream_t st, const pmx_pairs_opts_t *opts)
+{
+    if (n == 0) {
+        HIP_OR_RET(hipMemsetAsync(o.row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st));
+        HIP_OR_RET(hipMemsetAsync(o.counts, 0, 2 * sizeof(int64_t), st));
+        return 0;
+    }
+    pmx_ungapped_t *ung = nullptr; uint64_t *ka = nullptr, *kb = nullptr; uint32_t *flag = nullptr; void *temp = nullptr;
+    const size_t temp_bytes = pmx_ungap_select_temp_bytes(n, nq);
+    if (scratch_carve(SCR_UNGAP, [&](Carver &c) {
+            ung = c.take<pmx_ungapped_t>((size_t)n); flag = c.take<uint32_t>((size_t)n + 1);
+            if (f.top_n > 0) { ka = c.take<uint64_t>((size_t)n); kb = c.take<uint64_t>((size_t)n); }
+            temp = c.take<unsigned char>(temp_bytes);
+        })) return -1;
+    int rc = ungap_run(cfg, Q, R, n, d_pairs, plan, d_seeds, max_qlen, max_rlen, ung, st, opts);
+    if (rc) return rc;
+    rc = pmx_launch_ungap_select(ung, n, d_row_off, nq, f.min_score, f.top_n, d_pairs, plan.d_byte, d_seeds, ka, kb, flag, temp, temp_bytes,
+                                 o.pairs, o.byte, o.seeds, o.ungapped, o.source, o.capacity, o.row_off, o.counts, st);
+    if (rc) set_err("ungapped selection failed (%d)", rc);
+    return rc;
+}
+
+extern "C" int pmx_seed_filter_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                      const pmx_pair_t *d_pairs, const uint8_t *d_byte, int byte_kind, const uint8_t *code,
+                                      const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                                      int64_t nq, const int64_t *d_row_off, const pmx_seed_filter_opts_t *fopts,
+                                      pmx_pair_t *d_out_pairs, uint8_t *d_out_byte, pmx_seed_hit_t *d_out_seeds, pmx_ungapped_t *d_out_ungapped,
+                                      int64_t *d_out_source, int64_t capacity, int64_t *d_out_row_off, int64_t *d_counts, void *stream,
+                                      const pmx_pairs_opts_t *opts)
+{
+    SlotPlan plan;
+    if (ungap_list_check(cfg, Q, R, n, d_pairs, d_seeds, nullptr, false, d_byte, byte_kind, code, opts, &plan) || ungap_lens_check(cfg, max_qlen, max_rlen) ||
+        ungap_filter_check(n, nq, d_row_off, fopts, capacity, d_out_row_off, d_counts) || ungap_device_check(Q, R)) return -1;
+    StreamGuard guard(stream);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    const UngapFilterOut o = {d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts};
+    return ungap_filter_run(cfg, Q, R, n, d_pairs, plan, d_seeds, max_qlen, max_rlen, nq, d_row_off, *fopts, o, (hipStream_t)stream, opts);
+}
+
+// The host entries' maxima: the longest good windows of the uploaded list, found on the device (a bad descriptor counts for nothing);
+// with frames the letters of the longest translation.
+static int ungap_host_lens(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, const pmx_pair_t *d_pairs, int64_t n, const SlotPlan &plan,
+                           int32_t *mq, int32_t *mr, hipStream_t st)
+{
+    if (device_maxlens(Q, R, d_pairs, n, mq, mr, st)) return -1;
+    plan.to_letters(mq, mr);
+    return ungap_lens_check(cfg, *mq, *mr);
+}
+
+extern "C" int pmx_seed_ungapped(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                 const pmx_pair_t *pairs, const uint8_t *byte, int byte_kind, const uint8_t *code,
+                                 const pmx_seed_hit_t *seeds, pmx_ungapped_t *out, const pmx_pairs_opts_t *opts)
+{
+    SlotPlan plan;
+    if (ungap_list_check(cfg, Q, R, n, pairs, seeds, out, true, byte, byte_kind, code, opts, &plan)) return -1;
+    if (n == 0) return 0;
+    if (ungap_device_check(Q, R)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    StreamGuard guard(st);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    pmx_pair_t *dp = nullptr; pmx_seed_hit_t *ds = nullptr; uint8_t *db = nullptr; pmx_ungapped_t *du = nullptr;
+    if (scratch_carve(SCR_UNGAPHIT, [&](Carver &c) {
+            dp = c.take<pmx_pair_t>((size_t)n); ds = c.take<pmx_seed_hit_t>((size_t)n); db = c.take<uint8_t>((size_t)n); du = c.take<pmx_ungapped_t>((size_t)n);
+        })) return -1;
+    HIP_OR_RET(hipMemcpyAsync(dp, pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_OR_RET(hipMemcpyAsync(ds, seeds, sizeof(pmx_seed_hit_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (byte) { HIP_OR_RET(hipMemcpyAsync(db, byte, (size_t)n, hipMemcpyHostToDevice, st)); plan.d_byte = db; }
+    int32_t mq = 1, mr = 1;
+    if (ungap_host_lens(cfg, Q, R, dp, n, plan, &mq, &mr, st)) return -1;
+    const int rc = ungap_run(cfg, Q, R, n, dp, plan, ds, mq, mr, du, st, opts);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    HIP_OR_RET(hipMemcpyAsync(out, du, sizeof(pmx_ungapped_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" void pmx_seed_filtered_free(pmx_seed_filtered_t *result) { free(result); }
+
+extern "C" int pmx_seed_filter(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, const pmx_seed_hits_t *hits,
+                               int byte_kind, const uint8_t *code, const pmx_seed_filter_opts_t *fopts, const pmx_pairs_opts_t *opts,
+                               pmx_seed_filtered_t **result)
+{
+    if (!result) { set_err("null result pointer"); return -1; }
+    *result = nullptr;
+    if (!hits) { set_err("null hits"); return -1; }
+    if (hits->n_hits < 0 || hits->n_rows < 0) { set_err("negative n_hits or n_rows"); return -1; }
+    if (hits->n_hits < hits->n_passing) {
+        set_err("a list that max_hits cut (%lld of %lld candidates stored) cannot be filtered: the selection needs every row in full",
+                (long long)hits->n_hits, (long long)hits->n_passing);
+        return -1;
+    }
+    const int64_t n = hits->n_hits, nq = hits->n_rows;
+    SlotPlan plan;
+    if (ungap_list_check(cfg, Q, R, n, hits->pairs, hits->seeds, nullptr, false, hits->strand, byte_kind, code, opts, &plan)) return -1;
+    int64_t unused = 0;
+    if (ungap_filter_check(n, nq, hits->row_off, fopts, 0, &unused, &unused)) return -1;
+    // the result: one block -- header, row offsets, descriptors, seed records, ungapped records, sources, bytes
+    auto block = [&](int64_t kept) -> pmx_seed_filtered_t * {
+        Carver c; c.align = 16;
+        c.take<pmx_seed_filtered_t>(1); c.take<int64_t>((size_t)nq + 1); c.take<pmx_pair_t>((size_t)kept); c.take<pmx_seed_hit_t>((size_t)kept);
+        c.take<pmx_ungapped_t>((size_t)kept); c.take<int64_t>((size_t)kept); c.take<uint8_t>((size_t)kept);
+        unsigned char *p = (unsigned char *)calloc(1, c.used ? c.used : 16);
+        if (!p) { set_err("out of memory"); return nullptr; }
+        Carver d; d.align = 16; d.base = p;
+        pmx_seed_filtered_t *r = d.take<pmx_seed_filtered_t>(1);
+        r->hits.n_rows = nq; r->hits.n_hits = kept; r->hits.n_passing = kept;
+        r->hits.row_off = d.take<int64_t>((size_t)nq + 1); r->hits.pairs = d.take<pmx_pair_t>((size_t)kept);
+        r->hits.seeds = d.take<pmx_seed_hit_t>((size_t)kept); r->ungapped = d.take<pmx_ungapped_t>((size_t)kept);
+        r->source = d.take<int64_t>((size_t)kept); r->hits.strand = d.take<uint8_t>((size_t)kept);
+        return r;
+    };
+    if (n == 0) { *result = block(0); return *result ? 0 : -1; }
+    if (ungap_device_check(Q, R)) return -1;
+    static thread_local HostStreams hs;
+    if (hs.init(false)) return -1;
+    const hipStream_t st = hs.comp;
+    StreamGuard guard(st);
+    if (!guard.ok) { set_err("stream guard failed"); return -1; }
+    pmx_pair_t *dp = nullptr, *op = nullptr; pmx_seed_hit_t *ds = nullptr, *os = nullptr; uint8_t *db = nullptr, *ob = nullptr;
+    pmx_ungapped_t *ou = nullptr; int64_t *d_off = nullptr, *o_off = nullptr, *o_src = nullptr, *d_cnt = nullptr;
+    if (scratch_carve(SCR_UNGAPHIT, [&](Carver &c) {
+            dp = c.take<pmx_pair_t>((size_t)n); ds = c.take<pmx_seed_hit_t>((size_t)n); db = c.take<uint8_t>((size_t)n); d_off = c.take<int64_t>((size_t)nq + 1);
+            op = c.take<pmx_pair_t>((size_t)n); os = c.take<pmx_seed_hit_t>((size_t)n); ob = c.take<uint8_t>((size_t)n); ou = c.take<pmx_ungapped_t>((size_t)n);
+            o_src = c.take<int64_t>((size_t)n); o_off = c.take<int64_t>((size_t)nq + 1); d_cnt = c.take<int64_t>(2);
+        })) return -1;
+    HIP_OR_RET(hipMemcpyAsync(dp, hits->pairs, sizeof(pmx_pair_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_OR_RET(hipMemcpyAsync(ds, hits->seeds, sizeof(pmx_seed_hit_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_OR_RET(hipMemcpyAsync(d_off, hits->row_off, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice, st));
+    if (hits->strand) { HIP_OR_RET(hipMemcpyAsync(db, hits->strand, (size_t)n, hipMemcpyHostToDevice, st)); plan.d_byte = db; }
+    int32_t mq = 1, mr = 1;
+    if (ungap_host_lens(cfg, Q, R, dp, n, plan, &mq, &mr, st)) return -1;
+    const UngapFilterOut o = {op, ob, os, ou, o_src, n, o_off, d_cnt};
+    const int rc = ungap_filter_run(cfg, Q, R, n, dp, plan, ds, mq, mr, nq, d_off, *fopts, o, st, opts);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    int64_t h[2] = {0, 0};
+    HIP_OR_RET(hipMemcpyAsync(h, d_cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_OR_RET(hipStreamSynchronize(st));
+    const int64_t kept = h[0];
+    if (kept < 0 || kept > n || h[1] != kept) { set_err("the selection's counts are inconsistent"); return -1; }
+    pmx_seed_filtered_t *r = block(kept);
+    if (!r) return -1;
+    hipError_t e = hipMemcpy(r->hits.row_off, o_off, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && kept > 0) e = hipMemcpy(r->hits.pairs, op, sizeof(pmx_pair_t) * (size_t)kept, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && kept > 0) e = hipMemcpy(r->hits.seeds, os, sizeof(pmx_seed_hit_t) * (size_t)kept, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && kept > 0) e = hipMemcpy(r->hits.strand, ob, (size_t)kept, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && kept > 0) e = hipMemcpy(r->ungapped, ou, sizeof(pmx_ungapped_t) * (size_t)kept, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && kept > 0) e = hipMemcpy(r->source, o_src, sizeof(int64_t) * (size_t)kept, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_err("copying the kept candidates back failed: %s", hipGetErrorString(e)); free(r); return -1; }
+    *result = r;
+    return 0;
 }

@@ -510,6 +510,22 @@ size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slo
 int pmx_launch_seed_count(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedSource &src, long long row0, long long rows, hipStream_t stream);
 int pmx_launch_seed_cluster(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedOut &out, const PmxSeedSource &src, long long row0,
                             long long rows, long long m, hipStream_t stream);
+// The ungapped diagonal filter (pmx_ungap.hip; semantics: include/parasail_amd.h).  The hot kernel's shape: a group of
+// PMX_UNGAP_LANES lanes per candidate, pieces of whole PMX_UNGAP_STEP-cell steps per lane.
+#define PMX_UNGAP_LANES 16
+#define PMX_UNGAP_STEP 4
+// The n slots of a chunk (packed windows, offsets and validity bytes of the set batches' pipeline; the chunk's descriptors and seed
+// records) -> n records.  0 launched, 1 not eligible (a PSSM), <0 HIP error.
+int pmx_launch_ungapped(long long n, const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, const uint8_t *ok,
+                        const pmx_pair_t *pairs, const pmx_seed_hit_t *seeds, const PmxDevMatrix &m, pmx_ungapped_t *out, hipStream_t st);
+// The selection over the scored list: keys_a / keys_b n keys each (NULL without top_n), flag n + 1 entries, temp of
+// pmx_ungap_select_temp_bytes(n, nq) bytes; every output column optional.
+size_t pmx_ungap_select_temp_bytes(long long n, long long nq);
+int pmx_launch_ungap_select(const pmx_ungapped_t *ung, long long n, const int64_t *row_off, long long nq, int min_score, int top_n,
+                            const pmx_pair_t *pairs, const uint8_t *byte, const pmx_seed_hit_t *seeds,
+                            uint64_t *keys_a, uint64_t *keys_b, uint32_t *flag, void *temp, size_t temp_bytes,
+                            pmx_pair_t *out_pairs, uint8_t *out_byte, pmx_seed_hit_t *out_seeds, pmx_ungapped_t *out_ung, int64_t *out_source,
+                            long long capacity, int64_t *out_row_off, int64_t *counts, hipStream_t st);
 // out[0] / out[1] (zeroed by the caller): the longest good query / reference window; pairs == NULL: the n sequences of the first set
 int pmx_launch_pairs_maxlen(const pmx_pair_t *pairs, long long n, const int64_t *q_off, long long q_count, long long q_bytes,
                             const int64_t *r_off, long long r_count, long long r_bytes, int32_t *out, hipStream_t stream);
