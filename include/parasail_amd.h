@@ -1558,9 +1558,10 @@ int pmx_seed_pairs_translated_ref(const pmx_seqset_t *Q, const pmx_seed_index_t 
  * max_qlen >= 2^31; sets of another device than the current one; for the filter also NULL opts, top_n < 0, min_score < 0, non-zero
  * reserved fields, NULL d_row_off, d_out_row_off or d_counts, and n above 2^31 - 1.  n == 0 succeeds: zero counts and nq + 1 zero offsets.
  *
- * Out of scope, and the C entries cannot tell: the lists of the codon modes (PMX_SEED_CODONS_*) and of a translated index
+ * Not for these four entries, and they cannot tell: the lists of the codon modes (PMX_SEED_CODONS_*) and of a translated index
  * (pmx_seed_pairs_translated_ref).  Their diagonals are in nucleotides over three frames or belong to frames of the reference; passing
- * them here scores other cells than the seeds'.
+ * them here scores other cells than the seeds'.  They go to pmx_seed_ungapped_translated[_device] and
+ * pmx_seed_filter_translated[_device] below, which take a list_kind in place of the byte_kind.
  *
  * The host entries run the device entries on a stream of their own over uploaded arrays.  pmx_seed_filter takes a pmx_seed_hits_t and
  * returns one callee-allocated block released with pmx_seed_filtered_free: hits is a pmx_seed_hits_t of the kept candidates (n_passing
@@ -1591,6 +1592,75 @@ int  pmx_seed_filter(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_s
 void pmx_seed_filtered_free(pmx_seed_filtered_t *result);
 /* Test hook: the hot kernel's lanes per candidate and cells per lane step. */
 void pmx_seed_ungapped_shape(int32_t *lanes, int32_t *step);
+
+/* Ungapped diagonal filter for the codon and translated-index lists (extension): the same stage for the three seeding roads whose
+ * diagonals are not letter diagonals of one query frame (the same kernel in three more forms).  Everything the block
+ * above defines stays as it is: pmx_ungapped_t, the recurrence h = max(0, h + w) along a diagonal's existing cells and U = max h, exact
+ * in int32; the three record forms {U, diag, end_query, end_ref}, {0, diag_min, -1, -1} when no cell is positive (also when no cell
+ * exists) and {-1, 0, -1, -1} for a bad candidate; the tie rule (the lowest diagonal, then the earliest cell); the selection
+ * (threshold max(min_score, 0), top_n by score descending then position ascending, kept candidates in input order with `source`,
+ * `capacity`, d_counts = [kept, written], uncapped row offsets always written); w = matrix[mapper[query letter]][mapper[reference
+ * letter]].  list_kind says which cells a seed record's diagonals [diag_min, diag_max] mean; `code` (64 letters in NCBI order, NULL: the
+ * standard code) is read by all three kinds.
+ *
+ *   PMX_SEED_LIST_CODONS       The lists of pmx_seed_pairs_letters[_device] in a codon mode; the byte is a strand of the query (d_byte
+ *                              NULL: all forward).  Q holds nucleotides, R proteins.  T is the codon stream of the oriented query window,
+ *                              W - 2 letters, exactly what pmx_gather_pairs_codons_device writes; y is the reference window [r_beg,
+ *                              r_beg + r_len).  Cell (n, j) exists iff 0 <= n < W - 2, r_beg <= j < r_beg + r_len and n = 3 j - D for a D
+ *                              in [diag_min, diag_max] -- the seeds' rule D = 3 j - (off + 3 p) -- and scores T[n] against y[j - r_beg].
+ *                              The cells of one D are walked in ascending j.  Record {U, D, n + 2, j}: end_query is the last nucleotide
+ *                              of the last codon in the oriented window, the frameshift record's convention.
+ *   PMX_SEED_LIST_REF_FRAMES   The lists of pmx_seed_pairs_translated_ref[_device] with PMX_SEED_REF_FRAMES; the byte is the frame relative
+ *                              to the window (0 or 3; d_byte NULL: all 0) and seeds.reserved the sequence frame g.  x is the query window,
+ *                              y the translated reference window, exactly what pmx_gather_pairs_translated_ref_device writes.  Letter t
+ *                              of y is letter lb + t of frame g's translation of the WHOLE sequence of N nucleotides, off = g % 3:
+ *                              lb = (r_beg - off) / 3 on strand 0, lb = (N - off - (r_beg + r_len)) / 3 on strand 1 (r_len as resolved).
+ *                              Diagonals are the seeds': d = j - i, j a letter of that whole-frame translation; cell (i, j) exists iff
+ *                              0 <= i < L and lb <= j < lb + len(y).  Record {U, d, i, i + d}.  Bad candidate, besides the gather's own
+ *                              rule: a byte other than 0 or 3; g outside 0 .. 5 or g / 3 != byte / 3; a window that is not codon-aligned
+ *                              for frame g (one of the two divisions above leaves a remainder); diag_min > diag_max.
+ *   PMX_SEED_LIST_REF_CODONS   The lists of pmx_seed_pairs_translated_ref[_device] with PMX_SEED_REF_CODONS; the byte is a strand of the
+ *                              reference.  x is the query window of m letters; T is the codon stream of the oriented reference window
+ *                              [lo, hi), hi - lo - 2 letters, as pmx_gather_pairs_codons_ref_device writes it; lo = r_beg on strand 0,
+ *                              lo = N - (r_beg + r_len) on strand 1.  Cell (p, x) exists iff 0 <= p < m, lo <= x <= hi - 3 and x = D + 3 p
+ *                              for a D in [diag_min, diag_max]; x is an oriented position in the WHOLE sequence, the seeds' coordinate,
+ *                              and the cell scores x[p] against T[x - lo].  The cells of one D are walked in ascending p.  Record
+ *                              {U, D, p, x + 2}: end_ref is the last nucleotide of the last codon, in oriented whole-sequence coordinates.
+ * In the codon kinds a bad candidate is what the gather makes one (a bad descriptor, a byte above 1, a window of fewer than three
+ * nucleotides) or diag_min > diag_max.
+ *
+ * max_qlen and max_rlen bound what the corresponding gather entry bounds: letters; on a codon side the stream's W - 2; on the translated
+ * side of PMX_SEED_LIST_REF_FRAMES the letters of the window's translation.  An ungapped score is a sum over at most the cells of the
+ * longest diagonal -- one per codon of a stream, and never more than the other side's letters --, and max |w| times that count has to
+ * fit int32.
+ *
+ * The entries take the arguments of their untranslated counterparts with list_kind in place of byte_kind, use the same thread scratch,
+ * and behave like them: both device entries are ASYNCHRONOUS on the caller's stream, pmx_seed_filter_translated returns a
+ * pmx_seed_filtered_t released with pmx_seed_filtered_free, n == 0 succeeds, the selection is the same code.  Refused with -1 and a
+ * pmx_last_error() text before any GPU work: everything the entries above refuse, with their texts; an unknown list_kind (the text names
+ * the three constants); max |w| x the longest diagonal's cells >= 2^31.  pmx_last_kernel() reports the form that ran.
+ *
+ * Out of scope: x-drop, begin positions, narrowing the window of a kept candidate, PSSM, both sides translated. */
+#define PMX_SEED_LIST_CODONS     1
+#define PMX_SEED_LIST_REF_FRAMES 2
+#define PMX_SEED_LIST_REF_CODONS 3
+int pmx_seed_ungapped_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                        const pmx_pair_t *d_pairs, const uint8_t *d_byte /* or NULL */, int list_kind, const uint8_t *code,
+                                        const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                                        pmx_ungapped_t *d_out /* n */, void *stream, const pmx_pairs_opts_t *opts);
+int pmx_seed_ungapped_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                 const pmx_pair_t *pairs, const uint8_t *byte /* or NULL */, int list_kind, const uint8_t *code,
+                                 const pmx_seed_hit_t *seeds, pmx_ungapped_t *out /* n */, const pmx_pairs_opts_t *opts);
+int pmx_seed_filter_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                      const pmx_pair_t *d_pairs, const uint8_t *d_byte /* or NULL */, int list_kind, const uint8_t *code,
+                                      const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                                      int64_t nq, const int64_t *d_row_off /* nq + 1 */, const pmx_seed_filter_opts_t *fopts,
+                                      pmx_pair_t *d_out_pairs, uint8_t *d_out_byte, pmx_seed_hit_t *d_out_seeds, pmx_ungapped_t *d_out_ungapped,
+                                      int64_t *d_out_source, int64_t capacity, int64_t *d_out_row_off /* nq + 1 */,
+                                      int64_t *d_counts /* [0] kept, [1] written */, void *stream, const pmx_pairs_opts_t *opts);
+int pmx_seed_filter_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, const pmx_seed_hits_t *hits,
+                               int list_kind, const uint8_t *code, const pmx_seed_filter_opts_t *fopts, const pmx_pairs_opts_t *opts,
+                               pmx_seed_filtered_t **result);
 
 /* Long pairs with traceback in linear memory (extension).  pmx_align_batch_cigar and the one-pair *_trace_* functions keep one byte
  * per DP cell outside the packed kernels' window (20 kbp x 20 kbp: 400 MB, 100 kbp x 100 kbp: 10 GB on the device and the host).

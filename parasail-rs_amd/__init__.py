@@ -151,6 +151,7 @@ class pmx_seed_filtered_t(C.Structure):
 SEED_HIT_DTYPE = np.dtype([("n_seeds", "<i4"), ("diag_min", "<i4"), ("diag_max", "<i4"), ("reserved", "<i4")])
 UNGAPPED_DTYPE = np.dtype([("score", "<i4"), ("diag", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4")])
 SEED_BYTE_STRAND, SEED_BYTE_FRAME = 0, 1
+SEED_LIST_CODONS, SEED_LIST_REF_FRAMES, SEED_LIST_REF_CODONS = 1, 2, 3
 TOPK_MAX = 1024
 INT32_MIN = -(1 << 31)
 RECORD_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("flags", "<i4")])
@@ -339,6 +340,15 @@ _sig("pmx_seed_filter_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c
      C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(pmx_seed_filter_opts_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
 _sig("pmx_seed_filter", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.POINTER(pmx_seed_hits_t), C.c_int, C.c_void_p,
+     C.POINTER(pmx_seed_filter_opts_t), C.POINTER(pmx_pairs_opts_t), C.POINTER(C.POINTER(pmx_seed_filtered_t)))
+_sig("pmx_seed_ungapped_translated_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_seed_ungapped_translated", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_seed_filter_translated_device", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(pmx_seed_filter_opts_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(pmx_pairs_opts_t))
+_sig("pmx_seed_filter_translated", C.c_int, C.POINTER(pmx_config_t), C.c_void_p, C.c_void_p, C.POINTER(pmx_seed_hits_t), C.c_int, C.c_void_p,
      C.POINTER(pmx_seed_filter_opts_t), C.POINTER(pmx_pairs_opts_t), C.POINTER(C.POINTER(pmx_seed_filtered_t)))
 _sig("pmx_seed_filtered_free", None, C.POINTER(pmx_seed_filtered_t))
 _sig("pmx_seed_ungapped_shape", None, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
@@ -1957,7 +1967,7 @@ class SeedHits:
     .strand is zeros in the letters and frame modes.  Of a translated index (seed_pairs(ref_frames=)) .frame holds the byte with
     "frames" (0 or 3, relative to the window; seeds["reserved"] is the sequence frame) and .strand holds it with "codons".
     kind says which list this is: "strand" (a DNA index), "letters", "frame" or "codons" (a letters index), "ref_frames" or
-    "ref_codons" (a translated index); seed_filter reads it.  A list that seed_filter returns has .ungapped (UNGAPPED_DTYPE) and
+    "ref_codons" (a translated index); seed_filter and seed_filter_translated read it.  A list that either returns has .ungapped (UNGAPPED_DTYPE) and
     .source (int64: the candidate's index in the list that was filtered) as well."""
 
     def __init__(self, r, byte_is_frame=False, kind=None):
@@ -2114,13 +2124,33 @@ def _ungapped_kind(kind):
     return SEED_BYTE_FRAME if kind == "frame" else SEED_BYTE_STRAND
 
 
+def _ungapped_list_kind(kind):
+    names = {"codons": SEED_LIST_CODONS, "ref_frames": SEED_LIST_REF_FRAMES, "ref_codons": SEED_LIST_REF_CODONS}
+    if kind not in names:
+        raise BatchError("kind is \"codons\", \"ref_frames\" or \"ref_codons\"")
+    return names[kind]
+
+
 def seed_ungapped(Q, R, pairs, byte, seeds, matrix, kind="strand", code=None, chunk_pairs=0):
     """The ungapped score of listed candidates (UNGAPPED_DTYPE: score, diag, end_query, end_ref): the best run of matches and
     mismatches under `matrix` along the diagonals seeds["diag_min"] .. seeds["diag_max"] of each pair's windows.  byte: a strand
     per candidate (kind "strand"; None: all forward) or a frame 0 .. 5 of the query (kind "frame", with code).  A candidate
     without a positive cell gets (0, diag_min, -1, -1), a bad one (-1, 0, -1, -1)."""
+    return _seed_ungapped(lib.pmx_seed_ungapped, _ungapped_kind(kind), Q, R, pairs, byte, seeds, matrix, code, chunk_pairs)
+
+
+def seed_ungapped_translated(Q, R, pairs, byte, seeds, matrix, kind, code=None, chunk_pairs=0):
+    """seed_ungapped for the lists whose diagonals are not letter diagonals of one query frame.  kind "codons": Q nucleotides, R
+    proteins, byte a strand of the query, nucleotide diagonals D = 3 j - n over the query's codon stream, record (U, D, last
+    nucleotide of the codon in the oriented window, j).  kind "ref_frames": Q proteins, R nucleotides, byte the window's frame (0
+    or 3), seeds["reserved"] the sequence frame, letter diagonals of that frame's whole translation.  kind "ref_codons": byte a
+    strand of the reference, nucleotide diagonals D = x - 3 p in oriented whole-sequence coordinates, record (U, D, p, x + 2).
+    code: 64 letters that replace the standard genetic code."""
+    return _seed_ungapped(lib.pmx_seed_ungapped_translated, _ungapped_list_kind(kind), Q, R, pairs, byte, seeds, matrix, code, chunk_pairs)
+
+
+def _seed_ungapped(entry, bk, Q, R, pairs, byte, seeds, matrix, code, chunk_pairs):
     cfg = _ungapped_config(matrix)
-    bk = _ungapped_kind(kind)
     pairs = as_pairs(pairs)
     n = len(pairs)
     seeds = np.ascontiguousarray(seeds, dtype=SEED_HIT_DTYPE)
@@ -2133,20 +2163,31 @@ def seed_ungapped(Q, R, pairs, byte, seeds, matrix, kind="strand", code=None, ch
     code = _code_arg(code)
     out = np.zeros(n, dtype=UNGAPPED_DTYPE)
     opts = pmx_pairs_opts_t(int(chunk_pairs))
-    if lib.pmx_seed_ungapped(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, byte.ctypes.data if byte is not None else None, bk,
-                             code.ctypes.data if code is not None else None, seeds.ctypes.data, out.ctypes.data, C.byref(opts)):
+    if entry(C.byref(cfg), Q._handle(), R._handle(), n, pairs.ctypes.data, byte.ctypes.data if byte is not None else None, bk,
+             code.ctypes.data if code is not None else None, seeds.ctypes.data, out.ctypes.data, C.byref(opts)):
         raise BatchError(lib.pmx_last_error().decode())
     return out
 
 
 def seed_ungapped_device(Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, d_out, kind="strand", code=None, stream=0, chunk_pairs=0):
     """Device-pointer entry of seed_ungapped: n records into d_out; asynchronous on `stream`."""
+    _seed_ungapped_device(lib.pmx_seed_ungapped_device, _ungapped_kind(kind), Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, d_out,
+                          code, stream, chunk_pairs)
+
+
+def seed_ungapped_translated_device(Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, d_out, kind, code=None, stream=0, chunk_pairs=0):
+    """Device-pointer entry of seed_ungapped_translated: n records into d_out; asynchronous on `stream`.  max_qlen / max_rlen bound
+    what the kind's gather bounds: on a codon side the stream's W - 2 letters."""
+    _seed_ungapped_device(lib.pmx_seed_ungapped_translated_device, _ungapped_list_kind(kind), Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen,
+                          matrix, d_out, code, stream, chunk_pairs)
+
+
+def _seed_ungapped_device(entry, bk, Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, d_out, code, stream, chunk_pairs):
     cfg = _ungapped_config(matrix)
     code = _code_arg(code)
     opts = pmx_pairs_opts_t(int(chunk_pairs))
-    if lib.pmx_seed_ungapped_device(C.byref(cfg), Q._handle(), R._handle(), int(n), d_pairs, d_byte, _ungapped_kind(kind),
-                                    code.ctypes.data if code is not None else None, d_seeds, int(max_qlen), int(max_rlen), d_out, stream,
-                                    C.byref(opts)):
+    if entry(C.byref(cfg), Q._handle(), R._handle(), int(n), d_pairs, d_byte, bk, code.ctypes.data if code is not None else None, d_seeds,
+             int(max_qlen), int(max_rlen), d_out, stream, C.byref(opts)):
         raise BatchError(lib.pmx_last_error().decode())
 
 
@@ -2158,14 +2199,35 @@ def seed_filter(Q, R, hits, matrix, min_score=0, top_n=0, code=None, chunk_pairs
     (seed_ungapped), one below max(min_score, 0) is dropped, and with top_n > 0 only the top_n best of a query row stay (score
     descending, then position).  Returns a SeedHits of the kept candidates in their input order -- pairs / strand / frame go into
     Aligner.align_pairs as those of `hits` would -- with .ungapped and .source added.  hits.kind chooses the byte's meaning; the
-    lists of the codon modes and of a translated index ("codons", "ref_frames", "ref_codons") are refused."""
+    lists of the codon modes and of a translated index ("codons", "ref_frames", "ref_codons") are refused: they go to
+    seed_filter_translated."""
     kind = hits.kind if getattr(hits, "kind", None) is not None else ("frame" if hits.frame is not None else "strand")
     if kind not in _SEED_FILTER_KINDS:
         raise BatchError("seed_filter does not take a list of kind \"%s\": its diagonals are not letter diagonals of one query frame "
                          "(supported: \"strand\", \"letters\", \"frame\")" % kind)
-    cfg = _ungapped_config(matrix)
     byte_kind = _SEED_FILTER_KINDS[kind]
-    byte = np.ascontiguousarray(hits.frame if byte_kind == "frame" else hits.strand, dtype=np.uint8)
+    return _seed_filter(lib.pmx_seed_filter, _ungapped_kind(byte_kind), byte_kind == "frame", kind, Q, R, hits, matrix, min_score, top_n, code,
+                        chunk_pairs)
+
+
+def seed_filter_translated(Q, R, hits, matrix, min_score=0, top_n=0, code=None, chunk_pairs=0):
+    """seed_filter for the lists it refuses: hits.kind "codons" (seed_pairs(frames="codons..."): Q nucleotides, R proteins),
+    "ref_frames" and "ref_codons" (a translated index: Q proteins, R nucleotides); the cells a candidate's diagonals mean are those
+    of seed_ungapped_translated.  The result keeps kind, .strand / .frame and .seeds (with "reserved") and adds .ungapped and
+    .source; it goes where the unfiltered list goes: align_pairs(..., frameshift=, strand=hits.strand), align_pairs(...,
+    ref_frame=hits.frame), align_pairs(..., ref_frameshift=, ref_strand=hits.strand) and the frameshift_ref_cigar entries.  code: the
+    genetic code the list was seeded with (None: the standard code)."""
+    kind = getattr(hits, "kind", None)
+    if kind in _SEED_FILTER_KINDS or kind is None:
+        raise BatchError("seed_filter_translated takes the lists of kind \"codons\", \"ref_frames\" and \"ref_codons\"; a list of kind "
+                         "\"%s\" goes to seed_filter" % ("strand / letters / frame" if kind is None else kind))
+    return _seed_filter(lib.pmx_seed_filter_translated, _ungapped_list_kind(kind), kind == "ref_frames", kind, Q, R, hits, matrix, min_score,
+                        top_n, code, chunk_pairs)
+
+
+def _seed_filter(entry, kind_value, byte_is_frame, kind, Q, R, hits, matrix, min_score, top_n, code, chunk_pairs):
+    cfg = _ungapped_config(matrix)
+    byte = np.ascontiguousarray(hits.frame if byte_is_frame else hits.strand, dtype=np.uint8)
     pairs = np.ascontiguousarray(hits.pairs, dtype=PAIR_DTYPE)
     seeds = np.ascontiguousarray(hits.seeds, dtype=SEED_HIT_DTYPE)
     row_off = np.ascontiguousarray(hits.row_off, dtype=np.int64)
@@ -2178,12 +2240,12 @@ def seed_filter(Q, R, hits, matrix, min_score=0, top_n=0, code=None, chunk_pairs
     fopts = pmx_seed_filter_opts_t(int(min_score), int(top_n))
     opts = pmx_pairs_opts_t(int(chunk_pairs))
     res = C.POINTER(pmx_seed_filtered_t)()
-    if lib.pmx_seed_filter(C.byref(cfg), Q._handle(), R._handle(), C.byref(h), _ungapped_kind(byte_kind),
-                           code.ctypes.data if code is not None else None, C.byref(fopts), C.byref(opts), C.byref(res)):
+    if entry(C.byref(cfg), Q._handle(), R._handle(), C.byref(h), kind_value, code.ctypes.data if code is not None else None, C.byref(fopts),
+             C.byref(opts), C.byref(res)):
         raise BatchError(lib.pmx_last_error().decode())
     try:
         r = res.contents
-        out = SeedHits(r.hits, byte_is_frame=byte_kind == "frame", kind=kind)
+        out = SeedHits(r.hits, byte_is_frame=byte_is_frame, kind=kind)
         k = out.n_hits
         out.ungapped = (np.frombuffer(C.string_at(r.ungapped, k * UNGAPPED_DTYPE.itemsize), dtype=UNGAPPED_DTYPE).copy() if k
                         else np.zeros(0, dtype=UNGAPPED_DTYPE))
@@ -2198,14 +2260,30 @@ def seed_filter_device(Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, ma
                        stream=0, chunk_pairs=0):
     """Device-pointer entry of seed_filter over the complete list of nq rows (n = row_off[nq]): the kept candidates' columns (each
     optional, `capacity` entries), d_out_row_off gets nq + 1 offsets and d_counts [kept, written].  Asynchronous on `stream`."""
+    _seed_filter_device(lib.pmx_seed_filter_device, _ungapped_kind(kind), Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, nq, d_row_off,
+                        d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts, code, min_score, top_n,
+                        stream, chunk_pairs)
+
+
+def seed_filter_translated_device(Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, nq, d_row_off, d_out_pairs, d_out_byte,
+                                  d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts, kind, code=None, min_score=0,
+                                  top_n=0, stream=0, chunk_pairs=0):
+    """Device-pointer entry of seed_filter_translated (kind "codons", "ref_frames" or "ref_codons"), with seed_filter_device's
+    arguments and outputs.  Asynchronous on `stream`."""
+    _seed_filter_device(lib.pmx_seed_filter_translated_device, _ungapped_list_kind(kind), Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen,
+                        matrix, nq, d_row_off, d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts,
+                        code, min_score, top_n, stream, chunk_pairs)
+
+
+def _seed_filter_device(entry, kind_value, Q, R, n, d_pairs, d_byte, d_seeds, max_qlen, max_rlen, matrix, nq, d_row_off, d_out_pairs, d_out_byte,
+                        d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts, code, min_score, top_n, stream, chunk_pairs):
     cfg = _ungapped_config(matrix)
     code = _code_arg(code)
     fopts = pmx_seed_filter_opts_t(int(min_score), int(top_n))
     opts = pmx_pairs_opts_t(int(chunk_pairs))
-    if lib.pmx_seed_filter_device(C.byref(cfg), Q._handle(), R._handle(), int(n), d_pairs, d_byte, _ungapped_kind(kind),
-                                  code.ctypes.data if code is not None else None, d_seeds, int(max_qlen), int(max_rlen), int(nq), d_row_off,
-                                  C.byref(fopts), d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source, int(capacity),
-                                  d_out_row_off, d_counts, stream, C.byref(opts)):
+    if entry(C.byref(cfg), Q._handle(), R._handle(), int(n), d_pairs, d_byte, kind_value, code.ctypes.data if code is not None else None, d_seeds,
+             int(max_qlen), int(max_rlen), int(nq), d_row_off, C.byref(fopts), d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source,
+             int(capacity), d_out_row_off, d_counts, stream, C.byref(opts)):
         raise BatchError(lib.pmx_last_error().decode())
 
 

@@ -6310,18 +6310,20 @@ extern "C" int pmx_seed_pairs_translated_ref(const pmx_seqset_t *Q, const pmx_se
     return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_KIND_TRANSLATED, ref_mode, nullptr, result);
 }
 
-// ---- the ungapped diagonal filter: pmx_seed_ungapped[_device], pmx_seed_filter[_device] ----
+// ---- the ungapped diagonal filter: pmx_seed_ungapped[_device], pmx_seed_filter[_device], and (2.5t) their _translated
+// forms over the codon and translated-index lists.  One body per entry shape; `translated` says which of the two kinds `kind` is. ----
 extern "C" void pmx_seed_ungapped_shape(int32_t *lanes, int32_t *step)
 {
     if (lanes) *lanes = PMX_UNGAP_LANES;
     if (step) *step = PMX_UNGAP_STEP;
 }
 
-// What the four entries refuse about the list, the configuration and the byte's kind before any GPU work.  out: the record output
-// where the entry needs one.  *plan: the run's slots -- one per candidate, on the strand or in the frame of its byte.
+// What the entries refuse about the list, the configuration and the byte's kind before any GPU work.  out: the record output
+// where the entry needs one.  kind: a byte_kind, or (translated) a list_kind.  *plan: the run's slots -- one per candidate, on the
+// strand or in the frame of its byte; a list_kind's plan translates one side, as the gather entry the header names for it does.
 static int ungap_list_check(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const void *pairs, const void *seeds,
-                            const void *out, bool need_out, const uint8_t *d_byte, int byte_kind, const uint8_t *code, const pmx_pairs_opts_t *opts,
-                            SlotPlan *plan)
+                            const void *out, bool need_out, const uint8_t *d_byte, int kind, bool translated, const uint8_t *code,
+                            const pmx_pairs_opts_t *opts, SlotPlan *plan)
 {
     if (!Q || !R) { set_err("null sequence set"); return -1; }
     if (n < 0) { set_err("negative n"); return -1; }
@@ -6332,21 +6334,50 @@ static int ungap_list_check(const pmx_config_t *cfg, const pmx_seqset *Q, const 
     if (cfg->matrix->type == PARASAIL_MATRIX_TYPE_PSSM) {
         set_err("the ungapped filter takes no PSSM matrix: a profile belongs to one query, a candidate list has many"); return -1;
     }
-    if (byte_kind != PMX_SEED_BYTE_STRAND && byte_kind != PMX_SEED_BYTE_FRAME) {
-        set_err("unknown byte_kind %d (PMX_SEED_BYTE_STRAND 0, PMX_SEED_BYTE_FRAME 1)", byte_kind); return -1;
+    if (translated) {
+        if (kind != PMX_SEED_LIST_CODONS && kind != PMX_SEED_LIST_REF_FRAMES && kind != PMX_SEED_LIST_REF_CODONS) {
+            set_err("unknown list_kind %d (PMX_SEED_LIST_CODONS %d, PMX_SEED_LIST_REF_FRAMES %d, PMX_SEED_LIST_REF_CODONS %d)", kind,
+                    PMX_SEED_LIST_CODONS, PMX_SEED_LIST_REF_FRAMES, PMX_SEED_LIST_REF_CODONS);
+            return -1;
+        }
+        plan->kind = kind == PMX_SEED_LIST_REF_FRAMES ? SlotPlan::FRAMES : SlotPlan::CODONS;
+        plan->ref = kind != PMX_SEED_LIST_CODONS;
+        plan->set_code(code);
+        plan->d_byte = d_byte;
+        return 0;
     }
-    if (byte_kind == PMX_SEED_BYTE_FRAME) { plan->kind = SlotPlan::FRAMES; plan->set_code(code); }
+    if (kind != PMX_SEED_BYTE_STRAND && kind != PMX_SEED_BYTE_FRAME) {
+        set_err("unknown byte_kind %d (PMX_SEED_BYTE_STRAND 0, PMX_SEED_BYTE_FRAME 1)", kind); return -1;
+    }
+    if (kind == PMX_SEED_BYTE_FRAME) { plan->kind = SlotPlan::FRAMES; plan->set_code(code); }
     else plan->kind = SlotPlan::BYTES;
     plan->d_byte = d_byte;
     return 0;
 }
-// ... about the maxima: an ungapped score is a sum of at most max_qlen cells and has to be exact in int32
-static int ungap_lens_check(const pmx_config_t *cfg, int32_t max_qlen, int32_t max_rlen)
+// The kernel form of a plan that ungap_list_check made
+static int ungap_form(const SlotPlan &plan)
+{
+    if (plan.kind == SlotPlan::CODONS) return plan.ref ? PMX_UNGAP_REF_CODONS : PMX_UNGAP_CODONS;
+    return plan.kind == SlotPlan::FRAMES && plan.ref ? PMX_UNGAP_REF_FRAMES : PMX_UNGAP_PLAIN;
+}
+// ... about the maxima: an ungapped score is a sum of at most max_qlen cells and has to be exact in int32.  A translated list's
+// longest diagonal: one cell per codon of a stream (its maximum is the stream's W - 2 letters), and never more than the other side's letters.
+static int ungap_lens_check(const pmx_config_t *cfg, int32_t max_qlen, int32_t max_rlen, const SlotPlan &plan)
 {
     if (max_qlen < 1 || max_rlen < 1) { set_err("max_qlen / max_rlen must be positive"); return -1; }
     const int64_t w = std::max<int64_t>(std::abs((int64_t)cfg->matrix->min), std::abs((int64_t)cfg->matrix->max));
-    if (w * (int64_t)max_qlen >= ((int64_t)1 << 31)) {
-        set_err("max |w| x max_qlen = %lld x %d does not fit int32: the ungapped score would not be exact", (long long)w, (int)max_qlen); return -1;
+    const int form = ungap_form(plan);
+    if (form == PMX_UNGAP_PLAIN) {
+        if (w * (int64_t)max_qlen >= ((int64_t)1 << 31)) {
+            set_err("max |w| x max_qlen = %lld x %d does not fit int32: the ungapped score would not be exact", (long long)w, (int)max_qlen); return -1;
+        }
+        return 0;
+    }
+    const int64_t ql = form == PMX_UNGAP_CODONS ? ((int64_t)max_qlen + 2) / 3 : max_qlen, rl = form == PMX_UNGAP_REF_CODONS ? ((int64_t)max_rlen + 2) / 3 : max_rlen;
+    const int64_t cells = std::min(ql, rl);
+    if (w * cells >= ((int64_t)1 << 31)) {
+        set_err("max |w| x the longest diagonal's cells = %lld x %lld does not fit int32: the ungapped score would not be exact", (long long)w, (long long)cells);
+        return -1;
     }
     return 0;
 }
@@ -6375,34 +6406,52 @@ static int ungap_device_check(const pmx_seqset *Q, const pmx_seqset *R)
     return 0;
 }
 
-// The records of the n > 0 candidates behind the checks: every chunk of the set batches' pipeline through pmx_ungapped_kernel.
-// Asynchronous on `st`.
+// The records of the n > 0 candidates behind the checks: every chunk of the set batches' pipeline through pmx_ungapped_kernel in the
+// plan's form.  Asynchronous on `st`.
 static int ungap_run(const pmx_config_t *cfg, const pmx_seqset *Q, const pmx_seqset *R, int64_t n, const pmx_pair_t *d_pairs, const SlotPlan &plan,
                      const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen, pmx_ungapped_t *d_out, hipStream_t st, const pmx_pairs_opts_t *opts)
 {
     DevMat dm;
     if (get_devmat(cfg->matrix, &dm)) return -1;
+    const int form = ungap_form(plan);
+    static const char *const names[] = {"pmx_ungapped_kernel", "pmx_ungapped_kernel<codons>", "pmx_ungapped_kernel<ref_codons>", "pmx_ungapped_kernel<ref_frames>"};
     return pairs_run(Q, R, n, d_pairs, 0, PMX_PAIRS_LIST, plan, max_qlen, max_rlen, st, pairs_chunk(n, max_qlen, max_rlen, opts),
         [&](int64_t c0, int64_t cn, const PairsChunkBufs &b) -> int {
-            const int rc = pmx_launch_ungapped(cn, b.q, b.qoff, b.r, b.roff, b.ok, d_pairs + c0, d_seeds + c0, dm.d, d_out + c0, st);
+            const int rc = pmx_launch_ungapped(cn, b.q, b.qoff, b.r, b.roff, b.ok, d_pairs + c0, d_seeds + c0, form, R->d_off, b.tw, b.sflag, dm.d,
+                                               d_out + c0, st);
             if (rc) { set_err("ungapped filter launch failed (%d)", rc); return rc < 0 ? rc : -1; }
-            g_last_kernel = "pmx_ungapped_kernel";
+            g_last_kernel = names[form];
             return 0;
         });
 }
 
-extern "C" int pmx_seed_ungapped_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
-                                        const pmx_pair_t *d_pairs, const uint8_t *d_byte, int byte_kind, const uint8_t *code,
-                                        const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
-                                        pmx_ungapped_t *d_out, void *stream, const pmx_pairs_opts_t *opts)
+static int ungap_entry_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                              const pmx_pair_t *d_pairs, const uint8_t *d_byte, int kind, bool translated, const uint8_t *code,
+                              const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                              pmx_ungapped_t *d_out, void *stream, const pmx_pairs_opts_t *opts)
 {
     SlotPlan plan;
-    if (ungap_list_check(cfg, Q, R, n, d_pairs, d_seeds, d_out, true, d_byte, byte_kind, code, opts, &plan) || ungap_lens_check(cfg, max_qlen, max_rlen)) return -1;
+    if (ungap_list_check(cfg, Q, R, n, d_pairs, d_seeds, d_out, true, d_byte, kind, translated, code, opts, &plan) ||
+        ungap_lens_check(cfg, max_qlen, max_rlen, plan)) return -1;
     if (n == 0) return 0;
     if (ungap_device_check(Q, R)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     return ungap_run(cfg, Q, R, n, d_pairs, plan, d_seeds, max_qlen, max_rlen, d_out, (hipStream_t)stream, opts);
+}
+extern "C" int pmx_seed_ungapped_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                        const pmx_pair_t *d_pairs, const uint8_t *d_byte, int byte_kind, const uint8_t *code,
+                                        const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                                        pmx_ungapped_t *d_out, void *stream, const pmx_pairs_opts_t *opts)
+{
+    return ungap_entry_device(cfg, Q, R, n, d_pairs, d_byte, byte_kind, false, code, d_seeds, max_qlen, max_rlen, d_out, stream, opts);
+}
+extern "C" int pmx_seed_ungapped_translated_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                                   const pmx_pair_t *d_pairs, const uint8_t *d_byte, int list_kind, const uint8_t *code,
+                                                   const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
+                                                   pmx_ungapped_t *d_out, void *stream, const pmx_pairs_opts_t *opts)
+{
+    return ungap_entry_device(cfg, Q, R, n, d_pairs, d_byte, list_kind, true, code, d_seeds, max_qlen, max_rlen, d_out, stream, opts);
 }
 
 // The selection behind the checks; d_byte: the list's bytes as the caller gave them (may be NULL).  Asynchronous on `st`.
@@ -6431,21 +6480,30 @@ static int ungap_filter_run(const pmx_config_t *cfg, const pmx_seqset *Q, const 
     return rc;
 }
 
-extern "C" int pmx_seed_filter_device(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
-                                      const pmx_pair_t *d_pairs, const uint8_t *d_byte, int byte_kind, const uint8_t *code,
-                                      const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen,
-                                      int64_t nq, const int64_t *d_row_off, const pmx_seed_filter_opts_t *fopts,
-                                      pmx_pair_t *d_out_pairs, uint8_t *d_out_byte, pmx_seed_hit_t *d_out_seeds, pmx_ungapped_t *d_out_ungapped,
-                                      int64_t *d_out_source, int64_t capacity, int64_t *d_out_row_off, int64_t *d_counts, void *stream,
-                                      const pmx_pairs_opts_t *opts)
+#define PMX_UNGAP_FILTER_DEVICE_ARGS(kind_name) \
+    const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n, const pmx_pair_t *d_pairs, const uint8_t *d_byte, int kind_name, \
+    const uint8_t *code, const pmx_seed_hit_t *d_seeds, int32_t max_qlen, int32_t max_rlen, int64_t nq, const int64_t *d_row_off, \
+    const pmx_seed_filter_opts_t *fopts, pmx_pair_t *d_out_pairs, uint8_t *d_out_byte, pmx_seed_hit_t *d_out_seeds, pmx_ungapped_t *d_out_ungapped, \
+    int64_t *d_out_source, int64_t capacity, int64_t *d_out_row_off, int64_t *d_counts, void *stream, const pmx_pairs_opts_t *opts
+static int ungap_filter_entry_device(PMX_UNGAP_FILTER_DEVICE_ARGS(kind), bool translated)
 {
     SlotPlan plan;
-    if (ungap_list_check(cfg, Q, R, n, d_pairs, d_seeds, nullptr, false, d_byte, byte_kind, code, opts, &plan) || ungap_lens_check(cfg, max_qlen, max_rlen) ||
+    if (ungap_list_check(cfg, Q, R, n, d_pairs, d_seeds, nullptr, false, d_byte, kind, translated, code, opts, &plan) || ungap_lens_check(cfg, max_qlen, max_rlen, plan) ||
         ungap_filter_check(n, nq, d_row_off, fopts, capacity, d_out_row_off, d_counts) || ungap_device_check(Q, R)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
     const UngapFilterOut o = {d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts};
     return ungap_filter_run(cfg, Q, R, n, d_pairs, plan, d_seeds, max_qlen, max_rlen, nq, d_row_off, *fopts, o, (hipStream_t)stream, opts);
+}
+extern "C" int pmx_seed_filter_device(PMX_UNGAP_FILTER_DEVICE_ARGS(byte_kind))
+{
+    return ungap_filter_entry_device(cfg, Q, R, n, d_pairs, d_byte, byte_kind, code, d_seeds, max_qlen, max_rlen, nq, d_row_off, fopts, d_out_pairs, d_out_byte,
+                                     d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts, stream, opts, false);
+}
+extern "C" int pmx_seed_filter_translated_device(PMX_UNGAP_FILTER_DEVICE_ARGS(list_kind))
+{
+    return ungap_filter_entry_device(cfg, Q, R, n, d_pairs, d_byte, list_kind, code, d_seeds, max_qlen, max_rlen, nq, d_row_off, fopts, d_out_pairs, d_out_byte,
+                                     d_out_seeds, d_out_ungapped, d_out_source, capacity, d_out_row_off, d_counts, stream, opts, true);
 }
 
 // The host entries' maxima: the longest good windows of the uploaded list, found on the device (a bad descriptor counts for nothing);
@@ -6455,15 +6513,15 @@ static int ungap_host_lens(const pmx_config_t *cfg, const pmx_seqset *Q, const p
 {
     if (device_maxlens(Q, R, d_pairs, n, mq, mr, st)) return -1;
     plan.to_letters(mq, mr);
-    return ungap_lens_check(cfg, *mq, *mr);
+    return ungap_lens_check(cfg, *mq, *mr, plan);
 }
 
-extern "C" int pmx_seed_ungapped(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
-                                 const pmx_pair_t *pairs, const uint8_t *byte, int byte_kind, const uint8_t *code,
-                                 const pmx_seed_hit_t *seeds, pmx_ungapped_t *out, const pmx_pairs_opts_t *opts)
+static int ungap_entry_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                            const pmx_pair_t *pairs, const uint8_t *byte, int kind, bool translated, const uint8_t *code,
+                            const pmx_seed_hit_t *seeds, pmx_ungapped_t *out, const pmx_pairs_opts_t *opts)
 {
     SlotPlan plan;
-    if (ungap_list_check(cfg, Q, R, n, pairs, seeds, out, true, byte, byte_kind, code, opts, &plan)) return -1;
+    if (ungap_list_check(cfg, Q, R, n, pairs, seeds, out, true, byte, kind, translated, code, opts, &plan)) return -1;
     if (n == 0) return 0;
     if (ungap_device_check(Q, R)) return -1;
     static thread_local HostStreams hs;
@@ -6486,12 +6544,24 @@ extern "C" int pmx_seed_ungapped(const pmx_config_t *cfg, const pmx_seqset_t *Q,
     HIP_OR_RET(hipStreamSynchronize(st));
     return 0;
 }
+extern "C" int pmx_seed_ungapped(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                 const pmx_pair_t *pairs, const uint8_t *byte, int byte_kind, const uint8_t *code,
+                                 const pmx_seed_hit_t *seeds, pmx_ungapped_t *out, const pmx_pairs_opts_t *opts)
+{
+    return ungap_entry_host(cfg, Q, R, n, pairs, byte, byte_kind, false, code, seeds, out, opts);
+}
+extern "C" int pmx_seed_ungapped_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, int64_t n,
+                                            const pmx_pair_t *pairs, const uint8_t *byte, int list_kind, const uint8_t *code,
+                                            const pmx_seed_hit_t *seeds, pmx_ungapped_t *out, const pmx_pairs_opts_t *opts)
+{
+    return ungap_entry_host(cfg, Q, R, n, pairs, byte, list_kind, true, code, seeds, out, opts);
+}
 
 extern "C" void pmx_seed_filtered_free(pmx_seed_filtered_t *result) { free(result); }
 
-extern "C" int pmx_seed_filter(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, const pmx_seed_hits_t *hits,
-                               int byte_kind, const uint8_t *code, const pmx_seed_filter_opts_t *fopts, const pmx_pairs_opts_t *opts,
-                               pmx_seed_filtered_t **result)
+static int ungap_filter_entry_host(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, const pmx_seed_hits_t *hits,
+                                   int kind, bool translated, const uint8_t *code, const pmx_seed_filter_opts_t *fopts, const pmx_pairs_opts_t *opts,
+                                   pmx_seed_filtered_t **result)
 {
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
@@ -6504,7 +6574,7 @@ extern "C" int pmx_seed_filter(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
     }
     const int64_t n = hits->n_hits, nq = hits->n_rows;
     SlotPlan plan;
-    if (ungap_list_check(cfg, Q, R, n, hits->pairs, hits->seeds, nullptr, false, hits->strand, byte_kind, code, opts, &plan)) return -1;
+    if (ungap_list_check(cfg, Q, R, n, hits->pairs, hits->seeds, nullptr, false, hits->strand, kind, translated, code, opts, &plan)) return -1;
     int64_t unused = 0;
     if (ungap_filter_check(n, nq, hits->row_off, fopts, 0, &unused, &unused)) return -1;
     // the result: one block -- header, row offsets, descriptors, seed records, ungapped records, sources, bytes
@@ -6561,4 +6631,16 @@ extern "C" int pmx_seed_filter(const pmx_config_t *cfg, const pmx_seqset_t *Q, c
     if (e != hipSuccess) { set_err("copying the kept candidates back failed: %s", hipGetErrorString(e)); free(r); return -1; }
     *result = r;
     return 0;
+}
+extern "C" int pmx_seed_filter(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, const pmx_seed_hits_t *hits,
+                               int byte_kind, const uint8_t *code, const pmx_seed_filter_opts_t *fopts, const pmx_pairs_opts_t *opts,
+                               pmx_seed_filtered_t **result)
+{
+    return ungap_filter_entry_host(cfg, Q, R, hits, byte_kind, false, code, fopts, opts, result);
+}
+extern "C" int pmx_seed_filter_translated(const pmx_config_t *cfg, const pmx_seqset_t *Q, const pmx_seqset_t *R, const pmx_seed_hits_t *hits,
+                                          int list_kind, const uint8_t *code, const pmx_seed_filter_opts_t *fopts, const pmx_pairs_opts_t *opts,
+                                          pmx_seed_filtered_t **result)
+{
+    return ungap_filter_entry_host(cfg, Q, R, hits, list_kind, true, code, fopts, opts, result);
 }

@@ -510,14 +510,23 @@ size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slo
 int pmx_launch_seed_count(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedSource &src, long long row0, long long rows, hipStream_t stream);
 int pmx_launch_seed_cluster(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedOut &out, const PmxSeedSource &src, long long row0,
                             long long rows, long long m, hipStream_t stream);
-// The ungapped diagonal filter (pmx_ungap.hip; semantics: include/parasail_amd.h; DESIGN 2.5s).  The hot kernel's shape: a group of
+// The ungapped diagonal filter (pmx_ungap.hip; semantics: include/parasail_amd.h; DESIGN 2.5s, 2.5t).  The hot kernel's shape: a group of
 // PMX_UNGAP_LANES lanes per candidate, pieces of whole PMX_UNGAP_STEP-cell steps per lane.
 #define PMX_UNGAP_LANES 16
 #define PMX_UNGAP_STEP 4
 // The n slots of a chunk (packed windows, offsets and validity bytes of the set batches' pipeline; the chunk's descriptors and seed
 // records) -> n records.  0 launched, 1 not eligible (a PSSM), <0 HIP error.
+// form: which cells the seed records' diagonals mean -- PLAIN both sides at stride 1 from r_beg; CODONS the query side a
+// codon stream, nucleotide diagonals; REF_CODONS the reference side a codon stream; REF_FRAMES a translated reference window whose
+// origin is a letter of sequence frame seeds.reserved.  The two REF forms read r_off (the reference set's offsets) and the resolve's
+// tw and sflag columns; the others take NULL.
+#define PMX_UNGAP_PLAIN 0
+#define PMX_UNGAP_CODONS 1
+#define PMX_UNGAP_REF_CODONS 2
+#define PMX_UNGAP_REF_FRAMES 3
 int pmx_launch_ungapped(long long n, const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, const uint8_t *ok,
-                        const pmx_pair_t *pairs, const pmx_seed_hit_t *seeds, const PmxDevMatrix &m, pmx_ungapped_t *out, hipStream_t st);
+                        const pmx_pair_t *pairs, const pmx_seed_hit_t *seeds, int form, const int64_t *r_off, const int32_t *tw, const uint8_t *sflag,
+                        const PmxDevMatrix &m, pmx_ungapped_t *out, hipStream_t st);
 // The selection over the scored list: keys_a / keys_b n keys each (NULL without top_n), flag n + 1 entries, temp of
 // pmx_ungap_select_temp_bytes(n, nq) bytes; every output column optional.
 size_t pmx_ungap_select_temp_bytes(long long n, long long nq);

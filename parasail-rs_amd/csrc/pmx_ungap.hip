@@ -1,4 +1,4 @@
-// pmx_ungap.hip -- the ungapped diagonal filter behind the seeding entries (semantics: include/parasail_amd.h; DESIGN 2.5s): the best
+// pmx_ungap.hip -- the ungapped diagonal filter behind the seeding entries (semantics: include/parasail_amd.h; DESIGN 2.5s, 2.5t): the best
 // ungapped local score along the seeded diagonals of every candidate, and the selection behind it -- a score threshold and the best
 // top_n candidates per query row, compacted in input order.
 //
@@ -27,6 +27,18 @@
 // The score table: matrix[mapper[x]][mapper[y]].  A table of at most 32 x 32 letters whose scores fit a byte is staged in LDS as bytes
 // at a row stride of 32 beside the 256-byte mapper (1.25 KiB per block); any other square matrix is read from the device matrix's
 // int16 table through the vector L1.  Plain C++, vector loads and stores only.
+//
+// The forms.  FORM says which cells a seed record's diagonals mean; the grouping, the pieces, the fold, the butterfly and
+// both table forms are the same code in all of them.
+//   PMX_UNGAP_PLAIN        both sides at stride 1, d = j - i, origin r_beg: the DNA, letters and query-frame lists.
+//   PMX_UNGAP_CODONS       the query side is a codon stream (pmx_gather_pairs_codons_device) walked at stride 3: cell c is reference
+//                          letter c against stream letter 3 c - d, d = D - 3 r_beg a NUCLEOTIDE diagonal.  Cells are counted in codons.
+//   PMX_UNGAP_REF_CODONS   the reference side is the stream: cell c is query letter c against stream letter d + 3 c, d = D - lo, lo the
+//                          oriented window's start in the whole sequence (strand 1: N - (r_beg + W), N from the set's offsets).
+//   PMX_UNGAP_REF_FRAMES   stride 1 against a translated reference window (pmx_gather_pairs_translated_ref_device) whose origin is the
+//                          letter lb of sequence frame g = seeds.reserved; a window that is not codon-aligned for g is a bad candidate.
+// A strided step's four letters lie at byte distance 3, ten consecutive bytes: they come from the three aligned dwords that hold them
+// (four when the first letter is a dword's last byte), never from byte loads, and never from outside the chunk buffer and its slack.
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -66,17 +78,32 @@ static __device__ __forceinline__ uint32_t pmx_ungap_dword(const uint8_t *p)
     const uint32_t hi = sh ? *reinterpret_cast<const uint32_t *>(sa + 4) : 0u;
     return __builtin_amdgcn_alignbyte(hi, lo, sh);
 }
+// the four bytes at p, p + 3, p + 6 and p + 9, packed like a dword of a stride-1 side: ten bytes, at most p + 12 is touched (the slack)
+static __device__ __forceinline__ uint32_t pmx_ungap_dword3(const uint8_t *p)
+{
+    const uint32_t *w = reinterpret_cast<const uint32_t *>((uintptr_t)p & ~(uintptr_t)3);
+    const unsigned sh = (unsigned)((uintptr_t)p & 3);
+    const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], d3 = sh == 3 ? w[3] : 0u;
+    const uint32_t a = __builtin_amdgcn_alignbyte(d1, d0, sh), b = __builtin_amdgcn_alignbyte(d2, d1, sh), c = __builtin_amdgcn_alignbyte(d3, d2, sh);
+    return (a & 0xFFu) | ((a >> 24) << 8) | (b & 0x00FF0000u) | ((c << 16) & 0xFF000000u);          // bytes 0, 3, 6, 9
+}
+static __device__ __forceinline__ long long pmx_ungap_floor3(long long x) { return x >= 0 ? x / 3 : -((2 - x) / 3); }
 
 // Slot k of the chunk: the oriented query window qbuf[qoff[k] .. qoff[k + 1]), the reference window rbuf[roff[k] .. roff[k + 1]), ok[k]
 // from the resolve, the candidate's descriptor (for r_beg) and seed record (for the diagonals).  BYTES: the table staged in LDS as
-// bytes (msize <= 32, every score in -128 .. 127); else scores[a * msize + b] from global memory.
-template <bool BYTES>
+// bytes (msize <= 32, every score in -128 .. 127); else scores[a * msize + b] from global memory.  FORM: see above; the two reference
+// forms read the whole sequence's length from the set's offsets r_off, the translated side's W from tw[k] and the slot's byte from
+// sflag[k] (the resolve's columns), the plain and the query-stream form read none of the three.
+template <bool BYTES, int FORM>
 __global__ __launch_bounds__(256)
 void pmx_ungapped_kernel(long long n, const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff,
                          const uint8_t *__restrict__ rbuf, const int64_t *__restrict__ roff, const uint8_t *__restrict__ ok,
                          const pmx_pair_t *__restrict__ pairs, const pmx_seed_hit_t *__restrict__ seeds,
+                         const int64_t *__restrict__ r_off, const int32_t *__restrict__ tw, const uint8_t *__restrict__ sflag,
                          const int16_t *__restrict__ scores, const uint8_t *__restrict__ mapper, int msize, pmx_ungapped_t *__restrict__ out)
 {
+    constexpr bool QS = FORM == PMX_UNGAP_CODONS, RS = FORM == PMX_UNGAP_REF_CODONS;       // the strided side: the query's, the reference's
+    constexpr int SQ = QS ? 3 : 1, SR = RS ? 3 : 1;
     __shared__ uint8_t map[256];
     __shared__ int8_t tab[BYTES ? 32 * 32 : 4];
     map[threadIdx.x] = mapper[threadIdx.x];
@@ -88,22 +115,39 @@ void pmx_ungapped_kernel(long long n, const uint8_t *__restrict__ qbuf, const in
     const bool live = k < n;                    // (uniform per group; every lane reaches the shuffles)
     bool good = false;
     int L = 0, rlen = 0, r_beg = 0, dmin = 0;
-    long long dlo = 0, dhi = -1;                // the diagonals with cells, relative to the window: j - r_beg - i
+    long long org = 0;                          // the seeds' diagonal of relative diagonal 0: r_beg, 3 r_beg, lo, lb
+    long long dlo = 0, dhi = -1;                // the diagonals that can have cells, relative to the windows: SQ b - SR a over buffer letters a, b
     const uint8_t *q = qbuf, *r = rbuf;
     if (live) {
         const pmx_seed_hit_t s = seeds[k];
         dmin = s.diag_min;
         good = ok[k] != 0 && s.diag_min <= s.diag_max;
         if (good) {
+            const pmx_pair_t pr = pairs[k];
+            r_beg = pr.r_beg;
+            if (FORM == PMX_UNGAP_PLAIN) org = r_beg;
+            else if (QS) org = 3ll * r_beg;
+            else {                              // ok[k]: pr.r is a sequence of the set
+                const long long N = r_off[pr.r + 1] - r_off[pr.r], end = (long long)r_beg + tw[k];
+                const unsigned f = sflag[k];
+                if (RS) org = f ? N - end : r_beg;
+                else {
+                    const unsigned g = (unsigned)s.reserved, off = g % 3u;
+                    const long long lead = f ? N - off - end : (long long)r_beg - off;      // the nucleotides of frame g in front of the window
+                    good = (f == 0u || f == 3u) && g < 6u && g / 3u == f / 3u && lead % 3 == 0;
+                    org = lead / 3;
+                }
+            }
+        }
+        if (good) {
             const long long q0 = qoff[k], r0 = roff[k];
             L = (int)(qoff[k + 1] - q0); rlen = (int)(roff[k + 1] - r0);
             q += q0; r += r0;
-            r_beg = pairs[k].r_beg;
-            dlo = max((long long)s.diag_min - r_beg, -(long long)(L - 1));
-            dhi = min((long long)s.diag_max - r_beg, (long long)rlen - 1);
+            dlo = max((long long)s.diag_min - org, -(long long)SR * (L - 1));
+            dhi = min((long long)s.diag_max - org, (long long)SQ * (rlen - 1));
         }
     }
-    const long long span = dhi - dlo + 1;       // <= L + rlen - 1
+    const long long span = dhi - dlo + 1;       // <= SR L + SQ rlen
     int g = PMX_UNGAP_LANES;                    // lanes per diagonal
     while (g > 1 && PMX_UNGAP_LANES / g < span) g >>= 1;
     const int sub = lane & (g - 1), ndg = PMX_UNGAP_LANES / g;
@@ -111,13 +155,19 @@ void pmx_ungapped_kernel(long long n, const uint8_t *__restrict__ qbuf, const in
     int bd = INT32_MAX;                         // the diagonal of `best` (relative)
     for (long long dl = dlo + lane / g; dl <= dhi; dl += ndg) {
         const int d = (int)dl;
-        const int i0 = max(0, -d), i1 = min(L, rlen - d), cells = i1 - i0;          // cells >= 1 inside [dlo, dhi]
+        // the diagonal's cells i0 .. i1 - 1, counted on the stride-1 side (a strided form: in codons; it may have none when the stream
+        // is shorter than a codon's three frames): cell i is query letter i (QS: 3 i - d) against reference letter i + d (QS: i, RS: d + 3 i)
+        int i0, i1;
+        if (QS) { i0 = max(0, (int)pmx_ungap_floor3((long long)d + 2)); i1 = min(rlen, (int)pmx_ungap_floor3((long long)L - 1 + d) + 1); }
+        else if (RS) { i0 = max(0, (int)pmx_ungap_floor3(2 - (long long)d)); i1 = min(L, (int)pmx_ungap_floor3((long long)rlen - 1 - d) + 1); }
+        else { i0 = max(0, -d); i1 = min(L, rlen - d); }                            // cells >= 1 inside [dlo, dhi]
+        const int cells = max(i1 - i0, 0);
         const int c = (cells + PMX_UNGAP_STEP * g - 1) / (PMX_UNGAP_STEP * g) * PMX_UNGAP_STEP;
         const int a = i0 + sub * c, b = min(i1, a + c);
         PmxUngapPiece m = {0, 0, 0, 0, PMX_UNGAP_NOPOS, PMX_UNGAP_NOPOS};
-        const uint8_t *qp = q + a, *rp = r + (a + d);
-        for (int i = a; i < b; i += PMX_UNGAP_STEP, qp += PMX_UNGAP_STEP, rp += PMX_UNGAP_STEP) {
-            const uint32_t qd = pmx_ungap_dword(qp), rd = pmx_ungap_dword(rp);
+        const uint8_t *qp = q + (QS ? 3 * a - d : a), *rp = r + (QS ? a : RS ? d + 3 * a : a + d);
+        for (int i = a; i < b; i += PMX_UNGAP_STEP, qp += SQ * PMX_UNGAP_STEP, rp += SR * PMX_UNGAP_STEP) {
+            const uint32_t qd = QS ? pmx_ungap_dword3(qp) : pmx_ungap_dword(qp), rd = RS ? pmx_ungap_dword3(rp) : pmx_ungap_dword(rp);
 #pragma unroll
             for (int t = 0; t < PMX_UNGAP_STEP; ++t) {
                 if (i + t >= b) break;
@@ -141,20 +191,30 @@ void pmx_ungapped_kernel(long long n, const uint8_t *__restrict__ qbuf, const in
     int4 w;
     if (!good) w = make_int4(-1, 0, -1, -1);
     else if (best.B <= 0) w = make_int4(0, dmin, -1, -1);
-    else w = make_int4(best.B, bd + r_beg, best.pB, best.pB + bd + r_beg);
+    else if (QS) w = make_int4(best.B, (int)(bd + org), 3 * best.pB - bd + 2, best.pB + r_beg);          // the codon's last nucleotide
+    else if (RS) w = make_int4(best.B, (int)(bd + org), best.pB, (int)(org + bd + 3 * best.pB + 2));
+    else w = make_int4(best.B, (int)(bd + org), best.pB, (int)(best.pB + bd + org));
     if (((uintptr_t)out & 15) == 0) *reinterpret_cast<int4 *>(out + k) = w;
     else { pmx_ungapped_t u; u.score = w.x; u.diag = w.y; u.end_query = w.z; u.end_ref = w.w; out[k] = u; }
 }
 
 int pmx_launch_ungapped(long long n, const uint8_t *qbuf, const int64_t *qoff, const uint8_t *rbuf, const int64_t *roff, const uint8_t *ok,
-                        const pmx_pair_t *pairs, const pmx_seed_hit_t *seeds, const PmxDevMatrix &m, pmx_ungapped_t *out, hipStream_t st)
+                        const pmx_pair_t *pairs, const pmx_seed_hit_t *seeds, int form, const int64_t *r_off, const int32_t *tw, const uint8_t *sflag,
+                        const PmxDevMatrix &m, pmx_ungapped_t *out, hipStream_t st)
 {
     if (m.pssm || m.msize > 255) return 1;
+    if (form < PMX_UNGAP_PLAIN || form > PMX_UNGAP_REF_FRAMES) return 1;
+    if (form >= PMX_UNGAP_REF_CODONS && (!r_off || !tw || !sflag)) return 1;
     if (n <= 0) return 0;
     const bool bytes = m.msize <= 32 && m.min >= -128 && m.max <= 127;
-    const auto kernel = bytes ? pmx_ungapped_kernel<true> : pmx_ungapped_kernel<false>;
+    using Kernel = decltype(&pmx_ungapped_kernel<false, PMX_UNGAP_PLAIN>);
+    static const Kernel kernels[8] = {pmx_ungapped_kernel<false, PMX_UNGAP_PLAIN>, pmx_ungapped_kernel<true, PMX_UNGAP_PLAIN>,
+                                 pmx_ungapped_kernel<false, PMX_UNGAP_CODONS>, pmx_ungapped_kernel<true, PMX_UNGAP_CODONS>,
+                                 pmx_ungapped_kernel<false, PMX_UNGAP_REF_CODONS>, pmx_ungapped_kernel<true, PMX_UNGAP_REF_CODONS>,
+                                 pmx_ungapped_kernel<false, PMX_UNGAP_REF_FRAMES>, pmx_ungapped_kernel<true, PMX_UNGAP_REF_FRAMES>};
+    const Kernel kernel = kernels[2 * form + (bytes ? 1 : 0)];
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n * PMX_UNGAP_LANES + 255) / 256)), dim3(256), 0, st, n, qbuf, qoff, rbuf, roff, ok, pairs, seeds,
-                       m.scores, m.mapper, m.msize, out);
+                       r_off, tw, sflag, m.scores, m.mapper, m.msize, out);
     return pmx_launched();
 }
 
