@@ -1374,6 +1374,66 @@ void pmx_seed_hits_free(pmx_seed_hits_t *hits);
  * replaces.  A small bound makes the cut of a slice fall after a few rows. */
 int64_t pmx_seed_match_budget(int64_t bytes);
 
+/* Minimizer seeding (extension): a (w, k) sketch in place of every k-mer at stride 1, on both sides of a DNA index -- the index and the
+ * number of look-ups shrink by about (w + 1) / 2 (kernel: pmx_seed_sketch_kernel of parasail-rs_amd/csrc/pmx_seed.hip).
+ * Letters, validity and keys are those above.  DNA indexes only: the letters and translated builds take no w.
+ *
+ * Definitions.  A sequence of n bytes has nk = n - k + 1 k-mer positions (none if nk <= 0).  Position p HAS A K-MER iff its k letters
+ * are valid; its key is K(p).
+ *   Order.     h(p) = mix(K(p)), with mix on B = 2 k bits, M = 2^B - 1, all arithmetic in 64 bits:
+ *                h = (K ^ PMX_SEED_MIX_XOR) & M;  h = (h * PMX_SEED_MIX_MUL1) & M;  h ^= h >> k;  h = (h * PMX_SEED_MIX_MUL2) & M;  h ^= h >> k
+ *              Every step is a bijection on B bits (an xor with a constant, a multiplication by an odd number modulo 2^B, an xor with
+ *              the own upper half), so equal hashes mean equal k-mers, and a hash is below 2^62: "no k-mer" is never a hash value.
+ *              pmx_seed_mix(key, k) returns it (0 for k outside 8 .. 31).  Position q LOSES TO p iff q has no k-mer or
+ *              (h(q), q) > (h(p), p): the smaller hash wins and among equal k-mers the leftmost.
+ *   Windows.   If nk >= w the windows are [s, s + w) for s = 0 .. nk - w; if 0 < nk < w there is the single window [0, nk).  A window
+ *              never crosses a sequence end.  A window selects the position in it that every other position of it loses to; a window
+ *              without a k-mer selects nothing.
+ *   Minimizers of a sequence: the positions selected by at least one window.  Equivalently, with l the number of consecutive left
+ *              neighbours that lose to p (capped at w - 1, stopping at position 0) and r the same to the right (stopping at nk - 1):
+ *              p is a minimizer iff p has a k-mer and l + r + 1 >= min(w, nk).
+ *   Strand 1.  The minimizers of the ORIENTED read (the reverse complement, w'[x] = comp[w[L - 1 - x]]), positions and the leftmost
+ *              rule in oriented coordinates.
+ *   w = 1 is every k-mer: the index of pmx_seed_index_build and its hits.
+ *   Guarantee. If an oriented query and a reference sequence share a stretch of L >= w + k - 1 valid, equal letters and both have at
+ *              least w k-mer positions, they share a minimizer at corresponding positions inside the stretch: the stretch holds a whole
+ *              window of each, both windows hold the same k-mers in the same order, so both select the same offset.
+ *
+ * pmx_seed_index_build_minimizers: the index holds an entry (K, seq, pos) for the minimizer positions of R's sequences only, in the
+ * order and layout of pmx_seed_index_build: 16 bytes per ENTRY plus the bucket table resident, and while it is built 5 bytes per byte
+ * of the set (flags and their scan) plus twice the entries and rocPRIM's scratch.  It synchronises, as pmx_seed_index_build does.
+ * pmx_seed_index_count, _entries_device, _bits and _free serve it; max_occ counts entries of THIS index.  pmx_seed_index_window: w; 1 of
+ * every other build.  pmx_seed_index_bytes: the device bytes an index of any kind owns.  Refused (NULL, pmx_last_error()) before any
+ * GPU work: a NULL set, k outside 8 .. 31, w outside 1 .. 64, a set of more than 2^31 - 1 bytes or sequences, a set of another device.
+ * An empty set builds with no device work.
+ *
+ * Seeding.  pmx_seed_pairs[_device] take a minimizer index as it is and read w from it: a match is an (i, j) where i is a minimizer of
+ * the oriented query, j an entry, the keys are equal and the key has at most max_occ entries.  Everything else -- diagonals, clusters,
+ * min_seeds, band, pad, windows, order, capacity, slices, determinism, the refusals and the row budget rule -- is what is documented
+ * above (a position slot takes 17 bytes of scratch in place of 16).
+ *
+ * pmx_seed_sketch[_device]: the minimizers of rows q_first .. q_first + nq of Q alone.  flags receives one byte per position slot
+ * (row_local * strands + s) * max_qlen + i, strands = 2 with PMX_STRAND_BOTH (s = the strand) and 1 otherwise: 1 where oriented
+ * position i is a minimizer, 0 elsewhere -- every slot is written.  A row longer than max_qlen has no minimizer.  The device entry is
+ * ASYNCHRONOUS on `stream`; the host entry takes a host array.  Refused with -1 and a pmx_last_error() text before any GPU work: a NULL
+ * set; k outside 8 .. 31; w outside 1 .. 64; a negative q_first or nq; rows beyond |Q|; a bad strand mode; max_qlen < 1; more than
+ * 2^31 - 1 position slots; NULL flags with nq > 0; a set of another device.  nq == 0 succeeds and writes nothing. */
+#define PMX_SEED_MIX_XOR  0x9E3779B97F4A7C15ull
+#define PMX_SEED_MIX_MUL1 0xBF58476D1CE4E5B9ull
+#define PMX_SEED_MIX_MUL2 0x94D049BB133111EBull
+uint64_t pmx_seed_mix(uint64_t key, int32_t k);
+pmx_seed_index_t *pmx_seed_index_build_minimizers(const pmx_seqset_t *R, int32_t k, int32_t w, void *stream);
+int32_t pmx_seed_index_window(const pmx_seed_index_t *index);         /* w; 1 for every other build; -1 for NULL */
+int64_t pmx_seed_index_bytes(const pmx_seed_index_t *index);          /* device bytes the index owns; -1 for NULL */
+int pmx_seed_sketch_device(const pmx_seqset_t *Q, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t k, int32_t w, int strand_mode,
+                           uint8_t *d_flags /* nq x strands x max_qlen */, void *stream);
+int pmx_seed_sketch(const pmx_seqset_t *Q, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t k, int32_t w, int strand_mode,
+                    uint8_t *flags /* host, nq x strands x max_qlen */, void *stream);
+/* The longest of rows q_first .. q_first + nq of Q, a max_qlen for the entries above (0 for nq == 0; -1: a NULL set, rows beyond |Q|). */
+int64_t pmx_seed_rows_max_len(const pmx_seqset_t *Q, int64_t q_first, int64_t nq);
+/* Test hook: the positions a workgroup of the sketch kernel owns, in its row form and its set form. */
+void pmx_seed_sketch_shape(int32_t *row_tile, int32_t *set_tile);
+
 /* Protein seeding (extension): the same stage in front of the translated entries -- a k-mer index of a PROTEIN set over a reduced
  * alphabet, and a seeding entry whose queries are proteins or nucleotide reads translated on the device in up to six frames.  Its
  * candidate lists go unchanged into pmx_align_pairs_translated[_device] (a frame byte per pair) and pmx_align_pairs_frameshift[_device]
@@ -1817,6 +1877,10 @@ int pmx_long_plan_probe(int road, int mode, long long n, int max_qlen, int max_r
  * where one row's worst case does not fit the budget; -1 on an argument no entry would plan. */
 int pmx_seed_plan_probe(int kind, int mode, long long nq, int max_qlen, int max_occ, long long slice_rows, long long budget,
                         long long ref_count, long long *out);
+/* ... and with the window of the index as an argument: w = 1 is pmx_seed_plan_probe, number for number; w in 2 .. 64 (kind 0 only) is the
+ * plan of a minimizer index, whose position slots take one scratch byte more.  -1 also for w outside 1 .. 64 or w > 1 with kind != 0. */
+int pmx_seed_plan_probe_w(int kind, int mode, long long nq, int max_qlen, int max_occ, long long slice_rows, long long budget,
+                          long long ref_count, int w, long long *out);
 
 #ifdef __cplusplus
 }

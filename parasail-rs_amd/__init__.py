@@ -319,6 +319,14 @@ _sig("pmx_seed_pairs", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.
      C.POINTER(C.POINTER(pmx_seed_hits_t)))
 _sig("pmx_seed_hits_free", None, C.POINTER(pmx_seed_hits_t))
 _sig("pmx_seed_match_budget", C.c_int64, C.c_int64)
+_sig("pmx_seed_mix", C.c_uint64, C.c_uint64, C.c_int32)
+_sig("pmx_seed_index_build_minimizers", C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
+_sig("pmx_seed_index_window", C.c_int32, C.c_void_p)
+_sig("pmx_seed_index_bytes", C.c_int64, C.c_void_p)
+_sig("pmx_seed_sketch_device", C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_sketch", C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_rows_max_len", C.c_int64, C.c_void_p, C.c_int64, C.c_int64)
+_sig("pmx_seed_sketch_shape", None, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 _sig("pmx_seed_alphabet", C.c_int, C.c_int, C.c_void_p)
 _sig("pmx_seed_index_build_letters", C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
 _sig("pmx_seed_index_bits", C.c_int32, C.c_void_p)
@@ -464,6 +472,7 @@ _sig("pmx_swfsc_window_cols", C.c_longlong, C.c_longlong, C.c_longlong, C.c_long
 _sig("pmx_trace_plan_probe", C.c_int, *([C.c_int] * 7 + [C.c_longlong] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)]))
 _sig("pmx_long_plan_probe", C.c_int, *([C.c_int] * 2 + [C.c_longlong] + [C.c_int] * 2 + [C.c_double] + [C.c_int] * 7 + [C.POINTER(C.c_longlong)]))
 _sig("pmx_seed_plan_probe", C.c_int, *([C.c_int] * 2 + [C.c_longlong] + [C.c_int] * 2 + [C.c_longlong] * 3 + [C.POINTER(C.c_longlong)]))
+_sig("pmx_seed_plan_probe_w", C.c_int, *([C.c_int] * 2 + [C.c_longlong] + [C.c_int] * 2 + [C.c_longlong] * 3 + [C.c_int, C.POINTER(C.c_longlong)]))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [C.c_void_p]
 
@@ -1893,25 +1902,32 @@ class SeedIndex:
     """The k-mer index of a set (pmx_seed_index_t): every k-mer of R as (kmer, seq, pos), sorted, on R's device -- of a DNA set, or
     with `alphabet` of a protein set over a reduced alphabet (a letters index; .letters, .bits per letter), or with `alphabet` and
     `translated` of a nucleotide set read in the three frames of the strands named (a translated index; .translated, .strands: the
-    strand mode it holds, else None).  R is held: it outlives the index.  len(): the entries.  Released by close() or on deletion."""
+    strand mode it holds, else None).  A DNA index built with w > 1 holds the (w, k) minimizers of R only (.w: the window, 1 of every
+    other index); seed_pairs reads w from the index.  .nbytes: the device bytes the index owns.  R is held: it outlives the index.
+    len(): the entries.  Released by close() or on deletion."""
 
     def __init__(self, inner, R, k, letters=False, strands=None):
         self.inner, self.R, self.k, self.letters = inner, R, int(k), bool(letters)
         self.translated, self.strands = strands is not None, strands
 
     @classmethod
-    def build(cls, R, k, alphabet=None, stream=0, translated=None, code=None):
+    def build(cls, R, k, alphabet=None, stream=0, translated=None, code=None, w=1):
         """alphabet: None (a DNA index), "aa20", "aa11" or 256 bytes that map a byte to its group 0 .. 31 or to 255.  An integer in
         its place is the stream of a DNA index, build(R, k, stream), as before there were alphabets.  translated: "forward",
         "reverse" or "both" -- R holds nucleotides and the index their six-frame (or three-frame) k-mers over `alphabet`, for
-        seed_pairs(ref_frames=); code: 64 letters that replace the standard genetic code of a translated index."""
+        seed_pairs(ref_frames=); code: 64 letters that replace the standard genetic code of a translated index.  w: 1 .. 64, the
+        window of a DNA index -- with w > 1 the index holds minimizers only; the letters and translated builds take no w."""
         if isinstance(alphabet, (int, np.integer)) and not isinstance(alphabet, bool):
             alphabet, stream = None, int(alphabet)
+        if int(w) != 1 and alphabet is not None:
+            raise BatchError("w= is for a DNA index: a letters or translated index (alphabet=) holds every k-mer")
         if translated is not None and alphabet is None:
             raise BatchError("translated= needs alphabet=: a translated index holds letters of a reduced alphabet")
         if code is not None and translated is None:
             raise BatchError("code= is for a translated index (translated=)")
-        if alphabet is None:
+        if alphabet is None and int(w) != 1:
+            inner = lib.pmx_seed_index_build_minimizers(R._handle(), int(k), int(w), stream)
+        elif alphabet is None:
             inner = lib.pmx_seed_index_build(R._handle(), int(k), stream)
         else:
             if isinstance(alphabet, str):
@@ -1936,6 +1952,14 @@ class SeedIndex:
     @property
     def bits(self):
         return int(lib.pmx_seed_index_bits(self._handle()))
+
+    @property
+    def w(self):
+        return int(lib.pmx_seed_index_window(self._handle()))
+
+    @property
+    def nbytes(self):
+        return int(lib.pmx_seed_index_bytes(self._handle()))
 
     def _handle(self):
         if not self.inner:
@@ -2284,6 +2308,43 @@ def _seed_filter_device(entry, kind_value, Q, R, n, d_pairs, d_byte, d_seeds, ma
     if entry(C.byref(cfg), Q._handle(), R._handle(), int(n), d_pairs, d_byte, kind_value, code.ctypes.data if code is not None else None, d_seeds,
              int(max_qlen), int(max_rlen), int(nq), d_row_off, C.byref(fopts), d_out_pairs, d_out_byte, d_out_seeds, d_out_ungapped, d_out_source,
              int(capacity), d_out_row_off, d_counts, stream, C.byref(opts)):
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def seed_mix(key, k):
+    """The order of the minimizers: mix of include/parasail_amd.h on the 2 k bits of a k-mer's key."""
+    return int(lib.pmx_seed_mix(int(key), int(k)))
+
+
+def seed_sketch_shape():
+    """(row_tile, set_tile): the positions one workgroup of the sketch kernel owns in its row form and in its set form."""
+    r, s = C.c_int32(0), C.c_int32(0)
+    lib.pmx_seed_sketch_shape(C.byref(r), C.byref(s))
+    return int(r.value), int(s.value)
+
+
+def seed_minimizers(Q, k, w, strand="both", first_row=0, rows=None, max_qlen=None, stream=0):
+    """The (w, k) minimizers of the rows of Q (pmx_seed_sketch): a uint8 array of shape (rows, orientations, max_qlen), 1 where the
+    oriented position is a minimizer; orientations = 2 with strand "both" (index 1: the reverse complement, positions in oriented
+    coordinates).  max_qlen: None -- the longest of the rows; a row longer than max_qlen has no minimizer."""
+    rows = len(Q) - int(first_row) if rows is None else int(rows)
+    mode = _strand_mode(strand)
+    if max_qlen is None:
+        max_qlen = int(lib.pmx_seed_rows_max_len(Q._handle(), int(first_row), rows))
+        if max_qlen < 0:
+            raise BatchError(lib.pmx_last_error().decode())
+        max_qlen = max(1, max_qlen)
+    orients = 2 if mode == STRAND_BOTH else 1
+    out = np.zeros((max(rows, 0), orients, max(int(max_qlen), 0)), dtype=np.uint8)
+    if lib.pmx_seed_sketch(Q._handle(), int(first_row), rows, int(max_qlen), int(k), int(w), mode, out.ctypes.data if out.size else None, stream):
+        raise BatchError(lib.pmx_last_error().decode())
+    return out
+
+
+def seed_minimizers_device(Q, q_first, nq, max_qlen, k, w, d_flags, strand="both", stream=0):
+    """Device-pointer entry of seed_minimizers: one byte per position slot (row_local * orientations + s) * max_qlen + i into d_flags;
+    asynchronous on `stream`."""
+    if lib.pmx_seed_sketch_device(Q._handle(), int(q_first), int(nq), int(max_qlen), int(k), int(w), _strand_mode(strand), d_flags, stream):
         raise BatchError(lib.pmx_last_error().decode())
 
 

@@ -5832,6 +5832,8 @@ struct pmx_seed_index {
     int kind = PMX_SEED_KIND_DNA;          // PmxSeedKind: which build made it, and with that which entries seed it
     uint8_t table[256] = {0}; uint8_t *d_table = nullptr;       // letters, translated: the groups and their device copy
     int strands = -2;                      // translated: the PMX_STRAND_* mode it holds; else -2 (what pmx_seed_index_strands answers)
+    int w = 1;                             // the window: 1 every k-mer, > 1 a minimizer index (pmx_seed_index_build_minimizers)
+    int64_t owned = 0;                     // device bytes behind keys, vals, bucket and d_table
 };
 static const int PMX_SEED_BUCKET_BITS = 22;            // 2^22 + 1 numbers of 4 bytes: 16 MiB, resident in the Infinity Cache
 static const int32_t PMX_SEED_BAND_MAX = 1 << 20;
@@ -5858,6 +5860,8 @@ extern "C" void pmx_seed_index_free(pmx_seed_index_t *ix)
 }
 
 extern "C" int64_t pmx_seed_index_count(const pmx_seed_index_t *ix) { return ix ? ix->n : -1; }
+extern "C" int32_t pmx_seed_index_window(const pmx_seed_index_t *ix) { return ix ? ix->w : -1; }
+extern "C" int64_t pmx_seed_index_bytes(const pmx_seed_index_t *ix) { return ix ? ix->owned : -1; }
 
 // The index of R behind the entries' checks; table: the 256 groups of a letters or translated index of `bits` bits per letter, NULL:
 // the DNA index; translated: tr_strands is the strand mode held, under `code`, one entry slot per byte and strand
@@ -5908,19 +5912,170 @@ static pmx_seed_index_t *seed_index_build(const pmx_seqset_t *R, int kind, int32
         set_err("seed index build failed: %s", e != hipSuccess ? hipGetErrorString(e) : "kernel launch");
         pmx_seed_index_free(ix); return nullptr;
     }
+    ix->owned = (int64_t)(nbytes * 16 + sizeof(uint32_t) * (size_t)(ix->nb + 1) + (table ? 256 : 0));
     return ix;
+}
+
+// what both DNA builds refuse about set and k
+static int seed_dna_build_check(const pmx_seqset_t *R, int32_t k)
+{
+    if (!R) { set_err("null sequence set"); return -1; }
+    if (k < 8 || k > 31) { set_err("k %d is outside 8 .. 31", (int)k); return -1; }
+    if (R->bytes > INT32_MAX || R->count > INT32_MAX) {
+        set_err("a seed index holds a set of at most 2^31 - 1 bytes and sequences (this one: %lld bytes, %lld sequences): index parts of it",
+                (long long)R->bytes, (long long)R->count);
+        return -1;
+    }
+    return 0;
 }
 
 extern "C" pmx_seed_index_t *pmx_seed_index_build(const pmx_seqset_t *R, int32_t k, void *stream)
 {
-    if (!R) { set_err("null sequence set"); return nullptr; }
-    if (k < 8 || k > 31) { set_err("k %d is outside 8 .. 31", (int)k); return nullptr; }
-    if (R->bytes > INT32_MAX || R->count > INT32_MAX) {
-        set_err("a seed index holds a set of at most 2^31 - 1 bytes and sequences (this one: %lld bytes, %lld sequences): index parts of it",
-                (long long)R->bytes, (long long)R->count);
-        return nullptr;
-    }
+    if (seed_dna_build_check(R, k)) return nullptr;
     return seed_index_build(R, PMX_SEED_KIND_DNA, k, 2, nullptr, stream);
+}
+
+// ---- minimizers (semantics: include/parasail_amd.h; kernels: pmx_seed.hip) -----------------------------------------------
+static bool seed_window_valid(int32_t w)
+{
+    if (w >= 1 && w <= 64) return true;
+    set_err("w %d is outside 1 .. 64", (int)w);
+    return false;
+}
+
+extern "C" uint64_t pmx_seed_mix(uint64_t key, int32_t k) { return k < 8 || k > 31 ? 0 : pmx_seed_mix_bits(key & (((uint64_t)1 << (2 * k)) - 1), (int)k); }
+
+extern "C" void pmx_seed_sketch_shape(int32_t *row_tile, int32_t *set_tile)
+{
+    int r = 0, s = 0;
+    pmx_seed_sketch_tiles(&r, &s);
+    if (row_tile) *row_tile = r;
+    if (set_tile) *set_tile = s;
+}
+
+// Select first, then sort only what was selected: flag bytes from the sketch kernel's set form, their exclusive scan, a scatter of the
+// compact (key, val) pairs to the scanned places, rocPRIM's sort of the n entries, the buckets.  Beyond the 5 bytes per byte of the set
+// (flags, scan) everything allocated is proportional to n.
+extern "C" pmx_seed_index_t *pmx_seed_index_build_minimizers(const pmx_seqset_t *R, int32_t k, int32_t w, void *stream)
+{
+    if (seed_dna_build_check(R, k) || !seed_window_valid(w)) return nullptr;
+    pmx_seed_index *ix = new (std::nothrow) pmx_seed_index();
+    if (!ix) { set_err("out of memory"); return nullptr; }
+    ix->R = R; ix->k = k; ix->dev = R->dev; ix->w = w;
+    const int bbits = std::min(2 * k, PMX_SEED_BUCKET_BITS);
+    ix->shift = 2 * k - bbits; ix->nb = (int64_t)1 << bbits;
+    if (R->bytes == 0 || R->count == 0) return ix;               // nothing to index: no entry, no device memory, no GPU work
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); delete ix; return nullptr; }
+    if (R->dev != dev) { set_err("a sequence set of device %d cannot be used on the current device %d", R->dev, dev); delete ix; return nullptr; }
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)R->bytes, scan_bytes = pmx_seed_sketch_scan_bytes(R->bytes);
+    uint8_t *flags = nullptr; uint32_t *at = nullptr, h_n = 0; void *temp = nullptr; uint64_t *kin = nullptr, *vin = nullptr;
+    hipError_t e = hipMalloc((void **)&ix->bucket, sizeof(uint32_t) * (size_t)(ix->nb + 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&flags, (bytes + 1 + 3) & ~(size_t)3);
+    if (e == hipSuccess) e = hipMalloc((void **)&at, sizeof(uint32_t) * (bytes + 1));
+    if (e == hipSuccess) e = hipMalloc(&temp, scan_bytes);
+    int rc = 0;
+    if (e == hipSuccess) rc = pmx_launch_seed_sketch_set(R->d_buf, R->d_off, R->count, R->bytes, k, w, flags, at, temp, scan_bytes, st);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(&h_n, at + bytes, sizeof h_n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+    (void)hipFree(temp); temp = nullptr;
+    if (e == hipSuccess && !rc && h_n > 0) {
+        const size_t n = h_n, sort_bytes = pmx_seed_index_sort_bytes((long long)n, k);
+        e = hipMalloc((void **)&ix->keys, n * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&ix->vals, n * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&kin, n * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&vin, n * 8);
+        if (e == hipSuccess) e = hipMalloc(&temp, sort_bytes);
+        if (e == hipSuccess)
+            rc = pmx_launch_seed_index_selected(R->d_buf, R->d_off, R->count, R->bytes, k, flags, at, (long long)n, kin, vin, ix->keys, ix->vals, temp,
+                                                sort_bytes, st);
+    }
+    if (e == hipSuccess && !rc) { ix->n = (int64_t)h_n; rc = pmx_launch_seed_buckets(ix->keys, ix->n, ix->shift, ix->nb, ix->bucket, st); }
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(st);
+    (void)hipFree(flags); (void)hipFree(at); (void)hipFree(temp); (void)hipFree(kin); (void)hipFree(vin);
+    if (e != hipSuccess || rc) {
+        set_err("seed index build failed: %s", e != hipSuccess ? hipGetErrorString(e) : "kernel launch");
+        pmx_seed_index_free(ix); return nullptr;
+    }
+    ix->owned = 16 * ix->n + (int64_t)sizeof(uint32_t) * (ix->nb + 1);
+    return ix;
+}
+
+// what both sketch entries refuse; > 0: the orientations per row
+static int seed_sketch_check(const pmx_seqset *Q, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t k, int32_t w, int strand_mode, const void *flags)
+{
+    if (!Q) { set_err("null sequence set"); return -1; }
+    if (k < 8 || k > 31) { set_err("k %d is outside 8 .. 31", (int)k); return -1; }
+    if (!seed_window_valid(w)) return -1;
+    if (q_first < 0 || nq < 0) { set_err("negative q_first or nq"); return -1; }
+    if (q_first > Q->count || nq > Q->count - q_first) {
+        set_err("rows %lld .. %lld are beyond the %lld sequences of Q", (long long)q_first, (long long)q_first + (long long)nq - 1, (long long)Q->count);
+        return -1;
+    }
+    if (strand_mode < PMX_STRAND_FORWARD || strand_mode > PMX_STRAND_BOTH) { set_err("strand mode %d is outside 0 .. 2", strand_mode); return -1; }
+    if (max_qlen < 1) { set_err("max_qlen must be positive"); return -1; }
+    const int strands = strand_mode == PMX_STRAND_BOTH ? 2 : 1;
+    if ((double)nq * strands * ((double)max_qlen + 256.0) > 2147483647.0) {
+        set_err("%lld rows x %d strand(s) x max_qlen %d are more than 2^31 - 1 position slots: sketch fewer rows per call", (long long)nq, strands, (int)max_qlen);
+        return -1;
+    }
+    if (nq > 0 && !flags) { set_err("null flags with nq > 0"); return -1; }
+    return strands;
+}
+
+extern "C" int64_t pmx_seed_rows_max_len(const pmx_seqset_t *Q, int64_t q_first, int64_t nq)
+{
+    if (!Q) { set_err("null sequence set"); return -1; }
+    if (q_first < 0 || nq < 0) { set_err("negative q_first or nq"); return -1; }
+    if (q_first > Q->count || nq > Q->count - q_first) {
+        set_err("rows %lld .. %lld are beyond the %lld sequences of Q", (long long)q_first, (long long)q_first + (long long)nq - 1, (long long)Q->count);
+        return -1;
+    }
+    if (nq == 0) return 0;
+    std::vector<int64_t> copy;
+    const int64_t *off = nullptr;
+    if (!Q->h_off.empty()) off = Q->h_off.data() + q_first;
+    else {                                                   // a wrapped set: its offsets live on the device
+        copy.resize((size_t)nq + 1);
+        if (hipMemcpy(copy.data(), Q->d_off + q_first, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost) != hipSuccess) {
+            set_err("reading the offsets of a wrapped set failed"); return -1;
+        }
+        off = copy.data();
+    }
+    int64_t m = 0;
+    for (int64_t r = 0; r < nq; ++r) m = std::max(m, off[r + 1] - off[r]);
+    return m;
+}
+
+extern "C" int pmx_seed_sketch_device(const pmx_seqset_t *Q, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t k, int32_t w, int strand_mode,
+                                      uint8_t *d_flags, void *stream)
+{
+    const int strands = seed_sketch_check(Q, q_first, nq, max_qlen, k, w, strand_mode, d_flags);
+    if (strands < 0) return -1;
+    if (nq == 0) return 0;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { set_err("no usable HIP device"); return -1; }
+    if (Q->dev != dev) { set_err("a sequence set of device %d cannot be used on the current device %d", Q->dev, dev); return -1; }
+    const int rc = pmx_launch_seed_sketch_rows(Q->d_buf, Q->d_off, Q->bytes, q_first, nq * strands, strands, strand_mode == PMX_STRAND_REVERSE ? 1 : 0, max_qlen,
+                                               k, w, d_flags, (hipStream_t)stream);
+    if (rc) set_err("seed sketch failed (%d)", rc);
+    return rc;
+}
+
+extern "C" int pmx_seed_sketch(const pmx_seqset_t *Q, int64_t q_first, int64_t nq, int32_t max_qlen, int32_t k, int32_t w, int strand_mode,
+                               uint8_t *flags, void *stream)
+{
+    const int strands = seed_sketch_check(Q, q_first, nq, max_qlen, k, w, strand_mode, flags);
+    if (strands < 0) return -1;
+    if (nq == 0) return 0;
+    const size_t total = (size_t)nq * (size_t)strands * (size_t)max_qlen;
+    uint8_t *d_flags = nullptr;
+    if (scratch_reserve(total, (void **)&d_flags, SCR_SEEDHIT)) return -1;
+    if (pmx_seed_sketch_device(Q, q_first, nq, max_qlen, k, w, strand_mode, d_flags, stream)) return -1;
+    HIP_OR_RET(hipMemcpyAsync(flags, d_flags, total, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_OR_RET(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
 }
 
 // The built-in reduced alphabets: one string of letters per group
@@ -6019,10 +6174,10 @@ static int seed_mode_orients(int query_mode)
 // genetic code), ref_mode (translated); k, bits, ref_count: the index's; budget: the match buffer in bytes.
 // 0 planned; 1 one row's worst case does not fit the budget: the plan is filled up to the slice, which then has no size.
 static int seed_plan(int kind, int mode, const uint8_t *code, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t &o, int k, int bits, int64_t ref_count,
-                     int64_t budget, PmxSeedPlan *out)
+                     int64_t budget, PmxSeedPlan *out, int w = 1)
 {
     PmxSeedPlan p = {};
-    p.kind = kind; p.max_qlen = max_qlen; p.k = k; p.bits = bits; p.ref_count = ref_count;
+    p.kind = kind; p.max_qlen = max_qlen; p.k = k; p.bits = bits; p.ref_count = ref_count; p.w = w;
     p.band = o.band; p.min_seeds = o.min_seeds; p.pad = o.pad; p.max_occ = o.max_occ;
     if (code) memcpy(p.code.v, code, 64); else pmx_genetic_code_host(p.code.v);
     p.orients = p.segs = 1;
@@ -6038,7 +6193,7 @@ static int seed_plan(int kind, int mode, const uint8_t *code, int64_t nq, int32_
     } else
         p.geom = mode == PMX_SEED_REF_CODONS ? PMX_SEED_GEOM_REF_CODONS : PMX_SEED_GEOM_REF_FRAMES;       // the rows are proteins: one segment each
     p.row_slots = (int64_t)p.orients * max_qlen; p.seg_slots = p.row_slots / p.segs;
-    p.pos_bytes = kind == PMX_SEED_KIND_DNA ? PMX_SEED_POS_BYTES : PMX_SEED_POS_BYTES_LETTERS;
+    p.pos_bytes = kind != PMX_SEED_KIND_DNA ? PMX_SEED_POS_BYTES_LETTERS : w > 1 ? PMX_SEED_POS_BYTES_MINIMIZERS : PMX_SEED_POS_BYTES;
     p.key_bits = 33;                                     // the diagonal and the bits of an id: a reference, times the six frames of a translated index
     while (p.key_bits < 64 && ((int64_t)1 << (p.key_bits - 32)) < (kind == PMX_SEED_KIND_TRANSLATED ? 6 : 1) * ref_count) ++p.key_bits;
     *out = p;
@@ -6055,19 +6210,26 @@ static int seed_plan(int kind, int mode, const uint8_t *code, int64_t nq, int32_
 }
 
 /* Test hook (include/parasail_amd.h): the plan with the budget as an argument; no device needed. */
-extern "C" int pmx_seed_plan_probe(int kind, int mode, long long nq, int max_qlen, int max_occ, long long slice_rows, long long budget,
-                                   long long ref_count, long long *out)
+extern "C" int pmx_seed_plan_probe_w(int kind, int mode, long long nq, int max_qlen, int max_occ, long long slice_rows, long long budget,
+                                     long long ref_count, int w, long long *out)
 {
     if (!out || kind < PMX_SEED_KIND_DNA || kind > PMX_SEED_KIND_TRANSLATED || nq < 1 || max_qlen < 1 || max_occ < 1 || slice_rows < 0 || ref_count < 0) return -1;
+    if (w < 1 || w > 64 || (w > 1 && kind != PMX_SEED_KIND_DNA)) return -1;
     pmx_seed_opts_t o = {};
     o.strand = kind == PMX_SEED_KIND_DNA ? mode : 0; o.max_occ = max_occ; o.slice_rows = slice_rows;
     PmxSeedPlan p;
-    const int rc = seed_plan(kind, mode, nullptr, nq, max_qlen, o, 0, 0, ref_count, budget > 0 ? std::min<int64_t>(budget, (int64_t)1 << 34) : (int64_t)PMX_PAIRS_CHUNK_BYTES, &p);
+    const int rc = seed_plan(kind, mode, nullptr, nq, max_qlen, o, 0, 0, ref_count, budget > 0 ? std::min<int64_t>(budget, (int64_t)1 << 34) : (int64_t)PMX_PAIRS_CHUNK_BYTES, &p, w);
     const bool oriented = kind == PMX_SEED_KIND_DNA || p.rows_translated;
     const long long v[11] = {p.orients, oriented ? p.first : -1, p.segs, p.seg_slots, p.row_slots, p.pos_bytes, p.slice_rows, p.cap_m, p.positions, p.slots,
                              p.key_bits};
     for (int i = 0; i < 11; ++i) out[i] = rc ? 0 : v[i];
     return rc;
+}
+
+extern "C" int pmx_seed_plan_probe(int kind, int mode, long long nq, int max_qlen, int max_occ, long long slice_rows, long long budget,
+                                   long long ref_count, long long *out)
+{
+    return pmx_seed_plan_probe_w(kind, mode, nq, max_qlen, max_occ, slice_rows, budget, ref_count, 1, out);
 }
 
 // What the seeding entries refuse about their arguments, and behind that the run's plan.  kind / mode: the entry's (seed_plan); lens_known
@@ -6109,7 +6271,7 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int kind, i
     if (o->pad < 0 || o->pad > PMX_SEED_BAND_MAX) { set_err("pad %d is outside 0 .. 2^20", (int)o->pad); return -1; }
     if (o->max_occ < 1 || o->max_occ > 65535) { set_err("max_occ %d is outside 1 .. 65535", (int)o->max_occ); return -1; }
     if (o->reserved != 0) { set_err("reserved must be 0"); return -1; }
-    if (seed_plan(kind, mode, code, nq, max_qlen, *o, ix->k, ix->bits, ix->R->count, seed_match_budget(), plan)) {
+    if (seed_plan(kind, mode, code, nq, max_qlen, *o, ix->k, ix->bits, ix->R->count, seed_match_budget(), plan, ix->w)) {
         set_err("one row's worst case of %d positions x %d %s x max_occ %d x %d bytes per match does not fit the match buffer of %lld bytes: "
                 "lower max_occ or split the queries", (int)max_qlen, plan->orients, dna ? "strand(s)" : "orientation(s)", (int)o->max_occ,
                 PMX_SEED_MATCH_BYTES, (long long)seed_match_budget());
@@ -6141,6 +6303,7 @@ static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_fir
             s.head = c.take<uint32_t>((size_t)p.cap_m); s.flag = c.take<uint32_t>((size_t)p.cap_m + 1);
             s.cut = c.take<int64_t>(2); s.temp = c.take<unsigned char>(s.temp_bytes);
             if (p.kind != PMX_SEED_KIND_DNA) s.codes = c.take<uint8_t>((size_t)p.positions);
+            if (p.w > 1) s.mflag = c.take<uint8_t>((size_t)p.positions);
         })) return -1;
     const PmxSeedSource src = {ix->keys, ix->vals, ix->bucket, ix->shift, ix->d_table, ix->R->d_off, Q->d_buf, Q->d_off, Q->bytes};
     for (int64_t row = 0; row < nq;) {

@@ -450,6 +450,7 @@ int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, 
 #define PMX_SEED_MATCH_BYTES 24        // per match: two sort buffers of 8-byte keys, the head index, the candidate flag / position
 #define PMX_SEED_POS_BYTES   16        // per position slot: first entry, occurrences, match offset
 #define PMX_SEED_POS_BYTES_LETTERS (PMX_SEED_POS_BYTES + 1)        // ... and the code byte of a letters or translated index
+#define PMX_SEED_POS_BYTES_MINIMIZERS (PMX_SEED_POS_BYTES + 1)     // ... or the flag byte of a minimizer index (w > 1)
 size_t pmx_seed_index_sort_bytes(long long bytes, int k);
 int pmx_launch_seed_index(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k,
                           uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out, void *temp, size_t temp_bytes,
@@ -467,6 +468,29 @@ int pmx_launch_seed_index_letters(const uint8_t *buf, const int64_t *off, long l
 int pmx_launch_seed_index_translated(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int bits, const uint8_t *table,
                                      const PmxCodeTable &code, int nstr, int strand0, uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out,
                                      uint64_t *vals_out, void *temp, size_t temp_bytes, unsigned long long *n_valid, hipStream_t stream);
+// Minimizers (definitions: include/parasail_amd.h).  mix: the order of the k-mers, a bijection on the 2 k bits of a key --
+// every step (xor with a constant, multiplication by an odd number modulo 2^2k, xor with the own upper half) is one.
+__host__ __device__ __forceinline__ uint64_t pmx_seed_mix_bits(uint64_t key, int k)
+{
+    const uint64_t m = ((uint64_t)1 << (2 * k)) - 1;
+    uint64_t h = (key ^ PMX_SEED_MIX_XOR) & m;
+    h = (h * PMX_SEED_MIX_MUL1) & m; h ^= h >> k;
+    h = (h * PMX_SEED_MIX_MUL2) & m; h ^= h >> k;
+    return h;
+}
+// The sketch kernel's two forms (pmx_seed_sketch_kernel).  set: flags[p] for every byte p of the set's buffer and their exclusive scan
+// at[0 .. bytes] (at[bytes] = the minimizers; flags: bytes + 1 bytes, 4-byte aligned; temp: pmx_seed_sketch_scan_bytes(bytes)).
+// selected: the flagged positions as compact (key, val) pairs, sorted (n > 0 of them; temp: pmx_seed_index_sort_bytes(n, k)).  rows:
+// one byte per position slot (seg * max_qlen + i) of `segs` (row, orientation) segments from row0.  tiles: positions per workgroup.
+void pmx_seed_sketch_tiles(int *row_tile, int *set_tile);
+size_t pmx_seed_sketch_scan_bytes(long long bytes);
+int pmx_launch_seed_sketch_set(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int w, uint8_t *flags, uint32_t *at,
+                               void *temp, size_t temp_bytes, hipStream_t stream);
+int pmx_launch_seed_index_selected(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, const uint8_t *flags,
+                                   const uint32_t *at, long long n, uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out,
+                                   void *temp, size_t temp_bytes, hipStream_t stream);
+int pmx_launch_seed_sketch_rows(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long segs, int strands, int strand0,
+                                int max_qlen, int k, int w, uint8_t *flags, hipStream_t stream);
 // A seeding run, described once (filled by seed_plan of pmx_api.hip, host arithmetic only; pinned by tests/test_seed_plans.py).
 // A row has `orients` orientations of max_qlen position slots each: the strands of a DNA query, the frames of a translated one, the row
 // itself.  The sort's segments -- what one candidate's matches share -- are `segs` per row of seg_slots position slots each, and the
@@ -487,6 +511,7 @@ struct PmxSeedPlan {
     int max_qlen, k, bits, key_bits;       // bits per letter of the index; the sorted bits of a match key (the diagonal and the id)
     long long ref_count;                   // the sequences of the indexed set
     int band, min_seeds, pad, max_occ;
+    int w;                                 // the window of a DNA index: 1 every k-mer, > 1 minimizers (one flag byte more per position slot)
     PmxCodeTable code;                     // read where rows_translated
     long long slice_rows, cap_m, positions, slots;      // a slice: its rows at most, matches at most, position slots, rows x orients
 };
@@ -497,9 +522,11 @@ struct PmxSeedSource {
     const uint8_t *qbuf; const int64_t *qoff; long long q_bytes;
 };
 // ... a slice's scratch (lo, moff: positions, cnt: positions + 1; keys_a / keys_b / head: cap_m, flag: cap_m + 1; cut: 2; codes:
-// positions, NULL with a DNA index; temp: pmx_seed_temp_bytes(positions, cap_m, slots)) ...
+// positions, NULL with a DNA index; mflag: positions, the rows' minimizer flags, NULL unless the plan's w > 1; temp:
+// pmx_seed_temp_bytes(positions, cap_m, slots)) ...
 struct PmxSeedSlice {
     uint32_t *lo, *cnt; int64_t *moff; uint64_t *keys_a, *keys_b; uint32_t *head, *flag; int64_t *cut; uint8_t *codes; void *temp; size_t temp_bytes;
+    uint8_t *mflag;
 };
 // ... and where the candidates go: `capacity` entries each (seeds optional), row offsets, counts[0 .. 1].
 struct PmxSeedOut { pmx_pair_t *pairs; uint8_t *byte; pmx_seed_hit_t *seeds; long long capacity; int64_t *row_off, *counts; };

@@ -165,6 +165,234 @@ int pmx_launch_seed_entries(const uint64_t *keys, const uint64_t *vals, long lon
     return pmx_launched();
 }
 
+// ---- minimizers: the (w, k) sketch of a set's buffer or of oriented rows -----------------------------------------------
+// Definitions: include/parasail_amd.h.  A position loses to p iff it has no k-mer or its (hash, position) is larger; a window of w
+// consecutive k-mer positions of one sequence selects the position every other one loses to; a minimizer is a position some window
+// selects.  The kernel decides each position on its own by the equivalent rule: with l the consecutive left neighbours that lose to p
+// (at most w - 1, none before the sequence's first position) and r the same to the right (none behind its last k-mer position nk - 1),
+// p is a minimizer iff it has a k-mer and l + r + 1 >= min(w, nk).  A thread writes only its own positions' bytes: no marking across
+// threads, no atomics, the same bytes every run.
+//
+// One body, two forms.  A workgroup owns a tile of T = 256 C positions of a position space -- the set's buffer (C = 4: byte p of the
+// buffer is position p, whatever sequence it lies in) or one (row, orientation) segment of max_qlen slots (C = 1: reads are short) --
+// and stages the 2-bit codes of the tile, a halo of w - 1 positions on both sides and the k - 1 letters behind it in LDS, each byte read
+// from memory once.  Every thread then rolls the keys of a contiguous piece of tile + halo out of LDS and leaves their hashes there.
+// Traps:
+//   * "no k-mer" is PMX_SKETCH_NONE = 2^64 - 1, which no hash takes: mix is a bijection on 2 k <= 62 bits, so a hash is below 2^62.
+//   * the halo never lets a window cross a sequence end: the staged codes know nothing of sequences (a key rolled across an end is a
+//     valid-looking hash), so the scan of p is clamped to the k-mer positions [b, e - k] of p's OWN sequence [b, e), which the thread
+//     finds itself (pmx_seed_region); a row's segment is one sequence, [0, nk).
+//   * strand 1 is read backwards through the complement into the staged codes, so positions, windows and the leftmost-wins rule are all
+//     in oriented coordinates: the scans below never see the stored order.
+#define PMX_SKETCH_NONE (~(uint64_t)0)
+#define PMX_SKETCH_WMAX 64
+#define PMX_SKETCH_KMAX 31
+#define PMX_SKETCH_SET_C 4      // positions per thread, set form: T = 1024
+#define PMX_SKETCH_ROW_C 1      // row form: T = 256
+
+// the staged letters of the set form: position x is byte x of the buffer
+struct PmxSketchSetCodes {
+    const uint8_t *__restrict__ buf; long long bytes;
+    __device__ __forceinline__ uint32_t operator()(long long x) const
+    {
+        if (x < 0 || x >= bytes) return 4u;
+        const int c = pmx_seed_code(buf[x]);
+        return c < 0 ? 4u : (uint32_t)c;
+    }
+};
+// ... and of the row form: position x of the oriented row w of L letters (strand 1: comp[w[L - 1 - x]], never materialised)
+struct PmxSketchRowCodes {
+    const uint8_t *__restrict__ w; long long L; int strand;
+    __device__ __forceinline__ uint32_t operator()(long long x) const
+    {
+        if (x < 0 || x >= L) return 4u;
+        const int c = pmx_seed_code(strand ? w[L - 1 - x] : w[x]);
+        return c < 0 ? 4u : (uint32_t)(strand ? 3 - c : c);
+    }
+};
+
+// H[a] = the hash of position t0 - (w - 1) + a for a in [0, T + 2 (w - 1)), PMX_SKETCH_NONE where k valid letters do not start there.
+// cod: T + 2 (w - 1) + k - 1 bytes of LDS.  Every thread of the workgroup calls it (two barriers).
+template <int C, typename Codes>
+__device__ __forceinline__ void pmx_sketch_hashes(const Codes &codes, long long t0, int k, int w, uint64_t *H, uint8_t *cod)
+{
+    const int S = 256 * C + 2 * (w - 1), nbytes = S + k - 1;
+    const long long x0 = t0 - (w - 1);
+    for (int a = threadIdx.x; a < nbytes; a += 256) cod[a] = (uint8_t)codes(x0 + a);
+    __syncthreads();
+    const int per = (S + 255) / 256, a0 = (int)threadIdx.x * per, a1 = min(a0 + per, S);
+    const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;
+    uint64_t key = 0; int run = 0;
+    for (int a = a0; a0 < a1 && a < a1 + k - 1; ++a) {
+        const uint32_t c = cod[a];
+        run = c > 3u ? 0 : run + 1;
+        key = (key << 2) | (uint64_t)(c & 3u);
+        if (a - (k - 1) >= a0) H[a - (k - 1)] = run >= k ? pmx_seed_mix_bits(key & mask, k) : PMX_SKETCH_NONE;
+    }
+    __syncthreads();
+}
+
+// The per-position rule on the hashes in LDS: a = p's index in H, [lo, hi] = the indices of the positions of p's sequence that a window
+// with p may hold (lo >= a - (w - 1), hi <= a + (w - 1)), need = min(w, nk).  Left neighbours lose on a larger hash (an equal one is
+// left of p and wins), right ones on a larger or equal one; the scan stops at the first that does not lose or once `need` are together.
+__device__ __forceinline__ bool pmx_sketch_selected(const uint64_t *H, int a, int lo, int hi, int need)
+{
+    const uint64_t hp = H[a];
+    if (hp == PMX_SKETCH_NONE) return false;
+    int got = 1;
+    for (int q = a - 1; q >= lo && got < need && H[q] > hp; --q) ++got;
+    for (int q = a + 1; q <= hi && got < need && H[q] >= hp; ++q) ++got;
+    return got >= need;
+}
+
+struct PmxSketchArgs {
+    const uint8_t *buf; const int64_t *off; long long count, bytes;       // set form: the set; row form: Q's buffer, offsets, -, bytes
+    long long row0; int strands, strand0, max_qlen, tiles;                 // row form: the slice's first row, orientations, tiles per segment
+    int k, w;
+    uint8_t *flags;                                                        // one byte per position (set form) / per position slot (row form)
+};
+
+// flags[p] = 1 where position p is a minimizer, 0 elsewhere, for every position of the space.
+// ROWS false: the set's buffer, walked as pmx_seed_extract_kernel walks it (offsets read at 0 .. count only, bytes below `bytes` only);
+//   a thread owns C = 4 consecutive bytes and packs their flags into one store.
+// ROWS true: block = (segment, tile); segment t = (row_local * strands + s), slot (t * max_qlen + i).  A row longer than max_qlen or
+//   with bad offsets has no minimizer.
+template <bool ROWS>
+__global__ void __launch_bounds__(256) pmx_seed_sketch_kernel(PmxSketchArgs g)
+{
+    constexpr int C = ROWS ? PMX_SKETCH_ROW_C : PMX_SKETCH_SET_C, T = 256 * C;
+    __shared__ uint64_t H[T + 2 * (PMX_SKETCH_WMAX - 1)];
+    __shared__ uint8_t cod[T + 2 * (PMX_SKETCH_WMAX - 1) + PMX_SKETCH_KMAX - 1 + 2];
+    const int k = g.k, w = g.w, halo = w - 1;
+    if (ROWS) {
+        const long long t = (long long)blockIdx.x / g.tiles, t0 = ((long long)blockIdx.x - t * g.tiles) * T;
+        const long long row = g.row0 + t / g.strands;
+        const int strand = g.strands == 2 ? (int)(t & 1) : g.strand0;
+        const long long b = g.off[row], e = g.off[row + 1];
+        const bool good = b >= 0 && e >= b && e <= g.bytes && e - b <= g.max_qlen;
+        const long long L = good ? e - b : 0, nk = L - k + 1;
+        const long long i = t0 + threadIdx.x;
+        uint8_t *out = g.flags + t * g.max_qlen;
+        if (t0 >= nk) { if (i < g.max_qlen) out[i] = 0; return; }          // (the whole workgroup: nothing of the tile has a k-mer)
+        pmx_sketch_hashes<C>(PmxSketchRowCodes{g.buf + b, L, strand}, t0, k, w, H, cod);
+        if (i >= g.max_qlen) return;
+        bool sel = false;
+        if (i < nk) {
+            const int a = (int)threadIdx.x + halo;
+            sel = pmx_sketch_selected(H, a, a - (int)min((long long)halo, i), a + (int)min((long long)halo, nk - 1 - i), (int)min((long long)w, nk));
+        }
+        out[i] = sel ? 1 : 0;
+    } else {
+        const long long t0 = (long long)blockIdx.x * T;
+        pmx_sketch_hashes<C>(PmxSketchSetCodes{g.buf, g.bytes}, t0, k, w, H, cod);
+        const long long p0 = t0 + (long long)threadIdx.x * C;
+        if (p0 >= g.bytes) return;
+        PmxSeedRegion r = pmx_seed_region(g.off, g.count, p0);
+        uint32_t packed = 0;
+        const int n = (int)min((long long)C, g.bytes - p0);
+        for (int j = 0; j < n; ++j) {
+            const long long p = p0 + j;
+            (void)pmx_seed_region_advance(r, g.off, g.count, p);
+            bool sel = false;
+            if (pmx_seed_region_inside(r, g.count, g.bytes, p) && p + k <= r.e) {
+                const long long nk = r.e - r.b - k + 1;
+                const int a = (int)(p - t0) + halo;
+                sel = pmx_sketch_selected(H, a, a - (int)min((long long)halo, p - r.b), a + (int)min((long long)halo, r.e - k - p), (int)min((long long)w, nk));
+            }
+            packed |= (sel ? 1u : 0u) << (8 * j);
+        }
+        if (n == C) *(uint32_t *)(g.flags + p0) = packed;                   // p0 is a multiple of 4 and so is the buffer's address
+        else for (int j = 0; j < n; ++j) g.flags[p0 + j] = (uint8_t)(packed >> (8 * j));
+    }
+}
+
+// The compact entries of a minimizer index: pmx_seed_extract_kernel's walk, writing only the flagged positions, each at its scanned
+// place at[p] -- input order is buffer order, so the stable sort leaves (kmer, seq, pos) order.
+__global__ void __launch_bounds__(256) pmx_seed_scatter_kernel(const uint8_t *__restrict__ buf, const int64_t *__restrict__ off, long long count,
+                                                               long long bytes, int k, const uint8_t *__restrict__ flags, const uint32_t *__restrict__ at,
+                                                               uint64_t *__restrict__ keys, uint64_t *__restrict__ vals)
+{
+    const long long p0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * PMX_SEED_TILE;
+    if (p0 >= bytes) return;
+    const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;
+    PmxSeedRegion g = pmx_seed_region(off, count, p0);
+    const long long pend = min(p0 + PMX_SEED_TILE, bytes), xend = min(pend + k - 1, bytes);
+    uint64_t key = 0; int run = 0;
+    for (long long x = p0; x < xend; ++x) {
+        if (pmx_seed_region_advance(g, off, count, x)) run = 0;
+        const int c = pmx_seed_region_inside(g, count, bytes, x) ? pmx_seed_code(buf[x]) : -1;
+        if (c < 0) { run = 0; key = 0; } else { key = (key << 2) | (uint64_t)c; ++run; }
+        const long long s = x - k + 1;
+        if (s >= p0 && flags[s] && run >= k && s >= g.b) {
+            const uint32_t o = at[s];
+            keys[o] = key & mask;
+            vals[o] = ((uint64_t)g.r << 32) | (uint64_t)(uint32_t)(s - g.b);
+        }
+    }
+}
+
+struct PmxWidenU8 { __device__ __host__ uint32_t operator()(uint8_t v) const { return (uint32_t)v; } };
+
+void pmx_seed_sketch_tiles(int *row_tile, int *set_tile)
+{
+    if (row_tile) *row_tile = 256 * PMX_SKETCH_ROW_C;
+    if (set_tile) *set_tile = 256 * PMX_SKETCH_SET_C;
+}
+
+size_t pmx_seed_sketch_scan_bytes(long long bytes)
+{
+    size_t temp = 0;
+    auto in = rocprim::make_transform_iterator((const uint8_t *)nullptr, PmxWidenU8());
+    (void)rocprim::exclusive_scan(nullptr, temp, in, (uint32_t *)nullptr, 0u, (size_t)(bytes + 1), rocprim::plus<uint32_t>(), nullptr);
+    return temp + 256;
+}
+
+// flags: bytes + 1 bytes (the last one zeroed here: the scan's total), 4-byte aligned; at: bytes + 1 places, at[bytes] = the entries
+int pmx_launch_seed_sketch_set(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, int w, uint8_t *flags, uint32_t *at,
+                               void *temp, size_t temp_bytes, hipStream_t stream)
+{
+    if (bytes <= 0) return 0;
+    if (hipMemsetAsync(flags + bytes, 0, 1, stream) != hipSuccess) return -1;
+    PmxSketchArgs g = {};
+    g.buf = buf; g.off = off; g.count = count; g.bytes = bytes; g.k = k; g.w = w; g.flags = flags;
+    const long long T = 256 * PMX_SKETCH_SET_C;
+    hipLaunchKernelGGL(pmx_seed_sketch_kernel<false>, dim3((unsigned)((bytes + T - 1) / T)), dim3(256), 0, stream, g);
+    int rc = pmx_launched();
+    if (rc) return rc;
+    auto in = rocprim::make_transform_iterator((const uint8_t *)flags, PmxWidenU8());
+    const hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, in, at, 0u, (size_t)(bytes + 1), rocprim::plus<uint32_t>(), stream);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+// the n > 0 flagged positions as compact entries into keys_in / vals_in, sorted into keys_out / vals_out (n entries each; temp:
+// pmx_seed_index_sort_bytes(n, k))
+int pmx_launch_seed_index_selected(const uint8_t *buf, const int64_t *off, long long count, long long bytes, int k, const uint8_t *flags,
+                                   const uint32_t *at, long long n, uint64_t *keys_in, uint64_t *vals_in, uint64_t *keys_out, uint64_t *vals_out,
+                                   void *temp, size_t temp_bytes, hipStream_t stream)
+{
+    if (bytes <= 0 || n <= 0) return 0;
+    const long long threads = (bytes + PMX_SEED_TILE - 1) / PMX_SEED_TILE;
+    hipLaunchKernelGGL(pmx_seed_scatter_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, buf, off, count, bytes, k, flags, at,
+                       keys_in, vals_in);
+    int rc = pmx_launched();
+    if (rc) return rc;
+    const hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, 2 * k + 1, stream);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+// flags: segs * max_qlen bytes, every one written; segs = rows x strands of the slice (segs x tiles per segment < 2^31)
+int pmx_launch_seed_sketch_rows(const uint8_t *qbuf, const int64_t *qoff, long long q_bytes, long long row0, long long segs, int strands, int strand0,
+                                int max_qlen, int k, int w, uint8_t *flags, hipStream_t stream)
+{
+    if (segs <= 0) return 0;
+    const int T = 256 * PMX_SKETCH_ROW_C;
+    PmxSketchArgs g = {};
+    g.buf = qbuf; g.off = qoff; g.bytes = q_bytes; g.row0 = row0; g.strands = strands; g.strand0 = strand0; g.max_qlen = max_qlen;
+    g.tiles = (int)(((long long)max_qlen + T - 1) / T); g.k = k; g.w = w; g.flags = flags;
+    hipLaunchKernelGGL(pmx_seed_sketch_kernel<true>, dim3((unsigned)(segs * g.tiles)), dim3(256), 0, stream, g);
+    return pmx_launched();
+}
+
 // ---- seeding -------------------------------------------------------------------------------------------------------------------------
 // The index's entries of `key`: lo = the first one, cnt = how many; 0 / 0 where the k-mer is absent or occurs more than max_occ times.
 // One read of the bucket table, a lower bound inside the bucket, the probe at lo + max_occ, an upper bound below it.
@@ -188,21 +416,23 @@ __device__ __forceinline__ void pmx_seed_lookup(uint64_t key, const uint64_t *__
 // Position slot p = (row_local * strands + s) * max_qlen + i.  lo[p]: the first index entry of the slot's k-mer, cnt[p]: its
 // occurrences, 0 where the oriented query has no k-mer at i, the k-mer is absent or it occurs more than max_occ times.  cnt has one
 // entry more than there are slots (0: the scan's total).  The key comes straight from the row's bytes: no code stage on this road.
-__global__ void __launch_bounds__(256) pmx_seed_count_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
-                                                             long long row0, long long slots, int strands, int strand0, int max_qlen, int k,
-                                                             const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
-                                                             int max_occ, uint32_t *__restrict__ lo_out, uint32_t *__restrict__ cnt_out)
+__device__ __forceinline__ void pmx_seed_count_slot(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
+                                                    long long row0, long long slots, int strands, int strand0, int max_qlen, int k,
+                                                    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
+                                                    int max_occ, const uint8_t *__restrict__ mflag, uint32_t *__restrict__ lo_out,
+                                                    uint32_t *__restrict__ cnt_out)
 {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long total = slots * max_qlen;
     if (p > total) return;
     if (p == total) { cnt_out[p] = 0; return; }
+    uint32_t lo = 0, cnt = 0;
+    if (mflag && !mflag[p]) { lo_out[p] = lo; cnt_out[p] = cnt; return; }      // not a minimizer of the oriented row: no look-up
     const long long t = p / max_qlen;
     const int i = (int)(p - t * max_qlen);
     const long long row = row0 + t / strands;
     const int strand = strands == 2 ? (int)(t & 1) : strand0;
     const long long b = qoff[row], e = qoff[row + 1];
-    uint32_t lo = 0, cnt = 0;
     if (b >= 0 && e >= b && e <= q_bytes && e - b <= max_qlen && i + k <= e - b) {
         const uint8_t *w = qbuf + b;
         const int L = (int)(e - b);
@@ -215,6 +445,23 @@ __global__ void __launch_bounds__(256) pmx_seed_count_kernel(const uint8_t *__re
         if (ok) pmx_seed_lookup(key, keys, bucket, shift, max_occ, lo, cnt);
     }
     lo_out[p] = lo; cnt_out[p] = cnt;
+}
+__global__ void __launch_bounds__(256) pmx_seed_count_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
+                                                             long long row0, long long slots, int strands, int strand0, int max_qlen, int k,
+                                                             const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
+                                                             int max_occ, uint32_t *__restrict__ lo_out, uint32_t *__restrict__ cnt_out)
+{
+    pmx_seed_count_slot(qbuf, qoff, q_bytes, row0, slots, strands, strand0, max_qlen, k, keys, bucket, shift, max_occ, nullptr, lo_out, cnt_out);
+}
+// The flagged form (a minimizer index, w > 1): mflag[p] is the row form's byte of the slot (pmx_seed_sketch_kernel); a slot whose flag is
+// 0 writes lo = cnt = 0 without a look-up.
+__global__ void __launch_bounds__(256) pmx_seed_count_flagged_kernel(const uint8_t *__restrict__ qbuf, const int64_t *__restrict__ qoff, long long q_bytes,
+                                                                     long long row0, long long slots, int strands, int strand0, int max_qlen, int k,
+                                                                     const uint64_t *__restrict__ keys, const uint32_t *__restrict__ bucket, int shift,
+                                                                     int max_occ, const uint8_t *__restrict__ mflag, uint32_t *__restrict__ lo_out,
+                                                                     uint32_t *__restrict__ cnt_out)
+{
+    pmx_seed_count_slot(qbuf, qoff, q_bytes, row0, slots, strands, strand0, max_qlen, k, keys, bucket, shift, max_occ, mflag, lo_out, cnt_out);
 }
 
 // out[0] = the largest m <= rows whose matches moff[m * stride] fit `cap`; out[1] = that number of matches
@@ -646,7 +893,12 @@ int pmx_launch_seed_count(const PmxSeedPlan &p, const PmxSeedSlice &s, const Pmx
     const long long total = rows * p.row_slots;
     const dim3 cb((unsigned)((total + 1 + 255) / 256));
     int rc = 0;
-    if (p.kind == PMX_SEED_KIND_DNA)
+    if (p.kind == PMX_SEED_KIND_DNA && p.w > 1) {           // a minimizer index: the rows' own minimizers first, then only their look-ups
+        if ((rc = pmx_launch_seed_sketch_rows(src.qbuf, src.qoff, src.q_bytes, row0, rows * p.orients, p.orients, p.first, p.max_qlen, p.k, p.w, s.mflag, stream)))
+            return rc;
+        hipLaunchKernelGGL(pmx_seed_count_flagged_kernel, cb, dim3(256), 0, stream, src.qbuf, src.qoff, src.q_bytes, row0, rows * p.orients, p.orients, p.first,
+                           p.max_qlen, p.k, src.keys, src.bucket, src.shift, p.max_occ, (const uint8_t *)s.mflag, s.lo, s.cnt);
+    } else if (p.kind == PMX_SEED_KIND_DNA)
         hipLaunchKernelGGL(pmx_seed_count_kernel, cb, dim3(256), 0, stream, src.qbuf, src.qoff, src.q_bytes, row0, rows * p.orients, p.orients, p.first,
                            p.max_qlen, p.k, src.keys, src.bucket, src.shift, p.max_occ, s.lo, s.cnt);
     else {
