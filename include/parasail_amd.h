@@ -1434,6 +1434,65 @@ int64_t pmx_seed_rows_max_len(const pmx_seqset_t *Q, int64_t q_first, int64_t nq
 /* Test hook: the positions a workgroup of the sketch kernel owns, in its row form and its set form. */
 void pmx_seed_sketch_shape(int32_t *row_tile, int32_t *set_tile);
 
+/* Seed chaining (extension): collinear chains with gap costs in place of diagonal clusters, for a DNA index -- stride 1 or minimizers,
+ * any w (kernel: pmx_seed_chain_kernel of parasail-rs_amd/csrc/pmx_seed.hip).  A cluster knows a match's diagonal only;
+ * a chain also knows where along the read it lies, so a long indel does not split a locus and two distant matches on one diagonal
+ * do not merge.  Opt-in and additive: pmx_seed_pairs[_device] and every other entry do what they did.
+ *
+ * Definitions.  Letters, k-mers, the oriented query, max_occ, the matches (i, j) of (q, s, r) and minimizer sampling are
+ * pmx_seed_pairs' definitions above, unchanged.
+ *   Anchor order.  The matches of (q, s, r) are ordered ascending by (j, i).  a and b are positions in that order, which has no ties:
+ *              an (i, j) occurs once.
+ *   Link.      b < a may precede a iff, with dj = j_a - j_b and di = i_a - i_b, all of these hold:
+ *                dj >= 1 and di >= 1;   dj <= max_gap and di <= max_gap;   g = |dj - di| <= band;   a - b <= lookback.
+ *              Anchors of different r, strand or row never link.
+ *   Cost.      Integers only: cost(0) = 0; for g >= 1: cost(g) = ((int64)g * gap_scale >> 8) + ((32 - clz(g)) >> 1).
+ *              With gap_scale = 38 this is about minimap2's 0.01 k g + 0.5 log2 g at k = 15.
+ *   Score.     f(a) = max(k, max_b f(b) + min(di, dj, k) - cost(g)) over the admissible b.  pred(a) is the b that attains the
+ *              maximum, taken only when the value is strictly above k; among equal values the nearest b (the largest) wins;
+ *              pred(a) = -1 otherwise.
+ *   Chains.    child(b) is, among the a with pred(a) = b, the one with the largest f(a); among equal values the smallest a wins.
+ *              The link a -> pred(a) is kept iff child(pred(a)) = a.  Chains are the maximal paths of kept links, so they are disjoint
+ *              and every anchor is in exactly one.  The head h of a chain has no kept link to a predecessor, the tail t has no child.
+ *              A chain's score is f(t) - f(pred(h)), or f(t) when pred(h) = -1.
+ *   Candidate. A chain is a candidate iff score >= min_score and n_anchors >= min_seeds.  d_hit_pairs, d_hit_strand and
+ *              d_hit_seeds = {n_anchors, diag_min, diag_max, 0} follow the cluster road's rule exactly, over the chain's own anchors
+ *              (d = j - i): r_beg = max(0, diag_min - pad), r_end = min(len(r), diag_max + qlen + pad).  A chained list therefore goes
+ *              unchanged into pmx_align_pairs_ex[_device], pmx_seed_ungapped and pmx_seed_filter[_device] with PMX_SEED_BYTE_STRAND.
+ *              In addition an optional 32-byte record is written per candidate: pmx_seed_chain_t {score, n_anchors, q_beg = i_h,
+ *              q_end = i_t + k, r_beg = j_h, r_end = j_t + k, diag_min, diag_max}, coordinates of the oriented query and of the whole
+ *              reference.  Row q's candidates are ascending in (strand, r, the tail's (j, i)).
+ *   Determinism.  The output is bit-identical from run to run, under any slice_rows and any match budget.  No output position and no
+ *              tie is decided by an atomic: the sort is stable over matches emitted in ascending i, one wave walks a segment in anchor
+ *              order, and every output position is a scan.
+ *   Arithmetic.  f fits int32: i rises strictly along a chain, so a chain has at most max_qlen anchors of gain <= k <= 31 each, and
+ *              max_qlen <= 2^26 is required; cost < 2^28 (g <= 2^20, gap_scale < 2^16), so no intermediate leaves int32 either.
+ *
+ * pmx_seed_opts_t: strand, min_seeds, pad, max_occ, max_hits and slice_rows mean what they mean to pmx_seed_pairs; band (0 .. 2^20) is
+ * the link's bound on |dj - di|.  Capacity, d_row_off, d_counts, the one stream synchronisation per slice, nq == 0, the host entry's
+ * two-pass sizing and max_hits are pmx_seed_pairs[_device]'s, by the same code.  A match takes 40 bytes of scratch in place of 24.
+ *
+ * Refused with -1 and a pmx_last_error() text before any GPU work: everything pmx_seed_pairs_device refuses, with its texts; NULL
+ * copts; max_gap outside 1 .. 2^20; lookback outside 1 .. 1024; gap_scale outside 0 .. 65 535; min_score < 0; non-zero reserved; a
+ * letters or translated index (chaining takes a DNA index); max_qlen above 2^26; the per-row budget max_qlen x strands x max_occ x 40
+ * bytes.
+ *
+ * pmx_seed_chains returns one callee-allocated block released with pmx_seed_chained_free: hits as pmx_seed_pairs fills it, chains with
+ * hits.n_hits records.  pmx_seed_chain_shape (test hook): the lanes that evaluate predecessors at once and the anchors the kernel's
+ * ring holds at most. */
+typedef struct pmx_seed_chain_opts { int32_t max_gap, lookback, gap_scale, min_score, reserved[4]; } pmx_seed_chain_opts_t;   /* 32 bytes */
+typedef struct pmx_seed_chain { int32_t score, n_anchors, q_beg, q_end, r_beg, r_end, diag_min, diag_max; } pmx_seed_chain_t;  /* 32 bytes */
+int pmx_seed_chains_device(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq, int32_t max_qlen,
+                           const pmx_seed_opts_t *opts, const pmx_seed_chain_opts_t *copts,
+                           pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand, pmx_seed_hit_t *d_hit_seeds /* optional */,
+                           pmx_seed_chain_t *d_hit_chains /* optional */, int64_t capacity,
+                           int64_t *d_row_off /* nq + 1 */, int64_t *d_counts /* [0] candidates, [1] written */, void *stream);
+typedef struct pmx_seed_chained { pmx_seed_hits_t hits; pmx_seed_chain_t *chains; } pmx_seed_chained_t;
+int  pmx_seed_chains(const pmx_seqset_t *Q, const pmx_seed_index_t *index, int64_t q_first, int64_t nq,
+                     const pmx_seed_opts_t *opts, const pmx_seed_chain_opts_t *copts, pmx_seed_chained_t **result);
+void pmx_seed_chained_free(pmx_seed_chained_t *chained);
+void pmx_seed_chain_shape(int32_t *lanes, int32_t *ring);
+
 /* Protein seeding (extension): the same stage in front of the translated entries -- a k-mer index of a PROTEIN set over a reduced
  * alphabet, and a seeding entry whose queries are proteins or nucleotide reads translated on the device in up to six frames.  Its
  * candidate lists go unchanged into pmx_align_pairs_translated[_device] (a frame byte per pair) and pmx_align_pairs_frameshift[_device]

@@ -148,7 +148,22 @@ class pmx_seed_filtered_t(C.Structure):
     _fields_ = [("hits", pmx_seed_hits_t), ("ungapped", C.c_void_p), ("source", C.c_void_p)]
 
 
+class pmx_seed_chain_opts_t(C.Structure):
+    _fields_ = [("max_gap", C.c_int32), ("lookback", C.c_int32), ("gap_scale", C.c_int32), ("min_score", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class pmx_seed_chain_t(C.Structure):
+    _fields_ = [("score", C.c_int32), ("n_anchors", C.c_int32), ("q_beg", C.c_int32), ("q_end", C.c_int32), ("r_beg", C.c_int32),
+                ("r_end", C.c_int32), ("diag_min", C.c_int32), ("diag_max", C.c_int32)]
+
+
+class pmx_seed_chained_t(C.Structure):
+    _fields_ = [("hits", pmx_seed_hits_t), ("chains", C.c_void_p)]
+
+
 SEED_HIT_DTYPE = np.dtype([("n_seeds", "<i4"), ("diag_min", "<i4"), ("diag_max", "<i4"), ("reserved", "<i4")])
+SEED_CHAIN_DTYPE = np.dtype([("score", "<i4"), ("n_anchors", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"), ("r_beg", "<i4"), ("r_end", "<i4"),
+                             ("diag_min", "<i4"), ("diag_max", "<i4")])
 UNGAPPED_DTYPE = np.dtype([("score", "<i4"), ("diag", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4")])
 SEED_BYTE_STRAND, SEED_BYTE_FRAME = 0, 1
 SEED_LIST_CODONS, SEED_LIST_REF_FRAMES, SEED_LIST_REF_CODONS = 1, 2, 3
@@ -319,6 +334,12 @@ _sig("pmx_seed_pairs", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.
      C.POINTER(C.POINTER(pmx_seed_hits_t)))
 _sig("pmx_seed_hits_free", None, C.POINTER(pmx_seed_hits_t))
 _sig("pmx_seed_match_budget", C.c_int64, C.c_int64)
+_sig("pmx_seed_chains_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(pmx_seed_opts_t),
+     C.POINTER(pmx_seed_chain_opts_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("pmx_seed_chains", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(pmx_seed_opts_t), C.POINTER(pmx_seed_chain_opts_t),
+     C.POINTER(C.POINTER(pmx_seed_chained_t)))
+_sig("pmx_seed_chained_free", None, C.POINTER(pmx_seed_chained_t))
+_sig("pmx_seed_chain_shape", None, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 _sig("pmx_seed_mix", C.c_uint64, C.c_uint64, C.c_int32)
 _sig("pmx_seed_index_build_minimizers", C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
 _sig("pmx_seed_index_window", C.c_int32, C.c_void_p)
@@ -1992,7 +2013,8 @@ class SeedHits:
     "frames" (0 or 3, relative to the window; seeds["reserved"] is the sequence frame) and .strand holds it with "codons".
     kind says which list this is: "strand" (a DNA index), "letters", "frame" or "codons" (a letters index), "ref_frames" or
     "ref_codons" (a translated index); seed_filter and seed_filter_translated read it.  A list that either returns has .ungapped (UNGAPPED_DTYPE) and
-    .source (int64: the candidate's index in the list that was filtered) as well."""
+    .source (int64: the candidate's index in the list that was filtered) as well; the list of seed_chains has .chains
+    (SEED_CHAIN_DTYPE, one record per stored candidate)."""
 
     def __init__(self, r, byte_is_frame=False, kind=None):
         self.kind = kind
@@ -2126,6 +2148,56 @@ def seed_pairs_device(Q, index, q_first, nq, max_qlen, d_hit_pairs, d_hit_strand
     if device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), *extra, d_hit_pairs, d_hit_strand, d_hit_seeds,
               int(capacity), d_row_off, d_counts, stream):
         raise BatchError(lib.pmx_last_error().decode())
+
+
+def _seed_chain_opts(max_gap, lookback, gap_scale, min_score):
+    return pmx_seed_chain_opts_t(int(max_gap), int(lookback), int(gap_scale), int(min_score), (C.c_int32 * 4)(0, 0, 0, 0))
+
+
+def seed_chains(Q, index, strand=None, min_seeds=2, min_score=0, band=500, max_gap=5000, lookback=64, gap_scale=38, pad=16, max_occ=64,
+                first_row=0, rows=None, max_hits=0, slice_rows=0):
+    """Candidate windows of the queries Q[first_row : first_row + rows] by collinear chaining (include/parasail_amd.h, "Seed chaining"):
+    the matches of a (row, strand, reference) in (j, i) order, linked where both steps are 1 .. max_gap, their difference is at most
+    `band` and the predecessor is among the `lookback` anchors before; a link costs (g * gap_scale >> 8) + (bit length of g >> 1) for a
+    diagonal change g.  A chain of at least min_seeds anchors and a score of at least min_score is a candidate.  Takes a DNA index
+    (stride 1 or minimizers).  Returns a SeedHits of kind "strand" -- seed_filter and Aligner.align_pairs(Q, R, hits.pairs,
+    strand=hits.strand) take it as it is -- with .chains (SEED_CHAIN_DTYPE) added: score, n_anchors and the chain's extent on the
+    oriented query [q_beg, q_end) and the reference [r_beg, r_end).  strand: "both" unless given."""
+    if rows is None:
+        rows = max(0, len(Q) - int(first_row))
+    opts = _seed_opts("both" if strand is None else strand, min_seeds, band, pad, max_occ, max_hits, slice_rows)
+    copts = _seed_chain_opts(max_gap, lookback, gap_scale, min_score)
+    res = C.POINTER(pmx_seed_chained_t)()
+    if lib.pmx_seed_chains(Q._handle(), index._handle(), int(first_row), int(rows), C.byref(opts), C.byref(copts), C.byref(res)):
+        raise BatchError(lib.pmx_last_error().decode())
+    try:
+        hits = SeedHits(res.contents.hits, kind="strand")
+        ptr, n = res.contents.chains, hits.n_hits
+        hits.chains = (np.frombuffer(C.string_at(ptr, n * SEED_CHAIN_DTYPE.itemsize), dtype=SEED_CHAIN_DTYPE).copy() if ptr and n
+                       else np.zeros(n, dtype=SEED_CHAIN_DTYPE))
+        return hits
+    finally:
+        lib.pmx_seed_chained_free(res)
+
+
+def seed_chains_device(Q, index, q_first, nq, max_qlen, d_hit_pairs, d_hit_strand, d_hit_seeds, d_hit_chains, capacity, d_row_off, d_counts,
+                       strand=None, min_seeds=2, min_score=0, band=500, max_gap=5000, lookback=64, gap_scale=38, pad=16, max_occ=64,
+                       slice_rows=0, stream=0):
+    """Device-pointer entry of seed_chains, as seed_pairs_device: the candidates go to d_hit_pairs / d_hit_strand / d_hit_seeds
+    (optional) / d_hit_chains (optional), `capacity` entries each, d_row_off gets nq + 1 offsets and d_counts [candidates, written].
+    Synchronises `stream` once per slice."""
+    opts = _seed_opts("both" if strand is None else strand, min_seeds, band, pad, max_occ, 0, slice_rows)
+    copts = _seed_chain_opts(max_gap, lookback, gap_scale, min_score)
+    if lib.pmx_seed_chains_device(Q._handle(), index._handle(), int(q_first), int(nq), int(max_qlen), C.byref(opts), C.byref(copts), d_hit_pairs,
+                                  d_hit_strand, d_hit_seeds, d_hit_chains, int(capacity), d_row_off, d_counts, stream):
+        raise BatchError(lib.pmx_last_error().decode())
+
+
+def seed_chain_shape():
+    """(lanes that evaluate predecessors at once, the most anchors the ring holds = the largest lookback) of the chain kernel (test hook)."""
+    a, b = C.c_int32(), C.c_int32()
+    lib.pmx_seed_chain_shape(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
 
 
 def ungapped_shape():

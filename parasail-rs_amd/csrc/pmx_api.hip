@@ -6173,12 +6173,15 @@ static int seed_mode_orients(int query_mode)
 // entry's PmxSeedKind, with its own mode argument behind seed_check -- o.strand (DNA), query_mode (letters: `code` replaces the standard
 // genetic code), ref_mode (translated); k, bits, ref_count: the index's; budget: the match buffer in bytes.
 // 0 planned; 1 one row's worst case does not fit the budget: the plan is filled up to the slice, which then has no size.
+// co: the chain options of pmx_seed_chains[_device] (a DNA index), NULL on the cluster road -- a match then costs what it did.
 static int seed_plan(int kind, int mode, const uint8_t *code, int64_t nq, int32_t max_qlen, const pmx_seed_opts_t &o, int k, int bits, int64_t ref_count,
-                     int64_t budget, PmxSeedPlan *out, int w = 1)
+                     int64_t budget, PmxSeedPlan *out, int w = 1, const pmx_seed_chain_opts_t *co = nullptr)
 {
     PmxSeedPlan p = {};
     p.kind = kind; p.max_qlen = max_qlen; p.k = k; p.bits = bits; p.ref_count = ref_count; p.w = w;
     p.band = o.band; p.min_seeds = o.min_seeds; p.pad = o.pad; p.max_occ = o.max_occ;
+    p.chain = co != nullptr; p.match_bytes = co ? PMX_SEED_MATCH_BYTES_CHAIN : PMX_SEED_MATCH_BYTES;
+    if (co) { p.max_gap = co->max_gap; p.lookback = co->lookback; p.gap_scale = co->gap_scale; p.min_score = co->min_score; }
     if (code) memcpy(p.code.v, code, 64); else pmx_genetic_code_host(p.code.v);
     p.orients = p.segs = 1;
     if (kind == PMX_SEED_KIND_DNA) {
@@ -6197,14 +6200,14 @@ static int seed_plan(int kind, int mode, const uint8_t *code, int64_t nq, int32_
     p.key_bits = 33;                                     // the diagonal and the bits of an id: a reference, times the six frames of a translated index
     while (p.key_bits < 64 && ((int64_t)1 << (p.key_bits - 32)) < (kind == PMX_SEED_KIND_TRANSLATED ? 6 : 1) * ref_count) ++p.key_bits;
     *out = p;
-    if ((double)p.row_slots * (double)o.max_occ * (double)PMX_SEED_MATCH_BYTES > (double)budget) return 1;
+    if ((double)p.row_slots * (double)o.max_occ * (double)p.match_bytes > (double)budget) return 1;
     int64_t slice = std::max<int64_t>(1, (int64_t)PMX_PAIRS_CHUNK_BYTES / (p.row_slots * p.pos_bytes));
     if (o.slice_rows > 0) slice = std::min(slice, o.slice_rows);
     slice = std::min(slice, nq);
     // the match buffer: the budget, or the slice's worst case when that is smaller (positions fit 32 bits)
     const double worst = (double)slice * (double)p.row_slots * (double)o.max_occ;
     p.slice_rows = slice; p.positions = slice * p.row_slots; p.slots = slice * p.orients;
-    p.cap_m = (int64_t)std::min<double>(std::min<double>((double)(budget / PMX_SEED_MATCH_BYTES), worst), 2147483646.0);
+    p.cap_m = (int64_t)std::min<double>(std::min<double>((double)(budget / p.match_bytes), worst), 2147483646.0);
     *out = p;
     return 0;
 }
@@ -6234,14 +6237,22 @@ extern "C" int pmx_seed_plan_probe(int kind, int mode, long long nq, int max_qle
 
 // What the seeding entries refuse about their arguments, and behind that the run's plan.  kind / mode: the entry's (seed_plan); lens_known
 // false: the host entry before it has looked at the lengths (max_qlen and the budget rule are checked in its second call).
+// chain: the entry is pmx_seed_chains[_device] (kind DNA) and co its chain options, checked behind opts.
 static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int kind, int mode, const uint8_t *code, int64_t q_first, int64_t nq, int32_t max_qlen,
-                      const pmx_seed_opts_t *o, int64_t capacity, bool lens_known, PmxSeedPlan *plan)
+                      const pmx_seed_opts_t *o, int64_t capacity, bool lens_known, PmxSeedPlan *plan, bool chain = false,
+                      const pmx_seed_chain_opts_t *co = nullptr)
 {
     const bool dna = kind == PMX_SEED_KIND_DNA, tref = kind == PMX_SEED_KIND_TRANSLATED, letters = kind == PMX_SEED_KIND_LETTERS;
     if (!lens_known) max_qlen = 1;
     if (!Q) { set_err("null sequence set"); return -1; }
     if (!ix) { set_err("null seed index"); return -1; }
     if (!o) { set_err("null opts"); return -1; }
+    if (chain && !co) { set_err("null chain opts"); return -1; }
+    if (chain && ix->kind != kind) {
+        set_err("chaining takes a DNA index (pmx_seed_index_build, pmx_seed_index_build_minimizers), not a %s one",
+                ix->kind == PMX_SEED_KIND_TRANSLATED ? "translated" : "letters");
+        return -1;
+    }
     if (ix->kind != kind) {
         if (ix->kind == PMX_SEED_KIND_TRANSLATED) set_err("a translated index (pmx_seed_index_build_translated) is seeded by pmx_seed_pairs_translated_ref[_device]");
         else if (ix->kind == PMX_SEED_KIND_LETTERS) set_err("a letters index (pmx_seed_index_build_letters) is seeded by pmx_seed_pairs_letters[_device]");
@@ -6271,10 +6282,19 @@ static int seed_check(const pmx_seqset *Q, const pmx_seed_index *ix, int kind, i
     if (o->pad < 0 || o->pad > PMX_SEED_BAND_MAX) { set_err("pad %d is outside 0 .. 2^20", (int)o->pad); return -1; }
     if (o->max_occ < 1 || o->max_occ > 65535) { set_err("max_occ %d is outside 1 .. 65535", (int)o->max_occ); return -1; }
     if (o->reserved != 0) { set_err("reserved must be 0"); return -1; }
-    if (seed_plan(kind, mode, code, nq, max_qlen, *o, ix->k, ix->bits, ix->R->count, seed_match_budget(), plan, ix->w)) {
+    if (chain) {
+        if (co->max_gap < 1 || co->max_gap > PMX_SEED_BAND_MAX) { set_err("max_gap %d is outside 1 .. 2^20", (int)co->max_gap); return -1; }
+        if (co->lookback < 1 || co->lookback > PMX_SEED_CHAIN_RING) { set_err("lookback %d is outside 1 .. %d", (int)co->lookback, PMX_SEED_CHAIN_RING); return -1; }
+        if (co->gap_scale < 0 || co->gap_scale > 65535) { set_err("gap_scale %d is outside 0 .. 65535", (int)co->gap_scale); return -1; }
+        if (co->min_score < 0) { set_err("min_score %d is negative", (int)co->min_score); return -1; }
+        if (co->reserved[0] || co->reserved[1] || co->reserved[2] || co->reserved[3]) { set_err("chain opts: reserved must be 0"); return -1; }
+        // f <= 31 x max_qlen has to fit int32 (include/parasail_amd.h, "Arithmetic")
+        if (max_qlen > (1 << 26)) { set_err("max_qlen %d is above 2^26: a chain's score would not fit 32 bits", (int)max_qlen); return -1; }
+    }
+    if (seed_plan(kind, mode, code, nq, max_qlen, *o, ix->k, ix->bits, ix->R->count, seed_match_budget(), plan, ix->w, chain ? co : nullptr)) {
         set_err("one row's worst case of %d positions x %d %s x max_occ %d x %d bytes per match does not fit the match buffer of %lld bytes: "
                 "lower max_occ or split the queries", (int)max_qlen, plan->orients, dna ? "strand(s)" : "orientation(s)", (int)o->max_occ,
-                PMX_SEED_MATCH_BYTES, (long long)seed_match_budget());
+                plan->match_bytes, (long long)seed_match_budget());
         return -1;
     }
     return 0;
@@ -6296,11 +6316,16 @@ static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_fir
     if (ix->n == 0) { HIP_OR_RET(hipMemsetAsync(out.row_off, 0, sizeof(int64_t) * (size_t)(nq + 1), st)); return 0; }
     HIP_OR_RET(hipMemsetAsync(out.row_off, 0, sizeof(int64_t), st));
     PmxSeedSlice s = {};
-    s.temp_bytes = pmx_seed_temp_bytes(p.positions, p.cap_m, p.slots);
+    s.temp_bytes = pmx_seed_temp_bytes(p.positions, p.cap_m, p.slots, p.chain);
     if (scratch_carve(SCR_SEED, [&](Carver &c) {
             s.lo = c.take<uint32_t>((size_t)p.positions); s.cnt = c.take<uint32_t>((size_t)p.positions + 1); s.moff = c.take<int64_t>((size_t)p.positions + 1);
             s.keys_a = c.take<uint64_t>((size_t)p.cap_m); s.keys_b = c.take<uint64_t>((size_t)p.cap_m);
-            s.head = c.take<uint32_t>((size_t)p.cap_m); s.flag = c.take<uint32_t>((size_t)p.cap_m + 1);
+            if (!p.chain) s.head = c.take<uint32_t>((size_t)p.cap_m);
+            s.flag = c.take<uint32_t>((size_t)p.cap_m + 1);
+            if (p.chain) {
+                s.vals_a = c.take<uint32_t>((size_t)p.cap_m); s.vals_b = c.take<uint32_t>((size_t)p.cap_m);
+                s.f = c.take<int32_t>((size_t)p.cap_m); s.pred = c.take<int32_t>((size_t)p.cap_m); s.child = c.take<int32_t>((size_t)p.cap_m);
+            }
             s.cut = c.take<int64_t>(2); s.temp = c.take<unsigned char>(s.temp_bytes);
             if (p.kind != PMX_SEED_KIND_DNA) s.codes = c.take<uint8_t>((size_t)p.positions);
             if (p.w > 1) s.mflag = c.take<uint8_t>((size_t)p.positions);
@@ -6324,12 +6349,14 @@ static int seed_run(const pmx_seqset *Q, const pmx_seed_index *ix, int64_t q_fir
 }
 
 // The device entries; kind / mode / code: the public entry's own (seed_plan)
+// (chain, copts, d_hit_chains: pmx_seed_chains_device's)
 static int seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
                              const pmx_seed_opts_t *opts, int kind, int mode, const uint8_t *code, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand,
-                             pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream)
+                             pmx_seed_hit_t *d_hit_seeds, int64_t capacity, int64_t *d_row_off, int64_t *d_counts, void *stream,
+                             bool chain = false, const pmx_seed_chain_opts_t *copts = nullptr, pmx_seed_chain_t *d_hit_chains = nullptr)
 {
     PmxSeedPlan plan;
-    if (seed_check(Q, ix, kind, mode, code, q_first, nq, max_qlen, opts, capacity, true, &plan)) return -1;
+    if (seed_check(Q, ix, kind, mode, code, q_first, nq, max_qlen, opts, capacity, true, &plan, chain, copts)) return -1;
     if (capacity > 0 && (!d_hit_pairs || !d_hit_strand)) { set_err("null hit pairs or strand bytes with capacity > 0"); return -1; }
     if (nq == 0) {
         if (d_counts) HIP_OR_RET(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
@@ -6341,7 +6368,7 @@ static int seed_pairs_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, 
     if (seed_device_check(Q, ix)) return -1;
     StreamGuard guard(stream);
     if (!guard.ok) { set_err("stream guard failed"); return -1; }
-    const PmxSeedOut out = {d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts};
+    const PmxSeedOut out = {d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off, d_counts, d_hit_chains};
     return seed_run(Q, ix, q_first, nq, plan, out, (hipStream_t)stream);
 }
 
@@ -6364,25 +6391,33 @@ extern "C" int pmx_seed_pairs_letters_device(const pmx_seqset_t *Q, const pmx_se
 
 extern "C" void pmx_seed_hits_free(pmx_seed_hits_t *hits) { free(hits); }
 
+// chain: pmx_seed_chains -- the block's header is a pmx_seed_chained_t (its first member the pmx_seed_hits_t returned here) and the
+// chain records lie behind the strand bytes.
 static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
-                           int kind, int mode, const uint8_t *code, pmx_seed_hits_t **result)
+                           int kind, int mode, const uint8_t *code, pmx_seed_hits_t **result, bool chain = false,
+                           const pmx_seed_chain_opts_t *copts = nullptr)
 {
     if (!result) { set_err("null result pointer"); return -1; }
     *result = nullptr;
     PmxSeedPlan plan;                                        // of the ask first; of the run once the longest row is known
-    if (seed_check(Q, ix, kind, mode, code, q_first, nq, 0, opts, 0, false, &plan)) return -1;
-    // the result: one block -- header, row offsets, descriptors, seed records, strand bytes
+    if (seed_check(Q, ix, kind, mode, code, q_first, nq, 0, opts, 0, false, &plan, chain, copts)) return -1;
+    // the result: one block -- header, row offsets, descriptors, seed records, strand bytes (and chain records)
+    pmx_seed_chain_t *h_chains = nullptr;
     auto block = [&](int64_t stored, int64_t passing) -> pmx_seed_hits_t * {
         Carver c; c.align = 16;
-        c.take<pmx_seed_hits_t>(1); c.take<int64_t>((size_t)nq + 1); c.take<pmx_pair_t>((size_t)stored); c.take<pmx_seed_hit_t>((size_t)stored);
+        if (chain) c.take<pmx_seed_chained_t>(1); else c.take<pmx_seed_hits_t>(1);
+        c.take<int64_t>((size_t)nq + 1); c.take<pmx_pair_t>((size_t)stored); c.take<pmx_seed_hit_t>((size_t)stored);
         c.take<uint8_t>((size_t)stored);
+        if (chain) c.take<pmx_seed_chain_t>((size_t)stored);
         unsigned char *p = (unsigned char *)calloc(1, c.used ? c.used : 16);
         if (!p) { set_err("out of memory"); return nullptr; }
         Carver d; d.align = 16; d.base = p;
-        pmx_seed_hits_t *r = d.take<pmx_seed_hits_t>(1);
+        pmx_seed_chained_t *ch = chain ? d.take<pmx_seed_chained_t>(1) : nullptr;
+        pmx_seed_hits_t *r = chain ? &ch->hits : d.take<pmx_seed_hits_t>(1);
         r->n_rows = nq; r->n_hits = stored; r->n_passing = passing;
         r->row_off = d.take<int64_t>((size_t)nq + 1); r->pairs = d.take<pmx_pair_t>((size_t)stored);
         r->seeds = d.take<pmx_seed_hit_t>((size_t)stored); r->strand = d.take<uint8_t>((size_t)stored);
+        if (chain) h_chains = ch->chains = d.take<pmx_seed_chain_t>((size_t)stored);
         return r;
     };
     if (nq == 0) { *result = block(0, 0); return *result ? 0 : -1; }
@@ -6411,12 +6446,14 @@ static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, in
     }
     if (plan.rows_translated) mq /= 3;                       // the letters of the longest translation
     if (mq < 1) mq = 1;
-    if (seed_check(Q, ix, kind, mode, code, q_first, nq, mq, opts, 0, true, &plan)) return -1;
+    if (seed_check(Q, ix, kind, mode, code, q_first, nq, mq, opts, 0, true, &plan, chain, copts)) return -1;
     int64_t *d_off = nullptr, *d_cnt = nullptr; pmx_pair_t *d_pairs = nullptr; pmx_seed_hit_t *d_seeds = nullptr; uint8_t *d_strand = nullptr;
+    pmx_seed_chain_t *d_chains = nullptr;
     auto carve = [&](int64_t stored) {
         return scratch_carve(SCR_SEEDHIT, [&](Carver &c) {
             d_cnt = c.take<int64_t>(2); d_off = c.take<int64_t>((size_t)nq + 1);
             d_pairs = c.take<pmx_pair_t>((size_t)stored); d_seeds = c.take<pmx_seed_hit_t>((size_t)stored); d_strand = c.take<uint8_t>((size_t)stored);
+            if (chain) d_chains = c.take<pmx_seed_chain_t>((size_t)stored);
         });
     };
     // the number of candidates is known only behind a run: room for two per row first (max_hits when that is less), and where more
@@ -6425,14 +6462,14 @@ static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, in
     int64_t room = 2 * nq + 16;
     if (opts->max_hits > 0) room = std::min(room, opts->max_hits);
     if (carve(room)) return -1;
-    int rc = seed_run(Q, ix, q_first, nq, plan, PmxSeedOut{d_pairs, d_strand, d_seeds, room, d_off, d_cnt}, st);
+    int rc = seed_run(Q, ix, q_first, nq, plan, PmxSeedOut{d_pairs, d_strand, d_seeds, room, d_off, d_cnt, d_chains}, st);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     HIP_OR_RET(hipMemcpyAsync(h, d_cnt, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_OR_RET(hipStreamSynchronize(st));
     const int64_t passing = h[0], stored = opts->max_hits > 0 ? std::min(passing, opts->max_hits) : passing;
     if (stored > room) {
         if (carve(stored)) return -1;
-        rc = seed_run(Q, ix, q_first, nq, plan, PmxSeedOut{d_pairs, d_strand, d_seeds, stored, d_off, d_cnt}, st);
+        rc = seed_run(Q, ix, q_first, nq, plan, PmxSeedOut{d_pairs, d_strand, d_seeds, stored, d_off, d_cnt, d_chains}, st);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HIP_OR_RET(hipStreamSynchronize(st));
     }
@@ -6442,6 +6479,7 @@ static int seed_pairs_host(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, in
     if (e == hipSuccess && stored > 0) e = hipMemcpy(r->pairs, d_pairs, sizeof(pmx_pair_t) * (size_t)stored, hipMemcpyDeviceToHost);
     if (e == hipSuccess && stored > 0) e = hipMemcpy(r->seeds, d_seeds, sizeof(pmx_seed_hit_t) * (size_t)stored, hipMemcpyDeviceToHost);
     if (e == hipSuccess && stored > 0) e = hipMemcpy(r->strand, d_strand, (size_t)stored, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && stored > 0 && chain) e = hipMemcpy(h_chains, d_chains, sizeof(pmx_seed_chain_t) * (size_t)stored, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { set_err("copying the candidates back failed: %s", hipGetErrorString(e)); free(r); return -1; }
     *result = r;
     return 0;
@@ -6452,6 +6490,29 @@ extern "C" int pmx_seed_pairs(const pmx_seqset_t *Q, const pmx_seed_index_t *ix,
 {
     return seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_KIND_DNA, 0, nullptr, result);
 }
+
+// Chaining: the DNA road with chain options; the hits header is the first member of the chained block.
+extern "C" int pmx_seed_chains_device(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, int32_t max_qlen,
+                                      const pmx_seed_opts_t *opts, const pmx_seed_chain_opts_t *copts, pmx_pair_t *d_hit_pairs, uint8_t *d_hit_strand,
+                                      pmx_seed_hit_t *d_hit_seeds, pmx_seed_chain_t *d_hit_chains, int64_t capacity, int64_t *d_row_off,
+                                      int64_t *d_counts, void *stream)
+{
+    return seed_pairs_device(Q, ix, q_first, nq, max_qlen, opts, PMX_SEED_KIND_DNA, 0, nullptr, d_hit_pairs, d_hit_strand, d_hit_seeds, capacity, d_row_off,
+                             d_counts, stream, true, copts, d_hit_chains);
+}
+
+extern "C" int pmx_seed_chains(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
+                               const pmx_seed_chain_opts_t *copts, pmx_seed_chained_t **result)
+{
+    static_assert(offsetof(pmx_seed_chained_t, hits) == 0, "the chained block starts with its hits");
+    if (!result) { set_err("null result pointer"); return -1; }
+    pmx_seed_hits_t *hits = nullptr;
+    const int rc = seed_pairs_host(Q, ix, q_first, nq, opts, PMX_SEED_KIND_DNA, 0, nullptr, &hits, true, copts);
+    *result = (pmx_seed_chained_t *)hits;
+    return rc;
+}
+
+extern "C" void pmx_seed_chained_free(pmx_seed_chained_t *chained) { free(chained); }
 
 extern "C" int pmx_seed_pairs_letters(const pmx_seqset_t *Q, const pmx_seed_index_t *ix, int64_t q_first, int64_t nq, const pmx_seed_opts_t *opts,
                                       int query_mode, const uint8_t *code, pmx_seed_hits_t **result)

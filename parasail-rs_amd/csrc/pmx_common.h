@@ -448,6 +448,9 @@ int pmx_launch_topk_emit(long long nq, long long q_first, long long nr, int ks, 
 // into keys_in / vals_in, sorted into keys_out / vals_out (the k-mers in front, *n_valid of them; val = seq << 32 | pos); buckets: the
 // table of nb + 1 first-entry numbers on the keys' top bits (key >> shift).
 #define PMX_SEED_MATCH_BYTES 24        // per match: two sort buffers of 8-byte keys, the head index, the candidate flag / position
+#define PMX_SEED_MATCH_BYTES_CHAIN 40  // ... of a chaining run: two sort buffers of 8-byte keys and of 4-byte values (i), f, pred, child, the flag / position
+#define PMX_SEED_CHAIN_LANES 64        // the chain kernel: one wave per (row, strand) segment, a lane per predecessor of a round
+#define PMX_SEED_CHAIN_RING 1024       // ... and the most anchors its LDS ring holds (the largest lookback)
 #define PMX_SEED_POS_BYTES   16        // per position slot: first entry, occurrences, match offset
 #define PMX_SEED_POS_BYTES_LETTERS (PMX_SEED_POS_BYTES + 1)        // ... and the code byte of a letters or translated index
 #define PMX_SEED_POS_BYTES_MINIMIZERS (PMX_SEED_POS_BYTES + 1)     // ... or the flag byte of a minimizer index (w > 1)
@@ -512,6 +515,9 @@ struct PmxSeedPlan {
     long long ref_count;                   // the sequences of the indexed set
     int band, min_seeds, pad, max_occ;
     int w;                                 // the window of a DNA index: 1 every k-mer, > 1 minimizers (one flag byte more per position slot)
+    bool chain;                            // candidates are collinear chains (pmx_seed_chains; a DNA index), else diagonal clusters
+    int max_gap, lookback, gap_scale, min_score;        // read where chain: pmx_seed_chain_opts_t's
+    int match_bytes;                       // scratch bytes per match: PMX_SEED_MATCH_BYTES, PMX_SEED_MATCH_BYTES_CHAIN where chain
     PmxCodeTable code;                     // read where rows_translated
     long long slice_rows, cap_m, positions, slots;      // a slice: its rows at most, matches at most, position slots, rows x orients
 };
@@ -523,20 +529,28 @@ struct PmxSeedSource {
 };
 // ... a slice's scratch (lo, moff: positions, cnt: positions + 1; keys_a / keys_b / head: cap_m, flag: cap_m + 1; cut: 2; codes:
 // positions, NULL with a DNA index; mflag: positions, the rows' minimizer flags, NULL unless the plan's w > 1; temp:
-// pmx_seed_temp_bytes(positions, cap_m, slots)) ...
+// pmx_seed_temp_bytes(positions, cap_m, slots, chain)).  A chaining run has no head; it has vals_a / vals_b (the matches' i beside
+// the two key buffers), f, pred and child, cap_m entries each ...
 struct PmxSeedSlice {
     uint32_t *lo, *cnt; int64_t *moff; uint64_t *keys_a, *keys_b; uint32_t *head, *flag; int64_t *cut; uint8_t *codes; void *temp; size_t temp_bytes;
     uint8_t *mflag;
+    uint32_t *vals_a, *vals_b; int32_t *f, *pred, *child;
 };
-// ... and where the candidates go: `capacity` entries each (seeds optional), row offsets, counts[0 .. 1].
-struct PmxSeedOut { pmx_pair_t *pairs; uint8_t *byte; pmx_seed_hit_t *seeds; long long capacity; int64_t *row_off, *counts; };
-size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots);
+// ... and where the candidates go: `capacity` entries each (seeds optional; chains optional, a chaining run's), row offsets, counts[0 .. 1].
+struct PmxSeedOut { pmx_pair_t *pairs; uint8_t *byte; pmx_seed_hit_t *seeds; long long capacity; int64_t *row_off, *counts; pmx_seed_chain_t *chains; };
+size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots, bool chain = false);
 // count: the lookups of rows row0 .. row0 + rows of Q (with a letters or translated index behind the code stage), the scan of their
 // matches into moff and cut[0 .. 1] = the rows that fit cap_m / their matches.  cluster: those rows' m matches emitted, sorted per
 // segment and turned into candidates behind counts[0], row offsets (out.row_off points at the entry of the slice's first row) and counts.
 int pmx_launch_seed_count(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedSource &src, long long row0, long long rows, hipStream_t stream);
 int pmx_launch_seed_cluster(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedOut &out, const PmxSeedSource &src, long long row0,
                             long long rows, long long m, hipStream_t stream);
+// The gap cost of a chain link (include/parasail_amd.h): integers only; g <= 2^20 and scale <= 65 535 keep it below 2^28.
+__host__ __device__ __forceinline__ int32_t pmx_seed_chain_cost(int32_t g, int32_t scale)
+{
+    if (g < 1) return 0;
+    return (int32_t)(((int64_t)g * scale) >> 8) + ((32 - __builtin_clz((unsigned)g)) >> 1);
+}
 // The ungapped diagonal filter (pmx_ungap.hip; semantics: include/parasail_amd.h).  The hot kernel's shape: a group of
 // PMX_UNGAP_LANES lanes per candidate, pieces of whole PMX_UNGAP_STEP-cell steps per lane.
 #define PMX_UNGAP_LANES 16

@@ -15,6 +15,9 @@
 //
 // The letters and translated indexes run the same pipeline: a run is described once by PmxSeedPlan (pmx_common.h),
 // the two launchers at the end of this file read it, and emit and hits are one template each over the plan's geometry.
+//
+// Chaining is the DNA road with another middle: the matches sorted by (r, j) with i beside them, one wave per segment
+// that scores collinear chains with gap costs, a walk from every chain's tail -- and the same count pass, cut, flag scan and row offsets.
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -495,11 +498,13 @@ __device__ __forceinline__ uint64_t pmx_seed_match_key(uint64_t v, long long t, 
     return pmx_seed_key((uint64_t)id0, j - i);
 }
 
-// the matches of position slot p, behind moff[p]
-template <int G>
+// the matches of position slot p, behind moff[p].  CHAIN (a DNA index): the key is the index value itself, r << 32 | j, and the match's
+// i goes beside it into mvals -- anchors sort by (r, j), not by diagonal.
+template <int G, bool CHAIN = false>
 __global__ void __launch_bounds__(256) pmx_seed_emit_kernel(long long total, int max_qlen, long long count, const uint32_t *__restrict__ lo,
                                                             const uint32_t *__restrict__ cnt, const int64_t *__restrict__ moff,
-                                                            const uint64_t *__restrict__ vals, uint64_t *__restrict__ mkeys)
+                                                            const uint64_t *__restrict__ vals, uint64_t *__restrict__ mkeys,
+                                                            uint32_t *__restrict__ mvals)
 {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= total) return;
@@ -508,8 +513,10 @@ __global__ void __launch_bounds__(256) pmx_seed_emit_kernel(long long total, int
     const long long t = p / max_qlen;
     const long long i = p - t * max_qlen;
     const uint32_t first = lo[p];
-    uint64_t *out = mkeys + moff[p];
-    for (uint32_t x = 0; x < n; ++x) out[x] = pmx_seed_match_key<G>(vals[first + x], t, i, count);
+    const int64_t at = moff[p];
+    uint64_t *out = mkeys + at;
+    if (CHAIN) for (uint32_t x = 0; x < n; ++x) { out[x] = vals[first + x]; mvals[at + x] = (uint32_t)i; }
+    else for (uint32_t x = 0; x < n; ++x) out[x] = pmx_seed_match_key<G>(vals[first + x], t, i, count);
 }
 
 // segment t of the sort: the matches of (row, strand) slot t
@@ -651,7 +658,7 @@ struct PmxWidenU32 { __device__ __host__ int64_t operator()(uint32_t v) const { 
 
 // rocPRIM scratch of one slice: the scan over `positions` + 1 slot counts, the sort of `matches` keys in `slots` segments, the two scans
 // over the matches -- used one after the other, so the largest counts
-size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots)
+size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slots, bool chain)
 {
     size_t a = 0, b = 0, c = 0, d = 0;
     auto in = rocprim::make_transform_iterator((const uint32_t *)nullptr, PmxWidenU32());
@@ -659,6 +666,12 @@ size_t pmx_seed_temp_bytes(long long positions, long long matches, long long slo
     auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{nullptr, 1});
     (void)rocprim::segmented_radix_sort_keys(nullptr, b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (unsigned)matches, (unsigned)slots, seg, seg, 0, 64,
                                              nullptr);
+    if (chain) {                                // a chaining run sorts (key, i) pairs in place of keys
+        size_t bp = 0;
+        (void)rocprim::segmented_radix_sort_pairs(nullptr, bp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                  (unsigned)matches, (unsigned)slots, seg, seg, 0, 64, nullptr);
+        b = std::max(b, bp);
+    }
     (void)rocprim::inclusive_scan(nullptr, c, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)matches, PmxMaxU32(), nullptr);
     (void)rocprim::exclusive_scan(nullptr, d, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)(matches + 1), rocprim::plus<uint32_t>(), nullptr);
     return std::max(std::max(a, b), std::max(c, d)) + 256;
@@ -943,6 +956,199 @@ static int pmx_seed_sort_clusters(const PmxSeedPlan &p, const PmxSeedSlice &s, l
     return e == hipSuccess ? 0 : -(int)e;
 }
 
+// ---- chaining: collinear chains with gap costs in place of diagonal clusters (definitions: include/parasail_amd.h) --------
+// The anchors of a (row, strand) segment are its matches sorted by (r, j, i): the key r << 32 | j, the value i.  pmx_seed_chain_kernel
+// walks a segment in that order with one wave and leaves f, pred and child per anchor; a thread per anchor then walks back from every
+// tail over the kept links (chains are disjoint: m steps in all) and flags the candidates; the scan of the flags, the row offsets and
+// the running counts are the cluster road's.  pred and child are anchor numbers of the slice (int32, -1: none; m < 2^31).
+
+// the largest of v over the wave, in every lane: four DPP rotations leave each row of 16 its maximum, four v_readlane the rows'
+__device__ __forceinline__ int pmx_seed_wave_max(int v)
+{
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x121 /*row_ror:1*/, 0xF, 0xF, true));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x122 /*row_ror:2*/, 0xF, 0xF, true));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x124 /*row_ror:4*/, 0xF, 0xF, true));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x128 /*row_ror:8*/, 0xF, 0xF, true));
+    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// One wave (a workgroup of 64) per segment t = [moff[t * stride], moff[(t + 1) * stride]).  For anchor a the lanes evaluate the
+// predecessors a - 1 - lane, in rounds of 64 up to `lookback` and never before the first anchor of a's reference (a change of r empties
+// the window).  (j, i, f, child) of the last `ring` >= lookback anchors live in LDS, ring a power of two, anchor b in slot b & (ring - 1):
+// slot a & (ring - 1) is read (as a - ring, when lookback == ring) before lane 0 overwrites it with a.
+//   * nearest predecessor among equal values: inside a round the lowest lane is the nearest (the first set bit of the ballot), and a
+//     later round -- farther anchors -- replaces the best only by a strictly larger value; the same strict > against k takes no link
+//     at a value of k.
+//   * child: the ring's child of b is the anchor with the largest f among those that chose b so far; anchors arrive in ascending
+//     order and replace it only by a strictly larger f, so the smallest wins among equals.  A child is nearer than a than its parent
+//     is, so its f is still in the ring.  The child of an anchor goes to memory when the anchor leaves the ring, or at the segment's end.
+//   * arithmetic: f <= k x (anchors of a chain) <= 31 x max_qlen < 2^31 (i rises strictly along a chain; max_qlen <= 2^26), cost < 2^28,
+//     and dj - di is formed only where both are in 1 .. max_gap <= 2^20: nothing leaves int32.
+// The ring is written by lane 0 and read by all lanes of the same wave; the workgroup is that one wave, so the barrier behind the
+// write is a wait for the wave's own LDS traffic and orders the two.  The next 64 anchors are loaded, coalesced, while 64 are walked.
+__global__ void __launch_bounds__(PMX_SEED_CHAIN_LANES) pmx_seed_chain_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ mvals,
+                                                                              const int64_t *__restrict__ moff, long long stride, int k, int band, int max_gap,
+                                                                              int lookback, int gap_scale, int ring, int32_t *__restrict__ f_out,
+                                                                              int32_t *__restrict__ pred_out, int32_t *__restrict__ child_out)
+{
+    extern __shared__ int32_t pmx_chain_lds[];
+    const long long t = blockIdx.x;
+    const int64_t beg = moff[t * stride];
+    const int n = (int)(moff[(t + 1) * stride] - beg);
+    if (n <= 0) return;
+    int32_t *rj = pmx_chain_lds, *ri = rj + ring, *rf = ri + ring, *rc = rf + ring;
+    const int lane = (int)threadIdx.x, mask = ring - 1;
+    mkeys += beg; mvals += beg; f_out += beg; pred_out += beg; child_out += beg;
+    uint64_t nk = lane < n ? mkeys[lane] : 0;
+    uint32_t ni = lane < n ? mvals[lane] : 0;
+    uint32_t cur_r = 0; int wbeg = 0;                    // the reference of the window and its first anchor
+    for (int base = 0; base < n; base += PMX_SEED_CHAIN_LANES) {
+        const int rlo = (int)(uint32_t)nk, rhi = (int)(uint32_t)(nk >> 32), ci = (int)ni;
+        if (base + PMX_SEED_CHAIN_LANES + lane < n) { nk = mkeys[base + PMX_SEED_CHAIN_LANES + lane]; ni = mvals[base + PMX_SEED_CHAIN_LANES + lane]; }
+        const int cnt = min(PMX_SEED_CHAIN_LANES, n - base);
+        int myf = 0, mypred = -1;                        // lane x: those of anchor base + x
+        for (int x = 0; x < cnt; ++x) {
+            const int a = base + x;
+            const int ja = __builtin_amdgcn_readlane(rlo, x), ia = __builtin_amdgcn_readlane(ci, x);
+            const uint32_t ra = (uint32_t)__builtin_amdgcn_readlane(rhi, x);
+            if (a == 0 || ra != cur_r) { cur_r = ra; wbeg = a; }
+            const int reach = min(lookback, a - wbeg);
+            int best = k, bestb = -1;
+            for (int off = 0; off < reach; off += PMX_SEED_CHAIN_LANES) {
+                int v = INT32_MIN;
+                if (off + lane < reach) {
+                    const int s = (a - 1 - off - lane) & mask;
+                    const int dj = ja - rj[s], di = ia - ri[s];
+                    const bool near = dj >= 1 && di >= 1 && dj <= max_gap && di <= max_gap;
+                    const int g = near ? abs(dj - di) : 0;
+                    if (near && g <= band) v = rf[s] + min(min(di, dj), k) - pmx_seed_chain_cost(g, gap_scale);
+                }
+                const int vm = pmx_seed_wave_max(v);
+                if (vm > best) { best = vm; bestb = a - 1 - off - (__ffsll((unsigned long long)__ballot(v == vm)) - 1); }
+            }
+            if (lane == 0) {
+                if (bestb >= 0) {
+                    const int c = rc[bestb & mask];
+                    if (c < 0 || best > rf[c & mask]) rc[bestb & mask] = a;
+                }
+                const int sa = a & mask;
+                if (a >= ring) { const int c = rc[sa]; child_out[a - ring] = c < 0 ? -1 : (int32_t)(beg + c); }
+                rj[sa] = ja; ri[sa] = ia; rf[sa] = best; rc[sa] = -1;
+            }
+            if (lane == x) { myf = best; mypred = bestb < 0 ? -1 : (int32_t)(beg + bestb); }
+            __syncthreads();
+        }
+        if (lane < cnt) { f_out[base + lane] = myf; pred_out[base + lane] = mypred; }
+    }
+    for (int e = max(0, n - ring) + lane; e < n; e += PMX_SEED_CHAIN_LANES) { const int c = rc[e & mask]; child_out[e] = c < 0 ? -1 : (int32_t)(beg + c); }
+}
+
+// The chain that ends in tail x, walked back over the kept links (a -> pred(a) is kept iff child(pred(a)) == a).
+struct PmxSeedChainWalk { int32_t n, score, head, dmin, dmax; };
+__device__ __forceinline__ PmxSeedChainWalk pmx_seed_chain_walk(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ mvals, const int32_t *__restrict__ f,
+                                                                const int32_t *__restrict__ pred, const int32_t *__restrict__ child, int32_t x)
+{
+    PmxSeedChainWalk w;
+    w.n = 1; w.score = f[x];
+    w.dmin = w.dmax = (int32_t)(uint32_t)mkeys[x] - (int32_t)mvals[x];
+    for (;;) {
+        const int32_t b = pred[x];
+        if (b < 0) break;
+        if (child[b] != x) { w.score -= f[b]; break; }
+        x = b; ++w.n;
+        const int32_t d = (int32_t)(uint32_t)mkeys[x] - (int32_t)mvals[x];
+        w.dmin = min(w.dmin, d); w.dmax = max(w.dmax, d);
+    }
+    w.head = x;
+    return w;
+}
+
+// flag[x] = 1 where anchor x is the tail of a candidate (flag: m + 1 entries, the last one 0: the scan's total)
+__global__ void __launch_bounds__(256) pmx_seed_chain_tails_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ mvals, const int32_t *__restrict__ f,
+                                                                   const int32_t *__restrict__ pred, const int32_t *__restrict__ child, long long m,
+                                                                   int min_score, int min_seeds, uint32_t *__restrict__ flag)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x > m) return;
+    if (x == m || child[x] >= 0) { flag[x] = 0; return; }
+    const PmxSeedChainWalk w = pmx_seed_chain_walk(mkeys, mvals, f, pred, child, (int32_t)x);
+    flag[x] = w.score >= min_score && w.n >= min_seeds ? 1u : 0u;
+}
+
+// the chain form of pmx_seed_hits_kernel: candidate tails -> outputs at counts[0] + pos[x], below `capacity`; the tail's walk again
+__global__ void __launch_bounds__(256) pmx_seed_chain_hits_kernel(const uint64_t *__restrict__ mkeys, const uint32_t *__restrict__ mvals, const int32_t *__restrict__ f,
+                                                                  const int32_t *__restrict__ pred, const int32_t *__restrict__ child,
+                                                                  const uint32_t *__restrict__ pos, long long m, const int64_t *__restrict__ moff, long long slots,
+                                                                  long long stride, int k, PmxSeedWindowArgs g, const int64_t *__restrict__ counts, long long capacity,
+                                                                  pmx_pair_t *__restrict__ hit_pairs, uint8_t *__restrict__ hit_byte, pmx_seed_hit_t *__restrict__ hit_seeds,
+                                                                  pmx_seed_chain_t *__restrict__ hit_chains)
+{
+    const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= m || pos[x + 1] == pos[x]) return;
+    const long long at = counts[0] + (long long)pos[x];
+    if (at >= capacity) return;
+    long long a = 0, z = slots - 1;             // the segment of x, as pmx_seed_hits_kernel finds it
+    while (a < z) { const long long mid = (a + z + 1) >> 1; if (moff[mid * stride] <= x) a = mid; else z = mid - 1; }
+    const PmxSeedChainWalk c = pmx_seed_chain_walk(mkeys, mvals, f, pred, child, (int32_t)x);
+    const uint64_t kt = mkeys[x];
+    const PmxSeedWindow w = pmx_seed_window<PMX_SEED_GEOM_DNA>(g, a, (long long)(kt >> 32), c.dmin, c.dmax);
+    pmx_pair_t pr; pr.q = w.row; pr.r = w.r; pr.q_beg = 0; pr.q_len = -1; pr.r_beg = (int32_t)w.beg; pr.r_len = (int32_t)(w.end - w.beg);
+    hit_pairs[at] = pr;
+    hit_byte[at] = (uint8_t)w.byte;
+    if (hit_seeds) { pmx_seed_hit_t s; s.n_seeds = c.n; s.diag_min = c.dmin; s.diag_max = c.dmax; s.reserved = 0; hit_seeds[at] = s; }
+    if (hit_chains) {
+        pmx_seed_chain_t o;
+        o.score = c.score; o.n_anchors = c.n; o.q_beg = (int32_t)mvals[c.head]; o.q_end = (int32_t)mvals[x] + k;
+        o.r_beg = (int32_t)(uint32_t)mkeys[c.head]; o.r_end = (int32_t)(uint32_t)kt + k; o.diag_min = c.dmin; o.diag_max = c.dmax;
+        hit_chains[at] = o;
+    }
+}
+
+void pmx_seed_chain_shape(int32_t *lanes, int32_t *ring)
+{
+    if (lanes) *lanes = PMX_SEED_CHAIN_LANES;
+    if (ring) *ring = PMX_SEED_CHAIN_RING;
+}
+
+// A chaining slice between the cut and the row offsets: the m > 0 matches emitted as (r << 32 | j, i), sorted per segment, chained,
+// flagged, scanned and written.  The sort is stable and a segment's matches are emitted in ascending i (position slots ascend with i
+// inside an orientation, and a slot's entries are distinct (r, j)), so the sorted order is (r, j, i) whatever the sort does inside.
+static int pmx_seed_chain_slice(const PmxSeedPlan &p, const PmxSeedSlice &s, const PmxSeedOut &out, const PmxSeedSource &src, long long row0, long long m,
+                                long long segs, long long total, hipStream_t stream)
+{
+    int rc = 0;
+    const unsigned mb = (unsigned)((m + 1 + 255) / 256);
+    hipLaunchKernelGGL((pmx_seed_emit_kernel<PMX_SEED_GEOM_DNA, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, p.max_qlen, p.ref_count,
+                       (const uint32_t *)s.lo, (const uint32_t *)s.cnt, (const int64_t *)s.moff, src.vals, s.keys_a, s.vals_a);
+    if ((rc = pmx_launched())) return rc;
+    auto seg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0u), PmxSeedSegOff{s.moff, p.seg_slots});
+    size_t tb = s.temp_bytes;
+    hipError_t e = rocprim::segmented_radix_sort_pairs(s.temp, tb, (const uint64_t *)s.keys_a, s.keys_b, (const uint32_t *)s.vals_a, s.vals_b, (unsigned)m,
+                                                       (unsigned)segs, seg, seg + 1, 0, p.key_bits, stream);
+    if (e != hipSuccess) return -(int)e;
+    int ring = PMX_SEED_CHAIN_LANES;
+    while (ring < p.lookback) ring *= 2;                 // lookback <= PMX_SEED_CHAIN_RING
+    hipLaunchKernelGGL(pmx_seed_chain_kernel, dim3((unsigned)segs), dim3(PMX_SEED_CHAIN_LANES), (size_t)ring * 4 * sizeof(int32_t), stream,
+                       (const uint64_t *)s.keys_b, (const uint32_t *)s.vals_b, (const int64_t *)s.moff, p.seg_slots, p.k, p.band, p.max_gap, p.lookback,
+                       p.gap_scale, ring, s.f, s.pred, s.child);
+    if ((rc = pmx_launched())) return rc;
+    hipLaunchKernelGGL(pmx_seed_chain_tails_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)s.keys_b, (const uint32_t *)s.vals_b, (const int32_t *)s.f,
+                       (const int32_t *)s.pred, (const int32_t *)s.child, m, p.min_score, p.min_seeds, s.flag);
+    if ((rc = pmx_launched())) return rc;
+    tb = s.temp_bytes;
+    e = rocprim::exclusive_scan(s.temp, tb, s.flag, s.flag, 0u, (size_t)(m + 1), rocprim::plus<uint32_t>(), stream);
+    if (e != hipSuccess) return -(int)e;
+    if (out.capacity > 0) {
+        const PmxSeedWindowArgs g = {row0, p.segs, p.first, p.rows_translated, p.ref_count, p.pad, src.qoff, src.roff};
+        hipLaunchKernelGGL(pmx_seed_chain_hits_kernel, dim3(mb), dim3(256), 0, stream, (const uint64_t *)s.keys_b, (const uint32_t *)s.vals_b, (const int32_t *)s.f,
+                           (const int32_t *)s.pred, (const int32_t *)s.child, (const uint32_t *)s.flag, m, (const int64_t *)s.moff, segs, p.seg_slots, p.k, g,
+                           (const int64_t *)out.counts, out.capacity, out.pairs, out.byte, out.seeds, out.chains);
+        if ((rc = pmx_launched())) return rc;
+    }
+    return 0;
+}
+
 // The slice's `rows` rows (what the cut kept) with their m matches: emit, sort, clusters, outputs behind counts[0], then the slice's
 // row offsets and the running counts.  The geometry chooses the instantiation here and nowhere else; DNA is FRAMES with rows as they
 // stand, bit for bit.
@@ -951,7 +1157,9 @@ int pmx_launch_seed_cluster(const PmxSeedPlan &p, const PmxSeedSlice &s, const P
 {
     const long long segs = rows * p.segs, total = rows * p.row_slots;
     int rc = 0;
-    if (m > 0) {
+    if (m > 0 && p.chain) {
+        if ((rc = pmx_seed_chain_slice(p, s, out, src, row0, m, segs, total, stream))) return rc;
+    } else if (m > 0) {
         decltype(&pmx_seed_emit_kernel<PMX_SEED_GEOM_FRAMES>) emit = nullptr;
         decltype(&pmx_seed_hits_kernel<PMX_SEED_GEOM_FRAMES>) hits = nullptr;
         switch (p.geom) {
@@ -963,7 +1171,7 @@ int pmx_launch_seed_cluster(const PmxSeedPlan &p, const PmxSeedSlice &s, const P
         default: return -1;
         }
         hipLaunchKernelGGL(emit, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, p.max_qlen, p.ref_count, (const uint32_t *)s.lo,
-                           (const uint32_t *)s.cnt, (const int64_t *)s.moff, src.vals, s.keys_a);
+                           (const uint32_t *)s.cnt, (const int64_t *)s.moff, src.vals, s.keys_a, (uint32_t *)nullptr);
         if ((rc = pmx_launched())) return rc;
         if ((rc = pmx_seed_sort_clusters(p, s, m, segs, stream))) return rc;
         if (out.capacity > 0) {
